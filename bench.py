@@ -16,11 +16,15 @@ fixed); with N > 1 the job ends with ONE gather of all steps' result records to 
 Every step runs a DIFFERENT resident batch (--batches, default 3, all uploaded before the timed region), so the
 column-segment overlap a step is cut with was adapted to another batch's scores, never to its own.
 
+A plain run sets up, warms up, times the steps and prints the line (`--dump-outputs DIR`: the rows of the last timed step as
+DIR/<field>.npy).  `--full` adds what the headline figure does not need: the spot check against the CPU oracle, the
+PCIe-inclusive leg, the A/B legs and the CPU baseline.
+
 Rank 0 prints one JSON line.  `roofline` names what binds the dominant kernel (the forward flank DP):
 VALU issue -- wave instructions per second against 1024 SIMDs x 2.4 GHz / 2, with the instruction count
 per wave-step taken from the committed SQ_INSTS_VALU profile (profiles/dp_constants.json) and the
 wave-steps counted by the library in this run; the SURVEY.md 8d algorithmic-bytes figure is kept under
-`roofline.hbm_algorithmic`.  `host_inclusive_reads_per_s` is the same pipeline with the signals starting
+`roofline.hbm_algorithmic`.  With --full, `host_inclusive_reads_per_s` is the same pipeline with the signals starting
 in pageable host RAM.  `cpu_baseline` times the CPU oracle (the reference's own arithmetic: full matrix,
 one double pow per cell) on the host cores on a bounded sample.
 """
@@ -79,23 +83,31 @@ def _synth_chunk(args):
     return make_batch(pm, cfg, count, read_nt, first, workload=workload)
 
 
-def make_batches_parallel(n_reads, read_nt, first_index, workers, workload="clean"):
-    """The same reads as make_batch(..., first_index), synthesised by a few worker processes (a 50 kb read takes
-    ~7 ms of numpy; 3 x 4096 of them would otherwise dominate the run)."""
-    import multiprocessing as mp
+def _synth_jobs(n_reads, read_nt, first_index, workers, workload):
+    """The worker jobs of make_batches_parallel: contiguous ranges of read indices (make_batch derives every read, its seed and
+    its repeat count from its own index, so the chunking does not change a read)."""
     workers = max(1, min(workers, n_reads // 64 or 1))
-    if workers == 1:
-        pm, cfg = load_inputs()
-        return make_batch(pm, cfg, n_reads, read_nt, first_index, workload=workload)
     per = (n_reads + workers - 1) // workers
-    # chunks start at multiples of len(REPEAT_SWEEP) offsets of first_index: make_batch derives the repeat count from the index
-    jobs = [(first_index + k * per, min(per, n_reads - k * per), read_nt, workload) for k in range(workers) if k * per < n_reads]
-    with mp.get_context("spawn").Pool(len(jobs)) as pool:
-        parts = pool.map(_synth_chunk, jobs)
+    return [(first_index + k * per, min(per, n_reads - k * per), read_nt, workload) for k in range(workers) if k * per < n_reads]
+
+
+def _join_parts(parts):
     sigs, strands, nreps = [], [], []
     for a, b, c in parts:
         sigs += a; strands += b; nreps += c
     return sigs, strands, nreps
+
+
+def make_batches_parallel(n_reads, read_nt, first_index, workers, workload="clean"):
+    """The same reads as make_batch(..., first_index), synthesised by a few worker processes (a 50 kb read takes
+    ~7 ms of numpy; 3 x 4096 of them would otherwise dominate the run)."""
+    import multiprocessing as mp
+    jobs = _synth_jobs(n_reads, read_nt, first_index, workers, workload)
+    if len(jobs) == 1:
+        pm, cfg = load_inputs()
+        return make_batch(pm, cfg, n_reads, read_nt, first_index, workload=workload)
+    with mp.get_context("spawn").Pool(len(jobs)) as pool:
+        return _join_parts(pool.map(_synth_chunk, jobs))
 
 
 def _oracle_side(strand):
@@ -313,16 +325,26 @@ def launch_ranks(args, argv):
 
 def stage_resident(ctx, counter, args, first_read, n_batches, workers, workload, keep_first, keep_all):
     """The resident batches of one rank, one at a time: synthesise -> upload (strq_batch_upload_part, 512 reads per call) -> free,
-    so that a rank's peak host footprint is about one batch, not all of them plus a concatenated copy.  Returns the lengths,
+    so that a rank's peak host footprint is about two batches (the next one is synthesised during an upload), not all of them plus a concatenated copy.  Returns the lengths,
     strands and planted counts of all reads and the signals worth keeping on the host: the first `keep_first` of every batch
     (spot check, CPU baseline) or all of them (`keep_all`: the PCIe-inclusive leg at N = 1)."""
+    import multiprocessing as mp
     total = n_batches * args.reads
     est = int(total * args.read_nt * (9.6 if workload == "empirical" else 7.6))
     lens, strands_all, nreps_all, kept = [], [], [], {}
     t_gen = t_up = 0.0
+    # one pool of synthesis workers for all batches; batch b + 1 is synthesised while batch b uploads
+    jobs = [_synth_jobs(args.reads, args.read_nt, first_read + b * args.reads, workers, workload) for b in range(n_batches)]
+    pool = mp.get_context("spawn").Pool(max(len(j) for j in jobs)) if max(len(j) for j in jobs) > 1 else None
+    pending = pool.map_async(_synth_chunk, jobs[0]) if pool is not None else None
     for b in range(n_batches):
         t0 = time.time()
-        sigs, strands, nreps = make_batches_parallel(args.reads, args.read_nt, first_read + b * args.reads, workers, workload)
+        if pool is not None:
+            sigs, strands, nreps = _join_parts(pending.get())
+            if b + 1 < n_batches:
+                pending = pool.map_async(_synth_chunk, jobs[b + 1])
+        else:
+            sigs, strands, nreps = make_batches_parallel(args.reads, args.read_nt, first_read + b * args.reads, workers, workload)
         t_gen += time.time() - t0
         tids = [counter._classifier_for("c9orf72", st).target_id for st in strands]
         t0 = time.time()
@@ -335,6 +357,8 @@ def stage_resident(ctx, counter, args, first_read, n_batches, workers, workload,
         for j in range(len(sigs) if keep_all else min(keep_first, len(sigs))):
             kept[b * args.reads + j] = sigs[j]
         del sigs
+    if pool is not None:
+        pool.close(); pool.join()
     return np.array(lens, np.int64), strands_all, nreps_all, kept, t_gen, t_up
 
 
@@ -716,7 +740,16 @@ def main():
     ap.add_argument("--total-reads", type=int, default=0, help="--scaling strong: reads of one step over all GPUs (BASELINE configs[3]: 100000)")
     ap.add_argument("--detail", default=None, help="where rank 0 writes the full record (default: gpurun_out/bench_detail.json); the line on stdout is the compact one")
     ap.add_argument("--share-device", action="store_true", help="testing only: all ranks use HIP device 0 (needs --backend gloo)")
+    ap.add_argument("--full", action="store_true", help="also run what the headline figure does not need: the spot check against the CPU oracle (--check), "
+                                                        "the PCIe-inclusive leg, the A/B legs and the CPU baseline (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write the rows of the last timed step (every field of the "
+                                                                        "result record, float64) as DIR/<field>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
+    if not args.full:
+        # a plain run: set-up, warm-up, the timed steps and the result line -- nothing else
+        args.check = 0; args.no_host_leg = True; args.no_legs = True; args.no_cpu_baseline = True
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args, sys.argv[1:]))
@@ -872,6 +905,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     main_leg.elapsed = elapsed
+    if rank == 0 and args.dump_outputs:
+        # the last timed step's rows: the gathered rows of every rank when the job gathered once, this rank's own otherwise
+        rows = table[(args.steps - 1) * world * args.reads:args.steps * world * args.reads] if table is not None else mine[-1][1]
+        dump_outputs(args.dump_outputs, rows)
     peak_rss_gb = resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1048576.0
 
     # ---- correctness spot check against the oracle (same arithmetic, memoised scores): all six fields of a row
@@ -941,9 +978,9 @@ def main():
                         "us_per_time_step_per_wave_slot": (float(stage_ms[6]) / args.steps * 1e3) / max(1.0, main_leg.counters[7] / args.steps / (8 * N_SIMD / 4))},
             "host": {"synth_s": t_gen, "synth_workers": synth_workers, "upload_s": t_up, "upload_GBs": int(lens.sum()) * 2 / t_up / 1e9 if t_up > 0 else None,
                      "peak_host_rss_gb_per_rank": round(peak_rss_gb, 3) if world == 1 else (rank_report or {}).get("peak_host_rss_gb_per_rank"),
-                     "peak_host_rss_note": "resident batches are staged one at a time (synthesise -> upload in 512-read parts -> free); at N = 1 the signals of the PCIe-inclusive leg stay on the host as well",
+                     "peak_host_rss_note": "resident batches are staged one at a time (synthesise -> upload in 512-read parts -> free), the next one synthesised during the upload; at N = 1 the signals of the PCIe-inclusive leg stay on the host as well",
                      "memory_limit_gb": mem_lim, "cpu_quota_cores": _sdq.cpu_quota()},
-            "check": checked, "check_ok": check_ok,
+            "check": checked, "check_ok": check_ok if args.check > 0 else None,
         }
         if want_host_leg:
             # SURVEY.md 8d quotes the metric with the signals in host RAM: the boundary's host-buffer entry
@@ -1045,6 +1082,13 @@ def main():
     if rank == 0 and not check_ok:
         sys.stderr.write("bench.py: GPU rows differ from the CPU oracle -- see \"check\" in the JSON line\n")
         raise SystemExit(1)
+
+
+def dump_outputs(path, rows):
+    """Every field of the result records `rows` as path/<field>.npy, float64 (the integer fields are exact in it)."""
+    os.makedirs(path, exist_ok=True)
+    for name in rows.dtype.names:
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(rows[name], dtype=np.float64))
 
 
 def _r(v, sig=6):

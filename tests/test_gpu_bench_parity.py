@@ -117,7 +117,7 @@ def test_bench_two_ranks_on_one_gpu():
     processes): two rank processes sharing HIP device 0, gloo for the gather -- rank 0 prints the one JSON line,
     the collective saw two ranks, both ranks' reads are in `value`, and the spot check compares whole rows."""
     lines, recs = _run_bench(["--gpus", "2", "--backend", "gloo", "--share-device", "--reads", "64", "--steps", "2", "--warmup", "1",
-                              "--no-cpu-baseline", "--check", "1", "--synth-workers", "2"], world=2)
+                              "--no-cpu-baseline", "--check", "1", "--synth-workers", "2", "--full"], world=2)
     assert len(lines[0]) == 1 and len(lines[1]) == 0          # exactly one line, from rank 0
     r = recs[0]
     assert r["n_gpus"] == 2 and r["world_size_seen_by_the_collective"] == 2 and r["scaling"] == "weak"
@@ -140,7 +140,7 @@ def test_bench_four_and_eight_ranks_on_one_gpu(world, tmp_path, pm, cfg):
     shared = world == 4
     mode = ["--reads", str(reads)] if shared else ["--scaling", "strong", "--total-reads", str(8 * reads - 6), "--private-reads"]
     lines, recs = _run_bench(["--gpus", str(world), "--backend", "gloo", "--share-device", "--steps", str(steps), "--warmup", str(warmup),
-                              "--read-nt", str(read_nt), "--no-cpu-baseline", "--check", "1", "--synth-workers", "1", "--dump-rows", dump] + mode,
+                              "--read-nt", str(read_nt), "--no-cpu-baseline", "--check", "1", "--synth-workers", "1", "--dump-rows", dump, "--full"] + mode,
                              world=world, port=str(29560 + world), timeout=1500)
     assert [len(l) for l in lines] == [1] + [0] * (world - 1)
     r = recs[0]
@@ -185,7 +185,7 @@ def test_bench_line_single_gpu_small(screen, monkeypatch):
     line's roofline is the screen kernel's and the float32 kernel's figures sit under `exact_pass`; without, as in round 3."""
     if not screen:
         monkeypatch.setenv("STRQ_NO_SCREEN", "1")
-    lines, recs = _run_bench(["--reads", "512", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--check", "2", "--host-leg-batches", "2", "--leg-steps", "2"]
+    lines, recs = _run_bench(["--reads", "512", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--check", "2", "--host-leg-batches", "2", "--leg-steps", "2", "--full"]
                              + ([] if screen else ["--no-legs"]))
     r = recs[0]
     roof = r["roofline"]
@@ -228,7 +228,7 @@ def test_bench_launches_its_own_ranks_from_a_clean_environment(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--share-device", "--backend", "gloo", "--reads", "64", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--check", "1", "--synth-workers", "1"]
+           "--no-cpu-baseline", "--check", "1", "--synth-workers", "1", "--full"]
     p = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]
@@ -253,9 +253,34 @@ def test_bench_gather_falls_back_to_gloo_when_rccl_refuses():
     """Two ranks on ONE device with `--backend nccl`: RCCL refuses ("Duplicate GPU detected") -- the job agrees on that over its gloo
     control plane, gathers over gloo, and says so in the line (`collective.backend`, `collective.nccl_error`) instead of dying."""
     lines, recs = _run_bench(["--gpus", "2", "--backend", "nccl", "--share-device", "--reads", "64", "--steps", "2", "--warmup", "1",
-                              "--no-cpu-baseline", "--check", "1", "--synth-workers", "2"], world=2, port="29547")
+                              "--no-cpu-baseline", "--check", "1", "--synth-workers", "2", "--full"], world=2, port="29547")
     assert len(lines[0]) == 1 and len(lines[1]) == 0
     r = recs[0]; coll = r["collective"]
     assert r["n_gpus"] == 2 and r["world_size_seen_by_the_collective"] == 2 and r["check_ok"]
     assert coll["backend"] == "gloo" and coll["backend_requested"] == "nccl" and coll["nccl_error"]
     assert coll["ranks"]["rows_equal_every_ranks_digest"] is True and coll["rows_on_rank_0"] == 2 * 2 * 64
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path, pm, cfg):
+    """A plain run (no --full) times its steps and prints the line -- no oracle check, no extra legs, no CPU baseline -- and
+    --dump-outputs writes the rows of its LAST timed step, field by field in float64; they equal what one process computes for
+    the same reads (warm-up 1 + steps 2: the last timed step is step 2, resident batch 2 of 3), and a second run writes the same."""
+    reads = 64
+    runs = []
+    for d in ("a", "b"):
+        out = str(tmp_path / d)
+        lines, recs = _run_bench(["--reads", str(reads), "--steps", "2", "--warmup", "1", "--synth-workers", "2", "--dump-outputs", out])
+        r = recs[0]
+        assert r["steps"] == 2 and r["check_ok"] is None and not r["check"]
+        assert "legs" not in r and "cpu_baseline" not in r and "host_inclusive_reads_per_s" not in r
+        runs.append({f: np.load(os.path.join(out, f + ".npy")) for f in ("count", "status", "score_prefix", "score_suffix", "log_p", "offset", "ticks")})
+    for f, v in runs[0].items():
+        assert v.dtype == np.float64 and v.shape == (reads,), f
+        assert np.array_equal(v, runs[1][f]), f
+    sigs, strands, _ = _bench_batch(pm, cfg, reads, 2 * reads)
+    counter = _fresh_counter(pm, cfg, {"c9orf72": tuple(cfg["repeat"]["c9orf72"][3:6])})
+    got = counter.detect_batch([("c9orf72", s, st) for s, st in zip(sigs, strands)])
+    counter.ctx.close()
+    d = runs[0]
+    for i, g in enumerate(got):
+        assert (g[0], g[1], g[2], g[3], g[4], g[5]) == (int(d["count"][i]), d["score_prefix"][i], d["score_suffix"][i], d["log_p"][i], int(d["offset"][i]), int(d["ticks"][i])), i
