@@ -195,6 +195,20 @@ int strq_target_set_mod(strq_ctx* ctx, int32_t target_id, int32_t mod_model_id, 
 /* Modification patterns of the last batch: pattern of read i is pool[off[i] .. off[i+1]) ('0'/'1'
  * per repeat unit, "-" when there is none).  pool may be NULL to query the total size in off[n]. */
 int strq_batch_fetch_mod(strq_ctx* ctx, char* pool, int64_t pool_cap, int64_t* off);
+/* Repeat-unit positions (flankedRepeatHMM.count_repeats' Viterbi path, STRique.py:374-378,433-441, which detect drops at :604):
+ * with on = 1, later run calls (strq_batch_run*, strq_detect_batch*) also report, for every read whose gate passed and whose
+ * flanked-model decode found a path, the raw-signal sample indices prefix_begin + t of the observations t of the window
+ * [prefix_begin, suffix_end) that the best path -- the one whose count and log_p the row reports -- emits from a counted state
+ * (repeatdummy1 / repeatdummy2): count - count_bias ascending positions, one per repeat unit.  Sub-batches still in flight keep
+ * the mode they were launched with (the call waits for them).  Default 0. */
+int strq_set_units(strq_ctx* ctx, int32_t on);
+/* Unit positions of the last batch: read i's are pool[off[i] .. off[i+1]); decoded[i] (nullable) = 1 when the read was decoded,
+ * 0 when not (gate failed, signal not normalised, no path: no positions, unlike a decoded read with none).  pool may be NULL to
+ * query the total in off[n].  STRQ_ERR_ARG when the last run call ran with unit positions off. */
+int strq_batch_fetch_units(strq_ctx* ctx, int64_t* pool, int64_t pool_cap, int64_t* off, int32_t* decoded);
+/* The unit pass of the last run call: out[0] = ms on the GPU (all its sub-batches), out[1] = largest workspace of unit records /
+ * back-pointers one piece of it used (bytes), out[2] = windows decoded, out[3] = positions. */
+int strq_last_units(strq_ctx* ctx, double* out4);
 int strq_detect_batch(strq_ctx* ctx, int64_t n_reads, const void* signals, int32_t dtype,
                       const int64_t* offsets, const int32_t* target_id, const double* host_stats,
                       strq_result* out);

@@ -21,6 +21,8 @@ from collections import defaultdict, deque
 import numpy as np
 
 HEADER = ['ID', 'target', 'strand', 'count', 'score_prefix', 'score_suffix', 'log_p', 'offset', 'ticks', 'mod']
+# `count --units FILE`: the raw-signal sample of every repeat unit on the decoded Viterbi path, one row per count row
+UNITS_HEADER = ['ID', 'target', 'strand', 'count', 'n_units', 'units']
 LEVELS = ['error', 'warning', 'info', 'debug']
 
 
@@ -223,6 +225,8 @@ def count(argv):
     parser.add_argument("--device", type=int, default=0, help="HIP device")
     parser.add_argument("--backend", default=None, choices=["nccl", "gloo"], help="torch.distributed backend when launched with torchrun (default: nccl = RCCL)")
     parser.add_argument("--share-device", action="store_true", help="testing: every rank uses --device instead of its LOCAL_RANK")
+    parser.add_argument("--units", default=None, metavar="FILE", help="Also write the repeat-unit positions (raw-signal sample of every repeat unit "
+                                                                        "on the decoded path) to FILE: one row per count row, columns " + " ".join(UNITS_HEADER))
     parser.add_argument("--strict", action="store_true", help="Exit with status 2 when any read could not be processed (the reference only logs such reads and exits 0)")
     args = parser.parse_args(argv)
     log = Log(args.log_level)
@@ -262,6 +266,7 @@ def count(argv):
     f5 = Fast5Index(args.f5Index)
     stream = open(args.algn) if args.algn else sys.stdin
     out = (open(args.out, 'w') if args.out else sys.stdout) if rank == 0 else None
+    units_out = open(args.units, 'w') if (args.units and rank == 0) else None
     readers = args.t
     if readers <= 0:
         # one process per GPU: every rank takes its share of the cores (LOCAL_WORLD_SIZE is set by torchrun) for its reader threads, at most
@@ -277,7 +282,8 @@ def count(argv):
     stats = {}
     fault = 0
     try:
-        rows = run_count(stream, loci, f5.get_raw, counter, log, args.batch, rank, world, out if world == 1 else None, readers=readers, stats=stats)
+        rows = run_count(stream, loci, f5.get_raw, counter, log, args.batch, rank, world, out if world == 1 else None, readers=readers, stats=stats,
+                         units=bool(args.units), units_out=units_out if world == 1 else None)
     except DeviceFault:
         if world == 1:
             raise SystemExit(3)
@@ -291,13 +297,19 @@ def count(argv):
                 log("Main: a rank reported a device error; no output written.", 'error')
             dist.destroy_process_group()
             raise SystemExit(3)
-        merged = gather_rows(rows, stats["items"], sdist)
+        merged = gather_rows(rows, stats["items"], sdist, units=bool(args.units))
+        if args.units:
+            merged, merged_units = merged
         if rank == 0:
             write_rows(out, merged)
+            if units_out is not None:
+                write_rows(units_out, merged_units, header=UNITS_HEADER)
         dist.barrier()
         dist.destroy_process_group()
     if args.out and out is not None:
         out.close()
+    if units_out is not None:
+        units_out.close()
     if stats.get("failed"):
         # like the reference (STRique.py:704-713): reads that fail are logged, the run itself succeeds
         log("Main: %d read(s) could not be processed (see warnings above)." % stats["failed"], 'error')
@@ -332,37 +344,67 @@ def format_row(qname, target, strand, res):
     return '\t'.join(str(x) for x in (qname, target, strand) + tuple(res))
 
 
-def gather_rows(rows, items, sdist):
+def format_units(qname, target, strand, n, positions):
+    """One row of the `count --units` file: positions joined by commas, '-' when there are none (or no decode)."""
+    pos = [] if positions is None else [int(x) for x in positions]
+    return '\t'.join([str(qname), str(target), str(strand), str(n), str(len(pos)), ','.join(str(x) for x in pos) if pos else '-'])
+
+
+def parse_units(stream):
+    """Rows of a `count --units` file: [(ID, target, strand, count, [positions])] in file order."""
+    out = []
+    for line in stream:
+        f = line.rstrip('\n').split('\t')
+        if not line.strip() or f[0] == UNITS_HEADER[0]:
+            continue
+        pos = [] if f[5] == '-' else [int(x) for x in f[5].split(',')]
+        if len(pos) != int(f[4]):
+            raise ValueError("units row of %s: %s positions, n_units = %s" % (f[0], len(pos), f[4]))
+        out.append((f[0], f[1], f[2], int(f[3]), pos))
+    return out
+
+
+def gather_rows(rows, items, sdist, units=False):
     """Rows of this rank -> fixed-size records + modification strings -> one gather -> on rank 0 the
     merged [(sequence number, TSV row)] in input order (None elsewhere).  `items`: every accepted
-    (qname, strand, target) of the input, which each rank derives from the same SAM file."""
+    (qname, strand, target) of the input, which each rank derives from the same SAM file.
+    units=True: every result is (row tuple, unit positions or None); the positions travel in the same blob as the
+    modification string ("mod<TAB>p,p,..."), and the return value is (rows, unit rows) -- (None, None) off rank 0."""
     rec = np.zeros(len(rows), ROW_DTYPE); mods = []; idx = np.zeros(len(rows), np.int64)
     for k, (seq, res) in enumerate(rows):
         idx[k] = seq
         if res is None:
             mods.append("")
             continue
+        pos = None
+        if units:
+            res, pos = res
         n, sp, ss, p, offset, ticks, mod = res
         rec[k] = (n, 1, sp, ss, float(p), offset, ticks)
-        mods.append(mod)
+        mods.append(mod + '\t' + (','.join(str(int(x)) for x in pos) if pos is not None and len(pos) else '-') if units else mod)
     full, full_mods = sdist.gather_results(rec, idx, len(items), mods)
     if full is None:
-        return None
-    merged = []
+        return (None, None) if units else None
+    merged = []; merged_units = []
     for seq, (qname, strand, target) in enumerate(items):
         r = full[seq]
         if not r["valid"]:
             continue
         n = int(r["count"]); lp = float(r["log_p"])
         p = lp if (n or lp != 0) else 0              # the reference prints the integer 0 for a failed gate (STRique.py:602,616)
+        mod = full_mods[seq]
+        if units:
+            mod, ustr = mod.split('\t', 1)
+            merged_units.append((seq, format_units(qname, target, strand, n, [] if ustr == '-' else ustr.split(','))))
         merged.append((seq, format_row(qname, target, strand, (n, float(r["score_prefix"]), float(r["score_suffix"]), p,
-                                                                 int(r["offset"]), int(r["ticks"]), full_mods[seq]))))
-    return merged
+                                                                 int(r["offset"]), int(r["ticks"]), mod))))
+    return (merged, merged_units) if units else merged
 
 
 def write_rows(out, rows, header=True):
+    """header: True = the count header, a list = that header, False = none."""
     if header:
-        print('\t'.join(HEADER), file=out)
+        print('\t'.join(HEADER if header is True else header), file=out)
     for _, row in rows:
         print(row, file=out)
     out.flush()
@@ -382,7 +424,7 @@ def route(stream, loci, log):
         yield sr.QNAME, ('+' if sr.FLAG & 0x10 == 0 else '-'), targets, sr.QLEN
 
 
-def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, out=None, readers=0, stats=None):
+def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, out=None, readers=0, stats=None, units=False, units_out=None):
     """Route the SAM records of `stream` to their targets, run this rank's share through
     `counter.detect_batch` and return [(sequence number, result tuple or TSV row)].
 
@@ -393,13 +435,19 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
     return value is [(seq, result tuple)] for `gather_rows`.
     `readers` > 0: raw signals are fetched by that many threads ahead of the GPU batches (inflating
     the deflate chunks of a fast5 releases the GIL and is what bounds a `count` run on real files);
-    the order of the rows does not change."""
+    the order of the rows does not change.
+    `units`: the results also carry the repeat-unit positions (counter.detect_batch(..., units=True)); single process:
+    their rows (format_units) go to `units_out` with the count rows and to stats["unit_rows"]; several ranks: the
+    results are (row tuple, positions) pairs for `gather_rows(..., units=True)`."""
     from .ffi import StriqueHipError, STRQ_ERR_ARG, STRQ_ERR_UNSUPPORTED
     if stats is None:
         stats = {}
     stats.setdefault("failed", 0)
     if out is not None:
         print('\t'.join(HEADER), file=out)
+    if units_out is not None:
+        print('\t'.join(UNITS_HEADER), file=units_out)
+    stats.setdefault("unit_rows", [])
     rows = []
     records = route(stream, loci, log)
     mine_set = None
@@ -424,7 +472,10 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
         if faulted.is_set():                                      # queued behind the batch that faulted: the device is not touched again
             raise DeviceFault("not run: the device failed in an earlier batch")
         try:
-            results = counter.detect_batch([(t, raw, s) for _, _, t, s, raw in batch])
+            if units:
+                results = counter.detect_batch([(t, raw, s) for _, _, t, s, raw in batch], units=True)
+            else:
+                results = counter.detect_batch([(t, raw, s) for _, _, t, s, raw in batch])
         except StriqueHipError as e:
             if e.code not in (STRQ_ERR_ARG, STRQ_ERR_UNSUPPORTED):
                 # a device fault or an out-of-memory condition will not go away read by read
@@ -438,7 +489,7 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
             results = []
             for _, _, t, s, raw in batch:
                 try:
-                    results.append(counter.detect(t, raw, s))
+                    results.append(counter.detect(t, raw, s, units=True) if units else counter.detect(t, raw, s))
                 except StriqueHipError as e1:
                     if e1.code not in (STRQ_ERR_ARG, STRQ_ERR_UNSUPPORTED):
                         faulted.set()
@@ -447,13 +498,16 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
                     log("Detector: read failed: %s" % e1, 'warning'); results.append(None); failed += 1
                 except Exception as e1:
                     log("Detector: read failed: %s" % e1, 'warning'); results.append(None); failed += 1
-        done = []
+        done = []; udone = []
         for (seq, qname, target, strand, _), res in zip(batch, results):
             if world > 1:
                 done.append((seq, res))
             elif res is not None:
+                if units:
+                    res, pos = res
+                    udone.append((seq, format_units(qname, target, strand, res[0], pos)))
                 done.append((seq, format_row(qname, target, strand, res)))
-        return done, failed
+        return (done, udone), failed
 
     # The batches run on an engine thread, one at a time and in order, while this thread routes the next SAM records and
     # collects their signals: the GPU call of batch k overlaps the host-side preparation of batch k + 1 (at 50 kb per read
@@ -464,11 +518,14 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
 
     def collect(keep):
         while len(in_flight) > keep:
-            done, failed = in_flight.popleft().result()          # re-raises DeviceFault from the engine thread
+            (done, udone), failed = in_flight.popleft().result()          # re-raises DeviceFault from the engine thread
             stats["failed"] += failed
             rows.extend(done)
+            stats["unit_rows"].extend(udone)
             if out is not None:
                 write_rows(out, done, header=False)
+            if units_out is not None:
+                write_rows(units_out, udone, header=False)
 
     def flush(batch):
         if not batch:
@@ -600,6 +657,7 @@ def plot(argv):
     parser.add_argument("--dpi", default=80, type=int, help="Resolution of plot")
     parser.add_argument("--extension", type=float, default=0.1, help="Extension as fraction of repeat signal around STR region to plot")
     parser.add_argument("--zoom", type=int, default=500, help="Region around prefix and suffix to plot")
+    parser.add_argument("--units", default=None, metavar="FILE", help="Repeat-unit positions from `count --units`: marked in the panels")
     parser.add_argument("--log_level", default='warning', choices=LEVELS, help="Log level")
     args = parser.parse_args(argv)
     log = Log(args.log_level)
@@ -612,6 +670,10 @@ def plot(argv):
         os.makedirs(args.output, exist_ok=True)
     from matplotlib.figure import Figure
     reads = Fast5Index(args.f5Index)
+    unit_pos = None
+    if args.units:
+        with open(args.units) as f:
+            unit_pos = {(r[0], r[1], r[2]): r[4] for r in parse_units(f)}
     made = []
     with (open(args.counts) if args.counts else sys.stdin) as stream:
         for row in plotting.parse_counts(stream):
@@ -623,7 +685,11 @@ def plot(argv):
             else:
                 import matplotlib.pyplot as plt
                 fig = plt.figure(figsize=(args.width, args.height), dpi=args.dpi, layout="constrained")
-            plotting.draw(fig, raw, row, extension=args.extension, zoom=args.zoom)
+            if unit_pos is None:
+                plotting.draw(fig, raw, row, extension=args.extension, zoom=args.zoom)
+            else:
+                plotting.draw(fig, raw, row, extension=args.extension, zoom=args.zoom,
+                              units=unit_pos.get((row.read_id, row.target, row.strand), []))
             if args.output:
                 path = os.path.join(args.output, plotting.figure_name(row, args.format))
                 fig.savefig(path); made.append(path)

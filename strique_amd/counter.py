@@ -88,9 +88,11 @@ class repeatCounter(object):
         raise ValueError("RepeatCounter: Strand must be + or -.")
 
     # -------------------------------------------------------------------------------------
-    def detect_batch(self, items):
+    def detect_batch(self, items, units=False):
         """items: iterable of (target_name, raw_signal, strand).  Returns a list of the tuples
-        detect() returns, in input order."""
+        detect() returns, in input order.  units=True: a list of (tuple, positions) instead, positions being the
+        raw-signal sample indices of the repeat units on the decoded Viterbi path (one np.int64 array per read, ascending;
+        None when the read was not decoded -- gate failed, no path; strq_set_units)."""
         items = list(items)
         if not items:
             return []
@@ -111,13 +113,22 @@ class repeatCounter(object):
             if not idx:
                 continue
             arrs = [sigs[i].astype(np.int16 if want_int else np.float64, copy=False) for i in idx]
-            res = self.ctx.detect_batch_reads(arrs, [tcs[i].target_id for i in idx])      # one pointer per read: no host-side concatenation
-            mods = self.ctx.batch_fetch_mod() if self.pm is not self.pm_mod else ['-'] * len(res)
-            for i, r, m in zip(idx, res, mods):
+            if units:
+                self.ctx.set_units(True)
+            try:
+                res = self.ctx.detect_batch_reads(arrs, [tcs[i].target_id for i in idx])      # one pointer per read: no host-side concatenation
+                mods = self.ctx.batch_fetch_mod() if self.pm is not self.pm_mod else ['-'] * len(res)
+                pos = self.ctx.batch_fetch_units() if units else [None] * len(res)
+            finally:
+                if units:
+                    self.ctx.set_units(False)
+            for i, r, m, u in zip(idx, res, mods, pos):
                 n = int(r['count']); p = float(r['log_p']) if n or r['log_p'] != 0 else 0
-                out[i] = (n, float(r['score_prefix']), float(r['score_suffix']), p, int(r['offset']), int(r['ticks']), m)
+                row = (n, float(r['score_prefix']), float(r['score_suffix']), p, int(r['offset']), int(r['ticks']), m)
+                out[i] = (row, u) if units else row
         return out
 
-    def detect(self, target_name, raw_signal, strand):
-        """(n, score_prefix, score_suffix, log_p, offset, ticks, mod_pattern) -- STRique.py:581-618."""
-        return self.detect_batch([(target_name, raw_signal, strand)])[0]
+    def detect(self, target_name, raw_signal, strand, units=False):
+        """(n, score_prefix, score_suffix, log_p, offset, ticks, mod_pattern) -- STRique.py:581-618.  units=True:
+        (that tuple, unit positions or None) -- see detect_batch."""
+        return self.detect_batch([(target_name, raw_signal, strand)], units=units)[0]

@@ -19,6 +19,7 @@
 #include "cond_kernels.h"
 #include "viterbi_kernels.h"
 #include "mod_kernels.h"
+#include "unit_kernels.h"
 
 using namespace strq;
 
@@ -128,6 +129,10 @@ struct Batch {
     int64_t uploaded = 0;                // reads whose samples are in `raw`
     std::vector<strq_result> results;
     std::vector<std::string> mod;        // modification pattern per read ('-' if none)
+    bool units_ran = false;              // the last run call decoded unit positions (strq_set_units)
+    std::vector<std::vector<int64_t>> units;      // unit positions per read (strq_batch_fetch_units)
+    std::vector<uint8_t> unit_dec;       // 1: the read was decoded (gate passed, the flanked model found a path)
+    void reset_units(int64_t n) { units.assign((size_t)n, std::vector<int64_t>()); unit_dec.assign((size_t)n, 0); units_ran = false; }
     float t_cond = 0, t_lut = 0, t_fwd = 0, t_trace = 0, t_vit = 0, t_total = 0;
     double n_hard = 0;
     int n_fwd_launches = 0;
@@ -139,6 +144,9 @@ struct DetectState {
     std::vector<Target> targets;
     Batch batch;
     DevBuf rc, hist16, hist8, geom, idx, hist_raw, bp, path, modtask, modsig, modlen, pattern, hrange, modpool, f64s;
+    DevBuf unit_task, unit_ws, unit_path, unit_pool;      // unit pass (run_unit_pass): tasks, records / back-pointers, state paths, positions
+    bool units_on = false;               // strq_set_units
+    float unit_ms = 0; double unit_bytes = 0, unit_reads = 0, unit_positions = 0;      // strq_last_units: the last run call's unit pass
     hipEvent_t ev[4] = {};
     bool ev_ok = false;
     int64_t part_reads = 0;              // strq_batch_upload_part: reads uploaded so far
@@ -153,6 +161,7 @@ struct DetectState {
         struct VL { int shape, first, count, max_states; };
         std::vector<VL> vls;             // the Viterbi launches of the sub-batch: kernel shape, task range
         int vit_mode = 0;                // 0 count, 2 MARK (modification pass follows)
+        bool units = false;              // the unit pass follows (strq_set_units when the sub-batch was launched)
         int64_t r0 = 0; int nr = 0;
         std::vector<int32_t> vit_slot;
         void* pinned = nullptr; size_t pinned_cap = 0;      // ReadGeom[nr], VitResult[nr], ReadCond[nr], unsigned redo
@@ -187,7 +196,8 @@ void detect_state_free(strq_ctx* c)
     (void)upload_join(d);
     if (d->vit_stream) (void)hipStreamSynchronize(d->vit_stream);
     for (DevBuf* b : {&d->batch.raw, &d->rc, &d->hist16, &d->hist8, &d->geom, &d->idx,
-                      &d->hist_raw, &d->bp, &d->path, &d->modtask, &d->modsig, &d->modlen, &d->pattern, &d->hrange, &d->modpool, &d->f64s}) b->release();
+                      &d->hist_raw, &d->bp, &d->path, &d->modtask, &d->modsig, &d->modlen, &d->pattern, &d->hrange, &d->modpool, &d->f64s,
+                      &d->unit_task, &d->unit_ws, &d->unit_path, &d->unit_pool}) b->release();
     for (auto& sl : d->slot) {
         for (DevBuf* b : {&sl.flt, &sl.vit, &sl.vres, &sl.order, &sl.vq}) b->release();
         if (sl.pinned) (void)hipHostFree(sl.pinned);
@@ -345,6 +355,128 @@ static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, int6
     if (dense) STRQ_HIP(c, hipMemcpyAsync(chars.data(), d_dense, dense, hipMemcpyDeviceToHost, st));
     STRQ_HIP(c, hipStreamSynchronize(st));
     for (int k = 0; k < nm; ++k) B.mod[r0 + who[k]] = std::string(chars.data() + gt[k].dst, (size_t)gt[k].len);
+    return STRQ_OK;
+}
+
+// Unit positions of the reads of one sub-batch (strq_set_units; repeatHMM.count_repeats' path, STRique.py:374-378,433-441): the
+// windows the count / MARK launch decoded, once more with the same tasks (same windows, same affine source) -- in UNIT mode (unit
+// records, VIT_UNIT_T_MAX) where the model and the window allow it, else (STRQ_UNITS_BACKPOINTERS=1: always) with back-pointers and a
+// traceback.  Runs on the context's stream when the rows of the sub-batch are taken: the slot's filtered signal and tasks are live
+// until the slot is used again, which harvests it first.  Pieces of at most STRQ_UNITS_WS_BYTES (8 GiB) of records / back-pointers.
+static int run_unit_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, int64_t r0, int nr, const ReadGeom* geom, const VitResult* vres)
+{
+    Batch& B = d->batch;
+    hipStream_t st = c->stream;
+    std::vector<int> who;                      // reads with a decode: gate passed, the flanked model found a path
+    for (int i = 0; i < nr; ++i) {
+        B.units[(size_t)(r0 + i)].clear(); B.unit_dec[(size_t)(r0 + i)] = 0;
+        if (geom[i].gate && vres[sl.vit_slot[i]].status == 0) who.push_back(i);
+    }
+    if (who.empty()) return STRQ_OK;
+    STRQ_HIP(c, hipEventRecord(d->ev[2], st));
+    std::vector<VitTask> vt((size_t)nr);
+    STRQ_HIP(c, hipMemcpyAsync(vt.data(), sl.vit.p, (size_t)nr * sizeof(VitTask), hipMemcpyDeviceToHost, st));
+    STRQ_HIP(c, hipStreamSynchronize(st));
+    const bool force_bp = strq::opt("STRQ_UNITS_BACKPOINTERS") != nullptr;
+    size_t budget = (size_t)8 << 30;
+    if (const char* e = strq::opt("STRQ_UNITS_WS_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
+    struct W { int i; int shape; bool rec; size_t bytes; };
+    std::vector<W> ws;
+    for (int i : who) {
+        HostModel* hm = c->models[d->targets[B.target[r0 + i]].model_id];
+        const int64_t T = vt[(size_t)sl.vit_slot[i]].T;
+        W w; w.i = i; w.shape = vit_shape_for(hm->h, 4);
+        w.rec = !force_bp && vit_unit_ok(hm->h, w.shape) && T < VIT_UNIT_T_MAX;
+        if (!w.rec) w.shape = vit_shape_of(hm->h);
+        if (w.shape < 0) { c->err = "unit pass: model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
+        // unit records: two uint32 per observation; back-pointers: uint16 per (time step, state), and the state path
+        w.bytes = w.rec ? (size_t)T * 8 : (size_t)(T + 1) * (size_t)hm->h.n_states * 2;
+        ws.push_back(w);
+    }
+    for (size_t c0 = 0; c0 < ws.size();) {
+        size_t c1 = c0, bytes = 0;
+        while (c1 < ws.size() && (c1 == c0 || bytes + ws[c1].bytes <= budget)) bytes += ws[c1++].bytes;
+        // this piece's windows grouped by (route, kernel shape): unit-record launches first
+        std::map<std::pair<int, int>, std::vector<int>> groups;
+        for (size_t k = c0; k < c1; ++k) groups[{ws[k].rec ? 0 : 1, ws[k].shape}].push_back((int)k);
+        const int m = (int)(c1 - c0);
+        STRQ_HIP(c, d->unit_task.reserve((size_t)m * (sizeof(VitTask) + sizeof(VitResult) + 8 + sizeof(UnitTask) + 4) + 256));
+        VitTask* d_vt = d->unit_task.as<VitTask>();
+        VitResult* d_vr = reinterpret_cast<VitResult*>(d_vt + m);
+        int32_t** d_paths = reinterpret_cast<int32_t**>(d_vr + m);
+        UnitTask* d_ut = reinterpret_cast<UnitTask*>(d_paths + m);
+        int32_t* d_bad = reinterpret_cast<int32_t*>(d_ut + m);
+        size_t path_n = 0, pos_n = 0;
+        for (size_t k = c0; k < c1; ++k) {
+            if (!ws[k].rec) path_n += (size_t)vt[(size_t)sl.vit_slot[ws[k].i]].T;
+            pos_n += (size_t)vres[sl.vit_slot[ws[k].i]].counted;
+        }
+        STRQ_HIP(c, d->unit_ws.reserve(bytes + (size_t)m * 16 + 64));
+        if (path_n) STRQ_HIP(c, d->unit_path.reserve(path_n * 4 + 64));
+        STRQ_HIP(c, d->unit_pool.reserve(pos_n * 8 + 64));
+        std::vector<VitTask> tv((size_t)m); std::vector<int32_t*> pv((size_t)m, nullptr); std::vector<UnitTask> uv((size_t)m);
+        std::vector<int> read_of((size_t)m); std::vector<size_t> pos_off((size_t)m);
+        struct L { int shape, want, first, count, mx; };
+        std::vector<L> launches;
+        size_t wo = 0, po = 0, xo = 0; int at = 0, n_rec = 0;
+        for (auto& g : groups) {
+            const int first = at; int mx = 0;
+            for (int k : g.second) {
+                const W& w = ws[(size_t)k];
+                HostModel* hm = c->models[d->targets[B.target[r0 + w.i]].model_id];
+                const VitResult& v0 = vres[sl.vit_slot[w.i]];
+                VitTask t = vt[(size_t)sl.vit_slot[w.i]];
+                t.bp = reinterpret_cast<uint16_t*>(d->unit_ws.as<char>() + wo); wo += (w.bytes + 15) & ~(size_t)15;
+                if (wo > d->unit_ws.cap) { c->err = "unit pass: workspace"; return STRQ_ERR_NOMEM; }
+                UnitTask u; std::memset(&u, 0, sizeof(u));
+                u.rec = w.rec ? reinterpret_cast<const uint32_t*>(t.bp) : nullptr;
+                if (!w.rec) { pv[(size_t)at] = d->unit_path.as<int32_t>() + po; u.path = pv[(size_t)at]; u.count_inc = hm->h.count_inc; po += (size_t)t.T; }
+                u.result = d_vr + at; u.out = d->unit_pool.as<int64_t>() + xo; u.T = t.T; u.base = geom[w.i].prefix_begin; u.n = v0.counted; u.bad = d_bad + at;
+                pos_off[(size_t)at] = xo; xo += (size_t)v0.counted;
+                tv[(size_t)at] = t; uv[(size_t)at] = u; read_of[(size_t)at] = w.i;
+                mx = std::max(mx, hm->h.n_cells); ++at; n_rec += w.rec ? 1 : 0;
+            }
+            launches.push_back({g.first.second, g.first.first == 0 ? 4 : 1, first, at - first, mx});
+        }
+        STRQ_HIP(c, hipMemcpyAsync(d_vt, tv.data(), (size_t)m * sizeof(VitTask), hipMemcpyHostToDevice, st));
+        STRQ_HIP(c, hipMemcpyAsync(d_paths, pv.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
+        STRQ_HIP(c, hipMemcpyAsync(d_ut, uv.data(), (size_t)m * sizeof(UnitTask), hipMemcpyHostToDevice, st));
+        STRQ_HIP(c, hipMemsetAsync(d_bad, 0, (size_t)m * 4, st));
+        if (path_n) STRQ_HIP(c, hipMemsetAsync(d->unit_path.p, 0, path_n * 4, st));      // a traceback that stops early leaves valid states behind
+        STRQ_HIP(c, c->queue.reserve(1024));
+        STRQ_HIP(c, hipMemsetAsync(c->queue.p, 0, 1024, st));
+        int qi = 0;
+        for (const L& l : launches) {
+            int* d_order = nullptr;
+            if (l.count <= 8192) {
+                d_order = sl.order.as<int>() + l.first;
+                if (launch_vit_sort(st, d_vt + l.first, l.count, d_order)) { c->err = "sort launch failed"; return STRQ_ERR_DEVICE; }
+            }
+            const int vrc = launch_viterbi(st, l.shape, l.mx, d_vt + l.first, d_vr + l.first, l.count, c->queue.as<int>() + qi++, c->n_cu, l.want, d_order);
+            if (vrc) {
+                c->err = (vrc == 2 || vrc == 3) ? "unit pass: decode mode not available for this model's kernel shape" : "viterbi launch failed";
+                return (vrc == 2 || vrc == 3) ? STRQ_ERR_UNSUPPORTED : STRQ_ERR_DEVICE;
+            }
+            if (l.want == 1 && launch_vit_traceback(st, d_vt + l.first, d_vr + l.first, d_paths + l.first, l.count)) { c->err = "traceback launch failed"; return STRQ_ERR_DEVICE; }
+        }
+        if (launch_unit_hop(st, d_ut, n_rec) || launch_unit_scan(st, d_ut + n_rec, m - n_rec)) { c->err = "unit position launch failed"; return STRQ_ERR_DEVICE; }
+        std::vector<int64_t> pos(xo + 1); std::vector<int32_t> bad((size_t)m);
+        if (xo) STRQ_HIP(c, hipMemcpyAsync(pos.data(), d->unit_pool.p, xo * 8, hipMemcpyDeviceToHost, st));
+        STRQ_HIP(c, hipMemcpyAsync(bad.data(), d_bad, (size_t)m * 4, hipMemcpyDeviceToHost, st));
+        STRQ_HIP(c, hipStreamSynchronize(st));
+        for (int k = 0; k < m; ++k) {
+            if (bad[(size_t)k]) { c->err = "unit pass: the unit decode of a window disagrees with its count decode"; return STRQ_ERR_DEVICE; }
+            const int i = read_of[(size_t)k];
+            const int64_t n = vres[sl.vit_slot[i]].counted;
+            B.units[(size_t)(r0 + i)].assign(pos.begin() + (ptrdiff_t)pos_off[(size_t)k], pos.begin() + (ptrdiff_t)(pos_off[(size_t)k] + (size_t)n));
+            B.unit_dec[(size_t)(r0 + i)] = 1;
+        }
+        d->unit_bytes = std::max(d->unit_bytes, (double)bytes); d->unit_reads += m; d->unit_positions += (double)xo;
+        c0 = c1;
+    }
+    STRQ_HIP(c, hipEventRecord(d->ev[3], st));
+    STRQ_HIP(c, hipEventSynchronize(d->ev[3]));
+    float ms = 0; STRQ_HIP(c, hipEventElapsedTime(&ms, d->ev[2], d->ev[3])); d->unit_ms += ms;
     return STRQ_OK;
 }
 
@@ -523,7 +655,9 @@ static int harvest(strq_ctx* c, DetectState* d, DetectState::Slot& sl, bool unde
         c->overlap[3] += 1;
     }
     publish_timing(c, B);
-    if (any_mod) return run_mod_pass(c, d, sl, r0, nr, rc_out, geom, vres, sl.vit_slot);
+    if (any_mod) { const int mrc = run_mod_pass(c, d, sl, r0, nr, rc_out, geom, vres, sl.vit_slot); if (mrc) return mrc; }
+    if (sl.units) return run_unit_pass(c, d, sl, r0, nr, geom, vres);
+    for (int i = 0; i < nr; ++i) { B.units[(size_t)(r0 + i)].clear(); B.unit_dec[(size_t)(r0 + i)] = 0; }
     return STRQ_OK;
 }
 
@@ -766,6 +900,7 @@ static int run_sub_batch(strq_ctx* c, DetectState* d, int64_t r0, int64_t r1, in
     if (c->redo_total.p) STRQ_HIP(c, hipMemcpyAsync(h_redo, c->redo_total.p, 4, hipMemcpyDeviceToHost, st));
     STRQ_HIP(c, hipEventRecord(sl.fwd_done, st));
     sl.vit_mode = any_mod ? 2 : 0;
+    sl.units = d->units_on;
     sl.active = true; sl.launch_pending = true; sl.r0 = r0; sl.nr = nr;
     // The Viterbi launches of this sub-batch: now on the context's stream (serial order), or -- two sub-batches in flight -- behind the
     // conditioning of the NEXT sub-batch (launch_viterbi_of from there), at the latest when somebody asks for the rows.  Conditioning is a
@@ -860,6 +995,51 @@ int strq_batch_fetch_mod(strq_ctx* c, char* pool, int64_t pool_cap, int64_t* off
     return STRQ_OK;
 }
 
+int strq_set_units(strq_ctx* c, int32_t on)
+{
+    if (!c) return STRQ_ERR_ARG;
+    strq::CtxScope scope_(c);
+    if (on != 0 && on != 1) { c->err = "bad argument (strq_set_units takes 0 or 1)"; return STRQ_ERR_ARG; }
+    DetectState* d = dstate(c);
+    STRQ_HIP(c, hipSetDevice(c->device));
+    // sub-batches in flight keep the mode they were launched with: their unit pass (or none) runs now
+    { const int rc = drain(c, d); if (rc) return rc; }
+    d->units_on = on != 0;
+    return STRQ_OK;
+}
+
+int strq_batch_fetch_units(strq_ctx* c, int64_t* pool, int64_t pool_cap, int64_t* off, int32_t* decoded)
+{
+    if (!c || !off) return STRQ_ERR_ARG;
+    strq::CtxScope scope_(c);
+    DetectState* d = dstate(c);
+    STRQ_HIP(c, hipSetDevice(c->device));
+    { const int rc = drain(c, d); if (rc) return rc; }
+    const Batch& B = d->batch;
+    if (!B.units_ran) { c->err = "the last batch ran without unit positions (strq_set_units)"; return STRQ_ERR_ARG; }
+    int64_t pos = 0;
+    for (size_t i = 0; i < B.units.size(); ++i) {
+        off[i] = pos;
+        const std::vector<int64_t>& u = B.units[i];
+        if (pool) {
+            if (pos + (int64_t)u.size() > pool_cap) { c->err = "unit pool too small"; return STRQ_ERR_ARG; }
+            if (!u.empty()) std::memcpy(pool + pos, u.data(), u.size() * 8);
+        }
+        if (decoded) decoded[i] = B.unit_dec[i];
+        pos += (int64_t)u.size();
+    }
+    off[B.units.size()] = pos;
+    return STRQ_OK;
+}
+
+int strq_last_units(strq_ctx* c, double* out4)
+{
+    if (!c || !out4) return STRQ_ERR_ARG;
+    DetectState* d = dstate(c);
+    out4[0] = d->unit_ms; out4[1] = d->unit_bytes; out4[2] = d->unit_reads; out4[3] = d->unit_positions;
+    return STRQ_OK;
+}
+
 static int batch_prepare(strq_ctx* c, int64_t n_reads, const void* signals, int32_t dtype, const int64_t* offsets,
                          const int32_t* target_id, const double* host_stats, bool lazy, const void* const* reads = nullptr)
 {
@@ -893,6 +1073,7 @@ static int batch_prepare(strq_ctx* c, int64_t n_reads, const void* signals, int3
     }
     B.results.assign((size_t)n_reads, strq_result());
     B.mod.assign((size_t)n_reads, std::string("-"));
+    B.reset_units(n_reads);
     if (!d->ev_ok) { for (auto& e : d->ev) STRQ_HIP(c, hipEventCreate(&e)); d->ev_ok = true; }
     return STRQ_OK;
 }
@@ -925,6 +1106,7 @@ int strq_batch_upload_part(strq_ctx* c, int64_t total_reads, int64_t total_sampl
         STRQ_HIP(c, B.raw.reserve((size_t)total_samples * 2 + 64));      // total_samples is a hint: the buffer grows (below) when the parts hold more
         B.results.assign((size_t)total_reads, strq_result());
         B.mod.assign((size_t)total_reads, std::string("-"));
+        B.reset_units(total_reads);
         B.uploaded = 0; B.on_host = false;
         d->part_reads = 0;
         if (!d->ev_ok) { for (auto& e : d->ev) STRQ_HIP(c, hipEventCreate(&e)); d->ev_ok = true; }
@@ -982,6 +1164,8 @@ int strq_batch_run_range(strq_ctx* c, int64_t first, int64_t last)
     std::fill(c->overlap, c->overlap + 4, 0.0);
     c->second_round[0] = c->second_round[1] = 0; c->look2_served = 0;
     for (double& v : c->screen_stats) v = 0;
+    B.units_ran = d->units_on;
+    d->unit_ms = 0; d->unit_bytes = d->unit_reads = d->unit_positions = 0;
     STRQ_HIP(c, c->redo_total.reserve(64));
     STRQ_HIP(c, hipMemsetAsync(c->redo_total.p, 0, 64, c->stream));
     // partition into sub-batches first, so that the upload of piece k + 1 can overlap the kernels of piece k

@@ -33,6 +33,21 @@ static const char* validate_vit_model(int32_t n_states, int32_t silent_start, co
     return nullptr;
 }
 
+// The two counted states of a unit decode (VIT_UNIT_T_MAX): exactly two emitting states with count_inc 1 and no other counted state
+// -- STRique's dummy states, STRique.py:374-378
+static void vit_unit_states(VitModel& m, int32_t n_states, int32_t ne, const int32_t* count_inc)
+{
+    m.unit_state[0] = m.unit_state[1] = -1;
+    if (!count_inc) return;
+    int found = 0, st[2] = {-1, -1};
+    for (int l = 0; l < n_states; ++l) {
+        if (count_inc[l] == 0) continue;
+        if (l >= ne || count_inc[l] != 1 || found == 2) return;
+        st[found++] = l;
+    }
+    if (found == 2) { m.unit_state[0] = st[0]; m.unit_state[1] = st[1]; }
+}
+
 int build_vit_model(strq_ctx* c, int32_t n_states, int32_t silent_start, int32_t start, int32_t end,
                     const int32_t* in_ptr, const int32_t* in_src, const double* in_logp,
                     const int32_t* emis_kind, const double* emis_a, const double* emis_b, const double* emis_c,
@@ -228,6 +243,7 @@ int build_vit_model(strq_ctx* c, int32_t n_states, int32_t silent_start, int32_t
     for (int e = in_ptr[end]; e < in_ptr[end + 1]; ++e) if (in_src[e] < ne && state_tag && state_tag[in_src[e]] == 2) m.rec_state = in_src[e];
     m.silent_counted = 0;
     for (int s2 = ne; s2 < n_states; ++s2) if (count_inc && count_inc[s2] != 0) m.silent_counted = 1;
+    vit_unit_states(m, n_states, ne, count_inc);
     m.cell_state = reinterpret_cast<const int32_t*>(d + parts[12].off);
     hm->dev = reinterpret_cast<const VitModel*>(d + o_m);
     std::vector<char> host(total, 0);
@@ -251,6 +267,7 @@ int build_vit_model_csr(strq_ctx* c, int32_t n_states, int32_t silent_start, int
     std::memset(&m, 0, sizeof(m));
     m.n_states = n_states; m.n_emit = ne; m.n_silent = ns; m.start = start; m.end = end; m.epl = 0; m.spl = 0;
     m.csr = 1; m.n_cells = n_states + 1; m.start_cell = start; m.end_cell = end; m.rec_state = -1; m.single_stage = 0;
+    m.unit_state[0] = m.unit_state[1] = -1;          // no unit decode on this kernel: the unit pass takes back-pointers
     // level of a silent state: length of its longest chain of silent predecessors (they are in topological order)
     std::vector<int> level(n_states, 0); int nlev = 0;
     for (int l = ne; l < n_states; ++l) {
@@ -510,6 +527,19 @@ int build_vit_g2(strq_ctx* c, HostModel* hm, const int32_t* kind_hint, const int
         std::memcpy(&host[o_g], &G, sizeof(VitG2));
         if (hipMemcpy(d, host.data(), total, hipMemcpyHostToDevice) != hipSuccess) { c->err = "model upload failed"; return STRQ_ERR_DEVICE; }
         hm->h.g2 = reinterpret_cast<const VitG2*>(d + o_g); hm->h.g2_odd = L.odd; hm->h.g2_mark = L.mark_add.empty() ? 0 : 1;
+        // unit decodes: the two counted states are the broadcast sources, one in each of their slots (record index = the slot's)
+        {
+            int hits[2] = {0, 0}; bool other = false;
+            for (int k = 0; k < 4; ++k)
+                for (int lane = 0; lane < 64; ++lane) {
+                    const int32_t v = inc[(size_t)k * 64 + lane];
+                    if (!v) continue;
+                    if (v == 1 && (k == L.odd || k == 2 + L.odd) && lane == G.bc_lane[k >> 1] &&
+                        (own[(size_t)k * 64 + lane] == hm->h.unit_state[0] || own[(size_t)k * 64 + lane] == hm->h.unit_state[1])) ++hits[k >> 1];
+                    else other = true;
+                }
+            hm->h.g2_unit = (hm->h.unit_state[0] >= 0 && hits[0] == 1 && hits[1] == 1 && !other) ? 1 : 0;
+        }
         if (hipMemcpy(const_cast<VitModel*>(hm->dev), &hm->h, sizeof(VitModel), hipMemcpyHostToDevice) != hipSuccess) { hm->h.g2 = nullptr; c->err = "model upload failed"; return STRQ_ERR_DEVICE; }
         return STRQ_OK;
     }

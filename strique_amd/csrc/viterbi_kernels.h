@@ -91,9 +91,13 @@ struct VitModel {
     const int32_t* csr_level_state;   // n_silent
     const VitG2* g2;                  // register-resident profile layout of the same model, or null (strq_model_set_positions)
     int32_t g2_odd, g2_mark;          // that image has its broadcast sources at odd positions; it can carry the repeat-section marks (mark_add)
+    // unit decodes (want_bp 4): the model's two counted states (emitting, count_inc 1, ascending; -1: the model has no such pair),
+    // and whether the register-resident image holds them in the slots of its two broadcast sources (B0: record 0, B1: record 1)
+    int32_t unit_state[2];
+    int32_t g2_unit;
 };
 #define VIT_SHAPE_CSR 8              // launch_viterbi shape id of those models
-#define VIT_SHAPE_G2 9               // ... of models with a VitG2 image, for count / mark launches (want_bp 0 or 2); both parities (g2_odd) share the launch
+#define VIT_SHAPE_G2 9               // ... of models with a VitG2 image, for count / mark / unit launches (want_bp 0, 2 or 4); both parities (g2_odd) share the launch
 #define VIT_CSR_MAX_STATES 4096      // two buffers of 16-byte cells in 160 KB of LDS
 
 enum { VIT_SRC_F64 = 0, VIT_SRC_F64_AFFINE = 1, VIT_SRC_I16_AFFINE = 2 };
@@ -104,8 +108,16 @@ struct VitTask {
     int64_t T;
     int32_t src_kind, pad_;
     double c1, h1, h2, c2, lo, hi;    // x = clip((s - c1) / h1 * h2 + c2, lo, hi)  (STRique.py:159-160,178-179)
-    uint16_t* bp;            // (T + 1) x (n_states) predecessor states, nullable (count-only mode); hub mode: (T + 1) 8-byte hub records
+    uint16_t* bp;            // (T + 1) x (n_states) predecessor states, nullable (count-only mode); hub mode: (T + 1) 8-byte hub records;
+                             // unit mode: 2 x T 4-byte unit records (see VIT_UNIT_T_MAX)
 };
+
+// UNIT decode (want_bp 4, flanked model): the best path carries a 32-bit payload  p = (t + 1) << 1 | k  -- the observation t of its
+// last emission from a counted state and which of the two it was (k = 0: VitModel::unit_state[0]), 0 = none.  Every emission of
+// counted state k at observation t stores the payload it replaces as record 2 t + k of the task's buffer, so that the observations
+// of all counted emissions on the best path are read back from the end state's payload (VitResult::dbg[0]) with one hop per repeat
+// unit (unit_kernels.hip).  Windows below 2^30 observations (reads are at most 2^30 samples long: strq_batch_upload).
+#define VIT_UNIT_T_MAX ((int64_t)1 << 30)
 
 struct VitResult {
     double logp;
@@ -124,8 +136,10 @@ int vit_shape_silent_slots(int shape);             // silent slots per lane of t
 int launch_viterbi(hipStream_t stream, int shape, int max_cells, const VitTask* tasks, VitResult* results,
                    int n_tasks, int* queue, int n_cu, int want_bp, const int* order = nullptr, int waves_hint = 0);
 // waves_hint 4: the launch shares the GPU with other kernels (register-resident shape: four waves per workgroup instead of eight)
-// want_bp: 0 = count only, 1 = back-pointers, 2 = repeat-section marks (flanked model), 3 = hub records (modification model)
+// want_bp: 0 = count only, 1 = back-pointers, 2 = repeat-section marks (flanked model), 3 = hub records (modification model),
+// 4 = unit records (flanked model, VIT_UNIT_T_MAX; returns 2 for shapes and models without it: vit_unit_ok)
 int launch_vit_sort(hipStream_t stream, const VitTask* tasks, int n, int* order);   // order by descending T (n <= 8192)
+bool vit_unit_ok(const VitModel& model_host, int shape);      // a want_bp 4 launch of this shape (vit_shape_for(.., 4)) decodes this model
 int launch_vit_traceback(hipStream_t stream, const VitTask* tasks, const VitResult* results,
                          int32_t* const* paths, int n_tasks);
 

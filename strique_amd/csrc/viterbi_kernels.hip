@@ -151,7 +151,9 @@ template <int EPL, int SPL> struct VitLds {
 // best path carries the time of its last e0 emission and the branch of its current unit; every e0 emission
 // at time t stores that pair as record t (8 bytes) -- so the per-unit '0'/'1' string is read back by hopping
 // from hub to hub (one hop per repeat unit) instead of tracing a back-pointer per (time step, state).
-template <int EPL, int SPL, int DE_HI, int DE_LO, int DS, bool BP, bool SS, bool MARK = false, bool HUB = false>
+//
+// UNIT (flanked model): the same scheme for the two counted states that close the repeat loop -- see VIT_UNIT_T_MAX.
+template <int EPL, int SPL, int DE_HI, int DE_LO, int DS, bool BP, bool SS, bool MARK = false, bool HUB = false, bool UNIT = false>
 __global__ void __launch_bounds__((64 * VitLds<EPL, SPL>::WAVES))
 viterbi_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ results,
                int n_tasks, int* __restrict__ queue, const int* __restrict__ order)
@@ -197,7 +199,7 @@ viterbi_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ result
         }
     };
     auto pay_add = [](Pay v, int inc) -> Pay {       // count += inc (the count field never carries out of the low half)
-        if constexpr (HUB) return v;          // the modification model counts nothing
+        if constexpr (HUB || UNIT) return v;          // the modification model counts nothing; a unit decode carries records instead
         else if constexpr (MARK) return ((uint64_t)v & 0xFFFFFFFF00000000ull) | (uint32_t)((uint32_t)v + (uint32_t)inc);
         else return v + inc;
     };
@@ -211,6 +213,7 @@ viterbi_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ result
     constexpr bool single_stage = SS;
     // everything a lane needs about the states it owns lives in registers (reloaded when the model changes)
     int own_e[EPL], einc[EPL]; bool enorm[EPL]; bool etag[EPL]; bool ehub[EPL], erec[EPL];
+    int eunit[EPL];      // UNIT: record index of the counted state owned by (slot, lane), -1 none
     const char* esrc[EPL][DEMAX]; char* edst[EPL];
     double ea[EPL], eb[EPL], ec[EPL], elp[EPL][DEMAX];
     double ebf[EPL], ecf[EPL];     // branch-free emission: ecf - (x - ea)^2 * ebf  (uniform: ebf = 0; padding: ecf = -inf)
@@ -248,6 +251,7 @@ viterbi_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ result
                 etag[s] = own_e[s] >= 0 && M.state_tag[own_e[s]] == 1;
                 ehub[s] = own_e[s] >= 0 && M.state_tag[own_e[s]] == 2;
                 erec[s] = own_e[s] >= 0 && own_e[s] == M.rec_state;
+                if constexpr (UNIT) eunit[s] = own_e[s] < 0 ? -1 : (own_e[s] == M.unit_state[0] ? 0 : (own_e[s] == M.unit_state[1] ? 1 : -1));
                 edst[s] = vbase + 16 * (own_e[s] >= 0 ? s * 64 + lane : TRASH);
 #pragma unroll
                 for (int j = 0; j < DEMAX; ++j) {
@@ -495,6 +499,9 @@ viterbi_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ result
                         lo = tt1;
                     }
                     nc[s] = ((uint64_t)hi << 32) | lo;
+                } else if constexpr (UNIT) {
+                    if (eunit[s] >= 0 && tk.bp) reinterpret_cast<uint32_t*>(tk.bp)[2 * t + eunit[s]] = (uint32_t)bc;      // record of this counted emission
+                    nc[s] = eunit[s] >= 0 ? (int)((tt1 << 1) | (uint32_t)eunit[s]) : bc;
                 } else nc[s] = bc + einc[s];
             }
 #pragma unroll
@@ -592,6 +599,10 @@ viterbi_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ result
             r.dbg[0] = (plo >> 20) | ((phi & 0x3FFu) << 12);       // time (1-based) of the first repeat-section emission, 0 = none
             r.dbg[1] = phi >> 10;                                  // time of the first emission after the repeat section, 0 = none
             if (tk.T >= VIT_MARK_T_MAX) r.status = 2;              // window too long for the packed marks
+        } else if constexpr (UNIT) {
+            r.counted = 0;                                         // (the count decode reports it: the hops of the record chain)
+            r.dbg[0] = (uint32_t)fin.c;                            // payload of the end state: the last counted emission, 0 = none
+            if (tk.T >= VIT_UNIT_T_MAX) r.status = 2;
         } else {
             r.counted = (lp > NEGINF) ? (int64_t)fin.c : 0;
         }
@@ -642,7 +653,8 @@ static __device__ __forceinline__ void g2_tournament(double (&cv)[8], P (&cc)[8]
 // Both parities of the chain in one kernel: a repeat profile of odd length (CGG, CAG) puts the two broadcast sources at odd
 // positions, and which of the two code paths a window takes is decided per task -- wave-uniform, outside the time loop -- from
 // its model (VitModel::g2_odd).  A sub-batch that mixes such targets with even ones (C9orf72 + FMR1 + HTT) is one launch.
-template <bool MARK, int WAVES, int LXL>
+// UNIT: unit records (VIT_UNIT_T_MAX) instead of the count -- the counted states are the broadcast sources B0 (record 0) and B1 (record 1).
+template <bool MARK, int WAVES, int LXL, bool UNIT = false>
 __global__ void __launch_bounds__(64 * WAVES)
 viterbi_g2_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ results,
                   int n_tasks, int* __restrict__ queue, const int* __restrict__ order)
@@ -850,6 +862,14 @@ viterbi_g2_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ res
                 nv[k] = best[k] + em;
                 const Pay bc = bcnt[k];
                 if constexpr (MARK) nc[k] = bc + madd[k];          // the three counters of G2_MARK_* in one 64-bit addition
+                else if constexpr (UNIT) {
+                    if constexpr (k == B0 || k == B1) {
+                        constexpr uint32_t rk = k == B1 ? 1u : 0u;
+                        const bool hit = einc[k] != 0;          // the lane of the broadcast source (VitModel::g2_unit)
+                        if (hit && tk.bp) reinterpret_cast<uint32_t*>(tk.bp)[2 * t + rk] = (uint32_t)bc;
+                        nc[k] = hit ? (int)(((uint32_t)(t + 1) << 1) | rk) : bc;
+                    } else nc[k] = bc;
+                }
                 else nc[k] = (k == B0 || k == B1) ? bc + einc[k] : bc;          // counted states sit in the slots of the broadcast sources (checked when the image is built)
             };
             using K0 = std::integral_constant<int, 0>; using K1 = std::integral_constant<int, 1>;
@@ -945,6 +965,10 @@ viterbi_g2_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ res
             r.dbg[0] = tagged > 0 ? (uint32_t)(T - behind - tagged + 1) : 0u;
             r.dbg[1] = (tagged > 0 && behind > 0) ? (uint32_t)(T - behind + 1) : 0u;
             if (tk.T >= VIT_MARK_T_MAX) r.status = 2;
+        } else if constexpr (UNIT) {
+            r.counted = 0;
+            r.dbg[0] = (uint32_t)fc;          // payload of the end state (viterbi_kernel)
+            if (tk.T >= VIT_UNIT_T_MAX) r.status = 2;
         } else {
             r.counted = (lp > NEGINF) ? (int64_t)fc : 0;
         }
@@ -954,7 +978,11 @@ viterbi_g2_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ res
 
 static int launch_viterbi_g2(hipStream_t stream, const VitTask* tasks, VitResult* results, int n_tasks, int* queue, int n_cu, int want_bp, const int* order, int waves_hint)
 {
-    if (want_bp != 0 && want_bp != 2) return 2;
+    if (want_bp != 0 && want_bp != 2 && want_bp != 4) return 2;
+    if (want_bp == 4) {          // the unit pass runs alone on the GPU (strq_detect_api.hip: run_unit_pass): eight waves, all exchanges through LDS
+        hipLaunchKernelGGL((viterbi_g2_kernel<false, 8, 2, true>), dim3(n_cu), dim3(64 * 8), (size_t)8 * G2_LDS_WAVE_BYTES, stream, tasks, results, n_tasks, queue, order);
+        return hipGetLastError() == hipSuccess ? 0 : 1;
+    }
     // one workgroup per CU: eight waves (two per SIMD, 2 x 192 VGPRs) when the launch has the GPU to itself; four (one per SIMD) when it
     // shares the CUs with the next sub-batch's flank-alignment kernels, whose waves then find 320 VGPRs per SIMD instead of 128
     // (gpurun_out/r6i: 175 against 180 ms per step of 4096 reads; alone, four waves take 83 ms against 64)
@@ -1091,7 +1119,7 @@ viterbi_csr_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ re
 static int launch_viterbi_csr(hipStream_t stream, int max_cells, const VitTask* tasks, VitResult* results, int n_tasks,
                               int* queue, int n_cu, int want_bp, const int* order)
 {
-    if (max_cells - 1 > VIT_CSR_MAX_STATES || want_bp == 3) return 2;
+    if (max_cells - 1 > VIT_CSR_MAX_STATES || want_bp == 3 || want_bp == 4) return 2;
     const size_t lds = (size_t)2 * (size_t)(max_cells - 1) * 16;
     int per_cu = (int)((160 * 1024 - 64) / (lds ? lds : 1)); if (per_cu > 4) per_cu = 4; if (per_cu < 1) per_cu = 1;
     const dim3 grid(per_cu * n_cu), block(256);
@@ -1228,8 +1256,16 @@ int vit_shape_silent_slots(int shape)
 int vit_shape_for(const VitModel& mh, int want_bp)
 {
     const bool no_g2 = strq::opt("STRQ_VIT_NO_G2") != nullptr;      // A/B: the lane layout for every mode
-    if (mh.g2 && !no_g2 && (want_bp == 0 || (want_bp == 2 && mh.g2_mark))) return VIT_SHAPE_G2;          // either parity of the chain: decided per window inside the kernel
+    if (mh.g2 && !no_g2 && (want_bp == 0 || (want_bp == 2 && mh.g2_mark) || (want_bp == 4 && mh.g2_unit))) return VIT_SHAPE_G2;          // either parity of the chain: decided per window inside the kernel
     return vit_shape_of(mh);
+}
+
+bool vit_unit_ok(const VitModel& mh, int shape)
+{
+    if (shape < 0 || mh.unit_state[0] < 0 || mh.unit_state[1] < 0 || mh.silent_counted) return false;
+    const int b = shape & ~VIT_SHAPE_SS;
+    if (b == VIT_SHAPE_G2) return mh.g2 && mh.g2_unit;
+    return b != VIT_SHAPE_CSR && b != 1 && b != 6;          // lane layouts with at least two emitting slots (vit_launch_shape)
 }
 
 int vit_shape_of(const VitModel& mh)
@@ -1249,19 +1285,23 @@ static int vit_launch_shape(hipStream_t stream, int max_cells, const VitTask* ta
     if (const char* e = strq::opt("STRQ_VIT_WAVES")) { const int v = atoi(e); if (v >= 1 && v <= nw) nw = v; }      // experiments: fewer waves per CU
     const size_t lds = (size_t)nw * 2 * VitLds<E_, S_>::BUF;
     const dim3 grid(n_cu), block(64 * nw);
-#define VIT_GO(BP_, SS_, MK_, HB_)                                                                                        \
+#define VIT_GO(BP_, SS_, MK_, HB_, UN_)                                                                                   \
     do {                                                                                                                  \
-        (void)hipFuncSetAttribute((const void*)viterbi_kernel<E_, S_, H_, L_, D_, BP_, SS_, MK_, HB_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((viterbi_kernel<E_, S_, H_, L_, D_, BP_, SS_, MK_, HB_>), grid, block, lds, stream, tasks, results, n_tasks, queue, order);       \
+        (void)hipFuncSetAttribute((const void*)viterbi_kernel<E_, S_, H_, L_, D_, BP_, SS_, MK_, HB_, UN_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        hipLaunchKernelGGL((viterbi_kernel<E_, S_, H_, L_, D_, BP_, SS_, MK_, HB_, UN_>), grid, block, lds, stream, tasks, results, n_tasks, queue, order);       \
     } while (0)
-    // want_bp: 0 = count only, 1 = back-pointers, 2 = repeat-section marks carried along the best path, 3 = hub records
-    if (want_bp == 3) {
-        if constexpr (E_ <= 2) { if (single_stage) VIT_GO(false, true, false, true); else VIT_GO(false, false, false, true); }
+    // want_bp: 0 = count only, 1 = back-pointers, 2 = repeat-section marks carried along the best path, 3 = hub records, 4 = unit records
+    if (want_bp == 4) {
+        if constexpr (E_ >= 2) { if (single_stage) VIT_GO(false, true, false, false, true); else VIT_GO(false, false, false, false, true); }
         else return 2;
     }
-    else if (want_bp == 2) { if (single_stage) VIT_GO(false, true, true, false); else VIT_GO(false, false, true, false); }
-    else if (want_bp) { if (single_stage) VIT_GO(true, true, false, false); else VIT_GO(true, false, false, false); }
-    else { if (single_stage) VIT_GO(false, true, false, false); else VIT_GO(false, false, false, false); }
+    else if (want_bp == 3) {
+        if constexpr (E_ <= 2) { if (single_stage) VIT_GO(false, true, false, true, false); else VIT_GO(false, false, false, true, false); }
+        else return 2;
+    }
+    else if (want_bp == 2) { if (single_stage) VIT_GO(false, true, true, false, false); else VIT_GO(false, false, true, false, false); }
+    else if (want_bp) { if (single_stage) VIT_GO(true, true, false, false, false); else VIT_GO(true, false, false, false, false); }
+    else { if (single_stage) VIT_GO(false, true, false, false, false); else VIT_GO(false, false, false, false, false); }
 #undef VIT_GO
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }

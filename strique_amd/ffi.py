@@ -300,6 +300,26 @@ class Context(object):
         raw = pool.tobytes()
         return [raw[off[i]:off[i + 1]].decode() for i in range(self._n_batch)]
 
+    def set_units(self, on):
+        """strq_set_units: later run calls also produce repeat-unit positions (batch_fetch_units)."""
+        self._check(self._lib.strq_set_units(self._h, ctypes.c_int32(1 if on else 0)))
+
+    def batch_fetch_units(self):
+        """Unit positions of the last batch: one ascending np.int64 array of raw-signal sample indices per read, or None for a
+        read that was not decoded (strq_batch_fetch_units)."""
+        n = getattr(self, '_n_batch', 0)
+        off = np.zeros(n + 1, np.int64); dec = np.zeros(max(1, n), np.int32)
+        self._check(self._lib.strq_batch_fetch_units(self._h, None, ctypes.c_int64(0), _ptr(off), _ptr(dec)))
+        pool = np.zeros(max(1, int(off[-1])), np.int64)
+        self._check(self._lib.strq_batch_fetch_units(self._h, _ptr(pool), ctypes.c_int64(len(pool)), _ptr(off), _ptr(dec)))
+        return [pool[off[i]:off[i + 1]].copy() if dec[i] else None for i in range(n)]
+
+    def last_units(self):
+        """The unit pass of the last run call: {'ms', 'ws_bytes', 'windows', 'positions'} (strq_last_units)."""
+        out = np.zeros(4)
+        self._check(self._lib.strq_last_units(self._h, _ptr(out)))
+        return {'ms': float(out[0]), 'ws_bytes': float(out[1]), 'windows': int(out[2]), 'positions': int(out[3])}
+
     def batch_upload(self, signals, offsets, target_ids, host_stats=None):
         """signals: one concatenated int16 or float64 array; offsets: n_reads + 1."""
         signals = np.ascontiguousarray(signals)

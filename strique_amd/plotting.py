@@ -68,9 +68,11 @@ def smooth(raw):
 PANELS = (("overview", "whole"), ("left", "begin"), ("right", "end"))
 
 
-def draw(fig, raw, row, extension=0.1, zoom=500):
+def draw(fig, raw, row, extension=0.1, zoom=500, units=None):
     """One read on `fig` (a matplotlib Figure).  Returns {panel: Axes}; every Axes carries `strique_span`, the
-    (first, past) sample pair it shades, so that a caller or a test can read back what was drawn."""
+    (first, past) sample pair it shades, so that a caller or a test can read back what was drawn.
+    `units`: repeat-unit positions (`count --units`), marked as ticks along the bottom of every panel; each Axes then
+    also carries `strique_units`, the positions inside its range."""
     sig = smooth(raw)
     win = Windows(len(sig), row.offset, row.ticks, extension, zoom)
     grid = fig.add_gridspec(2, 2, height_ratios=(3, 2))
@@ -90,6 +92,13 @@ def draw(fig, raw, row, extension=0.1, zoom=500):
         edge = win.repeat[0] if panel == "left" else win.repeat[1] if panel == "right" else None
         if edge is not None:
             ax.axvline(edge, color="tab:red", linewidth=1.0)
+        if units is not None:
+            u = np.asarray(units, np.int64)
+            u = u[(u >= lo) & (u < hi)]
+            ax.strique_units = u
+            if u.size:
+                ax.plot(u, np.full(u.size, 0.02), transform=ax.get_xaxis_transform(), linestyle="none", marker="|",
+                        markersize=8, color="tab:green")
         ax.set_xlim(lo, max(hi, lo + 1))
         ax.set_title(captions[panel], fontsize=9)
         ax.set_xlabel("sample of the read")
