@@ -138,9 +138,19 @@ int align_validate_flank(strq_ctx* c, const float* f, int64_t m, int samples, in
 size_t align_workspace_bytes(int n, int m, int R, int NS);   // checkpoints + strip boundary of one alignment
 float host_cell_score(const AlignParams& p, float h, float v);
 void detect_state_free(strq_ctx* c);
+int detect_drain(strq_ctx* c);              // rows of every detect sub-batch in flight taken (strq_detect_api.hip); nothing to do without detect state
+// launch_viterbi's return code as a status of the C ABI.  2 / 3: this kernel shape has no such decode mode -- the caller's input, not a device fault
+int viterbi_launch_status(int vrc);
 void host_stats_batch(const double* signals, const int64_t* offsets, int64_t n_reads, bool want_raw, double* out,
                       const double* const* reads = nullptr);   // host_stats.hip; reads: one buffer per read instead of `signals`
 }
+
+// The way into the library, first statement of an entry point that can reach the device or strq::opt: a null context is rejected,
+// then the context's scope, then its device.
+#define STRQ_ENTER(ctx)                                                                        \
+    if (!(ctx)) return STRQ_ERR_ARG;                                                           \
+    strq::CtxScope scope_(ctx);                                                                \
+    STRQ_HIP(ctx, hipSetDevice((ctx)->device))
 
 #define STRQ_HIP(ctx, call)                                                                    \
     do {                                                                                       \

@@ -133,10 +133,19 @@ struct Batch {
     std::vector<std::vector<int64_t>> units;      // unit positions per read (strq_batch_fetch_units)
     std::vector<uint8_t> unit_dec;       // 1: the read was decoded (gate passed, the flanked model found a path)
     void reset_units(int64_t n) { units.assign((size_t)n, std::vector<int64_t>()); unit_dec.assign((size_t)n, 0); units_ran = false; }
+    // a new batch of n reads: rows, patterns and unit positions at their initial values, no samples uploaded, nothing of the caller's referenced
+    void begin(int64_t n, int dt)
+    {
+        forget_host();
+        n_reads = n; dtype = dt; uploaded = 0; host_stats.clear();
+        results.assign((size_t)n, strq_result()); mod.assign((size_t)n, std::string("-")); reset_units(n);
+    }
     float t_cond = 0, t_lut = 0, t_fwd = 0, t_trace = 0, t_vit = 0, t_total = 0;
     double n_hard = 0;
     int n_fwd_launches = 0;
 };
+
+struct VitGroup { int shape, first, count, max_cells; };      // one Viterbi launch: kernel shape, task range, largest n_cells of its models
 
 struct DetectState {
     PoreStats ps{0, 0, 0, 0};
@@ -148,7 +157,6 @@ struct DetectState {
     bool units_on = false;               // strq_set_units
     float unit_ms = 0; double unit_bytes = 0, unit_reads = 0, unit_positions = 0;      // strq_last_units: the last run call's unit pass
     hipEvent_t ev[4] = {};
-    bool ev_ok = false;
     int64_t part_reads = 0;              // strq_batch_upload_part: reads uploaded so far
     // Two sub-batches are in flight at a time: the Viterbi launches of sub-batch k run on `vit_stream` while the conditioning and the
     // flank alignments of sub-batch k + 1 are queued on the context's stream (the Viterbi launch lasts as long as its longest window --
@@ -156,16 +164,47 @@ struct DetectState {
     // reads or writes exists twice (filtered signal, tasks, results, order, queue heads); results come back one sub-batch late.
     struct Slot {
         DevBuf flt, vit, vres, order, vq;
-        bool active = false;             // forward stage done, results not yet in Batch::results
-        bool launch_pending = false;     // ... and its Viterbi launches not yet queued (they go behind the score-table kernel of the next sub-batch)
-        struct VL { int shape, first, count, max_states; };
-        std::vector<VL> vls;             // the Viterbi launches of the sub-batch: kernel shape, task range
+        // Idle -> Forward: publish_forward, the forward stage of reads [r0, r0 + nr) is queued, its Viterbi launches are not (they go behind the
+        //   score-table kernel of the next sub-batch)
+        // Forward -> Decoding: launch_viterbi_of, once the launches and the copy of their results are queued and `v1` is recorded
+        // Decoding -> Idle: harvest, once the rows are in Batch::results and the modification / unit pass of the sub-batch has run
+        // A failure on the way goes through abandon(): Idle, the rows at their initial values.
+        enum State { Idle, Forward, Decoding };
+        State state = Idle;
+        std::vector<VitGroup> vls;       // the Viterbi launches of the sub-batch
         int vit_mode = 0;                // 0 count, 2 MARK (modification pass follows)
         bool units = false;              // the unit pass follows (strq_set_units when the sub-batch was launched)
         int64_t r0 = 0; int nr = 0;
         std::vector<int32_t> vit_slot;
-        void* pinned = nullptr; size_t pinned_cap = 0;      // ReadGeom[nr], VitResult[nr], ReadCond[nr], unsigned redo
+        void* pinned = nullptr; size_t pinned_cap = 0;
         hipEvent_t fwd_done = nullptr, v0 = nullptr, v1 = nullptr;
+        // the pinned block of the slot: what the host reads of a sub-batch of `nr` reads
+        struct Pinned {
+            ReadGeom* geom; VitResult* vres; ReadCond* rc; unsigned int* redo;
+            static size_t bytes(int nr) { return (size_t)nr * (sizeof(ReadGeom) + sizeof(VitResult) + sizeof(ReadCond)) + 64; }
+        };
+        Pinned host() const
+        {
+            Pinned h; h.geom = static_cast<ReadGeom*>(pinned); h.vres = reinterpret_cast<VitResult*>(h.geom + nr);
+            h.rc = reinterpret_cast<ReadCond*>(h.vres + nr); h.redo = reinterpret_cast<unsigned int*>(h.rc + nr);
+            return h;
+        }
+        // buffers and pinned block for a sub-batch of `n` reads with `flt_bytes` of filtered signal
+        int reserve(strq_ctx* c, int n, size_t flt_bytes)
+        {
+            STRQ_HIP(c, flt.reserve(flt_bytes));
+            STRQ_HIP(c, vit.reserve((size_t)n * sizeof(VitTask)));
+            STRQ_HIP(c, vres.reserve((size_t)n * sizeof(VitResult)));
+            STRQ_HIP(c, order.reserve((size_t)n * 4 + 64));
+            STRQ_HIP(c, vq.reserve(1024));
+            const size_t need = Pinned::bytes(n);
+            if (need > pinned_cap) {
+                if (pinned) { STRQ_HIP(c, hipHostFree(pinned)); pinned = nullptr; pinned_cap = 0; }
+                STRQ_HIP(c, hipHostMalloc(&pinned, need + need / 8, hipHostMallocDefault));
+                pinned_cap = need + need / 8;
+            }
+            return STRQ_OK;
+        }
     };
     Slot slot[2];
     int next_slot = 0;
@@ -204,22 +243,69 @@ void detect_state_free(strq_ctx* c)
         for (hipEvent_t e : {sl.fwd_done, sl.v0, sl.v1}) if (e) (void)hipEventDestroy(e);
     }
     if (d->vit_stream) (void)hipStreamDestroy(d->vit_stream);
-    if (d->ev_ok) for (auto& e : d->ev) (void)hipEventDestroy(e);
+    for (hipEvent_t e : d->ev) if (e) (void)hipEventDestroy(e);
     if (d->copy_stream) (void)hipStreamDestroy(d->copy_stream);
     for (int i = 0; i < DetectState::N_STAGE; ++i) { if (d->stage[i]) (void)hipHostFree(d->stage[i]); if (d->stage_ev[i]) (void)hipEventDestroy(d->stage_ev[i]); }
     delete d;
     c->detect = nullptr;
 }
 
+// One group of Viterbi tasks (`tasks`, `results`, `order`: the arrays the group's range indexes).  Its tasks in descending window length
+// first, where vit_sort_kernel takes that many ...
+static int* group_order(int* order, const VitGroup& g) { return g.count <= 8192 ? order + g.first : nullptr; }
+static int sort_viterbi_group(strq_ctx* c, hipStream_t st, const VitGroup& g, const VitTask* tasks, int* order)
+{
+    int* d_order = group_order(order, g);
+    if (d_order && launch_vit_sort(st, tasks + g.first, g.count, d_order)) { c->err = "sort launch failed"; return STRQ_ERR_DEVICE; }
+    return STRQ_OK;
+}
+// ... then the persistent launch in decode mode `mode` on queue head `queue` (`what`: who says that the shape has no such mode)
+static int launch_viterbi_group(strq_ctx* c, hipStream_t st, const VitGroup& g, const VitTask* tasks, VitResult* results, int* order, int* queue,
+                                int mode, int waves_hint = 0, const char* what = "viterbi: ")
+{
+    const int vrc = launch_viterbi(st, g.shape, g.max_cells, tasks + g.first, results + g.first, g.count, queue, c->n_cu, mode, group_order(order, g), waves_hint);
+    if (viterbi_launch_status(vrc) == STRQ_ERR_UNSUPPORTED) c->err = std::string(what) + "decode mode not available for this model's kernel shape";
+    else if (vrc) c->err = "viterbi launch failed";
+    return viterbi_launch_status(vrc);
+}
+
+// read-back of the modification pass: the lengths first, then the strings gathered into a dense pool (the sparse buffer has one byte per
+// time step: ~180 MB per 4096 reads of 50 kb, 25 ms through pageable memory, for ~4 MB of strings)
+static int read_mod_patterns(strq_ctx* c, DetectState* d, int64_t r0, const std::vector<int>& who, const std::vector<int>& slot2, const std::vector<int64_t>& len,
+                             const std::vector<size_t>& p2_off, const int64_t* d_plen, const char* d_chars)
+{
+    hipStream_t st = c->stream;
+    const int nm = (int)who.size();
+    std::vector<int64_t> plen(nm);
+    STRQ_HIP(c, hipMemcpyAsync(plen.data(), d_plen, (size_t)nm * 8, hipMemcpyDeviceToHost, st));
+    STRQ_HIP(c, hipStreamSynchronize(st));
+    std::vector<GatherTask> gt(nm); size_t dense = 0;
+    for (int k = 0; k < nm; ++k) {
+        const int64_t ln = std::max<int64_t>(0, std::min<int64_t>(plen[slot2[k]], len[k] + 1));
+        gt[k] = {(int64_t)p2_off[k], (int64_t)dense, ln}; dense += (size_t)ln;
+    }
+    STRQ_HIP(c, d->modpool.reserve(dense + (size_t)nm * sizeof(GatherTask) + 64));
+    GatherTask* d_gt = d->modpool.as<GatherTask>(); char* d_dense = reinterpret_cast<char*>(d_gt + nm);
+    STRQ_HIP(c, hipMemcpyAsync(d_gt, gt.data(), (size_t)nm * sizeof(GatherTask), hipMemcpyHostToDevice, st));
+    if (launch_mod_gather(st, d_gt, nm, d_chars, d_dense)) { c->err = "gather launch failed"; return STRQ_ERR_DEVICE; }
+    std::vector<char> chars(dense + 1);
+    if (dense) STRQ_HIP(c, hipMemcpyAsync(chars.data(), d_dense, dense, hipMemcpyDeviceToHost, st));
+    STRQ_HIP(c, hipStreamSynchronize(st));
+    for (int k = 0; k < nm; ++k) d->batch.mod[r0 + who[k]] = std::string(chars.data() + gt[k].dst, (size_t)gt[k].len);
+    return STRQ_OK;
+}
+
 // Modification pass for the reads of one sub-batch whose target has a modification model.
 // The flanked-model Viterbi ran in MARK mode (viterbi_kernels.hip): its result carries the first and
 // last sample decoded into the repeat section, which is all detect step 13 (STRique.py:608) needs.
-static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, int64_t r0, int nr, const ReadCond* rc,
-                        const ReadGeom* geom, const VitResult* vres,
-                        const std::vector<int32_t>& vit_slot)
+static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
 {
     Batch& B = d->batch;
     hipStream_t st = c->stream;
+    const int64_t r0 = sl.r0; const int nr = sl.nr;
+    const DetectState::Slot::Pinned h = sl.host();
+    const ReadCond* rc = h.rc; const ReadGeom* geom = h.geom; const VitResult* vres = h.vres;
+    const std::vector<int32_t>& vit_slot = sl.vit_slot;
     const int esz = B.dtype == 0 ? 2 : 8;
     const int64_t s0 = B.off[r0];
     std::vector<int> who;                      // reads that reach the modification model
@@ -299,17 +385,9 @@ static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, int6
             slot2[k] = sidx; tp2[sidx] = d_path2 + p2_off[k]; mx = std::max(mx, hm->h.n_cells); ++sidx;
         }
         STRQ_HIP(c, hipMemcpyAsync(d_tb + first, vt2.data() + first, (size_t)(sidx - first) * sizeof(VitTask), hipMemcpyHostToDevice, st));
-        int* d_order = nullptr;
-        if (sidx - first <= 8192) {
-            d_order = sl.order.as<int>() + first;
-            if (launch_vit_sort(st, d_tb + first, sidx - first, d_order)) { c->err = "sort launch failed"; return STRQ_ERR_DEVICE; }
-        }
-        if (const int vrc = launch_viterbi(st, g.first, mx, d_tb + first, d_tr + first, sidx - first, c->queue.as<int>() + qi, c->n_cu, use_hub ? 3 : 1, d_order)) {
-            // 2 / 3: this kernel shape has no such decode mode -- the caller's input, not a device fault (strq_viterbi_batch maps them the same way)
-            c->err = (vrc == 2 || vrc == 3) ? "viterbi: decode mode not available for this model's kernel shape" : "viterbi launch failed";
-            return (vrc == 2 || vrc == 3) ? STRQ_ERR_UNSUPPORTED : STRQ_ERR_DEVICE;
-        }
-        ++qi;
+        const VitGroup vg = {g.first, first, sidx - first, mx};
+        if (const int src = sort_viterbi_group(c, st, vg, d_tb, sl.order.as<int>())) return src;
+        if (const int lrc = launch_viterbi_group(c, st, vg, d_tb, d_tr, sl.order.as<int>(), c->queue.as<int>() + qi++, use_hub ? 3 : 1)) return lrc;
       } }
     int64_t* d_plen = d_len;
     if (use_hub) {
@@ -337,25 +415,7 @@ static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, int6
         STRQ_HIP(c, hipMemcpyAsync(d_pt, pt.data(), (size_t)nm * sizeof(PatTask), hipMemcpyHostToDevice, st));
         if (launch_mod_pattern(st, d_pt, nm, d_plen)) { c->err = "pattern launch failed"; return STRQ_ERR_DEVICE; }
     }
-    // read-back: the lengths first, then the strings gathered into a dense pool (the sparse buffer has one byte per time step:
-    // ~180 MB per 4096 reads of 50 kb, 25 ms through pageable memory, for ~4 MB of strings)
-    std::vector<int64_t> plen(nm);
-    STRQ_HIP(c, hipMemcpyAsync(plen.data(), d_plen, (size_t)nm * 8, hipMemcpyDeviceToHost, st));
-    STRQ_HIP(c, hipStreamSynchronize(st));
-    std::vector<GatherTask> gt(nm); size_t dense = 0;
-    for (int k = 0; k < nm; ++k) {
-        const int64_t ln = std::max<int64_t>(0, std::min<int64_t>(plen[slot2[k]], len[k] + 1));
-        gt[k] = {(int64_t)p2_off[k], (int64_t)dense, ln}; dense += (size_t)ln;
-    }
-    STRQ_HIP(c, d->modpool.reserve(dense + (size_t)nm * sizeof(GatherTask) + 64));
-    GatherTask* d_gt = d->modpool.as<GatherTask>(); char* d_dense = reinterpret_cast<char*>(d_gt + nm);
-    STRQ_HIP(c, hipMemcpyAsync(d_gt, gt.data(), (size_t)nm * sizeof(GatherTask), hipMemcpyHostToDevice, st));
-    if (launch_mod_gather(st, d_gt, nm, d_chars, d_dense)) { c->err = "gather launch failed"; return STRQ_ERR_DEVICE; }
-    std::vector<char> chars(dense + 1);
-    if (dense) STRQ_HIP(c, hipMemcpyAsync(chars.data(), d_dense, dense, hipMemcpyDeviceToHost, st));
-    STRQ_HIP(c, hipStreamSynchronize(st));
-    for (int k = 0; k < nm; ++k) B.mod[r0 + who[k]] = std::string(chars.data() + gt[k].dst, (size_t)gt[k].len);
-    return STRQ_OK;
+    return read_mod_patterns(c, d, r0, who, slot2, len, p2_off, d_plen, d_chars);
 }
 
 // Unit positions of the reads of one sub-batch (strq_set_units; repeatHMM.count_repeats' path, STRique.py:374-378,433-441): the
@@ -363,10 +423,12 @@ static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, int6
 // records, VIT_UNIT_T_MAX) where the model and the window allow it, else (STRQ_UNITS_BACKPOINTERS=1: always) with back-pointers and a
 // traceback.  Runs on the context's stream when the rows of the sub-batch are taken: the slot's filtered signal and tasks are live
 // until the slot is used again, which harvests it first.  Pieces of at most STRQ_UNITS_WS_BYTES (8 GiB) of records / back-pointers.
-static int run_unit_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, int64_t r0, int nr, const ReadGeom* geom, const VitResult* vres)
+static int run_unit_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
 {
     Batch& B = d->batch;
     hipStream_t st = c->stream;
+    const int64_t r0 = sl.r0; const int nr = sl.nr;
+    const ReadGeom* geom = sl.host().geom; const VitResult* vres = sl.host().vres;
     std::vector<int> who;                      // reads with a decode: gate passed, the flanked model found a path
     for (int i = 0; i < nr; ++i) {
         B.units[(size_t)(r0 + i)].clear(); B.unit_dec[(size_t)(r0 + i)] = 0;
@@ -416,7 +478,7 @@ static int run_unit_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, int
         STRQ_HIP(c, d->unit_pool.reserve(pos_n * 8 + 64));
         std::vector<VitTask> tv((size_t)m); std::vector<int32_t*> pv((size_t)m, nullptr); std::vector<UnitTask> uv((size_t)m);
         std::vector<int> read_of((size_t)m); std::vector<size_t> pos_off((size_t)m);
-        struct L { int shape, want, first, count, mx; };
+        struct L { VitGroup g; int want; };
         std::vector<L> launches;
         size_t wo = 0, po = 0, xo = 0; int at = 0, n_rec = 0;
         for (auto& g : groups) {
@@ -436,7 +498,7 @@ static int run_unit_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, int
                 tv[(size_t)at] = t; uv[(size_t)at] = u; read_of[(size_t)at] = w.i;
                 mx = std::max(mx, hm->h.n_cells); ++at; n_rec += w.rec ? 1 : 0;
             }
-            launches.push_back({g.first.second, g.first.first == 0 ? 4 : 1, first, at - first, mx});
+            launches.push_back({{g.first.second, first, at - first, mx}, g.first.first == 0 ? 4 : 1});
         }
         STRQ_HIP(c, hipMemcpyAsync(d_vt, tv.data(), (size_t)m * sizeof(VitTask), hipMemcpyHostToDevice, st));
         STRQ_HIP(c, hipMemcpyAsync(d_paths, pv.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
@@ -447,17 +509,9 @@ static int run_unit_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, int
         STRQ_HIP(c, hipMemsetAsync(c->queue.p, 0, 1024, st));
         int qi = 0;
         for (const L& l : launches) {
-            int* d_order = nullptr;
-            if (l.count <= 8192) {
-                d_order = sl.order.as<int>() + l.first;
-                if (launch_vit_sort(st, d_vt + l.first, l.count, d_order)) { c->err = "sort launch failed"; return STRQ_ERR_DEVICE; }
-            }
-            const int vrc = launch_viterbi(st, l.shape, l.mx, d_vt + l.first, d_vr + l.first, l.count, c->queue.as<int>() + qi++, c->n_cu, l.want, d_order);
-            if (vrc) {
-                c->err = (vrc == 2 || vrc == 3) ? "unit pass: decode mode not available for this model's kernel shape" : "viterbi launch failed";
-                return (vrc == 2 || vrc == 3) ? STRQ_ERR_UNSUPPORTED : STRQ_ERR_DEVICE;
-            }
-            if (l.want == 1 && launch_vit_traceback(st, d_vt + l.first, d_vr + l.first, d_paths + l.first, l.count)) { c->err = "traceback launch failed"; return STRQ_ERR_DEVICE; }
+            if (const int src = sort_viterbi_group(c, st, l.g, d_vt, sl.order.as<int>())) return src;
+            if (const int lrc = launch_viterbi_group(c, st, l.g, d_vt, d_vr, sl.order.as<int>(), c->queue.as<int>() + qi++, l.want, 0, "unit pass: ")) return lrc;
+            if (l.want == 1 && launch_vit_traceback(st, d_vt + l.g.first, d_vr + l.g.first, d_paths + l.g.first, l.g.count)) { c->err = "traceback launch failed"; return STRQ_ERR_DEVICE; }
         }
         if (launch_unit_hop(st, d_ut, n_rec) || launch_unit_scan(st, d_ut + n_rec, m - n_rec)) { c->err = "unit position launch failed"; return STRQ_ERR_DEVICE; }
         std::vector<int64_t> pos(xo + 1); std::vector<int32_t> bad((size_t)m);
@@ -577,58 +631,63 @@ static void publish_timing(strq_ctx* c, const Batch& B)
     c->timing[3] = B.t_lut + B.t_fwd + B.t_trace + B.t_cond + B.t_vit; c->timing[4] = (float)B.n_hard; c->timing[7] = (float)B.n_fwd_launches;
 }
 
-// Queues the Viterbi launches of a sub-batch whose forward stage is complete (sort by window length, one persistent launch per kernel
-// shape, results to pinned host memory) on `vs`, behind `after` when given.
-static int launch_viterbi_of(strq_ctx* c, DetectState* d, DetectState::Slot& sl, hipStream_t vs, hipEvent_t after)
+// A slot whose sub-batch cannot be completed: Idle, and the rows of its reads back at their initial values, so that no later call hands
+// out rows that were never computed.  Returns `rc`, the error of the call that found out.
+static int abandon(DetectState* d, DetectState::Slot& sl, int rc)
 {
-    if (!sl.launch_pending) return STRQ_OK;
-    sl.launch_pending = false;
-    const int nr = sl.nr;
-    VitResult* h_vres = reinterpret_cast<VitResult*>(static_cast<ReadGeom*>(sl.pinned) + nr);
+    Batch& B = d->batch;
+    sl.state = DetectState::Slot::Idle;
+    for (int64_t r = sl.r0; r < sl.r0 + sl.nr && r < (int64_t)B.results.size(); ++r) {
+        B.results[(size_t)r] = strq_result(); B.mod[(size_t)r] = "-";
+        B.units[(size_t)r].clear(); B.unit_dec[(size_t)r] = 0;
+    }
+    return rc;
+}
+
+// the launches of launch_viterbi_of
+static int queue_viterbi_launches(strq_ctx* c, DetectState::Slot& sl, hipStream_t vs, hipEvent_t after)
+{
     if (after) STRQ_HIP(c, hipStreamWaitEvent(vs, after, 0));
     STRQ_HIP(c, hipMemsetAsync(sl.vq.p, 0, 1024, vs));
-    for (auto& v : sl.vls)
-        if (v.count <= 8192 && launch_vit_sort(vs, sl.vit.as<VitTask>() + v.first, v.count, sl.order.as<int>() + v.first)) { c->err = "sort launch failed"; return STRQ_ERR_DEVICE; }
+    for (auto& v : sl.vls) if (const int src = sort_viterbi_group(c, vs, v, sl.vit.as<VitTask>(), sl.order.as<int>())) return src;
     STRQ_HIP(c, hipEventRecord(sl.v0, vs));
     int qi = 0;
     std::memset(c->vit_launches, 0, sizeof(c->vit_launches));
     for (auto& v : sl.vls) {
         ++c->vit_launches[0];
         ++c->vit_launches[(v.shape & ~VIT_SHAPE_SS) == VIT_SHAPE_G2 ? 1 : ((v.shape & ~VIT_SHAPE_SS) == VIT_SHAPE_CSR ? 3 : 2)];
-        int* d_order = v.count <= 8192 ? sl.order.as<int>() + v.first : nullptr;
-        const int rc2 = launch_viterbi(vs, v.shape, v.max_states, sl.vit.as<VitTask>() + v.first, sl.vres.as<VitResult>() + v.first, v.count,
-                                       sl.vq.as<int>() + qi, c->n_cu, sl.vit_mode, d_order, (after && vs != c->stream) ? 4 : 0);
-        if (rc2) {
-            c->err = (rc2 == 2 || rc2 == 3) ? "viterbi: decode mode not available for this model's kernel shape" : "viterbi launch failed";
-            return (rc2 == 2 || rc2 == 3) ? STRQ_ERR_UNSUPPORTED : STRQ_ERR_DEVICE;
-        }
-        ++qi;
+        const int lrc = launch_viterbi_group(c, vs, v, sl.vit.as<VitTask>(), sl.vres.as<VitResult>(), sl.order.as<int>(), sl.vq.as<int>() + qi++,
+                                             sl.vit_mode, (after && vs != c->stream) ? 4 : 0);
+        if (lrc) return lrc;
     }
-    STRQ_HIP(c, hipMemcpyAsync(h_vres, sl.vres.p, (size_t)nr * sizeof(VitResult), hipMemcpyDeviceToHost, vs));
+    STRQ_HIP(c, hipMemcpyAsync(sl.host().vres, sl.vres.p, (size_t)sl.nr * sizeof(VitResult), hipMemcpyDeviceToHost, vs));
     STRQ_HIP(c, hipEventRecord(sl.v1, vs));
     return STRQ_OK;
 }
 
-// Results of a sub-batch whose Viterbi launches were queued earlier: waits for them, fills Batch::results (and runs the
-// modification pass of the sub-batch, which needs the decoded repeat stretch on the host).
-static int harvest(strq_ctx* c, DetectState* d, DetectState::Slot& sl, bool under_current = false)
+// Queues the Viterbi launches of a sub-batch whose forward stage is complete (sort by window length, one persistent launch per kernel
+// shape, results to pinned host memory) on `vs`, behind `after` when given.
+static int launch_viterbi_of(strq_ctx* c, DetectState* d, DetectState::Slot& sl, hipStream_t vs, hipEvent_t after)
 {
-    if (!sl.active) return STRQ_OK;
-    sl.active = false;
+    if (sl.state != DetectState::Slot::Forward) return STRQ_OK;
+    if (const int rc = queue_viterbi_launches(c, sl, vs, after)) return abandon(d, sl, rc);
+    sl.state = DetectState::Slot::Decoding;
+    return STRQ_OK;
+}
+
+// the rows of harvest
+static int take_rows(strq_ctx* c, DetectState* d, DetectState::Slot& sl, bool under_current)
+{
     Batch& B = d->batch;
-    { const int lrc = launch_viterbi_of(c, d, sl, d->vit_stream, nullptr); if (lrc) return lrc; }      // nobody came after this sub-batch
     STRQ_HIP(c, hipEventSynchronize(sl.v1));
     const int nr = sl.nr; const int64_t r0 = sl.r0;
-    const ReadGeom* geom = static_cast<const ReadGeom*>(sl.pinned);
-    const VitResult* vres = reinterpret_cast<const VitResult*>(geom + nr);
-    const ReadCond* rc_out = reinterpret_cast<const ReadCond*>(vres + nr);
-    bool any_mod = false;
+    const DetectState::Slot::Pinned h = sl.host();
     for (int i = 0; i < nr; ++i) {
         strq_result& o = B.results[r0 + i];
         std::memset(&o, 0, sizeof(o));
-        const ReadGeom& g = geom[i];
-        const VitResult& v = vres[sl.vit_slot[i]];
-        o.status = rc_out[i].status == COND_OK ? 0 : 1;
+        const ReadGeom& g = h.geom[i];
+        const VitResult& v = h.vres[sl.vit_slot[i]];
+        o.status = h.rc[i].status == COND_OK ? 0 : 1;
         o.score_prefix = g.score_prefix; o.score_suffix = g.score_suffix;
         o.prefix_begin = g.prefix_begin; o.prefix_end = g.prefix_end; o.suffix_begin = g.suffix_begin; o.suffix_end = g.suffix_end;
         o.offset = g.prefix_end; o.ticks = std::max<int64_t>(g.suffix_begin - g.prefix_end, 0);
@@ -637,7 +696,6 @@ static int harvest(strq_ctx* c, DetectState* d, DetectState::Slot& sl, bool unde
             o.count = (int32_t)v.counted + d->targets[B.target[r0 + i]].count_bias;
             o.log_p = v.logp;
         }
-        any_mod |= d->targets[B.target[r0 + i]].mod_model_id >= 0;
     }
     float ms;
     STRQ_HIP(c, hipEventElapsedTime(&ms, sl.v0, sl.v1)); B.t_vit += ms;
@@ -655,9 +713,21 @@ static int harvest(strq_ctx* c, DetectState* d, DetectState::Slot& sl, bool unde
         c->overlap[3] += 1;
     }
     publish_timing(c, B);
-    if (any_mod) { const int mrc = run_mod_pass(c, d, sl, r0, nr, rc_out, geom, vres, sl.vit_slot); if (mrc) return mrc; }
-    if (sl.units) return run_unit_pass(c, d, sl, r0, nr, geom, vres);
+    // the mode the launches ran with decides, not what the targets say by now
+    if (sl.vit_mode == 2) { const int mrc = run_mod_pass(c, d, sl); if (mrc) return mrc; }
+    if (sl.units) return run_unit_pass(c, d, sl);
     for (int i = 0; i < nr; ++i) { B.units[(size_t)(r0 + i)].clear(); B.unit_dec[(size_t)(r0 + i)] = 0; }
+    return STRQ_OK;
+}
+
+// Results of a sub-batch in flight: queues its Viterbi launches if nobody came after it, waits for them, fills Batch::results (and runs
+// the modification pass of the sub-batch, which needs the decoded repeat stretch on the host, and its unit pass).
+static int harvest(strq_ctx* c, DetectState* d, DetectState::Slot& sl, bool under_current = false)
+{
+    if (sl.state == DetectState::Slot::Idle) return STRQ_OK;
+    if (const int lrc = launch_viterbi_of(c, d, sl, d->vit_stream, nullptr)) return lrc;
+    if (const int rc = take_rows(c, d, sl, under_current)) return abandon(d, sl, rc);
+    sl.state = DetectState::Slot::Idle;
     return STRQ_OK;
 }
 
@@ -668,284 +738,478 @@ static int drain(strq_ctx* c, DetectState* d)
     return STRQ_OK;
 }
 
-static int run_sub_batch(strq_ctx* c, DetectState* d, int64_t r0, int64_t r1, int64_t next_r1)
+int detect_drain(strq_ctx* c) { return c->detect ? drain(c, static_cast<DetectState*>(c->detect)) : STRQ_OK; }
+
+// the Viterbi stream and the events of the pipeline, created once
+static int ensure_sync_objects(strq_ctx* c, DetectState* d)
 {
-    Batch& B = d->batch;
-    hipStream_t st = c->stream;
-    const int nr = (int)(r1 - r0);
-    const int esz = B.dtype == 0 ? 2 : 8;
-    const int64_t s0 = B.off[r0], tot = B.off[r1] - s0;
-    // the slot of this sub-batch (its previous user's results are taken first: normally done a sub-batch ago)
-    DetectState::Slot& sl = d->slot[d->next_slot];
-    DetectState::Slot& other = d->slot[d->next_slot ^ 1];
-    { const int urc = upload_join(d); if (urc) { c->err = "upload of the sub-batch's samples failed (prefetch thread)"; return urc; } }
-    { const int hrc = harvest(c, d, sl); if (hrc) return hrc; }
-    d->next_slot ^= 1;
-    int max_n = 0;
-    std::vector<ReadCond> rc(nr);
-    std::vector<int64_t> loff(nr + 1);
+    for (auto& e : d->ev) if (!e) STRQ_HIP(c, hipEventCreate(&e));
+    for (auto& sl : d->slot) {
+        if (sl.fwd_done) continue;
+        STRQ_HIP(c, hipEventCreateWithFlags(&sl.fwd_done, hipEventDisableTiming));
+        STRQ_HIP(c, hipEventCreate(&sl.v0)); STRQ_HIP(c, hipEventCreate(&sl.v1));
+    }
+    if (!d->vit_stream) {
+        // the older sub-batch's Viterbi launches go first where both streams have workgroups to place
+        int lo = 0, hi = 0;
+        STRQ_HIP(c, hipDeviceGetStreamPriorityRange(&lo, &hi));
+        STRQ_HIP(c, hipStreamCreateWithPriority(&d->vit_stream, hipStreamNonBlocking, hi));
+    }
+    return STRQ_OK;
+}
+
+// what the stages of one run_sub_batch call share
+struct SubBatch {
+    int64_t r0 = 0, s0 = 0, tot = 0;     // first read; its first sample in the batch; samples of the sub-batch
+    int nr = 0, esz = 2;
+    DetectState::Slot* sl = nullptr; DetectState::Slot* other = nullptr;
+    bool any_mod = false, serial = false;
+    std::vector<ReadCond> rc; std::vector<int64_t> loff;      // per read (host): conditioning row, offset in the sub-batch
+    const char* raw = nullptr; char* flt_base = nullptr; uint8_t* levels = nullptr;
+    ReadCond* d_rc = nullptr; uint32_t* d_hist_raw = nullptr; uint32_t* d_range = nullptr;
+    int32_t* d_task_of = nullptr; int32_t* d_trim = nullptr; int32_t* d_slot = nullptr; const VitModel** d_model_of = nullptr;
+};
+
+// stage 1: the ReadCond rows and offsets of the reads (with the caller's statistics, for float64 reads that bring them)
+static void read_table(DetectState* d, SubBatch& S)
+{
+    const Batch& B = d->batch;
+    const int nr = S.nr; const int64_t r0 = S.r0;
+    S.rc.resize(nr); S.loff.resize(nr + 1);
     for (int i = 0; i < nr; ++i) {
-        std::memset(&rc[i], 0, sizeof(ReadCond));
-        rc[i].off = B.off[r0 + i] - s0; rc[i].n = (int)(B.off[r0 + i + 1] - B.off[r0 + i]);
-        loff[i] = rc[i].off;
-        max_n = std::max(max_n, rc[i].n);
+        ReadCond& rc = S.rc[i];
+        std::memset(&rc, 0, sizeof(ReadCond));
+        rc.off = B.off[r0 + i] - S.s0; rc.n = (int)(B.off[r0 + i + 1] - B.off[r0 + i]);
+        S.loff[i] = rc.off;
         if (B.dtype == 1) {
-            rc[i].h2 = (d->ps.M_hi - d->ps.M_lo) / 2; rc[i].c2 = d->ps.M_lo + (d->ps.M_hi - d->ps.M_lo) / 2;
+            rc.h2 = (d->ps.M_hi - d->ps.M_lo) / 2; rc.c2 = d->ps.M_lo + (d->ps.M_hi - d->ps.M_lo) / 2;
         }
         if (B.dtype == 1 && !B.host_stats.empty()) {
             const double* hs = &B.host_stats[(size_t)(r0 + i) * 6];
-            rc[i].med = hs[0]; rc[i].mad = hs[1]; rc[i].f_c1 = hs[2]; rc[i].f_h1 = hs[3]; rc[i].r_c1 = hs[4]; rc[i].r_h1 = hs[5];
+            rc.med = hs[0]; rc.mad = hs[1]; rc.f_c1 = hs[2]; rc.f_h1 = hs[3]; rc.r_c1 = hs[4]; rc.r_h1 = hs[5];
             const bool okv = std::isfinite(hs[0]) && hs[1] > 0.0 && std::isfinite(hs[2]) && hs[3] > 0.0 && std::isfinite(hs[3]);
-            rc[i].status = okv ? COND_OK : COND_DEGENERATE;
+            rc.status = okv ? COND_OK : COND_DEGENERATE;
         }
+        S.any_mod |= d->targets[B.target[r0 + i]].mod_model_id >= 0;
     }
-    loff[nr] = tot;
+    S.loff[nr] = S.tot;
+}
+
+// stage 2: the buffers of the sub-batch, zeroed where the kernels accumulate; the ReadCond rows go up
+static int reserve_buffers(strq_ctx* c, DetectState* d, SubBatch& S)
+{
+    const Batch& B = d->batch;
+    hipStream_t st = c->stream;
+    const int nr = S.nr;
     // both slots are sized together: the first sub-batch on the second slot would otherwise pay a 3 GB hipMalloc in the middle of a run
-    for (DetectState::Slot* q : {&sl, &other}) if (q == &sl || !q->active) STRQ_HIP(c, q->flt.reserve((size_t)tot * esz + 64 + 16));
-    STRQ_HIP(c, c->levels.reserve((size_t)tot + 64 + 8));
+    // (a slot in flight is left alone: its buffers are in use and large enough for what it holds)
+    for (DetectState::Slot* q : {S.sl, S.other})
+        if (q == S.sl || q->state == DetectState::Slot::Idle) { const int rc = q->reserve(c, nr, (size_t)S.tot * S.esz + 64 + 16); if (rc) return rc; }
+    STRQ_HIP(c, c->levels.reserve((size_t)S.tot + 64 + 8));
     STRQ_HIP(c, c->level_val.reserve((size_t)nr * 256 * 4));
     STRQ_HIP(c, d->rc.reserve((size_t)nr * sizeof(ReadCond)));
     STRQ_HIP(c, d->hist8.reserve((size_t)nr * 256 * 4));
     if (B.dtype == 0) STRQ_HIP(c, d->hist16.reserve((size_t)nr * 65536 * 4));
-    ReadCond* d_rc = d->rc.as<ReadCond>();
-    STRQ_HIP(c, hipMemcpyAsync(d_rc, rc.data(), (size_t)nr * sizeof(ReadCond), hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, d->geom.reserve((size_t)nr * sizeof(ReadGeom)));
+    S.d_rc = d->rc.as<ReadCond>();
+    STRQ_HIP(c, hipMemcpyAsync(S.d_rc, S.rc.data(), (size_t)nr * sizeof(ReadCond), hipMemcpyHostToDevice, st));
     STRQ_HIP(c, hipMemsetAsync(d->hist8.p, 0, (size_t)nr * 256 * 4, st));
-    const char* raw = d->batch.raw.as<char>() + (size_t)s0 * esz;
+    S.raw = B.raw.as<char>() + (size_t)S.s0 * S.esz;
     // the filtered signal of the sub-batch starts at the same offset inside a 16-byte line as its raw signal, so that the
     // conditioning kernels can move both with aligned 16-byte accesses
-    char* const flt_base = sl.flt.as<char>() + (reinterpret_cast<uintptr_t>(raw) & 15);
-    bool any_mod = false;
-    for (int i = 0; i < nr; ++i) any_mod |= d->targets[B.target[r0 + i]].mod_model_id >= 0;
-    // STRQ_SERIAL=1: the Viterbi launches on the context's own stream and their results before the call returns, as up to round 5.
-    // (A sub-batch with a modification model is pipelined like any other: its MARK-mode Viterbi launches run under the next sub-batch's
-    // alignments; its second pass -- which needs the decoded repeat stretch on the host -- runs when its rows are taken, on the context's
-    // stream, which is idle then: the taking thread has just waited for the following sub-batch's forward stage, or is the caller's fetch.)
-    const bool serial = strq::opt("STRQ_SERIAL") != nullptr;
-    uint32_t* d_hist_raw = nullptr; uint32_t* d_range = nullptr;
+    S.flt_base = S.sl->flt.as<char>() + (reinterpret_cast<uintptr_t>(S.raw) & 15);
+    // levels: the same sample phase as the raw / filtered signal, so that a tile's eight-level groups are 8-byte aligned
+    d->levels_shift = (int)((reinterpret_cast<uintptr_t>(S.raw) & 15) >> (S.esz == 2 ? 1 : 4));
+    S.levels = c->levels.as<uint8_t>() + d->levels_shift;
     if (B.dtype == 0) {
         STRQ_HIP(c, hipMemsetAsync(d->hist16.p, 0, (size_t)nr * 65536 * 4, st));
-        if (any_mod) {
+        if (S.any_mod) {
             STRQ_HIP(c, d->hist_raw.reserve((size_t)nr * 65536 * 4));
             STRQ_HIP(c, hipMemsetAsync(d->hist_raw.p, 0, (size_t)nr * 65536 * 4, st));
-            d_hist_raw = d->hist_raw.as<uint32_t>();
+            S.d_hist_raw = d->hist_raw.as<uint32_t>();
         }
         STRQ_HIP(c, d->hrange.reserve((size_t)nr * 16));
         STRQ_HIP(c, hipMemsetAsync(d->hrange.p, 0, (size_t)nr * 16, st));
-        d_range = d->hrange.as<uint32_t>();
+        S.d_range = d->hrange.as<uint32_t>();
     }
-    // Viterbi tasks are grouped by kernel shape over the whole sub-batch (windows of all models with one
-    // shape share a launch)
+    const size_t idx_ints = (size_t)nr * 5;        // task_of (2 per read), trim (2 per read), vit_slot
+    STRQ_HIP(c, d->idx.reserve(idx_ints * 4 + (size_t)nr * 8 + 64));
+    S.d_task_of = d->idx.as<int32_t>(); S.d_trim = S.d_task_of + 2 * (size_t)nr; S.d_slot = S.d_trim + 2 * (size_t)nr;
+    S.d_model_of = reinterpret_cast<const VitModel**>(d->idx.as<char>() + ((idx_ints * 4 + 15) & ~(size_t)15));
+    return STRQ_OK;
+}
+
+// stage 3: the Viterbi launches of the sub-batch.  Tasks are grouped by kernel shape over the whole sub-batch (windows of all models
+// with one shape share a launch); finalize_kernel writes the task of read i to position vit_slot[i].
+static int plan_viterbi(strq_ctx* c, DetectState* d, SubBatch& S)
+{
+    const Batch& B = d->batch;
+    DetectState::Slot& sl = *S.sl;
+    const int nr = S.nr;
     std::map<int, std::vector<int>> by_shape;
     std::vector<const VitModel*> model_of(nr);
     for (int i = 0; i < nr; ++i) {
-        HostModel* hm = c->models[d->targets[B.target[r0 + i]].model_id];
+        HostModel* hm = c->models[d->targets[B.target[S.r0 + i]].model_id];
         model_of[i] = hm->dev;
-        const int shape = vit_shape_for(hm->h, any_mod ? 2 : 0);
+        const int shape = vit_shape_for(hm->h, S.any_mod ? 2 : 0);
         if (shape < 0) { c->err = "model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
         by_shape[shape].push_back(i);
     }
-    std::vector<int32_t>& vit_slot = sl.vit_slot;
-    vit_slot.assign(nr, 0);
-    std::vector<DetectState::Slot::VL>& vls = sl.vls;
-    vls.clear();
-    { int k = 0;
-      for (auto& g : by_shape) {
+    sl.vit_slot.assign(nr, 0);
+    sl.vls.clear();
+    int k = 0;
+    for (auto& g : by_shape) {
         int mx = 0;
-        for (int i : g.second) mx = std::max(mx, c->models[d->targets[B.target[r0 + i]].model_id]->h.n_cells);
-        vls.push_back({g.first, k, (int)g.second.size(), mx});
-        for (int i : g.second) vit_slot[i] = k++;
-      } }
-    const size_t idx_ints = (size_t)nr * 5;        // task_of (2 per read), trim (2 per read), vit_slot
-    STRQ_HIP(c, d->idx.reserve(idx_ints * 4 + (size_t)nr * 8 + 64));
-    int32_t* d_task_of = d->idx.as<int32_t>(); int32_t* d_trim = d_task_of + 2 * (size_t)nr; int32_t* d_slot = d_trim + 2 * (size_t)nr;
-    const VitModel** d_model_of = reinterpret_cast<const VitModel**>(d->idx.as<char>() + ((idx_ints * 4 + 15) & ~(size_t)15));
-    STRQ_HIP(c, hipMemcpyAsync(d_model_of, model_of.data(), (size_t)nr * 8, hipMemcpyHostToDevice, st));
-    STRQ_HIP(c, hipMemcpyAsync(d_slot, vit_slot.data(), (size_t)nr * 4, hipMemcpyHostToDevice, st));
-    STRQ_HIP(c, d->geom.reserve((size_t)nr * sizeof(ReadGeom)));
-    for (DetectState::Slot* q : {&sl, &other}) {
-        if (q != &sl && q->active) continue;          // (in flight: its buffers are in use and large enough for what it holds)
-        STRQ_HIP(c, q->vit.reserve((size_t)nr * sizeof(VitTask)));
-        STRQ_HIP(c, q->vres.reserve((size_t)nr * sizeof(VitResult)));
-        STRQ_HIP(c, q->order.reserve((size_t)nr * 4 + 64));
-        STRQ_HIP(c, q->vq.reserve(1024));
-        const size_t need = (size_t)nr * (sizeof(ReadGeom) + sizeof(VitResult) + sizeof(ReadCond)) + 64;
-        if (need > q->pinned_cap) {
-            if (q->pinned) { STRQ_HIP(c, hipHostFree(q->pinned)); q->pinned = nullptr; q->pinned_cap = 0; }
-            STRQ_HIP(c, hipHostMalloc(&q->pinned, need + need / 8, hipHostMallocDefault));
-            q->pinned_cap = need + need / 8;
-        }
-        if (!q->fwd_done) {
-            STRQ_HIP(c, hipEventCreateWithFlags(&q->fwd_done, hipEventDisableTiming));
-            STRQ_HIP(c, hipEventCreate(&q->v0)); STRQ_HIP(c, hipEventCreate(&q->v1));
-        }
+        for (int i : g.second) mx = std::max(mx, c->models[d->targets[B.target[S.r0 + i]].model_id]->h.n_cells);
+        sl.vls.push_back({g.first, k, (int)g.second.size(), mx});
+        for (int i : g.second) sl.vit_slot[i] = k++;
     }
-    {
-        if (!d->vit_stream) {
-            // the older sub-batch's Viterbi launches go first where both streams have workgroups to place
-            int lo = 0, hi = 0;
-            STRQ_HIP(c, hipDeviceGetStreamPriorityRange(&lo, &hi));
-            const char* e = strq::opt("STRQ_VIT_PRIORITY");
-            STRQ_HIP(c, hipStreamCreateWithPriority(&d->vit_stream, hipStreamNonBlocking, (e && atoi(e) == 0) ? lo : hi));
+    STRQ_HIP(c, hipMemcpyAsync(S.d_model_of, model_of.data(), (size_t)nr * 8, hipMemcpyHostToDevice, c->stream));
+    STRQ_HIP(c, hipMemcpyAsync(S.d_slot, sl.vit_slot.data(), (size_t)nr * 4, hipMemcpyHostToDevice, c->stream));
+    return STRQ_OK;
+}
+
+// per upload part, reads [i0, i0 + np) of the sub-batch: conditioning (STRique.py:590-597)
+static int condition_part(strq_ctx* c, DetectState* d, const SubBatch& S, int i0, int np)
+{
+    const Batch& B = d->batch;
+    hipStream_t st = c->stream;
+    ReadCond* d_rc = S.d_rc + i0;
+    int longest = 0;
+    for (int i = i0; i < i0 + np; ++i) longest = std::max(longest, S.rc[i].n);
+    int bad = 0;
+    float* level_val = c->level_val.as<float>() + (size_t)i0 * 256;
+    uint32_t* hist8 = d->hist8.as<uint32_t>() + (size_t)i0 * 256;
+    if (B.dtype == 0) {
+        uint32_t* h16 = d->hist16.as<uint32_t>() + (size_t)i0 * 65536;
+        uint32_t* hraw = S.d_hist_raw ? S.d_hist_raw + (size_t)i0 * 65536 : nullptr;
+        uint32_t* rng = S.d_range + (size_t)i0 * 4;
+        bad |= launch_medfilt_hist_i16(st, reinterpret_cast<const int16_t*>(S.raw), reinterpret_cast<int16_t*>(S.flt_base), d_rc, np, longest, h16, hraw, rng);
+        bad |= launch_hist_stats(st, h16, 65536, -32768, d_rc, np, d->ps, 0, nullptr, rng, 4);
+        if (S.any_mod) bad |= launch_hist_stats(st, hraw, 65536, -32768, d_rc, np, d->ps, 2, nullptr, rng + 2, 4);
+        bad |= launch_quant_morph_i16(st, reinterpret_cast<const int16_t*>(S.flt_base), S.levels, d_rc, np, longest, hist8);
+    } else {
+        bad |= launch_medfilt_f64(st, reinterpret_cast<const double*>(S.raw), reinterpret_cast<double*>(S.flt_base), d_rc, np, longest);
+        if (B.host_stats.empty()) {
+            // median, MAD and the two 'minmax' maps of every read: one double of scratch per 8192 samples (numpy's mean)
+            std::vector<int64_t> first((size_t)np + 1, 0);
+            for (int i = 0; i < np; ++i) first[(size_t)i + 1] = first[(size_t)i] + (S.rc[i0 + i].n + 8191) / 8192;
+            const size_t first_bytes = (((size_t)np + 1) * 8 + 255) & ~(size_t)255;
+            STRQ_HIP(c, d->f64s.reserve(first_bytes + (size_t)first[(size_t)np] * 8 + 256));
+            STRQ_HIP(c, hipMemcpyAsync(d->f64s.p, first.data(), ((size_t)np + 1) * 8, hipMemcpyHostToDevice, st));
+            bad |= launch_f64_stats(st, reinterpret_cast<const double*>(S.flt_base), S.any_mod ? reinterpret_cast<const double*>(S.raw) : nullptr, d_rc, np,
+                                    reinterpret_cast<double*>(d->f64s.as<char>() + first_bytes), d->f64s.as<int64_t>());
         }
+        bad |= launch_quant_morph_f64(st, reinterpret_cast<const double*>(S.flt_base), S.levels, d_rc, np, longest, hist8);
     }
-    ReadGeom* h_geom = static_cast<ReadGeom*>(sl.pinned);
-    VitResult* h_vres = reinterpret_cast<VitResult*>(h_geom + nr);
-    ReadCond* h_rc = reinterpret_cast<ReadCond*>(h_vres + nr);
-    unsigned int* h_redo = reinterpret_cast<unsigned int*>(h_rc + nr);
+    bad |= launch_hist_stats(st, hist8, 256, 0, d_rc, np, d->ps, 1, level_val, nullptr, 0);
+    if (bad) { c->err = "conditioning launch failed"; return STRQ_ERR_DEVICE; }
+    return STRQ_OK;
+}
 
-    // Conditioning, the two flank alignments and the positions / gate of the reads, in `parts` pieces: a
-    // sub-batch whose samples are still in the caller's buffer is uploaded piece by piece, each piece's
-    // kernels running under the upload of the next (only the first piece's upload is exposed); a resident
-    // or prefetched sub-batch is one piece.  The Viterbi launches below always cover the whole sub-batch.
-    int parts = 1;
-    if (B.on_host && B.uploaded < r1 && nr >= 1024) { parts = 2; if (const char* e = strq::opt("STRQ_UPLOAD_PARTS")) { const int v = atoi(e); if (v >= 1 && v <= 16) parts = v; } }
-    for (int part = 0; part < parts; ++part) {
-        const int i0 = (int)((int64_t)nr * part / parts), i1 = (int)((int64_t)nr * (part + 1) / parts), np_ = i1 - i0;
-        if (np_ <= 0) continue;
-        { const int urc = upload_reads(c, d, r0 + i1); if (urc) return urc; }
-        // this sub-batch's samples are in HBM (or queued): the next sub-batch's follow on their own thread from here on
-        if (part == parts - 1) upload_prefetch(c, d, next_r1);
-        int max_n = 0;
-        for (int i = i0; i < i1; ++i) max_n = std::max(max_n, rc[i].n);
-        if (part == 0) STRQ_HIP(c, hipEventRecord(d->ev[0], st));
-        // ---- conditioning (STRique.py:590-597)
-        int bad = 0;
-        // levels: the same sample phase as the raw / filtered signal, so that a tile's eight-level groups are 8-byte aligned
-        d->levels_shift = (int)((reinterpret_cast<uintptr_t>(raw) & 15) >> (esz == 2 ? 1 : 4));
-        uint8_t* levels = c->levels.as<uint8_t>() + d->levels_shift;
-        float* level_val = c->level_val.as<float>() + (size_t)i0 * 256;
-        uint32_t* hist8 = d->hist8.as<uint32_t>() + (size_t)i0 * 256;
-        if (B.dtype == 0) {
-            uint32_t* h16 = d->hist16.as<uint32_t>() + (size_t)i0 * 65536;
-            uint32_t* hraw = d_hist_raw ? d_hist_raw + (size_t)i0 * 65536 : nullptr;
-            uint32_t* rng = d_range + (size_t)i0 * 4;
-            bad |= launch_medfilt_hist_i16(st, reinterpret_cast<const int16_t*>(raw), reinterpret_cast<int16_t*>(flt_base), d_rc + i0, np_, max_n, h16, hraw, rng);
-            bad |= launch_hist_stats(st, h16, 65536, -32768, d_rc + i0, np_, d->ps, 0, nullptr, rng, 4);
-            if (any_mod) bad |= launch_hist_stats(st, hraw, 65536, -32768, d_rc + i0, np_, d->ps, 2, nullptr, rng + 2, 4);
-            bad |= launch_quant_morph_i16(st, reinterpret_cast<const int16_t*>(flt_base), levels, d_rc + i0, np_, max_n, hist8);
-        } else {
-            bad |= launch_medfilt_f64(st, reinterpret_cast<const double*>(raw), reinterpret_cast<double*>(flt_base), d_rc + i0, np_, max_n);
-            if (B.host_stats.empty()) {
-                // median, MAD and the two 'minmax' maps of every read: one double of scratch per 8192 samples (numpy's mean)
-                std::vector<int64_t> first((size_t)np_ + 1, 0);
-                for (int i = 0; i < np_; ++i) first[(size_t)i + 1] = first[(size_t)i] + (rc[i0 + i].n + 8191) / 8192;
-                const size_t first_bytes = (((size_t)np_ + 1) * 8 + 255) & ~(size_t)255;
-                STRQ_HIP(c, d->f64s.reserve(first_bytes + (size_t)first[(size_t)np_] * 8 + 256));
-                STRQ_HIP(c, hipMemcpyAsync(d->f64s.p, first.data(), ((size_t)np_ + 1) * 8, hipMemcpyHostToDevice, st));
-                bad |= launch_f64_stats(st, reinterpret_cast<const double*>(flt_base), any_mod ? reinterpret_cast<const double*>(raw) : nullptr, d_rc + i0, np_,
-                                        reinterpret_cast<double*>(d->f64s.as<char>() + first_bytes), d->f64s.as<int64_t>());
-            }
-            bad |= launch_quant_morph_f64(st, reinterpret_cast<const double*>(flt_base), levels, d_rc + i0, np_, max_n, hist8);
-        }
-        bad |= launch_hist_stats(st, hist8, 256, 0, d_rc + i0, np_, d->ps, 1, level_val, nullptr, 0);
-        if (bad) { c->err = "conditioning launch failed"; return STRQ_ERR_DEVICE; }
-        if (part == 0) STRQ_HIP(c, hipEventRecord(d->ev[1], st));
-
-        // ---- the two flank alignments of every read
-        const int na = 2 * np_;
-        std::vector<int32_t> a_read(na); std::vector<int> n(na), m(na), k(na), R(na), NS(na); std::vector<const float*> fl(na);
-        std::vector<int32_t> trim(na);
-        int S = 6;
-        for (int j = 0; j < np_; ++j) {
-            const Target& t = d->targets[B.target[r0 + i0 + j]];
-            S = t.samples;
-            a_read[2 * j] = a_read[2 * j + 1] = j;
-            n[2 * j] = n[2 * j + 1] = rc[i0 + j].n;
-            m[2 * j] = (int)t.prefix_ext.size(); k[2 * j] = t.kp; R[2 * j] = t.Rp; NS[2 * j] = t.NSp; fl[2 * j] = t.prefix_ext.data(); trim[2 * j] = t.trim_prefix;
-            m[2 * j + 1] = (int)t.suffix_ext.size(); k[2 * j + 1] = t.ks; R[2 * j + 1] = t.Rs; NS[2 * j + 1] = t.NSs; fl[2 * j + 1] = t.suffix_ext.data(); trim[2 * j + 1] = t.trim_suffix;
-        }
-        AlignCoreIn ci; AlignCoreOut co;
-        ci.nb = na; ci.samples = S; ci.d_levels = levels; ci.read_off = loff.data() + i0; ci.d_level_val = level_val;
-        ci.read = a_read.data(); ci.n = n.data(); ci.m = m.data(); ci.k = k.data(); ci.R = R.data(); ci.NS = NS.data(); ci.flank = fl.data();
-        // (Launched behind this sub-batch's SCREEN instead -- under the exact pass and the trace, whose launches leave most of the GPU idle --
-        // the eight Viterbi waves per CU take the LDS and registers those launches need: exact pass 69 instead of 19 ms, 180 against 175 ms per
-        // step on clean reads, 400 against 338 on empirical ones: gpurun_out/r6r.)
-        if (part == 0) ci.after_tables = [&]() -> int {
-            // The sub-batch before this one: its Viterbi launches start when this sub-batch's conditioning and score tables are through
-            // -- a few ms of HBM-bound streaming kernels that crawl next to a GPU full of Viterbi waves (gpurun_out/r6d: 66 ms instead
-            // of 5.7 ms; hist_stats_kernel alone keeps 60 KB of LDS per workgroup), and queued before the table kernel the Viterbi
-            // launch kept the next screen from being dispatched until it had ended (gpurun_out/r6h against r6i, measured, both
-            // priorities).  The alignment kernels that follow share the SIMDs with the Viterbi waves.
-            const bool queued_now = other.launch_pending;
-            const int lrc = launch_viterbi_of(c, d, other, d->vit_stream, c->ev[1]); if (lrc) return lrc;
-            // ... and they are dispatched after them: persistent workgroups that fill every CU for the length of the screen would
-            // otherwise win the race now and then, and the Viterbi workgroups (eight waves of 192 VGPRs each: a whole CU's worth at
-            // once) could not be placed before the screen has ended -- the serial order again
-            if (queued_now) STRQ_HIP(c, hipStreamWaitEvent(st, other.v0, 0));
-            return STRQ_OK;
-        };
-        const int rcode = align_core(c, ci, co);
-        if (rcode) return rcode;
-        B.n_hard += co.n_hard; B.n_fwd_launches += co.n_launches;
-        c->counters[0] += co.wave_steps; c->counters[1] += co.columns; c->counters[2] += na;
-        c->counters[3] = co.segs; c->counters[4] = co.tables; c->counters[5] = co.packed; c->counters[6] = co.rows_per_lane;
-
-        // ---- positions, gate, Viterbi tasks
-        std::vector<int32_t> task_of(na);
-        for (int pos = 0; pos < na; ++pos) task_of[co.order[pos]] = pos;
-        STRQ_HIP(c, hipMemcpyAsync(d_task_of + 2 * (size_t)i0, task_of.data(), (size_t)na * 4, hipMemcpyHostToDevice, st));
-        STRQ_HIP(c, hipMemcpyAsync(d_trim + 2 * (size_t)i0, trim.data(), (size_t)na * 4, hipMemcpyHostToDevice, st));
-        FinalizeArgs fa;
-        fa.tasks = co.d_tasks; fa.results = co.d_results; fa.task_of = d_task_of + 2 * (size_t)i0; fa.trim = d_trim + 2 * (size_t)i0; fa.vit_slot = d_slot + i0;
-        fa.rc = d_rc + i0; fa.model_of = d_model_of + i0; fa.flt = flt_base; fa.is_f64 = B.dtype; fa.ps = d->ps;
-        fa.geom = d->geom.as<ReadGeom>() + i0; fa.vit = sl.vit.as<VitTask>(); fa.n_reads = np_;
-        hipLaunchKernelGGL(finalize_kernel, dim3((np_ + 127) / 128), dim3(128), 0, st, fa);
-        STRQ_HIP(c, hipGetLastError());
+// per upload part: the two flank alignments of every read.  The first part's score-table kernel is where the Viterbi launches of the
+// sub-batch before this one are queued.
+static int align_part(strq_ctx* c, DetectState* d, const SubBatch& S, int i0, int np, bool first_part, AlignCoreOut& co, std::vector<int32_t>& trim)
+{
+    Batch& B = d->batch;
+    hipStream_t st = c->stream;
+    DetectState::Slot& other = *S.other;
+    const int na = 2 * np;
+    std::vector<int32_t> a_read(na); std::vector<int> n(na), m(na), k(na), R(na), NS(na); std::vector<const float*> fl(na);
+    trim.resize(na);
+    int samples = 6;
+    for (int j = 0; j < np; ++j) {
+        const Target& t = d->targets[B.target[S.r0 + i0 + j]];
+        samples = t.samples;
+        a_read[2 * j] = a_read[2 * j + 1] = j;
+        n[2 * j] = n[2 * j + 1] = S.rc[i0 + j].n;
+        m[2 * j] = (int)t.prefix_ext.size(); k[2 * j] = t.kp; R[2 * j] = t.Rp; NS[2 * j] = t.NSp; fl[2 * j] = t.prefix_ext.data(); trim[2 * j] = t.trim_prefix;
+        m[2 * j + 1] = (int)t.suffix_ext.size(); k[2 * j + 1] = t.ks; R[2 * j + 1] = t.Rs; NS[2 * j + 1] = t.NSs; fl[2 * j + 1] = t.suffix_ext.data(); trim[2 * j + 1] = t.trim_suffix;
     }
-    // positions and conditioning status of the sub-batch to the host (pinned: the copies do not block), then the fork: everything the
-    // Viterbi launches read is final behind `fwd_done`
-    STRQ_HIP(c, hipMemcpyAsync(h_geom, d->geom.p, (size_t)nr * sizeof(ReadGeom), hipMemcpyDeviceToHost, st));
-    STRQ_HIP(c, hipMemcpyAsync(h_rc, d_rc, (size_t)nr * sizeof(ReadCond), hipMemcpyDeviceToHost, st));
-    *h_redo = 0;
-    if (c->redo_total.p) STRQ_HIP(c, hipMemcpyAsync(h_redo, c->redo_total.p, 4, hipMemcpyDeviceToHost, st));
+    AlignCoreIn ci;
+    ci.nb = na; ci.samples = samples; ci.d_levels = S.levels; ci.read_off = S.loff.data() + i0; ci.d_level_val = c->level_val.as<float>() + (size_t)i0 * 256;
+    ci.read = a_read.data(); ci.n = n.data(); ci.m = m.data(); ci.k = k.data(); ci.R = R.data(); ci.NS = NS.data(); ci.flank = fl.data();
+    // (Launched behind this sub-batch's SCREEN instead -- under the exact pass and the trace, whose launches leave most of the GPU idle --
+    // the eight Viterbi waves per CU take the LDS and registers those launches need: exact pass 69 instead of 19 ms, 180 against 175 ms per
+    // step on clean reads, 400 against 338 on empirical ones: gpurun_out/r6r.)
+    if (first_part) ci.after_tables = [&]() -> int {
+        // The sub-batch before this one: its Viterbi launches start when this sub-batch's conditioning and score tables are through
+        // -- a few ms of HBM-bound streaming kernels that crawl next to a GPU full of Viterbi waves (gpurun_out/r6d: 66 ms instead
+        // of 5.7 ms; hist_stats_kernel alone keeps 60 KB of LDS per workgroup), and queued before the table kernel the Viterbi
+        // launch kept the next screen from being dispatched until it had ended (gpurun_out/r6h against r6i, measured, both
+        // priorities).  The alignment kernels that follow share the SIMDs with the Viterbi waves.
+        const bool queued_now = other.state == DetectState::Slot::Forward;
+        const int lrc = launch_viterbi_of(c, d, other, d->vit_stream, c->ev[1]); if (lrc) return lrc;
+        // ... and they are dispatched after them: persistent workgroups that fill every CU for the length of the screen would
+        // otherwise win the race now and then, and the Viterbi workgroups (eight waves of 192 VGPRs each: a whole CU's worth at
+        // once) could not be placed before the screen has ended -- the serial order again
+        if (queued_now) STRQ_HIP(c, hipStreamWaitEvent(st, other.v0, 0));
+        return STRQ_OK;
+    };
+    const int rcode = align_core(c, ci, co);
+    if (rcode) return rcode;
+    B.n_hard += co.n_hard; B.n_fwd_launches += co.n_launches;
+    c->counters[0] += co.wave_steps; c->counters[1] += co.columns; c->counters[2] += na;
+    c->counters[3] = co.segs; c->counters[4] = co.tables; c->counters[5] = co.packed; c->counters[6] = co.rows_per_lane;
+    return STRQ_OK;
+}
+
+// per upload part: positions, gate and Viterbi tasks of its reads
+static int finalize_part(strq_ctx* c, DetectState* d, const SubBatch& S, int i0, int np, const AlignCoreOut& co, const std::vector<int32_t>& trim)
+{
+    hipStream_t st = c->stream;
+    const int na = 2 * np;
+    std::vector<int32_t> task_of(na);
+    for (int pos = 0; pos < na; ++pos) task_of[co.order[pos]] = pos;
+    STRQ_HIP(c, hipMemcpyAsync(S.d_task_of + 2 * (size_t)i0, task_of.data(), (size_t)na * 4, hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, hipMemcpyAsync(S.d_trim + 2 * (size_t)i0, trim.data(), (size_t)na * 4, hipMemcpyHostToDevice, st));
+    FinalizeArgs fa;
+    fa.tasks = co.d_tasks; fa.results = co.d_results; fa.task_of = S.d_task_of + 2 * (size_t)i0; fa.trim = S.d_trim + 2 * (size_t)i0; fa.vit_slot = S.d_slot + i0;
+    fa.rc = S.d_rc + i0; fa.model_of = S.d_model_of + i0; fa.flt = S.flt_base; fa.is_f64 = d->batch.dtype; fa.ps = d->ps;
+    fa.geom = d->geom.as<ReadGeom>() + i0; fa.vit = S.sl->vit.as<VitTask>(); fa.n_reads = np;
+    hipLaunchKernelGGL(finalize_kernel, dim3((np + 127) / 128), dim3(128), 0, st, fa);
+    STRQ_HIP(c, hipGetLastError());
+    return STRQ_OK;
+}
+
+// the forward stage is queued: positions and conditioning status of the sub-batch to the host (pinned: the copies do not block), then
+// the fork: everything the Viterbi launches read is final behind `fwd_done`
+static int publish_forward(strq_ctx* c, DetectState* d, const SubBatch& S)
+{
+    DetectState::Slot& sl = *S.sl;
+    hipStream_t st = c->stream;
+    const DetectState::Slot::Pinned h = sl.host();
+    STRQ_HIP(c, hipMemcpyAsync(h.geom, d->geom.p, (size_t)S.nr * sizeof(ReadGeom), hipMemcpyDeviceToHost, st));
+    STRQ_HIP(c, hipMemcpyAsync(h.rc, S.d_rc, (size_t)S.nr * sizeof(ReadCond), hipMemcpyDeviceToHost, st));
+    *h.redo = 0;
+    if (c->redo_total.p) STRQ_HIP(c, hipMemcpyAsync(h.redo, c->redo_total.p, 4, hipMemcpyDeviceToHost, st));
     STRQ_HIP(c, hipEventRecord(sl.fwd_done, st));
-    sl.vit_mode = any_mod ? 2 : 0;
+    sl.vit_mode = S.any_mod ? 2 : 0;
     sl.units = d->units_on;
-    sl.active = true; sl.launch_pending = true; sl.r0 = r0; sl.nr = nr;
+    sl.state = DetectState::Slot::Forward;
+    return STRQ_OK;
+}
+
+// score distribution of this sub-batch for the overlap planning of the next one (align_core)
+static void plan_next_overlap(strq_ctx* c, DetectState* d, const SubBatch& S)
+{
+    if (!(c->ap.dist_offset > 0.0f)) return;
+    const ReadGeom* h_geom = S.sl->host().geom;
+    c->score_fracs.clear(); double sum_n = 0;
+    for (int i = 0; i < S.nr; ++i) {
+        if (S.rc[i].n <= 0) continue;
+        const Target& t = d->targets[d->batch.target[S.r0 + i]];
+        c->score_fracs.push_back(h_geom[i].best_prefix / ((float)t.prefix_ext.size() * c->ap.dist_offset));
+        c->score_fracs.push_back(h_geom[i].best_suffix / ((float)t.suffix_ext.size() * c->ap.dist_offset));
+        sum_n += S.rc[i].n;
+    }
+    std::sort(c->score_fracs.begin(), c->score_fracs.end());
+    c->mean_n = c->score_fracs.empty() ? 0.0 : sum_n / (double)(c->score_fracs.size() / 2);
+}
+
+// What follows the published forward stage: the Viterbi launches in the serial order, the wait for the forward stage, the planning of
+// the next sub-batch, the times, and the rows that are due.
+static int complete_sub_batch(strq_ctx* c, DetectState* d, const SubBatch& S)
+{
+    Batch& B = d->batch;
+    DetectState::Slot& sl = *S.sl; DetectState::Slot& other = *S.other;
     // The Viterbi launches of this sub-batch: now on the context's stream (serial order), or -- two sub-batches in flight -- behind the
     // conditioning of the NEXT sub-batch (launch_viterbi_of from there), at the latest when somebody asks for the rows.  Conditioning is a
     // few ms of HBM-bound streaming kernels that crawl next to a GPU full of Viterbi waves (gpurun_out/r6d: 66 ms instead of 5.7 ms); the
     // flank-alignment kernels that follow share the SIMDs with them at little cost.
-    if (serial) { const int lrc = launch_viterbi_of(c, d, sl, st, nullptr); if (lrc) return lrc; }
+    if (S.serial) { const int lrc = launch_viterbi_of(c, d, sl, c->stream, nullptr); if (lrc) return lrc; }
     // the forward stage of this sub-batch is complete here (its Viterbi launches need not be)
     STRQ_HIP(c, hipEventSynchronize(sl.fwd_done));
-    c->second_round[0] = (int64_t)*h_redo - c->look2_served; c->second_round[1] += 2 * (int64_t)nr;
-    // score distribution of this sub-batch for the overlap planning of the next one (align_core)
-    if (c->ap.dist_offset > 0.0f) {
-        c->score_fracs.clear(); double sum_n = 0;
-        for (int i = 0; i < nr; ++i) {
-            if (rc[i].n <= 0) continue;
-            const Target& t = d->targets[B.target[r0 + i]];
-            c->score_fracs.push_back(h_geom[i].best_prefix / ((float)t.prefix_ext.size() * c->ap.dist_offset));
-            c->score_fracs.push_back(h_geom[i].best_suffix / ((float)t.suffix_ext.size() * c->ap.dist_offset));
-            sum_n += rc[i].n;
-        }
-        std::sort(c->score_fracs.begin(), c->score_fracs.end());
-        c->mean_n = c->score_fracs.empty() ? 0.0 : sum_n / (double)(c->score_fracs.size() / 2);
-    }
+    c->second_round[0] = (int64_t)*sl.host().redo - c->look2_served; c->second_round[1] += 2 * (int64_t)S.nr;
+    plan_next_overlap(c, d, S);
     float ms;
     STRQ_HIP(c, hipEventElapsedTime(&ms, d->ev[0], d->ev[1])); B.t_cond += ms;
     const int rcode = align_core_times(c, &B.t_lut, &B.t_fwd, &B.t_trace);      // of the last piece when the sub-batch ran in pieces
     if (rcode) return rcode;
     // results: of the sub-batch before this one (its Viterbi launches ran under this sub-batch's forward stage) -- or, serially, of this one
-    if (strq::opt("STRQ_DEBUG") && !serial && other.active && !other.launch_pending && c->screen_ran) {
+    if (strq::opt("STRQ_DEBUG") && !S.serial && other.state == DetectState::Slot::Decoding && c->screen_ran) {
         float a = 0, b = 0, e = 0;
         (void)hipEventSynchronize(other.v1);
         (void)hipEventElapsedTime(&a, other.v0, c->ev[5]); (void)hipEventElapsedTime(&e, other.v0, c->ev[6]); (void)hipEventElapsedTime(&b, other.v0, other.v1);
         STRQ_DBG("overlap: Viterbi launches of the previous sub-batch start at 0, end at %.1f ms; this sub-batch's screen runs from %.1f to %.1f ms", b, a, e);
     }
-    if (serial) return harvest(c, d, sl);
+    if (S.serial) return harvest(c, d, sl);
     return harvest(c, d, other, /*under_current=*/true);
 }
 
+static int run_sub_batch(strq_ctx* c, DetectState* d, int64_t r0, int64_t r1, int64_t next_r1)
+{
+    Batch& B = d->batch;
+    SubBatch S;
+    S.r0 = r0; S.nr = (int)(r1 - r0); S.esz = B.dtype == 0 ? 2 : 8;
+    S.s0 = B.off[r0]; S.tot = B.off[r1] - S.s0;
+    // the slot of this sub-batch (its previous user's results are taken first: normally done a sub-batch ago)
+    DetectState::Slot& sl = d->slot[d->next_slot];
+    S.sl = &sl; S.other = &d->slot[d->next_slot ^ 1];
+    { const int urc = upload_join(d); if (urc) { c->err = "upload of the sub-batch's samples failed (prefetch thread)"; return urc; } }
+    { const int hrc = harvest(c, d, sl); if (hrc) return hrc; }
+    d->next_slot ^= 1;
+    sl.r0 = r0; sl.nr = S.nr;
+    // STRQ_SERIAL=1: the Viterbi launches on the context's own stream and their results before the call returns, as up to round 5.
+    // (A sub-batch with a modification model is pipelined like any other: its MARK-mode Viterbi launches run under the next sub-batch's
+    // alignments; its second pass -- which needs the decoded repeat stretch on the host -- runs when its rows are taken, on the context's
+    // stream, which is idle then: the taking thread has just waited for the following sub-batch's forward stage, or is the caller's fetch.)
+    S.serial = strq::opt("STRQ_SERIAL") != nullptr;
+    read_table(d, S);
+    if (const int rc = reserve_buffers(c, d, S)) return rc;
+    if (const int rc = plan_viterbi(c, d, S)) return rc;
+    // Conditioning, the two flank alignments and the positions / gate of the reads, in `parts` pieces: a
+    // sub-batch whose samples are still in the caller's buffer is uploaded piece by piece, each piece's
+    // kernels running under the upload of the next (only the first piece's upload is exposed); a resident
+    // or prefetched sub-batch is one piece.  The Viterbi launches always cover the whole sub-batch.
+    const int parts = (B.on_host && B.uploaded < r1 && S.nr >= 1024) ? 2 : 1;
+    for (int part = 0; part < parts; ++part) {
+        const int i0 = (int)((int64_t)S.nr * part / parts), i1 = (int)((int64_t)S.nr * (part + 1) / parts), np = i1 - i0;
+        if (np <= 0) continue;
+        if (const int urc = upload_reads(c, d, r0 + i1)) return urc;
+        // this sub-batch's samples are in HBM (or queued): the next sub-batch's follow on their own thread from here on
+        if (part == parts - 1) upload_prefetch(c, d, next_r1);
+        if (part == 0) STRQ_HIP(c, hipEventRecord(d->ev[0], c->stream));
+        if (const int rc = condition_part(c, d, S, i0, np)) return rc;
+        if (part == 0) STRQ_HIP(c, hipEventRecord(d->ev[1], c->stream));
+        AlignCoreOut co; std::vector<int32_t> trim;
+        if (const int rc = align_part(c, d, S, i0, np, part == 0, co, trim)) return rc;
+        if (const int rc = finalize_part(c, d, S, i0, np, co, trim)) return rc;
+    }
+    if (const int rc = publish_forward(c, d, S)) return rc;
+    // from here on the slot is in flight: a failure leaves no rows behind that were not computed
+    if (const int rc = complete_sub_batch(c, d, S)) return abandon(d, sl, rc);
+    return STRQ_OK;
+}
+
 }  // namespace strq
+
+namespace {
+
+// target ids and read lengths of `n` reads as a caller hands them over
+int check_reads(strq_ctx* c, const DetectState* d, int64_t n, const int64_t* offsets, const int32_t* target_id)
+{
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t len = offsets[i + 1] - offsets[i];
+        if (target_id[i] < 0 || target_id[i] >= (int32_t)d->targets.size()) { c->err = "unknown target id"; return STRQ_ERR_ARG; }
+        if (len < 0 || len > ((int64_t)1 << 30)) { c->err = "bad offsets"; return STRQ_ERR_ARG; }
+    }
+    return STRQ_OK;
+}
+
+// a new batch of `n` reads: the sub-batches of the previous one that are still in flight are taken first
+int begin_batch(strq_ctx* c, DetectState* d, int64_t n, int dtype)
+{
+    if (const int rc = drain(c, d)) return rc;
+    if (const int rc = ensure_sync_objects(c, d)) return rc;
+    d->batch.begin(n, dtype);
+    d->part_reads = 0;
+    return STRQ_OK;
+}
+
+int batch_prepare(strq_ctx* c, int64_t n_reads, const void* signals, int32_t dtype, const int64_t* offsets,
+                  const int32_t* target_id, const double* host_stats, bool lazy, const void* const* reads = nullptr)
+{
+    DetectState* d = dstate(c);
+    if (n_reads < 0 || (n_reads > 0 && ((!signals && !reads) || !offsets || !target_id)) || (dtype != 0 && dtype != 1)) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    if (!d->have_ps) { c->err = "strq_set_pore_stats has not been called"; return STRQ_ERR_ARG; }
+    if (const int rc = begin_batch(c, d, n_reads, dtype)) return rc;
+    Batch& B = d->batch;
+    B.off.assign(offsets, offsets + n_reads + 1);
+    B.target.assign(target_id, target_id + n_reads);
+    if (const int rc = check_reads(c, d, n_reads, offsets, target_id)) return rc;
+    // float64 reads have no exact histogram: their order statistics come from a radix selection on the GPU (cond_kernels.hip:
+    // f64_stats_kernel) unless the caller hands over its own (numpy's) six scalars per read
+    if (dtype == 1 && host_stats) B.host_stats.assign(host_stats, host_stats + n_reads * 6);
+    const size_t bytes = (size_t)(n_reads ? B.off[n_reads] : 0) * (dtype == 0 ? 2 : 8);
+    STRQ_HIP(c, B.raw.reserve(bytes + 64));
+    B.host_src = static_cast<const char*>(signals); B.on_host = true;
+    if (reads) B.host_reads.assign(reinterpret_cast<const char* const*>(reads), reinterpret_cast<const char* const*>(reads) + n_reads);
+    if (!lazy) {
+        const int rc = upload_reads(c, d, n_reads);      // resident batch: everything now
+        if (rc) return rc;
+        B.forget_host();
+    }
+    return STRQ_OK;
+}
+
+// sub-batches of reads [first, last): returns the cuts
+std::vector<int64_t> cut_sub_batches(const strq_ctx* c, const DetectState* d, int64_t first, int64_t last)
+{
+    const Batch& B = d->batch;
+    // Sub-batch size: 16 reads (32 alignments) per CU.  The alignments of a batch are about equally
+    // long, so the forward DP proceeds in rounds: 32 per CU is four full rounds of the eight waves the
+    // 24-bit tables allow (and, with six float32 waves -- two alone on their SIMD at 60.6 ms per
+    // alignment, four sharing one at 73 ms -- 6 x 60.6 = 5 x 73 ends without a ragged tail as well;
+    // 4608 reads measured 437 ms against 365 ms for 4096).
+    int64_t cap = std::min<int64_t>(16 * (int64_t)c->n_cu, 8192);      // 8192: task limit of vit_sort_kernel
+    if (const char* e = strq::opt("STRQ_SUBBATCH_READS")) { const int64_t v = atoll(e); if (v > 0) cap = std::min<int64_t>(v, 8192); }      // testing: force small sub-batches
+    std::vector<int64_t> cuts(1, first);
+    for (int64_t r0 = first; r0 < last;) {
+        int64_t r1 = r0; size_t ck = 0; int64_t samples = 0;
+        while (r1 < last && r1 - r0 < cap) {
+            const Target& t = d->targets[B.target[r1]];
+            const int n = (int)(B.off[r1 + 1] - B.off[r1]);
+            const size_t need = align_workspace_bytes(n, 0, t.Rp, t.NSp) + align_workspace_bytes(n, 0, t.Rs, t.NSs);
+            if (r1 > r0 && (ck + need > c->max_ws_bytes || samples + n > ((int64_t)3 << 30))) break;
+            ck += need; samples += n; ++r1;
+        }
+        cuts.push_back(r1);
+        r0 = r1;
+    }
+    return cuts;
+}
+
+int run_range(strq_ctx* c, DetectState* d, int64_t first, int64_t last)
+{
+    Batch& B = d->batch;
+    if (first < 0 || last < first || last > B.n_reads) { c->err = "read range outside the uploaded batch"; return STRQ_ERR_ARG; }
+    B.t_cond = B.t_lut = B.t_fwd = B.t_trace = B.t_vit = 0; B.n_hard = 0; B.n_fwd_launches = 0;
+    std::fill(c->counters, c->counters + 8, 0.0);
+    std::fill(c->overlap, c->overlap + 4, 0.0);
+    c->second_round[0] = c->second_round[1] = 0; c->look2_served = 0;
+    for (double& v : c->screen_stats) v = 0;
+    B.units_ran = d->units_on;
+    d->unit_ms = 0; d->unit_bytes = d->unit_reads = d->unit_positions = 0;
+    STRQ_HIP(c, c->redo_total.reserve(64));
+    STRQ_HIP(c, hipMemsetAsync(c->redo_total.p, 0, 64, c->stream));
+    // partition into sub-batches first, so that the upload of piece k + 1 can overlap the kernels of piece k
+    const std::vector<int64_t> cuts = cut_sub_batches(c, d, first, last);
+    for (size_t k = 0; k + 1 < cuts.size(); ++k) {
+        const double t1 = now_s();
+        // samples not yet in HBM (first sub-batch of strq_detect_batch) are uploaded piece by piece inside
+        const int rc = run_sub_batch(c, d, cuts[k], cuts[k + 1], k + 2 < cuts.size() ? cuts[k + 2] : cuts[k + 1]);
+        if (rc) { (void)upload_join(d); return rc; }          // (the prefetch thread reads the caller's buffers: never left running)
+        STRQ_DBG("sub-batch %zu: reads %ld..%ld  %.1f ms", k, (long)cuts[k], (long)cuts[k + 1], (now_s() - t1) * 1e3);
+    }
+    { const int urc = upload_join(d); if (urc) { c->err = "upload of the batch's samples failed (prefetch thread)"; return urc; } }
+    B.forget_host();      // the caller's buffers are not referenced after the call
+    publish_timing(c, B);
+    return STRQ_OK;
+}
+
+// tail of strq_detect_batch(_reads): the prepared batch through the pipeline, its rows to `out`
+int run_and_fetch(strq_ctx* c, strq_result* out)
+{
+    DetectState* d = dstate(c);
+    const int rc = run_range(c, d, 0, d->batch.n_reads);
+    d->batch.forget_host();
+    if (rc) return rc;
+    if (!out) return STRQ_ERR_ARG;
+    if (const int drc = drain(c, d)) return drc;
+    std::memcpy(out, d->batch.results.data(), d->batch.results.size() * sizeof(strq_result));
+    return STRQ_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
 int strq_set_pore_stats(strq_ctx* c, double tail_lo, double tail_hi, double model_min, double model_max)
 {
-    if (!c) return STRQ_ERR_ARG;
+    STRQ_ENTER(c);
     DetectState* d = dstate(c);
+    if (const int rc = drain(c, d)) return rc;          // a sub-batch in flight is taken with the statistics it ran with
     d->ps.M_lo = tail_lo; d->ps.M_hi = tail_hi; d->ps.clip_lo = model_min + .5; d->ps.clip_hi = model_max - .5;
     d->have_ps = true;
     return STRQ_OK;
@@ -955,8 +1219,7 @@ int strq_target_add(strq_ctx* c, const float* prefix_ext, int64_t m_prefix, cons
                     int32_t trim_prefix, int32_t trim_suffix, int32_t samples, int32_t hmm_model_id, int32_t count_bias,
                     int32_t* target_id)
 {
-    strq::CtxScope scope_(c);
-    if (!c) return STRQ_ERR_ARG;
+    STRQ_ENTER(c);
     if (!prefix_ext || !suffix_ext || !target_id || hmm_model_id < 0 || hmm_model_id >= (int32_t)c->models.size() ||
         trim_prefix < 0 || trim_suffix < 0 || trim_prefix >= m_prefix || trim_suffix >= m_suffix) { c->err = "bad argument"; return STRQ_ERR_ARG; }
     DetectState* d = dstate(c);
@@ -972,18 +1235,20 @@ int strq_target_add(strq_ctx* c, const float* prefix_ext, int64_t m_prefix, cons
 
 int strq_target_set_mod(strq_ctx* c, int32_t target_id, int32_t mod_model_id, double mod_min, double mod_max)
 {
-    if (!c) return STRQ_ERR_ARG;
+    STRQ_ENTER(c);
     DetectState* d = dstate(c);
     if (target_id < 0 || target_id >= (int32_t)d->targets.size() || mod_model_id < 0 || mod_model_id >= (int32_t)c->models.size()) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    if (const int rc = drain(c, d)) return rc;          // a sub-batch in flight is taken with the target it ran with
     d->targets[target_id].mod_model_id = mod_model_id; d->targets[target_id].mod_min = mod_min; d->targets[target_id].mod_max = mod_max;
     return STRQ_OK;
 }
 
 int strq_batch_fetch_mod(strq_ctx* c, char* pool, int64_t pool_cap, int64_t* off)
 {
-    if (!c || !off) return STRQ_ERR_ARG;
+    STRQ_ENTER(c);
+    if (!off) return STRQ_ERR_ARG;
     DetectState* d = dstate(c);
-    { const int rc = drain(c, d); if (rc) return rc; }
+    if (const int rc = drain(c, d)) return rc;
     int64_t pos = 0;
     for (size_t i = 0; i < d->batch.mod.size(); ++i) {
         off[i] = pos;
@@ -997,24 +1262,21 @@ int strq_batch_fetch_mod(strq_ctx* c, char* pool, int64_t pool_cap, int64_t* off
 
 int strq_set_units(strq_ctx* c, int32_t on)
 {
-    if (!c) return STRQ_ERR_ARG;
-    strq::CtxScope scope_(c);
+    STRQ_ENTER(c);
     if (on != 0 && on != 1) { c->err = "bad argument (strq_set_units takes 0 or 1)"; return STRQ_ERR_ARG; }
     DetectState* d = dstate(c);
-    STRQ_HIP(c, hipSetDevice(c->device));
     // sub-batches in flight keep the mode they were launched with: their unit pass (or none) runs now
-    { const int rc = drain(c, d); if (rc) return rc; }
+    if (const int rc = drain(c, d)) return rc;
     d->units_on = on != 0;
     return STRQ_OK;
 }
 
 int strq_batch_fetch_units(strq_ctx* c, int64_t* pool, int64_t pool_cap, int64_t* off, int32_t* decoded)
 {
-    if (!c || !off) return STRQ_ERR_ARG;
-    strq::CtxScope scope_(c);
+    STRQ_ENTER(c);
+    if (!off) return STRQ_ERR_ARG;
     DetectState* d = dstate(c);
-    STRQ_HIP(c, hipSetDevice(c->device));
-    { const int rc = drain(c, d); if (rc) return rc; }
+    if (const int rc = drain(c, d)) return rc;
     const Batch& B = d->batch;
     if (!B.units_ran) { c->err = "the last batch ran without unit positions (strq_set_units)"; return STRQ_ERR_ARG; }
     int64_t pos = 0;
@@ -1040,84 +1302,33 @@ int strq_last_units(strq_ctx* c, double* out4)
     return STRQ_OK;
 }
 
-static int batch_prepare(strq_ctx* c, int64_t n_reads, const void* signals, int32_t dtype, const int64_t* offsets,
-                         const int32_t* target_id, const double* host_stats, bool lazy, const void* const* reads = nullptr)
-{
-    if (!c) return STRQ_ERR_ARG;
-    DetectState* d = dstate(c);
-    if (n_reads < 0 || (n_reads > 0 && ((!signals && !reads) || !offsets || !target_id)) || (dtype != 0 && dtype != 1)) { c->err = "bad argument"; return STRQ_ERR_ARG; }
-    if (!d->have_ps) { c->err = "strq_set_pore_stats has not been called"; return STRQ_ERR_ARG; }
-    STRQ_HIP(c, hipSetDevice(c->device));
-    { const int rc = drain(c, d); if (rc) return rc; }          // sub-batches of the previous batch still in flight
-    Batch& B = d->batch;
-    B.n_reads = n_reads; B.dtype = dtype;
-    B.off.assign(offsets, offsets + n_reads + 1);
-    B.target.assign(target_id, target_id + n_reads);
-    for (int64_t i = 0; i < n_reads; ++i) {
-        if (B.target[i] < 0 || B.target[i] >= (int32_t)d->targets.size()) { c->err = "unknown target id"; return STRQ_ERR_ARG; }
-        if (B.off[i + 1] < B.off[i] || B.off[i + 1] - B.off[i] > ((int64_t)1 << 30)) { c->err = "bad offsets"; return STRQ_ERR_ARG; }
-    }
-    B.host_stats.clear();
-    // float64 reads have no exact histogram: their order statistics come from a radix selection on the GPU (cond_kernels.hip:
-    // f64_stats_kernel) unless the caller hands over its own (numpy's) six scalars per read
-    if (dtype == 1 && host_stats) B.host_stats.assign(host_stats, host_stats + n_reads * 6);
-    const size_t bytes = (size_t)(n_reads ? B.off[n_reads] : 0) * (dtype == 0 ? 2 : 8);
-    STRQ_HIP(c, B.raw.reserve(bytes + 64));
-    B.forget_host();
-    B.host_src = static_cast<const char*>(signals); B.uploaded = 0; B.on_host = true;
-    if (reads) B.host_reads.assign(reinterpret_cast<const char* const*>(reads), reinterpret_cast<const char* const*>(reads) + n_reads);
-    if (!lazy) {
-        const int rc = upload_reads(c, d, n_reads);      // resident batch: everything now
-        if (rc) return rc;
-        B.forget_host();
-    }
-    B.results.assign((size_t)n_reads, strq_result());
-    B.mod.assign((size_t)n_reads, std::string("-"));
-    B.reset_units(n_reads);
-    if (!d->ev_ok) { for (auto& e : d->ev) STRQ_HIP(c, hipEventCreate(&e)); d->ev_ok = true; }
-    return STRQ_OK;
-}
-
 int strq_batch_upload(strq_ctx* c, int64_t n_reads, const void* signals, int32_t dtype, const int64_t* offsets,
                       const int32_t* target_id, const double* host_stats)
 {
-    strq::CtxScope scope_(c);
+    STRQ_ENTER(c);
     return batch_prepare(c, n_reads, signals, dtype, offsets, target_id, host_stats, false);
 }
 
 int strq_batch_upload_part(strq_ctx* c, int64_t total_reads, int64_t total_samples, int64_t first_read, int64_t n_reads,
                            const void* signals, int32_t dtype, const int64_t* offsets, const int32_t* target_id)
 {
-    if (!c) return STRQ_ERR_ARG;
-    strq::CtxScope scope_(c);
+    STRQ_ENTER(c);
     DetectState* d = dstate(c);
     if (total_reads < 0 || total_samples < 0 || first_read < 0 || n_reads < 0 || first_read + n_reads > total_reads || dtype != 0 ||
         (n_reads > 0 && (!signals || !offsets || !target_id))) { c->err = "bad argument (strq_batch_upload_part takes int16 reads)"; return STRQ_ERR_ARG; }
     if (!d->have_ps) { c->err = "strq_set_pore_stats has not been called"; return STRQ_ERR_ARG; }
-    STRQ_HIP(c, hipSetDevice(c->device));
     Batch& B = d->batch;
     if (first_read == 0) {
         // a new resident batch: device memory for all of it now, the parts follow in order
-        { const int rc = drain(c, d); if (rc) return rc; }
-        B.forget_host();
-        B.n_reads = total_reads; B.dtype = dtype;
+        if (const int rc = begin_batch(c, d, total_reads, dtype)) return rc;
         B.off.assign((size_t)total_reads + 1, 0); B.target.assign((size_t)total_reads, 0);
-        B.host_stats.clear();
         STRQ_HIP(c, B.raw.reserve((size_t)total_samples * 2 + 64));      // total_samples is a hint: the buffer grows (below) when the parts hold more
-        B.results.assign((size_t)total_reads, strq_result());
-        B.mod.assign((size_t)total_reads, std::string("-"));
-        B.reset_units(total_reads);
-        B.uploaded = 0; B.on_host = false;
-        d->part_reads = 0;
-        if (!d->ev_ok) { for (auto& e : d->ev) STRQ_HIP(c, hipEventCreate(&e)); d->ev_ok = true; }
     }
     if (B.n_reads != total_reads || d->part_reads != first_read) { c->err = "parts of a resident batch must follow each other, first_read = reads uploaded so far"; return STRQ_ERR_ARG; }
     if (n_reads == 0) return STRQ_OK;
+    if (const int rc = check_reads(c, d, n_reads, offsets, target_id)) return rc;
     const int64_t base = B.off[(size_t)first_read];
     for (int64_t i = 0; i < n_reads; ++i) {
-        const int64_t len = offsets[i + 1] - offsets[i];
-        if (target_id[i] < 0 || target_id[i] >= (int32_t)d->targets.size()) { c->err = "unknown target id"; return STRQ_ERR_ARG; }
-        if (len < 0 || len > ((int64_t)1 << 30)) { c->err = "bad offsets"; return STRQ_ERR_ARG; }
         B.off[(size_t)(first_read + i + 1)] = base + (offsets[i + 1] - offsets[0]);
         B.target[(size_t)(first_read + i)] = target_id[i];
     }
@@ -1147,91 +1358,37 @@ int strq_batch_upload_part(strq_ctx* c, int64_t total_reads, int64_t total_sampl
 
 int strq_batch_run(strq_ctx* c)
 {
-    if (!c) return STRQ_ERR_ARG;
-    return strq_batch_run_range(c, 0, dstate(c)->batch.n_reads);
+    STRQ_ENTER(c);
+    return run_range(c, dstate(c), 0, dstate(c)->batch.n_reads);
 }
 
 int strq_batch_run_range(strq_ctx* c, int64_t first, int64_t last)
 {
-    strq::CtxScope scope_(c);
-    if (!c) return STRQ_ERR_ARG;
-    DetectState* d = dstate(c);
-    Batch& B = d->batch;
-    if (first < 0 || last < first || last > B.n_reads) { c->err = "read range outside the uploaded batch"; return STRQ_ERR_ARG; }
-    STRQ_HIP(c, hipSetDevice(c->device));
-    B.t_cond = B.t_lut = B.t_fwd = B.t_trace = B.t_vit = 0; B.n_hard = 0; B.n_fwd_launches = 0;
-    std::fill(c->counters, c->counters + 8, 0.0);
-    std::fill(c->overlap, c->overlap + 4, 0.0);
-    c->second_round[0] = c->second_round[1] = 0; c->look2_served = 0;
-    for (double& v : c->screen_stats) v = 0;
-    B.units_ran = d->units_on;
-    d->unit_ms = 0; d->unit_bytes = d->unit_reads = d->unit_positions = 0;
-    STRQ_HIP(c, c->redo_total.reserve(64));
-    STRQ_HIP(c, hipMemsetAsync(c->redo_total.p, 0, 64, c->stream));
-    // partition into sub-batches first, so that the upload of piece k + 1 can overlap the kernels of piece k
-    std::vector<int64_t> cuts(1, first);
-    int64_t r0 = first;
-    const int64_t n_end = last;
-    while (r0 < n_end) {
-        int64_t r1 = r0; size_t ck = 0; int64_t samples = 0;
-        bool mod_batch = false;
-        // Sub-batch size: 16 reads (32 alignments) per CU.  The alignments of a batch are about equally
-        // long, so the forward DP proceeds in rounds: 32 per CU is four full rounds of the eight waves the
-        // 24-bit tables allow (and, with six float32 waves -- two alone on their SIMD at 60.6 ms per
-        // alignment, four sharing one at 73 ms -- 6 x 60.6 = 5 x 73 ends without a ragged tail as well;
-        // 4608 reads measured 437 ms against 365 ms for 4096).
-        const int64_t full = std::min<int64_t>(16 * (int64_t)c->n_cu, 8192);      // 8192: task limit of vit_sort_kernel
-        int64_t full_env = 0;
-        if (const char* e = strq::opt("STRQ_SUBBATCH_READS")) full_env = atoll(e);      // testing: force small sub-batches
-        for (int64_t r = r0; r < n_end && r < r0 + full; ++r) mod_batch |= d->targets[B.target[r]].mod_model_id >= 0;
-        const int64_t cap = full_env > 0 ? std::min<int64_t>(full_env, 8192) : full;      // (the modification pass keeps back-pointers of the small dual model only: ~3 MB per 50 kb read)
-        (void)mod_batch;
-        while (r1 < n_end && r1 - r0 < cap) {
-            const Target& t = d->targets[B.target[r1]];
-            const int n = (int)(B.off[r1 + 1] - B.off[r1]);
-            const size_t need = align_workspace_bytes(n, 0, t.Rp, t.NSp) + align_workspace_bytes(n, 0, t.Rs, t.NSs);
-            if (r1 > r0 && (ck + need > c->max_ws_bytes || samples + n > ((int64_t)3 << 30))) break;
-            ck += need; samples += n; ++r1;
-        }
-        cuts.push_back(r1);
-        r0 = r1;
-    }
-    for (size_t k = 0; k + 1 < cuts.size(); ++k) {
-        const double t1 = now_s();
-        // samples not yet in HBM (first sub-batch of strq_detect_batch) are uploaded piece by piece inside
-        const int rc = run_sub_batch(c, d, cuts[k], cuts[k + 1], k + 2 < cuts.size() ? cuts[k + 2] : cuts[k + 1]);
-        if (rc) { (void)upload_join(d); return rc; }          // (the prefetch thread reads the caller's buffers: never left running)
-        STRQ_DBG("sub-batch %zu: reads %ld..%ld  %.1f ms", k, (long)cuts[k], (long)cuts[k + 1], (now_s() - t1) * 1e3);
-    }
-    { const int urc = upload_join(d); if (urc) { c->err = "upload of the batch's samples failed (prefetch thread)"; return urc; } }
-    B.forget_host();      // the caller's buffers are not referenced after the call
-    publish_timing(c, B);
-    return STRQ_OK;
+    STRQ_ENTER(c);
+    return run_range(c, dstate(c), first, last);
 }
 
 int strq_batch_fetch(strq_ctx* c, strq_result* out)
 {
-    if (!c || !out) return STRQ_ERR_ARG;
-    strq::CtxScope scope_(c);
+    STRQ_ENTER(c);
+    if (!out) return STRQ_ERR_ARG;
     DetectState* d = dstate(c);
-    STRQ_HIP(c, hipSetDevice(c->device));
-    { const int rc = drain(c, d); if (rc) return rc; }
+    if (const int rc = drain(c, d)) return rc;
     std::memcpy(out, d->batch.results.data(), d->batch.results.size() * sizeof(strq_result));
     return STRQ_OK;
 }
 
 int strq_batch_fetch_range(strq_ctx* c, int64_t first, int64_t last, strq_result* out)
 {
-    if (!c || !out) return STRQ_ERR_ARG;
-    strq::CtxScope scope_(c);
+    STRQ_ENTER(c);
+    if (!out) return STRQ_ERR_ARG;
     DetectState* d = dstate(c);
     if (first < 0 || last < first || last > d->batch.n_reads) { c->err = "read range outside the uploaded batch"; return STRQ_ERR_ARG; }
-    STRQ_HIP(c, hipSetDevice(c->device));
     // only the sub-batches in flight that hold reads of the range are waited for (oldest first): a caller that runs range k + 1
     // before it fetches range k never waits for the Viterbi launches of k + 1
     for (int k = 0; k < 2; ++k) {
         DetectState::Slot& sl = d->slot[(d->next_slot + k) & 1];
-        if (sl.active && sl.r0 < last && sl.r0 + sl.nr > first) { const int rc = harvest(c, d, sl); if (rc) return rc; }
+        if (sl.state != DetectState::Slot::Idle && sl.r0 < last && sl.r0 + sl.nr > first) { const int rc = harvest(c, d, sl); if (rc) return rc; }
     }
     std::memcpy(out, d->batch.results.data() + first, (size_t)(last - first) * sizeof(strq_result));
     return STRQ_OK;
@@ -1240,44 +1397,35 @@ int strq_batch_fetch_range(strq_ctx* c, int64_t first, int64_t last, strq_result
 int strq_detect_batch(strq_ctx* c, int64_t n_reads, const void* signals, int32_t dtype, const int64_t* offsets,
                       const int32_t* target_id, const double* host_stats, strq_result* out)
 {
-    strq::CtxScope scope_(c);
+    STRQ_ENTER(c);
     // signals stay in the caller's buffer and are uploaded one sub-batch ahead of the kernels
-    int rc = batch_prepare(c, n_reads, signals, dtype, offsets, target_id, host_stats, true);
-    if (rc) return rc;
-    rc = strq_batch_run(c);
-    dstate(c)->batch.forget_host();
-    if (rc) return rc;
-    return strq_batch_fetch(c, out);
+    if (const int rc = batch_prepare(c, n_reads, signals, dtype, offsets, target_id, host_stats, true)) return rc;
+    return run_and_fetch(c, out);
 }
 
 int strq_detect_batch_reads(strq_ctx* c, int64_t n_reads, const void* const* reads, const int64_t* lengths, int32_t dtype,
                             const int32_t* target_id, const double* host_stats, strq_result* out)
 {
-    strq::CtxScope scope_(c);
+    STRQ_ENTER(c);
     // one buffer per read (what a caller holding a list of arrays has): no concatenated copy on the host, the staging
     // threads gather straight from the reads
-    if (!c) return STRQ_ERR_ARG;
     if (n_reads < 0 || (n_reads > 0 && (!reads || !lengths))) { c->err = "bad argument"; return STRQ_ERR_ARG; }
     std::vector<int64_t> off((size_t)n_reads + 1, 0);
     for (int64_t i = 0; i < n_reads; ++i) {
         if (lengths[i] < 0 || (lengths[i] > 0 && !reads[i])) { c->err = "bad argument"; return STRQ_ERR_ARG; }
         off[(size_t)i + 1] = off[(size_t)i] + lengths[i];
     }
-    int rc = batch_prepare(c, n_reads, nullptr, dtype, off.data(), target_id, host_stats, true, reads);
-    if (rc) return rc;
-    rc = strq_batch_run(c);
-    dstate(c)->batch.forget_host();
-    if (rc) return rc;
-    return strq_batch_fetch(c, out);
+    if (const int rc = batch_prepare(c, n_reads, nullptr, dtype, off.data(), target_id, host_stats, true, reads)) return rc;
+    return run_and_fetch(c, out);
 }
 
 // conditioning outputs of the last sub-batch (parity tests of STRique.py:590-597): levels of read
 // `read` (index inside the last sub-batch), its 256 level values and the scalars.
 int strq_debug_conditioning(strq_ctx* c, int64_t read, uint8_t* levels, int64_t n, float* level_val, double* scalars10)
 {
-    if (!c) return STRQ_ERR_ARG;
+    STRQ_ENTER(c);
     DetectState* d = dstate(c);
-    { const int drc = drain(c, d); if (drc) return drc; }
+    if (const int drc = drain(c, d)) return drc;
     ReadCond rc;
     STRQ_HIP(c, hipMemcpy(&rc, d->rc.as<ReadCond>() + read, sizeof(rc), hipMemcpyDeviceToHost));
     if (levels) STRQ_HIP(c, hipMemcpy(levels, c->levels.as<uint8_t>() + d->levels_shift + rc.off, (size_t)std::min<int64_t>(n, rc.n), hipMemcpyDeviceToHost));

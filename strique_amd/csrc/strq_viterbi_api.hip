@@ -547,6 +547,8 @@ int build_vit_g2(strq_ctx* c, HostModel* hm, const int32_t* kind_hint, const int
 
 }  // namespace strq
 
+int strq::viterbi_launch_status(int vrc) { return vrc == 0 ? STRQ_OK : (vrc == 2 || vrc == 3) ? STRQ_ERR_UNSUPPORTED : STRQ_ERR_DEVICE; }
+
 extern "C" {
 
 int strq_model_create(strq_ctx* c, int32_t n_states, int32_t silent_start, int32_t start, int32_t end,
@@ -605,6 +607,8 @@ int strq_model_set_positions(strq_ctx* c, int32_t model_id, const int32_t* kind,
     if (!c) return STRQ_ERR_ARG;
     if (model_id < 0 || model_id >= (int32_t)c->models.size() || !c->models[model_id] || !kind || !pos) { c->err = "bad argument"; return STRQ_ERR_ARG; }
     STRQ_HIP(c, hipSetDevice(c->device));
+    // a detect sub-batch whose Viterbi launches are not yet queued points to the model's present device image through its tasks
+    { const int rc = detect_drain(c); if (rc) return rc; }
     return build_vit_g2(c, c->models[model_id], kind, pos);
 }
 
@@ -650,7 +654,7 @@ int strq_viterbi_batch(strq_ctx* c, int32_t model_id, int64_t n_seq, const doubl
     const int shape = vit_shape_for(hm->h, paths ? 1 : 0);
     if (shape < 0) { c->err = "model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
     int rc = launch_viterbi(st, shape, hm->h.n_cells, d_tasks, d_res, (int)n_seq, c->queue.as<int>(), c->n_cu, paths ? 1 : 0);
-    if (rc) { c->err = "viterbi launch failed"; return rc == 2 || rc == 3 ? STRQ_ERR_UNSUPPORTED : STRQ_ERR_DEVICE; }
+    if (rc) { c->err = "viterbi launch failed"; return viterbi_launch_status(rc); }
     STRQ_HIP(c, hipEventRecord(c->ev[1], st));
     if (paths) {
         if (launch_vit_traceback(st, d_tasks, d_res, d_paths, (int)n_seq)) { c->err = "traceback launch failed"; return STRQ_ERR_DEVICE; }

@@ -310,8 +310,73 @@ def test_rows_of_a_range_while_the_next_is_in_flight(gpu_counter, pm, targets, m
     ctx.batch_run()
     assert ctx.batch_fetch().tobytes() == one_call.tobytes()
     assert (one_call["count"] > 0).sum() >= 10
+    # every slot is idle after a fetch: a second one returns the same rows and launches nothing
+    launches = ctx.last_viterbi_launches()
+    assert ctx.batch_fetch().tobytes() == one_call.tobytes() and ctx.last_viterbi_launches() == launches
     with pytest.raises(Exception):
         ctx.batch_fetch_range(5, 13)
+
+
+def _resident(gpu_counter, pm, targets, n, first_idx):
+    """n small reads of c9orf72 as a resident batch: (signals, offsets, target ids)"""
+    sigs = [np.ascontiguousarray(_read(pm, targets, "c9orf72", "+-"[k % 2], 3000 + 400 * k, 8 + 5 * k, first_idx + k)) for k in range(n)]
+    off = np.zeros(n + 1, np.int64); off[1:] = np.cumsum([len(x) for x in sigs])
+    tids = [gpu_counter._classifier_for("c9orf72", "+-"[k % 2]).target_id for k in range(n)]
+    return np.concatenate(sigs), off, tids
+
+
+def test_set_mod_between_run_and_fetch_leaves_the_rows_in_flight_alone(pm, cfg, targets, monkeypatch):
+    """strq_target_set_mod after strq_batch_run, before the fetch: the sub-batches in flight ran in count mode and are taken as
+    such -- the rows of the same batch fetched without the call, every pattern '-' (no modification pass over count-mode results)."""
+    from strique_amd.counter import repeatCounter
+    rc = repeatCounter(pm, align_config=cfg["align"], HMM_config=cfg["HMM"], device=0)
+    chrom, b, e, repeat, prefix, suffix = cfg["repeat"]["c9orf72"]
+    rc.add_target("c9orf72", repeat, prefix, suffix)
+    ctx = rc.ctx
+    sig, off, tids = _resident(rc, pm, targets, 8, 7100)
+    monkeypatch.setenv("STRQ_SUBBATCH_READS", "3")
+    ctx.batch_upload(sig, off, tids)
+    ctx.batch_run(); plain = ctx.batch_fetch().copy()
+    assert (plain["count"] > 0).sum() >= 7
+    ctx.batch_upload(sig, off, tids)
+    ctx.batch_run()
+    tc = rc._classifier_for("c9orf72", "+")
+    ctx.target_set_mod(tc.target_id, tc.repeatHMM.model_id, -4.0, 4.0)      # any model of the context will do: it must not be run
+    assert ctx.batch_fetch_mod() == ["-"] * 8
+    assert ctx.batch_fetch().tobytes() == plain.tobytes()
+    ctx.close()
+
+
+def test_fetch_mod_and_debug_conditioning_first_from_a_fresh_thread(gpu_counter, pm, targets, monkeypatch):
+    """strq_batch_fetch_mod / strq_debug_conditioning as the first call after strq_batch_run, on a thread that has never touched
+    the context (they take the rows of the sub-batches in flight, so they enter the library like every other call: the context's
+    options, the context's device): the same patterns / scalars as from the main thread.  With one GPU this cannot show an
+    allocation on the wrong device; it only pins that the calls work from a fresh thread."""
+    import threading
+    ctx = gpu_counter.ctx
+    sig, off, tids = _resident(gpu_counter, pm, targets, 5, 7200)
+    monkeypatch.setenv("STRQ_SUBBATCH_READS", "3")
+    ctx.batch_upload(sig, off, tids)
+    ctx.batch_run()
+    mods = ctx.batch_fetch_mod()
+    cond = ctx.debug_conditioning(1, 64)          # read 1 of the last sub-batch
+    rows = ctx.batch_fetch().copy()
+    for call in (ctx.batch_fetch_mod, lambda: ctx.debug_conditioning(1, 64)):
+        ctx.batch_upload(sig, off, tids)
+        ctx.batch_run()
+        box = []
+        def work():
+            try:
+                box.append(call())
+            except Exception as exc:          # noqa: BLE001 -- reported on the main thread
+                box.append(exc)
+        t = threading.Thread(target=work); t.start(); t.join()
+        assert len(box) == 1 and not isinstance(box[0], Exception), box
+        if call == ctx.batch_fetch_mod:
+            assert box[0] == mods == ["-"] * 5
+        else:
+            assert all(np.array_equal(x, y) for x, y in zip(box[0], cond))
+        assert ctx.batch_fetch().tobytes() == rows.tobytes()
 
 
 def test_config1_ten_kb_thirty_repeats(gpu_counter, want, pm, targets):

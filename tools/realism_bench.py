@@ -66,10 +66,11 @@ def main():
         for _ in range(3):
             ctx.batch_run(); tm += ctx.last_timing()
             a_, b_ = ctx.last_second_round(); redo += a_; total += b_
+        res = ctx.batch_fetch()                               # inside the window: the last sub-batch's decode ends with its rows
         ctx.device_synchronize()
         dt = (time.time() - t0) / 3
         tm /= 3
-        res = ctx.batch_fetch(); geo = ctx.last_geometry()
+        geo = ctx.last_geometry()
         m_rows = 6 * (len(prefix) - 5)
         fr = np.concatenate([res["score_prefix"], res["score_suffix"]])          # normalised scores; the raw fraction is what the library planned with
         ok = int(sum(abs(int(x["count"]) - w) <= 2 for x, w in zip(res, nreps)))
