@@ -241,6 +241,30 @@ int strq_batch_run(strq_ctx* ctx);
 int strq_batch_run_range(strq_ctx* ctx, int64_t first, int64_t last);
 int strq_batch_fetch(strq_ctx* ctx, strq_result* out);
 int strq_batch_fetch_range(strq_ctx* ctx, int64_t first, int64_t last, strq_result* out);
+/* ---- scan: which target and strand a read spans, from its signal alone (no counterpart in the reference, which takes both from a
+ * SAM record: scripts/STRique.py:673-679,689-692) ----
+ * A candidate is a target id of strq_target_add: one strand of one target.  Every read is uploaded and conditioned once and aligned
+ * against both flanks of every candidate; for candidate c the six values score_prefix, score_suffix, prefix_begin, prefix_end,
+ * suffix_begin, suffix_end are exactly those of strq_detect_batch for (read, c).  With key_c = min(score_prefix, score_suffix),
+ * c is eligible when prefix_begin < suffix_end and key_c >= min_score (min_score > 0); the eligible candidate with the largest key
+ * wins, the lowest position in the list on a tie.  Only the winner's window is decoded: the read's row is the row strq_detect_batch
+ * gives for (read, winner), field for field.  A read without a winner (none eligible, or status 1) has out_cand -1 and a row that is
+ * zero but for its status.  One winner per read.
+ * out_cand[i]: the winner of read i as a position in cand_target_id.  out_scores (nullable): n_reads x n_cand x 2 doubles,
+ * score_prefix and score_suffix of every candidate.  STRQ_ERR_ARG: n_cand < 1 (or > 256), an unknown target id, min_score <= 0.
+ * strq_batch_fetch_mod / strq_batch_fetch_units after a scan refer to the winners. */
+int strq_scan_batch_reads(strq_ctx* ctx, int64_t n_reads, const void* const* reads, const int64_t* lengths, int32_t dtype,
+                          int32_t n_cand, const int32_t* cand_target_id, double min_score,
+                          strq_result* out_rows, int32_t* out_cand, double* out_scores);
+/* The resident form: after strq_scan_set the run calls (strq_batch_run, strq_batch_run_range) scan the uploaded reads for these
+ * candidates (the target ids given at upload are not used, and are in force again after strq_scan_clear); strq_batch_fetch* hand
+ * out the winners' rows, strq_batch_fetch_scan the winners and scores (out_scores nullable) of the whole upload -- like the rows, those
+ * of a read are the ones of the last scan run call that covered it (-1 and zeros when none has since the upload or since the
+ * candidate count changed).  Sub-batches in flight are taken first by both calls.  strq_detect_batch* stay plain
+ * detects whatever is set here. */
+int strq_scan_set(strq_ctx* ctx, int32_t n_cand, const int32_t* cand_target_id, double min_score);
+int strq_scan_clear(strq_ctx* ctx);
+int strq_batch_fetch_scan(strq_ctx* ctx, int32_t* out_cand, double* out_scores);
 /* A host-side helper, not on the path of strq_detect_batch (which takes these on the GPU): the statistics of float64 reads
  * with numpy's arithmetic (no context, no device): out[6 * i ..] = median, MAD, c1, h1 of
  * medfilt(read i, 3) and c1, h1 of read i itself (0, 1 unless want_raw) -- what numpy's median / mean / percentile

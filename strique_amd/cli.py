@@ -227,8 +227,23 @@ def count(argv):
     parser.add_argument("--share-device", action="store_true", help="testing: every rank uses --device instead of its LOCAL_RANK")
     parser.add_argument("--units", default=None, metavar="FILE", help="Also write the repeat-unit positions (raw-signal sample of every repeat unit "
                                                                         "on the decoded path) to FILE: one row per count row, columns " + " ".join(UNITS_HEADER))
+    parser.add_argument("--scan", action="store_true", help="No alignment: every read of the index is compared with every target of the repeat config on both strands, "
+                                                             "from its raw signal alone, and counted for the one it spans (if any).  Excludes --algn; stdin is not read")
+    parser.add_argument("--scan-min-score", type=float, default=None, metavar="X", help="--scan: the smallest min(score_prefix, score_suffix) a target and strand needs to be "
+                                                                                       "taken for a read.  Required with --scan: there is no default (README, 'Scan')")
+    parser.add_argument("--scan-scores", default=None, metavar="FILE", help="--scan: also write score_prefix and score_suffix of every candidate to FILE, one row per read, "
+                                                                            "with or without a winner (what a threshold for one's own data is chosen from)")
     parser.add_argument("--strict", action="store_true", help="Exit with status 2 when any read could not be processed (the reference only logs such reads and exits 0)")
     args = parser.parse_args(argv)
+    if args.scan and args.algn:
+        parser.error("--scan takes the target and strand of a read from its signal: it cannot be combined with --algn")
+    if not args.scan and (args.scan_scores or args.scan_min_score is not None):
+        parser.error("--scan-min-score and --scan-scores need --scan")
+    if args.scan and args.scan_min_score is None:
+        parser.error("--scan needs --scan-min-score X: the scores of wrong and of true candidates overlap on noisy reads, so there is no default "
+                     "(a first run with a high X and --scan-scores FILE shows what to choose from)")
+    if args.scan_min_score is not None and not args.scan_min_score > 0:
+        parser.error("--scan-min-score must be above 0")
     log = Log(args.log_level)
     config = parse_config(args.repeat, args.config, log)
     for path, what in ((args.f5Index, "Fast5 index file"), (args.model, "Pore model file")):
@@ -242,7 +257,7 @@ def count(argv):
         # one process per GPU (torchrun): the accepted (read, target) pairs are dealt to the ranks by read
         # length (strique_amd.dist.shard_indices), rank 0 gathers fixed-size result records plus the
         # modification strings once at the end (strique_amd.dist.gather_results) and writes the rows in input order
-        if not args.algn:
+        if not args.algn and not args.scan:
             log("Main: --algn FILE is required when running on several GPUs (stdin cannot be shared).", 'error'); raise SystemExit(1)
         # this rank's share of the host's CPUs FIRST: sched_setaffinity pins the calling thread and what it creates afterwards, so the
         # threads torch.distributed / RCCL / gloo start in init_process_group -- and the reader, upload and statistics threads -- follow
@@ -264,7 +279,16 @@ def count(argv):
             continue
         loci[chrom].append((name, begin, end))
     f5 = Fast5Index(args.f5Index)
-    stream = open(args.algn) if args.algn else sys.stdin
+    scan = None
+    if args.scan:
+        from . import scan as scan_mod
+        scan = {"min_score": args.scan_min_score,
+                "candidates": counter.candidates(), "scores": bool(args.scan_scores)}
+        if not scan["candidates"]:
+            log("Main: --scan without a usable target.", 'error'); raise SystemExit(1)
+    # --scan: every read id of the index, in index order, instead of SAM records
+    stream = list(f5.index) if args.scan else (open(args.algn) if args.algn else sys.stdin)
+    scores_out = open(args.scan_scores, 'w') if (args.scan_scores and rank == 0) else None
     out = (open(args.out, 'w') if args.out else sys.stdout) if rank == 0 else None
     units_out = open(args.units, 'w') if (args.units and rank == 0) else None
     readers = args.t
@@ -283,7 +307,7 @@ def count(argv):
     fault = 0
     try:
         rows = run_count(stream, loci, f5.get_raw, counter, log, args.batch, rank, world, out if world == 1 else None, readers=readers, stats=stats,
-                         units=bool(args.units), units_out=units_out if world == 1 else None)
+                         units=bool(args.units), units_out=units_out if world == 1 else None, scan=scan, scores_out=scores_out if world == 1 else None)
     except DeviceFault:
         if world == 1:
             raise SystemExit(3)
@@ -297,19 +321,25 @@ def count(argv):
                 log("Main: a rank reported a device error; no output written.", 'error')
             dist.destroy_process_group()
             raise SystemExit(3)
-        merged = gather_rows(rows, stats["items"], sdist, units=bool(args.units))
-        if args.units:
+        merged = gather_rows(rows, stats["items"], sdist, units=bool(args.units), scan=scan)
+        if scan:
+            merged, merged_units, merged_scores = merged
+        elif args.units:
             merged, merged_units = merged
         if rank == 0:
             write_rows(out, merged)
             if units_out is not None:
                 write_rows(units_out, merged_units, header=UNITS_HEADER)
+            if scores_out is not None:
+                write_rows(scores_out, merged_scores, header=scan_mod.scores_header(scan["candidates"]))
         dist.barrier()
         dist.destroy_process_group()
     if args.out and out is not None:
         out.close()
     if units_out is not None:
         units_out.close()
+    if scores_out is not None:
+        scores_out.close()
     if stats.get("failed"):
         # like the reference (STRique.py:704-713): reads that fail are logged, the run itself succeeds
         log("Main: %d read(s) could not be processed (see warnings above)." % stats["failed"], 'error')
@@ -364,32 +394,50 @@ def parse_units(stream):
     return out
 
 
-def gather_rows(rows, items, sdist, units=False):
+def gather_rows(rows, items, sdist, units=False, scan=None):
     """Rows of this rank -> fixed-size records + modification strings -> one gather -> on rank 0 the
     merged [(sequence number, TSV row)] in input order (None elsewhere).  `items`: every accepted
     (qname, strand, target) of the input, which each rank derives from the same SAM file.
     units=True: every result is (row tuple, unit positions or None); the positions travel in the same blob as the
-    modification string ("mod<TAB>p,p,..."), and the return value is (rows, unit rows) -- (None, None) off rank 0."""
+    modification string ("mod<TAB>p,p,..."), and the return value is (rows, unit rows) -- (None, None) off rank 0.
+    scan (the dict of run_count): every result is (winner, scores) -- winner None or (target, strand, result as above); target,
+    strand and the scores travel in front of the blob ("target<TAB>strand<TAB>s,s,...<TAB>..."), a read without a winner as a
+    record with valid = 2; the return value is (rows, unit rows or None, score rows) -- Nones off rank 0."""
+    from . import scan as scan_mod
     rec = np.zeros(len(rows), ROW_DTYPE); mods = []; idx = np.zeros(len(rows), np.int64)
     for k, (seq, res) in enumerate(rows):
         idx[k] = seq
         if res is None:
             mods.append("")
             continue
+        head = ""
+        if scan:
+            winner, sc = res
+            head = '\t'.join([winner[0] if winner else '-', winner[1] if winner else '-', ','.join(repr(float(x)) for pair in sc for x in pair)]) + '\t'
+            if winner is None:
+                rec[k]["valid"] = 2; mods.append(head)
+                continue
+            res = winner[2]
         pos = None
         if units:
             res, pos = res
         n, sp, ss, p, offset, ticks, mod = res
         rec[k] = (n, 1, sp, ss, float(p), offset, ticks)
-        mods.append(mod + '\t' + (','.join(str(int(x)) for x in pos) if pos is not None and len(pos) else '-') if units else mod)
+        mods.append(head + (mod + '\t' + (','.join(str(int(x)) for x in pos) if pos is not None and len(pos) else '-') if units else mod))
     full, full_mods = sdist.gather_results(rec, idx, len(items), mods)
     if full is None:
-        return (None, None) if units else None
-    merged = []; merged_units = []
+        return (None, None, None) if scan else ((None, None) if units else None)
+    merged = []; merged_units = []; merged_scores = []
     for seq, (qname, strand, target) in enumerate(items):
         r = full[seq]
         if not r["valid"]:
             continue
+        if scan:
+            target, strand, sc, full_mods[seq] = full_mods[seq].split('\t', 3)
+            vals = [float(x) for x in sc.split(',')]
+            merged_scores.append((seq, scan_mod.format_scores(qname, None if r["valid"] == 2 else (target, strand), list(zip(vals[0::2], vals[1::2])))))
+            if r["valid"] == 2:
+                continue
         n = int(r["count"]); lp = float(r["log_p"])
         p = lp if (n or lp != 0) else 0              # the reference prints the integer 0 for a failed gate (STRique.py:602,616)
         mod = full_mods[seq]
@@ -398,6 +446,8 @@ def gather_rows(rows, items, sdist, units=False):
             merged_units.append((seq, format_units(qname, target, strand, n, [] if ustr == '-' else ustr.split(','))))
         merged.append((seq, format_row(qname, target, strand, (n, float(r["score_prefix"]), float(r["score_suffix"]), p,
                                                                  int(r["offset"]), int(r["ticks"]), mod))))
+    if scan:
+        return merged, (merged_units if units else None), merged_scores
     return (merged, merged_units) if units else merged
 
 
@@ -424,7 +474,8 @@ def route(stream, loci, log):
         yield sr.QNAME, ('+' if sr.FLAG & 0x10 == 0 else '-'), targets, sr.QLEN
 
 
-def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, out=None, readers=0, stats=None, units=False, units_out=None):
+def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, out=None, readers=0, stats=None, units=False, units_out=None,
+              scan=None, scores_out=None):
     """Route the SAM records of `stream` to their targets, run this rank's share through
     `counter.detect_batch` and return [(sequence number, result tuple or TSV row)].
 
@@ -438,7 +489,12 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
     the order of the rows does not change.
     `units`: the results also carry the repeat-unit positions (counter.detect_batch(..., units=True)); single process:
     their rows (format_units) go to `units_out` with the count rows and to stats["unit_rows"]; several ranks: the
-    results are (row tuple, positions) pairs for `gather_rows(..., units=True)`."""
+    results are (row tuple, positions) pairs for `gather_rows(..., units=True)`.
+    `scan` ({"min_score", "candidates", "scores"}): `stream` is a list of read ids instead of a SAM stream; every read goes through
+    counter.scan_batch and takes target and strand from its winner -- a read without one writes no row, as a read without a target
+    writes none; single process: the score rows (strique_amd.scan.format_scores, every read) go to `scores_out`; several ranks: the
+    reads are dealt out by position (no SAM, no lengths) and the results are (winner, scores) pairs for `gather_rows(..., scan=scan)`."""
+    from . import scan as scan_mod
     from .ffi import StriqueHipError, STRQ_ERR_ARG, STRQ_ERR_UNSUPPORTED
     if stats is None:
         stats = {}
@@ -447,9 +503,12 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
         print('\t'.join(HEADER), file=out)
     if units_out is not None:
         print('\t'.join(UNITS_HEADER), file=units_out)
+    if scores_out is not None:
+        print('\t'.join(scan_mod.scores_header(scan["candidates"])), file=scores_out)
     stats.setdefault("unit_rows", [])
+    stats.setdefault("score_rows", [])
     rows = []
-    records = route(stream, loci, log)
+    records = ((rid, '.', ['.'], 0) for rid in stream) if scan else route(stream, loci, log)
     mine_set = None
     if world > 1:
         from . import dist as sdist
@@ -471,8 +530,13 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
         results = None
         if faulted.is_set():                                      # queued behind the batch that faulted: the device is not touched again
             raise DeviceFault("not run: the device failed in an earlier batch")
+        def scan_some(raws):
+            got, sc = counter.scan_batch(raws, min_score=scan["min_score"], units=units, scores=True)
+            return [(g, [tuple(x) for x in s]) for g, s in zip(got, sc)]
         try:
-            if units:
+            if scan:
+                results = scan_some([raw for _, _, _, _, raw in batch])
+            elif units:
                 results = counter.detect_batch([(t, raw, s) for _, _, t, s, raw in batch], units=True)
             else:
                 results = counter.detect_batch([(t, raw, s) for _, _, t, s, raw in batch])
@@ -489,7 +553,7 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
             results = []
             for _, _, t, s, raw in batch:
                 try:
-                    results.append(counter.detect(t, raw, s, units=True) if units else counter.detect(t, raw, s))
+                    results.append(scan_some([raw])[0] if scan else (counter.detect(t, raw, s, units=True) if units else counter.detect(t, raw, s)))
                 except StriqueHipError as e1:
                     if e1.code not in (STRQ_ERR_ARG, STRQ_ERR_UNSUPPORTED):
                         faulted.set()
@@ -498,16 +562,23 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
                     log("Detector: read failed: %s" % e1, 'warning'); results.append(None); failed += 1
                 except Exception as e1:
                     log("Detector: read failed: %s" % e1, 'warning'); results.append(None); failed += 1
-        done = []; udone = []
+        done = []; udone = []; sdone = []
         for (seq, qname, target, strand, _), res in zip(batch, results):
             if world > 1:
                 done.append((seq, res))
             elif res is not None:
+                if scan:
+                    winner, sc = res
+                    if scan["scores"]:
+                        sdone.append((seq, scan_mod.format_scores(qname, winner[:2] if winner else None, sc)))
+                    if winner is None:
+                        continue
+                    target, strand, res = winner
                 if units:
                     res, pos = res
                     udone.append((seq, format_units(qname, target, strand, res[0], pos)))
                 done.append((seq, format_row(qname, target, strand, res)))
-        return (done, udone), failed
+        return (done, udone, sdone), failed
 
     # The batches run on an engine thread, one at a time and in order, while this thread routes the next SAM records and
     # collects their signals: the GPU call of batch k overlaps the host-side preparation of batch k + 1 (at 50 kb per read
@@ -518,10 +589,13 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
 
     def collect(keep):
         while len(in_flight) > keep:
-            (done, udone), failed = in_flight.popleft().result()          # re-raises DeviceFault from the engine thread
+            (done, udone, sdone), failed = in_flight.popleft().result()          # re-raises DeviceFault from the engine thread
             stats["failed"] += failed
             rows.extend(done)
             stats["unit_rows"].extend(udone)
+            stats["score_rows"].extend(sdone)
+            if scores_out is not None:
+                write_rows(scores_out, sdone, header=False)
             if out is not None:
                 write_rows(out, done, header=False)
             if units_out is not None:

@@ -100,13 +100,7 @@ class repeatCounter(object):
         sigs = [np.asarray(r) for _, r, _ in items]
         # DAC samples that fit int16 take their order statistics from exact histograms; everything else is float64
         # (radix selection on the GPU, cond_kernels.hip: f64_stats_kernel).  A mixed batch runs as two device batches.
-        def fits_int16(s):
-            if s.dtype.kind not in 'iu':
-                return False
-            if s.dtype in (np.int8, np.uint8, np.int16):
-                return True
-            return s.size == 0 or (int(s.min()) >= -32768 and int(s.max()) <= 32767)
-        is_int = [fits_int16(s) for s in sigs]
+        is_int = [self._fits_int16(s) for s in sigs]
         out = [None] * len(items)
         for want_int in (True, False):
             idx = [i for i, f in enumerate(is_int) if f == want_int]
@@ -127,6 +121,68 @@ class repeatCounter(object):
                 row = (n, float(r['score_prefix']), float(r['score_suffix']), p, int(r['offset']), int(r['ticks']), m)
                 out[i] = (row, u) if units else row
         return out
+
+    def candidates(self, targets=None):
+        """[(target_name, strand)] of a scan: every target added (or the named ones), in add_target order, '+' before '-'."""
+        names = list(self.targets) if targets is None else list(targets)
+        for t in names:
+            if t not in self.targets:
+                raise ValueError("RepeatCounter: Target with name " + str(t) + " not defined.")
+        return [(t, s) for t in names for s in '+-']
+
+    def scan_batch(self, signals, targets=None, min_score=None, units=False, scores=False):
+        """Which target and strand each read spans, and detect()'s row for it -- no alignment of basecalls needed.
+
+        signals: iterable of raw signals.  Every read is compared with every candidate of `candidates(targets)` on the two
+        normalised flank scores detect() reports (strique_amd.scan.select states the rule); min_score: the smallest
+        min(score_prefix, score_suffix) a candidate needs.  It has no default (ValueError when None): the scores of wrong and
+        of true candidates overlap on noisy reads ("Scan"), so the threshold is the caller's decision.
+        Returns, per read, None (no candidate eligible) or (target_name, strand, row), row being the tuple detect() returns
+        for that target and strand -- (row, unit positions) with units=True.  scores=True: (that list, float64 array
+        [n_reads, n_candidates, 2] of score_prefix, score_suffix of every candidate)."""
+        if min_score is None:
+            raise ValueError("RepeatCounter: scan_batch needs min_score (there is no default: see README, 'Scan').")
+        if not min_score > 0:
+            raise ValueError("RepeatCounter: min_score must be above 0.")
+        cands = self.candidates(targets)
+        if not cands:
+            raise ValueError("RepeatCounter: no targets to scan for.")
+        ids = [self._classifier_for(t, s).target_id for t, s in cands]
+        sigs = [np.asarray(r) for r in signals]
+        is_int = [self._fits_int16(s) for s in sigs]
+        out = [None] * len(sigs)
+        all_scores = np.zeros((len(sigs), len(cands), 2), np.float64)
+        for want_int in (True, False):
+            idx = [i for i, f in enumerate(is_int) if f == want_int]
+            if not idx:
+                continue
+            arrs = [sigs[i].astype(np.int16 if want_int else np.float64, copy=False) for i in idx]
+            if units:
+                self.ctx.set_units(True)
+            try:
+                res, win, sc = self.ctx.scan_batch_reads(arrs, ids, min_score, scores=True)
+                mods = self.ctx.batch_fetch_mod() if self.pm is not self.pm_mod else ['-'] * len(res)
+                pos = self.ctx.batch_fetch_units() if units else [None] * len(res)
+            finally:
+                if units:
+                    self.ctx.set_units(False)
+            for k, (i, r, w, m, u) in enumerate(zip(idx, res, win, mods, pos)):
+                all_scores[i] = sc[k]
+                if w < 0:
+                    continue
+                n = int(r['count']); p = float(r['log_p']) if n or r['log_p'] != 0 else 0
+                row = (n, float(r['score_prefix']), float(r['score_suffix']), p, int(r['offset']), int(r['ticks']), m)
+                out[i] = cands[int(w)] + ((row, u) if units else row,)
+        return (out, all_scores) if scores else out
+
+    @staticmethod
+    def _fits_int16(s):
+        """DAC samples that fit int16 (see detect_batch)."""
+        if s.dtype.kind not in 'iu':
+            return False
+        if s.dtype in (np.int8, np.uint8, np.int16):
+            return True
+        return s.size == 0 or (int(s.min()) >= -32768 and int(s.max()) <= 32767)
 
     def detect(self, target_name, raw_signal, strand, units=False):
         """(n, score_prefix, score_suffix, log_p, offset, ticks, mod_pattern) -- STRique.py:581-618.  units=True:

@@ -566,7 +566,13 @@ static int screen_two_flank(CorePlan& p, int merge, int max_n)
     for (int i = 0; i < nb; ++i)
         if (in.NS[i] == 1 && p.NJ[i] == 1 && in.n[i] >= min_n && screen2_flank_ok(in.m[i], in.k[i])) by_read[in.read[i]].push_back(i);
     std::vector<std::pair<int, int>> pairs;
-    for (auto& kv : by_read) if (kv.second.size() == 2) pairs.emplace_back(kv.second[0], kv.second[1]);
+    for (auto& kv : by_read) {
+        const std::vector<int>& v = kv.second;
+        if (v.size() == 2) { pairs.emplace_back(v[0], v[1]); continue; }
+        // a read with more alignments (a scan: the two flanks of every candidate at 2 q, 2 q + 1): every such pair that is here whole
+        for (size_t x = 0; x + 1 < v.size(); ++x)
+            if (!(v[x] & 1) && v[x + 1] == v[x] + 1) { pairs.emplace_back(v[x], v[x + 1]); ++x; }
+    }
     std::stable_sort(pairs.begin(), pairs.end(), [&](const std::pair<int, int>& x, const std::pair<int, int>& y) { return in.n[x.first] > in.n[y.first]; });
     const int ngr = (int)pairs.size();
     if (ngr == 0 || 2 * ngr < (nb * 9) / 10) return STRQ_OK;

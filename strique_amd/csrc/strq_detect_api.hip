@@ -20,6 +20,7 @@
 #include "viterbi_kernels.h"
 #include "mod_kernels.h"
 #include "unit_kernels.h"
+#include "scan_kernels.h"
 
 using namespace strq;
 
@@ -27,29 +28,6 @@ using namespace strq;
 static double now_s() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; }
 
 namespace strq {
-
-struct ReadGeom {           // per read, written by finalize_kernel
-    double score_prefix, score_suffix;
-    int64_t prefix_begin, prefix_end, suffix_begin, suffix_end;
-    int32_t gate, pad_;
-    float best_prefix, best_suffix;      // raw alignment scores (the overlap planning of the next sub-batch reads their distribution)
-};
-
-// position of flank row k in the read: argmin_i |a_idx[i] - b_idx[k]| of __detect_range__
-// (STRique.py:540-547) evaluated on the compact record: a diagonal row sits on its sample; a row
-// inside a vertical run sits between two samples and takes the nearer one, the lower index on a tie.
-static __device__ int64_t row_position(const int32_t* rec, int m, int k, int n)
-{
-    const int32_t r = rec[k];
-    const int64_t j = r >> 1;
-    if (!(r & 1)) return j - 1;
-    int k1 = k; while (k1 > 0 && rec[k1 - 1] == r) --k1;
-    int k2 = k; while (k2 < m - 1 && rec[k2 + 1] == r) ++k2;
-    const int d_prev = k - k1 + 1, d_next = k2 - k + 1;
-    const bool has_prev = j >= 1, has_next = j < n;
-    if (has_prev && (!has_next || d_prev <= d_next)) return j - 1;
-    return j;
-}
 
 struct FinalizeArgs {
     const AlignTask* tasks; const AlignResult* results;
@@ -71,40 +49,16 @@ __global__ void finalize_kernel(FinalizeArgs a)
     if (r >= a.n_reads) return;
     const ReadCond rc = a.rc[r];
     ReadGeom g = {};
-    VitTask vt = {};
     // the alignments run on whatever the conditioning produced (an all-NaN signal scores dist_min in every
     // cell, as it does in the reference), so the positions are reported for every non-empty read
     if (rc.n > 0) {
-        const AlignTask& tp = a.tasks[a.task_of[2 * r]]; const AlignResult& rp = a.results[a.task_of[2 * r]];
-        const AlignTask& ts = a.tasks[a.task_of[2 * r + 1]]; const AlignResult& rs = a.results[a.task_of[2 * r + 1]];
-        {
-            const int64_t b = row_position(tp.rec, tp.m_total, 0, tp.n), e = row_position(tp.rec, tp.m_total, tp.m_total - 1, tp.n);
-            g.score_prefix = e > b ? (double)rp.best / (double)(e - b) : 0.0;
-            g.best_prefix = rp.best;
-            g.prefix_begin = row_position(tp.rec, tp.m_total, a.trim[2 * r], tp.n);
-            g.prefix_end = e;
-        }
-        {
-            const int64_t b = row_position(ts.rec, ts.m_total, 0, ts.n), e = row_position(ts.rec, ts.m_total, ts.m_total - 1, ts.n);
-            g.score_suffix = e > b ? (double)rs.best / (double)(e - b) : 0.0;
-            g.best_suffix = rs.best;
-            g.suffix_begin = b;
-            g.suffix_end = row_position(ts.rec, ts.m_total, ts.m_total - 1 - a.trim[2 * r + 1], ts.n);
-        }
-        // the reference's gate (STRique.py:602) looks at the two alignments only: a read whose 8-bit morphology signal
-        // normalises while its filtered signal does not (empty percentile tails: NaN constants) still goes to the HMM,
-        // as a window of NaN observations -- pomegranate's missing-value rule, see viterbi_kernels.hip
-        g.gate = (g.prefix_begin < g.suffix_end && g.score_prefix > 0.0 && g.score_suffix > 0.0) ? 1 : 0;
-    }
-    vt.model = a.model_of[r];
-    if (g.gate) {
-        vt.T = g.suffix_end - g.prefix_begin;
-        if (a.is_f64) { vt.sig = reinterpret_cast<const double*>(a.flt) + rc.off + g.prefix_begin; vt.src_kind = VIT_SRC_F64_AFFINE; }
-        else { vt.sig = reinterpret_cast<const int16_t*>(a.flt) + rc.off + g.prefix_begin; vt.src_kind = VIT_SRC_I16_AFFINE; }
-        vt.c1 = rc.f_c1; vt.h1 = rc.f_h1; vt.h2 = rc.h2; vt.c2 = rc.c2; vt.lo = a.ps.clip_lo; vt.hi = a.ps.clip_hi;
+        const int tp = a.task_of[2 * r], ts = a.task_of[2 * r + 1];
+        prefix_geometry(a.tasks[tp], a.results[tp], a.trim[2 * r], g);
+        suffix_geometry(a.tasks[ts], a.results[ts], a.trim[2 * r + 1], g);
+        g.gate = geometry_gate(g);
     }
     a.geom[r] = g;
-    a.vit[a.vit_slot[r]] = vt;
+    a.vit[a.vit_slot[r]] = window_task(g, rc, a.model_of[r], a.flt, a.is_f64, a.ps);
 }
 
 struct Target {
@@ -120,6 +74,10 @@ struct Batch {
     int dtype = 0;                       // 0 int16, 1 float64
     std::vector<int64_t> off;            // n_reads + 1
     std::vector<int32_t> target;
+    std::vector<int32_t> target_given;   // a scan run writes the winners' targets into `target`: what the caller uploaded, for a plain run after it
+    int scan_ncand = 0;                  // the last run call was a scan over this many candidates (0: a plain detect)
+    std::vector<int32_t> cand;           // scan: winner of every read as a position in the candidate list, -1 = none
+    std::vector<double> scores;          // scan: score_prefix, score_suffix of every (read, candidate)
     std::vector<double> host_stats;      // 6 per read (float64 input only)
     DevBuf raw;                          // all reads, resident
     bool on_host = false;                // samples still (partly) in the caller's memory: uploaded sub-batch by sub-batch
@@ -138,6 +96,7 @@ struct Batch {
     {
         forget_host();
         n_reads = n; dtype = dt; uploaded = 0; host_stats.clear();
+        target_given.clear(); scan_ncand = 0; cand.clear(); scores.clear();
         results.assign((size_t)n, strq_result()); mod.assign((size_t)n, std::string("-")); reset_units(n);
     }
     float t_cond = 0, t_lut = 0, t_fwd = 0, t_trace = 0, t_vit = 0, t_total = 0;
@@ -155,6 +114,10 @@ struct DetectState {
     DevBuf rc, hist16, hist8, geom, idx, hist_raw, bp, path, modtask, modsig, modlen, pattern, hrange, modpool, f64s;
     DevBuf unit_task, unit_ws, unit_path, unit_pool;      // unit pass (run_unit_pass): tasks, records / back-pointers, state paths, positions
     bool units_on = false;               // strq_set_units
+    // strq_scan_set: run calls compare these candidates (target ids) on every read instead of taking the read's own target
+    bool scan_on = false; std::vector<int32_t> scan_cand; double scan_min = 0;
+    DevBuf scan_idx, scan_out;           // scan: task table and candidate trims / winners, scores and raw scores of a sub-batch
+    void* scan_pin = nullptr; size_t scan_pin_cap = 0;      // ... and what the host reads of them before the Viterbi launches are planned
     float unit_ms = 0; double unit_bytes = 0, unit_reads = 0, unit_positions = 0;      // strq_last_units: the last run call's unit pass
     hipEvent_t ev[4] = {};
     int64_t part_reads = 0;              // strq_batch_upload_part: reads uploaded so far
@@ -174,6 +137,7 @@ struct DetectState {
         std::vector<VitGroup> vls;       // the Viterbi launches of the sub-batch
         int vit_mode = 0;                // 0 count, 2 MARK (modification pass follows)
         bool units = false;              // the unit pass follows (strq_set_units when the sub-batch was launched)
+        bool scan = false;               // a scan sub-batch: a read without a winner has no row
         int64_t r0 = 0; int nr = 0;
         std::vector<int32_t> vit_slot;
         void* pinned = nullptr; size_t pinned_cap = 0;
@@ -236,7 +200,8 @@ void detect_state_free(strq_ctx* c)
     if (d->vit_stream) (void)hipStreamSynchronize(d->vit_stream);
     for (DevBuf* b : {&d->batch.raw, &d->rc, &d->hist16, &d->hist8, &d->geom, &d->idx,
                       &d->hist_raw, &d->bp, &d->path, &d->modtask, &d->modsig, &d->modlen, &d->pattern, &d->hrange, &d->modpool, &d->f64s,
-                      &d->unit_task, &d->unit_ws, &d->unit_path, &d->unit_pool}) b->release();
+                      &d->unit_task, &d->unit_ws, &d->unit_path, &d->unit_pool, &d->scan_idx, &d->scan_out}) b->release();
+    if (d->scan_pin) (void)hipHostFree(d->scan_pin);
     for (auto& sl : d->slot) {
         for (DevBuf* b : {&sl.flt, &sl.vit, &sl.vres, &sl.order, &sl.vq}) b->release();
         if (sl.pinned) (void)hipHostFree(sl.pinned);
@@ -640,6 +605,10 @@ static int abandon(DetectState* d, DetectState::Slot& sl, int rc)
     for (int64_t r = sl.r0; r < sl.r0 + sl.nr && r < (int64_t)B.results.size(); ++r) {
         B.results[(size_t)r] = strq_result(); B.mod[(size_t)r] = "-";
         B.units[(size_t)r].clear(); B.unit_dec[(size_t)r] = 0;
+        if (sl.scan && (size_t)r < B.cand.size()) {
+            B.cand[(size_t)r] = -1;
+            std::fill(B.scores.begin() + (ptrdiff_t)((size_t)r * 2 * B.scan_ncand), B.scores.begin() + (ptrdiff_t)((size_t)(r + 1) * 2 * B.scan_ncand), 0.0);
+        }
     }
     return rc;
 }
@@ -688,6 +657,7 @@ static int take_rows(strq_ctx* c, DetectState* d, DetectState::Slot& sl, bool un
         const ReadGeom& g = h.geom[i];
         const VitResult& v = h.vres[sl.vit_slot[i]];
         o.status = h.rc[i].status == COND_OK ? 0 : 1;
+        if (sl.scan && B.cand[(size_t)(r0 + i)] < 0) continue;          // no winner: no row (the scores of its candidates are in Batch::scores)
         o.score_prefix = g.score_prefix; o.score_suffix = g.score_suffix;
         o.prefix_begin = g.prefix_begin; o.prefix_end = g.prefix_end; o.suffix_begin = g.suffix_begin; o.suffix_end = g.suffix_end;
         o.offset = g.prefix_end; o.ticks = std::max<int64_t>(g.suffix_begin - g.prefix_end, 0);
@@ -764,10 +734,16 @@ struct SubBatch {
     int nr = 0, esz = 2;
     DetectState::Slot* sl = nullptr; DetectState::Slot* other = nullptr;
     bool any_mod = false, serial = false;
+    int nc = 0;                          // scan: candidates per read (0: a plain detect, every read with its own target)
     std::vector<ReadCond> rc; std::vector<int64_t> loff;      // per read (host): conditioning row, offset in the sub-batch
     const char* raw = nullptr; char* flt_base = nullptr; uint8_t* levels = nullptr;
     ReadCond* d_rc = nullptr; uint32_t* d_hist_raw = nullptr; uint32_t* d_range = nullptr;
     int32_t* d_task_of = nullptr; int32_t* d_trim = nullptr; int32_t* d_slot = nullptr; const VitModel** d_model_of = nullptr;
+    // scan: task table (2 * nc per read), trims (2 per candidate); scores, raw scores and winners on the device and in pinned memory
+    int32_t* d_scan_task_of = nullptr; int32_t* d_scan_trim = nullptr;
+    double* d_scores = nullptr; float* d_best = nullptr; int32_t* d_winner = nullptr;
+    const double* h_scores = nullptr; const float* h_best = nullptr; const int32_t* h_winner = nullptr;
+    size_t scan_out_bytes = 0;
 };
 
 // stage 1: the ReadCond rows and offsets of the reads (with the caller's statistics, for float64 reads that bring them)
@@ -790,8 +766,10 @@ static void read_table(DetectState* d, SubBatch& S)
             const bool okv = std::isfinite(hs[0]) && hs[1] > 0.0 && std::isfinite(hs[2]) && hs[3] > 0.0 && std::isfinite(hs[3]);
             rc.status = okv ? COND_OK : COND_DEGENERATE;
         }
-        S.any_mod |= d->targets[B.target[r0 + i]].mod_model_id >= 0;
+        if (!S.nc) S.any_mod |= d->targets[B.target[r0 + i]].mod_model_id >= 0;
     }
+    // scan: any candidate may win
+    for (int c = 0; c < S.nc; ++c) S.any_mod |= d->targets[d->scan_cand[(size_t)c]].mod_model_id >= 0;
     S.loff[nr] = S.tot;
 }
 
@@ -914,17 +892,20 @@ static int align_part(strq_ctx* c, DetectState* d, const SubBatch& S, int i0, in
     Batch& B = d->batch;
     hipStream_t st = c->stream;
     DetectState::Slot& other = *S.other;
-    const int na = 2 * np;
+    // a plain detect aligns the two flanks of the read's target; a scan those of every candidate, all on the one conditioned read
+    const int per = S.nc ? S.nc : 1;
+    const int na = 2 * per * np;
     std::vector<int32_t> a_read(na); std::vector<int> n(na), m(na), k(na), R(na), NS(na); std::vector<const float*> fl(na);
     trim.resize(na);
     int samples = 6;
-    for (int j = 0; j < np; ++j) {
-        const Target& t = d->targets[B.target[S.r0 + i0 + j]];
+    for (int j = 0; j < np; ++j) for (int ci = 0; ci < per; ++ci) {
+        const Target& t = d->targets[S.nc ? d->scan_cand[(size_t)ci] : B.target[S.r0 + i0 + j]];
+        const int p = 2 * (j * per + ci), q = p + 1;
         samples = t.samples;
-        a_read[2 * j] = a_read[2 * j + 1] = j;
-        n[2 * j] = n[2 * j + 1] = S.rc[i0 + j].n;
-        m[2 * j] = (int)t.prefix_ext.size(); k[2 * j] = t.kp; R[2 * j] = t.Rp; NS[2 * j] = t.NSp; fl[2 * j] = t.prefix_ext.data(); trim[2 * j] = t.trim_prefix;
-        m[2 * j + 1] = (int)t.suffix_ext.size(); k[2 * j + 1] = t.ks; R[2 * j + 1] = t.Rs; NS[2 * j + 1] = t.NSs; fl[2 * j + 1] = t.suffix_ext.data(); trim[2 * j + 1] = t.trim_suffix;
+        a_read[p] = a_read[q] = j;
+        n[p] = n[q] = S.rc[i0 + j].n;
+        m[p] = (int)t.prefix_ext.size(); k[p] = t.kp; R[p] = t.Rp; NS[p] = t.NSp; fl[p] = t.prefix_ext.data(); trim[p] = t.trim_prefix;
+        m[q] = (int)t.suffix_ext.size(); k[q] = t.ks; R[q] = t.Rs; NS[q] = t.NSs; fl[q] = t.suffix_ext.data(); trim[q] = t.trim_suffix;
     }
     AlignCoreIn ci;
     ci.nb = na; ci.samples = samples; ci.d_levels = S.levels; ci.read_off = S.loff.data() + i0; ci.d_level_val = c->level_val.as<float>() + (size_t)i0 * 256;
@@ -972,6 +953,75 @@ static int finalize_part(strq_ctx* c, DetectState* d, const SubBatch& S, int i0,
     return STRQ_OK;
 }
 
+// scan: the task table, the candidates' trims and the outputs of scan_select_kernel for the sub-batch
+static int scan_reserve(strq_ctx* c, DetectState* d, SubBatch& S)
+{
+    const size_t nr = (size_t)S.nr, nc = (size_t)S.nc;
+    STRQ_HIP(c, d->scan_idx.reserve((2 * nc * nr + 2 * nc) * 4 + 64));
+    S.d_scan_task_of = d->scan_idx.as<int32_t>(); S.d_scan_trim = S.d_scan_task_of + 2 * nc * nr;
+    const size_t n_sc = 2 * nc * nr;
+    S.scan_out_bytes = n_sc * 8 + n_sc * 4 + nr * 4;
+    STRQ_HIP(c, d->scan_out.reserve(S.scan_out_bytes + 64));
+    S.d_scores = d->scan_out.as<double>(); S.d_best = reinterpret_cast<float*>(S.d_scores + n_sc); S.d_winner = reinterpret_cast<int32_t*>(S.d_best + n_sc);
+    if (S.scan_out_bytes > d->scan_pin_cap) {
+        if (d->scan_pin) { STRQ_HIP(c, hipHostFree(d->scan_pin)); d->scan_pin = nullptr; d->scan_pin_cap = 0; }
+        STRQ_HIP(c, hipHostMalloc(&d->scan_pin, S.scan_out_bytes + S.scan_out_bytes / 8, hipHostMallocDefault));
+        d->scan_pin_cap = S.scan_out_bytes + S.scan_out_bytes / 8;
+    }
+    S.h_scores = static_cast<const double*>(d->scan_pin); S.h_best = reinterpret_cast<const float*>(S.h_scores + n_sc);
+    S.h_winner = reinterpret_cast<const int32_t*>(S.h_best + n_sc);
+    std::vector<int32_t> trim(2 * nc);
+    for (size_t ci = 0; ci < nc; ++ci) {
+        const Target& t = d->targets[d->scan_cand[ci]];
+        trim[2 * ci] = t.trim_prefix; trim[2 * ci + 1] = t.trim_suffix;
+    }
+    STRQ_HIP(c, hipMemcpyAsync(S.d_scan_trim, trim.data(), 2 * nc * 4, hipMemcpyHostToDevice, c->stream));
+    return STRQ_OK;
+}
+
+// scan, per upload part: positions and scores of all candidates of its reads, and the winner of each (scan_select_kernel)
+static int select_part(strq_ctx* c, DetectState* d, const SubBatch& S, int i0, int np, const AlignCoreOut& co)
+{
+    hipStream_t st = c->stream;
+    const size_t per = 2 * (size_t)S.nc;
+    const int na = (int)per * np;
+    std::vector<int32_t> task_of(na);
+    for (int pos = 0; pos < na; ++pos) task_of[co.order[pos]] = pos;
+    STRQ_HIP(c, hipMemcpyAsync(S.d_scan_task_of + per * i0, task_of.data(), (size_t)na * 4, hipMemcpyHostToDevice, st));
+    ScanSelectArgs sa;
+    sa.tasks = co.d_tasks; sa.results = co.d_results; sa.task_of = S.d_scan_task_of + per * i0; sa.trim = S.d_scan_trim; sa.rc = S.d_rc + i0;
+    sa.min_score = d->scan_min; sa.geom = d->geom.as<ReadGeom>() + i0; sa.winner = S.d_winner + i0;
+    sa.scores = S.d_scores + per * i0; sa.best = S.d_best + per * i0; sa.n_reads = np; sa.n_cand = S.nc;
+    if (launch_scan_select(st, sa)) { c->err = "scan select launch failed"; return STRQ_ERR_DEVICE; }
+    return STRQ_OK;
+}
+
+// scan: the winners of the sub-batch come back (one pinned copy, one wait on a stream that align_core has just waited on), every read
+// takes the target of its winner, and from there the sub-batch is a plain one: its Viterbi launches are grouped by kernel shape on the
+// host (plan_viterbi) and scan_task_kernel writes the winners' windows where finalize_kernel would have
+static int resolve_winners(strq_ctx* c, DetectState* d, SubBatch& S)
+{
+    Batch& B = d->batch;
+    hipStream_t st = c->stream;
+    STRQ_HIP(c, hipMemcpyAsync(d->scan_pin, d->scan_out.p, S.scan_out_bytes, hipMemcpyDeviceToHost, st));
+    STRQ_HIP(c, hipStreamSynchronize(st));
+    const size_t per = 2 * (size_t)S.nc;
+    for (int i = 0; i < S.nr; ++i) {
+        const int32_t w = S.h_winner[i];
+        if (w < -1 || w >= S.nc) { c->err = "scan: winner outside the candidate list"; return STRQ_ERR_DEVICE; }
+        B.cand[(size_t)(S.r0 + i)] = w;
+        // a read without a winner keeps a (gate 0, never decoded) task with the first candidate's model
+        B.target[(size_t)(S.r0 + i)] = d->scan_cand[(size_t)(w < 0 ? 0 : w)];
+        std::memcpy(&B.scores[(size_t)(S.r0 + i) * per], S.h_scores + (size_t)i * per, per * 8);
+    }
+    if (const int rc = plan_viterbi(c, d, S)) return rc;
+    ScanTaskArgs ta;
+    ta.geom = d->geom.as<ReadGeom>(); ta.rc = S.d_rc; ta.vit_slot = S.d_slot; ta.model_of = S.d_model_of; ta.flt = S.flt_base; ta.is_f64 = B.dtype;
+    ta.ps = d->ps; ta.vit = S.sl->vit.as<VitTask>(); ta.n_reads = S.nr;
+    if (launch_scan_tasks(st, ta)) { c->err = "scan task launch failed"; return STRQ_ERR_DEVICE; }
+    return STRQ_OK;
+}
+
 // the forward stage is queued: positions and conditioning status of the sub-batch to the host (pinned: the copies do not block), then
 // the fork: everything the Viterbi launches read is final behind `fwd_done`
 static int publish_forward(strq_ctx* c, DetectState* d, const SubBatch& S)
@@ -986,6 +1036,7 @@ static int publish_forward(strq_ctx* c, DetectState* d, const SubBatch& S)
     STRQ_HIP(c, hipEventRecord(sl.fwd_done, st));
     sl.vit_mode = S.any_mod ? 2 : 0;
     sl.units = d->units_on;
+    sl.scan = S.nc > 0;
     sl.state = DetectState::Slot::Forward;
     return STRQ_OK;
 }
@@ -998,6 +1049,16 @@ static void plan_next_overlap(strq_ctx* c, DetectState* d, const SubBatch& S)
     c->score_fracs.clear(); double sum_n = 0;
     for (int i = 0; i < S.nr; ++i) {
         if (S.rc[i].n <= 0) continue;
+        if (S.nc) {          // a scan: the next sub-batch aligns every candidate again, most of them on reads that do not hold their flanks
+            for (int ci = 0; ci < S.nc; ++ci) {
+                const Target& t = d->targets[d->scan_cand[(size_t)ci]];
+                const float* b = S.h_best + 2 * ((size_t)i * S.nc + ci);
+                c->score_fracs.push_back(b[0] / ((float)t.prefix_ext.size() * c->ap.dist_offset));
+                c->score_fracs.push_back(b[1] / ((float)t.suffix_ext.size() * c->ap.dist_offset));
+                sum_n += S.rc[i].n;
+            }
+            continue;
+        }
         const Target& t = d->targets[d->batch.target[S.r0 + i]];
         c->score_fracs.push_back(h_geom[i].best_prefix / ((float)t.prefix_ext.size() * c->ap.dist_offset));
         c->score_fracs.push_back(h_geom[i].best_suffix / ((float)t.suffix_ext.size() * c->ap.dist_offset));
@@ -1020,7 +1081,7 @@ static int complete_sub_batch(strq_ctx* c, DetectState* d, const SubBatch& S)
     if (S.serial) { const int lrc = launch_viterbi_of(c, d, sl, c->stream, nullptr); if (lrc) return lrc; }
     // the forward stage of this sub-batch is complete here (its Viterbi launches need not be)
     STRQ_HIP(c, hipEventSynchronize(sl.fwd_done));
-    c->second_round[0] = (int64_t)*sl.host().redo - c->look2_served; c->second_round[1] += 2 * (int64_t)S.nr;
+    c->second_round[0] = (int64_t)*sl.host().redo - c->look2_served; c->second_round[1] += 2 * (int64_t)S.nr * (S.nc ? S.nc : 1);
     plan_next_overlap(c, d, S);
     float ms;
     STRQ_HIP(c, hipEventElapsedTime(&ms, d->ev[0], d->ev[1])); B.t_cond += ms;
@@ -1055,9 +1116,12 @@ static int run_sub_batch(strq_ctx* c, DetectState* d, int64_t r0, int64_t r1, in
     // alignments; its second pass -- which needs the decoded repeat stretch on the host -- runs when its rows are taken, on the context's
     // stream, which is idle then: the taking thread has just waited for the following sub-batch's forward stage, or is the caller's fetch.)
     S.serial = strq::opt("STRQ_SERIAL") != nullptr;
+    S.nc = B.scan_ncand;
     read_table(d, S);
     if (const int rc = reserve_buffers(c, d, S)) return rc;
-    if (const int rc = plan_viterbi(c, d, S)) return rc;
+    // a scan plans its Viterbi launches when the winners are known (resolve_winners)
+    if (S.nc) { if (const int rc = scan_reserve(c, d, S)) return rc; }
+    else if (const int rc = plan_viterbi(c, d, S)) return rc;
     // Conditioning, the two flank alignments and the positions / gate of the reads, in `parts` pieces: a
     // sub-batch whose samples are still in the caller's buffer is uploaded piece by piece, each piece's
     // kernels running under the upload of the next (only the first piece's upload is exposed); a resident
@@ -1074,8 +1138,10 @@ static int run_sub_batch(strq_ctx* c, DetectState* d, int64_t r0, int64_t r1, in
         if (part == 0) STRQ_HIP(c, hipEventRecord(d->ev[1], c->stream));
         AlignCoreOut co; std::vector<int32_t> trim;
         if (const int rc = align_part(c, d, S, i0, np, part == 0, co, trim)) return rc;
-        if (const int rc = finalize_part(c, d, S, i0, np, co, trim)) return rc;
+        if (S.nc) { if (const int rc = select_part(c, d, S, i0, np, co)) return rc; }
+        else if (const int rc = finalize_part(c, d, S, i0, np, co, trim)) return rc;
     }
+    if (S.nc) if (const int rc = resolve_winners(c, d, S)) { sl.scan = true; return abandon(d, sl, rc); }
     if (const int rc = publish_forward(c, d, S)) return rc;
     // from here on the slot is in flight: a failure leaves no rows behind that were not computed
     if (const int rc = complete_sub_batch(c, d, S)) return abandon(d, sl, rc);
@@ -1143,14 +1209,19 @@ std::vector<int64_t> cut_sub_batches(const strq_ctx* c, const DetectState* d, in
     // alignment, four sharing one at 73 ms -- 6 x 60.6 = 5 x 73 ends without a ragged tail as well;
     // 4608 reads measured 437 ms against 365 ms for 4096).
     int64_t cap = std::min<int64_t>(16 * (int64_t)c->n_cu, 8192);      // 8192: task limit of vit_sort_kernel
-    if (const char* e = strq::opt("STRQ_SUBBATCH_READS")) { const int64_t v = atoll(e); if (v > 0) cap = std::min<int64_t>(v, 8192); }      // testing: force small sub-batches
+    // a scan aligns every read 2 * n_cand times: as many alignments per sub-batch as a plain detect has
+    if (B.scan_ncand) cap = std::max<int64_t>(1, cap / B.scan_ncand);
+    if (const char* e = strq::opt("STRQ_SUBBATCH_READS")) { const int64_t v = atoll(e); if (v > 0) cap = std::min<int64_t>(v, B.scan_ncand ? std::max<int64_t>(1, 8192 / B.scan_ncand) : 8192); }      // testing: force small sub-batches
     std::vector<int64_t> cuts(1, first);
     for (int64_t r0 = first; r0 < last;) {
         int64_t r1 = r0; size_t ck = 0; int64_t samples = 0;
         while (r1 < last && r1 - r0 < cap) {
-            const Target& t = d->targets[B.target[r1]];
             const int n = (int)(B.off[r1 + 1] - B.off[r1]);
-            const size_t need = align_workspace_bytes(n, 0, t.Rp, t.NSp) + align_workspace_bytes(n, 0, t.Rs, t.NSs);
+            size_t need = 0;
+            for (int ci = 0; ci < std::max(1, B.scan_ncand); ++ci) {
+                const Target& t = d->targets[B.scan_ncand ? d->scan_cand[(size_t)ci] : B.target[r1]];
+                need += align_workspace_bytes(n, 0, t.Rp, t.NSp) + align_workspace_bytes(n, 0, t.Rs, t.NSs);
+            }
             if (r1 > r0 && (ck + need > c->max_ws_bytes || samples + n > ((int64_t)3 << 30))) break;
             ck += need; samples += n; ++r1;
         }
@@ -1169,6 +1240,25 @@ int run_range(strq_ctx* c, DetectState* d, int64_t first, int64_t last)
     std::fill(c->overlap, c->overlap + 4, 0.0);
     c->second_round[0] = c->second_round[1] = 0; c->look2_served = 0;
     for (double& v : c->screen_stats) v = 0;
+    // Rows in flight belong to the call that launched them: a change between scan and plain detect takes them first.
+    if ((d->scan_on ? (int)d->scan_cand.size() : 0) != B.scan_ncand) {
+        if (const int rc = drain(c, d)) return rc;
+        // What the context has learnt about its workload does not carry over: three alignments in four of a scan look for a flank the
+        // read does not hold, so the screens' pauses and the score distribution of the overlap planning would send the first sub-batches
+        // of a detect after a scan (or of a scan after a detect) down the route of the other workload.
+        c->screen_pause = c->coarse_pause = 0; c->screen_fail = c->coarse_fail = 0;
+        c->score_fracs.clear(); c->mean_n = 0;
+    }
+    if (d->scan_on) {
+        if (B.target_given.empty()) B.target_given = B.target;
+        B.scan_ncand = (int)d->scan_cand.size();
+        if (B.cand.size() != (size_t)B.n_reads || B.scores.size() != (size_t)B.n_reads * 2 * (size_t)B.scan_ncand) {
+            B.cand.assign((size_t)B.n_reads, -1); B.scores.assign((size_t)B.n_reads * 2 * (size_t)B.scan_ncand, 0.0);
+        }
+    } else {
+        if (!B.target_given.empty()) { B.target = B.target_given; B.target_given.clear(); }
+        B.scan_ncand = 0; B.cand.clear(); B.scores.clear();
+    }
     B.units_ran = d->units_on;
     d->unit_ms = 0; d->unit_bytes = d->unit_reads = d->unit_positions = 0;
     STRQ_HIP(c, c->redo_total.reserve(64));
@@ -1200,6 +1290,34 @@ int run_and_fetch(strq_ctx* c, strq_result* out)
     std::memcpy(out, d->batch.results.data(), d->batch.results.size() * sizeof(strq_result));
     return STRQ_OK;
 }
+
+// the arguments of a scan: at least one candidate, every one a target of the context, a threshold above 0
+int scan_check(strq_ctx* c, const DetectState* d, int32_t n_cand, const int32_t* ids, double min_score)
+{
+    if (n_cand <= 0 || n_cand > 256 || !ids) { c->err = "scan: between 1 and 256 candidates"; return STRQ_ERR_ARG; }
+    if (!(min_score > 0.0)) { c->err = "scan: min_score must be above 0"; return STRQ_ERR_ARG; }
+    for (int32_t i = 0; i < n_cand; ++i)
+        if (ids[i] < 0 || ids[i] >= (int32_t)d->targets.size()) { c->err = "scan: unknown target id"; return STRQ_ERR_ARG; }
+    return STRQ_OK;
+}
+
+// winners and scores of the last run call (drained by the caller)
+int copy_scan(strq_ctx* c, const DetectState* d, int32_t* out_cand, double* out_scores)
+{
+    const Batch& B = d->batch;
+    if (!B.scan_ncand) { c->err = "the last run call was no scan (strq_scan_set)"; return STRQ_ERR_ARG; }
+    if (!out_cand && B.n_reads > 0) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    if (!B.cand.empty()) std::memcpy(out_cand, B.cand.data(), B.cand.size() * 4);
+    if (out_scores && !B.scores.empty()) std::memcpy(out_scores, B.scores.data(), B.scores.size() * 8);
+    return STRQ_OK;
+}
+
+// strq_detect_batch*: a plain detect whatever scan set the context holds (put back when the call is through)
+struct PlainScope {
+    DetectState* d; bool on;
+    explicit PlainScope(DetectState* d_) : d(d_), on(d_->scan_on) { d->scan_on = false; }
+    ~PlainScope() { d->scan_on = on; }
+};
 
 }  // namespace
 
@@ -1302,6 +1420,59 @@ int strq_last_units(strq_ctx* c, double* out4)
     return STRQ_OK;
 }
 
+int strq_scan_set(strq_ctx* c, int32_t n_cand, const int32_t* cand_target_id, double min_score)
+{
+    STRQ_ENTER(c);
+    DetectState* d = dstate(c);
+    if (const int rc = scan_check(c, d, n_cand, cand_target_id, min_score)) return rc;
+    if (const int rc = drain(c, d)) return rc;          // sub-batches in flight are taken as what they were launched as
+    d->scan_cand.assign(cand_target_id, cand_target_id + n_cand); d->scan_min = min_score; d->scan_on = true;
+    return STRQ_OK;
+}
+
+int strq_scan_clear(strq_ctx* c)
+{
+    STRQ_ENTER(c);
+    DetectState* d = dstate(c);
+    if (const int rc = drain(c, d)) return rc;
+    d->scan_on = false; d->scan_cand.clear(); d->scan_min = 0;
+    return STRQ_OK;
+}
+
+int strq_batch_fetch_scan(strq_ctx* c, int32_t* out_cand, double* out_scores)
+{
+    STRQ_ENTER(c);
+    DetectState* d = dstate(c);
+    if (const int rc = drain(c, d)) return rc;
+    return copy_scan(c, d, out_cand, out_scores);
+}
+
+int strq_scan_batch_reads(strq_ctx* c, int64_t n_reads, const void* const* reads, const int64_t* lengths, int32_t dtype,
+                          int32_t n_cand, const int32_t* cand_target_id, double min_score,
+                          strq_result* out_rows, int32_t* out_cand, double* out_scores)
+{
+    STRQ_ENTER(c);
+    DetectState* d = dstate(c);
+    if (const int rc = scan_check(c, d, n_cand, cand_target_id, min_score)) return rc;
+    if (n_reads < 0 || (n_reads > 0 && (!reads || !lengths || !out_rows || !out_cand))) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    std::vector<int64_t> off((size_t)n_reads + 1, 0);
+    for (int64_t i = 0; i < n_reads; ++i) {
+        if (lengths[i] < 0 || (lengths[i] > 0 && !reads[i])) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+        off[(size_t)i + 1] = off[(size_t)i] + lengths[i];
+    }
+    if (const int rc = drain(c, d)) return rc;
+    // the scan set of the context (if any) is put back when the call is through
+    const bool on0 = d->scan_on; const std::vector<int32_t> cand0 = d->scan_cand; const double min0 = d->scan_min;
+    d->scan_cand.assign(cand_target_id, cand_target_id + n_cand); d->scan_min = min_score; d->scan_on = true;
+    const std::vector<int32_t> tid((size_t)n_reads, cand_target_id[0]);      // every read's target until its winner is known
+    int rc = batch_prepare(c, n_reads, nullptr, dtype, off.data(), tid.data(), nullptr, true, reads);
+    if (!rc) rc = run_and_fetch(c, out_rows);
+    if (!rc) rc = copy_scan(c, d, out_cand, out_scores);
+    if (rc) { (void)upload_join(d); d->batch.forget_host(); }
+    d->scan_on = on0; d->scan_cand = cand0; d->scan_min = min0;
+    return rc;
+}
+
 int strq_batch_upload(strq_ctx* c, int64_t n_reads, const void* signals, int32_t dtype, const int64_t* offsets,
                       const int32_t* target_id, const double* host_stats)
 {
@@ -1331,6 +1502,7 @@ int strq_batch_upload_part(strq_ctx* c, int64_t total_reads, int64_t total_sampl
     for (int64_t i = 0; i < n_reads; ++i) {
         B.off[(size_t)(first_read + i + 1)] = base + (offsets[i + 1] - offsets[0]);
         B.target[(size_t)(first_read + i)] = target_id[i];
+        if (!B.target_given.empty()) B.target_given[(size_t)(first_read + i)] = target_id[i];
     }
     {
         const size_t need = (size_t)B.off[(size_t)(first_read + n_reads)] * 2 + 64;
@@ -1399,6 +1571,8 @@ int strq_detect_batch(strq_ctx* c, int64_t n_reads, const void* signals, int32_t
 {
     STRQ_ENTER(c);
     // signals stay in the caller's buffer and are uploaded one sub-batch ahead of the kernels
+    if (const int rc = drain(c, dstate(c))) return rc;
+    PlainScope plain_(dstate(c));
     if (const int rc = batch_prepare(c, n_reads, signals, dtype, offsets, target_id, host_stats, true)) return rc;
     return run_and_fetch(c, out);
 }
@@ -1415,6 +1589,8 @@ int strq_detect_batch_reads(strq_ctx* c, int64_t n_reads, const void* const* rea
         if (lengths[i] < 0 || (lengths[i] > 0 && !reads[i])) { c->err = "bad argument"; return STRQ_ERR_ARG; }
         off[(size_t)i + 1] = off[(size_t)i] + lengths[i];
     }
+    if (const int rc = drain(c, dstate(c))) return rc;
+    PlainScope plain_(dstate(c));
     if (const int rc = batch_prepare(c, n_reads, nullptr, dtype, off.data(), target_id, host_stats, true, reads)) return rc;
     return run_and_fetch(c, out);
 }

@@ -13,6 +13,8 @@ LIB_PATH = os.environ.get("STRQ_LIB") or os.path.join(_HERE, "lib", "libstrique_
 
 STRQ_OK, STRQ_ERR_ARG, STRQ_ERR_DEVICE, STRQ_ERR_UNSUPPORTED, STRQ_ERR_NOMEM = 0, 1, 2, 3, 4
 
+SCAN_SYMBOLS = ("strq_scan_batch_reads", "strq_scan_set", "strq_scan_clear", "strq_batch_fetch_scan")
+
 _lib = None
 
 
@@ -86,6 +88,8 @@ def load_library(path=None):
         lib.strq_ctx_destroy.argtypes = [ctypes.c_void_p]
         lib.strq_set_option.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p]
         lib.strq_get_option.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int32]
+        for name in SCAN_SYMBOLS:
+            getattr(lib, name).restype = ctypes.c_int          # a library without the scan entries is an error here, not at the first scan
         _lib = lib
     return _lib
 
@@ -404,6 +408,52 @@ class Context(object):
         self._check(self._lib.strq_detect_batch_reads(self._h, ctypes.c_int64(n), ptrs, _ptr(lengths), ctypes.c_int32(dtype),
                                                       _ptr(target_ids), None, _ptr(out)))
         return out
+
+    # ---- scan -----------------------------------------------------------------------------
+    def scan_batch_reads(self, reads, cand_ids, min_score, scores=False):
+        """strq_scan_batch_reads: every read (a list of 1-D arrays, all int16 or all float64) against every candidate (target ids);
+        returns (rows, winners) -- winners[i] the position of read i's winner in `cand_ids`, -1 = none -- or, with scores=True,
+        (rows, winners, scores[n_reads, n_cand, 2])."""
+        n = len(reads)
+        cand = _c(cand_ids, np.int32)
+        sc = np.zeros((n, len(cand), 2), np.float64)
+        if n == 0:
+            if len(cand) == 0 or not min_score > 0:
+                raise StriqueHipError(STRQ_ERR_ARG, "scan: at least one candidate, min_score above 0")
+            out = np.zeros(0, dtype=RESULT_DTYPE); win = np.zeros(0, np.int32)
+            return (out, win, sc) if scores else (out, win)
+        dt = reads[0].dtype
+        if dt == np.int16:
+            dtype = 0
+        elif dt == np.float64:
+            dtype = 1
+        else:
+            raise ValueError("signals must be int16 or float64")
+        reads = [np.ascontiguousarray(r, dtype=dt) for r in reads]
+        ptrs = (ctypes.c_void_p * n)(*[r.ctypes.data for r in reads])
+        lengths = np.array([len(r) for r in reads], np.int64)
+        self._n_batch = n
+        out = np.zeros(n, dtype=RESULT_DTYPE); win = np.full(n, -1, np.int32)
+        self._check(self._lib.strq_scan_batch_reads(self._h, ctypes.c_int64(n), ptrs, _ptr(lengths), ctypes.c_int32(dtype),
+                                                    ctypes.c_int32(len(cand)), _ptr(cand), ctypes.c_double(min_score),
+                                                    _ptr(out), _ptr(win), _ptr(sc) if scores else None))
+        return (out, win, sc) if scores else (out, win)
+
+    def scan_set(self, cand_ids, min_score):
+        """strq_scan_set: batch_run / batch_run_range scan the uploaded reads for these candidates from now on."""
+        cand = _c(cand_ids, np.int32)
+        self._check(self._lib.strq_scan_set(self._h, ctypes.c_int32(len(cand)), _ptr(cand), ctypes.c_double(min_score)))
+        self._n_cand = len(cand)
+
+    def scan_clear(self):
+        self._check(self._lib.strq_scan_clear(self._h))
+
+    def batch_fetch_scan(self, scores=False):
+        """Winners (and scores[n_reads, n_cand, 2]) of the last run call (strq_batch_fetch_scan)."""
+        n = getattr(self, '_n_batch', 0)
+        win = np.full(max(1, n), -1, np.int32); sc = np.zeros((n, getattr(self, '_n_cand', 0), 2), np.float64)
+        self._check(self._lib.strq_batch_fetch_scan(self._h, _ptr(win), _ptr(sc) if scores else None))
+        return (win[:n], sc) if scores else win[:n]
 
     def debug_conditioning(self, read, n):
         levels = np.zeros(n, np.uint8); lval = np.zeros(256, np.float32); sc = np.zeros(10)
