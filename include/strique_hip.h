@@ -35,7 +35,7 @@ extern "C" {
 typedef struct strq_ctx strq_ctx;
 
 /* Version of this ABI (bumped on any signature change). */
-int strq_abi_version(void);   /* currently 12 (12: strq_batch_fetch_range, strq_last_overlap, two sub-batches in flight; 11: strq_set_option, strq_get_option, strq_batch_upload_part, strq_last_screen_mode; 10: strq_last_screen, strq_debug_screen_plan; 9: strq_last_viterbi_launches, strq_last_second_round, strq_inflate_backend, strq_inflate_many, strq_inflate_stats, strq_h5_locate, strq_vbz_chunks; 8: strq_model_set_positions; 5: strq_host_stats, host_stats of strq_detect_batch / strq_batch_upload optional; 6: strq_detect_batch_reads; 7: strq_last_geometry, strq_batch_run_range, strq_inflate_chunks) */
+int strq_abi_version(void);   /* currently 13 (13: strq_debug_filtered; 12: strq_batch_fetch_range, strq_last_overlap, two sub-batches in flight; 11: strq_set_option, strq_get_option, strq_batch_upload_part, strq_last_screen_mode; 10: strq_last_screen, strq_debug_screen_plan; 9: strq_last_viterbi_launches, strq_last_second_round, strq_inflate_backend, strq_inflate_many, strq_inflate_stats, strq_h5_locate, strq_vbz_chunks; 8: strq_model_set_positions; 5: strq_host_stats, host_stats of strq_detect_batch / strq_batch_upload optional; 6: strq_detect_batch_reads; 7: strq_last_geometry, strq_batch_run_range, strq_inflate_chunks) */
 
 /* Create a context on HIP device `device_id`.  Fails (STRQ_ERR_DEVICE) when no GPU is present:
  * there is no CPU fallback in this library. */
@@ -320,6 +320,10 @@ int strq_inflate_backend(void);
  * last sub-batch processed by strq_batch_run. */
 int strq_debug_conditioning(strq_ctx* ctx, int64_t read, uint8_t* levels, int64_t n, float* level_val,
                             double* scalars10);
+/* Test hook: the median-filtered signal (scipy.signal.medfilt(raw, 3)) of read `read` of the last sub-batch processed by
+ * strq_batch_run, in the element type of the batch (int16 or float64): min(n, length of the read) elements to `out`.
+ * STRQ_ERR_ARG when the last sub-batch has no such read. */
+int strq_debug_filtered(strq_ctx* ctx, int64_t read, void* out, int64_t n);
 /* Test hook, host only (no context, no device): the tables strq_model_set_positions would upload for this model --
  * out_lp[31 * 64] (log-probability of every column of the layout per lane, -inf where a lane has no such edge),
  * out_own[6 * 64] (state of every slot and lane, -1 if none, -2 for a virtual relay state), out_meta[10] = {slot, lane of

@@ -25,11 +25,19 @@ namespace strq {
 #define COND_TILE 2048      // samples per workgroup (256 threads x 8)
 #define COND_HALO 16        // >= 14 = 3+4+4+3 samples of context on each side of a tile
 
+// a < b in the order np.sort uses: a NaN is larger than everything else (the median of three then drops a lone NaN, like the
+// oracle's medfilt3 and scipy's medfilt do; two of them in a window stay)
+template <class T> static __device__ __forceinline__ bool lt_nan_last(T a, T b)
+{
+    if constexpr (std::is_floating_point<T>::value) return a < b || (b != b && a == a);
+    else return a < b;
+}
 template <class T> static __device__ __forceinline__ T med3(T a, T b, T c)
 {
-    const T lo = a < b ? a : b, hi = a < b ? b : a;
-    const T m = hi < c ? hi : c;
-    return lo > m ? lo : m;
+    const bool ab = lt_nan_last(a, b);
+    const T lo = ab ? a : b, hi = ab ? b : a;
+    const T m = lt_nan_last(hi, c) ? hi : c;
+    return lt_nan_last(m, lo) ? lo : m;
 }
 
 // scipy.ndimage 'reflect' (d c b a | a b c d | d c b a), valid for any offset
@@ -42,8 +50,7 @@ static __device__ __forceinline__ int reflect_idx(int i, int n)
 
 template <class T>
 __global__ void __launch_bounds__(256)
-medfilt_kernel(const T* __restrict__ raw_all, T* __restrict__ flt_all, const ReadCond* __restrict__ rc_all,
-               uint32_t* __restrict__ hist_flt, uint32_t* __restrict__ hist_raw)
+medfilt_kernel(const T* __restrict__ raw_all, T* __restrict__ flt_all, const ReadCond* __restrict__ rc_all)
 {
     const ReadCond rc = rc_all[blockIdx.y];
     const int n = rc.n;
@@ -60,7 +67,6 @@ medfilt_kernel(const T* __restrict__ raw_all, T* __restrict__ flt_all, const Rea
         const T m = med3<T>(a, c, b);
         flt[i] = m;
     }
-    (void)hist_flt; (void)hist_raw;
 }
 
 // 65536-bin histogram of an int16 signal.  One workgroup takes HIST_TILE consecutive samples of
@@ -771,14 +777,14 @@ int launch_medfilt_hist_i16(hipStream_t s, const int16_t* raw, int16_t* flt, con
     const dim3 vgrid((max_n + 7 + HIST_TILE - 1) / HIST_TILE, n_reads);
     if (hist_flt && same_phase) hipLaunchKernelGGL(medfilt_hist16_vec_kernel, vgrid, dim3(256), 0, s, raw, flt, rc, hist_flt, range4, 4);
     else if (hist_flt) hipLaunchKernelGGL(medfilt_hist16_kernel, hgrid, dim3(256), 0, s, raw, flt, rc, hist_flt, range4, 4);
-    else hipLaunchKernelGGL((medfilt_kernel<int16_t>), tile_grid(max_n, n_reads), dim3(256), 0, s, raw, flt, rc, hist_flt, hist_raw);
+    else return 1;      // int16 reads are always filtered together with their histogram
     if (hist_raw) hipLaunchKernelGGL(hist16_kernel, hgrid, dim3(256), 0, s, raw, rc, hist_raw, range4 ? range4 + 2 : nullptr, 4);
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 int launch_medfilt_f64(hipStream_t s, const double* raw, double* flt, const ReadCond* rc, int n_reads, int max_n)
 {
     if (n_reads <= 0 || max_n <= 0) return 0;
-    hipLaunchKernelGGL((medfilt_kernel<double>), tile_grid(max_n, n_reads), dim3(256), 0, s, raw, flt, rc, (uint32_t*)nullptr, (uint32_t*)nullptr);
+    hipLaunchKernelGGL((medfilt_kernel<double>), tile_grid(max_n, n_reads), dim3(256), 0, s, raw, flt, rc);
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 int launch_f64_stats(hipStream_t s, const double* flt, const double* raw, ReadCond* rc, int n_reads, double* chunk_sums, const int64_t* chunk_first)

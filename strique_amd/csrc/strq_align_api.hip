@@ -1384,7 +1384,7 @@ static int run_align_batch(strq_ctx* c, const BatchIn& in, const BatchOut& out)
 
 extern "C" {
 
-int strq_abi_version(void) { return 12; }
+int strq_abi_version(void) { return 13; }
 
 int strq_set_option(strq_ctx* c, const char* key, const char* value)
 {

@@ -179,6 +179,8 @@ struct DetectState {
     int up_rc = 0;
     hipStream_t vit_stream = nullptr;
     int levels_shift = 0;                // bytes the level stream of the current sub-batch starts behind the buffer's base (alignment phase)
+    // strq_debug_filtered: the slot that holds the filtered signal of the last sub-batch, the bytes it starts behind the buffer's base, its reads
+    int last_slot = -1, flt_shift = 0, last_nr = 0;
     hipStream_t copy_stream = nullptr;   // host -> HBM uploads that overlap the kernels of the previous sub-batch
     static constexpr int N_STAGE = 4;    // pinned staging ring of upload_reads
     void* stage[N_STAGE] = {}; hipEvent_t stage_ev[N_STAGE] = {}; bool stage_busy[N_STAGE] = {};
@@ -796,6 +798,7 @@ static int reserve_buffers(strq_ctx* c, DetectState* d, SubBatch& S)
     // the filtered signal of the sub-batch starts at the same offset inside a 16-byte line as its raw signal, so that the
     // conditioning kernels can move both with aligned 16-byte accesses
     S.flt_base = S.sl->flt.as<char>() + (reinterpret_cast<uintptr_t>(S.raw) & 15);
+    d->last_slot = (int)(S.sl - d->slot); d->flt_shift = (int)(reinterpret_cast<uintptr_t>(S.raw) & 15); d->last_nr = nr;
     // levels: the same sample phase as the raw / filtered signal, so that a tile's eight-level groups are 8-byte aligned
     d->levels_shift = (int)((reinterpret_cast<uintptr_t>(S.raw) & 15) >> (S.esz == 2 ? 1 : 4));
     S.levels = c->levels.as<uint8_t>() + d->levels_shift;
@@ -1610,6 +1613,22 @@ int strq_debug_conditioning(strq_ctx* c, int64_t read, uint8_t* levels, int64_t 
         const double v[10] = {rc.med, rc.mad, rc.f_c1, rc.f_h1, rc.m_c1, rc.m_h1, rc.r_c1, rc.r_h1, rc.h2, rc.c2};
         std::memcpy(scalars10, v, sizeof(v));
     }
+    return STRQ_OK;
+}
+
+// the median-filtered samples of read `read` of the last sub-batch, in the batch's element type: the slot's buffer outlives the
+// sub-batch (it is reallocated only when a later sub-batch reserves it)
+int strq_debug_filtered(strq_ctx* c, int64_t read, void* out, int64_t n)
+{
+    STRQ_ENTER(c);
+    DetectState* d = dstate(c);
+    if (const int drc = drain(c, d)) return drc;
+    if (d->last_slot < 0 || read < 0 || read >= d->last_nr || n < 0 || (n > 0 && !out)) { c->err = "no such read in the last sub-batch"; return STRQ_ERR_ARG; }
+    const size_t esz = d->batch.dtype == 0 ? 2 : 8;
+    ReadCond rc;
+    STRQ_HIP(c, hipMemcpy(&rc, d->rc.as<ReadCond>() + read, sizeof(rc), hipMemcpyDeviceToHost));
+    const size_t count = (size_t)std::min<int64_t>(n, rc.n);
+    if (count) STRQ_HIP(c, hipMemcpy(out, d->slot[d->last_slot].flt.as<char>() + d->flt_shift + (size_t)rc.off * esz, count * esz, hipMemcpyDeviceToHost));
     return STRQ_OK;
 }
 

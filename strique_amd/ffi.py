@@ -460,6 +460,15 @@ class Context(object):
         self._check(self._lib.strq_debug_conditioning(self._h, ctypes.c_int64(read), _ptr(levels), ctypes.c_int64(n), _ptr(lval), _ptr(sc)))
         return levels, lval, sc
 
+    def debug_filtered(self, read, n, dtype=np.int16):
+        """strq_debug_filtered: the first `n` median-filtered samples of read `read` of the last sub-batch; `dtype` is the
+        element type of the batch (int16 or float64)."""
+        out = np.zeros(n, np.dtype(dtype))
+        if out.dtype not in (np.dtype(np.int16), np.dtype(np.float64)):
+            raise ValueError("dtype must be int16 or float64")
+        self._check(self._lib.strq_debug_filtered(self._h, ctypes.c_int64(read), _ptr(out), ctypes.c_int64(n)))
+        return out
+
 
 RESULT_DTYPE = np.dtype([("count", np.int32), ("status", np.int32), ("score_prefix", np.float64),
                          ("score_suffix", np.float64), ("log_p", np.float64), ("offset", np.int64),
