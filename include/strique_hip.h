@@ -147,6 +147,30 @@ int strq_viterbi_batch(strq_ctx* ctx, int32_t model_id, int64_t n_seq, const dou
                        int32_t* paths);
 
 /*
+ * HiddenMarkovModel.log_probability(x) -- the forward algorithm, a sum over all paths where strq_viterbi takes the best one --
+ * and the spread of the visit count over those paths, for n_seq windows (x_off[n_seq + 1], at most 8192 windows).
+ *   log_lik      log sum_paths P(path, x); never below strq_viterbi's logp but for rounding (-inf and status 1 without a path)
+ *   visits_mean  E[v | x], v = observations a path emits from count_inc states (what `counted` is on the best path)
+ *   visits_var   Var[v | x], clamped at 0 (NaN, like the mean, without a path)
+ *   c0[n_seq]    nullable: the moments are accumulated about c0[i] -- pass the window's `counted`; they stay O(1) then, where
+ *                moments about zero lose the variance of a count near 1000 to cancellation.  Any value gives the same
+ *                mathematical result.
+ * float64, one wave per window, deterministic: the same window gives the same bits whatever else is in the call.  Missing
+ * observations (NaN) have probability 1 under every distribution, as in strq_viterbi.  Models on the wave-per-window kernels
+ * (strq_model_create) whose counted states are emitting states; others return STRQ_ERR_UNSUPPORTED, strq_last_error says why.
+ * No count bias is applied: raw visits.
+ */
+int strq_forward_batch(strq_ctx* ctx, int32_t model_id, int64_t n_seq, const double* x, const int64_t* x_off,
+                       const int64_t* c0, double* log_lik, double* visits_mean, double* visits_var, int32_t* status);
+/*
+ * Optional, after strq_model_create: in_logp_sum[e] for every in-edge e of the arrays given there.  Where the baked graph holds
+ * ONE edge for several parallel paths of the original graph (two spliced silent states between the same pair of states), in_logp
+ * carries the largest of them -- all a best-path decode needs -- and in_logp_sum the log of their summed probability, which a sum
+ * over paths needs; equal to in_logp everywhere else.  Only the forward pass reads it.  STRQ_ERR_ARG when an entry is below in_logp's.
+ */
+int strq_model_set_forward_logp(strq_ctx* ctx, int32_t model_id, const double* in_logp_sum);
+
+/*
  * ---- repeatCounter.add_target / detect (scripts/STRique.py:553-618) as one device pipeline ----
  *
  * strq_set_pore_stats   the four model-side constants of pore_model.normalize2model('minmax')
@@ -209,6 +233,20 @@ int strq_batch_fetch_units(strq_ctx* ctx, int64_t* pool, int64_t pool_cap, int64
 /* The unit pass of the last run call: out[0] = ms on the GPU (all its sub-batches), out[1] = largest workspace of unit records /
  * back-pointers one piece of it used (bytes), out[2] = windows decoded, out[3] = positions. */
 int strq_last_units(strq_ctx* ctx, double* out4);
+/* Count confidence: with on = 1, later run calls also run the forward pass (strq_forward_batch) over the window
+ * [prefix_begin, suffix_end) of every read whose gate passed and whose flanked-model decode found a path -- the same observations,
+ * normalised and clipped, that the decode saw, with c0 = the visits of the best path.  Rows, modification patterns and unit
+ * positions do not change.  Sub-batches still in flight keep the mode they were launched with (the call waits for them).
+ * Default 0: no further kernel runs and no further buffer is reserved. */
+int strq_set_confidence(strq_ctx* ctx, int32_t on);
+/* Confidence of the last batch: out3[3 i .. 3 i + 3) = log_lik, count_mean = count_bias + E[v | x], count_sd = sqrt(Var[v | x])
+ * of read i; decoded[i] (nullable) = 1 when the read was decoded, 0 when not (its three values are NaN).  A decoded window
+ * without a path in the forward pass (see forward_kernels.hip on range) reports -inf, NaN, NaN.  STRQ_ERR_ARG when the last
+ * run call ran with confidence off. */
+int strq_batch_fetch_confidence(strq_ctx* ctx, double* out3, int32_t* decoded);
+/* The forward pass of the last run call: out[0] = ms on the GPU (all its sub-batches), out[1] = windows processed,
+ * out[2] = of them, windows without a path, out[3] = largest rescale exponent of a window (|log2| of its likelihood). */
+int strq_last_confidence(strq_ctx* ctx, double* out4);
 int strq_detect_batch(strq_ctx* ctx, int64_t n_reads, const void* signals, int32_t dtype,
                       const int64_t* offsets, const int32_t* target_id, const double* host_stats,
                       strq_result* out);

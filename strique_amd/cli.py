@@ -23,6 +23,8 @@ import numpy as np
 HEADER = ['ID', 'target', 'strand', 'count', 'score_prefix', 'score_suffix', 'log_p', 'offset', 'ticks', 'mod']
 # `count --units FILE`: the raw-signal sample of every repeat unit on the decoded Viterbi path, one row per count row
 UNITS_HEADER = ['ID', 'target', 'strand', 'count', 'n_units', 'units']
+# `count --confidence FILE`: forward log-likelihood and posterior mean / standard deviation of the count, one row per count row
+CONF_HEADER = ['ID', 'target', 'strand', 'count', 'log_p', 'log_lik', 'count_mean', 'count_sd']
 LEVELS = ['error', 'warning', 'info', 'debug']
 
 
@@ -227,6 +229,9 @@ def count(argv):
     parser.add_argument("--share-device", action="store_true", help="testing: every rank uses --device instead of its LOCAL_RANK")
     parser.add_argument("--units", default=None, metavar="FILE", help="Also write the repeat-unit positions (raw-signal sample of every repeat unit "
                                                                         "on the decoded path) to FILE: one row per count row, columns " + " ".join(UNITS_HEADER))
+    parser.add_argument("--confidence", default=None, metavar="FILE", help="Also write how far to trust each count to FILE: the forward log-likelihood of the decoded "
+                                                                             "window (all paths, where log_p is the best one) and the posterior mean and standard deviation "
+                                                                             "of the count; one row per count row, columns " + " ".join(CONF_HEADER))
     parser.add_argument("--scan", action="store_true", help="No alignment: every read of the index is compared with every target of the repeat config on both strands, "
                                                              "from its raw signal alone, and counted for the one it spans (if any).  Excludes --algn; stdin is not read")
     parser.add_argument("--scan-min-score", type=float, default=None, metavar="X", help="--scan: the smallest min(score_prefix, score_suffix) a target and strand needs to be "
@@ -235,6 +240,8 @@ def count(argv):
                                                                             "with or without a winner (what a threshold for one's own data is chosen from)")
     parser.add_argument("--strict", action="store_true", help="Exit with status 2 when any read could not be processed (the reference only logs such reads and exits 0)")
     args = parser.parse_args(argv)
+    if args.scan and args.confidence:
+        parser.error("--confidence cannot be combined with --scan: the forward pass runs on reads whose target and strand an alignment gives")
     if args.scan and args.algn:
         parser.error("--scan takes the target and strand of a read from its signal: it cannot be combined with --algn")
     if not args.scan and (args.scan_scores or args.scan_min_score is not None):
@@ -291,6 +298,7 @@ def count(argv):
     scores_out = open(args.scan_scores, 'w') if (args.scan_scores and rank == 0) else None
     out = (open(args.out, 'w') if args.out else sys.stdout) if rank == 0 else None
     units_out = open(args.units, 'w') if (args.units and rank == 0) else None
+    conf_out = open(args.confidence, 'w') if (args.confidence and rank == 0) else None
     readers = args.t
     if readers <= 0:
         # one process per GPU: every rank takes its share of the cores (LOCAL_WORLD_SIZE is set by torchrun) for its reader threads, at most
@@ -307,7 +315,8 @@ def count(argv):
     fault = 0
     try:
         rows = run_count(stream, loci, f5.get_raw, counter, log, args.batch, rank, world, out if world == 1 else None, readers=readers, stats=stats,
-                         units=bool(args.units), units_out=units_out if world == 1 else None, scan=scan, scores_out=scores_out if world == 1 else None)
+                         units=bool(args.units), units_out=units_out if world == 1 else None, scan=scan, scores_out=scores_out if world == 1 else None,
+                         confidence=bool(args.confidence), conf_out=conf_out if world == 1 else None)
     except DeviceFault:
         if world == 1:
             raise SystemExit(3)
@@ -321,13 +330,17 @@ def count(argv):
                 log("Main: a rank reported a device error; no output written.", 'error')
             dist.destroy_process_group()
             raise SystemExit(3)
-        merged = gather_rows(rows, stats["items"], sdist, units=bool(args.units), scan=scan)
+        merged = gather_rows(rows, stats["items"], sdist, units=bool(args.units), scan=scan, confidence=bool(args.confidence))
         if scan:
             merged, merged_units, merged_scores = merged
+        elif args.confidence:
+            merged, merged_units, merged_conf = merged
         elif args.units:
             merged, merged_units = merged
         if rank == 0:
             write_rows(out, merged)
+            if conf_out is not None:
+                write_rows(conf_out, merged_conf, header=CONF_HEADER)
             if units_out is not None:
                 write_rows(units_out, merged_units, header=UNITS_HEADER)
             if scores_out is not None:
@@ -338,6 +351,8 @@ def count(argv):
         out.close()
     if units_out is not None:
         units_out.close()
+    if conf_out is not None:
+        conf_out.close()
     if scores_out is not None:
         scores_out.close()
     if stats.get("failed"):
@@ -394,7 +409,37 @@ def parse_units(stream):
     return out
 
 
-def gather_rows(rows, items, sdist, units=False, scan=None):
+def format_confidence(qname, target, strand, n, log_p, conf):
+    """One row of the `count --confidence` file: count and log_p as the count row has them, then log_lik, count_mean, count_sd
+    (str() of the floats, like the count TSV), '-' three times for a read that was not decoded."""
+    tail = ['-', '-', '-'] if conf is None else [str(float(x)) for x in conf]
+    return '\t'.join([str(qname), str(target), str(strand), str(n), str(log_p)] + tail)
+
+
+def parse_confidence(stream):
+    """Rows of a `count --confidence` file: [(ID, target, strand, count, log_p, (log_lik, count_mean, count_sd) or None)]."""
+    out = []
+    for line in stream:
+        f = line.rstrip('\n').split('\t')
+        if not line.strip() or f[0] == CONF_HEADER[0]:
+            continue
+        conf = None if f[5] == '-' else (float(f[5]), float(f[6]), float(f[7]))
+        out.append((f[0], f[1], f[2], int(f[3]), float(f[4]), conf))
+    return out
+
+
+def _split_result(res, units, confidence):
+    """(row tuple, unit positions or None, confidence or None) of one result of counter.detect_batch(..., units, confidence)."""
+    if units and confidence:
+        return res
+    if units:
+        return res[0], res[1], None
+    if confidence:
+        return res[0], None, res[1]
+    return res, None, None
+
+
+def gather_rows(rows, items, sdist, units=False, scan=None, confidence=False):
     """Rows of this rank -> fixed-size records + modification strings -> one gather -> on rank 0 the
     merged [(sequence number, TSV row)] in input order (None elsewhere).  `items`: every accepted
     (qname, strand, target) of the input, which each rank derives from the same SAM file.
@@ -402,7 +447,10 @@ def gather_rows(rows, items, sdist, units=False, scan=None):
     modification string ("mod<TAB>p,p,..."), and the return value is (rows, unit rows) -- (None, None) off rank 0.
     scan (the dict of run_count): every result is (winner, scores) -- winner None or (target, strand, result as above); target,
     strand and the scores travel in front of the blob ("target<TAB>strand<TAB>s,s,...<TAB>..."), a read without a winner as a
-    record with valid = 2; the return value is (rows, unit rows or None, score rows) -- Nones off rank 0."""
+    record with valid = 2; the return value is (rows, unit rows or None, score rows) -- Nones off rank 0.
+    confidence=True (not with scan): every result is (row tuple, conf) -- (row tuple, positions, conf) with units -- conf being
+    (log_lik, count_mean, count_sd) or None; the three values travel at the end of the same blob ("...<TAB>l,m,s", repr() of the
+    floats, '-' for None), and the return value is (rows, unit rows or None, confidence rows) -- Nones off rank 0."""
     from . import scan as scan_mod
     rec = np.zeros(len(rows), ROW_DTYPE); mods = []; idx = np.zeros(len(rows), np.int64)
     for k, (seq, res) in enumerate(rows):
@@ -418,16 +466,17 @@ def gather_rows(rows, items, sdist, units=False, scan=None):
                 rec[k]["valid"] = 2; mods.append(head)
                 continue
             res = winner[2]
-        pos = None
-        if units:
-            res, pos = res
+        res, pos, conf = _split_result(res, units, confidence)
         n, sp, ss, p, offset, ticks, mod = res
         rec[k] = (n, 1, sp, ss, float(p), offset, ticks)
-        mods.append(head + (mod + '\t' + (','.join(str(int(x)) for x in pos) if pos is not None and len(pos) else '-') if units else mod))
+        blob = mod + '\t' + (','.join(str(int(x)) for x in pos) if pos is not None and len(pos) else '-') if units else mod
+        if confidence:
+            blob += '\t' + ('-' if conf is None else ','.join(repr(float(x)) for x in conf))
+        mods.append(head + blob)
     full, full_mods = sdist.gather_results(rec, idx, len(items), mods)
     if full is None:
-        return (None, None, None) if scan else ((None, None) if units else None)
-    merged = []; merged_units = []; merged_scores = []
+        return (None, None, None) if (scan or confidence) else ((None, None) if units else None)
+    merged = []; merged_units = []; merged_scores = []; merged_conf = []
     for seq, (qname, strand, target) in enumerate(items):
         r = full[seq]
         if not r["valid"]:
@@ -441,6 +490,9 @@ def gather_rows(rows, items, sdist, units=False, scan=None):
         n = int(r["count"]); lp = float(r["log_p"])
         p = lp if (n or lp != 0) else 0              # the reference prints the integer 0 for a failed gate (STRique.py:602,616)
         mod = full_mods[seq]
+        if confidence:
+            mod, cstr = mod.rsplit('\t', 1)
+            merged_conf.append((seq, format_confidence(qname, target, strand, n, p, None if cstr == '-' else [float(x) for x in cstr.split(',')])))
         if units:
             mod, ustr = mod.split('\t', 1)
             merged_units.append((seq, format_units(qname, target, strand, n, [] if ustr == '-' else ustr.split(','))))
@@ -448,6 +500,8 @@ def gather_rows(rows, items, sdist, units=False, scan=None):
                                                                  int(r["offset"]), int(r["ticks"]), mod))))
     if scan:
         return merged, (merged_units if units else None), merged_scores
+    if confidence:
+        return merged, (merged_units if units else None), merged_conf
     return (merged, merged_units) if units else merged
 
 
@@ -475,7 +529,7 @@ def route(stream, loci, log):
 
 
 def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, out=None, readers=0, stats=None, units=False, units_out=None,
-              scan=None, scores_out=None):
+              scan=None, scores_out=None, confidence=False, conf_out=None):
     """Route the SAM records of `stream` to their targets, run this rank's share through
     `counter.detect_batch` and return [(sequence number, result tuple or TSV row)].
 
@@ -493,7 +547,10 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
     `scan` ({"min_score", "candidates", "scores"}): `stream` is a list of read ids instead of a SAM stream; every read goes through
     counter.scan_batch and takes target and strand from its winner -- a read without one writes no row, as a read without a target
     writes none; single process: the score rows (strique_amd.scan.format_scores, every read) go to `scores_out`; several ranks: the
-    reads are dealt out by position (no SAM, no lengths) and the results are (winner, scores) pairs for `gather_rows(..., scan=scan)`."""
+    reads are dealt out by position (no SAM, no lengths) and the results are (winner, scores) pairs for `gather_rows(..., scan=scan)`.
+    `confidence` (not with scan): the results also carry (log_lik, count_mean, count_sd) or None (counter.detect_batch(...,
+    confidence=True)); single process: their rows (format_confidence) go to `conf_out` and to stats["conf_rows"]; several ranks:
+    the results go to `gather_rows(..., confidence=True)` as they are."""
     from . import scan as scan_mod
     from .ffi import StriqueHipError, STRQ_ERR_ARG, STRQ_ERR_UNSUPPORTED
     if stats is None:
@@ -503,10 +560,16 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
         print('\t'.join(HEADER), file=out)
     if units_out is not None:
         print('\t'.join(UNITS_HEADER), file=units_out)
+    if conf_out is not None:
+        print('\t'.join(CONF_HEADER), file=conf_out)
     if scores_out is not None:
         print('\t'.join(scan_mod.scores_header(scan["candidates"])), file=scores_out)
     stats.setdefault("unit_rows", [])
     stats.setdefault("score_rows", [])
+    stats.setdefault("conf_rows", [])
+    extras = dict(units=True) if units else {}
+    if confidence:
+        extras["confidence"] = True
     rows = []
     records = ((rid, '.', ['.'], 0) for rid in stream) if scan else route(stream, loci, log)
     mine_set = None
@@ -536,10 +599,8 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
         try:
             if scan:
                 results = scan_some([raw for _, _, _, _, raw in batch])
-            elif units:
-                results = counter.detect_batch([(t, raw, s) for _, _, t, s, raw in batch], units=True)
             else:
-                results = counter.detect_batch([(t, raw, s) for _, _, t, s, raw in batch])
+                results = counter.detect_batch([(t, raw, s) for _, _, t, s, raw in batch], **extras)
         except StriqueHipError as e:
             if e.code not in (STRQ_ERR_ARG, STRQ_ERR_UNSUPPORTED):
                 # a device fault or an out-of-memory condition will not go away read by read
@@ -553,7 +614,7 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
             results = []
             for _, _, t, s, raw in batch:
                 try:
-                    results.append(scan_some([raw])[0] if scan else (counter.detect(t, raw, s, units=True) if units else counter.detect(t, raw, s)))
+                    results.append(scan_some([raw])[0] if scan else counter.detect(t, raw, s, **extras))
                 except StriqueHipError as e1:
                     if e1.code not in (STRQ_ERR_ARG, STRQ_ERR_UNSUPPORTED):
                         faulted.set()
@@ -562,7 +623,7 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
                     log("Detector: read failed: %s" % e1, 'warning'); results.append(None); failed += 1
                 except Exception as e1:
                     log("Detector: read failed: %s" % e1, 'warning'); results.append(None); failed += 1
-        done = []; udone = []; sdone = []
+        done = []; udone = []; sdone = []; cdone = []
         for (seq, qname, target, strand, _), res in zip(batch, results):
             if world > 1:
                 done.append((seq, res))
@@ -574,11 +635,16 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
                     if winner is None:
                         continue
                     target, strand, res = winner
+                if scan:
+                    res, pos, conf = _split_result(res, units, False)
+                else:
+                    res, pos, conf = _split_result(res, units, confidence)
                 if units:
-                    res, pos = res
                     udone.append((seq, format_units(qname, target, strand, res[0], pos)))
+                if confidence:
+                    cdone.append((seq, format_confidence(qname, target, strand, res[0], res[3], conf)))
                 done.append((seq, format_row(qname, target, strand, res)))
-        return (done, udone, sdone), failed
+        return (done, udone, sdone, cdone), failed
 
     # The batches run on an engine thread, one at a time and in order, while this thread routes the next SAM records and
     # collects their signals: the GPU call of batch k overlaps the host-side preparation of batch k + 1 (at 50 kb per read
@@ -589,11 +655,14 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
 
     def collect(keep):
         while len(in_flight) > keep:
-            (done, udone, sdone), failed = in_flight.popleft().result()          # re-raises DeviceFault from the engine thread
+            (done, udone, sdone, cdone), failed = in_flight.popleft().result()          # re-raises DeviceFault from the engine thread
             stats["failed"] += failed
             rows.extend(done)
             stats["unit_rows"].extend(udone)
             stats["score_rows"].extend(sdone)
+            stats["conf_rows"].extend(cdone)
+            if conf_out is not None:
+                write_rows(conf_out, cdone, header=False)
             if scores_out is not None:
                 write_rows(scores_out, sdone, header=False)
             if out is not None:

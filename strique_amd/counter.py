@@ -88,11 +88,15 @@ class repeatCounter(object):
         raise ValueError("RepeatCounter: Strand must be + or -.")
 
     # -------------------------------------------------------------------------------------
-    def detect_batch(self, items, units=False):
+    def detect_batch(self, items, units=False, confidence=False):
         """items: iterable of (target_name, raw_signal, strand).  Returns a list of the tuples
         detect() returns, in input order.  units=True: a list of (tuple, positions) instead, positions being the
         raw-signal sample indices of the repeat units on the decoded Viterbi path (one np.int64 array per read, ascending;
-        None when the read was not decoded -- gate failed, no path; strq_set_units)."""
+        None when the read was not decoded -- gate failed, no path; strq_set_units).
+        confidence=True: a list of (tuple, conf) -- (tuple, positions, conf) with units=True -- conf being (log_lik, count_mean,
+        count_sd) as floats: the forward log-likelihood of the decoded window over all paths (log_p is the best one's), and the
+        posterior mean and standard deviation of the count (count_bias included); None when the read was not decoded
+        (strq_set_confidence)."""
         items = list(items)
         if not items:
             return []
@@ -109,17 +113,22 @@ class repeatCounter(object):
             arrs = [sigs[i].astype(np.int16 if want_int else np.float64, copy=False) for i in idx]
             if units:
                 self.ctx.set_units(True)
+            if confidence:
+                self.ctx.set_confidence(True)
             try:
                 res = self.ctx.detect_batch_reads(arrs, [tcs[i].target_id for i in idx])      # one pointer per read: no host-side concatenation
                 mods = self.ctx.batch_fetch_mod() if self.pm is not self.pm_mod else ['-'] * len(res)
                 pos = self.ctx.batch_fetch_units() if units else [None] * len(res)
+                conf = self.ctx.batch_fetch_confidence() if confidence else [None] * len(res)
             finally:
                 if units:
                     self.ctx.set_units(False)
-            for i, r, m, u in zip(idx, res, mods, pos):
+                if confidence:
+                    self.ctx.set_confidence(False)
+            for i, r, m, u, cf in zip(idx, res, mods, pos, conf):
                 n = int(r['count']); p = float(r['log_p']) if n or r['log_p'] != 0 else 0
                 row = (n, float(r['score_prefix']), float(r['score_suffix']), p, int(r['offset']), int(r['ticks']), m)
-                out[i] = (row, u) if units else row
+                out[i] = ((row, u) if units else (row,)) + (cf,) if confidence else ((row, u) if units else row)
         return out
 
     def candidates(self, targets=None):
@@ -184,7 +193,8 @@ class repeatCounter(object):
             return True
         return s.size == 0 or (int(s.min()) >= -32768 and int(s.max()) <= 32767)
 
-    def detect(self, target_name, raw_signal, strand, units=False):
+    def detect(self, target_name, raw_signal, strand, units=False, confidence=False):
         """(n, score_prefix, score_suffix, log_p, offset, ticks, mod_pattern) -- STRique.py:581-618.  units=True:
-        (that tuple, unit positions or None) -- see detect_batch."""
-        return self.detect_batch([(target_name, raw_signal, strand)], units=units)[0]
+        (that tuple, unit positions or None); confidence=True: (that tuple, [positions,] (log_lik, count_mean, count_sd) or
+        None) -- see detect_batch."""
+        return self.detect_batch([(target_name, raw_signal, strand)], units=units, confidence=confidence)[0]

@@ -10,6 +10,7 @@
 #include <mutex>
 #include "align_kernels.h"
 #include "viterbi_kernels.h"
+#include "forward_kernels.h"
 #include "screen_kernels.h"
 #include "strq_opt.h"
 
@@ -73,6 +74,14 @@ struct HostModel {
     int32_t n_states = 0, silent_start = 0, start = 0, end = 0;
     std::vector<int32_t> in_ptr, in_src, emis_kind, count_inc, state_tag;
     std::vector<double> in_logp, emis_a, emis_b, emis_c;
+    // forward pass (forward_kernels.h): which CSR in-edge every entry of the image's edge rows / chain edges holds (-1: padding),
+    // rounds of its silent phase, the per-edge log-probabilities of a sum over paths where they differ from in_logp
+    // (strq_model_set_forward_logp), and the image of transition probabilities, built on first use
+    std::vector<int32_t> edge_csr, chain_csr;
+    int32_t fwd_stages = 1;
+    std::vector<double> fwd_logp;
+    DevBuf fwd_blob;
+    const FwdModel* fwd_dev = nullptr;
 };
 
 }  // namespace strq
@@ -141,6 +150,8 @@ void detect_state_free(strq_ctx* c);
 int detect_drain(strq_ctx* c);              // rows of every detect sub-batch in flight taken (strq_detect_api.hip); nothing to do without detect state
 // launch_viterbi's return code as a status of the C ABI.  2 / 3: this kernel shape has no such decode mode -- the caller's input, not a device fault
 int viterbi_launch_status(int vrc);
+// the forward image of a model (HostModel::fwd_dev), built if it is not there; STRQ_ERR_UNSUPPORTED (c->err says why) for a model without one
+int forward_model(strq_ctx* c, HostModel* hm);
 void host_stats_batch(const double* signals, const int64_t* offsets, int64_t n_reads, bool want_raw, double* out,
                       const double* const* reads = nullptr);   // host_stats.hip; reads: one buffer per read instead of `signals`
 }

@@ -20,6 +20,7 @@
 #include "viterbi_kernels.h"
 #include "mod_kernels.h"
 #include "unit_kernels.h"
+#include "forward_kernels.h"
 #include "scan_kernels.h"
 
 using namespace strq;
@@ -91,6 +92,10 @@ struct Batch {
     std::vector<std::vector<int64_t>> units;      // unit positions per read (strq_batch_fetch_units)
     std::vector<uint8_t> unit_dec;       // 1: the read was decoded (gate passed, the flanked model found a path)
     void reset_units(int64_t n) { units.assign((size_t)n, std::vector<int64_t>()); unit_dec.assign((size_t)n, 0); units_ran = false; }
+    bool conf_ran = false;               // the last run call ran the forward pass (strq_set_confidence)
+    std::vector<double> conf;            // log_lik, count_mean, count_sd per read (strq_batch_fetch_confidence); empty until a run call with confidence on
+    std::vector<uint8_t> conf_dec;
+    void clear_conf(int64_t r) { if ((size_t)r < conf_dec.size()) { conf[3 * (size_t)r] = conf[3 * (size_t)r + 1] = conf[3 * (size_t)r + 2] = NAN; conf_dec[(size_t)r] = 0; } }
     // a new batch of n reads: rows, patterns and unit positions at their initial values, no samples uploaded, nothing of the caller's referenced
     void begin(int64_t n, int dt)
     {
@@ -98,6 +103,7 @@ struct Batch {
         n_reads = n; dtype = dt; uploaded = 0; host_stats.clear();
         target_given.clear(); scan_ncand = 0; cand.clear(); scores.clear();
         results.assign((size_t)n, strq_result()); mod.assign((size_t)n, std::string("-")); reset_units(n);
+        conf.clear(); conf_dec.clear(); conf_ran = false;
     }
     float t_cond = 0, t_lut = 0, t_fwd = 0, t_trace = 0, t_vit = 0, t_total = 0;
     double n_hard = 0;
@@ -114,6 +120,9 @@ struct DetectState {
     DevBuf rc, hist16, hist8, geom, idx, hist_raw, bp, path, modtask, modsig, modlen, pattern, hrange, modpool, f64s;
     DevBuf unit_task, unit_ws, unit_path, unit_pool;      // unit pass (run_unit_pass): tasks, records / back-pointers, state paths, positions
     bool units_on = false;               // strq_set_units
+    bool conf_on = false;                // strq_set_confidence
+    DevBuf conf_task;                    // forward pass (run_conf_pass): tasks, model images, c0, results, order
+    float conf_ms = 0; double conf_windows = 0, conf_nopath = 0, conf_expo = 0;      // strq_last_confidence: the last run call's forward pass
     // strq_scan_set: run calls compare these candidates (target ids) on every read instead of taking the read's own target
     bool scan_on = false; std::vector<int32_t> scan_cand; double scan_min = 0;
     DevBuf scan_idx, scan_out;           // scan: task table and candidate trims / winners, scores and raw scores of a sub-batch
@@ -137,6 +146,7 @@ struct DetectState {
         std::vector<VitGroup> vls;       // the Viterbi launches of the sub-batch
         int vit_mode = 0;                // 0 count, 2 MARK (modification pass follows)
         bool units = false;              // the unit pass follows (strq_set_units when the sub-batch was launched)
+        bool conf = false;               // the forward pass follows (strq_set_confidence when the sub-batch was launched)
         bool scan = false;               // a scan sub-batch: a read without a winner has no row
         int64_t r0 = 0; int nr = 0;
         std::vector<int32_t> vit_slot;
@@ -202,7 +212,7 @@ void detect_state_free(strq_ctx* c)
     if (d->vit_stream) (void)hipStreamSynchronize(d->vit_stream);
     for (DevBuf* b : {&d->batch.raw, &d->rc, &d->hist16, &d->hist8, &d->geom, &d->idx,
                       &d->hist_raw, &d->bp, &d->path, &d->modtask, &d->modsig, &d->modlen, &d->pattern, &d->hrange, &d->modpool, &d->f64s,
-                      &d->unit_task, &d->unit_ws, &d->unit_path, &d->unit_pool, &d->scan_idx, &d->scan_out}) b->release();
+                      &d->unit_task, &d->unit_ws, &d->unit_path, &d->unit_pool, &d->conf_task, &d->scan_idx, &d->scan_out}) b->release();
     if (d->scan_pin) (void)hipHostFree(d->scan_pin);
     for (auto& sl : d->slot) {
         for (DevBuf* b : {&sl.flt, &sl.vit, &sl.vres, &sl.order, &sl.vq}) b->release();
@@ -501,6 +511,84 @@ static int run_unit_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
     return STRQ_OK;
 }
 
+// Count confidence of the reads of one sub-batch (strq_set_confidence): the forward pass (forward_kernels.hip) over the windows the
+// count / MARK launch decoded, with the same tasks -- same windows, same affine source on the slot's filtered signal -- and c0 = the
+// visits of the best path from the rows just taken.  Runs on the context's stream like the unit pass; one launch per kernel shape.
+static int run_conf_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
+{
+    Batch& B = d->batch;
+    hipStream_t st = c->stream;
+    const int64_t r0 = sl.r0; const int nr = sl.nr;
+    const ReadGeom* geom = sl.host().geom; const VitResult* vres = sl.host().vres;
+    std::vector<int> who;                      // reads with a decode: gate passed, the flanked model found a path
+    for (int i = 0; i < nr; ++i) {
+        B.clear_conf(r0 + i);
+        if (geom[i].gate && vres[sl.vit_slot[i]].status == 0) who.push_back(i);
+    }
+    if (who.empty()) return STRQ_OK;
+    STRQ_HIP(c, hipEventRecord(d->ev[2], st));
+    std::vector<VitTask> vt((size_t)nr);
+    STRQ_HIP(c, hipMemcpyAsync(vt.data(), sl.vit.p, (size_t)nr * sizeof(VitTask), hipMemcpyDeviceToHost, st));
+    STRQ_HIP(c, hipStreamSynchronize(st));
+    std::map<int, std::vector<int>> groups;          // kernel shape -> reads
+    for (int i : who) {
+        HostModel* hm = c->models[d->targets[B.target[r0 + i]].model_id];
+        if (const int rc = forward_model(c, hm)) return rc;
+        groups[vit_shape_of(hm->h)].push_back(i);
+    }
+    const int m = (int)who.size();
+    STRQ_HIP(c, d->conf_task.reserve((size_t)m * (sizeof(VitTask) + sizeof(FwdResult) + 8 + 8 + 4) + 256));
+    VitTask* d_vt = d->conf_task.as<VitTask>();
+    FwdResult* d_fr = reinterpret_cast<FwdResult*>(d_vt + m);
+    const FwdModel** d_fm = reinterpret_cast<const FwdModel**>(d_fr + m);
+    int64_t* d_c0 = reinterpret_cast<int64_t*>(d_fm + m);
+    int* d_order = reinterpret_cast<int*>(d_c0 + m);
+    std::vector<VitTask> tv((size_t)m); std::vector<const FwdModel*> fv((size_t)m); std::vector<int64_t> cv((size_t)m); std::vector<int> read_of((size_t)m);
+    std::vector<VitGroup> launches;
+    int at = 0;
+    for (auto& g : groups) {
+        const int first = at; int mx = 0;
+        for (int i : g.second) {
+            HostModel* hm = c->models[d->targets[B.target[r0 + i]].model_id];
+            tv[(size_t)at] = vt[(size_t)sl.vit_slot[i]]; tv[(size_t)at].bp = nullptr;
+            fv[(size_t)at] = hm->fwd_dev; cv[(size_t)at] = vres[sl.vit_slot[i]].counted; read_of[(size_t)at] = i;
+            mx = std::max(mx, hm->h.n_cells); ++at;
+        }
+        launches.push_back({g.first, first, at - first, mx});
+    }
+    STRQ_HIP(c, hipMemcpyAsync(d_vt, tv.data(), (size_t)m * sizeof(VitTask), hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, hipMemcpyAsync(d_fm, fv.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, hipMemcpyAsync(d_c0, cv.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, c->queue.reserve(1024));
+    STRQ_HIP(c, hipMemsetAsync(c->queue.p, 0, 1024, st));
+    int every = 1;
+    if (const char* e = strq::opt("STRQ_FWD_RESCALE_EVERY")) { const int v = atoi(e); if (v >= 1) every = v; }
+    int qi = 0;
+    for (const VitGroup& l : launches) {
+        if (launch_vit_sort(st, d_vt + l.first, l.count, d_order + l.first)) { c->err = "forward pass: sort launch failed"; return STRQ_ERR_DEVICE; }
+        const int lrc = launch_forward(st, l.shape, l.max_cells, d_vt + l.first, d_fm + l.first, d_c0 + l.first, d_fr + l.first, l.count,
+                                       c->queue.as<int>() + qi++, c->n_cu, d_order + l.first, every);
+        if (lrc) { c->err = lrc == 2 ? "forward pass: no kernel for this model's layout" : "forward launch failed"; return lrc == 2 ? STRQ_ERR_UNSUPPORTED : STRQ_ERR_DEVICE; }
+    }
+    std::vector<FwdResult> fr((size_t)m);
+    STRQ_HIP(c, hipMemcpyAsync(fr.data(), d_fr, (size_t)m * sizeof(FwdResult), hipMemcpyDeviceToHost, st));
+    STRQ_HIP(c, hipEventRecord(d->ev[3], st));
+    STRQ_HIP(c, hipStreamSynchronize(st));
+    for (int k = 0; k < m; ++k) {
+        const int64_t r = r0 + read_of[(size_t)k];
+        double ll, mean, var;
+        const int nopath = fwd_finish(fr[(size_t)k], cv[(size_t)k], &ll, &mean, &var);
+        B.conf[3 * (size_t)r] = ll;
+        B.conf[3 * (size_t)r + 1] = nopath ? mean : (double)d->targets[B.target[r]].count_bias + mean;
+        B.conf[3 * (size_t)r + 2] = nopath ? var : std::sqrt(var);
+        B.conf_dec[(size_t)r] = 1;
+        d->conf_nopath += nopath; d->conf_expo = std::max(d->conf_expo, std::fabs((double)fr[(size_t)k].expo));
+    }
+    d->conf_windows += m;
+    float ms = 0; STRQ_HIP(c, hipEventElapsedTime(&ms, d->ev[2], d->ev[3])); d->conf_ms += ms;
+    return STRQ_OK;
+}
+
 // bytes [pos, pos + len) of the batch (reads back to back) from the caller's memory: one buffer, or one per read
 static void host_bytes(const Batch& B, size_t esz, char* dst, size_t pos, size_t len)
 {
@@ -607,6 +695,7 @@ static int abandon(DetectState* d, DetectState::Slot& sl, int rc)
     for (int64_t r = sl.r0; r < sl.r0 + sl.nr && r < (int64_t)B.results.size(); ++r) {
         B.results[(size_t)r] = strq_result(); B.mod[(size_t)r] = "-";
         B.units[(size_t)r].clear(); B.unit_dec[(size_t)r] = 0;
+        B.clear_conf(r);
         if (sl.scan && (size_t)r < B.cand.size()) {
             B.cand[(size_t)r] = -1;
             std::fill(B.scores.begin() + (ptrdiff_t)((size_t)r * 2 * B.scan_ncand), B.scores.begin() + (ptrdiff_t)((size_t)(r + 1) * 2 * B.scan_ncand), 0.0);
@@ -687,8 +776,10 @@ static int take_rows(strq_ctx* c, DetectState* d, DetectState::Slot& sl, bool un
     publish_timing(c, B);
     // the mode the launches ran with decides, not what the targets say by now
     if (sl.vit_mode == 2) { const int mrc = run_mod_pass(c, d, sl); if (mrc) return mrc; }
-    if (sl.units) return run_unit_pass(c, d, sl);
-    for (int i = 0; i < nr; ++i) { B.units[(size_t)(r0 + i)].clear(); B.unit_dec[(size_t)(r0 + i)] = 0; }
+    if (sl.units) { const int urc = run_unit_pass(c, d, sl); if (urc) return urc; }
+    else for (int i = 0; i < nr; ++i) { B.units[(size_t)(r0 + i)].clear(); B.unit_dec[(size_t)(r0 + i)] = 0; }
+    if (sl.conf) return run_conf_pass(c, d, sl);
+    for (int i = 0; i < nr; ++i) B.clear_conf(r0 + i);
     return STRQ_OK;
 }
 
@@ -1039,6 +1130,7 @@ static int publish_forward(strq_ctx* c, DetectState* d, const SubBatch& S)
     STRQ_HIP(c, hipEventRecord(sl.fwd_done, st));
     sl.vit_mode = S.any_mod ? 2 : 0;
     sl.units = d->units_on;
+    sl.conf = d->conf_on;
     sl.scan = S.nc > 0;
     sl.state = DetectState::Slot::Forward;
     return STRQ_OK;
@@ -1264,6 +1356,9 @@ int run_range(strq_ctx* c, DetectState* d, int64_t first, int64_t last)
     }
     B.units_ran = d->units_on;
     d->unit_ms = 0; d->unit_bytes = d->unit_reads = d->unit_positions = 0;
+    B.conf_ran = d->conf_on;
+    if (d->conf_on && B.conf_dec.size() != (size_t)B.n_reads) { B.conf.assign(3 * (size_t)B.n_reads, NAN); B.conf_dec.assign((size_t)B.n_reads, 0); }
+    d->conf_ms = 0; d->conf_windows = d->conf_nopath = d->conf_expo = 0;
     STRQ_HIP(c, c->redo_total.reserve(64));
     STRQ_HIP(c, hipMemsetAsync(c->redo_total.p, 0, 64, c->stream));
     // partition into sub-batches first, so that the upload of piece k + 1 can overlap the kernels of piece k
@@ -1420,6 +1515,39 @@ int strq_last_units(strq_ctx* c, double* out4)
     if (!c || !out4) return STRQ_ERR_ARG;
     DetectState* d = dstate(c);
     out4[0] = d->unit_ms; out4[1] = d->unit_bytes; out4[2] = d->unit_reads; out4[3] = d->unit_positions;
+    return STRQ_OK;
+}
+
+int strq_set_confidence(strq_ctx* c, int32_t on)
+{
+    STRQ_ENTER(c);
+    if (on != 0 && on != 1) { c->err = "bad argument (strq_set_confidence takes 0 or 1)"; return STRQ_ERR_ARG; }
+    DetectState* d = dstate(c);
+    // sub-batches in flight keep the mode they were launched with: their forward pass (or none) runs now
+    if (const int rc = drain(c, d)) return rc;
+    d->conf_on = on != 0;
+    return STRQ_OK;
+}
+
+int strq_batch_fetch_confidence(strq_ctx* c, double* out3, int32_t* decoded)
+{
+    STRQ_ENTER(c);
+    if (!out3) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    DetectState* d = dstate(c);
+    if (const int rc = drain(c, d)) return rc;
+    const Batch& B = d->batch;
+    if (!B.conf_ran) { c->err = "the last batch ran without confidence (strq_set_confidence)"; return STRQ_ERR_ARG; }
+    if (!B.conf.empty()) std::memcpy(out3, B.conf.data(), B.conf.size() * 8);
+    if (decoded) for (size_t i = 0; i < B.conf_dec.size(); ++i) decoded[i] = B.conf_dec[i];
+    return STRQ_OK;
+}
+
+int strq_last_confidence(strq_ctx* c, double* out4)
+{
+    STRQ_ENTER(c);
+    if (!out4) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    DetectState* d = dstate(c);
+    out4[0] = d->conf_ms; out4[1] = d->conf_windows; out4[2] = d->conf_nopath; out4[3] = d->conf_expo;
     return STRQ_OK;
 }
 

@@ -100,11 +100,11 @@ int build_vit_model(strq_ctx* c, int32_t n_states, int32_t silent_start, int32_t
     // silent states: chains.  The chain predecessor of b is its highest-numbered silent predecessor
     // (the last in-edge in evaluation order, so a strict '>' reproduces the tie rule) if that state
     // does not already lead another chain.
-    std::vector<int> chain_pred(n_states, -1), chain_succ(n_states, -1); std::vector<double> chain_lp(n_states, 0.0);
+    std::vector<int> chain_pred(n_states, -1), chain_succ(n_states, -1), chain_e(n_states, -1); std::vector<double> chain_lp(n_states, 0.0);
     for (int b = ne; b < n_states; ++b) {
-        int a = -1; double lpv = 0;
-        for (int e = in_ptr[b]; e < in_ptr[b + 1]; ++e) if (in_src[e] >= ne) { a = in_src[e]; lpv = in_logp[e]; }
-        if (a >= 0 && chain_succ[a] < 0) { chain_pred[b] = a; chain_succ[a] = b; chain_lp[b] = lpv; }
+        int a = -1, ae = -1; double lpv = 0;
+        for (int e = in_ptr[b]; e < in_ptr[b + 1]; ++e) if (in_src[e] >= ne) { a = in_src[e]; lpv = in_logp[e]; ae = e; }
+        if (a >= 0 && chain_succ[a] < 0) { chain_pred[b] = a; chain_succ[a] = b; chain_lp[b] = lpv; chain_e[b] = ae; }
     }
     std::vector<std::vector<int>> chains;
     for (int b = ne; b < n_states; ++b) if (chain_pred[b] < 0) { std::vector<int> ch; for (int x = b; x >= 0; x = chain_succ[x]) ch.push_back(x); chains.push_back(ch); }
@@ -196,16 +196,31 @@ int build_vit_model(strq_ctx* c, int32_t n_states, int32_t silent_start, int32_t
     m.start_cell = cell_of[start]; m.end_cell = cell_of[end];
     std::vector<int32_t> src((size_t)std::max(rows, 1) * 64, m.n_cells - 1);   // padding -> the -inf cell
     std::vector<double> lp((size_t)std::max(rows, 1) * 64, 0.0);
+    hm->edge_csr.assign((size_t)std::max(rows, 1) * 64, -1);
     auto fill = [&](int state, int base, int lane) {
         for (int e = in_ptr[state], j = 0; e < in_ptr[state + 1]; ++e) {
             if (state >= ne && is_chain_edge(state, in_src[e])) continue;
             src[(size_t)(base + j) * 64 + lane] = cell_of[in_src[e]];
             lp[(size_t)(base + j) * 64 + lane] = in_logp[e];
+            hm->edge_csr[(size_t)(base + j) * 64 + lane] = e;
             ++j;
         }
     };
     for (int s = 0; s < epl; ++s) for (int lane = 0; lane < 64; ++lane) if (own_e[s * 64 + lane] >= 0) fill(own_e[s * 64 + lane], m.e_base[s], lane);
     for (int s = 0; s < spl2; ++s) for (int lane = 0; lane < 64; ++lane) if (own_s[s * 64 + lane] >= 0) fill(own_s[s * 64 + lane], m.s_base[s], lane);
+    // forward pass: the CSR edge behind every chain edge, and how many silent states a path can cross through edges that are
+    // not chain edges (the silent phase of forward_kernel runs once more for each)
+    hm->chain_csr.assign((size_t)spl2 * 64, -1);
+    for (int i = 0; i < spl2 * 64; ++i) if (own_s[i] >= 0 && chain_src_v[i] >= 0) hm->chain_csr[i] = chain_e[own_s[i]];
+    {
+        std::vector<int> depth(n_states, 0); int deepest = 0;
+        for (int b = ne; b < n_states; ++b) {
+            int dp = 0;
+            for (int e = in_ptr[b]; e < in_ptr[b + 1]; ++e) if (in_src[e] >= ne) dp = std::max(dp, depth[in_src[e]] + (is_chain_edge(b, in_src[e]) ? 0 : 1));
+            depth[b] = dp; deepest = std::max(deepest, dp);
+        }
+        hm->fwd_stages = deepest + 1;
+    }
     std::vector<int32_t> kind((size_t)epl * 64, 0); std::vector<double> a((size_t)epl * 64, 0.0), b(a), cc(a);
     for (int i = 0; i < epl * 64; ++i) if (own_e[i] >= 0) { const int e = own_e[i]; kind[i] = emis_kind[e]; a[i] = emis_a[e]; b[i] = emis_b[e]; cc[i] = emis_c[e]; }
     m.uni_lo_max = -INFINITY; m.uni_hi_min = INFINITY;
@@ -545,6 +560,33 @@ int build_vit_g2(strq_ctx* c, HostModel* hm, const int32_t* kind_hint, const int
     }
 }
 
+// Forward image of a model: the transition probabilities behind the rows of its lane layout (FwdModel).  exp() of the per-edge
+// log-probabilities runs here, on the host, once per model.
+int forward_model(strq_ctx* c, HostModel* hm)
+{
+    if (hm->fwd_dev) return STRQ_OK;
+    if (hm->h.csr) { c->err = "forward pass: the model has no lane layout (more than 512 emitting / 256 silent states or more than 8 in-edges per state)"; return STRQ_ERR_UNSUPPORTED; }
+    for (int l = 0; l < hm->n_states && !hm->count_inc.empty(); ++l)
+        if (hm->count_inc[l] != 0 && (l >= hm->silent_start || hm->count_inc[l] != 1)) { c->err = "forward pass: counted states must be emitting states with an increment of 1"; return STRQ_ERR_UNSUPPORTED; }
+    if (vit_shape_of(hm->h) < 0) { c->err = "forward pass: model does not fit a compiled kernel"; return STRQ_ERR_UNSUPPORTED; }
+    const std::vector<double>& lp = hm->fwd_logp.empty() ? hm->in_logp : hm->fwd_logp;
+    std::vector<double> ew(hm->edge_csr.size(), 0.0), cw(hm->chain_csr.size(), 0.0);
+    for (size_t i = 0; i < ew.size(); ++i) if (hm->edge_csr[i] >= 0) ew[i] = std::exp(lp[(size_t)hm->edge_csr[i]]);
+    for (size_t i = 0; i < cw.size(); ++i) if (hm->chain_csr[i] >= 0) cw[i] = std::exp(lp[(size_t)hm->chain_csr[i]]);
+    const size_t o_c = (ew.size() * 8 + 15) & ~(size_t)15, o_m = o_c + ((cw.size() * 8 + 15) & ~(size_t)15), total = o_m + sizeof(FwdModel);
+    if (hm->fwd_blob.reserve(total) != hipSuccess) { c->err = "out of device memory"; return STRQ_ERR_NOMEM; }
+    char* d = hm->fwd_blob.as<char>();
+    FwdModel F; std::memset(&F, 0, sizeof(F));
+    F.vit = hm->dev; F.edge_w = reinterpret_cast<const double*>(d); F.chain_w = reinterpret_cast<const double*>(d + o_c); F.n_stages = hm->fwd_stages;
+    std::vector<char> host(total, 0);
+    std::memcpy(&host[0], ew.data(), ew.size() * 8);
+    if (!cw.empty()) std::memcpy(&host[o_c], cw.data(), cw.size() * 8);
+    std::memcpy(&host[o_m], &F, sizeof(F));
+    if (hipMemcpy(d, host.data(), total, hipMemcpyHostToDevice) != hipSuccess) { c->err = "model upload failed"; return STRQ_ERR_DEVICE; }
+    hm->fwd_dev = reinterpret_cast<const FwdModel*>(d + o_m);
+    return STRQ_OK;
+}
+
 }  // namespace strq
 
 int strq::viterbi_launch_status(int vrc) { return vrc == 0 ? STRQ_OK : (vrc == 2 || vrc == 3) ? STRQ_ERR_UNSUPPORTED : STRQ_ERR_DEVICE; }
@@ -674,6 +716,71 @@ int strq_viterbi_batch(strq_ctx* c, int32_t model_id, int64_t n_seq, const doubl
     STRQ_HIP(c, hipEventElapsedTime(&c->timing[0], c->ev[0], c->ev[1]));
     STRQ_HIP(c, hipEventElapsedTime(&c->timing[1], c->ev[1], c->ev[2]));
     c->timing[3] = c->timing[0] + c->timing[1];
+    return STRQ_OK;
+}
+
+int strq_model_set_forward_logp(strq_ctx* c, int32_t model_id, const double* in_logp_sum)
+{
+    STRQ_ENTER(c);
+    if (model_id < 0 || model_id >= (int32_t)c->models.size() || !c->models[model_id] || !in_logp_sum) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    HostModel* hm = c->models[model_id];
+    for (size_t e = 0; e < hm->in_logp.size(); ++e)
+        if (!(in_logp_sum[e] >= hm->in_logp[e])) { c->err = "the summed log-probability of an edge is below its largest term"; return STRQ_ERR_ARG; }
+    // a detect sub-batch in flight may be about to run its forward pass on the present image
+    { const int rc = detect_drain(c); if (rc) return rc; }
+    hm->fwd_logp.assign(in_logp_sum, in_logp_sum + hm->in_logp.size());
+    hm->fwd_dev = nullptr;          // built again on the next forward pass
+    return STRQ_OK;
+}
+
+int strq_forward_batch(strq_ctx* c, int32_t model_id, int64_t n_seq, const double* x, const int64_t* x_off, const int64_t* c0,
+                       double* log_lik, double* visits_mean, double* visits_var, int32_t* status)
+{
+    STRQ_ENTER(c);
+    if (model_id < 0 || model_id >= (int32_t)c->models.size() || !c->models[model_id] || n_seq < 0 || n_seq > 8192 || (n_seq > 0 && !x_off)) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    if (n_seq == 0) return STRQ_OK;
+    const int64_t tot = x_off[n_seq];
+    if (tot < 0 || (tot > 0 && !x)) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    for (int64_t i = 0; i < n_seq; ++i) if (x_off[i + 1] < x_off[i] || x_off[i] < 0) { c->err = "bad argument (x_off must not decrease)"; return STRQ_ERR_ARG; }
+    HostModel* hm = c->models[model_id];
+    if (const int rc = forward_model(c, hm)) return rc;
+    hipStream_t st = c->stream;
+    STRQ_HIP(c, c->vit_x.reserve((size_t)tot * 8 + 64));
+    if (tot) STRQ_HIP(c, hipMemcpyAsync(c->vit_x.p, x, (size_t)tot * 8, hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, c->vit_tasks.reserve((size_t)n_seq * (sizeof(VitTask) + sizeof(FwdResult) + 8 + 8 + 4) + 64));
+    VitTask* d_tasks = c->vit_tasks.as<VitTask>();
+    FwdResult* d_res = reinterpret_cast<FwdResult*>(d_tasks + n_seq);
+    const FwdModel** d_fm = reinterpret_cast<const FwdModel**>(d_res + n_seq);
+    int64_t* d_c0 = reinterpret_cast<int64_t*>(d_fm + n_seq);
+    int* d_order = reinterpret_cast<int*>(d_c0 + n_seq);
+    std::vector<VitTask> tasks(n_seq); std::vector<const FwdModel*> fms((size_t)n_seq, hm->fwd_dev); std::vector<int64_t> c0v((size_t)n_seq, 0);
+    for (int64_t i = 0; i < n_seq; ++i) {
+        VitTask& t = tasks[i];
+        std::memset(&t, 0, sizeof(t));
+        t.model = hm->dev; t.sig = c->vit_x.as<double>() + x_off[i]; t.T = x_off[i + 1] - x_off[i]; t.src_kind = VIT_SRC_F64;
+        if (c0) c0v[(size_t)i] = c0[i];
+    }
+    STRQ_HIP(c, hipMemcpyAsync(d_tasks, tasks.data(), (size_t)n_seq * sizeof(VitTask), hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, hipMemcpyAsync(d_fm, fms.data(), (size_t)n_seq * 8, hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, hipMemcpyAsync(d_c0, c0v.data(), (size_t)n_seq * 8, hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, c->queue.reserve(1024));
+    STRQ_HIP(c, hipMemsetAsync(c->queue.p, 0, 1024, st));
+    if (launch_vit_sort(st, d_tasks, (int)n_seq, d_order)) { c->err = "forward pass: sort launch failed"; return STRQ_ERR_DEVICE; }
+    int every = 1;
+    if (const char* e = strq::opt("STRQ_FWD_RESCALE_EVERY")) { const int v = atoi(e); if (v >= 1) every = v; }
+    const int lrc = launch_forward(st, vit_shape_of(hm->h), hm->h.n_cells, d_tasks, d_fm, d_c0, d_res, (int)n_seq, c->queue.as<int>(), c->n_cu, d_order, every);
+    if (lrc) { c->err = lrc == 2 ? "forward pass: no kernel for this model's layout" : "forward launch failed"; return lrc == 2 ? STRQ_ERR_UNSUPPORTED : STRQ_ERR_DEVICE; }
+    std::vector<FwdResult> res(n_seq);
+    STRQ_HIP(c, hipMemcpyAsync(res.data(), d_res, (size_t)n_seq * sizeof(FwdResult), hipMemcpyDeviceToHost, st));
+    STRQ_HIP(c, hipStreamSynchronize(st));
+    for (int64_t i = 0; i < n_seq; ++i) {
+        double ll, mean, var;
+        const int s = fwd_finish(res[i], c0v[(size_t)i], &ll, &mean, &var);
+        if (log_lik) log_lik[i] = ll;
+        if (visits_mean) visits_mean[i] = mean;
+        if (visits_var) visits_var[i] = var;
+        if (status) status[i] = s;
+    }
     return STRQ_OK;
 }
 

@@ -251,6 +251,11 @@ class Context(object):
         self._check(self._lib.strq_model_create(self._h, ctypes.c_int32(baked.n_states), ctypes.c_int32(baked.silent_start),
                                                 ctypes.c_int32(baked.start), ctypes.c_int32(baked.end),
                                                 *[_ptr(a) for a in arrs], ctypes.byref(mid)))
+        psum = getattr(baked, 'in_logp_sum', None)
+        if psum is not None and len(psum) == len(baked.in_logp) and np.all(psum >= baked.in_logp) and not np.array_equal(psum, baked.in_logp):
+            # edges that stand for several parallel paths: the forward pass sums them (the decode took the largest).  Arrays whose
+            # in_logp was replaced after bake() carry a sum that no longer belongs to them: their in_logp stands alone
+            self._check(self._lib.strq_model_set_forward_logp(self._h, mid, _ptr(_c(baked.in_logp_sum, np.float64))))
         self.last_positions_rc = None
         if getattr(baked, 'pos_kind', None) is not None:
             # optional register-resident image (profile chains); a model that is no such chain keeps its lane layout
@@ -274,6 +279,24 @@ class Context(object):
         if want_path:
             paths = [paths[off[i]:off[i + 1]] for i in range(n)]
         return logp, counted, status, paths
+
+    def forward_batch(self, model_id, xs, c0=None):
+        """strq_forward_batch: xs a list of float64 arrays; c0 None or one int per window (the moments are accumulated about it:
+        pass the Viterbi visit count).  Returns (log_lik[], visits_mean[], visits_var[], status[])."""
+        n = len(xs)
+        off = np.zeros(n + 1, np.int64)
+        for i, s in enumerate(xs):
+            off[i + 1] = off[i] + len(s)
+        x = np.concatenate([_c(s, np.float64) for s in xs]) if n else np.zeros(0)
+        if len(x) == 0:
+            x = np.zeros(1)
+        ll = np.zeros(n); mean = np.zeros(n); var = np.zeros(n); status = np.zeros(n, np.int32)
+        c0a = None if c0 is None else _c(c0, np.int64)
+        if c0a is not None and len(c0a) != n:
+            raise ValueError("c0 must have one entry per window")
+        self._check(self._lib.strq_forward_batch(self._h, ctypes.c_int32(model_id), ctypes.c_int64(n), _ptr(x), _ptr(off), _ptr(c0a),
+                                                 _ptr(ll), _ptr(mean), _ptr(var), _ptr(status)))
+        return ll, mean, var, status
 
     def viterbi(self, model_id, x, want_path=True):
         logp, counted, status, paths = self.viterbi_batch(model_id, [x], want_path)
@@ -323,6 +346,24 @@ class Context(object):
         out = np.zeros(4)
         self._check(self._lib.strq_last_units(self._h, _ptr(out)))
         return {'ms': float(out[0]), 'ws_bytes': float(out[1]), 'windows': int(out[2]), 'positions': int(out[3])}
+
+    def set_confidence(self, on):
+        """strq_set_confidence: later run calls also run the forward pass over every decoded window (batch_fetch_confidence)."""
+        self._check(self._lib.strq_set_confidence(self._h, ctypes.c_int32(1 if on else 0)))
+
+    def batch_fetch_confidence(self):
+        """Confidence of the last batch: per read (log_lik, count_mean, count_sd) as Python floats, or None for a read that was
+        not decoded (strq_batch_fetch_confidence)."""
+        n = getattr(self, '_n_batch', 0)
+        out = np.zeros((max(1, n), 3), np.float64); dec = np.zeros(max(1, n), np.int32)
+        self._check(self._lib.strq_batch_fetch_confidence(self._h, _ptr(out), _ptr(dec)))
+        return [(float(out[i, 0]), float(out[i, 1]), float(out[i, 2])) if dec[i] else None for i in range(n)]
+
+    def last_confidence(self):
+        """The forward pass of the last run call: {'ms', 'windows', 'no_path', 'max_exponent'} (strq_last_confidence)."""
+        out = np.zeros(4)
+        self._check(self._lib.strq_last_confidence(self._h, _ptr(out)))
+        return {'ms': float(out[0]), 'windows': int(out[1]), 'no_path': int(out[2]), 'max_exponent': int(out[3])}
 
     def batch_upload(self, signals, offsets, target_ids, host_stats=None):
         """signals: one concatenated int16 or float64 array; offsets: n_reads + 1."""

@@ -257,7 +257,8 @@ BakedHMM = namedtuple("BakedHMM", [
     "names", "orig_index",
     "hint_slot", "hint_lane",               # placement hints (-1 = none), see strq_model_create
     "pos_kind", "pos_index",                # position of every emitting state along the profile chain (None = unknown), see strq_model_set_positions
-], defaults=(None, None))
+    "in_logp_sum",                          # per in-edge: log of the summed probability of the parallel edges it stands for (None = in_logp), see strq_model_set_forward_logp
+], defaults=(None, None, None))
 
 
 def bake(g, count_states=(), tag_substring=None, tag2_states=()):
@@ -308,10 +309,15 @@ def bake(g, count_states=(), tag_substring=None, tag2_states=()):
     # single edge with the larger probability.  (pomegranate's networkx DiGraph would keep
     # whichever of the two it happened to re-insert last -- an order that depends on id() hashes
     # and differs between runs of the reference; see DESIGN.md "unpinned semantics".)
-    best = {}
+    # A sum over paths (the forward pass, strq_forward_batch) needs the summed probability of such a pair instead: kept per edge
+    # beside the maximum, in the same order.
+    best, mass, mult = {}, {}, {}
     for a, b, lp in edges:
         if (a, b) not in best or lp > best[(a, b)]:
             best[(a, b)] = lp
+        mass[(a, b)] = mass.get((a, b), 0.0) + math.exp(lp)
+        mult[(a, b)] = mult.get((a, b), 0) + 1
+    total = {k: (math.log(mass[k]) if mult[k] > 1 else best[k]) for k in best}
     seen = set()
     dedup = []
     for a, b, lp in edges:
@@ -347,14 +353,15 @@ def bake(g, count_states=(), tag_substring=None, tag2_states=()):
     m = len(final)
     ins = [[] for _ in range(m)]
     for a, b, lp in edges:
-        ins[new[b]].append((new[a], lp))
+        ins[new[b]].append((new[a], lp, total[(a, b)]))
     in_ptr = np.zeros(m + 1, np.int32)
-    in_src, in_logp = [], []
+    in_src, in_logp, in_logp_sum = [], [], []
     for k in range(m):
         ins[k].sort(key=lambda t: t[0])
         in_ptr[k + 1] = in_ptr[k] + len(ins[k])
         in_src += [t[0] for t in ins[k]]
         in_logp += [t[1] for t in ins[k]]
+        in_logp_sum += [t[2] for t in ins[k]]
     ne = len(emitting)
     kind = np.zeros(ne, np.int32); ea = np.zeros(ne); eb = np.zeros(ne); ec = np.zeros(ne)
     for k, old in enumerate(emitting):
@@ -385,4 +392,5 @@ def bake(g, count_states=(), tag_substring=None, tag2_states=()):
             pos_kind[new[old]], pos_index[new[old]] = g.positions[old]
     return BakedHMM(m, ne, new[g.start], new[g.end], in_ptr, np.array(in_src, np.int32),
                     np.array(in_logp, np.float64), kind, ea, eb, ec, count_inc, tag,
-                    [g.names[i] for i in final], np.array(final, np.int32), hint_slot, hint_lane, pos_kind, pos_index)
+                    [g.names[i] for i in final], np.array(final, np.int32), hint_slot, hint_lane, pos_kind, pos_index,
+                    np.array(in_logp_sum, np.float64))
