@@ -233,6 +233,27 @@ int strq_batch_fetch_units(strq_ctx* ctx, int64_t* pool, int64_t pool_cap, int64
 /* The unit pass of the last run call: out[0] = ms on the GPU (all its sub-batches), out[1] = largest workspace of unit records /
  * back-pointers one piece of it used (bytes), out[2] = windows decoded, out[3] = positions. */
 int strq_last_units(strq_ctx* ctx, double* out4);
+/* Per-unit scores behind the hard mCpG calls (repeatModHMM.mod_repeats, STRique.py:492-500, keeps the argmax only): with on = 1,
+ * later run calls also score every repeat unit of every modification pattern under both branches of the dual model.  With the
+ * segmentation of the pattern's decode fixed, unit j covers the observations x[u_j .. w_j] of the clipped repeat stretch (the s0
+ * emission in front of it, its branch emissions, the e0 emission behind it) and V_B(j), B in {base, mod}, is the Viterbi
+ * log-probability (start to end, float64, evaluated edge by edge like the decode itself) of the dual model on them with every edge
+ * removed that has an emitting state of the other branch at either end; -inf when that branch has no path.  The log-likelihood
+ * ratio of unit j is V_mod(j) - V_base(j): >= 0 (up to rounding) where the pattern says '1', <= 0 where it says '0'.  Rows,
+ * patterns, unit positions and confidence do not change.  Sub-batches still in flight keep the mode they were launched with (the
+ * call waits for them).  Dual models of at most 128 emitting states whose only silent states are start and end (repeat units of up
+ * to 31 nt at k = 6): STRQ_ERR_UNSUPPORTED, and the switch stays off, when a modification model registered with a target is not
+ * such a model -- and from strq_target_set_mod, which then leaves the target alone, while the switch is on.  Default 0: no further
+ * kernel runs and no further buffer is reserved. */
+int strq_set_mod_llr(strq_ctx* ctx, int32_t on);
+/* Scores of the last batch (STRique.py:492-500: one entry per character of the pattern string): the units of read i are
+ * [off[i], off[i+1]), unit k of the batch has V_base = pool[2 k], V_mod = pool[2 k + 1]; pool_cap counts units.  A read has as many
+ * units as its pattern has characters, none when the pattern is "-", when its target has no modification model or when the run
+ * call ran with the switch off.  pool may be NULL to query the total in off[n]. */
+int strq_batch_fetch_mod_llr(strq_ctx* ctx, double* pool, int64_t pool_cap, int64_t* off);
+/* The scoring pass of the last run call (STRique.py:492-500 has no counterpart): out[0] = ms on the GPU (all its sub-batches),
+ * out[1] = units scored, out[2] = reads with units, out[3] = kernels launched (bounds and scoring; 0 with the switch off). */
+int strq_last_mod_llr(strq_ctx* ctx, double* out4);
 /* Count confidence: with on = 1, later run calls also run the forward pass (strq_forward_batch) over the window
  * [prefix_begin, suffix_end) of every read whose gate passed and whose flanked-model decode found a path -- the same observations,
  * normalised and clipped, that the decode saw, with c0 = the visits of the best path.  Rows, modification patterns and unit

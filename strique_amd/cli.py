@@ -25,6 +25,8 @@ HEADER = ['ID', 'target', 'strand', 'count', 'score_prefix', 'score_suffix', 'lo
 UNITS_HEADER = ['ID', 'target', 'strand', 'count', 'n_units', 'units']
 # `count --confidence FILE`: forward log-likelihood and posterior mean / standard deviation of the count, one row per count row
 CONF_HEADER = ['ID', 'target', 'strand', 'count', 'log_p', 'log_lik', 'count_mean', 'count_sd']
+# `count --mod_model M --mod-llr FILE`: log-likelihood ratio (modified over unmodified) of every unit of the pattern, one row per count row
+MODLLR_HEADER = ['ID', 'target', 'strand', 'count', 'mod_pattern', 'n_units', 'llr']
 LEVELS = ['error', 'warning', 'info', 'debug']
 
 
@@ -232,6 +234,9 @@ def count(argv):
     parser.add_argument("--confidence", default=None, metavar="FILE", help="Also write how far to trust each count to FILE: the forward log-likelihood of the decoded "
                                                                              "window (all paths, where log_p is the best one) and the posterior mean and standard deviation "
                                                                              "of the count; one row per count row, columns " + " ".join(CONF_HEADER))
+    parser.add_argument("--mod-llr", dest="mod_llr", default=None, metavar="FILE", help="With --mod_model: also write how far to trust each methylation call to FILE: per repeat unit of "
+                                                                                        "the pattern the log-likelihood ratio of the modified over the unmodified branch (positive: "
+                                                                                        "modified); one row per count row, columns " + " ".join(MODLLR_HEADER))
     parser.add_argument("--scan", action="store_true", help="No alignment: every read of the index is compared with every target of the repeat config on both strands, "
                                                              "from its raw signal alone, and counted for the one it spans (if any).  Excludes --algn; stdin is not read")
     parser.add_argument("--scan-min-score", type=float, default=None, metavar="X", help="--scan: the smallest min(score_prefix, score_suffix) a target and strand needs to be "
@@ -242,6 +247,10 @@ def count(argv):
     args = parser.parse_args(argv)
     if args.scan and args.confidence:
         parser.error("--confidence cannot be combined with --scan: the forward pass runs on reads whose target and strand an alignment gives")
+    if args.mod_llr and not args.mod_model:
+        parser.error("--mod-llr needs --mod_model: the ratios belong to the calls of the modification model")
+    if args.scan and args.mod_llr:
+        parser.error("--mod-llr cannot be combined with --scan: the scoring pass runs on reads whose target and strand an alignment gives")
     if args.scan and args.algn:
         parser.error("--scan takes the target and strand of a read from its signal: it cannot be combined with --algn")
     if not args.scan and (args.scan_scores or args.scan_min_score is not None):
@@ -299,6 +308,7 @@ def count(argv):
     out = (open(args.out, 'w') if args.out else sys.stdout) if rank == 0 else None
     units_out = open(args.units, 'w') if (args.units and rank == 0) else None
     conf_out = open(args.confidence, 'w') if (args.confidence and rank == 0) else None
+    llr_out = open(args.mod_llr, 'w') if (args.mod_llr and rank == 0) else None
     readers = args.t
     if readers <= 0:
         # one process per GPU: every rank takes its share of the cores (LOCAL_WORLD_SIZE is set by torchrun) for its reader threads, at most
@@ -316,7 +326,8 @@ def count(argv):
     try:
         rows = run_count(stream, loci, f5.get_raw, counter, log, args.batch, rank, world, out if world == 1 else None, readers=readers, stats=stats,
                          units=bool(args.units), units_out=units_out if world == 1 else None, scan=scan, scores_out=scores_out if world == 1 else None,
-                         confidence=bool(args.confidence), conf_out=conf_out if world == 1 else None)
+                         confidence=bool(args.confidence), conf_out=conf_out if world == 1 else None,
+                         mod_llr=bool(args.mod_llr), llr_out=llr_out if world == 1 else None)
     except DeviceFault:
         if world == 1:
             raise SystemExit(3)
@@ -330,8 +341,10 @@ def count(argv):
                 log("Main: a rank reported a device error; no output written.", 'error')
             dist.destroy_process_group()
             raise SystemExit(3)
-        merged = gather_rows(rows, stats["items"], sdist, units=bool(args.units), scan=scan, confidence=bool(args.confidence))
-        if scan:
+        merged = gather_rows(rows, stats["items"], sdist, units=bool(args.units), scan=scan, confidence=bool(args.confidence), mod_llr=bool(args.mod_llr))
+        if args.mod_llr:
+            merged, merged_units, merged_conf, merged_llr = merged
+        elif scan:
             merged, merged_units, merged_scores = merged
         elif args.confidence:
             merged, merged_units, merged_conf = merged
@@ -343,6 +356,8 @@ def count(argv):
                 write_rows(conf_out, merged_conf, header=CONF_HEADER)
             if units_out is not None:
                 write_rows(units_out, merged_units, header=UNITS_HEADER)
+            if llr_out is not None:
+                write_rows(llr_out, merged_llr, header=MODLLR_HEADER)
             if scores_out is not None:
                 write_rows(scores_out, merged_scores, header=scan_mod.scores_header(scan["candidates"]))
         dist.barrier()
@@ -353,6 +368,8 @@ def count(argv):
         units_out.close()
     if conf_out is not None:
         conf_out.close()
+    if llr_out is not None:
+        llr_out.close()
     if scores_out is not None:
         scores_out.close()
     if stats.get("failed"):
@@ -428,8 +445,33 @@ def parse_confidence(stream):
     return out
 
 
-def _split_result(res, units, confidence):
-    """(row tuple, unit positions or None, confidence or None) of one result of counter.detect_batch(..., units, confidence)."""
+def format_mod_llr(qname, target, strand, n, mod, llr):
+    """One row of the `count --mod-llr` file: count and pattern as the count row has them, the number of ratios, then the ratios
+    with four decimals joined by commas (inf / -inf where one branch has no path), '-' when there are none."""
+    vals = [] if llr is None else [float(x) for x in llr]
+    return '\t'.join([str(qname), str(target), str(strand), str(n), str(mod), str(len(vals)), ','.join('%.4f' % x for x in vals) if vals else '-'])
+
+
+def parse_mod_llr(stream):
+    """Rows of a `count --mod-llr` file: [(ID, target, strand, count, mod_pattern, [ratios])] in file order."""
+    out = []
+    for line in stream:
+        f = line.rstrip('\n').split('\t')
+        if not line.strip() or f[0] == MODLLR_HEADER[0]:
+            continue
+        vals = [] if f[6] == '-' else [float(x) for x in f[6].split(',')]
+        if len(vals) != int(f[5]):
+            raise ValueError("mod-llr row of %s: %s ratios, n_units = %s" % (f[0], len(vals), f[5]))
+        out.append((f[0], f[1], f[2], int(f[3]), f[4], vals))
+    return out
+
+
+def _split_result(res, units, confidence, mod_llr=False):
+    """(row tuple, unit positions or None, confidence or None) of one result of counter.detect_batch(..., units, confidence);
+    with mod_llr a fourth element, the log-likelihood ratios or None (detect_batch(..., mod_llr=True) puts them last)."""
+    if mod_llr:
+        rest = iter(res[1:])
+        return res[0], (next(rest) if units else None), (next(rest) if confidence else None), next(rest)
     if units and confidence:
         return res
     if units:
@@ -439,7 +481,7 @@ def _split_result(res, units, confidence):
     return res, None, None
 
 
-def gather_rows(rows, items, sdist, units=False, scan=None, confidence=False):
+def gather_rows(rows, items, sdist, units=False, scan=None, confidence=False, mod_llr=False):
     """Rows of this rank -> fixed-size records + modification strings -> one gather -> on rank 0 the
     merged [(sequence number, TSV row)] in input order (None elsewhere).  `items`: every accepted
     (qname, strand, target) of the input, which each rank derives from the same SAM file.
@@ -450,7 +492,9 @@ def gather_rows(rows, items, sdist, units=False, scan=None, confidence=False):
     record with valid = 2; the return value is (rows, unit rows or None, score rows) -- Nones off rank 0.
     confidence=True (not with scan): every result is (row tuple, conf) -- (row tuple, positions, conf) with units -- conf being
     (log_lik, count_mean, count_sd) or None; the three values travel at the end of the same blob ("...<TAB>l,m,s", repr() of the
-    floats, '-' for None), and the return value is (rows, unit rows or None, confidence rows) -- Nones off rank 0."""
+    floats, '-' for None), and the return value is (rows, unit rows or None, confidence rows) -- Nones off rank 0.
+    mod_llr=True (not with scan): every result ends in the log-likelihood ratios or None; they travel last in the blob ("...<TAB>r,r,...",
+    repr() of the floats, '-' for None), and the return value is (rows, unit rows or None, confidence rows or None, ratio rows)."""
     from . import scan as scan_mod
     rec = np.zeros(len(rows), ROW_DTYPE); mods = []; idx = np.zeros(len(rows), np.int64)
     for k, (seq, res) in enumerate(rows):
@@ -466,17 +510,24 @@ def gather_rows(rows, items, sdist, units=False, scan=None, confidence=False):
                 rec[k]["valid"] = 2; mods.append(head)
                 continue
             res = winner[2]
-        res, pos, conf = _split_result(res, units, confidence)
+        if mod_llr:
+            res, pos, conf, llr = _split_result(res, units, confidence, True)
+        else:
+            res, pos, conf = _split_result(res, units, confidence)
         n, sp, ss, p, offset, ticks, mod = res
         rec[k] = (n, 1, sp, ss, float(p), offset, ticks)
         blob = mod + '\t' + (','.join(str(int(x)) for x in pos) if pos is not None and len(pos) else '-') if units else mod
         if confidence:
             blob += '\t' + ('-' if conf is None else ','.join(repr(float(x)) for x in conf))
+        if mod_llr:
+            blob += '\t' + ('-' if llr is None or not len(llr) else ','.join(repr(float(x)) for x in llr))
         mods.append(head + blob)
     full, full_mods = sdist.gather_results(rec, idx, len(items), mods)
     if full is None:
+        if mod_llr:
+            return None, None, None, None
         return (None, None, None) if (scan or confidence) else ((None, None) if units else None)
-    merged = []; merged_units = []; merged_scores = []; merged_conf = []
+    merged = []; merged_units = []; merged_scores = []; merged_conf = []; merged_llr = []
     for seq, (qname, strand, target) in enumerate(items):
         r = full[seq]
         if not r["valid"]:
@@ -490,14 +541,21 @@ def gather_rows(rows, items, sdist, units=False, scan=None, confidence=False):
         n = int(r["count"]); lp = float(r["log_p"])
         p = lp if (n or lp != 0) else 0              # the reference prints the integer 0 for a failed gate (STRique.py:602,616)
         mod = full_mods[seq]
+        lstr = None
+        if mod_llr:
+            mod, lstr = mod.rsplit('\t', 1)
         if confidence:
             mod, cstr = mod.rsplit('\t', 1)
             merged_conf.append((seq, format_confidence(qname, target, strand, n, p, None if cstr == '-' else [float(x) for x in cstr.split(',')])))
         if units:
             mod, ustr = mod.split('\t', 1)
             merged_units.append((seq, format_units(qname, target, strand, n, [] if ustr == '-' else ustr.split(','))))
+        if mod_llr:
+            merged_llr.append((seq, format_mod_llr(qname, target, strand, n, mod, None if lstr == '-' else [float(x) for x in lstr.split(',')])))
         merged.append((seq, format_row(qname, target, strand, (n, float(r["score_prefix"]), float(r["score_suffix"]), p,
                                                                  int(r["offset"]), int(r["ticks"]), mod))))
+    if mod_llr:
+        return merged, (merged_units if units else None), (merged_conf if confidence else None), merged_llr
     if scan:
         return merged, (merged_units if units else None), merged_scores
     if confidence:
@@ -529,7 +587,7 @@ def route(stream, loci, log):
 
 
 def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, out=None, readers=0, stats=None, units=False, units_out=None,
-              scan=None, scores_out=None, confidence=False, conf_out=None):
+              scan=None, scores_out=None, confidence=False, conf_out=None, mod_llr=False, llr_out=None):
     """Route the SAM records of `stream` to their targets, run this rank's share through
     `counter.detect_batch` and return [(sequence number, result tuple or TSV row)].
 
@@ -550,7 +608,10 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
     reads are dealt out by position (no SAM, no lengths) and the results are (winner, scores) pairs for `gather_rows(..., scan=scan)`.
     `confidence` (not with scan): the results also carry (log_lik, count_mean, count_sd) or None (counter.detect_batch(...,
     confidence=True)); single process: their rows (format_confidence) go to `conf_out` and to stats["conf_rows"]; several ranks:
-    the results go to `gather_rows(..., confidence=True)` as they are."""
+    the results go to `gather_rows(..., confidence=True)` as they are.
+    `mod_llr` (not with scan; a counter with a modification model): the results end in the per-unit log-likelihood ratios or None
+    (counter.detect_batch(..., mod_llr=True)); single process: their rows (format_mod_llr) go to `llr_out` and to stats["llr_rows"];
+    several ranks: the results go to `gather_rows(..., mod_llr=True)` as they are."""
     from . import scan as scan_mod
     from .ffi import StriqueHipError, STRQ_ERR_ARG, STRQ_ERR_UNSUPPORTED
     if stats is None:
@@ -562,14 +623,19 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
         print('\t'.join(UNITS_HEADER), file=units_out)
     if conf_out is not None:
         print('\t'.join(CONF_HEADER), file=conf_out)
+    if llr_out is not None:
+        print('\t'.join(MODLLR_HEADER), file=llr_out)
     if scores_out is not None:
         print('\t'.join(scan_mod.scores_header(scan["candidates"])), file=scores_out)
     stats.setdefault("unit_rows", [])
     stats.setdefault("score_rows", [])
     stats.setdefault("conf_rows", [])
+    stats.setdefault("llr_rows", [])
     extras = dict(units=True) if units else {}
     if confidence:
         extras["confidence"] = True
+    if mod_llr:
+        extras["mod_llr"] = True
     rows = []
     records = ((rid, '.', ['.'], 0) for rid in stream) if scan else route(stream, loci, log)
     mine_set = None
@@ -623,7 +689,7 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
                     log("Detector: read failed: %s" % e1, 'warning'); results.append(None); failed += 1
                 except Exception as e1:
                     log("Detector: read failed: %s" % e1, 'warning'); results.append(None); failed += 1
-        done = []; udone = []; sdone = []; cdone = []
+        done = []; udone = []; sdone = []; cdone = []; ldone = []
         for (seq, qname, target, strand, _), res in zip(batch, results):
             if world > 1:
                 done.append((seq, res))
@@ -635,16 +701,21 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
                     if winner is None:
                         continue
                     target, strand, res = winner
+                llr = None
                 if scan:
                     res, pos, conf = _split_result(res, units, False)
+                elif mod_llr:
+                    res, pos, conf, llr = _split_result(res, units, confidence, True)
                 else:
                     res, pos, conf = _split_result(res, units, confidence)
                 if units:
                     udone.append((seq, format_units(qname, target, strand, res[0], pos)))
                 if confidence:
                     cdone.append((seq, format_confidence(qname, target, strand, res[0], res[3], conf)))
+                if mod_llr:
+                    ldone.append((seq, format_mod_llr(qname, target, strand, res[0], res[6], llr)))
                 done.append((seq, format_row(qname, target, strand, res)))
-        return (done, udone, sdone, cdone), failed
+        return (done, udone, sdone, cdone, ldone), failed
 
     # The batches run on an engine thread, one at a time and in order, while this thread routes the next SAM records and
     # collects their signals: the GPU call of batch k overlaps the host-side preparation of batch k + 1 (at 50 kb per read
@@ -655,12 +726,15 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
 
     def collect(keep):
         while len(in_flight) > keep:
-            (done, udone, sdone, cdone), failed = in_flight.popleft().result()          # re-raises DeviceFault from the engine thread
+            (done, udone, sdone, cdone, ldone), failed = in_flight.popleft().result()          # re-raises DeviceFault from the engine thread
             stats["failed"] += failed
             rows.extend(done)
             stats["unit_rows"].extend(udone)
             stats["score_rows"].extend(sdone)
             stats["conf_rows"].extend(cdone)
+            stats["llr_rows"].extend(ldone)
+            if llr_out is not None:
+                write_rows(llr_out, ldone, header=False)
             if conf_out is not None:
                 write_rows(conf_out, cdone, header=False)
             if scores_out is not None:

@@ -88,7 +88,7 @@ class repeatCounter(object):
         raise ValueError("RepeatCounter: Strand must be + or -.")
 
     # -------------------------------------------------------------------------------------
-    def detect_batch(self, items, units=False, confidence=False):
+    def detect_batch(self, items, units=False, confidence=False, mod_llr=False):
         """items: iterable of (target_name, raw_signal, strand).  Returns a list of the tuples
         detect() returns, in input order.  units=True: a list of (tuple, positions) instead, positions being the
         raw-signal sample indices of the repeat units on the decoded Viterbi path (one np.int64 array per read, ascending;
@@ -96,8 +96,14 @@ class repeatCounter(object):
         confidence=True: a list of (tuple, conf) -- (tuple, positions, conf) with units=True -- conf being (log_lik, count_mean,
         count_sd) as floats: the forward log-likelihood of the decoded window over all paths (log_p is the best one's), and the
         posterior mean and standard deviation of the count (count_bias included); None when the read was not decoded
-        (strq_set_confidence)."""
+        (strq_set_confidence).
+        mod_llr=True (a counter with a modification model): the per-unit log-likelihood ratio of the mCpG calls comes last -- a
+        float64 array V_mod - V_base with one value per character of mod_pattern (>= 0 where it says '1', <= 0 where it says '0',
+        +-inf where one branch has no path), or None for a read without units (strq_set_mod_llr).
+        Order of the elements: (tuple[, positions][, conf][, llr]); without any of the three the bare tuple."""
         items = list(items)
+        if mod_llr and self.pm is self.pm_mod:
+            raise ValueError("RepeatCounter: mod_llr needs a modification model.")
         if not items:
             return []
         tcs = [self._classifier_for(t, s) for t, _, s in items]
@@ -111,24 +117,32 @@ class repeatCounter(object):
             if not idx:
                 continue
             arrs = [sigs[i].astype(np.int16 if want_int else np.float64, copy=False) for i in idx]
-            if units:
-                self.ctx.set_units(True)
-            if confidence:
-                self.ctx.set_confidence(True)
             try:
+                # inside the try: set_mod_llr refuses a modification model the scoring pass does not cover, and the switches a
+                # failed call leaves behind must not stay on for the next caller of a shared context
+                if units:
+                    self.ctx.set_units(True)
+                if confidence:
+                    self.ctx.set_confidence(True)
+                if mod_llr:
+                    self.ctx.set_mod_llr(True)
                 res = self.ctx.detect_batch_reads(arrs, [tcs[i].target_id for i in idx])      # one pointer per read: no host-side concatenation
                 mods = self.ctx.batch_fetch_mod() if self.pm is not self.pm_mod else ['-'] * len(res)
                 pos = self.ctx.batch_fetch_units() if units else [None] * len(res)
                 conf = self.ctx.batch_fetch_confidence() if confidence else [None] * len(res)
+                vs = self.ctx.batch_fetch_mod_llr() if mod_llr else [None] * len(res)
             finally:
+                if mod_llr:
+                    self.ctx.set_mod_llr(False)
                 if units:
                     self.ctx.set_units(False)
                 if confidence:
                     self.ctx.set_confidence(False)
-            for i, r, m, u, cf in zip(idx, res, mods, pos, conf):
+            for i, r, m, u, cf, v in zip(idx, res, mods, pos, conf, vs):
                 n = int(r['count']); p = float(r['log_p']) if n or r['log_p'] != 0 else 0
                 row = (n, float(r['score_prefix']), float(r['score_suffix']), p, int(r['offset']), int(r['ticks']), m)
-                out[i] = ((row, u) if units else (row,)) + (cf,) if confidence else ((row, u) if units else row)
+                extra = ((u,) if units else ()) + ((cf,) if confidence else ()) + ((None if v is None else v[:, 1] - v[:, 0],) if mod_llr else ())
+                out[i] = (row,) + extra if extra else row
         return out
 
     def candidates(self, targets=None):
@@ -193,8 +207,8 @@ class repeatCounter(object):
             return True
         return s.size == 0 or (int(s.min()) >= -32768 and int(s.max()) <= 32767)
 
-    def detect(self, target_name, raw_signal, strand, units=False, confidence=False):
+    def detect(self, target_name, raw_signal, strand, units=False, confidence=False, mod_llr=False):
         """(n, score_prefix, score_suffix, log_p, offset, ticks, mod_pattern) -- STRique.py:581-618.  units=True:
         (that tuple, unit positions or None); confidence=True: (that tuple, [positions,] (log_lik, count_mean, count_sd) or
-        None) -- see detect_batch."""
-        return self.detect_batch([(target_name, raw_signal, strand)], units=units, confidence=confidence)[0]
+        None); mod_llr=True: the per-unit log-likelihood ratios (or None) after them -- see detect_batch."""
+        return self.detect_batch([(target_name, raw_signal, strand)], units=units, confidence=confidence, mod_llr=mod_llr)[0]

@@ -1434,7 +1434,7 @@ void strq_ctx_destroy(strq_ctx* c)
                       &c->rec, &c->tasks, &c->results, &c->queue, &c->scratch, &c->lutinfo, &c->hard, &c->misc,
                       &c->vit_x, &c->vit_tasks, &c->vit_bp, &c->vit_path, &c->bnd, &c->gen_codes, &c->gen_table, &c->gen_bnd, &c->gen_trace, &c->gen_hard, &c->redo_total, &c->screen, &c->ckpt2})
         b->release();
-    for (HostModel* m : c->models) if (m) { m->blob.release(); delete m; }
+    for (HostModel* m : c->models) if (m) { m->blob.release(); m->llr_blob.release(); delete m; }
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->side_join) (void)hipEventDestroy(c->side_join);

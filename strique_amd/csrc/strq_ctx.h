@@ -11,6 +11,7 @@
 #include "align_kernels.h"
 #include "viterbi_kernels.h"
 #include "forward_kernels.h"
+#include "mod_llr_kernels.h"
 #include "screen_kernels.h"
 #include "strq_opt.h"
 
@@ -82,6 +83,10 @@ struct HostModel {
     std::vector<double> fwd_logp;
     DevBuf fwd_blob;
     const FwdModel* fwd_dev = nullptr;
+    // per-unit scores of the modification pass (mod_llr_kernels.h): the edge image of a dual model, built on first use
+    DevBuf llr_blob;
+    const LlrModel* llr_dev = nullptr;
+    int32_t llr_mode = -1;
 };
 
 }  // namespace strq

@@ -95,6 +95,8 @@ struct Batch {
     bool conf_ran = false;               // the last run call ran the forward pass (strq_set_confidence)
     std::vector<double> conf;            // log_lik, count_mean, count_sd per read (strq_batch_fetch_confidence); empty until a run call with confidence on
     std::vector<uint8_t> conf_dec;
+    std::vector<std::vector<double>> llr;         // (V_base, V_mod) per repeat unit and read (strq_batch_fetch_mod_llr); empty: none
+    void clear_llr(int64_t r) { if ((size_t)r < llr.size()) llr[(size_t)r].clear(); }
     void clear_conf(int64_t r) { if ((size_t)r < conf_dec.size()) { conf[3 * (size_t)r] = conf[3 * (size_t)r + 1] = conf[3 * (size_t)r + 2] = NAN; conf_dec[(size_t)r] = 0; } }
     // a new batch of n reads: rows, patterns and unit positions at their initial values, no samples uploaded, nothing of the caller's referenced
     void begin(int64_t n, int dt)
@@ -104,6 +106,7 @@ struct Batch {
         target_given.clear(); scan_ncand = 0; cand.clear(); scores.clear();
         results.assign((size_t)n, strq_result()); mod.assign((size_t)n, std::string("-")); reset_units(n);
         conf.clear(); conf_dec.clear(); conf_ran = false;
+        llr.assign((size_t)n, std::vector<double>());
     }
     float t_cond = 0, t_lut = 0, t_fwd = 0, t_trace = 0, t_vit = 0, t_total = 0;
     double n_hard = 0;
@@ -121,6 +124,9 @@ struct DetectState {
     DevBuf unit_task, unit_ws, unit_path, unit_pool;      // unit pass (run_unit_pass): tasks, records / back-pointers, state paths, positions
     bool units_on = false;               // strq_set_units
     bool conf_on = false;                // strq_set_confidence
+    bool llr_on = false;                 // strq_set_mod_llr
+    DevBuf llr_ws;                       // per-unit scores (run_llr_pass): tasks, unit bounds, scores
+    float llr_ms = 0; double llr_units = 0, llr_reads = 0, llr_launches = 0;      // strq_last_mod_llr: the last run call's scoring pass
     DevBuf conf_task;                    // forward pass (run_conf_pass): tasks, model images, c0, results, order
     float conf_ms = 0; double conf_windows = 0, conf_nopath = 0, conf_expo = 0;      // strq_last_confidence: the last run call's forward pass
     // strq_scan_set: run calls compare these candidates (target ids) on every read instead of taking the read's own target
@@ -147,6 +153,7 @@ struct DetectState {
         int vit_mode = 0;                // 0 count, 2 MARK (modification pass follows)
         bool units = false;              // the unit pass follows (strq_set_units when the sub-batch was launched)
         bool conf = false;               // the forward pass follows (strq_set_confidence when the sub-batch was launched)
+        bool llr = false;                // the per-unit scores follow the modification pass (strq_set_mod_llr when the sub-batch was launched)
         bool scan = false;               // a scan sub-batch: a read without a winner has no row
         int64_t r0 = 0; int nr = 0;
         std::vector<int32_t> vit_slot;
@@ -212,7 +219,7 @@ void detect_state_free(strq_ctx* c)
     if (d->vit_stream) (void)hipStreamSynchronize(d->vit_stream);
     for (DevBuf* b : {&d->batch.raw, &d->rc, &d->hist16, &d->hist8, &d->geom, &d->idx,
                       &d->hist_raw, &d->bp, &d->path, &d->modtask, &d->modsig, &d->modlen, &d->pattern, &d->hrange, &d->modpool, &d->f64s,
-                      &d->unit_task, &d->unit_ws, &d->unit_path, &d->unit_pool, &d->conf_task, &d->scan_idx, &d->scan_out}) b->release();
+                      &d->unit_task, &d->unit_ws, &d->unit_path, &d->unit_pool, &d->conf_task, &d->llr_ws, &d->scan_idx, &d->scan_out}) b->release();
     if (d->scan_pin) (void)hipHostFree(d->scan_pin);
     for (auto& sl : d->slot) {
         for (DevBuf* b : {&sl.flt, &sl.vit, &sl.vres, &sl.order, &sl.vq}) b->release();
@@ -269,6 +276,108 @@ static int read_mod_patterns(strq_ctx* c, DetectState* d, int64_t r0, const std:
     if (dense) STRQ_HIP(c, hipMemcpyAsync(chars.data(), d_dense, dense, hipMemcpyDeviceToHost, st));
     STRQ_HIP(c, hipStreamSynchronize(st));
     for (int k = 0; k < nm; ++k) d->batch.mod[r0 + who[k]] = std::string(chars.data() + gt[k].dst, (size_t)gt[k].len);
+    return STRQ_OK;
+}
+
+// The edge image of a dual model for the per-unit scores (HostModel::llr_dev), built if it is not there; STRQ_ERR_UNSUPPORTED
+// (c->err says why) for a model the pass does not cover.
+static int llr_model(strq_ctx* c, HostModel* hm)
+{
+    if (hm->llr_dev) return STRQ_OK;
+    if (hm->llr_blob.reserve(llr_image_bytes()) != hipSuccess) { c->err = "out of device memory"; return STRQ_ERR_NOMEM; }
+    std::vector<char> blob; std::string why; int32_t mode = -1;
+    if (llr_build_image(hm->n_states, hm->silent_start, hm->start, hm->end, hm->in_ptr.data(), hm->in_src.data(), hm->in_logp.data(),
+                        hm->emis_kind.data(), hm->emis_a.data(), hm->emis_b.data(), hm->emis_c.data(),
+                        hm->state_tag.empty() ? nullptr : hm->state_tag.data(), hm->llr_blob.p, blob, &mode, why)) { c->err = why; return STRQ_ERR_UNSUPPORTED; }
+    STRQ_HIP(c, hipMemcpy(hm->llr_blob.p, blob.data(), blob.size(), hipMemcpyHostToDevice));
+    hm->llr_dev = hm->llr_blob.as<LlrModel>(); hm->llr_mode = mode;
+    return STRQ_OK;
+}
+
+// what run_mod_pass hands to run_llr_pass: its reads, where their decode left signal, records / paths and results
+struct LlrPassIn {
+    const std::vector<int>* who; const std::vector<int>* slot2; const std::vector<int64_t>* len;
+    const std::vector<size_t>* sig_off; const std::vector<size_t>* bp2_off; const std::vector<int32_t*>* paths;
+    bool use_hub; VitResult* results;
+};
+
+// Per-unit scores of the reads of one sub-batch (strq_set_mod_llr; mod_llr_kernels.h): behind the pattern read-back of run_mod_pass, on
+// the context's stream.  The pattern lengths size everything: one bound and two doubles per unit.
+static int run_llr_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, const LlrPassIn& in)
+{
+    Batch& B = d->batch;
+    hipStream_t st = c->stream;
+    const int64_t r0 = sl.r0;
+    const std::vector<int>& who = *in.who;
+    const int nm = (int)who.size();
+    std::vector<int64_t> n_units((size_t)nm), unit_off((size_t)nm + 1, 0);
+    for (int k = 0; k < nm; ++k) {
+        const std::string& pat = B.mod[(size_t)(r0 + who[k])];
+        n_units[(size_t)k] = pat == "-" ? 0 : (int64_t)pat.size();
+        unit_off[(size_t)k + 1] = unit_off[(size_t)k] + n_units[(size_t)k];
+    }
+    const int64_t U = unit_off[(size_t)nm];
+    if (!U) return STRQ_OK;
+    STRQ_HIP(c, hipEventRecord(d->ev[2], st));
+    // reads with units, by kernel mode (states per lane / units per wave)
+    std::vector<int> by_mode[3];
+    for (int k = 0; k < nm; ++k) {
+        if (!n_units[(size_t)k]) continue;
+        HostModel* hm = c->models[d->targets[B.target[r0 + who[k]]].mod_model_id];
+        // the image was built, and a model without one refused, when the switch went on or the target's model was registered:
+        // nothing is built or refused in the middle of a batch
+        if (!hm->llr_dev || hm->llr_mode < 0 || hm->llr_mode > 2) { c->err = "mod-llr: modification model without an edge image (strq_set_mod_llr validates them)"; return STRQ_ERR_DEVICE; }
+        by_mode[hm->llr_mode].push_back(k);
+    }
+    const size_t o_w = ((size_t)U * 16 + 15) & ~(size_t)15, o_bt = o_w + (((size_t)U * 4 + 15) & ~(size_t)15),
+                 o_rd = o_bt + (size_t)nm * sizeof(LlrBoundTask), o_first = o_rd + (size_t)nm * sizeof(LlrRead),
+                 o_bad = o_first + ((size_t)nm + 3) * 8, total = o_bad + (size_t)nm * 4;
+    STRQ_HIP(c, d->llr_ws.reserve(total + 64));
+    char* ws = d->llr_ws.as<char>();
+    double* d_out = reinterpret_cast<double*>(ws); int32_t* d_w = reinterpret_cast<int32_t*>(ws + o_w);
+    LlrBoundTask* d_bt = reinterpret_cast<LlrBoundTask*>(ws + o_bt); LlrRead* d_rd = reinterpret_cast<LlrRead*>(ws + o_rd);
+    int64_t* d_first = reinterpret_cast<int64_t*>(ws + o_first); int32_t* d_bad = reinterpret_cast<int32_t*>(ws + o_bad);
+    std::vector<LlrBoundTask> bt; std::vector<LlrRead> rdv; std::vector<int64_t> first;
+    struct L { int mode, at, n, first_at; int64_t units; };
+    std::vector<L> launches;
+    for (int mode = 0; mode < 3; ++mode) {
+        if (by_mode[mode].empty()) continue;
+        L l = {mode, (int)rdv.size(), (int)by_mode[mode].size(), (int)first.size(), 0};
+        for (int k : by_mode[mode]) {
+            HostModel* hm = c->models[d->targets[B.target[r0 + who[k]]].mod_model_id];
+            const int s2 = (*in.slot2)[(size_t)k];
+            LlrBoundTask b; std::memset(&b, 0, sizeof(b));
+            b.rec = in.use_hub ? reinterpret_cast<const uint64_t*>(d->bp.as<uint16_t>() + (*in.bp2_off)[(size_t)k]) : nullptr;
+            b.result = in.results + s2; b.path = in.use_hub ? nullptr : (*in.paths)[(size_t)s2]; b.tag = hm->h.state_tag;
+            b.w = d_w + unit_off[(size_t)k]; b.n = n_units[(size_t)k]; b.T = (*in.len)[(size_t)k]; b.bad = d_bad + (int)bt.size();
+            bt.push_back(b);
+            LlrRead r; r.model = hm->llr_dev; r.x = d->modsig.as<double>() + (*in.sig_off)[(size_t)k]; r.w = b.w;
+            r.out = d_out + 2 * unit_off[(size_t)k]; r.T = b.T;
+            rdv.push_back(r);
+            first.push_back(l.units); l.units += n_units[(size_t)k];
+        }
+        first.push_back(l.units);
+        launches.push_back(l);
+    }
+    const int nb = (int)bt.size();
+    STRQ_HIP(c, hipMemcpyAsync(d_bt, bt.data(), (size_t)nb * sizeof(LlrBoundTask), hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, hipMemcpyAsync(d_rd, rdv.data(), (size_t)nb * sizeof(LlrRead), hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, hipMemcpyAsync(d_first, first.data(), first.size() * 8, hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, hipMemsetAsync(d_bad, 0, (size_t)nb * 4, st));
+    STRQ_HIP(c, hipMemsetAsync(d_w, 0xFF, (size_t)U * 4, st));          // a bound nobody wrote is -1: its unit scores -inf, -inf
+    if (launch_llr_bounds(st, in.use_hub ? d_bt : nullptr, in.use_hub ? nb : 0, in.use_hub ? nullptr : d_bt, in.use_hub ? 0 : nb)) { c->err = "mod-llr: bounds launch failed"; return STRQ_ERR_DEVICE; }
+    for (const L& l : launches)
+        if (launch_llr_score(st, l.mode, d_rd + l.at, d_first + l.first_at, l.n, l.units, c->n_cu)) { c->err = "mod-llr: launch failed"; return STRQ_ERR_DEVICE; }
+    std::vector<double> out((size_t)U * 2); std::vector<int32_t> bad((size_t)nb);
+    STRQ_HIP(c, hipMemcpyAsync(out.data(), d_out, (size_t)U * 16, hipMemcpyDeviceToHost, st));
+    STRQ_HIP(c, hipMemcpyAsync(bad.data(), d_bad, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+    STRQ_HIP(c, hipEventRecord(d->ev[3], st));
+    STRQ_HIP(c, hipStreamSynchronize(st));
+    for (int32_t b : bad) if (b) { c->err = "mod-llr: the unit bounds of a read disagree with its pattern"; return STRQ_ERR_DEVICE; }
+    for (int k = 0; k < nm; ++k)
+        if (n_units[(size_t)k]) B.llr[(size_t)(r0 + who[k])].assign(out.begin() + (ptrdiff_t)(2 * unit_off[(size_t)k]), out.begin() + (ptrdiff_t)(2 * unit_off[(size_t)k + 1]));
+    d->llr_units += (double)U; d->llr_reads += nb; d->llr_launches += 1 + (double)launches.size();
+    float ms = 0; STRQ_HIP(c, hipEventElapsedTime(&ms, d->ev[2], d->ev[3])); d->llr_ms += ms;
     return STRQ_OK;
 }
 
@@ -392,7 +501,13 @@ static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
         STRQ_HIP(c, hipMemcpyAsync(d_pt, pt.data(), (size_t)nm * sizeof(PatTask), hipMemcpyHostToDevice, st));
         if (launch_mod_pattern(st, d_pt, nm, d_plen)) { c->err = "pattern launch failed"; return STRQ_ERR_DEVICE; }
     }
-    return read_mod_patterns(c, d, r0, who, slot2, len, p2_off, d_plen, d_chars);
+    if (const int prc = read_mod_patterns(c, d, r0, who, slot2, len, p2_off, d_plen, d_chars)) return prc;
+    if (!sl.llr) return STRQ_OK;
+    // 5. per-unit scores of both branches: modsig, the records / the traced paths and the results are live until the next pass
+    LlrPassIn li;
+    li.who = &who; li.slot2 = &slot2; li.len = &len; li.sig_off = &sig_off; li.bp2_off = &bp2_off; li.paths = &tp2;
+    li.use_hub = use_hub; li.results = d_tr;
+    return run_llr_pass(c, d, sl, li);
 }
 
 // Unit positions of the reads of one sub-batch (strq_set_units; repeatHMM.count_repeats' path, STRique.py:374-378,433-441): the
@@ -695,7 +810,7 @@ static int abandon(DetectState* d, DetectState::Slot& sl, int rc)
     for (int64_t r = sl.r0; r < sl.r0 + sl.nr && r < (int64_t)B.results.size(); ++r) {
         B.results[(size_t)r] = strq_result(); B.mod[(size_t)r] = "-";
         B.units[(size_t)r].clear(); B.unit_dec[(size_t)r] = 0;
-        B.clear_conf(r);
+        B.clear_conf(r); B.clear_llr(r);
         if (sl.scan && (size_t)r < B.cand.size()) {
             B.cand[(size_t)r] = -1;
             std::fill(B.scores.begin() + (ptrdiff_t)((size_t)r * 2 * B.scan_ncand), B.scores.begin() + (ptrdiff_t)((size_t)(r + 1) * 2 * B.scan_ncand), 0.0);
@@ -774,6 +889,7 @@ static int take_rows(strq_ctx* c, DetectState* d, DetectState::Slot& sl, bool un
         c->overlap[3] += 1;
     }
     publish_timing(c, B);
+    for (int i = 0; i < nr; ++i) B.clear_llr(r0 + i);
     // the mode the launches ran with decides, not what the targets say by now
     if (sl.vit_mode == 2) { const int mrc = run_mod_pass(c, d, sl); if (mrc) return mrc; }
     if (sl.units) { const int urc = run_unit_pass(c, d, sl); if (urc) return urc; }
@@ -1131,6 +1247,7 @@ static int publish_forward(strq_ctx* c, DetectState* d, const SubBatch& S)
     sl.vit_mode = S.any_mod ? 2 : 0;
     sl.units = d->units_on;
     sl.conf = d->conf_on;
+    sl.llr = d->llr_on;
     sl.scan = S.nc > 0;
     sl.state = DetectState::Slot::Forward;
     return STRQ_OK;
@@ -1359,6 +1476,7 @@ int run_range(strq_ctx* c, DetectState* d, int64_t first, int64_t last)
     B.conf_ran = d->conf_on;
     if (d->conf_on && B.conf_dec.size() != (size_t)B.n_reads) { B.conf.assign(3 * (size_t)B.n_reads, NAN); B.conf_dec.assign((size_t)B.n_reads, 0); }
     d->conf_ms = 0; d->conf_windows = d->conf_nopath = d->conf_expo = 0;
+    d->llr_ms = 0; d->llr_units = d->llr_reads = d->llr_launches = 0;
     STRQ_HIP(c, c->redo_total.reserve(64));
     STRQ_HIP(c, hipMemsetAsync(c->redo_total.p, 0, 64, c->stream));
     // partition into sub-batches first, so that the upload of piece k + 1 can overlap the kernels of piece k
@@ -1455,6 +1573,7 @@ int strq_target_set_mod(strq_ctx* c, int32_t target_id, int32_t mod_model_id, do
     DetectState* d = dstate(c);
     if (target_id < 0 || target_id >= (int32_t)d->targets.size() || mod_model_id < 0 || mod_model_id >= (int32_t)c->models.size()) { c->err = "bad argument"; return STRQ_ERR_ARG; }
     if (const int rc = drain(c, d)) return rc;          // a sub-batch in flight is taken with the target it ran with
+    if (d->llr_on) { if (const int rc = llr_model(c, c->models[mod_model_id])) return rc; }          // (the target stays as it was)
     d->targets[target_id].mod_model_id = mod_model_id; d->targets[target_id].mod_min = mod_min; d->targets[target_id].mod_max = mod_max;
     return STRQ_OK;
 }
@@ -1548,6 +1667,52 @@ int strq_last_confidence(strq_ctx* c, double* out4)
     if (!out4) { c->err = "bad argument"; return STRQ_ERR_ARG; }
     DetectState* d = dstate(c);
     out4[0] = d->conf_ms; out4[1] = d->conf_windows; out4[2] = d->conf_nopath; out4[3] = d->conf_expo;
+    return STRQ_OK;
+}
+
+int strq_set_mod_llr(strq_ctx* c, int32_t on)
+{
+    STRQ_ENTER(c);
+    if (on != 0 && on != 1) { c->err = "bad argument (strq_set_mod_llr takes 0 or 1)"; return STRQ_ERR_ARG; }
+    DetectState* d = dstate(c);
+    // sub-batches in flight keep the mode they were launched with: their scoring pass (or none) runs now
+    if (const int rc = drain(c, d)) return rc;
+    if (on)          // every modification model registered so far must be one the pass covers (later ones: strq_target_set_mod)
+        for (const Target& t : d->targets)
+            if (t.mod_model_id >= 0) { if (const int rc = llr_model(c, c->models[t.mod_model_id])) return rc; }
+    d->llr_on = on != 0;
+    return STRQ_OK;
+}
+
+int strq_batch_fetch_mod_llr(strq_ctx* c, double* pool, int64_t pool_cap, int64_t* off)
+{
+    STRQ_ENTER(c);
+    if (!off) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    DetectState* d = dstate(c);
+    if (const int rc = drain(c, d)) return rc;
+    const Batch& B = d->batch;
+    int64_t pos = 0;
+    for (int64_t i = 0; i < B.n_reads; ++i) {
+        off[i] = pos;
+        if ((size_t)i >= B.llr.size()) continue;
+        const std::vector<double>& v = B.llr[(size_t)i];
+        const int64_t n = (int64_t)v.size() / 2;
+        if (pool) {
+            if (pos + n > pool_cap) { c->err = "mod-llr pool too small"; return STRQ_ERR_ARG; }
+            if (n) std::memcpy(pool + 2 * pos, v.data(), (size_t)n * 16);
+        }
+        pos += n;
+    }
+    off[B.n_reads] = pos;
+    return STRQ_OK;
+}
+
+int strq_last_mod_llr(strq_ctx* c, double* out4)
+{
+    STRQ_ENTER(c);
+    if (!out4) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    DetectState* d = dstate(c);
+    out4[0] = d->llr_ms; out4[1] = d->llr_units; out4[2] = d->llr_reads; out4[3] = d->llr_launches;
     return STRQ_OK;
 }
 

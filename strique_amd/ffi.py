@@ -365,6 +365,27 @@ class Context(object):
         self._check(self._lib.strq_last_confidence(self._h, _ptr(out)))
         return {'ms': float(out[0]), 'windows': int(out[1]), 'no_path': int(out[2]), 'max_exponent': int(out[3])}
 
+    def set_mod_llr(self, on):
+        """strq_set_mod_llr: later run calls also score every repeat unit of a modification pattern under both branches of the
+        dual model (batch_fetch_mod_llr).  StriqueHipError (STRQ_ERR_UNSUPPORTED) for a modification model the pass does not cover."""
+        self._check(self._lib.strq_set_mod_llr(self._h, ctypes.c_int32(1 if on else 0)))
+
+    def batch_fetch_mod_llr(self):
+        """Per-unit scores of the last batch: per read an (n_units, 2) float64 array of (V_base, V_mod), one row per character of
+        its modification pattern, or None for a read without units (strq_batch_fetch_mod_llr)."""
+        n = getattr(self, '_n_batch', 0)
+        off = np.zeros(n + 1, np.int64)
+        self._check(self._lib.strq_batch_fetch_mod_llr(self._h, None, ctypes.c_int64(0), _ptr(off)))
+        pool = np.zeros((max(1, int(off[-1])), 2), np.float64)
+        self._check(self._lib.strq_batch_fetch_mod_llr(self._h, _ptr(pool), ctypes.c_int64(len(pool)), _ptr(off)))
+        return [pool[off[i]:off[i + 1]].copy() if off[i + 1] > off[i] else None for i in range(n)]
+
+    def last_mod_llr(self):
+        """The scoring pass of the last run call: {'ms', 'units', 'reads', 'launches'} (strq_last_mod_llr)."""
+        out = np.zeros(4)
+        self._check(self._lib.strq_last_mod_llr(self._h, _ptr(out)))
+        return {'ms': float(out[0]), 'units': int(out[1]), 'reads': int(out[2]), 'launches': int(out[3])}
+
     def batch_upload(self, signals, offsets, target_ids, host_stats=None):
         """signals: one concatenated int16 or float64 array; offsets: n_reads + 1."""
         signals = np.ascontiguousarray(signals)
