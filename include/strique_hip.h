@@ -400,6 +400,28 @@ int strq_debug_g2_layout(int32_t n_states, int32_t silent_start, int32_t start, 
  * columns below which candidate chunks merge}, or 0 when the parameters allow no screen (then the float32 DP runs over whole reads). */
 int strq_debug_screen_plan(const float params[6], int32_t samples, int32_t max_n, int32_t out[6]);
 
+/* Test hook: the score tables of the flank DP (csrc/lut_kernels.hip) as strq_align_batch would build them for n_jobs (1 ... 4096)
+ * (read, flank) pairs under the context's current alignment parameters -- the same code: the build kernel, the host's
+ * re-evaluation of the borderline entries and the patch kernel, the host's rebuild of the tables the kernel gave up on.
+ *   level_val[n_jobs x 256]   the 256 level values of job j's read (any float32)
+ *   cls_val, cls_off[n_jobs + 1]   the class values of job j's flank are cls_val[cls_off[j] .. cls_off[j + 1]): 1 ... 158 per job
+ * Out, raw -- job j has k = cls_off[j + 1] - cls_off[j] classes:
+ *   info[5 j ..]   total (entries of the ragged table), need (widest row), packed (1: the 24-bit copy holds the same numbers),
+ *                  n_hard (borderline entries listed for the host; -1: the whole table went to the host) -- all four as the kernel
+ *                  reported them -- and the entries of the finished table (256 k after a rebuild, else `total`)
+ *   band_lo[cls_off[j] + x]   row descriptor of class x: e_l | (e_r - e_l) << 8 | row offset << 16.  The entry the DP reads for
+ *                  level q is table[row offset + clamp(q, e_l, e_r) - e_l]
+ *   table[256 cls_off[j] ..]   the float32 entries of job j (a slot of 256 k)
+ *   planes[768 cls_off[j] + 8 j ..]   the 24-bit copy of job j's entries as the kernel wrote it (a slot of 768 k + 8 bytes): `total`
+ *                  uint16 (bits 8-23 of every entry), then from byte (2 total + 3) & ~3 on `total` uint8 (bits 0-7); an entry is
+ *                  (hi16 << 8 | lo8) * 2^-20.  Meaningful where packed = 1; zeros for a table the kernel left before it wrote any
+ *   handed[4 i ..], n_handed   the borderline entries the kernel listed: job, class, level, index into the job's table; at most
+ *                  handed_cap are written, *n_handed is their number (strq_last_timing [4] of a batched call)
+ * Uses the context's alignment workspace: not while a batch is resident or in flight on it. */
+int strq_debug_score_tables(strq_ctx* ctx, int32_t n_jobs, const float* level_val, const float* cls_val, const int64_t* cls_off,
+                            int32_t* info, int32_t* band_lo, float* table, uint8_t* planes,
+                            int32_t* handed, int32_t handed_cap, int32_t* n_handed);
+
 /* Kernel timing of the last batched call, milliseconds (HIP events on the library's stream):
  * [0] table build  [1] forward DP  [2] trace pass  [3] total  [4] table entries re-evaluated on
  * the host  [5] conditioning  [6] Viterbi  [7] number of forward-DP kernel launches.  */

@@ -77,7 +77,8 @@ lut_build_kernel(const LutJob* __restrict__ jobs, LutInfo* __restrict__ info, Ha
     }
     __syncthreads();
     if (rebuild) { if (q == 0) { info[blockIdx.x].total = 0; info[blockIdx.x].need = 0; info[blockIdx.x].packed = 0; info[blockIdx.x].n_hard = -1; } return; }
-    const int plat_lo_r = plat_lo, plat_hi_r = plat_hi;
+    // 256 level values with the same bits leave plat_lo = 255 above plat_hi = 0: one plateau, rows of the one entry at level 255
+    const int plat_lo_r = plat_lo, plat_hi_r = plat_hi < plat_lo ? plat_lo : plat_hi;
     auto in_band = [&](int lv, float c) { bool hd; return cell_score_dev(p, v[lv], c, &hd) > p.dist_min; };
     // ---- band of every class: first / last level scoring above dist_min
     for (int k = q; k < jb.k; k += 256) {

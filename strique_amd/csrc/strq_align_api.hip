@@ -277,46 +277,51 @@ static int upload_inputs(CorePlan& p)
 }
 
 // ---- score tables: launch, the after_tables hook, the host's patch of borderline entries / rebuild of whole tables
-static int build_tables(CorePlan& p)
+// What build_tables and the test hook strq_debug_score_tables share.  The caller has reserved c->lutinfo, c->hard and c->queue (its
+// first int zeroed on the stream) and filled `jobs` with device pointers; job j belongs to read job_read[j] of d_level_val and its
+// class values are also on the host at job_cls[j].
+struct TableBuild {
+    int nj = 0, max_k = 0;
+    std::vector<LutJob>* jobs = nullptr;
+    const float* d_level_val = nullptr;
+    std::vector<int> job_read;
+    std::vector<const float*> job_cls;
+    std::function<int()> after_tables;
+    std::vector<LutInfo>* info = nullptr;          // out: per job; `total` of a host-rebuilt table is its full width
+    std::vector<LutInfo>* reported = nullptr;      // out (nullable): what the kernel reported, before the host touched anything
+    std::vector<HardEntry>* handed = nullptr;      // out (nullable): the borderline entries the kernel listed for the host
+    int hard_count = 0;                            // out
+};
+
+static int run_table_build(strq_ctx* c, hipStream_t st, TableBuild& b)
 {
-    strq_ctx* c = p.c; const AlignCoreIn& in = p.in;
-    const int nb = p.nb, nj = p.nj;
-    hipStream_t st = p.st;
-    std::vector<LutJob>& jobs = p.jobs;
-    std::vector<LutInfo>& info = p.info;
-    jobs.resize(nj);
+    const int nj = b.nj;
+    std::vector<LutJob>& jobs = *b.jobs;
+    std::vector<LutInfo>& info = *b.info;
     LutJob* d_jobs = c->lutinfo.as<LutJob>();
     LutInfo* d_info = reinterpret_cast<LutInfo*>(d_jobs + nj);
-    for (int j = 0; j < nj; ++j) {
-        const int i = p.job_align[j];
-        jobs[j].level_val = in.d_level_val + (size_t)in.read[i] * 256;
-        jobs[j].cls_val = c->flank_cls.as<float>() + p.cls_off[i] + p.job_k0[j];
-        jobs[j].table = c->tables.as<float>() + p.tab_off[j];
-        jobs[j].table3 = c->tables3.as<uint8_t>() + p.tab_off[j] * 3 + (size_t)j * 8 - (p.tab_off[j] * 3 + (size_t)j * 8) % 4;      // 4-byte aligned slot
-        jobs[j].band_lo = c->band_lo.as<int32_t>() + p.desc_off[j];
-        jobs[j].k = p.job_k[j]; jobs[j].pad_ = 0;
-    }
     STRQ_HIP(c, hipMemcpyAsync(d_jobs, jobs.data(), (size_t)nj * sizeof(LutJob), hipMemcpyHostToDevice, st));
     HardEntry* d_hard = c->hard.as<HardEntry>();
     float* d_hard_vals = reinterpret_cast<float*>(d_hard + hard_cap);
     int* d_hard_count = c->queue.as<int>();
     STRQ_HIP(c, hipEventRecord(c->ev[0], st));
-    if (launch_lut_build(st, d_jobs, d_info, nj, p.max_k, d_hard, d_hard_count, hard_cap, c->ap)) { c->err = "lut launch failed"; return STRQ_ERR_DEVICE; }
+    if (launch_lut_build(st, d_jobs, d_info, nj, b.max_k, d_hard, d_hard_count, hard_cap, c->ap)) { c->err = "lut launch failed"; return STRQ_ERR_DEVICE; }
     STRQ_HIP(c, hipEventRecord(c->ev[1], st));
-    if (in.after_tables) { const int arc = in.after_tables(); if (arc) return arc; }
+    if (b.after_tables) { const int arc = b.after_tables(); if (arc) return arc; }
     info.resize(nj);
     int hard_count = 0;
     STRQ_HIP(c, hipMemcpyAsync(info.data(), d_info, (size_t)nj * sizeof(LutInfo), hipMemcpyDeviceToHost, st));
     STRQ_HIP(c, hipMemcpyAsync(&hard_count, d_hard_count, 4, hipMemcpyDeviceToHost, st));
     STRQ_HIP(c, hipStreamSynchronize(st));
-    STRQ_DBG("lut done nb=%d hard=%d floats0=%d", nb, hard_count, info[0].total);
+    if (b.reported) *b.reported = info;
+    STRQ_DBG("lut done jobs=%d hard=%d floats0=%d", nj, hard_count, info[0].total);
     if (strq::opt("STRQ_DEBUG")) { int hist[9] = {0}; for (int i = 0; i < nj; ++i) hist[std::min(8, info[i].need / 8)]++; STRQ_DBG("band need histogram (x8 levels): %d %d %d %d %d %d %d %d %d", hist[0], hist[1], hist[2], hist[3], hist[4], hist[5], hist[6], hist[7], hist[8]); }
-    if (strq::opt("STRQ_DEBUG")) { long tot = 0; int mx = 0; for (int i = 0; i < nj; ++i) { tot += info[i].total; mx = std::max(mx, info[i].total); } STRQ_DBG("table floats: mean %.0f max %d (k=%d)", (double)tot / nj, mx, in.k[0]); }
+    if (strq::opt("STRQ_DEBUG")) { long tot = 0; int mx = 0; for (int i = 0; i < nj; ++i) { tot += info[i].total; mx = std::max(mx, info[i].total); } STRQ_DBG("table floats: mean %.0f max %d (k=%d)", (double)tot / nj, mx, jobs[0].k); }
     if (hard_count > hard_cap) { c->err = "too many borderline table entries"; return STRQ_ERR_DEVICE; }
     bool any_rebuild = false;
     for (int j = 0; j < nj; ++j) any_rebuild |= info[j].n_hard < 0;
     auto level_vals_of = [&](int read, float* dst) -> int {      // level values of a read involved in host work
-        STRQ_HIP(c, hipMemcpy(dst, in.d_level_val + (size_t)read * 256, 256 * 4, hipMemcpyDeviceToHost));
+        STRQ_HIP(c, hipMemcpy(dst, b.d_level_val + (size_t)read * 256, 256 * 4, hipMemcpyDeviceToHost));
         return STRQ_OK;
     };
     if (hard_count > 0) {
@@ -324,32 +329,66 @@ static int build_tables(CorePlan& p)
         STRQ_HIP(c, hipMemcpy(he.data(), d_hard, (size_t)hard_count * sizeof(HardEntry), hipMemcpyDeviceToHost));
         float lv[256]; int last_read = -1;
         for (int i = 0; i < hard_count; ++i) {
-            const int rd = in.read[p.job_align[he[i].job]];
+            const int rd = b.job_read[he[i].job];
             if (rd != last_read) { const int rc = level_vals_of(rd, lv); if (rc) return rc; last_read = rd; }
-            hv[i] = host_cell_score(c->ap, lv[he[i].level], p.h_cls[p.cls_off[p.job_align[he[i].job]] + p.job_k0[he[i].job] + he[i].k]);
+            hv[i] = host_cell_score(c->ap, lv[he[i].level], b.job_cls[he[i].job][he[i].k]);
         }
         STRQ_HIP(c, hipMemcpyAsync(d_hard_vals, hv.data(), (size_t)hard_count * 4, hipMemcpyHostToDevice, st));
         if (launch_lut_patch(st, d_jobs, d_hard, d_hard_vals, hard_count)) { c->err = "patch launch failed"; return STRQ_ERR_DEVICE; }
         STRQ_HIP(c, hipStreamSynchronize(st));
-    }
+        if (b.handed) *b.handed = he;
+    } else if (b.handed) b.handed->clear();
     if (any_rebuild) for (int j = 0; j < nj; ++j) if (info[j].n_hard < 0) {
         // whole table from the host libm, full width
-        const int kk = p.job_k[j], i = p.job_align[j];
+        const int kk = jobs[j].k;
         std::vector<float> tab((size_t)kk * 256); std::vector<int32_t> blo(kk);
         float lv[256];
-        { const int rc = level_vals_of(in.read[i], lv); if (rc) return rc; }
+        { const int rc = level_vals_of(b.job_read[j], lv); if (rc) return rc; }
         for (int x = 0; x < kk; ++x) {
             float* row = &tab[(size_t)x * 256];
-            for (int q = 0; q < 256; ++q) row[q] = host_cell_score(c->ap, lv[q], p.h_cls[p.cls_off[i] + p.job_k0[j] + x]);
+            for (int q = 0; q < 256; ++q) row[q] = host_cell_score(c->ap, lv[q], b.job_cls[j][x]);
             blo[x] = (int32_t)((255u << 8) | ((uint32_t)(x * 256) << 16));     // levels 0..255, row offset x * 256
         }
         STRQ_HIP(c, hipMemcpy(jobs[j].table, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
         STRQ_HIP(c, hipMemcpy(jobs[j].band_lo, blo.data(), (size_t)kk * 4, hipMemcpyHostToDevice));
         info[j].total = kk * 256;
     }
+    b.hard_count = hard_count;
+    return STRQ_OK;
+}
+
+// 4-byte aligned slot of job j's 24-bit planes in c->tables3 (tab_off: floats of the slots before it)
+static uint8_t* table3_slot(strq_ctx* c, size_t tab_off, int j)
+{
+    const size_t o = tab_off * 3 + (size_t)j * 8;
+    return c->tables3.as<uint8_t>() + o - o % 4;
+}
+
+static int build_tables(CorePlan& p)
+{
+    strq_ctx* c = p.c; const AlignCoreIn& in = p.in;
+    const int nb = p.nb, nj = p.nj;
+    std::vector<LutJob>& jobs = p.jobs;
+    jobs.resize(nj);
+    TableBuild b;
+    b.nj = nj; b.max_k = p.max_k; b.jobs = &jobs; b.d_level_val = in.d_level_val; b.after_tables = in.after_tables; b.info = &p.info;
+    b.job_read.resize(nj); b.job_cls.resize(nj);
+    for (int j = 0; j < nj; ++j) {
+        const int i = p.job_align[j];
+        jobs[j].level_val = in.d_level_val + (size_t)in.read[i] * 256;
+        jobs[j].cls_val = c->flank_cls.as<float>() + p.cls_off[i] + p.job_k0[j];
+        jobs[j].table = c->tables.as<float>() + p.tab_off[j];
+        jobs[j].table3 = table3_slot(c, p.tab_off[j], j);
+        jobs[j].band_lo = c->band_lo.as<int32_t>() + p.desc_off[j];
+        jobs[j].k = p.job_k[j]; jobs[j].pad_ = 0;
+        b.job_read[j] = in.read[i];
+        b.job_cls[j] = &p.h_cls[p.cls_off[i] + p.job_k0[j]];
+    }
+    const int rc = run_table_build(c, p.st, b);
+    if (rc) return rc;
     p.tab_total.assign(nb, 0);
-    for (int j = 0; j < nj; ++j) p.tab_total[p.job_align[j]] = std::max(p.tab_total[p.job_align[j]], info[j].total);
-    p.out.n_hard = hard_count;
+    for (int j = 0; j < nj; ++j) p.tab_total[p.job_align[j]] = std::max(p.tab_total[p.job_align[j]], p.info[j].total);
+    p.out.n_hard = b.hard_count;
     return STRQ_OK;
 }
 
@@ -1489,6 +1528,69 @@ int strq_debug_screen_plan(const float params[6], int32_t samples, int32_t max_n
     if (!screen_plan(p, samples, max_n, &sp)) return 0;
     out[0] = sp.sc; out[1] = sp.hh; out[2] = sp.v; out[3] = sp.cadd; out[4] = sp.slack; out[5] = sp.merge_gap;
     return 1;
+}
+
+int strq_debug_score_tables(strq_ctx* c, int32_t n_jobs, const float* level_val, const float* cls_val, const int64_t* cls_off,
+                            int32_t* info_out, int32_t* band_lo, float* table, uint8_t* planes,
+                            int32_t* handed, int32_t handed_cap, int32_t* n_handed)
+{
+    strq::CtxScope scope_(c);
+    if (!c) return STRQ_ERR_ARG;
+    if (n_jobs < 1 || n_jobs > 4096 || !level_val || !cls_val || !cls_off || !info_out || !band_lo || !table || !planes || !n_handed ||
+        handed_cap < 0 || (handed_cap > 0 && !handed) || cls_off[0] != 0) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    int max_k = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+        const int64_t k = cls_off[j + 1] - cls_off[j];
+        if (k < 1 || k > STRQ_LUT_MAX_K) { c->err = "a score table has 1 to 158 classes"; return STRQ_ERR_ARG; }
+        max_k = std::max(max_k, (int)k);
+    }
+    STRQ_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const size_t cls_tot = (size_t)cls_off[n_jobs], tab_tot = STRQ_TABLE_SLOT_FLOATS(cls_tot);
+    STRQ_HIP(c, c->level_val.reserve((size_t)n_jobs * 256 * 4));
+    STRQ_HIP(c, c->flank_cls.reserve(cls_tot * 4));
+    STRQ_HIP(c, c->band_lo.reserve(cls_tot * 4));
+    STRQ_HIP(c, c->tables.reserve(tab_tot * 4));
+    STRQ_HIP(c, c->tables3.reserve(tab_tot * 3 + (size_t)n_jobs * 8 + 64));
+    STRQ_HIP(c, c->lutinfo.reserve((size_t)n_jobs * (sizeof(LutJob) + sizeof(LutInfo))));
+    STRQ_HIP(c, c->hard.reserve((size_t)hard_cap * (sizeof(HardEntry) + 4) + 64));
+    STRQ_HIP(c, c->queue.reserve(STRQ_QUEUE_BYTES));
+    STRQ_HIP(c, hipMemcpyAsync(c->level_val.p, level_val, (size_t)n_jobs * 256 * 4, hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, hipMemcpyAsync(c->flank_cls.p, cls_val, cls_tot * 4, hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, hipMemsetAsync(c->queue.p, 0, STRQ_QUEUE_BYTES, st));
+    STRQ_HIP(c, hipMemsetAsync(c->tables3.p, 0, tab_tot * 3 + (size_t)n_jobs * 8, st));      // the planes of a table the kernel gave up on read as zeros
+    std::vector<LutJob> jobs(n_jobs);
+    std::vector<LutInfo> info, reported;
+    std::vector<HardEntry> he;
+    TableBuild b;
+    b.nj = n_jobs; b.max_k = max_k; b.jobs = &jobs; b.d_level_val = c->level_val.as<float>(); b.info = &info; b.reported = &reported; b.handed = &he;
+    b.job_read.resize(n_jobs); b.job_cls.resize(n_jobs);
+    for (int j = 0; j < n_jobs; ++j) {
+        const size_t tab_off = STRQ_TABLE_SLOT_FLOATS(cls_off[j]);
+        jobs[j].level_val = c->level_val.as<float>() + (size_t)j * 256;
+        jobs[j].cls_val = c->flank_cls.as<float>() + cls_off[j];
+        jobs[j].table = c->tables.as<float>() + tab_off;
+        jobs[j].table3 = table3_slot(c, tab_off, j);
+        jobs[j].band_lo = c->band_lo.as<int32_t>() + cls_off[j];
+        jobs[j].k = (int32_t)(cls_off[j + 1] - cls_off[j]); jobs[j].pad_ = 0;
+        b.job_read[j] = j;
+        b.job_cls[j] = cls_val + cls_off[j];
+    }
+    const int rc = run_table_build(c, st, b);
+    if (rc) return rc;
+    for (int j = 0; j < n_jobs; ++j) {
+        info_out[5 * j] = reported[j].total; info_out[5 * j + 1] = reported[j].need; info_out[5 * j + 2] = reported[j].packed;
+        info_out[5 * j + 3] = reported[j].n_hard; info_out[5 * j + 4] = info[j].total;
+    }
+    STRQ_HIP(c, hipMemcpy(band_lo, c->band_lo.p, cls_tot * 4, hipMemcpyDeviceToHost));
+    STRQ_HIP(c, hipMemcpy(table, c->tables.p, tab_tot * 4, hipMemcpyDeviceToHost));
+    for (int j = 0; j < n_jobs; ++j)
+        STRQ_HIP(c, hipMemcpy(planes + (size_t)cls_off[j] * 768 + (size_t)j * 8, jobs[j].table3, (size_t)jobs[j].k * 768 + 8, hipMemcpyDeviceToHost));
+    *n_handed = (int32_t)he.size();
+    for (size_t i = 0; i < he.size() && (int64_t)i < handed_cap; ++i) {
+        handed[4 * i] = he[i].job; handed[4 * i + 1] = he[i].k; handed[4 * i + 2] = he[i].level; handed[4 * i + 3] = he[i].index;
+    }
+    return STRQ_OK;
 }
 
 int strq_last_overlap(const strq_ctx* c, double out[4])

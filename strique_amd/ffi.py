@@ -522,6 +522,41 @@ class Context(object):
         self._check(self._lib.strq_debug_conditioning(self._h, ctypes.c_int64(read), _ptr(levels), ctypes.c_int64(n), _ptr(lval), _ptr(sc)))
         return levels, lval, sc
 
+    def debug_score_tables(self, level_val, classes):
+        """strq_debug_score_tables: the score tables of len(classes) jobs -- level_val[j] the 256 level values, classes[j] the class
+        values of job j -- built by the code strq_align_batch builds them with.  One dict per job, everything raw: 'total', 'need',
+        'packed', 'n_hard' as the kernel reported them, 'entries' (of the finished table), 'band_lo' (int32 per class), 'table'
+        (float32[entries]), 'hi16' / 'lo8' (the two planes of the 24-bit copy, `total` elements each) and 'handed' (the
+        (class, level) pairs the kernel listed for the host)."""
+        level_val = _c(level_val, np.float32).reshape(-1, 256)
+        nj = len(classes)
+        if nj != len(level_val):
+            raise ValueError("one row of 256 level values per job")
+        cls_off = np.zeros(nj + 1, np.int64)
+        for j, cl in enumerate(classes):
+            cls_off[j + 1] = cls_off[j] + len(cl)
+        cls = np.concatenate([_c(cl, np.float32) for cl in classes])
+        tot = int(cls_off[-1])
+        info = np.zeros((nj, 5), np.int32); band_lo = np.zeros(tot, np.int32); table = np.zeros(256 * tot, np.float32)
+        planes = np.zeros(768 * tot + 8 * nj, np.uint8)
+        cap = 1 << 16
+        handed = np.zeros((cap, 4), np.int32); n_handed = ctypes.c_int32(0)
+        self._check(self._lib.strq_debug_score_tables(self._h, ctypes.c_int32(nj), _ptr(level_val), _ptr(cls), _ptr(cls_off), _ptr(info),
+                                                      _ptr(band_lo), _ptr(table), _ptr(planes), _ptr(handed), ctypes.c_int32(cap),
+                                                      ctypes.byref(n_handed)))
+        handed = handed[:min(cap, n_handed.value)]
+        out = []
+        for j in range(nj):
+            c0, k = int(cls_off[j]), int(cls_off[j + 1] - cls_off[j])
+            total, need, packed, n_hard, entries = (int(v) for v in info[j])
+            slot = planes[768 * c0 + 8 * j:768 * (c0 + k) + 8 * j + 8]
+            lo_at = (2 * total + 3) & ~3
+            out.append({"total": total, "need": need, "packed": packed, "n_hard": n_hard, "entries": entries,
+                        "band_lo": band_lo[c0:c0 + k].copy(), "table": table[256 * c0:256 * c0 + entries].copy(),
+                        "hi16": slot[:2 * total].view(np.uint16).copy(), "lo8": slot[lo_at:lo_at + total].copy(),
+                        "handed": [(int(h[1]), int(h[2])) for h in handed if h[0] == j]})
+        return out
+
     def debug_filtered(self, read, n, dtype=np.int16):
         """strq_debug_filtered: the first `n` median-filtered samples of read `read` of the last sub-batch; `dtype` is the
         element type of the batch (int16 or float64)."""
