@@ -8,6 +8,7 @@ a time, the records of the SAM stream are collected and handed to the GPU in bat
 (`repeatCounter.detect_batch`); rows are written in input order.
 """
 import argparse
+import contextlib
 import glob
 import json
 import os
@@ -16,9 +17,12 @@ import sys
 import tarfile
 import tempfile
 import threading
-from collections import defaultdict, deque
+from collections import defaultdict, deque, namedtuple
 
 import numpy as np
+
+from . import scan as scan_mod
+from .counter import Detected
 
 HEADER = ['ID', 'target', 'strand', 'count', 'score_prefix', 'score_suffix', 'log_p', 'offset', 'ticks', 'mod']
 # `count --units FILE`: the raw-signal sample of every repeat unit on the decoded Viterbi path, one row per count row
@@ -297,18 +301,12 @@ def count(argv):
     f5 = Fast5Index(args.f5Index)
     scan = None
     if args.scan:
-        from . import scan as scan_mod
         scan = {"min_score": args.scan_min_score,
                 "candidates": counter.candidates(), "scores": bool(args.scan_scores)}
         if not scan["candidates"]:
             log("Main: --scan without a usable target.", 'error'); raise SystemExit(1)
     # --scan: every read id of the index, in index order, instead of SAM records
     stream = list(f5.index) if args.scan else (open(args.algn) if args.algn else sys.stdin)
-    scores_out = open(args.scan_scores, 'w') if (args.scan_scores and rank == 0) else None
-    out = (open(args.out, 'w') if args.out else sys.stdout) if rank == 0 else None
-    units_out = open(args.units, 'w') if (args.units and rank == 0) else None
-    conf_out = open(args.confidence, 'w') if (args.confidence and rank == 0) else None
-    llr_out = open(args.mod_llr, 'w') if (args.mod_llr and rank == 0) else None
     readers = args.t
     if readers <= 0:
         # one process per GPU: every rank takes its share of the cores (LOCAL_WORLD_SIZE is set by torchrun) for its reader threads, at most
@@ -323,55 +321,37 @@ def count(argv):
         readers = max(1, min(24, share))            # inflating is what the readers do: one per core they can get, 16 ... 24 measure the same end to end
     stats = {}
     fault = 0
-    try:
-        rows = run_count(stream, loci, f5.get_raw, counter, log, args.batch, rank, world, out if world == 1 else None, readers=readers, stats=stats,
-                         units=bool(args.units), units_out=units_out if world == 1 else None, scan=scan, scores_out=scores_out if world == 1 else None,
-                         confidence=bool(args.confidence), conf_out=conf_out if world == 1 else None,
-                         mod_llr=bool(args.mod_llr), llr_out=llr_out if world == 1 else None)
-    except DeviceFault:
-        if world == 1:
-            raise SystemExit(3)
-        fault = 1; rows = []
-    if world > 1:
-        import torch.distributed as dist
-        # a rank that lost its device must not leave the others waiting in the gather: every rank learns about it
-        # here (the faulty rank arrives at once, the others when their share is done) and all of them exit 3
-        if sdist.any_rank(fault):
+    paths = dict(units=args.units, confidence=args.confidence, mod_llr=args.mod_llr, scores=args.scan_scores)
+    with contextlib.ExitStack() as stack:
+        # rank 0 writes: as the batches are done in a single process (run_count), after the gather otherwise
+        files = {name: stack.enter_context(open(path, 'w')) if (path and rank == 0) else None for name, path in paths.items()}
+        out = (stack.enter_context(open(args.out, 'w')) if args.out else sys.stdout) if rank == 0 else None
+        now = {name: f if world == 1 else None for name, f in files.items()}
+        try:
+            rows = run_count(stream, loci, f5.get_raw, counter, log, args.batch, rank, world, out if world == 1 else None, readers=readers, stats=stats,
+                             units=bool(args.units), units_out=now['units'], scan=scan, scores_out=now['scores'],
+                             confidence=bool(args.confidence), conf_out=now['confidence'], mod_llr=bool(args.mod_llr), llr_out=now['mod_llr'])
+        except DeviceFault:
+            if world == 1:
+                raise SystemExit(3)
+            fault = 1; rows = []
+        if world > 1:
+            import torch.distributed as dist
+            # a rank that lost its device must not leave the others waiting in the gather: every rank learns about it
+            # here (the faulty rank arrives at once, the others when their share is done) and all of them exit 3
+            if sdist.any_rank(fault):
+                if rank == 0:
+                    log("Main: a rank reported a device error; no output written.", 'error')
+                dist.destroy_process_group()
+                raise SystemExit(3)
+            merged = gather_rows(rows, stats["items"], sdist, units=bool(args.units), scan=scan, confidence=bool(args.confidence), mod_llr=bool(args.mod_llr))
             if rank == 0:
-                log("Main: a rank reported a device error; no output written.", 'error')
+                write_rows(out, merged.rows)
+                for o in OUTPUTS:
+                    if files[o.name] is not None:
+                        write_rows(files[o.name], getattr(merged, o.name), header=o.header(scan))
+            dist.barrier()
             dist.destroy_process_group()
-            raise SystemExit(3)
-        merged = gather_rows(rows, stats["items"], sdist, units=bool(args.units), scan=scan, confidence=bool(args.confidence), mod_llr=bool(args.mod_llr))
-        if args.mod_llr:
-            merged, merged_units, merged_conf, merged_llr = merged
-        elif scan:
-            merged, merged_units, merged_scores = merged
-        elif args.confidence:
-            merged, merged_units, merged_conf = merged
-        elif args.units:
-            merged, merged_units = merged
-        if rank == 0:
-            write_rows(out, merged)
-            if conf_out is not None:
-                write_rows(conf_out, merged_conf, header=CONF_HEADER)
-            if units_out is not None:
-                write_rows(units_out, merged_units, header=UNITS_HEADER)
-            if llr_out is not None:
-                write_rows(llr_out, merged_llr, header=MODLLR_HEADER)
-            if scores_out is not None:
-                write_rows(scores_out, merged_scores, header=scan_mod.scores_header(scan["candidates"]))
-        dist.barrier()
-        dist.destroy_process_group()
-    if args.out and out is not None:
-        out.close()
-    if units_out is not None:
-        units_out.close()
-    if conf_out is not None:
-        conf_out.close()
-    if llr_out is not None:
-        llr_out.close()
-    if scores_out is not None:
-        scores_out.close()
     if stats.get("failed"):
         # like the reference (STRique.py:704-713): reads that fail are logged, the run itself succeeds
         log("Main: %d read(s) could not be processed (see warnings above)." % stats["failed"], 'error')
@@ -466,101 +446,125 @@ def parse_mod_llr(stream):
     return out
 
 
-def _split_result(res, units, confidence, mod_llr=False):
-    """(row tuple, unit positions or None, confidence or None) of one result of counter.detect_batch(..., units, confidence);
-    with mod_llr a fourth element, the log-likelihood ratios or None (detect_batch(..., mod_llr=True) puts them last)."""
-    if mod_llr:
-        rest = iter(res[1:])
-        return res[0], (next(rest) if units else None), (next(rest) if confidence else None), next(rest)
-    if units and confidence:
+def _floats(values):
+    """Floats as they travel between ranks: repr(), which float() reads back bit for bit."""
+    return ','.join(repr(float(x)) for x in values)
+
+
+def _unfloats(text):
+    return [float(x) for x in text.split(',')]
+
+
+# The optional per-read outputs of `count`, in the order of the fields of `Merged` and of the gather blob.  name: the keyword of
+# run_count / counter.detect_batch and the field of `Merged`; header(scan): the header of its file; format(qname, target, strand, row,
+# value): one row of its file (row: the count row's tuple, None for a scan read without a winner -- only an output with rowless=True
+# writes one then); pack(value) / unpack(text): its field of the gather blob (absent values are '-' and never reach them); stat: the
+# key of run_count's `stats` that collects its rows.
+Output = namedtuple('Output', ['name', 'header', 'format', 'pack', 'unpack', 'stat', 'rowless'])
+OUTPUTS = (
+    Output('units', lambda scan: UNITS_HEADER, lambda q, t, s, row, v: format_units(q, t, s, row[0], v),
+           lambda v: ','.join(str(int(x)) for x in v), lambda text: [int(x) for x in text.split(',')], 'unit_rows', False),
+    Output('confidence', lambda scan: CONF_HEADER, lambda q, t, s, row, v: format_confidence(q, t, s, row[0], row[3], v),
+           _floats, _unfloats, 'conf_rows', False),
+    Output('mod_llr', lambda scan: MODLLR_HEADER, lambda q, t, s, row, v: format_mod_llr(q, t, s, row[0], row[6], v),
+           _floats, _unfloats, 'llr_rows', False),
+    Output('scores', lambda scan: scan_mod.scores_header(scan["candidates"]),
+           lambda q, t, s, row, v: scan_mod.format_scores(q, None if row is None else (t, s), v),
+           lambda v: _floats(x for pair in v for x in pair), lambda text: list(zip(*[iter(_unfloats(text))] * 2)), 'score_rows', True),
+)
+Merged = namedtuple('Merged', ['rows'] + [o.name for o in OUTPUTS])
+
+
+def outputs_on(**flags):
+    """The entries of OUTPUTS whose flag (units=, confidence=, mod_llr=, scores=) is set."""
+    return [o for o in OUTPUTS if flags.get(o.name)]
+
+
+def as_detected(res, units=False, confidence=False, mod_llr=False):
+    """One result of counter.detect_batch(..., units, confidence, mod_llr) as a Detected record: a record as it is, else the legacy
+    shape detect_batch documents -- (row[, positions][, conf][, llr]), without any of the three the bare row."""
+    if isinstance(res, Detected):
         return res
-    if units:
-        return res[0], res[1], None
-    if confidence:
-        return res[0], None, res[1]
-    return res, None, None
+    if not (units or confidence or mod_llr):
+        return Detected(res, None, None, None)
+    rest = iter(res[1:])
+    return Detected(res[0], *[next(rest) if asked else None for asked in (units, confidence, mod_llr)])
+
+
+def _read_values(target, strand, det, scores=None):
+    """What the writers know of one read: (target, strand, row or None, {output name: value or None})."""
+    if det is None:
+        return target, strand, None, dict(scores=scores)
+    return target, strand, det.row, dict(units=det.units, confidence=det.conf, mod_llr=det.llr, scores=scores)
+
+
+def _emit(sink, on, seq, qname, target, strand, row, values):
+    """The rows of one read, (seq, text) each: its count row to sink['rows'], the row of every output of `on` to sink[name]."""
+    for o in on:
+        if row is not None or o.rowless:
+            sink[o.name].append((seq, o.format(qname, target, strand, row, values.get(o.name))))
+    if row is not None:
+        sink['rows'].append((seq, format_row(qname, target, strand, row)))
+
+
+def _absent(v):
+    return v is None or (not isinstance(v, str) and len(v) == 0)
+
+
+def pack_blob(on, target, strand, mod, values):
+    """What travels beside the fixed-size record of a read: target, strand, modification pattern, then one field per entry of
+    OUTPUTS, tab-separated; '-' for the target and strand of a scan read without a winner (its record says so: valid = 2), for an
+    output that is not in `on` and for a value that is None or empty."""
+    fields = ['-' if target is None else target, '-' if strand is None else strand, mod]
+    for o in OUTPUTS:
+        v = values.get(o.name) if o in on else None
+        fields.append('-' if _absent(v) else o.pack(v))
+    return '\t'.join(fields)
+
+
+def unpack_blob(on, blob):
+    """(target, strand, mod, values) of pack_blob(on, ...): target and strand as they travelled, None for every '-' value."""
+    fields = blob.split('\t')
+    values = {o.name: None if (o not in on or f == '-') else o.unpack(f) for o, f in zip(OUTPUTS, fields[3:])}
+    return fields[0], fields[1], fields[2], values
 
 
 def gather_rows(rows, items, sdist, units=False, scan=None, confidence=False, mod_llr=False):
-    """Rows of this rank -> fixed-size records + modification strings -> one gather -> on rank 0 the
-    merged [(sequence number, TSV row)] in input order (None elsewhere).  `items`: every accepted
-    (qname, strand, target) of the input, which each rank derives from the same SAM file.
-    units=True: every result is (row tuple, unit positions or None); the positions travel in the same blob as the
-    modification string ("mod<TAB>p,p,..."), and the return value is (rows, unit rows) -- (None, None) off rank 0.
-    scan (the dict of run_count): every result is (winner, scores) -- winner None or (target, strand, result as above); target,
-    strand and the scores travel in front of the blob ("target<TAB>strand<TAB>s,s,...<TAB>..."), a read without a winner as a
-    record with valid = 2; the return value is (rows, unit rows or None, score rows) -- Nones off rank 0.
-    confidence=True (not with scan): every result is (row tuple, conf) -- (row tuple, positions, conf) with units -- conf being
-    (log_lik, count_mean, count_sd) or None; the three values travel at the end of the same blob ("...<TAB>l,m,s", repr() of the
-    floats, '-' for None), and the return value is (rows, unit rows or None, confidence rows) -- Nones off rank 0.
-    mod_llr=True (not with scan): every result ends in the log-likelihood ratios or None; they travel last in the blob ("...<TAB>r,r,...",
-    repr() of the floats, '-' for None), and the return value is (rows, unit rows or None, confidence rows or None, ratio rows)."""
-    from . import scan as scan_mod
-    rec = np.zeros(len(rows), ROW_DTYPE); mods = []; idx = np.zeros(len(rows), np.int64)
-    for k, (seq, res) in enumerate(rows):
+    """Reads of this rank (run_count with world > 1) -> fixed-size records + one blob per read (pack_blob) -> one gather -> on rank 0
+    the rows of every file in input order: Merged(rows, units, confidence, mod_llr, scores), [(sequence number, TSV row)] each, None
+    for an output that was not asked for (scores: asked for by scan) and for every field off rank 0.  `items`: every accepted (qname,
+    strand, target) of the input, which each rank derives from the same SAM file (scan: from the same index).  A read that failed
+    travels as a record with valid = 0 and writes nothing; a scan read without a winner as one with valid = 2: it writes a score row."""
+    on = outputs_on(units=units, confidence=confidence, mod_llr=mod_llr, scores=bool(scan))
+    rec = np.zeros(len(rows), ROW_DTYPE); blobs = []; idx = np.zeros(len(rows), np.int64)
+    for k, (seq, read) in enumerate(rows):
         idx[k] = seq
-        if res is None:
-            mods.append("")
+        if read is None:
+            blobs.append("")
             continue
-        head = ""
-        if scan:
-            winner, sc = res
-            head = '\t'.join([winner[0] if winner else '-', winner[1] if winner else '-', ','.join(repr(float(x)) for pair in sc for x in pair)]) + '\t'
-            if winner is None:
-                rec[k]["valid"] = 2; mods.append(head)
-                continue
-            res = winner[2]
-        if mod_llr:
-            res, pos, conf, llr = _split_result(res, units, confidence, True)
+        target, strand, row, values = read
+        if row is None:
+            rec[k]["valid"] = 2
         else:
-            res, pos, conf = _split_result(res, units, confidence)
-        n, sp, ss, p, offset, ticks, mod = res
-        rec[k] = (n, 1, sp, ss, float(p), offset, ticks)
-        blob = mod + '\t' + (','.join(str(int(x)) for x in pos) if pos is not None and len(pos) else '-') if units else mod
-        if confidence:
-            blob += '\t' + ('-' if conf is None else ','.join(repr(float(x)) for x in conf))
-        if mod_llr:
-            blob += '\t' + ('-' if llr is None or not len(llr) else ','.join(repr(float(x)) for x in llr))
-        mods.append(head + blob)
-    full, full_mods = sdist.gather_results(rec, idx, len(items), mods)
+            n, sp, ss, p, offset, ticks, mod = row
+            rec[k] = (n, 1, sp, ss, float(p), offset, ticks)
+        blobs.append(pack_blob(on, target, strand, '-' if row is None else mod, values))
+    full, full_blobs = sdist.gather_results(rec, idx, len(items), blobs)
     if full is None:
-        if mod_llr:
-            return None, None, None, None
-        return (None, None, None) if (scan or confidence) else ((None, None) if units else None)
-    merged = []; merged_units = []; merged_scores = []; merged_conf = []; merged_llr = []
-    for seq, (qname, strand, target) in enumerate(items):
+        return Merged(*[None] * len(Merged._fields))
+    sink = defaultdict(list)
+    for seq, (qname, _, _) in enumerate(items):
         r = full[seq]
         if not r["valid"]:
             continue
-        if scan:
-            target, strand, sc, full_mods[seq] = full_mods[seq].split('\t', 3)
-            vals = [float(x) for x in sc.split(',')]
-            merged_scores.append((seq, scan_mod.format_scores(qname, None if r["valid"] == 2 else (target, strand), list(zip(vals[0::2], vals[1::2])))))
-            if r["valid"] == 2:
-                continue
-        n = int(r["count"]); lp = float(r["log_p"])
-        p = lp if (n or lp != 0) else 0              # the reference prints the integer 0 for a failed gate (STRique.py:602,616)
-        mod = full_mods[seq]
-        lstr = None
-        if mod_llr:
-            mod, lstr = mod.rsplit('\t', 1)
-        if confidence:
-            mod, cstr = mod.rsplit('\t', 1)
-            merged_conf.append((seq, format_confidence(qname, target, strand, n, p, None if cstr == '-' else [float(x) for x in cstr.split(',')])))
-        if units:
-            mod, ustr = mod.split('\t', 1)
-            merged_units.append((seq, format_units(qname, target, strand, n, [] if ustr == '-' else ustr.split(','))))
-        if mod_llr:
-            merged_llr.append((seq, format_mod_llr(qname, target, strand, n, mod, None if lstr == '-' else [float(x) for x in lstr.split(',')])))
-        merged.append((seq, format_row(qname, target, strand, (n, float(r["score_prefix"]), float(r["score_suffix"]), p,
-                                                                 int(r["offset"]), int(r["ticks"]), mod))))
-    if mod_llr:
-        return merged, (merged_units if units else None), (merged_conf if confidence else None), merged_llr
-    if scan:
-        return merged, (merged_units if units else None), merged_scores
-    if confidence:
-        return merged, (merged_units if units else None), merged_conf
-    return (merged, merged_units) if units else merged
+        target, strand, mod, values = unpack_blob(on, full_blobs[seq])
+        row = None
+        if r["valid"] != 2:
+            n = int(r["count"]); lp = float(r["log_p"])
+            p = lp if (n or lp != 0) else 0              # the reference prints the integer 0 for a failed gate (STRique.py:602,616)
+            row = (n, float(r["score_prefix"]), float(r["score_suffix"]), p, int(r["offset"]), int(r["ticks"]), mod)
+        _emit(sink, on, seq, qname, target, strand, row, values)
+    return Merged(sink['rows'], *[sink[o.name] if o in on else None for o in OUTPUTS])
 
 
 def write_rows(out, rows, header=True):
@@ -589,53 +593,38 @@ def route(stream, loci, log):
 def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, out=None, readers=0, stats=None, units=False, units_out=None,
               scan=None, scores_out=None, confidence=False, conf_out=None, mod_llr=False, llr_out=None):
     """Route the SAM records of `stream` to their targets, run this rank's share through
-    `counter.detect_batch` and return [(sequence number, result tuple or TSV row)].
+    `counter.detect_batch` and return [(sequence number, TSV row or -- several ranks -- what gather_rows takes)].
 
     Single process: rows [(seq, TSV row)] are also written to `out` as soon as their batch is done.
     Several ranks: the records are read first (the SAM carries the read lengths), the accepted
     (read, target) pairs are dealt to the ranks by descending read length
     (strique_amd.dist.shard_indices: the DP cost of a read is proportional to its length), and the
-    return value is [(seq, result tuple)] for `gather_rows`.
+    return value goes to `gather_rows`.
     `readers` > 0: raw signals are fetched by that many threads ahead of the GPU batches (inflating
     the deflate chunks of a fast5 releases the GIL and is what bounds a `count` run on real files);
     the order of the rows does not change.
-    `units`: the results also carry the repeat-unit positions (counter.detect_batch(..., units=True)); single process:
-    their rows (format_units) go to `units_out` with the count rows and to stats["unit_rows"]; several ranks: the
-    results are (row tuple, positions) pairs for `gather_rows(..., units=True)`.
+    `units`, `confidence`, `mod_llr` (the latter two not with scan; mod_llr: a counter with a modification model): the optional outputs
+    of OUTPUTS -- the counter is asked for them (counter.detect_batch(..., units=True) and so on), and every result is normalised to a
+    Detected record (as_detected); single process: their rows (format_units, format_confidence, format_mod_llr) go to `units_out`,
+    `conf_out`, `llr_out` with the count rows and to stats["unit_rows"], stats["conf_rows"], stats["llr_rows"].
     `scan` ({"min_score", "candidates", "scores"}): `stream` is a list of read ids instead of a SAM stream; every read goes through
     counter.scan_batch and takes target and strand from its winner -- a read without one writes no row, as a read without a target
-    writes none; single process: the score rows (strique_amd.scan.format_scores, every read) go to `scores_out`; several ranks: the
-    reads are dealt out by position (no SAM, no lengths) and the results are (winner, scores) pairs for `gather_rows(..., scan=scan)`.
-    `confidence` (not with scan): the results also carry (log_lik, count_mean, count_sd) or None (counter.detect_batch(...,
-    confidence=True)); single process: their rows (format_confidence) go to `conf_out` and to stats["conf_rows"]; several ranks:
-    the results go to `gather_rows(..., confidence=True)` as they are.
-    `mod_llr` (not with scan; a counter with a modification model): the results end in the per-unit log-likelihood ratios or None
-    (counter.detect_batch(..., mod_llr=True)); single process: their rows (format_mod_llr) go to `llr_out` and to stats["llr_rows"];
-    several ranks: the results go to `gather_rows(..., mod_llr=True)` as they are."""
-    from . import scan as scan_mod
+    writes none; single process: the score rows (strique_amd.scan.format_scores, every read) go to `scores_out` and to
+    stats["score_rows"]; several ranks: the reads are dealt out by position (no SAM, no lengths).
+    Several ranks: every result is (seq, (target, strand, row or None, values) or None) for `gather_rows` -- see _read_values."""
     from .ffi import StriqueHipError, STRQ_ERR_ARG, STRQ_ERR_UNSUPPORTED
     if stats is None:
         stats = {}
     stats.setdefault("failed", 0)
+    files = dict(rows=out, units=units_out, confidence=conf_out, mod_llr=llr_out, scores=scores_out)
+    on = outputs_on(units=units, confidence=confidence, mod_llr=mod_llr, scores=scan and scan["scores"])
     if out is not None:
         print('\t'.join(HEADER), file=out)
-    if units_out is not None:
-        print('\t'.join(UNITS_HEADER), file=units_out)
-    if conf_out is not None:
-        print('\t'.join(CONF_HEADER), file=conf_out)
-    if llr_out is not None:
-        print('\t'.join(MODLLR_HEADER), file=llr_out)
-    if scores_out is not None:
-        print('\t'.join(scan_mod.scores_header(scan["candidates"])), file=scores_out)
-    stats.setdefault("unit_rows", [])
-    stats.setdefault("score_rows", [])
-    stats.setdefault("conf_rows", [])
-    stats.setdefault("llr_rows", [])
-    extras = dict(units=True) if units else {}
-    if confidence:
-        extras["confidence"] = True
-    if mod_llr:
-        extras["mod_llr"] = True
+    for o in OUTPUTS:
+        stats.setdefault(o.stat, [])
+        if files[o.name] is not None:
+            print('\t'.join(o.header(scan)), file=files[o.name])
+    extras = {o.name: True for o in on if o.name != 'scores'}
     rows = []
     records = ((rid, '.', ['.'], 0) for rid in stream) if scan else route(stream, loci, log)
     mine_set = None
@@ -689,33 +678,19 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
                     log("Detector: read failed: %s" % e1, 'warning'); results.append(None); failed += 1
                 except Exception as e1:
                     log("Detector: read failed: %s" % e1, 'warning'); results.append(None); failed += 1
-        done = []; udone = []; sdone = []; cdone = []; ldone = []
+        sink = defaultdict(list)
         for (seq, qname, target, strand, _), res in zip(batch, results):
-            if world > 1:
-                done.append((seq, res))
+            read = None
+            if res is not None and scan:
+                winner, sc = res
+                read = _read_values(None, None, None, sc) if winner is None else _read_values(winner[0], winner[1], as_detected(winner[2], units), sc)
             elif res is not None:
-                if scan:
-                    winner, sc = res
-                    if scan["scores"]:
-                        sdone.append((seq, scan_mod.format_scores(qname, winner[:2] if winner else None, sc)))
-                    if winner is None:
-                        continue
-                    target, strand, res = winner
-                llr = None
-                if scan:
-                    res, pos, conf = _split_result(res, units, False)
-                elif mod_llr:
-                    res, pos, conf, llr = _split_result(res, units, confidence, True)
-                else:
-                    res, pos, conf = _split_result(res, units, confidence)
-                if units:
-                    udone.append((seq, format_units(qname, target, strand, res[0], pos)))
-                if confidence:
-                    cdone.append((seq, format_confidence(qname, target, strand, res[0], res[3], conf)))
-                if mod_llr:
-                    ldone.append((seq, format_mod_llr(qname, target, strand, res[0], res[6], llr)))
-                done.append((seq, format_row(qname, target, strand, res)))
-        return (done, udone, sdone, cdone, ldone), failed
+                read = _read_values(target, strand, as_detected(res, units, confidence, mod_llr))
+            if world > 1:
+                sink['rows'].append((seq, read))
+            elif read is not None:
+                _emit(sink, on, seq, qname, *read)
+        return sink, failed
 
     # The batches run on an engine thread, one at a time and in order, while this thread routes the next SAM records and
     # collects their signals: the GPU call of batch k overlaps the host-side preparation of batch k + 1 (at 50 kb per read
@@ -726,23 +701,14 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
 
     def collect(keep):
         while len(in_flight) > keep:
-            (done, udone, sdone, cdone, ldone), failed = in_flight.popleft().result()          # re-raises DeviceFault from the engine thread
+            sink, failed = in_flight.popleft().result()          # re-raises DeviceFault from the engine thread
             stats["failed"] += failed
-            rows.extend(done)
-            stats["unit_rows"].extend(udone)
-            stats["score_rows"].extend(sdone)
-            stats["conf_rows"].extend(cdone)
-            stats["llr_rows"].extend(ldone)
-            if llr_out is not None:
-                write_rows(llr_out, ldone, header=False)
-            if conf_out is not None:
-                write_rows(conf_out, cdone, header=False)
-            if scores_out is not None:
-                write_rows(scores_out, sdone, header=False)
-            if out is not None:
-                write_rows(out, done, header=False)
-            if units_out is not None:
-                write_rows(units_out, udone, header=False)
+            rows.extend(sink['rows'])
+            for o in OUTPUTS:
+                stats[o.stat].extend(sink[o.name])
+            for name, f in files.items():
+                if f is not None:
+                    write_rows(f, sink[name], header=False)
 
     def flush(batch):
         if not batch:

@@ -9,8 +9,8 @@ All numerical work of detect() happens in libstrique_hip (strique_amd/ffi.py); t
 builds the per-target inputs (flank templates, HMM arrays) and turns results into the reference's
 output tuple.
 """
+import contextlib
 from collections import namedtuple
-
 
 import numpy as np
 
@@ -30,6 +30,10 @@ def reverse_complement(sequence):
 
 target_classifier = namedtuple('target_classifier',
                                ['prefix', 'suffix', 'prefix_ext', 'suffix_ext', 'repeatHMM', 'modHMM', 'target_id'])
+
+# one read out of the device pipeline: the tuple detect() returns, and what was asked for beside it (None otherwise) -- unit positions,
+# (log_lik, count_mean, count_sd), per-unit log-likelihood ratios; see repeatCounter.detect_batch
+Detected = namedtuple('Detected', ['row', 'units', 'conf', 'llr'])
 
 
 class repeatCounter(object):
@@ -104,46 +108,59 @@ class repeatCounter(object):
         items = list(items)
         if mod_llr and self.pm is self.pm_mod:
             raise ValueError("RepeatCounter: mod_llr needs a modification model.")
-        if not items:
-            return []
-        tcs = [self._classifier_for(t, s) for t, _, s in items]
-        sigs = [np.asarray(r) for _, r, _ in items]
+        reads = [(self._classifier_for(t, s).target_id, r) for t, r, s in items]
+        out = [None] * len(items)
+        for i, d, _, _ in self._run(reads, units=units, confidence=confidence, mod_llr=mod_llr):
+            extra = ((d.units,) if units else ()) + ((d.conf,) if confidence else ()) + ((d.llr,) if mod_llr else ())
+            out[i] = (d.row,) + extra if extra else d.row
+        return out
+
+    @contextlib.contextmanager
+    def _switches(self, units, confidence, mod_llr):
+        """The optional passes that were asked for are on inside the block, and all of them off after it."""
+        try:
+            # inside the try: set_mod_llr refuses a modification model the scoring pass does not cover, and the switches a
+            # failed call leaves behind must not stay on for the next caller of a shared context
+            if units:
+                self.ctx.set_units(True)
+            if confidence:
+                self.ctx.set_confidence(True)
+            if mod_llr:
+                self.ctx.set_mod_llr(True)
+            yield
+        finally:
+            self.ctx.set_mod_llr(False)
+            self.ctx.set_units(False)
+            self.ctx.set_confidence(False)
+
+    def _run(self, reads, units=False, confidence=False, mod_llr=False, scan=None):
+        """reads: [(target_id, raw_signal)] through the context.  Yields (position in `reads`, Detected, winner, scores) per read, the
+        fields of Detected that were not asked for being None.  scan=(candidate target ids, min_score): the target ids of the reads
+        are ignored, every read is compared with every candidate (Context.scan_batch_reads); winner is its position in the candidate
+        list or -1, scores the [n_candidates, 2] array of its flank scores (both None without scan)."""
+        sigs = [np.asarray(r) for _, r in reads]
         # DAC samples that fit int16 take their order statistics from exact histograms; everything else is float64
         # (radix selection on the GPU, cond_kernels.hip: f64_stats_kernel).  A mixed batch runs as two device batches.
         is_int = [self._fits_int16(s) for s in sigs]
-        out = [None] * len(items)
         for want_int in (True, False):
             idx = [i for i, f in enumerate(is_int) if f == want_int]
             if not idx:
                 continue
             arrs = [sigs[i].astype(np.int16 if want_int else np.float64, copy=False) for i in idx]
-            try:
-                # inside the try: set_mod_llr refuses a modification model the scoring pass does not cover, and the switches a
-                # failed call leaves behind must not stay on for the next caller of a shared context
-                if units:
-                    self.ctx.set_units(True)
-                if confidence:
-                    self.ctx.set_confidence(True)
-                if mod_llr:
-                    self.ctx.set_mod_llr(True)
-                res = self.ctx.detect_batch_reads(arrs, [tcs[i].target_id for i in idx])      # one pointer per read: no host-side concatenation
+            with self._switches(units, confidence, mod_llr):
+                if scan is None:
+                    res = self.ctx.detect_batch_reads(arrs, [reads[i][0] for i in idx])      # one pointer per read: no host-side concatenation
+                    win = sc = [None] * len(res)
+                else:
+                    res, win, sc = self.ctx.scan_batch_reads(arrs, scan[0], scan[1], scores=True)
                 mods = self.ctx.batch_fetch_mod() if self.pm is not self.pm_mod else ['-'] * len(res)
                 pos = self.ctx.batch_fetch_units() if units else [None] * len(res)
                 conf = self.ctx.batch_fetch_confidence() if confidence else [None] * len(res)
                 vs = self.ctx.batch_fetch_mod_llr() if mod_llr else [None] * len(res)
-            finally:
-                if mod_llr:
-                    self.ctx.set_mod_llr(False)
-                if units:
-                    self.ctx.set_units(False)
-                if confidence:
-                    self.ctx.set_confidence(False)
-            for i, r, m, u, cf, v in zip(idx, res, mods, pos, conf, vs):
+            for i, r, m, u, cf, v, w, s in zip(idx, res, mods, pos, conf, vs, win, sc):
                 n = int(r['count']); p = float(r['log_p']) if n or r['log_p'] != 0 else 0
                 row = (n, float(r['score_prefix']), float(r['score_suffix']), p, int(r['offset']), int(r['ticks']), m)
-                extra = ((u,) if units else ()) + ((cf,) if confidence else ()) + ((None if v is None else v[:, 1] - v[:, 0],) if mod_llr else ())
-                out[i] = (row,) + extra if extra else row
-        return out
+                yield i, Detected(row, u, cf, None if v is None else v[:, 1] - v[:, 0]), w, s
 
     def candidates(self, targets=None):
         """[(target_name, strand)] of a scan: every target added (or the named ones), in add_target order, '+' before '-'."""
@@ -171,31 +188,13 @@ class repeatCounter(object):
         if not cands:
             raise ValueError("RepeatCounter: no targets to scan for.")
         ids = [self._classifier_for(t, s).target_id for t, s in cands]
-        sigs = [np.asarray(r) for r in signals]
-        is_int = [self._fits_int16(s) for s in sigs]
-        out = [None] * len(sigs)
-        all_scores = np.zeros((len(sigs), len(cands), 2), np.float64)
-        for want_int in (True, False):
-            idx = [i for i, f in enumerate(is_int) if f == want_int]
-            if not idx:
-                continue
-            arrs = [sigs[i].astype(np.int16 if want_int else np.float64, copy=False) for i in idx]
-            if units:
-                self.ctx.set_units(True)
-            try:
-                res, win, sc = self.ctx.scan_batch_reads(arrs, ids, min_score, scores=True)
-                mods = self.ctx.batch_fetch_mod() if self.pm is not self.pm_mod else ['-'] * len(res)
-                pos = self.ctx.batch_fetch_units() if units else [None] * len(res)
-            finally:
-                if units:
-                    self.ctx.set_units(False)
-            for k, (i, r, w, m, u) in enumerate(zip(idx, res, win, mods, pos)):
-                all_scores[i] = sc[k]
-                if w < 0:
-                    continue
-                n = int(r['count']); p = float(r['log_p']) if n or r['log_p'] != 0 else 0
-                row = (n, float(r['score_prefix']), float(r['score_suffix']), p, int(r['offset']), int(r['ticks']), m)
-                out[i] = cands[int(w)] + ((row, u) if units else row,)
+        reads = [(None, r) for r in signals]
+        out = [None] * len(reads)
+        all_scores = np.zeros((len(reads), len(cands), 2), np.float64)
+        for i, d, w, sc in self._run(reads, units=units, scan=(ids, min_score)):
+            all_scores[i] = sc
+            if w >= 0:
+                out[i] = cands[int(w)] + ((d.row, d.units) if units else d.row,)
         return (out, all_scores) if scores else out
 
     @staticmethod

@@ -1,0 +1,73 @@
+// Host-side bookkeeping of the detect pipeline (strq_detect_api.hip) that needs no device: the optional per-read outputs and their
+// switches, the per-read rows of a batch, and the grouping of Viterbi tasks into launches.  Plain C++: no HIP headers.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <map>
+#include <string>
+#include <utility>
+#include <vector>
+#include "../../include/strique_hip.h"
+
+namespace strq {
+
+// The optional passes behind the count decode: unit positions (strq_set_units), forward pass (strq_set_confidence), per-unit scores
+// (strq_set_mod_llr).  DetectState holds what the next run call uses, a slot what its sub-batch was launched with, Batch what the last
+// run call ran with.
+struct Extras { bool units = false, conf = false, llr = false; };
+
+// What a batch holds per read: the row, the modification pattern and the outputs of the optional passes.  One place sizes them, one
+// function puts a read back to its initial values -- a row that was never computed is never handed out.
+struct ReadRows {
+    std::vector<strq_result> results;
+    std::vector<std::string> mod;                 // modification pattern ('-' if none)
+    std::vector<std::vector<int64_t>> units;      // unit positions (strq_batch_fetch_units)
+    std::vector<uint8_t> unit_dec;                // 1: the read was decoded (gate passed, the flanked model found a path)
+    std::vector<double> conf;                     // log_lik, count_mean, count_sd (strq_batch_fetch_confidence); NaN while not decoded
+    std::vector<uint8_t> conf_dec;
+    std::vector<std::vector<double>> llr;         // (V_base, V_mod) per repeat unit (strq_batch_fetch_mod_llr); empty: none
+    void size_reads(int64_t n)
+    {
+        const size_t m = (size_t)n;
+        results.assign(m, strq_result()); mod.assign(m, std::string("-"));
+        units.assign(m, std::vector<int64_t>()); unit_dec.assign(m, 0);
+        conf.assign(3 * m, NAN); conf_dec.assign(m, 0);
+        llr.assign(m, std::vector<double>());
+    }
+    void clear_read(int64_t read)
+    {
+        const size_t r = (size_t)read;
+        if (read < 0 || r >= results.size()) return;
+        results[r] = strq_result(); mod[r] = "-";
+        units[r].clear(); unit_dec[r] = 0;
+        conf[3 * r] = conf[3 * r + 1] = conf[3 * r + 2] = NAN; conf_dec[r] = 0;
+        llr[r].clear();
+    }
+};
+
+struct VitGroup { int shape, first, count, max_cells, route; };      // one Viterbi launch: kernel shape, task range, largest n_cells of its models; its route (unit pass)
+
+struct GroupItem { int route, shape, n_cells; };
+
+// The launches of `items`: one per (route, shape) in ascending order, the items of a launch in their own order.  pos[k]: the task
+// position of item k; order[p]: the item at task position p.
+struct Grouping { std::vector<VitGroup> groups; std::vector<int32_t> pos, order; };
+
+inline Grouping group_items(const std::vector<GroupItem>& items)
+{
+    std::map<std::pair<int, int>, std::vector<int32_t>> by_key;
+    for (size_t k = 0; k < items.size(); ++k) by_key[{items[k].route, items[k].shape}].push_back((int32_t)k);
+    Grouping G; G.pos.assign(items.size(), 0); G.order.reserve(items.size());
+    for (const auto& g : by_key) {
+        VitGroup v = {g.first.second, (int)G.order.size(), (int)g.second.size(), 0, g.first.first};
+        for (int32_t k : g.second) {
+            v.max_cells = std::max(v.max_cells, items[(size_t)k].n_cells);
+            G.pos[(size_t)k] = (int32_t)G.order.size(); G.order.push_back(k);
+        }
+        G.groups.push_back(v);
+    }
+    return G;
+}
+
+}  // namespace strq

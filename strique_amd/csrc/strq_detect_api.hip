@@ -16,6 +16,7 @@
 #include <vector>
 #include "../../include/strique_hip.h"
 #include "strq_ctx.h"
+#include "detect_plan.h"
 #include "cond_kernels.h"
 #include "viterbi_kernels.h"
 #include "mod_kernels.h"
@@ -70,7 +71,7 @@ struct Target {
     int mod_model_id = -1; double mod_min = 0, mod_max = 0;
 };
 
-struct Batch {
+struct Batch : ReadRows {
     int64_t n_reads = 0;
     int dtype = 0;                       // 0 int16, 1 float64
     std::vector<int64_t> off;            // n_reads + 1
@@ -86,34 +87,19 @@ struct Batch {
     std::vector<const char*> host_reads; // strq_detect_batch_reads: one buffer per read instead
     void forget_host() { on_host = false; host_src = nullptr; host_reads.clear(); }
     int64_t uploaded = 0;                // reads whose samples are in `raw`
-    std::vector<strq_result> results;
-    std::vector<std::string> mod;        // modification pattern per read ('-' if none)
-    bool units_ran = false;              // the last run call decoded unit positions (strq_set_units)
-    std::vector<std::vector<int64_t>> units;      // unit positions per read (strq_batch_fetch_units)
-    std::vector<uint8_t> unit_dec;       // 1: the read was decoded (gate passed, the flanked model found a path)
-    void reset_units(int64_t n) { units.assign((size_t)n, std::vector<int64_t>()); unit_dec.assign((size_t)n, 0); units_ran = false; }
-    bool conf_ran = false;               // the last run call ran the forward pass (strq_set_confidence)
-    std::vector<double> conf;            // log_lik, count_mean, count_sd per read (strq_batch_fetch_confidence); empty until a run call with confidence on
-    std::vector<uint8_t> conf_dec;
-    std::vector<std::vector<double>> llr;         // (V_base, V_mod) per repeat unit and read (strq_batch_fetch_mod_llr); empty: none
-    void clear_llr(int64_t r) { if ((size_t)r < llr.size()) llr[(size_t)r].clear(); }
-    void clear_conf(int64_t r) { if ((size_t)r < conf_dec.size()) { conf[3 * (size_t)r] = conf[3 * (size_t)r + 1] = conf[3 * (size_t)r + 2] = NAN; conf_dec[(size_t)r] = 0; } }
-    // a new batch of n reads: rows, patterns and unit positions at their initial values, no samples uploaded, nothing of the caller's referenced
+    Extras ran;                          // what the last run call ran with: fetching an output it did not produce is an error
+    // a new batch of n reads: rows, patterns and the optional outputs at their initial values, no samples uploaded, nothing of the caller's referenced
     void begin(int64_t n, int dt)
     {
         forget_host();
         n_reads = n; dtype = dt; uploaded = 0; host_stats.clear();
         target_given.clear(); scan_ncand = 0; cand.clear(); scores.clear();
-        results.assign((size_t)n, strq_result()); mod.assign((size_t)n, std::string("-")); reset_units(n);
-        conf.clear(); conf_dec.clear(); conf_ran = false;
-        llr.assign((size_t)n, std::vector<double>());
+        size_reads(n); ran = Extras();
     }
     float t_cond = 0, t_lut = 0, t_fwd = 0, t_trace = 0, t_vit = 0, t_total = 0;
     double n_hard = 0;
     int n_fwd_launches = 0;
 };
-
-struct VitGroup { int shape, first, count, max_cells; };      // one Viterbi launch: kernel shape, task range, largest n_cells of its models
 
 struct DetectState {
     PoreStats ps{0, 0, 0, 0};
@@ -122,9 +108,7 @@ struct DetectState {
     Batch batch;
     DevBuf rc, hist16, hist8, geom, idx, hist_raw, bp, path, modtask, modsig, modlen, pattern, hrange, modpool, f64s;
     DevBuf unit_task, unit_ws, unit_path, unit_pool;      // unit pass (run_unit_pass): tasks, records / back-pointers, state paths, positions
-    bool units_on = false;               // strq_set_units
-    bool conf_on = false;                // strq_set_confidence
-    bool llr_on = false;                 // strq_set_mod_llr
+    Extras extras;                       // strq_set_units, strq_set_confidence, strq_set_mod_llr: what the next run call uses
     DevBuf llr_ws;                       // per-unit scores (run_llr_pass): tasks, unit bounds, scores
     float llr_ms = 0; double llr_units = 0, llr_reads = 0, llr_launches = 0;      // strq_last_mod_llr: the last run call's scoring pass
     DevBuf conf_task;                    // forward pass (run_conf_pass): tasks, model images, c0, results, order
@@ -151,9 +135,7 @@ struct DetectState {
         State state = Idle;
         std::vector<VitGroup> vls;       // the Viterbi launches of the sub-batch
         int vit_mode = 0;                // 0 count, 2 MARK (modification pass follows)
-        bool units = false;              // the unit pass follows (strq_set_units when the sub-batch was launched)
-        bool conf = false;               // the forward pass follows (strq_set_confidence when the sub-batch was launched)
-        bool llr = false;                // the per-unit scores follow the modification pass (strq_set_mod_llr when the sub-batch was launched)
+        Extras ex;                       // the switches when the sub-batch was launched: the unit pass, the forward pass, the per-unit scores (behind the modification pass) follow
         bool scan = false;               // a scan sub-batch: a read without a winner has no row
         int64_t r0 = 0; int nr = 0;
         std::vector<int32_t> vit_slot;
@@ -294,6 +276,37 @@ static int llr_model(strq_ctx* c, HostModel* hm)
     return STRQ_OK;
 }
 
+// GPU time of a pass on the context's stream: pass_start before its first command, pass_stop behind its last one -- it waits for the
+// stream and adds the milliseconds in between to `total_ms`
+static int pass_start(strq_ctx* c, DetectState* d)
+{
+    STRQ_HIP(c, hipEventRecord(d->ev[2], c->stream));
+    return STRQ_OK;
+}
+static int pass_stop(strq_ctx* c, DetectState* d, float& total_ms)
+{
+    STRQ_HIP(c, hipEventRecord(d->ev[3], c->stream));
+    STRQ_HIP(c, hipStreamSynchronize(c->stream));
+    float ms = 0; STRQ_HIP(c, hipEventElapsedTime(&ms, d->ev[2], d->ev[3])); total_ms += ms;
+    return STRQ_OK;
+}
+
+// The decoded windows of a sub-batch whose rows are being taken: the reads whose gate passed and whose flanked model found a path, and
+// the slot's Viterbi tasks (same windows, same affine source) as the count / MARK launch had them.  The unit pass and the forward pass
+// both start from here; the tasks are read back once, and only when there is a decoded read.
+struct Decoded { std::vector<int> who; std::vector<VitTask> vt; };
+static int read_decoded(strq_ctx* c, DetectState::Slot& sl, Decoded& out)
+{
+    const ReadGeom* geom = sl.host().geom; const VitResult* vres = sl.host().vres;
+    for (int i = 0; i < sl.nr; ++i)
+        if (geom[i].gate && vres[sl.vit_slot[i]].status == 0) out.who.push_back(i);
+    if (out.who.empty()) return STRQ_OK;
+    out.vt.resize((size_t)sl.nr);
+    STRQ_HIP(c, hipMemcpyAsync(out.vt.data(), sl.vit.p, (size_t)sl.nr * sizeof(VitTask), hipMemcpyDeviceToHost, c->stream));
+    STRQ_HIP(c, hipStreamSynchronize(c->stream));
+    return STRQ_OK;
+}
+
 // what run_mod_pass hands to run_llr_pass: its reads, where their decode left signal, records / paths and results
 struct LlrPassIn {
     const std::vector<int>* who; const std::vector<int>* slot2; const std::vector<int64_t>* len;
@@ -318,7 +331,7 @@ static int run_llr_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, cons
     }
     const int64_t U = unit_off[(size_t)nm];
     if (!U) return STRQ_OK;
-    STRQ_HIP(c, hipEventRecord(d->ev[2], st));
+    if (const int rc = pass_start(c, d)) return rc;
     // reads with units, by kernel mode (states per lane / units per wave)
     std::vector<int> by_mode[3];
     for (int k = 0; k < nm; ++k) {
@@ -371,13 +384,11 @@ static int run_llr_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, cons
     std::vector<double> out((size_t)U * 2); std::vector<int32_t> bad((size_t)nb);
     STRQ_HIP(c, hipMemcpyAsync(out.data(), d_out, (size_t)U * 16, hipMemcpyDeviceToHost, st));
     STRQ_HIP(c, hipMemcpyAsync(bad.data(), d_bad, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
-    STRQ_HIP(c, hipEventRecord(d->ev[3], st));
-    STRQ_HIP(c, hipStreamSynchronize(st));
+    if (const int rc = pass_stop(c, d, d->llr_ms)) return rc;
     for (int32_t b : bad) if (b) { c->err = "mod-llr: the unit bounds of a read disagree with its pattern"; return STRQ_ERR_DEVICE; }
     for (int k = 0; k < nm; ++k)
         if (n_units[(size_t)k]) B.llr[(size_t)(r0 + who[k])].assign(out.begin() + (ptrdiff_t)(2 * unit_off[(size_t)k]), out.begin() + (ptrdiff_t)(2 * unit_off[(size_t)k + 1]));
     d->llr_units += (double)U; d->llr_reads += nb; d->llr_launches += 1 + (double)launches.size();
-    float ms = 0; STRQ_HIP(c, hipEventElapsedTime(&ms, d->ev[2], d->ev[3])); d->llr_ms += ms;
     return STRQ_OK;
 }
 
@@ -440,16 +451,18 @@ static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
     if (launch_mod_compact(st, d_mt, nm, d_len)) { c->err = "compaction launch failed"; return STRQ_ERR_DEVICE; }
     // 3. Viterbi on the modification model.  Hub records (one 8-byte record per time step, read back with one
     //    hop per repeat unit) when the model has the hub structure; back-pointers + traceback otherwise.
-    std::map<int, std::vector<int>> by_shape;
+    std::vector<GroupItem> items(nm);
     bool use_hub = !strq::opt("STRQ_MOD_BACKPOINTERS");
     for (int k = 0; k < nm; ++k) {
         HostModel* hm = c->models[d->targets[B.target[r0 + who[k]]].mod_model_id];
         const int shape = vit_shape_of(hm->h);
         if (shape < 0) { c->err = "modification model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
-        by_shape[shape].push_back(k);
+        items[k] = {0, shape, hm->h.n_cells};
         if (hm->h.rec_state < 0 || hm->h.epl > 2 || len[k] >= ((int64_t)1 << 31)) use_hub = false;
     }
-    std::vector<VitTask> vt2(nm); std::vector<int> slot2(nm); std::vector<int32_t*> tp2(nm);
+    const Grouping G = group_items(items);
+    const std::vector<int>& slot2 = G.pos;          // task position of read k
+    std::vector<VitTask> vt2(nm); std::vector<int32_t*> tp2(nm);
     size_t bp2 = 0, p2 = 0; std::vector<size_t> bp2_off(nm), p2_off(nm);
     for (int k = 0; k < nm; ++k) {
         HostModel* hm = c->models[d->targets[B.target[r0 + who[k]]].mod_model_id];
@@ -461,20 +474,18 @@ static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
     STRQ_HIP(c, d->pattern.reserve((use_hub ? 0 : p2 * 4) + p2 + (size_t)nm * 8 + (size_t)nm * sizeof(HubTask) + 64));
     int32_t* d_path2 = d->pattern.as<int32_t>(); char* d_chars = reinterpret_cast<char*>(d_path2 + (use_hub ? 0 : p2));
     STRQ_HIP(c, hipMemsetAsync(c->queue.p, 0, 1024, st));
-    { int sidx = 0, qi = 0;
-      for (auto& g : by_shape) {
-        const int first = sidx; int mx = 0;
-        for (int k : g.second) {
-            HostModel* hm = c->models[d->targets[B.target[r0 + who[k]]].mod_model_id];
-            VitTask& v = vt2[sidx]; v = VitTask();
-            v.model = hm->dev; v.sig = mt[k].out; v.T = len[k]; v.src_kind = VIT_SRC_F64; v.bp = d->bp.as<uint16_t>() + bp2_off[k];
-            slot2[k] = sidx; tp2[sidx] = d_path2 + p2_off[k]; mx = std::max(mx, hm->h.n_cells); ++sidx;
-        }
-        STRQ_HIP(c, hipMemcpyAsync(d_tb + first, vt2.data() + first, (size_t)(sidx - first) * sizeof(VitTask), hipMemcpyHostToDevice, st));
-        const VitGroup vg = {g.first, first, sidx - first, mx};
+    for (int k = 0; k < nm; ++k) {
+        VitTask& v = vt2[slot2[k]]; v = VitTask();
+        v.model = c->models[d->targets[B.target[r0 + who[k]]].mod_model_id]->dev; v.sig = mt[k].out; v.T = len[k]; v.src_kind = VIT_SRC_F64;
+        v.bp = d->bp.as<uint16_t>() + bp2_off[k];
+        tp2[slot2[k]] = d_path2 + p2_off[k];
+    }
+    int qi = 0;
+    for (const VitGroup& vg : G.groups) {
+        STRQ_HIP(c, hipMemcpyAsync(d_tb + vg.first, vt2.data() + vg.first, (size_t)vg.count * sizeof(VitTask), hipMemcpyHostToDevice, st));
         if (const int src = sort_viterbi_group(c, st, vg, d_tb, sl.order.as<int>())) return src;
         if (const int lrc = launch_viterbi_group(c, st, vg, d_tb, d_tr, sl.order.as<int>(), c->queue.as<int>() + qi++, use_hub ? 3 : 1)) return lrc;
-      } }
+    }
     int64_t* d_plen = d_len;
     if (use_hub) {
         // 4. pattern strings from the hub records
@@ -502,7 +513,7 @@ static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
         if (launch_mod_pattern(st, d_pt, nm, d_plen)) { c->err = "pattern launch failed"; return STRQ_ERR_DEVICE; }
     }
     if (const int prc = read_mod_patterns(c, d, r0, who, slot2, len, p2_off, d_plen, d_chars)) return prc;
-    if (!sl.llr) return STRQ_OK;
+    if (!sl.ex.llr) return STRQ_OK;
     // 5. per-unit scores of both branches: modsig, the records / the traced paths and the results are live until the next pass
     LlrPassIn li;
     li.who = &who; li.slot2 = &slot2; li.len = &len; li.sig_off = &sig_off; li.bp2_off = &bp2_off; li.paths = &tp2;
@@ -515,22 +526,14 @@ static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
 // records, VIT_UNIT_T_MAX) where the model and the window allow it, else (STRQ_UNITS_BACKPOINTERS=1: always) with back-pointers and a
 // traceback.  Runs on the context's stream when the rows of the sub-batch are taken: the slot's filtered signal and tasks are live
 // until the slot is used again, which harvests it first.  Pieces of at most STRQ_UNITS_WS_BYTES (8 GiB) of records / back-pointers.
-static int run_unit_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
+static int run_unit_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, const Decoded& dec)
 {
     Batch& B = d->batch;
     hipStream_t st = c->stream;
-    const int64_t r0 = sl.r0; const int nr = sl.nr;
+    const int64_t r0 = sl.r0;
     const ReadGeom* geom = sl.host().geom; const VitResult* vres = sl.host().vres;
-    std::vector<int> who;                      // reads with a decode: gate passed, the flanked model found a path
-    for (int i = 0; i < nr; ++i) {
-        B.units[(size_t)(r0 + i)].clear(); B.unit_dec[(size_t)(r0 + i)] = 0;
-        if (geom[i].gate && vres[sl.vit_slot[i]].status == 0) who.push_back(i);
-    }
-    if (who.empty()) return STRQ_OK;
-    STRQ_HIP(c, hipEventRecord(d->ev[2], st));
-    std::vector<VitTask> vt((size_t)nr);
-    STRQ_HIP(c, hipMemcpyAsync(vt.data(), sl.vit.p, (size_t)nr * sizeof(VitTask), hipMemcpyDeviceToHost, st));
-    STRQ_HIP(c, hipStreamSynchronize(st));
+    const std::vector<int>& who = dec.who; const std::vector<VitTask>& vt = dec.vt;
+    if (const int rc = pass_start(c, d)) return rc;
     const bool force_bp = strq::opt("STRQ_UNITS_BACKPOINTERS") != nullptr;
     size_t budget = (size_t)8 << 30;
     if (const char* e = strq::opt("STRQ_UNITS_WS_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
@@ -550,10 +553,14 @@ static int run_unit_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
     for (size_t c0 = 0; c0 < ws.size();) {
         size_t c1 = c0, bytes = 0;
         while (c1 < ws.size() && (c1 == c0 || bytes + ws[c1].bytes <= budget)) bytes += ws[c1++].bytes;
-        // this piece's windows grouped by (route, kernel shape): unit-record launches first
-        std::map<std::pair<int, int>, std::vector<int>> groups;
-        for (size_t k = c0; k < c1; ++k) groups[{ws[k].rec ? 0 : 1, ws[k].shape}].push_back((int)k);
+        // this piece's windows grouped by (route, kernel shape): unit-record launches (route 0) first
         const int m = (int)(c1 - c0);
+        std::vector<GroupItem> items((size_t)m);
+        for (int k = 0; k < m; ++k) {
+            const W& w = ws[c0 + (size_t)k];
+            items[(size_t)k] = {w.rec ? 0 : 1, w.shape, c->models[d->targets[B.target[r0 + w.i]].model_id]->h.n_cells};
+        }
+        const Grouping G = group_items(items);
         STRQ_HIP(c, d->unit_task.reserve((size_t)m * (sizeof(VitTask) + sizeof(VitResult) + 8 + sizeof(UnitTask) + 4) + 256));
         VitTask* d_vt = d->unit_task.as<VitTask>();
         VitResult* d_vr = reinterpret_cast<VitResult*>(d_vt + m);
@@ -570,27 +577,21 @@ static int run_unit_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
         STRQ_HIP(c, d->unit_pool.reserve(pos_n * 8 + 64));
         std::vector<VitTask> tv((size_t)m); std::vector<int32_t*> pv((size_t)m, nullptr); std::vector<UnitTask> uv((size_t)m);
         std::vector<int> read_of((size_t)m); std::vector<size_t> pos_off((size_t)m);
-        struct L { VitGroup g; int want; };
-        std::vector<L> launches;
-        size_t wo = 0, po = 0, xo = 0; int at = 0, n_rec = 0;
-        for (auto& g : groups) {
-            const int first = at; int mx = 0;
-            for (int k : g.second) {
-                const W& w = ws[(size_t)k];
-                HostModel* hm = c->models[d->targets[B.target[r0 + w.i]].model_id];
-                const VitResult& v0 = vres[sl.vit_slot[w.i]];
-                VitTask t = vt[(size_t)sl.vit_slot[w.i]];
-                t.bp = reinterpret_cast<uint16_t*>(d->unit_ws.as<char>() + wo); wo += (w.bytes + 15) & ~(size_t)15;
-                if (wo > d->unit_ws.cap) { c->err = "unit pass: workspace"; return STRQ_ERR_NOMEM; }
-                UnitTask u; std::memset(&u, 0, sizeof(u));
-                u.rec = w.rec ? reinterpret_cast<const uint32_t*>(t.bp) : nullptr;
-                if (!w.rec) { pv[(size_t)at] = d->unit_path.as<int32_t>() + po; u.path = pv[(size_t)at]; u.count_inc = hm->h.count_inc; po += (size_t)t.T; }
-                u.result = d_vr + at; u.out = d->unit_pool.as<int64_t>() + xo; u.T = t.T; u.base = geom[w.i].prefix_begin; u.n = v0.counted; u.bad = d_bad + at;
-                pos_off[(size_t)at] = xo; xo += (size_t)v0.counted;
-                tv[(size_t)at] = t; uv[(size_t)at] = u; read_of[(size_t)at] = w.i;
-                mx = std::max(mx, hm->h.n_cells); ++at; n_rec += w.rec ? 1 : 0;
-            }
-            launches.push_back({{g.first.second, first, at - first, mx}, g.first.first == 0 ? 4 : 1});
+        size_t wo = 0, po = 0, xo = 0; int n_rec = 0;
+        for (int at = 0; at < m; ++at) {          // in task order: the workspace, the paths and the positions lie in that order too
+            const W& w = ws[c0 + (size_t)G.order[(size_t)at]];
+            HostModel* hm = c->models[d->targets[B.target[r0 + w.i]].model_id];
+            const VitResult& v0 = vres[sl.vit_slot[w.i]];
+            VitTask t = vt[(size_t)sl.vit_slot[w.i]];
+            t.bp = reinterpret_cast<uint16_t*>(d->unit_ws.as<char>() + wo); wo += (w.bytes + 15) & ~(size_t)15;
+            if (wo > d->unit_ws.cap) { c->err = "unit pass: workspace"; return STRQ_ERR_NOMEM; }
+            UnitTask u; std::memset(&u, 0, sizeof(u));
+            u.rec = w.rec ? reinterpret_cast<const uint32_t*>(t.bp) : nullptr;
+            if (!w.rec) { pv[(size_t)at] = d->unit_path.as<int32_t>() + po; u.path = pv[(size_t)at]; u.count_inc = hm->h.count_inc; po += (size_t)t.T; }
+            u.result = d_vr + at; u.out = d->unit_pool.as<int64_t>() + xo; u.T = t.T; u.base = geom[w.i].prefix_begin; u.n = v0.counted; u.bad = d_bad + at;
+            pos_off[(size_t)at] = xo; xo += (size_t)v0.counted;
+            tv[(size_t)at] = t; uv[(size_t)at] = u; read_of[(size_t)at] = w.i;
+            n_rec += w.rec ? 1 : 0;
         }
         STRQ_HIP(c, hipMemcpyAsync(d_vt, tv.data(), (size_t)m * sizeof(VitTask), hipMemcpyHostToDevice, st));
         STRQ_HIP(c, hipMemcpyAsync(d_paths, pv.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
@@ -600,10 +601,11 @@ static int run_unit_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
         STRQ_HIP(c, c->queue.reserve(1024));
         STRQ_HIP(c, hipMemsetAsync(c->queue.p, 0, 1024, st));
         int qi = 0;
-        for (const L& l : launches) {
-            if (const int src = sort_viterbi_group(c, st, l.g, d_vt, sl.order.as<int>())) return src;
-            if (const int lrc = launch_viterbi_group(c, st, l.g, d_vt, d_vr, sl.order.as<int>(), c->queue.as<int>() + qi++, l.want, 0, "unit pass: ")) return lrc;
-            if (l.want == 1 && launch_vit_traceback(st, d_vt + l.g.first, d_vr + l.g.first, d_paths + l.g.first, l.g.count)) { c->err = "traceback launch failed"; return STRQ_ERR_DEVICE; }
+        for (const VitGroup& g : G.groups) {
+            const int want = g.route == 0 ? 4 : 1;          // unit records, or back-pointers and a traceback
+            if (const int src = sort_viterbi_group(c, st, g, d_vt, sl.order.as<int>())) return src;
+            if (const int lrc = launch_viterbi_group(c, st, g, d_vt, d_vr, sl.order.as<int>(), c->queue.as<int>() + qi++, want, 0, "unit pass: ")) return lrc;
+            if (want == 1 && launch_vit_traceback(st, d_vt + g.first, d_vr + g.first, d_paths + g.first, g.count)) { c->err = "traceback launch failed"; return STRQ_ERR_DEVICE; }
         }
         if (launch_unit_hop(st, d_ut, n_rec) || launch_unit_scan(st, d_ut + n_rec, m - n_rec)) { c->err = "unit position launch failed"; return STRQ_ERR_DEVICE; }
         std::vector<int64_t> pos(xo + 1); std::vector<int32_t> bad((size_t)m);
@@ -620,38 +622,29 @@ static int run_unit_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
         d->unit_bytes = std::max(d->unit_bytes, (double)bytes); d->unit_reads += m; d->unit_positions += (double)xo;
         c0 = c1;
     }
-    STRQ_HIP(c, hipEventRecord(d->ev[3], st));
-    STRQ_HIP(c, hipEventSynchronize(d->ev[3]));
-    float ms = 0; STRQ_HIP(c, hipEventElapsedTime(&ms, d->ev[2], d->ev[3])); d->unit_ms += ms;
-    return STRQ_OK;
+    return pass_stop(c, d, d->unit_ms);
 }
 
 // Count confidence of the reads of one sub-batch (strq_set_confidence): the forward pass (forward_kernels.hip) over the windows the
 // count / MARK launch decoded, with the same tasks -- same windows, same affine source on the slot's filtered signal -- and c0 = the
 // visits of the best path from the rows just taken.  Runs on the context's stream like the unit pass; one launch per kernel shape.
-static int run_conf_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
+static int run_conf_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, const Decoded& dec)
 {
     Batch& B = d->batch;
     hipStream_t st = c->stream;
-    const int64_t r0 = sl.r0; const int nr = sl.nr;
-    const ReadGeom* geom = sl.host().geom; const VitResult* vres = sl.host().vres;
-    std::vector<int> who;                      // reads with a decode: gate passed, the flanked model found a path
-    for (int i = 0; i < nr; ++i) {
-        B.clear_conf(r0 + i);
-        if (geom[i].gate && vres[sl.vit_slot[i]].status == 0) who.push_back(i);
-    }
-    if (who.empty()) return STRQ_OK;
-    STRQ_HIP(c, hipEventRecord(d->ev[2], st));
-    std::vector<VitTask> vt((size_t)nr);
-    STRQ_HIP(c, hipMemcpyAsync(vt.data(), sl.vit.p, (size_t)nr * sizeof(VitTask), hipMemcpyDeviceToHost, st));
-    STRQ_HIP(c, hipStreamSynchronize(st));
-    std::map<int, std::vector<int>> groups;          // kernel shape -> reads
-    for (int i : who) {
-        HostModel* hm = c->models[d->targets[B.target[r0 + i]].model_id];
-        if (const int rc = forward_model(c, hm)) return rc;
-        groups[vit_shape_of(hm->h)].push_back(i);
-    }
+    const int64_t r0 = sl.r0;
+    const VitResult* vres = sl.host().vres;
+    const std::vector<int>& who = dec.who; const std::vector<VitTask>& vt = dec.vt;
+    if (const int rc = pass_start(c, d)) return rc;
     const int m = (int)who.size();
+    std::vector<GroupItem> items((size_t)m);
+    for (int k = 0; k < m; ++k) {
+        HostModel* hm = c->models[d->targets[B.target[r0 + who[(size_t)k]]].model_id];
+        if (const int rc = forward_model(c, hm)) return rc;
+        items[(size_t)k] = {0, vit_shape_of(hm->h), hm->h.n_cells};
+    }
+    const Grouping G = group_items(items);
+    const std::vector<VitGroup>& launches = G.groups;
     STRQ_HIP(c, d->conf_task.reserve((size_t)m * (sizeof(VitTask) + sizeof(FwdResult) + 8 + 8 + 4) + 256));
     VitTask* d_vt = d->conf_task.as<VitTask>();
     FwdResult* d_fr = reinterpret_cast<FwdResult*>(d_vt + m);
@@ -659,17 +652,10 @@ static int run_conf_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
     int64_t* d_c0 = reinterpret_cast<int64_t*>(d_fm + m);
     int* d_order = reinterpret_cast<int*>(d_c0 + m);
     std::vector<VitTask> tv((size_t)m); std::vector<const FwdModel*> fv((size_t)m); std::vector<int64_t> cv((size_t)m); std::vector<int> read_of((size_t)m);
-    std::vector<VitGroup> launches;
-    int at = 0;
-    for (auto& g : groups) {
-        const int first = at; int mx = 0;
-        for (int i : g.second) {
-            HostModel* hm = c->models[d->targets[B.target[r0 + i]].model_id];
-            tv[(size_t)at] = vt[(size_t)sl.vit_slot[i]]; tv[(size_t)at].bp = nullptr;
-            fv[(size_t)at] = hm->fwd_dev; cv[(size_t)at] = vres[sl.vit_slot[i]].counted; read_of[(size_t)at] = i;
-            mx = std::max(mx, hm->h.n_cells); ++at;
-        }
-        launches.push_back({g.first, first, at - first, mx});
+    for (int at = 0; at < m; ++at) {
+        const int i = who[(size_t)G.order[(size_t)at]];
+        tv[(size_t)at] = vt[(size_t)sl.vit_slot[i]]; tv[(size_t)at].bp = nullptr;
+        fv[(size_t)at] = c->models[d->targets[B.target[r0 + i]].model_id]->fwd_dev; cv[(size_t)at] = vres[sl.vit_slot[i]].counted; read_of[(size_t)at] = i;
     }
     STRQ_HIP(c, hipMemcpyAsync(d_vt, tv.data(), (size_t)m * sizeof(VitTask), hipMemcpyHostToDevice, st));
     STRQ_HIP(c, hipMemcpyAsync(d_fm, fv.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
@@ -687,8 +673,7 @@ static int run_conf_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
     }
     std::vector<FwdResult> fr((size_t)m);
     STRQ_HIP(c, hipMemcpyAsync(fr.data(), d_fr, (size_t)m * sizeof(FwdResult), hipMemcpyDeviceToHost, st));
-    STRQ_HIP(c, hipEventRecord(d->ev[3], st));
-    STRQ_HIP(c, hipStreamSynchronize(st));
+    if (const int rc = pass_stop(c, d, d->conf_ms)) return rc;
     for (int k = 0; k < m; ++k) {
         const int64_t r = r0 + read_of[(size_t)k];
         double ll, mean, var;
@@ -700,7 +685,6 @@ static int run_conf_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
         d->conf_nopath += nopath; d->conf_expo = std::max(d->conf_expo, std::fabs((double)fr[(size_t)k].expo));
     }
     d->conf_windows += m;
-    float ms = 0; STRQ_HIP(c, hipEventElapsedTime(&ms, d->ev[2], d->ev[3])); d->conf_ms += ms;
     return STRQ_OK;
 }
 
@@ -808,9 +792,7 @@ static int abandon(DetectState* d, DetectState::Slot& sl, int rc)
     Batch& B = d->batch;
     sl.state = DetectState::Slot::Idle;
     for (int64_t r = sl.r0; r < sl.r0 + sl.nr && r < (int64_t)B.results.size(); ++r) {
-        B.results[(size_t)r] = strq_result(); B.mod[(size_t)r] = "-";
-        B.units[(size_t)r].clear(); B.unit_dec[(size_t)r] = 0;
-        B.clear_conf(r); B.clear_llr(r);
+        B.clear_read(r);
         if (sl.scan && (size_t)r < B.cand.size()) {
             B.cand[(size_t)r] = -1;
             std::fill(B.scores.begin() + (ptrdiff_t)((size_t)r * 2 * B.scan_ncand), B.scores.begin() + (ptrdiff_t)((size_t)(r + 1) * 2 * B.scan_ncand), 0.0);
@@ -858,8 +840,8 @@ static int take_rows(strq_ctx* c, DetectState* d, DetectState::Slot& sl, bool un
     const int nr = sl.nr; const int64_t r0 = sl.r0;
     const DetectState::Slot::Pinned h = sl.host();
     for (int i = 0; i < nr; ++i) {
+        B.clear_read(r0 + i);          // row, pattern and the outputs of the passes below: whatever is not computed now stays at its initial value
         strq_result& o = B.results[r0 + i];
-        std::memset(&o, 0, sizeof(o));
         const ReadGeom& g = h.geom[i];
         const VitResult& v = h.vres[sl.vit_slot[i]];
         o.status = h.rc[i].status == COND_OK ? 0 : 1;
@@ -889,14 +871,14 @@ static int take_rows(strq_ctx* c, DetectState* d, DetectState::Slot& sl, bool un
         c->overlap[3] += 1;
     }
     publish_timing(c, B);
-    for (int i = 0; i < nr; ++i) B.clear_llr(r0 + i);
     // the mode the launches ran with decides, not what the targets say by now
     if (sl.vit_mode == 2) { const int mrc = run_mod_pass(c, d, sl); if (mrc) return mrc; }
-    if (sl.units) { const int urc = run_unit_pass(c, d, sl); if (urc) return urc; }
-    else for (int i = 0; i < nr; ++i) { B.units[(size_t)(r0 + i)].clear(); B.unit_dec[(size_t)(r0 + i)] = 0; }
-    if (sl.conf) return run_conf_pass(c, d, sl);
-    for (int i = 0; i < nr; ++i) B.clear_conf(r0 + i);
-    return STRQ_OK;
+    if (!sl.ex.units && !sl.ex.conf) return STRQ_OK;
+    Decoded dec;
+    if (const int drc = read_decoded(c, sl, dec)) return drc;
+    if (dec.who.empty()) return STRQ_OK;
+    if (sl.ex.units) { const int urc = run_unit_pass(c, d, sl, dec); if (urc) return urc; }
+    return sl.ex.conf ? run_conf_pass(c, d, sl, dec) : STRQ_OK;
 }
 
 // Results of a sub-batch in flight: queues its Viterbi launches if nobody came after it, waits for them, fills Batch::results (and runs
@@ -1034,24 +1016,17 @@ static int plan_viterbi(strq_ctx* c, DetectState* d, SubBatch& S)
     const Batch& B = d->batch;
     DetectState::Slot& sl = *S.sl;
     const int nr = S.nr;
-    std::map<int, std::vector<int>> by_shape;
+    std::vector<GroupItem> items(nr);
     std::vector<const VitModel*> model_of(nr);
     for (int i = 0; i < nr; ++i) {
         HostModel* hm = c->models[d->targets[B.target[S.r0 + i]].model_id];
         model_of[i] = hm->dev;
         const int shape = vit_shape_for(hm->h, S.any_mod ? 2 : 0);
         if (shape < 0) { c->err = "model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
-        by_shape[shape].push_back(i);
+        items[i] = {0, shape, hm->h.n_cells};
     }
-    sl.vit_slot.assign(nr, 0);
-    sl.vls.clear();
-    int k = 0;
-    for (auto& g : by_shape) {
-        int mx = 0;
-        for (int i : g.second) mx = std::max(mx, c->models[d->targets[B.target[S.r0 + i]].model_id]->h.n_cells);
-        sl.vls.push_back({g.first, k, (int)g.second.size(), mx});
-        for (int i : g.second) sl.vit_slot[i] = k++;
-    }
+    Grouping G = group_items(items);
+    sl.vls.swap(G.groups); sl.vit_slot.swap(G.pos);
     STRQ_HIP(c, hipMemcpyAsync(S.d_model_of, model_of.data(), (size_t)nr * 8, hipMemcpyHostToDevice, c->stream));
     STRQ_HIP(c, hipMemcpyAsync(S.d_slot, sl.vit_slot.data(), (size_t)nr * 4, hipMemcpyHostToDevice, c->stream));
     return STRQ_OK;
@@ -1245,9 +1220,7 @@ static int publish_forward(strq_ctx* c, DetectState* d, const SubBatch& S)
     if (c->redo_total.p) STRQ_HIP(c, hipMemcpyAsync(h.redo, c->redo_total.p, 4, hipMemcpyDeviceToHost, st));
     STRQ_HIP(c, hipEventRecord(sl.fwd_done, st));
     sl.vit_mode = S.any_mod ? 2 : 0;
-    sl.units = d->units_on;
-    sl.conf = d->conf_on;
-    sl.llr = d->llr_on;
+    sl.ex = d->extras;
     sl.scan = S.nc > 0;
     sl.state = DetectState::Slot::Forward;
     return STRQ_OK;
@@ -1471,10 +1444,8 @@ int run_range(strq_ctx* c, DetectState* d, int64_t first, int64_t last)
         if (!B.target_given.empty()) { B.target = B.target_given; B.target_given.clear(); }
         B.scan_ncand = 0; B.cand.clear(); B.scores.clear();
     }
-    B.units_ran = d->units_on;
+    B.ran = d->extras;
     d->unit_ms = 0; d->unit_bytes = d->unit_reads = d->unit_positions = 0;
-    B.conf_ran = d->conf_on;
-    if (d->conf_on && B.conf_dec.size() != (size_t)B.n_reads) { B.conf.assign(3 * (size_t)B.n_reads, NAN); B.conf_dec.assign((size_t)B.n_reads, 0); }
     d->conf_ms = 0; d->conf_windows = d->conf_nopath = d->conf_expo = 0;
     d->llr_ms = 0; d->llr_units = d->llr_reads = d->llr_launches = 0;
     STRQ_HIP(c, c->redo_total.reserve(64));
@@ -1528,6 +1499,19 @@ int copy_scan(strq_ctx* c, const DetectState* d, int32_t* out_cand, double* out_
     return STRQ_OK;
 }
 
+// strq_set_units / _confidence / _mod_llr: one switch of DetectState::extras.  `bad`: the entry's message for an argument other than 0
+// or 1; `validate`: what must hold before the switch goes on.
+int set_extra(strq_ctx* c, int32_t on, const char* bad, bool Extras::* which, int (*validate)(strq_ctx*, DetectState*) = nullptr)
+{
+    if (on != 0 && on != 1) { c->err = bad; return STRQ_ERR_ARG; }
+    DetectState* d = dstate(c);
+    // sub-batches in flight keep the mode they were launched with: their pass (or none) runs now
+    if (const int rc = drain(c, d)) return rc;
+    if (on && validate) { if (const int rc = validate(c, d)) return rc; }
+    d->extras.*which = on != 0;
+    return STRQ_OK;
+}
+
 // strq_detect_batch*: a plain detect whatever scan set the context holds (put back when the call is through)
 struct PlainScope {
     DetectState* d; bool on;
@@ -1573,7 +1557,7 @@ int strq_target_set_mod(strq_ctx* c, int32_t target_id, int32_t mod_model_id, do
     DetectState* d = dstate(c);
     if (target_id < 0 || target_id >= (int32_t)d->targets.size() || mod_model_id < 0 || mod_model_id >= (int32_t)c->models.size()) { c->err = "bad argument"; return STRQ_ERR_ARG; }
     if (const int rc = drain(c, d)) return rc;          // a sub-batch in flight is taken with the target it ran with
-    if (d->llr_on) { if (const int rc = llr_model(c, c->models[mod_model_id])) return rc; }          // (the target stays as it was)
+    if (d->extras.llr) { if (const int rc = llr_model(c, c->models[mod_model_id])) return rc; }          // (the target stays as it was)
     d->targets[target_id].mod_model_id = mod_model_id; d->targets[target_id].mod_min = mod_min; d->targets[target_id].mod_max = mod_max;
     return STRQ_OK;
 }
@@ -1598,12 +1582,7 @@ int strq_batch_fetch_mod(strq_ctx* c, char* pool, int64_t pool_cap, int64_t* off
 int strq_set_units(strq_ctx* c, int32_t on)
 {
     STRQ_ENTER(c);
-    if (on != 0 && on != 1) { c->err = "bad argument (strq_set_units takes 0 or 1)"; return STRQ_ERR_ARG; }
-    DetectState* d = dstate(c);
-    // sub-batches in flight keep the mode they were launched with: their unit pass (or none) runs now
-    if (const int rc = drain(c, d)) return rc;
-    d->units_on = on != 0;
-    return STRQ_OK;
+    return set_extra(c, on, "bad argument (strq_set_units takes 0 or 1)", &Extras::units);
 }
 
 int strq_batch_fetch_units(strq_ctx* c, int64_t* pool, int64_t pool_cap, int64_t* off, int32_t* decoded)
@@ -1613,7 +1592,7 @@ int strq_batch_fetch_units(strq_ctx* c, int64_t* pool, int64_t pool_cap, int64_t
     DetectState* d = dstate(c);
     if (const int rc = drain(c, d)) return rc;
     const Batch& B = d->batch;
-    if (!B.units_ran) { c->err = "the last batch ran without unit positions (strq_set_units)"; return STRQ_ERR_ARG; }
+    if (!B.ran.units) { c->err = "the last batch ran without unit positions (strq_set_units)"; return STRQ_ERR_ARG; }
     int64_t pos = 0;
     for (size_t i = 0; i < B.units.size(); ++i) {
         off[i] = pos;
@@ -1640,12 +1619,7 @@ int strq_last_units(strq_ctx* c, double* out4)
 int strq_set_confidence(strq_ctx* c, int32_t on)
 {
     STRQ_ENTER(c);
-    if (on != 0 && on != 1) { c->err = "bad argument (strq_set_confidence takes 0 or 1)"; return STRQ_ERR_ARG; }
-    DetectState* d = dstate(c);
-    // sub-batches in flight keep the mode they were launched with: their forward pass (or none) runs now
-    if (const int rc = drain(c, d)) return rc;
-    d->conf_on = on != 0;
-    return STRQ_OK;
+    return set_extra(c, on, "bad argument (strq_set_confidence takes 0 or 1)", &Extras::conf);
 }
 
 int strq_batch_fetch_confidence(strq_ctx* c, double* out3, int32_t* decoded)
@@ -1655,7 +1629,7 @@ int strq_batch_fetch_confidence(strq_ctx* c, double* out3, int32_t* decoded)
     DetectState* d = dstate(c);
     if (const int rc = drain(c, d)) return rc;
     const Batch& B = d->batch;
-    if (!B.conf_ran) { c->err = "the last batch ran without confidence (strq_set_confidence)"; return STRQ_ERR_ARG; }
+    if (!B.ran.conf) { c->err = "the last batch ran without confidence (strq_set_confidence)"; return STRQ_ERR_ARG; }
     if (!B.conf.empty()) std::memcpy(out3, B.conf.data(), B.conf.size() * 8);
     if (decoded) for (size_t i = 0; i < B.conf_dec.size(); ++i) decoded[i] = B.conf_dec[i];
     return STRQ_OK;
@@ -1673,15 +1647,12 @@ int strq_last_confidence(strq_ctx* c, double* out4)
 int strq_set_mod_llr(strq_ctx* c, int32_t on)
 {
     STRQ_ENTER(c);
-    if (on != 0 && on != 1) { c->err = "bad argument (strq_set_mod_llr takes 0 or 1)"; return STRQ_ERR_ARG; }
-    DetectState* d = dstate(c);
-    // sub-batches in flight keep the mode they were launched with: their scoring pass (or none) runs now
-    if (const int rc = drain(c, d)) return rc;
-    if (on)          // every modification model registered so far must be one the pass covers (later ones: strq_target_set_mod)
+    // every modification model registered so far must be one the pass covers (later ones: strq_target_set_mod)
+    return set_extra(c, on, "bad argument (strq_set_mod_llr takes 0 or 1)", &Extras::llr, [](strq_ctx* c, DetectState* d) -> int {
         for (const Target& t : d->targets)
             if (t.mod_model_id >= 0) { if (const int rc = llr_model(c, c->models[t.mod_model_id])) return rc; }
-    d->llr_on = on != 0;
-    return STRQ_OK;
+        return STRQ_OK;
+    });
 }
 
 int strq_batch_fetch_mod_llr(strq_ctx* c, double* pool, int64_t pool_cap, int64_t* off)
@@ -1694,7 +1665,6 @@ int strq_batch_fetch_mod_llr(strq_ctx* c, double* pool, int64_t pool_cap, int64_
     int64_t pos = 0;
     for (int64_t i = 0; i < B.n_reads; ++i) {
         off[i] = pos;
-        if ((size_t)i >= B.llr.size()) continue;
         const std::vector<double>& v = B.llr[(size_t)i];
         const int64_t n = (int64_t)v.size() / 2;
         if (pool) {

@@ -186,7 +186,8 @@ import torch.distributed as dist
 for units in (False, True):
     stats = {}
     mine = cli.run_count(iter(lines), loci, get_raw, FakeCounter(), log, 4, rank, world, stats=stats, units=units, confidence=True)
-    merged, merged_units, merged_conf = cli.gather_rows(mine, stats["items"], sdist, units=units, confidence=True)      # still one gather
+    got = cli.gather_rows(mine, stats["items"], sdist, units=units, confidence=True)      # still one gather
+    merged, merged_units, merged_conf = got.rows, got.units, got.confidence
     if rank == 0:
         buf = io.StringIO(); cli.write_rows(buf, merged)
         cbuf = io.StringIO(); cli.write_rows(cbuf, merged_conf, header=cli.CONF_HEADER)

@@ -71,7 +71,7 @@ log = cli.Log("error")
 stats = {}
 mine = cli.run_count(iter(lines), loci, get_raw, FakeCounter(), log, 5, rank, world, stats=stats)
 import torch.distributed as dist
-merged = cli.gather_rows(mine, stats["items"], sdist)            # the run's one collective (records + byte pool)
+merged = cli.gather_rows(mine, stats["items"], sdist).rows            # the run's one collective (records + byte pool)
 if rank == 0:
     buf = io.StringIO(); cli.write_rows(buf, merged)
     one = io.StringIO(); cli.run_count(iter(lines), loci, get_raw, FakeCounter(), log, 5, 0, 1, one)

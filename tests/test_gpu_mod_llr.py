@@ -229,6 +229,64 @@ def test_routes_and_scheduling_give_the_same_bytes(pm, pm_mod, cfg, targets, six
         assert np.array_equal(a[1], u[1]) and a[2] == c[1] and _same_bits(a[3], b[1])
 
 
+def test_all_outputs_share_one_read_back_and_one_grouping(pm, pm_mod, cfg, targets):
+    """Units, confidence and mod_llr together, in sub-batches of 3 (two in flight, the last one harvested by the fetch) and serially:
+    every element equals, bit for bit, the one of a run that asks for that output alone in one sub-batch.  The batch is the smallest
+    at which the decoded windows the passes share and the launch grouping can go wrong: two targets in different Viterbi kernel
+    shapes, interleaved (the task position of a read is not its index), and a read in the middle that fails the gate (the decoded
+    list skips a position).  C9orf72 decodes on the register-resident kernel, as every bundled target does; the 12-nt unit of
+    test_gpu_units.py has no such layout and takes a lane-layout shape."""
+    from strique_amd import synth
+    from strique_amd.ffi import StriqueHipError
+    from test_gpu_units import CUSTOM
+    both = {"c9orf72": targets["c9orf72"], "units_dodeca": CUSTOM["units_dodeca"]}
+    rc = _counter(pm, pm_mod, cfg)
+    for name, target in both.items():
+        rc.add_target(name, *target)
+    plan = [("c9orf72", "+", 3000, 9), ("units_dodeca", "-", 4500, 14), ("c9orf72", "-", 5200, 31), None,
+            ("units_dodeca", "+", 6000, 22), ("c9orf72", "+", 3600, 17), ("units_dodeca", "-", 3300, 6)]
+    items = []
+    for k, p in enumerate(plan):
+        if p is None:          # pure noise: no flank, the gate fails
+            items.append(("c9orf72", np.random.default_rng(3).integers(200, 800, 4000).astype(np.int16), "-"))
+            continue
+        name, strand, nt, nrep = p
+        table = synth.KmerTable(pm_mod if k % 2 else pm)
+        items.append((name, synth.make_read(table, 53, k, nt, both[name], nrep, strand=strand, as_int16=True)[0], strand))
+    bad = plan.index(None)
+
+    def run(options, **kw):
+        for k, v in options.items():
+            rc.ctx.set_option(k, v)
+        try:
+            return rc.detect_batch(items, **kw)
+        finally:
+            for k in options:
+                rc.ctx.set_option(k, "")
+
+    units = run({}, units=True)
+    assert rc.ctx.last_viterbi_launches()["launches"] == 2          # one sub-batch, two kernel shapes
+    conf, llr = run({}, confidence=True), run({}, mod_llr=True)
+    rows = [u[0] for u in units]
+    assert rows[bad][0] == 0 and units[bad][1] is None and conf[bad][1] is None and llr[bad][1] is None
+    assert sum(u[1] is not None and len(u[1]) > 0 for u in units) == len(items) - 1
+    assert all(c[1] is not None for k, c in enumerate(conf) if k != bad) and sum(v[1] is not None for v in llr) >= len(items) - 2
+    for options in ({"STRQ_SUBBATCH_READS": "3"}, {"STRQ_SERIAL": "1"}):
+        got = run(options, units=True, confidence=True, mod_llr=True)
+        assert len(got) == len(items)
+        for k, (a, u, c, v) in enumerate(zip(got, units, conf, llr)):
+            assert len(a) == 4 and tuple(a[0]) == tuple(u[0]) == tuple(c[0]) == tuple(v[0]), (options, k)
+            for x, y in ((a[1], u[1]), (a[2], c[1]), (a[3], v[1])):
+                assert (x is None) == (y is None), (options, k)
+                assert x is None or _same_bits(x, y), (options, k, x, y)
+        assert got[bad][1:] == (None, None, None)
+    # the switches are off again: a plain run gives the plain rows, and its batch holds no unit positions
+    assert run({}) == rows
+    with pytest.raises(StriqueHipError, match="ran without unit positions"):
+        rc.ctx.batch_fetch_units()
+    rc.ctx.close()
+
+
 def test_switch_off_launches_nothing_and_returns_no_units(mod_counter, six):
     items, refs = six
     ctx = mod_counter.ctx

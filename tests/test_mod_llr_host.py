@@ -144,7 +144,8 @@ def test_count_rows_with_a_stubbed_counter(cfg, units, confidence):
     st2 = {}
     mine = cli.run_count(iter(lines), loci, get_raw, FakeCounter(), log, 4, 0, 2, stats=st2, mod_llr=True, **kw)
     other = cli.run_count(iter(lines), loci, get_raw, FakeCounter(), log, 4, 1, 2, stats={}, mod_llr=True, **kw)
-    merged, munits, mconf, mllr = cli.gather_rows(mine + other, st2["items"], OneRank, mod_llr=True, **kw)
+    got = cli.gather_rows(mine + other, st2["items"], OneRank, mod_llr=True, **kw)
+    merged, munits, mconf, mllr = got.rows, got.units, got.confidence, got.mod_llr
     buf = io.StringIO(); cli.write_rows(buf, merged)
     lbuf = io.StringIO(); cli.write_rows(lbuf, mllr, header=cli.MODLLR_HEADER)
     assert buf.getvalue() == plain.getvalue() and lbuf.getvalue() == lone.getvalue()

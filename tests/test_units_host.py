@@ -83,7 +83,8 @@ def get_raw(qname):
 log = cli.Log("error")
 stats = {}
 mine = cli.run_count(iter(lines), loci, get_raw, FakeCounter(), log, 4, rank, world, stats=stats, units=True)
-merged, merged_units = cli.gather_rows(mine, stats["items"], sdist, units=True)       # still one gather: records + one blob per row
+got = cli.gather_rows(mine, stats["items"], sdist, units=True)       # still one gather: records + one blob per row
+merged, merged_units = got.rows, got.units
 import torch.distributed as dist
 if rank == 0:
     buf = io.StringIO(); cli.write_rows(buf, merged)
