@@ -324,6 +324,42 @@ int strq_scan_batch_reads(strq_ctx* ctx, int64_t n_reads, const void* const* rea
 int strq_scan_set(strq_ctx* ctx, int32_t n_cand, const int32_t* cand_target_id, double min_score);
 int strq_scan_clear(strq_ctx* ctx);
 int strq_batch_fetch_scan(strq_ctx* ctx, int32_t* out_cand, double* out_scores);
+/* ---- anchored counting: reads that end or start inside the repeat (no counterpart in the reference, whose gate, STRique.py:602,
+ * sends such a read to the flanked model between one flank and a position that means nothing) ----
+ * A read that could be conditioned (status 0, n > 0 samples) is, with m = min_score and the scores / positions of its row:
+ *   kind 1 spanning           score_prefix >= m, score_suffix >= m and prefix_begin < suffix_end
+ *   kind 2 ends in repeat     score_prefix >= m and score_suffix <  m      window [prefix_begin, n)
+ *   kind 3 starts in repeat   score_suffix >= m and score_prefix <  m      window [0, suffix_end)
+ *   kind 0 none               everything else (a NaN score; both flanks at m or above in the wrong order)
+ * (strique_amd/anchored.py states the same rule).  A read of kind 2 / 3 is decoded once more, on its window of the filtered signal,
+ * with the target's end / start model: the flanked model with the missing flank profile replaced by one free emitting state
+ * (strq_model_create; counted states and tag 1 on the repeat section as in the flanked model).  count = visits of the counted states
+ * + the model's bias; it is a lower bound on the allele up to the decode's own error, not a proven one.  free_samples, the
+ * observations the free state emitted, is the check on the classification: a handful on a read that really ends in the repeat,
+ * thousands on one that does not. */
+typedef struct strq_anchored {
+    int32_t kind;           /* 0 none, 1 spanning, 2 ends in repeat, 3 starts in repeat */
+    int32_t status;         /* kind 2 / 3: 0 decoded, 1 no path, 2 window of 2^21 samples or more (then the fields below are zero) */
+    int32_t count, pad_;
+    double log_p;
+    int64_t begin, end;     /* raw-signal samples [begin, end) the best path decodes into the repeat section */
+    int64_t free_samples;
+} strq_anchored;
+/* The two models of a target and their biases.  Both or none: a model id of -1 in both places takes them away. */
+int strq_target_set_anchored(strq_ctx* ctx, int32_t target_id, int32_t end_model_id, int32_t end_bias, int32_t start_model_id, int32_t start_bias);
+/* on = 1: later run calls classify every read and decode those of kind 2 / 3 behind the rows (which do not change, nor do the
+ * other optional outputs).  STRQ_ERR_ARG for min_score not above 0 (it has no default: the scores of a flank that is there and of
+ * one that is not overlap on noisy reads).  A run call with the switch on fails before any launch (STRQ_ERR_ARG) when a read's
+ * target has no anchored models, and when it is a scan.  Sub-batches still in flight keep the mode they were launched with (the
+ * call waits for them).  Default 0: no further kernel runs and no further buffer is reserved. */
+int strq_set_anchored(strq_ctx* ctx, int32_t on, double min_score);
+/* One record per read of the last batch (n = its reads).  STRQ_ERR_ARG when the last run call ran with the switch off. */
+int strq_batch_fetch_anchored(strq_ctx* ctx, strq_anchored* out, int64_t n);
+/* The anchored pass of the last run call: out[0] = ms on the GPU (all its sub-batches), out[1 .. 4] = reads of kind 0, 1, 2, 3,
+ * out[5] = kernels launched (classification, tasks, sorts and decodes; 0 with the switch off), out[6] / out[7] = of the decodes,
+ * windows that ran on the register-resident / on a lane-layout kernel shape.  After a run call that failed inside the pass the
+ * figures are those of the part that ran (the rows of the failed sub-batch are back at their initial values). */
+int strq_last_anchored(strq_ctx* ctx, double* out8);
 /* A host-side helper, not on the path of strq_detect_batch (which takes these on the GPU): the statistics of float64 reads
  * with numpy's arithmetic (no context, no device): out[6 * i ..] = median, MAD, c1, h1 of
  * medfilt(read i, 3) and c1, h1 of read i itself (0, 1 unless want_raw) -- what numpy's median / mean / percentile

@@ -21,6 +21,7 @@ from collections import defaultdict, deque, namedtuple
 
 import numpy as np
 
+from . import anchored as anchored_mod
 from . import scan as scan_mod
 from .counter import Detected
 
@@ -247,6 +248,12 @@ def count(argv):
                                                                                        "taken for a read.  Required with --scan: there is no default (README, 'Scan')")
     parser.add_argument("--scan-scores", default=None, metavar="FILE", help="--scan: also write score_prefix and score_suffix of every candidate to FILE, one row per read, "
                                                                             "with or without a winner (what a threshold for one's own data is chosen from)")
+    parser.add_argument("--anchored", default=None, metavar="FILE", help="Also count the reads that end or start inside the repeat, from their one flank, and write them to FILE: "
+                                                                           "one row per count row, columns " + " ".join(anchored_mod.HEADER) + " (kind: none, spanning, "
+                                                                           "ends_in_repeat, starts_in_repeat; the count is a lower bound up to the decode's own error; "
+                                                                           "free_samples in the thousands means the read was wrongly taken for anchored)")
+    parser.add_argument("--anchored-min-score", type=float, default=None, metavar="X", help="--anchored: a flank counts as found when its normalised score is at least X.  "
+                                                                                           "Required with --anchored: there is no default (README, 'Anchored counting')")
     parser.add_argument("--strict", action="store_true", help="Exit with status 2 when any read could not be processed (the reference only logs such reads and exits 0)")
     args = parser.parse_args(argv)
     if args.scan and args.confidence:
@@ -264,6 +271,14 @@ def count(argv):
                      "(a first run with a high X and --scan-scores FILE shows what to choose from)")
     if args.scan_min_score is not None and not args.scan_min_score > 0:
         parser.error("--scan-min-score must be above 0")
+    if args.anchored and args.scan:
+        parser.error("--anchored cannot be combined with --scan: a scan takes a read for a target when it finds both flanks")
+    if args.anchored and args.anchored_min_score is None:
+        parser.error("--anchored needs --anchored-min-score X: the scores of a flank that is there and of one that is not overlap on noisy reads, so there is no default")
+    if args.anchored_min_score is not None and not args.anchored:
+        parser.error("--anchored-min-score needs --anchored FILE")
+    if args.anchored_min_score is not None and not args.anchored_min_score > 0:
+        parser.error("--anchored-min-score must be above 0")
     log = Log(args.log_level)
     config = parse_config(args.repeat, args.config, log)
     for path, what in ((args.f5Index, "Fast5 index file"), (args.model, "Pore model file")):
@@ -321,7 +336,7 @@ def count(argv):
         readers = max(1, min(24, share))            # inflating is what the readers do: one per core they can get, 16 ... 24 measure the same end to end
     stats = {}
     fault = 0
-    paths = dict(units=args.units, confidence=args.confidence, mod_llr=args.mod_llr, scores=args.scan_scores)
+    paths = dict(units=args.units, confidence=args.confidence, mod_llr=args.mod_llr, scores=args.scan_scores, anchored=args.anchored)
     with contextlib.ExitStack() as stack:
         # rank 0 writes: as the batches are done in a single process (run_count), after the gather otherwise
         files = {name: stack.enter_context(open(path, 'w')) if (path and rank == 0) else None for name, path in paths.items()}
@@ -330,7 +345,8 @@ def count(argv):
         try:
             rows = run_count(stream, loci, f5.get_raw, counter, log, args.batch, rank, world, out if world == 1 else None, readers=readers, stats=stats,
                              units=bool(args.units), units_out=now['units'], scan=scan, scores_out=now['scores'],
-                             confidence=bool(args.confidence), conf_out=now['confidence'], mod_llr=bool(args.mod_llr), llr_out=now['mod_llr'])
+                             confidence=bool(args.confidence), conf_out=now['confidence'], mod_llr=bool(args.mod_llr), llr_out=now['mod_llr'],
+                             anchored=args.anchored_min_score, anchored_out=now['anchored'])
         except DeviceFault:
             if world == 1:
                 raise SystemExit(3)
@@ -344,7 +360,8 @@ def count(argv):
                     log("Main: a rank reported a device error; no output written.", 'error')
                 dist.destroy_process_group()
                 raise SystemExit(3)
-            merged = gather_rows(rows, stats["items"], sdist, units=bool(args.units), scan=scan, confidence=bool(args.confidence), mod_llr=bool(args.mod_llr))
+            merged = gather_rows(rows, stats["items"], sdist, units=bool(args.units), scan=scan, confidence=bool(args.confidence), mod_llr=bool(args.mod_llr),
+                                 anchored=bool(args.anchored))
             if rank == 0:
                 write_rows(out, merged.rows)
                 for o in OUTPUTS:
@@ -471,18 +488,33 @@ OUTPUTS = (
     Output('scores', lambda scan: scan_mod.scores_header(scan["candidates"]),
            lambda q, t, s, row, v: scan_mod.format_scores(q, None if row is None else (t, s), v),
            lambda v: _floats(x for pair in v for x in pair), lambda text: list(zip(*[iter(_unfloats(text))] * 2)), 'score_rows', True),
+    Output('anchored', lambda scan: anchored_mod.HEADER, lambda q, t, s, row, v: anchored_mod.format_row(q, t, s, v),
+           lambda v: _pack_anchored(v), lambda text: _unpack_anchored(text), 'anchored_rows', False),
 )
-Merged = namedtuple('Merged', ['rows'] + [o.name for o in OUTPUTS])
+# (`anchored`, the last field, defaults to None: callers that build a Merged from the five values before it keep working)
+Merged = namedtuple('Merged', ['rows'] + [o.name for o in OUTPUTS], defaults=(None,))
+
+
+def _pack_anchored(rec):
+    """The anchored record of a read (kind, status, count, log_p, begin, end, free_samples) as it travels between ranks."""
+    kind, status, count, log_p, begin, end, free = rec
+    return ','.join([str(int(kind)), str(int(status)), str(int(count)), repr(float(log_p)), str(int(begin)), str(int(end)), str(int(free))])
+
+
+def _unpack_anchored(text):
+    f = text.split(',')
+    return (int(f[0]), int(f[1]), int(f[2]), float(f[3]), int(f[4]), int(f[5]), int(f[6]))
 
 
 def outputs_on(**flags):
-    """The entries of OUTPUTS whose flag (units=, confidence=, mod_llr=, scores=) is set."""
+    """The entries of OUTPUTS whose flag (units=, confidence=, mod_llr=, scores=, anchored=) is set."""
     return [o for o in OUTPUTS if flags.get(o.name)]
 
 
 def as_detected(res, units=False, confidence=False, mod_llr=False):
-    """One result of counter.detect_batch(..., units, confidence, mod_llr) as a Detected record: a record as it is, else the legacy
-    shape detect_batch documents -- (row[, positions][, conf][, llr]), without any of the three the bare row."""
+    """One result of counter.detect_batch(..., units, confidence, mod_llr) as a Detected record: a record as it is (what run_count
+    asks for with anchored counting on: the anchored record of every read travels in it), else the legacy shape detect_batch
+    documents -- (row[, positions][, conf][, llr]), without any of the three the bare row."""
     if isinstance(res, Detected):
         return res
     if not (units or confidence or mod_llr):
@@ -495,7 +527,7 @@ def _read_values(target, strand, det, scores=None):
     """What the writers know of one read: (target, strand, row or None, {output name: value or None})."""
     if det is None:
         return target, strand, None, dict(scores=scores)
-    return target, strand, det.row, dict(units=det.units, confidence=det.conf, mod_llr=det.llr, scores=scores)
+    return target, strand, det.row, dict(units=det.units, confidence=det.conf, mod_llr=det.llr, scores=scores, anchored=det.anchored)
 
 
 def _emit(sink, on, seq, qname, target, strand, row, values):
@@ -529,13 +561,13 @@ def unpack_blob(on, blob):
     return fields[0], fields[1], fields[2], values
 
 
-def gather_rows(rows, items, sdist, units=False, scan=None, confidence=False, mod_llr=False):
+def gather_rows(rows, items, sdist, units=False, scan=None, confidence=False, mod_llr=False, anchored=False):
     """Reads of this rank (run_count with world > 1) -> fixed-size records + one blob per read (pack_blob) -> one gather -> on rank 0
-    the rows of every file in input order: Merged(rows, units, confidence, mod_llr, scores), [(sequence number, TSV row)] each, None
+    the rows of every file in input order: Merged(rows, units, confidence, mod_llr, scores, anchored), [(sequence number, TSV row)] each, None
     for an output that was not asked for (scores: asked for by scan) and for every field off rank 0.  `items`: every accepted (qname,
     strand, target) of the input, which each rank derives from the same SAM file (scan: from the same index).  A read that failed
     travels as a record with valid = 0 and writes nothing; a scan read without a winner as one with valid = 2: it writes a score row."""
-    on = outputs_on(units=units, confidence=confidence, mod_llr=mod_llr, scores=bool(scan))
+    on = outputs_on(units=units, confidence=confidence, mod_llr=mod_llr, scores=bool(scan), anchored=anchored)
     rec = np.zeros(len(rows), ROW_DTYPE); blobs = []; idx = np.zeros(len(rows), np.int64)
     for k, (seq, read) in enumerate(rows):
         idx[k] = seq
@@ -591,7 +623,7 @@ def route(stream, loci, log):
 
 
 def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, out=None, readers=0, stats=None, units=False, units_out=None,
-              scan=None, scores_out=None, confidence=False, conf_out=None, mod_llr=False, llr_out=None):
+              scan=None, scores_out=None, confidence=False, conf_out=None, mod_llr=False, llr_out=None, anchored=None, anchored_out=None):
     """Route the SAM records of `stream` to their targets, run this rank's share through
     `counter.detect_batch` and return [(sequence number, TSV row or -- several ranks -- what gather_rows takes)].
 
@@ -607,6 +639,9 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
     of OUTPUTS -- the counter is asked for them (counter.detect_batch(..., units=True) and so on), and every result is normalised to a
     Detected record (as_detected); single process: their rows (format_units, format_confidence, format_mod_llr) go to `units_out`,
     `conf_out`, `llr_out` with the count rows and to stats["unit_rows"], stats["conf_rows"], stats["llr_rows"].
+    `anchored` (a score threshold, not with scan): the counter is asked for Detected records with the anchored record of every read
+    (counter.detect_batch(..., anchored=threshold, records=True)); their rows (strique_amd.anchored.format_row) go to `anchored_out`
+    and to stats["anchored_rows"].  The count rows and the other files do not change.
     `scan` ({"min_score", "candidates", "scores"}): `stream` is a list of read ids instead of a SAM stream; every read goes through
     counter.scan_batch and takes target and strand from its winner -- a read without one writes no row, as a read without a target
     writes none; single process: the score rows (strique_amd.scan.format_scores, every read) go to `scores_out` and to
@@ -616,15 +651,19 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
     if stats is None:
         stats = {}
     stats.setdefault("failed", 0)
-    files = dict(rows=out, units=units_out, confidence=conf_out, mod_llr=llr_out, scores=scores_out)
-    on = outputs_on(units=units, confidence=confidence, mod_llr=mod_llr, scores=scan and scan["scores"])
+    if anchored is not None and scan:
+        raise ValueError("anchored counting cannot be combined with a scan")
+    files = dict(rows=out, units=units_out, confidence=conf_out, mod_llr=llr_out, scores=scores_out, anchored=anchored_out)
+    on = outputs_on(units=units, confidence=confidence, mod_llr=mod_llr, scores=scan and scan["scores"], anchored=anchored is not None)
     if out is not None:
         print('\t'.join(HEADER), file=out)
     for o in OUTPUTS:
         stats.setdefault(o.stat, [])
         if files[o.name] is not None:
             print('\t'.join(o.header(scan)), file=files[o.name])
-    extras = {o.name: True for o in on if o.name != 'scores'}
+    extras = {o.name: True for o in on if o.name not in ('scores', 'anchored')}
+    if anchored is not None:
+        extras.update(anchored=anchored, records=True)
     rows = []
     records = ((rid, '.', ['.'], 0) for rid in stream) if scan else route(stream, loci, log)
     mine_set = None

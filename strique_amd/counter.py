@@ -14,6 +14,7 @@ from collections import namedtuple
 
 import numpy as np
 
+from . import anchored as anchored_mod
 from . import ffi
 from . import hmm as hmm_mod
 from .pore_model import pore_model
@@ -32,8 +33,9 @@ target_classifier = namedtuple('target_classifier',
                                ['prefix', 'suffix', 'prefix_ext', 'suffix_ext', 'repeatHMM', 'modHMM', 'target_id'])
 
 # one read out of the device pipeline: the tuple detect() returns, and what was asked for beside it (None otherwise) -- unit positions,
-# (log_lik, count_mean, count_sd), per-unit log-likelihood ratios; see repeatCounter.detect_batch
-Detected = namedtuple('Detected', ['row', 'units', 'conf', 'llr'])
+# (log_lik, count_mean, count_sd), per-unit log-likelihood ratios, the anchored record (kind, status, count, log_p, begin, end,
+# free_samples -- every kind, as strq_batch_fetch_anchored hands it out); see repeatCounter.detect_batch
+Detected = namedtuple('Detected', ['row', 'units', 'conf', 'llr', 'anchored'], defaults=(None,))
 
 
 class repeatCounter(object):
@@ -53,6 +55,10 @@ class repeatCounter(object):
         self.samples = cfg['samples']
         self.HMM_config = HMM_config
         self.targets = {}
+        # anchored counting: what the two extra models of a classifier are baked from, and the classifiers that have them
+        # registered ({target_id: {kind: {'model_id', 'bias', 'states', 'positions_rc', 'positions_error'}}}); nothing is baked before somebody asks
+        self._anchored_src = {}
+        self.anchored_models = {}
 
     # -------------------------------------------------------------------------------------
     def _classifier(self, repeat, prefix, suffix, prefix_ext, suffix_ext):
@@ -68,7 +74,25 @@ class repeatCounter(object):
         if mod is not None:
             mod.model_id = self.ctx.model_create(mod.baked)
             self.ctx.target_set_mod(tid, mod.model_id, mod.model_min, mod.model_max)
+        self._anchored_src[tid] = (repeat, prefix, suffix)
         return target_classifier(p, s, pe, se, flanked, mod, tid)
+
+    def _ensure_anchored(self):
+        """The end / start model of every classifier that has none yet: baked, uploaded and registered with its target."""
+        for tid, (repeat, prefix, suffix) in self._anchored_src.items():
+            if tid in self.anchored_models:
+                continue
+            made = {}
+            for kind in hmm_mod.ANCHORED_KINDS:
+                m = hmm_mod.AnchoredRepeatModel(kind, repeat, prefix, suffix, self.pm, self.HMM_config)
+                mid = self.ctx.model_create(m.baked)
+                # which kernel the model runs on is reported, not assumed: 0 = the chain builder took its positions (register-resident
+                # kernel), 3 = it refused them (lane layout, or the general kernel); tools/anchored_probe.py prints its reason
+                made[kind] = {'model_id': mid, 'bias': m.count_bias, 'states': m.baked.n_states, 'positions_rc': self.ctx.last_positions_rc,
+                              'positions_error': self.ctx.last_positions_error}
+            e, s = made['ends_in_repeat'], made['starts_in_repeat']
+            self.ctx.target_set_anchored(tid, e['model_id'], e['bias'], s['model_id'], s['bias'])
+            self.anchored_models[tid] = made
 
     def add_target(self, target_name, repeat, prefix, suffix):
         if target_name in self.targets:
@@ -92,7 +116,7 @@ class repeatCounter(object):
         raise ValueError("RepeatCounter: Strand must be + or -.")
 
     # -------------------------------------------------------------------------------------
-    def detect_batch(self, items, units=False, confidence=False, mod_llr=False):
+    def detect_batch(self, items, units=False, confidence=False, mod_llr=False, anchored=None, records=False):
         """items: iterable of (target_name, raw_signal, strand).  Returns a list of the tuples
         detect() returns, in input order.  units=True: a list of (tuple, positions) instead, positions being the
         raw-signal sample indices of the repeat units on the decoded Viterbi path (one np.int64 array per read, ascending;
@@ -104,21 +128,41 @@ class repeatCounter(object):
         mod_llr=True (a counter with a modification model): the per-unit log-likelihood ratio of the mCpG calls comes last -- a
         float64 array V_mod - V_base with one value per character of mod_pattern (>= 0 where it says '1', <= 0 where it says '0',
         +-inf where one branch has no path), or None for a read without units (strq_set_mod_llr).
-        Order of the elements: (tuple[, positions][, conf][, llr]); without any of the three the bare tuple."""
+        anchored=m (a score threshold above 0; there is no default): one more element after them, for a read that holds one flank
+        only -- it ends inside the repeat, or starts there (strique_amd.anchored.classify states the rule, with m the threshold on the
+        two normalised flank scores) -- (kind, count, log_p, begin, end, free_samples): kind 'ends_in_repeat' or 'starts_in_repeat',
+        the count of the repeat units the read holds (a lower bound on the allele up to the decode's own error, not a proven one),
+        the raw-signal samples [begin, end) decoded into the repeat, and the observations the free state took (a handful on a read
+        that really ends in the repeat, thousands on one wrongly taken for anchored).  A read whose decode found no path has zeros
+        behind its kind; None for every other read (spanning, or neither).  The tuple itself does not change.
+        Order of the elements: (tuple[, positions][, conf][, llr][, anchored]); without any of the four the bare tuple.
+        records=True: a list of Detected records instead (the fields that were not asked for None; `anchored` the record of every
+        read, whatever its kind: (kind number, status, count, log_p, begin, end, free_samples))."""
         items = list(items)
         if mod_llr and self.pm is self.pm_mod:
             raise ValueError("RepeatCounter: mod_llr needs a modification model.")
+        if anchored is not None and not anchored > 0:
+            raise ValueError("RepeatCounter: the anchored score threshold must be above 0.")
         reads = [(self._classifier_for(t, s).target_id, r) for t, r, s in items]
         out = [None] * len(items)
-        for i, d, _, _ in self._run(reads, units=units, confidence=confidence, mod_llr=mod_llr):
+        for i, d, _, _ in self._run(reads, units=units, confidence=confidence, mod_llr=mod_llr, anchored=anchored):
+            if records:
+                out[i] = d
+                continue
             extra = ((d.units,) if units else ()) + ((d.conf,) if confidence else ()) + ((d.llr,) if mod_llr else ())
+            if anchored is not None:
+                a = d.anchored
+                extra += ((anchored_mod.KIND_NAMES[a[0]],) + tuple(a[2:]) if a[0] in (anchored_mod.ENDS_IN_REPEAT, anchored_mod.STARTS_IN_REPEAT) else None,)
             out[i] = (d.row,) + extra if extra else d.row
         return out
 
     @contextlib.contextmanager
-    def _switches(self, units, confidence, mod_llr):
+    def _switches(self, units, confidence, mod_llr, anchored=None):
         """The optional passes that were asked for are on inside the block, and all of them off after it."""
         try:
+            if anchored is not None:
+                self._ensure_anchored()
+                self.ctx.set_anchored(True, anchored)
             # inside the try: set_mod_llr refuses a modification model the scoring pass does not cover, and the switches a
             # failed call leaves behind must not stay on for the next caller of a shared context
             if units:
@@ -129,11 +173,12 @@ class repeatCounter(object):
                 self.ctx.set_mod_llr(True)
             yield
         finally:
+            self.ctx.set_anchored(False)
             self.ctx.set_mod_llr(False)
             self.ctx.set_units(False)
             self.ctx.set_confidence(False)
 
-    def _run(self, reads, units=False, confidence=False, mod_llr=False, scan=None):
+    def _run(self, reads, units=False, confidence=False, mod_llr=False, scan=None, anchored=None):
         """reads: [(target_id, raw_signal)] through the context.  Yields (position in `reads`, Detected, winner, scores) per read, the
         fields of Detected that were not asked for being None.  scan=(candidate target ids, min_score): the target ids of the reads
         are ignored, every read is compared with every candidate (Context.scan_batch_reads); winner is its position in the candidate
@@ -147,7 +192,7 @@ class repeatCounter(object):
             if not idx:
                 continue
             arrs = [sigs[i].astype(np.int16 if want_int else np.float64, copy=False) for i in idx]
-            with self._switches(units, confidence, mod_llr):
+            with self._switches(units, confidence, mod_llr, anchored):
                 if scan is None:
                     res = self.ctx.detect_batch_reads(arrs, [reads[i][0] for i in idx])      # one pointer per read: no host-side concatenation
                     win = sc = [None] * len(res)
@@ -157,10 +202,14 @@ class repeatCounter(object):
                 pos = self.ctx.batch_fetch_units() if units else [None] * len(res)
                 conf = self.ctx.batch_fetch_confidence() if confidence else [None] * len(res)
                 vs = self.ctx.batch_fetch_mod_llr() if mod_llr else [None] * len(res)
-            for i, r, m, u, cf, v, w, s in zip(idx, res, mods, pos, conf, vs, win, sc):
+                an = [None] * len(res)
+                if anchored is not None:
+                    an = [(int(a['kind']), int(a['status']), int(a['count']), float(a['log_p']), int(a['begin']), int(a['end']), int(a['free_samples']))
+                          for a in self.ctx.batch_fetch_anchored()]
+            for i, r, m, u, cf, v, w, s, a in zip(idx, res, mods, pos, conf, vs, win, sc, an):
                 n = int(r['count']); p = float(r['log_p']) if n or r['log_p'] != 0 else 0
                 row = (n, float(r['score_prefix']), float(r['score_suffix']), p, int(r['offset']), int(r['ticks']), m)
-                yield i, Detected(row, u, cf, None if v is None else v[:, 1] - v[:, 0]), w, s
+                yield i, Detected(row, u, cf, None if v is None else v[:, 1] - v[:, 0], a), w, s
 
     def candidates(self, targets=None):
         """[(target_name, strand)] of a scan: every target added (or the named ones), in add_target order, '+' before '-'."""
@@ -206,8 +255,11 @@ class repeatCounter(object):
             return True
         return s.size == 0 or (int(s.min()) >= -32768 and int(s.max()) <= 32767)
 
-    def detect(self, target_name, raw_signal, strand, units=False, confidence=False, mod_llr=False):
+    def detect(self, target_name, raw_signal, strand, units=False, confidence=False, mod_llr=False, anchored=None, records=False):
         """(n, score_prefix, score_suffix, log_p, offset, ticks, mod_pattern) -- STRique.py:581-618.  units=True:
         (that tuple, unit positions or None); confidence=True: (that tuple, [positions,] (log_lik, count_mean, count_sd) or
-        None); mod_llr=True: the per-unit log-likelihood ratios (or None) after them -- see detect_batch."""
-        return self.detect_batch([(target_name, raw_signal, strand)], units=units, confidence=confidence, mod_llr=mod_llr)[0]
+        None); mod_llr=True: the per-unit log-likelihood ratios (or None) after them; anchored=m: (kind, count, log_p, begin, end,
+        free_samples) of a read that holds one flank only (or None) last; records=True: a Detected record instead -- see
+        detect_batch."""
+        return self.detect_batch([(target_name, raw_signal, strand)], units=units, confidence=confidence, mod_llr=mod_llr, anchored=anchored,
+                                 records=records)[0]

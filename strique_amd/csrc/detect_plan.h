@@ -15,7 +15,8 @@ namespace strq {
 // The optional passes behind the count decode: unit positions (strq_set_units), forward pass (strq_set_confidence), per-unit scores
 // (strq_set_mod_llr).  DetectState holds what the next run call uses, a slot what its sub-batch was launched with, Batch what the last
 // run call ran with.
-struct Extras { bool units = false, conf = false, llr = false; };
+// Anchored counting (strq_set_anchored) is the fourth: it comes with its score threshold.
+struct Extras { bool units = false, conf = false, llr = false, anch = false; double anch_min = 0.0; };
 
 // What a batch holds per read: the row, the modification pattern and the outputs of the optional passes.  One place sizes them, one
 // function puts a read back to its initial values -- a row that was never computed is never handed out.
@@ -27,6 +28,7 @@ struct ReadRows {
     std::vector<double> conf;                     // log_lik, count_mean, count_sd (strq_batch_fetch_confidence); NaN while not decoded
     std::vector<uint8_t> conf_dec;
     std::vector<std::vector<double>> llr;         // (V_base, V_mod) per repeat unit (strq_batch_fetch_mod_llr); empty: none
+    std::vector<strq_anchored> anch;              // kind and decode of a read that holds one flank (strq_batch_fetch_anchored); zeros: kind 0
     void size_reads(int64_t n)
     {
         const size_t m = (size_t)n;
@@ -34,6 +36,7 @@ struct ReadRows {
         units.assign(m, std::vector<int64_t>()); unit_dec.assign(m, 0);
         conf.assign(3 * m, NAN); conf_dec.assign(m, 0);
         llr.assign(m, std::vector<double>());
+        anch.assign(m, strq_anchored());
     }
     void clear_read(int64_t read)
     {
@@ -43,8 +46,27 @@ struct ReadRows {
         units[r].clear(); unit_dec[r] = 0;
         conf[3 * r] = conf[3 * r + 1] = conf[3 * r + 2] = NAN; conf_dec[r] = 0;
         llr[r].clear();
+        anch[r] = strq_anchored();
     }
 };
+
+// The record of a read of kind 2 (ends in the repeat) or 3 (starts in it) from the MARK decode of its window: `first` observations
+// into the read, T observations, `enter` / `leave` the 1-based observation of the first emission inside the repeat section and of the
+// first one behind it (0: none), as VitResult::dbg[0 .. 1] report them.  The free state of kind 2 emits behind the section, that of kind 3
+// in front of it.  A decode without a path, or one whose marks do not describe such a path, keeps the kind with zeros.
+inline strq_anchored anchored_record(int32_t kind, int64_t first, int64_t T, int32_t vit_status, int64_t visits, int32_t bias, double logp,
+                                     int64_t enter, int64_t leave)
+{
+    strq_anchored a = strq_anchored();
+    a.kind = kind; a.status = vit_status ? (vit_status == 2 ? 2 : 1) : 0;
+    if (a.status) return a;
+    if (leave == 0) leave = T + 1;          // the section reaches the end of the window
+    if (enter < 1 || leave <= enter || leave > T + 1) { a.status = 1; return a; }
+    a.count = (int32_t)(visits + bias); a.log_p = logp;
+    a.begin = first + enter - 1; a.end = first + leave - 1;
+    a.free_samples = kind == 2 ? T - (leave - 1) : enter - 1;
+    return a;
+}
 
 struct VitGroup { int shape, first, count, max_cells, route; };      // one Viterbi launch: kernel shape, task range, largest n_cells of its models; its route (unit pass)
 

@@ -61,18 +61,24 @@ static __device__ inline int geometry_gate(const ReadGeom& g)
     return (g.prefix_begin < g.suffix_end && g.score_prefix > 0.0 && g.score_suffix > 0.0) ? 1 : 0;
 }
 
-// the Viterbi task of a read: the window [prefix_begin, suffix_end) of its filtered signal when the gate passed, else an empty one
-static __device__ inline VitTask window_task(const ReadGeom& g, const ReadCond& rc, const VitModel* model, const void* flt, int is_f64, const PoreStats& ps)
+// the Viterbi task of a window [begin, end) of a read's filtered signal (an empty task when `open` is 0)
+static __device__ inline VitTask window_task(int open, int64_t begin, int64_t end, const ReadCond& rc, const VitModel* model, const void* flt, int is_f64, const PoreStats& ps)
 {
     VitTask vt = {};
     vt.model = model;
-    if (g.gate) {
-        vt.T = g.suffix_end - g.prefix_begin;
-        if (is_f64) { vt.sig = reinterpret_cast<const double*>(flt) + rc.off + g.prefix_begin; vt.src_kind = VIT_SRC_F64_AFFINE; }
-        else { vt.sig = reinterpret_cast<const int16_t*>(flt) + rc.off + g.prefix_begin; vt.src_kind = VIT_SRC_I16_AFFINE; }
+    if (open) {
+        vt.T = end - begin;
+        if (is_f64) { vt.sig = reinterpret_cast<const double*>(flt) + rc.off + begin; vt.src_kind = VIT_SRC_F64_AFFINE; }
+        else { vt.sig = reinterpret_cast<const int16_t*>(flt) + rc.off + begin; vt.src_kind = VIT_SRC_I16_AFFINE; }
         vt.c1 = rc.f_c1; vt.h1 = rc.f_h1; vt.h2 = rc.h2; vt.c2 = rc.c2; vt.lo = ps.clip_lo; vt.hi = ps.clip_hi;
     }
     return vt;
+}
+
+// the Viterbi task of a read: the window [prefix_begin, suffix_end) of its filtered signal when the gate passed, else an empty one
+static __device__ inline VitTask window_task(const ReadGeom& g, const ReadCond& rc, const VitModel* model, const void* flt, int is_f64, const PoreStats& ps)
+{
+    return window_task(g.gate, g.prefix_begin, g.suffix_end, rc, model, flt, is_f64, ps);
 }
 #endif
 

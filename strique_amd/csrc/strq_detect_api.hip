@@ -23,6 +23,7 @@
 #include "unit_kernels.h"
 #include "forward_kernels.h"
 #include "scan_kernels.h"
+#include "anchored_kernels.h"
 
 using namespace strq;
 
@@ -69,6 +70,7 @@ struct Target {
     int kp = 0, Rp = 0, NSp = 1, ks = 0, Rs = 0, NSs = 1;
     int model_id = -1, count_bias = 0;
     int mod_model_id = -1; double mod_min = 0, mod_max = 0;
+    int end_model_id = -1, end_bias = 0, start_model_id = -1, start_bias = 0;      // strq_target_set_anchored: both models or none
 };
 
 struct Batch : ReadRows {
@@ -113,6 +115,8 @@ struct DetectState {
     float llr_ms = 0; double llr_units = 0, llr_reads = 0, llr_launches = 0;      // strq_last_mod_llr: the last run call's scoring pass
     DevBuf conf_task;                    // forward pass (run_conf_pass): tasks, model images, c0, results, order
     float conf_ms = 0; double conf_windows = 0, conf_nopath = 0, conf_expo = 0;      // strq_last_confidence: the last run call's forward pass
+    DevBuf anch_ws, anch_task;           // anchored pass (run_anchored_pass): geometry, conditioning rows and kinds of a sub-batch; tasks, results, their reads and models
+    float anch_ms = 0; double anch_kinds[4] = {}, anch_launches = 0, anch_g2 = 0, anch_lane = 0;      // strq_last_anchored: the last run call's anchored pass
     // strq_scan_set: run calls compare these candidates (target ids) on every read instead of taking the read's own target
     bool scan_on = false; std::vector<int32_t> scan_cand; double scan_min = 0;
     DevBuf scan_idx, scan_out;           // scan: task table and candidate trims / winners, scores and raw scores of a sub-batch
@@ -138,6 +142,7 @@ struct DetectState {
         Extras ex;                       // the switches when the sub-batch was launched: the unit pass, the forward pass, the per-unit scores (behind the modification pass) follow
         bool scan = false;               // a scan sub-batch: a read without a winner has no row
         int64_t r0 = 0; int nr = 0;
+        const char* flt_base = nullptr;  // where the filtered signal of the sub-batch starts in `flt` (ReadCond::off counts from here)
         std::vector<int32_t> vit_slot;
         void* pinned = nullptr; size_t pinned_cap = 0;
         hipEvent_t fwd_done = nullptr, v0 = nullptr, v1 = nullptr;
@@ -201,7 +206,7 @@ void detect_state_free(strq_ctx* c)
     if (d->vit_stream) (void)hipStreamSynchronize(d->vit_stream);
     for (DevBuf* b : {&d->batch.raw, &d->rc, &d->hist16, &d->hist8, &d->geom, &d->idx,
                       &d->hist_raw, &d->bp, &d->path, &d->modtask, &d->modsig, &d->modlen, &d->pattern, &d->hrange, &d->modpool, &d->f64s,
-                      &d->unit_task, &d->unit_ws, &d->unit_path, &d->unit_pool, &d->conf_task, &d->llr_ws, &d->scan_idx, &d->scan_out}) b->release();
+                      &d->unit_task, &d->unit_ws, &d->unit_path, &d->unit_pool, &d->conf_task, &d->llr_ws, &d->scan_idx, &d->scan_out, &d->anch_ws, &d->anch_task}) b->release();
     if (d->scan_pin) (void)hipHostFree(d->scan_pin);
     for (auto& sl : d->slot) {
         for (DevBuf* b : {&sl.flt, &sl.vit, &sl.vres, &sl.order, &sl.vq}) b->release();
@@ -688,6 +693,102 @@ static int run_conf_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, con
     return STRQ_OK;
 }
 
+// Anchored counting of the reads of one sub-batch (strq_set_anchored): the reads that hold one flank only are decoded once more, from
+// their flank to their end (or from their start to their flank), with the target's end / start model.  Runs on the context's stream
+// when the rows of the sub-batch are taken, like the unit pass: the geometry and the conditioning rows go back up from the slot's
+// pinned block (the device copies belong to the sub-batch that followed), anchored_classify_kernel applies the rule, the host groups
+// the reads of kind 2 / 3 by kernel shape, anchored_task_kernel writes their tasks on the slot's filtered signal, and the Viterbi
+// kernels decode them in MARK mode: visits, log_p and the bounds of the repeat section in one decode.
+static int run_anchored_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
+{
+    Batch& B = d->batch;
+    hipStream_t st = c->stream;
+    const int64_t r0 = sl.r0; const int nr = sl.nr;
+    if (nr <= 0) return STRQ_OK;
+    const DetectState::Slot::Pinned h = sl.host();
+    if (const int rc = pass_start(c, d)) return rc;
+    const size_t o_rc = ((size_t)nr * sizeof(ReadGeom) + 15) & ~(size_t)15, o_cls = o_rc + (((size_t)nr * sizeof(ReadCond) + 15) & ~(size_t)15);
+    STRQ_HIP(c, d->anch_ws.reserve(o_cls + (size_t)nr * sizeof(AnchoredClass) + 64));
+    ReadGeom* d_geom = d->anch_ws.as<ReadGeom>(); ReadCond* d_rc = reinterpret_cast<ReadCond*>(d->anch_ws.as<char>() + o_rc);
+    AnchoredClass* d_cls = reinterpret_cast<AnchoredClass*>(d->anch_ws.as<char>() + o_cls);
+    STRQ_HIP(c, hipMemcpyAsync(d_geom, h.geom, (size_t)nr * sizeof(ReadGeom), hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, hipMemcpyAsync(d_rc, h.rc, (size_t)nr * sizeof(ReadCond), hipMemcpyHostToDevice, st));
+    AnchoredClassifyArgs ca;
+    ca.geom = d_geom; ca.rc = d_rc; ca.min_score = sl.ex.anch_min; ca.out = d_cls; ca.n_reads = nr;
+    if (launch_anchored_classify(st, ca)) { c->err = "anchored: classify launch failed"; return STRQ_ERR_DEVICE; }
+    std::vector<AnchoredClass> cls((size_t)nr);
+    STRQ_HIP(c, hipMemcpyAsync(cls.data(), d_cls, (size_t)nr * sizeof(AnchoredClass), hipMemcpyDeviceToHost, st));
+    STRQ_HIP(c, hipStreamSynchronize(st));
+    d->anch_launches += 1;
+    std::vector<int> who;
+    for (int i = 0; i < nr; ++i) {
+        const AnchoredClass& k = cls[(size_t)i];
+        if (k.kind < ANCH_NONE || k.kind > ANCH_STARTS) { c->err = "anchored: kind outside the rule"; return STRQ_ERR_DEVICE; }
+        d->anch_kinds[k.kind] += 1;
+        B.anch[(size_t)(r0 + i)].kind = k.kind;
+        if (k.kind != ANCH_ENDS && k.kind != ANCH_STARTS) continue;
+        // the window once more on the host, against the read as the conditioning saw it
+        if (k.begin < 0 || k.begin >= k.end || k.end > (int64_t)h.rc[i].n) { c->err = "anchored: window outside its read"; return STRQ_ERR_DEVICE; }
+        who.push_back(i);
+    }
+    const int m = (int)who.size();
+    if (!m) return pass_stop(c, d, d->anch_ms);
+    auto model_of = [&](int i) -> HostModel* {
+        const Target& t = d->targets[B.target[r0 + i]];
+        return c->models[cls[(size_t)i].kind == ANCH_ENDS ? t.end_model_id : t.start_model_id];
+    };
+    std::vector<GroupItem> items((size_t)m);
+    for (int k = 0; k < m; ++k) {
+        const Target& t = d->targets[B.target[r0 + who[(size_t)k]]];
+        // (run_range refused the call before any launch when a target of the range had none)
+        if (t.end_model_id < 0 || t.start_model_id < 0) { c->err = "anchored: target without anchored models (strq_target_set_anchored)"; return STRQ_ERR_ARG; }
+        HostModel* hm = model_of(who[(size_t)k]);
+        const int shape = vit_shape_for(hm->h, 2);
+        if (shape < 0) { c->err = "anchored: model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
+        items[(size_t)k] = {0, shape, hm->h.n_cells};
+    }
+    const Grouping G = group_items(items);
+    const size_t o_vr = (size_t)m * sizeof(VitTask), o_md = o_vr + (size_t)m * sizeof(VitResult), o_rd = o_md + (size_t)m * 8;
+    STRQ_HIP(c, d->anch_task.reserve(o_rd + (size_t)m * 4 + 64));
+    VitTask* d_vt = d->anch_task.as<VitTask>(); VitResult* d_vr = reinterpret_cast<VitResult*>(d->anch_task.as<char>() + o_vr);
+    const VitModel** d_md = reinterpret_cast<const VitModel**>(d->anch_task.as<char>() + o_md);
+    int32_t* d_rd = reinterpret_cast<int32_t*>(d->anch_task.as<char>() + o_rd);
+    std::vector<int32_t> read_of((size_t)m); std::vector<const VitModel*> mv((size_t)m);
+    for (int at = 0; at < m; ++at) {
+        const int i = who[(size_t)G.order[(size_t)at]];
+        read_of[(size_t)at] = i; mv[(size_t)at] = model_of(i)->dev;
+    }
+    STRQ_HIP(c, hipMemcpyAsync(d_rd, read_of.data(), (size_t)m * 4, hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, hipMemcpyAsync(d_md, mv.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
+    AnchoredTaskArgs ta;
+    ta.cls = d_cls; ta.rc = d_rc; ta.read = d_rd; ta.model = d_md; ta.flt = sl.flt_base; ta.is_f64 = B.dtype; ta.ps = d->ps;
+    ta.vit = d_vt; ta.n_tasks = m; ta.n_reads = nr;
+    if (launch_anchored_tasks(st, ta)) { c->err = "anchored: task launch failed"; return STRQ_ERR_DEVICE; }
+    d->anch_launches += 1;
+    STRQ_HIP(c, c->queue.reserve(1024));
+    STRQ_HIP(c, hipMemsetAsync(c->queue.p, 0, 1024, st));
+    int qi = 0;
+    for (const VitGroup& g : G.groups) {
+        if (const int src = sort_viterbi_group(c, st, g, d_vt, sl.order.as<int>())) return src;
+        if (const int lrc = launch_viterbi_group(c, st, g, d_vt, d_vr, sl.order.as<int>(), c->queue.as<int>() + qi++, 2, 0, "anchored: ")) return lrc;
+        d->anch_launches += group_order(sl.order.as<int>(), g) ? 2 : 1;
+        const int base = g.shape & ~VIT_SHAPE_SS;
+        if (base == VIT_SHAPE_G2) d->anch_g2 += g.count; else if (base != VIT_SHAPE_CSR) d->anch_lane += g.count;
+    }
+    std::vector<VitResult> vr((size_t)m);
+    STRQ_HIP(c, hipMemcpyAsync(vr.data(), d_vr, (size_t)m * sizeof(VitResult), hipMemcpyDeviceToHost, st));
+    if (const int rc = pass_stop(c, d, d->anch_ms)) return rc;
+    for (int at = 0; at < m; ++at) {
+        const int i = read_of[(size_t)at];
+        const AnchoredClass& k = cls[(size_t)i];
+        const Target& t = d->targets[B.target[r0 + i]];
+        const VitResult& v = vr[(size_t)at];
+        B.anch[(size_t)(r0 + i)] = anchored_record(k.kind, k.begin, k.end - k.begin, v.status, v.counted, k.kind == ANCH_ENDS ? t.end_bias : t.start_bias,
+                                                   v.logp, (int64_t)v.dbg[0], (int64_t)v.dbg[1]);
+    }
+    return STRQ_OK;
+}
+
 // bytes [pos, pos + len) of the batch (reads back to back) from the caller's memory: one buffer, or one per read
 static void host_bytes(const Batch& B, size_t esz, char* dst, size_t pos, size_t len)
 {
@@ -873,12 +974,15 @@ static int take_rows(strq_ctx* c, DetectState* d, DetectState::Slot& sl, bool un
     publish_timing(c, B);
     // the mode the launches ran with decides, not what the targets say by now
     if (sl.vit_mode == 2) { const int mrc = run_mod_pass(c, d, sl); if (mrc) return mrc; }
-    if (!sl.ex.units && !sl.ex.conf) return STRQ_OK;
-    Decoded dec;
-    if (const int drc = read_decoded(c, sl, dec)) return drc;
-    if (dec.who.empty()) return STRQ_OK;
-    if (sl.ex.units) { const int urc = run_unit_pass(c, d, sl, dec); if (urc) return urc; }
-    return sl.ex.conf ? run_conf_pass(c, d, sl, dec) : STRQ_OK;
+    if (sl.ex.units || sl.ex.conf) {
+        Decoded dec;
+        if (const int drc = read_decoded(c, sl, dec)) return drc;
+        if (!dec.who.empty()) {
+            if (sl.ex.units) { const int urc = run_unit_pass(c, d, sl, dec); if (urc) return urc; }
+            if (sl.ex.conf) { const int crc = run_conf_pass(c, d, sl, dec); if (crc) return crc; }
+        }
+    }
+    return sl.ex.anch ? run_anchored_pass(c, d, sl) : STRQ_OK;
 }
 
 // Results of a sub-batch in flight: queues its Viterbi launches if nobody came after it, waits for them, fills Batch::results (and runs
@@ -1222,6 +1326,7 @@ static int publish_forward(strq_ctx* c, DetectState* d, const SubBatch& S)
     sl.vit_mode = S.any_mod ? 2 : 0;
     sl.ex = d->extras;
     sl.scan = S.nc > 0;
+    sl.flt_base = S.flt_base;
     sl.state = DetectState::Slot::Forward;
     return STRQ_OK;
 }
@@ -1444,7 +1549,16 @@ int run_range(strq_ctx* c, DetectState* d, int64_t first, int64_t last)
         if (!B.target_given.empty()) { B.target = B.target_given; B.target_given.clear(); }
         B.scan_ncand = 0; B.cand.clear(); B.scores.clear();
     }
+    if (d->extras.anch) {
+        // nothing is launched for a call the anchored pass could not finish
+        if (d->scan_on) { c->err = "anchored: not available in a scan (strq_scan_set)"; return STRQ_ERR_ARG; }
+        for (int64_t r = first; r < last; ++r) {
+            const Target& t = d->targets[B.target_given.empty() ? B.target[(size_t)r] : B.target_given[(size_t)r]];
+            if (t.end_model_id < 0 || t.start_model_id < 0) { c->err = "anchored: target without anchored models (strq_target_set_anchored)"; return STRQ_ERR_ARG; }
+        }
+    }
     B.ran = d->extras;
+    d->anch_ms = 0; std::fill(d->anch_kinds, d->anch_kinds + 4, 0.0); d->anch_launches = d->anch_g2 = d->anch_lane = 0;
     d->unit_ms = 0; d->unit_bytes = d->unit_reads = d->unit_positions = 0;
     d->conf_ms = 0; d->conf_windows = d->conf_nopath = d->conf_expo = 0;
     d->llr_ms = 0; d->llr_units = d->llr_reads = d->llr_launches = 0;
@@ -1683,6 +1797,59 @@ int strq_last_mod_llr(strq_ctx* c, double* out4)
     if (!out4) { c->err = "bad argument"; return STRQ_ERR_ARG; }
     DetectState* d = dstate(c);
     out4[0] = d->llr_ms; out4[1] = d->llr_units; out4[2] = d->llr_reads; out4[3] = d->llr_launches;
+    return STRQ_OK;
+}
+
+int strq_target_set_anchored(strq_ctx* c, int32_t target_id, int32_t end_model_id, int32_t end_bias, int32_t start_model_id, int32_t start_bias)
+{
+    STRQ_ENTER(c);
+    DetectState* d = dstate(c);
+    const int32_t nm = (int32_t)c->models.size();
+    const bool none = end_model_id == -1 && start_model_id == -1;
+    if (target_id < 0 || target_id >= (int32_t)d->targets.size() ||
+        (!none && (end_model_id < 0 || end_model_id >= nm || start_model_id < 0 || start_model_id >= nm))) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    if (!none)
+        for (int32_t id : {end_model_id, start_model_id})
+            if (vit_shape_for(c->models[id]->h, 2) < 0) { c->err = "anchored: model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
+    if (const int rc = drain(c, d)) return rc;          // a sub-batch in flight is taken with the target it ran with
+    Target& t = d->targets[target_id];
+    t.end_model_id = end_model_id; t.start_model_id = start_model_id;
+    t.end_bias = none ? 0 : end_bias; t.start_bias = none ? 0 : start_bias;
+    return STRQ_OK;
+}
+
+int strq_set_anchored(strq_ctx* c, int32_t on, double min_score)
+{
+    STRQ_ENTER(c);
+    if (on != 0 && on != 1) { c->err = "bad argument (strq_set_anchored takes 0 or 1)"; return STRQ_ERR_ARG; }
+    if (on && !(min_score > 0.0)) { c->err = "anchored: min_score must be above 0"; return STRQ_ERR_ARG; }
+    DetectState* d = dstate(c);
+    // sub-batches in flight keep the mode they were launched with: their pass (or none) runs now
+    if (const int rc = drain(c, d)) return rc;
+    d->extras.anch = on != 0; d->extras.anch_min = on ? min_score : 0.0;
+    return STRQ_OK;
+}
+
+int strq_batch_fetch_anchored(strq_ctx* c, strq_anchored* out, int64_t n)
+{
+    STRQ_ENTER(c);
+    DetectState* d = dstate(c);
+    if (const int rc = drain(c, d)) return rc;
+    const Batch& B = d->batch;
+    if (!B.ran.anch) { c->err = "the last batch ran without anchored counting (strq_set_anchored)"; return STRQ_ERR_ARG; }
+    if (n != B.n_reads || (n > 0 && !out)) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    if (n) std::memcpy(out, B.anch.data(), (size_t)n * sizeof(strq_anchored));
+    return STRQ_OK;
+}
+
+int strq_last_anchored(strq_ctx* c, double* out8)
+{
+    STRQ_ENTER(c);
+    if (!out8) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    DetectState* d = dstate(c);
+    out8[0] = d->anch_ms;
+    for (int k = 0; k < 4; ++k) out8[1 + k] = d->anch_kinds[k];
+    out8[5] = d->anch_launches; out8[6] = d->anch_g2; out8[7] = d->anch_lane;
     return STRQ_OK;
 }
 

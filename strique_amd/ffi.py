@@ -256,11 +256,13 @@ class Context(object):
             # edges that stand for several parallel paths: the forward pass sums them (the decode took the largest).  Arrays whose
             # in_logp was replaced after bake() carry a sum that no longer belongs to them: their in_logp stands alone
             self._check(self._lib.strq_model_set_forward_logp(self._h, mid, _ptr(_c(baked.in_logp_sum, np.float64))))
-        self.last_positions_rc = None
+        self.last_positions_rc = self.last_positions_error = None
         if getattr(baked, 'pos_kind', None) is not None:
             # optional register-resident image (profile chains); a model that is no such chain keeps its lane layout
             rc = self._lib.strq_model_set_positions(self._h, mid, _ptr(_c(baked.pos_kind, np.int32)), _ptr(_c(baked.pos_index, np.int32)))
             self.last_positions_rc = rc
+            # why the chain builder refused (a model that is no such chain keeps its lane layout): kept for whoever reports layouts
+            self.last_positions_error = self._lib.strq_last_error(self._h).decode() if rc == STRQ_ERR_UNSUPPORTED else None
             if rc not in (STRQ_OK, STRQ_ERR_UNSUPPORTED):
                 self._check(rc)
         return mid.value
@@ -385,6 +387,32 @@ class Context(object):
         out = np.zeros(4)
         self._check(self._lib.strq_last_mod_llr(self._h, _ptr(out)))
         return {'ms': float(out[0]), 'units': int(out[1]), 'reads': int(out[2]), 'launches': int(out[3])}
+
+    # ---- anchored counting ---------------------------------------------------------------
+    def target_set_anchored(self, target_id, end_model_id, end_bias, start_model_id, start_bias):
+        """strq_target_set_anchored: the end / start model of a target (hmm.AnchoredRepeatModel) and their count biases."""
+        self._check(self._lib.strq_target_set_anchored(self._h, ctypes.c_int32(target_id), ctypes.c_int32(end_model_id), ctypes.c_int32(end_bias),
+                                                       ctypes.c_int32(start_model_id), ctypes.c_int32(start_bias)))
+
+    def set_anchored(self, on, min_score=0.0):
+        """strq_set_anchored: later run calls also classify every read (strique_amd.anchored) and decode those that hold one flank
+        only.  StriqueHipError (STRQ_ERR_ARG) for a min_score that is not above 0."""
+        self._check(self._lib.strq_set_anchored(self._h, ctypes.c_int32(1 if on else 0), ctypes.c_double(min_score if on else 0.0)))
+
+    def batch_fetch_anchored(self):
+        """Records of the last batch (strq_batch_fetch_anchored): a structured array of ANCHORED_DTYPE, one element per read."""
+        n = getattr(self, '_n_batch', 0)
+        out = np.zeros(max(1, n), dtype=ANCHORED_DTYPE)
+        self._check(self._lib.strq_batch_fetch_anchored(self._h, _ptr(out), ctypes.c_int64(n)))
+        return out[:n]
+
+    def last_anchored(self):
+        """The anchored pass of the last run call (strq_last_anchored): {'ms', 'kinds' (reads of kind 0..3), 'launches',
+        'register_resident', 'lane_layout' (windows decoded on those kernel shapes)}."""
+        out = np.zeros(8)
+        self._check(self._lib.strq_last_anchored(self._h, _ptr(out)))
+        return {'ms': float(out[0]), 'kinds': tuple(int(v) for v in out[1:5]), 'launches': int(out[5]),
+                'register_resident': int(out[6]), 'lane_layout': int(out[7])}
 
     def batch_upload(self, signals, offsets, target_ids, host_stats=None):
         """signals: one concatenated int16 or float64 array; offsets: n_reads + 1."""
@@ -571,3 +599,6 @@ RESULT_DTYPE = np.dtype([("count", np.int32), ("status", np.int32), ("score_pref
                          ("score_suffix", np.float64), ("log_p", np.float64), ("offset", np.int64),
                          ("ticks", np.int64), ("prefix_begin", np.int64), ("prefix_end", np.int64),
                          ("suffix_begin", np.int64), ("suffix_end", np.int64)], align=True)
+
+ANCHORED_DTYPE = np.dtype([("kind", np.int32), ("status", np.int32), ("count", np.int32), ("pad_", np.int32), ("log_p", np.float64),
+                           ("begin", np.int64), ("end", np.int64), ("free_samples", np.int64)], align=True)

@@ -207,6 +207,90 @@ class FlankedRepeatModel(object):
         self.baked = bake(g, count_states=self.count_states, tag_substring='repeat')
 
 
+ANCHORED_KINDS = ('ends_in_repeat', 'starts_in_repeat')
+
+
+class AnchoredRepeatModel(object):
+    """FlankedRepeatModel with one flank profile replaced by a single emitting free state, for a read that holds one flank only
+    (strique_amd/anchored.py states which reads those are):
+
+      ends_in_repeat    prefix profile -> repeat loop -> `tail` -> end      the read breaks off inside the array
+      starts_in_repeat  start -> `head` -> repeat loop -> suffix profile    the read starts inside it
+
+    `tail` / `head` emit uniformly over the pore model's range, stay with `free_loop` and emit at least one observation, so that
+    the end state keeps its single kind of in-edge and no state gains an in-edge over the flanked model.  The topology forces
+    one pass through the loop (a read cut one base into the array decodes one visit), hence the -1 in `count_bias`."""
+
+    def __init__(self, kind, repeat, prefix, suffix, pm, config=None):
+        if kind not in ANCHORED_KINDS:
+            raise ValueError("AnchoredRepeatModel: kind must be one of %s" % (ANCHORED_KINDS,))
+        tp = _layer({'skip': 1 - 1e-4, 'seq_std_scale': 1.0, 'rep_std_scale': 1.0,
+                     'seq_std_offset': 0.0, 'rep_std_offset': 0.0, 'e1_ratio': 0.1, 'free_loop': 0.999},
+                    config if isinstance(config, dict) else None)
+        units = int(np.ceil(pm.kmer / len(repeat)))
+        self.kind = kind
+        g = Graph()
+        lay, pos = {}, {}
+        if kind == 'ends_in_repeat':
+            pre = add_profile(g, prefix + (repeat * units)[:-1], pm, tp, 'prefix', std_scale=tp['seq_std_scale'], std_offset=tp['seq_std_offset'])
+            rep = add_repeat(g, repeat, pm, tp, 'repeat', std_scale=tp['rep_std_scale'], std_offset=tp['rep_std_offset'])
+            free = g.add_state('tail', UNIFORM, (pm.model_min, pm.model_max))
+            g.add_transition(g.start, pre.s1, tp['e1_ratio'])
+            g.add_transition(g.start, pre.s2, 1 - tp['e1_ratio'])
+            g.add_transition(pre.e1, rep.s1, 1)
+            g.add_transition(pre.e2, rep.s2, 1)
+            g.add_transition(rep.e1, free, 1)
+            g.add_transition(rep.e2, free, 1)
+            g.add_transition(free, free, tp['free_loop'])
+            g.add_transition(free, g.end, 1 - tp['free_loop'])
+            # two slots: match-type states, insert-type states; lane = position along the chain.  The free state takes the next lane
+            # of the first slot, or -- where the flanked model's layout fills all 64 lanes -- the first lane of a third slot (the model
+            # then has 129 emitting states, i.e. three slots): whenever the flanked model has a layout, so has this one
+            P, R = len(pre.match), len(rep.profile.match)
+            for p_, st in enumerate(pre.match): lay[st] = (0, p_); pos[st] = (0, p_)
+            for p_, st in enumerate(pre.insert): lay[st] = (1, p_); pos[st] = (1, p_)
+            for q_, st in enumerate(rep.profile.match): lay[st] = (0, P + q_); pos[st] = (0, P + q_)
+            for q_, st in enumerate(rep.profile.insert): lay[st] = (1, P + q_); pos[st] = (1, P + q_)
+            lay[rep.d2] = (0, P + R); lay[rep.d1] = (1, P + R); lay[free] = (0, P + R + 1) if P + R + 1 < 64 else (2, 0)
+            pos[rep.d2] = (0, P + R); pos[rep.d1] = (1, P + R); pos[free] = (0, P + R + 1)
+            bias = -units - 1
+        else:
+            free = g.add_state('head', UNIFORM, (pm.model_min, pm.model_max))
+            rep = add_repeat(g, repeat, pm, tp, 'repeat', std_scale=tp['rep_std_scale'], std_offset=tp['rep_std_offset'])
+            suf = add_profile(g, repeat * units + suffix, pm, tp, 'suffix', std_scale=tp['seq_std_scale'], std_offset=tp['seq_std_offset'])
+            g.add_transition(g.start, free, 1)
+            g.add_transition(free, free, tp['free_loop'])
+            g.add_transition(free, rep.s1, (1 - tp['free_loop']) * tp['e1_ratio'])
+            g.add_transition(free, rep.s2, (1 - tp['free_loop']) * (1 - tp['e1_ratio']))
+            g.add_transition(rep.e1, suf.s1, 1)
+            g.add_transition(rep.e2, suf.s2, 1)
+            g.add_transition(suf.e1, g.end, 1)
+            g.add_transition(suf.e2, g.end, 1)
+            # the same two slots, the free state behind the suffix matches (or in a third slot, as above); along the chain it stands
+            # in front of the unit
+            R, S = len(rep.profile.match), len(suf.match)
+            pos[free] = (0, 0)
+            for q_, st in enumerate(rep.profile.match): lay[st] = (0, q_); pos[st] = (0, 1 + q_)
+            for q_, st in enumerate(rep.profile.insert): lay[st] = (1, q_); pos[st] = (1, 1 + q_)
+            lay[rep.d2] = (0, R); lay[rep.d1] = (1, R)
+            pos[rep.d2] = (0, 1 + R); pos[rep.d1] = (1, 1 + R)
+            for p_, st in enumerate(suf.match): lay[st] = (0, 1 + R + p_); pos[st] = (0, 2 + R + p_)
+            for p_, st in enumerate(suf.insert): lay[st] = (1, 1 + R + p_); pos[st] = (1, 2 + R + p_)
+            lay[free] = (0, 1 + R + S) if 1 + R + S < 64 else (2, 0)
+            bias = -1
+        if max(l for _, l in lay.values()) < 64:
+            g.layout = lay
+        g.positions = pos
+        self.graph = g
+        self.free_state = free
+        self.repeat_offset = rep.repeat_offset
+        self.count_states = (rep.d1, rep.d2)
+        # the flanked model's bias (flanking units - units the padded repeat profile holds), less the units of the flank profile
+        # that is gone (ends_in_repeat: the suffix profile starts with `units` of them), less the forced pass through the loop
+        self.count_bias = (units * 2 - 1) - rep.repeat_offset + bias
+        self.baked = bake(g, count_states=self.count_states, tag_substring='repeat')
+
+
 class RepeatModModel(object):
     """Unmodified and modified repeat-unit profiles side by side between two emitting hub states
     (STRique.py:447-490)."""
