@@ -419,6 +419,10 @@ int strq_debug_conditioning(strq_ctx* ctx, int64_t read, uint8_t* levels, int64_
  * strq_batch_run, in the element type of the batch (int16 or float64): min(n, length of the read) elements to `out`.
  * STRQ_ERR_ARG when the last sub-batch has no such read. */
 int strq_debug_filtered(strq_ctx* ctx, int64_t read, void* out, int64_t n);
+/* Test hook, no context and no device: the blocks of memory the library holds in this process right now, over all contexts --
+ * out[0] device blocks, out[1] blocks of pinned host memory.  Whatever a context, its models and its batches allocated is given
+ * back by strq_ctx_destroy: the two numbers are then what they were before strq_ctx_create. */
+int strq_debug_live_allocations(int64_t out[2]);
 /* Test hook, host only (no context, no device): the tables strq_model_set_positions would upload for this model --
  * out_lp[31 * 64] (log-probability of every column of the layout per lane, -inf where a lane has no such edge),
  * out_own[6 * 64] (state of every slot and lane, -1 if none, -2 for a virtual relay state), out_meta[10] = {slot, lane of

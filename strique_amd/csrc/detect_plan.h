@@ -12,6 +12,22 @@
 
 namespace strq {
 
+// The layout of one block of memory, said once: add<T>(count) hands out the byte offset of a region of `count` T and advances, every
+// region starts on a 16-byte boundary (a region of no elements takes no bytes), total() is what to reserve, at<T>(base, offset) the
+// region's pointer in a block that starts at `base` (null in no block).  A block and its mirror (device / pinned) take their pointers
+// from one Carve.
+struct Carve {
+    size_t end = 0;
+    template <class T> size_t add(size_t count)
+    {
+        const size_t at = end;
+        end += (count * sizeof(T) + 15) & ~(size_t)15;
+        return at;
+    }
+    size_t total() const { return end; }
+    template <class T> static T* at(void* base, size_t offset) { return base ? reinterpret_cast<T*>(static_cast<char*>(base) + offset) : nullptr; }
+};
+
 // The optional passes behind the count decode: unit positions (strq_set_units), forward pass (strq_set_confidence), per-unit scores
 // (strq_set_mod_llr).  DetectState holds what the next run call uses, a slot what its sub-batch was launched with, Batch what the last
 // run call ran with.

@@ -1469,17 +1469,20 @@ void strq_ctx_destroy(strq_ctx* c)
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     detect_state_free(c);
-    for (DevBuf* b : {&c->levels, &c->level_val, &c->flank_cls, &c->tables, &c->tables3, &c->band_lo, &c->col0, &c->ckpt,
-                      &c->rec, &c->tasks, &c->results, &c->queue, &c->scratch, &c->lutinfo, &c->hard, &c->misc,
-                      &c->vit_x, &c->vit_tasks, &c->vit_bp, &c->vit_path, &c->bnd, &c->gen_codes, &c->gen_table, &c->gen_bnd, &c->gen_trace, &c->gen_hard, &c->redo_total, &c->screen, &c->ckpt2})
-        b->release();
-    for (HostModel* m : c->models) if (m) { m->blob.release(); m->llr_blob.release(); delete m; }
+    for (HostModel* m : c->models) delete m;          // every image of a model goes with it
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->side_join) (void)hipEventDestroy(c->side_join);
     if (c->side_stream) (void)hipStreamDestroy(c->side_stream);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;          // ... and the workspace with the context
+}
+
+int strq_debug_live_allocations(int64_t out[2])
+{
+    if (!out) return STRQ_ERR_ARG;
+    out[0] = live_allocations[0].load(); out[1] = live_allocations[1].load();
+    return STRQ_OK;
 }
 
 const char* strq_last_error(const strq_ctx* c) { return c ? c->err.c_str() : "null context"; }

@@ -8,6 +8,8 @@
 #include <cstdio>
 #include <functional>
 #include <mutex>
+#include <atomic>
+#include <utility>
 #include "align_kernels.h"
 #include "viterbi_kernels.h"
 #include "forward_kernels.h"
@@ -17,22 +19,40 @@
 
 namespace strq {
 
-// grow-only device buffer
-struct DevBuf {
+// Blocks the process holds right now (strq_debug_live_allocations): [0] device, [1] pinned host memory.  Atomic: the upload thread of
+// a context allocates too.
+inline std::atomic<int64_t> live_allocations[2];
+
+// Grow-only buffer that owns its block: device memory (DevBuf) or pinned host memory (PinBuf).  reserve() frees the old block and takes
+// a larger one with slack; the destructor frees -- whatever holds a buffer (the context, the detect state, a slot, a HostModel) gives it
+// back when it is deleted.  Not copyable.
+template <bool PINNED> struct OwnedBuf {
     void* p = nullptr;
     size_t cap = 0;
+    OwnedBuf() = default;
+    OwnedBuf(const OwnedBuf&) = delete;
+    OwnedBuf& operator=(const OwnedBuf&) = delete;
+    ~OwnedBuf() { release(); }
     hipError_t reserve(size_t bytes)
     {
         if (bytes <= cap) return hipSuccess;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-        size_t want = bytes + bytes / 8 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) cap = want;
+        release();
+        const size_t want = bytes + bytes / 8 + (PINNED ? 0 : 256);
+        const hipError_t e = PINNED ? hipHostMalloc(&p, want, hipHostMallocDefault) : hipMalloc(&p, want);
+        if (e != hipSuccess) { p = nullptr; return e; }
+        cap = want; ++live_allocations[PINNED];
         return e;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    void release()
+    {
+        if (p) { (void)(PINNED ? hipHostFree(p) : hipFree(p)); --live_allocations[PINNED]; }
+        p = nullptr; cap = 0;
+    }
+    void swap(OwnedBuf& o) { std::swap(p, o.p); std::swap(cap, o.cap); }
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
+using DevBuf = OwnedBuf<false>;
+using PinBuf = OwnedBuf<true>;
 
 // strq_ctx::queue: work-queue heads of the persistent kernels, one zero-initialised int per launch of a call (index 0:
 // the table kernel's count of borderline entries, launches from index STRQ_QUEUE_FIRST on)
@@ -176,3 +196,13 @@ void host_stats_batch(const double* signals, const int64_t* offsets, int64_t n_r
             return STRQ_ERR_DEVICE;                                                            \
         }                                                                                      \
     } while (0)
+
+namespace strq {
+// the first 256 queue heads of the context zeroed on `st`, in front of the Viterbi / forward launches of a pass (one head each)
+inline int reset_queue_heads(strq_ctx* c, hipStream_t st)
+{
+    STRQ_HIP(c, c->queue.reserve(1024));
+    STRQ_HIP(c, hipMemsetAsync(c->queue.p, 0, 1024, st));
+    return STRQ_OK;
+}
+}

@@ -120,7 +120,7 @@ struct DetectState {
     // strq_scan_set: run calls compare these candidates (target ids) on every read instead of taking the read's own target
     bool scan_on = false; std::vector<int32_t> scan_cand; double scan_min = 0;
     DevBuf scan_idx, scan_out;           // scan: task table and candidate trims / winners, scores and raw scores of a sub-batch
-    void* scan_pin = nullptr; size_t scan_pin_cap = 0;      // ... and what the host reads of them before the Viterbi launches are planned
+    PinBuf scan_pin;                     // ... and what the host reads of them before the Viterbi launches are planned
     float unit_ms = 0; double unit_bytes = 0, unit_reads = 0, unit_positions = 0;      // strq_last_units: the last run call's unit pass
     hipEvent_t ev[4] = {};
     int64_t part_reads = 0;              // strq_batch_upload_part: reads uploaded so far
@@ -144,19 +144,20 @@ struct DetectState {
         int64_t r0 = 0; int nr = 0;
         const char* flt_base = nullptr;  // where the filtered signal of the sub-batch starts in `flt` (ReadCond::off counts from here)
         std::vector<int32_t> vit_slot;
-        void* pinned = nullptr; size_t pinned_cap = 0;
+        PinBuf pinned;
         hipEvent_t fwd_done = nullptr, v0 = nullptr, v1 = nullptr;
         // the pinned block of the slot: what the host reads of a sub-batch of `nr` reads
         struct Pinned {
-            ReadGeom* geom; VitResult* vres; ReadCond* rc; unsigned int* redo;
-            static size_t bytes(int nr) { return (size_t)nr * (sizeof(ReadGeom) + sizeof(VitResult) + sizeof(ReadCond)) + 64; }
+            ReadGeom* geom; VitResult* vres; ReadCond* rc; unsigned int* redo; size_t bytes;
+            Pinned(void* base, int n)
+            {
+                Carve L;
+                geom = Carve::at<ReadGeom>(base, L.add<ReadGeom>(n)); vres = Carve::at<VitResult>(base, L.add<VitResult>(n));
+                rc = Carve::at<ReadCond>(base, L.add<ReadCond>(n)); redo = Carve::at<unsigned int>(base, L.add<unsigned int>(1));
+                bytes = L.total();
+            }
         };
-        Pinned host() const
-        {
-            Pinned h; h.geom = static_cast<ReadGeom*>(pinned); h.vres = reinterpret_cast<VitResult*>(h.geom + nr);
-            h.rc = reinterpret_cast<ReadCond*>(h.vres + nr); h.redo = reinterpret_cast<unsigned int*>(h.rc + nr);
-            return h;
-        }
+        Pinned host() const { return Pinned(pinned.p, nr); }
         // buffers and pinned block for a sub-batch of `n` reads with `flt_bytes` of filtered signal
         int reserve(strq_ctx* c, int n, size_t flt_bytes)
         {
@@ -165,12 +166,7 @@ struct DetectState {
             STRQ_HIP(c, vres.reserve((size_t)n * sizeof(VitResult)));
             STRQ_HIP(c, order.reserve((size_t)n * 4 + 64));
             STRQ_HIP(c, vq.reserve(1024));
-            const size_t need = Pinned::bytes(n);
-            if (need > pinned_cap) {
-                if (pinned) { STRQ_HIP(c, hipHostFree(pinned)); pinned = nullptr; pinned_cap = 0; }
-                STRQ_HIP(c, hipHostMalloc(&pinned, need + need / 8, hipHostMallocDefault));
-                pinned_cap = need + need / 8;
-            }
+            STRQ_HIP(c, pinned.reserve(Pinned(nullptr, n).bytes + 64));
             return STRQ_OK;
         }
     };
@@ -187,8 +183,17 @@ struct DetectState {
     int last_slot = -1, flt_shift = 0, last_nr = 0;
     hipStream_t copy_stream = nullptr;   // host -> HBM uploads that overlap the kernels of the previous sub-batch
     static constexpr int N_STAGE = 4;    // pinned staging ring of upload_reads
-    void* stage[N_STAGE] = {}; hipEvent_t stage_ev[N_STAGE] = {}; bool stage_busy[N_STAGE] = {};
+    PinBuf stage[N_STAGE]; hipEvent_t stage_ev[N_STAGE] = {}; bool stage_busy[N_STAGE] = {};
 };
+
+// the target of a read of the batch and its models: the flanked one, the modification model, the anchored model of a read of `kind`
+static const Target& target_of(const DetectState* d, int64_t read) { return d->targets[d->batch.target[(size_t)read]]; }
+static HostModel* flank_model(const strq_ctx* c, const DetectState* d, int64_t read) { return c->models[target_of(d, read).model_id]; }
+static HostModel* mod_model(const strq_ctx* c, const DetectState* d, int64_t read) { return c->models[target_of(d, read).mod_model_id]; }
+static HostModel* anchored_model(const strq_ctx* c, const DetectState* d, int64_t read, int kind)
+{
+    return c->models[kind == ANCH_ENDS ? target_of(d, read).end_model_id : target_of(d, read).start_model_id];
+}
 
 static int upload_join(DetectState* d);
 
@@ -204,20 +209,13 @@ void detect_state_free(strq_ctx* c)
     DetectState* d = static_cast<DetectState*>(c->detect);
     (void)upload_join(d);
     if (d->vit_stream) (void)hipStreamSynchronize(d->vit_stream);
-    for (DevBuf* b : {&d->batch.raw, &d->rc, &d->hist16, &d->hist8, &d->geom, &d->idx,
-                      &d->hist_raw, &d->bp, &d->path, &d->modtask, &d->modsig, &d->modlen, &d->pattern, &d->hrange, &d->modpool, &d->f64s,
-                      &d->unit_task, &d->unit_ws, &d->unit_path, &d->unit_pool, &d->conf_task, &d->llr_ws, &d->scan_idx, &d->scan_out, &d->anch_ws, &d->anch_task}) b->release();
-    if (d->scan_pin) (void)hipHostFree(d->scan_pin);
-    for (auto& sl : d->slot) {
-        for (DevBuf* b : {&sl.flt, &sl.vit, &sl.vres, &sl.order, &sl.vq}) b->release();
-        if (sl.pinned) (void)hipHostFree(sl.pinned);
+    for (auto& sl : d->slot)
         for (hipEvent_t e : {sl.fwd_done, sl.v0, sl.v1}) if (e) (void)hipEventDestroy(e);
-    }
     if (d->vit_stream) (void)hipStreamDestroy(d->vit_stream);
     for (hipEvent_t e : d->ev) if (e) (void)hipEventDestroy(e);
     if (d->copy_stream) (void)hipStreamDestroy(d->copy_stream);
-    for (int i = 0; i < DetectState::N_STAGE; ++i) { if (d->stage[i]) (void)hipHostFree(d->stage[i]); if (d->stage_ev[i]) (void)hipEventDestroy(d->stage_ev[i]); }
-    delete d;
+    for (hipEvent_t e : d->stage_ev) if (e) (void)hipEventDestroy(e);
+    delete d;          // its buffers, device and pinned, go with it
     c->detect = nullptr;
 }
 
@@ -341,20 +339,20 @@ static int run_llr_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, cons
     std::vector<int> by_mode[3];
     for (int k = 0; k < nm; ++k) {
         if (!n_units[(size_t)k]) continue;
-        HostModel* hm = c->models[d->targets[B.target[r0 + who[k]]].mod_model_id];
+        HostModel* hm = mod_model(c, d, r0 + who[k]);
         // the image was built, and a model without one refused, when the switch went on or the target's model was registered:
         // nothing is built or refused in the middle of a batch
         if (!hm->llr_dev || hm->llr_mode < 0 || hm->llr_mode > 2) { c->err = "mod-llr: modification model without an edge image (strq_set_mod_llr validates them)"; return STRQ_ERR_DEVICE; }
         by_mode[hm->llr_mode].push_back(k);
     }
-    const size_t o_w = ((size_t)U * 16 + 15) & ~(size_t)15, o_bt = o_w + (((size_t)U * 4 + 15) & ~(size_t)15),
-                 o_rd = o_bt + (size_t)nm * sizeof(LlrBoundTask), o_first = o_rd + (size_t)nm * sizeof(LlrRead),
-                 o_bad = o_first + ((size_t)nm + 3) * 8, total = o_bad + (size_t)nm * 4;
-    STRQ_HIP(c, d->llr_ws.reserve(total + 64));
-    char* ws = d->llr_ws.as<char>();
-    double* d_out = reinterpret_cast<double*>(ws); int32_t* d_w = reinterpret_cast<int32_t*>(ws + o_w);
-    LlrBoundTask* d_bt = reinterpret_cast<LlrBoundTask*>(ws + o_bt); LlrRead* d_rd = reinterpret_cast<LlrRead*>(ws + o_rd);
-    int64_t* d_first = reinterpret_cast<int64_t*>(ws + o_first); int32_t* d_bad = reinterpret_cast<int32_t*>(ws + o_bad);
+    Carve lay;
+    const size_t o_out = lay.add<double>(2 * (size_t)U), o_w = lay.add<int32_t>((size_t)U), o_bt = lay.add<LlrBoundTask>((size_t)nm),
+                 o_rd = lay.add<LlrRead>((size_t)nm), o_first = lay.add<int64_t>((size_t)nm + 3), o_bad = lay.add<int32_t>((size_t)nm);
+    STRQ_HIP(c, d->llr_ws.reserve(lay.total() + 64));
+    void* ws = d->llr_ws.p;
+    double* d_out = Carve::at<double>(ws, o_out); int32_t* d_w = Carve::at<int32_t>(ws, o_w);
+    LlrBoundTask* d_bt = Carve::at<LlrBoundTask>(ws, o_bt); LlrRead* d_rd = Carve::at<LlrRead>(ws, o_rd);
+    int64_t* d_first = Carve::at<int64_t>(ws, o_first); int32_t* d_bad = Carve::at<int32_t>(ws, o_bad);
     std::vector<LlrBoundTask> bt; std::vector<LlrRead> rdv; std::vector<int64_t> first;
     struct L { int mode, at, n, first_at; int64_t units; };
     std::vector<L> launches;
@@ -362,7 +360,7 @@ static int run_llr_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, cons
         if (by_mode[mode].empty()) continue;
         L l = {mode, (int)rdv.size(), (int)by_mode[mode].size(), (int)first.size(), 0};
         for (int k : by_mode[mode]) {
-            HostModel* hm = c->models[d->targets[B.target[r0 + who[k]]].mod_model_id];
+            HostModel* hm = mod_model(c, d, r0 + who[k]);
             const int s2 = (*in.slot2)[(size_t)k];
             LlrBoundTask b; std::memset(&b, 0, sizeof(b));
             b.rec = in.use_hub ? reinterpret_cast<const uint64_t*>(d->bp.as<uint16_t>() + (*in.bp2_off)[(size_t)k]) : nullptr;
@@ -412,8 +410,7 @@ static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
     const int64_t s0 = B.off[r0];
     std::vector<int> who;                      // reads that reach the modification model
     for (int i = 0; i < nr; ++i) {
-        const Target& t = d->targets[B.target[r0 + i]];
-        if (t.mod_model_id < 0 || !geom[i].gate) continue;
+        if (target_of(d, r0 + i).mod_model_id < 0 || !geom[i].gate) continue;
         const VitResult& v = vres[vit_slot[i]];
         if (v.status == 2) { c->err = "modification pass: repeat window of 2^21 samples or more"; return STRQ_ERR_UNSUPPORTED; }
         if (v.status == 0) who.push_back(i);
@@ -433,17 +430,18 @@ static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
         len[k] = enter ? (leave ? leave - 1 : T) - (enter - 1) : 0;
         sig_off[k] = sig_tot; sig_tot += (size_t)len[k];
     }
-    STRQ_HIP(c, d->modtask.reserve((size_t)nm * (sizeof(VitTask) + sizeof(VitResult) + 8 + sizeof(ModTask) + sizeof(PatTask)) + 256));
-    VitTask* d_tb = d->modtask.as<VitTask>();
-    VitResult* d_tr = reinterpret_cast<VitResult*>(d_tb + nm);
-    int32_t** d_tp = reinterpret_cast<int32_t**>(d_tr + nm);
-    ModTask* d_mt = reinterpret_cast<ModTask*>(d_tp + nm);
-    PatTask* d_pt = reinterpret_cast<PatTask*>(d_mt + nm);
+    Carve lay;
+    const size_t o_tb = lay.add<VitTask>((size_t)nm), o_tr = lay.add<VitResult>((size_t)nm), o_tp = lay.add<int32_t*>((size_t)nm),
+                 o_mt = lay.add<ModTask>((size_t)nm), o_pt = lay.add<PatTask>((size_t)nm);
+    STRQ_HIP(c, d->modtask.reserve(lay.total() + 256));
+    void* ws = d->modtask.p;
+    VitTask* d_tb = Carve::at<VitTask>(ws, o_tb); VitResult* d_tr = Carve::at<VitResult>(ws, o_tr); int32_t** d_tp = Carve::at<int32_t*>(ws, o_tp);
+    ModTask* d_mt = Carve::at<ModTask>(ws, o_mt); PatTask* d_pt = Carve::at<PatTask>(ws, o_pt);
     STRQ_HIP(c, d->modsig.reserve(sig_tot * 8 + 64));
     STRQ_HIP(c, d->modlen.reserve((size_t)nm * 16 + 64));
     std::vector<ModTask> mt(nm);
     for (int k = 0; k < nm; ++k) {
-        const int i = who[k]; const Target& t = d->targets[B.target[r0 + i]];
+        const int i = who[k]; const Target& t = target_of(d, r0 + i);
         ModTask& m = mt[k];
         m.path = nullptr; m.tag = nullptr;          // contiguous stretch: every sample is kept
         m.raw = d->batch.raw.as<char>() + (size_t)(s0 + rc[i].off + geom[i].prefix_begin + first[k]) * esz;
@@ -459,7 +457,7 @@ static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
     std::vector<GroupItem> items(nm);
     bool use_hub = !strq::opt("STRQ_MOD_BACKPOINTERS");
     for (int k = 0; k < nm; ++k) {
-        HostModel* hm = c->models[d->targets[B.target[r0 + who[k]]].mod_model_id];
+        HostModel* hm = mod_model(c, d, r0 + who[k]);
         const int shape = vit_shape_of(hm->h);
         if (shape < 0) { c->err = "modification model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
         items[k] = {0, shape, hm->h.n_cells};
@@ -470,18 +468,20 @@ static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
     std::vector<VitTask> vt2(nm); std::vector<int32_t*> tp2(nm);
     size_t bp2 = 0, p2 = 0; std::vector<size_t> bp2_off(nm), p2_off(nm);
     for (int k = 0; k < nm; ++k) {
-        HostModel* hm = c->models[d->targets[B.target[r0 + who[k]]].mod_model_id];
         // back-pointers: uint16 per (time step, state); hub records: 8 bytes per time step (in uint16 units: 4)
-        bp2_off[k] = bp2; bp2 += use_hub ? (size_t)(len[k] + 1) * 4 : (size_t)(len[k] + 1) * hm->h.n_states;
+        bp2_off[k] = bp2; bp2 += use_hub ? (size_t)(len[k] + 1) * 4 : (size_t)(len[k] + 1) * mod_model(c, d, r0 + who[k])->h.n_states;
         p2_off[k] = p2; p2 += (size_t)len[k] + 1;
     }
     STRQ_HIP(c, d->bp.reserve(bp2 * 2 + 64));
-    STRQ_HIP(c, d->pattern.reserve((use_hub ? 0 : p2 * 4) + p2 + (size_t)nm * 8 + (size_t)nm * sizeof(HubTask) + 64));
-    int32_t* d_path2 = d->pattern.as<int32_t>(); char* d_chars = reinterpret_cast<char*>(d_path2 + (use_hub ? 0 : p2));
-    STRQ_HIP(c, hipMemsetAsync(c->queue.p, 0, 1024, st));
+    // traced state paths (back-pointer route only), the pattern strings, the tasks of the hub route
+    Carve pat;
+    const size_t o_path2 = pat.add<int32_t>(use_hub ? 0 : p2), o_chars = pat.add<char>(p2), o_ht = pat.add<HubTask>(use_hub ? (size_t)nm : 0);
+    STRQ_HIP(c, d->pattern.reserve(pat.total() + 64));
+    int32_t* d_path2 = Carve::at<int32_t>(d->pattern.p, o_path2); char* d_chars = Carve::at<char>(d->pattern.p, o_chars);
+    if (const int qrc = reset_queue_heads(c, st)) return qrc;
     for (int k = 0; k < nm; ++k) {
         VitTask& v = vt2[slot2[k]]; v = VitTask();
-        v.model = c->models[d->targets[B.target[r0 + who[k]]].mod_model_id]->dev; v.sig = mt[k].out; v.T = len[k]; v.src_kind = VIT_SRC_F64;
+        v.model = mod_model(c, d, r0 + who[k])->dev; v.sig = mt[k].out; v.T = len[k]; v.src_kind = VIT_SRC_F64;
         v.bp = d->bp.as<uint16_t>() + bp2_off[k];
         tp2[slot2[k]] = d_path2 + p2_off[k];
     }
@@ -500,7 +500,7 @@ static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
             ht[sl].rec = reinterpret_cast<const uint64_t*>(d->bp.as<uint16_t>() + bp2_off[k]);
             ht[sl].result = d_tr + sl; ht[sl].out = d_chars + p2_off[k];
         }
-        HubTask* d_ht = reinterpret_cast<HubTask*>(d_chars + ((p2 + 15) & ~(size_t)15));
+        HubTask* d_ht = Carve::at<HubTask>(d->pattern.p, o_ht);
         STRQ_HIP(c, hipMemcpyAsync(d_ht, ht.data(), (size_t)nm * sizeof(HubTask), hipMemcpyHostToDevice, st));
         if (launch_mod_hub_pattern(st, d_ht, nm, d_plen)) { c->err = "pattern launch failed"; return STRQ_ERR_DEVICE; }
     } else {
@@ -510,8 +510,7 @@ static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
         std::vector<PatTask> pt(nm);
         for (int k = 0; k < nm; ++k) {
             const int sl = slot2[k];
-            HostModel* hm = c->models[d->targets[B.target[r0 + who[k]]].mod_model_id];
-            pt[sl].path = tp2[sl]; pt[sl].tag = hm->h.state_tag; pt[sl].out = d_chars + p2_off[k]; pt[sl].T = len[k];
+            pt[sl].path = tp2[sl]; pt[sl].tag = mod_model(c, d, r0 + who[k])->h.state_tag; pt[sl].out = d_chars + p2_off[k]; pt[sl].T = len[k];
             pt[sl].status = &d_tr[sl].status;
         }
         STRQ_HIP(c, hipMemcpyAsync(d_pt, pt.data(), (size_t)nm * sizeof(PatTask), hipMemcpyHostToDevice, st));
@@ -545,7 +544,7 @@ static int run_unit_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, con
     struct W { int i; int shape; bool rec; size_t bytes; };
     std::vector<W> ws;
     for (int i : who) {
-        HostModel* hm = c->models[d->targets[B.target[r0 + i]].model_id];
+        HostModel* hm = flank_model(c, d, r0 + i);
         const int64_t T = vt[(size_t)sl.vit_slot[i]].T;
         W w; w.i = i; w.shape = vit_shape_for(hm->h, 4);
         w.rec = !force_bp && vit_unit_ok(hm->h, w.shape) && T < VIT_UNIT_T_MAX;
@@ -563,15 +562,16 @@ static int run_unit_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, con
         std::vector<GroupItem> items((size_t)m);
         for (int k = 0; k < m; ++k) {
             const W& w = ws[c0 + (size_t)k];
-            items[(size_t)k] = {w.rec ? 0 : 1, w.shape, c->models[d->targets[B.target[r0 + w.i]].model_id]->h.n_cells};
+            items[(size_t)k] = {w.rec ? 0 : 1, w.shape, flank_model(c, d, r0 + w.i)->h.n_cells};
         }
         const Grouping G = group_items(items);
-        STRQ_HIP(c, d->unit_task.reserve((size_t)m * (sizeof(VitTask) + sizeof(VitResult) + 8 + sizeof(UnitTask) + 4) + 256));
-        VitTask* d_vt = d->unit_task.as<VitTask>();
-        VitResult* d_vr = reinterpret_cast<VitResult*>(d_vt + m);
-        int32_t** d_paths = reinterpret_cast<int32_t**>(d_vr + m);
-        UnitTask* d_ut = reinterpret_cast<UnitTask*>(d_paths + m);
-        int32_t* d_bad = reinterpret_cast<int32_t*>(d_ut + m);
+        Carve lay;
+        const size_t o_vt = lay.add<VitTask>((size_t)m), o_vr = lay.add<VitResult>((size_t)m), o_paths = lay.add<int32_t*>((size_t)m),
+                     o_ut = lay.add<UnitTask>((size_t)m), o_bad = lay.add<int32_t>((size_t)m);
+        STRQ_HIP(c, d->unit_task.reserve(lay.total() + 256));
+        void* tb = d->unit_task.p;
+        VitTask* d_vt = Carve::at<VitTask>(tb, o_vt); VitResult* d_vr = Carve::at<VitResult>(tb, o_vr); int32_t** d_paths = Carve::at<int32_t*>(tb, o_paths);
+        UnitTask* d_ut = Carve::at<UnitTask>(tb, o_ut); int32_t* d_bad = Carve::at<int32_t>(tb, o_bad);
         size_t path_n = 0, pos_n = 0;
         for (size_t k = c0; k < c1; ++k) {
             if (!ws[k].rec) path_n += (size_t)vt[(size_t)sl.vit_slot[ws[k].i]].T;
@@ -585,7 +585,7 @@ static int run_unit_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, con
         size_t wo = 0, po = 0, xo = 0; int n_rec = 0;
         for (int at = 0; at < m; ++at) {          // in task order: the workspace, the paths and the positions lie in that order too
             const W& w = ws[c0 + (size_t)G.order[(size_t)at]];
-            HostModel* hm = c->models[d->targets[B.target[r0 + w.i]].model_id];
+            HostModel* hm = flank_model(c, d, r0 + w.i);
             const VitResult& v0 = vres[sl.vit_slot[w.i]];
             VitTask t = vt[(size_t)sl.vit_slot[w.i]];
             t.bp = reinterpret_cast<uint16_t*>(d->unit_ws.as<char>() + wo); wo += (w.bytes + 15) & ~(size_t)15;
@@ -603,8 +603,7 @@ static int run_unit_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, con
         STRQ_HIP(c, hipMemcpyAsync(d_ut, uv.data(), (size_t)m * sizeof(UnitTask), hipMemcpyHostToDevice, st));
         STRQ_HIP(c, hipMemsetAsync(d_bad, 0, (size_t)m * 4, st));
         if (path_n) STRQ_HIP(c, hipMemsetAsync(d->unit_path.p, 0, path_n * 4, st));      // a traceback that stops early leaves valid states behind
-        STRQ_HIP(c, c->queue.reserve(1024));
-        STRQ_HIP(c, hipMemsetAsync(c->queue.p, 0, 1024, st));
+        if (const int qrc = reset_queue_heads(c, st)) return qrc;
         int qi = 0;
         for (const VitGroup& g : G.groups) {
             const int want = g.route == 0 ? 4 : 1;          // unit records, or back-pointers and a traceback
@@ -644,29 +643,29 @@ static int run_conf_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, con
     const int m = (int)who.size();
     std::vector<GroupItem> items((size_t)m);
     for (int k = 0; k < m; ++k) {
-        HostModel* hm = c->models[d->targets[B.target[r0 + who[(size_t)k]]].model_id];
+        HostModel* hm = flank_model(c, d, r0 + who[(size_t)k]);
         if (const int rc = forward_model(c, hm)) return rc;
         items[(size_t)k] = {0, vit_shape_of(hm->h), hm->h.n_cells};
     }
     const Grouping G = group_items(items);
     const std::vector<VitGroup>& launches = G.groups;
-    STRQ_HIP(c, d->conf_task.reserve((size_t)m * (sizeof(VitTask) + sizeof(FwdResult) + 8 + 8 + 4) + 256));
-    VitTask* d_vt = d->conf_task.as<VitTask>();
-    FwdResult* d_fr = reinterpret_cast<FwdResult*>(d_vt + m);
-    const FwdModel** d_fm = reinterpret_cast<const FwdModel**>(d_fr + m);
-    int64_t* d_c0 = reinterpret_cast<int64_t*>(d_fm + m);
-    int* d_order = reinterpret_cast<int*>(d_c0 + m);
+    Carve lay;
+    const size_t o_vt = lay.add<VitTask>((size_t)m), o_fr = lay.add<FwdResult>((size_t)m), o_fm = lay.add<const FwdModel*>((size_t)m),
+                 o_c0 = lay.add<int64_t>((size_t)m), o_order = lay.add<int>((size_t)m);
+    STRQ_HIP(c, d->conf_task.reserve(lay.total() + 256));
+    void* tb = d->conf_task.p;
+    VitTask* d_vt = Carve::at<VitTask>(tb, o_vt); FwdResult* d_fr = Carve::at<FwdResult>(tb, o_fr); const FwdModel** d_fm = Carve::at<const FwdModel*>(tb, o_fm);
+    int64_t* d_c0 = Carve::at<int64_t>(tb, o_c0); int* d_order = Carve::at<int>(tb, o_order);
     std::vector<VitTask> tv((size_t)m); std::vector<const FwdModel*> fv((size_t)m); std::vector<int64_t> cv((size_t)m); std::vector<int> read_of((size_t)m);
     for (int at = 0; at < m; ++at) {
         const int i = who[(size_t)G.order[(size_t)at]];
         tv[(size_t)at] = vt[(size_t)sl.vit_slot[i]]; tv[(size_t)at].bp = nullptr;
-        fv[(size_t)at] = c->models[d->targets[B.target[r0 + i]].model_id]->fwd_dev; cv[(size_t)at] = vres[sl.vit_slot[i]].counted; read_of[(size_t)at] = i;
+        fv[(size_t)at] = flank_model(c, d, r0 + i)->fwd_dev; cv[(size_t)at] = vres[sl.vit_slot[i]].counted; read_of[(size_t)at] = i;
     }
     STRQ_HIP(c, hipMemcpyAsync(d_vt, tv.data(), (size_t)m * sizeof(VitTask), hipMemcpyHostToDevice, st));
     STRQ_HIP(c, hipMemcpyAsync(d_fm, fv.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
     STRQ_HIP(c, hipMemcpyAsync(d_c0, cv.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
-    STRQ_HIP(c, c->queue.reserve(1024));
-    STRQ_HIP(c, hipMemsetAsync(c->queue.p, 0, 1024, st));
+    if (const int qrc = reset_queue_heads(c, st)) return qrc;
     int every = 1;
     if (const char* e = strq::opt("STRQ_FWD_RESCALE_EVERY")) { const int v = atoi(e); if (v >= 1) every = v; }
     int qi = 0;
@@ -684,7 +683,7 @@ static int run_conf_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, con
         double ll, mean, var;
         const int nopath = fwd_finish(fr[(size_t)k], cv[(size_t)k], &ll, &mean, &var);
         B.conf[3 * (size_t)r] = ll;
-        B.conf[3 * (size_t)r + 1] = nopath ? mean : (double)d->targets[B.target[r]].count_bias + mean;
+        B.conf[3 * (size_t)r + 1] = nopath ? mean : (double)target_of(d, r).count_bias + mean;
         B.conf[3 * (size_t)r + 2] = nopath ? var : std::sqrt(var);
         B.conf_dec[(size_t)r] = 1;
         d->conf_nopath += nopath; d->conf_expo = std::max(d->conf_expo, std::fabs((double)fr[(size_t)k].expo));
@@ -707,10 +706,11 @@ static int run_anchored_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
     if (nr <= 0) return STRQ_OK;
     const DetectState::Slot::Pinned h = sl.host();
     if (const int rc = pass_start(c, d)) return rc;
-    const size_t o_rc = ((size_t)nr * sizeof(ReadGeom) + 15) & ~(size_t)15, o_cls = o_rc + (((size_t)nr * sizeof(ReadCond) + 15) & ~(size_t)15);
-    STRQ_HIP(c, d->anch_ws.reserve(o_cls + (size_t)nr * sizeof(AnchoredClass) + 64));
-    ReadGeom* d_geom = d->anch_ws.as<ReadGeom>(); ReadCond* d_rc = reinterpret_cast<ReadCond*>(d->anch_ws.as<char>() + o_rc);
-    AnchoredClass* d_cls = reinterpret_cast<AnchoredClass*>(d->anch_ws.as<char>() + o_cls);
+    Carve wl;
+    const size_t o_geom = wl.add<ReadGeom>((size_t)nr), o_rc = wl.add<ReadCond>((size_t)nr), o_cls = wl.add<AnchoredClass>((size_t)nr);
+    STRQ_HIP(c, d->anch_ws.reserve(wl.total() + 64));
+    ReadGeom* d_geom = Carve::at<ReadGeom>(d->anch_ws.p, o_geom); ReadCond* d_rc = Carve::at<ReadCond>(d->anch_ws.p, o_rc);
+    AnchoredClass* d_cls = Carve::at<AnchoredClass>(d->anch_ws.p, o_cls);
     STRQ_HIP(c, hipMemcpyAsync(d_geom, h.geom, (size_t)nr * sizeof(ReadGeom), hipMemcpyHostToDevice, st));
     STRQ_HIP(c, hipMemcpyAsync(d_rc, h.rc, (size_t)nr * sizeof(ReadCond), hipMemcpyHostToDevice, st));
     AnchoredClassifyArgs ca;
@@ -733,13 +733,10 @@ static int run_anchored_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
     }
     const int m = (int)who.size();
     if (!m) return pass_stop(c, d, d->anch_ms);
-    auto model_of = [&](int i) -> HostModel* {
-        const Target& t = d->targets[B.target[r0 + i]];
-        return c->models[cls[(size_t)i].kind == ANCH_ENDS ? t.end_model_id : t.start_model_id];
-    };
+    auto model_of = [&](int i) { return anchored_model(c, d, r0 + i, cls[(size_t)i].kind); };
     std::vector<GroupItem> items((size_t)m);
     for (int k = 0; k < m; ++k) {
-        const Target& t = d->targets[B.target[r0 + who[(size_t)k]]];
+        const Target& t = target_of(d, r0 + who[(size_t)k]);
         // (run_range refused the call before any launch when a target of the range had none)
         if (t.end_model_id < 0 || t.start_model_id < 0) { c->err = "anchored: target without anchored models (strq_target_set_anchored)"; return STRQ_ERR_ARG; }
         HostModel* hm = model_of(who[(size_t)k]);
@@ -748,11 +745,11 @@ static int run_anchored_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
         items[(size_t)k] = {0, shape, hm->h.n_cells};
     }
     const Grouping G = group_items(items);
-    const size_t o_vr = (size_t)m * sizeof(VitTask), o_md = o_vr + (size_t)m * sizeof(VitResult), o_rd = o_md + (size_t)m * 8;
-    STRQ_HIP(c, d->anch_task.reserve(o_rd + (size_t)m * 4 + 64));
-    VitTask* d_vt = d->anch_task.as<VitTask>(); VitResult* d_vr = reinterpret_cast<VitResult*>(d->anch_task.as<char>() + o_vr);
-    const VitModel** d_md = reinterpret_cast<const VitModel**>(d->anch_task.as<char>() + o_md);
-    int32_t* d_rd = reinterpret_cast<int32_t*>(d->anch_task.as<char>() + o_rd);
+    Carve tl;
+    const size_t o_vt = tl.add<VitTask>((size_t)m), o_vr = tl.add<VitResult>((size_t)m), o_md = tl.add<const VitModel*>((size_t)m), o_rd = tl.add<int32_t>((size_t)m);
+    STRQ_HIP(c, d->anch_task.reserve(tl.total() + 64));
+    VitTask* d_vt = Carve::at<VitTask>(d->anch_task.p, o_vt); VitResult* d_vr = Carve::at<VitResult>(d->anch_task.p, o_vr);
+    const VitModel** d_md = Carve::at<const VitModel*>(d->anch_task.p, o_md); int32_t* d_rd = Carve::at<int32_t>(d->anch_task.p, o_rd);
     std::vector<int32_t> read_of((size_t)m); std::vector<const VitModel*> mv((size_t)m);
     for (int at = 0; at < m; ++at) {
         const int i = who[(size_t)G.order[(size_t)at]];
@@ -765,8 +762,7 @@ static int run_anchored_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
     ta.vit = d_vt; ta.n_tasks = m; ta.n_reads = nr;
     if (launch_anchored_tasks(st, ta)) { c->err = "anchored: task launch failed"; return STRQ_ERR_DEVICE; }
     d->anch_launches += 1;
-    STRQ_HIP(c, c->queue.reserve(1024));
-    STRQ_HIP(c, hipMemsetAsync(c->queue.p, 0, 1024, st));
+    if (const int qrc = reset_queue_heads(c, st)) return qrc;
     int qi = 0;
     for (const VitGroup& g : G.groups) {
         if (const int src = sort_viterbi_group(c, st, g, d_vt, sl.order.as<int>())) return src;
@@ -781,7 +777,7 @@ static int run_anchored_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
     for (int at = 0; at < m; ++at) {
         const int i = read_of[(size_t)at];
         const AnchoredClass& k = cls[(size_t)i];
-        const Target& t = d->targets[B.target[r0 + i]];
+        const Target& t = target_of(d, r0 + i);
         const VitResult& v = vr[(size_t)at];
         B.anch[(size_t)(r0 + i)] = anchored_record(k.kind, k.begin, k.end - k.begin, v.status, v.counted, k.kind == ANCH_ENDS ? t.end_bias : t.start_bias,
                                                    v.logp, (int64_t)v.dbg[0], (int64_t)v.dbg[1]);
@@ -847,18 +843,15 @@ static int upload_reads(strq_ctx* c, DetectState* d, int64_t upto)
         }
         STRQ_HIP(c, hipStreamSynchronize(d->copy_stream));
     } else if (b1 > b0) {
-        if (!d->stage[0]) {
-            for (int i = 0; i < DetectState::N_STAGE; ++i) {
-                STRQ_HIP(c, hipHostMalloc(&d->stage[i], SLOT, hipHostMallocDefault));
-                STRQ_HIP(c, hipEventCreateWithFlags(&d->stage_ev[i], hipEventDisableTiming));
-                d->stage_busy[i] = false;
-            }
+        for (int i = 0; i < DetectState::N_STAGE; ++i) {          // every entry on its own: what an earlier call could not get is tried again
+            STRQ_HIP(c, d->stage[i].reserve(SLOT));
+            if (!d->stage_ev[i]) STRQ_HIP(c, hipEventCreateWithFlags(&d->stage_ev[i], hipEventDisableTiming));
         }
         int slot = 0;
         for (size_t pos = b0; pos < b1; pos += SLOT, slot = (slot + 1) % DetectState::N_STAGE) {
             const size_t len = std::min(SLOT, b1 - pos);
             if (d->stage_busy[slot]) { STRQ_HIP(c, hipEventSynchronize(d->stage_ev[slot])); d->stage_busy[slot] = false; }
-            char* dst = static_cast<char*>(d->stage[slot]);
+            char* dst = d->stage[slot].as<char>();
             const size_t part = ((len + n_threads - 1) / n_threads + 4095) & ~(size_t)4095;
             std::vector<std::thread> th;
             const Batch* Bp = &B;
@@ -952,7 +945,7 @@ static int take_rows(strq_ctx* c, DetectState* d, DetectState::Slot& sl, bool un
         o.offset = g.prefix_end; o.ticks = std::max<int64_t>(g.suffix_begin - g.prefix_end, 0);
         if (g.gate) c->counters[7] += (double)(g.suffix_end - g.prefix_begin);
         if (g.gate && v.status == 0) {
-            o.count = (int32_t)v.counted + d->targets[B.target[r0 + i]].count_bias;
+            o.count = (int32_t)v.counted + target_of(d, r0 + i).count_bias;
             o.log_p = v.logp;
         }
     }
@@ -1061,7 +1054,7 @@ static void read_table(DetectState* d, SubBatch& S)
             const bool okv = std::isfinite(hs[0]) && hs[1] > 0.0 && std::isfinite(hs[2]) && hs[3] > 0.0 && std::isfinite(hs[3]);
             rc.status = okv ? COND_OK : COND_DEGENERATE;
         }
-        if (!S.nc) S.any_mod |= d->targets[B.target[r0 + i]].mod_model_id >= 0;
+        if (!S.nc) S.any_mod |= target_of(d, r0 + i).mod_model_id >= 0;
     }
     // scan: any candidate may win
     for (int c = 0; c < S.nc; ++c) S.any_mod |= d->targets[d->scan_cand[(size_t)c]].mod_model_id >= 0;
@@ -1106,10 +1099,12 @@ static int reserve_buffers(strq_ctx* c, DetectState* d, SubBatch& S)
         STRQ_HIP(c, hipMemsetAsync(d->hrange.p, 0, (size_t)nr * 16, st));
         S.d_range = d->hrange.as<uint32_t>();
     }
-    const size_t idx_ints = (size_t)nr * 5;        // task_of (2 per read), trim (2 per read), vit_slot
-    STRQ_HIP(c, d->idx.reserve(idx_ints * 4 + (size_t)nr * 8 + 64));
-    S.d_task_of = d->idx.as<int32_t>(); S.d_trim = S.d_task_of + 2 * (size_t)nr; S.d_slot = S.d_trim + 2 * (size_t)nr;
-    S.d_model_of = reinterpret_cast<const VitModel**>(d->idx.as<char>() + ((idx_ints * 4 + 15) & ~(size_t)15));
+    Carve lay;
+    const size_t o_task_of = lay.add<int32_t>(2 * (size_t)nr), o_trim = lay.add<int32_t>(2 * (size_t)nr), o_slot = lay.add<int32_t>((size_t)nr),
+                 o_model_of = lay.add<const VitModel*>((size_t)nr);
+    STRQ_HIP(c, d->idx.reserve(lay.total() + 64));
+    S.d_task_of = Carve::at<int32_t>(d->idx.p, o_task_of); S.d_trim = Carve::at<int32_t>(d->idx.p, o_trim); S.d_slot = Carve::at<int32_t>(d->idx.p, o_slot);
+    S.d_model_of = Carve::at<const VitModel*>(d->idx.p, o_model_of);
     return STRQ_OK;
 }
 
@@ -1117,13 +1112,12 @@ static int reserve_buffers(strq_ctx* c, DetectState* d, SubBatch& S)
 // with one shape share a launch); finalize_kernel writes the task of read i to position vit_slot[i].
 static int plan_viterbi(strq_ctx* c, DetectState* d, SubBatch& S)
 {
-    const Batch& B = d->batch;
     DetectState::Slot& sl = *S.sl;
     const int nr = S.nr;
     std::vector<GroupItem> items(nr);
     std::vector<const VitModel*> model_of(nr);
     for (int i = 0; i < nr; ++i) {
-        HostModel* hm = c->models[d->targets[B.target[S.r0 + i]].model_id];
+        HostModel* hm = flank_model(c, d, S.r0 + i);
         model_of[i] = hm->dev;
         const int shape = vit_shape_for(hm->h, S.any_mod ? 2 : 0);
         if (shape < 0) { c->err = "model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
@@ -1246,19 +1240,19 @@ static int finalize_part(strq_ctx* c, DetectState* d, const SubBatch& S, int i0,
 static int scan_reserve(strq_ctx* c, DetectState* d, SubBatch& S)
 {
     const size_t nr = (size_t)S.nr, nc = (size_t)S.nc;
-    STRQ_HIP(c, d->scan_idx.reserve((2 * nc * nr + 2 * nc) * 4 + 64));
-    S.d_scan_task_of = d->scan_idx.as<int32_t>(); S.d_scan_trim = S.d_scan_task_of + 2 * nc * nr;
     const size_t n_sc = 2 * nc * nr;
-    S.scan_out_bytes = n_sc * 8 + n_sc * 4 + nr * 4;
+    Carve il;
+    const size_t o_task_of = il.add<int32_t>(n_sc), o_trim = il.add<int32_t>(2 * nc);
+    STRQ_HIP(c, d->scan_idx.reserve(il.total() + 64));
+    S.d_scan_task_of = Carve::at<int32_t>(d->scan_idx.p, o_task_of); S.d_scan_trim = Carve::at<int32_t>(d->scan_idx.p, o_trim);
+    // one layout for the outputs on the device and their pinned mirror (resolve_winners copies the block)
+    Carve ol;
+    const size_t o_scores = ol.add<double>(n_sc), o_best = ol.add<float>(n_sc), o_winner = ol.add<int32_t>(nr);
+    S.scan_out_bytes = ol.total();
     STRQ_HIP(c, d->scan_out.reserve(S.scan_out_bytes + 64));
-    S.d_scores = d->scan_out.as<double>(); S.d_best = reinterpret_cast<float*>(S.d_scores + n_sc); S.d_winner = reinterpret_cast<int32_t*>(S.d_best + n_sc);
-    if (S.scan_out_bytes > d->scan_pin_cap) {
-        if (d->scan_pin) { STRQ_HIP(c, hipHostFree(d->scan_pin)); d->scan_pin = nullptr; d->scan_pin_cap = 0; }
-        STRQ_HIP(c, hipHostMalloc(&d->scan_pin, S.scan_out_bytes + S.scan_out_bytes / 8, hipHostMallocDefault));
-        d->scan_pin_cap = S.scan_out_bytes + S.scan_out_bytes / 8;
-    }
-    S.h_scores = static_cast<const double*>(d->scan_pin); S.h_best = reinterpret_cast<const float*>(S.h_scores + n_sc);
-    S.h_winner = reinterpret_cast<const int32_t*>(S.h_best + n_sc);
+    STRQ_HIP(c, d->scan_pin.reserve(S.scan_out_bytes));
+    S.d_scores = Carve::at<double>(d->scan_out.p, o_scores); S.d_best = Carve::at<float>(d->scan_out.p, o_best); S.d_winner = Carve::at<int32_t>(d->scan_out.p, o_winner);
+    S.h_scores = Carve::at<double>(d->scan_pin.p, o_scores); S.h_best = Carve::at<float>(d->scan_pin.p, o_best); S.h_winner = Carve::at<int32_t>(d->scan_pin.p, o_winner);
     std::vector<int32_t> trim(2 * nc);
     for (size_t ci = 0; ci < nc; ++ci) {
         const Target& t = d->targets[d->scan_cand[ci]];
@@ -1292,7 +1286,7 @@ static int resolve_winners(strq_ctx* c, DetectState* d, SubBatch& S)
 {
     Batch& B = d->batch;
     hipStream_t st = c->stream;
-    STRQ_HIP(c, hipMemcpyAsync(d->scan_pin, d->scan_out.p, S.scan_out_bytes, hipMemcpyDeviceToHost, st));
+    STRQ_HIP(c, hipMemcpyAsync(d->scan_pin.p, d->scan_out.p, S.scan_out_bytes, hipMemcpyDeviceToHost, st));
     STRQ_HIP(c, hipStreamSynchronize(st));
     const size_t per = 2 * (size_t)S.nc;
     for (int i = 0; i < S.nr; ++i) {
@@ -1349,7 +1343,7 @@ static void plan_next_overlap(strq_ctx* c, DetectState* d, const SubBatch& S)
             }
             continue;
         }
-        const Target& t = d->targets[d->batch.target[S.r0 + i]];
+        const Target& t = target_of(d, S.r0 + i);
         c->score_fracs.push_back(h_geom[i].best_prefix / ((float)t.prefix_ext.size() * c->ap.dist_offset));
         c->score_fracs.push_back(h_geom[i].best_suffix / ((float)t.suffix_ext.size() * c->ap.dist_offset));
         sum_n += S.rc[i].n;
@@ -1944,10 +1938,9 @@ int strq_batch_upload_part(strq_ctx* c, int64_t total_reads, int64_t total_sampl
             STRQ_HIP(c, bigger.reserve(need + need / 2));
             if (base > 0) {
                 const hipError_t e = hipMemcpy(bigger.p, B.raw.p, (size_t)base * 2, hipMemcpyDeviceToDevice);
-                if (e != hipSuccess) { bigger.release(); c->err = std::string("hipMemcpy (growing the resident batch): ") + hipGetErrorString(e); return STRQ_ERR_DEVICE; }
+                if (e != hipSuccess) { c->err = std::string("hipMemcpy (growing the resident batch): ") + hipGetErrorString(e); return STRQ_ERR_DEVICE; }
             }
-            B.raw.release();
-            B.raw = bigger;
+            B.raw.swap(bigger);          // the old block goes with `bigger`
         }
     }
     for (int64_t i = first_read + n_reads; i < total_reads; ++i) B.off[(size_t)i + 1] = B.off[(size_t)(first_read + n_reads)];      // reads not yet uploaded: empty

@@ -9,11 +9,28 @@
 #include <string>
 #include "../../include/strique_hip.h"
 #include "strq_ctx.h"
+#include "detect_plan.h"
 #include "viterbi_kernels.h"
 
 using namespace strq;
 
 namespace strq {
+
+// A model image -- arrays and, behind them, the struct that points to them, in one device blob: put() carves the region of an array
+// and keeps where its bytes come from, host() is the block as it goes up (the sources as they are then: the struct with its pointers set).
+struct Image {
+    Carve lay;
+    struct Part { const void* src; size_t bytes, off; };
+    std::vector<Part> parts;
+    template <class T> size_t put(const T* src, size_t n) { parts.push_back({src, n * sizeof(T), lay.add<T>(n)}); return parts.back().off; }
+    template <class T> size_t put(const std::vector<T>& v) { return put(v.data(), v.size()); }
+    std::vector<char> host() const
+    {
+        std::vector<char> h(lay.total(), 0);
+        for (const Part& pt : parts) if (pt.bytes) std::memcpy(&h[pt.off], pt.src, pt.bytes);
+        return h;
+    }
+};
 
 // What every builder relies on: in_ptr monotone from 0, sources in range, silent states in topological order, the in-edges
 // of a state sorted by ascending source (the order ties are broken in), emitting states Normal (1) or Uniform (2).
@@ -229,42 +246,25 @@ int build_vit_model(strq_ctx* c, int32_t n_states, int32_t silent_start, int32_t
     if (count_inc) std::copy(count_inc, count_inc + n_states, inc.begin());
     std::vector<int32_t> tagv((size_t)n_states + 1, 0);
     if (state_tag) std::copy(state_tag, state_tag + n_states, tagv.begin());
-    // one device blob
-    struct Part { const void* p; size_t bytes; size_t off; };
-    std::vector<Part> parts = {
-        {lp.data(), lp.size() * 8, 0}, {a.data(), a.size() * 8, 0}, {b.data(), b.size() * 8, 0}, {cc.data(), cc.size() * 8, 0},
-        {src.data(), src.size() * 4, 0}, {kind.data(), kind.size() * 4, 0}, {inc.data(), inc.size() * 4, 0},
-        {own_e.data(), own_e.size() * 4, 0}, {own_s.data(), own_s.size() * 4, 0},
-        {chain_src_v.data(), chain_src_v.size() * 4, 0}, {chain_lp_v.data(), chain_lp_v.size() * 8, 0},
-        {tagv.data(), tagv.size() * 4, 0}, {cell_state.data(), cell_state.size() * 4, 0}};
-    size_t total = 0;
-    for (auto& pt : parts) { pt.off = total; total += (pt.bytes + 15) & ~(size_t)15; }
-    const size_t o_m = total; total += sizeof(VitModel);
-    if (hm->blob.reserve(total) != hipSuccess) { delete hm; c->err = "out of device memory"; return STRQ_ERR_NOMEM; }
-    char* d = hm->blob.as<char>();
-    m.edge_logp = reinterpret_cast<const double*>(d + parts[0].off);
-    m.emis_a = reinterpret_cast<const double*>(d + parts[1].off);
-    m.emis_b = reinterpret_cast<const double*>(d + parts[2].off);
-    m.emis_c = reinterpret_cast<const double*>(d + parts[3].off);
-    m.edge_src = reinterpret_cast<const int32_t*>(d + parts[4].off);
-    m.emis_kind = reinterpret_cast<const int32_t*>(d + parts[5].off);
-    m.count_inc = reinterpret_cast<const int32_t*>(d + parts[6].off);
-    m.own_e = reinterpret_cast<const int32_t*>(d + parts[7].off);
-    m.own_s = reinterpret_cast<const int32_t*>(d + parts[8].off);
-    m.chain_src = reinterpret_cast<const int32_t*>(d + parts[9].off);
-    m.chain_logp = reinterpret_cast<const double*>(d + parts[10].off);
-    m.state_tag = reinterpret_cast<const int32_t*>(d + parts[11].off);
+    // one device blob: the arrays, the VitModel that points to them behind
+    Image im;
+    const size_t o_lp = im.put(lp), o_a = im.put(a), o_b = im.put(b), o_c = im.put(cc), o_src = im.put(src), o_kind = im.put(kind), o_inc = im.put(inc),
+                 o_own_e = im.put(own_e), o_own_s = im.put(own_s), o_chain_src = im.put(chain_src_v), o_chain_lp = im.put(chain_lp_v),
+                 o_tag = im.put(tagv), o_cell = im.put(cell_state), o_m = im.put(&m, 1);
+    if (hm->blob.reserve(im.lay.total()) != hipSuccess) { delete hm; c->err = "out of device memory"; return STRQ_ERR_NOMEM; }
+    void* d = hm->blob.p;
+    m.edge_logp = Carve::at<const double>(d, o_lp); m.emis_a = Carve::at<const double>(d, o_a); m.emis_b = Carve::at<const double>(d, o_b);
+    m.emis_c = Carve::at<const double>(d, o_c); m.edge_src = Carve::at<const int32_t>(d, o_src); m.emis_kind = Carve::at<const int32_t>(d, o_kind);
+    m.count_inc = Carve::at<const int32_t>(d, o_inc); m.own_e = Carve::at<const int32_t>(d, o_own_e); m.own_s = Carve::at<const int32_t>(d, o_own_s);
+    m.chain_src = Carve::at<const int32_t>(d, o_chain_src); m.chain_logp = Carve::at<const double>(d, o_chain_lp);
+    m.state_tag = Carve::at<const int32_t>(d, o_tag); m.cell_state = Carve::at<const int32_t>(d, o_cell);
+    hm->dev = Carve::at<const VitModel>(d, o_m);
     m.rec_state = -1;
     for (int e = in_ptr[end]; e < in_ptr[end + 1]; ++e) if (in_src[e] < ne && state_tag && state_tag[in_src[e]] == 2) m.rec_state = in_src[e];
     m.silent_counted = 0;
     for (int s2 = ne; s2 < n_states; ++s2) if (count_inc && count_inc[s2] != 0) m.silent_counted = 1;
     vit_unit_states(m, n_states, ne, count_inc);
-    m.cell_state = reinterpret_cast<const int32_t*>(d + parts[12].off);
-    hm->dev = reinterpret_cast<const VitModel*>(d + o_m);
-    std::vector<char> host(total, 0);
-    for (auto& pt : parts) std::memcpy(&host[pt.off], pt.p, pt.bytes);
-    std::memcpy(&host[o_m], &m, sizeof(VitModel));
-    if (hipMemcpy(d, host.data(), total, hipMemcpyHostToDevice) != hipSuccess) { delete hm; c->err = "model upload failed"; return STRQ_ERR_DEVICE; }
+    if (hipMemcpy(d, im.host().data(), im.lay.total(), hipMemcpyHostToDevice) != hipSuccess) { delete hm; c->err = "model upload failed"; return STRQ_ERR_DEVICE; }
     *out = hm;
     return STRQ_OK;
 }
@@ -302,33 +302,18 @@ int build_vit_model_csr(strq_ctx* c, int32_t n_states, int32_t silent_start, int
     if (count_inc) std::copy(count_inc, count_inc + n_states, inc.begin());
     if (state_tag) std::copy(state_tag, state_tag + n_states, tagv.begin());
     const int n_edges = in_ptr[n_states];
-    struct Part { const void* p; size_t bytes; size_t off; };
-    std::vector<Part> parts = {
-        {in_logp, (size_t)n_edges * 8, 0}, {emis_a, (size_t)ne * 8, 0}, {emis_b, (size_t)ne * 8, 0}, {emis_c, (size_t)ne * 8, 0},
-        {in_ptr, ((size_t)n_states + 1) * 4, 0}, {in_src, (size_t)n_edges * 4, 0}, {emis_kind, (size_t)ne * 4, 0},
-        {inc.data(), inc.size() * 4, 0}, {tagv.data(), tagv.size() * 4, 0},
-        {level_ptr.data(), level_ptr.size() * 4, 0}, {level_state.data(), level_state.size() * 4, 0}};
-    size_t total = 0;
-    for (auto& pt : parts) { pt.off = total; total += (pt.bytes + 15) & ~(size_t)15; }
-    const size_t o_m = total; total += sizeof(VitModel);
-    if (hm->blob.reserve(total) != hipSuccess) { delete hm; c->err = "out of device memory"; return STRQ_ERR_NOMEM; }
-    char* d = hm->blob.as<char>();
-    m.csr_in_logp = reinterpret_cast<const double*>(d + parts[0].off);
-    m.csr_a = reinterpret_cast<const double*>(d + parts[1].off);
-    m.csr_b = reinterpret_cast<const double*>(d + parts[2].off);
-    m.csr_c = reinterpret_cast<const double*>(d + parts[3].off);
-    m.csr_in_ptr = reinterpret_cast<const int32_t*>(d + parts[4].off);
-    m.csr_in_src = reinterpret_cast<const int32_t*>(d + parts[5].off);
-    m.csr_kind = reinterpret_cast<const int32_t*>(d + parts[6].off);
-    m.count_inc = reinterpret_cast<const int32_t*>(d + parts[7].off);
-    m.state_tag = reinterpret_cast<const int32_t*>(d + parts[8].off);
-    m.csr_level_ptr = reinterpret_cast<const int32_t*>(d + parts[9].off);
-    m.csr_level_state = reinterpret_cast<const int32_t*>(d + parts[10].off);
-    hm->dev = reinterpret_cast<const VitModel*>(d + o_m);
-    std::vector<char> host(total, 0);
-    for (auto& pt : parts) if (pt.bytes) std::memcpy(&host[pt.off], pt.p, pt.bytes);
-    std::memcpy(&host[o_m], &m, sizeof(VitModel));
-    if (hipMemcpy(d, host.data(), total, hipMemcpyHostToDevice) != hipSuccess) { delete hm; c->err = "model upload failed"; return STRQ_ERR_DEVICE; }
+    Image im;
+    const size_t o_lp = im.put(in_logp, (size_t)n_edges), o_a = im.put(emis_a, (size_t)ne), o_b = im.put(emis_b, (size_t)ne), o_c = im.put(emis_c, (size_t)ne),
+                 o_ptr = im.put(in_ptr, (size_t)n_states + 1), o_src = im.put(in_src, (size_t)n_edges), o_kind = im.put(emis_kind, (size_t)ne),
+                 o_inc = im.put(inc), o_tag = im.put(tagv), o_level_ptr = im.put(level_ptr), o_level_state = im.put(level_state), o_m = im.put(&m, 1);
+    if (hm->blob.reserve(im.lay.total()) != hipSuccess) { delete hm; c->err = "out of device memory"; return STRQ_ERR_NOMEM; }
+    void* d = hm->blob.p;
+    m.csr_in_logp = Carve::at<const double>(d, o_lp); m.csr_a = Carve::at<const double>(d, o_a); m.csr_b = Carve::at<const double>(d, o_b);
+    m.csr_c = Carve::at<const double>(d, o_c); m.csr_in_ptr = Carve::at<const int32_t>(d, o_ptr); m.csr_in_src = Carve::at<const int32_t>(d, o_src);
+    m.csr_kind = Carve::at<const int32_t>(d, o_kind); m.count_inc = Carve::at<const int32_t>(d, o_inc); m.state_tag = Carve::at<const int32_t>(d, o_tag);
+    m.csr_level_ptr = Carve::at<const int32_t>(d, o_level_ptr); m.csr_level_state = Carve::at<const int32_t>(d, o_level_state);
+    hm->dev = Carve::at<const VitModel>(d, o_m);
+    if (hipMemcpy(d, im.host().data(), im.lay.total(), hipMemcpyHostToDevice) != hipSuccess) { delete hm; c->err = "model upload failed"; return STRQ_ERR_DEVICE; }
     *out = hm;
     return STRQ_OK;
 }
@@ -524,24 +509,17 @@ int build_vit_g2(strq_ctx* c, HostModel* hm, const int32_t* kind_hint, const int
         VitG2& G = L.G;
         std::vector<double>& lp = L.lp; std::vector<double>& em = L.em;
         std::vector<int32_t>& knd = L.knd; std::vector<int32_t>& own = L.own; std::vector<int32_t>& inc = L.inc; std::vector<int32_t>& tag = L.tag;
-        struct Part { const void* p; size_t bytes; size_t off; };
-        std::vector<Part> parts = {{lp.data(), lp.size() * 8, 0}, {em.data(), em.size() * 8, 0}, {knd.data(), knd.size() * 4, 0},
-                                   {own.data(), own.size() * 4, 0}, {inc.data(), inc.size() * 4, 0}, {tag.data(), tag.size() * 4, 0},
-                                   {L.mark_add.data(), L.mark_add.size() * 8, 0}};
-        size_t total = 0;
-        for (auto& pt : parts) { pt.off = total; total += (pt.bytes + 15) & ~(size_t)15; }
-        const size_t o_g = total; total += sizeof(VitG2);
-        if (hm->g2_blob.reserve(total) != hipSuccess) { c->err = "out of device memory"; return STRQ_ERR_NOMEM; }
-        char* d = hm->g2_blob.as<char>();
-        G.lp = reinterpret_cast<const double*>(d + parts[0].off); G.em = reinterpret_cast<const double*>(d + parts[1].off);
-        G.kind = reinterpret_cast<const int32_t*>(d + parts[2].off); G.own = reinterpret_cast<const int32_t*>(d + parts[3].off);
-        G.inc = reinterpret_cast<const int32_t*>(d + parts[4].off); G.tag = reinterpret_cast<const int32_t*>(d + parts[5].off);
-        G.mark_add = L.mark_add.empty() ? nullptr : reinterpret_cast<const uint64_t*>(d + parts[6].off);
-        std::vector<char> host(total, 0);
-        for (auto& pt : parts) std::memcpy(&host[pt.off], pt.p, pt.bytes);
-        std::memcpy(&host[o_g], &G, sizeof(VitG2));
-        if (hipMemcpy(d, host.data(), total, hipMemcpyHostToDevice) != hipSuccess) { c->err = "model upload failed"; return STRQ_ERR_DEVICE; }
-        hm->h.g2 = reinterpret_cast<const VitG2*>(d + o_g); hm->h.g2_odd = L.odd; hm->h.g2_mark = L.mark_add.empty() ? 0 : 1;
+        Image im;
+        const size_t o_lp = im.put(lp), o_em = im.put(em), o_kind = im.put(knd), o_own = im.put(own), o_inc = im.put(inc), o_tag = im.put(tag),
+                     o_mark = im.put(L.mark_add), o_g = im.put(&G, 1);
+        if (hm->g2_blob.reserve(im.lay.total()) != hipSuccess) { c->err = "out of device memory"; return STRQ_ERR_NOMEM; }
+        void* d = hm->g2_blob.p;
+        G.lp = Carve::at<const double>(d, o_lp); G.em = Carve::at<const double>(d, o_em);
+        G.kind = Carve::at<const int32_t>(d, o_kind); G.own = Carve::at<const int32_t>(d, o_own);
+        G.inc = Carve::at<const int32_t>(d, o_inc); G.tag = Carve::at<const int32_t>(d, o_tag);
+        G.mark_add = L.mark_add.empty() ? nullptr : Carve::at<const uint64_t>(d, o_mark);
+        if (hipMemcpy(d, im.host().data(), im.lay.total(), hipMemcpyHostToDevice) != hipSuccess) { c->err = "model upload failed"; return STRQ_ERR_DEVICE; }
+        hm->h.g2 = Carve::at<const VitG2>(d, o_g); hm->h.g2_odd = L.odd; hm->h.g2_mark = L.mark_add.empty() ? 0 : 1;
         // unit decodes: the two counted states are the broadcast sources, one in each of their slots (record index = the slot's)
         {
             int hits[2] = {0, 0}; bool other = false;
@@ -573,17 +551,14 @@ int forward_model(strq_ctx* c, HostModel* hm)
     std::vector<double> ew(hm->edge_csr.size(), 0.0), cw(hm->chain_csr.size(), 0.0);
     for (size_t i = 0; i < ew.size(); ++i) if (hm->edge_csr[i] >= 0) ew[i] = std::exp(lp[(size_t)hm->edge_csr[i]]);
     for (size_t i = 0; i < cw.size(); ++i) if (hm->chain_csr[i] >= 0) cw[i] = std::exp(lp[(size_t)hm->chain_csr[i]]);
-    const size_t o_c = (ew.size() * 8 + 15) & ~(size_t)15, o_m = o_c + ((cw.size() * 8 + 15) & ~(size_t)15), total = o_m + sizeof(FwdModel);
-    if (hm->fwd_blob.reserve(total) != hipSuccess) { c->err = "out of device memory"; return STRQ_ERR_NOMEM; }
-    char* d = hm->fwd_blob.as<char>();
     FwdModel F; std::memset(&F, 0, sizeof(F));
-    F.vit = hm->dev; F.edge_w = reinterpret_cast<const double*>(d); F.chain_w = reinterpret_cast<const double*>(d + o_c); F.n_stages = hm->fwd_stages;
-    std::vector<char> host(total, 0);
-    std::memcpy(&host[0], ew.data(), ew.size() * 8);
-    if (!cw.empty()) std::memcpy(&host[o_c], cw.data(), cw.size() * 8);
-    std::memcpy(&host[o_m], &F, sizeof(F));
-    if (hipMemcpy(d, host.data(), total, hipMemcpyHostToDevice) != hipSuccess) { c->err = "model upload failed"; return STRQ_ERR_DEVICE; }
-    hm->fwd_dev = reinterpret_cast<const FwdModel*>(d + o_m);
+    Image im;
+    const size_t o_e = im.put(ew), o_c = im.put(cw), o_m = im.put(&F, 1);
+    if (hm->fwd_blob.reserve(im.lay.total()) != hipSuccess) { c->err = "out of device memory"; return STRQ_ERR_NOMEM; }
+    void* d = hm->fwd_blob.p;
+    F.vit = hm->dev; F.edge_w = Carve::at<const double>(d, o_e); F.chain_w = Carve::at<const double>(d, o_c); F.n_stages = hm->fwd_stages;
+    if (hipMemcpy(d, im.host().data(), im.lay.total(), hipMemcpyHostToDevice) != hipSuccess) { c->err = "model upload failed"; return STRQ_ERR_DEVICE; }
+    hm->fwd_dev = Carve::at<const FwdModel>(d, o_m);
     return STRQ_OK;
 }
 
@@ -668,10 +643,11 @@ int strq_viterbi_batch(strq_ctx* c, int32_t model_id, int64_t n_seq, const doubl
     const int n = hm->h.n_states;
     STRQ_HIP(c, c->vit_x.reserve((size_t)tot * 8 + 64));
     STRQ_HIP(c, hipMemcpyAsync(c->vit_x.p, x, (size_t)tot * 8, hipMemcpyHostToDevice, st));
-    STRQ_HIP(c, c->vit_tasks.reserve((size_t)n_seq * (sizeof(VitTask) + sizeof(VitResult) + 8)));
-    VitTask* d_tasks = c->vit_tasks.as<VitTask>();
-    VitResult* d_res = reinterpret_cast<VitResult*>(d_tasks + n_seq);
-    int32_t** d_paths = reinterpret_cast<int32_t**>(d_res + n_seq);
+    Carve lay;
+    const size_t o_tasks = lay.add<VitTask>((size_t)n_seq), o_res = lay.add<VitResult>((size_t)n_seq), o_paths = lay.add<int32_t*>((size_t)n_seq);
+    STRQ_HIP(c, c->vit_tasks.reserve(lay.total()));
+    VitTask* d_tasks = Carve::at<VitTask>(c->vit_tasks.p, o_tasks); VitResult* d_res = Carve::at<VitResult>(c->vit_tasks.p, o_res);
+    int32_t** d_paths = Carve::at<int32_t*>(c->vit_tasks.p, o_paths);
     size_t bp_cells = 0;
     if (paths) { for (int64_t i = 0; i < n_seq; ++i) bp_cells += (size_t)(x_off[i + 1] - x_off[i] + 1) * n; }
     if (paths) { STRQ_HIP(c, c->vit_bp.reserve(bp_cells * 2 + 64)); STRQ_HIP(c, c->vit_path.reserve((size_t)tot * 4 + 64)); }
@@ -690,8 +666,7 @@ int strq_viterbi_batch(strq_ctx* c, int32_t model_id, int64_t n_seq, const doubl
     }
     STRQ_HIP(c, hipMemcpyAsync(d_tasks, tasks.data(), (size_t)n_seq * sizeof(VitTask), hipMemcpyHostToDevice, st));
     if (paths) STRQ_HIP(c, hipMemcpyAsync(d_paths, hp.data(), (size_t)n_seq * 8, hipMemcpyHostToDevice, st));
-    STRQ_HIP(c, c->queue.reserve(1024));
-    STRQ_HIP(c, hipMemsetAsync(c->queue.p, 0, 1024, st));
+    if (const int qrc = reset_queue_heads(c, st)) return qrc;
     STRQ_HIP(c, hipEventRecord(c->ev[0], st));
     const int shape = vit_shape_for(hm->h, paths ? 1 : 0);
     if (shape < 0) { c->err = "model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
@@ -747,12 +722,13 @@ int strq_forward_batch(strq_ctx* c, int32_t model_id, int64_t n_seq, const doubl
     hipStream_t st = c->stream;
     STRQ_HIP(c, c->vit_x.reserve((size_t)tot * 8 + 64));
     if (tot) STRQ_HIP(c, hipMemcpyAsync(c->vit_x.p, x, (size_t)tot * 8, hipMemcpyHostToDevice, st));
-    STRQ_HIP(c, c->vit_tasks.reserve((size_t)n_seq * (sizeof(VitTask) + sizeof(FwdResult) + 8 + 8 + 4) + 64));
-    VitTask* d_tasks = c->vit_tasks.as<VitTask>();
-    FwdResult* d_res = reinterpret_cast<FwdResult*>(d_tasks + n_seq);
-    const FwdModel** d_fm = reinterpret_cast<const FwdModel**>(d_res + n_seq);
-    int64_t* d_c0 = reinterpret_cast<int64_t*>(d_fm + n_seq);
-    int* d_order = reinterpret_cast<int*>(d_c0 + n_seq);
+    Carve lay;
+    const size_t o_tasks = lay.add<VitTask>((size_t)n_seq), o_res = lay.add<FwdResult>((size_t)n_seq), o_fm = lay.add<const FwdModel*>((size_t)n_seq),
+                 o_c0 = lay.add<int64_t>((size_t)n_seq), o_order = lay.add<int>((size_t)n_seq);
+    STRQ_HIP(c, c->vit_tasks.reserve(lay.total() + 64));
+    void* tb = c->vit_tasks.p;
+    VitTask* d_tasks = Carve::at<VitTask>(tb, o_tasks); FwdResult* d_res = Carve::at<FwdResult>(tb, o_res); const FwdModel** d_fm = Carve::at<const FwdModel*>(tb, o_fm);
+    int64_t* d_c0 = Carve::at<int64_t>(tb, o_c0); int* d_order = Carve::at<int>(tb, o_order);
     std::vector<VitTask> tasks(n_seq); std::vector<const FwdModel*> fms((size_t)n_seq, hm->fwd_dev); std::vector<int64_t> c0v((size_t)n_seq, 0);
     for (int64_t i = 0; i < n_seq; ++i) {
         VitTask& t = tasks[i];
@@ -763,8 +739,7 @@ int strq_forward_batch(strq_ctx* c, int32_t model_id, int64_t n_seq, const doubl
     STRQ_HIP(c, hipMemcpyAsync(d_tasks, tasks.data(), (size_t)n_seq * sizeof(VitTask), hipMemcpyHostToDevice, st));
     STRQ_HIP(c, hipMemcpyAsync(d_fm, fms.data(), (size_t)n_seq * 8, hipMemcpyHostToDevice, st));
     STRQ_HIP(c, hipMemcpyAsync(d_c0, c0v.data(), (size_t)n_seq * 8, hipMemcpyHostToDevice, st));
-    STRQ_HIP(c, c->queue.reserve(1024));
-    STRQ_HIP(c, hipMemsetAsync(c->queue.p, 0, 1024, st));
+    if (const int qrc = reset_queue_heads(c, st)) return qrc;
     if (launch_vit_sort(st, d_tasks, (int)n_seq, d_order)) { c->err = "forward pass: sort launch failed"; return STRQ_ERR_DEVICE; }
     int every = 1;
     if (const char* e = strq::opt("STRQ_FWD_RESCALE_EVERY")) { const int v = atoi(e); if (v >= 1) every = v; }

@@ -114,6 +114,16 @@ def host_stats(signals, offsets, want_raw=False):
     return out
 
 
+def live_allocations():
+    """strq_debug_live_allocations: (device blocks, pinned host blocks) the library holds in this process right now, over all
+    contexts.  No context and no device involved."""
+    out = np.zeros(2, np.int64)
+    rc = load_library().strq_debug_live_allocations(_ptr(out))
+    if rc != STRQ_OK:
+        raise StriqueHipError(rc, "strq_debug_live_allocations: bad argument")
+    return int(out[0]), int(out[1])
+
+
 class Context(object):
     """One HIP context / stream / workspace on one GPU (strq_ctx)."""
 
