@@ -36,30 +36,11 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "forward_kernels.h"
+#include "hmm_wave.h"
 
 namespace strq {
 
 #define FWD_WAVES 4
-#define FWD_FENCE() __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront")
-
-static __device__ __forceinline__ int fwd_next_task(int* queue, int lane)
-{
-    __builtin_amdgcn_wave_barrier();
-    int ti = 0;
-    if (lane == 0) ti = atomicAdd(queue, 1);
-    __builtin_amdgcn_wave_barrier();
-    ti = __builtin_amdgcn_readfirstlane(ti);
-    __builtin_amdgcn_wave_barrier();
-    return ti;
-}
-
-static __device__ __forceinline__ double fwd_readlane(double v, int l)
-{
-    const uint64_t u = __builtin_bit_cast(uint64_t, v);
-    const uint32_t lo = __builtin_amdgcn_readlane((int)(uint32_t)u, l);
-    const uint32_t hi = __builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), l);
-    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
-}
 
 // lane l receives lane l - N of its row of 16; the first N lanes of a row keep `old`
 template <int N>
@@ -68,14 +49,6 @@ static __device__ __forceinline__ double fwd_row_shr(double old, double v)
     const uint64_t u = __builtin_bit_cast(uint64_t, v), o = __builtin_bit_cast(uint64_t, old);
     const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)o, (int)(uint32_t)u, 0x110 + N, 0xF, 0xF, false);
     const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)(o >> 32), (int)(uint32_t)(u >> 32), 0x110 + N, 0xF, 0xF, false);
-    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
-}
-// wave_shr:1 -- lane l receives lane l - 1, lane 0 receives 0.0
-static __device__ __forceinline__ double fwd_wave_shr1(double v)
-{
-    const uint64_t u = __builtin_bit_cast(uint64_t, v);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)u, 0x138, 0xF, 0xF, true);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u >> 32), 0x138, 0xF, 0xF, true);
     return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
 }
 // largest value of the wave, in every lane: butterflies inside the rows of 16 (quad_perm, row_half_mirror, row_mirror), the four
@@ -117,7 +90,7 @@ forward_kernel(const VitTask* __restrict__ tasks, const FwdModel* const* __restr
     int ssrc[SPL][DS]; double sw[SPL][DS], cw[SPL];
 
     for (;;) {
-        const int tq = fwd_next_task(queue, lane);
+        const int tq = wave_next_task(queue, lane);
         if (tq >= n_tasks) break;
         const int ti = order ? order[tq] : tq;        // longest observation windows first
         const VitTask tk = tasks[ti];
@@ -162,7 +135,7 @@ forward_kernel(const VitTask* __restrict__ tasks, const FwdModel* const* __restr
         const int64_t T = tk.T;
         const double c0 = (double)(c0s ? c0s[ti] : 0);
         for (int i = lane; i < 2 * BUF; i += 64) vbase[i] = 0.0;
-        FWD_FENCE();
+        wave_fence();
         (void)NP;
 
         // silent states of the vector at `X` (its emitting cells are final); `pin`: the start state holds the whole mass (t = 0)
@@ -203,23 +176,23 @@ forward_kernel(const VitTask* __restrict__ tasks, const FwdModel* const* __restr
                 double ylast[3];
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
-                    const double c1 = fwd_readlane(B[k], 15);
-                    const double c2 = fwd_readlane(B[k], 31) + fwd_readlane(A, 31) * c1;
-                    const double c3 = fwd_readlane(B[k], 47) + fwd_readlane(A, 47) * c2;
+                    const double c1 = readlane_f64(B[k], 15);
+                    const double c2 = readlane_f64(B[k], 31) + readlane_f64(A, 31) * c1;
+                    const double c3 = readlane_f64(B[k], 47) + readlane_f64(A, 47) * c2;
                     const double cin = row == 0 ? 0.0 : (row == 1 ? c1 : (row == 2 ? c2 : c3));
                     ylast[k] = B[k] + A * cin;
                 }
-                FWD_FENCE();          // every lane has read the vector before anyone overwrites its silent cells
+                wave_fence();          // every lane has read the vector before anyone overwrites its silent cells
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
-                    double y = fwd_wave_shr1(ylast[k]);
+                    double y = dpp_shr1_f64(ylast[k]);
 #pragma unroll
                     for (int s = 0; s < SPL; ++s) {
                         y = own[s][k] + cw[s] * y;
                         if (has_s[s]) X[k * PL + scell[s]] = y;
                     }
                 }
-                FWD_FENCE();
+                wave_fence();
             }
         };
 
@@ -229,26 +202,15 @@ forward_kernel(const VitTask* __restrict__ tasks, const FwdModel* const* __restr
         int since = 0;
         double xchunk = 0.0;
         for (int64_t t0 = 0; t0 < T; t0 += 64) {
-            {   // observations t0 .. t0 + 63, one per lane: the window exactly as the Viterbi kernels see it
+            {   // observations t0 .. t0 + 63, one per lane: the window as the Viterbi kernels read it
                 const int64_t idx = t0 + lane;
                 double xv = 0.0;
-                if (idx < T) {
-                    if (tk.src_kind == VIT_SRC_F64) xv = reinterpret_cast<const double*>(tk.sig)[idx];
-                    else {
-                        double sv = tk.src_kind == VIT_SRC_I16_AFFINE ? (double)reinterpret_cast<const int16_t*>(tk.sig)[idx]
-                                                                      : reinterpret_cast<const double*>(tk.sig)[idx];
-                        sv = (sv - tk.c1) / tk.h1;
-                        sv = sv * tk.h2 + tk.c2;
-                        sv = sv < tk.lo ? tk.lo : sv;          // np.clip
-                        sv = sv > tk.hi ? tk.hi : sv;
-                        xv = sv;
-                    }
-                }
+                if (idx < T) xv = vit_observation(tk, idx);
                 xchunk = xv;
             }
             const int send = (int)((T - t0) < 64 ? (T - t0) : 64);
             for (int s0 = 0; s0 < send; ++s0) {
-                const double x = fwd_readlane(xchunk, s0);
+                const double x = readlane_f64(xchunk, s0);
                 const int64_t t = t0 + s0;
                 const double* const RD = vbase + (t & 1) * BUF;
                 double* const WR = vbase + ((t + 1) & 1) * BUF;
@@ -288,7 +250,7 @@ forward_kernel(const VitTask* __restrict__ tasks, const FwdModel* const* __restr
 #pragma unroll
                 for (int s = 0; s < EPL; ++s)
                     if (has_e[s]) { WR[ecell[s]] = np_[s]; WR[PL + ecell[s]] = nr_[s]; WR[2 * PL + ecell[s]] = nq_[s]; }
-                FWD_FENCE();
+                wave_fence();
                 silent_phase(WR, false);
             }
         }
@@ -297,14 +259,16 @@ forward_kernel(const VitTask* __restrict__ tasks, const FwdModel* const* __restr
         res.p = FIN[m_end]; res.r = FIN[PL + m_end]; res.s = FIN[2 * PL + m_end];
         res.expo = expo; res.steps_rescaled = n_rescaled; res.pad_ = 0;
         if (lane == 0) results[ti] = res;
-        FWD_FENCE();
+        wave_fence();
     }
 }
 
-template <int EPL, int SPL, int DE, int DS>
+// instance F of VIT_FWD_SHAPES
+template <int F>
 static int fwd_launch_shape(hipStream_t stream, int max_cells, const VitTask* tasks, const FwdModel* const* models, const int64_t* c0,
                             FwdResult* results, int n_tasks, int* queue, int n_cu, const int* order, int rescale_every)
 {
+    constexpr int EPL = VIT_FWD_SHAPES[F].epl, SPL = VIT_FWD_SHAPES[F].spl, DE = VIT_FWD_SHAPES[F].de, DS = VIT_FWD_SHAPES[F].ds;
     if (max_cells > (EPL + SPL) * 64 + 1) return 2;
     const size_t lds = (size_t)FWD_WAVES * 2 * 3 * (size_t)max_cells * sizeof(double);
     if (lds > 160 * 1024) return 2;
@@ -316,18 +280,16 @@ static int fwd_launch_shape(hipStream_t stream, int max_cells, const VitTask* ta
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
-// one instance per family of lane layouts (viterbi_kernels.hip: vit_shape_base)
+// one instance per family of lane layouts: the `fwd` column of VIT_SHAPES
 int launch_forward(hipStream_t stream, int shape, int max_cells, const VitTask* tasks, const FwdModel* const* models,
                    const int64_t* c0, FwdResult* results, int n_tasks, int* queue, int n_cu, const int* order, int rescale_every)
 {
     if (n_tasks <= 0) return 0;
     if (rescale_every < 1) rescale_every = 1;
-    switch (shape & ~VIT_SHAPE_SS) {
-        case 0: case 5: case 7: return fwd_launch_shape<4, 2, 6, 3>(stream, max_cells, tasks, models, c0, results, n_tasks, queue, n_cu, order, rescale_every);
-        case 1: case 2: case 6: return fwd_launch_shape<2, 2, 8, 4>(stream, max_cells, tasks, models, c0, results, n_tasks, queue, n_cu, order, rescale_every);
-        case 3: case 4: return fwd_launch_shape<8, 4, 8, 8>(stream, max_cells, tasks, models, c0, results, n_tasks, queue, n_cu, order, rescale_every);
-        default: return 2;
-    }
+    if (vit_shape_family(shape) != VIT_FAMILY_LANE) return 2;
+    return vit_dispatch<(int)(sizeof(VIT_FWD_SHAPES) / sizeof(VIT_FWD_SHAPES[0]))>(VIT_SHAPES[shape & ~VIT_SHAPE_SS].fwd, [&](auto f) {
+        return fwd_launch_shape<decltype(f)::value>(stream, max_cells, tasks, models, c0, results, n_tasks, queue, n_cu, order, rescale_every);
+    });
 }
 
 }  // namespace strq

@@ -12,11 +12,9 @@
 #include <cmath>
 #include <cstring>
 #include "mod_llr_kernels.h"
-#include "viterbi_kernels.h"
+#include "hmm_wave.h"
 
 namespace strq {
-
-#define LLR_FENCE() __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront")
 
 // One thread per read: the chain of hub records, last unit first (record t = the e0 emission at observation t - 1).
 __global__ void __launch_bounds__(64) llr_hop_kernel(const LlrBoundTask* __restrict__ tasks, int n_tasks)
@@ -117,7 +115,7 @@ mod_llr_kernel(const LlrRead* __restrict__ reads, const int64_t* __restrict__ fi
             cur = m;
         }
         for (int i = li; i < 2 * NC; i += W) cell[i] = NEGINF;
-        LLR_FENCE();
+        wave_fence();
         int maxlen = len;
         if (HALF) maxlen = max(__shfl(len, 0), __shfl(len, 32));
         maxlen = __builtin_amdgcn_readfirstlane(maxlen);
@@ -157,7 +155,7 @@ mod_llr_kernel(const LlrRead* __restrict__ reads, const int64_t* __restrict__ fi
                         if (hub[s]) dst[NS + s * 64 + li] = nvb[s];
                     }
                 }
-                LLR_FENCE();
+                wave_fence();
             }
         }
         if (valid && li == 0) {
@@ -172,7 +170,7 @@ mod_llr_kernel(const LlrRead* __restrict__ reads, const int64_t* __restrict__ fi
                 rd.out[2 * j + c] = len > 0 ? best : NEGINF;
             }
         }
-        LLR_FENCE();
+        wave_fence();
     }
 }
 

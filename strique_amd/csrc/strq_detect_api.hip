@@ -138,7 +138,7 @@ struct DetectState {
         enum State { Idle, Forward, Decoding };
         State state = Idle;
         std::vector<VitGroup> vls;       // the Viterbi launches of the sub-batch
-        int vit_mode = 0;                // 0 count, 2 MARK (modification pass follows)
+        VitMode vit_mode = VIT_COUNT;    // or VIT_MARK (modification pass follows)
         Extras ex;                       // the switches when the sub-batch was launched: the unit pass, the forward pass, the per-unit scores (behind the modification pass) follow
         bool scan = false;               // a scan sub-batch: a read without a winner has no row
         int64_t r0 = 0; int nr = 0;
@@ -230,7 +230,7 @@ static int sort_viterbi_group(strq_ctx* c, hipStream_t st, const VitGroup& g, co
 }
 // ... then the persistent launch in decode mode `mode` on queue head `queue` (`what`: who says that the shape has no such mode)
 static int launch_viterbi_group(strq_ctx* c, hipStream_t st, const VitGroup& g, const VitTask* tasks, VitResult* results, int* order, int* queue,
-                                int mode, int waves_hint = 0, const char* what = "viterbi: ")
+                                VitMode mode, int waves_hint = 0, const char* what = "viterbi: ")
 {
     const int vrc = launch_viterbi(st, g.shape, g.max_cells, tasks + g.first, results + g.first, g.count, queue, c->n_cu, mode, group_order(order, g), waves_hint);
     if (viterbi_launch_status(vrc) == STRQ_ERR_UNSUPPORTED) c->err = std::string(what) + "decode mode not available for this model's kernel shape";
@@ -461,7 +461,7 @@ static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
         const int shape = vit_shape_of(hm->h);
         if (shape < 0) { c->err = "modification model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
         items[k] = {0, shape, hm->h.n_cells};
-        if (hm->h.rec_state < 0 || hm->h.epl > 2 || len[k] >= ((int64_t)1 << 31)) use_hub = false;
+        if (hm->h.rec_state < 0 || !vit_mode_ok(shape, VIT_HUB) || len[k] >= ((int64_t)1 << 31)) use_hub = false;
     }
     const Grouping G = group_items(items);
     const std::vector<int>& slot2 = G.pos;          // task position of read k
@@ -489,7 +489,7 @@ static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
     for (const VitGroup& vg : G.groups) {
         STRQ_HIP(c, hipMemcpyAsync(d_tb + vg.first, vt2.data() + vg.first, (size_t)vg.count * sizeof(VitTask), hipMemcpyHostToDevice, st));
         if (const int src = sort_viterbi_group(c, st, vg, d_tb, sl.order.as<int>())) return src;
-        if (const int lrc = launch_viterbi_group(c, st, vg, d_tb, d_tr, sl.order.as<int>(), c->queue.as<int>() + qi++, use_hub ? 3 : 1)) return lrc;
+        if (const int lrc = launch_viterbi_group(c, st, vg, d_tb, d_tr, sl.order.as<int>(), c->queue.as<int>() + qi++, use_hub ? VIT_HUB : VIT_BACKPTR)) return lrc;
     }
     int64_t* d_plen = d_len;
     if (use_hub) {
@@ -546,7 +546,7 @@ static int run_unit_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, con
     for (int i : who) {
         HostModel* hm = flank_model(c, d, r0 + i);
         const int64_t T = vt[(size_t)sl.vit_slot[i]].T;
-        W w; w.i = i; w.shape = vit_shape_for(hm->h, 4);
+        W w; w.i = i; w.shape = vit_shape_for(hm->h, VIT_UNIT);
         w.rec = !force_bp && vit_unit_ok(hm->h, w.shape) && T < VIT_UNIT_T_MAX;
         if (!w.rec) w.shape = vit_shape_of(hm->h);
         if (w.shape < 0) { c->err = "unit pass: model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
@@ -606,10 +606,10 @@ static int run_unit_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, con
         if (const int qrc = reset_queue_heads(c, st)) return qrc;
         int qi = 0;
         for (const VitGroup& g : G.groups) {
-            const int want = g.route == 0 ? 4 : 1;          // unit records, or back-pointers and a traceback
+            const VitMode want = g.route == 0 ? VIT_UNIT : VIT_BACKPTR;          // unit records, or back-pointers and a traceback
             if (const int src = sort_viterbi_group(c, st, g, d_vt, sl.order.as<int>())) return src;
             if (const int lrc = launch_viterbi_group(c, st, g, d_vt, d_vr, sl.order.as<int>(), c->queue.as<int>() + qi++, want, 0, "unit pass: ")) return lrc;
-            if (want == 1 && launch_vit_traceback(st, d_vt + g.first, d_vr + g.first, d_paths + g.first, g.count)) { c->err = "traceback launch failed"; return STRQ_ERR_DEVICE; }
+            if (want == VIT_BACKPTR && launch_vit_traceback(st, d_vt + g.first, d_vr + g.first, d_paths + g.first, g.count)) { c->err = "traceback launch failed"; return STRQ_ERR_DEVICE; }
         }
         if (launch_unit_hop(st, d_ut, n_rec) || launch_unit_scan(st, d_ut + n_rec, m - n_rec)) { c->err = "unit position launch failed"; return STRQ_ERR_DEVICE; }
         std::vector<int64_t> pos(xo + 1); std::vector<int32_t> bad((size_t)m);
@@ -740,7 +740,7 @@ static int run_anchored_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
         // (run_range refused the call before any launch when a target of the range had none)
         if (t.end_model_id < 0 || t.start_model_id < 0) { c->err = "anchored: target without anchored models (strq_target_set_anchored)"; return STRQ_ERR_ARG; }
         HostModel* hm = model_of(who[(size_t)k]);
-        const int shape = vit_shape_for(hm->h, 2);
+        const int shape = vit_shape_for(hm->h, VIT_MARK);
         if (shape < 0) { c->err = "anchored: model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
         items[(size_t)k] = {0, shape, hm->h.n_cells};
     }
@@ -766,10 +766,10 @@ static int run_anchored_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
     int qi = 0;
     for (const VitGroup& g : G.groups) {
         if (const int src = sort_viterbi_group(c, st, g, d_vt, sl.order.as<int>())) return src;
-        if (const int lrc = launch_viterbi_group(c, st, g, d_vt, d_vr, sl.order.as<int>(), c->queue.as<int>() + qi++, 2, 0, "anchored: ")) return lrc;
+        if (const int lrc = launch_viterbi_group(c, st, g, d_vt, d_vr, sl.order.as<int>(), c->queue.as<int>() + qi++, VIT_MARK, 0, "anchored: ")) return lrc;
         d->anch_launches += group_order(sl.order.as<int>(), g) ? 2 : 1;
-        const int base = g.shape & ~VIT_SHAPE_SS;
-        if (base == VIT_SHAPE_G2) d->anch_g2 += g.count; else if (base != VIT_SHAPE_CSR) d->anch_lane += g.count;
+        const VitFamily fam = vit_shape_family(g.shape);
+        if (fam == VIT_FAMILY_G2) d->anch_g2 += g.count; else if (fam == VIT_FAMILY_LANE) d->anch_lane += g.count;
     }
     std::vector<VitResult> vr((size_t)m);
     STRQ_HIP(c, hipMemcpyAsync(vr.data(), d_vr, (size_t)m * sizeof(VitResult), hipMemcpyDeviceToHost, st));
@@ -906,7 +906,8 @@ static int queue_viterbi_launches(strq_ctx* c, DetectState::Slot& sl, hipStream_
     std::memset(c->vit_launches, 0, sizeof(c->vit_launches));
     for (auto& v : sl.vls) {
         ++c->vit_launches[0];
-        ++c->vit_launches[(v.shape & ~VIT_SHAPE_SS) == VIT_SHAPE_G2 ? 1 : ((v.shape & ~VIT_SHAPE_SS) == VIT_SHAPE_CSR ? 3 : 2)];
+        const VitFamily fam = vit_shape_family(v.shape);
+        ++c->vit_launches[fam == VIT_FAMILY_G2 ? 1 : (fam == VIT_FAMILY_CSR ? 3 : 2)];
         const int lrc = launch_viterbi_group(c, vs, v, sl.vit.as<VitTask>(), sl.vres.as<VitResult>(), sl.order.as<int>(), sl.vq.as<int>() + qi++,
                                              sl.vit_mode, (after && vs != c->stream) ? 4 : 0);
         if (lrc) return lrc;
@@ -966,7 +967,7 @@ static int take_rows(strq_ctx* c, DetectState* d, DetectState::Slot& sl, bool un
     }
     publish_timing(c, B);
     // the mode the launches ran with decides, not what the targets say by now
-    if (sl.vit_mode == 2) { const int mrc = run_mod_pass(c, d, sl); if (mrc) return mrc; }
+    if (sl.vit_mode == VIT_MARK) { const int mrc = run_mod_pass(c, d, sl); if (mrc) return mrc; }
     if (sl.ex.units || sl.ex.conf) {
         Decoded dec;
         if (const int drc = read_decoded(c, sl, dec)) return drc;
@@ -1119,7 +1120,7 @@ static int plan_viterbi(strq_ctx* c, DetectState* d, SubBatch& S)
     for (int i = 0; i < nr; ++i) {
         HostModel* hm = flank_model(c, d, S.r0 + i);
         model_of[i] = hm->dev;
-        const int shape = vit_shape_for(hm->h, S.any_mod ? 2 : 0);
+        const int shape = vit_shape_for(hm->h, S.any_mod ? VIT_MARK : VIT_COUNT);
         if (shape < 0) { c->err = "model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
         items[i] = {0, shape, hm->h.n_cells};
     }
@@ -1317,7 +1318,7 @@ static int publish_forward(strq_ctx* c, DetectState* d, const SubBatch& S)
     *h.redo = 0;
     if (c->redo_total.p) STRQ_HIP(c, hipMemcpyAsync(h.redo, c->redo_total.p, 4, hipMemcpyDeviceToHost, st));
     STRQ_HIP(c, hipEventRecord(sl.fwd_done, st));
-    sl.vit_mode = S.any_mod ? 2 : 0;
+    sl.vit_mode = S.any_mod ? VIT_MARK : VIT_COUNT;
     sl.ex = d->extras;
     sl.scan = S.nc > 0;
     sl.flt_base = S.flt_base;
@@ -1804,7 +1805,7 @@ int strq_target_set_anchored(strq_ctx* c, int32_t target_id, int32_t end_model_i
         (!none && (end_model_id < 0 || end_model_id >= nm || start_model_id < 0 || start_model_id >= nm))) { c->err = "bad argument"; return STRQ_ERR_ARG; }
     if (!none)
         for (int32_t id : {end_model_id, start_model_id})
-            if (vit_shape_for(c->models[id]->h, 2) < 0) { c->err = "anchored: model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
+            if (vit_shape_for(c->models[id]->h, VIT_MARK) < 0) { c->err = "anchored: model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
     if (const int rc = drain(c, d)) return rc;          // a sub-batch in flight is taken with the target it ran with
     Target& t = d->targets[target_id];
     t.end_model_id = end_model_id; t.start_model_id = start_model_id;

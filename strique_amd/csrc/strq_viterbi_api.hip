@@ -318,7 +318,7 @@ int build_vit_model_csr(strq_ctx* c, int32_t n_states, int32_t silent_start, int
     return STRQ_OK;
 }
 
-// Register-resident image of a profile chain (VitG2, viterbi_kernels.h) from the position of every emitting state along the
+// Register-resident image of a profile chain (VitG2, vit_model.h) from the position of every emitting state along the
 // chain: kind 0 = match-type, 1 = insert-type, pos >= 0.  Silent states take the position after their emitting / silent
 // predecessors (a silent state without predecessors -- start -- the position before its match-type successor).  Every
 // in-edge must fall into a column of the layout, in ascending column order (= ascending source state, the order ties are
@@ -378,7 +378,7 @@ static bool g2_layout(const HostModel* hm, const int32_t* kind_hint, const int32
             slot = l;
         }
         if (!ok) continue;
-        // ---- in-edges per state, then the virtual relay states (see viterbi_kernels.h).  The in-edges of an insert-type state T
+        // ---- in-edges per state, then the virtual relay states (see vit_model.h).  The in-edges of an insert-type state T
         // at position g, in evaluation order, must read   F ++ mid ++ back   with
         //   F    = sources among {I_{g-1}, M_{g-1}}                         (repeat0i, dummy1 <- e1 <- last insert / match before them)
         //   mid  = the regular columns {I_g (T itself), M_g, D_g}
@@ -668,9 +668,9 @@ int strq_viterbi_batch(strq_ctx* c, int32_t model_id, int64_t n_seq, const doubl
     if (paths) STRQ_HIP(c, hipMemcpyAsync(d_paths, hp.data(), (size_t)n_seq * 8, hipMemcpyHostToDevice, st));
     if (const int qrc = reset_queue_heads(c, st)) return qrc;
     STRQ_HIP(c, hipEventRecord(c->ev[0], st));
-    const int shape = vit_shape_for(hm->h, paths ? 1 : 0);
+    const int shape = vit_shape_for(hm->h, paths ? VIT_BACKPTR : VIT_COUNT);
     if (shape < 0) { c->err = "model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
-    int rc = launch_viterbi(st, shape, hm->h.n_cells, d_tasks, d_res, (int)n_seq, c->queue.as<int>(), c->n_cu, paths ? 1 : 0);
+    int rc = launch_viterbi(st, shape, hm->h.n_cells, d_tasks, d_res, (int)n_seq, c->queue.as<int>(), c->n_cu, paths ? VIT_BACKPTR : VIT_COUNT);
     if (rc) { c->err = "viterbi launch failed"; return viterbi_launch_status(rc); }
     STRQ_HIP(c, hipEventRecord(c->ev[1], st));
     if (paths) {

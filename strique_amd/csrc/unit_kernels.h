@@ -6,7 +6,7 @@
 namespace strq {
 
 // One decoded window: the observations t of the best path that emit from a counted state, written as base + t (ascending) to
-// out[0 .. n).  Record route: `rec` = the 2 x T unit records of a want_bp 4 decode (VIT_UNIT_T_MAX) and the end payload in
+// out[0 .. n).  Record route: `rec` = the 2 x T unit records of a VIT_UNIT decode (VIT_UNIT_T_MAX) and the end payload in
 // result->dbg[0]; back-pointer route: `path` = the emitting state of every observation (launch_vit_traceback) and `count_inc`
 // of the model.  n comes from the count decode of the same window; *bad is set to 1 when the window does not give exactly n.
 struct UnitTask {

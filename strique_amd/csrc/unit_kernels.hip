@@ -1,6 +1,6 @@
 // Repeat-unit positions from a flanked-model decode (repeatHMM's path, STRique.py:374-378,433-441): the observations of the best
 // path that emit from the two counted (dummy) states.  Two routes, same positions:
-//   unit_hop_kernel   -- from the unit records of a want_bp 4 decode: one hop per repeat unit, back from the end state's payload;
+//   unit_hop_kernel   -- from the unit records of a VIT_UNIT decode: one hop per repeat unit, back from the end state's payload;
 //   unit_scan_kernel  -- from the state path that the back-pointer traceback wrote (models and windows without a unit decode).
 #include <hip/hip_runtime.h>
 #include <stdint.h>

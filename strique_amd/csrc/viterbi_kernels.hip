@@ -34,29 +34,9 @@
 #include <type_traits>
 #include <stdlib.h>
 #include "viterbi_kernels.h"
+#include "hmm_wave.h"
 
 namespace strq {
-
-static __device__ __forceinline__ int vit_next_task(int* queue, int lane)
-{
-    __builtin_amdgcn_wave_barrier();
-    int ti = 0;
-    if (lane == 0) ti = atomicAdd(queue, 1);
-    __builtin_amdgcn_wave_barrier();
-    ti = __builtin_amdgcn_readfirstlane(ti);
-    __builtin_amdgcn_wave_barrier();
-    return ti;
-}
-
-static __device__ __forceinline__ double readlane_f64(double v, int l)
-{
-    const uint64_t u = __builtin_bit_cast(uint64_t, v);
-    const uint32_t lo = __builtin_amdgcn_readlane((int)(uint32_t)u, l);
-    const uint32_t hi = __builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), l);
-    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
-}
-
-#define VIT_FENCE() __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront")
 
 // -DSTRQ_VIT_TIMING (diagnostic build, tools/vit_timing.py): shader cycles spent in the four parts of a time step, summed
 // over all waves -- [0] emitting phase up to its stores, [1] silent gather + tournament, [2] chain sweeps, [3] stores and loop
@@ -67,16 +47,8 @@ __device__ unsigned long long vit_timing_acc[8];
 #define VIT_CLOCK() __builtin_readcyclecounter()
 #endif
 
-// wave_shr:1 -- lane l receives lane l-1; lane 0 receives +0.0 / 0 (bound_ctrl).  The chain sweeps add the
-// chain log-probability afterwards, which is -inf for every lane without a chain predecessor (lane 0
-// never has one), so the filler value cannot survive.
-static __device__ __forceinline__ double dpp_shr1_f64(double v)
-{
-    const uint64_t u = __builtin_bit_cast(uint64_t, v);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)u, 0x138, 0xF, 0xF, true);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u >> 32), 0x138, 0xF, 0xF, true);
-    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
-}
+// wave_shr:1 (dpp_shr1_f64, hmm_wave.h) -- lane l receives lane l-1; lane 0 receives +0.0 / 0 (bound_ctrl).  The chain sweeps add the chain
+// log-probability afterwards, which is -inf for every lane without a chain predecessor (lane 0 never has one), so the filler value cannot survive.
 static __device__ __forceinline__ int dpp_shr1_i32(int v)
 {
     return __builtin_amdgcn_update_dpp(0, v, 0x138, 0xF, 0xF, true);
@@ -128,11 +100,7 @@ template <int EPL, int SPL> struct VitLds {
     // waves per CU: two per SIMD.  (Three fit shape (4,2) at 168 VGPRs and raise the throughput of
     // large uniform batches by ~8%, but a 4096-read batch is bound by its longest window, whose
     // per-step latency gets worse -- measured 176 ms vs 164 ms per bench step.)
-#ifdef STRQ_VIT_WAVES12
-    static constexpr int WAVES = (160 * 1024) / (2 * BUF) >= 12 ? 12 : ((160 * 1024) / (2 * BUF) >= 8 ? 8 : ((160 * 1024) / (2 * BUF) >= 4 ? 4 : 2));
-#else
     static constexpr int WAVES = (160 * 1024) / (2 * BUF) >= 8 ? 8 : ((160 * 1024) / (2 * BUF) >= 4 ? 4 : 2);
-#endif
 };
 
 // SS: every model of the launch is single-stage (no silent state has a silent predecessor outside
@@ -143,8 +111,7 @@ template <int EPL, int SPL> struct VitLds {
 // Instead of back-pointers for every (time step, state) the best path carries, next to its repeat count,
 // the time of its first emission inside the repeat section and of its first emission after it: the 8
 // payload bytes of a cell hold  lo = count | enter[11:0] << 20,  hi = enter[21:12] | leave << 10  (windows below
-// 2^21 samples): the split keeps every update a 32-bit operation (64-bit shifts are slow on the VALU).
-#define VIT_MARK_T_MAX ((int64_t)1 << 21)
+// 2^21 samples, VIT_MARK_T_MAX): the split keeps every update a 32-bit operation (64-bit shifts are slow on the VALU).
 //
 // HUB (modification model): every path passes through the emitting hub states between two repeat units
 // (s0 -> base | modified unit profile -> e0 -> s0 ...), and all states of a unit belong to one branch.  The
@@ -163,16 +130,14 @@ viterbi_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ result
     constexpr int TRASH = VitLds<EPL, SPL>::TRASH, BUF = VitLds<EPL, SPL>::BUF;
     // one 16-byte cell per state: {double value; int count; int pad} -> one ds_read_b128 per in-edge
     char* const vbase = reinterpret_cast<char*>(lds_d) + (size_t)wave * 2 * BUF;
-    // DE_HI above 16 packs two degrees: tens = in-edge registers of slot 0, units = of the other busy slots (65: the one
-    // or two states of a flanked-repeat model with six in-edges sit in slot 0, the matches with five in the next)
-    constexpr int HI0 = DE_HI > 16 ? DE_HI / 10 : DE_HI, HI1 = DE_HI > 16 ? DE_HI % 10 : DE_HI;
-    // DE_LO above 10: the units are the degree, and the slots of the second half hold no Normal emission (the inserts of
-    // a profile: uniform) -- with clipped observations inside every uniform support their emission is the constant ecf
-    constexpr int LO = DE_LO > 10 ? DE_LO % 10 : DE_LO;
-    constexpr bool LO_FLAT = DE_LO > 10;
-    // the packed shapes are chosen for models without counted silent states (vit_shape_base): the payload of a silent state is
+    // the packed degrees of DE_HI and DE_LO: vit_model.h (VIT_SHAPES)
+    constexpr int HI0 = vit_deg_slot0(DE_HI), HI1 = vit_deg_hi(DE_HI), LO = vit_deg_lo(DE_LO);
+    // the slots of the second half hold no Normal emission (the inserts of a profile: uniform) -- with clipped observations
+    // inside every uniform support their emission is the constant ecf
+    constexpr bool LO_FLAT = vit_lo_flat(DE_LO);
+    // the packed shapes are chosen for models without counted silent states (vit_shape_covers): the payload of a silent state is
     // then its predecessor's as it is -- one VALU instruction less per chain hop (the lane shift folds into the select)
-    constexpr bool SILENT_COUNTED = DE_HI <= 16;
+    constexpr bool SILENT_COUNTED = vit_silent_counted(DE_HI);
     constexpr int DEMAX = HI0 > LO ? HI0 : LO;
     auto de_of = [](int s) constexpr { return s == 0 ? HI0 : (s < (EPL + 1) / 2 ? HI1 : LO); };
     const double NEGINF = -__builtin_inf();
@@ -223,13 +188,9 @@ viterbi_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ result
     double slp[SPL][DS], clp[SPL];
 
     for (;;) {
-        const int tq = vit_next_task(queue, lane);
+        const int tq = wave_next_task(queue, lane);
         if (tq >= n_tasks) break;
         const int ti = order ? order[tq] : tq;        // longest observation windows first
-#ifdef STRQ_VIT_PRIO
-        // experiment: the longest windows of a launch are its critical path -- let their waves issue ahead of the wave they share a SIMD with
-        if (tq < n_tasks / STRQ_VIT_PRIO) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(0);
-#endif
         const VitTask tk = tasks[ti];
         if (tk.model != cur_model) {
             cur_model = tk.model;
@@ -288,9 +249,9 @@ viterbi_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ result
         // percentile tails, STRique.py:597,603) is all NaN and takes the general emission code below
         const bool fast_em = tk.src_kind != VIT_SRC_F64 && tk.lo >= uni_lo_max && tk.hi <= uni_hi_min && tk.c1 == tk.c1 && tk.h1 == tk.h1;
         for (int i = lane; i < NP; i += 64) { stcell(vbase, 16 * i, NEGINF, 0); stcell(vbase, BUF + 16 * i, NEGINF, 0); }
-        VIT_FENCE();
+        wave_fence();
         if (lane == 0) stcell(vbase, 16 * m_start, 0.0, 0);
-        VIT_FENCE();
+        wave_fence();
 
         // Best of the first `cnt` candidates into element 0 (value, carried count, source cell).  Pairwise
         // tournament instead of a serial chain (shorter dependency chains); the right-hand candidate wins
@@ -370,7 +331,7 @@ viterbi_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ result
 #endif
 #pragma unroll
                 for (int s = 0; s < SPL; ++s) stcell(sdst[s], OFF, y[s], yc[s]);
-                VIT_FENCE();
+                wave_fence();
                 if (BP) {
 #pragma unroll
                     for (int s = 0; s < SPL; ++s)
@@ -424,10 +385,10 @@ viterbi_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ result
                     }
                 }
                 if (!single_stage && !__any(changed)) break;
-                VIT_FENCE();
+                wave_fence();
 #pragma unroll
                 for (int s = 0; s < SPL; ++s) stcell(sdst[s], OFF, y[s], yc[s]);
-                VIT_FENCE();
+                wave_fence();
                 if (single_stage) break;     // nothing downstream of the chains inside this time step
             }
             if (BP) {
@@ -513,7 +474,7 @@ viterbi_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ result
 #pragma unroll
                 for (int s = 0; s < SPL; ++s) stcell(sdst[s], WR, NEGINF, 0);
             }
-            VIT_FENCE();
+            wave_fence();
 #ifdef STRQ_VIT_TIMING
             const unsigned long long tc1 = VIT_CLOCK();
             tm_emit += tc1 - tc0;
@@ -562,18 +523,7 @@ viterbi_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ result
             {
                 const int64_t idx = t0 + lane;
                 double xv = 0.0;
-                if (idx < T) {
-                    if (tk.src_kind == VIT_SRC_F64) xv = reinterpret_cast<const double*>(tk.sig)[idx];
-                    else {
-                        double sv = tk.src_kind == VIT_SRC_I16_AFFINE ? (double)reinterpret_cast<const int16_t*>(tk.sig)[idx]
-                                                                      : reinterpret_cast<const double*>(tk.sig)[idx];
-                        sv = (sv - tk.c1) / tk.h1;
-                        sv = sv * tk.h2 + tk.c2;
-                        sv = sv < tk.lo ? tk.lo : sv;          // np.clip
-                        sv = sv > tk.hi ? tk.hi : sv;
-                        xv = sv;
-                    }
-                }
+                if (idx < T) xv = vit_observation(tk, idx);
                 xchunk = xv;
             }
             const int send = (int)((T - t0) < 64 ? (T - t0) : 64);
@@ -594,11 +544,7 @@ viterbi_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ result
             r.counted = 0;
             r.dbg[0] = (uint32_t)fin.c;          // time of the last e0 emission on the best path (= T when the path ends properly)
         } else if constexpr (MARK) {
-            const uint32_t plo = (uint32_t)fin.c, phi = (uint32_t)((uint64_t)fin.c >> 32);
-            r.counted = (lp > NEGINF) ? (int64_t)(plo & 0xFFFFFu) : 0;
-            r.dbg[0] = (plo >> 20) | ((phi & 0x3FFu) << 12);       // time (1-based) of the first repeat-section emission, 0 = none
-            r.dbg[1] = phi >> 10;                                  // time of the first emission after the repeat section, 0 = none
-            if (tk.T >= VIT_MARK_T_MAX) r.status = 2;              // window too long for the packed marks
+            vit_unpack_marks((uint64_t)fin.c, lp > NEGINF, tk.T, r);
         } else if constexpr (UNIT) {
             r.counted = 0;                                         // (the count decode reports it: the hops of the record chain)
             r.dbg[0] = (uint32_t)fin.c;                            // payload of the end state: the last counted emission, 0 = none
@@ -616,12 +562,12 @@ viterbi_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ result
             atomicAdd(&vit_timing_acc[3], tm_rest - tm_sweep); atomicAdd(&vit_timing_acc[4], tm_steps);
         }
 #endif
-        VIT_FENCE();
+        wave_fence();
     }
 }
 
 // ------------------------------------------------------------------------------------------
-// Register-resident profile chain (VitG2, viterbi_kernels.h): one wave per window, two chain positions per lane, the value
+// Register-resident profile chain (VitG2, vit_model.h): one wave per window, two chain positions per lane, the value
 // vector of the previous time step in VGPRs.  What the lane layouts above fetch through LDS -- 21 ds_read_b128 and 6
 // ds_write_b96 per time step, the unit the step was found to wait for (profiles/r03_vit_sensitivity.md) -- is here the lane's
 // own registers, one wave_shr:1 DPP shift of four previous values, and two v_readlane broadcasts for the edges that close the
@@ -705,7 +651,7 @@ viterbi_g2_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ res
     int bc0_lane = 0, bc1_lane = 0, start_slot = 0, start_lane = 0, end_slot = 0, end_lane = 0;
 
     for (;;) {
-        const int tq = vit_next_task(queue, lane);
+        const int tq = wave_next_task(queue, lane);
         if (tq >= n_tasks) break;
         const int ti = order ? order[tq] : tq;        // longest observation windows first
         const VitTask tk = tasks[ti];
@@ -786,9 +732,9 @@ viterbi_g2_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ res
         uint64_t front_won = 0;
         if constexpr (LX) {
             if (lane < 5) { const uint64_t u = __builtin_bit_cast(uint64_t, NEGINF); v4u q; q.x = (unsigned)u; q.y = (unsigned)(u >> 32); q.z = 0; q.w = 0; *reinterpret_cast<v4u*>(xbase + lane * (G2_LDS_CELLS * 16)) = q; }
-            VIT_FENCE();
+            wave_fence();
             xstore(2, dv[1], dc[1]);
-            VIT_FENCE();
+            wave_fence();
             xload(2, rDo, qDo);
         }
 
@@ -825,7 +771,7 @@ viterbi_g2_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ res
                 g2_tournament<6>(cv, cc); best[1] = cv[0]; bcnt[1] = cc[0];
             };
             // insert-type states: themselves, the match and the delete state of their position (what else feeds one in the
-            // baked model reaches it through a virtual delete state, viterbi_kernels.h)
+            // baked model reaches it through a virtual delete state, vit_model.h)
             auto tour_ie = [&]() {
                 const double c0 = pv[2] + lc[0], c1 = pv[0] + lc[1], c2 = dv[0] + lc[2];
                 const bool g1 = c1 > c0;
@@ -884,7 +830,7 @@ viterbi_g2_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ res
                     tour_me(); tour_mo(); tour_ie(); tour_io(); finish(K0{}); finish(K1{}); finish(K2{}); finish(K3{});
                     xstore(0, nv[1], nc[1]); xstore(1, nv[3], nc[3]);
                     if constexpr (LX2) { xstore(3, nv[0], nc[0]); if constexpr (!ODD) xstore(4, nv[2], nc[2]); }
-                    VIT_FENCE();
+                    wave_fence();
                     xload(0, nM, cM); xload(1, nI, cI);
                     rMo = nM; rIo = nI; qMo = cM; qIo = cI;          // ... which are next step's shifted previous values
                     if constexpr (LX2) {
@@ -913,9 +859,9 @@ viterbi_g2_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ res
             // the broadcast source wins only on '>' and the chain only raises a value: the slot kept a gather column's value iff it still equals it
             front_won = __builtin_amdgcn_ballot_w64(y[0] == gather01) & hub_mask;
             if constexpr (LX) {
-                VIT_FENCE();
+                wave_fence();
                 xstore(2, y[1], yc[1]);
-                VIT_FENCE();
+                wave_fence();
                 xload(2, rDo, qDo);
             }
 #pragma unroll
@@ -929,18 +875,7 @@ viterbi_g2_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ res
                 {
                     const int64_t idx = t0 + lane;
                     double xv = 0.0;
-                    if (idx < T) {
-                        if (tk.src_kind == VIT_SRC_F64) xv = reinterpret_cast<const double*>(tk.sig)[idx];
-                        else {
-                            double sv = tk.src_kind == VIT_SRC_I16_AFFINE ? (double)reinterpret_cast<const int16_t*>(tk.sig)[idx]
-                                                                          : reinterpret_cast<const double*>(tk.sig)[idx];
-                            sv = (sv - tk.c1) / tk.h1;
-                            sv = sv * tk.h2 + tk.c2;
-                            sv = sv < tk.lo ? tk.lo : sv;          // np.clip
-                            sv = sv > tk.hi ? tk.hi : sv;
-                            xv = sv;
-                        }
-                    }
+                    if (idx < T) xv = vit_observation(tk, idx);
                     xchunk = xv;
                 }
                 const int send = (int)((T - t0) < 64 ? (T - t0) : 64);
@@ -976,10 +911,10 @@ viterbi_g2_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ res
     }
 }
 
-static int launch_viterbi_g2(hipStream_t stream, const VitTask* tasks, VitResult* results, int n_tasks, int* queue, int n_cu, int want_bp, const int* order, int waves_hint)
+static int launch_viterbi_g2(hipStream_t stream, const VitTask* tasks, VitResult* results, int n_tasks, int* queue, int n_cu, VitMode mode, const int* order, int waves_hint)
 {
-    if (want_bp != 0 && want_bp != 2 && want_bp != 4) return 2;
-    if (want_bp == 4) {          // the unit pass runs alone on the GPU (strq_detect_api.hip: run_unit_pass): eight waves, all exchanges through LDS
+    if (!vit_mode_ok(VIT_SHAPE_G2, mode)) return 2;
+    if (mode == VIT_UNIT) {          // the unit pass runs alone on the GPU (strq_detect_api.hip: run_unit_pass): eight waves, all exchanges through LDS
         hipLaunchKernelGGL((viterbi_g2_kernel<false, 8, 2, true>), dim3(n_cu), dim3(64 * 8), (size_t)8 * G2_LDS_WAVE_BYTES, stream, tasks, results, n_tasks, queue, order);
         return hipGetLastError() == hipSuccess ? 0 : 1;
     }
@@ -993,7 +928,7 @@ static int launch_viterbi_g2(hipStream_t stream, const VitTask* tasks, VitResult
     const size_t lds = lx ? (size_t)nw * G2_LDS_WAVE_BYTES : 0;
 #define G2_GO2(MK_, W_, LX_) hipLaunchKernelGGL((viterbi_g2_kernel<MK_, W_, LX_>), grid, block, lds, stream, tasks, results, n_tasks, queue, order)
 #define G2_GO(MK_, W_) do { if (lx == 2) G2_GO2(MK_, W_, 2); else if (lx == 1) G2_GO2(MK_, W_, 1); else G2_GO2(MK_, W_, 0); } while (0)
-    if (want_bp == 2) { if (nw == 12) G2_GO(true, 12); else if (nw == 4) G2_GO(true, 4); else G2_GO(true, 8); }
+    if (mode == VIT_MARK) { if (nw == 12) G2_GO(true, 12); else if (nw == 4) G2_GO(true, 4); else G2_GO(true, 8); }
     else { if (nw == 12) G2_GO(false, 12); else if (nw == 4) G2_GO(false, 4); else G2_GO(false, 8); }
 #undef G2_GO
 #undef G2_GO2
@@ -1009,7 +944,7 @@ static int launch_viterbi_g2(hipStream_t stream, const VitTask* tasks, VitResult
 // levels -- with a workgroup barrier in between.  Not a throughput path (a flank profile has ~50 levels: ~100 barriers
 // per time step); it exists so that a target whose HMM exceeds the lane layouts (repeat units beyond ~50 nt, states with
 // more than eight in-edges) runs instead of being refused -- the reference takes whatever pomegranate takes
-// (scripts/STRique.py:553-579).  MODE 0: count, 1: back-pointers (predecessor state per (time step, state)), 2: MARK.
+// (scripts/STRique.py:553-579).  MODE: VIT_COUNT, VIT_BACKPTR (predecessor state per (time step, state)) or VIT_MARK.
 template <int MODE>
 __global__ void __launch_bounds__(256)
 viterbi_csr_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ results,
@@ -1019,7 +954,7 @@ viterbi_csr_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ re
     __shared__ int next_task;
     struct alignas(16) Cell { double v; uint64_t c; };
     const double NEGINF = -__builtin_inf();
-    constexpr bool MARK = MODE == 2, BP = MODE == 1;
+    constexpr bool MARK = MODE == VIT_MARK, BP = MODE == VIT_BACKPTR;
     auto count_add = [](uint64_t v, int inc) -> uint64_t { return (v & 0xFFFFFFFF00000000ull) | (uint32_t)((uint32_t)v + (uint32_t)inc); };
     for (;;) {
         __syncthreads();
@@ -1059,16 +994,7 @@ viterbi_csr_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ re
         const int64_t T = tk.T;
         for (int64_t t = 0; t < T; ++t) {
             Cell* prev = (t & 1) ? buf1 : buf0; Cell* cur = (t & 1) ? buf0 : buf1;
-            double x;
-            if (tk.src_kind == VIT_SRC_F64) x = reinterpret_cast<const double*>(tk.sig)[t];
-            else {
-                double sv = tk.src_kind == VIT_SRC_I16_AFFINE ? (double)reinterpret_cast<const int16_t*>(tk.sig)[t] : reinterpret_cast<const double*>(tk.sig)[t];
-                sv = (sv - tk.c1) / tk.h1;
-                sv = sv * tk.h2 + tk.c2;
-                sv = sv < tk.lo ? tk.lo : sv;
-                sv = sv > tk.hi ? tk.hi : sv;
-                x = sv;
-            }
+            const double x = vit_observation(tk, t);
             const uint32_t tt1 = (uint32_t)(t + 1);
             const uint32_t mark_e_lo = (tt1 & 0xFFFu) << 20, mark_e_hi = tt1 >> 12, mark_l_hi = tt1 << 10;
             (void)mark_e_lo; (void)mark_e_hi; (void)mark_l_hi;
@@ -1105,11 +1031,7 @@ viterbi_csr_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ re
             VitResult r; r.logp = lp; r.status = (lp > NEGINF) ? 0 : 1; r.pad_ = 0;
             r.dbg[0] = r.dbg[1] = r.dbg[2] = r.dbg[3] = 0;
             if constexpr (MARK) {
-                const uint32_t plo = (uint32_t)fin.c, phi = (uint32_t)(fin.c >> 32);
-                r.counted = (lp > NEGINF) ? (int64_t)(plo & 0xFFFFFu) : 0;
-                r.dbg[0] = (plo >> 20) | ((phi & 0x3FFu) << 12);
-                r.dbg[1] = phi >> 10;
-                if (tk.T >= VIT_MARK_T_MAX) r.status = 2;
+                vit_unpack_marks(fin.c, lp > NEGINF, tk.T, r);
             } else r.counted = (lp > NEGINF) ? (int64_t)(uint32_t)fin.c : 0;
             results[ti] = r;
         }
@@ -1117,9 +1039,9 @@ viterbi_csr_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ re
 }
 
 static int launch_viterbi_csr(hipStream_t stream, int max_cells, const VitTask* tasks, VitResult* results, int n_tasks,
-                              int* queue, int n_cu, int want_bp, const int* order)
+                              int* queue, int n_cu, VitMode mode, const int* order)
 {
-    if (max_cells - 1 > VIT_CSR_MAX_STATES || want_bp == 3 || want_bp == 4) return 2;
+    if (!vit_mode_ok(VIT_SHAPE_CSR, mode) || max_cells - 1 > VIT_CSR_MAX_STATES) return 2;
     const size_t lds = (size_t)2 * (size_t)(max_cells - 1) * 16;
     int per_cu = (int)((160 * 1024 - 64) / (lds ? lds : 1)); if (per_cu > 4) per_cu = 4; if (per_cu < 1) per_cu = 1;
     const dim3 grid(per_cu * n_cu), block(256);
@@ -1128,7 +1050,7 @@ static int launch_viterbi_csr(hipStream_t stream, int max_cells, const VitTask* 
         (void)hipFuncSetAttribute((const void*)viterbi_csr_kernel<MODE_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         hipLaunchKernelGGL((viterbi_csr_kernel<MODE_>), grid, block, lds, stream, tasks, results, n_tasks, queue, order);  \
     } while (0)
-    if (want_bp == 2) VIT_CSR_GO(2); else if (want_bp == 1) VIT_CSR_GO(1); else VIT_CSR_GO(0);
+    if (mode == VIT_MARK) VIT_CSR_GO(VIT_MARK); else if (mode == VIT_BACKPTR) VIT_CSR_GO(VIT_BACKPTR); else VIT_CSR_GO(VIT_COUNT);
 #undef VIT_CSR_GO
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
@@ -1221,64 +1143,18 @@ vit_traceback_kernel(const VitTask* __restrict__ tasks, const VitResult* __restr
     }
 }
 
-// kernel shapes: (EPL, SPL, DE_HI, DE_LO, DS)
-static int vit_shape_base(const VitModel& mh)
+int vit_shape_for(const VitModel& mh, VitMode mode)
 {
-    const int e = mh.epl, s = mh.spl;
-    int hi = 0, lo = 0, ds = 0;
-    for (int i = 0; i < e; ++i) { if (i < (e + 1) / 2) hi = hi > mh.e_deg[i] ? hi : mh.e_deg[i]; else lo = lo > mh.e_deg[i] ? lo : mh.e_deg[i]; }
-    for (int i = 0; i < s; ++i) ds = ds > mh.s_deg[i] ? ds : mh.s_deg[i];
-    // flanked-repeat models: six-edge states in slot 0, two in-edges per delete state besides its chain
-    // (their kernels leave the count increments of silent states out: STRique counts the emitting dummy states, STRique.py:341-342,375-377)
-    if (e <= 4 && s <= 2 && e > 2 && mh.e_deg[0] <= 6 && mh.e_deg[1] <= 5 && lo <= 3 && ds <= 2 && !mh.silent_counted) {
-        bool flat = true;
-        for (int i = (e + 1) / 2; i < e; ++i) flat = flat && mh.e_flat[i];
-        if (flat && e == 4) return 7;          // ... and only uniform emissions (the inserts) in the last two slots
-        return 5;
-    }
-    if (e <= 4 && s <= 2 && e > 2 && hi <= 6 && lo <= 3 && ds <= 3) return 0;      // flanked-repeat models
-    if (e <= 1 && s <= 1 && hi <= 5 && ds <= 1) return 6;                          // STRique's dual base / mCpG model: 26 + 2 states, at most five in-edges
-    if (e <= 1 && s <= 1 && hi <= 8 && ds <= 4) return 1;                          // modification models
-    if (e <= 2 && s <= 2 && hi <= 8 && lo <= 8 && ds <= 4) return 2;
-    if (e <= 4 && s <= 4 && hi <= 8 && lo <= 8 && ds <= 8) return 3;
-    if (e <= 8 && s <= 4 && hi <= 8 && lo <= 8 && ds <= 8) return 4;
-    return -1;
+    return vit_shape_for(mh, mode, strq::opt("STRQ_VIT_NO_G2") == nullptr);      // A/B: the lane layout for every mode
 }
 
-// silent slots per lane of a kernel shape (the template's SPL)
-int vit_shape_silent_slots(int shape)
-{
-    static const int spl[8] = {2, 1, 2, 4, 4, 2, 1, 2};
-    const int b = shape & ~VIT_SHAPE_SS;
-    return b >= 0 && b < 8 ? spl[b] : 0;
-}
-
-int vit_shape_for(const VitModel& mh, int want_bp)
-{
-    const bool no_g2 = strq::opt("STRQ_VIT_NO_G2") != nullptr;      // A/B: the lane layout for every mode
-    if (mh.g2 && !no_g2 && (want_bp == 0 || (want_bp == 2 && mh.g2_mark) || (want_bp == 4 && mh.g2_unit))) return VIT_SHAPE_G2;          // either parity of the chain: decided per window inside the kernel
-    return vit_shape_of(mh);
-}
-
-bool vit_unit_ok(const VitModel& mh, int shape)
-{
-    if (shape < 0 || mh.unit_state[0] < 0 || mh.unit_state[1] < 0 || mh.silent_counted) return false;
-    const int b = shape & ~VIT_SHAPE_SS;
-    if (b == VIT_SHAPE_G2) return mh.g2 && mh.g2_unit;
-    return b != VIT_SHAPE_CSR && b != 1 && b != 6;          // lane layouts with at least two emitting slots (vit_launch_shape)
-}
-
-int vit_shape_of(const VitModel& mh)
-{
-    if (mh.csr) return VIT_SHAPE_CSR;
-    const int b = vit_shape_base(mh);
-    return b < 0 ? b : (b | (mh.single_stage ? VIT_SHAPE_SS : 0));
-}
-
-template <int E_, int S_, int H_, int L_, int D_>
+// the kernels of row ID of VIT_SHAPES: an instance exists exactly where the row has the mode
+template <int ID>
 static int vit_launch_shape(hipStream_t stream, int max_cells, const VitTask* tasks, VitResult* results, int n_tasks,
-                            int* queue, int n_cu, int want_bp, int single_stage, const int* order)
+                            int* queue, int n_cu, VitMode mode, int single_stage, const int* order)
 {
+    constexpr int E_ = VIT_SHAPES[ID].epl, S_ = VIT_SHAPES[ID].spl, H_ = VIT_SHAPES[ID].de_hi, L_ = VIT_SHAPES[ID].de_lo, D_ = VIT_SHAPES[ID].ds;
+    if (!vit_mode_ok(ID, mode)) return 2;
     if (max_cells > VitLds<E_, S_>::TRASH) return 3;
     // per wave: two buffers of 16-byte {value, count} cells; waves of a block are independent
     int nw = VitLds<E_, S_>::WAVES;
@@ -1290,39 +1166,25 @@ static int vit_launch_shape(hipStream_t stream, int max_cells, const VitTask* ta
         (void)hipFuncSetAttribute((const void*)viterbi_kernel<E_, S_, H_, L_, D_, BP_, SS_, MK_, HB_, UN_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         hipLaunchKernelGGL((viterbi_kernel<E_, S_, H_, L_, D_, BP_, SS_, MK_, HB_, UN_>), grid, block, lds, stream, tasks, results, n_tasks, queue, order);       \
     } while (0)
-    // want_bp: 0 = count only, 1 = back-pointers, 2 = repeat-section marks carried along the best path, 3 = hub records, 4 = unit records
-    if (want_bp == 4) {
-        if constexpr (E_ >= 2) { if (single_stage) VIT_GO(false, true, false, false, true); else VIT_GO(false, false, false, false, true); }
-        else return 2;
-    }
-    else if (want_bp == 3) {
-        if constexpr (E_ <= 2) { if (single_stage) VIT_GO(false, true, false, true, false); else VIT_GO(false, false, false, true, false); }
-        else return 2;
-    }
-    else if (want_bp == 2) { if (single_stage) VIT_GO(false, true, true, false, false); else VIT_GO(false, false, true, false, false); }
-    else if (want_bp) { if (single_stage) VIT_GO(true, true, false, false, false); else VIT_GO(true, false, false, false, false); }
-    else { if (single_stage) VIT_GO(false, true, false, false, false); else VIT_GO(false, false, false, false, false); }
+#define VIT_GO_SS(M_, SS_) VIT_GO(M_ == VIT_BACKPTR, SS_, M_ == VIT_MARK, M_ == VIT_HUB, M_ == VIT_UNIT)
+#define VIT_GO_MODE(M_) case M_: if constexpr (vit_mode_ok(ID, M_)) { if (single_stage) VIT_GO_SS(M_, true); else VIT_GO_SS(M_, false); } break
+    switch (mode) { VIT_GO_MODE(VIT_COUNT); VIT_GO_MODE(VIT_BACKPTR); VIT_GO_MODE(VIT_MARK); VIT_GO_MODE(VIT_HUB); VIT_GO_MODE(VIT_UNIT); }
+#undef VIT_GO_MODE
+#undef VIT_GO_SS
 #undef VIT_GO
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
-// `shape` as returned by vit_shape_of: kernel shape | VIT_SHAPE_SS for single-stage models
 int launch_viterbi(hipStream_t stream, int shape, int max_cells, const VitTask* tasks, VitResult* results,
-                   int n_tasks, int* queue, int n_cu, int want_bp, const int* order, int waves_hint)
+                   int n_tasks, int* queue, int n_cu, VitMode mode, const int* order, int waves_hint)
 {
-    const int ss = (shape & VIT_SHAPE_SS) ? 1 : 0;
-    if ((shape & ~VIT_SHAPE_SS) == VIT_SHAPE_CSR) return launch_viterbi_csr(stream, max_cells, tasks, results, n_tasks, queue, n_cu, want_bp, order);
-    if ((shape & ~VIT_SHAPE_SS) == VIT_SHAPE_G2)
-        return launch_viterbi_g2(stream, tasks, results, n_tasks, queue, n_cu, want_bp, order, waves_hint);
-    switch (shape & ~VIT_SHAPE_SS) {
-        case 0: return vit_launch_shape<4, 2, 6, 3, 3>(stream, max_cells, tasks, results, n_tasks, queue, n_cu, want_bp, ss, order);
-        case 1: return vit_launch_shape<1, 1, 8, 8, 4>(stream, max_cells, tasks, results, n_tasks, queue, n_cu, want_bp, ss, order);
-        case 2: return vit_launch_shape<2, 2, 8, 8, 4>(stream, max_cells, tasks, results, n_tasks, queue, n_cu, want_bp, ss, order);
-        case 3: return vit_launch_shape<4, 4, 8, 8, 8>(stream, max_cells, tasks, results, n_tasks, queue, n_cu, want_bp, ss, order);
-        case 4: return vit_launch_shape<8, 4, 8, 8, 8>(stream, max_cells, tasks, results, n_tasks, queue, n_cu, want_bp, ss, order);
-        case 7: return vit_launch_shape<4, 2, 65, 13, 2>(stream, max_cells, tasks, results, n_tasks, queue, n_cu, want_bp, ss, order);
-        case 6: return vit_launch_shape<1, 1, 5, 5, 1>(stream, max_cells, tasks, results, n_tasks, queue, n_cu, want_bp, ss, order);
-        case 5: return vit_launch_shape<4, 2, 65, 3, 2>(stream, max_cells, tasks, results, n_tasks, queue, n_cu, want_bp, ss, order);
+    switch (vit_shape_family(shape)) {
+        case VIT_FAMILY_CSR: return launch_viterbi_csr(stream, max_cells, tasks, results, n_tasks, queue, n_cu, mode, order);
+        case VIT_FAMILY_G2: return launch_viterbi_g2(stream, tasks, results, n_tasks, queue, n_cu, mode, order, waves_hint);
+        case VIT_FAMILY_LANE:
+            return vit_dispatch<VIT_LANE_SHAPES>(shape & ~VIT_SHAPE_SS, [&](auto id) {
+                return vit_launch_shape<decltype(id)::value>(stream, max_cells, tasks, results, n_tasks, queue, n_cu, mode, (shape & VIT_SHAPE_SS) ? 1 : 0, order);
+            });
         default: return 2;
     }
 }

@@ -1,4 +1,4 @@
-"""The register-resident layout of a profile chain (strq_model_set_positions / VitG2, strique_amd/csrc/viterbi_kernels.h),
+"""The register-resident layout of a profile chain (strq_model_set_positions / VitG2, strique_amd/csrc/vit_model.h),
 checked without a GPU: the tables the library would upload (host-only debug export) drive a plain-Python restatement of
 viterbi_g2_kernel's time step, whose log-probability and count must equal the oracle's bit for bit -- on STRique's
 flanked models (scripts/STRique.py:384-431) with even and odd repeat profiles, missing observations included."""

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """How long the flanked-HMM Viterbi of a sub-batch lasts against its work: the window lengths (suffix_end - prefix_begin) of a batch of clean or
-empirical-noise reads, the Viterbi stage time with and without the raised wave priority for the windows the launch waits for (STRQ_VIT_NO_PRIO).
+empirical-noise reads, and the Viterbi stage time against the work bound and the longest window.
 
     python tools/vit_tail_probe.py [reads=4096] [clean|empirical]
 """
@@ -33,15 +33,12 @@ def main():
     T = np.where((res["score_prefix"] > 0) & (res["score_suffix"] > 0) & (T > 0), T, 0)
     slots = 2048
     print("%s reads: %d windows, time steps total %.3e, per wave slot %.0f; longest windows %s; median %d" % (workload, int((T > 0).sum()), T.sum(), T.sum() / slots, np.sort(T)[-6:][::-1].tolist(), int(np.median(T[T > 0]))))
-    for tag, val in (("priority for the longest windows", None), ("STRQ_VIT_NO_PRIO", "1"), ("priority for the longest windows", None)):
-        ctx.set_option("STRQ_VIT_NO_PRIO", val)
+    t0 = time.time()
+    for _ in range(3):
         ctx.batch_run()
-        t0 = time.time()
-        for _ in range(3):
-            ctx.batch_run()
-        dt = (time.time() - t0) / 3
-        tm = ctx.last_timing()
-        print("  %-34s %.1f ms per pass, Viterbi %.1f ms (work bound at 0.67 us per step and slot: %.1f ms, longest window alone: %.1f ms)" % (tag, dt * 1e3, tm[6], T.sum() / slots * 0.67e-3, T.max() * 0.67e-3))
+    dt = (time.time() - t0) / 3
+    tm = ctx.last_timing()
+    print("  %.1f ms per pass, Viterbi %.1f ms (work bound at 0.67 us per step and slot: %.1f ms, longest window alone: %.1f ms)" % (dt * 1e3, tm[6], T.sum() / slots * 0.67e-3, T.max() * 0.67e-3))
 
 
 if __name__ == "__main__":
