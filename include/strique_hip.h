@@ -254,6 +254,40 @@ int strq_batch_fetch_mod_llr(strq_ctx* ctx, double* pool, int64_t pool_cap, int6
 /* The scoring pass of the last run call (STRique.py:492-500 has no counterpart): out[0] = ms on the GPU (all its sub-batches),
  * out[1] = units scored, out[2] = reads with units, out[3] = kernels launched (bounds and scoring; 0 with the switch off). */
 int strq_last_mod_llr(strq_ctx* ctx, double* out4);
+/* Sequence variants of the repeat unit (interruptions; the reference has no counterpart): a variant model is a dual model with 2 to 4
+ * branches over one pore model -- branch 0 the repeat unit, branch b >= 1 the k-mers around alt unit b (state tags: 0 base, 2 the hub
+ * states s0 / e0, 1 / 3 / 4 alt branch 1 / 2 / 3; n_alt of them), decoded on the clipped repeat stretch the modification pass decodes
+ * (clipped to [lo, hi]).  context_units = m: the units in front of an alt unit that its branch holds besides it, so a passage through
+ * an alt branch stands for m + 1 units.  model_id = -1 takes the variant model away.  STRQ_ERR_UNSUPPORTED, and the target stays as
+ * it was, for a model the pass does not cover: more than 128 emitting states, silent states besides start and end, tags that do not
+ * describe exactly n_alt alt branches (a tag beyond them, or a branch without a state), no compiled Viterbi kernel -- never in the
+ * middle of a batch.  A target may hold a modification model and a variant model. */
+int strq_target_set_variants(strq_ctx* ctx, int32_t target_id, int32_t model_id, double lo, double hi, int32_t n_alt, int32_t context_units);
+/* With on = 1, later run calls also decode the variant model of every read whose gate passed, whose flanked-model decode found a
+ * path (in a window below 2^21 samples) and whose target has a variant model.  A passage is a maximal run of emissions of one branch
+ * on the best path; passage j covers the observations x[u_j .. w_j] (the s0 emission in front of it, its branch emissions, the e0
+ * emission behind it), and V_b(j), b in 0 .. n_alt, is the Viterbi log-probability (start to end, float64, evaluated edge by edge
+ * like the decode itself) of the model on them with every edge removed that touches an emitting state of another branch; -inf
+ * where a branch has no path.  A base passage scored under an alt branch is an (m + 1)-unit profile forced onto one unit of signal:
+ * meaningful only as "very negative".  Rows, modification patterns and every other output do not change, with one exception: a
+ * sub-batch that holds a read of a target with a variant model decodes with the packed marks of the modification pass, so a read of
+ * it whose window has 2^21 samples or more keeps count 0 (as the sub-batch mates of a modification target do).  Sub-batches still in
+ * flight keep the mode they were launched with (the call waits for them).  Default 0: no further kernel runs and no further buffer
+ * is reserved. */
+int strq_set_variants(strq_ctx* ctx, int32_t on);
+/* Variants of the last batch.  Per read i: count_v[i] = units of its passages (1 per base passage, m + 1 per alt passage) + the
+ * target's count_bias, decoded[i] = 1 when its variant model was decoded (else count_v[i] = 0 and the read has no passages).  The
+ * passages of read i are [off[i], off[i+1]): branch[k] in 0 .. n_alt, end[k] = raw sample (index into the read) of the e0 emission
+ * w_j -- observation t of the stretch is raw sample first + t, first = the first repeat emission of the flanked path, because the
+ * repeat section of a flanked model cannot be re-entered -- and V of passage k at vpool[voff[k] .. voff[k + 1]) (n_alt + 1 doubles,
+ * voff has off[n] + 1 entries).  pass_cap counts passages, v_cap doubles.  branch, end, vpool and voff may be NULL to query the
+ * totals: off[n] passages, and v_total (nullable) doubles.  STRQ_ERR_ARG when the last run call ran with the switch off. */
+int strq_batch_fetch_variants(strq_ctx* ctx, int32_t* count_v, int32_t* decoded, int64_t* off, int8_t* branch, int64_t* end, int64_t pass_cap,
+                              double* vpool, int64_t* voff, int64_t v_cap, int64_t* v_total);
+/* The variant pass of the last run call: out[0] = kernels launched (0 with the switch off: the count and the write pass of the bounds,
+ * one scoring launch per kernel instance in use, and the traceback where the bounds come from traced paths), out[1] = passages,
+ * out[2] = ms on the GPU (all its sub-batches: compaction, decode, bounds, scoring), out[3] = reads decoded. */
+int strq_last_variants(strq_ctx* ctx, double* out4);
 /* Count confidence: with on = 1, later run calls also run the forward pass (strq_forward_batch) over the window
  * [prefix_begin, suffix_end) of every read whose gate passed and whose flanked-model decode found a path -- the same observations,
  * normalised and clipped, that the decode saw, with c0 = the visits of the best path.  Rows, modification patterns and unit

@@ -32,6 +32,8 @@ UNITS_HEADER = ['ID', 'target', 'strand', 'count', 'n_units', 'units']
 CONF_HEADER = ['ID', 'target', 'strand', 'count', 'log_p', 'log_lik', 'count_mean', 'count_sd']
 # `count --mod_model M --mod-llr FILE`: log-likelihood ratio (modified over unmodified) of every unit of the pattern, one row per count row
 MODLLR_HEADER = ['ID', 'target', 'strand', 'count', 'mod_pattern', 'n_units', 'llr']
+# `count --alt-units FILE --variants OUT`: the interruption calls of every read, one row per count row; calls: index:unit:sample:llr per alt call
+VARIANTS_HEADER = ['ID', 'target', 'strand', 'count', 'count_v', 'n_passages', 'n_alt', 'pattern', 'calls']
 LEVELS = ['error', 'warning', 'info', 'debug']
 
 
@@ -242,6 +244,13 @@ def count(argv):
     parser.add_argument("--mod-llr", dest="mod_llr", default=None, metavar="FILE", help="With --mod_model: also write how far to trust each methylation call to FILE: per repeat unit of "
                                                                                         "the pattern the log-likelihood ratio of the modified over the unmodified branch (positive: "
                                                                                         "modified); one row per count row, columns " + " ".join(MODLLR_HEADER))
+    parser.add_argument("--alt-units", dest="alt_units", default=None, metavar="FILE", help="Sequence variants of the repeat unit (interruptions) to tell from it: a TSV of "
+                                                                                          "target<TAB>unit[,unit...] (at most 3 units per target, as long as its repeat unit, on the "
+                                                                                          "+ strand like it; # comments and blank lines allowed)")
+    parser.add_argument("--variants", default=None, metavar="FILE", help="With --alt-units: also write which repeat units of a read are one of the alt units, and a count "
+                                                                           "corrected for them, to FILE: one row per count row, columns " + " ".join(VARIANTS_HEADER) +
+                                                                           " (calls: index:unit:sample:llr per alt call -- its index in pattern, the unit as configured, the raw "
+                                                                           "sample behind it, the log-likelihood ratio of the best alt branch over the repeat unit)")
     parser.add_argument("--scan", action="store_true", help="No alignment: every read of the index is compared with every target of the repeat config on both strands, "
                                                              "from its raw signal alone, and counted for the one it spans (if any).  Excludes --algn; stdin is not read")
     parser.add_argument("--scan-min-score", type=float, default=None, metavar="X", help="--scan: the smallest min(score_prefix, score_suffix) a target and strand needs to be "
@@ -262,6 +271,10 @@ def count(argv):
         parser.error("--mod-llr needs --mod_model: the ratios belong to the calls of the modification model")
     if args.scan and args.mod_llr:
         parser.error("--mod-llr cannot be combined with --scan: the scoring pass runs on reads whose target and strand an alignment gives")
+    if args.variants and not args.alt_units:
+        parser.error("--variants needs --alt-units FILE: the units to tell from the repeat unit")
+    if args.variants and args.scan:
+        parser.error("--variants cannot be combined with --scan: the variant pass runs on reads whose target and strand an alignment gives")
     if args.scan and args.algn:
         parser.error("--scan takes the target and strand of a read from its signal: it cannot be combined with --algn")
     if not args.scan and (args.scan_scores or args.scan_min_score is not None):
@@ -281,6 +294,17 @@ def count(argv):
         parser.error("--anchored-min-score must be above 0")
     log = Log(args.log_level)
     config = parse_config(args.repeat, args.config, log)
+    alt_units = {}
+    if args.alt_units:
+        if not os.path.isfile(args.alt_units):
+            log("Main: Alt-units file does not exist.", 'error'); raise SystemExit(1)
+        try:
+            with open(args.alt_units) as fp:
+                alt_units = parse_alt_units(fp, {name: v[3] for name, v in config['repeat'].items()})
+        except ValueError as e:
+            log("Main: %s" % e, 'error'); raise SystemExit(1)
+        if args.variants and not alt_units:
+            log("Main: --variants: the alt-units file names no unit.", 'error'); raise SystemExit(1)
     for path, what in ((args.f5Index, "Fast5 index file"), (args.model, "Pore model file")):
         if not os.path.isfile(path):
             log("Main: %s does not exist." % what, 'error'); raise SystemExit(1)
@@ -306,7 +330,7 @@ def count(argv):
     loci = defaultdict(list)
     for name, (chrom, begin, end, repeat, prefix, suffix) in config['repeat'].items():
         try:
-            counter.add_target(name, repeat, prefix, suffix)
+            counter.add_target(name, repeat, prefix, suffix, **({'alt_units': alt_units[name]} if name in alt_units else {}))
         except ValueError:
             raise
         except Exception as e:                # e.g. a flank longer than the compiled kernel shapes cover
@@ -336,7 +360,7 @@ def count(argv):
         readers = max(1, min(24, share))            # inflating is what the readers do: one per core they can get, 16 ... 24 measure the same end to end
     stats = {}
     fault = 0
-    paths = dict(units=args.units, confidence=args.confidence, mod_llr=args.mod_llr, scores=args.scan_scores, anchored=args.anchored)
+    paths = dict(units=args.units, confidence=args.confidence, mod_llr=args.mod_llr, scores=args.scan_scores, anchored=args.anchored, variants=args.variants)
     with contextlib.ExitStack() as stack:
         # rank 0 writes: as the batches are done in a single process (run_count), after the gather otherwise
         files = {name: stack.enter_context(open(path, 'w')) if (path and rank == 0) else None for name, path in paths.items()}
@@ -346,7 +370,8 @@ def count(argv):
             rows = run_count(stream, loci, f5.get_raw, counter, log, args.batch, rank, world, out if world == 1 else None, readers=readers, stats=stats,
                              units=bool(args.units), units_out=now['units'], scan=scan, scores_out=now['scores'],
                              confidence=bool(args.confidence), conf_out=now['confidence'], mod_llr=bool(args.mod_llr), llr_out=now['mod_llr'],
-                             anchored=args.anchored_min_score, anchored_out=now['anchored'])
+                             anchored=args.anchored_min_score, anchored_out=now['anchored'],
+                             variants=alt_units if args.variants else None, variants_out=now['variants'])
         except DeviceFault:
             if world == 1:
                 raise SystemExit(3)
@@ -361,7 +386,7 @@ def count(argv):
                 dist.destroy_process_group()
                 raise SystemExit(3)
             merged = gather_rows(rows, stats["items"], sdist, units=bool(args.units), scan=scan, confidence=bool(args.confidence), mod_llr=bool(args.mod_llr),
-                                 anchored=bool(args.anchored))
+                                 anchored=bool(args.anchored), variants=bool(args.variants))
             if rank == 0:
                 write_rows(out, merged.rows)
                 for o in OUTPUTS:
@@ -463,6 +488,98 @@ def parse_mod_llr(stream):
     return out
 
 
+def parse_alt_units(stream, repeats):
+    """The `--alt-units` file: lines of target<TAB>unit[,unit...], `#` comments and blank lines skipped.  repeats: {target: repeat
+    unit} of the repeat config.  Returns {target: [units]}, upper-cased; ValueError for an unknown target, a target given twice, more
+    than 3 units, and whatever hmm.check_alt_units refuses (a unit of another length than the repeat unit, a unit given twice, ...)."""
+    from .hmm import VARIANT_TAGS, check_alt_units
+    out = {}
+    for no, line in enumerate(stream, 1):
+        text = line.split('#', 1)[0].strip()
+        if not text:
+            continue
+        f = text.split('\t') if '\t' in text else text.split()
+        if len(f) != 2:
+            raise ValueError("alt units, line %d: expected target<TAB>unit[,unit...]" % no)
+        name, units = f[0], [u.strip().upper() for u in f[1].split(',') if u.strip()]
+        if name not in repeats:
+            raise ValueError("alt units, line %d: unknown target %s" % (no, name))
+        if name in out:
+            raise ValueError("alt units, line %d: target %s is given twice" % (no, name))
+        if len(units) > len(VARIANT_TAGS):
+            raise ValueError("alt units, line %d: %d units for target %s, at most %d" % (no, len(units), name, len(VARIANT_TAGS)))
+        try:
+            out[name] = check_alt_units(repeats[name], units)
+        except ValueError as e:
+            raise ValueError("alt units, line %d: %s" % (no, e))
+    return out
+
+
+def variant_value(raw, units):
+    """What the variants file says of one read, from the counter's (count_v, pattern, branch, end, V) and the alt units of its target as
+    configured: (count_v, n_passages, pattern, [(index, unit, sample, llr)]) -- one call per alt passage: the index of its alt character in
+    the pattern, the raw sample of the hub emission behind it, llr = max over the alt branches of V_b, less V_0.  None stays None."""
+    if raw is None:
+        return None
+    count_v, pattern, branch, end, V = raw
+    n_alt = int(np.count_nonzero(branch))
+    m = (len(pattern) - len(branch)) // n_alt if n_alt else 0          # an alt passage is '0' * m + str(b): m characters more than a base one
+    calls, at = [], 0
+    for j, b in enumerate(branch):
+        if b:
+            at += m
+            calls.append((at, units[int(b) - 1], int(end[j]), float(np.max(V[j, 1:]) - V[j, 0])))
+        at += 1
+    return int(count_v), len(branch), pattern, calls
+
+
+def format_variants(qname, target, strand, n, v):
+    """One row of the `count --variants` file: the count as the count row has it, then count_v, the passages, the alt calls, the pattern
+    and the calls as index:unit:sample:llr (llr with four decimals) joined by commas; '-' for a field without value."""
+    if v is None:
+        return '\t'.join([str(qname), str(target), str(strand), str(n), '-', '-', '-', '-', '-'])
+    count_v, n_pass, pattern, calls = v
+    return '\t'.join([str(qname), str(target), str(strand), str(n), str(count_v), str(n_pass), str(len(calls)), pattern if pattern else '-',
+                      ','.join('%d:%s:%d:%.4f' % c for c in calls) if calls else '-'])
+
+
+def parse_variants(stream):
+    """Rows of a `count --variants` file: [(ID, target, strand, count, count_v, n_passages, pattern, [(index, unit, sample, llr)])] in file
+    order; count_v, n_passages and pattern None for a read without a decode."""
+    out = []
+    for line in stream:
+        f = line.rstrip('\n').split('\t')
+        if not line.strip() or f[0] == VARIANTS_HEADER[0]:
+            continue
+        if f[4] == '-':
+            out.append((f[0], f[1], f[2], int(f[3]), None, None, None, []))
+            continue
+        calls = []
+        if f[8] != '-':
+            for c in f[8].split(','):
+                i, unit, sample, llr = c.split(':')
+                calls.append((int(i), unit, int(sample), float(llr)))
+        if len(calls) != int(f[6]):
+            raise ValueError("variants row of %s: %s calls, n_alt = %s" % (f[0], len(calls), f[6]))
+        out.append((f[0], f[1], f[2], int(f[3]), int(f[4]), int(f[5]), '' if f[7] == '-' else f[7], calls))
+    return out
+
+
+def _pack_variants(v):
+    """(count_v, n_passages, pattern, calls) as it travels between ranks: the ratios as repr(), which float() reads back bit for bit."""
+    count_v, n_pass, pattern, calls = v
+    return '|'.join([str(int(count_v)), str(int(n_pass)), pattern, ','.join('%d:%s:%d:%s' % (i, u, s, repr(float(x))) for i, u, s, x in calls)])
+
+
+def _unpack_variants(text):
+    count_v, n_pass, pattern, calls = text.split('|')
+    out = []
+    for c in calls.split(',') if calls else []:
+        i, u, s, x = c.split(':')
+        out.append((int(i), u, int(s), float(x)))
+    return int(count_v), int(n_pass), pattern, out
+
+
 def _floats(values):
     """Floats as they travel between ranks: repr(), which float() reads back bit for bit."""
     return ','.join(repr(float(x)) for x in values)
@@ -488,11 +605,13 @@ OUTPUTS = (
     Output('scores', lambda scan: scan_mod.scores_header(scan["candidates"]),
            lambda q, t, s, row, v: scan_mod.format_scores(q, None if row is None else (t, s), v),
            lambda v: _floats(x for pair in v for x in pair), lambda text: list(zip(*[iter(_unfloats(text))] * 2)), 'score_rows', True),
+    Output('variants', lambda scan: VARIANTS_HEADER, lambda q, t, s, row, v: format_variants(q, t, s, row[0], v),
+           lambda v: _pack_variants(v), lambda text: _unpack_variants(text), 'variant_rows', False),
     Output('anchored', lambda scan: anchored_mod.HEADER, lambda q, t, s, row, v: anchored_mod.format_row(q, t, s, v),
            lambda v: _pack_anchored(v), lambda text: _unpack_anchored(text), 'anchored_rows', False),
 )
-# (`anchored`, the last field, defaults to None: callers that build a Merged from the five values before it keep working)
-Merged = namedtuple('Merged', ['rows'] + [o.name for o in OUTPUTS], defaults=(None,))
+# (`variants` and `anchored`, the last fields, default to None: callers that build a Merged from the five values before them keep working)
+Merged = namedtuple('Merged', ['rows'] + [o.name for o in OUTPUTS], defaults=(None, None))
 
 
 def _pack_anchored(rec):
@@ -507,7 +626,7 @@ def _unpack_anchored(text):
 
 
 def outputs_on(**flags):
-    """The entries of OUTPUTS whose flag (units=, confidence=, mod_llr=, scores=, anchored=) is set."""
+    """The entries of OUTPUTS whose flag (units=, confidence=, mod_llr=, scores=, anchored=, variants=) is set."""
     return [o for o in OUTPUTS if flags.get(o.name)]
 
 
@@ -527,7 +646,7 @@ def _read_values(target, strand, det, scores=None):
     """What the writers know of one read: (target, strand, row or None, {output name: value or None})."""
     if det is None:
         return target, strand, None, dict(scores=scores)
-    return target, strand, det.row, dict(units=det.units, confidence=det.conf, mod_llr=det.llr, scores=scores, anchored=det.anchored)
+    return target, strand, det.row, dict(units=det.units, confidence=det.conf, mod_llr=det.llr, scores=scores, anchored=det.anchored, variants=det.variants)
 
 
 def _emit(sink, on, seq, qname, target, strand, row, values):
@@ -561,13 +680,13 @@ def unpack_blob(on, blob):
     return fields[0], fields[1], fields[2], values
 
 
-def gather_rows(rows, items, sdist, units=False, scan=None, confidence=False, mod_llr=False, anchored=False):
+def gather_rows(rows, items, sdist, units=False, scan=None, confidence=False, mod_llr=False, anchored=False, variants=False):
     """Reads of this rank (run_count with world > 1) -> fixed-size records + one blob per read (pack_blob) -> one gather -> on rank 0
-    the rows of every file in input order: Merged(rows, units, confidence, mod_llr, scores, anchored), [(sequence number, TSV row)] each, None
+    the rows of every file in input order: Merged(rows, units, confidence, mod_llr, scores, variants, anchored), [(sequence number, TSV row)] each, None
     for an output that was not asked for (scores: asked for by scan) and for every field off rank 0.  `items`: every accepted (qname,
     strand, target) of the input, which each rank derives from the same SAM file (scan: from the same index).  A read that failed
     travels as a record with valid = 0 and writes nothing; a scan read without a winner as one with valid = 2: it writes a score row."""
-    on = outputs_on(units=units, confidence=confidence, mod_llr=mod_llr, scores=bool(scan), anchored=anchored)
+    on = outputs_on(units=units, confidence=confidence, mod_llr=mod_llr, scores=bool(scan), anchored=anchored, variants=variants)
     rec = np.zeros(len(rows), ROW_DTYPE); blobs = []; idx = np.zeros(len(rows), np.int64)
     for k, (seq, read) in enumerate(rows):
         idx[k] = seq
@@ -623,7 +742,8 @@ def route(stream, loci, log):
 
 
 def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, out=None, readers=0, stats=None, units=False, units_out=None,
-              scan=None, scores_out=None, confidence=False, conf_out=None, mod_llr=False, llr_out=None, anchored=None, anchored_out=None):
+              scan=None, scores_out=None, confidence=False, conf_out=None, mod_llr=False, llr_out=None, anchored=None, anchored_out=None,
+              variants=None, variants_out=None):
     """Route the SAM records of `stream` to their targets, run this rank's share through
     `counter.detect_batch` and return [(sequence number, TSV row or -- several ranks -- what gather_rows takes)].
 
@@ -642,6 +762,9 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
     `anchored` (a score threshold, not with scan): the counter is asked for Detected records with the anchored record of every read
     (counter.detect_batch(..., anchored=threshold, records=True)); their rows (strique_amd.anchored.format_row) go to `anchored_out`
     and to stats["anchored_rows"].  The count rows and the other files do not change.
+    `variants` ({target: [alt units as configured]}, not with scan; the counter's targets were added with them): the counter is asked
+    for Detected records with the variant pass on (counter.set_variants(True), counter.detect_batch(..., records=True)); their rows
+    (variant_value, format_variants) go to `variants_out` and to stats["variant_rows"].  The count rows and the other files do not change.
     `scan` ({"min_score", "candidates", "scores"}): `stream` is a list of read ids instead of a SAM stream; every read goes through
     counter.scan_batch and takes target and strand from its winner -- a read without one writes no row, as a read without a target
     writes none; single process: the score rows (strique_amd.scan.format_scores, every read) go to `scores_out` and to
@@ -653,17 +776,23 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
     stats.setdefault("failed", 0)
     if anchored is not None and scan:
         raise ValueError("anchored counting cannot be combined with a scan")
-    files = dict(rows=out, units=units_out, confidence=conf_out, mod_llr=llr_out, scores=scores_out, anchored=anchored_out)
-    on = outputs_on(units=units, confidence=confidence, mod_llr=mod_llr, scores=scan and scan["scores"], anchored=anchored is not None)
+    if variants is not None and scan:
+        raise ValueError("variants cannot be combined with a scan")
+    files = dict(rows=out, units=units_out, confidence=conf_out, mod_llr=llr_out, scores=scores_out, anchored=anchored_out, variants=variants_out)
+    on = outputs_on(units=units, confidence=confidence, mod_llr=mod_llr, scores=scan and scan["scores"], anchored=anchored is not None,
+                    variants=variants is not None)
     if out is not None:
         print('\t'.join(HEADER), file=out)
     for o in OUTPUTS:
         stats.setdefault(o.stat, [])
         if files[o.name] is not None:
             print('\t'.join(o.header(scan)), file=files[o.name])
-    extras = {o.name: True for o in on if o.name not in ('scores', 'anchored')}
+    extras = {o.name: True for o in on if o.name not in ('scores', 'anchored', 'variants')}
     if anchored is not None:
         extras.update(anchored=anchored, records=True)
+    if variants is not None:
+        counter.set_variants(True)
+        extras.update(records=True)
     rows = []
     records = ((rid, '.', ['.'], 0) for rid in stream) if scan else route(stream, loci, log)
     mine_set = None
@@ -724,7 +853,10 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
                 winner, sc = res
                 read = _read_values(None, None, None, sc) if winner is None else _read_values(winner[0], winner[1], as_detected(winner[2], units), sc)
             elif res is not None:
-                read = _read_values(target, strand, as_detected(res, units, confidence, mod_llr))
+                det = as_detected(res, units, confidence, mod_llr)
+                if variants is not None:
+                    det = det._replace(variants=variant_value(det.variants, variants.get(target, ())))
+                read = _read_values(target, strand, det)
             if world > 1:
                 sink['rows'].append((seq, read))
             elif read is not None:
@@ -843,6 +975,8 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
             engine.shutdown(wait=True)
             if pool is not None:
                 pool.shutdown()
+            if variants is not None:
+                counter.set_variants(False)          # the switch belongs to this run
         else:
             # an exception is on its way out (a DeviceFault from the engine thread, a broken input): the batch queued behind
             # the failed one must not be handed to a device that may be hung, and nobody waits for it -- the caller exits,

@@ -35,7 +35,8 @@ target_classifier = namedtuple('target_classifier',
 # one read out of the device pipeline: the tuple detect() returns, and what was asked for beside it (None otherwise) -- unit positions,
 # (log_lik, count_mean, count_sd), per-unit log-likelihood ratios, the anchored record (kind, status, count, log_p, begin, end,
 # free_samples -- every kind, as strq_batch_fetch_anchored hands it out); see repeatCounter.detect_batch
-Detected = namedtuple('Detected', ['row', 'units', 'conf', 'llr', 'anchored'], defaults=(None,))
+# variants: (count_v, pattern, branch, end, V) of the variant pass, see repeatCounter.detect_batch
+Detected = namedtuple('Detected', ['row', 'units', 'conf', 'llr', 'anchored', 'variants'], defaults=(None, None))
 
 
 class repeatCounter(object):
@@ -59,6 +60,12 @@ class repeatCounter(object):
         # registered ({target_id: {kind: {'model_id', 'bias', 'states', 'positions_rc', 'positions_error'}}}); nothing is baked before somebody asks
         self._anchored_src = {}
         self.anchored_models = {}
+        # variants: (repeat, alt units) of the classifiers of a target added with alt units, and the classifiers whose variant model is
+        # registered ({target_id: RepeatVariantModel}); baked when somebody asks, like the anchored models
+        self._variant_src = {}
+        self.variant_models = {}
+        self.variant_refused = {}      # {target_id: message} of the variant models strq_target_set_variants refused
+        self.variants = False          # set_variants
 
     # -------------------------------------------------------------------------------------
     def _classifier(self, repeat, prefix, suffix, prefix_ext, suffix_ext):
@@ -94,9 +101,41 @@ class repeatCounter(object):
             self.ctx.target_set_anchored(tid, e['model_id'], e['bias'], s['model_id'], s['bias'])
             self.anchored_models[tid] = made
 
-    def add_target(self, target_name, repeat, prefix, suffix):
+    def _ensure_variants(self):
+        """The variant model of every classifier with alt units that has none yet: baked, uploaded and registered with its target."""
+        refused = None
+        for tid, (repeat, alts) in self._variant_src.items():
+            if tid in self.variant_models or tid in self.variant_refused:
+                continue
+            m = hmm_mod.RepeatVariantModel(repeat, alts, self.pm, self.HMM_config)
+            m.model_id = self.ctx.model_create(m.baked)
+            try:
+                self.ctx.target_set_variants(tid, m.model_id, m.model_min, m.model_max, len(m.alt_units), m.context_units)
+            except ffi.StriqueHipError as e:
+                # a model the pass does not cover: the target stays without one, its reads report None; said once, after the
+                # other targets are registered, and the model is not uploaded again
+                if e.code != ffi.STRQ_ERR_UNSUPPORTED:
+                    raise
+                self.variant_refused[tid] = str(e)
+                refused = refused or e
+                continue
+            self.variant_models[tid] = m
+        if refused is not None:
+            raise refused
+
+    def set_variants(self, on):
+        """on: detect and detect_batch also run the variant pass (strq_set_variants) and report one more element per read -- see
+        detect_batch.  ValueError when no target was added with alt_units.  Not with scan_batch."""
+        if on and not self._variant_src:
+            raise ValueError("RepeatCounter: variants needs a target added with alt_units.")
+        self.variants = bool(on)
+
+    def add_target(self, target_name, repeat, prefix, suffix, alt_units=None):
+        """alt_units: 1 to 3 sequence variants of the repeat unit (on the + strand, as `repeat`) that detect
+        tells from it once set_variants(True) is called; ValueError for units hmm.check_alt_units does not take."""
         if target_name in self.targets:
             raise ValueError("RepeatCounter: Target with name " + str(target_name) + " already defined.")
+        alts = hmm_mod.check_alt_units(repeat, alt_units) if alt_units else None
         prefix_ext = prefix.upper(); prefix = prefix[-50:].upper()            # STRique.py:555-559
         suffix_ext = suffix.upper(); suffix = suffix[:50].upper()
         repeat = repeat.upper()
@@ -105,6 +144,10 @@ class repeatCounter(object):
         # reverse strand: flanks swap roles (STRique.py:569-575)
         tc_minus = self._classifier(rc(repeat), rc(suffix), rc(prefix), rc(suffix_ext), rc(prefix_ext))
         self.targets[target_name] = (tc_plus, tc_minus)
+        if alts:
+            # the - strand reads the reverse complement of unit and alt units; calls are reported with the number of the unit as configured
+            self._variant_src[tc_plus.target_id] = (repeat, alts)
+            self._variant_src[tc_minus.target_id] = (rc(repeat), [rc(a) for a in alts])
 
     def _classifier_for(self, target_name, strand):
         if target_name not in self.targets:
@@ -135,7 +178,16 @@ class repeatCounter(object):
         the raw-signal samples [begin, end) decoded into the repeat, and the observations the free state took (a handful on a read
         that really ends in the repeat, thousands on one wrongly taken for anchored).  A read whose decode found no path has zeros
         behind its kind; None for every other read (spanning, or neither).  The tuple itself does not change.
-        Order of the elements: (tuple[, positions][, conf][, llr][, anchored]); without any of the four the bare tuple.
+        With set_variants(True) (a counter with a target added with alt_units; a switch of the counter, not a keyword: the keywords of
+        detect and detect_batch are those every stand-in counter of run_count answers): one more element after all of them -- None for a read that was
+        not decoded or whose target has no alt units, else (count_v, pattern, branch, end, V): the variant model's passages in
+        signal order.  branch (int8 array) is 0 for a passage through the repeat unit's profile, b for one through alt unit b's (the
+        b-th unit as configured, on either strand); end (int64) the raw sample of the hub emission behind each passage; V
+        (float64 [n_passages, 1 + n_alt]) every branch's masked Viterbi score of the passage, -inf without a path -- a base passage
+        scored under an alt branch is an (m + 1)-unit profile forced onto one unit of signal, meaningful only as "very negative".
+        pattern has one character per unit: '0' per base passage, '0' * m + str(b) per alt passage (m = the model's context units);
+        count_v = len(pattern) + count_bias is an estimate on the scale of the tuple's count, not equal to it in general.
+        Order of the elements: (tuple[, positions][, conf][, llr][, anchored][, variants]); without any of the five the bare tuple.
         records=True: a list of Detected records instead (the fields that were not asked for None; `anchored` the record of every
         read, whatever its kind: (kind number, status, count, log_p, begin, end, free_samples))."""
         items = list(items)
@@ -143,9 +195,10 @@ class repeatCounter(object):
             raise ValueError("RepeatCounter: mod_llr needs a modification model.")
         if anchored is not None and not anchored > 0:
             raise ValueError("RepeatCounter: the anchored score threshold must be above 0.")
+        variants = self.variants
         reads = [(self._classifier_for(t, s).target_id, r) for t, r, s in items]
         out = [None] * len(items)
-        for i, d, _, _ in self._run(reads, units=units, confidence=confidence, mod_llr=mod_llr, anchored=anchored):
+        for i, d, _, _ in self._run(reads, units=units, confidence=confidence, mod_llr=mod_llr, anchored=anchored, variants=variants):
             if records:
                 out[i] = d
                 continue
@@ -153,11 +206,13 @@ class repeatCounter(object):
             if anchored is not None:
                 a = d.anchored
                 extra += ((anchored_mod.KIND_NAMES[a[0]],) + tuple(a[2:]) if a[0] in (anchored_mod.ENDS_IN_REPEAT, anchored_mod.STARTS_IN_REPEAT) else None,)
+            if variants:
+                extra += (d.variants,)
             out[i] = (d.row,) + extra if extra else d.row
         return out
 
     @contextlib.contextmanager
-    def _switches(self, units, confidence, mod_llr, anchored=None):
+    def _switches(self, units, confidence, mod_llr, anchored=None, variants=False):
         """The optional passes that were asked for are on inside the block, and all of them off after it."""
         try:
             if anchored is not None:
@@ -171,14 +226,18 @@ class repeatCounter(object):
                 self.ctx.set_confidence(True)
             if mod_llr:
                 self.ctx.set_mod_llr(True)
+            if variants:
+                self._ensure_variants()
+                self.ctx.set_variants(True)
             yield
         finally:
+            self.ctx.set_variants(False)
             self.ctx.set_anchored(False)
             self.ctx.set_mod_llr(False)
             self.ctx.set_units(False)
             self.ctx.set_confidence(False)
 
-    def _run(self, reads, units=False, confidence=False, mod_llr=False, scan=None, anchored=None):
+    def _run(self, reads, units=False, confidence=False, mod_llr=False, scan=None, anchored=None, variants=False):
         """reads: [(target_id, raw_signal)] through the context.  Yields (position in `reads`, Detected, winner, scores) per read, the
         fields of Detected that were not asked for being None.  scan=(candidate target ids, min_score): the target ids of the reads
         are ignored, every read is compared with every candidate (Context.scan_batch_reads); winner is its position in the candidate
@@ -192,7 +251,7 @@ class repeatCounter(object):
             if not idx:
                 continue
             arrs = [sigs[i].astype(np.int16 if want_int else np.float64, copy=False) for i in idx]
-            with self._switches(units, confidence, mod_llr, anchored):
+            with self._switches(units, confidence, mod_llr, anchored, variants):
                 if scan is None:
                     res = self.ctx.detect_batch_reads(arrs, [reads[i][0] for i in idx])      # one pointer per read: no host-side concatenation
                     win = sc = [None] * len(res)
@@ -202,14 +261,23 @@ class repeatCounter(object):
                 pos = self.ctx.batch_fetch_units() if units else [None] * len(res)
                 conf = self.ctx.batch_fetch_confidence() if confidence else [None] * len(res)
                 vs = self.ctx.batch_fetch_mod_llr() if mod_llr else [None] * len(res)
+                var = [None] * len(res)
+                if variants:
+                    var = []
+                    for i, v in zip(idx, self.ctx.batch_fetch_variants()):
+                        if v is not None:
+                            m = self.variant_models[reads[i][0]]
+                            pattern = "".join("0" if b == 0 else "0" * m.context_units + str(int(b)) for b in v[1])
+                            v = (v[0], pattern, v[1], v[2], v[3].reshape(len(v[1]), m.n_branches))      # (a read without passages: (0, NB))
+                        var.append(v)
                 an = [None] * len(res)
                 if anchored is not None:
                     an = [(int(a['kind']), int(a['status']), int(a['count']), float(a['log_p']), int(a['begin']), int(a['end']), int(a['free_samples']))
                           for a in self.ctx.batch_fetch_anchored()]
-            for i, r, m, u, cf, v, w, s, a in zip(idx, res, mods, pos, conf, vs, win, sc, an):
+            for i, r, m, u, cf, v, w, s, a, vr in zip(idx, res, mods, pos, conf, vs, win, sc, an, var):
                 n = int(r['count']); p = float(r['log_p']) if n or r['log_p'] != 0 else 0
                 row = (n, float(r['score_prefix']), float(r['score_suffix']), p, int(r['offset']), int(r['ticks']), m)
-                yield i, Detected(row, u, cf, None if v is None else v[:, 1] - v[:, 0], a), w, s
+                yield i, Detected(row, u, cf, None if v is None else v[:, 1] - v[:, 0], a, vr), w, s
 
     def candidates(self, targets=None):
         """[(target_name, strand)] of a scan: every target added (or the named ones), in add_target order, '+' before '-'."""
@@ -259,7 +327,7 @@ class repeatCounter(object):
         """(n, score_prefix, score_suffix, log_p, offset, ticks, mod_pattern) -- STRique.py:581-618.  units=True:
         (that tuple, unit positions or None); confidence=True: (that tuple, [positions,] (log_lik, count_mean, count_sd) or
         None); mod_llr=True: the per-unit log-likelihood ratios (or None) after them; anchored=m: (kind, count, log_p, begin, end,
-        free_samples) of a read that holds one flank only (or None) last; records=True: a Detected record instead -- see
-        detect_batch."""
+        free_samples) of a read that holds one flank only (or None) behind them; after set_variants(True): (count_v, pattern, branch, end, V)
+        or None last; records=True: a Detected record instead -- see detect_batch."""
         return self.detect_batch([(target_name, raw_signal, strand)], units=units, confidence=confidence, mod_llr=mod_llr, anchored=anchored,
                                  records=records)[0]

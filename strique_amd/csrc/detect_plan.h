@@ -32,7 +32,14 @@ struct Carve {
 // (strq_set_mod_llr).  DetectState holds what the next run call uses, a slot what its sub-batch was launched with, Batch what the last
 // run call ran with.
 // Anchored counting (strq_set_anchored) is the fourth: it comes with its score threshold.
-struct Extras { bool units = false, conf = false, llr = false, anch = false; double anch_min = 0.0; };
+// The variant pass (strq_set_variants) is the fifth.
+struct Extras { bool units = false, conf = false, llr = false, anch = false, var = false; double anch_min = 0.0; };
+
+// What the variant pass leaves per read: the passages of its variant-model decode (strq_batch_fetch_variants)
+struct VariantRow {
+    int32_t decoded = 0, count_v = 0, n_branch = 0;
+    std::vector<int8_t> branch; std::vector<int64_t> end; std::vector<double> V;      // per passage: branch, raw sample of w_j, n_branch scores
+};
 
 // What a batch holds per read: the row, the modification pattern and the outputs of the optional passes.  One place sizes them, one
 // function puts a read back to its initial values -- a row that was never computed is never handed out.
@@ -45,6 +52,7 @@ struct ReadRows {
     std::vector<uint8_t> conf_dec;
     std::vector<std::vector<double>> llr;         // (V_base, V_mod) per repeat unit (strq_batch_fetch_mod_llr); empty: none
     std::vector<strq_anchored> anch;              // kind and decode of a read that holds one flank (strq_batch_fetch_anchored); zeros: kind 0
+    std::vector<VariantRow> var;                  // passages of the variant model (strq_batch_fetch_variants); decoded = 0: none
     void size_reads(int64_t n)
     {
         const size_t m = (size_t)n;
@@ -53,6 +61,7 @@ struct ReadRows {
         conf.assign(3 * m, NAN); conf_dec.assign(m, 0);
         llr.assign(m, std::vector<double>());
         anch.assign(m, strq_anchored());
+        var.assign(m, VariantRow());
     }
     void clear_read(int64_t read)
     {
@@ -63,6 +72,7 @@ struct ReadRows {
         conf[3 * r] = conf[3 * r + 1] = conf[3 * r + 2] = NAN; conf_dec[r] = 0;
         llr[r].clear();
         anch[r] = strq_anchored();
+        var[r] = VariantRow();
     }
 };
 

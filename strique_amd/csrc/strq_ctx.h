@@ -14,6 +14,7 @@
 #include "viterbi_kernels.h"
 #include "forward_kernels.h"
 #include "mod_llr_kernels.h"
+#include "variant_kernels.h"
 #include "screen_kernels.h"
 #include "strq_opt.h"
 
@@ -107,6 +108,10 @@ struct HostModel {
     DevBuf llr_blob;
     const LlrModel* llr_dev = nullptr;
     int32_t llr_mode = -1;
+    // variant pass (variant_kernels.h): the edge image of a variant model, built by strq_target_set_variants
+    DevBuf var_blob;
+    const VarModel* var_dev = nullptr;
+    int32_t var_mode = -1, var_nb = 0;
 };
 
 }  // namespace strq

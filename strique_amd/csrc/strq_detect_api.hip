@@ -24,6 +24,7 @@
 #include "forward_kernels.h"
 #include "scan_kernels.h"
 #include "anchored_kernels.h"
+#include "variant_kernels.h"
 
 using namespace strq;
 
@@ -71,6 +72,7 @@ struct Target {
     int model_id = -1, count_bias = 0;
     int mod_model_id = -1; double mod_min = 0, mod_max = 0;
     int end_model_id = -1, end_bias = 0, start_model_id = -1, start_bias = 0;      // strq_target_set_anchored: both models or none
+    int var_model_id = -1, var_nalt = 0, var_ctx = 0; double var_lo = 0, var_hi = 0;      // strq_target_set_variants
 };
 
 struct Batch : ReadRows {
@@ -112,6 +114,8 @@ struct DetectState {
     DevBuf unit_task, unit_ws, unit_path, unit_pool;      // unit pass (run_unit_pass): tasks, records / back-pointers, state paths, positions
     Extras extras;                       // strq_set_units, strq_set_confidence, strq_set_mod_llr: what the next run call uses
     DevBuf llr_ws;                       // per-unit scores (run_llr_pass): tasks, unit bounds, scores
+    DevBuf var_ws, var_bounds, var_out;  // variant pass (run_variant_tail): tasks and passage counts; passage bounds; scores
+    float var_ms = 0; double var_launches = 0, var_passages = 0, var_reads = 0;      // strq_last_variants: the last run call's variant pass
     float llr_ms = 0; double llr_units = 0, llr_reads = 0, llr_launches = 0;      // strq_last_mod_llr: the last run call's scoring pass
     DevBuf conf_task;                    // forward pass (run_conf_pass): tasks, model images, c0, results, order
     float conf_ms = 0; double conf_windows = 0, conf_nopath = 0, conf_expo = 0;      // strq_last_confidence: the last run call's forward pass
@@ -189,7 +193,11 @@ struct DetectState {
 // the target of a read of the batch and its models: the flanked one, the modification model, the anchored model of a read of `kind`
 static const Target& target_of(const DetectState* d, int64_t read) { return d->targets[d->batch.target[(size_t)read]]; }
 static HostModel* flank_model(const strq_ctx* c, const DetectState* d, int64_t read) { return c->models[target_of(d, read).model_id]; }
-static HostModel* mod_model(const strq_ctx* c, const DetectState* d, int64_t read) { return c->models[target_of(d, read).mod_model_id]; }
+// the dual models of a target: the modification model (base | mCpG over two pore models), the variant model (repeat unit | alt units)
+enum Dual { DUAL_MOD, DUAL_VAR };
+static int dual_id(const Target& t, Dual which) { return which == DUAL_MOD ? t.mod_model_id : t.var_model_id; }
+static HostModel* dual_model(const strq_ctx* c, const DetectState* d, int64_t read, Dual which) { return c->models[dual_id(target_of(d, read), which)]; }
+static HostModel* mod_model(const strq_ctx* c, const DetectState* d, int64_t read) { return dual_model(c, d, read, DUAL_MOD); }
 static HostModel* anchored_model(const strq_ctx* c, const DetectState* d, int64_t read, int kind)
 {
     return c->models[kind == ANCH_ENDS ? target_of(d, read).end_model_id : target_of(d, read).start_model_id];
@@ -395,10 +403,151 @@ static int run_llr_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, cons
     return STRQ_OK;
 }
 
-// Modification pass for the reads of one sub-batch whose target has a modification model.
+// The edge image of a variant model with `n_alt` alt branches (HostModel::var_dev), built if it is not there; STRQ_ERR_UNSUPPORTED
+// (c->err says why) for a model the pass does not cover.
+static int variant_model(strq_ctx* c, HostModel* hm, int32_t n_alt)
+{
+    if (hm->var_dev && hm->var_nb == n_alt + 1) return STRQ_OK;
+    std::vector<char> blob; std::string why; int32_t mode = -1;
+    if (var_build_image(hm->n_states, hm->silent_start, hm->start, hm->end, hm->in_ptr.data(), hm->in_src.data(), hm->in_logp.data(),
+                        hm->emis_kind.data(), hm->emis_a.data(), hm->emis_b.data(), hm->emis_c.data(),
+                        hm->state_tag.empty() ? nullptr : hm->state_tag.data(), n_alt, nullptr, blob, &mode, why)) { c->err = why; return STRQ_ERR_UNSUPPORTED; }
+    if (vit_shape_of(hm->h) < 0) { c->err = "variants: the variant model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
+    if (hm->var_blob.reserve(var_image_bytes()) != hipSuccess) { c->err = "out of device memory"; return STRQ_ERR_NOMEM; }
+    var_build_image(hm->n_states, hm->silent_start, hm->start, hm->end, hm->in_ptr.data(), hm->in_src.data(), hm->in_logp.data(),
+                    hm->emis_kind.data(), hm->emis_a.data(), hm->emis_b.data(), hm->emis_c.data(), hm->state_tag.data(), n_alt, hm->var_blob.p, blob, &mode, why);
+    STRQ_HIP(c, hipMemcpy(hm->var_blob.p, blob.data(), blob.size(), hipMemcpyHostToDevice));
+    hm->var_dev = hm->var_blob.as<VarModel>(); hm->var_mode = mode; hm->var_nb = n_alt + 1;
+    return STRQ_OK;
+}
+
+// Behind the decode of the variant models of one sub-batch (run_mod_pass, DUAL_VAR): the passages of every read from its hub records
+// or its traced path (their number comes back first: it sizes the scores), all branches' scores of every passage, the rows.
+static int run_variant_tail(strq_ctx* c, DetectState* d, DetectState::Slot& sl, const LlrPassIn& in, const std::vector<int64_t>& first)
+{
+    Batch& B = d->batch;
+    hipStream_t st = c->stream;
+    const int64_t r0 = sl.r0;
+    const ReadGeom* geom = sl.host().geom;
+    const std::vector<int>& who = *in.who;
+    const int nm = (int)who.size();
+    // count pass: a passage takes three observations at least (s0, one branch emission, e0), so T / 3 + 1 bounds the count
+    Carve lay;
+    const size_t o_n = lay.add<int32_t>((size_t)nm), o_bad = lay.add<int32_t>((size_t)nm), o_bt = lay.add<VarBoundTask>((size_t)nm),
+                 o_rd = lay.add<VarRead>((size_t)nm), o_first = lay.add<int64_t>((size_t)nm + 16);
+    STRQ_HIP(c, d->var_ws.reserve(lay.total() + 64));
+    void* ws = d->var_ws.p;
+    int32_t* d_n = Carve::at<int32_t>(ws, o_n); int32_t* d_bad = Carve::at<int32_t>(ws, o_bad);
+    VarBoundTask* d_bt = Carve::at<VarBoundTask>(ws, o_bt); VarRead* d_rd = Carve::at<VarRead>(ws, o_rd);
+    int64_t* d_first = Carve::at<int64_t>(ws, o_first);
+    std::vector<VarBoundTask> bt((size_t)nm);
+    for (int k = 0; k < nm; ++k) {
+        HostModel* hm = dual_model(c, d, r0 + who[k], DUAL_VAR);
+        // (strq_target_set_variants built the image or refused the model: nothing is built or refused in the middle of a batch)
+        if (!hm->var_dev || hm->var_mode < 0 || hm->var_mode > 2) { c->err = "variants: variant model without an edge image (strq_target_set_variants validates them)"; return STRQ_ERR_DEVICE; }
+        const int s2 = (*in.slot2)[(size_t)k];
+        VarBoundTask& b = bt[(size_t)k]; std::memset(&b, 0, sizeof(b));
+        b.rec = in.use_hub ? reinterpret_cast<const uint64_t*>(d->bp.as<uint16_t>() + (*in.bp2_off)[(size_t)k]) : nullptr;
+        b.result = in.results + s2; b.path = in.use_hub ? nullptr : (*in.paths)[(size_t)s2]; b.tag = hm->h.state_tag;
+        b.w = nullptr; b.branch = nullptr; b.n = d_n + k; b.bad = d_bad + k;
+        b.T = (*in.len)[(size_t)k]; b.cap = (int32_t)((*in.len)[(size_t)k] / 3 + 1); b.n_branch = hm->var_nb;
+    }
+    auto bounds = [&]() -> int {
+        STRQ_HIP(c, hipMemcpyAsync(d_bt, bt.data(), (size_t)nm * sizeof(VarBoundTask), hipMemcpyHostToDevice, st));
+        if (launch_var_bounds(st, in.use_hub ? d_bt : nullptr, in.use_hub ? nm : 0, in.use_hub ? nullptr : d_bt, in.use_hub ? 0 : nm)) { c->err = "variants: bounds launch failed"; return STRQ_ERR_DEVICE; }
+        return STRQ_OK;
+    };
+    STRQ_HIP(c, hipMemsetAsync(d_n, 0, (size_t)nm * 4, st));
+    STRQ_HIP(c, hipMemsetAsync(d_bad, 0, (size_t)nm * 4, st));
+    if (const int rc = bounds()) return rc;
+    std::vector<int32_t> np((size_t)nm), bad((size_t)nm); std::vector<VitResult> vr((size_t)nm);
+    STRQ_HIP(c, hipMemcpyAsync(np.data(), d_n, (size_t)nm * 4, hipMemcpyDeviceToHost, st));
+    STRQ_HIP(c, hipMemcpyAsync(bad.data(), d_bad, (size_t)nm * 4, hipMemcpyDeviceToHost, st));
+    STRQ_HIP(c, hipMemcpyAsync(vr.data(), in.results, (size_t)nm * sizeof(VitResult), hipMemcpyDeviceToHost, st));
+    STRQ_HIP(c, hipStreamSynchronize(st));
+    const char* no_chain = "variants: the hub records / the traced path of a read do not describe a chain of passages";
+    std::vector<size_t> cap_off((size_t)nm + 1, 0);
+    for (int k = 0; k < nm; ++k) {
+        if (bad[(size_t)k] || np[(size_t)k] < 0 || np[(size_t)k] > bt[(size_t)k].cap) { c->err = no_chain; return STRQ_ERR_DEVICE; }
+        cap_off[(size_t)k + 1] = cap_off[(size_t)k] + (size_t)np[(size_t)k];
+    }
+    // write pass: the counts size the bounds -- dense, exactly as many as were counted (another number sets `bad`)
+    const size_t caps = cap_off[(size_t)nm];
+    STRQ_HIP(c, d->var_bounds.reserve(caps * 8 + 64));
+    int32_t* d_w = d->var_bounds.as<int32_t>(); int32_t* d_br = d_w + caps;
+    std::vector<int32_t> w(caps + 1), br(caps + 1);
+    double launches = in.use_hub ? 1 : 2;          // count pass (behind the traceback on the back-pointer route)
+    if (caps) {
+        for (int k = 0; k < nm; ++k) { VarBoundTask& b = bt[(size_t)k]; b.w = d_w + cap_off[(size_t)k]; b.branch = d_br + cap_off[(size_t)k]; b.cap = np[(size_t)k]; }
+        if (const int rc = bounds()) return rc;
+        launches += 1;
+        STRQ_HIP(c, hipMemcpyAsync(w.data(), d_w, caps * 4, hipMemcpyDeviceToHost, st));
+        STRQ_HIP(c, hipMemcpyAsync(br.data(), d_br, caps * 4, hipMemcpyDeviceToHost, st));
+        STRQ_HIP(c, hipMemcpyAsync(bad.data(), d_bad, (size_t)nm * 4, hipMemcpyDeviceToHost, st));
+    }
+    // scores: the reads with passages by (kernel mode, branches), NB doubles per passage, dense
+    std::vector<size_t> v_off((size_t)nm + 1, 0);
+    for (int k = 0; k < nm; ++k) v_off[(size_t)k + 1] = v_off[(size_t)k] + (size_t)np[(size_t)k] * (size_t)dual_model(c, d, r0 + who[k], DUAL_VAR)->var_nb;
+    const size_t nv = v_off[(size_t)nm];
+    std::vector<double> out(nv + 1);
+    double passages = 0;
+    if (nv) {
+        STRQ_HIP(c, d->var_out.reserve(nv * 8 + 64));
+        double* d_out = d->var_out.as<double>();
+        std::vector<VarRead> rdv; std::vector<int64_t> firstv;
+        struct L { int mode, nb, at, n, first_at; int64_t passages; };
+        std::vector<L> ls;
+        for (int mode = 0; mode < 3; ++mode)
+            for (int nb = 2; nb <= VAR_MAX_NB; ++nb) {
+                L l = {mode, nb, (int)rdv.size(), 0, (int)firstv.size(), 0};
+                for (int k = 0; k < nm; ++k) {
+                    HostModel* hm = dual_model(c, d, r0 + who[k], DUAL_VAR);
+                    if (!np[(size_t)k] || hm->var_mode != mode || hm->var_nb != nb) continue;
+                    VarRead r; r.model = hm->var_dev; r.x = d->modsig.as<double>() + (*in.sig_off)[(size_t)k]; r.w = d_w + cap_off[(size_t)k];
+                    r.out = d_out + v_off[(size_t)k]; r.T = (*in.len)[(size_t)k];
+                    rdv.push_back(r); firstv.push_back(l.passages); l.passages += np[(size_t)k]; ++l.n;
+                }
+                if (!l.n) continue;
+                firstv.push_back(l.passages); ls.push_back(l);
+            }
+        if (firstv.size() > (size_t)nm + 16) { c->err = "variants: workspace"; return STRQ_ERR_NOMEM; }
+        STRQ_HIP(c, hipMemcpyAsync(d_rd, rdv.data(), rdv.size() * sizeof(VarRead), hipMemcpyHostToDevice, st));
+        STRQ_HIP(c, hipMemcpyAsync(d_first, firstv.data(), firstv.size() * 8, hipMemcpyHostToDevice, st));
+        for (const L& l : ls) {
+            if (launch_var_score(st, l.mode, l.nb, d_rd + l.at, d_first + l.first_at, l.n, l.passages, c->n_cu)) { c->err = "variants: launch failed"; return STRQ_ERR_DEVICE; }
+            passages += (double)l.passages;
+        }
+        launches += (double)ls.size();
+        STRQ_HIP(c, hipMemcpyAsync(out.data(), d_out, nv * 8, hipMemcpyDeviceToHost, st));
+    }
+    if (const int rc = pass_stop(c, d, d->var_ms)) return rc;
+    for (int32_t b : bad) if (b) { c->err = no_chain; return STRQ_ERR_DEVICE; }
+    for (int k = 0; k < nm; ++k) {
+        const int i = who[k]; const Target& t = target_of(d, r0 + i);
+        if (vr[(size_t)(*in.slot2)[(size_t)k]].status != 0) continue;          // the variant model found no path: not decoded
+        VariantRow& row = B.var[(size_t)(r0 + i)];
+        row.decoded = 1; row.n_branch = t.var_nalt + 1;
+        const int n = np[(size_t)k]; int64_t units = 0;
+        row.branch.resize((size_t)n); row.end.resize((size_t)n);
+        for (int j = 0; j < n; ++j) {
+            const int32_t b = br[cap_off[(size_t)k] + (size_t)j];
+            row.branch[(size_t)j] = (int8_t)b; units += b ? t.var_ctx + 1 : 1;
+            // observation t of the stretch is raw sample first + t: the repeat section of a flanked model is one contiguous stretch
+            row.end[(size_t)j] = geom[i].prefix_begin + first[(size_t)k] + (int64_t)w[cap_off[(size_t)k] + (size_t)j];
+        }
+        row.V.assign(out.begin() + (ptrdiff_t)v_off[(size_t)k], out.begin() + (ptrdiff_t)v_off[(size_t)k + 1]);
+        row.count_v = (int32_t)(units + t.count_bias);
+        d->var_reads += 1;
+    }
+    d->var_launches += launches; d->var_passages += passages;
+    return STRQ_OK;
+}
+
+// The pass of one of the targets' dual models (`which`) for the reads of one sub-batch whose target has that model: the modification
+// pass (patterns, and the per-unit scores behind them), or the variant pass (strq_set_variants: passages and their scores).
 // The flanked-model Viterbi ran in MARK mode (viterbi_kernels.hip): its result carries the first and
 // last sample decoded into the repeat section, which is all detect step 13 (STRique.py:608) needs.
-static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
+static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, Dual which = DUAL_MOD)
 {
     Batch& B = d->batch;
     hipStream_t st = c->stream;
@@ -410,13 +559,15 @@ static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
     const int64_t s0 = B.off[r0];
     std::vector<int> who;                      // reads that reach the modification model
     for (int i = 0; i < nr; ++i) {
-        if (target_of(d, r0 + i).mod_model_id < 0 || !geom[i].gate) continue;
+        if (dual_id(target_of(d, r0 + i), which) < 0 || !geom[i].gate) continue;
         const VitResult& v = vres[vit_slot[i]];
+        if (v.status == 2 && which == DUAL_VAR) continue;          // not decoded: no variants
         if (v.status == 2) { c->err = "modification pass: repeat window of 2^21 samples or more"; return STRQ_ERR_UNSUPPORTED; }
         if (v.status == 0) who.push_back(i);
     }
     const int nm = (int)who.size();
     if (!nm) return STRQ_OK;
+    if (which == DUAL_VAR) { if (const int rc = pass_start(c, d)) return rc; }          // one bracket around the whole variant pass
     // 1. + 2. the samples decoded into repeat states: one contiguous stretch [enter, leave) of the window,
     //         renormalised from the raw signal and clipped
     std::vector<int64_t> len(nm), first(nm);
@@ -447,7 +598,8 @@ static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
         m.raw = d->batch.raw.as<char>() + (size_t)(s0 + rc[i].off + geom[i].prefix_begin + first[k]) * esz;
         m.out = d->modsig.as<double>() + sig_off[k]; m.T = len[k]; m.is_f64 = B.dtype; m.pad_ = 0;
         m.c1 = rc[i].r_c1; m.h1 = rc[i].r_h1; m.h2 = rc[i].h2; m.c2 = rc[i].c2;
-        m.clip_lo = d->ps.clip_lo; m.clip_hi = d->ps.clip_hi; m.mod_lo = t.mod_min; m.mod_hi = t.mod_max;
+        m.clip_lo = d->ps.clip_lo; m.clip_hi = d->ps.clip_hi;
+        m.mod_lo = which == DUAL_MOD ? t.mod_min : t.var_lo; m.mod_hi = which == DUAL_MOD ? t.mod_max : t.var_hi;
     }
     int64_t* d_len = d->modlen.as<int64_t>();
     STRQ_HIP(c, hipMemcpyAsync(d_mt, mt.data(), (size_t)nm * sizeof(ModTask), hipMemcpyHostToDevice, st));
@@ -457,7 +609,7 @@ static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
     std::vector<GroupItem> items(nm);
     bool use_hub = !strq::opt("STRQ_MOD_BACKPOINTERS");
     for (int k = 0; k < nm; ++k) {
-        HostModel* hm = mod_model(c, d, r0 + who[k]);
+        HostModel* hm = dual_model(c, d, r0 + who[k], which);
         const int shape = vit_shape_of(hm->h);
         if (shape < 0) { c->err = "modification model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
         items[k] = {0, shape, hm->h.n_cells};
@@ -469,7 +621,7 @@ static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
     size_t bp2 = 0, p2 = 0; std::vector<size_t> bp2_off(nm), p2_off(nm);
     for (int k = 0; k < nm; ++k) {
         // back-pointers: uint16 per (time step, state); hub records: 8 bytes per time step (in uint16 units: 4)
-        bp2_off[k] = bp2; bp2 += use_hub ? (size_t)(len[k] + 1) * 4 : (size_t)(len[k] + 1) * mod_model(c, d, r0 + who[k])->h.n_states;
+        bp2_off[k] = bp2; bp2 += use_hub ? (size_t)(len[k] + 1) * 4 : (size_t)(len[k] + 1) * dual_model(c, d, r0 + who[k], which)->h.n_states;
         p2_off[k] = p2; p2 += (size_t)len[k] + 1;
     }
     STRQ_HIP(c, d->bp.reserve(bp2 * 2 + 64));
@@ -481,7 +633,7 @@ static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
     if (const int qrc = reset_queue_heads(c, st)) return qrc;
     for (int k = 0; k < nm; ++k) {
         VitTask& v = vt2[slot2[k]]; v = VitTask();
-        v.model = mod_model(c, d, r0 + who[k])->dev; v.sig = mt[k].out; v.T = len[k]; v.src_kind = VIT_SRC_F64;
+        v.model = dual_model(c, d, r0 + who[k], which)->dev; v.sig = mt[k].out; v.T = len[k]; v.src_kind = VIT_SRC_F64;
         v.bp = d->bp.as<uint16_t>() + bp2_off[k];
         tp2[slot2[k]] = d_path2 + p2_off[k];
     }
@@ -490,6 +642,17 @@ static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
         STRQ_HIP(c, hipMemcpyAsync(d_tb + vg.first, vt2.data() + vg.first, (size_t)vg.count * sizeof(VitTask), hipMemcpyHostToDevice, st));
         if (const int src = sort_viterbi_group(c, st, vg, d_tb, sl.order.as<int>())) return src;
         if (const int lrc = launch_viterbi_group(c, st, vg, d_tb, d_tr, sl.order.as<int>(), c->queue.as<int>() + qi++, use_hub ? VIT_HUB : VIT_BACKPTR)) return lrc;
+    }
+    if (which == DUAL_VAR) {
+        // 4. + 5. passages and their scores (the back-pointer route traces the paths first)
+        if (!use_hub) {
+            STRQ_HIP(c, hipMemcpyAsync(d_tp, tp2.data(), (size_t)nm * 8, hipMemcpyHostToDevice, st));
+            if (launch_vit_traceback(st, d_tb, d_tr, d_tp, nm)) { c->err = "traceback launch failed"; return STRQ_ERR_DEVICE; }
+        }
+        LlrPassIn vi;
+        vi.who = &who; vi.slot2 = &slot2; vi.len = &len; vi.sig_off = &sig_off; vi.bp2_off = &bp2_off; vi.paths = &tp2;
+        vi.use_hub = use_hub; vi.results = d_tr;
+        return run_variant_tail(c, d, sl, vi, first);
     }
     int64_t* d_plen = d_len;
     if (use_hub) {
@@ -510,7 +673,7 @@ static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
         std::vector<PatTask> pt(nm);
         for (int k = 0; k < nm; ++k) {
             const int sl = slot2[k];
-            pt[sl].path = tp2[sl]; pt[sl].tag = mod_model(c, d, r0 + who[k])->h.state_tag; pt[sl].out = d_chars + p2_off[k]; pt[sl].T = len[k];
+            pt[sl].path = tp2[sl]; pt[sl].tag = dual_model(c, d, r0 + who[k], which)->h.state_tag; pt[sl].out = d_chars + p2_off[k]; pt[sl].T = len[k];
             pt[sl].status = &d_tr[sl].status;
         }
         STRQ_HIP(c, hipMemcpyAsync(d_pt, pt.data(), (size_t)nm * sizeof(PatTask), hipMemcpyHostToDevice, st));
@@ -968,6 +1131,7 @@ static int take_rows(strq_ctx* c, DetectState* d, DetectState::Slot& sl, bool un
     publish_timing(c, B);
     // the mode the launches ran with decides, not what the targets say by now
     if (sl.vit_mode == VIT_MARK) { const int mrc = run_mod_pass(c, d, sl); if (mrc) return mrc; }
+    if (sl.vit_mode == VIT_MARK && sl.ex.var) { const int vrc = run_mod_pass(c, d, sl, DUAL_VAR); if (vrc) return vrc; }
     if (sl.ex.units || sl.ex.conf) {
         Decoded dec;
         if (const int drc = read_decoded(c, sl, dec)) return drc;
@@ -1055,7 +1219,8 @@ static void read_table(DetectState* d, SubBatch& S)
             const bool okv = std::isfinite(hs[0]) && hs[1] > 0.0 && std::isfinite(hs[2]) && hs[3] > 0.0 && std::isfinite(hs[3]);
             rc.status = okv ? COND_OK : COND_DEGENERATE;
         }
-        if (!S.nc) S.any_mod |= target_of(d, r0 + i).mod_model_id >= 0;
+        // (the variant pass needs the bounds of the repeat section like the modification pass: a MARK decode)
+        if (!S.nc) S.any_mod |= target_of(d, r0 + i).mod_model_id >= 0 || (d->extras.var && target_of(d, r0 + i).var_model_id >= 0);
     }
     // scan: any candidate may win
     for (int c = 0; c < S.nc; ++c) S.any_mod |= d->targets[d->scan_cand[(size_t)c]].mod_model_id >= 0;
@@ -1552,11 +1717,13 @@ int run_range(strq_ctx* c, DetectState* d, int64_t first, int64_t last)
             if (t.end_model_id < 0 || t.start_model_id < 0) { c->err = "anchored: target without anchored models (strq_target_set_anchored)"; return STRQ_ERR_ARG; }
         }
     }
+    if (d->extras.var && d->scan_on) { c->err = "variants: not available in a scan (strq_scan_set)"; return STRQ_ERR_ARG; }
     B.ran = d->extras;
     d->anch_ms = 0; std::fill(d->anch_kinds, d->anch_kinds + 4, 0.0); d->anch_launches = d->anch_g2 = d->anch_lane = 0;
     d->unit_ms = 0; d->unit_bytes = d->unit_reads = d->unit_positions = 0;
     d->conf_ms = 0; d->conf_windows = d->conf_nopath = d->conf_expo = 0;
     d->llr_ms = 0; d->llr_units = d->llr_reads = d->llr_launches = 0;
+    d->var_ms = 0; d->var_launches = d->var_passages = d->var_reads = 0;
     STRQ_HIP(c, c->redo_total.reserve(64));
     STRQ_HIP(c, hipMemsetAsync(c->redo_total.p, 0, 64, c->stream));
     // partition into sub-batches first, so that the upload of piece k + 1 can overlap the kernels of piece k
@@ -1792,6 +1959,69 @@ int strq_last_mod_llr(strq_ctx* c, double* out4)
     if (!out4) { c->err = "bad argument"; return STRQ_ERR_ARG; }
     DetectState* d = dstate(c);
     out4[0] = d->llr_ms; out4[1] = d->llr_units; out4[2] = d->llr_reads; out4[3] = d->llr_launches;
+    return STRQ_OK;
+}
+
+int strq_target_set_variants(strq_ctx* c, int32_t target_id, int32_t model_id, double lo, double hi, int32_t n_alt, int32_t context_units)
+{
+    STRQ_ENTER(c);
+    DetectState* d = dstate(c);
+    if (target_id < 0 || target_id >= (int32_t)d->targets.size() || model_id < -1 || model_id >= (int32_t)c->models.size()) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    if (model_id >= 0 && (n_alt < 1 || n_alt > VAR_MAX_NB - 1 || context_units < 0 || !(lo < hi))) { c->err = "bad argument (strq_target_set_variants: 1 to 3 alt units, context_units >= 0, lo < hi)"; return STRQ_ERR_ARG; }
+    if (const int rc = drain(c, d)) return rc;          // a sub-batch in flight is taken with the target it ran with
+    if (model_id >= 0) { if (const int rc = variant_model(c, c->models[model_id], n_alt)) return rc; }          // (the target stays as it was)
+    Target& t = d->targets[target_id];
+    t.var_model_id = model_id; t.var_nalt = model_id < 0 ? 0 : n_alt; t.var_ctx = model_id < 0 ? 0 : context_units;
+    t.var_lo = model_id < 0 ? 0 : lo; t.var_hi = model_id < 0 ? 0 : hi;
+    return STRQ_OK;
+}
+
+int strq_set_variants(strq_ctx* c, int32_t on)
+{
+    STRQ_ENTER(c);
+    return set_extra(c, on, "bad argument (strq_set_variants takes 0 or 1)", &Extras::var);
+}
+
+int strq_batch_fetch_variants(strq_ctx* c, int32_t* count_v, int32_t* decoded, int64_t* off, int8_t* branch, int64_t* end, int64_t pass_cap,
+                              double* vpool, int64_t* voff, int64_t v_cap, int64_t* v_total)
+{
+    STRQ_ENTER(c);
+    if (!off) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    DetectState* d = dstate(c);
+    if (const int rc = drain(c, d)) return rc;
+    const Batch& B = d->batch;
+    if (!B.ran.var) { c->err = "the last batch ran without variants (strq_set_variants)"; return STRQ_ERR_ARG; }
+    const bool pools = branch || end || vpool || voff;
+    if (pools && !(branch && end && vpool && voff)) { c->err = "bad argument (strq_batch_fetch_variants: all pools or none)"; return STRQ_ERR_ARG; }
+    int64_t pos = 0, vpos = 0;
+    for (int64_t i = 0; i < B.n_reads; ++i) {
+        const VariantRow& r = B.var[(size_t)i];
+        off[i] = pos;
+        if (count_v) count_v[i] = r.count_v;
+        if (decoded) decoded[i] = r.decoded;
+        const int64_t n = (int64_t)r.branch.size();
+        if (pools) {
+            if (pos + n > pass_cap || vpos + (int64_t)r.V.size() > v_cap) { c->err = "variant pool too small"; return STRQ_ERR_ARG; }
+            for (int64_t j = 0; j < n; ++j) {
+                branch[pos + j] = r.branch[(size_t)j]; end[pos + j] = r.end[(size_t)j];
+                voff[pos + j] = vpos + j * r.n_branch;
+            }
+            if (!r.V.empty()) std::memcpy(vpool + vpos, r.V.data(), r.V.size() * 8);
+        }
+        pos += n; vpos += (int64_t)r.V.size();
+    }
+    off[B.n_reads] = pos;
+    if (pools) voff[pos] = vpos;
+    if (v_total) *v_total = vpos;
+    return STRQ_OK;
+}
+
+int strq_last_variants(strq_ctx* c, double* out4)
+{
+    STRQ_ENTER(c);
+    if (!out4) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    DetectState* d = dstate(c);
+    out4[0] = d->var_launches; out4[1] = d->var_passages; out4[2] = d->var_ms; out4[3] = d->var_reads;
     return STRQ_OK;
 }
 

@@ -178,6 +178,7 @@ viterbi_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ result
     constexpr bool single_stage = SS;
     // everything a lane needs about the states it owns lives in registers (reloaded when the model changes)
     int own_e[EPL], einc[EPL]; bool enorm[EPL]; bool etag[EPL]; bool ehub[EPL], erec[EPL];
+    uint32_t ebranch[EPL];      // HUB: branch id of the state owned by (slot, lane): tag 1 -> 1, 3 -> 2, 4 -> 3 (variant models), else 0
     int eunit[EPL];      // UNIT: record index of the counted state owned by (slot, lane), -1 none
     const char* esrc[EPL][DEMAX]; char* edst[EPL];
     double ea[EPL], eb[EPL], ec[EPL], elp[EPL][DEMAX];
@@ -212,6 +213,7 @@ viterbi_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ result
                 etag[s] = own_e[s] >= 0 && M.state_tag[own_e[s]] == 1;
                 ehub[s] = own_e[s] >= 0 && M.state_tag[own_e[s]] == 2;
                 erec[s] = own_e[s] >= 0 && own_e[s] == M.rec_state;
+                if constexpr (HUB) { const int tg = own_e[s] >= 0 ? M.state_tag[own_e[s]] : 0; ebranch[s] = tg == 1 ? 1u : (tg >= 3 ? (uint32_t)(tg - 1) : 0u); }
                 if constexpr (UNIT) eunit[s] = own_e[s] < 0 ? -1 : (own_e[s] == M.unit_state[0] ? 0 : (own_e[s] == M.unit_state[1] ? 1 : -1));
                 edst[s] = vbase + 16 * (own_e[s] >= 0 ? s * 64 + lane : TRASH);
 #pragma unroll
@@ -454,7 +456,7 @@ viterbi_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ result
                     nc[s] = ((uint64_t)hi << 32) | lo;
                 } else if constexpr (HUB) {
                     uint32_t lo = (uint32_t)bc, hi = (uint32_t)((uint64_t)bc >> 32);      // last e0 time, branch of the current unit
-                    if (!ehub[s]) hi = etag[s] ? 1u : 0u;
+                    if (!ehub[s]) hi = ebranch[s];
                     if (erec[s] && tk.bp) {
                         reinterpret_cast<uint64_t*>(tk.bp)[t + 1] = ((uint64_t)hi << 32) | lo;      // record of this e0 emission
                         lo = tt1;

@@ -398,6 +398,49 @@ class Context(object):
         self._check(self._lib.strq_last_mod_llr(self._h, _ptr(out)))
         return {'ms': float(out[0]), 'units': int(out[1]), 'reads': int(out[2]), 'launches': int(out[3])}
 
+    # ---- variants ------------------------------------------------------------------------
+    def target_set_variants(self, target_id, model_id, lo, hi, n_alt, context_units):
+        """strq_target_set_variants: the variant model of a target (hmm.RepeatVariantModel), the range its stretch is clipped to, its
+        alt branches and context units; model_id = -1 takes it away.  StriqueHipError (STRQ_ERR_UNSUPPORTED) for a model the pass
+        does not cover: the target stays as it was."""
+        self._check(self._lib.strq_target_set_variants(self._h, ctypes.c_int32(target_id), ctypes.c_int32(model_id), ctypes.c_double(lo), ctypes.c_double(hi),
+                                                       ctypes.c_int32(n_alt), ctypes.c_int32(context_units)))
+
+    def set_variants(self, on):
+        """strq_set_variants: later run calls also decode the variant model of every decoded read whose target has one
+        (batch_fetch_variants)."""
+        self._check(self._lib.strq_set_variants(self._h, ctypes.c_int32(1 if on else 0)))
+
+    def batch_fetch_variants(self):
+        """Variants of the last batch (strq_batch_fetch_variants): per read None (not decoded, or a target without a variant model) or
+        (count_v, branch int8 [n], end int64 [n], V float64 [n, n_branches]) of its n passages in signal order."""
+        n = getattr(self, '_n_batch', 0)
+        count_v = np.zeros(max(1, n), np.int32); dec = np.zeros(max(1, n), np.int32); off = np.zeros(n + 1, np.int64)
+        vt = ctypes.c_int64(0)
+        self._check(self._lib.strq_batch_fetch_variants(self._h, _ptr(count_v), _ptr(dec), _ptr(off), None, None, ctypes.c_int64(0),
+                                                        None, None, ctypes.c_int64(0), ctypes.byref(vt)))
+        npass = int(off[-1])
+        branch = np.zeros(max(1, npass), np.int8); end = np.zeros(max(1, npass), np.int64)
+        vpool = np.zeros(max(1, vt.value), np.float64); voff = np.zeros(npass + 1, np.int64)
+        self._check(self._lib.strq_batch_fetch_variants(self._h, _ptr(count_v), _ptr(dec), _ptr(off), _ptr(branch), _ptr(end), ctypes.c_int64(len(branch)),
+                                                        _ptr(vpool), _ptr(voff), ctypes.c_int64(len(vpool)), None))
+        out = []
+        for i in range(n):
+            if not dec[i]:
+                out.append(None)
+                continue
+            a, b = int(off[i]), int(off[i + 1])
+            nb = int(voff[a + 1] - voff[a]) if b > a else 0
+            V = vpool[voff[a]:voff[b]].reshape(b - a, nb).copy() if b > a else np.zeros((0, 0))
+            out.append((int(count_v[i]), branch[a:b].copy(), end[a:b].copy(), V))
+        return out
+
+    def last_variants(self):
+        """The variant pass of the last run call: {'launches', 'passages', 'ms', 'reads'} (strq_last_variants)."""
+        out = np.zeros(4)
+        self._check(self._lib.strq_last_variants(self._h, _ptr(out)))
+        return {'launches': int(out[0]), 'passages': int(out[1]), 'ms': float(out[2]), 'reads': int(out[3])}
+
     # ---- anchored counting ---------------------------------------------------------------
     def target_set_anchored(self, target_id, end_model_id, end_bias, start_model_id, start_bias):
         """strq_target_set_anchored: the end / start model of a target (hmm.AnchoredRepeatModel) and their count biases."""

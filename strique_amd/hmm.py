@@ -331,6 +331,90 @@ class RepeatModModel(object):
         self.baked = bake(g, count_states=(), tag_substring='mod', tag2_states=(s0, e0))
 
 
+VARIANT_TAGS = (1, 3, 4)        # state tag of alt branch 1 / 2 / 3 (0 base, 2 hub: as the dual model of RepeatModModel)
+
+
+def check_alt_units(repeat, alt_units):
+    """The alt units of a variant model, upper-cased: 1 to 3 units over ACGT, as long as `repeat`, each different from it and from
+    the others.  ValueError names the unit that is not."""
+    repeat = repeat.upper()
+    if isinstance(alt_units, str):
+        alt_units = [alt_units]
+    alts = [str(a).upper() for a in alt_units]
+    if not 1 <= len(alts) <= len(VARIANT_TAGS):
+        raise ValueError("alt units: between 1 and %d units per target, got %d (%s)" % (len(VARIANT_TAGS), len(alts), ",".join(alts)))
+    for i, a in enumerate(alts):
+        if not a or set(a) - set("ACGT"):
+            raise ValueError("alt unit %r: only the letters A, C, G, T" % a)
+        if len(a) != len(repeat):
+            raise ValueError("alt unit %r: %d nt, the repeat unit %s has %d" % (a, len(a), repeat, len(repeat)))
+        if a == repeat:
+            raise ValueError("alt unit %r is the repeat unit itself" % a)
+        if a in alts[:i]:
+            raise ValueError("alt unit %r is given twice" % a)
+    return alts
+
+
+def variant_context_units(repeat, kmer):
+    """m: the units in front of an alt unit whose k-mers reach into it."""
+    return -(-(kmer - 1) // len(repeat))
+
+
+class RepeatVariantModel(object):
+    """The repeat-unit profile and one profile per alt unit side by side between two emitting hub states: the topology of
+    RepeatModModel with up to four branches over one pore model.  Branch b >= 1 holds the k-mers of repeat * m + alt_b that start in
+    the m context units in front of the alt unit and in the alt unit itself (m = variant_context_units), so one passage through it
+    covers m + 1 units of signal.  HMM-config key `variant_prior` = p: every alt branch is entered with p, the base branch with
+    1 - (NB - 1) p; without it all NB branches alike."""
+
+    def __init__(self, repeat, alt_units, pm, config=None):
+        tp = _layer({'rep_std_scale': 1.5, 'rep_std_offset': 0.0, 'leave_repeat': .002, 'variant_prior': None},
+                    config if isinstance(config, dict) else None)
+        repeat = repeat.upper()
+        self.alt_units = check_alt_units(repeat, alt_units)
+        K, L = pm.kmer, len(repeat)
+        m = self.context_units = variant_context_units(repeat, K)
+        NB = self.n_branches = 1 + len(self.alt_units)
+        self.model_min, self.model_max = pm.model_min, pm.model_max
+        g = Graph()
+        s0 = g.add_state('s0', UNIFORM, (pm.model_min, pm.model_max))
+        e0 = g.add_state('e0', UNIFORM, (pm.model_min, pm.model_max))
+        kw = dict(no_silent=True, std_scale=tp['rep_std_scale'], std_offset=tp['rep_std_offset'])
+        profiles = [add_profile(g, extend_repeat(repeat, K)[0], pm, tp, 'base', **kw)]
+        for b, alt in enumerate(self.alt_units, 1):
+            profiles.append(add_profile(g, (repeat * m + alt + repeat * K)[:(m + 1) * L + K - 1], pm, tp, 'alt%d' % b, **kw))
+        p_alt = tp['variant_prior']
+        if p_alt is None:
+            prior = [1.0 / NB] * NB
+        else:
+            if not 0.0 < p_alt * (NB - 1) < 1.0:
+                raise ValueError("variant_prior %r: the %d alt branches must leave the base branch a probability above 0" % (p_alt, NB - 1))
+            prior = [1.0 - (NB - 1) * p_alt] + [p_alt] * (NB - 1)
+        g.add_transition(g.start, s0, 1)
+        for p, pr in zip(profiles, prior):
+            g.add_transition(s0, p.s1, pr / 2)
+            g.add_transition(s0, p.s2, pr / 2)
+        for p in profiles:
+            g.add_transition(p.e1, e0, 1)
+            g.add_transition(p.e2, e0, 1)
+        g.add_transition(e0, g.end, tp['leave_repeat'])
+        g.add_transition(e0, s0, 1 - tp['leave_repeat'])
+        lay = {}
+        lane = 0
+        for group in [q for p in profiles for q in (p.match, p.insert)] + [[s0, e0]]:
+            for st in group:
+                lay[st] = (0, lane); lane += 1
+        if lane <= 64:
+            g.layout = lay
+        self.graph = g
+        self.hub_states = (s0, e0)
+        extra = {}
+        for b, p in enumerate(profiles[1:]):
+            for st in p.match + p.insert:
+                extra[st] = VARIANT_TAGS[b]
+        self.baked = bake(g, count_states=(), tag2_states=(s0, e0), extra_tags=extra)
+
+
 # ---------------------------------------------------------------------------------------------
 BakedHMM = namedtuple("BakedHMM", [
     "n_states", "silent_start", "start", "end",
@@ -345,7 +429,8 @@ BakedHMM = namedtuple("BakedHMM", [
 ], defaults=(None, None, None))
 
 
-def bake(g, count_states=(), tag_substring=None, tag2_states=()):
+def bake(g, count_states=(), tag_substring=None, tag2_states=(), extra_tags=None):
+    """`extra_tags`: state -> tag for states that are neither hubs (`tag2_states`) nor named after `tag_substring`."""
     n = len(g.names)
     alive = [True] * n
     edges = [(a, b, math.log(p) if p > 0 else -math.inf) for a, b, p in g.edges]
@@ -465,6 +550,9 @@ def bake(g, count_states=(), tag_substring=None, tag2_states=()):
         count_inc[new[s]] = 1
     tag = np.array([2 if old in tag2_states else (1 if (tag_substring and tag_substring in g.names[old]) else 0)
                     for old in final], np.int32)
+    for k, old in enumerate(final):
+        if extra_tags and old in extra_tags:
+            tag[k] = extra_tags[old]
     hint_slot = np.full(m, -1, np.int32); hint_lane = np.full(m, -1, np.int32)
     if g.layout and all(old in g.layout for old in emitting):
         for old in emitting:

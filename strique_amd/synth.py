@@ -141,3 +141,23 @@ def make_read(table, config_id, read_idx, total_nt, target, n_repeat, strand=Non
     repeat, prefix, suffix = target
     seq = make_sequence(rng, total_nt, prefix, repeat, n_repeat, suffix, strand)
     return make_signal(rng, table, seq, as_int16, realism, noise), strand
+
+
+def make_variant_read(seed, table, target, n_units, alt, strand, flank_nt=3000, base_positions=(8, 20, 32, 44), as_int16=True, noise=None):
+    """A read whose repeat array holds interruptions: `flank_nt` of random background on either side of prefix + n_units units +
+    suffix, the units at base_positions + U{0..3} replaced by `alt` (on the + strand, like the target = (repeat, prefix, suffix)).
+    Returns (signal, planted): the planted unit indices in signal order -- on the - strand the read runs through the array
+    backwards, unit i of the + strand is unit n_units - 1 - i of the signal."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    repeat, prefix, suffix = (s.upper() for s in target)
+    planted = [int(p) + int(j) for p, j in zip(base_positions, rng.integers(0, 4, len(base_positions)))]
+    units = [repeat] * n_units
+    for p in planted:
+        units[p] = alt.upper()
+    letters = np.frombuffer(b"ACGT", np.uint8)
+    left = letters[rng.integers(0, 4, flank_nt)].tobytes(); right = letters[rng.integers(0, 4, flank_nt)].tobytes()
+    seq = left + (prefix + "".join(units) + suffix).encode() + right
+    if strand == "-":
+        seq = seq.translate(_COMP)[::-1]
+        planted = sorted(n_units - 1 - p for p in planted)
+    return make_signal(rng, table, seq, as_int16, 0.0, noise), planted
