@@ -394,6 +394,43 @@ int strq_batch_fetch_anchored(strq_ctx* ctx, strq_anchored* out, int64_t n);
  * windows that ran on the register-resident / on a lane-layout kernel shape.  After a run call that failed inside the pass the
  * figures are those of the part that ran (the rows of the failed sub-batch are back at their initial values). */
 int strq_last_anchored(strq_ctx* ctx, double* out8);
+/* ---- renorm: a second normalisation step for reads that are mostly repeat (no counterpart in the reference, whose 'minmax' map,
+ * STRique.py:150-180, assumes that a read's k-mer composition looks like the pore model's) ----
+ * Between the conditioning statistics and the flank alignments, every conditioned read of a target with tables gets scale and shift
+ * of each of its normalised signals (0 the 8-bit morphology levels, 1 the median-filtered signal, 2 the raw signal where the target
+ * has a modification model) refitted against the mixture w * (the target's repeat k-mers) + (1 - w) * (all k-mers) on a grid of 1024
+ * bins: alpha = a / 64, beta = b bins, w one of 15 shares.  The fit maximises an int64 score over the signal's histogram
+ * (strique_amd/renorm.py states grid, tables, schedule and tie rule; the kernels apply the same integer arithmetic).  A read whose
+ * filtered signal fits a share below min_share keeps all its maps (applied = 0); every other fitted read gets the corrected c1, h1
+ * of its fitted signals and the level values of the morphology signal, and everything behind conditioning runs on them. */
+typedef struct strq_renorm_fit {
+    int32_t a, b, w;        /* alpha * 64, beta in bins, index of the share */
+    int32_t fitted;         /* 0: not fitted (degenerate read, empty histogram, no tables, no such signal); the other fields are zero then */
+    int64_t score;          /* the best score */
+} strq_renorm_fit;
+typedef struct strq_renorm {
+    int32_t applied, pad_;
+    strq_renorm_fit fit[3]; /* morphology levels, filtered signal, raw signal */
+} strq_renorm;
+/* The tables of a target: Q[15][1024] (the scores of the grid's bins per share, |Q| < 2^15), q_out (the score of a bin mapped outside
+ * the grid), A[105] (A[a] = the score of the scale a; entries below 24 are not read), W[15] (the shares), and the grid: start of bin
+ * 0, bin width, pivot.  W and the grid belong to the context: while another target holds tables, a call whose W or grid differ from theirs is
+ * refused (STRQ_ERR_ARG).  A call replaces the tables the target had (they are freed); Q = NULL takes them away. */
+int strq_target_set_renorm(strq_ctx* ctx, int32_t target_id, const int16_t* Q, int32_t q_out, const int32_t* A, const double* W,
+                           double grid_lo, double grid_d, double grid_p);
+/* on = 1: later run calls refit the maps as described above.  STRQ_ERR_ARG for min_share outside (0, 1) (it has no default), and
+ * while a scan is set (strq_scan_set); a run call with the switch on fails before any launch (STRQ_ERR_ARG) when a read's target has
+ * no tables, and when it is a scan.  Sub-batches still in flight keep the mode they were launched with (the call waits for them).
+ * Default 0: no further kernel runs and no further buffer is reserved. */
+int strq_set_renorm(strq_ctx* ctx, int32_t on, double min_share);
+/* One record per read of the last batch (n = its reads).  STRQ_ERR_ARG when the last run call ran with the switch off. */
+int strq_batch_fetch_renorm(strq_ctx* ctx, strq_renorm* out, int64_t n);
+/* The renorm pass of the last run call: out[0] = ms on the GPU (all its sub-batches), out[1] = reads whose filtered
+ * signal was fitted, out[2] = reads applied, out[3] = kernels launched (0 with the switch off). */
+int strq_last_renorm(strq_ctx* ctx, double* out4);
+/* Testing: the fit kernel alone on three histograms of 1024 counters (every one below 2^31) with the tables of `target_id`:
+ * out->fit[k] is the fit of h3[k * 1024 ..], out->applied stays 0. */
+int strq_debug_renorm_fit(strq_ctx* ctx, int32_t target_id, const uint32_t* h3, strq_renorm* out);
 /* A host-side helper, not on the path of strq_detect_batch (which takes these on the GPU): the statistics of float64 reads
  * with numpy's arithmetic (no context, no device): out[6 * i ..] = median, MAD, c1, h1 of
  * medfilt(read i, 3) and c1, h1 of read i itself (0, 1 unless want_raw) -- what numpy's median / mean / percentile

@@ -22,6 +22,7 @@ from collections import defaultdict, deque, namedtuple
 import numpy as np
 
 from . import anchored as anchored_mod
+from . import renorm as renorm_mod
 from . import scan as scan_mod
 from .counter import Detected
 
@@ -263,6 +264,12 @@ def count(argv):
                                                                            "free_samples in the thousands means the read was wrongly taken for anchored)")
     parser.add_argument("--anchored-min-score", type=float, default=None, metavar="X", help="--anchored: a flank counts as found when its normalised score is at least X.  "
                                                                                            "Required with --anchored: there is no default (README, 'Anchored counting')")
+    parser.add_argument("--renorm", type=float, default=None, metavar="MIN_SHARE", help="Refit scale and shift of every read's normalised signals against its target's k-mer "
+                                                                                      "composition, and count on the corrected signals where the fitted repeat share is at least "
+                                                                                      "MIN_SHARE (inside (0, 1); there is no default: README, 'Renorm').  The count rows of such "
+                                                                                      "reads change: reads that are mostly repeat are the ones detect() loses without it")
+    parser.add_argument("--renorm-out", dest="renorm_out", default=None, metavar="FILE", help="--renorm: also write the fit of every read to FILE: one row per count row, columns " +
+                                                                                                " ".join(renorm_mod.HEADER) + " ('-' where a signal was not fitted)")
     parser.add_argument("--strict", action="store_true", help="Exit with status 2 when any read could not be processed (the reference only logs such reads and exits 0)")
     args = parser.parse_args(argv)
     if args.scan and args.confidence:
@@ -292,6 +299,12 @@ def count(argv):
         parser.error("--anchored-min-score needs --anchored FILE")
     if args.anchored_min_score is not None and not args.anchored_min_score > 0:
         parser.error("--anchored-min-score must be above 0")
+    if args.renorm is not None and not 0 < args.renorm < 1:
+        parser.error("--renorm MIN_SHARE must be inside (0, 1)")
+    if args.renorm_out and args.renorm is None:
+        parser.error("--renorm-out needs --renorm MIN_SHARE")
+    if args.renorm is not None and args.scan:
+        parser.error("--renorm cannot be combined with --scan: the fit needs the target of a read, which a scan finds with the maps as they are")
     log = Log(args.log_level)
     config = parse_config(args.repeat, args.config, log)
     alt_units = {}
@@ -360,7 +373,8 @@ def count(argv):
         readers = max(1, min(24, share))            # inflating is what the readers do: one per core they can get, 16 ... 24 measure the same end to end
     stats = {}
     fault = 0
-    paths = dict(units=args.units, confidence=args.confidence, mod_llr=args.mod_llr, scores=args.scan_scores, anchored=args.anchored, variants=args.variants)
+    paths = dict(units=args.units, confidence=args.confidence, mod_llr=args.mod_llr, scores=args.scan_scores, anchored=args.anchored, variants=args.variants,
+                 renorm=args.renorm_out)
     with contextlib.ExitStack() as stack:
         # rank 0 writes: as the batches are done in a single process (run_count), after the gather otherwise
         files = {name: stack.enter_context(open(path, 'w')) if (path and rank == 0) else None for name, path in paths.items()}
@@ -371,7 +385,8 @@ def count(argv):
                              units=bool(args.units), units_out=now['units'], scan=scan, scores_out=now['scores'],
                              confidence=bool(args.confidence), conf_out=now['confidence'], mod_llr=bool(args.mod_llr), llr_out=now['mod_llr'],
                              anchored=args.anchored_min_score, anchored_out=now['anchored'],
-                             variants=alt_units if args.variants else None, variants_out=now['variants'])
+                             variants=alt_units if args.variants else None, variants_out=now['variants'],
+                             renorm=args.renorm, renorm_out=now['renorm'])
         except DeviceFault:
             if world == 1:
                 raise SystemExit(3)
@@ -386,7 +401,7 @@ def count(argv):
                 dist.destroy_process_group()
                 raise SystemExit(3)
             merged = gather_rows(rows, stats["items"], sdist, units=bool(args.units), scan=scan, confidence=bool(args.confidence), mod_llr=bool(args.mod_llr),
-                                 anchored=bool(args.anchored), variants=bool(args.variants))
+                                 anchored=bool(args.anchored), variants=bool(args.variants), renorm=args.renorm is not None)
             if rank == 0:
                 write_rows(out, merged.rows)
                 for o in OUTPUTS:
@@ -605,13 +620,16 @@ OUTPUTS = (
     Output('scores', lambda scan: scan_mod.scores_header(scan["candidates"]),
            lambda q, t, s, row, v: scan_mod.format_scores(q, None if row is None else (t, s), v),
            lambda v: _floats(x for pair in v for x in pair), lambda text: list(zip(*[iter(_unfloats(text))] * 2)), 'score_rows', True),
+    Output('renorm', lambda scan: renorm_mod.HEADER, lambda q, t, s, row, v: renorm_mod.format_row(q, t, s, v),
+           lambda v: renorm_mod.pack(v), lambda text: renorm_mod.unpack(text), 'renorm_rows', False),
     Output('variants', lambda scan: VARIANTS_HEADER, lambda q, t, s, row, v: format_variants(q, t, s, row[0], v),
            lambda v: _pack_variants(v), lambda text: _unpack_variants(text), 'variant_rows', False),
     Output('anchored', lambda scan: anchored_mod.HEADER, lambda q, t, s, row, v: anchored_mod.format_row(q, t, s, v),
            lambda v: _pack_anchored(v), lambda text: _unpack_anchored(text), 'anchored_rows', False),
 )
-# (`variants` and `anchored`, the last fields, default to None: callers that build a Merged from the five values before them keep working)
-Merged = namedtuple('Merged', ['rows'] + [o.name for o in OUTPUTS], defaults=(None, None))
+# (`renorm`, `variants` and `anchored`, the last fields, default to None: callers that build a Merged from the five values before them keep
+# working.  `anchored` stays the last field, as it did when `variants` came in: fields behind the first five are taken by name.)
+Merged = namedtuple('Merged', ['rows'] + [o.name for o in OUTPUTS], defaults=(None, None, None))
 
 
 def _pack_anchored(rec):
@@ -626,7 +644,7 @@ def _unpack_anchored(text):
 
 
 def outputs_on(**flags):
-    """The entries of OUTPUTS whose flag (units=, confidence=, mod_llr=, scores=, anchored=, variants=) is set."""
+    """The entries of OUTPUTS whose flag (units=, confidence=, mod_llr=, scores=, anchored=, variants=, renorm=) is set."""
     return [o for o in OUTPUTS if flags.get(o.name)]
 
 
@@ -646,7 +664,8 @@ def _read_values(target, strand, det, scores=None):
     """What the writers know of one read: (target, strand, row or None, {output name: value or None})."""
     if det is None:
         return target, strand, None, dict(scores=scores)
-    return target, strand, det.row, dict(units=det.units, confidence=det.conf, mod_llr=det.llr, scores=scores, anchored=det.anchored, variants=det.variants)
+    return target, strand, det.row, dict(units=det.units, confidence=det.conf, mod_llr=det.llr, scores=scores, anchored=det.anchored, variants=det.variants,
+                                         renorm=getattr(det, 'renorm', None))
 
 
 def _emit(sink, on, seq, qname, target, strand, row, values):
@@ -680,13 +699,13 @@ def unpack_blob(on, blob):
     return fields[0], fields[1], fields[2], values
 
 
-def gather_rows(rows, items, sdist, units=False, scan=None, confidence=False, mod_llr=False, anchored=False, variants=False):
+def gather_rows(rows, items, sdist, units=False, scan=None, confidence=False, mod_llr=False, anchored=False, variants=False, renorm=False):
     """Reads of this rank (run_count with world > 1) -> fixed-size records + one blob per read (pack_blob) -> one gather -> on rank 0
-    the rows of every file in input order: Merged(rows, units, confidence, mod_llr, scores, variants, anchored), [(sequence number, TSV row)] each, None
+    the rows of every file in input order: Merged(rows, units, confidence, mod_llr, scores, renorm, variants, anchored), [(sequence number, TSV row)] each, None
     for an output that was not asked for (scores: asked for by scan) and for every field off rank 0.  `items`: every accepted (qname,
     strand, target) of the input, which each rank derives from the same SAM file (scan: from the same index).  A read that failed
     travels as a record with valid = 0 and writes nothing; a scan read without a winner as one with valid = 2: it writes a score row."""
-    on = outputs_on(units=units, confidence=confidence, mod_llr=mod_llr, scores=bool(scan), anchored=anchored, variants=variants)
+    on = outputs_on(units=units, confidence=confidence, mod_llr=mod_llr, scores=bool(scan), anchored=anchored, variants=variants, renorm=renorm)
     rec = np.zeros(len(rows), ROW_DTYPE); blobs = []; idx = np.zeros(len(rows), np.int64)
     for k, (seq, read) in enumerate(rows):
         idx[k] = seq
@@ -743,7 +762,7 @@ def route(stream, loci, log):
 
 def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, out=None, readers=0, stats=None, units=False, units_out=None,
               scan=None, scores_out=None, confidence=False, conf_out=None, mod_llr=False, llr_out=None, anchored=None, anchored_out=None,
-              variants=None, variants_out=None):
+              variants=None, variants_out=None, renorm=None, renorm_out=None):
     """Route the SAM records of `stream` to their targets, run this rank's share through
     `counter.detect_batch` and return [(sequence number, TSV row or -- several ranks -- what gather_rows takes)].
 
@@ -765,6 +784,9 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
     `variants` ({target: [alt units as configured]}, not with scan; the counter's targets were added with them): the counter is asked
     for Detected records with the variant pass on (counter.set_variants(True), counter.detect_batch(..., records=True)); their rows
     (variant_value, format_variants) go to `variants_out` and to stats["variant_rows"].  The count rows and the other files do not change.
+    `renorm` (a share threshold inside (0, 1), not with scan): the second normalisation step is on for this run
+    (counter.set_renorm(threshold)) and the counter is asked for Detected records; the fit of every read (strique_amd.renorm.report,
+    format_row) goes to `renorm_out` and to stats["renorm_rows"].  The count rows of the reads it applies to change.
     `scan` ({"min_score", "candidates", "scores"}): `stream` is a list of read ids instead of a SAM stream; every read goes through
     counter.scan_batch and takes target and strand from its winner -- a read without one writes no row, as a read without a target
     writes none; single process: the score rows (strique_amd.scan.format_scores, every read) go to `scores_out` and to
@@ -778,20 +800,28 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
         raise ValueError("anchored counting cannot be combined with a scan")
     if variants is not None and scan:
         raise ValueError("variants cannot be combined with a scan")
-    files = dict(rows=out, units=units_out, confidence=conf_out, mod_llr=llr_out, scores=scores_out, anchored=anchored_out, variants=variants_out)
+    if renorm is not None and scan:
+        raise ValueError("renorm cannot be combined with a scan")
+    if renorm is not None and not 0 < renorm < 1:
+        raise ValueError("the renorm share threshold must be inside (0, 1)")
+    files = dict(rows=out, units=units_out, confidence=conf_out, mod_llr=llr_out, scores=scores_out, anchored=anchored_out, variants=variants_out,
+                 renorm=renorm_out)
     on = outputs_on(units=units, confidence=confidence, mod_llr=mod_llr, scores=scan and scan["scores"], anchored=anchored is not None,
-                    variants=variants is not None)
+                    variants=variants is not None, renorm=renorm is not None)
     if out is not None:
         print('\t'.join(HEADER), file=out)
     for o in OUTPUTS:
         stats.setdefault(o.stat, [])
         if files[o.name] is not None:
             print('\t'.join(o.header(scan)), file=files[o.name])
-    extras = {o.name: True for o in on if o.name not in ('scores', 'anchored', 'variants')}
+    extras = {o.name: True for o in on if o.name not in ('scores', 'anchored', 'variants', 'renorm')}
     if anchored is not None:
         extras.update(anchored=anchored, records=True)
     if variants is not None:
         counter.set_variants(True)
+        extras.update(records=True)
+    if renorm is not None:
+        counter.set_renorm(renorm)
         extras.update(records=True)
     rows = []
     records = ((rid, '.', ['.'], 0) for rid in stream) if scan else route(stream, loci, log)
@@ -856,6 +886,8 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
                 det = as_detected(res, units, confidence, mod_llr)
                 if variants is not None:
                     det = det._replace(variants=variant_value(det.variants, variants.get(target, ())))
+                if renorm is not None:
+                    det = det._replace(renorm=renorm_mod.report(det.renorm, counter.renorm_bin_width))
                 read = _read_values(target, strand, det)
             if world > 1:
                 sink['rows'].append((seq, read))
@@ -977,6 +1009,8 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
                 pool.shutdown()
             if variants is not None:
                 counter.set_variants(False)          # the switch belongs to this run
+            if renorm is not None:
+                counter.set_renorm(None)
         else:
             # an exception is on its way out (a DeviceFault from the engine thread, a broken input): the batch queued behind
             # the failed one must not be handed to a device that may be hung, and nobody waits for it -- the caller exits,

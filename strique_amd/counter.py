@@ -17,6 +17,7 @@ import numpy as np
 from . import anchored as anchored_mod
 from . import ffi
 from . import hmm as hmm_mod
+from . import renorm as renorm_mod
 from .pore_model import pore_model
 
 ALIGN_DEFAULTS = {'dist_offset': 16.0, 'dist_min': 0.0, 'gap_open_h': -1.0, 'gap_open_v': -16.0,
@@ -36,7 +37,8 @@ target_classifier = namedtuple('target_classifier',
 # (log_lik, count_mean, count_sd), per-unit log-likelihood ratios, the anchored record (kind, status, count, log_p, begin, end,
 # free_samples -- every kind, as strq_batch_fetch_anchored hands it out); see repeatCounter.detect_batch
 # variants: (count_v, pattern, branch, end, V) of the variant pass, see repeatCounter.detect_batch
-Detected = namedtuple('Detected', ['row', 'units', 'conf', 'llr', 'anchored', 'variants'], defaults=(None, None))
+# renorm: (applied, {signal: None or (a, b, w, score)}) of the second normalisation step, see repeatCounter.set_renorm
+Detected = namedtuple('Detected', ['row', 'units', 'conf', 'llr', 'anchored', 'variants', 'renorm'], defaults=(None, None, None))
 
 
 class repeatCounter(object):
@@ -66,6 +68,8 @@ class repeatCounter(object):
         self.variant_models = {}
         self.variant_refused = {}      # {target_id: message} of the variant models strq_target_set_variants refused
         self.variants = False          # set_variants
+        self.renorm = None             # set_renorm: min_share, or None
+        self._renorm_done = set()      # classifiers whose tables are registered
 
     # -------------------------------------------------------------------------------------
     def _classifier(self, repeat, prefix, suffix, prefix_ext, suffix_ext):
@@ -122,6 +126,34 @@ class repeatCounter(object):
             self.variant_models[tid] = m
         if refused is not None:
             raise refused
+
+    def _ensure_renorm(self):
+        """The tables of the second normalisation step for every classifier that has none yet (strique_amd.renorm.tables)."""
+        for tid, (repeat, _, _) in self._anchored_src.items():
+            if tid in self._renorm_done:
+                continue
+            Q, A = renorm_mod.tables(self.pm.model_dict, self.pm.kmer, self.pm.model_min, self.pm.model_max, repeat)
+            self.ctx.target_set_renorm(tid, Q, A, self.pm.model_min, self.pm.model_max)
+            self._renorm_done.add(tid)
+
+    def set_renorm(self, min_share):
+        """min_share in (0, 1): detect and detect_batch refit scale and shift of every read's normalised signals against its
+        target's k-mer composition (strique_amd.renorm states the rule) and run on the corrected maps where the fitted repeat share
+        reaches min_share -- the rows of such reads change, which is the point: a read that is mostly repeat is stretched by the
+        whole-read statistics of detect() until its flanks are not found.  There is no default (README, "Renorm").  None or False:
+        off.  A switch of the counter, like set_variants: the keywords of detect stay; records=True reports the fit of every read
+        as Detected.renorm = (applied, {'morph' | 'filtered' | 'raw': None or (a, b, w, score)}).  Not with scan_batch."""
+        if min_share is None or min_share is False:
+            self.renorm = None
+            return
+        if not 0 < min_share < 1:
+            raise ValueError("RepeatCounter: the renorm share threshold must be inside (0, 1).")
+        self.renorm = float(min_share)
+
+    @property
+    def renorm_bin_width(self):
+        """Width of a bin of the rule's grid in pA (beta of a fit is b bins)."""
+        return renorm_mod.grid(self.pm.model_min, self.pm.model_max)[1]
 
     def set_variants(self, on):
         """on: detect and detect_batch also run the variant pass (strq_set_variants) and report one more element per read -- see
@@ -198,7 +230,7 @@ class repeatCounter(object):
         variants = self.variants
         reads = [(self._classifier_for(t, s).target_id, r) for t, r, s in items]
         out = [None] * len(items)
-        for i, d, _, _ in self._run(reads, units=units, confidence=confidence, mod_llr=mod_llr, anchored=anchored, variants=variants):
+        for i, d, _, _ in self._run(reads, units=units, confidence=confidence, mod_llr=mod_llr, anchored=anchored, variants=variants, renorm=self.renorm):
             if records:
                 out[i] = d
                 continue
@@ -212,7 +244,7 @@ class repeatCounter(object):
         return out
 
     @contextlib.contextmanager
-    def _switches(self, units, confidence, mod_llr, anchored=None, variants=False):
+    def _switches(self, units, confidence, mod_llr, anchored=None, variants=False, renorm=None):
         """The optional passes that were asked for are on inside the block, and all of them off after it."""
         try:
             if anchored is not None:
@@ -229,15 +261,19 @@ class repeatCounter(object):
             if variants:
                 self._ensure_variants()
                 self.ctx.set_variants(True)
+            if renorm is not None:
+                self._ensure_renorm()
+                self.ctx.set_renorm(True, renorm)
             yield
         finally:
+            self.ctx.set_renorm(False)
             self.ctx.set_variants(False)
             self.ctx.set_anchored(False)
             self.ctx.set_mod_llr(False)
             self.ctx.set_units(False)
             self.ctx.set_confidence(False)
 
-    def _run(self, reads, units=False, confidence=False, mod_llr=False, scan=None, anchored=None, variants=False):
+    def _run(self, reads, units=False, confidence=False, mod_llr=False, scan=None, anchored=None, variants=False, renorm=None):
         """reads: [(target_id, raw_signal)] through the context.  Yields (position in `reads`, Detected, winner, scores) per read, the
         fields of Detected that were not asked for being None.  scan=(candidate target ids, min_score): the target ids of the reads
         are ignored, every read is compared with every candidate (Context.scan_batch_reads); winner is its position in the candidate
@@ -251,7 +287,7 @@ class repeatCounter(object):
             if not idx:
                 continue
             arrs = [sigs[i].astype(np.int16 if want_int else np.float64, copy=False) for i in idx]
-            with self._switches(units, confidence, mod_llr, anchored, variants):
+            with self._switches(units, confidence, mod_llr, anchored, variants, renorm):
                 if scan is None:
                     res = self.ctx.detect_batch_reads(arrs, [reads[i][0] for i in idx])      # one pointer per read: no host-side concatenation
                     win = sc = [None] * len(res)
@@ -270,14 +306,18 @@ class repeatCounter(object):
                             pattern = "".join("0" if b == 0 else "0" * m.context_units + str(int(b)) for b in v[1])
                             v = (v[0], pattern, v[1], v[2], v[3].reshape(len(v[1]), m.n_branches))      # (a read without passages: (0, NB))
                         var.append(v)
+                rn = [None] * len(res)
+                if renorm is not None:
+                    rn = [(int(r['applied']), {s: (int(f['a']), int(f['b']), int(f['w']), int(f['score'])) if f['fitted'] else None
+                                               for s, f in zip(renorm_mod.SIGNALS, r['fit'])}) for r in self.ctx.batch_fetch_renorm()]
                 an = [None] * len(res)
                 if anchored is not None:
                     an = [(int(a['kind']), int(a['status']), int(a['count']), float(a['log_p']), int(a['begin']), int(a['end']), int(a['free_samples']))
                           for a in self.ctx.batch_fetch_anchored()]
-            for i, r, m, u, cf, v, w, s, a, vr in zip(idx, res, mods, pos, conf, vs, win, sc, an, var):
+            for i, r, m, u, cf, v, w, s, a, vr, rnr in zip(idx, res, mods, pos, conf, vs, win, sc, an, var, rn):
                 n = int(r['count']); p = float(r['log_p']) if n or r['log_p'] != 0 else 0
                 row = (n, float(r['score_prefix']), float(r['score_suffix']), p, int(r['offset']), int(r['ticks']), m)
-                yield i, Detected(row, u, cf, None if v is None else v[:, 1] - v[:, 0], a, vr), w, s
+                yield i, Detected(row, u, cf, None if v is None else v[:, 1] - v[:, 0], a, vr, rnr), w, s
 
     def candidates(self, targets=None):
         """[(target_name, strand)] of a scan: every target added (or the named ones), in add_target order, '+' before '-'."""
@@ -297,6 +337,8 @@ class repeatCounter(object):
         Returns, per read, None (no candidate eligible) or (target_name, strand, row), row being the tuple detect() returns
         for that target and strand -- (row, unit positions) with units=True.  scores=True: (that list, float64 array
         [n_reads, n_candidates, 2] of score_prefix, score_suffix of every candidate)."""
+        if self.renorm is not None:
+            raise ValueError("RepeatCounter: renorm is not available in a scan (set_renorm(None) first).")
         if min_score is None:
             raise ValueError("RepeatCounter: scan_batch needs min_score (there is no default: see README, 'Scan').")
         if not min_score > 0:

@@ -33,7 +33,8 @@ struct Carve {
 // run call ran with.
 // Anchored counting (strq_set_anchored) is the fourth: it comes with its score threshold.
 // The variant pass (strq_set_variants) is the fifth.
-struct Extras { bool units = false, conf = false, llr = false, anch = false, var = false; double anch_min = 0.0; };
+// Renorm (strq_set_renorm) is the sixth, in front of the alignments instead of behind the decode: it comes with its share threshold.
+struct Extras { bool units = false, conf = false, llr = false, anch = false, var = false; double anch_min = 0.0; bool renorm = false; double renorm_min = 0.0; };
 
 // What the variant pass leaves per read: the passages of its variant-model decode (strq_batch_fetch_variants)
 struct VariantRow {
@@ -53,6 +54,8 @@ struct ReadRows {
     std::vector<std::vector<double>> llr;         // (V_base, V_mod) per repeat unit (strq_batch_fetch_mod_llr); empty: none
     std::vector<strq_anchored> anch;              // kind and decode of a read that holds one flank (strq_batch_fetch_anchored); zeros: kind 0
     std::vector<VariantRow> var;                  // passages of the variant model (strq_batch_fetch_variants); decoded = 0: none
+    std::vector<strq_renorm> renorm;              // fits of the second normalisation step (strq_batch_fetch_renorm); zeros: not fitted.  Empty
+                                                  // until a run call with the switch on sizes it (size_renorm)
     void size_reads(int64_t n)
     {
         const size_t m = (size_t)n;
@@ -62,7 +65,9 @@ struct ReadRows {
         llr.assign(m, std::vector<double>());
         anch.assign(m, strq_anchored());
         var.assign(m, VariantRow());
+        renorm.clear();
     }
+    void size_renorm() { if (renorm.size() != results.size()) renorm.assign(results.size(), strq_renorm()); }
     void clear_read(int64_t read)
     {
         const size_t r = (size_t)read;
@@ -73,6 +78,7 @@ struct ReadRows {
         llr[r].clear();
         anch[r] = strq_anchored();
         var[r] = VariantRow();
+        if (r < renorm.size()) renorm[r] = strq_renorm();
     }
 };
 

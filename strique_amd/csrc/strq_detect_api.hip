@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -24,6 +25,7 @@
 #include "forward_kernels.h"
 #include "scan_kernels.h"
 #include "anchored_kernels.h"
+#include "renorm_kernels.h"
 #include "variant_kernels.h"
 
 using namespace strq;
@@ -73,6 +75,7 @@ struct Target {
     int mod_model_id = -1; double mod_min = 0, mod_max = 0;
     int end_model_id = -1, end_bias = 0, start_model_id = -1, start_bias = 0;      // strq_target_set_anchored: both models or none
     int var_model_id = -1, var_nalt = 0, var_ctx = 0; double var_lo = 0, var_hi = 0;      // strq_target_set_variants
+    const RenormTable* rn_dev = nullptr;      // strq_target_set_renorm: the tables of the target on the device (DetectState::rn_tables owns them)
 };
 
 struct Batch : ReadRows {
@@ -121,6 +124,12 @@ struct DetectState {
     float conf_ms = 0; double conf_windows = 0, conf_nopath = 0, conf_expo = 0;      // strq_last_confidence: the last run call's forward pass
     DevBuf anch_ws, anch_task;           // anchored pass (run_anchored_pass): geometry, conditioning rows and kinds of a sub-batch; tasks, results, their reads and models
     float anch_ms = 0; double anch_kinds[4] = {}, anch_launches = 0, anch_g2 = 0, anch_lane = 0;      // strq_last_anchored: the last run call's anchored pass
+    // renorm (run_renorm_part): the tables of the targets, the grid and the shares, the histograms and the per-read table rows of a sub-batch
+    std::vector<std::unique_ptr<DevBuf>> rn_tables;
+    RenormGrid rn_grid = {}; bool rn_have_grid = false;
+    DevBuf rn_h, rn_reads;
+    hipEvent_t rn_ev[4] = {}; int rn_timed = 0;      // one pair of events per piece of a sub-batch (at most two); pairs recorded by the sub-batch under way
+    float rn_ms = 0; double rn_fitted = 0, rn_applied = 0, rn_launches = 0;      // strq_last_renorm: the last run call's renorm pass
     // strq_scan_set: run calls compare these candidates (target ids) on every read instead of taking the read's own target
     bool scan_on = false; std::vector<int32_t> scan_cand; double scan_min = 0;
     DevBuf scan_idx, scan_out;           // scan: task table and candidate trims / winners, scores and raw scores of a sub-batch
@@ -134,6 +143,7 @@ struct DetectState {
     // reads or writes exists twice (filtered signal, tasks, results, order, queue heads); results come back one sub-batch late.
     struct Slot {
         DevBuf flt, vit, vres, order, vq;
+        DevBuf rn_rec; PinBuf rn_pin;    // renorm: the records of the sub-batch on the device and what the host reads of them
         // Idle -> Forward: publish_forward, the forward stage of reads [r0, r0 + nr) is queued, its Viterbi launches are not (they go behind the
         //   score-table kernel of the next sub-batch)
         // Forward -> Decoding: launch_viterbi_of, once the launches and the copy of their results are queued and `v1` is recorded
@@ -221,6 +231,7 @@ void detect_state_free(strq_ctx* c)
         for (hipEvent_t e : {sl.fwd_done, sl.v0, sl.v1}) if (e) (void)hipEventDestroy(e);
     if (d->vit_stream) (void)hipStreamDestroy(d->vit_stream);
     for (hipEvent_t e : d->ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : d->rn_ev) if (e) (void)hipEventDestroy(e);
     if (d->copy_stream) (void)hipStreamDestroy(d->copy_stream);
     for (hipEvent_t e : d->stage_ev) if (e) (void)hipEventDestroy(e);
     delete d;          // its buffers, device and pinned, go with it
@@ -1103,6 +1114,11 @@ static int take_rows(strq_ctx* c, DetectState* d, DetectState::Slot& sl, bool un
         const ReadGeom& g = h.geom[i];
         const VitResult& v = h.vres[sl.vit_slot[i]];
         o.status = h.rc[i].status == COND_OK ? 0 : 1;
+        if (sl.ex.renorm) {
+            const strq_renorm& rn = sl.rn_pin.as<strq_renorm>()[i];
+            B.renorm[(size_t)(r0 + i)] = rn;
+            d->rn_fitted += rn.fit[1].fitted != 0; d->rn_applied += rn.applied != 0;
+        }
         if (sl.scan && B.cand[(size_t)(r0 + i)] < 0) continue;          // no winner: no row (the scores of its candidates are in Batch::scores)
         o.score_prefix = g.score_prefix; o.score_suffix = g.score_suffix;
         o.prefix_begin = g.prefix_begin; o.prefix_end = g.prefix_end; o.suffix_begin = g.suffix_begin; o.suffix_end = g.suffix_end;
@@ -1334,6 +1350,53 @@ static int condition_part(strq_ctx* c, DetectState* d, const SubBatch& S, int i0
     return STRQ_OK;
 }
 
+// per upload part, with strq_set_renorm on: the second normalisation step of its reads (strique_amd/renorm.py), between the conditioning
+// statistics and everything that reads them.  Histograms of the three signals under their maps, the fit of each, the gate and the
+// fold into the ReadCond rows and the level values; the records stay in the slot until its rows are taken.
+static int run_renorm_part(strq_ctx* c, DetectState* d, const SubBatch& S, int i0, int np)
+{
+    const Batch& B = d->batch;
+    hipStream_t st = c->stream;
+    DetectState::Slot& sl = *S.sl;
+    STRQ_HIP(c, d->rn_h.reserve((size_t)S.nr * RN_SIGNALS * RN_GRID * 4));
+    STRQ_HIP(c, d->rn_reads.reserve((size_t)S.nr * sizeof(RenormRead)));
+    STRQ_HIP(c, sl.rn_rec.reserve((size_t)S.nr * sizeof(strq_renorm)));
+    for (auto& e : d->rn_ev) if (!e) STRQ_HIP(c, hipEventCreate(&e));
+    std::vector<RenormRead> rr((size_t)np);
+    int longest = 0;
+    for (int i = 0; i < np; ++i) {
+        const Target& t = target_of(d, S.r0 + i0 + i);
+        rr[(size_t)i].table = t.rn_dev; rr[(size_t)i].raw = t.mod_model_id >= 0; rr[(size_t)i].pad_ = 0;
+        longest = std::max(longest, S.rc[i0 + i].n);
+    }
+    RenormRead* d_rr = d->rn_reads.as<RenormRead>() + i0;
+    uint32_t* h = d->rn_h.as<uint32_t>() + (size_t)i0 * RN_SIGNALS * RN_GRID;
+    strq_renorm* rec = sl.rn_rec.as<strq_renorm>() + i0;
+    ReadCond* d_rc = S.d_rc + i0;
+    const uint32_t* hist8 = d->hist8.as<uint32_t>() + (size_t)i0 * 256;
+    STRQ_HIP(c, hipMemcpyAsync(d_rr, rr.data(), (size_t)np * sizeof(RenormRead), hipMemcpyHostToDevice, st));
+    const bool timed = d->rn_timed < 2;
+    if (timed) STRQ_HIP(c, hipEventRecord(d->rn_ev[2 * d->rn_timed], st));
+    STRQ_HIP(c, hipMemsetAsync(h, 0, (size_t)np * RN_SIGNALS * RN_GRID * 4, st));
+    STRQ_HIP(c, hipMemsetAsync(rec, 0, (size_t)np * sizeof(strq_renorm), st));
+    int bad = 0;
+    if (B.dtype == 0) {
+        const uint32_t* hraw = S.d_hist_raw ? S.d_hist_raw + (size_t)i0 * 65536 : nullptr;
+        bad |= launch_renorm_hist_i16(st, d->hist16.as<uint32_t>() + (size_t)i0 * 65536, hraw, hist8, d_rc, d_rr, np, d->rn_grid, h);
+        d->rn_launches += hraw ? 3 : 2;
+    } else {
+        bad |= launch_renorm_hist_f64(st, reinterpret_cast<const double*>(S.flt_base), S.any_mod ? reinterpret_cast<const double*>(S.raw) : nullptr, hist8, d_rc, d_rr,
+                                      np, longest, d->rn_grid, h);
+        d->rn_launches += longest > 0 ? 2 : 1;
+    }
+    bad |= launch_renorm_fit(st, h, d_rr, np, rec);
+    bad |= launch_renorm_fold(st, d_rc, np, d->rn_grid, d->extras.renorm_min, d->ps, c->level_val.as<float>() + (size_t)i0 * 256, rec);
+    d->rn_launches += 2;
+    if (timed) { STRQ_HIP(c, hipEventRecord(d->rn_ev[2 * d->rn_timed + 1], st)); ++d->rn_timed; }
+    if (bad) { c->err = "renorm: launch failed"; return STRQ_ERR_DEVICE; }
+    return STRQ_OK;
+}
+
 // per upload part: the two flank alignments of every read.  The first part's score-table kernel is where the Viterbi launches of the
 // sub-batch before this one are queued.
 static int align_part(strq_ctx* c, DetectState* d, const SubBatch& S, int i0, int np, bool first_part, AlignCoreOut& co, std::vector<int32_t>& trim)
@@ -1480,6 +1543,10 @@ static int publish_forward(strq_ctx* c, DetectState* d, const SubBatch& S)
     const DetectState::Slot::Pinned h = sl.host();
     STRQ_HIP(c, hipMemcpyAsync(h.geom, d->geom.p, (size_t)S.nr * sizeof(ReadGeom), hipMemcpyDeviceToHost, st));
     STRQ_HIP(c, hipMemcpyAsync(h.rc, S.d_rc, (size_t)S.nr * sizeof(ReadCond), hipMemcpyDeviceToHost, st));
+    if (d->extras.renorm && !S.nc) {
+        STRQ_HIP(c, sl.rn_pin.reserve((size_t)S.nr * sizeof(strq_renorm) + 64));
+        STRQ_HIP(c, hipMemcpyAsync(sl.rn_pin.p, sl.rn_rec.p, (size_t)S.nr * sizeof(strq_renorm), hipMemcpyDeviceToHost, st));
+    }
     *h.redo = 0;
     if (c->redo_total.p) STRQ_HIP(c, hipMemcpyAsync(h.redo, c->redo_total.p, 4, hipMemcpyDeviceToHost, st));
     STRQ_HIP(c, hipEventRecord(sl.fwd_done, st));
@@ -1535,6 +1602,8 @@ static int complete_sub_batch(strq_ctx* c, DetectState* d, const SubBatch& S)
     plan_next_overlap(c, d, S);
     float ms;
     STRQ_HIP(c, hipEventElapsedTime(&ms, d->ev[0], d->ev[1])); B.t_cond += ms;
+    for (int k = 0; k < d->rn_timed; ++k) { STRQ_HIP(c, hipEventElapsedTime(&ms, d->rn_ev[2 * k], d->rn_ev[2 * k + 1])); d->rn_ms += ms; }
+    d->rn_timed = 0;
     const int rcode = align_core_times(c, &B.t_lut, &B.t_fwd, &B.t_trace);      // of the last piece when the sub-batch ran in pieces
     if (rcode) return rcode;
     // results: of the sub-batch before this one (its Viterbi launches ran under this sub-batch's forward stage) -- or, serially, of this one
@@ -1586,6 +1655,7 @@ static int run_sub_batch(strq_ctx* c, DetectState* d, int64_t r0, int64_t r1, in
         if (part == 0) STRQ_HIP(c, hipEventRecord(d->ev[0], c->stream));
         if (const int rc = condition_part(c, d, S, i0, np)) return rc;
         if (part == 0) STRQ_HIP(c, hipEventRecord(d->ev[1], c->stream));
+        if (d->extras.renorm && !S.nc) { if (const int rc = run_renorm_part(c, d, S, i0, np)) return rc; }
         AlignCoreOut co; std::vector<int32_t> trim;
         if (const int rc = align_part(c, d, S, i0, np, part == 0, co, trim)) return rc;
         if (S.nc) { if (const int rc = select_part(c, d, S, i0, np, co)) return rc; }
@@ -1718,7 +1788,16 @@ int run_range(strq_ctx* c, DetectState* d, int64_t first, int64_t last)
         }
     }
     if (d->extras.var && d->scan_on) { c->err = "variants: not available in a scan (strq_scan_set)"; return STRQ_ERR_ARG; }
+    if (d->extras.renorm) {
+        // nothing is launched for a call whose reads the pass could not fit
+        if (d->scan_on) { c->err = "renorm: not available in a scan (strq_scan_set)"; return STRQ_ERR_ARG; }
+        if (!d->rn_have_grid) { c->err = "renorm: no tables (strq_target_set_renorm)"; return STRQ_ERR_ARG; }
+        for (int64_t r = first; r < last; ++r)
+            if (!d->targets[B.target_given.empty() ? B.target[(size_t)r] : B.target_given[(size_t)r]].rn_dev) { c->err = "renorm: target without tables (strq_target_set_renorm)"; return STRQ_ERR_ARG; }
+        B.size_renorm();
+    }
     B.ran = d->extras;
+    d->rn_ms = 0; d->rn_fitted = d->rn_applied = d->rn_launches = 0; d->rn_timed = 0;
     d->anch_ms = 0; std::fill(d->anch_kinds, d->anch_kinds + 4, 0.0); d->anch_launches = d->anch_g2 = d->anch_lane = 0;
     d->unit_ms = 0; d->unit_bytes = d->unit_reads = d->unit_positions = 0;
     d->conf_ms = 0; d->conf_windows = d->conf_nopath = d->conf_expo = 0;
@@ -2075,6 +2154,108 @@ int strq_last_anchored(strq_ctx* c, double* out8)
     out8[0] = d->anch_ms;
     for (int k = 0; k < 4; ++k) out8[1 + k] = d->anch_kinds[k];
     out8[5] = d->anch_launches; out8[6] = d->anch_g2; out8[7] = d->anch_lane;
+    return STRQ_OK;
+}
+
+int strq_target_set_renorm(strq_ctx* c, int32_t target_id, const int16_t* Q, int32_t q_out, const int32_t* A, const double* W,
+                           double grid_lo, double grid_d, double grid_p)
+{
+    STRQ_ENTER(c);
+    DetectState* d = dstate(c);
+    if (target_id < 0 || target_id >= (int32_t)d->targets.size()) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    if (const int rc = drain(c, d)) return rc;          // a sub-batch in flight is taken with the target it ran with
+    // after the drain nothing on the device reads the tables the target had before: they are freed here
+    auto drop_tables = [&]() {
+        const RenormTable* old = d->targets[target_id].rn_dev;
+        d->targets[target_id].rn_dev = nullptr;
+        d->rn_tables.erase(std::remove_if(d->rn_tables.begin(), d->rn_tables.end(), [old](const std::unique_ptr<DevBuf>& b) { return old && b->p == (const void*)old; }),
+                           d->rn_tables.end());
+        if (d->rn_tables.empty()) d->rn_have_grid = false;
+    };
+    if (!Q) { drop_tables(); return STRQ_OK; }
+    if (!A || !W || !(grid_d > 0.0) || !std::isfinite(grid_lo) || !std::isfinite(grid_d) || !std::isfinite(grid_p) || q_out < -32768 || q_out > 32767) {
+        c->err = "bad argument (strq_target_set_renorm: tables, shares and a grid of positive bin width)"; return STRQ_ERR_ARG;
+    }
+    for (int w = 0; w < RN_NW; ++w) if (!(W[w] >= 0.0 && W[w] < 1.0)) { c->err = "bad argument (strq_target_set_renorm: shares inside [0, 1))"; return STRQ_ERR_ARG; }
+    // the grid and the shares are the context's: while another target holds tables, a call with other ones is refused, not taken for both
+    const bool others = d->rn_tables.size() > (d->targets[target_id].rn_dev ? 1u : 0u);
+    if (d->rn_have_grid && others) {
+        bool same = d->rn_grid.lo == grid_lo && d->rn_grid.d == grid_d && d->rn_grid.p == grid_p;
+        for (int w = 0; w < RN_NW; ++w) same = same && d->rn_grid.w[w] == W[w];
+        if (!same) { c->err = "renorm: grid or shares differ from those of the tables the context holds (strq_target_set_renorm)"; return STRQ_ERR_ARG; }
+    }
+    std::vector<RenormTable> img(1);
+    RenormTable& t = img[0];
+    for (int w = 0; w < RN_NW; ++w) {
+        std::memcpy(t.q + (size_t)w * RN_Q_STRIDE, Q + (size_t)w * RN_GRID, RN_GRID * sizeof(int16_t));
+        for (int k = RN_GRID; k < RN_Q_STRIDE; ++k) t.q[(size_t)w * RN_Q_STRIDE + k] = (int16_t)q_out;
+    }
+    std::memcpy(t.a, A, sizeof(t.a)); t.pad_ = 0;
+    std::unique_ptr<DevBuf> buf(new DevBuf());
+    STRQ_HIP(c, buf->reserve(sizeof(RenormTable)));
+    STRQ_HIP(c, hipMemcpy(buf->p, &t, sizeof(RenormTable), hipMemcpyHostToDevice));
+    drop_tables();
+    d->targets[target_id].rn_dev = buf->as<RenormTable>();
+    d->rn_tables.push_back(std::move(buf));
+    d->rn_grid.lo = grid_lo; d->rn_grid.d = grid_d; d->rn_grid.p = grid_p;
+    for (int w = 0; w < RN_NW; ++w) d->rn_grid.w[w] = W[w];
+    d->rn_have_grid = true;
+    return STRQ_OK;
+}
+
+int strq_set_renorm(strq_ctx* c, int32_t on, double min_share)
+{
+    STRQ_ENTER(c);
+    if (on != 0 && on != 1) { c->err = "bad argument (strq_set_renorm takes 0 or 1)"; return STRQ_ERR_ARG; }
+    if (on && !(min_share > 0.0 && min_share < 1.0)) { c->err = "renorm: min_share must be inside (0, 1)"; return STRQ_ERR_ARG; }
+    DetectState* d = dstate(c);
+    if (on && d->scan_on) { c->err = "renorm: not available in a scan (strq_scan_set)"; return STRQ_ERR_ARG; }
+    // sub-batches in flight keep the mode they were launched with
+    if (const int rc = drain(c, d)) return rc;
+    d->extras.renorm = on != 0; d->extras.renorm_min = on ? min_share : 0.0;
+    return STRQ_OK;
+}
+
+int strq_batch_fetch_renorm(strq_ctx* c, strq_renorm* out, int64_t n)
+{
+    STRQ_ENTER(c);
+    DetectState* d = dstate(c);
+    if (const int rc = drain(c, d)) return rc;
+    const Batch& B = d->batch;
+    if (!B.ran.renorm) { c->err = "the last batch ran without renorm (strq_set_renorm)"; return STRQ_ERR_ARG; }
+    if (n != B.n_reads || (n > 0 && !out)) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    if (n) std::memcpy(out, B.renorm.data(), (size_t)n * sizeof(strq_renorm));
+    return STRQ_OK;
+}
+
+int strq_debug_renorm_fit(strq_ctx* c, int32_t target_id, const uint32_t* h3, strq_renorm* out)
+{
+    STRQ_ENTER(c);
+    DetectState* d = dstate(c);
+    if (target_id < 0 || target_id >= (int32_t)d->targets.size() || !h3 || !out) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    if (!d->targets[target_id].rn_dev) { c->err = "renorm: target without tables (strq_target_set_renorm)"; return STRQ_ERR_ARG; }
+    for (int k = 0; k < RN_SIGNALS * RN_GRID; ++k) if (h3[k] >> 31) { c->err = "bad argument (strq_debug_renorm_fit: a counter of 2^31 or more)"; return STRQ_ERR_ARG; }
+    if (const int rc = drain(c, d)) return rc;
+    Carve lay;
+    const size_t o_h = lay.add<uint32_t>(RN_SIGNALS * RN_GRID), o_rr = lay.add<RenormRead>(1), o_rec = lay.add<strq_renorm>(1);
+    DevBuf ws;
+    STRQ_HIP(c, ws.reserve(lay.total()));
+    const RenormRead rr = {d->targets[target_id].rn_dev, 1, 0};
+    STRQ_HIP(c, hipMemcpyAsync(Carve::at<uint32_t>(ws.p, o_h), h3, RN_SIGNALS * RN_GRID * 4, hipMemcpyHostToDevice, c->stream));
+    STRQ_HIP(c, hipMemcpyAsync(Carve::at<RenormRead>(ws.p, o_rr), &rr, sizeof(rr), hipMemcpyHostToDevice, c->stream));
+    STRQ_HIP(c, hipMemsetAsync(Carve::at<strq_renorm>(ws.p, o_rec), 0, sizeof(strq_renorm), c->stream));
+    if (launch_renorm_fit(c->stream, Carve::at<uint32_t>(ws.p, o_h), Carve::at<RenormRead>(ws.p, o_rr), 1, Carve::at<strq_renorm>(ws.p, o_rec))) { c->err = "renorm: launch failed"; return STRQ_ERR_DEVICE; }
+    STRQ_HIP(c, hipMemcpyAsync(out, Carve::at<strq_renorm>(ws.p, o_rec), sizeof(strq_renorm), hipMemcpyDeviceToHost, c->stream));
+    STRQ_HIP(c, hipStreamSynchronize(c->stream));
+    return STRQ_OK;
+}
+
+int strq_last_renorm(strq_ctx* c, double* out4)
+{
+    STRQ_ENTER(c);
+    if (!out4) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    DetectState* d = dstate(c);
+    out4[0] = d->rn_ms; out4[1] = d->rn_fitted; out4[2] = d->rn_applied; out4[3] = d->rn_launches;
     return STRQ_OK;
 }
 

@@ -467,6 +467,46 @@ class Context(object):
         return {'ms': float(out[0]), 'kinds': tuple(int(v) for v in out[1:5]), 'launches': int(out[5]),
                 'register_resident': int(out[6]), 'lane_layout': int(out[7])}
 
+    # ---- renorm: the second normalisation step ---------------------------------------------
+    def target_set_renorm(self, target_id, Q, A, model_min, model_max):
+        """strq_target_set_renorm: the tables of a target (strique_amd.renorm.tables) with the rule's shares and its grid over
+        [model_min, model_max]."""
+        from . import renorm
+        Q = _c(Q, np.int16); A = _c(A, np.int32); W = _c(renorm.W, np.float64)
+        if Q.shape != (renorm.N_W, renorm.GRID) or A.shape != (renorm.A_MAX + 1,):
+            raise ValueError("renorm tables: Q[%d][%d], A[%d]" % (renorm.N_W, renorm.GRID, renorm.A_MAX + 1))
+        lo, d, p = renorm.grid(model_min, model_max)
+        self._check(self._lib.strq_target_set_renorm(self._h, ctypes.c_int32(target_id), _ptr(Q), ctypes.c_int32(renorm.Q_OUT), _ptr(A), _ptr(W),
+                                                     ctypes.c_double(lo), ctypes.c_double(d), ctypes.c_double(p)))
+
+    def set_renorm(self, on, min_share=0.0):
+        """strq_set_renorm: later run calls refit the maps of every read against its target's composition and fold the fit in where
+        the fitted repeat share reaches min_share.  StriqueHipError (STRQ_ERR_ARG) for a min_share outside (0, 1), or with a scan set."""
+        self._check(self._lib.strq_set_renorm(self._h, ctypes.c_int32(1 if on else 0), ctypes.c_double(min_share if on else 0.0)))
+
+    def batch_fetch_renorm(self):
+        """Records of the last batch (strq_batch_fetch_renorm): a structured array of RENORM_DTYPE, one element per read; 'fit' holds
+        the morphology levels, the filtered and the raw signal in that order."""
+        n = getattr(self, '_n_batch', 0)
+        out = np.zeros(max(1, n), dtype=RENORM_DTYPE)
+        self._check(self._lib.strq_batch_fetch_renorm(self._h, _ptr(out), ctypes.c_int64(n)))
+        return out[:n]
+
+    def debug_renorm_fit(self, target_id, h3):
+        """strq_debug_renorm_fit: the fit kernel alone on three histograms (uint32 [3, 1024]); one element of RENORM_DTYPE."""
+        h3 = _c(h3, np.uint32)
+        if h3.shape != (3, 1024):
+            raise ValueError("three histograms of 1024 counters")
+        out = np.zeros(1, dtype=RENORM_DTYPE)
+        self._check(self._lib.strq_debug_renorm_fit(self._h, ctypes.c_int32(target_id), _ptr(h3), _ptr(out)))
+        return out[0]
+
+    def last_renorm(self):
+        """The renorm pass of the last run call (strq_last_renorm): {'ms', 'fitted', 'applied', 'launches'}."""
+        out = np.zeros(4)
+        self._check(self._lib.strq_last_renorm(self._h, _ptr(out)))
+        return {'ms': float(out[0]), 'fitted': int(out[1]), 'applied': int(out[2]), 'launches': int(out[3])}
+
     def batch_upload(self, signals, offsets, target_ids, host_stats=None):
         """signals: one concatenated int16 or float64 array; offsets: n_reads + 1."""
         signals = np.ascontiguousarray(signals)
@@ -652,6 +692,9 @@ RESULT_DTYPE = np.dtype([("count", np.int32), ("status", np.int32), ("score_pref
                          ("score_suffix", np.float64), ("log_p", np.float64), ("offset", np.int64),
                          ("ticks", np.int64), ("prefix_begin", np.int64), ("prefix_end", np.int64),
                          ("suffix_begin", np.int64), ("suffix_end", np.int64)], align=True)
+
+RENORM_FIT_DTYPE = np.dtype([("a", np.int32), ("b", np.int32), ("w", np.int32), ("fitted", np.int32), ("score", np.int64)], align=True)
+RENORM_DTYPE = np.dtype([("applied", np.int32), ("pad_", np.int32), ("fit", RENORM_FIT_DTYPE, (3,))], align=True)
 
 ANCHORED_DTYPE = np.dtype([("kind", np.int32), ("status", np.int32), ("count", np.int32), ("pad_", np.int32), ("log_p", np.float64),
                            ("begin", np.int64), ("end", np.int64), ("free_samples", np.int64)], align=True)
