@@ -533,6 +533,53 @@ int strq_debug_score_tables(strq_ctx* ctx, int32_t n_jobs, const float* level_va
                             int32_t* info, int32_t* band_lo, float* table, uint8_t* planes,
                             int32_t* handed, int32_t handed_cap, int32_t* n_handed);
 
+/* Test hooks, host only (no context, no device): the edge image the variant pass / the per-unit scores of the modification pass
+ * would upload for this model (csrc/variant_kernels.h VarModel, csrc/mod_llr_kernels.h LlrModel), built for a null device base.
+ * Model arrays as strq_model_create takes them; n_alt as strq_target_set_variants takes it.
+ *   *build_rc      what the image builder returned: 0, or 1 with the reason in `why` (a model the pass does not cover)
+ *   head[10]       n_emit, branches (2 for the dual model), mode, deg, deg2, end_deg[0 .. 3], 0
+ *   offsets[12]    byte offsets inside `image` of src, lp, src2, lp2, start_lp, kind, hub, ea, eb, ec, end_src, end_lp -- int32 / float64
+ *                  arrays in the layout the two headers document (rows of 64 lanes)
+ *   image          the image itself, *image_bytes of it (nothing is copied when image_cap is smaller; image may then be NULL)
+ * STRQ_ERR_ARG for a null array or a start / end outside the states; STRQ_OK otherwise, whatever *build_rc is.
+ * tests/passage_cases.py interprets the image on the CPU. */
+int strq_debug_variant_image(int32_t n_states, int32_t silent_start, int32_t start, int32_t end,
+                             const int32_t* in_ptr, const int32_t* in_src, const double* in_logp,
+                             const int32_t* emis_kind, const double* emis_a, const double* emis_b, const double* emis_c,
+                             const int32_t* state_tag, int32_t n_alt, int32_t* build_rc, int32_t* head, int64_t* offsets,
+                             void* image, int64_t image_cap, int64_t* image_bytes, char* why, int32_t why_len);
+int strq_debug_mod_llr_image(int32_t n_states, int32_t silent_start, int32_t start, int32_t end,
+                             const int32_t* in_ptr, const int32_t* in_src, const double* in_logp,
+                             const int32_t* emis_kind, const double* emis_a, const double* emis_b, const double* emis_c,
+                             const int32_t* state_tag, int32_t* build_rc, int32_t* head, int64_t* offsets,
+                             void* image, int64_t image_cap, int64_t* image_bytes, char* why, int32_t why_len);
+/* Test hooks: the scores of given passages / units, by one launch of the score kernel of the variant pass / of the per-unit scores --
+ * the kernels of strq_set_variants / strq_set_mod_llr without the pipeline around them.  For n_reads (1 ...) reads: model_id[r] a
+ * model of strq_model_create (its image is built, or reused, as strq_target_set_variants / strq_set_mod_llr build it -- but a model
+ * that fits no Viterbi kernel is not refused: nothing is decoded), the stretch x[x_off[r] .. x_off[r + 1]) and its bounds
+ * w[w_off[r] .. w_off[r + 1]) -- any int32: passage j of a read covers x[u_j .. w_j], u_0 = 0, u_j = w_{j-1} + 1, and scores -inf
+ * throughout unless 0 <= u_j <= w_j < T.  out: NB = n_alt + 1 (or 2) doubles per bound, in the order of w.  launched[0] = the kernel
+ * mode that ran (0: two passages per wave, 1: one state per lane, 2: two states per lane), launched[1] = NB.
+ * STRQ_ERR_ARG when the models of a call do not share (mode, NB), STRQ_ERR_UNSUPPORTED for a model the pass does not cover.
+ * Own buffers on the context's stream: a batch in flight and its results are left alone. */
+int strq_debug_variant_scores(strq_ctx* ctx, int32_t n_reads, const int32_t* model_id, int32_t n_alt, const double* x,
+                              const int64_t* x_off, const int32_t* w, const int64_t* w_off, double* out, int32_t* launched);
+int strq_debug_mod_llr_scores(strq_ctx* ctx, int32_t n_reads, const int32_t* model_id, const double* x, const int64_t* x_off,
+                              const int32_t* w, const int64_t* w_off, double* out, int32_t* launched);
+/* Test hook: the two passes of the bounds kernels of the variant pass (count, then write) for n_reads reads of one model, set up as
+ * the pipeline sets them up.  Read r has T_r = off[r + 1] - off[r] observations.  Scan route (path != NULL): path[off[r] ..] the
+ * emitting state of every observation (each below silent_start).  Hop route (path == NULL): rec[off[r] + r ..] the T_r + 1 hub
+ * records of the read, last[r] the index of the last record (what the decode leaves in its result).  status[r]: the decode status
+ * to present (0 a path, 1 none).  cap[r] >= 0 replaces the count of the first pass as the `cap` of the write pass (at most
+ * stride - guard); -1 takes the count.  Out: n[r] passages counted; bad[2 r], bad[2 r + 1] the flag behind the count / the write
+ * pass; w, branch [r * stride ..]: `stride` entries per read as the write pass left them, 0x7F7F7F7F where nothing was written;
+ * untouched[r] = 1 when every entry from the write pass's cap on still holds that value.
+ * STRQ_ERR_ARG for a state outside the emitting ones, a cap beyond the stride, n_alt outside 1 .. 3. */
+int strq_debug_variant_bounds(strq_ctx* ctx, int32_t model_id, int32_t n_alt, int32_t n_reads, const int64_t* off,
+                              const int32_t* path, const uint64_t* rec, const uint32_t* last, const int32_t* status,
+                              const int32_t* cap, int32_t stride, int32_t guard, int32_t* n, int32_t* bad, int32_t* w,
+                              int32_t* branch, int32_t* untouched);
+
 /* Kernel timing of the last batched call, milliseconds (HIP events on the library's stream):
  * [0] table build  [1] forward DP  [2] trace pass  [3] total  [4] table entries re-evaluated on
  * the host  [5] conditioning  [6] Viterbi  [7] number of forward-DP kernel launches.  */

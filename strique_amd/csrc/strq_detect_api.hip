@@ -415,21 +415,39 @@ static int run_llr_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, cons
 }
 
 // The edge image of a variant model with `n_alt` alt branches (HostModel::var_dev), built if it is not there; STRQ_ERR_UNSUPPORTED
-// (c->err says why) for a model the pass does not cover.
-static int variant_model(strq_ctx* c, HostModel* hm, int32_t n_alt)
+// (c->err says why) for a model the pass does not cover.  `decoded`: the model is to be decoded as well (the pipeline), so it must
+// fit a Viterbi kernel; strq_debug_variant_scores scores given passages only.
+static int variant_model(strq_ctx* c, HostModel* hm, int32_t n_alt, bool decoded = true)
 {
-    if (hm->var_dev && hm->var_nb == n_alt + 1) return STRQ_OK;
+    const char* no_shape = "variants: the variant model does not fit a compiled Viterbi kernel";
+    if (hm->var_dev && hm->var_nb == n_alt + 1) {
+        if (decoded && vit_shape_of(hm->h) < 0) { c->err = no_shape; return STRQ_ERR_UNSUPPORTED; }          // (an image the hook built)
+        return STRQ_OK;
+    }
     std::vector<char> blob; std::string why; int32_t mode = -1;
     if (var_build_image(hm->n_states, hm->silent_start, hm->start, hm->end, hm->in_ptr.data(), hm->in_src.data(), hm->in_logp.data(),
                         hm->emis_kind.data(), hm->emis_a.data(), hm->emis_b.data(), hm->emis_c.data(),
                         hm->state_tag.empty() ? nullptr : hm->state_tag.data(), n_alt, nullptr, blob, &mode, why)) { c->err = why; return STRQ_ERR_UNSUPPORTED; }
-    if (vit_shape_of(hm->h) < 0) { c->err = "variants: the variant model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
+    if (decoded && vit_shape_of(hm->h) < 0) { c->err = no_shape; return STRQ_ERR_UNSUPPORTED; }
     if (hm->var_blob.reserve(var_image_bytes()) != hipSuccess) { c->err = "out of device memory"; return STRQ_ERR_NOMEM; }
     var_build_image(hm->n_states, hm->silent_start, hm->start, hm->end, hm->in_ptr.data(), hm->in_src.data(), hm->in_logp.data(),
                     hm->emis_kind.data(), hm->emis_a.data(), hm->emis_b.data(), hm->emis_c.data(), hm->state_tag.data(), n_alt, hm->var_blob.p, blob, &mode, why);
     STRQ_HIP(c, hipMemcpy(hm->var_blob.p, blob.data(), blob.size(), hipMemcpyHostToDevice));
     hm->var_dev = hm->var_blob.as<VarModel>(); hm->var_mode = mode; hm->var_nb = n_alt + 1;
     return STRQ_OK;
+}
+
+// The task of the count pass of the variant bounds kernels for one read of T observations: its hub records (or null and its traced
+// path), the result of its decode, the model's tags; no bounds yet, and cap = T / 3 + 1 -- a passage takes three observations at
+// least (s0, one branch emission, e0).  The write pass is the same task with w, branch and the count as cap filled in.
+static VarBoundTask var_count_task(const uint64_t* rec, const VitResult* result, const int32_t* path, const int32_t* tag, int32_t* n, int32_t* bad,
+                                   int64_t T, int32_t n_branch)
+{
+    VarBoundTask b; std::memset(&b, 0, sizeof(b));
+    b.rec = rec; b.result = result; b.path = path; b.tag = tag;
+    b.w = nullptr; b.branch = nullptr; b.n = n; b.bad = bad;
+    b.T = T; b.cap = (int32_t)(T / 3 + 1); b.n_branch = n_branch;
+    return b;
 }
 
 // Behind the decode of the variant models of one sub-batch (run_mod_pass, DUAL_VAR): the passages of every read from its hub records
@@ -442,7 +460,7 @@ static int run_variant_tail(strq_ctx* c, DetectState* d, DetectState::Slot& sl, 
     const ReadGeom* geom = sl.host().geom;
     const std::vector<int>& who = *in.who;
     const int nm = (int)who.size();
-    // count pass: a passage takes three observations at least (s0, one branch emission, e0), so T / 3 + 1 bounds the count
+    // count pass (var_count_task)
     Carve lay;
     const size_t o_n = lay.add<int32_t>((size_t)nm), o_bad = lay.add<int32_t>((size_t)nm), o_bt = lay.add<VarBoundTask>((size_t)nm),
                  o_rd = lay.add<VarRead>((size_t)nm), o_first = lay.add<int64_t>((size_t)nm + 16);
@@ -457,11 +475,8 @@ static int run_variant_tail(strq_ctx* c, DetectState* d, DetectState::Slot& sl, 
         // (strq_target_set_variants built the image or refused the model: nothing is built or refused in the middle of a batch)
         if (!hm->var_dev || hm->var_mode < 0 || hm->var_mode > 2) { c->err = "variants: variant model without an edge image (strq_target_set_variants validates them)"; return STRQ_ERR_DEVICE; }
         const int s2 = (*in.slot2)[(size_t)k];
-        VarBoundTask& b = bt[(size_t)k]; std::memset(&b, 0, sizeof(b));
-        b.rec = in.use_hub ? reinterpret_cast<const uint64_t*>(d->bp.as<uint16_t>() + (*in.bp2_off)[(size_t)k]) : nullptr;
-        b.result = in.results + s2; b.path = in.use_hub ? nullptr : (*in.paths)[(size_t)s2]; b.tag = hm->h.state_tag;
-        b.w = nullptr; b.branch = nullptr; b.n = d_n + k; b.bad = d_bad + k;
-        b.T = (*in.len)[(size_t)k]; b.cap = (int32_t)((*in.len)[(size_t)k] / 3 + 1); b.n_branch = hm->var_nb;
+        bt[(size_t)k] = var_count_task(in.use_hub ? reinterpret_cast<const uint64_t*>(d->bp.as<uint16_t>() + (*in.bp2_off)[(size_t)k]) : nullptr, in.results + s2,
+                                       in.use_hub ? nullptr : (*in.paths)[(size_t)s2], hm->h.state_tag, d_n + k, d_bad + k, (*in.len)[(size_t)k], hm->var_nb);
     }
     auto bounds = [&]() -> int {
         STRQ_HIP(c, hipMemcpyAsync(d_bt, bt.data(), (size_t)nm * sizeof(VarBoundTask), hipMemcpyHostToDevice, st));
@@ -1874,6 +1889,75 @@ struct PlainScope {
     ~PlainScope() { d->scan_on = on; }
 };
 
+// strq_debug_variant_image / strq_debug_mod_llr_image: what an image built for a null device base holds, as plain numbers -- the
+// pointers of its struct are then the byte offsets of the arrays
+template <class Model>
+int debug_image_out(int brc, const std::vector<char>& blob, const std::string& reason, int n_branch,
+                    int32_t* build_rc, int32_t* head, int64_t* offsets, void* image, int64_t image_cap, int64_t* image_bytes, char* why, int32_t why_len)
+{
+    *build_rc = brc;
+    if (why && why_len > 0) snprintf(why, (size_t)why_len, "%s", brc ? reason.c_str() : "");
+    for (int i = 0; i < 10; ++i) head[i] = 0;
+    for (int i = 0; i < 12; ++i) offsets[i] = 0;
+    *image_bytes = 0;
+    if (brc) return STRQ_OK;
+    Model M; std::memcpy(&M, blob.data(), sizeof(M));
+    head[0] = M.n_emit; head[1] = n_branch; head[2] = M.mode; head[3] = M.deg; head[4] = M.deg2;
+    for (size_t i = 0; i < sizeof(M.end_deg) / sizeof(M.end_deg[0]); ++i) head[5 + i] = M.end_deg[i];
+    const void* at[12] = {M.src, M.lp, M.src2, M.lp2, M.start_lp, M.kind, M.hub, M.ea, M.eb, M.ec, M.end_src, M.end_lp};
+    for (int i = 0; i < 12; ++i) offsets[i] = (int64_t)reinterpret_cast<intptr_t>(at[i]);
+    *image_bytes = (int64_t)blob.size();
+    if (image && image_cap >= (int64_t)blob.size()) std::memcpy(image, blob.data(), blob.size());
+    return STRQ_OK;
+}
+
+// strq_debug_variant_scores / strq_debug_mod_llr_scores: the reads with bounds as Read structs over buffers of the call's own, one
+// launch, the scores back.  dev[r]: the device image of read r's model; nv doubles per bound.
+template <class Read, class Model, class Launch>
+int debug_scores(strq_ctx* c, int32_t n_reads, const std::vector<const Model*>& dev, int nv, const double* x, const int64_t* x_off,
+                 const int32_t* w, const int64_t* w_off, double* out, Launch launch)
+{
+    hipStream_t st = c->stream;
+    const int64_t nx = x_off[n_reads], nw = w_off[n_reads];
+    if (!nw) return STRQ_OK;
+    DevBuf b_x, b_w, b_out, b_rd, b_first;
+    STRQ_HIP(c, b_x.reserve((size_t)nx * 8 + 64)); STRQ_HIP(c, b_w.reserve((size_t)nw * 4 + 64)); STRQ_HIP(c, b_out.reserve((size_t)nw * nv * 8 + 64));
+    STRQ_HIP(c, b_rd.reserve((size_t)n_reads * sizeof(Read) + 64)); STRQ_HIP(c, b_first.reserve(((size_t)n_reads + 1) * 8 + 64));
+    std::vector<Read> rdv; std::vector<int64_t> first, at;
+    int64_t total = 0;
+    for (int32_t r = 0; r < n_reads; ++r) {          // (a read without bounds takes no part, as in the pipeline)
+        const int64_t k = w_off[r + 1] - w_off[r];
+        if (!k) continue;
+        Read rd; rd.model = dev[(size_t)r]; rd.x = b_x.as<double>() + x_off[r]; rd.w = b_w.as<int32_t>() + w_off[r];
+        rd.out = b_out.as<double>() + (size_t)nv * (size_t)w_off[r]; rd.T = x_off[r + 1] - x_off[r];
+        rdv.push_back(rd); first.push_back(total); total += k;
+    }
+    first.push_back(total);
+    if (nx) STRQ_HIP(c, hipMemcpyAsync(b_x.p, x, (size_t)nx * 8, hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, hipMemcpyAsync(b_w.p, w, (size_t)nw * 4, hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, hipMemcpyAsync(b_rd.p, rdv.data(), rdv.size() * sizeof(Read), hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, hipMemcpyAsync(b_first.p, first.data(), first.size() * 8, hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, hipMemsetAsync(b_out.p, 0, (size_t)nw * nv * 8, st));
+    if (launch(st, b_rd.as<Read>(), b_first.as<int64_t>(), (int)rdv.size(), total)) { c->err = "score launch failed"; return STRQ_ERR_DEVICE; }
+    STRQ_HIP(c, hipMemcpyAsync(out, b_out.p, (size_t)nw * nv * 8, hipMemcpyDeviceToHost, st));
+    STRQ_HIP(c, hipStreamSynchronize(st));
+    return STRQ_OK;
+}
+
+// the arguments the two score hooks share
+int debug_scores_args(strq_ctx* c, int32_t n_reads, const int32_t* model_id, const double* x, const int64_t* x_off, const int32_t* w,
+                      const int64_t* w_off, double* out, int32_t* launched)
+{
+    const char* bad = "bad argument";
+    if (n_reads < 1 || !model_id || !x_off || !w_off || !out || !launched || x_off[0] != 0 || w_off[0] != 0) { c->err = bad; return STRQ_ERR_ARG; }
+    for (int32_t r = 0; r < n_reads; ++r) {
+        if (x_off[r + 1] < x_off[r] || w_off[r + 1] < w_off[r]) { c->err = "bad argument (offsets must not decrease)"; return STRQ_ERR_ARG; }
+        if (model_id[r] < 0 || model_id[r] >= (int32_t)c->models.size() || !c->models[(size_t)model_id[r]]) { c->err = "bad argument (no such model)"; return STRQ_ERR_ARG; }
+    }
+    if ((x_off[n_reads] > 0 && !x) || (w_off[n_reads] > 0 && !w)) { c->err = bad; return STRQ_ERR_ARG; }
+    return STRQ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2464,6 +2548,144 @@ int strq_debug_filtered(strq_ctx* c, int64_t read, void* out, int64_t n)
     STRQ_HIP(c, hipMemcpy(&rc, d->rc.as<ReadCond>() + read, sizeof(rc), hipMemcpyDeviceToHost));
     const size_t count = (size_t)std::min<int64_t>(n, rc.n);
     if (count) STRQ_HIP(c, hipMemcpy(out, d->slot[d->last_slot].flt.as<char>() + d->flt_shift + (size_t)rc.off * esz, count * esz, hipMemcpyDeviceToHost));
+    return STRQ_OK;
+}
+
+// the edge images of the variant pass and of the per-unit scores as plain arrays (host only): what the CPU tests interpret
+int strq_debug_variant_image(int32_t n_states, int32_t silent_start, int32_t start, int32_t end, const int32_t* in_ptr, const int32_t* in_src,
+                             const double* in_logp, const int32_t* emis_kind, const double* emis_a, const double* emis_b, const double* emis_c,
+                             const int32_t* state_tag, int32_t n_alt, int32_t* build_rc, int32_t* head, int64_t* offsets,
+                             void* image, int64_t image_cap, int64_t* image_bytes, char* why, int32_t why_len)
+{
+    if (!in_ptr || !in_src || !in_logp || !emis_kind || !emis_a || !emis_b || !emis_c || !build_rc || !head || !offsets || !image_bytes ||
+        n_states < 2 || silent_start < 0 || start < 0 || start >= n_states || end < 0 || end >= n_states) return STRQ_ERR_ARG;
+    std::vector<char> blob; std::string reason; int32_t mode = -1;
+    const int brc = var_build_image(n_states, silent_start, start, end, in_ptr, in_src, in_logp, emis_kind, emis_a, emis_b, emis_c, state_tag, n_alt,
+                                    nullptr, blob, &mode, reason);
+    return debug_image_out<VarModel>(brc, blob, reason, n_alt + 1, build_rc, head, offsets, image, image_cap, image_bytes, why, why_len);
+}
+
+int strq_debug_mod_llr_image(int32_t n_states, int32_t silent_start, int32_t start, int32_t end, const int32_t* in_ptr, const int32_t* in_src,
+                             const double* in_logp, const int32_t* emis_kind, const double* emis_a, const double* emis_b, const double* emis_c,
+                             const int32_t* state_tag, int32_t* build_rc, int32_t* head, int64_t* offsets,
+                             void* image, int64_t image_cap, int64_t* image_bytes, char* why, int32_t why_len)
+{
+    if (!in_ptr || !in_src || !in_logp || !emis_kind || !emis_a || !emis_b || !emis_c || !build_rc || !head || !offsets || !image_bytes ||
+        n_states < 2 || silent_start < 0 || start < 0 || start >= n_states || end < 0 || end >= n_states) return STRQ_ERR_ARG;
+    std::vector<char> blob; std::string reason; int32_t mode = -1;
+    const int brc = llr_build_image(n_states, silent_start, start, end, in_ptr, in_src, in_logp, emis_kind, emis_a, emis_b, emis_c, state_tag,
+                                    nullptr, blob, &mode, reason);
+    return debug_image_out<LlrModel>(brc, blob, reason, 2, build_rc, head, offsets, image, image_cap, image_bytes, why, why_len);
+}
+
+// given passages / units through one launch of the score kernels
+int strq_debug_variant_scores(strq_ctx* c, int32_t n_reads, const int32_t* model_id, int32_t n_alt, const double* x, const int64_t* x_off,
+                              const int32_t* w, const int64_t* w_off, double* out, int32_t* launched)
+{
+    STRQ_ENTER(c);
+    if (const int rc = debug_scores_args(c, n_reads, model_id, x, x_off, w, w_off, out, launched)) return rc;
+    std::vector<const VarModel*> dev((size_t)n_reads);
+    int mode = -1;
+    for (int32_t r = 0; r < n_reads; ++r) {
+        HostModel* hm = c->models[(size_t)model_id[r]];
+        if (const int rc = variant_model(c, hm, n_alt, false)) return rc;
+        if (mode >= 0 && hm->var_mode != mode) { c->err = "bad argument (the models of a call must share the kernel mode and the branches)"; return STRQ_ERR_ARG; }
+        mode = hm->var_mode; dev[(size_t)r] = hm->var_dev;
+    }
+    launched[0] = mode; launched[1] = n_alt + 1;
+    const int n_cu = c->n_cu;
+    return debug_scores<VarRead, VarModel>(c, n_reads, dev, n_alt + 1, x, x_off, w, w_off, out,
+        [=](hipStream_t st, const VarRead* rd, const int64_t* first, int n, int64_t total) { return launch_var_score(st, mode, n_alt + 1, rd, first, n, total, n_cu); });
+}
+
+int strq_debug_mod_llr_scores(strq_ctx* c, int32_t n_reads, const int32_t* model_id, const double* x, const int64_t* x_off,
+                              const int32_t* w, const int64_t* w_off, double* out, int32_t* launched)
+{
+    STRQ_ENTER(c);
+    if (const int rc = debug_scores_args(c, n_reads, model_id, x, x_off, w, w_off, out, launched)) return rc;
+    std::vector<const LlrModel*> dev((size_t)n_reads);
+    int mode = -1;
+    for (int32_t r = 0; r < n_reads; ++r) {
+        HostModel* hm = c->models[(size_t)model_id[r]];
+        if (const int rc = llr_model(c, hm)) return rc;
+        if (mode >= 0 && hm->llr_mode != mode) { c->err = "bad argument (the models of a call must share the kernel mode)"; return STRQ_ERR_ARG; }
+        mode = hm->llr_mode; dev[(size_t)r] = hm->llr_dev;
+    }
+    launched[0] = mode; launched[1] = 2;
+    const int n_cu = c->n_cu;
+    return debug_scores<LlrRead, LlrModel>(c, n_reads, dev, 2, x, x_off, w, w_off, out,
+        [=](hipStream_t st, const LlrRead* rd, const int64_t* first, int n, int64_t total) { return launch_llr_score(st, mode, rd, first, n, total, n_cu); });
+}
+
+// count pass and write pass of the variant bounds kernels, the tasks filled as run_variant_tail fills them
+int strq_debug_variant_bounds(strq_ctx* c, int32_t model_id, int32_t n_alt, int32_t n_reads, const int64_t* off, const int32_t* path,
+                              const uint64_t* rec, const uint32_t* last, const int32_t* status, const int32_t* cap, int32_t stride,
+                              int32_t guard, int32_t* n, int32_t* bad, int32_t* w, int32_t* branch, int32_t* untouched)
+{
+    STRQ_ENTER(c);
+    const char* bad_arg = "bad argument";
+    if (model_id < 0 || model_id >= (int32_t)c->models.size() || !c->models[(size_t)model_id] || n_alt < 1 || n_alt > VAR_MAX_NB - 1 || n_reads < 1 ||
+        !off || off[0] != 0 || (!path && (!rec || !last)) || !status || !cap || stride < 1 || guard < 0 || guard > stride || !n || !bad || !w || !branch || !untouched) {
+        c->err = bad_arg; return STRQ_ERR_ARG;
+    }
+    HostModel* hm = c->models[(size_t)model_id];
+    if (!hm->h.state_tag) { c->err = "bad argument (the model carries no state tags)"; return STRQ_ERR_ARG; }
+    const bool hop = !path;
+    for (int32_t r = 0; r < n_reads; ++r) {
+        const int64_t T = off[r + 1] - off[r];
+        if (T < 0 || T >= ((int64_t)1 << 30) || T / 3 + 1 > stride - guard || cap[r] < -1 || cap[r] > stride - guard) { c->err = "bad argument (a read's length or cap against the stride)"; return STRQ_ERR_ARG; }
+        if (!hop) for (int64_t t = off[r]; t < off[r + 1]; ++t) if (path[t] < 0 || path[t] >= hm->silent_start) { c->err = "bad argument (a path state that does not emit)"; return STRQ_ERR_ARG; }
+    }
+    hipStream_t st = c->stream;
+    const int64_t nT = off[n_reads];
+    const size_t n_in = hop ? (size_t)nT + (size_t)n_reads : (size_t)nT, slots = (size_t)n_reads * (size_t)stride;
+    DevBuf b_in, b_res, b_bt, b_n, b_bad, b_w;
+    STRQ_HIP(c, b_in.reserve(n_in * (hop ? 8 : 4) + 64)); STRQ_HIP(c, b_res.reserve((size_t)n_reads * sizeof(VitResult) + 64));
+    STRQ_HIP(c, b_bt.reserve((size_t)n_reads * sizeof(VarBoundTask) + 64)); STRQ_HIP(c, b_n.reserve((size_t)n_reads * 4 + 64));
+    STRQ_HIP(c, b_bad.reserve((size_t)n_reads * 4 + 64)); STRQ_HIP(c, b_w.reserve(slots * 8 + 64));
+    int32_t* d_n = b_n.as<int32_t>(); int32_t* d_bad = b_bad.as<int32_t>(); int32_t* d_w = b_w.as<int32_t>(); int32_t* d_br = d_w + slots;
+    VarBoundTask* d_bt = b_bt.as<VarBoundTask>();
+    std::vector<VitResult> res((size_t)n_reads); std::vector<VarBoundTask> bt((size_t)n_reads);
+    for (int32_t r = 0; r < n_reads; ++r) {
+        VitResult& v = res[(size_t)r]; std::memset(&v, 0, sizeof(v));
+        v.status = status[r]; v.dbg[0] = hop ? last[r] : 0;
+        bt[(size_t)r] = var_count_task(hop ? b_in.as<uint64_t>() + off[r] + r : nullptr, b_res.as<VitResult>() + r, hop ? nullptr : b_in.as<int32_t>() + off[r],
+                                       hm->h.state_tag, d_n + r, d_bad + r, off[r + 1] - off[r], n_alt + 1);
+    }
+    auto bounds = [&]() -> int {
+        STRQ_HIP(c, hipMemcpyAsync(d_bt, bt.data(), (size_t)n_reads * sizeof(VarBoundTask), hipMemcpyHostToDevice, st));
+        if (launch_var_bounds(st, hop ? d_bt : nullptr, hop ? n_reads : 0, hop ? nullptr : d_bt, hop ? 0 : n_reads)) { c->err = "variants: bounds launch failed"; return STRQ_ERR_DEVICE; }
+        return STRQ_OK;
+    };
+    if (n_in) STRQ_HIP(c, hipMemcpyAsync(b_in.p, hop ? static_cast<const void*>(rec) : static_cast<const void*>(path), n_in * (hop ? 8 : 4), hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, hipMemcpyAsync(b_res.p, res.data(), (size_t)n_reads * sizeof(VitResult), hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, hipMemsetAsync(d_n, 0, (size_t)n_reads * 4, st));
+    STRQ_HIP(c, hipMemsetAsync(d_bad, 0, (size_t)n_reads * 4, st));
+    STRQ_HIP(c, hipMemsetAsync(d_w, 0x7F, slots * 8, st));
+    if (const int rc = bounds()) return rc;
+    std::vector<int32_t> bad1((size_t)n_reads), bad2((size_t)n_reads);
+    STRQ_HIP(c, hipMemcpyAsync(n, d_n, (size_t)n_reads * 4, hipMemcpyDeviceToHost, st));
+    STRQ_HIP(c, hipMemcpyAsync(bad1.data(), d_bad, (size_t)n_reads * 4, hipMemcpyDeviceToHost, st));
+    STRQ_HIP(c, hipStreamSynchronize(st));
+    // write pass: the count (or the caller's number) as the cap, bounds at the read's stride
+    for (int32_t r = 0; r < n_reads; ++r) {
+        VarBoundTask& b = bt[(size_t)r];
+        if (cap[r] < 0 && (n[r] < 0 || n[r] > stride - guard)) { c->err = "variants: the count pass returned a count beyond what the read can hold"; return STRQ_ERR_DEVICE; }
+        b.w = d_w + (size_t)r * (size_t)stride; b.branch = d_br + (size_t)r * (size_t)stride; b.cap = cap[r] >= 0 ? cap[r] : n[r];
+    }
+    STRQ_HIP(c, hipMemsetAsync(d_bad, 0, (size_t)n_reads * 4, st));
+    if (const int rc = bounds()) return rc;
+    STRQ_HIP(c, hipMemcpyAsync(w, d_w, slots * 4, hipMemcpyDeviceToHost, st));
+    STRQ_HIP(c, hipMemcpyAsync(branch, d_br, slots * 4, hipMemcpyDeviceToHost, st));
+    STRQ_HIP(c, hipMemcpyAsync(bad2.data(), d_bad, (size_t)n_reads * 4, hipMemcpyDeviceToHost, st));
+    STRQ_HIP(c, hipStreamSynchronize(st));
+    for (int32_t r = 0; r < n_reads; ++r) {
+        bad[2 * r] = bad1[(size_t)r]; bad[2 * r + 1] = bad2[(size_t)r];
+        int same = 1;
+        for (int32_t k = bt[(size_t)r].cap; k < stride; ++k)
+            if (w[(size_t)r * (size_t)stride + (size_t)k] != 0x7F7F7F7F || branch[(size_t)r * (size_t)stride + (size_t)k] != 0x7F7F7F7F) same = 0;
+        untouched[r] = same;
+    }
     return STRQ_OK;
 }
 

@@ -124,6 +124,61 @@ def live_allocations():
     return int(out[0]), int(out[1])
 
 
+def _offsets(arrays, dtype):
+    """Concatenation and int64 offsets of a list of arrays (one entry of at least one element, so that the pointer is never null)."""
+    off = np.zeros(len(arrays) + 1, np.int64)
+    for i, a in enumerate(arrays):
+        off[i + 1] = off[i] + len(a)
+    flat = np.concatenate([_c(a, dtype).ravel() for a in arrays] + [np.zeros(1, dtype)])
+    return flat, off
+
+
+# arrays of an edge image: name -> (dtype, shape), in the order of the hooks' offsets (csrc/variant_kernels.h, csrc/mod_llr_kernels.h)
+_IMAGE_ORDER = ("src", "lp", "src2", "lp2", "start_lp", "kind", "hub", "ea", "eb", "ec", "end_src", "end_lp")
+VARIANT_IMAGE_SHAPES = {"src": (np.int32, (2, 8, 64)), "lp": (np.float64, (2, 8, 64)), "src2": (np.int32, (3, 2, 4, 64)), "lp2": (np.float64, (3, 2, 4, 64)),
+                        "start_lp": (np.float64, (2, 64)), "kind": (np.int32, (2, 64)), "hub": (np.int32, (2, 64)), "ea": (np.float64, (2, 64)),
+                        "eb": (np.float64, (2, 64)), "ec": (np.float64, (2, 64)), "end_src": (np.int32, (4, 8)), "end_lp": (np.float64, (4, 8))}
+MOD_LLR_IMAGE_SHAPES = dict(VARIANT_IMAGE_SHAPES, src2=(np.int32, (2, 4, 64)), lp2=(np.float64, (2, 4, 64)), start_lp=(np.float64, (2, 2, 64)),
+                            end_src=(np.int32, (2, 8)), end_lp=(np.float64, (2, 8)))
+
+
+def _debug_image(entry, shapes, baked, extra):
+    lib = load_library()
+    arrs = [_c(baked.in_ptr, np.int32), _c(baked.in_src, np.int32), _c(baked.in_logp, np.float64), _c(baked.emis_kind, np.int32),
+            _c(baked.emis_a, np.float64), _c(baked.emis_b, np.float64), _c(baked.emis_c, np.float64),
+            None if baked.tag is None else _c(baked.tag, np.int32)]
+    brc = ctypes.c_int32(-1); head = np.zeros(10, np.int32); offs = np.zeros(12, np.int64); nbytes = ctypes.c_int64(0)
+    image = np.zeros(1 << 16, np.uint8); why = ctypes.create_string_buffer(512)
+    rc = getattr(lib, entry)(ctypes.c_int32(baked.n_states), ctypes.c_int32(baked.silent_start), ctypes.c_int32(baked.start), ctypes.c_int32(baked.end),
+                             *([_ptr(a) for a in arrs] + extra + [ctypes.byref(brc), _ptr(head), _ptr(offs), _ptr(image), ctypes.c_int64(len(image)),
+                                                                ctypes.byref(nbytes), why, ctypes.c_int32(512)]))
+    if rc != STRQ_OK:
+        raise StriqueHipError(rc, "%s: bad argument" % entry)
+    out = {"rc": int(brc.value), "why": why.value.decode()}
+    if brc.value:
+        return out
+    if nbytes.value > len(image):
+        raise StriqueHipError(STRQ_ERR_NOMEM, "%s: an image of %d bytes" % (entry, nbytes.value))
+    out.update(n_emit=int(head[0]), n_branch=int(head[1]), mode=int(head[2]), deg=int(head[3]), deg2=int(head[4]),
+               end_deg=[int(v) for v in head[5:5 + int(head[1])]])
+    for name, at in zip(_IMAGE_ORDER, offs):
+        dtype, shape = shapes[name]
+        count = int(np.prod(shape))
+        out[name] = np.frombuffer(image.tobytes(), dtype, count, int(at)).reshape(shape).copy()
+    return out
+
+
+def debug_variant_image(baked, n_alt):
+    """strq_debug_variant_image: the edge image of the variant pass for a baked model, as a dict -- 'rc' (0, or 1 with 'why': a model
+    the pass does not cover), 'mode', 'n_branch', 'deg', 'deg2', 'end_deg' and the arrays of VARIANT_IMAGE_SHAPES.  No context, no device."""
+    return _debug_image("strq_debug_variant_image", VARIANT_IMAGE_SHAPES, baked, [ctypes.c_int32(n_alt)])
+
+
+def debug_mod_llr_image(baked):
+    """strq_debug_mod_llr_image: the same for the per-unit scores of the modification pass (MOD_LLR_IMAGE_SHAPES)."""
+    return _debug_image("strq_debug_mod_llr_image", MOD_LLR_IMAGE_SHAPES, baked, [])
+
+
 class Context(object):
     """One HIP context / stream / workspace on one GPU (strq_ctx)."""
 
@@ -676,6 +731,51 @@ class Context(object):
                         "band_lo": band_lo[c0:c0 + k].copy(), "table": table[256 * c0:256 * c0 + entries].copy(),
                         "hi16": slot[:2 * total].view(np.uint16).copy(), "lo8": slot[lo_at:lo_at + total].copy(),
                         "handed": [(int(h[1]), int(h[2])) for h in handed if h[0] == j]})
+        return out
+
+    def _debug_scores(self, entry, nv, model_ids, xs, ws, extra):
+        if not (len(model_ids) == len(xs) == len(ws)):
+            raise ValueError("one model id, one stretch and one array of bounds per read")
+        x, x_off = _offsets(xs, np.float64); w, w_off = _offsets(ws, np.int32)
+        ids = _c(model_ids, np.int32); out = np.zeros((max(1, int(w_off[-1])), nv), np.float64); launched = np.full(2, -1, np.int32)
+        self._check(getattr(self._lib, entry)(self._h, ctypes.c_int32(len(xs)), _ptr(ids), *(extra + [_ptr(x), _ptr(x_off), _ptr(w), _ptr(w_off),
+                                                                                                  _ptr(out), _ptr(launched)])))
+        out = out[:int(w_off[-1])]
+        return [out[int(w_off[r]):int(w_off[r + 1])] for r in range(len(xs))], (int(launched[0]), int(launched[1]))
+
+    def debug_variant_scores(self, model_ids, n_alt, xs, ws):
+        """strq_debug_variant_scores: per read a model id, its stretch (float64) and its bounds (int32); one launch of the variant
+        score kernel.  Returns ([(passages, n_alt + 1) float64 per read], (mode, NB) of the instance that ran)."""
+        return self._debug_scores("strq_debug_variant_scores", n_alt + 1, model_ids, xs, ws, [ctypes.c_int32(n_alt)])
+
+    def debug_mod_llr_scores(self, model_ids, xs, ws):
+        """strq_debug_mod_llr_scores: the same through the kernel of the per-unit scores; (V_base, V_mod) per unit, (mode, 2)."""
+        return self._debug_scores("strq_debug_mod_llr_scores", 2, model_ids, xs, ws, [])
+
+    def debug_variant_bounds(self, model_id, n_alt, lengths, paths=None, recs=None, last=None, status=None, cap=None, guard=4):
+        """strq_debug_variant_bounds: count pass and write pass of the bounds kernels for reads of `lengths` observations -- `paths`
+        (one int32 state path per read: the scan route) or `recs` (T + 1 uint64 hub records per read) with `last` (the hop route);
+        `status` the decode status per read (default 0), `cap` the cap of the write pass per read (default -1: the count).
+        One dict per read: 'n', 'bad_count', 'bad_write', 'cap' (of the write pass), 'w', 'branch' (the `cap` entries), 'untouched'."""
+        nr = len(lengths)
+        off = np.zeros(nr + 1, np.int64); off[1:] = np.cumsum(lengths)
+        status = _c(np.zeros(nr) if status is None else status, np.int32); cap = _c(np.full(nr, -1) if cap is None else cap, np.int32)
+        stride = int(max([t // 3 + 1 for t in lengths] + [int(v) for v in cap])) + guard
+        p = r = l = None
+        if paths is not None:
+            p, _ = _offsets(paths, np.int32)
+        else:
+            r, _ = _offsets(recs, np.uint64); l = _c(last, np.uint32)
+        n = np.zeros(nr, np.int32); bad = np.zeros((nr, 2), np.int32); w = np.zeros((nr, stride), np.int32); br = np.zeros((nr, stride), np.int32)
+        same = np.zeros(nr, np.int32)
+        self._check(self._lib.strq_debug_variant_bounds(self._h, ctypes.c_int32(model_id), ctypes.c_int32(n_alt), ctypes.c_int32(nr), _ptr(off), _ptr(p),
+                                                        _ptr(r), _ptr(l), _ptr(status), _ptr(cap), ctypes.c_int32(stride), ctypes.c_int32(guard),
+                                                        _ptr(n), _ptr(bad), _ptr(w), _ptr(br), _ptr(same)))
+        out = []
+        for i in range(nr):
+            k = int(cap[i]) if cap[i] >= 0 else int(n[i])
+            out.append({"n": int(n[i]), "bad_count": int(bad[i, 0]), "bad_write": int(bad[i, 1]), "cap": k, "w": w[i, :k].copy(),
+                        "branch": br[i, :k].copy(), "untouched": bool(same[i])})
         return out
 
     def debug_filtered(self, read, n, dtype=np.int16):
