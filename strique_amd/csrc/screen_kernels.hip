@@ -43,6 +43,10 @@ __device__ __forceinline__ int dpp_shr1(int v, int fill)      // lane l receives
 {
     return __builtin_amdgcn_update_dpp(fill, v, 0x138, 0xF, 0xF, false);
 }
+__device__ __forceinline__ int dpp_shr1_open(int v)      // lane l receives lane l - 1; lane 0 receives 0: for callers that overwrite lane 0
+{
+    return __builtin_amdgcn_mov_dpp(v, 0x138, 0xF, 0xF, true);
+}
 __device__ __forceinline__ int med3i(int a, int lo, int hi)
 {
     int r;
@@ -60,6 +64,14 @@ __device__ __forceinline__ int max3i(int a, int b, int c)
 {
     int r;
     asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+// v + u (u wave-uniform) as one instruction the compiler takes as it stands: left to itself it turns the column potentials of an
+// unrolled loop body into induction variables of their own, one addition and one copy more per body than the chain written here
+__device__ __forceinline__ int add_uniform(int v, int u)
+{
+    int r;
+    asm("v_add_u32 %0, %2, %1" : "=v"(r) : "v"(v), "s"(u));
     return r;
 }
 __device__ __forceinline__ int sel_mask(int if0, int if1, uint64_t mask)      // wave-uniform lane mask in an SGPR pair
@@ -281,14 +293,17 @@ constexpr int CPL = STRQ_SCREEN2_CPL, LPF = STRQ_SCREEN2_LPF, LB = STRQ_SCREEN2_
 
 struct Lane2Const { int lo2[CPL], hi2[CPL], off[CPL]; };
 
-template <int RPC>
+// CMG: how many steps of a full chunk share one sample of the last row for the chunk's maximum (1: every column, the fine bound)
+template <int RPC, int CMG>
 struct Screen2 {
     static constexpr int R2 = RPC * CPL;
+    static_assert(CMG == 1 || CMG == 2 || CMG == 4, "groups must divide the 64 steps of a chunk");
     const char* lds;
     const Lane2Const& lc;
     const uint64_t top_mask;           // lanes 0 and LB: their row above is the free top row
     const int lane, n, hh;
     int T[R2], SbotA, upS, potB, cmax;
+    int gpot, gmax;                    // CMG > 1: the potential of the group's first column; the running maximum of the samples (no bias)
     int qq;
     int scA[CPL], scB[CPL];
 
@@ -306,18 +321,29 @@ struct Screen2 {
     // One step = the lane's two columns.  Written so that nothing is copied from one step to the next: column B of row r - 1 is
     // computed right after column A of row r and takes the register of the old T[r - 1] (dead from there on), and the scores of a
     // class are fetched for the NEXT step as soon as its rows are done, into the registers they just left (the LDS latency hides
-    // behind the rest of the step).  99 VALU instructions per step at RPC = 3 (30 cells), of which 47 issue at the half rate
-    // (31 v_max3_f32, 10 v_med3_i32, 3 DPP moves, 2 selects, 1 v_readlane): 4.7 cycles each + 2.4 for the others is the step's
-    // 357 SIMD cycles (tools/runs_r05: hoisting the additions out of the chain or other waves-per-SIMD settings move it by < 1 %).
+    // behind the rest of the step).  What one step hands to the next -- the level pair, the potential, the row above -- is not
+    // copied either as long as the loop body holds an even number of steps (screen2_body): the values alternate between two
+    // registers.  72 VALU instructions per step at RPC = 2 (20 cells: 40; 10 look-ups: 20; 2 potentials, 3 DPP moves, 2 selects,
+    // the level pair's v_readlane, v_mov and unpacking: 11; the chunk maximum: 2 per group of CMG steps), 156 at RPC = 6
+    // (DESIGN.md 4.2e has the table and what the instructions cost).
+    //
+    // The chunk's maximum.  The predicated path and CMG = 1 take every column: max(T[last row] - pot) over the chunk's columns.  The
+    // full path with CMG > 1 takes ONE sample per group of CMG steps (gfirst / glast mark the group's ends): the last row at the
+    // group's last column minus the potential of its first.  T does not decrease along a row (horizontal moves are free in the T
+    // potential) and the potential grows by hh per column, so T(j) - pot(j) <= T(j_last) - pot(j_first) for every column j of the
+    // group: still an upper bound, at most (2 CMG - 1) hh above the per-column value.
     template <bool PRED>
-    __device__ __forceinline__ void step(int t, int qsrc, int snext)
+    __device__ __forceinline__ void step(int t, int qsrc, int snext, bool gfirst = true, bool glast = true)
     {
         const int qn = __builtin_amdgcn_update_dpp(__builtin_amdgcn_readlane(qsrc, snext), qq, 0x138, 0xF, 0xF, false);
         const int qa = qn & 0xffff, qb = (int)((unsigned)qn >> 16);
-        const int potA = potB + hh, potBn = potA + hh;
-        // the row above the lane: lane - 1's bottom cells; lanes 0 and LB: the top row (the column potential)
-        const int upA = sel_mask(dpp_shr1(SbotA, potA), potA, top_mask);
-        const int upB = sel_mask(dpp_shr1(T[R2 - 1], potBn), potBn, top_mask);
+        const int potA = add_uniform(potB, hh), potBn = add_uniform(potA, hh);
+        // the row above the lane: lane - 1's bottom cells; lanes 0 and LB: the top row (the column potential).  The select overwrites
+        // the one lane the shift leaves without a source, so the shift needs no defined value there (and no copy to provide it)
+        const int upA = sel_mask(dpp_shr1_open(SbotA), potA, top_mask);
+        const int upB = sel_mask(dpp_shr1_open(T[R2 - 1]), potBn, top_mask);
+        constexpr bool GROUPED = !PRED && CMG > 1;
+        if (GROUPED && gfirst) gpot = potA;
         bool act = true, okB = true;
         if constexpr (PRED) { const int jB = 2 * (t - lane), jA = jB - 1; act = (jA >= 1) && (jA <= n); okB = jB <= n; }
         int ta_prev = upA, ta_prev2 = upS;          // column A of rows r - 1, r - 2 (row -1: the row above the lane)
@@ -341,8 +367,12 @@ struct Screen2 {
                     T[R2 - 1] = tb;
                     SbotA = ta_prev;
                     upS = upB;
-                    const int cA = ta_prev - potA + STRQ_SCREEN_BIAS, cB = okB ? tb - potBn + STRQ_SCREEN_BIAS : cA;
-                    cmax = max3i(cmax, cA, cB);
+                    if constexpr (GROUPED) {
+                        if (glast) { const int d = tb - gpot; gmax = d > gmax ? d : gmax; }
+                    } else {
+                        const int cA = ta_prev - potA + STRQ_SCREEN_BIAS, cB = okB ? tb - potBn + STRQ_SCREEN_BIAS : cA;
+                        cmax = max3i(cmax, cA, cB);
+                    }
                 }
             }
             // the class's scores for the next step (scB[c] serves the last row of class c one row later: fetch B one class behind)
@@ -364,7 +394,7 @@ __device__ __forceinline__ int load_chunk2(const Screen2Task& tk, int chunk, int
     return (a * 2) | ((b * 2) << 16);
 }
 
-template <int RPC>
+template <int RPC, int CMG>
 __device__ __forceinline__ void screen2_body(const Screen2Task* __restrict__ tasks, int n_groups, int* __restrict__ queue, const ScreenParams& sp)
 {
     constexpr int R2 = RPC * CPL, MERGE = S / RPC;
@@ -415,13 +445,13 @@ __device__ __forceinline__ void screen2_body(const Screen2Task* __restrict__ tas
         const uint64_t top_mask = 1ull | (1ull << LB);
         // lanes whose last register holds a flank's last row (rows below a flank score 0 and copy it)
         const int lMa = (tk.k[0] - 1) / CPL, lMb = LB + (tk.k[1] - 1) / CPL;
-        Screen2<RPC> s2{ldsb, lc, top_mask, lane, tk.n, sp.hh};
+        Screen2<RPC, CMG> s2{ldsb, lc, top_mask, lane, tk.n, sp.hh};
         {
 #pragma unroll
             for (int r = 0; r < R2; ++r) s2.T[r] = STRQ_SCREEN_BIAS;
             s2.SbotA = STRQ_SCREEN_BIAS; s2.upS = STRQ_SCREEN_BIAS;
             s2.potB = STRQ_SCREEN_BIAS - 2 * lane * sp.hh;
-            s2.cmax = STRQ_SCREEN_BIAS;
+            s2.cmax = STRQ_SCREEN_BIAS; s2.gpot = 0; s2.gmax = 0;
         }
         const int nsteps = (tk.n + 1) / 2 + 63;
         int qcur = load_chunk2(tk, 0, lane);
@@ -431,8 +461,20 @@ __device__ __forceinline__ void screen2_body(const Screen2Task* __restrict__ tas
             const bool full = (t0s >= 63) && (2 * (t0s + 64) <= tk.n);
             const int send = nsteps - t0s < 64 ? nsteps - t0s : 64;
             if (full) {
-                for (int s = 0; s < 63; ++s) s2.template step<false>(t0s + s + 1, qcur, s + 1);
-                s2.template step<false>(t0s + 64, qnext, 0);
+                // U steps per loop body: a whole group of the chunk maximum, and an even number of steps, so that what one step hands
+                // to the next (levels, potential, the row above) alternates between two registers instead of being copied back
+                constexpr int U = CMG > 2 ? CMG : 2;
+                s2.gmax = 0;
+#pragma unroll 1
+                for (int s = 0; s < 64 - U; s += U) {
+#pragma unroll
+                    for (int u = 0; u < U; ++u) s2.template step<false>(0, qcur, s + u + 1, u % CMG == 0, u % CMG == CMG - 1);
+                }
+                // the chunk's last U steps: the last one takes the first level pair of the next chunk
+#pragma unroll
+                for (int u = 0; u < U - 1; ++u) s2.template step<false>(0, qcur, 64 - U + u + 1, u % CMG == 0, u % CMG == CMG - 1);
+                s2.template step<false>(0, qnext, 0, CMG == 1, true);
+                if constexpr (CMG > 1) s2.cmax = s2.gmax + STRQ_SCREEN_BIAS;
             } else {
                 for (int s = 0; s < send; ++s) {
                     const int qsrc = s == 63 ? qnext : qcur, snext = (s + 1) & 63;
@@ -458,16 +500,23 @@ size_t screen2_lds_bytes(int tsize_a, int tsize_b)
 
 // MERGE = 3: two DP rows per class, ten per lane.  (Rounds 5 measured MERGE 2 and 6 as well -- 114.4 and 96.6 ms per 4096 reads against
 // 94.7, with 2.4 % / 14 % of the alignments in the second look against 6 %: DESIGN.md 4.2e -- those instances are gone.)
+#ifndef STRQ_SCREEN3_CMG
+#define STRQ_SCREEN3_CMG 2         // steps per sample of the chunk maximum in the coarse screen's full chunks (1, 2 or 4): the bound is up to
+                                   // (2 CMG - 1) hh looser -- 3 score units; 4 measured the same step time as 2
+#endif
 #define STRQ_SCREEN2_ATTR(WPE_) __attribute__((amdgpu_flat_work_group_size(64 * STRQ_SCREEN_SEG, 64 * STRQ_SCREEN_SEG), amdgpu_waves_per_eu(WPE_, WPE_)))
-__global__ void STRQ_SCREEN2_ATTR(6) align_screen3_kernel(const Screen2Task* __restrict__ tasks, int n_groups, int* __restrict__ queue, ScreenParams sp) { screen2_body<2>(tasks, n_groups, queue, sp); }
+__global__ void STRQ_SCREEN2_ATTR(6) align_screen3_kernel(const Screen2Task* __restrict__ tasks, int n_groups, int* __restrict__ queue, ScreenParams sp) { screen2_body<2, STRQ_SCREEN3_CMG>(tasks, n_groups, queue, sp); }
 // ... and no merging at all: the fine screen's bound (one DP row per flank row, 30 per lane) for both flanks of a read in one wave, without the class
 // selects of align_screen_kernel -- what the fine screen runs on whenever a sub-batch holds both alignments of its reads (every detect call)
-__global__ void STRQ_SCREEN2_ATTR(4) align_screen1_kernel(const Screen2Task* __restrict__ tasks, int n_groups, int* __restrict__ queue, ScreenParams sp) { screen2_body<6>(tasks, n_groups, queue, sp); }
+__global__ void STRQ_SCREEN2_ATTR(4) align_screen1_kernel(const Screen2Task* __restrict__ tasks, int n_groups, int* __restrict__ queue, ScreenParams sp) { screen2_body<6, 1>(tasks, n_groups, queue, sp); }
 
 // Candidate windows of every alignment.
 // A chunk's value v bounds the float32 last-row values S of its columns: S * sc <= max(v', bound) + slack, v' = v - m * v_gap
 // (bound: the cold-start score of the pieces).  The best chunk value vmax is reached by a real path whose float32 score is at
 // least (vmax' - m) / sc - slack / sc.  Columns of chunks with max(v', bound) + slack < vmax' - m - slack cannot hold the optimum.
+// (That is the fine screen's rule.  The coarse screen's values -- merged rows, grouped chunk maxima -- are upper bounds that no
+// path needs to attain: its threshold is vmax - margin, taken on trust by nobody -- the exact pass certifies the windows by reaching
+// lower_bound, and what it cannot certify gets the second look.  Nothing on that route reads a chunk value as a score some path has.)
 __global__ void __launch_bounds__(256)
 screen_windows_kernel(const ScreenTask* __restrict__ tasks, int n_groups, ScreenParams sp,
                       const int32_t* __restrict__ bound_scaled, ScreenWindows* __restrict__ out,
