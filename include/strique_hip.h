@@ -618,7 +618,9 @@ int strq_last_screen(const strq_ctx* ctx, double out[8]);
  * (it did not pay on the last one it ran on)   [3] the coarse screen's candidate margin in score units (x 1.3 / 1.75 at three / six
  * rows per DP row)   [4] flank rows per DP row of the screen that ran (3: align_screen3_kernel, 1: align_screen1_kernel, 0: the one-flank
  * kernel)   [5] alignments of the last batched call that missed the first look's certificate and were resolved by the coarse screen's second look
- * (or belonged to an attempt that started over with the fine screen)   [6..7] 0. */
+ * (or belonged to an attempt that started over with the fine screen)   [6] LDS layout of the score tables in the two-flank kernels of that
+ * screen: 1 the lane-major image (one 16-bit column per lane, no bank conflicts), 2 class rows (STRQ_SCREEN_LDS=rows, or an image that
+ * would not fit: wide bands), 0 the one-flank kernel or no screen   [7] 0. */
 int strq_last_screen_mode(const strq_ctx* ctx, int32_t out[8]);
 /* The two sub-batches in flight, since the start of the last run call: [0] ms of HMM Viterbi launches whose rows were taken
  * [1] of them, ms that lay under the screen kernel of the sub-batch that followed   [2] ... under its whole alignment stage

@@ -71,9 +71,17 @@ int launch_screen(hipStream_t stream, const ScreenTask* tasks, int n_groups, int
 // merge times as large, so the scale is smaller); screen2_flank_ok: the flank fits 29 lanes of 5 classes
 int screen2_plan(const AlignParams& p, int samples, int max_n, int merge, ScreenParams* sp);
 static inline bool screen2_flank_ok(int m, int k) { return k >= 1 && k <= STRQ_SCREEN2_LPF * STRQ_SCREEN2_CPL && m == k * STRQ_SCREEN_S; }
+// The two LDS layouts of the read's 16-bit tables (screen_kernels.hip: screen2_body).  Class rows: screen2_lds_bytes from the entries of
+// the two float32 tables.  Lane-major image (screen_lds_layout.h, no bank conflicts): screen2_lanes_rows bounds its rows from the widest
+// band of either table (LutInfo::need), screen2_lanes_fit says whether a launch may use it (the LDS budget beside the Viterbi),
+// screen2_lanes_lds_bytes sizes it.  launch_screen2: lanes_rows > 0 runs the lane-major kernels with an image of that many rows
+// (lds_bytes covers it), 0 the class-row ones.
 size_t screen2_lds_bytes(int tsize_a, int tsize_b);
+int screen2_lanes_rows(int need_a, int need_b);
+bool screen2_lanes_fit(int rows);
+size_t screen2_lanes_lds_bytes(int rows);
 int launch_screen2(hipStream_t stream, const Screen2Task* tasks, int n_groups, int* queue, const ScreenParams& sp,
-                   size_t lds_bytes, int groups_per_cu, int n_cu, int merge);
+                   size_t lds_bytes, int groups_per_cu, int n_cu, int merge, int lanes_rows);
 // list / theta_list (nullable, device): only the alignments list[0 .. n_groups), each with the candidate threshold theta_list[idx]
 // in chunk units (the coarse screen's second look: every chunk whose bound reaches the score the first look found); out[idx]
 int launch_screen_windows(hipStream_t stream, const ScreenTask* tasks, int n_groups, const ScreenParams& sp,

@@ -30,6 +30,7 @@
 #include <stdlib.h>
 #include <cmath>
 #include "screen_kernels.h"
+#include "screen_lds_layout.h"
 
 namespace strq {
 
@@ -385,23 +386,38 @@ struct Screen2 {
     }
 };
 
+// The level pairs of a chunk, each level pre-scaled to the byte offset of its table entry: by 2 (16-bit entries side by side in a class
+// row) or by screen_lanes::ROW_BYTES (one entry per row of the lane-major image)
+template <int SHIFT>
 __device__ __forceinline__ int load_chunk2(const Screen2Task& tk, int chunk, int lane)
 {
     const int idx = (chunk * 64 + lane) * 2;
     int a = 0, b = 0;
     if (idx < tk.n) a = tk.levels[idx];
     if (idx + 1 < tk.n) b = tk.levels[idx + 1];
-    return (a * 2) | ((b * 2) << 16);
+    return (a << SHIFT) | (b << (SHIFT + 16));
 }
 
-template <int RPC, int CMG>
-__device__ __forceinline__ void screen2_body(const Screen2Task* __restrict__ tasks, int n_groups, int* __restrict__ queue, const ScreenParams& sp)
+// The two 16-bit score tables of a read in LDS.  Both layouts hold the same numbers -- MERGE (ceil(s * sc) + hh + v): what the merged row
+// gains on a diagonal step (all its rows' scores and potentials) -- and a look-up is v_med3_i32 (the level's byte offset clamped into
+// the class's band), v_add_u32, ds_read_u16 in both.
+//   LANES = false, class rows: the ragged rows of the float32 table back to back, each table padded to a dword and followed by a zero
+//     pair (classes beyond the flank).  The lanes of a look-up fall on effectively random banks: about two thirds of the kernel's
+//     LDS cycles were bank conflicts (profiles/r06_sq.md).
+//   LANES = true, lane-major image (screen_lds_layout.h): every lane reads its own 16-bit column of 128-byte rows, no conflicts.
+//     Larger (a row per level of the tallest lane; repeated k-mers stored per occurrence): the host launches it only where the image
+//     stays within screen_lanes::MAX_ROWS (launch_screen2), lds_rows is what it allocated.
+template <int RPC, int CMG, bool LANES>
+__device__ __forceinline__ void screen2_body(const Screen2Task* __restrict__ tasks, int n_groups, int* __restrict__ queue, const ScreenParams& sp, int lds_rows)
 {
     constexpr int R2 = RPC * CPL, MERGE = S / RPC;
+    constexpr int QSHIFT = LANES ? screen_lanes::ROW_SHIFT : 1;
+    static_assert(CPL == screen_lanes::CPL, "screen_lds_layout.h stacks the lane's five classes");
     extern __shared__ uint32_t lds_all[];
     __shared__ int next_group;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const char* ldsb = reinterpret_cast<const char*>(lds_all);
+    const int f = lane >= LB ? 1 : 0, lf = lane - f * LB;
     for (;;) {
         __syncthreads();
         if (threadIdx.x == 0) next_group = atomicAdd(queue, 1);
@@ -409,26 +425,52 @@ __device__ __forceinline__ void screen2_body(const Screen2Task* __restrict__ tas
         const int gi = __builtin_amdgcn_readfirstlane(next_group);
         if (gi >= n_groups) break;
         const Screen2Task& t0 = tasks[(size_t)gi * SEG];
-        int base[2], zero_idx[2];          // in 16-bit entries
+        const float scf = (float)sp.sc;
+        Lane2Const lc;
+        if constexpr (LANES) {
+            // the lane's classes (the same for the four pieces of the read: every wave fills rows of the one image)
+            uint32_t desc[CPL];
+            int nc = 0, rowbase[CPL];
+#pragma unroll
+            for (int c = 0; c < CPL; ++c) {
+                const int k = lf * CPL + c;
+                const bool in = lf < LPF && k < t0.k[f];
+                desc[c] = in ? (uint32_t)t0.band_lo[f][k] : 0u;
+                nc += in ? 1 : 0;
+            }
+            screen_lanes::row_bases(desc, nc, rowbase);
+            // wave w fills rows = w (mod 4) of every lane's column: a store's 32 lanes of a flank hit 32 banks
+            char* dst = reinterpret_cast<char*>(lds_all);
+            if (wave == 0) *reinterpret_cast<uint16_t*>(dst + screen_lanes::slot(lane)) = 0;
+#pragma unroll
+            for (int c = 0; c < CPL; ++c) {
+                const screen_lanes::ClassAddr a = c < nc ? screen_lanes::class_addr(lane, rowbase[c], desc[c]) : screen_lanes::padding_addr(lane);
+                lc.lo2[c] = a.lo2; lc.hi2[c] = a.hi2; lc.off[c] = a.off;
+                if (c < nc) {
+                    const float* src = t0.table[f] + screen_lanes::desc_off(desc[c]);
+                    const int w1 = screen_lanes::desc_w1(desc[c]);
+                    for (int i = (wave - rowbase[c]) & (SEG - 1); i <= w1; i += SEG)
+                        if (rowbase[c] + i < lds_rows)
+                            *reinterpret_cast<uint16_t*>(dst + screen_lanes::entry_address(lane, rowbase[c], i)) = (uint16_t)(MERGE * ((int)ceilf(src[i] * scf) + sp.cadd));
+                }
+            }
+        }
+        [[maybe_unused]] int base[2], zero_idx[2];          // class rows, in 16-bit entries
         base[0] = 0; zero_idx[0] = (t0.tsize[0] + 1) & ~1;
         base[1] = zero_idx[0] + 2; zero_idx[1] = base[1] + ((t0.tsize[1] + 1) & ~1);
-        {
-            // MERGE (ceil(s * sc) + hh + v): what the merged row gains on a diagonal step (all its rows' scores and potentials)
+        if constexpr (!LANES) {
             uint16_t* dst = reinterpret_cast<uint16_t*>(lds_all);
-            const float scf = (float)sp.sc;
 #pragma unroll
-            for (int f = 0; f < 2; ++f) {
-                for (int i = threadIdx.x; i < t0.tsize[f]; i += 64 * SEG) dst[base[f] + i] = (uint16_t)(MERGE * ((int)ceilf(t0.table[f][i] * scf) + sp.cadd));
-                if (threadIdx.x == 0) { dst[zero_idx[f]] = 0; dst[zero_idx[f] + 1] = 0; }
+            for (int ff = 0; ff < 2; ++ff) {
+                for (int i = threadIdx.x; i < t0.tsize[ff]; i += 64 * SEG) dst[base[ff] + i] = (uint16_t)(MERGE * ((int)ceilf(t0.table[ff][i] * scf) + sp.cadd));
+                if (threadIdx.x == 0) { dst[zero_idx[ff]] = 0; dst[zero_idx[ff] + 1] = 0; }
             }
         }
         __syncthreads();
         const Screen2Task& tk = tasks[(size_t)gi * SEG + wave];
         if (tk.n <= 0) continue;
 
-        Lane2Const lc;
-        const int f = lane >= LB ? 1 : 0, lf = lane - f * LB;
-        {
+        if constexpr (!LANES) {
 #pragma unroll
             for (int c = 0; c < CPL; ++c) {
                 const int k = lf * CPL + c;
@@ -454,10 +496,10 @@ __device__ __forceinline__ void screen2_body(const Screen2Task* __restrict__ tas
             s2.cmax = STRQ_SCREEN_BIAS; s2.gpot = 0; s2.gmax = 0;
         }
         const int nsteps = (tk.n + 1) / 2 + 63;
-        int qcur = load_chunk2(tk, 0, lane);
+        int qcur = load_chunk2<QSHIFT>(tk, 0, lane);
         s2.prime(qcur);
         for (int t0s = 0; t0s < nsteps; t0s += 64) {
-            const int qnext = load_chunk2(tk, t0s / 64 + 1, lane);
+            const int qnext = load_chunk2<QSHIFT>(tk, t0s / 64 + 1, lane);
             const bool full = (t0s >= 63) && (2 * (t0s + 64) <= tk.n);
             const int send = nsteps - t0s < 64 ? nsteps - t0s : 64;
             if (full) {
@@ -494,9 +536,13 @@ __device__ __forceinline__ void screen2_body(const Screen2Task* __restrict__ tas
 
 size_t screen2_lds_bytes(int tsize_a, int tsize_b)
 {
-    // both tables as 16-bit entries, each padded to a dword and followed by a zero pair (the rows below a flank)
+    // class rows: both tables as 16-bit entries, each padded to a dword and followed by a zero pair (the rows below a flank)
     return (size_t)(((tsize_a + 1) & ~1) + 2 + ((tsize_b + 1) & ~1) + 2) * 2;
 }
+
+int screen2_lanes_rows(int need_a, int need_b) { return screen_lanes::rows_bound(need_a, need_b); }
+bool screen2_lanes_fit(int rows) { return screen_lanes::fits(rows); }
+size_t screen2_lanes_lds_bytes(int rows) { return screen_lanes::bytes(rows); }
 
 // MERGE = 3: two DP rows per class, ten per lane.  (Rounds 5 measured MERGE 2 and 6 as well -- 114.4 and 96.6 ms per 4096 reads against
 // 94.7, with 2.4 % / 14 % of the alignments in the second look against 6 %: DESIGN.md 4.2e -- those instances are gone.)
@@ -505,10 +551,16 @@ size_t screen2_lds_bytes(int tsize_a, int tsize_b)
                                    // (2 CMG - 1) hh looser -- 3 score units; 4 measured the same step time as 2
 #endif
 #define STRQ_SCREEN2_ATTR(WPE_) __attribute__((amdgpu_flat_work_group_size(64 * STRQ_SCREEN_SEG, 64 * STRQ_SCREEN_SEG), amdgpu_waves_per_eu(WPE_, WPE_)))
-__global__ void STRQ_SCREEN2_ATTR(6) align_screen3_kernel(const Screen2Task* __restrict__ tasks, int n_groups, int* __restrict__ queue, ScreenParams sp) { screen2_body<2, STRQ_SCREEN3_CMG>(tasks, n_groups, queue, sp); }
+#define STRQ_SCREEN2_ARGS const Screen2Task* __restrict__ tasks, int n_groups, int* __restrict__ queue, ScreenParams sp, int lds_rows
+__global__ void STRQ_SCREEN2_ATTR(6) align_screen3_kernel(STRQ_SCREEN2_ARGS) { screen2_body<2, STRQ_SCREEN3_CMG, true>(tasks, n_groups, queue, sp, lds_rows); }
 // ... and no merging at all: the fine screen's bound (one DP row per flank row, 30 per lane) for both flanks of a read in one wave, without the class
 // selects of align_screen_kernel -- what the fine screen runs on whenever a sub-batch holds both alignments of its reads (every detect call)
-__global__ void STRQ_SCREEN2_ATTR(4) align_screen1_kernel(const Screen2Task* __restrict__ tasks, int n_groups, int* __restrict__ queue, ScreenParams sp) { screen2_body<6, 1>(tasks, n_groups, queue, sp); }
+__global__ void STRQ_SCREEN2_ATTR(4) align_screen1_kernel(STRQ_SCREEN2_ARGS) { screen2_body<6, 1, true>(tasks, n_groups, queue, sp, lds_rows); }
+// the same two on the class-row layout: launches whose lane-major image would exceed screen_lanes::MAX_ROWS (a flat level map: wide bands),
+// and STRQ_SCREEN_LDS=rows
+__global__ void STRQ_SCREEN2_ATTR(6) align_screen3_rows_kernel(STRQ_SCREEN2_ARGS) { screen2_body<2, STRQ_SCREEN3_CMG, false>(tasks, n_groups, queue, sp, lds_rows); }
+__global__ void STRQ_SCREEN2_ATTR(4) align_screen1_rows_kernel(STRQ_SCREEN2_ARGS) { screen2_body<6, 1, false>(tasks, n_groups, queue, sp, lds_rows); }
+#undef STRQ_SCREEN2_ARGS
 
 // Candidate windows of every alignment.
 // A chunk's value v bounds the float32 last-row values S of its columns: S * sc <= max(v', bound) + slack, v' = v - m * v_gap
@@ -702,15 +754,17 @@ int screen2_plan(const AlignParams& p, int samples, int max_n, int merge, Screen
 }
 
 int launch_screen2(hipStream_t stream, const Screen2Task* tasks, int n_groups, int* queue, const ScreenParams& sp,
-                   size_t lds_bytes, int groups_per_cu, int n_cu, int merge)
+                   size_t lds_bytes, int groups_per_cu, int n_cu, int merge, int lanes_rows)
 {
     if (n_groups <= 0) return 0;
     if (merge != 3 && merge != 1) return 2;
-    auto kern = merge == 3 ? align_screen3_kernel : align_screen1_kernel;
+    const bool lanes = lanes_rows > 0;
+    if (lanes && (!screen_lanes::fits(lanes_rows) || lds_bytes < screen_lanes::bytes(lanes_rows))) return 2;
+    auto kern = merge == 3 ? (lanes ? align_screen3_kernel : align_screen3_rows_kernel) : (lanes ? align_screen1_kernel : align_screen1_rows_kernel);
     if (merge == 1 && groups_per_cu > 4) groups_per_cu = 4;          // ... for four
     if (groups_per_cu > 6) groups_per_cu = 6;
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    hipLaunchKernelGGL(kern, dim3(groups_per_cu * n_cu), dim3(64 * SEG), lds_bytes, stream, tasks, n_groups, queue, sp);
+    hipLaunchKernelGGL(kern, dim3(groups_per_cu * n_cu), dim3(64 * SEG), lds_bytes, stream, tasks, n_groups, queue, sp, lanes_rows);
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 

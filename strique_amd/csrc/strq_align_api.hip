@@ -351,7 +351,7 @@ static int run_table_build(strq_ctx* c, hipStream_t st, TableBuild& b)
         }
         STRQ_HIP(c, hipMemcpy(jobs[j].table, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
         STRQ_HIP(c, hipMemcpy(jobs[j].band_lo, blo.data(), (size_t)kk * 4, hipMemcpyHostToDevice));
-        info[j].total = kk * 256;
+        info[j].total = kk * 256; info[j].need = 256;
     }
     b.hard_count = hard_count;
     return STRQ_OK;
@@ -424,6 +424,7 @@ struct ScreenJob {
     std::vector<int32_t> bound;          // per view: below this score a piece's values are not bounds of the whole matrix
     std::vector<size_t> out_off;         // per view and piece: its chunk maxima in the output
     size_t out_words = 0, lds_bytes = 0;
+    int lanes_rows = 0;                  // two-flank kernel: rows of the tallest lane-major table image of the launch (a bound: screen2_lanes_rows)
     double steps = 0;
 };
 
@@ -457,6 +458,7 @@ static void screen_tasks(CorePlan& p, const ScreenParams& sp, ScreenJob& j)
         Piece pc[SSEG];
         const int used = cut(n, SSEG, ov_s, pc);
         j.lds_bytes = std::max(j.lds_bytes, F == 2 ? screen2_lds_bytes(p.info[p.J0[a[0]]].total, p.info[p.J0[a[1]]].total) : screen_lds_bytes(p.info[p.J0[a[0]]].total));
+        if (F == 2) j.lanes_rows = std::max(j.lanes_rows, screen2_lanes_rows(p.info[p.J0[a[0]]].need, p.info[p.J0[a[1]]].need));
         // what the cold start of the pieces costs: below this score a piece's values are not bounds of the whole matrix
         for (int f = 0; f < F; ++f)
             j.bound[(size_t)g * F + f] = used <= 1 ? INT32_MIN / 2 : (ov_s >= ov_worst ? 0 : (int32_t)std::ceil((double)align_segment_min_score(p.c->ap, in.m[a[f]], ov_s) * sp.sc));
@@ -489,6 +491,14 @@ static int run_screen(CorePlan& p, ScreenJob& j, const ScreenParams& sp, const S
     strq_ctx* c = p.c; const AlignCoreIn& in = p.in;
     hipStream_t st = p.st;
     const int nv = (int)j.al.size();
+    // Two-flank kernels: the lane-major table image (screen_lds_layout.h: no bank conflicts) when the tallest image of the launch stays
+    // within the LDS budget, else -- wide bands: a flat level map, a host-rebuilt table -- the class rows for the whole launch.
+    // STRQ_SCREEN_LDS=rows|lanes: the class rows always / the default.
+    int lanes_rows = 0;
+    if (j.flanks == 2) {
+        const char* e = strq::opt("STRQ_SCREEN_LDS");
+        if (!(e && std::strcmp(e, "rows") == 0) && screen2_lanes_fit(j.lanes_rows)) { lanes_rows = j.lanes_rows; j.lds_bytes = screen2_lanes_lds_bytes(lanes_rows); }
+    }
     if (j.lds_bytes > 160 * 1024 - 64) { c->err = r.lds_err; return STRQ_ERR_UNSUPPORTED; }
     const int groups = std::max(1, std::min(r.groups_per_cu, (int)((160 * 1024 - 64) / j.lds_bytes)));
     auto aligned = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
@@ -510,7 +520,7 @@ static int run_screen(CorePlan& p, ScreenJob& j, const ScreenParams& sp, const S
     STRQ_HIP(c, hipEventRecord(c->ev[5], st));
     int* queue = c->queue.as<int>() + STRQ_QUEUE_FIRST - 1;
     if (j.flanks == 2) {
-        if (launch_screen2(st, d_t2, nv / 2, queue, sp, j.lds_bytes, groups, c->n_cu, r.merge)) { c->err = "coarse screen launch failed"; return STRQ_ERR_DEVICE; }
+        if (launch_screen2(st, d_t2, nv / 2, queue, sp, j.lds_bytes, groups, c->n_cu, r.merge, lanes_rows)) { c->err = "coarse screen launch failed"; return STRQ_ERR_DEVICE; }
     } else {
         if (launch_screen(st, d_st, nv, queue, sp, j.lds_bytes, groups, c->n_cu)) { c->err = "screen launch failed"; return STRQ_ERR_DEVICE; }
     }
@@ -520,6 +530,7 @@ static int run_screen(CorePlan& p, ScreenJob& j, const ScreenParams& sp, const S
     STRQ_HIP(c, hipMemcpyAsync(hw.data(), d_win, hw.size() * sizeof(ScreenWindows), hipMemcpyDeviceToHost, st));
     STRQ_HIP(c, hipStreamSynchronize(st));
     c->screen_ran = true; c->screen_mode_last = r.merge > 1 ? 2 : 1; c->coarse_merge_last = r.merge;
+    c->screen_lds_last = j.flanks == 2 ? (lanes_rows > 0 ? 1 : 2) : 0;
     if (const char* path = strq::opt("STRQ_SCREEN_DUMP")) {
         // tests: the chunk maxima as the kernel wrote them (tests/test_gpu_screen.py checks them against the exact last row)
         std::vector<int32_t> ho(j.out_words);
@@ -1616,6 +1627,7 @@ int strq_last_screen_mode(const strq_ctx* c, int32_t out[8])
     out[0] = c->screen_mode_last; out[1] = c->coarse_pause; out[2] = c->screen_pause; out[3] = (int32_t)c->coarse_margin;
     out[5] = (int32_t)std::min<int64_t>(c->look2_served, INT32_MAX);
     out[4] = c->screen_mode_last ? c->coarse_merge_last : 0;
+    out[6] = c->screen_mode_last ? c->screen_lds_last : 0;
     return STRQ_OK;
 }
 
