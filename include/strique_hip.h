@@ -394,6 +394,29 @@ int strq_batch_fetch_anchored(strq_ctx* ctx, strq_anchored* out, int64_t n);
  * windows that ran on the register-resident / on a lane-layout kernel shape.  After a run call that failed inside the pass the
  * figures are those of the part that ran (the rows of the failed sub-batch are back at their initial values). */
 int strq_last_anchored(strq_ctx* ctx, double* out8);
+/* Methylation calls of anchored reads (repeatModHMM.mod_repeats, STRique.py:492-500, on the stretch detect step 13,
+ * STRique.py:605-609, would hand it -- the reference itself calls spanning reads only).  With on = 1, a read gets a call when
+ *   its anchored record has kind 2 or 3 and status 0, begin < end (which status 0 implies), and its target has a modification model
+ *   (strq_target_set_mod);
+ * with nrm = normalize2model(raw, 'minmax') of the RAW signal, as the modification pass of a spanning read takes it,
+ *   pattern = mod_repeats(mod_model, [mod_min, mod_max], nrm[begin:end]): one character per unit the best path of the dual model
+ *   passes ('0' / '1'), "-" when that decode has no path;
+ * and, with strq_set_mod_llr on, (V_base(j), V_mod(j)) per character, defined on this stretch exactly as strq_set_mod_llr defines
+ * them on the stretch of a spanning read.  Spanning reads (their row has the pattern), kinds 0 / 1, records of status 1 / 2 and
+ * targets without a modification model get nothing.  The number of characters is not tied to the record's count.  Rows, records
+ * and every other output do not change.  A run call with the switch on fails before any launch (STRQ_ERR_ARG) when anchored
+ * counting is off, and when it is a scan.  Sub-batches still in flight keep the mode they were launched with (the call waits for
+ * them).  Default 0: no further kernel runs and no further buffer is reserved. */
+int strq_set_anchored_mod(strq_ctx* ctx, int32_t on);
+/* Calls of the last batch, in two calls like the other variable-length outputs: with chars = pool = NULL the lengths -- called[i]
+ * (nullable) = 1 when read i has a call, its characters are [off[i], off[i+1]), its units [voff[i], voff[i+1]) (none unless the run
+ * call also ran with strq_set_mod_llr; else as many as characters, none for "-"), totals in off[n] and voff[n]; then the
+ * characters in chars (chars_cap bytes) and V_base = pool[2 k], V_mod = pool[2 k + 1] of unit k (pool_cap counts units).
+ * STRQ_ERR_ARG when the last run call ran with the switch off. */
+int strq_batch_fetch_anchored_mod(strq_ctx* ctx, int32_t* called, int64_t* off, char* chars, int64_t chars_cap, int64_t* voff, double* pool, int64_t pool_cap);
+/* The calls of the last run call: out[0] = ms on the GPU (all its sub-batches: tasks, compaction, decode, patterns, scores),
+ * out[1] = reads called, out[2] = units (characters '0' / '1'), out[3] = kernels launched (0 with the switch off). */
+int strq_last_anchored_mod(strq_ctx* ctx, double* out4);
 /* ---- renorm: a second normalisation step for reads that are mostly repeat (no counterpart in the reference, whose 'minmax' map,
  * STRique.py:150-180, assumes that a read's k-mer composition looks like the pore model's) ----
  * Between the conditioning statistics and the flank alignments, every conditioned read of a target with tables gets scale and shift

@@ -264,6 +264,10 @@ def count(argv):
                                                                            "free_samples in the thousands means the read was wrongly taken for anchored)")
     parser.add_argument("--anchored-min-score", type=float, default=None, metavar="X", help="--anchored: a flank counts as found when its normalised score is at least X.  "
                                                                                            "Required with --anchored: there is no default (README, 'Anchored counting')")
+    parser.add_argument("--anchored-mod", dest="anchored_mod", default=None, metavar="FILE", help="With --mod_model and --anchored: also call the methylation pattern of the reads "
+                                                                                                  "that end or start inside the repeat, on the samples their record puts into the repeat, and "
+                                                                                                  "write it to FILE: one row per count row, columns " + " ".join(anchored_mod.MOD_HEADER) +
+                                                                                                  " (llr: the per-unit ratios when --mod-llr is given as well, else -)")
     parser.add_argument("--renorm", type=float, default=None, metavar="MIN_SHARE", help="Refit scale and shift of every read's normalised signals against its target's k-mer "
                                                                                       "composition, and count on the corrected signals where the fitted repeat share is at least "
                                                                                       "MIN_SHARE (inside (0, 1); there is no default: README, 'Renorm').  The count rows of such "
@@ -299,6 +303,12 @@ def count(argv):
         parser.error("--anchored-min-score needs --anchored FILE")
     if args.anchored_min_score is not None and not args.anchored_min_score > 0:
         parser.error("--anchored-min-score must be above 0")
+    if args.anchored_mod and not args.anchored:
+        parser.error("--anchored-mod needs --anchored FILE --anchored-min-score X: the calls are made on the reads anchored counting finds")
+    if args.anchored_mod and not args.mod_model:
+        parser.error("--anchored-mod needs --mod_model: the calls are those of the modification model")
+    if args.anchored_mod and args.scan:
+        parser.error("--anchored-mod cannot be combined with --scan: a scan takes a read for a target when it finds both flanks")
     if args.renorm is not None and not 0 < args.renorm < 1:
         parser.error("--renorm MIN_SHARE must be inside (0, 1)")
     if args.renorm_out and args.renorm is None:
@@ -374,7 +384,7 @@ def count(argv):
     stats = {}
     fault = 0
     paths = dict(units=args.units, confidence=args.confidence, mod_llr=args.mod_llr, scores=args.scan_scores, anchored=args.anchored, variants=args.variants,
-                 renorm=args.renorm_out)
+                 renorm=args.renorm_out, anchored_mod=args.anchored_mod)
     with contextlib.ExitStack() as stack:
         # rank 0 writes: as the batches are done in a single process (run_count), after the gather otherwise
         files = {name: stack.enter_context(open(path, 'w')) if (path and rank == 0) else None for name, path in paths.items()}
@@ -385,6 +395,7 @@ def count(argv):
                              units=bool(args.units), units_out=now['units'], scan=scan, scores_out=now['scores'],
                              confidence=bool(args.confidence), conf_out=now['confidence'], mod_llr=bool(args.mod_llr), llr_out=now['mod_llr'],
                              anchored=args.anchored_min_score, anchored_out=now['anchored'],
+                             anchored_mod=bool(args.anchored_mod), anchored_mod_out=now['anchored_mod'],
                              variants=alt_units if args.variants else None, variants_out=now['variants'],
                              renorm=args.renorm, renorm_out=now['renorm'])
         except DeviceFault:
@@ -401,7 +412,7 @@ def count(argv):
                 dist.destroy_process_group()
                 raise SystemExit(3)
             merged = gather_rows(rows, stats["items"], sdist, units=bool(args.units), scan=scan, confidence=bool(args.confidence), mod_llr=bool(args.mod_llr),
-                                 anchored=bool(args.anchored), variants=bool(args.variants), renorm=args.renorm is not None)
+                                 anchored=bool(args.anchored), variants=bool(args.variants), renorm=args.renorm is not None, anchored_mod=bool(args.anchored_mod))
             if rank == 0:
                 write_rows(out, merged.rows)
                 for o in OUTPUTS:
@@ -624,12 +635,31 @@ OUTPUTS = (
            lambda v: renorm_mod.pack(v), lambda text: renorm_mod.unpack(text), 'renorm_rows', False),
     Output('variants', lambda scan: VARIANTS_HEADER, lambda q, t, s, row, v: format_variants(q, t, s, row[0], v),
            lambda v: _pack_variants(v), lambda text: _unpack_variants(text), 'variant_rows', False),
+    Output('anchored_mod', lambda scan: anchored_mod.MOD_HEADER, lambda q, t, s, row, v: anchored_mod.format_mod_row(q, t, s, *(v or (None, None))),
+           lambda v: _pack_anchored_mod(v), lambda text: _unpack_anchored_mod(text), 'anchored_mod_rows', False),
     Output('anchored', lambda scan: anchored_mod.HEADER, lambda q, t, s, row, v: anchored_mod.format_row(q, t, s, v),
            lambda v: _pack_anchored(v), lambda text: _unpack_anchored(text), 'anchored_rows', False),
 )
-# (`renorm`, `variants` and `anchored`, the last fields, default to None: callers that build a Merged from the five values before them keep
-# working.  `anchored` stays the last field, as it did when `variants` came in: fields behind the first five are taken by name.)
-Merged = namedtuple('Merged', ['rows'] + [o.name for o in OUTPUTS], defaults=(None, None, None))
+# (`renorm`, `variants`, `anchored_mod` and `anchored`, the last fields, default to None: callers that build a Merged from the five values
+# before them keep working.  `anchored` stays the last field, as it did when `variants` and `anchored_mod` came in: fields behind the first
+# five are taken by name.)
+Merged = namedtuple('Merged', ['rows'] + [o.name for o in OUTPUTS], defaults=(None, None, None, None))
+
+
+def _pack_anchored_mod(v):
+    """(anchored record or None, methylation call or None) of a read as it travels between ranks: the record as _pack_anchored
+    packs it, then the pattern and the ratios ('-' for None each); call (pattern, ratios or None)."""
+    rec, call = v
+    fields = ['-' if rec is None else _pack_anchored(rec)]
+    if call is not None:
+        fields += ['+' + call[0], '-' if call[1] is None or len(call[1]) == 0 else _floats(call[1])]
+    return ';'.join(fields)
+
+
+def _unpack_anchored_mod(text):
+    f = text.split(';')
+    rec = None if f[0] == '-' else _unpack_anchored(f[0])
+    return (rec, None) if len(f) == 1 else (rec, (f[1][1:], None if f[2] == '-' else _unfloats(f[2])))
 
 
 def _pack_anchored(rec):
@@ -644,7 +674,7 @@ def _unpack_anchored(text):
 
 
 def outputs_on(**flags):
-    """The entries of OUTPUTS whose flag (units=, confidence=, mod_llr=, scores=, anchored=, variants=, renorm=) is set."""
+    """The entries of OUTPUTS whose flag (units=, confidence=, mod_llr=, scores=, anchored=, variants=, renorm=, anchored_mod=) is set."""
     return [o for o in OUTPUTS if flags.get(o.name)]
 
 
@@ -665,7 +695,7 @@ def _read_values(target, strand, det, scores=None):
     if det is None:
         return target, strand, None, dict(scores=scores)
     return target, strand, det.row, dict(units=det.units, confidence=det.conf, mod_llr=det.llr, scores=scores, anchored=det.anchored, variants=det.variants,
-                                         renorm=getattr(det, 'renorm', None))
+                                         renorm=getattr(det, 'renorm', None), anchored_mod=(det.anchored, getattr(det, 'anchored_mod', None)))
 
 
 def _emit(sink, on, seq, qname, target, strand, row, values):
@@ -699,13 +729,14 @@ def unpack_blob(on, blob):
     return fields[0], fields[1], fields[2], values
 
 
-def gather_rows(rows, items, sdist, units=False, scan=None, confidence=False, mod_llr=False, anchored=False, variants=False, renorm=False):
+def gather_rows(rows, items, sdist, units=False, scan=None, confidence=False, mod_llr=False, anchored=False, variants=False, renorm=False, anchored_mod=False):
     """Reads of this rank (run_count with world > 1) -> fixed-size records + one blob per read (pack_blob) -> one gather -> on rank 0
-    the rows of every file in input order: Merged(rows, units, confidence, mod_llr, scores, renorm, variants, anchored), [(sequence number, TSV row)] each, None
+    the rows of every file in input order: Merged(rows, units, confidence, mod_llr, scores, renorm, variants, anchored_mod, anchored), [(sequence number, TSV row)] each, None
     for an output that was not asked for (scores: asked for by scan) and for every field off rank 0.  `items`: every accepted (qname,
     strand, target) of the input, which each rank derives from the same SAM file (scan: from the same index).  A read that failed
     travels as a record with valid = 0 and writes nothing; a scan read without a winner as one with valid = 2: it writes a score row."""
-    on = outputs_on(units=units, confidence=confidence, mod_llr=mod_llr, scores=bool(scan), anchored=anchored, variants=variants, renorm=renorm)
+    on = outputs_on(units=units, confidence=confidence, mod_llr=mod_llr, scores=bool(scan), anchored=anchored, variants=variants, renorm=renorm,
+                    anchored_mod=anchored_mod)
     rec = np.zeros(len(rows), ROW_DTYPE); blobs = []; idx = np.zeros(len(rows), np.int64)
     for k, (seq, read) in enumerate(rows):
         idx[k] = seq
@@ -762,7 +793,7 @@ def route(stream, loci, log):
 
 def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, out=None, readers=0, stats=None, units=False, units_out=None,
               scan=None, scores_out=None, confidence=False, conf_out=None, mod_llr=False, llr_out=None, anchored=None, anchored_out=None,
-              variants=None, variants_out=None, renorm=None, renorm_out=None):
+              variants=None, variants_out=None, renorm=None, renorm_out=None, anchored_mod=False, anchored_mod_out=None):
     """Route the SAM records of `stream` to their targets, run this rank's share through
     `counter.detect_batch` and return [(sequence number, TSV row or -- several ranks -- what gather_rows takes)].
 
@@ -781,6 +812,9 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
     `anchored` (a score threshold, not with scan): the counter is asked for Detected records with the anchored record of every read
     (counter.detect_batch(..., anchored=threshold, records=True)); their rows (strique_amd.anchored.format_row) go to `anchored_out`
     and to stats["anchored_rows"].  The count rows and the other files do not change.
+    `anchored_mod` (with `anchored`, a counter with a modification model): the methylation calls of the anchored reads are on for this
+    run (counter.set_anchored_mod(True)); their rows (strique_amd.anchored.format_mod_row; the ratios with `mod_llr`) go to
+    `anchored_mod_out` and to stats["anchored_mod_rows"].  The count rows and the other files do not change.
     `variants` ({target: [alt units as configured]}, not with scan; the counter's targets were added with them): the counter is asked
     for Detected records with the variant pass on (counter.set_variants(True), counter.detect_batch(..., records=True)); their rows
     (variant_value, format_variants) go to `variants_out` and to stats["variant_rows"].  The count rows and the other files do not change.
@@ -798,6 +832,8 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
     stats.setdefault("failed", 0)
     if anchored is not None and scan:
         raise ValueError("anchored counting cannot be combined with a scan")
+    if anchored_mod and anchored is None:
+        raise ValueError("anchored methylation calls need anchored counting")
     if variants is not None and scan:
         raise ValueError("variants cannot be combined with a scan")
     if renorm is not None and scan:
@@ -805,18 +841,20 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
     if renorm is not None and not 0 < renorm < 1:
         raise ValueError("the renorm share threshold must be inside (0, 1)")
     files = dict(rows=out, units=units_out, confidence=conf_out, mod_llr=llr_out, scores=scores_out, anchored=anchored_out, variants=variants_out,
-                 renorm=renorm_out)
+                 renorm=renorm_out, anchored_mod=anchored_mod_out)
     on = outputs_on(units=units, confidence=confidence, mod_llr=mod_llr, scores=scan and scan["scores"], anchored=anchored is not None,
-                    variants=variants is not None, renorm=renorm is not None)
+                    variants=variants is not None, renorm=renorm is not None, anchored_mod=anchored_mod)
     if out is not None:
         print('\t'.join(HEADER), file=out)
     for o in OUTPUTS:
         stats.setdefault(o.stat, [])
         if files[o.name] is not None:
             print('\t'.join(o.header(scan)), file=files[o.name])
-    extras = {o.name: True for o in on if o.name not in ('scores', 'anchored', 'variants', 'renorm')}
+    extras = {o.name: True for o in on if o.name not in ('scores', 'anchored', 'variants', 'renorm', 'anchored_mod')}
     if anchored is not None:
         extras.update(anchored=anchored, records=True)
+    if anchored_mod:
+        counter.set_anchored_mod(True)
     if variants is not None:
         counter.set_variants(True)
         extras.update(records=True)

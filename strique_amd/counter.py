@@ -38,7 +38,8 @@ target_classifier = namedtuple('target_classifier',
 # free_samples -- every kind, as strq_batch_fetch_anchored hands it out); see repeatCounter.detect_batch
 # variants: (count_v, pattern, branch, end, V) of the variant pass, see repeatCounter.detect_batch
 # renorm: (applied, {signal: None or (a, b, w, score)}) of the second normalisation step, see repeatCounter.set_renorm
-Detected = namedtuple('Detected', ['row', 'units', 'conf', 'llr', 'anchored', 'variants', 'renorm'], defaults=(None, None, None))
+# anchored_mod: None or (pattern, llr) -- the methylation call of an anchored read, see repeatCounter.set_anchored_mod
+Detected = namedtuple('Detected', ['row', 'units', 'conf', 'llr', 'anchored', 'variants', 'renorm', 'anchored_mod'], defaults=(None, None, None, None))
 
 
 class repeatCounter(object):
@@ -69,6 +70,7 @@ class repeatCounter(object):
         self.variant_refused = {}      # {target_id: message} of the variant models strq_target_set_variants refused
         self.variants = False          # set_variants
         self.renorm = None             # set_renorm: min_share, or None
+        self.anchored_mod = False      # set_anchored_mod
         self._renorm_done = set()      # classifiers whose tables are registered
 
     # -------------------------------------------------------------------------------------
@@ -155,6 +157,18 @@ class repeatCounter(object):
         """Width of a bin of the rule's grid in pA (beta of a fit is b bins)."""
         return renorm_mod.grid(self.pm.model_min, self.pm.model_max)[1]
 
+    def set_anchored_mod(self, on):
+        """on: detect and detect_batch with anchored=m also call the methylation pattern of the reads that hold one flank only
+        (strique_amd.anchored states which reads get a call and on which stretch) and report one more element per read, directly
+        behind the anchored one: None, or (pattern, llr) -- the '0' / '1' string of the units the dual model passes on the raw-signal
+        samples [begin, end) of the record ('-' when it finds no path), and with mod_llr=True the float64 array V_mod - V_base with
+        one value per character (None without it, or for a pattern without units).  records=True: Detected.anchored_mod.  A switch
+        of the counter, like set_variants: the keywords of detect and detect_batch stay those every stand-in counter of run_count
+        answers.  ValueError without a modification model; a call without anchored=m is a ValueError then.  Not with scan_batch."""
+        if on and self.pm is self.pm_mod:
+            raise ValueError("RepeatCounter: anchored_mod needs a modification model.")
+        self.anchored_mod = bool(on)
+
     def set_variants(self, on):
         """on: detect and detect_batch also run the variant pass (strq_set_variants) and report one more element per read -- see
         detect_batch.  ValueError when no target was added with alt_units.  Not with scan_batch."""
@@ -219,7 +233,9 @@ class repeatCounter(object):
         scored under an alt branch is an (m + 1)-unit profile forced onto one unit of signal, meaningful only as "very negative".
         pattern has one character per unit: '0' per base passage, '0' * m + str(b) per alt passage (m = the model's context units);
         count_v = len(pattern) + count_bias is an estimate on the scale of the tuple's count, not equal to it in general.
-        Order of the elements: (tuple[, positions][, conf][, llr][, anchored][, variants]); without any of the five the bare tuple.
+        With set_anchored_mod(True) and anchored=m: the methylation call of the read, (pattern, llr) or None, directly behind the
+        anchored element -- see set_anchored_mod.
+        Order of the elements: (tuple[, positions][, conf][, llr][, anchored][, anchored_mod][, variants]); without any of them the bare tuple.
         records=True: a list of Detected records instead (the fields that were not asked for None; `anchored` the record of every
         read, whatever its kind: (kind number, status, count, log_p, begin, end, free_samples))."""
         items = list(items)
@@ -227,10 +243,13 @@ class repeatCounter(object):
             raise ValueError("RepeatCounter: mod_llr needs a modification model.")
         if anchored is not None and not anchored > 0:
             raise ValueError("RepeatCounter: the anchored score threshold must be above 0.")
+        if self.anchored_mod and anchored is None:
+            raise ValueError("RepeatCounter: anchored_mod needs anchored=m (the calls hang on the anchored records).")
         variants = self.variants
         reads = [(self._classifier_for(t, s).target_id, r) for t, r, s in items]
         out = [None] * len(items)
-        for i, d, _, _ in self._run(reads, units=units, confidence=confidence, mod_llr=mod_llr, anchored=anchored, variants=variants, renorm=self.renorm):
+        for i, d, _, _ in self._run(reads, units=units, confidence=confidence, mod_llr=mod_llr, anchored=anchored, variants=variants, renorm=self.renorm,
+                                    anchored_mod=self.anchored_mod):
             if records:
                 out[i] = d
                 continue
@@ -238,18 +257,22 @@ class repeatCounter(object):
             if anchored is not None:
                 a = d.anchored
                 extra += ((anchored_mod.KIND_NAMES[a[0]],) + tuple(a[2:]) if a[0] in (anchored_mod.ENDS_IN_REPEAT, anchored_mod.STARTS_IN_REPEAT) else None,)
+            if self.anchored_mod:
+                extra += (d.anchored_mod,)
             if variants:
                 extra += (d.variants,)
             out[i] = (d.row,) + extra if extra else d.row
         return out
 
     @contextlib.contextmanager
-    def _switches(self, units, confidence, mod_llr, anchored=None, variants=False, renorm=None):
+    def _switches(self, units, confidence, mod_llr, anchored=None, variants=False, renorm=None, anchored_mod=False):
         """The optional passes that were asked for are on inside the block, and all of them off after it."""
         try:
             if anchored is not None:
                 self._ensure_anchored()
                 self.ctx.set_anchored(True, anchored)
+            if anchored_mod:
+                self.ctx.set_anchored_mod(True)
             # inside the try: set_mod_llr refuses a modification model the scoring pass does not cover, and the switches a
             # failed call leaves behind must not stay on for the next caller of a shared context
             if units:
@@ -268,12 +291,13 @@ class repeatCounter(object):
         finally:
             self.ctx.set_renorm(False)
             self.ctx.set_variants(False)
+            self.ctx.set_anchored_mod(False)
             self.ctx.set_anchored(False)
             self.ctx.set_mod_llr(False)
             self.ctx.set_units(False)
             self.ctx.set_confidence(False)
 
-    def _run(self, reads, units=False, confidence=False, mod_llr=False, scan=None, anchored=None, variants=False, renorm=None):
+    def _run(self, reads, units=False, confidence=False, mod_llr=False, scan=None, anchored=None, variants=False, renorm=None, anchored_mod=False):
         """reads: [(target_id, raw_signal)] through the context.  Yields (position in `reads`, Detected, winner, scores) per read, the
         fields of Detected that were not asked for being None.  scan=(candidate target ids, min_score): the target ids of the reads
         are ignored, every read is compared with every candidate (Context.scan_batch_reads); winner is its position in the candidate
@@ -287,7 +311,7 @@ class repeatCounter(object):
             if not idx:
                 continue
             arrs = [sigs[i].astype(np.int16 if want_int else np.float64, copy=False) for i in idx]
-            with self._switches(units, confidence, mod_llr, anchored, variants, renorm):
+            with self._switches(units, confidence, mod_llr, anchored, variants, renorm, anchored_mod):
                 if scan is None:
                     res = self.ctx.detect_batch_reads(arrs, [reads[i][0] for i in idx])      # one pointer per read: no host-side concatenation
                     win = sc = [None] * len(res)
@@ -314,10 +338,13 @@ class repeatCounter(object):
                 if anchored is not None:
                     an = [(int(a['kind']), int(a['status']), int(a['count']), float(a['log_p']), int(a['begin']), int(a['end']), int(a['free_samples']))
                           for a in self.ctx.batch_fetch_anchored()]
-            for i, r, m, u, cf, v, w, s, a, vr, rnr in zip(idx, res, mods, pos, conf, vs, win, sc, an, var, rn):
+                am = [None] * len(res)
+                if anchored_mod:
+                    am = [None if x is None else (x[0], None if x[1] is None else x[1][:, 1] - x[1][:, 0]) for x in self.ctx.batch_fetch_anchored_mod()]
+            for i, r, m, u, cf, v, w, s, a, vr, rnr, amr in zip(idx, res, mods, pos, conf, vs, win, sc, an, var, rn, am):
                 n = int(r['count']); p = float(r['log_p']) if n or r['log_p'] != 0 else 0
                 row = (n, float(r['score_prefix']), float(r['score_suffix']), p, int(r['offset']), int(r['ticks']), m)
-                yield i, Detected(row, u, cf, None if v is None else v[:, 1] - v[:, 0], a, vr, rnr), w, s
+                yield i, Detected(row, u, cf, None if v is None else v[:, 1] - v[:, 0], a, vr, rnr, amr), w, s
 
     def candidates(self, targets=None):
         """[(target_name, strand)] of a scan: every target added (or the named ones), in add_target order, '+' before '-'."""

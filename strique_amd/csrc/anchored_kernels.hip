@@ -46,6 +46,43 @@ __global__ void __launch_bounds__(128) anchored_task_kernel(AnchoredTaskArgs a)
     a.vit[k] = vt;
 }
 
+// One thread per item.  The stretch is read off the marks exactly as anchored_record (detect_plan.h) reads it for the record, and
+// checked once more against the window, the read and what the host reserved: a task never leaves the read's samples or its buffers.
+__global__ void __launch_bounds__(128) anchored_mod_task_kernel(AnchoredModTaskArgs a)
+{
+    const int k = blockIdx.x * 128 + threadIdx.x;
+    if (k >= a.n_items) return;
+    const AnchoredModItem it = a.item[k];
+    ModTask m = {};
+    VitTask vt = {};
+    m.out = it.out; m.is_f64 = a.is_f64;
+    m.clip_lo = a.clip_lo; m.clip_hi = a.clip_hi; m.mod_lo = it.mod_lo; m.mod_hi = it.mod_hi;
+    vt.model = it.model; vt.sig = it.out; vt.src_kind = VIT_SRC_F64; vt.bp = it.bp;
+    if (it.read >= 0 && it.read < a.n_reads && it.res >= 0 && it.res < a.n_res) {
+        const AnchoredClass c = a.cls[it.read];
+        const ReadCond rc = a.rc[it.read];
+        const VitResult v = a.res[it.res];
+        const bool open = (c.kind == ANCH_ENDS || c.kind == ANCH_STARTS) && c.begin >= 0 && c.begin < c.end && c.end <= (int64_t)rc.n;
+        const int64_t W = c.end - c.begin;
+        const int64_t enter = v.dbg[0], leave = v.dbg[1] ? (int64_t)v.dbg[1] : W + 1;
+        if (open && v.status == 0 && enter >= 1 && leave > enter && leave <= W + 1 && leave - enter <= it.cap) {
+            const int64_t begin = c.begin + enter - 1, T = leave - enter;
+            m.raw = static_cast<const char*>(a.raw) + (size_t)(rc.off + begin) * (a.is_f64 ? 8 : 2);
+            m.T = T; vt.T = T;
+            m.c1 = rc.r_c1; m.h1 = rc.r_h1; m.h2 = rc.h2; m.c2 = rc.c2;
+        }
+    }
+    a.mod[k] = m;
+    if (it.slot >= 0 && it.slot < a.n_items) a.vit[it.slot] = vt;
+}
+
+int launch_anchored_mod_tasks(hipStream_t s, const AnchoredModTaskArgs& a)
+{
+    if (a.n_items <= 0) return 0;
+    hipLaunchKernelGGL(anchored_mod_task_kernel, dim3((a.n_items + 127) / 128), dim3(128), 0, s, a);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
 int launch_anchored_classify(hipStream_t s, const AnchoredClassifyArgs& a)
 {
     if (a.n_reads <= 0) return 0;

@@ -34,7 +34,8 @@ struct Carve {
 // Anchored counting (strq_set_anchored) is the fourth: it comes with its score threshold.
 // The variant pass (strq_set_variants) is the fifth.
 // Renorm (strq_set_renorm) is the sixth, in front of the alignments instead of behind the decode: it comes with its share threshold.
-struct Extras { bool units = false, conf = false, llr = false, anch = false, var = false; double anch_min = 0.0; bool renorm = false; double renorm_min = 0.0; };
+// Methylation calls of anchored reads (strq_set_anchored_mod) are the seventh: behind the anchored decode, which they need.
+struct Extras { bool units = false, conf = false, llr = false, anch = false, var = false; double anch_min = 0.0; bool renorm = false; double renorm_min = 0.0; bool amod = false; };
 
 // What the variant pass leaves per read: the passages of its variant-model decode (strq_batch_fetch_variants)
 struct VariantRow {
@@ -53,6 +54,10 @@ struct ReadRows {
     std::vector<uint8_t> conf_dec;
     std::vector<std::vector<double>> llr;         // (V_base, V_mod) per repeat unit (strq_batch_fetch_mod_llr); empty: none
     std::vector<strq_anchored> anch;              // kind and decode of a read that holds one flank (strq_batch_fetch_anchored); zeros: kind 0
+    // methylation calls of anchored reads: empty until a run call with the switch on sizes them (size_amod), like `renorm`
+    std::vector<uint8_t> amod_called;             // 1: the read has an anchored methylation call (strq_batch_fetch_anchored_mod)
+    std::vector<std::string> amod;                // ... its pattern ('-': the dual model found no path)
+    std::vector<std::vector<double>> amod_llr;    // ... (V_base, V_mod) per character of it, with strq_set_mod_llr on; empty: none
     std::vector<VariantRow> var;                  // passages of the variant model (strq_batch_fetch_variants); decoded = 0: none
     std::vector<strq_renorm> renorm;              // fits of the second normalisation step (strq_batch_fetch_renorm); zeros: not fitted.  Empty
                                                   // until a run call with the switch on sizes it (size_renorm)
@@ -64,10 +69,16 @@ struct ReadRows {
         conf.assign(3 * m, NAN); conf_dec.assign(m, 0);
         llr.assign(m, std::vector<double>());
         anch.assign(m, strq_anchored());
+        amod_called.clear(); amod.clear(); amod_llr.clear();
         var.assign(m, VariantRow());
         renorm.clear();
     }
     void size_renorm() { if (renorm.size() != results.size()) renorm.assign(results.size(), strq_renorm()); }
+    void size_amod()
+    {
+        if (amod_called.size() == results.size()) return;
+        amod_called.assign(results.size(), 0); amod.assign(results.size(), std::string()); amod_llr.assign(results.size(), std::vector<double>());
+    }
     void clear_read(int64_t read)
     {
         const size_t r = (size_t)read;
@@ -77,6 +88,7 @@ struct ReadRows {
         conf[3 * r] = conf[3 * r + 1] = conf[3 * r + 2] = NAN; conf_dec[r] = 0;
         llr[r].clear();
         anch[r] = strq_anchored();
+        if (r < amod_called.size()) { amod_called[r] = 0; amod[r].clear(); amod_llr[r].clear(); }
         var[r] = VariantRow();
         if (r < renorm.size()) renorm[r] = strq_renorm();
     }

@@ -124,6 +124,8 @@ struct DetectState {
     float conf_ms = 0; double conf_windows = 0, conf_nopath = 0, conf_expo = 0;      // strq_last_confidence: the last run call's forward pass
     DevBuf anch_ws, anch_task;           // anchored pass (run_anchored_pass): geometry, conditioning rows and kinds of a sub-batch; tasks, results, their reads and models
     float anch_ms = 0; double anch_kinds[4] = {}, anch_launches = 0, anch_g2 = 0, anch_lane = 0;      // strq_last_anchored: the last run call's anchored pass
+    hipEvent_t amod_ev[2] = {};          // methylation calls of anchored reads (run_anchored_mod): their own bracket, inside the anchored pass
+    float amod_ms = 0; double amod_reads = 0, amod_units = 0, amod_launches = 0;      // strq_last_anchored_mod: the last run call's calls
     // renorm (run_renorm_part): the tables of the targets, the grid and the shares, the histograms and the per-read table rows of a sub-batch
     std::vector<std::unique_ptr<DevBuf>> rn_tables;
     RenormGrid rn_grid = {}; bool rn_have_grid = false;
@@ -232,6 +234,7 @@ void detect_state_free(strq_ctx* c)
     if (d->vit_stream) (void)hipStreamDestroy(d->vit_stream);
     for (hipEvent_t e : d->ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : d->rn_ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : d->amod_ev) if (e) (void)hipEventDestroy(e);
     if (d->copy_stream) (void)hipStreamDestroy(d->copy_stream);
     for (hipEvent_t e : d->stage_ev) if (e) (void)hipEventDestroy(e);
     delete d;          // its buffers, device and pinned, go with it
@@ -260,7 +263,7 @@ static int launch_viterbi_group(strq_ctx* c, hipStream_t st, const VitGroup& g, 
 // read-back of the modification pass: the lengths first, then the strings gathered into a dense pool (the sparse buffer has one byte per
 // time step: ~180 MB per 4096 reads of 50 kb, 25 ms through pageable memory, for ~4 MB of strings)
 static int read_mod_patterns(strq_ctx* c, DetectState* d, int64_t r0, const std::vector<int>& who, const std::vector<int>& slot2, const std::vector<int64_t>& len,
-                             const std::vector<size_t>& p2_off, const int64_t* d_plen, const char* d_chars)
+                             const std::vector<size_t>& p2_off, const int64_t* d_plen, const char* d_chars, std::vector<std::string>& dst)
 {
     hipStream_t st = c->stream;
     const int nm = (int)who.size();
@@ -279,7 +282,7 @@ static int read_mod_patterns(strq_ctx* c, DetectState* d, int64_t r0, const std:
     std::vector<char> chars(dense + 1);
     if (dense) STRQ_HIP(c, hipMemcpyAsync(chars.data(), d_dense, dense, hipMemcpyDeviceToHost, st));
     STRQ_HIP(c, hipStreamSynchronize(st));
-    for (int k = 0; k < nm; ++k) d->batch.mod[r0 + who[k]] = std::string(chars.data() + gt[k].dst, (size_t)gt[k].len);
+    for (int k = 0; k < nm; ++k) dst[(size_t)(r0 + who[k])] = std::string(chars.data() + gt[k].dst, (size_t)gt[k].len);
     return STRQ_OK;
 }
 
@@ -334,6 +337,8 @@ struct LlrPassIn {
     const std::vector<int>* who; const std::vector<int>* slot2; const std::vector<int64_t>* len;
     const std::vector<size_t>* sig_off; const std::vector<size_t>* bp2_off; const std::vector<int32_t*>* paths;
     bool use_hub; VitResult* results;
+    // whose patterns are scored and where the scores go: the rows' (Batch::mod / llr), or the anchored calls' (Batch::amod / amod_llr)
+    const std::vector<std::string>* pattern; std::vector<std::vector<double>>* scores; bool anchored;
 };
 
 // Per-unit scores of the reads of one sub-batch (strq_set_mod_llr; mod_llr_kernels.h): behind the pattern read-back of run_mod_pass, on
@@ -347,7 +352,7 @@ static int run_llr_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, cons
     const int nm = (int)who.size();
     std::vector<int64_t> n_units((size_t)nm), unit_off((size_t)nm + 1, 0);
     for (int k = 0; k < nm; ++k) {
-        const std::string& pat = B.mod[(size_t)(r0 + who[k])];
+        const std::string& pat = (*in.pattern)[(size_t)(r0 + who[k])];
         n_units[(size_t)k] = pat == "-" ? 0 : (int64_t)pat.size();
         unit_off[(size_t)k + 1] = unit_off[(size_t)k] + n_units[(size_t)k];
     }
@@ -406,10 +411,11 @@ static int run_llr_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, cons
     std::vector<double> out((size_t)U * 2); std::vector<int32_t> bad((size_t)nb);
     STRQ_HIP(c, hipMemcpyAsync(out.data(), d_out, (size_t)U * 16, hipMemcpyDeviceToHost, st));
     STRQ_HIP(c, hipMemcpyAsync(bad.data(), d_bad, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
-    if (const int rc = pass_stop(c, d, d->llr_ms)) return rc;
+    if (const int rc = pass_stop(c, d, in.anchored ? d->amod_ms : d->llr_ms)) return rc;
     for (int32_t b : bad) if (b) { c->err = "mod-llr: the unit bounds of a read disagree with its pattern"; return STRQ_ERR_DEVICE; }
     for (int k = 0; k < nm; ++k)
-        if (n_units[(size_t)k]) B.llr[(size_t)(r0 + who[k])].assign(out.begin() + (ptrdiff_t)(2 * unit_off[(size_t)k]), out.begin() + (ptrdiff_t)(2 * unit_off[(size_t)k + 1]));
+        if (n_units[(size_t)k]) (*in.scores)[(size_t)(r0 + who[k])].assign(out.begin() + (ptrdiff_t)(2 * unit_off[(size_t)k]), out.begin() + (ptrdiff_t)(2 * unit_off[(size_t)k + 1]));
+    if (in.anchored) { d->amod_launches += 1 + (double)launches.size(); return STRQ_OK; }
     d->llr_units += (double)U; d->llr_reads += nb; d->llr_launches += 1 + (double)launches.size();
     return STRQ_OK;
 }
@@ -569,6 +575,183 @@ static int run_variant_tail(strq_ctx* c, DetectState* d, DetectState::Slot& sl, 
     return STRQ_OK;
 }
 
+// Steps 1 to 3 of a dual-model pass for a list of stretches, and what they leave for the steps behind them.  A stretch is `len`
+// raw samples of read `who` of the sub-batch from sample `raw_first` of that read: the samples a MARK decode put into the repeat
+// section (detect step 13, STRique.py:608, hands exactly those to repeatModHMM.mod_repeats, STRique.py:492-500,605-609).  The
+// spanning caller (run_mod_pass) knows its stretches on the host; the anchored caller (run_anchored_mod) may know only the windows
+// they lie in: then `len` is that bound, it sizes every buffer, and anchored_mod_task_kernel writes the tasks from the device copies
+// of the records (`dev`) -- nothing waits for the host between the anchored decode and the pattern read-back.
+struct AnchoredModSrc { const AnchoredClass* cls; const ReadCond* rc; const VitResult* res; int n_res; std::vector<int32_t> res_of; };
+struct DualRun {
+    std::vector<int> who; std::vector<int64_t> raw_first, len;
+    std::vector<size_t> sig_off, bp2_off, p2_off; std::vector<int> slot2; std::vector<int32_t*> tp2;
+    bool use_hub = false; double launches = 0;
+    VitTask* d_tb = nullptr; VitResult* d_tr = nullptr; int32_t** d_tp = nullptr; PatTask* d_pt = nullptr;
+    char* d_chars = nullptr; int64_t* d_plen = nullptr; HubTask* d_ht = nullptr;
+};
+// hub records (one 8-byte record per time step, read back with one hop per repeat unit) when every model of the list has the hub
+// structure; back-pointers + traceback otherwise
+static int dual_route(strq_ctx* c, DetectState* d, int64_t r0, Dual which, const DualRun& R, std::vector<GroupItem>& items, bool& use_hub)
+{
+    const int nm = (int)R.who.size();
+    items.resize((size_t)nm);
+    use_hub = !strq::opt("STRQ_MOD_BACKPOINTERS");
+    for (int k = 0; k < nm; ++k) {
+        HostModel* hm = dual_model(c, d, r0 + R.who[k], which);
+        const int shape = vit_shape_of(hm->h);
+        if (shape < 0) { c->err = "modification model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
+        items[k] = {0, shape, hm->h.n_cells};
+        if (hm->h.rec_state < 0 || !vit_mode_ok(shape, VIT_HUB) || R.len[k] >= ((int64_t)1 << 31)) use_hub = false;
+    }
+    return STRQ_OK;
+}
+static int dual_decode(strq_ctx* c, DetectState* d, DetectState::Slot& sl, Dual which, DualRun& R, const AnchoredModSrc* dev = nullptr)
+{
+    Batch& B = d->batch;
+    hipStream_t st = c->stream;
+    const int64_t r0 = sl.r0;
+    const ReadCond* rc = sl.host().rc;
+    const int esz = B.dtype == 0 ? 2 : 8;
+    const int64_t s0 = B.off[r0];
+    const std::vector<int>& who = R.who; const std::vector<int64_t>& len = R.len;
+    const int nm = (int)who.size();
+    // 1. + 2. the samples decoded into repeat states: one contiguous stretch, renormalised from the raw signal and clipped
+    size_t sig_tot = 0; R.sig_off.resize(nm);
+    for (int k = 0; k < nm; ++k) { R.sig_off[k] = sig_tot; sig_tot += (size_t)len[k]; }
+    const std::vector<size_t>& sig_off = R.sig_off;
+    std::vector<GroupItem> items;
+    if (const int rrc = dual_route(c, d, r0, which, R, items, R.use_hub)) return rrc;
+    const bool use_hub = R.use_hub;
+    if (dev && !use_hub) { c->err = "anchored-mod: tasks from the device need the hub route"; return STRQ_ERR_DEVICE; }
+    Carve lay;
+    const size_t o_tb = lay.add<VitTask>((size_t)nm), o_tr = lay.add<VitResult>((size_t)nm), o_tp = lay.add<int32_t*>((size_t)nm),
+                 o_mt = lay.add<ModTask>((size_t)nm), o_pt = lay.add<PatTask>((size_t)nm), o_it = lay.add<AnchoredModItem>(dev ? (size_t)nm : 0);
+    STRQ_HIP(c, d->modtask.reserve(lay.total() + 256));
+    void* ws = d->modtask.p;
+    VitTask* d_tb = Carve::at<VitTask>(ws, o_tb); VitResult* d_tr = Carve::at<VitResult>(ws, o_tr); int32_t** d_tp = Carve::at<int32_t*>(ws, o_tp);
+    ModTask* d_mt = Carve::at<ModTask>(ws, o_mt); PatTask* d_pt = Carve::at<PatTask>(ws, o_pt);
+    STRQ_HIP(c, d->modsig.reserve(sig_tot * 8 + 64));
+    STRQ_HIP(c, d->modlen.reserve((size_t)nm * 16 + 64));
+    const Grouping G = group_items(items);
+    R.slot2 = G.pos;          // task position of read k
+    const std::vector<int>& slot2 = R.slot2;
+    std::vector<VitTask> vt2(nm); R.tp2.assign(nm, nullptr);
+    size_t bp2 = 0, p2 = 0; R.bp2_off.resize(nm); R.p2_off.resize(nm);
+    for (int k = 0; k < nm; ++k) {
+        // back-pointers: uint16 per (time step, state); hub records: 8 bytes per time step (in uint16 units: 4)
+        R.bp2_off[k] = bp2; bp2 += use_hub ? (size_t)(len[k] + 1) * 4 : (size_t)(len[k] + 1) * dual_model(c, d, r0 + who[k], which)->h.n_states;
+        R.p2_off[k] = p2; p2 += (size_t)len[k] + 1;
+    }
+    STRQ_HIP(c, d->bp.reserve(bp2 * 2 + 64));
+    // traced state paths (back-pointer route only), the pattern strings, the tasks of the hub route
+    Carve pat;
+    const size_t o_path2 = pat.add<int32_t>(use_hub ? 0 : p2), o_chars = pat.add<char>(p2), o_ht = pat.add<HubTask>(use_hub ? (size_t)nm : 0);
+    STRQ_HIP(c, d->pattern.reserve(pat.total() + 64));
+    int32_t* d_path2 = Carve::at<int32_t>(d->pattern.p, o_path2);
+    R.d_chars = Carve::at<char>(d->pattern.p, o_chars); R.d_ht = Carve::at<HubTask>(d->pattern.p, o_ht);
+    R.d_tb = d_tb; R.d_tr = d_tr; R.d_tp = d_tp; R.d_pt = d_pt;
+    std::vector<ModTask> mt(dev ? 0 : nm);
+    if (dev) {
+        // the tasks from the records on the device (anchored_mod_task_kernel): both the ModTask and the HUB VitTask of every read
+        std::vector<AnchoredModItem> it((size_t)nm);
+        for (int k = 0; k < nm; ++k) {
+            const Target& t = target_of(d, r0 + who[k]);
+            AnchoredModItem& a = it[(size_t)k]; std::memset(&a, 0, sizeof(a));
+            a.read = who[k]; a.res = dev->res_of[(size_t)k]; a.slot = slot2[k];
+            a.model = dual_model(c, d, r0 + who[k], which)->dev;
+            a.out = d->modsig.as<double>() + sig_off[k]; a.bp = d->bp.as<uint16_t>() + R.bp2_off[k];
+            a.mod_lo = t.mod_min; a.mod_hi = t.mod_max; a.cap = len[k];
+        }
+        AnchoredModItem* d_it = Carve::at<AnchoredModItem>(ws, o_it);
+        STRQ_HIP(c, hipMemcpyAsync(d_it, it.data(), (size_t)nm * sizeof(AnchoredModItem), hipMemcpyHostToDevice, st));
+        AnchoredModTaskArgs ta;
+        ta.cls = dev->cls; ta.rc = dev->rc; ta.res = dev->res; ta.item = d_it;
+        ta.raw = d->batch.raw.as<char>() + (size_t)s0 * esz; ta.is_f64 = B.dtype;
+        ta.clip_lo = d->ps.clip_lo; ta.clip_hi = d->ps.clip_hi;
+        ta.mod = d_mt; ta.vit = d_tb; ta.n_items = nm; ta.n_reads = sl.nr; ta.n_res = dev->n_res;
+        if (launch_anchored_mod_tasks(st, ta)) { c->err = "anchored-mod: task launch failed"; return STRQ_ERR_DEVICE; }
+        R.launches += 1;
+    } else {
+        for (int k = 0; k < nm; ++k) {
+            const int i = who[k]; const Target& t = target_of(d, r0 + i);
+            ModTask& m = mt[k];
+            m.path = nullptr; m.tag = nullptr;          // contiguous stretch: every sample is kept
+            m.raw = d->batch.raw.as<char>() + (size_t)(s0 + rc[i].off + R.raw_first[k]) * esz;
+            m.out = d->modsig.as<double>() + sig_off[k]; m.T = len[k]; m.is_f64 = B.dtype; m.pad_ = 0;
+            m.c1 = rc[i].r_c1; m.h1 = rc[i].r_h1; m.h2 = rc[i].h2; m.c2 = rc[i].c2;
+            m.clip_lo = d->ps.clip_lo; m.clip_hi = d->ps.clip_hi;
+            m.mod_lo = which == DUAL_MOD ? t.mod_min : t.var_lo; m.mod_hi = which == DUAL_MOD ? t.mod_max : t.var_hi;
+        }
+        STRQ_HIP(c, hipMemcpyAsync(d_mt, mt.data(), (size_t)nm * sizeof(ModTask), hipMemcpyHostToDevice, st));
+    }
+    int64_t* d_len = d->modlen.as<int64_t>();
+    R.d_plen = d_len;
+    if (launch_mod_compact(st, d_mt, nm, d_len)) { c->err = "compaction launch failed"; return STRQ_ERR_DEVICE; }
+    R.launches += 1;
+    // 3. Viterbi on the dual model
+    if (const int qrc = reset_queue_heads(c, st)) return qrc;
+    for (int k = 0; k < nm; ++k) {
+        R.tp2[slot2[k]] = d_path2 + R.p2_off[k];
+        if (dev) continue;
+        VitTask& v = vt2[slot2[k]]; v = VitTask();
+        v.model = dual_model(c, d, r0 + who[k], which)->dev; v.sig = mt[k].out; v.T = len[k]; v.src_kind = VIT_SRC_F64;
+        v.bp = d->bp.as<uint16_t>() + R.bp2_off[k];
+    }
+    int qi = 0;
+    for (const VitGroup& vg : G.groups) {
+        if (!dev) STRQ_HIP(c, hipMemcpyAsync(d_tb + vg.first, vt2.data() + vg.first, (size_t)vg.count * sizeof(VitTask), hipMemcpyHostToDevice, st));
+        if (const int src = sort_viterbi_group(c, st, vg, d_tb, sl.order.as<int>())) return src;
+        if (const int lrc = launch_viterbi_group(c, st, vg, d_tb, d_tr, sl.order.as<int>(), c->queue.as<int>() + qi++, use_hub ? VIT_HUB : VIT_BACKPTR)) return lrc;
+        R.launches += group_order(sl.order.as<int>(), vg) ? 2 : 1;
+    }
+    return STRQ_OK;
+}
+
+// Step 4 behind dual_decode for a modification model: the pattern strings from the hub records, or from traced paths, into `dst`
+static int dual_patterns(strq_ctx* c, DetectState* d, DetectState::Slot& sl, Dual which, DualRun& R, std::vector<std::string>& dst)
+{
+    hipStream_t st = c->stream;
+    const int64_t r0 = sl.r0;
+    const int nm = (int)R.who.size();
+    const std::vector<int>& slot2 = R.slot2;
+    if (R.use_hub) {
+        // 4. pattern strings from the hub records
+        std::vector<HubTask> ht(nm);
+        for (int k = 0; k < nm; ++k) {
+            const int sl = slot2[k];
+            ht[sl].rec = reinterpret_cast<const uint64_t*>(d->bp.as<uint16_t>() + R.bp2_off[k]);
+            ht[sl].result = R.d_tr + sl; ht[sl].out = R.d_chars + R.p2_off[k];
+        }
+        STRQ_HIP(c, hipMemcpyAsync(R.d_ht, ht.data(), (size_t)nm * sizeof(HubTask), hipMemcpyHostToDevice, st));
+        if (launch_mod_hub_pattern(st, R.d_ht, nm, R.d_plen)) { c->err = "pattern launch failed"; return STRQ_ERR_DEVICE; }
+        R.launches += 1;
+    } else {
+        STRQ_HIP(c, hipMemcpyAsync(R.d_tp, R.tp2.data(), (size_t)nm * 8, hipMemcpyHostToDevice, st));
+        if (launch_vit_traceback(st, R.d_tb, R.d_tr, R.d_tp, nm)) { c->err = "traceback launch failed"; return STRQ_ERR_DEVICE; }
+        // 4. pattern strings
+        std::vector<PatTask> pt(nm);
+        for (int k = 0; k < nm; ++k) {
+            const int sl = slot2[k];
+            pt[sl].path = R.tp2[sl]; pt[sl].tag = dual_model(c, d, r0 + R.who[k], which)->h.state_tag; pt[sl].out = R.d_chars + R.p2_off[k]; pt[sl].T = R.len[k];
+            pt[sl].status = &R.d_tr[sl].status;
+        }
+        STRQ_HIP(c, hipMemcpyAsync(R.d_pt, pt.data(), (size_t)nm * sizeof(PatTask), hipMemcpyHostToDevice, st));
+        if (launch_mod_pattern(st, R.d_pt, nm, R.d_plen)) { c->err = "pattern launch failed"; return STRQ_ERR_DEVICE; }
+        R.launches += 2;
+    }
+    R.launches += 1;          // (the gather of read_mod_patterns)
+    return read_mod_patterns(c, d, r0, R.who, slot2, R.len, R.p2_off, R.d_plen, R.d_chars, dst);
+}
+
+// what the steps behind the decode take from it
+static LlrPassIn dual_tail_in(const DualRun& R)
+{
+    LlrPassIn li = {};
+    li.who = &R.who; li.slot2 = &R.slot2; li.len = &R.len; li.sig_off = &R.sig_off; li.bp2_off = &R.bp2_off; li.paths = &R.tp2;
+    li.use_hub = R.use_hub; li.results = R.d_tr;
+    return li;
+}
+
 // The pass of one of the targets' dual models (`which`) for the reads of one sub-batch whose target has that model: the modification
 // pass (patterns, and the per-unit scores behind them), or the variant pass (strq_set_variants: passages and their scores).
 // The flanked-model Viterbi ran in MARK mode (viterbi_kernels.hip): its result carries the first and
@@ -576,14 +759,12 @@ static int run_variant_tail(strq_ctx* c, DetectState* d, DetectState::Slot& sl, 
 static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, Dual which = DUAL_MOD)
 {
     Batch& B = d->batch;
-    hipStream_t st = c->stream;
     const int64_t r0 = sl.r0; const int nr = sl.nr;
     const DetectState::Slot::Pinned h = sl.host();
-    const ReadCond* rc = h.rc; const ReadGeom* geom = h.geom; const VitResult* vres = h.vres;
+    const ReadGeom* geom = h.geom; const VitResult* vres = h.vres;
     const std::vector<int32_t>& vit_slot = sl.vit_slot;
-    const int esz = B.dtype == 0 ? 2 : 8;
-    const int64_t s0 = B.off[r0];
-    std::vector<int> who;                      // reads that reach the modification model
+    DualRun R;
+    std::vector<int>& who = R.who;             // reads that reach the modification model
     for (int i = 0; i < nr; ++i) {
         if (dual_id(target_of(d, r0 + i), which) < 0 || !geom[i].gate) continue;
         const VitResult& v = vres[vit_slot[i]];
@@ -594,123 +775,32 @@ static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, Dual
     const int nm = (int)who.size();
     if (!nm) return STRQ_OK;
     if (which == DUAL_VAR) { if (const int rc = pass_start(c, d)) return rc; }          // one bracket around the whole variant pass
-    // 1. + 2. the samples decoded into repeat states: one contiguous stretch [enter, leave) of the window,
-    //         renormalised from the raw signal and clipped
-    std::vector<int64_t> len(nm), first(nm);
-    size_t sig_tot = 0; std::vector<size_t> sig_off(nm);
+    // the samples decoded into repeat states: one contiguous stretch [enter, leave) of the window
+    std::vector<int64_t> first(nm);
+    R.len.resize(nm); R.raw_first.resize(nm);
     for (int k = 0; k < nm; ++k) {
         const int i = who[k];
         const VitResult& v = vres[vit_slot[i]];
         const int64_t T = geom[i].suffix_end - geom[i].prefix_begin;
         const int64_t enter = v.dbg[0], leave = v.dbg[1];
         first[k] = enter ? enter - 1 : 0;
-        len[k] = enter ? (leave ? leave - 1 : T) - (enter - 1) : 0;
-        sig_off[k] = sig_tot; sig_tot += (size_t)len[k];
+        R.len[k] = enter ? (leave ? leave - 1 : T) - (enter - 1) : 0;
+        R.raw_first[k] = geom[i].prefix_begin + first[k];
     }
-    Carve lay;
-    const size_t o_tb = lay.add<VitTask>((size_t)nm), o_tr = lay.add<VitResult>((size_t)nm), o_tp = lay.add<int32_t*>((size_t)nm),
-                 o_mt = lay.add<ModTask>((size_t)nm), o_pt = lay.add<PatTask>((size_t)nm);
-    STRQ_HIP(c, d->modtask.reserve(lay.total() + 256));
-    void* ws = d->modtask.p;
-    VitTask* d_tb = Carve::at<VitTask>(ws, o_tb); VitResult* d_tr = Carve::at<VitResult>(ws, o_tr); int32_t** d_tp = Carve::at<int32_t*>(ws, o_tp);
-    ModTask* d_mt = Carve::at<ModTask>(ws, o_mt); PatTask* d_pt = Carve::at<PatTask>(ws, o_pt);
-    STRQ_HIP(c, d->modsig.reserve(sig_tot * 8 + 64));
-    STRQ_HIP(c, d->modlen.reserve((size_t)nm * 16 + 64));
-    std::vector<ModTask> mt(nm);
-    for (int k = 0; k < nm; ++k) {
-        const int i = who[k]; const Target& t = target_of(d, r0 + i);
-        ModTask& m = mt[k];
-        m.path = nullptr; m.tag = nullptr;          // contiguous stretch: every sample is kept
-        m.raw = d->batch.raw.as<char>() + (size_t)(s0 + rc[i].off + geom[i].prefix_begin + first[k]) * esz;
-        m.out = d->modsig.as<double>() + sig_off[k]; m.T = len[k]; m.is_f64 = B.dtype; m.pad_ = 0;
-        m.c1 = rc[i].r_c1; m.h1 = rc[i].r_h1; m.h2 = rc[i].h2; m.c2 = rc[i].c2;
-        m.clip_lo = d->ps.clip_lo; m.clip_hi = d->ps.clip_hi;
-        m.mod_lo = which == DUAL_MOD ? t.mod_min : t.var_lo; m.mod_hi = which == DUAL_MOD ? t.mod_max : t.var_hi;
-    }
-    int64_t* d_len = d->modlen.as<int64_t>();
-    STRQ_HIP(c, hipMemcpyAsync(d_mt, mt.data(), (size_t)nm * sizeof(ModTask), hipMemcpyHostToDevice, st));
-    if (launch_mod_compact(st, d_mt, nm, d_len)) { c->err = "compaction launch failed"; return STRQ_ERR_DEVICE; }
-    // 3. Viterbi on the modification model.  Hub records (one 8-byte record per time step, read back with one
-    //    hop per repeat unit) when the model has the hub structure; back-pointers + traceback otherwise.
-    std::vector<GroupItem> items(nm);
-    bool use_hub = !strq::opt("STRQ_MOD_BACKPOINTERS");
-    for (int k = 0; k < nm; ++k) {
-        HostModel* hm = dual_model(c, d, r0 + who[k], which);
-        const int shape = vit_shape_of(hm->h);
-        if (shape < 0) { c->err = "modification model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
-        items[k] = {0, shape, hm->h.n_cells};
-        if (hm->h.rec_state < 0 || !vit_mode_ok(shape, VIT_HUB) || len[k] >= ((int64_t)1 << 31)) use_hub = false;
-    }
-    const Grouping G = group_items(items);
-    const std::vector<int>& slot2 = G.pos;          // task position of read k
-    std::vector<VitTask> vt2(nm); std::vector<int32_t*> tp2(nm);
-    size_t bp2 = 0, p2 = 0; std::vector<size_t> bp2_off(nm), p2_off(nm);
-    for (int k = 0; k < nm; ++k) {
-        // back-pointers: uint16 per (time step, state); hub records: 8 bytes per time step (in uint16 units: 4)
-        bp2_off[k] = bp2; bp2 += use_hub ? (size_t)(len[k] + 1) * 4 : (size_t)(len[k] + 1) * dual_model(c, d, r0 + who[k], which)->h.n_states;
-        p2_off[k] = p2; p2 += (size_t)len[k] + 1;
-    }
-    STRQ_HIP(c, d->bp.reserve(bp2 * 2 + 64));
-    // traced state paths (back-pointer route only), the pattern strings, the tasks of the hub route
-    Carve pat;
-    const size_t o_path2 = pat.add<int32_t>(use_hub ? 0 : p2), o_chars = pat.add<char>(p2), o_ht = pat.add<HubTask>(use_hub ? (size_t)nm : 0);
-    STRQ_HIP(c, d->pattern.reserve(pat.total() + 64));
-    int32_t* d_path2 = Carve::at<int32_t>(d->pattern.p, o_path2); char* d_chars = Carve::at<char>(d->pattern.p, o_chars);
-    if (const int qrc = reset_queue_heads(c, st)) return qrc;
-    for (int k = 0; k < nm; ++k) {
-        VitTask& v = vt2[slot2[k]]; v = VitTask();
-        v.model = dual_model(c, d, r0 + who[k], which)->dev; v.sig = mt[k].out; v.T = len[k]; v.src_kind = VIT_SRC_F64;
-        v.bp = d->bp.as<uint16_t>() + bp2_off[k];
-        tp2[slot2[k]] = d_path2 + p2_off[k];
-    }
-    int qi = 0;
-    for (const VitGroup& vg : G.groups) {
-        STRQ_HIP(c, hipMemcpyAsync(d_tb + vg.first, vt2.data() + vg.first, (size_t)vg.count * sizeof(VitTask), hipMemcpyHostToDevice, st));
-        if (const int src = sort_viterbi_group(c, st, vg, d_tb, sl.order.as<int>())) return src;
-        if (const int lrc = launch_viterbi_group(c, st, vg, d_tb, d_tr, sl.order.as<int>(), c->queue.as<int>() + qi++, use_hub ? VIT_HUB : VIT_BACKPTR)) return lrc;
-    }
+    if (const int drc = dual_decode(c, d, sl, which, R)) return drc;
     if (which == DUAL_VAR) {
         // 4. + 5. passages and their scores (the back-pointer route traces the paths first)
-        if (!use_hub) {
-            STRQ_HIP(c, hipMemcpyAsync(d_tp, tp2.data(), (size_t)nm * 8, hipMemcpyHostToDevice, st));
-            if (launch_vit_traceback(st, d_tb, d_tr, d_tp, nm)) { c->err = "traceback launch failed"; return STRQ_ERR_DEVICE; }
+        if (!R.use_hub) {
+            STRQ_HIP(c, hipMemcpyAsync(R.d_tp, R.tp2.data(), (size_t)nm * 8, hipMemcpyHostToDevice, c->stream));
+            if (launch_vit_traceback(c->stream, R.d_tb, R.d_tr, R.d_tp, nm)) { c->err = "traceback launch failed"; return STRQ_ERR_DEVICE; }
         }
-        LlrPassIn vi;
-        vi.who = &who; vi.slot2 = &slot2; vi.len = &len; vi.sig_off = &sig_off; vi.bp2_off = &bp2_off; vi.paths = &tp2;
-        vi.use_hub = use_hub; vi.results = d_tr;
-        return run_variant_tail(c, d, sl, vi, first);
+        return run_variant_tail(c, d, sl, dual_tail_in(R), first);
     }
-    int64_t* d_plen = d_len;
-    if (use_hub) {
-        // 4. pattern strings from the hub records
-        std::vector<HubTask> ht(nm);
-        for (int k = 0; k < nm; ++k) {
-            const int sl = slot2[k];
-            ht[sl].rec = reinterpret_cast<const uint64_t*>(d->bp.as<uint16_t>() + bp2_off[k]);
-            ht[sl].result = d_tr + sl; ht[sl].out = d_chars + p2_off[k];
-        }
-        HubTask* d_ht = Carve::at<HubTask>(d->pattern.p, o_ht);
-        STRQ_HIP(c, hipMemcpyAsync(d_ht, ht.data(), (size_t)nm * sizeof(HubTask), hipMemcpyHostToDevice, st));
-        if (launch_mod_hub_pattern(st, d_ht, nm, d_plen)) { c->err = "pattern launch failed"; return STRQ_ERR_DEVICE; }
-    } else {
-        STRQ_HIP(c, hipMemcpyAsync(d_tp, tp2.data(), (size_t)nm * 8, hipMemcpyHostToDevice, st));
-        if (launch_vit_traceback(st, d_tb, d_tr, d_tp, nm)) { c->err = "traceback launch failed"; return STRQ_ERR_DEVICE; }
-        // 4. pattern strings
-        std::vector<PatTask> pt(nm);
-        for (int k = 0; k < nm; ++k) {
-            const int sl = slot2[k];
-            pt[sl].path = tp2[sl]; pt[sl].tag = dual_model(c, d, r0 + who[k], which)->h.state_tag; pt[sl].out = d_chars + p2_off[k]; pt[sl].T = len[k];
-            pt[sl].status = &d_tr[sl].status;
-        }
-        STRQ_HIP(c, hipMemcpyAsync(d_pt, pt.data(), (size_t)nm * sizeof(PatTask), hipMemcpyHostToDevice, st));
-        if (launch_mod_pattern(st, d_pt, nm, d_plen)) { c->err = "pattern launch failed"; return STRQ_ERR_DEVICE; }
-    }
-    if (const int prc = read_mod_patterns(c, d, r0, who, slot2, len, p2_off, d_plen, d_chars)) return prc;
+    if (const int prc = dual_patterns(c, d, sl, which, R, B.mod)) return prc;
     if (!sl.ex.llr) return STRQ_OK;
     // 5. per-unit scores of both branches: modsig, the records / the traced paths and the results are live until the next pass
-    LlrPassIn li;
-    li.who = &who; li.slot2 = &slot2; li.len = &len; li.sig_off = &sig_off; li.bp2_off = &bp2_off; li.paths = &tp2;
-    li.use_hub = use_hub; li.results = d_tr;
+    LlrPassIn li = dual_tail_in(R);
+    li.pattern = &B.mod; li.scores = &B.llr; li.anchored = false;
     return run_llr_pass(c, d, sl, li);
 }
 
@@ -881,6 +971,64 @@ static int run_conf_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, con
     return STRQ_OK;
 }
 
+// The bracket of the methylation calls of anchored reads: events of its own (the anchored pass around it holds the pass events),
+// made when the switch is first used; amod_stop waits for the stream and adds the milliseconds in between to amod_ms.
+static int amod_start(strq_ctx* c, DetectState* d)
+{
+    for (hipEvent_t& e : d->amod_ev) if (!e) STRQ_HIP(c, hipEventCreate(&e));
+    STRQ_HIP(c, hipEventRecord(d->amod_ev[0], c->stream));
+    return STRQ_OK;
+}
+static int amod_stop(strq_ctx* c, DetectState* d)
+{
+    STRQ_HIP(c, hipEventRecord(d->amod_ev[1], c->stream));
+    STRQ_HIP(c, hipStreamSynchronize(c->stream));
+    float ms = 0; STRQ_HIP(c, hipEventElapsedTime(&ms, d->amod_ev[0], d->amod_ev[1])); d->amod_ms += ms;
+    return STRQ_OK;
+}
+
+// Methylation calls of the anchored reads of one sub-batch (strq_set_anchored_mod), behind their records: a read of `R` is called
+// when its record has status 0 -- its stretch [begin, end) is then not empty.  queued: dual_decode and dual_patterns ran behind the
+// anchored decode on window-sized buffers (hub route); the patterns of the reads that turned out not to qualify are dropped and the
+// lengths become the stretches'.  Otherwise (back-pointer route) the same two steps run here, on the stretches of the reads that
+// qualify.  Then, with strq_set_mod_llr on, the per-unit scores of both branches as for a spanning read.
+static int run_anchored_mod(strq_ctx* c, DetectState* d, DetectState::Slot& sl, DualRun& R, bool queued)
+{
+    Batch& B = d->batch;
+    const int64_t r0 = sl.r0;
+    auto called = [&](int i) { const strq_anchored& a = B.anch[(size_t)(r0 + i)]; return (a.kind == ANCH_ENDS || a.kind == ANCH_STARTS) && a.status == 0 && a.begin < a.end; };
+    if (queued) {
+        for (size_t k = 0; k < R.who.size(); ++k) {
+            const strq_anchored& a = B.anch[(size_t)(r0 + R.who[k])];
+            if (called(R.who[k])) R.len[k] = a.end - a.begin; else { R.len[k] = 0; B.amod[(size_t)(r0 + R.who[k])].clear(); }
+        }
+    } else {
+        DualRun X;
+        for (int i : R.who) {
+            if (!called(i)) continue;
+            const strq_anchored& a = B.anch[(size_t)(r0 + i)];
+            X.who.push_back(i); X.raw_first.push_back(a.begin); X.len.push_back(a.end - a.begin);
+        }
+        R = std::move(X);
+        if (R.who.empty()) return STRQ_OK;
+        if (const int arc = amod_start(c, d)) return arc;
+        if (const int drc = dual_decode(c, d, sl, DUAL_MOD, R)) return drc;
+        if (const int prc = dual_patterns(c, d, sl, DUAL_MOD, R, B.amod)) return prc;
+        if (const int arc = amod_stop(c, d)) return arc;
+    }
+    for (int i : R.who) {
+        if (!called(i)) continue;
+        const std::string& pat = B.amod[(size_t)(r0 + i)];
+        B.amod_called[(size_t)(r0 + i)] = 1;
+        d->amod_reads += 1; d->amod_units += pat == "-" ? 0.0 : (double)pat.size();
+    }
+    d->amod_launches += R.launches;
+    if (!sl.ex.llr) return STRQ_OK;
+    LlrPassIn li = dual_tail_in(R);
+    li.pattern = &B.amod; li.scores = &B.amod_llr; li.anchored = true;
+    return run_llr_pass(c, d, sl, li);
+}
+
 // Anchored counting of the reads of one sub-batch (strq_set_anchored): the reads that hold one flank only are decoded once more, from
 // their flank to their end (or from their start to their flank), with the target's end / start model.  Runs on the context's stream
 // when the rows of the sub-batch are taken, like the unit pass: the geometry and the conditioning rows go back up from the slot's
@@ -962,7 +1110,32 @@ static int run_anchored_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
     }
     std::vector<VitResult> vr((size_t)m);
     STRQ_HIP(c, hipMemcpyAsync(vr.data(), d_vr, (size_t)m * sizeof(VitResult), hipMemcpyDeviceToHost, st));
-    if (const int rc = pass_stop(c, d, d->anch_ms)) return rc;
+    // methylation calls (strq_set_anchored_mod): the reads of kind 2 / 3 whose target has a modification model, in task order
+    DualRun R; AnchoredModSrc src = {d_cls, d_rc, d_vr, m, {}};
+    if (sl.ex.amod)
+        for (int at = 0; at < m; ++at) {
+            const int i = read_of[(size_t)at];
+            if (target_of(d, r0 + i).mod_model_id < 0) continue;
+            const AnchoredClass& k = cls[(size_t)i];
+            R.who.push_back(i); R.raw_first.push_back(k.begin); R.len.push_back(k.end - k.begin); src.res_of.push_back(at);
+        }
+    bool queued = false;
+    if (!R.who.empty()) {
+        // With hub records the pass is queued behind the decode, its buffers sized by the windows (the stretch of a read is never
+        // longer), and the bracket of the anchored pass closes without a wait; the back-pointer route waits for the records first.
+        std::vector<GroupItem> items; bool use_hub = false;
+        if (const int rrc = dual_route(c, d, r0, DUAL_MOD, R, items, use_hub)) return rrc;
+        if (use_hub) {
+            STRQ_HIP(c, hipEventRecord(d->ev[3], st));
+            if (const int arc = amod_start(c, d)) return arc;
+            if (const int drc = dual_decode(c, d, sl, DUAL_MOD, R, &src)) return drc;
+            if (const int prc = dual_patterns(c, d, sl, DUAL_MOD, R, B.amod)) return prc;          // (waits for the stream: the records are here)
+            float ms = 0; STRQ_HIP(c, hipEventElapsedTime(&ms, d->ev[2], d->ev[3])); d->anch_ms += ms;
+            if (const int arc = amod_stop(c, d)) return arc;
+            queued = true;
+        }
+    }
+    if (!queued) { if (const int rc = pass_stop(c, d, d->anch_ms)) return rc; }
     for (int at = 0; at < m; ++at) {
         const int i = read_of[(size_t)at];
         const AnchoredClass& k = cls[(size_t)i];
@@ -971,7 +1144,7 @@ static int run_anchored_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
         B.anch[(size_t)(r0 + i)] = anchored_record(k.kind, k.begin, k.end - k.begin, v.status, v.counted, k.kind == ANCH_ENDS ? t.end_bias : t.start_bias,
                                                    v.logp, (int64_t)v.dbg[0], (int64_t)v.dbg[1]);
     }
-    return STRQ_OK;
+    return R.who.empty() ? STRQ_OK : run_anchored_mod(c, d, sl, R, queued);
 }
 
 // bytes [pos, pos + len) of the batch (reads back to back) from the caller's memory: one buffer, or one per read
@@ -1794,6 +1967,12 @@ int run_range(strq_ctx* c, DetectState* d, int64_t first, int64_t last)
         if (!B.target_given.empty()) { B.target = B.target_given; B.target_given.clear(); }
         B.scan_ncand = 0; B.cand.clear(); B.scores.clear();
     }
+    if (d->extras.amod) {
+        // (refused here, before any launch: the calls hang on the anchored records, and a scan has none)
+        if (d->scan_on) { c->err = "anchored-mod: not available in a scan (strq_scan_set)"; return STRQ_ERR_ARG; }
+        if (!d->extras.anch) { c->err = "anchored-mod: needs anchored counting (strq_set_anchored)"; return STRQ_ERR_ARG; }
+        B.size_amod();
+    }
     if (d->extras.anch) {
         // nothing is launched for a call the anchored pass could not finish
         if (d->scan_on) { c->err = "anchored: not available in a scan (strq_scan_set)"; return STRQ_ERR_ARG; }
@@ -1814,6 +1993,7 @@ int run_range(strq_ctx* c, DetectState* d, int64_t first, int64_t last)
     B.ran = d->extras;
     d->rn_ms = 0; d->rn_fitted = d->rn_applied = d->rn_launches = 0; d->rn_timed = 0;
     d->anch_ms = 0; std::fill(d->anch_kinds, d->anch_kinds + 4, 0.0); d->anch_launches = d->anch_g2 = d->anch_lane = 0;
+    d->amod_ms = 0; d->amod_reads = d->amod_units = d->amod_launches = 0;
     d->unit_ms = 0; d->unit_bytes = d->unit_reads = d->unit_positions = 0;
     d->conf_ms = 0; d->conf_windows = d->conf_nopath = d->conf_expo = 0;
     d->llr_ms = 0; d->llr_units = d->llr_reads = d->llr_launches = 0;
@@ -2238,6 +2418,49 @@ int strq_last_anchored(strq_ctx* c, double* out8)
     out8[0] = d->anch_ms;
     for (int k = 0; k < 4; ++k) out8[1 + k] = d->anch_kinds[k];
     out8[5] = d->anch_launches; out8[6] = d->anch_g2; out8[7] = d->anch_lane;
+    return STRQ_OK;
+}
+
+int strq_set_anchored_mod(strq_ctx* c, int32_t on)
+{
+    STRQ_ENTER(c);
+    return set_extra(c, on, "bad argument (strq_set_anchored_mod takes 0 or 1)", &Extras::amod);
+}
+
+int strq_batch_fetch_anchored_mod(strq_ctx* c, int32_t* called, int64_t* off, char* chars, int64_t chars_cap, int64_t* voff, double* pool, int64_t pool_cap)
+{
+    STRQ_ENTER(c);
+    if (!off || !voff) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    DetectState* d = dstate(c);
+    if (const int rc = drain(c, d)) return rc;
+    const Batch& B = d->batch;
+    if (!B.ran.amod) { c->err = "the last batch ran without anchored methylation calls (strq_set_anchored_mod)"; return STRQ_ERR_ARG; }
+    const bool pools = chars || pool;
+    if (pools && !(chars && pool)) { c->err = "bad argument (strq_batch_fetch_anchored_mod: both pools or none)"; return STRQ_ERR_ARG; }
+    int64_t pos = 0, vpos = 0;
+    for (int64_t i = 0; i < B.n_reads; ++i) {
+        off[i] = pos; voff[i] = vpos;
+        if (called) called[i] = B.amod_called[(size_t)i];
+        if (!B.amod_called[(size_t)i]) continue;
+        const std::string& p = B.amod[(size_t)i]; const std::vector<double>& v = B.amod_llr[(size_t)i];
+        const int64_t n = (int64_t)p.size(), nv = (int64_t)v.size() / 2;
+        if (pools) {
+            if (pos + n > chars_cap || vpos + nv > pool_cap) { c->err = "anchored-mod pool too small"; return STRQ_ERR_ARG; }
+            if (n) std::memcpy(chars + pos, p.data(), (size_t)n);
+            if (nv) std::memcpy(pool + 2 * vpos, v.data(), (size_t)nv * 16);
+        }
+        pos += n; vpos += nv;
+    }
+    off[B.n_reads] = pos; voff[B.n_reads] = vpos;
+    return STRQ_OK;
+}
+
+int strq_last_anchored_mod(strq_ctx* c, double* out4)
+{
+    STRQ_ENTER(c);
+    if (!out4) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    DetectState* d = dstate(c);
+    out4[0] = d->amod_ms; out4[1] = d->amod_reads; out4[2] = d->amod_units; out4[3] = d->amod_launches;
     return STRQ_OK;
 }
 

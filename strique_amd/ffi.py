@@ -523,6 +523,35 @@ class Context(object):
         return {'ms': float(out[0]), 'kinds': tuple(int(v) for v in out[1:5]), 'launches': int(out[5]),
                 'register_resident': int(out[6]), 'lane_layout': int(out[7])}
 
+    def set_anchored_mod(self, on):
+        """strq_set_anchored_mod: later run calls with anchored counting on also call the methylation pattern of every read of
+        kind 2 / 3 whose record was decoded and whose target has a modification model (batch_fetch_anchored_mod)."""
+        self._check(self._lib.strq_set_anchored_mod(self._h, ctypes.c_int32(1 if on else 0)))
+
+    def batch_fetch_anchored_mod(self):
+        """Methylation calls of the anchored reads of the last batch (strq_batch_fetch_anchored_mod): per read None (no call), or
+        (pattern, scores) -- the pattern string ('-' when the dual model found no path) and an (n_units, 2) float64 array of
+        (V_base, V_mod), one row per character, or None when the run call ran without set_mod_llr or the pattern has no units."""
+        n = getattr(self, '_n_batch', 0)
+        called = np.zeros(max(1, n), np.int32); off = np.zeros(n + 1, np.int64); voff = np.zeros(n + 1, np.int64)
+        self._check(self._lib.strq_batch_fetch_anchored_mod(self._h, _ptr(called), _ptr(off), None, ctypes.c_int64(0), _ptr(voff), None, ctypes.c_int64(0)))
+        chars = np.zeros(max(1, int(off[-1])), np.uint8); pool = np.zeros((max(1, int(voff[-1])), 2), np.float64)
+        self._check(self._lib.strq_batch_fetch_anchored_mod(self._h, _ptr(called), _ptr(off), _ptr(chars), ctypes.c_int64(len(chars)), _ptr(voff), _ptr(pool),
+                                                            ctypes.c_int64(len(pool))))
+        out = []
+        for i in range(n):
+            if not called[i]:
+                out.append(None)
+                continue
+            out.append((chars[off[i]:off[i + 1]].tobytes().decode('ascii'), pool[voff[i]:voff[i + 1]].copy() if voff[i + 1] > voff[i] else None))
+        return out
+
+    def last_anchored_mod(self):
+        """The methylation calls of the last run call (strq_last_anchored_mod): {'ms', 'reads', 'units', 'launches'}."""
+        out = np.zeros(4)
+        self._check(self._lib.strq_last_anchored_mod(self._h, _ptr(out)))
+        return {'ms': float(out[0]), 'reads': int(out[1]), 'units': int(out[2]), 'launches': int(out[3])}
+
     # ---- renorm: the second normalisation step ---------------------------------------------
     def target_set_renorm(self, target_id, Q, A, model_min, model_max):
         """strq_target_set_renorm: the tables of a target (strique_amd.renorm.tables) with the rule's shares and its grid over
