@@ -528,6 +528,38 @@ int strq_debug_g2_layout(int32_t n_states, int32_t silent_start, int32_t start, 
                          const int32_t* emis_kind, const int32_t* count_inc, const int32_t* kind, const int32_t* pos,
                          double* out_lp, int32_t* out_own, int32_t* out_meta, char* why, int32_t why_len);
 
+/* Test hook, host only (no context, no device): the Viterbi kernel shape strq_model_create would put this model on.  Model arrays
+ * and placement hints as strq_model_create takes them (count_inc, state_tag, hint_slot, hint_lane may be NULL).  out[48]:
+ *   [0..4]    the shape id of a launch of decode mode 0 count, 1 back-pointers, 2 mark, 3 hub, 4 unit: the row of the lane-layout
+ *             table (csrc/vit_model.h, VIT_SHAPES) plus 16 for a single-stage model, or 8 for the general kernel; -1: no kernel
+ *             (the register-resident image of strq_model_set_positions is not planned here: it needs no row)
+ *   [5..9]    1 where the library has a launch of that mode for this model (the shape has the mode; hub: the model has a hub state
+ *             with an edge into `end`; unit: exactly two counted emitting states and no counted silent one)
+ *   [10] emitting, [11] silent slots per lane   [12..19] in-edge registers of the emitting, [20..27] of the silent slots (without
+ *   chain edges)   [28..35] 1: the emitting slot holds no Normal emission   [36] single-stage   [37] a silent state is counted
+ *   [38] the recording hub state or -1   [39], [40] the two counted states of a unit decode or -1   [41] 1: the general kernel
+ * STRQ_ERR_ARG (bad arrays) or STRQ_ERR_UNSUPPORTED (more than 4096 states) with the reason in `why`. */
+int strq_debug_viterbi_plan(int32_t n_states, int32_t silent_start, int32_t start, int32_t end,
+                            const int32_t* in_ptr, const int32_t* in_src, const double* in_logp,
+                            const int32_t* emis_kind, const double* emis_a, const double* emis_b, const double* emis_c,
+                            const int32_t* count_inc, const int32_t* state_tag,
+                            const int32_t* hint_slot, const int32_t* hint_lane, int32_t* out, char* why, int32_t why_len);
+/* Test hook: ONE Viterbi launch of decode mode `mode` (0 count, 2 mark, 3 hub, 4 unit) over n_seq (1 ... 8192) windows
+ * x[x_off[i] .. x_off[i + 1]) of model `model_id`, on the kernel shape the pipeline would take for that mode (STRQ_VIT_NO_G2 and
+ * STRQ_VIT_G2_* act as they do there).  Everything comes back raw, per window: logp, counted, status, dbg[4 i .. 4 i + 3] -- mark:
+ * dbg[0] / dbg[1] the 1-based time of the first emission of a state tagged 1 / of the first emission behind that stretch, 0 = none;
+ * hub, unit: dbg[0] the payload of the end state -- and the record buffer of window i, zeroed before the launch, at
+ * records + rec_off[i] (bytes): hub T + 1 records of 8 bytes (record t, written by the emission of the recording hub state at
+ * time t: low word the time of the previous such emission on that state's best path, high word the branch of the unit in between:
+ * tag 1 -> 1, 3 -> 2, 4 -> 3, else 0), unit 2 T records of 4 bytes (record 2 t + k, written by counted state k at observation t:
+ * the payload (t' + 1) << 1 | k' of the previous counted emission, 0 = none).  rec_off[i + 1] - rec_off[i] must be 8 (T + 1) / 8 T;
+ * records and rec_off may be NULL for count and mark.  launched[0] = the shape id that ran (as strq_debug_viterbi_plan reports it;
+ * 9 = the register-resident kernel).  STRQ_ERR_UNSUPPORTED where the library has no launch of that mode for the model.
+ * Own buffers on the context's stream: a batch in flight and its results are left alone. */
+int strq_debug_viterbi_mode(strq_ctx* ctx, int32_t model_id, int32_t mode, int64_t n_seq, const double* x, const int64_t* x_off,
+                            double* logp, int64_t* counted, int32_t* status, uint32_t* dbg, void* records, const int64_t* rec_off,
+                            int32_t* launched);
+
 /* Test hook, host only (no context, no device): the integer frame the upper-bound screen would run in for these alignment
  * parameters (open_h, ext_h, open_v, ext_v, dist_offset, dist_min; src/align_raw.h:84-103) and reads of up to `max_n` samples.
  * Returns 1 and out[6] = {scale, -ext_h * scale, -ext_v * scale, what is added to every table entry, float32 slack * scale,

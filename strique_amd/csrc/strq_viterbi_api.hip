@@ -65,23 +65,32 @@ static void vit_unit_states(VitModel& m, int32_t n_states, int32_t ne, const int
     if (found == 2) { m.unit_state[0] = st[0]; m.unit_state[1] = st[1]; }
 }
 
-int build_vit_model(strq_ctx* c, int32_t n_states, int32_t silent_start, int32_t start, int32_t end,
-                    const int32_t* in_ptr, const int32_t* in_src, const double* in_logp,
-                    const int32_t* emis_kind, const double* emis_a, const double* emis_b, const double* emis_c,
-                    const int32_t* count_inc, const int32_t* state_tag,
-                    const int32_t* hint_slot, const int32_t* hint_lane, HostModel** out)
+// The lane layout of a model as the host plans it -- no context, no device: the VitModel with its dimensions, degrees and flags (its
+// pointers stay null) and every array of the image.  build_vit_model uploads it, strq_debug_viterbi_plan reports it.
+struct VitPlan {
+    VitModel m;
+    std::vector<double> lp, a, b, cc, chain_lp;
+    std::vector<int32_t> src, kind, inc, own_e, own_s, chain_src, tag, cell_state, edge_csr, chain_csr;
+    int32_t fwd_stages = 1;
+};
+
+// Returns STRQ_OK, or the status build_vit_model is to return with the reason in *why.
+static int plan_vit_model(int32_t n_states, int32_t silent_start, int32_t start, int32_t end,
+                          const int32_t* in_ptr, const int32_t* in_src, const double* in_logp,
+                          const int32_t* emis_kind, const double* emis_a, const double* emis_b, const double* emis_c,
+                          const int32_t* count_inc, const int32_t* state_tag,
+                          const int32_t* hint_slot, const int32_t* hint_lane, VitPlan& P, const char** why)
 {
     const int ne = silent_start, ns = n_states - silent_start;
     if (n_states < 2 || ne < 1 || ns < 2 || start < ne || end < ne || start >= n_states || end >= n_states) {
-        c->err = "bad model dimensions"; return STRQ_ERR_ARG;
+        *why = "bad model dimensions"; return STRQ_ERR_ARG;
     }
     // the edge lists are validated before any size decision: a model too large for the lane layouts goes on to the general
     // kernel's builder, which indexes host arrays with these sources
-    if (const char* bad = validate_vit_model(n_states, silent_start, in_ptr, in_src, emis_kind)) { c->err = bad; return STRQ_ERR_ARG; }
+    if (const char* bad = validate_vit_model(n_states, silent_start, in_ptr, in_src, emis_kind)) { *why = bad; return STRQ_ERR_ARG; }
     const int epl = (ne + 63) / 64, spl = (ns + 63) / 64;
-    if (epl > 8 || spl > 4 || n_states >= 65535) { c->err = "model too large for the compiled Viterbi kernels"; return STRQ_ERR_UNSUPPORTED; }
-    HostModel* hm = new HostModel();
-    VitModel& m = hm->h;
+    if (epl > 8 || spl > 4 || n_states >= 65535) { *why = "model too large for the compiled Viterbi kernels"; return STRQ_ERR_UNSUPPORTED; }
+    VitModel& m = P.m;
     std::memset(&m, 0, sizeof(m));
     m.n_states = n_states; m.n_emit = ne; m.n_silent = ns; m.start = start; m.end = end; m.epl = epl; m.spl = spl;
     // emitting states: dealt to slots by descending in-degree (slot 0 takes the 64 busiest, ...)
@@ -89,7 +98,8 @@ int build_vit_model(strq_ctx* c, int32_t n_states, int32_t silent_start, int32_t
     std::vector<int> eord(ne);
     for (int i = 0; i < ne; ++i) eord[i] = i;
     std::stable_sort(eord.begin(), eord.end(), [&](int a, int b) { return deg_of(a) > deg_of(b); });
-    std::vector<int32_t> own_e((size_t)epl * 64, -1);
+    std::vector<int32_t>& own_e = P.own_e;
+    own_e.assign((size_t)epl * 64, -1);
     bool hinted = hint_slot && hint_lane;
     if (hinted) {      // caller-provided (slot, lane) of every emitting state: must be a valid injective map
         for (int e = 0; e < ne && hinted; ++e) {
@@ -130,7 +140,7 @@ int build_vit_model(strq_ctx* c, int32_t n_states, int32_t silent_start, int32_t
     // slot p % Z; the first cell of a chain has no chain edge), so that one lane shift of the kernel's chain sweep carries
     // a value Z positions along (viterbi_kernels.hip).  Z is the slot count of the kernel shape the model runs on: the smallest layout is tried
     // first and widened until the shape that fits it has exactly that many silent slots.
-    std::vector<int32_t> own_s, chain_src_v; std::vector<double> chain_lp_v;
+    std::vector<int32_t>& own_s = P.own_s; std::vector<int32_t>& chain_src_v = P.chain_src; std::vector<double>& chain_lp_v = P.chain_lp;
     auto lay_out = [&](int Z) -> bool {
         if (ns > 64 * Z) return false;
         own_s.assign((size_t)Z * 64, -1); chain_src_v.assign((size_t)Z * 64, -1); chain_lp_v.assign((size_t)Z * 64, 0.0);
@@ -176,7 +186,7 @@ int build_vit_model(strq_ctx* c, int32_t n_states, int32_t silent_start, int32_t
             const int shape = vit_shape_of(m);
             if (shape >= 0 && vit_shape_silent_slots(shape) == Z) placed = true;
         }
-        if (!placed) { delete hm; c->err = "model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
+        if (!placed) { *why = "model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
     }
     const int spl2 = m.spl;
     auto is_chain_edge = [&](int dst, int srcst) {
@@ -198,11 +208,12 @@ int build_vit_model(strq_ctx* c, int32_t n_states, int32_t silent_start, int32_t
     }
     m.single_stage = 1;
     for (int b = ne; b < n_states; ++b) for (int e = in_ptr[b]; e < in_ptr[b + 1]; ++e) if (in_src[e] >= ne && !is_chain_edge(b, in_src[e])) m.single_stage = 0;
-    for (int s = 0; s < 8; ++s) if (m.e_deg[s] > 8 || m.s_deg[s] > 8) { delete hm; c->err = "a state has more than 8 in-edges"; return STRQ_ERR_UNSUPPORTED; }
+    for (int s = 0; s < 8; ++s) if (m.e_deg[s] > 8 || m.s_deg[s] > 8) { *why = "a state has more than 8 in-edges"; return STRQ_ERR_UNSUPPORTED; }
     m.n_edge_rows = rows;
     // LDS cells: the owner (slot, lane) of a state is its cell; the last cell is the -inf cell
     m.n_cells = (epl + spl2) * 64 + 1;
-    std::vector<int32_t> cell_of(n_states, -1), cell_state((size_t)m.n_cells, -1);
+    std::vector<int32_t> cell_of(n_states, -1); std::vector<int32_t>& cell_state = P.cell_state;
+    cell_state.assign((size_t)m.n_cells, -1);
     for (int i = 0; i < epl * 64; ++i) if (own_e[i] >= 0) { cell_of[own_e[i]] = i; cell_state[i] = own_e[i]; }
     // silent cells are interleaved (cell = first silent cell + lane * spl + slot = position along the zig-zag), so that
     // the emitting states of consecutive lanes read their delete predecessors from consecutive LDS cells
@@ -211,15 +222,16 @@ int build_vit_model(strq_ctx* c, int32_t n_states, int32_t silent_start, int32_t
         cell_of[own_s[i]] = cell; cell_state[cell] = own_s[i];
     }
     m.start_cell = cell_of[start]; m.end_cell = cell_of[end];
-    std::vector<int32_t> src((size_t)std::max(rows, 1) * 64, m.n_cells - 1);   // padding -> the -inf cell
-    std::vector<double> lp((size_t)std::max(rows, 1) * 64, 0.0);
-    hm->edge_csr.assign((size_t)std::max(rows, 1) * 64, -1);
+    std::vector<int32_t>& src = P.src; std::vector<double>& lp = P.lp;
+    src.assign((size_t)std::max(rows, 1) * 64, m.n_cells - 1);   // padding -> the -inf cell
+    lp.assign((size_t)std::max(rows, 1) * 64, 0.0);
+    P.edge_csr.assign((size_t)std::max(rows, 1) * 64, -1);
     auto fill = [&](int state, int base, int lane) {
         for (int e = in_ptr[state], j = 0; e < in_ptr[state + 1]; ++e) {
             if (state >= ne && is_chain_edge(state, in_src[e])) continue;
             src[(size_t)(base + j) * 64 + lane] = cell_of[in_src[e]];
             lp[(size_t)(base + j) * 64 + lane] = in_logp[e];
-            hm->edge_csr[(size_t)(base + j) * 64 + lane] = e;
+            P.edge_csr[(size_t)(base + j) * 64 + lane] = e;
             ++j;
         }
     };
@@ -227,8 +239,8 @@ int build_vit_model(strq_ctx* c, int32_t n_states, int32_t silent_start, int32_t
     for (int s = 0; s < spl2; ++s) for (int lane = 0; lane < 64; ++lane) if (own_s[s * 64 + lane] >= 0) fill(own_s[s * 64 + lane], m.s_base[s], lane);
     // forward pass: the CSR edge behind every chain edge, and how many silent states a path can cross through edges that are
     // not chain edges (the silent phase of forward_kernel runs once more for each)
-    hm->chain_csr.assign((size_t)spl2 * 64, -1);
-    for (int i = 0; i < spl2 * 64; ++i) if (own_s[i] >= 0 && chain_src_v[i] >= 0) hm->chain_csr[i] = chain_e[own_s[i]];
+    P.chain_csr.assign((size_t)spl2 * 64, -1);
+    for (int i = 0; i < spl2 * 64; ++i) if (own_s[i] >= 0 && chain_src_v[i] >= 0) P.chain_csr[i] = chain_e[own_s[i]];
     {
         std::vector<int> depth(n_states, 0); int deepest = 0;
         for (int b = ne; b < n_states; ++b) {
@@ -236,21 +248,43 @@ int build_vit_model(strq_ctx* c, int32_t n_states, int32_t silent_start, int32_t
             for (int e = in_ptr[b]; e < in_ptr[b + 1]; ++e) if (in_src[e] >= ne) dp = std::max(dp, depth[in_src[e]] + (is_chain_edge(b, in_src[e]) ? 0 : 1));
             depth[b] = dp; deepest = std::max(deepest, dp);
         }
-        hm->fwd_stages = deepest + 1;
+        P.fwd_stages = deepest + 1;
     }
-    std::vector<int32_t> kind((size_t)epl * 64, 0); std::vector<double> a((size_t)epl * 64, 0.0), b(a), cc(a);
+    std::vector<int32_t>& kind = P.kind; std::vector<double>& a = P.a; std::vector<double>& b = P.b; std::vector<double>& cc = P.cc;
+    kind.assign((size_t)epl * 64, 0); a.assign((size_t)epl * 64, 0.0); b = a; cc = a;
     for (int i = 0; i < epl * 64; ++i) if (own_e[i] >= 0) { const int e = own_e[i]; kind[i] = emis_kind[e]; a[i] = emis_a[e]; b[i] = emis_b[e]; cc[i] = emis_c[e]; }
     m.uni_lo_max = -INFINITY; m.uni_hi_min = INFINITY;
     for (int e = 0; e < ne; ++e) if (emis_kind[e] == 2) { m.uni_lo_max = std::max(m.uni_lo_max, emis_a[e]); m.uni_hi_min = std::min(m.uni_hi_min, emis_b[e]); }
-    std::vector<int32_t> inc((size_t)n_states + 1, 0);
-    if (count_inc) std::copy(count_inc, count_inc + n_states, inc.begin());
-    std::vector<int32_t> tagv((size_t)n_states + 1, 0);
-    if (state_tag) std::copy(state_tag, state_tag + n_states, tagv.begin());
+    P.inc.assign((size_t)n_states + 1, 0);
+    if (count_inc) std::copy(count_inc, count_inc + n_states, P.inc.begin());
+    P.tag.assign((size_t)n_states + 1, 0);
+    if (state_tag) std::copy(state_tag, state_tag + n_states, P.tag.begin());
+    m.rec_state = -1;
+    for (int e = in_ptr[end]; e < in_ptr[end + 1]; ++e) if (in_src[e] < ne && state_tag && state_tag[in_src[e]] == 2) m.rec_state = in_src[e];
+    m.silent_counted = 0;
+    for (int s2 = ne; s2 < n_states; ++s2) if (count_inc && count_inc[s2] != 0) m.silent_counted = 1;
+    vit_unit_states(m, n_states, ne, count_inc);
+    return STRQ_OK;
+}
+
+int build_vit_model(strq_ctx* c, int32_t n_states, int32_t silent_start, int32_t start, int32_t end,
+                    const int32_t* in_ptr, const int32_t* in_src, const double* in_logp,
+                    const int32_t* emis_kind, const double* emis_a, const double* emis_b, const double* emis_c,
+                    const int32_t* count_inc, const int32_t* state_tag,
+                    const int32_t* hint_slot, const int32_t* hint_lane, HostModel** out)
+{
+    VitPlan P; const char* why = nullptr;
+    if (const int prc = plan_vit_model(n_states, silent_start, start, end, in_ptr, in_src, in_logp, emis_kind, emis_a, emis_b, emis_c, count_inc, state_tag,
+                                       hint_slot, hint_lane, P, &why)) { c->err = why; return prc; }
+    HostModel* hm = new HostModel();
+    VitModel& m = hm->h;
+    m = P.m;
+    hm->edge_csr.swap(P.edge_csr); hm->chain_csr.swap(P.chain_csr); hm->fwd_stages = P.fwd_stages;
     // one device blob: the arrays, the VitModel that points to them behind
     Image im;
-    const size_t o_lp = im.put(lp), o_a = im.put(a), o_b = im.put(b), o_c = im.put(cc), o_src = im.put(src), o_kind = im.put(kind), o_inc = im.put(inc),
-                 o_own_e = im.put(own_e), o_own_s = im.put(own_s), o_chain_src = im.put(chain_src_v), o_chain_lp = im.put(chain_lp_v),
-                 o_tag = im.put(tagv), o_cell = im.put(cell_state), o_m = im.put(&m, 1);
+    const size_t o_lp = im.put(P.lp), o_a = im.put(P.a), o_b = im.put(P.b), o_c = im.put(P.cc), o_src = im.put(P.src), o_kind = im.put(P.kind), o_inc = im.put(P.inc),
+                 o_own_e = im.put(P.own_e), o_own_s = im.put(P.own_s), o_chain_src = im.put(P.chain_src), o_chain_lp = im.put(P.chain_lp),
+                 o_tag = im.put(P.tag), o_cell = im.put(P.cell_state), o_m = im.put(&m, 1);
     if (hm->blob.reserve(im.lay.total()) != hipSuccess) { delete hm; c->err = "out of device memory"; return STRQ_ERR_NOMEM; }
     void* d = hm->blob.p;
     m.edge_logp = Carve::at<const double>(d, o_lp); m.emis_a = Carve::at<const double>(d, o_a); m.emis_b = Carve::at<const double>(d, o_b);
@@ -259,11 +293,6 @@ int build_vit_model(strq_ctx* c, int32_t n_states, int32_t silent_start, int32_t
     m.chain_src = Carve::at<const int32_t>(d, o_chain_src); m.chain_logp = Carve::at<const double>(d, o_chain_lp);
     m.state_tag = Carve::at<const int32_t>(d, o_tag); m.cell_state = Carve::at<const int32_t>(d, o_cell);
     hm->dev = Carve::at<const VitModel>(d, o_m);
-    m.rec_state = -1;
-    for (int e = in_ptr[end]; e < in_ptr[end + 1]; ++e) if (in_src[e] < ne && state_tag && state_tag[in_src[e]] == 2) m.rec_state = in_src[e];
-    m.silent_counted = 0;
-    for (int s2 = ne; s2 < n_states; ++s2) if (count_inc && count_inc[s2] != 0) m.silent_counted = 1;
-    vit_unit_states(m, n_states, ne, count_inc);
     if (hipMemcpy(d, im.host().data(), im.lay.total(), hipMemcpyHostToDevice) != hipSuccess) { delete hm; c->err = "model upload failed"; return STRQ_ERR_DEVICE; }
     *out = hm;
     return STRQ_OK;
@@ -618,6 +647,41 @@ int strq_debug_g2_layout(int32_t n_states, int32_t silent_start, int32_t start, 
     return STRQ_OK;
 }
 
+// Host-only (no context, no device): which kernel shape strq_model_create would put this model on and what its layout looks like.
+// out[48]: [0..4] the shape id of a launch of mode 0..4 (vit_shape_of, VIT_SHAPE_SS included; -1: none), [5..9] 1 where the product
+// has a launch of that mode for the model, [10] epl, [11] spl, [12..19] e_deg, [20..27] s_deg, [28..35] e_flat, [36] single_stage,
+// [37] silent_counted, [38] rec_state, [39..40] unit_state, [41] 1 = the general kernel (no lane layout), the rest 0.
+int strq_debug_viterbi_plan(int32_t n_states, int32_t silent_start, int32_t start, int32_t end,
+                            const int32_t* in_ptr, const int32_t* in_src, const double* in_logp,
+                            const int32_t* emis_kind, const double* emis_a, const double* emis_b, const double* emis_c,
+                            const int32_t* count_inc, const int32_t* state_tag,
+                            const int32_t* hint_slot, const int32_t* hint_lane, int32_t* out, char* why, int32_t why_len)
+{
+    auto say = [&](const char* w) { if (why && why_len > 0) snprintf(why, why_len, "%s", w); };
+    if (!in_ptr || !in_src || !in_logp || !emis_kind || !emis_a || !emis_b || !emis_c || !out) { say("bad argument"); return STRQ_ERR_ARG; }
+    VitPlan P; const char* w = nullptr;
+    int rc = plan_vit_model(n_states, silent_start, start, end, in_ptr, in_src, in_logp, emis_kind, emis_a, emis_b, emis_c, count_inc, state_tag,
+                            hint_slot, hint_lane, P, &w);
+    if (rc == STRQ_ERR_UNSUPPORTED) {          // as strq_model_create: the general kernel takes what no lane layout holds
+        if (n_states > VIT_CSR_MAX_STATES) { say("model too large: more than 4096 states"); return STRQ_ERR_UNSUPPORTED; }
+        std::memset(&P.m, 0, sizeof(P.m));
+        P.m.csr = 1; P.m.rec_state = -1; P.m.unit_state[0] = P.m.unit_state[1] = -1;
+        rc = STRQ_OK;
+    }
+    if (rc) { say(w ? w : "?"); return rc; }
+    const VitModel& m = P.m;
+    std::fill(out, out + 48, 0);
+    const int shape = vit_shape_of(m);
+    for (int mode = VIT_COUNT; mode <= VIT_UNIT; ++mode) {
+        out[mode] = shape;
+        out[5 + mode] = (vit_mode_ok(shape, mode) && (mode != VIT_HUB || m.rec_state >= 0) && (mode != VIT_UNIT || vit_unit_ok(m, shape))) ? 1 : 0;
+    }
+    out[10] = m.epl; out[11] = m.spl;
+    for (int i = 0; i < 8; ++i) { out[12 + i] = m.e_deg[i]; out[20 + i] = m.s_deg[i]; out[28 + i] = m.e_flat[i]; }
+    out[36] = m.single_stage; out[37] = m.silent_counted; out[38] = m.rec_state; out[39] = m.unit_state[0]; out[40] = m.unit_state[1]; out[41] = m.csr;
+    return STRQ_OK;
+}
+
 int strq_model_set_positions(strq_ctx* c, int32_t model_id, const int32_t* kind, const int32_t* pos)
 {
     strq::CtxScope scope_(c);
@@ -691,6 +755,64 @@ int strq_viterbi_batch(strq_ctx* c, int32_t model_id, int64_t n_seq, const doubl
     STRQ_HIP(c, hipEventElapsedTime(&c->timing[0], c->ev[0], c->ev[1]));
     STRQ_HIP(c, hipEventElapsedTime(&c->timing[1], c->ev[1], c->ev[2]));
     c->timing[3] = c->timing[0] + c->timing[1];
+    return STRQ_OK;
+}
+
+// Test hook: one launch_viterbi of `mode` over the windows, on buffers of the call's own (strique_hip.h).
+int strq_debug_viterbi_mode(strq_ctx* c, int32_t model_id, int32_t mode, int64_t n_seq, const double* x, const int64_t* x_off,
+                            double* logp, int64_t* counted, int32_t* status, uint32_t* dbg, void* records, const int64_t* rec_off,
+                            int32_t* launched)
+{
+    STRQ_ENTER(c);
+    const char* bad = "bad argument";
+    if (model_id < 0 || model_id >= (int32_t)c->models.size() || !c->models[model_id] || n_seq < 1 || n_seq > 8192 || !x_off || !launched || x_off[0] != 0) { c->err = bad; return STRQ_ERR_ARG; }
+    if (mode != VIT_COUNT && mode != VIT_MARK && mode != VIT_HUB && mode != VIT_UNIT) { c->err = "bad argument (mode: count, mark, hub or unit)"; return STRQ_ERR_ARG; }
+    const bool rec = mode == VIT_HUB || mode == VIT_UNIT;
+    if (rec && (!records || !rec_off || rec_off[0] != 0)) { c->err = bad; return STRQ_ERR_ARG; }
+    for (int64_t i = 0; i < n_seq; ++i) {
+        const int64_t T = x_off[i + 1] - x_off[i];
+        if (T < 0 || T >= ((int64_t)1 << 28)) { c->err = "bad argument (window lengths)"; return STRQ_ERR_ARG; }
+        // HUB: T + 1 records of 8 bytes; UNIT: 2 T records of 4 bytes
+        if (rec && rec_off[i + 1] - rec_off[i] != (mode == VIT_HUB ? 8 * (T + 1) : 8 * T)) { c->err = "bad argument (rec_off: the bytes of every window's records)"; return STRQ_ERR_ARG; }
+    }
+    const int64_t tot = x_off[n_seq];
+    if (tot > 0 && !x) { c->err = bad; return STRQ_ERR_ARG; }
+    HostModel* hm = c->models[model_id];
+    const int shape = vit_shape_for(hm->h, (VitMode)mode);
+    launched[0] = shape;
+    if (shape < 0 || !vit_mode_ok(shape, mode) || (mode == VIT_HUB && hm->h.rec_state < 0) || (mode == VIT_UNIT && !vit_unit_ok(hm->h, shape))) {
+        c->err = "the model has no launch of this decode mode"; return STRQ_ERR_UNSUPPORTED;
+    }
+    hipStream_t st = c->stream;
+    const size_t rec_bytes = rec ? (size_t)rec_off[n_seq] : 0;
+    DevBuf b_x, b_tasks, b_res, b_rec, b_queue;
+    STRQ_HIP(c, b_x.reserve((size_t)tot * 8 + 64)); STRQ_HIP(c, b_tasks.reserve((size_t)n_seq * sizeof(VitTask)));
+    STRQ_HIP(c, b_res.reserve((size_t)n_seq * sizeof(VitResult))); STRQ_HIP(c, b_rec.reserve(rec_bytes + 64)); STRQ_HIP(c, b_queue.reserve(64));
+    std::vector<VitTask> tasks((size_t)n_seq);
+    for (int64_t i = 0; i < n_seq; ++i) {
+        VitTask& t = tasks[(size_t)i];
+        std::memset(&t, 0, sizeof(t));
+        t.model = hm->dev; t.sig = b_x.as<double>() + x_off[i]; t.T = x_off[i + 1] - x_off[i]; t.src_kind = VIT_SRC_F64;
+        if (rec) t.bp = reinterpret_cast<uint16_t*>(b_rec.as<char>() + rec_off[i]);
+    }
+    if (tot) STRQ_HIP(c, hipMemcpyAsync(b_x.p, x, (size_t)tot * 8, hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, hipMemcpyAsync(b_tasks.p, tasks.data(), (size_t)n_seq * sizeof(VitTask), hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, hipMemsetAsync(b_res.p, 0, (size_t)n_seq * sizeof(VitResult), st));
+    STRQ_HIP(c, hipMemsetAsync(b_rec.p, 0, rec_bytes + 64, st));
+    STRQ_HIP(c, hipMemsetAsync(b_queue.p, 0, 64, st));
+    const int lrc = launch_viterbi(st, shape, hm->h.n_cells, b_tasks.as<VitTask>(), b_res.as<VitResult>(), (int)n_seq, b_queue.as<int>(), c->n_cu, (VitMode)mode);
+    if (lrc) { (void)hipStreamSynchronize(st); c->err = "viterbi launch failed"; return viterbi_launch_status(lrc); }
+    std::vector<VitResult> res((size_t)n_seq);
+    STRQ_HIP(c, hipMemcpyAsync(res.data(), b_res.p, (size_t)n_seq * sizeof(VitResult), hipMemcpyDeviceToHost, st));
+    if (rec_bytes) STRQ_HIP(c, hipMemcpyAsync(records, b_rec.p, rec_bytes, hipMemcpyDeviceToHost, st));
+    STRQ_HIP(c, hipStreamSynchronize(st));
+    for (int64_t i = 0; i < n_seq; ++i) {
+        const VitResult& r = res[(size_t)i];
+        if (logp) logp[i] = r.logp;
+        if (counted) counted[i] = r.counted;
+        if (status) status[i] = r.status;
+        if (dbg) std::memcpy(dbg + 4 * i, r.dbg, sizeof(r.dbg));
+    }
     return STRQ_OK;
 }
 

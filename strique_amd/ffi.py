@@ -179,6 +179,34 @@ def debug_mod_llr_image(baked):
     return _debug_image("strq_debug_mod_llr_image", MOD_LLR_IMAGE_SHAPES, baked, [])
 
 
+VIT_COUNT, VIT_BACKPTR, VIT_MARK, VIT_HUB, VIT_UNIT = range(5)
+VIT_SHAPE_CSR, VIT_SHAPE_G2, VIT_SHAPE_SS = 8, 9, 16
+
+
+def debug_viterbi_plan(baked):
+    """strq_debug_viterbi_plan: the Viterbi kernel shape strq_model_create would put a baked model on, as a dict -- 'shape' (the id,
+    16 added for a single-stage model, 8 = the general kernel), 'row', 'ss', 'modes' (the decode modes the library launches for it),
+    'epl', 'spl', 'e_deg', 's_deg', 'e_flat', 'single_stage', 'silent_counted', 'rec_state', 'unit_state', 'csr'.  No context, no device."""
+    lib = load_library()
+    hints = getattr(baked, 'hint_slot', None) is not None and (np.asarray(baked.hint_slot)[:baked.silent_start] >= 0).all()
+    arrs = [_c(baked.in_ptr, np.int32), _c(baked.in_src, np.int32), _c(baked.in_logp, np.float64), _c(baked.emis_kind, np.int32),
+            _c(baked.emis_a, np.float64), _c(baked.emis_b, np.float64), _c(baked.emis_c, np.float64), _c(baked.count_inc, np.int32),
+            None if baked.tag is None else _c(baked.tag, np.int32),
+            _c(baked.hint_slot, np.int32) if hints else None, _c(baked.hint_lane, np.int32) if hints else None]
+    out = np.zeros(48, np.int32); why = ctypes.create_string_buffer(256)
+    rc = lib.strq_debug_viterbi_plan(ctypes.c_int32(baked.n_states), ctypes.c_int32(baked.silent_start), ctypes.c_int32(baked.start),
+                                     ctypes.c_int32(baked.end), *([_ptr(a) for a in arrs] + [_ptr(out), why, ctypes.c_int32(256)]))
+    if rc != STRQ_OK:
+        raise StriqueHipError(rc, "strq_debug_viterbi_plan: " + why.value.decode())
+    shape = int(out[0])
+    epl, spl = int(out[10]), int(out[11])
+    return {"shape": shape, "row": shape & ~VIT_SHAPE_SS if shape >= 0 else -1, "ss": bool(shape >= 0 and shape & VIT_SHAPE_SS),
+            "shapes": [int(v) for v in out[0:5]], "modes": [m for m in range(5) if out[5 + m]], "epl": epl, "spl": spl,
+            "e_deg": [int(v) for v in out[12:12 + epl]], "s_deg": [int(v) for v in out[20:20 + spl]], "e_flat": [int(v) for v in out[28:28 + epl]],
+            "single_stage": int(out[36]), "silent_counted": int(out[37]), "rec_state": int(out[38]),
+            "unit_state": (int(out[39]), int(out[40])), "csr": int(out[41])}
+
+
 class Context(object):
     """One HIP context / stream / workspace on one GPU (strq_ctx)."""
 
@@ -347,6 +375,29 @@ class Context(object):
         if want_path:
             paths = [paths[off[i]:off[i + 1]] for i in range(n)]
         return logp, counted, status, paths
+
+    def debug_viterbi_mode(self, model_id, mode, seqs):
+        """strq_debug_viterbi_mode: one Viterbi launch of decode mode `mode` (VIT_COUNT, VIT_MARK, VIT_HUB, VIT_UNIT) over the windows
+        `seqs` (float64 arrays).  Returns a dict of raw results: 'logp', 'counted', 'status', 'dbg' (n, 4 uint32), 'records' (per
+        window: hub T + 1 uint64, unit (T, 2) uint32, else None) and 'launched' (the shape id that ran)."""
+        n = len(seqs)
+        x, x_off = _offsets(seqs, np.float64)
+        logp = np.zeros(n); counted = np.zeros(n, np.int64); status = np.zeros(n, np.int32); dbg = np.zeros((n, 4), np.uint32)
+        launched = np.full(1, -1, np.int32)
+        rec = rec_off = None
+        if mode in (VIT_HUB, VIT_UNIT):
+            rec_off = np.zeros(n + 1, np.int64)
+            for i, s in enumerate(seqs):
+                rec_off[i + 1] = rec_off[i] + (8 * (len(s) + 1) if mode == VIT_HUB else 8 * len(s))
+            rec = np.full(int(rec_off[-1]) + 8, 0xA5, np.uint8)
+        self._check(self._lib.strq_debug_viterbi_mode(self._h, ctypes.c_int32(model_id), ctypes.c_int32(mode), ctypes.c_int64(n), _ptr(x), _ptr(x_off),
+                                                      _ptr(logp), _ptr(counted), _ptr(status), _ptr(dbg), _ptr(rec), _ptr(rec_off), _ptr(launched)))
+        records = [None] * n
+        if rec is not None:
+            for i in range(n):
+                raw = rec[int(rec_off[i]):int(rec_off[i + 1])]
+                records[i] = raw.view(np.uint64).copy() if mode == VIT_HUB else raw.view(np.uint32).reshape(-1, 2).copy()
+        return {"logp": logp, "counted": counted, "status": status, "dbg": dbg, "records": records, "launched": int(launched[0])}
 
     def forward_batch(self, model_id, xs, c0=None):
         """strq_forward_batch: xs a list of float64 arrays; c0 None or one int per window (the moments are accumulated about it:

@@ -1,6 +1,7 @@
 // Stand-alone host program over strique_amd/csrc/vit_model.h (no HIP): which kernel shape a model runs on, which decode modes a shape
 // has, and that the shape table agrees with itself.  Built and run under ASan/UBSan by tests/test_vit_shapes_host.py; exits 0 when
-// every check holds.
+// every check holds.  With --modes it prints one line "row mode" for every pair vit_mode_ok has (rows 0 .. VIT_LANE_SHAPES - 1, then the
+// general and the register-resident shape) and nothing else: tests/test_vit_mode_cases_host.py holds its cases against that list.
 #include <cstdio>
 #include <cstring>
 #include <initializer_list>
@@ -146,8 +147,13 @@ static void consistency()
     CHECK(n > 100000 && fitted > n / 2);
 }
 
-int main()
+int main(int argc, char** argv)
 {
+    if (argc > 1 && std::strcmp(argv[1], "--modes") == 0) {
+        for (int id = 0; id <= VIT_SHAPE_G2; ++id)
+            for (int mode = VIT_COUNT; mode <= VIT_UNIT; ++mode) if (vit_mode_ok(id, mode)) std::printf("%d %d\n", id, mode);
+        return 0;
+    }
     shape_choice();
     mode_table();
     shape_for();

@@ -191,13 +191,27 @@ def _random_model(rng, ne, ns, extra_silent_edges):
                     np.full(n, -1, np.int32), np.full(n, -1, np.int32))
 
 
-@pytest.mark.parametrize("ne,ns,multi", [(5, 3, False), (40, 10, False), (64, 20, True), (130, 40, True), (200, 70, False), (260, 130, True)])
+# (ne, ns, multi) -> the row of VIT_SHAPES (strique_amd/csrc/vit_model.h) the model runs on and whether it is single-stage: rows 1 to 4,
+# each single-stage and multi-stage, and row 0; both the count-only and the back-pointer instance of each run below
+GENERIC_SHAPES = {(5, 3, False): (1, True), (40, 10, False): (1, True), (64, 20, True): (1, False), (130, 40, True): (3, False),
+                  (200, 70, False): (0, True), (260, 130, True): (4, False), (100, 80, False): (2, True), (100, 80, True): (2, False),
+                  (130, 140, False): (3, True), (300, 70, False): (4, True)}
+
+
+def test_generic_shapes_cover_rows_1_to_4():
+    assert {(row, ss) for row, ss in GENERIC_SHAPES.values()} >= {(row, ss) for row in (1, 2, 3, 4) for ss in (True, False)}
+
+
+@pytest.mark.parametrize("ne,ns,multi", list(GENERIC_SHAPES))
 def test_random_models_generic_kernel_shapes(ctx, orc, ne, ns, multi):
     """Models without layout hints and with arbitrary topology go through the generic kernel shapes
     (degree-sorted ownership, chain decomposition, multi-stage silent phase): log-probability bits,
-    state path and carried counts must equal the oracle's."""
+    state path and carried counts must equal the oracle's.  Which shape that is, the plan says."""
+    from strique_amd import ffi
     rng = np.random.default_rng(1000 + ne)
     baked = _random_model(rng, ne, ns, multi)
+    plan = ffi.debug_viterbi_plan(baked)
+    assert (plan["row"], plan["ss"]) == GENERIC_SHAPES[(ne, ns, multi)] and {ffi.VIT_COUNT, ffi.VIT_BACKPTR} <= set(plan["modes"]), plan
     mid = ctx.model_create(baked)
     for T in (1, 7, 150):
         x = rng.uniform(55, 125, T)
@@ -253,6 +267,8 @@ def test_models_beyond_the_lane_layouts_run_on_the_general_kernel(ctx, orc, ne, 
                 order = np.argsort(ks); ks = [ks[i] for i in order]; ps = [ps[i] for i in order]
             src += ks; lp += ps; in_ptr.append(len(src))
         baked = baked._replace(in_ptr=np.array(in_ptr, np.int32), in_src=np.array(src, np.int32), in_logp=np.array(lp))
+    plan = ffi.debug_viterbi_plan(baked)
+    assert plan["csr"] == 1 and plan["shape"] == ffi.VIT_SHAPE_CSR and {ffi.VIT_COUNT, ffi.VIT_BACKPTR} <= set(plan["modes"]), plan
     mid = ctx.model_create(baked)
     for T in (1, 9, 120):
         x = rng.uniform(55, 125, T)
