@@ -169,6 +169,29 @@ int strq_forward_batch(strq_ctx* ctx, int32_t model_id, int64_t n_seq, const dou
  * over paths needs; equal to in_logp everywhere else.  Only the forward pass reads it.  STRQ_ERR_ARG when an entry is below in_logp's.
  */
 int strq_model_set_forward_logp(strq_ctx* ctx, int32_t model_id, const double* in_logp_sum);
+/*
+ * Tract decodes: compound models -- several repeat loops in a fixed order, hmm.CompoundRepeatModel -- count the visits of every loop
+ * separately.  Optional, after strq_model_create: tract_of[n_states] is -1 or the tract 0 .. n_tracts - 1 (n_tracts 1 .. 3) whose
+ * counter an emission of the state advances.  A state with a tract must be an emitting state with count_inc 1, otherwise
+ * STRQ_ERR_ARG.  The per-state increments are a device array of the model's own (uint64: 1 << 21 j for tract j); state_tag and
+ * count_inc keep their meaning, every other decode of the model is unchanged.  Waits for detect sub-batches in flight.
+ */
+int strq_model_set_tracts(strq_ctx* ctx, int32_t model_id, int32_t n_tracts, const int32_t* tract_of);
+/*
+ * The tract decode of n_seq float64 windows as they are given (x_off[n_seq + 1], at most 8192 windows, offsets must not decrease):
+ * strq_viterbi's best path -- the same log-probability bits and tie-breaks, the count decode of the model's lane row or of the
+ * general kernel with a 64-bit payload of three 21-bit counters -- with
+ *   logp            log-probability of the best path (-inf without one)
+ *   counts[3 i + j] emissions of the states of tract j on the best path of window i (0 beyond n_tracts, without a path, and
+ *                   for a window that was not decoded); no bias applied
+ *   status          0 ok, 1 no path, 2 a window of 2^21 observations or more: the counters could carry into each other, the
+ *                   window is not decoded
+ * Never the register-resident kernel (its image has one loop).  STRQ_ERR_ARG for a model without tracts.
+ */
+int strq_viterbi_tracts(strq_ctx* ctx, int32_t model_id, int64_t n_seq, const double* x, const int64_t* x_off,
+                        double* logp, int64_t* counts, int32_t* status);
+/* Test hook: the kernel shape id (as strq_debug_viterbi_plan gives it) of the context's last tract launch; -1 before the first. */
+int strq_debug_tract_shape(const strq_ctx* ctx, int32_t* shape);
 
 /*
  * ---- repeatCounter.add_target / detect (scripts/STRique.py:553-618) as one device pipeline ----
@@ -417,6 +440,37 @@ int strq_batch_fetch_anchored_mod(strq_ctx* ctx, int32_t* called, int64_t* off, 
 /* The calls of the last run call: out[0] = ms on the GPU (all its sub-batches: tasks, compaction, decode, patterns, scores),
  * out[1] = reads called, out[2] = units (characters '0' / '1'), out[3] = kernels launched (0 with the switch off). */
 int strq_last_anchored_mod(strq_ctx* ctx, double* out4);
+/* ---- tracts: per-tract unit counts for compound repeat loci (no counterpart in the reference, whose flankedRepeatHMM,
+ * STRique.py:384-431, has one repeat loop) ----
+ * A target may hold a compound model beside its flanked one: K = 2 or 3 repeat loops in a fixed order with profiles between them
+ * (strq_model_create + strq_model_set_tracts; strique_amd/tracts.py states the rule).  With the switch on, every read whose gate
+ * passed, that could be normalised, whose flanked decode found a path and whose target has a compound model is decoded once more on
+ * the window of the count decode -- [prefix_begin, suffix_end) of the filtered signal under the read's conditioning record -- with
+ * the tract decode of strq_viterbi_tracts: count[j] = emissions of the counted states of tract j on the best path + bias[j], in model
+ * order; log_p the log-probability of that path.  Limits: K <= 3, windows below 2^21 samples, tracts in a fixed order, every tract
+ * at least bias[j] + 1 units long (each loop is passed once), one compound model per target, no anchored reads, no scan. */
+typedef struct strq_tracts {
+    int32_t status;         /* 0 decoded, 1 not decoded (gate failed, read not normalised, no path in the flanked decode, target without
+                             * tracts), 2 window of 2^21 samples or more, 3 no path in the compound model; 1 .. 3: the fields below are zero */
+    int32_t n_tracts;
+    int32_t count[3];       /* model order, bias applied; zero beyond n_tracts */
+    int32_t pad_;
+    double log_p;
+} strq_tracts;
+/* The compound model of a target and the biases of its tracts (bias[j] read for j < n_tracts).  model_id = -1 takes it away.
+ * STRQ_ERR_ARG for a model without tracts or with another number of them (strq_model_set_tracts), STRQ_ERR_UNSUPPORTED for a model
+ * no compiled Viterbi kernel takes; the target stays as it was.  Never in the middle of a batch: sub-batches in flight are taken first. */
+int strq_target_set_tracts(strq_ctx* ctx, int32_t target_id, int32_t model_id, int32_t n_tracts, const int32_t bias[3]);
+/* on = 1: later run calls run the tract pass behind the rows, where the forward pass of strq_set_confidence runs: a task kernel writes
+ * the windows on the device, one decode launch per kernel instance in use.  Rows and every other output do not change.  A run call
+ * with the switch on fails before any launch (STRQ_ERR_ARG) when it is a scan.  Sub-batches still in flight keep the mode they were
+ * launched with (the call waits for them).  Default 0: no further kernel runs and no further buffer is reserved. */
+int strq_set_tracts(strq_ctx* ctx, int32_t on);
+/* One record per read of the last batch (n = its reads).  STRQ_ERR_ARG when the last run call ran with the switch off. */
+int strq_batch_fetch_tracts(strq_ctx* ctx, strq_tracts* out, int64_t n);
+/* The tract pass of the last run call: out[0] = ms on the GPU (all its sub-batches), out[1] = windows decoded (status 0),
+ * out[2] = kernels launched (tasks, sorts and decodes; 0 with the switch off), out[3] = windows with status 2 or 3. */
+int strq_last_tracts(strq_ctx* ctx, double* out4);
 /* ---- renorm: a second normalisation step for reads that are mostly repeat (no counterpart in the reference, whose 'minmax' map,
  * STRique.py:150-180, assumes that a read's k-mer composition looks like the pore model's) ----
  * Between the conditioning statistics and the flank alignments, every conditioned read of a target with tables gets scale and shift

@@ -24,6 +24,7 @@ import numpy as np
 from . import anchored as anchored_mod
 from . import renorm as renorm_mod
 from . import scan as scan_mod
+from . import tracts as tracts_mod
 from .counter import Detected
 
 HEADER = ['ID', 'target', 'strand', 'count', 'score_prefix', 'score_suffix', 'log_p', 'offset', 'ticks', 'mod']
@@ -252,6 +253,11 @@ def count(argv):
                                                                            "corrected for them, to FILE: one row per count row, columns " + " ".join(VARIANTS_HEADER) +
                                                                            " (calls: index:unit:sample:llr per alt call -- its index in pattern, the unit as configured, the raw "
                                                                            "sample behind it, the log-likelihood ratio of the best alt branch over the repeat unit)")
+    parser.add_argument("--tract-units", dest="tract_units", default=None, metavar="FILE", help="Compound repeat loci -- several tracts in a fixed order, as (CAG)n CAACAG (CCG)m: a TSV "
+                                                                                              "of target<TAB>U0,U1[,U2][<TAB>L0[,L1]] (2 or 3 units and the linkers between them on the + "
+                                                                                              "strand; - or no third column: empty linkers; # comments and blank lines allowed)")
+    parser.add_argument("--tracts", default=None, metavar="FILE", help="With --tract-units: also write the unit count of every tract of a read to FILE: one row per count row, "
+                                                                       "columns " + " ".join(tracts_mod.HEADER) + " (counts in the configured order, joined by commas)")
     parser.add_argument("--scan", action="store_true", help="No alignment: every read of the index is compared with every target of the repeat config on both strands, "
                                                              "from its raw signal alone, and counted for the one it spans (if any).  Excludes --algn; stdin is not read")
     parser.add_argument("--scan-min-score", type=float, default=None, metavar="X", help="--scan: the smallest min(score_prefix, score_suffix) a target and strand needs to be "
@@ -286,6 +292,10 @@ def count(argv):
         parser.error("--variants needs --alt-units FILE: the units to tell from the repeat unit")
     if args.variants and args.scan:
         parser.error("--variants cannot be combined with --scan: the variant pass runs on reads whose target and strand an alignment gives")
+    if bool(args.tracts) != bool(args.tract_units):
+        parser.error("--tract-units FILE and --tracts FILE need each other: the definitions, and where the counts go")
+    if args.tracts and args.scan:
+        parser.error("--tracts cannot be combined with --scan: the tract pass runs on reads whose target and strand an alignment gives")
     if args.scan and args.algn:
         parser.error("--scan takes the target and strand of a read from its signal: it cannot be combined with --algn")
     if not args.scan and (args.scan_scores or args.scan_min_score is not None):
@@ -328,6 +338,17 @@ def count(argv):
             log("Main: %s" % e, 'error'); raise SystemExit(1)
         if args.variants and not alt_units:
             log("Main: --variants: the alt-units file names no unit.", 'error'); raise SystemExit(1)
+    tract_defs = {}
+    if args.tract_units:
+        if not os.path.isfile(args.tract_units):
+            log("Main: Tract-units file does not exist.", 'error'); raise SystemExit(1)
+        try:
+            with open(args.tract_units) as fp:
+                tract_defs = tracts_mod.parse_definitions(fp, set(config['repeat']))
+        except ValueError as e:
+            log("Main: %s" % e, 'error'); raise SystemExit(1)
+        if not tract_defs:
+            log("Main: --tracts: the tract-units file defines no target.", 'error'); raise SystemExit(1)
     for path, what in ((args.f5Index, "Fast5 index file"), (args.model, "Pore model file")):
         if not os.path.isfile(path):
             log("Main: %s does not exist." % what, 'error'); raise SystemExit(1)
@@ -353,7 +374,8 @@ def count(argv):
     loci = defaultdict(list)
     for name, (chrom, begin, end, repeat, prefix, suffix) in config['repeat'].items():
         try:
-            counter.add_target(name, repeat, prefix, suffix, **({'alt_units': alt_units[name]} if name in alt_units else {}))
+            counter.add_target(name, repeat, prefix, suffix, **({'alt_units': alt_units[name]} if name in alt_units else {}),
+                               **({'tracts': tract_defs[name]} if name in tract_defs else {}))
         except ValueError:
             raise
         except Exception as e:                # e.g. a flank longer than the compiled kernel shapes cover
@@ -384,7 +406,7 @@ def count(argv):
     stats = {}
     fault = 0
     paths = dict(units=args.units, confidence=args.confidence, mod_llr=args.mod_llr, scores=args.scan_scores, anchored=args.anchored, variants=args.variants,
-                 renorm=args.renorm_out, anchored_mod=args.anchored_mod)
+                 renorm=args.renorm_out, anchored_mod=args.anchored_mod, tracts=args.tracts)
     with contextlib.ExitStack() as stack:
         # rank 0 writes: as the batches are done in a single process (run_count), after the gather otherwise
         files = {name: stack.enter_context(open(path, 'w')) if (path and rank == 0) else None for name, path in paths.items()}
@@ -397,7 +419,7 @@ def count(argv):
                              anchored=args.anchored_min_score, anchored_out=now['anchored'],
                              anchored_mod=bool(args.anchored_mod), anchored_mod_out=now['anchored_mod'],
                              variants=alt_units if args.variants else None, variants_out=now['variants'],
-                             renorm=args.renorm, renorm_out=now['renorm'])
+                             renorm=args.renorm, renorm_out=now['renorm'], tracts=bool(args.tracts), tracts_out=now['tracts'])
         except DeviceFault:
             if world == 1:
                 raise SystemExit(3)
@@ -412,7 +434,8 @@ def count(argv):
                 dist.destroy_process_group()
                 raise SystemExit(3)
             merged = gather_rows(rows, stats["items"], sdist, units=bool(args.units), scan=scan, confidence=bool(args.confidence), mod_llr=bool(args.mod_llr),
-                                 anchored=bool(args.anchored), variants=bool(args.variants), renorm=args.renorm is not None, anchored_mod=bool(args.anchored_mod))
+                                 anchored=bool(args.anchored), variants=bool(args.variants), renorm=args.renorm is not None, anchored_mod=bool(args.anchored_mod),
+                                 tracts=bool(args.tracts))
             if rank == 0:
                 write_rows(out, merged.rows)
                 for o in OUTPUTS:
@@ -635,15 +658,28 @@ OUTPUTS = (
            lambda v: renorm_mod.pack(v), lambda text: renorm_mod.unpack(text), 'renorm_rows', False),
     Output('variants', lambda scan: VARIANTS_HEADER, lambda q, t, s, row, v: format_variants(q, t, s, row[0], v),
            lambda v: _pack_variants(v), lambda text: _unpack_variants(text), 'variant_rows', False),
+    Output('tracts', lambda scan: tracts_mod.HEADER, lambda q, t, s, row, v: tracts_mod.format_row(q, t, s, row[0], v),
+           lambda v: _pack_tracts(v), lambda text: _unpack_tracts(text), 'tract_rows', False),
     Output('anchored_mod', lambda scan: anchored_mod.MOD_HEADER, lambda q, t, s, row, v: anchored_mod.format_mod_row(q, t, s, *(v or (None, None))),
            lambda v: _pack_anchored_mod(v), lambda text: _unpack_anchored_mod(text), 'anchored_mod_rows', False),
     Output('anchored', lambda scan: anchored_mod.HEADER, lambda q, t, s, row, v: anchored_mod.format_row(q, t, s, v),
            lambda v: _pack_anchored(v), lambda text: _unpack_anchored(text), 'anchored_rows', False),
 )
-# (`renorm`, `variants`, `anchored_mod` and `anchored`, the last fields, default to None: callers that build a Merged from the five values
-# before them keep working.  `anchored` stays the last field, as it did when `variants` and `anchored_mod` came in: fields behind the first
-# five are taken by name.)
-Merged = namedtuple('Merged', ['rows'] + [o.name for o in OUTPUTS], defaults=(None, None, None, None))
+# (`renorm`, `variants`, `tracts`, `anchored_mod` and `anchored`, the last fields, default to None: callers that build a Merged from the five
+# values before them keep working.  `anchored` stays the last field, as it did when `variants`, `anchored_mod` and `tracts` came in: fields
+# behind the first five are taken by name.)
+Merged = namedtuple('Merged', ['rows'] + [o.name for o in OUTPUTS], defaults=(None, None, None, None, None))
+
+
+def _pack_tracts(v):
+    """(counts, log_p) of a read as it travels between ranks: the log-probability as repr(), which float() reads back bit for bit."""
+    counts, log_p = v
+    return ','.join(str(int(c)) for c in counts) + ';' + repr(float(log_p))
+
+
+def _unpack_tracts(text):
+    counts, log_p = text.split(';')
+    return tuple(int(c) for c in counts.split(',')), float(log_p)
 
 
 def _pack_anchored_mod(v):
@@ -674,7 +710,7 @@ def _unpack_anchored(text):
 
 
 def outputs_on(**flags):
-    """The entries of OUTPUTS whose flag (units=, confidence=, mod_llr=, scores=, anchored=, variants=, renorm=, anchored_mod=) is set."""
+    """The entries of OUTPUTS whose flag (units=, confidence=, mod_llr=, scores=, anchored=, variants=, renorm=, anchored_mod=, tracts=) is set."""
     return [o for o in OUTPUTS if flags.get(o.name)]
 
 
@@ -695,7 +731,8 @@ def _read_values(target, strand, det, scores=None):
     if det is None:
         return target, strand, None, dict(scores=scores)
     return target, strand, det.row, dict(units=det.units, confidence=det.conf, mod_llr=det.llr, scores=scores, anchored=det.anchored, variants=det.variants,
-                                         renorm=getattr(det, 'renorm', None), anchored_mod=(det.anchored, getattr(det, 'anchored_mod', None)))
+                                         renorm=getattr(det, 'renorm', None), anchored_mod=(det.anchored, getattr(det, 'anchored_mod', None)),
+                                         tracts=getattr(det, 'tracts', None))
 
 
 def _emit(sink, on, seq, qname, target, strand, row, values):
@@ -729,14 +766,15 @@ def unpack_blob(on, blob):
     return fields[0], fields[1], fields[2], values
 
 
-def gather_rows(rows, items, sdist, units=False, scan=None, confidence=False, mod_llr=False, anchored=False, variants=False, renorm=False, anchored_mod=False):
+def gather_rows(rows, items, sdist, units=False, scan=None, confidence=False, mod_llr=False, anchored=False, variants=False, renorm=False, anchored_mod=False,
+                tracts=False):
     """Reads of this rank (run_count with world > 1) -> fixed-size records + one blob per read (pack_blob) -> one gather -> on rank 0
-    the rows of every file in input order: Merged(rows, units, confidence, mod_llr, scores, renorm, variants, anchored_mod, anchored), [(sequence number, TSV row)] each, None
+    the rows of every file in input order: Merged(rows, units, confidence, mod_llr, scores, renorm, variants, tracts, anchored_mod, anchored), [(sequence number, TSV row)] each, None
     for an output that was not asked for (scores: asked for by scan) and for every field off rank 0.  `items`: every accepted (qname,
     strand, target) of the input, which each rank derives from the same SAM file (scan: from the same index).  A read that failed
     travels as a record with valid = 0 and writes nothing; a scan read without a winner as one with valid = 2: it writes a score row."""
     on = outputs_on(units=units, confidence=confidence, mod_llr=mod_llr, scores=bool(scan), anchored=anchored, variants=variants, renorm=renorm,
-                    anchored_mod=anchored_mod)
+                    anchored_mod=anchored_mod, tracts=tracts)
     rec = np.zeros(len(rows), ROW_DTYPE); blobs = []; idx = np.zeros(len(rows), np.int64)
     for k, (seq, read) in enumerate(rows):
         idx[k] = seq
@@ -793,7 +831,7 @@ def route(stream, loci, log):
 
 def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, out=None, readers=0, stats=None, units=False, units_out=None,
               scan=None, scores_out=None, confidence=False, conf_out=None, mod_llr=False, llr_out=None, anchored=None, anchored_out=None,
-              variants=None, variants_out=None, renorm=None, renorm_out=None, anchored_mod=False, anchored_mod_out=None):
+              variants=None, variants_out=None, renorm=None, renorm_out=None, anchored_mod=False, anchored_mod_out=None, tracts=False, tracts_out=None):
     """Route the SAM records of `stream` to their targets, run this rank's share through
     `counter.detect_batch` and return [(sequence number, TSV row or -- several ranks -- what gather_rows takes)].
 
@@ -821,6 +859,9 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
     `renorm` (a share threshold inside (0, 1), not with scan): the second normalisation step is on for this run
     (counter.set_renorm(threshold)) and the counter is asked for Detected records; the fit of every read (strique_amd.renorm.report,
     format_row) goes to `renorm_out` and to stats["renorm_rows"].  The count rows of the reads it applies to change.
+    `tracts` (not with scan; the counter's targets were added with their compound definitions): the tract pass is on for this run
+    (counter.set_tracts(True)) and the counter is asked for Detected records; their rows (strique_amd.tracts.format_row) go to
+    `tracts_out` and to stats["tract_rows"].  The count rows and the other files do not change.
     `scan` ({"min_score", "candidates", "scores"}): `stream` is a list of read ids instead of a SAM stream; every read goes through
     counter.scan_batch and takes target and strand from its winner -- a read without one writes no row, as a read without a target
     writes none; single process: the score rows (strique_amd.scan.format_scores, every read) go to `scores_out` and to
@@ -838,19 +879,21 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
         raise ValueError("variants cannot be combined with a scan")
     if renorm is not None and scan:
         raise ValueError("renorm cannot be combined with a scan")
+    if tracts and scan:
+        raise ValueError("tracts cannot be combined with a scan")
     if renorm is not None and not 0 < renorm < 1:
         raise ValueError("the renorm share threshold must be inside (0, 1)")
     files = dict(rows=out, units=units_out, confidence=conf_out, mod_llr=llr_out, scores=scores_out, anchored=anchored_out, variants=variants_out,
-                 renorm=renorm_out, anchored_mod=anchored_mod_out)
+                 renorm=renorm_out, anchored_mod=anchored_mod_out, tracts=tracts_out)
     on = outputs_on(units=units, confidence=confidence, mod_llr=mod_llr, scores=scan and scan["scores"], anchored=anchored is not None,
-                    variants=variants is not None, renorm=renorm is not None, anchored_mod=anchored_mod)
+                    variants=variants is not None, renorm=renorm is not None, anchored_mod=anchored_mod, tracts=tracts)
     if out is not None:
         print('\t'.join(HEADER), file=out)
     for o in OUTPUTS:
         stats.setdefault(o.stat, [])
         if files[o.name] is not None:
             print('\t'.join(o.header(scan)), file=files[o.name])
-    extras = {o.name: True for o in on if o.name not in ('scores', 'anchored', 'variants', 'renorm', 'anchored_mod')}
+    extras = {o.name: True for o in on if o.name not in ('scores', 'anchored', 'variants', 'renorm', 'anchored_mod', 'tracts')}
     if anchored is not None:
         extras.update(anchored=anchored, records=True)
     if anchored_mod:
@@ -860,6 +903,9 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
         extras.update(records=True)
     if renorm is not None:
         counter.set_renorm(renorm)
+        extras.update(records=True)
+    if tracts:
+        counter.set_tracts(True)
         extras.update(records=True)
     rows = []
     records = ((rid, '.', ['.'], 0) for rid in stream) if scan else route(stream, loci, log)
@@ -1049,6 +1095,8 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
                 counter.set_variants(False)          # the switch belongs to this run
             if renorm is not None:
                 counter.set_renorm(None)
+            if tracts:
+                counter.set_tracts(False)
         else:
             # an exception is on its way out (a DeviceFault from the engine thread, a broken input): the batch queued behind
             # the failed one must not be handed to a device that may be hung, and nobody waits for it -- the caller exits,

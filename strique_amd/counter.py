@@ -18,6 +18,7 @@ from . import anchored as anchored_mod
 from . import ffi
 from . import hmm as hmm_mod
 from . import renorm as renorm_mod
+from . import tracts as tracts_mod
 from .pore_model import pore_model
 
 ALIGN_DEFAULTS = {'dist_offset': 16.0, 'dist_min': 0.0, 'gap_open_h': -1.0, 'gap_open_v': -16.0,
@@ -39,7 +40,9 @@ target_classifier = namedtuple('target_classifier',
 # variants: (count_v, pattern, branch, end, V) of the variant pass, see repeatCounter.detect_batch
 # renorm: (applied, {signal: None or (a, b, w, score)}) of the second normalisation step, see repeatCounter.set_renorm
 # anchored_mod: None or (pattern, llr) -- the methylation call of an anchored read, see repeatCounter.set_anchored_mod
-Detected = namedtuple('Detected', ['row', 'units', 'conf', 'llr', 'anchored', 'variants', 'renorm', 'anchored_mod'], defaults=(None, None, None, None))
+# tracts: None or (counts in configured order, log_p) of the compound model, see repeatCounter.set_tracts
+Detected = namedtuple('Detected', ['row', 'units', 'conf', 'llr', 'anchored', 'variants', 'renorm', 'anchored_mod', 'tracts'],
+                      defaults=(None, None, None, None, None))
 
 
 class repeatCounter(object):
@@ -71,6 +74,11 @@ class repeatCounter(object):
         self.variants = False          # set_variants
         self.renorm = None             # set_renorm: min_share, or None
         self.anchored_mod = False      # set_anchored_mod
+        # tracts: (units, linkers, prefix, suffix) as the strand reads them, of the classifiers of a target added with a compound
+        # definition, and the classifiers whose compound model is registered ({target_id: (CompoundRepeatModel, strand)}); baked on first use
+        self._tract_src = {}
+        self.tract_models = {}
+        self.tracts = False            # set_tracts
         self._renorm_done = set()      # classifiers whose tables are registered
 
     # -------------------------------------------------------------------------------------
@@ -129,6 +137,28 @@ class repeatCounter(object):
         if refused is not None:
             raise refused
 
+    def _ensure_tracts(self):
+        """The compound model of every classifier with a tract definition that has none yet: baked, uploaded and registered."""
+        for tid, (strand, units, linkers, prefix, suffix) in self._tract_src.items():
+            if tid in self.tract_models:
+                continue
+            m = hmm_mod.CompoundRepeatModel(units, linkers, prefix, suffix, self.pm, self.HMM_config)
+            m.model_id = self.ctx.model_create(m.baked)
+            self.ctx.model_set_tracts(m.model_id, m.n_tracts, m.tract_of)
+            self.ctx.target_set_tracts(tid, m.model_id, m.n_tracts, m.count_bias)
+            self.tract_models[tid] = (m, strand)
+
+    def set_tracts(self, on):
+        """on: detect and detect_batch also decode the compound model of every read of a target added with tracts=(units, linkers)
+        (strique_amd.tracts states the rule) and report one more element per read, behind all others: None -- the read was not
+        decoded, its window has 2^21 samples or more, the compound model found no path, or its target has no tracts -- or (counts,
+        log_p): the unit count of every tract in the order the definition was configured in, on either strand, and the
+        log-probability of the compound model's best path.  records=True: Detected.tracts.  A switch of the counter, like
+        set_variants.  ValueError when no target was added with tracts.  Not with scan_batch."""
+        if on and not self._tract_src:
+            raise ValueError("RepeatCounter: tracts needs a target added with tracts=(units, linkers).")
+        self.tracts = bool(on)
+
     def _ensure_renorm(self):
         """The tables of the second normalisation step for every classifier that has none yet (strique_amd.renorm.tables)."""
         for tid, (repeat, _, _) in self._anchored_src.items():
@@ -176,12 +206,16 @@ class repeatCounter(object):
             raise ValueError("RepeatCounter: variants needs a target added with alt_units.")
         self.variants = bool(on)
 
-    def add_target(self, target_name, repeat, prefix, suffix, alt_units=None):
+    def add_target(self, target_name, repeat, prefix, suffix, alt_units=None, tracts=None):
         """alt_units: 1 to 3 sequence variants of the repeat unit (on the + strand, as `repeat`) that detect
-        tells from it once set_variants(True) is called; ValueError for units hmm.check_alt_units does not take."""
+        tells from it once set_variants(True) is called; ValueError for units hmm.check_alt_units does not take.
+        tracts: (units, linkers), the compound definition of the locus on the + strand (strique_amd.tracts: 2 or 3 units, one linker
+        -- possibly empty -- between neighbours), counted per tract once set_tracts(True) is called; ValueError for what
+        tracts.check does not take.  `repeat` stays the unit of the count row."""
         if target_name in self.targets:
             raise ValueError("RepeatCounter: Target with name " + str(target_name) + " already defined.")
         alts = hmm_mod.check_alt_units(repeat, alt_units) if alt_units else None
+        tract_def = tracts_mod.check(*tracts) if tracts else None
         prefix_ext = prefix.upper(); prefix = prefix[-50:].upper()            # STRique.py:555-559
         suffix_ext = suffix.upper(); suffix = suffix[:50].upper()
         repeat = repeat.upper()
@@ -194,6 +228,10 @@ class repeatCounter(object):
             # the - strand reads the reverse complement of unit and alt units; calls are reported with the number of the unit as configured
             self._variant_src[tc_plus.target_id] = (repeat, alts)
             self._variant_src[tc_minus.target_id] = (rc(repeat), [rc(a) for a in alts])
+        if tract_def:
+            # the - strand reads the reverse complements in reverse order; counts are reported in the configured order
+            self._tract_src[tc_plus.target_id] = ('+',) + tracts_mod.strand_definition(*tract_def, '+') + (prefix, suffix)
+            self._tract_src[tc_minus.target_id] = ('-',) + tracts_mod.strand_definition(*tract_def, '-') + (rc(suffix), rc(prefix))
 
     def _classifier_for(self, target_name, strand):
         if target_name not in self.targets:
@@ -235,7 +273,8 @@ class repeatCounter(object):
         count_v = len(pattern) + count_bias is an estimate on the scale of the tuple's count, not equal to it in general.
         With set_anchored_mod(True) and anchored=m: the methylation call of the read, (pattern, llr) or None, directly behind the
         anchored element -- see set_anchored_mod.
-        Order of the elements: (tuple[, positions][, conf][, llr][, anchored][, anchored_mod][, variants]); without any of them the bare tuple.
+        With set_tracts(True) (a counter with a target added with tracts=): one last element, None or (counts, log_p) -- see set_tracts.
+        Order of the elements: (tuple[, positions][, conf][, llr][, anchored][, anchored_mod][, variants][, tracts]); without any of them the bare tuple.
         records=True: a list of Detected records instead (the fields that were not asked for None; `anchored` the record of every
         read, whatever its kind: (kind number, status, count, log_p, begin, end, free_samples))."""
         items = list(items)
@@ -246,10 +285,11 @@ class repeatCounter(object):
         if self.anchored_mod and anchored is None:
             raise ValueError("RepeatCounter: anchored_mod needs anchored=m (the calls hang on the anchored records).")
         variants = self.variants
+        tracts = self.tracts
         reads = [(self._classifier_for(t, s).target_id, r) for t, r, s in items]
         out = [None] * len(items)
         for i, d, _, _ in self._run(reads, units=units, confidence=confidence, mod_llr=mod_llr, anchored=anchored, variants=variants, renorm=self.renorm,
-                                    anchored_mod=self.anchored_mod):
+                                    anchored_mod=self.anchored_mod, tracts=tracts):
             if records:
                 out[i] = d
                 continue
@@ -261,11 +301,13 @@ class repeatCounter(object):
                 extra += (d.anchored_mod,)
             if variants:
                 extra += (d.variants,)
+            if tracts:
+                extra += (d.tracts,)
             out[i] = (d.row,) + extra if extra else d.row
         return out
 
     @contextlib.contextmanager
-    def _switches(self, units, confidence, mod_llr, anchored=None, variants=False, renorm=None, anchored_mod=False):
+    def _switches(self, units, confidence, mod_llr, anchored=None, variants=False, renorm=None, anchored_mod=False, tracts=False):
         """The optional passes that were asked for are on inside the block, and all of them off after it."""
         try:
             if anchored is not None:
@@ -287,8 +329,12 @@ class repeatCounter(object):
             if renorm is not None:
                 self._ensure_renorm()
                 self.ctx.set_renorm(True, renorm)
+            if tracts:
+                self._ensure_tracts()
+                self.ctx.set_tracts(True)
             yield
         finally:
+            self.ctx.set_tracts(False)
             self.ctx.set_renorm(False)
             self.ctx.set_variants(False)
             self.ctx.set_anchored_mod(False)
@@ -297,7 +343,7 @@ class repeatCounter(object):
             self.ctx.set_units(False)
             self.ctx.set_confidence(False)
 
-    def _run(self, reads, units=False, confidence=False, mod_llr=False, scan=None, anchored=None, variants=False, renorm=None, anchored_mod=False):
+    def _run(self, reads, units=False, confidence=False, mod_llr=False, scan=None, anchored=None, variants=False, renorm=None, anchored_mod=False, tracts=False):
         """reads: [(target_id, raw_signal)] through the context.  Yields (position in `reads`, Detected, winner, scores) per read, the
         fields of Detected that were not asked for being None.  scan=(candidate target ids, min_score): the target ids of the reads
         are ignored, every read is compared with every candidate (Context.scan_batch_reads); winner is its position in the candidate
@@ -311,7 +357,7 @@ class repeatCounter(object):
             if not idx:
                 continue
             arrs = [sigs[i].astype(np.int16 if want_int else np.float64, copy=False) for i in idx]
-            with self._switches(units, confidence, mod_llr, anchored, variants, renorm, anchored_mod):
+            with self._switches(units, confidence, mod_llr, anchored, variants, renorm, anchored_mod, tracts):
                 if scan is None:
                     res = self.ctx.detect_batch_reads(arrs, [reads[i][0] for i in idx])      # one pointer per read: no host-side concatenation
                     win = sc = [None] * len(res)
@@ -341,10 +387,19 @@ class repeatCounter(object):
                 am = [None] * len(res)
                 if anchored_mod:
                     am = [None if x is None else (x[0], None if x[1] is None else x[1][:, 1] - x[1][:, 0]) for x in self.ctx.batch_fetch_anchored_mod()]
-            for i, r, m, u, cf, v, w, s, a, vr, rnr, amr in zip(idx, res, mods, pos, conf, vs, win, sc, an, var, rn, am):
+                tr = [None] * len(res)
+                if tracts:
+                    tr = []
+                    for i, t in zip(idx, self.ctx.batch_fetch_tracts()):
+                        rec = None
+                        if int(t['status']) == 0:
+                            strand = self.tract_models[reads[i][0]][1]
+                            rec = (tracts_mod.configured_order([int(c) for c in t['count'][:int(t['n_tracts'])]], strand), float(t['log_p']))
+                        tr.append(rec)
+            for i, r, m, u, cf, v, w, s, a, vr, rnr, amr, trr in zip(idx, res, mods, pos, conf, vs, win, sc, an, var, rn, am, tr):
                 n = int(r['count']); p = float(r['log_p']) if n or r['log_p'] != 0 else 0
                 row = (n, float(r['score_prefix']), float(r['score_suffix']), p, int(r['offset']), int(r['ticks']), m)
-                yield i, Detected(row, u, cf, None if v is None else v[:, 1] - v[:, 0], a, vr, rnr, amr), w, s
+                yield i, Detected(row, u, cf, None if v is None else v[:, 1] - v[:, 0], a, vr, rnr, amr, trr), w, s
 
     def candidates(self, targets=None):
         """[(target_name, strand)] of a scan: every target added (or the named ones), in add_target order, '+' before '-'."""
@@ -366,6 +421,8 @@ class repeatCounter(object):
         [n_reads, n_candidates, 2] of score_prefix, score_suffix of every candidate)."""
         if self.renorm is not None:
             raise ValueError("RepeatCounter: renorm is not available in a scan (set_renorm(None) first).")
+        if self.tracts:
+            raise ValueError("RepeatCounter: tracts are not available in a scan (set_tracts(False) first).")
         if min_score is None:
             raise ValueError("RepeatCounter: scan_batch needs min_score (there is no default: see README, 'Scan').")
         if not min_score > 0:

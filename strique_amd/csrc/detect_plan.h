@@ -35,7 +35,9 @@ struct Carve {
 // The variant pass (strq_set_variants) is the fifth.
 // Renorm (strq_set_renorm) is the sixth, in front of the alignments instead of behind the decode: it comes with its share threshold.
 // Methylation calls of anchored reads (strq_set_anchored_mod) are the seventh: behind the anchored decode, which they need.
-struct Extras { bool units = false, conf = false, llr = false, anch = false, var = false; double anch_min = 0.0; bool renorm = false; double renorm_min = 0.0; bool amod = false; };
+// The tract pass (strq_set_tracts) is the eighth: where the forward pass runs, behind the rows.
+struct Extras { bool units = false, conf = false, llr = false, anch = false, var = false; double anch_min = 0.0; bool renorm = false; double renorm_min = 0.0; bool amod = false;
+                bool tracts = false; };
 
 // What the variant pass leaves per read: the passages of its variant-model decode (strq_batch_fetch_variants)
 struct VariantRow {
@@ -71,8 +73,12 @@ struct ReadRows {
         anch.assign(m, strq_anchored());
         amod_called.clear(); amod.clear(); amod_llr.clear();
         var.assign(m, VariantRow());
-        renorm.clear();
+        renorm.clear(); tracts.clear();
     }
+    std::vector<strq_tracts> tracts;              // per-tract counts of the compound model (strq_batch_fetch_tracts); status 1: not decoded.  Empty
+                                                  // until a run call with the switch on sizes it (size_tracts)
+    static strq_tracts no_tracts() { strq_tracts t = strq_tracts(); t.status = 1; return t; }
+    void size_tracts() { if (tracts.size() != results.size()) tracts.assign(results.size(), no_tracts()); }
     void size_renorm() { if (renorm.size() != results.size()) renorm.assign(results.size(), strq_renorm()); }
     void size_amod()
     {
@@ -91,6 +97,7 @@ struct ReadRows {
         if (r < amod_called.size()) { amod_called[r] = 0; amod[r].clear(); amod_llr[r].clear(); }
         var[r] = VariantRow();
         if (r < renorm.size()) renorm[r] = strq_renorm();
+        if (r < tracts.size()) tracts[r] = no_tracts();
     }
 };
 

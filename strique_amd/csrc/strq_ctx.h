@@ -112,6 +112,9 @@ struct HostModel {
     DevBuf var_blob;
     const VarModel* var_dev = nullptr;
     int32_t var_mode = -1, var_nb = 0;
+    // tract decodes (strq_model_set_tracts): the per-state increments behind VitModel::tract_inc
+    DevBuf tract_blob;
+    int32_t n_tracts = 0;
 };
 
 }  // namespace strq
@@ -134,6 +137,7 @@ struct strq_ctx {
     double counters[8] = {};
     int32_t geometry[8] = {};                 // strq_last_geometry
     int32_t vit_launches[4] = {};             // strq_last_viterbi_launches
+    int32_t tract_shape_last = -1;            // strq_debug_tract_shape: kernel shape of the last tract launch
     int64_t second_round[2] = {};             // strq_last_second_round: alignments that ran the second forward round / alignments, last batched call
     strq::DevBuf redo_total;                  // device counter: alignments whose first forward round missed its certificate (second look + whole-read second round)
     int64_t look2_served = 0;                 // of them, resolved by the coarse screen's second look (or dropped with an attempt that started over): not whole-read reruns

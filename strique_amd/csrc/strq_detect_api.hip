@@ -25,6 +25,7 @@
 #include "forward_kernels.h"
 #include "scan_kernels.h"
 #include "anchored_kernels.h"
+#include "tract_kernels.h"
 #include "renorm_kernels.h"
 #include "variant_kernels.h"
 
@@ -76,6 +77,7 @@ struct Target {
     int end_model_id = -1, end_bias = 0, start_model_id = -1, start_bias = 0;      // strq_target_set_anchored: both models or none
     int var_model_id = -1, var_nalt = 0, var_ctx = 0; double var_lo = 0, var_hi = 0;      // strq_target_set_variants
     const RenormTable* rn_dev = nullptr;      // strq_target_set_renorm: the tables of the target on the device (DetectState::rn_tables owns them)
+    int tract_model_id = -1, n_tracts = 0, tract_bias[3] = {0, 0, 0};      // strq_target_set_tracts
 };
 
 struct Batch : ReadRows {
@@ -122,6 +124,8 @@ struct DetectState {
     float llr_ms = 0; double llr_units = 0, llr_reads = 0, llr_launches = 0;      // strq_last_mod_llr: the last run call's scoring pass
     DevBuf conf_task;                    // forward pass (run_conf_pass): tasks, model images, c0, results, order
     float conf_ms = 0; double conf_windows = 0, conf_nopath = 0, conf_expo = 0;      // strq_last_confidence: the last run call's forward pass
+    DevBuf tract_ws, tract_task;         // tract pass (run_tract_pass): geometry and conditioning rows of a sub-batch; tasks, results, their reads and models
+    float tract_ms = 0; double tract_windows = 0, tract_launches = 0, tract_failed = 0;      // strq_last_tracts: the last run call's tract pass
     DevBuf anch_ws, anch_task;           // anchored pass (run_anchored_pass): geometry, conditioning rows and kinds of a sub-batch; tasks, results, their reads and models
     float anch_ms = 0; double anch_kinds[4] = {}, anch_launches = 0, anch_g2 = 0, anch_lane = 0;      // strq_last_anchored: the last run call's anchored pass
     hipEvent_t amod_ev[2] = {};          // methylation calls of anchored reads (run_anchored_mod): their own bracket, inside the anchored pass
@@ -252,9 +256,9 @@ static int sort_viterbi_group(strq_ctx* c, hipStream_t st, const VitGroup& g, co
 }
 // ... then the persistent launch in decode mode `mode` on queue head `queue` (`what`: who says that the shape has no such mode)
 static int launch_viterbi_group(strq_ctx* c, hipStream_t st, const VitGroup& g, const VitTask* tasks, VitResult* results, int* order, int* queue,
-                                VitMode mode, int waves_hint = 0, const char* what = "viterbi: ")
+                                VitMode mode, int waves_hint = 0, const char* what = "viterbi: ", bool tracts = false)
 {
-    const int vrc = launch_viterbi(st, g.shape, g.max_cells, tasks + g.first, results + g.first, g.count, queue, c->n_cu, mode, group_order(order, g), waves_hint);
+    const int vrc = launch_viterbi(st, g.shape, g.max_cells, tasks + g.first, results + g.first, g.count, queue, c->n_cu, mode, group_order(order, g), waves_hint, tracts);
     if (viterbi_launch_status(vrc) == STRQ_ERR_UNSUPPORTED) c->err = std::string(what) + "decode mode not available for this model's kernel shape";
     else if (vrc) c->err = "viterbi launch failed";
     return viterbi_launch_status(vrc);
@@ -971,6 +975,89 @@ static int run_conf_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, con
     return STRQ_OK;
 }
 
+// Tract counts of the reads of one sub-batch (strq_set_tracts): every read whose gate passed, that was normalised, whose flanked decode
+// found a path and whose target has a compound model is decoded once more with that model, on the window of the count decode.  Runs
+// on the context's stream when the rows of the sub-batch are taken, like the forward pass: the geometry and the conditioning rows go
+// back up from the slot's pinned block (the device copies belong to the sub-batch that followed), the host groups the reads by
+// kernel shape, tract_task_kernel writes their tasks on the slot's filtered signal, and the Viterbi kernels decode them as a count
+// launch with the wide payload -- one launch per kernel instance in use; the first wait is the read-back of the results.
+static int run_tract_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
+{
+    Batch& B = d->batch;
+    hipStream_t st = c->stream;
+    const int64_t r0 = sl.r0; const int nr = sl.nr;
+    if (nr <= 0 || sl.scan) return STRQ_OK;
+    const DetectState::Slot::Pinned h = sl.host();
+    std::vector<int> who;
+    for (int i = 0; i < nr; ++i) {
+        const Target& t = target_of(d, r0 + i);
+        if (t.tract_model_id < 0 || !h.geom[i].gate || h.rc[i].status != COND_OK || h.vres[sl.vit_slot[i]].status != 0) continue;
+        who.push_back(i);
+    }
+    const int m = (int)who.size();
+    if (!m) return STRQ_OK;
+    if (const int rc = pass_start(c, d)) return rc;
+    auto model_of = [&](int i) { return c->models[target_of(d, r0 + i).tract_model_id]; };
+    std::vector<GroupItem> items((size_t)m);
+    for (int k = 0; k < m; ++k) {
+        HostModel* hm = model_of(who[(size_t)k]);
+        const int shape = vit_shape_of(hm->h);          // (never the register-resident image: it has one loop)
+        if (shape < 0 || !hm->h.tract_inc) { c->err = "tracts: the target's model has no tract decode"; return STRQ_ERR_UNSUPPORTED; }
+        items[(size_t)k] = {0, shape, hm->h.n_cells};
+    }
+    const Grouping G = group_items(items);
+    Carve wl;
+    const size_t o_geom = wl.add<ReadGeom>((size_t)nr), o_rc = wl.add<ReadCond>((size_t)nr);
+    STRQ_HIP(c, d->tract_ws.reserve(wl.total() + 64));
+    ReadGeom* d_geom = Carve::at<ReadGeom>(d->tract_ws.p, o_geom); ReadCond* d_rc = Carve::at<ReadCond>(d->tract_ws.p, o_rc);
+    STRQ_HIP(c, hipMemcpyAsync(d_geom, h.geom, (size_t)nr * sizeof(ReadGeom), hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, hipMemcpyAsync(d_rc, h.rc, (size_t)nr * sizeof(ReadCond), hipMemcpyHostToDevice, st));
+    Carve tl;
+    const size_t o_vt = tl.add<VitTask>((size_t)m), o_vr = tl.add<VitResult>((size_t)m), o_md = tl.add<const VitModel*>((size_t)m), o_rd = tl.add<int32_t>((size_t)m),
+                 o_order = tl.add<int>((size_t)m);
+    STRQ_HIP(c, d->tract_task.reserve(tl.total() + 64));
+    void* tb = d->tract_task.p;
+    VitTask* d_vt = Carve::at<VitTask>(tb, o_vt); VitResult* d_vr = Carve::at<VitResult>(tb, o_vr);
+    const VitModel** d_md = Carve::at<const VitModel*>(tb, o_md); int32_t* d_rd = Carve::at<int32_t>(tb, o_rd); int* d_order = Carve::at<int>(tb, o_order);
+    std::vector<int32_t> read_of((size_t)m); std::vector<const VitModel*> mv((size_t)m);
+    for (int at = 0; at < m; ++at) {
+        const int i = who[(size_t)G.order[(size_t)at]];
+        read_of[(size_t)at] = i; mv[(size_t)at] = model_of(i)->dev;
+    }
+    STRQ_HIP(c, hipMemcpyAsync(d_rd, read_of.data(), (size_t)m * 4, hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, hipMemcpyAsync(d_md, mv.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
+    TractTaskArgs ta;
+    ta.geom = d_geom; ta.rc = d_rc; ta.read = d_rd; ta.model = d_md; ta.flt = sl.flt_base; ta.is_f64 = B.dtype; ta.ps = d->ps;
+    ta.vit = d_vt; ta.n_tasks = m; ta.n_reads = nr;
+    if (launch_tract_tasks(st, ta)) { c->err = "tracts: task launch failed"; return STRQ_ERR_DEVICE; }
+    d->tract_launches += 1;
+    if (const int qrc = reset_queue_heads(c, st)) return qrc;
+    int qi = 0;
+    for (const VitGroup& g : G.groups) {
+        if (const int src = sort_viterbi_group(c, st, g, d_vt, d_order)) return src;
+        if (const int lrc = launch_viterbi_group(c, st, g, d_vt, d_vr, d_order, c->queue.as<int>() + qi++, VIT_COUNT, 0, "tracts: ", true)) return lrc;
+        d->tract_launches += group_order(d_order, g) ? 2 : 1;
+    }
+    std::vector<VitResult> vr((size_t)m);
+    STRQ_HIP(c, hipMemcpyAsync(vr.data(), d_vr, (size_t)m * sizeof(VitResult), hipMemcpyDeviceToHost, st));
+    if (const int rc = pass_stop(c, d, d->tract_ms)) return rc;
+    for (int at = 0; at < m; ++at) {
+        const int i = read_of[(size_t)at];
+        const Target& t = target_of(d, r0 + i);
+        const VitResult& v = vr[(size_t)at];
+        strq_tracts o = strq_tracts();
+        o.status = v.status == 0 ? 0 : (v.status == 2 ? 2 : 3);
+        if (o.status == 0) {
+            o.n_tracts = t.n_tracts; o.log_p = v.logp;
+            for (int j = 0; j < t.n_tracts; ++j)
+                o.count[j] = (int32_t)(((uint64_t)v.counted >> (VIT_TRACT_BITS * j)) & (((uint64_t)1 << VIT_TRACT_BITS) - 1)) + t.tract_bias[j];
+            d->tract_windows += 1;
+        } else d->tract_failed += 1;
+        B.tracts[(size_t)(r0 + i)] = o;
+    }
+    return STRQ_OK;
+}
+
 // The bracket of the methylation calls of anchored reads: events of its own (the anchored pass around it holds the pass events),
 // made when the switch is first used; amod_stop waits for the stream and adds the milliseconds in between to amod_ms.
 static int amod_start(strq_ctx* c, DetectState* d)
@@ -1344,6 +1431,7 @@ static int take_rows(strq_ctx* c, DetectState* d, DetectState::Slot& sl, bool un
             if (sl.ex.conf) { const int crc = run_conf_pass(c, d, sl, dec); if (crc) return crc; }
         }
     }
+    if (sl.ex.tracts) { const int trc = run_tract_pass(c, d, sl); if (trc) return trc; }
     return sl.ex.anch ? run_anchored_pass(c, d, sl) : STRQ_OK;
 }
 
@@ -1982,6 +2070,10 @@ int run_range(strq_ctx* c, DetectState* d, int64_t first, int64_t last)
         }
     }
     if (d->extras.var && d->scan_on) { c->err = "variants: not available in a scan (strq_scan_set)"; return STRQ_ERR_ARG; }
+    if (d->extras.tracts) {
+        if (d->scan_on) { c->err = "tracts: not available in a scan (strq_scan_set)"; return STRQ_ERR_ARG; }
+        B.size_tracts();
+    }
     if (d->extras.renorm) {
         // nothing is launched for a call whose reads the pass could not fit
         if (d->scan_on) { c->err = "renorm: not available in a scan (strq_scan_set)"; return STRQ_ERR_ARG; }
@@ -1998,6 +2090,7 @@ int run_range(strq_ctx* c, DetectState* d, int64_t first, int64_t last)
     d->conf_ms = 0; d->conf_windows = d->conf_nopath = d->conf_expo = 0;
     d->llr_ms = 0; d->llr_units = d->llr_reads = d->llr_launches = 0;
     d->var_ms = 0; d->var_launches = d->var_passages = d->var_reads = 0;
+    d->tract_ms = 0; d->tract_windows = d->tract_launches = d->tract_failed = 0;
     STRQ_HIP(c, c->redo_total.reserve(64));
     STRQ_HIP(c, hipMemsetAsync(c->redo_total.p, 0, 64, c->stream));
     // partition into sub-batches first, so that the upload of piece k + 1 can overlap the kernels of piece k
@@ -2418,6 +2511,52 @@ int strq_last_anchored(strq_ctx* c, double* out8)
     out8[0] = d->anch_ms;
     for (int k = 0; k < 4; ++k) out8[1 + k] = d->anch_kinds[k];
     out8[5] = d->anch_launches; out8[6] = d->anch_g2; out8[7] = d->anch_lane;
+    return STRQ_OK;
+}
+
+int strq_target_set_tracts(strq_ctx* c, int32_t target_id, int32_t model_id, int32_t n_tracts, const int32_t* bias)
+{
+    STRQ_ENTER(c);
+    DetectState* d = dstate(c);
+    if (target_id < 0 || target_id >= (int32_t)d->targets.size()) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    if (model_id != -1) {
+        if (model_id < 0 || model_id >= (int32_t)c->models.size() || !c->models[model_id] || !bias) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+        const HostModel* hm = c->models[model_id];
+        if (!hm->h.tract_inc || hm->n_tracts < 1) { c->err = "tracts: the model has no tracts (strq_model_set_tracts)"; return STRQ_ERR_ARG; }
+        if (n_tracts != hm->n_tracts) { c->err = "tracts: the model has another number of tracts"; return STRQ_ERR_ARG; }
+        if (vit_shape_of(hm->h) < 0) { c->err = "tracts: model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
+    }
+    if (const int rc = drain(c, d)) return rc;          // a sub-batch in flight is taken with the target it ran with
+    Target& t = d->targets[target_id];
+    t.tract_model_id = model_id; t.n_tracts = model_id < 0 ? 0 : n_tracts;
+    for (int j = 0; j < 3; ++j) t.tract_bias[j] = (model_id >= 0 && j < n_tracts) ? bias[j] : 0;
+    return STRQ_OK;
+}
+
+int strq_set_tracts(strq_ctx* c, int32_t on)
+{
+    STRQ_ENTER(c);
+    return set_extra(c, on, "bad argument (strq_set_tracts takes 0 or 1)", &Extras::tracts);
+}
+
+int strq_batch_fetch_tracts(strq_ctx* c, strq_tracts* out, int64_t n)
+{
+    STRQ_ENTER(c);
+    DetectState* d = dstate(c);
+    if (const int rc = drain(c, d)) return rc;
+    const Batch& B = d->batch;
+    if (!B.ran.tracts) { c->err = "the last batch ran without tracts (strq_set_tracts)"; return STRQ_ERR_ARG; }
+    if (n != B.n_reads || (n > 0 && !out) || B.tracts.size() != (size_t)n) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    if (n) std::memcpy(out, B.tracts.data(), (size_t)n * sizeof(strq_tracts));
+    return STRQ_OK;
+}
+
+int strq_last_tracts(strq_ctx* c, double* out4)
+{
+    STRQ_ENTER(c);
+    if (!out4) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    DetectState* d = dstate(c);
+    out4[0] = d->tract_ms; out4[1] = d->tract_windows; out4[2] = d->tract_launches; out4[3] = d->tract_failed;
     return STRQ_OK;
 }
 

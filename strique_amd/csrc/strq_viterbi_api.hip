@@ -881,6 +881,86 @@ int strq_forward_batch(strq_ctx* c, int32_t model_id, int64_t n_seq, const doubl
     return STRQ_OK;
 }
 
+int strq_model_set_tracts(strq_ctx* c, int32_t model_id, int32_t n_tracts, const int32_t* tract_of)
+{
+    STRQ_ENTER(c);
+    if (model_id < 0 || model_id >= (int32_t)c->models.size() || !c->models[model_id] || !tract_of) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    if (n_tracts < 1 || n_tracts > VIT_TRACTS_MAX) { c->err = "bad argument (between 1 and 3 tracts)"; return STRQ_ERR_ARG; }
+    HostModel* hm = c->models[model_id];
+    const int n = hm->n_states;
+    std::vector<uint64_t> inc((size_t)n + 1, 0);
+    for (int l = 0; l < n; ++l) {
+        const int j = tract_of[l];
+        if (j == -1) continue;
+        if (j < 0 || j >= n_tracts) { c->err = "bad argument (tract_of: -1 or a tract below n_tracts)"; return STRQ_ERR_ARG; }
+        if (l >= hm->silent_start || hm->count_inc.empty() || hm->count_inc[l] != 1) { c->err = "a state with a tract must be an emitting state with count_inc 1"; return STRQ_ERR_ARG; }
+        inc[(size_t)l] = (uint64_t)1 << (VIT_TRACT_BITS * j);
+    }
+    // a detect sub-batch in flight points to the model's present device image through its tasks
+    { const int rc = detect_drain(c); if (rc) return rc; }
+    STRQ_HIP(c, hipStreamSynchronize(c->stream));
+    STRQ_HIP(c, hm->tract_blob.reserve(inc.size() * 8));
+    STRQ_HIP(c, hipMemcpy(hm->tract_blob.p, inc.data(), inc.size() * 8, hipMemcpyHostToDevice));
+    hm->h.tract_inc = hm->tract_blob.as<const uint64_t>(); hm->n_tracts = n_tracts;
+    if (hipMemcpy(const_cast<VitModel*>(hm->dev), &hm->h, sizeof(VitModel), hipMemcpyHostToDevice) != hipSuccess) {
+        hm->h.tract_inc = nullptr; hm->n_tracts = 0; c->err = "model upload failed"; return STRQ_ERR_DEVICE;
+    }
+    return STRQ_OK;
+}
+
+int strq_viterbi_tracts(strq_ctx* c, int32_t model_id, int64_t n_seq, const double* x, const int64_t* x_off,
+                        double* logp, int64_t* counts, int32_t* status)
+{
+    STRQ_ENTER(c);
+    if (model_id < 0 || model_id >= (int32_t)c->models.size() || !c->models[model_id] || n_seq < 0 || n_seq > 8192 || (n_seq > 0 && !x_off)) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    HostModel* hm = c->models[model_id];
+    if (!hm->h.tract_inc) { c->err = "the model has no tracts (strq_model_set_tracts)"; return STRQ_ERR_ARG; }
+    const int shape = vit_shape_of(hm->h);          // never the register-resident image: it has one loop
+    if (n_seq == 0) return STRQ_OK;
+    const int64_t tot = x_off[n_seq];
+    if (tot < 0 || (tot > 0 && !x)) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    for (int64_t i = 0; i < n_seq; ++i) if (x_off[i + 1] < x_off[i] || x_off[i] < 0) { c->err = "bad argument (x_off must not decrease)"; return STRQ_ERR_ARG; }
+    if (shape < 0) { c->err = "model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
+    hipStream_t st = c->stream;
+    STRQ_HIP(c, c->vit_x.reserve((size_t)tot * 8 + 64));
+    if (tot) STRQ_HIP(c, hipMemcpyAsync(c->vit_x.p, x, (size_t)tot * 8, hipMemcpyHostToDevice, st));
+    Carve lay;
+    const size_t o_tasks = lay.add<VitTask>((size_t)n_seq), o_res = lay.add<VitResult>((size_t)n_seq), o_order = lay.add<int>((size_t)n_seq);
+    STRQ_HIP(c, c->vit_tasks.reserve(lay.total() + 64));
+    VitTask* d_tasks = Carve::at<VitTask>(c->vit_tasks.p, o_tasks); VitResult* d_res = Carve::at<VitResult>(c->vit_tasks.p, o_res);
+    int* d_order = Carve::at<int>(c->vit_tasks.p, o_order);
+    std::vector<VitTask> tasks((size_t)n_seq);
+    for (int64_t i = 0; i < n_seq; ++i) {
+        VitTask& t = tasks[(size_t)i];
+        std::memset(&t, 0, sizeof(t));
+        t.model = hm->dev; t.sig = c->vit_x.as<double>() + x_off[i]; t.T = x_off[i + 1] - x_off[i]; t.src_kind = VIT_SRC_F64;
+    }
+    STRQ_HIP(c, hipMemcpyAsync(d_tasks, tasks.data(), (size_t)n_seq * sizeof(VitTask), hipMemcpyHostToDevice, st));
+    if (const int qrc = reset_queue_heads(c, st)) return qrc;
+    if (launch_vit_sort(st, d_tasks, (int)n_seq, d_order)) { c->err = "tract decode: sort launch failed"; return STRQ_ERR_DEVICE; }
+    const int lrc = launch_viterbi(st, shape, hm->h.n_cells, d_tasks, d_res, (int)n_seq, c->queue.as<int>(), c->n_cu, VIT_COUNT, d_order, 0, true);
+    if (lrc) { (void)hipStreamSynchronize(st); c->err = "viterbi launch failed"; return viterbi_launch_status(lrc); }
+    c->tract_shape_last = shape;
+    std::vector<VitResult> res((size_t)n_seq);
+    STRQ_HIP(c, hipMemcpyAsync(res.data(), d_res, (size_t)n_seq * sizeof(VitResult), hipMemcpyDeviceToHost, st));
+    STRQ_HIP(c, hipStreamSynchronize(st));
+    for (int64_t i = 0; i < n_seq; ++i) {
+        const VitResult& r = res[(size_t)i];
+        const uint64_t pay = r.status == 0 ? (uint64_t)r.counted : 0;
+        if (logp) logp[i] = r.logp;
+        if (status) status[i] = r.status;
+        if (counts) for (int j = 0; j < VIT_TRACTS_MAX; ++j) counts[3 * i + j] = (int64_t)((pay >> (VIT_TRACT_BITS * j)) & (((uint64_t)1 << VIT_TRACT_BITS) - 1));
+    }
+    return STRQ_OK;
+}
+
+int strq_debug_tract_shape(const strq_ctx* c, int32_t* shape)
+{
+    if (!c || !shape) return STRQ_ERR_ARG;
+    *shape = c->tract_shape_last;
+    return STRQ_OK;
+}
+
 int strq_viterbi(strq_ctx* c, int32_t model_id, const double* x, int64_t T, double* logp, int64_t* counted,
                  int32_t* status, int32_t* path)
 {

@@ -98,7 +98,13 @@ struct VitModel {
     // and whether the register-resident image holds them in the slots of its two broadcast sources (B0: record 0, B1: record 1)
     int32_t unit_state[2];
     int32_t g2_unit;
+    // tract decodes (a VIT_COUNT launch with the wide payload, strq_model_set_tracts): n_states + 1 by state, what an emission of the
+    // state adds to the 64-bit payload -- (uint64_t)1 << (VIT_TRACT_BITS * j) for a counted state of tract j, else 0 -- or null
+    const uint64_t* tract_inc;
 };
+// three counters of 21 bits: windows below VIT_MARK_T_MAX observations cannot carry from one into the next (every counted state emits)
+#define VIT_TRACT_BITS 21
+#define VIT_TRACTS_MAX 3
 #define VIT_CSR_MAX_STATES 4096      // two buffers of 16-byte cells in 160 KB of LDS
 
 enum { VIT_SRC_F64 = 0, VIT_SRC_F64_AFFINE = 1, VIT_SRC_I16_AFFINE = 2 };

@@ -120,7 +120,12 @@ template <int EPL, int SPL> struct VitLds {
 // from hub to hub (one hop per repeat unit) instead of tracing a back-pointer per (time step, state).
 //
 // UNIT (flanked model): the same scheme for the two counted states that close the repeat loop -- see VIT_UNIT_T_MAX.
-template <int EPL, int SPL, int DE_HI, int DE_LO, int DS, bool BP, bool SS, bool MARK = false, bool HUB = false, bool UNIT = false>
+//
+// TRACT (compound models, a property of a VIT_COUNT launch: launch_viterbi's `tracts`): the count payload 64 bits wide, three 21-bit
+// counters -- an emission of state l adds VitModel::tract_inc[l] (1 << 21 j for a counted state of tract j, else 0).  Every counted
+// state emits, so the fields of a window below VIT_MARK_T_MAX observations cannot carry into each other; longer windows are not
+// decoded (status 2).  count_inc is not looked at.
+template <int EPL, int SPL, int DE_HI, int DE_LO, int DS, bool BP, bool SS, bool MARK = false, bool HUB = false, bool UNIT = false, bool TRACT = false>
 __global__ void __launch_bounds__((64 * VitLds<EPL, SPL>::WAVES))
 viterbi_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ results,
                int n_tasks, int* __restrict__ queue, const int* __restrict__ order)
@@ -141,7 +146,7 @@ viterbi_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ result
     constexpr int DEMAX = HI0 > LO ? HI0 : LO;
     auto de_of = [](int s) constexpr { return s == 0 ? HI0 : (s < (EPL + 1) / 2 ? HI1 : LO); };
     const double NEGINF = -__builtin_inf();
-    constexpr bool WIDE = MARK || HUB;
+    constexpr bool WIDE = MARK || HUB || TRACT;
     using Pay = std::conditional_t<WIDE, uint64_t, int>;      // what rides along the best path
     struct alignas(16) Cell { double v; Pay c; };
     typedef unsigned v4u __attribute__((ext_vector_type(4)));
@@ -164,7 +169,7 @@ viterbi_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ result
         }
     };
     auto pay_add = [](Pay v, int inc) -> Pay {       // count += inc (the count field never carries out of the low half)
-        if constexpr (HUB || UNIT) return v;          // the modification model counts nothing; a unit decode carries records instead
+        if constexpr (HUB || UNIT || TRACT) return v;          // the modification model counts nothing; a unit decode carries records instead; tract counters: in the step
         else if constexpr (MARK) return ((uint64_t)v & 0xFFFFFFFF00000000ull) | (uint32_t)((uint32_t)v + (uint32_t)inc);
         else return v + inc;
     };
@@ -180,6 +185,7 @@ viterbi_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ result
     int own_e[EPL], einc[EPL]; bool enorm[EPL]; bool etag[EPL]; bool ehub[EPL], erec[EPL];
     uint32_t ebranch[EPL];      // HUB: branch id of the state owned by (slot, lane): tag 1 -> 1, 3 -> 2, 4 -> 3 (variant models), else 0
     int eunit[EPL];      // UNIT: record index of the counted state owned by (slot, lane), -1 none
+    uint64_t etract[EPL];      // TRACT: what an emission of the state owned by (slot, lane) adds to the payload
     const char* esrc[EPL][DEMAX]; char* edst[EPL];
     double ea[EPL], eb[EPL], ec[EPL], elp[EPL][DEMAX];
     double ebf[EPL], ecf[EPL];     // branch-free emission: ecf - (x - ea)^2 * ebf  (uniform: ebf = 0; padding: ecf = -inf)
@@ -193,6 +199,14 @@ viterbi_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ result
         if (tq >= n_tasks) break;
         const int ti = order ? order[tq] : tq;        // longest observation windows first
         const VitTask tk = tasks[ti];
+        if constexpr (TRACT) {
+            if (tk.T >= VIT_MARK_T_MAX) {          // (wave-uniform) the counters could carry: not decoded
+                VitResult r; r.logp = NEGINF; r.counted = 0; r.status = 2; r.pad_ = 0;
+                r.dbg[0] = r.dbg[1] = r.dbg[2] = r.dbg[3] = 0;
+                results[ti] = r;
+                continue;
+            }
+        }
         if (tk.model != cur_model) {
             cur_model = tk.model;
             const VitModel& M = *cur_model;
@@ -215,6 +229,7 @@ viterbi_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ result
                 erec[s] = own_e[s] >= 0 && own_e[s] == M.rec_state;
                 if constexpr (HUB) { const int tg = own_e[s] >= 0 ? M.state_tag[own_e[s]] : 0; ebranch[s] = tg == 1 ? 1u : (tg >= 3 ? (uint32_t)(tg - 1) : 0u); }
                 if constexpr (UNIT) eunit[s] = own_e[s] < 0 ? -1 : (own_e[s] == M.unit_state[0] ? 0 : (own_e[s] == M.unit_state[1] ? 1 : -1));
+                if constexpr (TRACT) etract[s] = (own_e[s] >= 0 && M.tract_inc) ? M.tract_inc[own_e[s]] : 0;
                 edst[s] = vbase + 16 * (own_e[s] >= 0 ? s * 64 + lane : TRASH);
 #pragma unroll
                 for (int j = 0; j < DEMAX; ++j) {
@@ -465,6 +480,8 @@ viterbi_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ result
                 } else if constexpr (UNIT) {
                     if (eunit[s] >= 0 && tk.bp) reinterpret_cast<uint32_t*>(tk.bp)[2 * t + eunit[s]] = (uint32_t)bc;      // record of this counted emission
                     nc[s] = eunit[s] >= 0 ? (int)((tt1 << 1) | (uint32_t)eunit[s]) : bc;
+                } else if constexpr (TRACT) {
+                    nc[s] = bc + etract[s];
                 } else nc[s] = bc + einc[s];
             }
 #pragma unroll
@@ -551,6 +568,8 @@ viterbi_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ result
             r.counted = 0;                                         // (the count decode reports it: the hops of the record chain)
             r.dbg[0] = (uint32_t)fin.c;                            // payload of the end state: the last counted emission, 0 = none
             if (tk.T >= VIT_UNIT_T_MAX) r.status = 2;
+        } else if constexpr (TRACT) {
+            r.counted = (lp > NEGINF) ? (int64_t)(uint64_t)fin.c : 0;      // the three counters as they are (VIT_TRACT_BITS)
         } else {
             r.counted = (lp > NEGINF) ? (int64_t)fin.c : 0;
         }
@@ -947,7 +966,8 @@ static int launch_viterbi_g2(hipStream_t stream, const VitTask* tasks, VitResult
 // per time step); it exists so that a target whose HMM exceeds the lane layouts (repeat units beyond ~50 nt, states with
 // more than eight in-edges) runs instead of being refused -- the reference takes whatever pomegranate takes
 // (scripts/STRique.py:553-579).  MODE: VIT_COUNT, VIT_BACKPTR (predecessor state per (time step, state)) or VIT_MARK.
-template <int MODE>
+// TRACT (with VIT_COUNT): the payload holds the tract counters of viterbi_kernel instead of the count.
+template <int MODE, bool TRACT = false>
 __global__ void __launch_bounds__(256)
 viterbi_csr_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ results,
                    int n_tasks, int* __restrict__ queue, const int* __restrict__ order)
@@ -957,7 +977,10 @@ viterbi_csr_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ re
     struct alignas(16) Cell { double v; uint64_t c; };
     const double NEGINF = -__builtin_inf();
     constexpr bool MARK = MODE == VIT_MARK, BP = MODE == VIT_BACKPTR;
-    auto count_add = [](uint64_t v, int inc) -> uint64_t { return (v & 0xFFFFFFFF00000000ull) | (uint32_t)((uint32_t)v + (uint32_t)inc); };
+    auto count_add = [](uint64_t v, int inc) -> uint64_t {
+        if constexpr (TRACT) return v;          // counted states of a tract emit: added in the emitting phase
+        else return (v & 0xFFFFFFFF00000000ull) | (uint32_t)((uint32_t)v + (uint32_t)inc);
+    };
     for (;;) {
         __syncthreads();
         if (threadIdx.x == 0) next_task = atomicAdd(queue, 1);
@@ -966,6 +989,16 @@ viterbi_csr_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ re
         if (tq >= n_tasks) break;
         const int ti = order ? order[tq] : tq;
         const VitTask tk = tasks[ti];
+        if constexpr (TRACT) {
+            if (tk.T >= VIT_MARK_T_MAX) {          // (uniform over the workgroup) not decoded
+                if (threadIdx.x == 0) {
+                    VitResult r; r.logp = NEGINF; r.counted = 0; r.status = 2; r.pad_ = 0;
+                    r.dbg[0] = r.dbg[1] = r.dbg[2] = r.dbg[3] = 0;
+                    results[ti] = r;
+                }
+                continue;
+            }
+        }
         const VitModel& M = *tk.model;
         const int n = M.n_states, ne = M.n_emit, start = M.start, nlev = M.n_levels;
         Cell* buf0 = reinterpret_cast<Cell*>(lds_d); Cell* buf1 = buf0 + n;
@@ -1020,7 +1053,8 @@ viterbi_csr_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ re
                     lo |= set_e ? mark_e_lo : 0u;
                     hi |= set_e ? mark_e_hi : (set_l ? mark_l_hi : 0u);
                     nc = ((uint64_t)hi << 32) | lo;
-                } else nc = count_add(bc, M.count_inc[l]);
+                } else if constexpr (TRACT) nc = bc + (M.tract_inc ? M.tract_inc[l] : 0);
+                else nc = count_add(bc, M.count_inc[l]);
                 cur[l].v = best + em; cur[l].c = nc;
                 if (BP && tk.bp) tk.bp[(size_t)(t + 1) * n + l] = (uint16_t)arg;
             }
@@ -1034,25 +1068,26 @@ viterbi_csr_kernel(const VitTask* __restrict__ tasks, VitResult* __restrict__ re
             r.dbg[0] = r.dbg[1] = r.dbg[2] = r.dbg[3] = 0;
             if constexpr (MARK) {
                 vit_unpack_marks(fin.c, lp > NEGINF, tk.T, r);
-            } else r.counted = (lp > NEGINF) ? (int64_t)(uint32_t)fin.c : 0;
+            } else if constexpr (TRACT) r.counted = (lp > NEGINF) ? (int64_t)fin.c : 0;
+            else r.counted = (lp > NEGINF) ? (int64_t)(uint32_t)fin.c : 0;
             results[ti] = r;
         }
     }
 }
 
 static int launch_viterbi_csr(hipStream_t stream, int max_cells, const VitTask* tasks, VitResult* results, int n_tasks,
-                              int* queue, int n_cu, VitMode mode, const int* order)
+                              int* queue, int n_cu, VitMode mode, const int* order, bool tracts)
 {
-    if (!vit_mode_ok(VIT_SHAPE_CSR, mode) || max_cells - 1 > VIT_CSR_MAX_STATES) return 2;
+    if (!vit_mode_ok(VIT_SHAPE_CSR, mode) || max_cells - 1 > VIT_CSR_MAX_STATES || (tracts && mode != VIT_COUNT)) return 2;
     const size_t lds = (size_t)2 * (size_t)(max_cells - 1) * 16;
     int per_cu = (int)((160 * 1024 - 64) / (lds ? lds : 1)); if (per_cu > 4) per_cu = 4; if (per_cu < 1) per_cu = 1;
     const dim3 grid(per_cu * n_cu), block(256);
-#define VIT_CSR_GO(MODE_)                                                                                                 \
+#define VIT_CSR_GO(...)                                                                                                   \
     do {                                                                                                                  \
-        (void)hipFuncSetAttribute((const void*)viterbi_csr_kernel<MODE_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((viterbi_csr_kernel<MODE_>), grid, block, lds, stream, tasks, results, n_tasks, queue, order);  \
+        (void)hipFuncSetAttribute((const void*)viterbi_csr_kernel<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        hipLaunchKernelGGL((viterbi_csr_kernel<__VA_ARGS__>), grid, block, lds, stream, tasks, results, n_tasks, queue, order);  \
     } while (0)
-    if (mode == VIT_MARK) VIT_CSR_GO(VIT_MARK); else if (mode == VIT_BACKPTR) VIT_CSR_GO(VIT_BACKPTR); else VIT_CSR_GO(VIT_COUNT);
+    if (tracts) VIT_CSR_GO(VIT_COUNT, true); else if (mode == VIT_MARK) VIT_CSR_GO(VIT_MARK); else if (mode == VIT_BACKPTR) VIT_CSR_GO(VIT_BACKPTR); else VIT_CSR_GO(VIT_COUNT);
 #undef VIT_CSR_GO
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
@@ -1153,24 +1188,28 @@ int vit_shape_for(const VitModel& mh, VitMode mode)
 // the kernels of row ID of VIT_SHAPES: an instance exists exactly where the row has the mode
 template <int ID>
 static int vit_launch_shape(hipStream_t stream, int max_cells, const VitTask* tasks, VitResult* results, int n_tasks,
-                            int* queue, int n_cu, VitMode mode, int single_stage, const int* order)
+                            int* queue, int n_cu, VitMode mode, int single_stage, const int* order, bool tracts)
 {
     constexpr int E_ = VIT_SHAPES[ID].epl, S_ = VIT_SHAPES[ID].spl, H_ = VIT_SHAPES[ID].de_hi, L_ = VIT_SHAPES[ID].de_lo, D_ = VIT_SHAPES[ID].ds;
-    if (!vit_mode_ok(ID, mode)) return 2;
+    if (!vit_mode_ok(ID, mode) || (tracts && mode != VIT_COUNT)) return 2;
     if (max_cells > VitLds<E_, S_>::TRASH) return 3;
     // per wave: two buffers of 16-byte {value, count} cells; waves of a block are independent
     int nw = VitLds<E_, S_>::WAVES;
     if (const char* e = strq::opt("STRQ_VIT_WAVES")) { const int v = atoi(e); if (v >= 1 && v <= nw) nw = v; }      // experiments: fewer waves per CU
     const size_t lds = (size_t)nw * 2 * VitLds<E_, S_>::BUF;
     const dim3 grid(n_cu), block(64 * nw);
-#define VIT_GO(BP_, SS_, MK_, HB_, UN_)                                                                                   \
+#define VIT_GO(BP_, SS_, MK_, HB_, UN_, TR_)                                                                              \
     do {                                                                                                                  \
-        (void)hipFuncSetAttribute((const void*)viterbi_kernel<E_, S_, H_, L_, D_, BP_, SS_, MK_, HB_, UN_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((viterbi_kernel<E_, S_, H_, L_, D_, BP_, SS_, MK_, HB_, UN_>), grid, block, lds, stream, tasks, results, n_tasks, queue, order);       \
+        (void)hipFuncSetAttribute((const void*)viterbi_kernel<E_, S_, H_, L_, D_, BP_, SS_, MK_, HB_, UN_, TR_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        hipLaunchKernelGGL((viterbi_kernel<E_, S_, H_, L_, D_, BP_, SS_, MK_, HB_, UN_, TR_>), grid, block, lds, stream, tasks, results, n_tasks, queue, order);       \
     } while (0)
-#define VIT_GO_SS(M_, SS_) VIT_GO(M_ == VIT_BACKPTR, SS_, M_ == VIT_MARK, M_ == VIT_HUB, M_ == VIT_UNIT)
+#define VIT_GO_SS(M_, SS_) VIT_GO(M_ == VIT_BACKPTR, SS_, M_ == VIT_MARK, M_ == VIT_HUB, M_ == VIT_UNIT, false)
 #define VIT_GO_MODE(M_) case M_: if constexpr (vit_mode_ok(ID, M_)) { if (single_stage) VIT_GO_SS(M_, true); else VIT_GO_SS(M_, false); } break
-    switch (mode) { VIT_GO_MODE(VIT_COUNT); VIT_GO_MODE(VIT_BACKPTR); VIT_GO_MODE(VIT_MARK); VIT_GO_MODE(VIT_HUB); VIT_GO_MODE(VIT_UNIT); }
+    if (tracts) {          // every row has VIT_COUNT: the same launch with the wide payload
+        if (single_stage) VIT_GO(false, true, false, false, false, true); else VIT_GO(false, false, false, false, false, true);
+    } else {
+        switch (mode) { VIT_GO_MODE(VIT_COUNT); VIT_GO_MODE(VIT_BACKPTR); VIT_GO_MODE(VIT_MARK); VIT_GO_MODE(VIT_HUB); VIT_GO_MODE(VIT_UNIT); }
+    }
 #undef VIT_GO_MODE
 #undef VIT_GO_SS
 #undef VIT_GO
@@ -1178,14 +1217,15 @@ static int vit_launch_shape(hipStream_t stream, int max_cells, const VitTask* ta
 }
 
 int launch_viterbi(hipStream_t stream, int shape, int max_cells, const VitTask* tasks, VitResult* results,
-                   int n_tasks, int* queue, int n_cu, VitMode mode, const int* order, int waves_hint)
+                   int n_tasks, int* queue, int n_cu, VitMode mode, const int* order, int waves_hint, bool tracts)
 {
     switch (vit_shape_family(shape)) {
-        case VIT_FAMILY_CSR: return launch_viterbi_csr(stream, max_cells, tasks, results, n_tasks, queue, n_cu, mode, order);
-        case VIT_FAMILY_G2: return launch_viterbi_g2(stream, tasks, results, n_tasks, queue, n_cu, mode, order, waves_hint);
+        case VIT_FAMILY_CSR: return launch_viterbi_csr(stream, max_cells, tasks, results, n_tasks, queue, n_cu, mode, order, tracts);
+        case VIT_FAMILY_G2: if (tracts) return 2;          // (its image has one loop: no compound model gets one)
+            return launch_viterbi_g2(stream, tasks, results, n_tasks, queue, n_cu, mode, order, waves_hint);
         case VIT_FAMILY_LANE:
             return vit_dispatch<VIT_LANE_SHAPES>(shape & ~VIT_SHAPE_SS, [&](auto id) {
-                return vit_launch_shape<decltype(id)::value>(stream, max_cells, tasks, results, n_tasks, queue, n_cu, mode, (shape & VIT_SHAPE_SS) ? 1 : 0, order);
+                return vit_launch_shape<decltype(id)::value>(stream, max_cells, tasks, results, n_tasks, queue, n_cu, mode, (shape & VIT_SHAPE_SS) ? 1 : 0, order, tracts);
             });
         default: return 2;
     }

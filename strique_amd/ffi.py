@@ -417,6 +417,27 @@ class Context(object):
                                                  _ptr(ll), _ptr(mean), _ptr(var), _ptr(status)))
         return ll, mean, var, status
 
+    def model_set_tracts(self, model_id, n_tracts, tract_of):
+        """strq_model_set_tracts: tract_of one entry per state, -1 or the tract (0 .. n_tracts - 1) whose counter an emission of
+        the state advances."""
+        self._check(self._lib.strq_model_set_tracts(self._h, ctypes.c_int32(model_id), ctypes.c_int32(n_tracts), _ptr(_c(tract_of, np.int32))))
+
+    def viterbi_tracts(self, model_id, xs):
+        """strq_viterbi_tracts: xs a list of float64 arrays.  Returns (logp[], counts (n, 3) int64, status[]); status 0 ok, 1 no
+        path, 2 a window of 2^21 observations or more (not decoded)."""
+        n = len(xs)
+        x, off = _offsets(xs, np.float64)
+        logp = np.zeros(n); counts = np.zeros((n, 3), np.int64); status = np.zeros(n, np.int32)
+        self._check(self._lib.strq_viterbi_tracts(self._h, ctypes.c_int32(model_id), ctypes.c_int64(n), _ptr(x), _ptr(off),
+                                                  _ptr(logp), _ptr(counts), _ptr(status)))
+        return logp, counts, status
+
+    def debug_tract_shape(self):
+        """strq_debug_tract_shape: the kernel shape id of this context's last tract launch (-1: none yet)."""
+        shape = ctypes.c_int32(-1)
+        self._check(self._lib.strq_debug_tract_shape(self._h, ctypes.byref(shape)))
+        return int(shape.value)
+
     def viterbi(self, model_id, x, want_path=True):
         logp, counted, status, paths = self.viterbi_batch(model_id, [x], want_path)
         return logp[0], int(counted[0]), int(status[0]), (paths[0] if want_path else None)
@@ -573,6 +594,31 @@ class Context(object):
         self._check(self._lib.strq_last_anchored(self._h, _ptr(out)))
         return {'ms': float(out[0]), 'kinds': tuple(int(v) for v in out[1:5]), 'launches': int(out[5]),
                 'register_resident': int(out[6]), 'lane_layout': int(out[7])}
+
+    def target_set_tracts(self, target_id, model_id, n_tracts=0, bias=()):
+        """strq_target_set_tracts: the compound model of a target (hmm.CompoundRepeatModel, with model_set_tracts applied) and the
+        count bias of each of its tracts; model_id -1 takes it away."""
+        b = np.zeros(3, np.int32)
+        b[:len(bias)] = bias
+        self._check(self._lib.strq_target_set_tracts(self._h, ctypes.c_int32(target_id), ctypes.c_int32(model_id), ctypes.c_int32(n_tracts), _ptr(b)))
+
+    def set_tracts(self, on):
+        """strq_set_tracts: later run calls also decode the compound model of every decoded read whose target has one
+        (batch_fetch_tracts)."""
+        self._check(self._lib.strq_set_tracts(self._h, ctypes.c_int32(1 if on else 0)))
+
+    def batch_fetch_tracts(self):
+        """Records of the last batch (strq_batch_fetch_tracts): a structured array of TRACTS_DTYPE, one element per read."""
+        n = getattr(self, '_n_batch', 0)
+        out = np.zeros(max(1, n), dtype=TRACTS_DTYPE)
+        self._check(self._lib.strq_batch_fetch_tracts(self._h, _ptr(out), ctypes.c_int64(n)))
+        return out[:n]
+
+    def last_tracts(self):
+        """The tract pass of the last run call (strq_last_tracts): {'ms', 'windows' (decoded), 'launches', 'failed' (status 2 or 3)}."""
+        out = np.zeros(4)
+        self._check(self._lib.strq_last_tracts(self._h, _ptr(out)))
+        return {'ms': float(out[0]), 'windows': int(out[1]), 'launches': int(out[2]), 'failed': int(out[3])}
 
     def set_anchored_mod(self, on):
         """strq_set_anchored_mod: later run calls with anchored counting on also call the methylation pattern of every read of
@@ -877,5 +923,6 @@ RESULT_DTYPE = np.dtype([("count", np.int32), ("status", np.int32), ("score_pref
 RENORM_FIT_DTYPE = np.dtype([("a", np.int32), ("b", np.int32), ("w", np.int32), ("fitted", np.int32), ("score", np.int64)], align=True)
 RENORM_DTYPE = np.dtype([("applied", np.int32), ("pad_", np.int32), ("fit", RENORM_FIT_DTYPE, (3,))], align=True)
 
+TRACTS_DTYPE = np.dtype([("status", np.int32), ("n_tracts", np.int32), ("count", np.int32, (3,)), ("pad_", np.int32), ("log_p", np.float64)], align=True)
 ANCHORED_DTYPE = np.dtype([("kind", np.int32), ("status", np.int32), ("count", np.int32), ("pad_", np.int32), ("log_p", np.float64),
                            ("begin", np.int64), ("end", np.int64), ("free_samples", np.int64)], align=True)

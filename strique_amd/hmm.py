@@ -207,6 +207,67 @@ class FlankedRepeatModel(object):
         self.baked = bake(g, count_states=self.count_states, tag_substring='repeat')
 
 
+class CompoundRepeatModel(object):
+    """prefix profile -> loop tract0 -> junction0 profile -> loop tract1 [-> junction1 -> tract2] -> suffix profile: the flanked
+    model with K = 2 or 3 repeat loops in a fixed order (strique_amd.tracts states the rule and the sequences of the sections).
+    `units`, `linkers`, `prefix`, `suffix` as the strand reads them (tracts.strand_definition).  Loops take the rep_std_*
+    parameters, profiles -- the junctions too, with their delete states -- the seq_std_* ones; the sections are joined e1 -> s1,
+    e2 -> s2 with probability 1 and start is wired as in FlankedRepeatModel.  `tract_of[state]` is the tract whose two dummy
+    states the baked state is one of (else -1), `count_bias[j]` what turns the visits of tract j into its count."""
+
+    def __init__(self, units, linkers, prefix, suffix, pm, config=None):
+        from . import tracts
+        tp = _layer({'skip': 1 - 1e-4, 'seq_std_scale': 1.0, 'rep_std_scale': 1.0,
+                     'seq_std_offset': 0.0, 'rep_std_offset': 0.0, 'e1_ratio': 0.1},
+                    config if isinstance(config, dict) else None)
+        self.units, self.linkers = tracts.check(units, linkers)
+        g = Graph()
+        parts, loops, profiles = [], [], []
+        for what, name, seq in tracts.sections(self.units, self.linkers, prefix, suffix, pm.kmer):
+            if what == 'loop':
+                parts.append(add_repeat(g, seq, pm, tp, name, std_scale=tp['rep_std_scale'], std_offset=tp['rep_std_offset']))
+                loops.append(parts[-1])
+            else:
+                parts.append(add_profile(g, seq, pm, tp, name, std_scale=tp['seq_std_scale'], std_offset=tp['seq_std_offset']))
+                profiles.append(parts[-1])
+        g.add_transition(g.start, parts[0].s1, tp['e1_ratio'])
+        g.add_transition(g.start, parts[0].s2, 1 - tp['e1_ratio'])
+        for a, b in zip(parts, parts[1:]):
+            g.add_transition(a.e1, b.s1, 1)
+            g.add_transition(a.e2, b.s2, 1)
+        g.add_transition(parts[-1].e1, g.end, 1)
+        g.add_transition(parts[-1].e2, g.end, 1)
+        # placement hint for the lane kernels, in the spirit of the flanked model's: the states with many in-edges -- the matches
+        # and the first insert of every loop, which the spliced hubs feed -- fill the first two slots in model order, the states
+        # with uniform emissions and at most three in-edges (the other inserts, the dummy states) the last two -- where they fit.
+        # The loops go first: their first match and insert are the states with six in-edges, which the packed kernel shapes want
+        # in the first slot
+        busy, flat = [], []
+        for p in parts:
+            if isinstance(p, Repeat):
+                busy += p.profile.match + p.profile.insert[:1]
+                flat += p.profile.insert[1:] + [p.d1, p.d2]
+        for p in parts:
+            if not isinstance(p, Repeat):
+                busy += p.match; flat += p.insert
+        if len(busy) <= 128 and len(flat) <= 128:
+            lay = {}
+            for i, st in enumerate(busy): lay[st] = (i // 64, i % 64)
+            for i, st in enumerate(flat): lay[st] = (2 + i // 64, i % 64)
+            g.layout = lay
+        self.graph = g
+        self.repeat_offset = tuple(l.repeat_offset for l in loops)
+        self.count_states = tuple((l.d1, l.d2) for l in loops)
+        self.count_bias = tuple(2 * tracts.flank_units(u, pm.kmer) - 1 - l.repeat_offset for u, l in zip(self.units, loops))
+        self.n_tracts = len(loops)
+        self.baked = bake(g, count_states=[s for pair in self.count_states for s in pair], tag_substring='tract')
+        new = {int(old): k for k, old in enumerate(self.baked.orig_index)}
+        self.tract_of = np.full(self.baked.n_states, -1, np.int32)
+        for j, pair in enumerate(self.count_states):
+            for s in pair:
+                self.tract_of[new[s]] = j
+
+
 ANCHORED_KINDS = ('ends_in_repeat', 'starts_in_repeat')
 
 
