@@ -218,6 +218,8 @@ int strq_debug_tract_shape(const strq_ctx* ctx, int32_t* shape);
  *                       samples and numpy's own summation tree on the GPU when host_stats is NULL
  *                       (cond_kernels.hip: f64_stats_kernel; bit-equal to np.median / np.mean /
  *                       np.percentile), or from the caller (six doubles per read, e.g. strq_host_stats).
+ *                       A read with a NaN among its median-filtered samples is undefined (below) whatever
+ *                       the caller's scalars say: the library looks at the samples for that itself.
  * A read whose normalisation is undefined (constant signal, empty percentile tails: numpy hands the
  * reference NaN medians there) gets status 1 and the n = 0 row the reference writes for it -- its
  * offset / ticks come from aligning an all-NaN signal, every cell scoring dist_min, which is what
@@ -613,6 +615,20 @@ int strq_debug_viterbi_plan(int32_t n_states, int32_t silent_start, int32_t star
 int strq_debug_viterbi_mode(strq_ctx* ctx, int32_t model_id, int32_t mode, int64_t n_seq, const double* x, const int64_t* x_off,
                             double* logp, int64_t* counted, int32_t* status, uint32_t* dbg, void* records, const int64_t* rec_off,
                             int32_t* launched);
+/* Test hook: the same launch over windows given the way the detect pipeline gives them -- samples and a per-window map instead of
+ * observations.  src_kind 2: `samples` are int16_t, 1: double; x_off counts samples.  consts[6 i .. 6 i + 5] = c1, h1, h2, c2, lo, hi
+ * of window i: the kernels read observation x = clip((s - c1) / h1 * h2 + c2, lo, hi), every operation rounded on its own, and take
+ * their branch-free emission code for a window whose [lo, hi] lies inside every uniform emission's support and whose c1 and h1 are
+ * numbers (NaN c1 or h1: a window of missing observations).  tracts != 0 (mode 0, a model with strq_model_set_tracts): the
+ * wide-payload count launch of strq_viterbi_tracts -- never the register-resident kernel -- and tract_counts[3 i .. 3 i + 2] as that
+ * call returns them (`counted` then holds the raw payload); tract_counts may be NULL otherwise.  Everything else as
+ * strq_debug_viterbi_mode.  STRQ_ERR_ARG: a source kind other than 1 or 2, h1 == 0, lo > hi (or either not a number), a float64
+ * sample that is not a number (the branch-free code has no test for a missing observation; the pipeline never hands it one),
+ * tracts with another mode or a model without tracts.  STRQ_ERR_UNSUPPORTED exactly where strq_debug_viterbi_mode returns it. */
+int strq_debug_viterbi_sourced(strq_ctx* ctx, int32_t model_id, int32_t mode, int32_t src_kind, int32_t tracts, int64_t n_seq,
+                               const void* samples, const int64_t* x_off, const double* consts,
+                               double* logp, int64_t* counted, int32_t* status, uint32_t* dbg, void* records, const int64_t* rec_off,
+                               int64_t* tract_counts, int32_t* launched);
 
 /* Test hook, host only (no context, no device): the integer frame the upper-bound screen would run in for these alignment
  * parameters (open_h, ext_h, open_v, ext_v, dist_offset, dist_min; src/align_raw.h:84-103) and reads of up to `max_n` samples.

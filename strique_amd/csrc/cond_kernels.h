@@ -31,6 +31,9 @@ int launch_medfilt_f64(hipStream_t s, const double* raw, double* flt, const Read
 // float64 reads: median, MAD, f_c1, f_h1 and the status of every read from its filtered samples, r_c1, r_h1 from the raw ones when `raw` is
 // given; chunk_sums: one double per 8192 samples of a read, read i's at chunk_first[i]
 int launch_f64_stats(hipStream_t s, const double* flt, const double* raw, ReadCond* rc, int n_reads, double* chunk_sums, const int64_t* chunk_first);
+// float64 reads whose statistics came from the caller (strq_detect_batch: host_stats): a read whose filtered samples hold a NaN gets
+// what launch_f64_stats gives it -- NaN med, mad, f_c1, f_h1 and COND_DEGENERATE -- and NaN r_c1, r_h1 where `raw` is given and holds one
+int launch_f64_nan_guard(hipStream_t s, const double* flt, const double* raw, ReadCond* rc, int n_reads);
 // which: 0 = filtered int16 histogram (fills med, mad, f_*), 1 = 8-bit histogram (fills m_* and level_val),
 //        2 = raw int16 histogram (fills r_*)
 int launch_hist_stats(hipStream_t s, const uint32_t* hist, int nbins, int bias, ReadCond* rc, int n_reads,

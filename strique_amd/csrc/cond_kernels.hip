@@ -764,6 +764,31 @@ f64_stats_kernel(const double* __restrict__ flt_all, const double* __restrict__ 
     }
 }
 
+// float64 reads with the caller's statistics: the six scalars say nothing about the samples.  The decode kernels take their
+// branch-free emission code for a window whose constants are numbers (viterbi_kernels.hip: fast_em) and that code has no test for a
+// missing observation -- so a read with a NaN among its filtered samples gets here what f64_stats_kernel gives it ("NaN in, NaN
+// out"): its windows are then all NaN and decode by the missing-observation rule, and its row has status 1.
+// One workgroup per (read, signal) as there: signal 0 the filtered samples, 1 the raw ones.
+__global__ void __launch_bounds__(256)
+f64_nan_guard_kernel(const double* __restrict__ flt_all, const double* __restrict__ raw_all, ReadCond* __restrict__ rc_all)
+{
+    __shared__ int s_flag;
+    const int t = threadIdx.x, which = blockIdx.y;
+    ReadCond& rc = rc_all[blockIdx.x];
+    const int n = rc.n;
+    const double* x = (which == 0 ? flt_all : raw_all) + rc.off;
+    if (t == 0) s_flag = 0;
+    __syncthreads();
+    { int bad = 0;
+      for (int i = t; i < n; i += 256) { const double v = x[i]; bad |= !(v == v); }
+      if (bad) s_flag = 1; }
+    __syncthreads();
+    if (t != 0 || !s_flag) return;
+    const double nan = __builtin_nan("");
+    if (which == 0) { rc.med = nan; rc.mad = nan; rc.f_c1 = nan; rc.f_h1 = nan; rc.status = COND_DEGENERATE; }
+    else { rc.r_c1 = nan; rc.r_h1 = nan; }
+}
+
 static inline dim3 tile_grid(int max_n, int n_reads) { return dim3((max_n + 7 + COND_TILE - 1) / COND_TILE, n_reads); }      // + 7: tiles may start up to seven samples in front of a read
 
 int launch_medfilt_hist_i16(hipStream_t s, const int16_t* raw, int16_t* flt, const ReadCond* rc, int n_reads, int max_n,
@@ -791,6 +816,12 @@ int launch_f64_stats(hipStream_t s, const double* flt, const double* raw, ReadCo
 {
     if (n_reads <= 0) return 0;
     hipLaunchKernelGGL(f64_stats_kernel, dim3(n_reads, raw ? 2 : 1), dim3(F64S_THREADS), 0, s, flt, raw, rc, chunk_sums, chunk_first);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+int launch_f64_nan_guard(hipStream_t s, const double* flt, const double* raw, ReadCond* rc, int n_reads)
+{
+    if (n_reads <= 0) return 0;
+    hipLaunchKernelGGL(f64_nan_guard_kernel, dim3(n_reads, raw ? 2 : 1), dim3(256), 0, s, flt, raw, rc);
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 int launch_hist_stats(hipStream_t s, const uint32_t* hist, int nbins, int bias, ReadCond* rc, int n_reads, PoreStats ps,

@@ -1618,6 +1618,9 @@ static int condition_part(strq_ctx* c, DetectState* d, const SubBatch& S, int i0
             STRQ_HIP(c, hipMemcpyAsync(d->f64s.p, first.data(), ((size_t)np + 1) * 8, hipMemcpyHostToDevice, st));
             bad |= launch_f64_stats(st, reinterpret_cast<const double*>(S.flt_base), S.any_mod ? reinterpret_cast<const double*>(S.raw) : nullptr, d_rc, np,
                                     reinterpret_cast<double*>(d->f64s.as<char>() + first_bytes), d->f64s.as<int64_t>());
+        } else {
+            // the caller's statistics: nothing ties them to the samples -- a NaN among them makes the read degenerate
+            bad |= launch_f64_nan_guard(st, reinterpret_cast<const double*>(S.flt_base), S.any_mod ? reinterpret_cast<const double*>(S.raw) : nullptr, d_rc, np);
         }
         bad |= launch_quant_morph_f64(st, reinterpret_cast<const double*>(S.flt_base), S.levels, d_rc, np, longest, hist8);
     }

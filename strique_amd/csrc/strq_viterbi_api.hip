@@ -758,12 +758,14 @@ int strq_viterbi_batch(strq_ctx* c, int32_t model_id, int64_t n_seq, const doubl
     return STRQ_OK;
 }
 
-// Test hook: one launch_viterbi of `mode` over the windows, on buffers of the call's own (strique_hip.h).
-int strq_debug_viterbi_mode(strq_ctx* c, int32_t model_id, int32_t mode, int64_t n_seq, const double* x, const int64_t* x_off,
-                            double* logp, int64_t* counted, int32_t* status, uint32_t* dbg, void* records, const int64_t* rec_off,
-                            int32_t* launched)
+// The two test hooks below: one launch_viterbi of `mode` over the windows, on buffers of the call's own (strique_hip.h).  src_kind
+// VIT_SRC_F64: x holds the observations themselves, consts is not read; the affine kinds: x holds int16 / float64 samples and
+// consts six doubles per window (c1, h1, h2, c2, lo, hi) -- what window_task() (scan_kernels.h) gives the pipeline's windows.
+// tracts: the wide-payload count launch of strq_viterbi_tracts (sorted order, never the register-resident image).
+static int debug_viterbi_launch(strq_ctx* c, int32_t model_id, int32_t mode, int64_t n_seq, int32_t src_kind, const void* x, const int64_t* x_off,
+                                const double* consts, bool tracts, double* logp, int64_t* counted, int32_t* status, uint32_t* dbg,
+                                void* records, const int64_t* rec_off, int64_t* tract_counts, int32_t* launched)
 {
-    STRQ_ENTER(c);
     const char* bad = "bad argument";
     if (model_id < 0 || model_id >= (int32_t)c->models.size() || !c->models[model_id] || n_seq < 1 || n_seq > 8192 || !x_off || !launched || x_off[0] != 0) { c->err = bad; return STRQ_ERR_ARG; }
     if (mode != VIT_COUNT && mode != VIT_MARK && mode != VIT_HUB && mode != VIT_UNIT) { c->err = "bad argument (mode: count, mark, hub or unit)"; return STRQ_ERR_ARG; }
@@ -777,30 +779,46 @@ int strq_debug_viterbi_mode(strq_ctx* c, int32_t model_id, int32_t mode, int64_t
     }
     const int64_t tot = x_off[n_seq];
     if (tot > 0 && !x) { c->err = bad; return STRQ_ERR_ARG; }
+    const size_t esz = src_kind == VIT_SRC_I16_AFFINE ? 2 : 8;
+    if (src_kind != VIT_SRC_F64) {
+        if (!consts) { c->err = bad; return STRQ_ERR_ARG; }
+        for (int64_t i = 0; i < n_seq; ++i) {
+            const double* k = consts + 6 * i;
+            if (k[1] == 0.0 || !(k[4] <= k[5])) { c->err = "bad argument (window constants: h1 must not be 0, lo must not exceed hi)"; return STRQ_ERR_ARG; }
+        }
+        // the branch-free emission code has no test for a missing observation: samples are numbers
+        if (src_kind == VIT_SRC_F64_AFFINE)
+            for (int64_t i = 0; i < tot; ++i) { const double v = static_cast<const double*>(x)[i]; if (v != v) { c->err = "bad argument (a float64 sample is not a number)"; return STRQ_ERR_ARG; } }
+    }
     HostModel* hm = c->models[model_id];
-    const int shape = vit_shape_for(hm->h, (VitMode)mode);
+    if (tracts && (mode != VIT_COUNT || !hm->h.tract_inc || !tract_counts)) { c->err = "bad argument (tract payload: a count launch of a model with tracts)"; return STRQ_ERR_ARG; }
+    const int shape = tracts ? vit_shape_of(hm->h) : vit_shape_for(hm->h, (VitMode)mode);
     launched[0] = shape;
     if (shape < 0 || !vit_mode_ok(shape, mode) || (mode == VIT_HUB && hm->h.rec_state < 0) || (mode == VIT_UNIT && !vit_unit_ok(hm->h, shape))) {
         c->err = "the model has no launch of this decode mode"; return STRQ_ERR_UNSUPPORTED;
     }
     hipStream_t st = c->stream;
     const size_t rec_bytes = rec ? (size_t)rec_off[n_seq] : 0;
-    DevBuf b_x, b_tasks, b_res, b_rec, b_queue;
-    STRQ_HIP(c, b_x.reserve((size_t)tot * 8 + 64)); STRQ_HIP(c, b_tasks.reserve((size_t)n_seq * sizeof(VitTask)));
+    DevBuf b_x, b_tasks, b_res, b_rec, b_queue, b_order;
+    STRQ_HIP(c, b_x.reserve((size_t)tot * esz + 64)); STRQ_HIP(c, b_tasks.reserve((size_t)n_seq * sizeof(VitTask)));
     STRQ_HIP(c, b_res.reserve((size_t)n_seq * sizeof(VitResult))); STRQ_HIP(c, b_rec.reserve(rec_bytes + 64)); STRQ_HIP(c, b_queue.reserve(64));
+    if (tracts) STRQ_HIP(c, b_order.reserve((size_t)n_seq * sizeof(int) + 64));
     std::vector<VitTask> tasks((size_t)n_seq);
     for (int64_t i = 0; i < n_seq; ++i) {
         VitTask& t = tasks[(size_t)i];
         std::memset(&t, 0, sizeof(t));
-        t.model = hm->dev; t.sig = b_x.as<double>() + x_off[i]; t.T = x_off[i + 1] - x_off[i]; t.src_kind = VIT_SRC_F64;
+        t.model = hm->dev; t.sig = b_x.as<char>() + (size_t)x_off[i] * esz; t.T = x_off[i + 1] - x_off[i]; t.src_kind = src_kind;
+        if (src_kind != VIT_SRC_F64) { const double* k = consts + 6 * i; t.c1 = k[0]; t.h1 = k[1]; t.h2 = k[2]; t.c2 = k[3]; t.lo = k[4]; t.hi = k[5]; }
         if (rec) t.bp = reinterpret_cast<uint16_t*>(b_rec.as<char>() + rec_off[i]);
     }
-    if (tot) STRQ_HIP(c, hipMemcpyAsync(b_x.p, x, (size_t)tot * 8, hipMemcpyHostToDevice, st));
+    if (tot) STRQ_HIP(c, hipMemcpyAsync(b_x.p, x, (size_t)tot * esz, hipMemcpyHostToDevice, st));
     STRQ_HIP(c, hipMemcpyAsync(b_tasks.p, tasks.data(), (size_t)n_seq * sizeof(VitTask), hipMemcpyHostToDevice, st));
     STRQ_HIP(c, hipMemsetAsync(b_res.p, 0, (size_t)n_seq * sizeof(VitResult), st));
     STRQ_HIP(c, hipMemsetAsync(b_rec.p, 0, rec_bytes + 64, st));
     STRQ_HIP(c, hipMemsetAsync(b_queue.p, 0, 64, st));
-    const int lrc = launch_viterbi(st, shape, hm->h.n_cells, b_tasks.as<VitTask>(), b_res.as<VitResult>(), (int)n_seq, b_queue.as<int>(), c->n_cu, (VitMode)mode);
+    if (tracts && launch_vit_sort(st, b_tasks.as<VitTask>(), (int)n_seq, b_order.as<int>())) { (void)hipStreamSynchronize(st); c->err = "sort launch failed"; return STRQ_ERR_DEVICE; }
+    const int lrc = launch_viterbi(st, shape, hm->h.n_cells, b_tasks.as<VitTask>(), b_res.as<VitResult>(), (int)n_seq, b_queue.as<int>(), c->n_cu, (VitMode)mode,
+                                   tracts ? b_order.as<int>() : nullptr, 0, tracts);
     if (lrc) { (void)hipStreamSynchronize(st); c->err = "viterbi launch failed"; return viterbi_launch_status(lrc); }
     std::vector<VitResult> res((size_t)n_seq);
     STRQ_HIP(c, hipMemcpyAsync(res.data(), b_res.p, (size_t)n_seq * sizeof(VitResult), hipMemcpyDeviceToHost, st));
@@ -812,8 +830,30 @@ int strq_debug_viterbi_mode(strq_ctx* c, int32_t model_id, int32_t mode, int64_t
         if (counted) counted[i] = r.counted;
         if (status) status[i] = r.status;
         if (dbg) std::memcpy(dbg + 4 * i, r.dbg, sizeof(r.dbg));
+        if (tracts) {          // as strq_viterbi_tracts unpacks them
+            const uint64_t pay = r.status == 0 ? (uint64_t)r.counted : 0;
+            for (int j = 0; j < VIT_TRACTS_MAX; ++j) tract_counts[3 * i + j] = (int64_t)((pay >> (VIT_TRACT_BITS * j)) & (((uint64_t)1 << VIT_TRACT_BITS) - 1));
+        }
     }
     return STRQ_OK;
+}
+
+int strq_debug_viterbi_mode(strq_ctx* c, int32_t model_id, int32_t mode, int64_t n_seq, const double* x, const int64_t* x_off,
+                            double* logp, int64_t* counted, int32_t* status, uint32_t* dbg, void* records, const int64_t* rec_off,
+                            int32_t* launched)
+{
+    STRQ_ENTER(c);
+    return debug_viterbi_launch(c, model_id, mode, n_seq, VIT_SRC_F64, x, x_off, nullptr, false, logp, counted, status, dbg, records, rec_off, nullptr, launched);
+}
+
+int strq_debug_viterbi_sourced(strq_ctx* c, int32_t model_id, int32_t mode, int32_t src_kind, int32_t tracts, int64_t n_seq,
+                               const void* samples, const int64_t* x_off, const double* consts,
+                               double* logp, int64_t* counted, int32_t* status, uint32_t* dbg, void* records, const int64_t* rec_off,
+                               int64_t* tract_counts, int32_t* launched)
+{
+    STRQ_ENTER(c);
+    if (src_kind != VIT_SRC_F64_AFFINE && src_kind != VIT_SRC_I16_AFFINE) { c->err = "bad argument (source kind: 1 float64 samples, 2 int16 samples)"; return STRQ_ERR_ARG; }
+    return debug_viterbi_launch(c, model_id, mode, n_seq, src_kind, samples, x_off, consts, tracts != 0, logp, counted, status, dbg, records, rec_off, tract_counts, launched);
 }
 
 int strq_model_set_forward_logp(strq_ctx* c, int32_t model_id, const double* in_logp_sum)

@@ -181,6 +181,7 @@ def debug_mod_llr_image(baked):
 
 VIT_COUNT, VIT_BACKPTR, VIT_MARK, VIT_HUB, VIT_UNIT = range(5)
 VIT_SHAPE_CSR, VIT_SHAPE_G2, VIT_SHAPE_SS = 8, 9, 16
+VIT_SRC_F64, VIT_SRC_F64_AFFINE, VIT_SRC_I16_AFFINE = 0, 1, 2          # how a window is given (csrc/vit_model.h)
 
 
 def debug_viterbi_plan(baked):
@@ -380,8 +381,20 @@ class Context(object):
         """strq_debug_viterbi_mode: one Viterbi launch of decode mode `mode` (VIT_COUNT, VIT_MARK, VIT_HUB, VIT_UNIT) over the windows
         `seqs` (float64 arrays).  Returns a dict of raw results: 'logp', 'counted', 'status', 'dbg' (n, 4 uint32), 'records' (per
         window: hub T + 1 uint64, unit (T, 2) uint32, else None) and 'launched' (the shape id that ran)."""
+        return self._debug_viterbi(model_id, mode, seqs, VIT_SRC_F64, None, False, False)
+
+    def debug_viterbi_sourced(self, model_id, mode, kind, samples, consts, tracts=False):
+        """strq_debug_viterbi_sourced: the same launch over windows given as the detect pipeline gives them -- `samples` a list of
+        int16 (kind VIT_SRC_I16_AFFINE) or float64 (VIT_SRC_F64_AFFINE) arrays, `consts` one (c1, h1, h2, c2, lo, hi) per window.
+        The dict of debug_viterbi_mode; with `tracts` (a count launch of a model with tracts) also 'tract_counts' (n, 3 int64)."""
+        consts = _c(consts, np.float64).reshape(-1, 6)
+        if len(consts) != len(samples):
+            raise ValueError("consts must have one row per window")
+        return self._debug_viterbi(model_id, mode, samples, kind, consts, tracts, True)
+
+    def _debug_viterbi(self, model_id, mode, seqs, kind, consts, tracts, sourced):
         n = len(seqs)
-        x, x_off = _offsets(seqs, np.float64)
+        x, x_off = _offsets(seqs, np.int16 if kind == VIT_SRC_I16_AFFINE else np.float64)
         logp = np.zeros(n); counted = np.zeros(n, np.int64); status = np.zeros(n, np.int32); dbg = np.zeros((n, 4), np.uint32)
         launched = np.full(1, -1, np.int32)
         rec = rec_off = None
@@ -390,14 +403,24 @@ class Context(object):
             for i, s in enumerate(seqs):
                 rec_off[i + 1] = rec_off[i] + (8 * (len(s) + 1) if mode == VIT_HUB else 8 * len(s))
             rec = np.full(int(rec_off[-1]) + 8, 0xA5, np.uint8)
-        self._check(self._lib.strq_debug_viterbi_mode(self._h, ctypes.c_int32(model_id), ctypes.c_int32(mode), ctypes.c_int64(n), _ptr(x), _ptr(x_off),
-                                                      _ptr(logp), _ptr(counted), _ptr(status), _ptr(dbg), _ptr(rec), _ptr(rec_off), _ptr(launched)))
+        tcounts = np.zeros((n, 3), np.int64) if tracts else None
+        if not sourced:
+            self._check(self._lib.strq_debug_viterbi_mode(self._h, ctypes.c_int32(model_id), ctypes.c_int32(mode), ctypes.c_int64(n), _ptr(x), _ptr(x_off),
+                                                          _ptr(logp), _ptr(counted), _ptr(status), _ptr(dbg), _ptr(rec), _ptr(rec_off), _ptr(launched)))
+        else:
+            self._check(self._lib.strq_debug_viterbi_sourced(self._h, ctypes.c_int32(model_id), ctypes.c_int32(mode), ctypes.c_int32(kind),
+                                                             ctypes.c_int32(1 if tracts else 0), ctypes.c_int64(n), _ptr(x), _ptr(x_off), _ptr(consts),
+                                                             _ptr(logp), _ptr(counted), _ptr(status), _ptr(dbg), _ptr(rec), _ptr(rec_off), _ptr(tcounts),
+                                                             _ptr(launched)))
         records = [None] * n
         if rec is not None:
             for i in range(n):
                 raw = rec[int(rec_off[i]):int(rec_off[i + 1])]
                 records[i] = raw.view(np.uint64).copy() if mode == VIT_HUB else raw.view(np.uint32).reshape(-1, 2).copy()
-        return {"logp": logp, "counted": counted, "status": status, "dbg": dbg, "records": records, "launched": int(launched[0])}
+        out = {"logp": logp, "counted": counted, "status": status, "dbg": dbg, "records": records, "launched": int(launched[0])}
+        if tracts:
+            out["tract_counts"] = tcounts
+        return out
 
     def forward_batch(self, model_id, xs, c0=None):
         """strq_forward_batch: xs a list of float64 arrays; c0 None or one int per window (the moments are accumulated about it:

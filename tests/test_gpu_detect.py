@@ -253,6 +253,47 @@ def test_float64_reads_with_the_callers_own_statistics(gpu_counter, pm, targets)
     assert (own["count"] > 0).sum() >= 5
 
 
+def test_nan_samples_under_the_callers_own_statistics(gpu_counter, want, orc, pm, targets):
+    """The six scalars a caller hands over say nothing about the samples.  A float64 read with a run of NaN samples -- one that
+    survives the median filter -- under statistics that are numbers (here: those of the same read without the NaNs) must not reach
+    the HMM kernels as a window with finite constants: their branch-free emission code has no test for a missing observation.  The
+    library gives such a read what its own statistics give it -- an undefined normalisation, status 1 -- and the row is the
+    oracle's (whose np.median of the filtered signal is NaN).  A lone NaN is dropped by the median filter (np.sort's order) and
+    changes nothing but that sample: with numpy's statistics of that read the row is the oracle's, status 0."""
+    import warnings
+    from strique_amd import ffi
+    ctx = gpu_counter.ctx
+    sigs, tids, stats, rows = [], [], [], []
+    with np.errstate(all="ignore"), warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        for k, (name, strand) in enumerate((("c9orf72", "+"), ("fmr1", "-"))):
+            clean = _read(pm, targets, name, strand, 5000, 30, 900 + k, as_int16=False)
+            w = want(name, clean, strand)
+            assert w[0] == 30
+            mid = int(w[4] + w[5] // 2)          # inside the repeat: inside the decoded window
+            run = clean.copy(); run[mid:mid + 3] = np.nan
+            lone = clean.copy(); lone[mid] = np.nan
+            def one(s):          # numpy's six scalars of a read (STRique.py:142-143, 152-160), the filter in np.sort's order
+                flt = orc.medfilt3(s)
+                q_lo, q_hi = np.percentile(flt, [1, 99])
+                m_lo = np.median(flt[flt < q_lo]); m_hi = np.median(flt[flt > q_hi])
+                return np.array([np.median(flt), orc.mad(flt), m_lo + (m_hi - m_lo) / 2, (m_hi - m_lo) / 2, 0.0, 1.0])
+            assert np.array_equal(one(clean), ffi.host_stats(clean, np.array([0, len(clean)], np.int64))[0])
+            assert np.isfinite(one(clean)).all() and np.isfinite(one(lone)).all() and np.isnan(one(run)[:4]).all()
+            for s, hs in ((clean, one(clean)), (run, one(clean)), (lone, one(lone))):
+                sigs.append(s); tids.append(gpu_counter._classifier_for(name, strand).target_id); stats.append(hs); rows.append(want(name, s, strand))
+    off = np.zeros(len(sigs) + 1, np.int64); off[1:] = np.cumsum([len(s) for s in sigs])
+    flat = np.concatenate(sigs)
+    given = ctx.detect_batch(flat, off, tids, host_stats=np.array(stats))
+    own = ctx.detect_batch(flat, off, tids)
+    assert given.tobytes() == own.tobytes()
+    for i, (g, w) in enumerate(zip(given, rows)):
+        row = (int(g["count"]), float(g["score_prefix"]), float(g["score_suffix"]), float(g["log_p"]), int(g["offset"]), int(g["ticks"]))
+        assert row == tuple(w[:6]), (i, row, w)
+        assert int(g["status"]) == (1 if i % 3 == 1 else 0), (i, g)
+    assert [int(g["count"]) for g in given] == [30, 0, 30, 30, 0, 30]
+
+
 def test_sub_batches_give_the_same_results(gpu_counter, want, pm, targets, monkeypatch):
     """A batch larger than one sub-batch is processed in pieces (strq_batch_run); the pieces must not
     see each other: results equal those of the one-piece run, in input order."""

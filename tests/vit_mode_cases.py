@@ -6,7 +6,11 @@ kernels against them through strq_debug_viterbi_mode.
 Reference A comes from the oracle's state path (orc.viterbi: bit-exact log-probability, ties to the lowest source).  Reference B is
 a float64 DP of its own, written from the contract in vit_model.h: it carries the three payloads along the winner of every state
 (first of equal candidates, silent states in topological order) and so yields every record of every time step, also those off the
-best path."""
+best path.
+
+The last section gives the same models windows the way the detect pipeline hands them over -- int16 or float64 samples and a
+per-window map -- for tests/test_gpu_viterbi_sources.py (strq_debug_viterbi_sourced): the kernels then take another instantiation of
+their time loop than for plain float64 windows."""
 import math
 from collections import namedtuple
 
@@ -42,6 +46,7 @@ ROW_MODES = {0: (0, 1, 2, 4), 1: (0, 1, 2, 3), 2: (0, 1, 2, 3, 4), 3: (0, 1, 2, 
              SHAPE_CSR: (0, 1, 2), SHAPE_G2: (0, 2, 4)}
 SPECIAL_MU = (28.0, 34.0, 146.0, 152.0)          # hub, recording hub, counted 0, counted 1: outside every other emission
 UNI_LO, UNI_HI = 50.0, 130.0
+UNI_WIDE = (20.0, 160.0)          # a support that holds the special means too: the models of the clipped, sourced windows (below)
 
 
 def _baked(n, ne, start, end, ins, lps, kind, ea, eb, ec, count_inc, tag):
@@ -57,9 +62,10 @@ def _baked(n, ne, start, end, ins, lps, kind, ea, eb, ec, count_inc, tag):
                     np.full(n, -1, np.int32), np.full(n, -1, np.int32))
 
 
-def generated_model(row, multi, seed=0, fan=0):
+def generated_model(row, multi, seed=0, fan=0, support=(UNI_LO, UNI_HI)):
     """A baked model steered onto lane row `row` (single-stage unless `multi`); with fan > 8 every third emitting state gets that
-    many more in-edges and the model goes to the general kernel."""
+    many more in-edges and the model goes to the general kernel.  `support`: the range of its Uniform emissions (no random draw
+    depends on it: models of two supports differ in those three emission arrays only)."""
     sp = ROW_SPECS[row]
     rng = np.random.default_rng(9000 + 100 * row + 10 * int(multi) + seed + fan)
     ne, ns = sp["ne"], sp["ns"]
@@ -107,8 +113,8 @@ def generated_model(row, multi, seed=0, fan=0):
     mu = rng.uniform(60, 120, ne); sigma = rng.uniform(1.0, 4.0, ne)
     for s, m in zip(specials, SPECIAL_MU):
         mu[s] = m; sigma[s] = 1.5
-    ea = np.where(kind == 1, mu, UNI_LO); eb = np.where(kind == 1, 1.0 / (2 * sigma ** 2), UNI_HI)
-    ec = np.where(kind == 1, -np.log(sigma * 2.50662827463), -math.log(UNI_HI - UNI_LO))
+    ea = np.where(kind == 1, mu, support[0]); eb = np.where(kind == 1, 1.0 / (2 * sigma ** 2), support[1])
+    ec = np.where(kind == 1, -np.log(sigma * 2.50662827463), -math.log(support[1] - support[0]))
     tag = rng.choice(np.array([0, 1, 3, 4]), n).astype(np.int32)
     tag[ne:] = 0
     tag[specials[0]] = tag[specials[1]] = 2
@@ -183,8 +189,8 @@ def _standard_windows(make, rng, nopath_T=()):
     return wins
 
 
-def _generated_case(name, row, multi, fan=0):
-    bk = generated_model(row, multi, fan=fan)
+def _generated_case(name, row, multi, fan=0, support=(UNI_LO, UNI_HI)):
+    bk = generated_model(row, multi, fan=fan, support=support)
     rng = np.random.default_rng(77 + 13 * row + int(multi))
     wins = _standard_windows(lambda T: _walk_signal(bk, rng, T), rng)
     shape = SHAPE_CSR if fan else row
@@ -479,3 +485,175 @@ def reference_b(case, label, x):
            "unit_last": pay["up"][e], "hub_rec": hub_rec, "hub_live": hub_live, "unit_rec": unit_rec, "unit_live": unit_live, "tied": tied}
     _REF_B[key] = out
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Sourced windows: samples and a per-window map, the way the detect pipeline hands its windows to the kernels
+# ------------------------------------------------------------------------------------------------------------------------
+# The kernels read observation x' = clip((s - c1) / h1 * h2 + c2, lo, hi) from int16 or float64 samples s (hmm_wave.h:
+# vit_observation) and, once per window, evaluate
+#     fast = lo >= max(lower bounds of the Uniform emissions) and hi <= min(upper bounds) and c1 == c1 and h1 == h1
+# -- true: the branch-free instantiation of the whole time loop, false: the general one that plain float64 windows take.  The
+# generated models above keep their special states outside the Uniform support 50..130; a clip range inside it would tear every
+# window off those states.  Their "wide" twins (support 20..160, everything else equal) keep hub and unit chains under a clip of
+# 20.5..159.5.
+VIT_SRC_F64_AFFINE, VIT_SRC_I16_AFFINE = 1, 2
+WIDE_CLIP = (UNI_WIDE[0] + 0.5, UNI_WIDE[1] - 0.5)
+BOUNDARY_CLIP = (40.0, 160.0)          # (the boundary models have no Uniform emission: any range gives the branch-free code)
+# non-dyadic constants of the pipeline's magnitude: a sample step is h2 / h1 = 0.21 pA
+MAP_C1, MAP_H1, MAP_H2, MAP_C2 = 417.3, 61.7, 13.1, 90.2
+WIDE_NAMES = ["wide_row%d_%s" % (row, v) for row in range(8) for v in ("ss", "multi")] + ["wide_general"]
+STRIQUE_NAMES = [n for n in CASE_NAMES if n.startswith(("flanked_", "tie_", "dual_"))]
+BOUNDARY_NAMES = ["boundary_ss", "boundary_multi", "boundary_csr"]
+SOURCED_NAMES = WIDE_NAMES + BOUNDARY_NAMES + STRIQUE_NAMES
+# one model per kernel family meets the edges of the predicate: a lane row single-stage, one multi-stage, row 7 (the variant that
+# skips the arithmetic of its upper slots), the general kernel and a flanked model on the register-resident kernel
+EDGE_NAMES = ("wide_row2_ss", "wide_row4_multi", "wide_row7_ss", "wide_general", "flanked_c9orf72")
+
+# `fast`: what the predicate is to give for the window; x_prime is the window both references decode
+Sourced = namedtuple("Sourced", ["label", "kind", "samples", "consts", "x_prime", "fast"])
+
+_WIDE = {}
+_SOURCED = {}
+
+
+def narrow_name(name):
+    return name[len("wide_"):]
+
+
+def wide_cases():
+    """The generated cases once more, on models whose Uniform emissions span UNI_WIDE."""
+    if not _WIDE:
+        for row in sorted(ROW_SPECS):
+            for multi in (False, True):
+                c = _generated_case("wide_row%d_%s" % (row, "multi" if multi else "ss"), row, multi, support=UNI_WIDE)
+                _WIDE[c.name] = c
+        _WIDE["wide_general"] = _generated_case("wide_general", 1, True, fan=14, support=UNI_WIDE)
+    return _WIDE
+
+
+def sourced_cases(pm, pm_mod, cfg):
+    """name -> Case of every model that decodes sourced windows (SOURCED_NAMES)."""
+    both = dict(cases(pm, pm_mod, cfg)); both.update(wide_cases())
+    return {n: both[n] for n in SOURCED_NAMES}
+
+
+def uniform_bounds(bk):
+    """(largest lower bound, smallest upper bound) of the model's Uniform emissions; (-inf, inf) without one."""
+    uni = np.asarray(bk.emis_kind) == 2
+    if not uni.any():
+        return -np.inf, np.inf
+    return float(np.asarray(bk.emis_a)[uni].max()), float(np.asarray(bk.emis_b)[uni].min())
+
+
+def predicate(bk, consts):
+    """The kernels' choice of the branch-free code for a window of an affine source."""
+    c1, h1, h2, c2, lo, hi = consts
+    ulo, uhi = uniform_bounds(bk)
+    return bool(lo >= ulo and hi <= uhi and c1 == c1 and h1 == h1)
+
+
+def observations(samples, consts):
+    """x' of the samples, in the kernel's order of operations, every one rounded on its own."""
+    c1, h1, h2, c2, lo, hi = (np.float64(v) for v in consts)
+    v = (np.asarray(samples).astype(np.float64) - c1) / h1
+    v = v * h2 + c2
+    v = np.where(v < lo, lo, v)          # (a NaN stays: both comparisons are false)
+    v = np.where(v > hi, hi, v)
+    return v
+
+
+def sourced(case, label, x, kind, consts, clip_at=None):
+    """(samples, x_prime) of window `x`: samples from the inverse of the map, rounded to int16 or kept as float64, with -- windows of
+    at least 63 observations -- two samples that clip at lo and two at hi, the first of each an extreme of int16; clip_at: their
+    positions ((lo, lo), (hi, hi)).  NaN constants are inverted as the standard ones (the window is all NaN whatever the samples)."""
+    c1, h1, h2, c2, lo, hi = consts
+    ic1, ih1 = (c1 if c1 == c1 else MAP_C1), (h1 if h1 == h1 else MAP_H1)
+    inv = lambda v: (np.asarray(v, np.float64) - c2) / h2 * ih1 + ic1
+    s = inv(x)
+    T = len(x)
+    if T >= 63:
+        (la, lb), (ha, hb) = clip_at or ((3, T // 3), (T - 4, 2 * T // 3))
+        s[la] = -32768.0; s[lb] = inv(lo - 3.0); s[ha] = 32767.0; s[hb] = inv(hi + 3.0)
+    if kind == VIT_SRC_I16_AFFINE:
+        s = np.clip(np.rint(s), -32768, 32767).astype(np.int16)
+    return s, observations(s, consts)
+
+
+def _dual_mixed_window(bk):
+    """A window of the dual model whose units alternate between the two branches -- the means of the branch's match states, six
+    observations each, a little noise -- so that marks and hub records of both branches are on the best path (the case's own
+    windows are unmodified signal: one branch)."""
+    import re
+    def means(prefix):
+        st = sorted((int(re.fullmatch(prefix + r"(\d+)m", n).group(1)), i) for i, n in enumerate(bk.names) if re.fullmatch(prefix + r"\d+m", n))
+        return [float(bk.emis_a[i]) for _, i in st]
+    rng = np.random.default_rng(601)
+    mu = {"b": means("base"), "m": means("mod")}
+    return np.concatenate([np.repeat(mu[u], 6) + rng.normal(0.0, 0.4, 6 * len(mu[u])) for u in "bmmbmbbm"])
+
+
+def _sourced_windows(c):
+    bk = c.baked
+    w = dict(c.windows)
+    ulo, uhi = uniform_bounds(bk)
+    boundary = c.name in BOUNDARY_NAMES
+    clip = BOUNDARY_CLIP if boundary else (ulo + 0.5, uhi - 0.5)          # the pipeline's: model_min + 0.5 .. model_max - 0.5
+    if c.tie_prone:          # (every emission Uniform over 0..200) the range of the flanked model they were made from
+        flo, fhi = uniform_bounds(_CASES["flanked_" + c.name.split("_")[1]].baked)
+        clip = (flo + 0.5, fhi - 0.5)
+    short = (1, 2) if c.name in STRIQUE_NAMES else ()                     # no path that short in STRique's models
+    out = []
+
+    def add(label, x, kind, lo, hi, fast, c1=None, h1=None, clip_at=None):
+        i = len(out)          # every window its own map
+        consts = (MAP_C1 + 1.9 * i if c1 is None else c1, MAP_H1 + 0.3 * i if h1 is None else h1, MAP_H2, MAP_C2, lo, hi)
+        s, xp = sourced(c, label, x, kind, consts, clip_at)
+        out.append(Sourced(label, kind, s, consts, xp, fast))
+
+    if boundary:
+        for label, x in c.windows:          # clipped samples where they move no mark: low ones on the first level, high ones on the last
+            add("i16_" + label, x, VIT_SRC_I16_AFFINE, clip[0], clip[1], True, clip_at=((1, 3), (len(x) - 4, len(x) - 2)))
+        return out
+    base = w["T333"]
+    at = lambda T: w["T%d" % T] if ("T%d" % T) in w else (w["nopath_T%d" % T] if ("nopath_T%d" % T) in w else base[:T])
+    for T in T_LIST:
+        add(("nopath_i16_T%d" if T in short else "i16_T%d") % T, at(T), VIT_SRC_I16_AFFINE, clip[0], clip[1], True)
+    for T in (65, 333):
+        add("f64_T%d" % T, at(T), VIT_SRC_F64_AFFINE, clip[0], clip[1], True)
+    if c.name in STRIQUE_NAMES:          # their own windows, those that samples can hold (no NaN, no infinity)
+        for label, x in c.windows:
+            if not label.startswith(("T", "nopath")) and np.isfinite(x).all():
+                add("i16_" + label, x, VIT_SRC_I16_AFFINE, clip[0], clip[1], True)
+        for label in ("T40", "T75", "T130"):
+            if label in w:
+                add("i16_own_" + label, w[label], VIT_SRC_I16_AFFINE, clip[0], clip[1], True)
+    if c.name == "dual_ggcccc":
+        x = _dual_mixed_window(bk)
+        add("i16_mixed", x, VIT_SRC_I16_AFFINE, clip[0], clip[1], True)
+        add("f64_mixed", x, VIT_SRC_F64_AFFINE, clip[0], clip[1], True)
+    if c.name in EDGE_NAMES:
+        # the clip range equal to the tightest Uniform support; one ulp wider on either side -- the observations that sit on that
+        # limit are then outside an emission: the one way an affine source meets the general code; NaN constants: all NaN
+        x = at(150)
+        add("edge_eq_i16_T150", x, VIT_SRC_I16_AFFINE, ulo, uhi, True)
+        add("edge_eq_f64_T150", x, VIT_SRC_F64_AFFINE, ulo, uhi, True)
+        add("edge_lo_ulp_i16_T150", x, VIT_SRC_I16_AFFINE, np.nextafter(ulo, -np.inf), uhi, False)
+        add("edge_hi_ulp_f64_T150", x, VIT_SRC_F64_AFFINE, ulo, np.nextafter(uhi, np.inf), False)
+        add("edge_hi_ulp_i16_T150", x, VIT_SRC_I16_AFFINE, ulo, np.nextafter(uhi, np.inf), False)
+        add("edge_nan_c1_i16_T65", at(65), VIT_SRC_I16_AFFINE, clip[0], clip[1], False, c1=np.nan)
+        add("edge_nan_h1_f64_T65", at(65), VIT_SRC_F64_AFFINE, clip[0], clip[1], False, h1=np.nan)
+        add("edge_nan_h1_i16_T64", at(64), VIT_SRC_I16_AFFINE, clip[0], clip[1], False, h1=np.nan)
+    return out
+
+
+def sourced_windows(c):
+    """The sourced windows of a case (a list of Sourced), built once.  Labels are unique within the case and serve, behind "src:", as
+    the cache labels of the references on x_prime; a label that starts with "nopath" marks a window too short for any path."""
+    if c.name not in _SOURCED:
+        _SOURCED[c.name] = _sourced_windows(c)
+    return _SOURCED[c.name]
+
+
+def ref_label(sw):
+    return ("nopath_src:" if sw.label.startswith("nopath") else "src:") + sw.label
