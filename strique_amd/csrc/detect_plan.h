@@ -1,5 +1,5 @@
-// Host-side bookkeeping of the detect pipeline (strq_detect_api.hip) that needs no device: the optional per-read outputs and their
-// switches, the per-read rows of a batch, and the grouping of Viterbi tasks into launches.  Plain C++: no HIP headers.
+// Host-side bookkeeping of the detect pipeline (strq_detect_api.hip) that needs no device: the optional passes (switches, counters,
+// refusals), the ragged packer of their fetches, the per-read rows of a batch, and the grouping of Viterbi tasks into launches.  Plain C++: no HIP headers.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -28,16 +28,77 @@ struct Carve {
     template <class T> static T* at(void* base, size_t offset) { return base ? reinterpret_cast<T*>(static_cast<char*>(base) + offset) : nullptr; }
 };
 
-// The optional passes behind the count decode: unit positions (strq_set_units), forward pass (strq_set_confidence), per-unit scores
-// (strq_set_mod_llr).  DetectState holds what the next run call uses, a slot what its sub-batch was launched with, Batch what the last
-// run call ran with.
-// Anchored counting (strq_set_anchored) is the fourth: it comes with its score threshold.
-// The variant pass (strq_set_variants) is the fifth.
-// Renorm (strq_set_renorm) is the sixth, in front of the alignments instead of behind the decode: it comes with its share threshold.
-// Methylation calls of anchored reads (strq_set_anchored_mod) are the seventh: behind the anchored decode, which they need.
-// The tract pass (strq_set_tracts) is the eighth: where the forward pass runs, behind the rows.
+// The switches of the optional passes around the count decode (PASSES below lists them), and the thresholds anchored counting and renorm
+// come with.  DetectState holds what the next run call uses, a slot what its sub-batch was launched with, Batch what the last run call
+// ran with.
 struct Extras { bool units = false, conf = false, llr = false, anch = false, var = false; double anch_min = 0.0; bool renorm = false; double renorm_min = 0.0; bool amod = false;
                 bool tracts = false; };
+
+// The passes, said once.  What the last run call's pass did is one PassStats: the GPU milliseconds and up to seven counters, which the
+// pass's own enum names.  A row of PASSES holds what the entry points need of a pass: its name in messages, its switch, what a batch
+// that ran without it lacks and the entry that turns it on (the "ran without" refusal of its fetch), whether a scan refuses it, and the
+// layout strq_last_* hands out -- `out[k]` is the counter at position k, MS the milliseconds.
+enum Pass { PASS_UNITS, PASS_CONF, PASS_LLR, PASS_VAR, PASS_ANCH, PASS_AMOD, PASS_TRACTS, PASS_RENORM, N_PASS };
+struct PassStats { float ms; double v[7]; };
+enum { UNIT_BYTES, UNIT_READS, UNIT_POSITIONS, CONF_WINDOWS = 0, CONF_NOPATH, CONF_EXPO, LLR_UNITS = 0, LLR_READS, LLR_LAUNCHES,
+       VAR_LAUNCHES = 0, VAR_PASSAGES, VAR_READS, ANCH_KINDS = 0 /* .. 3: reads of kind 0 .. 3 */, ANCH_LAUNCHES = 4, ANCH_G2, ANCH_LANE,
+       AMOD_READS = 0, AMOD_UNITS, AMOD_LAUNCHES, TRACT_WINDOWS = 0, TRACT_LAUNCHES, TRACT_FAILED, RN_FITTED = 0, RN_APPLIED, RN_LAUNCHES };
+constexpr int8_t MS = -1;
+struct PassInfo { const char* name; bool Extras::* on; const char* lacks; const char* entry; bool scan_refuses; int n_out; int8_t out[8]; };
+constexpr PassInfo PASSES[N_PASS] = {
+    {"units", &Extras::units, "unit positions", "strq_set_units", false, 4, {MS, 0, 1, 2}},
+    {"confidence", &Extras::conf, "confidence", "strq_set_confidence", false, 4, {MS, 0, 1, 2}},
+    {"mod-llr", &Extras::llr, "per-unit scores", "strq_set_mod_llr", false, 4, {MS, 0, 1, 2}},
+    {"variants", &Extras::var, "variants", "strq_set_variants", true, 4, {VAR_LAUNCHES, VAR_PASSAGES, MS, VAR_READS}},
+    {"anchored", &Extras::anch, "anchored counting", "strq_set_anchored", true, 8, {MS, 0, 1, 2, 3, ANCH_LAUNCHES, ANCH_G2, ANCH_LANE}},
+    {"anchored-mod", &Extras::amod, "anchored methylation calls", "strq_set_anchored_mod", true, 4, {MS, 0, 1, 2}},
+    {"tracts", &Extras::tracts, "tracts", "strq_set_tracts", true, 4, {MS, 0, 1, 2}},
+    {"renorm", &Extras::renorm, "renorm", "strq_set_renorm", true, 4, {MS, 0, 1, 2}},
+};
+inline void pass_stats_out(Pass p, const PassStats& s, double* out)
+{
+    for (int k = 0; k < PASSES[p].n_out; ++k) out[k] = PASSES[p].out[k] == MS ? (double)s.ms : s.v[PASSES[p].out[k]];
+}
+// The pass a scan refuses first among those switched on, in the order the run call has always looked (N_PASS: none); the refusals as text
+constexpr Pass SCAN_CHECKS[] = {PASS_AMOD, PASS_ANCH, PASS_VAR, PASS_TRACTS, PASS_RENORM};
+inline Pass scan_refusal(const Extras& ex)
+{
+    for (Pass p : SCAN_CHECKS) if (PASSES[p].scan_refuses && ex.*PASSES[p].on) return p;
+    return N_PASS;
+}
+inline std::string scan_refusal_text(Pass p) { return std::string(PASSES[p].name) + ": not available in a scan (strq_scan_set)"; }
+inline std::string ran_without_text(Pass p) { return std::string("the last batch ran without ") + PASSES[p].lacks + " (" + PASSES[p].entry + ")"; }
+
+// off[0 .. n] of a ragged output of n reads, and with `pools` its values: len(i, &k, &k2) gives the elements read i adds to either pool,
+// copy(i, pos, pos2) puts them at those positions -- called only where both pools hold them (`cap`, `cap2`).  Returns n, or the read
+// whose values did not fit: off[] is then written up to that read.  Without pools it only measures.  off2 (or null) takes the second
+// pool's offsets per read, total2 (or null) its size.
+template <class Len, class Copy>
+int64_t pack_ragged2(int64_t n, int64_t* off, int64_t* off2, bool pools, int64_t cap, int64_t cap2, int64_t* total2, Len len, Copy copy)
+{
+    int64_t pos = 0, pos2 = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        off[i] = pos;
+        if (off2) off2[i] = pos2;
+        int64_t k = 0, k2 = 0;
+        len(i, &k, &k2);
+        if (pools) {
+            if (pos + k > cap || pos2 + k2 > cap2) return i;
+            copy(i, pos, pos2);
+        }
+        pos += k; pos2 += k2;
+    }
+    off[n] = pos;
+    if (off2) off2[n] = pos2;
+    if (total2) *total2 = pos2;
+    return n;
+}
+// ... with one pool: len(i) elements of read i, copy(i, pos)
+template <class Len, class Copy>
+int64_t pack_ragged(int64_t n, int64_t* off, bool pool, int64_t cap, Len len, Copy copy)
+{
+    return pack_ragged2(n, off, nullptr, pool, cap, 0, nullptr, [&](int64_t i, int64_t* k, int64_t*) { *k = len(i); }, [&](int64_t i, int64_t pos, int64_t) { copy(i, pos); });
+}
 
 // What the variant pass leaves per read: the passages of its variant-model decode (strq_batch_fetch_variants)
 struct VariantRow {
@@ -141,6 +202,20 @@ inline Grouping group_items(const std::vector<GroupItem>& items)
         G.groups.push_back(v);
     }
     return G;
+}
+
+// The order of a second decode of the reads `who` of a sub-batch (tract pass, anchored pass, forward pass): of(i, item, model) gives
+// the route, shape and cells of read i's model and the model's device image, or false for a read the pass cannot take (nothing is
+// planned then).  The launches, and per task position the read and its model.
+template <class Model> struct DecodeOrder { Grouping G; std::vector<int32_t> read_of; std::vector<const Model*> model; };
+template <class Model, class Of>
+bool decode_order(const std::vector<int>& who, Of of, DecodeOrder<Model>& out)
+{
+    std::vector<GroupItem> items(who.size()); std::vector<const Model*> mv(who.size());
+    for (size_t k = 0; k < who.size(); ++k) if (!of(who[k], items[k], mv[k])) return false;
+    out.G = group_items(items);
+    for (int32_t k : out.G.order) { out.read_of.push_back(who[(size_t)k]); out.model.push_back(mv[(size_t)k]); }
+    return true;
 }
 
 }  // namespace strq

@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -118,29 +119,22 @@ struct DetectState {
     DevBuf rc, hist16, hist8, geom, idx, hist_raw, bp, path, modtask, modsig, modlen, pattern, hrange, modpool, f64s;
     DevBuf unit_task, unit_ws, unit_path, unit_pool;      // unit pass (run_unit_pass): tasks, records / back-pointers, state paths, positions
     Extras extras;                       // strq_set_units, strq_set_confidence, strq_set_mod_llr: what the next run call uses
+    PassStats stats[N_PASS] = {}; double& stat(Pass p, int k) { return stats[p].v[k]; }      // strq_last_*: what every pass of the last run call did
     DevBuf llr_ws;                       // per-unit scores (run_llr_pass): tasks, unit bounds, scores
     DevBuf var_ws, var_bounds, var_out;  // variant pass (run_variant_tail): tasks and passage counts; passage bounds; scores
-    float var_ms = 0; double var_launches = 0, var_passages = 0, var_reads = 0;      // strq_last_variants: the last run call's variant pass
-    float llr_ms = 0; double llr_units = 0, llr_reads = 0, llr_launches = 0;      // strq_last_mod_llr: the last run call's scoring pass
     DevBuf conf_task;                    // forward pass (run_conf_pass): tasks, model images, c0, results, order
-    float conf_ms = 0; double conf_windows = 0, conf_nopath = 0, conf_expo = 0;      // strq_last_confidence: the last run call's forward pass
     DevBuf tract_ws, tract_task;         // tract pass (run_tract_pass): geometry and conditioning rows of a sub-batch; tasks, results, their reads and models
-    float tract_ms = 0; double tract_windows = 0, tract_launches = 0, tract_failed = 0;      // strq_last_tracts: the last run call's tract pass
     DevBuf anch_ws, anch_task;           // anchored pass (run_anchored_pass): geometry, conditioning rows and kinds of a sub-batch; tasks, results, their reads and models
-    float anch_ms = 0; double anch_kinds[4] = {}, anch_launches = 0, anch_g2 = 0, anch_lane = 0;      // strq_last_anchored: the last run call's anchored pass
     hipEvent_t amod_ev[2] = {};          // methylation calls of anchored reads (run_anchored_mod): their own bracket, inside the anchored pass
-    float amod_ms = 0; double amod_reads = 0, amod_units = 0, amod_launches = 0;      // strq_last_anchored_mod: the last run call's calls
     // renorm (run_renorm_part): the tables of the targets, the grid and the shares, the histograms and the per-read table rows of a sub-batch
     std::vector<std::unique_ptr<DevBuf>> rn_tables;
     RenormGrid rn_grid = {}; bool rn_have_grid = false;
     DevBuf rn_h, rn_reads;
     hipEvent_t rn_ev[4] = {}; int rn_timed = 0;      // one pair of events per piece of a sub-batch (at most two); pairs recorded by the sub-batch under way
-    float rn_ms = 0; double rn_fitted = 0, rn_applied = 0, rn_launches = 0;      // strq_last_renorm: the last run call's renorm pass
     // strq_scan_set: run calls compare these candidates (target ids) on every read instead of taking the read's own target
     bool scan_on = false; std::vector<int32_t> scan_cand; double scan_min = 0;
     DevBuf scan_idx, scan_out;           // scan: task table and candidate trims / winners, scores and raw scores of a sub-batch
     PinBuf scan_pin;                     // ... and what the host reads of them before the Viterbi launches are planned
-    float unit_ms = 0; double unit_bytes = 0, unit_reads = 0, unit_positions = 0;      // strq_last_units: the last run call's unit pass
     hipEvent_t ev[4] = {};
     int64_t part_reads = 0;              // strq_batch_upload_part: reads uploaded so far
     // Two sub-batches are in flight at a time: the Viterbi launches of sub-batch k run on `vit_stream` while the conditioning and the
@@ -264,6 +258,35 @@ static int launch_viterbi_group(strq_ctx* c, hipStream_t st, const VitGroup& g, 
     return viterbi_launch_status(vrc);
 }
 
+// The launches of a second decode of a sub-batch (unit pass, forward pass, tract pass, anchored pass, dual models), on stream `st` with
+// the context's queue heads: the heads are reset, then group by group the sort and the launch.  What differs between the passes:
+using GroupHook = std::function<int(const VitGroup&)>;
+struct GroupDecode {
+    VitTask* tasks; VitResult* results; int* order;      // the arrays the groups index; the order buffer is the slot's, or the pass's own
+    VitMode mode[2];                                     // decode mode of a group by its route (the unit pass alone has two routes)
+    const char* what; bool tracts;                       // who says that the shape has no such mode; the wide payload of the tract counts
+    double* launches;                                    // (or null) takes 2 for a sorted group, 1 otherwise
+    GroupHook before, after;                             // (or none) in front of a group's sort; behind its launch
+    std::function<int(const VitGroup&, int*)> launch;    // (or none) in place of sort and launch: the forward pass's own two on a queue head
+};
+static int launch_groups(strq_ctx* c, hipStream_t st, const std::vector<VitGroup>& groups, const GroupDecode& v)
+{
+    if (const int qrc = reset_queue_heads(c, st)) return qrc;
+    int qi = 0;
+    for (const VitGroup& g : groups) {
+        int* queue = c->queue.as<int>() + qi++;
+        if (v.before) { if (const int rc = v.before(g)) return rc; }
+        if (v.launch) { if (const int rc = v.launch(g, queue)) return rc; }
+        else {
+            if (const int src = sort_viterbi_group(c, st, g, v.tasks, v.order)) return src;
+            if (const int lrc = launch_viterbi_group(c, st, g, v.tasks, v.results, v.order, queue, v.mode[g.route], 0, v.what, v.tracts)) return lrc;
+            if (v.launches) *v.launches += group_order(v.order, g) ? 2 : 1;
+        }
+        if (v.after) { if (const int rc = v.after(g)) return rc; }
+    }
+    return STRQ_OK;
+}
+
 // read-back of the modification pass: the lengths first, then the strings gathered into a dense pool (the sparse buffer has one byte per
 // time step: ~180 MB per 4096 reads of 50 kb, 25 ms through pageable memory, for ~4 MB of strings)
 static int read_mod_patterns(strq_ctx* c, DetectState* d, int64_t r0, const std::vector<int>& who, const std::vector<int>& slot2, const std::vector<int64_t>& len,
@@ -305,18 +328,22 @@ static int llr_model(strq_ctx* c, HostModel* hm)
     return STRQ_OK;
 }
 
-// GPU time of a pass on the context's stream: pass_start before its first command, pass_stop behind its last one -- it waits for the
-// stream and adds the milliseconds in between to `total_ms`
-static int pass_start(strq_ctx* c, DetectState* d)
+// GPU time of a pass on the context's stream, between the events ev[0] and ev[1]: pass_start before its first command (it makes the
+// events if they are not there), pass_stop behind its last one -- it waits for the stream and adds the milliseconds in between to
+// `into`.  The passes share the pair pass_ev(d); the methylation calls of anchored reads run inside the anchored pass's bracket and
+// have a pair of their own (DetectState::amod_ev).
+static hipEvent_t* pass_ev(DetectState* d) { return d->ev + 2; }
+static int pass_start(strq_ctx* c, hipEvent_t* ev)
 {
-    STRQ_HIP(c, hipEventRecord(d->ev[2], c->stream));
+    for (int k = 0; k < 2; ++k) if (!ev[k]) STRQ_HIP(c, hipEventCreate(&ev[k]));
+    STRQ_HIP(c, hipEventRecord(ev[0], c->stream));
     return STRQ_OK;
 }
-static int pass_stop(strq_ctx* c, DetectState* d, float& total_ms)
+static int pass_stop(strq_ctx* c, hipEvent_t* ev, PassStats& into)
 {
-    STRQ_HIP(c, hipEventRecord(d->ev[3], c->stream));
+    STRQ_HIP(c, hipEventRecord(ev[1], c->stream));
     STRQ_HIP(c, hipStreamSynchronize(c->stream));
-    float ms = 0; STRQ_HIP(c, hipEventElapsedTime(&ms, d->ev[2], d->ev[3])); total_ms += ms;
+    float ms = 0; STRQ_HIP(c, hipEventElapsedTime(&ms, ev[0], ev[1])); into.ms += ms;
     return STRQ_OK;
 }
 
@@ -362,7 +389,7 @@ static int run_llr_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, cons
     }
     const int64_t U = unit_off[(size_t)nm];
     if (!U) return STRQ_OK;
-    if (const int rc = pass_start(c, d)) return rc;
+    if (const int rc = pass_start(c, pass_ev(d))) return rc;
     // reads with units, by kernel mode (states per lane / units per wave)
     std::vector<int> by_mode[3];
     for (int k = 0; k < nm; ++k) {
@@ -415,12 +442,12 @@ static int run_llr_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, cons
     std::vector<double> out((size_t)U * 2); std::vector<int32_t> bad((size_t)nb);
     STRQ_HIP(c, hipMemcpyAsync(out.data(), d_out, (size_t)U * 16, hipMemcpyDeviceToHost, st));
     STRQ_HIP(c, hipMemcpyAsync(bad.data(), d_bad, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
-    if (const int rc = pass_stop(c, d, in.anchored ? d->amod_ms : d->llr_ms)) return rc;
+    if (const int rc = pass_stop(c, pass_ev(d), d->stats[in.anchored ? PASS_AMOD : PASS_LLR])) return rc;
     for (int32_t b : bad) if (b) { c->err = "mod-llr: the unit bounds of a read disagree with its pattern"; return STRQ_ERR_DEVICE; }
     for (int k = 0; k < nm; ++k)
         if (n_units[(size_t)k]) (*in.scores)[(size_t)(r0 + who[k])].assign(out.begin() + (ptrdiff_t)(2 * unit_off[(size_t)k]), out.begin() + (ptrdiff_t)(2 * unit_off[(size_t)k + 1]));
-    if (in.anchored) { d->amod_launches += 1 + (double)launches.size(); return STRQ_OK; }
-    d->llr_units += (double)U; d->llr_reads += nb; d->llr_launches += 1 + (double)launches.size();
+    if (in.anchored) { d->stat(PASS_AMOD, AMOD_LAUNCHES) += 1 + (double)launches.size(); return STRQ_OK; }
+    d->stat(PASS_LLR, LLR_UNITS) += (double)U; d->stat(PASS_LLR, LLR_READS) += nb; d->stat(PASS_LLR, LLR_LAUNCHES) += 1 + (double)launches.size();
     return STRQ_OK;
 }
 
@@ -556,7 +583,7 @@ static int run_variant_tail(strq_ctx* c, DetectState* d, DetectState::Slot& sl, 
         launches += (double)ls.size();
         STRQ_HIP(c, hipMemcpyAsync(out.data(), d_out, nv * 8, hipMemcpyDeviceToHost, st));
     }
-    if (const int rc = pass_stop(c, d, d->var_ms)) return rc;
+    if (const int rc = pass_stop(c, pass_ev(d), d->stats[PASS_VAR])) return rc;
     for (int32_t b : bad) if (b) { c->err = no_chain; return STRQ_ERR_DEVICE; }
     for (int k = 0; k < nm; ++k) {
         const int i = who[k]; const Target& t = target_of(d, r0 + i);
@@ -573,9 +600,9 @@ static int run_variant_tail(strq_ctx* c, DetectState* d, DetectState::Slot& sl, 
         }
         row.V.assign(out.begin() + (ptrdiff_t)v_off[(size_t)k], out.begin() + (ptrdiff_t)v_off[(size_t)k + 1]);
         row.count_v = (int32_t)(units + t.count_bias);
-        d->var_reads += 1;
+        d->stat(PASS_VAR, VAR_READS) += 1;
     }
-    d->var_launches += launches; d->var_passages += passages;
+    d->stat(PASS_VAR, VAR_LAUNCHES) += launches; d->stat(PASS_VAR, VAR_PASSAGES) += passages;
     return STRQ_OK;
 }
 
@@ -693,7 +720,6 @@ static int dual_decode(strq_ctx* c, DetectState* d, DetectState::Slot& sl, Dual 
     if (launch_mod_compact(st, d_mt, nm, d_len)) { c->err = "compaction launch failed"; return STRQ_ERR_DEVICE; }
     R.launches += 1;
     // 3. Viterbi on the dual model
-    if (const int qrc = reset_queue_heads(c, st)) return qrc;
     for (int k = 0; k < nm; ++k) {
         R.tp2[slot2[k]] = d_path2 + R.p2_off[k];
         if (dev) continue;
@@ -701,14 +727,12 @@ static int dual_decode(strq_ctx* c, DetectState* d, DetectState::Slot& sl, Dual 
         v.model = dual_model(c, d, r0 + who[k], which)->dev; v.sig = mt[k].out; v.T = len[k]; v.src_kind = VIT_SRC_F64;
         v.bp = d->bp.as<uint16_t>() + R.bp2_off[k];
     }
-    int qi = 0;
-    for (const VitGroup& vg : G.groups) {
-        if (!dev) STRQ_HIP(c, hipMemcpyAsync(d_tb + vg.first, vt2.data() + vg.first, (size_t)vg.count * sizeof(VitTask), hipMemcpyHostToDevice, st));
-        if (const int src = sort_viterbi_group(c, st, vg, d_tb, sl.order.as<int>())) return src;
-        if (const int lrc = launch_viterbi_group(c, st, vg, d_tb, d_tr, sl.order.as<int>(), c->queue.as<int>() + qi++, use_hub ? VIT_HUB : VIT_BACKPTR)) return lrc;
-        R.launches += group_order(sl.order.as<int>(), vg) ? 2 : 1;
-    }
-    return STRQ_OK;
+    GroupHook upload;          // the tasks of a group go up in front of its sort
+    if (!dev) upload = [&](const VitGroup& vg) -> int {
+        STRQ_HIP(c, hipMemcpyAsync(d_tb + vg.first, vt2.data() + vg.first, (size_t)vg.count * sizeof(VitTask), hipMemcpyHostToDevice, st));
+        return STRQ_OK;
+    };
+    return launch_groups(c, st, G.groups, {d_tb, d_tr, sl.order.as<int>(), {use_hub ? VIT_HUB : VIT_BACKPTR}, "viterbi: ", false, &R.launches, upload});
 }
 
 // Step 4 behind dual_decode for a modification model: the pattern strings from the hub records, or from traced paths, into `dst`
@@ -778,7 +802,7 @@ static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, Dual
     }
     const int nm = (int)who.size();
     if (!nm) return STRQ_OK;
-    if (which == DUAL_VAR) { if (const int rc = pass_start(c, d)) return rc; }          // one bracket around the whole variant pass
+    if (which == DUAL_VAR) { if (const int rc = pass_start(c, pass_ev(d))) return rc; }          // one bracket around the whole variant pass
     // the samples decoded into repeat states: one contiguous stretch [enter, leave) of the window
     std::vector<int64_t> first(nm);
     R.len.resize(nm); R.raw_first.resize(nm);
@@ -820,7 +844,7 @@ static int run_unit_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, con
     const int64_t r0 = sl.r0;
     const ReadGeom* geom = sl.host().geom; const VitResult* vres = sl.host().vres;
     const std::vector<int>& who = dec.who; const std::vector<VitTask>& vt = dec.vt;
-    if (const int rc = pass_start(c, d)) return rc;
+    if (const int rc = pass_start(c, pass_ev(d))) return rc;
     const bool force_bp = strq::opt("STRQ_UNITS_BACKPOINTERS") != nullptr;
     size_t budget = (size_t)8 << 30;
     if (const char* e = strq::opt("STRQ_UNITS_WS_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
@@ -886,14 +910,11 @@ static int run_unit_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, con
         STRQ_HIP(c, hipMemcpyAsync(d_ut, uv.data(), (size_t)m * sizeof(UnitTask), hipMemcpyHostToDevice, st));
         STRQ_HIP(c, hipMemsetAsync(d_bad, 0, (size_t)m * 4, st));
         if (path_n) STRQ_HIP(c, hipMemsetAsync(d->unit_path.p, 0, path_n * 4, st));      // a traceback that stops early leaves valid states behind
-        if (const int qrc = reset_queue_heads(c, st)) return qrc;
-        int qi = 0;
-        for (const VitGroup& g : G.groups) {
-            const VitMode want = g.route == 0 ? VIT_UNIT : VIT_BACKPTR;          // unit records, or back-pointers and a traceback
-            if (const int src = sort_viterbi_group(c, st, g, d_vt, sl.order.as<int>())) return src;
-            if (const int lrc = launch_viterbi_group(c, st, g, d_vt, d_vr, sl.order.as<int>(), c->queue.as<int>() + qi++, want, 0, "unit pass: ")) return lrc;
-            if (want == VIT_BACKPTR && launch_vit_traceback(st, d_vt + g.first, d_vr + g.first, d_paths + g.first, g.count)) { c->err = "traceback launch failed"; return STRQ_ERR_DEVICE; }
-        }
+        const GroupHook trace = [&](const VitGroup& g) -> int {          // by route: unit records, or back-pointers and a traceback
+            if (g.route == 1 && launch_vit_traceback(st, d_vt + g.first, d_vr + g.first, d_paths + g.first, g.count)) { c->err = "traceback launch failed"; return STRQ_ERR_DEVICE; }
+            return STRQ_OK;
+        };
+        if (const int grc = launch_groups(c, st, G.groups, {d_vt, d_vr, sl.order.as<int>(), {VIT_UNIT, VIT_BACKPTR}, "unit pass: ", false, nullptr, nullptr, trace})) return grc;
         if (launch_unit_hop(st, d_ut, n_rec) || launch_unit_scan(st, d_ut + n_rec, m - n_rec)) { c->err = "unit position launch failed"; return STRQ_ERR_DEVICE; }
         std::vector<int64_t> pos(xo + 1); std::vector<int32_t> bad((size_t)m);
         if (xo) STRQ_HIP(c, hipMemcpyAsync(pos.data(), d->unit_pool.p, xo * 8, hipMemcpyDeviceToHost, st));
@@ -906,10 +927,10 @@ static int run_unit_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, con
             B.units[(size_t)(r0 + i)].assign(pos.begin() + (ptrdiff_t)pos_off[(size_t)k], pos.begin() + (ptrdiff_t)(pos_off[(size_t)k] + (size_t)n));
             B.unit_dec[(size_t)(r0 + i)] = 1;
         }
-        d->unit_bytes = std::max(d->unit_bytes, (double)bytes); d->unit_reads += m; d->unit_positions += (double)xo;
+        d->stat(PASS_UNITS, UNIT_BYTES) = std::max(d->stat(PASS_UNITS, UNIT_BYTES), (double)bytes); d->stat(PASS_UNITS, UNIT_READS) += m; d->stat(PASS_UNITS, UNIT_POSITIONS) += (double)xo;
         c0 = c1;
     }
-    return pass_stop(c, d, d->unit_ms);
+    return pass_stop(c, pass_ev(d), d->stats[PASS_UNITS]);
 }
 
 // Count confidence of the reads of one sub-batch (strq_set_confidence): the forward pass (forward_kernels.hip) over the windows the
@@ -922,16 +943,17 @@ static int run_conf_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, con
     const int64_t r0 = sl.r0;
     const VitResult* vres = sl.host().vres;
     const std::vector<int>& who = dec.who; const std::vector<VitTask>& vt = dec.vt;
-    if (const int rc = pass_start(c, d)) return rc;
+    if (const int rc = pass_start(c, pass_ev(d))) return rc;
     const int m = (int)who.size();
-    std::vector<GroupItem> items((size_t)m);
-    for (int k = 0; k < m; ++k) {
-        HostModel* hm = flank_model(c, d, r0 + who[(size_t)k]);
-        if (const int rc = forward_model(c, hm)) return rc;
-        items[(size_t)k] = {0, vit_shape_of(hm->h), hm->h.n_cells};
-    }
-    const Grouping G = group_items(items);
-    const std::vector<VitGroup>& launches = G.groups;
+    DecodeOrder<FwdModel> D; int frc = STRQ_OK;
+    decode_order(who, [&](int i, GroupItem& it, const FwdModel*& fm) {
+        HostModel* hm = flank_model(c, d, r0 + i);
+        if ((frc = forward_model(c, hm))) return false;
+        it = {0, vit_shape_of(hm->h), hm->h.n_cells}; fm = hm->fwd_dev;
+        return true;
+    }, D);
+    if (frc) return frc;
+    const std::vector<int32_t>& read_of = D.read_of; const std::vector<const FwdModel*>& fv = D.model;
     Carve lay;
     const size_t o_vt = lay.add<VitTask>((size_t)m), o_fr = lay.add<FwdResult>((size_t)m), o_fm = lay.add<const FwdModel*>((size_t)m),
                  o_c0 = lay.add<int64_t>((size_t)m), o_order = lay.add<int>((size_t)m);
@@ -939,28 +961,29 @@ static int run_conf_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, con
     void* tb = d->conf_task.p;
     VitTask* d_vt = Carve::at<VitTask>(tb, o_vt); FwdResult* d_fr = Carve::at<FwdResult>(tb, o_fr); const FwdModel** d_fm = Carve::at<const FwdModel*>(tb, o_fm);
     int64_t* d_c0 = Carve::at<int64_t>(tb, o_c0); int* d_order = Carve::at<int>(tb, o_order);
-    std::vector<VitTask> tv((size_t)m); std::vector<const FwdModel*> fv((size_t)m); std::vector<int64_t> cv((size_t)m); std::vector<int> read_of((size_t)m);
+    std::vector<VitTask> tv((size_t)m); std::vector<int64_t> cv((size_t)m);
     for (int at = 0; at < m; ++at) {
-        const int i = who[(size_t)G.order[(size_t)at]];
+        const int i = read_of[(size_t)at];
         tv[(size_t)at] = vt[(size_t)sl.vit_slot[i]]; tv[(size_t)at].bp = nullptr;
-        fv[(size_t)at] = flank_model(c, d, r0 + i)->fwd_dev; cv[(size_t)at] = vres[sl.vit_slot[i]].counted; read_of[(size_t)at] = i;
+        cv[(size_t)at] = vres[sl.vit_slot[i]].counted;
     }
     STRQ_HIP(c, hipMemcpyAsync(d_vt, tv.data(), (size_t)m * sizeof(VitTask), hipMemcpyHostToDevice, st));
     STRQ_HIP(c, hipMemcpyAsync(d_fm, fv.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
     STRQ_HIP(c, hipMemcpyAsync(d_c0, cv.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
-    if (const int qrc = reset_queue_heads(c, st)) return qrc;
     int every = 1;
     if (const char* e = strq::opt("STRQ_FWD_RESCALE_EVERY")) { const int v = atoi(e); if (v >= 1) every = v; }
-    int qi = 0;
-    for (const VitGroup& l : launches) {
+    GroupDecode gd = {};
+    gd.launch = [&](const VitGroup& l, int* queue) -> int {
         if (launch_vit_sort(st, d_vt + l.first, l.count, d_order + l.first)) { c->err = "forward pass: sort launch failed"; return STRQ_ERR_DEVICE; }
         const int lrc = launch_forward(st, l.shape, l.max_cells, d_vt + l.first, d_fm + l.first, d_c0 + l.first, d_fr + l.first, l.count,
-                                       c->queue.as<int>() + qi++, c->n_cu, d_order + l.first, every);
+                                       queue, c->n_cu, d_order + l.first, every);
         if (lrc) { c->err = lrc == 2 ? "forward pass: no kernel for this model's layout" : "forward launch failed"; return lrc == 2 ? STRQ_ERR_UNSUPPORTED : STRQ_ERR_DEVICE; }
-    }
+        return STRQ_OK;
+    };
+    if (const int grc = launch_groups(c, st, D.G.groups, gd)) return grc;
     std::vector<FwdResult> fr((size_t)m);
     STRQ_HIP(c, hipMemcpyAsync(fr.data(), d_fr, (size_t)m * sizeof(FwdResult), hipMemcpyDeviceToHost, st));
-    if (const int rc = pass_stop(c, d, d->conf_ms)) return rc;
+    if (const int rc = pass_stop(c, pass_ev(d), d->stats[PASS_CONF])) return rc;
     for (int k = 0; k < m; ++k) {
         const int64_t r = r0 + read_of[(size_t)k];
         double ll, mean, var;
@@ -969,9 +992,25 @@ static int run_conf_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, con
         B.conf[3 * (size_t)r + 1] = nopath ? mean : (double)target_of(d, r).count_bias + mean;
         B.conf[3 * (size_t)r + 2] = nopath ? var : std::sqrt(var);
         B.conf_dec[(size_t)r] = 1;
-        d->conf_nopath += nopath; d->conf_expo = std::max(d->conf_expo, std::fabs((double)fr[(size_t)k].expo));
+        d->stat(PASS_CONF, CONF_NOPATH) += nopath; d->stat(PASS_CONF, CONF_EXPO) = std::max(d->stat(PASS_CONF, CONF_EXPO), std::fabs((double)fr[(size_t)k].expo));
     }
-    d->conf_windows += m;
+    d->stat(PASS_CONF, CONF_WINDOWS) += m;
+    return STRQ_OK;
+}
+
+// The geometry and the conditioning rows of a sub-batch back on the device, from the slot's pinned block (the device copies belong to
+// the sub-batch that followed): two regions at the front of `buf`, and `tail_bytes` of the caller's behind them.
+struct SlotRows { ReadGeom* geom = nullptr; ReadCond* rc = nullptr; void* tail = nullptr; };
+static int upload_slot_rows(strq_ctx* c, const DetectState::Slot& sl, DevBuf& buf, SlotRows& rows, size_t tail_bytes = 0)
+{
+    const DetectState::Slot::Pinned h = sl.host();
+    const size_t nr = (size_t)sl.nr;
+    Carve wl;
+    const size_t o_geom = wl.add<ReadGeom>(nr), o_rc = wl.add<ReadCond>(nr), o_tail = wl.add<char>(tail_bytes);
+    STRQ_HIP(c, buf.reserve(wl.total() + 64));
+    rows.geom = Carve::at<ReadGeom>(buf.p, o_geom); rows.rc = Carve::at<ReadCond>(buf.p, o_rc); rows.tail = Carve::at<char>(buf.p, o_tail);
+    STRQ_HIP(c, hipMemcpyAsync(rows.geom, h.geom, nr * sizeof(ReadGeom), hipMemcpyHostToDevice, c->stream));
+    STRQ_HIP(c, hipMemcpyAsync(rows.rc, h.rc, nr * sizeof(ReadCond), hipMemcpyHostToDevice, c->stream));
     return STRQ_OK;
 }
 
@@ -996,22 +1035,18 @@ static int run_tract_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
     }
     const int m = (int)who.size();
     if (!m) return STRQ_OK;
-    if (const int rc = pass_start(c, d)) return rc;
-    auto model_of = [&](int i) { return c->models[target_of(d, r0 + i).tract_model_id]; };
-    std::vector<GroupItem> items((size_t)m);
-    for (int k = 0; k < m; ++k) {
-        HostModel* hm = model_of(who[(size_t)k]);
-        const int shape = vit_shape_of(hm->h);          // (never the register-resident image: it has one loop)
-        if (shape < 0 || !hm->h.tract_inc) { c->err = "tracts: the target's model has no tract decode"; return STRQ_ERR_UNSUPPORTED; }
-        items[(size_t)k] = {0, shape, hm->h.n_cells};
-    }
-    const Grouping G = group_items(items);
-    Carve wl;
-    const size_t o_geom = wl.add<ReadGeom>((size_t)nr), o_rc = wl.add<ReadCond>((size_t)nr);
-    STRQ_HIP(c, d->tract_ws.reserve(wl.total() + 64));
-    ReadGeom* d_geom = Carve::at<ReadGeom>(d->tract_ws.p, o_geom); ReadCond* d_rc = Carve::at<ReadCond>(d->tract_ws.p, o_rc);
-    STRQ_HIP(c, hipMemcpyAsync(d_geom, h.geom, (size_t)nr * sizeof(ReadGeom), hipMemcpyHostToDevice, st));
-    STRQ_HIP(c, hipMemcpyAsync(d_rc, h.rc, (size_t)nr * sizeof(ReadCond), hipMemcpyHostToDevice, st));
+    if (const int rc = pass_start(c, pass_ev(d))) return rc;
+    DecodeOrder<VitModel> D;
+    if (!decode_order(who, [&](int i, GroupItem& it, const VitModel*& vm) {
+            HostModel* hm = c->models[target_of(d, r0 + i).tract_model_id];
+            const int shape = vit_shape_of(hm->h);          // (never the register-resident image: it has one loop)
+            if (shape < 0 || !hm->h.tract_inc) return false;
+            it = {0, shape, hm->h.n_cells}; vm = hm->dev;
+            return true;
+        }, D)) { c->err = "tracts: the target's model has no tract decode"; return STRQ_ERR_UNSUPPORTED; }
+    const std::vector<int32_t>& read_of = D.read_of;
+    SlotRows rows;
+    if (const int rc = upload_slot_rows(c, sl, d->tract_ws, rows)) return rc;
     Carve tl;
     const size_t o_vt = tl.add<VitTask>((size_t)m), o_vr = tl.add<VitResult>((size_t)m), o_md = tl.add<const VitModel*>((size_t)m), o_rd = tl.add<int32_t>((size_t)m),
                  o_order = tl.add<int>((size_t)m);
@@ -1019,28 +1054,17 @@ static int run_tract_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
     void* tb = d->tract_task.p;
     VitTask* d_vt = Carve::at<VitTask>(tb, o_vt); VitResult* d_vr = Carve::at<VitResult>(tb, o_vr);
     const VitModel** d_md = Carve::at<const VitModel*>(tb, o_md); int32_t* d_rd = Carve::at<int32_t>(tb, o_rd); int* d_order = Carve::at<int>(tb, o_order);
-    std::vector<int32_t> read_of((size_t)m); std::vector<const VitModel*> mv((size_t)m);
-    for (int at = 0; at < m; ++at) {
-        const int i = who[(size_t)G.order[(size_t)at]];
-        read_of[(size_t)at] = i; mv[(size_t)at] = model_of(i)->dev;
-    }
     STRQ_HIP(c, hipMemcpyAsync(d_rd, read_of.data(), (size_t)m * 4, hipMemcpyHostToDevice, st));
-    STRQ_HIP(c, hipMemcpyAsync(d_md, mv.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, hipMemcpyAsync(d_md, D.model.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
     TractTaskArgs ta;
-    ta.geom = d_geom; ta.rc = d_rc; ta.read = d_rd; ta.model = d_md; ta.flt = sl.flt_base; ta.is_f64 = B.dtype; ta.ps = d->ps;
+    ta.geom = rows.geom; ta.rc = rows.rc; ta.read = d_rd; ta.model = d_md; ta.flt = sl.flt_base; ta.is_f64 = B.dtype; ta.ps = d->ps;
     ta.vit = d_vt; ta.n_tasks = m; ta.n_reads = nr;
     if (launch_tract_tasks(st, ta)) { c->err = "tracts: task launch failed"; return STRQ_ERR_DEVICE; }
-    d->tract_launches += 1;
-    if (const int qrc = reset_queue_heads(c, st)) return qrc;
-    int qi = 0;
-    for (const VitGroup& g : G.groups) {
-        if (const int src = sort_viterbi_group(c, st, g, d_vt, d_order)) return src;
-        if (const int lrc = launch_viterbi_group(c, st, g, d_vt, d_vr, d_order, c->queue.as<int>() + qi++, VIT_COUNT, 0, "tracts: ", true)) return lrc;
-        d->tract_launches += group_order(d_order, g) ? 2 : 1;
-    }
+    d->stat(PASS_TRACTS, TRACT_LAUNCHES) += 1;
+    if (const int grc = launch_groups(c, st, D.G.groups, {d_vt, d_vr, d_order, {VIT_COUNT}, "tracts: ", true, &d->stat(PASS_TRACTS, TRACT_LAUNCHES)})) return grc;
     std::vector<VitResult> vr((size_t)m);
     STRQ_HIP(c, hipMemcpyAsync(vr.data(), d_vr, (size_t)m * sizeof(VitResult), hipMemcpyDeviceToHost, st));
-    if (const int rc = pass_stop(c, d, d->tract_ms)) return rc;
+    if (const int rc = pass_stop(c, pass_ev(d), d->stats[PASS_TRACTS])) return rc;
     for (int at = 0; at < m; ++at) {
         const int i = read_of[(size_t)at];
         const Target& t = target_of(d, r0 + i);
@@ -1051,26 +1075,10 @@ static int run_tract_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
             o.n_tracts = t.n_tracts; o.log_p = v.logp;
             for (int j = 0; j < t.n_tracts; ++j)
                 o.count[j] = (int32_t)(((uint64_t)v.counted >> (VIT_TRACT_BITS * j)) & (((uint64_t)1 << VIT_TRACT_BITS) - 1)) + t.tract_bias[j];
-            d->tract_windows += 1;
-        } else d->tract_failed += 1;
+            d->stat(PASS_TRACTS, TRACT_WINDOWS) += 1;
+        } else d->stat(PASS_TRACTS, TRACT_FAILED) += 1;
         B.tracts[(size_t)(r0 + i)] = o;
     }
-    return STRQ_OK;
-}
-
-// The bracket of the methylation calls of anchored reads: events of its own (the anchored pass around it holds the pass events),
-// made when the switch is first used; amod_stop waits for the stream and adds the milliseconds in between to amod_ms.
-static int amod_start(strq_ctx* c, DetectState* d)
-{
-    for (hipEvent_t& e : d->amod_ev) if (!e) STRQ_HIP(c, hipEventCreate(&e));
-    STRQ_HIP(c, hipEventRecord(d->amod_ev[0], c->stream));
-    return STRQ_OK;
-}
-static int amod_stop(strq_ctx* c, DetectState* d)
-{
-    STRQ_HIP(c, hipEventRecord(d->amod_ev[1], c->stream));
-    STRQ_HIP(c, hipStreamSynchronize(c->stream));
-    float ms = 0; STRQ_HIP(c, hipEventElapsedTime(&ms, d->amod_ev[0], d->amod_ev[1])); d->amod_ms += ms;
     return STRQ_OK;
 }
 
@@ -1098,18 +1106,18 @@ static int run_anchored_mod(strq_ctx* c, DetectState* d, DetectState::Slot& sl, 
         }
         R = std::move(X);
         if (R.who.empty()) return STRQ_OK;
-        if (const int arc = amod_start(c, d)) return arc;
+        if (const int arc = pass_start(c, d->amod_ev)) return arc;
         if (const int drc = dual_decode(c, d, sl, DUAL_MOD, R)) return drc;
         if (const int prc = dual_patterns(c, d, sl, DUAL_MOD, R, B.amod)) return prc;
-        if (const int arc = amod_stop(c, d)) return arc;
+        if (const int arc = pass_stop(c, d->amod_ev, d->stats[PASS_AMOD])) return arc;
     }
     for (int i : R.who) {
         if (!called(i)) continue;
         const std::string& pat = B.amod[(size_t)(r0 + i)];
         B.amod_called[(size_t)(r0 + i)] = 1;
-        d->amod_reads += 1; d->amod_units += pat == "-" ? 0.0 : (double)pat.size();
+        d->stat(PASS_AMOD, AMOD_READS) += 1; d->stat(PASS_AMOD, AMOD_UNITS) += pat == "-" ? 0.0 : (double)pat.size();
     }
-    d->amod_launches += R.launches;
+    d->stat(PASS_AMOD, AMOD_LAUNCHES) += R.launches;
     if (!sl.ex.llr) return STRQ_OK;
     LlrPassIn li = dual_tail_in(R);
     li.pattern = &B.amod; li.scores = &B.amod_llr; li.anchored = true;
@@ -1129,26 +1137,22 @@ static int run_anchored_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
     const int64_t r0 = sl.r0; const int nr = sl.nr;
     if (nr <= 0) return STRQ_OK;
     const DetectState::Slot::Pinned h = sl.host();
-    if (const int rc = pass_start(c, d)) return rc;
-    Carve wl;
-    const size_t o_geom = wl.add<ReadGeom>((size_t)nr), o_rc = wl.add<ReadCond>((size_t)nr), o_cls = wl.add<AnchoredClass>((size_t)nr);
-    STRQ_HIP(c, d->anch_ws.reserve(wl.total() + 64));
-    ReadGeom* d_geom = Carve::at<ReadGeom>(d->anch_ws.p, o_geom); ReadCond* d_rc = Carve::at<ReadCond>(d->anch_ws.p, o_rc);
-    AnchoredClass* d_cls = Carve::at<AnchoredClass>(d->anch_ws.p, o_cls);
-    STRQ_HIP(c, hipMemcpyAsync(d_geom, h.geom, (size_t)nr * sizeof(ReadGeom), hipMemcpyHostToDevice, st));
-    STRQ_HIP(c, hipMemcpyAsync(d_rc, h.rc, (size_t)nr * sizeof(ReadCond), hipMemcpyHostToDevice, st));
+    if (const int rc = pass_start(c, pass_ev(d))) return rc;
+    SlotRows rows;          // ... and the kinds of the reads behind them
+    if (const int rc = upload_slot_rows(c, sl, d->anch_ws, rows, (size_t)nr * sizeof(AnchoredClass))) return rc;
+    ReadCond* d_rc = rows.rc; AnchoredClass* d_cls = static_cast<AnchoredClass*>(rows.tail);
     AnchoredClassifyArgs ca;
-    ca.geom = d_geom; ca.rc = d_rc; ca.min_score = sl.ex.anch_min; ca.out = d_cls; ca.n_reads = nr;
+    ca.geom = rows.geom; ca.rc = d_rc; ca.min_score = sl.ex.anch_min; ca.out = d_cls; ca.n_reads = nr;
     if (launch_anchored_classify(st, ca)) { c->err = "anchored: classify launch failed"; return STRQ_ERR_DEVICE; }
     std::vector<AnchoredClass> cls((size_t)nr);
     STRQ_HIP(c, hipMemcpyAsync(cls.data(), d_cls, (size_t)nr * sizeof(AnchoredClass), hipMemcpyDeviceToHost, st));
     STRQ_HIP(c, hipStreamSynchronize(st));
-    d->anch_launches += 1;
+    d->stat(PASS_ANCH, ANCH_LAUNCHES) += 1;
     std::vector<int> who;
     for (int i = 0; i < nr; ++i) {
         const AnchoredClass& k = cls[(size_t)i];
         if (k.kind < ANCH_NONE || k.kind > ANCH_STARTS) { c->err = "anchored: kind outside the rule"; return STRQ_ERR_DEVICE; }
-        d->anch_kinds[k.kind] += 1;
+        d->stat(PASS_ANCH, ANCH_KINDS + k.kind) += 1;
         B.anch[(size_t)(r0 + i)].kind = k.kind;
         if (k.kind != ANCH_ENDS && k.kind != ANCH_STARTS) continue;
         // the window once more on the host, against the read as the conditioning saw it
@@ -1156,45 +1160,38 @@ static int run_anchored_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
         who.push_back(i);
     }
     const int m = (int)who.size();
-    if (!m) return pass_stop(c, d, d->anch_ms);
-    auto model_of = [&](int i) { return anchored_model(c, d, r0 + i, cls[(size_t)i].kind); };
-    std::vector<GroupItem> items((size_t)m);
-    for (int k = 0; k < m; ++k) {
-        const Target& t = target_of(d, r0 + who[(size_t)k]);
+    if (!m) return pass_stop(c, pass_ev(d), d->stats[PASS_ANCH]);
+    DecodeOrder<VitModel> D; int orc = STRQ_OK;
+    decode_order(who, [&](int i, GroupItem& it, const VitModel*& vm) {
+        const Target& t = target_of(d, r0 + i);
         // (run_range refused the call before any launch when a target of the range had none)
-        if (t.end_model_id < 0 || t.start_model_id < 0) { c->err = "anchored: target without anchored models (strq_target_set_anchored)"; return STRQ_ERR_ARG; }
-        HostModel* hm = model_of(who[(size_t)k]);
+        if (t.end_model_id < 0 || t.start_model_id < 0) { c->err = "anchored: target without anchored models (strq_target_set_anchored)"; orc = STRQ_ERR_ARG; return false; }
+        HostModel* hm = anchored_model(c, d, r0 + i, cls[(size_t)i].kind);
         const int shape = vit_shape_for(hm->h, VIT_MARK);
-        if (shape < 0) { c->err = "anchored: model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
-        items[(size_t)k] = {0, shape, hm->h.n_cells};
-    }
-    const Grouping G = group_items(items);
+        if (shape < 0) { c->err = "anchored: model does not fit a compiled Viterbi kernel"; orc = STRQ_ERR_UNSUPPORTED; return false; }
+        it = {0, shape, hm->h.n_cells}; vm = hm->dev;
+        return true;
+    }, D);
+    if (orc) return orc;
+    const std::vector<int32_t>& read_of = D.read_of;
     Carve tl;
     const size_t o_vt = tl.add<VitTask>((size_t)m), o_vr = tl.add<VitResult>((size_t)m), o_md = tl.add<const VitModel*>((size_t)m), o_rd = tl.add<int32_t>((size_t)m);
     STRQ_HIP(c, d->anch_task.reserve(tl.total() + 64));
     VitTask* d_vt = Carve::at<VitTask>(d->anch_task.p, o_vt); VitResult* d_vr = Carve::at<VitResult>(d->anch_task.p, o_vr);
     const VitModel** d_md = Carve::at<const VitModel*>(d->anch_task.p, o_md); int32_t* d_rd = Carve::at<int32_t>(d->anch_task.p, o_rd);
-    std::vector<int32_t> read_of((size_t)m); std::vector<const VitModel*> mv((size_t)m);
-    for (int at = 0; at < m; ++at) {
-        const int i = who[(size_t)G.order[(size_t)at]];
-        read_of[(size_t)at] = i; mv[(size_t)at] = model_of(i)->dev;
-    }
     STRQ_HIP(c, hipMemcpyAsync(d_rd, read_of.data(), (size_t)m * 4, hipMemcpyHostToDevice, st));
-    STRQ_HIP(c, hipMemcpyAsync(d_md, mv.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, hipMemcpyAsync(d_md, D.model.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
     AnchoredTaskArgs ta;
     ta.cls = d_cls; ta.rc = d_rc; ta.read = d_rd; ta.model = d_md; ta.flt = sl.flt_base; ta.is_f64 = B.dtype; ta.ps = d->ps;
     ta.vit = d_vt; ta.n_tasks = m; ta.n_reads = nr;
     if (launch_anchored_tasks(st, ta)) { c->err = "anchored: task launch failed"; return STRQ_ERR_DEVICE; }
-    d->anch_launches += 1;
-    if (const int qrc = reset_queue_heads(c, st)) return qrc;
-    int qi = 0;
-    for (const VitGroup& g : G.groups) {
-        if (const int src = sort_viterbi_group(c, st, g, d_vt, sl.order.as<int>())) return src;
-        if (const int lrc = launch_viterbi_group(c, st, g, d_vt, d_vr, sl.order.as<int>(), c->queue.as<int>() + qi++, VIT_MARK, 0, "anchored: ")) return lrc;
-        d->anch_launches += group_order(sl.order.as<int>(), g) ? 2 : 1;
+    d->stat(PASS_ANCH, ANCH_LAUNCHES) += 1;
+    const GroupHook by_family = [&](const VitGroup& g) -> int {          // the windows by the family of kernels that decoded them
         const VitFamily fam = vit_shape_family(g.shape);
-        if (fam == VIT_FAMILY_G2) d->anch_g2 += g.count; else if (fam == VIT_FAMILY_LANE) d->anch_lane += g.count;
-    }
+        if (fam == VIT_FAMILY_G2) d->stat(PASS_ANCH, ANCH_G2) += g.count; else if (fam == VIT_FAMILY_LANE) d->stat(PASS_ANCH, ANCH_LANE) += g.count;
+        return STRQ_OK;
+    };
+    if (const int grc = launch_groups(c, st, D.G.groups, {d_vt, d_vr, sl.order.as<int>(), {VIT_MARK}, "anchored: ", false, &d->stat(PASS_ANCH, ANCH_LAUNCHES), nullptr, by_family})) return grc;
     std::vector<VitResult> vr((size_t)m);
     STRQ_HIP(c, hipMemcpyAsync(vr.data(), d_vr, (size_t)m * sizeof(VitResult), hipMemcpyDeviceToHost, st));
     // methylation calls (strq_set_anchored_mod): the reads of kind 2 / 3 whose target has a modification model, in task order
@@ -1213,16 +1210,16 @@ static int run_anchored_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
         std::vector<GroupItem> items; bool use_hub = false;
         if (const int rrc = dual_route(c, d, r0, DUAL_MOD, R, items, use_hub)) return rrc;
         if (use_hub) {
-            STRQ_HIP(c, hipEventRecord(d->ev[3], st));
-            if (const int arc = amod_start(c, d)) return arc;
+            STRQ_HIP(c, hipEventRecord(pass_ev(d)[1], st));
+            if (const int arc = pass_start(c, d->amod_ev)) return arc;
             if (const int drc = dual_decode(c, d, sl, DUAL_MOD, R, &src)) return drc;
             if (const int prc = dual_patterns(c, d, sl, DUAL_MOD, R, B.amod)) return prc;          // (waits for the stream: the records are here)
-            float ms = 0; STRQ_HIP(c, hipEventElapsedTime(&ms, d->ev[2], d->ev[3])); d->anch_ms += ms;
-            if (const int arc = amod_stop(c, d)) return arc;
+            float ms = 0; STRQ_HIP(c, hipEventElapsedTime(&ms, pass_ev(d)[0], pass_ev(d)[1])); d->stats[PASS_ANCH].ms += ms;
+            if (const int arc = pass_stop(c, d->amod_ev, d->stats[PASS_AMOD])) return arc;
             queued = true;
         }
     }
-    if (!queued) { if (const int rc = pass_stop(c, d, d->anch_ms)) return rc; }
+    if (!queued) { if (const int rc = pass_stop(c, pass_ev(d), d->stats[PASS_ANCH])) return rc; }
     for (int at = 0; at < m; ++at) {
         const int i = read_of[(size_t)at];
         const AnchoredClass& k = cls[(size_t)i];
@@ -1392,7 +1389,7 @@ static int take_rows(strq_ctx* c, DetectState* d, DetectState::Slot& sl, bool un
         if (sl.ex.renorm) {
             const strq_renorm& rn = sl.rn_pin.as<strq_renorm>()[i];
             B.renorm[(size_t)(r0 + i)] = rn;
-            d->rn_fitted += rn.fit[1].fitted != 0; d->rn_applied += rn.applied != 0;
+            d->stat(PASS_RENORM, RN_FITTED) += rn.fit[1].fitted != 0; d->stat(PASS_RENORM, RN_APPLIED) += rn.applied != 0;
         }
         if (sl.scan && B.cand[(size_t)(r0 + i)] < 0) continue;          // no winner: no row (the scores of its candidates are in Batch::scores)
         o.score_prefix = g.score_prefix; o.score_suffix = g.score_suffix;
@@ -1662,15 +1659,15 @@ static int run_renorm_part(strq_ctx* c, DetectState* d, const SubBatch& S, int i
     if (B.dtype == 0) {
         const uint32_t* hraw = S.d_hist_raw ? S.d_hist_raw + (size_t)i0 * 65536 : nullptr;
         bad |= launch_renorm_hist_i16(st, d->hist16.as<uint32_t>() + (size_t)i0 * 65536, hraw, hist8, d_rc, d_rr, np, d->rn_grid, h);
-        d->rn_launches += hraw ? 3 : 2;
+        d->stat(PASS_RENORM, RN_LAUNCHES) += hraw ? 3 : 2;
     } else {
         bad |= launch_renorm_hist_f64(st, reinterpret_cast<const double*>(S.flt_base), S.any_mod ? reinterpret_cast<const double*>(S.raw) : nullptr, hist8, d_rc, d_rr,
                                       np, longest, d->rn_grid, h);
-        d->rn_launches += longest > 0 ? 2 : 1;
+        d->stat(PASS_RENORM, RN_LAUNCHES) += longest > 0 ? 2 : 1;
     }
     bad |= launch_renorm_fit(st, h, d_rr, np, rec);
     bad |= launch_renorm_fold(st, d_rc, np, d->rn_grid, d->extras.renorm_min, d->ps, c->level_val.as<float>() + (size_t)i0 * 256, rec);
-    d->rn_launches += 2;
+    d->stat(PASS_RENORM, RN_LAUNCHES) += 2;
     if (timed) { STRQ_HIP(c, hipEventRecord(d->rn_ev[2 * d->rn_timed + 1], st)); ++d->rn_timed; }
     if (bad) { c->err = "renorm: launch failed"; return STRQ_ERR_DEVICE; }
     return STRQ_OK;
@@ -1881,7 +1878,7 @@ static int complete_sub_batch(strq_ctx* c, DetectState* d, const SubBatch& S)
     plan_next_overlap(c, d, S);
     float ms;
     STRQ_HIP(c, hipEventElapsedTime(&ms, d->ev[0], d->ev[1])); B.t_cond += ms;
-    for (int k = 0; k < d->rn_timed; ++k) { STRQ_HIP(c, hipEventElapsedTime(&ms, d->rn_ev[2 * k], d->rn_ev[2 * k + 1])); d->rn_ms += ms; }
+    for (int k = 0; k < d->rn_timed; ++k) { STRQ_HIP(c, hipEventElapsedTime(&ms, d->rn_ev[2 * k], d->rn_ev[2 * k + 1])); d->stats[PASS_RENORM].ms += ms; }
     d->rn_timed = 0;
     const int rcode = align_core_times(c, &B.t_lut, &B.t_fwd, &B.t_trace);      // of the last piece when the sub-batch ran in pieces
     if (rcode) return rcode;
@@ -2058,42 +2055,30 @@ int run_range(strq_ctx* c, DetectState* d, int64_t first, int64_t last)
         if (!B.target_given.empty()) { B.target = B.target_given; B.target_given.clear(); }
         B.scan_ncand = 0; B.cand.clear(); B.scores.clear();
     }
+    // refused here, before any launch: a scan has no anchored records, variants, tracts or fits (the first pass in SCAN_CHECKS says so)
+    if (d->scan_on) { const Pass p = scan_refusal(d->extras); if (p != N_PASS) { c->err = scan_refusal_text(p); return STRQ_ERR_ARG; } }
     if (d->extras.amod) {
-        // (refused here, before any launch: the calls hang on the anchored records, and a scan has none)
-        if (d->scan_on) { c->err = "anchored-mod: not available in a scan (strq_scan_set)"; return STRQ_ERR_ARG; }
+        // (the calls hang on the anchored records)
         if (!d->extras.anch) { c->err = "anchored-mod: needs anchored counting (strq_set_anchored)"; return STRQ_ERR_ARG; }
         B.size_amod();
     }
     if (d->extras.anch) {
         // nothing is launched for a call the anchored pass could not finish
-        if (d->scan_on) { c->err = "anchored: not available in a scan (strq_scan_set)"; return STRQ_ERR_ARG; }
         for (int64_t r = first; r < last; ++r) {
             const Target& t = d->targets[B.target_given.empty() ? B.target[(size_t)r] : B.target_given[(size_t)r]];
             if (t.end_model_id < 0 || t.start_model_id < 0) { c->err = "anchored: target without anchored models (strq_target_set_anchored)"; return STRQ_ERR_ARG; }
         }
     }
-    if (d->extras.var && d->scan_on) { c->err = "variants: not available in a scan (strq_scan_set)"; return STRQ_ERR_ARG; }
-    if (d->extras.tracts) {
-        if (d->scan_on) { c->err = "tracts: not available in a scan (strq_scan_set)"; return STRQ_ERR_ARG; }
-        B.size_tracts();
-    }
+    if (d->extras.tracts) B.size_tracts();
     if (d->extras.renorm) {
         // nothing is launched for a call whose reads the pass could not fit
-        if (d->scan_on) { c->err = "renorm: not available in a scan (strq_scan_set)"; return STRQ_ERR_ARG; }
         if (!d->rn_have_grid) { c->err = "renorm: no tables (strq_target_set_renorm)"; return STRQ_ERR_ARG; }
         for (int64_t r = first; r < last; ++r)
             if (!d->targets[B.target_given.empty() ? B.target[(size_t)r] : B.target_given[(size_t)r]].rn_dev) { c->err = "renorm: target without tables (strq_target_set_renorm)"; return STRQ_ERR_ARG; }
         B.size_renorm();
     }
     B.ran = d->extras;
-    d->rn_ms = 0; d->rn_fitted = d->rn_applied = d->rn_launches = 0; d->rn_timed = 0;
-    d->anch_ms = 0; std::fill(d->anch_kinds, d->anch_kinds + 4, 0.0); d->anch_launches = d->anch_g2 = d->anch_lane = 0;
-    d->amod_ms = 0; d->amod_reads = d->amod_units = d->amod_launches = 0;
-    d->unit_ms = 0; d->unit_bytes = d->unit_reads = d->unit_positions = 0;
-    d->conf_ms = 0; d->conf_windows = d->conf_nopath = d->conf_expo = 0;
-    d->llr_ms = 0; d->llr_units = d->llr_reads = d->llr_launches = 0;
-    d->var_ms = 0; d->var_launches = d->var_passages = d->var_reads = 0;
-    d->tract_ms = 0; d->tract_windows = d->tract_launches = d->tract_failed = 0;
+    std::fill(d->stats, d->stats + N_PASS, PassStats()); d->rn_timed = 0;
     STRQ_HIP(c, c->redo_total.reserve(64));
     STRQ_HIP(c, hipMemsetAsync(c->redo_total.p, 0, 64, c->stream));
     // partition into sub-batches first, so that the upload of piece k + 1 can overlap the kernels of piece k
@@ -2145,16 +2130,49 @@ int copy_scan(strq_ctx* c, const DetectState* d, int32_t* out_cand, double* out_
     return STRQ_OK;
 }
 
-// strq_set_units / _confidence / _mod_llr: one switch of DetectState::extras.  `bad`: the entry's message for an argument other than 0
-// or 1; `validate`: what must hold before the switch goes on.
-int set_extra(strq_ctx* c, int32_t on, const char* bad, bool Extras::* which, int (*validate)(strq_ctx*, DetectState*) = nullptr)
+// strq_set_<pass>: one switch of DetectState::extras.  An argument other than 0 or 1 is refused in the entry's name; `validate`: what
+// must hold before the switch goes on.  A switch that comes with a threshold (anchored, renorm): `level` is where it goes (0 with the
+// switch off), `level_ok` whether the value will do and `level_bad` the message if not; a scan refuses renorm here already.
+int set_extra(strq_ctx* c, int32_t on, Pass p, int (*validate)(strq_ctx*, DetectState*) = nullptr,
+              double Extras::* level = nullptr, double value = 0.0, bool level_ok = true, const char* level_bad = nullptr)
 {
-    if (on != 0 && on != 1) { c->err = bad; return STRQ_ERR_ARG; }
+    if (on != 0 && on != 1) { c->err = std::string("bad argument (") + PASSES[p].entry + " takes 0 or 1)"; return STRQ_ERR_ARG; }
+    if (on && !level_ok) { c->err = level_bad; return STRQ_ERR_ARG; }
     DetectState* d = dstate(c);
+    if (on && p == PASS_RENORM && d->scan_on) { c->err = scan_refusal_text(p); return STRQ_ERR_ARG; }
     // sub-batches in flight keep the mode they were launched with: their pass (or none) runs now
     if (const int rc = drain(c, d)) return rc;
     if (on && validate) { if (const int rc = validate(c, d)) return rc; }
-    d->extras.*which = on != 0;
+    d->extras.*PASSES[p].on = on != 0;
+    if (level) d->extras.*level = on ? value : 0.0;
+    return STRQ_OK;
+}
+
+// strq_last_<pass>: the pass's counters in the layout of its entry
+int last_pass(strq_ctx* c, Pass p, double* out)
+{
+    if (!out) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    pass_stats_out(p, dstate(c)->stats[p], out);
+    return STRQ_OK;
+}
+
+// strq_batch_fetch_<pass> begins: the sub-batches in flight are taken, and a batch that ran without the pass has nothing to fetch
+int fetch_begin(strq_ctx* c, DetectState* d, Pass p)
+{
+    if (const int rc = drain(c, d)) return rc;
+    if (!(d->batch.ran.*PASSES[p].on)) { c->err = ran_without_text(p); return STRQ_ERR_ARG; }
+    return STRQ_OK;
+}
+
+// strq_batch_fetch_anchored / _tracts / _renorm: one record per read
+template <class T>
+int fetch_records(strq_ctx* c, Pass p, std::vector<T> ReadRows::* rows, T* out, int64_t n)
+{
+    DetectState* d = dstate(c);
+    if (const int rc = fetch_begin(c, d, p)) return rc;
+    const Batch& B = d->batch;
+    if (n != B.n_reads || (n > 0 && !out) || (B.*rows).size() != (size_t)n) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    if (n) std::memcpy(out, (B.*rows).data(), (size_t)n * sizeof(T));
     return STRQ_OK;
 }
 
@@ -2283,21 +2301,17 @@ int strq_batch_fetch_mod(strq_ctx* c, char* pool, int64_t pool_cap, int64_t* off
     if (!off) return STRQ_ERR_ARG;
     DetectState* d = dstate(c);
     if (const int rc = drain(c, d)) return rc;
-    int64_t pos = 0;
-    for (size_t i = 0; i < d->batch.mod.size(); ++i) {
-        off[i] = pos;
-        const std::string& m = d->batch.mod[i];
-        if (pool) { if (pos + (int64_t)m.size() > pool_cap) { c->err = "pattern pool too small"; return STRQ_ERR_ARG; } std::memcpy(pool + pos, m.data(), m.size()); }
-        pos += (int64_t)m.size();
-    }
-    off[d->batch.mod.size()] = pos;
+    const std::vector<std::string>& mod = d->batch.mod;
+    const int64_t n = (int64_t)mod.size();
+    if (pack_ragged(n, off, pool != nullptr, pool_cap, [&](int64_t i) { return (int64_t)mod[(size_t)i].size(); },
+                    [&](int64_t i, int64_t pos) { std::memcpy(pool + pos, mod[(size_t)i].data(), mod[(size_t)i].size()); }) < n) { c->err = "pattern pool too small"; return STRQ_ERR_ARG; }
     return STRQ_OK;
 }
 
 int strq_set_units(strq_ctx* c, int32_t on)
 {
     STRQ_ENTER(c);
-    return set_extra(c, on, "bad argument (strq_set_units takes 0 or 1)", &Extras::units);
+    return set_extra(c, on, PASS_UNITS);
 }
 
 int strq_batch_fetch_units(strq_ctx* c, int64_t* pool, int64_t pool_cap, int64_t* off, int32_t* decoded)
@@ -2305,36 +2319,28 @@ int strq_batch_fetch_units(strq_ctx* c, int64_t* pool, int64_t pool_cap, int64_t
     STRQ_ENTER(c);
     if (!off) return STRQ_ERR_ARG;
     DetectState* d = dstate(c);
-    if (const int rc = drain(c, d)) return rc;
+    if (const int rc = fetch_begin(c, d, PASS_UNITS)) return rc;
     const Batch& B = d->batch;
-    if (!B.ran.units) { c->err = "the last batch ran without unit positions (strq_set_units)"; return STRQ_ERR_ARG; }
-    int64_t pos = 0;
-    for (size_t i = 0; i < B.units.size(); ++i) {
-        off[i] = pos;
-        const std::vector<int64_t>& u = B.units[i];
-        if (pool) {
-            if (pos + (int64_t)u.size() > pool_cap) { c->err = "unit pool too small"; return STRQ_ERR_ARG; }
-            if (!u.empty()) std::memcpy(pool + pos, u.data(), u.size() * 8);
-        }
-        if (decoded) decoded[i] = B.unit_dec[i];
-        pos += (int64_t)u.size();
-    }
-    off[B.units.size()] = pos;
+    const int64_t n = (int64_t)B.units.size();
+    const int64_t done = pack_ragged(n, off, pool != nullptr, pool_cap, [&](int64_t i) { return (int64_t)B.units[(size_t)i].size(); }, [&](int64_t i, int64_t pos) {
+        const std::vector<int64_t>& u = B.units[(size_t)i];
+        if (!u.empty()) std::memcpy(pool + pos, u.data(), u.size() * 8);
+    });
+    if (decoded) for (int64_t i = 0; i < done; ++i) decoded[i] = B.unit_dec[(size_t)i];          // (of the reads that fitted)
+    if (done < n) { c->err = "unit pool too small"; return STRQ_ERR_ARG; }
     return STRQ_OK;
 }
 
 int strq_last_units(strq_ctx* c, double* out4)
 {
-    if (!c || !out4) return STRQ_ERR_ARG;
-    DetectState* d = dstate(c);
-    out4[0] = d->unit_ms; out4[1] = d->unit_bytes; out4[2] = d->unit_reads; out4[3] = d->unit_positions;
-    return STRQ_OK;
+    if (!c || !out4) return STRQ_ERR_ARG;          // (no way into the device and no message: the entry is older than STRQ_ENTER)
+    return last_pass(c, PASS_UNITS, out4);
 }
 
 int strq_set_confidence(strq_ctx* c, int32_t on)
 {
     STRQ_ENTER(c);
-    return set_extra(c, on, "bad argument (strq_set_confidence takes 0 or 1)", &Extras::conf);
+    return set_extra(c, on, PASS_CONF);
 }
 
 int strq_batch_fetch_confidence(strq_ctx* c, double* out3, int32_t* decoded)
@@ -2342,9 +2348,8 @@ int strq_batch_fetch_confidence(strq_ctx* c, double* out3, int32_t* decoded)
     STRQ_ENTER(c);
     if (!out3) { c->err = "bad argument"; return STRQ_ERR_ARG; }
     DetectState* d = dstate(c);
-    if (const int rc = drain(c, d)) return rc;
+    if (const int rc = fetch_begin(c, d, PASS_CONF)) return rc;
     const Batch& B = d->batch;
-    if (!B.ran.conf) { c->err = "the last batch ran without confidence (strq_set_confidence)"; return STRQ_ERR_ARG; }
     if (!B.conf.empty()) std::memcpy(out3, B.conf.data(), B.conf.size() * 8);
     if (decoded) for (size_t i = 0; i < B.conf_dec.size(); ++i) decoded[i] = B.conf_dec[i];
     return STRQ_OK;
@@ -2353,17 +2358,14 @@ int strq_batch_fetch_confidence(strq_ctx* c, double* out3, int32_t* decoded)
 int strq_last_confidence(strq_ctx* c, double* out4)
 {
     STRQ_ENTER(c);
-    if (!out4) { c->err = "bad argument"; return STRQ_ERR_ARG; }
-    DetectState* d = dstate(c);
-    out4[0] = d->conf_ms; out4[1] = d->conf_windows; out4[2] = d->conf_nopath; out4[3] = d->conf_expo;
-    return STRQ_OK;
+    return last_pass(c, PASS_CONF, out4);
 }
 
 int strq_set_mod_llr(strq_ctx* c, int32_t on)
 {
     STRQ_ENTER(c);
     // every modification model registered so far must be one the pass covers (later ones: strq_target_set_mod)
-    return set_extra(c, on, "bad argument (strq_set_mod_llr takes 0 or 1)", &Extras::llr, [](strq_ctx* c, DetectState* d) -> int {
+    return set_extra(c, on, PASS_LLR, [](strq_ctx* c, DetectState* d) -> int {
         for (const Target& t : d->targets)
             if (t.mod_model_id >= 0) { if (const int rc = llr_model(c, c->models[t.mod_model_id])) return rc; }
         return STRQ_OK;
@@ -2377,28 +2379,17 @@ int strq_batch_fetch_mod_llr(strq_ctx* c, double* pool, int64_t pool_cap, int64_
     DetectState* d = dstate(c);
     if (const int rc = drain(c, d)) return rc;
     const Batch& B = d->batch;
-    int64_t pos = 0;
-    for (int64_t i = 0; i < B.n_reads; ++i) {
-        off[i] = pos;
-        const std::vector<double>& v = B.llr[(size_t)i];
-        const int64_t n = (int64_t)v.size() / 2;
-        if (pool) {
-            if (pos + n > pool_cap) { c->err = "mod-llr pool too small"; return STRQ_ERR_ARG; }
-            if (n) std::memcpy(pool + 2 * pos, v.data(), (size_t)n * 16);
-        }
-        pos += n;
-    }
-    off[B.n_reads] = pos;
+    if (pack_ragged(B.n_reads, off, pool != nullptr, pool_cap, [&](int64_t i) { return (int64_t)B.llr[(size_t)i].size() / 2; }, [&](int64_t i, int64_t pos) {
+            const std::vector<double>& v = B.llr[(size_t)i];
+            if (v.size() / 2) std::memcpy(pool + 2 * pos, v.data(), v.size() / 2 * 16);
+        }) < B.n_reads) { c->err = "mod-llr pool too small"; return STRQ_ERR_ARG; }
     return STRQ_OK;
 }
 
 int strq_last_mod_llr(strq_ctx* c, double* out4)
 {
     STRQ_ENTER(c);
-    if (!out4) { c->err = "bad argument"; return STRQ_ERR_ARG; }
-    DetectState* d = dstate(c);
-    out4[0] = d->llr_ms; out4[1] = d->llr_units; out4[2] = d->llr_reads; out4[3] = d->llr_launches;
-    return STRQ_OK;
+    return last_pass(c, PASS_LLR, out4);
 }
 
 int strq_target_set_variants(strq_ctx* c, int32_t target_id, int32_t model_id, double lo, double hi, int32_t n_alt, int32_t context_units)
@@ -2418,7 +2409,7 @@ int strq_target_set_variants(strq_ctx* c, int32_t target_id, int32_t model_id, d
 int strq_set_variants(strq_ctx* c, int32_t on)
 {
     STRQ_ENTER(c);
-    return set_extra(c, on, "bad argument (strq_set_variants takes 0 or 1)", &Extras::var);
+    return set_extra(c, on, PASS_VAR);
 }
 
 int strq_batch_fetch_variants(strq_ctx* c, int32_t* count_v, int32_t* decoded, int64_t* off, int8_t* branch, int64_t* end, int64_t pass_cap,
@@ -2427,41 +2418,35 @@ int strq_batch_fetch_variants(strq_ctx* c, int32_t* count_v, int32_t* decoded, i
     STRQ_ENTER(c);
     if (!off) { c->err = "bad argument"; return STRQ_ERR_ARG; }
     DetectState* d = dstate(c);
-    if (const int rc = drain(c, d)) return rc;
+    if (const int rc = fetch_begin(c, d, PASS_VAR)) return rc;
     const Batch& B = d->batch;
-    if (!B.ran.var) { c->err = "the last batch ran without variants (strq_set_variants)"; return STRQ_ERR_ARG; }
     const bool pools = branch || end || vpool || voff;
     if (pools && !(branch && end && vpool && voff)) { c->err = "bad argument (strq_batch_fetch_variants: all pools or none)"; return STRQ_ERR_ARG; }
-    int64_t pos = 0, vpos = 0;
-    for (int64_t i = 0; i < B.n_reads; ++i) {
+    // two pools: the passages (branch, end and the offset of their scores), and the scores
+    int64_t vtot = 0;
+    const int64_t done = pack_ragged2(B.n_reads, off, nullptr, pools, pass_cap, v_cap, &vtot, [&](int64_t i, int64_t* n, int64_t* nv) {
         const VariantRow& r = B.var[(size_t)i];
-        off[i] = pos;
         if (count_v) count_v[i] = r.count_v;
         if (decoded) decoded[i] = r.decoded;
-        const int64_t n = (int64_t)r.branch.size();
-        if (pools) {
-            if (pos + n > pass_cap || vpos + (int64_t)r.V.size() > v_cap) { c->err = "variant pool too small"; return STRQ_ERR_ARG; }
-            for (int64_t j = 0; j < n; ++j) {
-                branch[pos + j] = r.branch[(size_t)j]; end[pos + j] = r.end[(size_t)j];
-                voff[pos + j] = vpos + j * r.n_branch;
-            }
-            if (!r.V.empty()) std::memcpy(vpool + vpos, r.V.data(), r.V.size() * 8);
+        *n = (int64_t)r.branch.size(); *nv = (int64_t)r.V.size();
+    }, [&](int64_t i, int64_t pos, int64_t vpos) {
+        const VariantRow& r = B.var[(size_t)i];
+        for (int64_t j = 0; j < (int64_t)r.branch.size(); ++j) {
+            branch[pos + j] = r.branch[(size_t)j]; end[pos + j] = r.end[(size_t)j];
+            voff[pos + j] = vpos + j * r.n_branch;
         }
-        pos += n; vpos += (int64_t)r.V.size();
-    }
-    off[B.n_reads] = pos;
-    if (pools) voff[pos] = vpos;
-    if (v_total) *v_total = vpos;
+        if (!r.V.empty()) std::memcpy(vpool + vpos, r.V.data(), r.V.size() * 8);
+    });
+    if (done < B.n_reads) { c->err = "variant pool too small"; return STRQ_ERR_ARG; }
+    if (pools) voff[off[B.n_reads]] = vtot;
+    if (v_total) *v_total = vtot;
     return STRQ_OK;
 }
 
 int strq_last_variants(strq_ctx* c, double* out4)
 {
     STRQ_ENTER(c);
-    if (!out4) { c->err = "bad argument"; return STRQ_ERR_ARG; }
-    DetectState* d = dstate(c);
-    out4[0] = d->var_launches; out4[1] = d->var_passages; out4[2] = d->var_ms; out4[3] = d->var_reads;
-    return STRQ_OK;
+    return last_pass(c, PASS_VAR, out4);
 }
 
 int strq_target_set_anchored(strq_ctx* c, int32_t target_id, int32_t end_model_id, int32_t end_bias, int32_t start_model_id, int32_t start_bias)
@@ -2485,36 +2470,19 @@ int strq_target_set_anchored(strq_ctx* c, int32_t target_id, int32_t end_model_i
 int strq_set_anchored(strq_ctx* c, int32_t on, double min_score)
 {
     STRQ_ENTER(c);
-    if (on != 0 && on != 1) { c->err = "bad argument (strq_set_anchored takes 0 or 1)"; return STRQ_ERR_ARG; }
-    if (on && !(min_score > 0.0)) { c->err = "anchored: min_score must be above 0"; return STRQ_ERR_ARG; }
-    DetectState* d = dstate(c);
-    // sub-batches in flight keep the mode they were launched with: their pass (or none) runs now
-    if (const int rc = drain(c, d)) return rc;
-    d->extras.anch = on != 0; d->extras.anch_min = on ? min_score : 0.0;
-    return STRQ_OK;
+    return set_extra(c, on, PASS_ANCH, nullptr, &Extras::anch_min, min_score, min_score > 0.0, "anchored: min_score must be above 0");
 }
 
 int strq_batch_fetch_anchored(strq_ctx* c, strq_anchored* out, int64_t n)
 {
     STRQ_ENTER(c);
-    DetectState* d = dstate(c);
-    if (const int rc = drain(c, d)) return rc;
-    const Batch& B = d->batch;
-    if (!B.ran.anch) { c->err = "the last batch ran without anchored counting (strq_set_anchored)"; return STRQ_ERR_ARG; }
-    if (n != B.n_reads || (n > 0 && !out)) { c->err = "bad argument"; return STRQ_ERR_ARG; }
-    if (n) std::memcpy(out, B.anch.data(), (size_t)n * sizeof(strq_anchored));
-    return STRQ_OK;
+    return fetch_records(c, PASS_ANCH, &ReadRows::anch, out, n);
 }
 
 int strq_last_anchored(strq_ctx* c, double* out8)
 {
     STRQ_ENTER(c);
-    if (!out8) { c->err = "bad argument"; return STRQ_ERR_ARG; }
-    DetectState* d = dstate(c);
-    out8[0] = d->anch_ms;
-    for (int k = 0; k < 4; ++k) out8[1 + k] = d->anch_kinds[k];
-    out8[5] = d->anch_launches; out8[6] = d->anch_g2; out8[7] = d->anch_lane;
-    return STRQ_OK;
+    return last_pass(c, PASS_ANCH, out8);
 }
 
 int strq_target_set_tracts(strq_ctx* c, int32_t target_id, int32_t model_id, int32_t n_tracts, const int32_t* bias)
@@ -2539,34 +2507,25 @@ int strq_target_set_tracts(strq_ctx* c, int32_t target_id, int32_t model_id, int
 int strq_set_tracts(strq_ctx* c, int32_t on)
 {
     STRQ_ENTER(c);
-    return set_extra(c, on, "bad argument (strq_set_tracts takes 0 or 1)", &Extras::tracts);
+    return set_extra(c, on, PASS_TRACTS);
 }
 
 int strq_batch_fetch_tracts(strq_ctx* c, strq_tracts* out, int64_t n)
 {
     STRQ_ENTER(c);
-    DetectState* d = dstate(c);
-    if (const int rc = drain(c, d)) return rc;
-    const Batch& B = d->batch;
-    if (!B.ran.tracts) { c->err = "the last batch ran without tracts (strq_set_tracts)"; return STRQ_ERR_ARG; }
-    if (n != B.n_reads || (n > 0 && !out) || B.tracts.size() != (size_t)n) { c->err = "bad argument"; return STRQ_ERR_ARG; }
-    if (n) std::memcpy(out, B.tracts.data(), (size_t)n * sizeof(strq_tracts));
-    return STRQ_OK;
+    return fetch_records(c, PASS_TRACTS, &ReadRows::tracts, out, n);
 }
 
 int strq_last_tracts(strq_ctx* c, double* out4)
 {
     STRQ_ENTER(c);
-    if (!out4) { c->err = "bad argument"; return STRQ_ERR_ARG; }
-    DetectState* d = dstate(c);
-    out4[0] = d->tract_ms; out4[1] = d->tract_windows; out4[2] = d->tract_launches; out4[3] = d->tract_failed;
-    return STRQ_OK;
+    return last_pass(c, PASS_TRACTS, out4);
 }
 
 int strq_set_anchored_mod(strq_ctx* c, int32_t on)
 {
     STRQ_ENTER(c);
-    return set_extra(c, on, "bad argument (strq_set_anchored_mod takes 0 or 1)", &Extras::amod);
+    return set_extra(c, on, PASS_AMOD);
 }
 
 int strq_batch_fetch_anchored_mod(strq_ctx* c, int32_t* called, int64_t* off, char* chars, int64_t chars_cap, int64_t* voff, double* pool, int64_t pool_cap)
@@ -2574,36 +2533,29 @@ int strq_batch_fetch_anchored_mod(strq_ctx* c, int32_t* called, int64_t* off, ch
     STRQ_ENTER(c);
     if (!off || !voff) { c->err = "bad argument"; return STRQ_ERR_ARG; }
     DetectState* d = dstate(c);
-    if (const int rc = drain(c, d)) return rc;
+    if (const int rc = fetch_begin(c, d, PASS_AMOD)) return rc;
     const Batch& B = d->batch;
-    if (!B.ran.amod) { c->err = "the last batch ran without anchored methylation calls (strq_set_anchored_mod)"; return STRQ_ERR_ARG; }
     const bool pools = chars || pool;
     if (pools && !(chars && pool)) { c->err = "bad argument (strq_batch_fetch_anchored_mod: both pools or none)"; return STRQ_ERR_ARG; }
-    int64_t pos = 0, vpos = 0;
-    for (int64_t i = 0; i < B.n_reads; ++i) {
-        off[i] = pos; voff[i] = vpos;
+    // two pools: the characters of the patterns and their pairs; a read without a call adds to neither
+    const int64_t done = pack_ragged2(B.n_reads, off, voff, pools, chars_cap, pool_cap, nullptr, [&](int64_t i, int64_t* n, int64_t* nv) {
         if (called) called[i] = B.amod_called[(size_t)i];
-        if (!B.amod_called[(size_t)i]) continue;
+        if (!B.amod_called[(size_t)i]) return;
+        *n = (int64_t)B.amod[(size_t)i].size(); *nv = (int64_t)B.amod_llr[(size_t)i].size() / 2;
+    }, [&](int64_t i, int64_t pos, int64_t vpos) {
         const std::string& p = B.amod[(size_t)i]; const std::vector<double>& v = B.amod_llr[(size_t)i];
-        const int64_t n = (int64_t)p.size(), nv = (int64_t)v.size() / 2;
-        if (pools) {
-            if (pos + n > chars_cap || vpos + nv > pool_cap) { c->err = "anchored-mod pool too small"; return STRQ_ERR_ARG; }
-            if (n) std::memcpy(chars + pos, p.data(), (size_t)n);
-            if (nv) std::memcpy(pool + 2 * vpos, v.data(), (size_t)nv * 16);
-        }
-        pos += n; vpos += nv;
-    }
-    off[B.n_reads] = pos; voff[B.n_reads] = vpos;
+        if (!B.amod_called[(size_t)i]) return;
+        if (!p.empty()) std::memcpy(chars + pos, p.data(), p.size());
+        if (v.size() / 2) std::memcpy(pool + 2 * vpos, v.data(), v.size() / 2 * 16);
+    });
+    if (done < B.n_reads) { c->err = "anchored-mod pool too small"; return STRQ_ERR_ARG; }
     return STRQ_OK;
 }
 
 int strq_last_anchored_mod(strq_ctx* c, double* out4)
 {
     STRQ_ENTER(c);
-    if (!out4) { c->err = "bad argument"; return STRQ_ERR_ARG; }
-    DetectState* d = dstate(c);
-    out4[0] = d->amod_ms; out4[1] = d->amod_reads; out4[2] = d->amod_units; out4[3] = d->amod_launches;
-    return STRQ_OK;
+    return last_pass(c, PASS_AMOD, out4);
 }
 
 int strq_target_set_renorm(strq_ctx* c, int32_t target_id, const int16_t* Q, int32_t q_out, const int32_t* A, const double* W,
@@ -2655,26 +2607,13 @@ int strq_target_set_renorm(strq_ctx* c, int32_t target_id, const int16_t* Q, int
 int strq_set_renorm(strq_ctx* c, int32_t on, double min_share)
 {
     STRQ_ENTER(c);
-    if (on != 0 && on != 1) { c->err = "bad argument (strq_set_renorm takes 0 or 1)"; return STRQ_ERR_ARG; }
-    if (on && !(min_share > 0.0 && min_share < 1.0)) { c->err = "renorm: min_share must be inside (0, 1)"; return STRQ_ERR_ARG; }
-    DetectState* d = dstate(c);
-    if (on && d->scan_on) { c->err = "renorm: not available in a scan (strq_scan_set)"; return STRQ_ERR_ARG; }
-    // sub-batches in flight keep the mode they were launched with
-    if (const int rc = drain(c, d)) return rc;
-    d->extras.renorm = on != 0; d->extras.renorm_min = on ? min_share : 0.0;
-    return STRQ_OK;
+    return set_extra(c, on, PASS_RENORM, nullptr, &Extras::renorm_min, min_share, min_share > 0.0 && min_share < 1.0, "renorm: min_share must be inside (0, 1)");
 }
 
 int strq_batch_fetch_renorm(strq_ctx* c, strq_renorm* out, int64_t n)
 {
     STRQ_ENTER(c);
-    DetectState* d = dstate(c);
-    if (const int rc = drain(c, d)) return rc;
-    const Batch& B = d->batch;
-    if (!B.ran.renorm) { c->err = "the last batch ran without renorm (strq_set_renorm)"; return STRQ_ERR_ARG; }
-    if (n != B.n_reads || (n > 0 && !out)) { c->err = "bad argument"; return STRQ_ERR_ARG; }
-    if (n) std::memcpy(out, B.renorm.data(), (size_t)n * sizeof(strq_renorm));
-    return STRQ_OK;
+    return fetch_records(c, PASS_RENORM, &ReadRows::renorm, out, n);
 }
 
 int strq_debug_renorm_fit(strq_ctx* c, int32_t target_id, const uint32_t* h3, strq_renorm* out)
@@ -2702,10 +2641,7 @@ int strq_debug_renorm_fit(strq_ctx* c, int32_t target_id, const uint32_t* h3, st
 int strq_last_renorm(strq_ctx* c, double* out4)
 {
     STRQ_ENTER(c);
-    if (!out4) { c->err = "bad argument"; return STRQ_ERR_ARG; }
-    DetectState* d = dstate(c);
-    out4[0] = d->rn_ms; out4[1] = d->rn_fitted; out4[2] = d->rn_applied; out4[3] = d->rn_launches;
-    return STRQ_OK;
+    return last_pass(c, PASS_RENORM, out4);
 }
 
 int strq_scan_set(strq_ctx* c, int32_t n_cand, const int32_t* cand_target_id, double min_score)

@@ -490,6 +490,19 @@ class Context(object):
         raw = pool.tobytes()
         return [raw[off[i]:off[i + 1]].decode() for i in range(self._n_batch)]
 
+    def _last(self, entry, keys, floats=("ms",)):
+        """strq_last_<entry> as a dict: `keys` in the order of the entry's layout, integers but for `floats`."""
+        out = np.zeros(len(keys))
+        self._check(getattr(self._lib, "strq_last_" + entry)(self._h, _ptr(out)))
+        return {k: float(v) if k in floats else int(v) for k, v in zip(keys, out)}
+
+    def _fetch_records(self, entry, dtype):
+        """strq_batch_fetch_<entry>: one element of `dtype` per read of the last batch."""
+        n = getattr(self, '_n_batch', 0)
+        out = np.zeros(max(1, n), dtype=dtype)
+        self._check(getattr(self._lib, "strq_batch_fetch_" + entry)(self._h, _ptr(out), ctypes.c_int64(n)))
+        return out[:n]
+
     def set_units(self, on):
         """strq_set_units: later run calls also produce repeat-unit positions (batch_fetch_units)."""
         self._check(self._lib.strq_set_units(self._h, ctypes.c_int32(1 if on else 0)))
@@ -506,9 +519,7 @@ class Context(object):
 
     def last_units(self):
         """The unit pass of the last run call: {'ms', 'ws_bytes', 'windows', 'positions'} (strq_last_units)."""
-        out = np.zeros(4)
-        self._check(self._lib.strq_last_units(self._h, _ptr(out)))
-        return {'ms': float(out[0]), 'ws_bytes': float(out[1]), 'windows': int(out[2]), 'positions': int(out[3])}
+        return self._last("units", ("ms", "ws_bytes", "windows", "positions"), floats=("ms", "ws_bytes"))
 
     def set_confidence(self, on):
         """strq_set_confidence: later run calls also run the forward pass over every decoded window (batch_fetch_confidence)."""
@@ -524,9 +535,7 @@ class Context(object):
 
     def last_confidence(self):
         """The forward pass of the last run call: {'ms', 'windows', 'no_path', 'max_exponent'} (strq_last_confidence)."""
-        out = np.zeros(4)
-        self._check(self._lib.strq_last_confidence(self._h, _ptr(out)))
-        return {'ms': float(out[0]), 'windows': int(out[1]), 'no_path': int(out[2]), 'max_exponent': int(out[3])}
+        return self._last("confidence", ("ms", "windows", "no_path", "max_exponent"))
 
     def set_mod_llr(self, on):
         """strq_set_mod_llr: later run calls also score every repeat unit of a modification pattern under both branches of the
@@ -545,9 +554,7 @@ class Context(object):
 
     def last_mod_llr(self):
         """The scoring pass of the last run call: {'ms', 'units', 'reads', 'launches'} (strq_last_mod_llr)."""
-        out = np.zeros(4)
-        self._check(self._lib.strq_last_mod_llr(self._h, _ptr(out)))
-        return {'ms': float(out[0]), 'units': int(out[1]), 'reads': int(out[2]), 'launches': int(out[3])}
+        return self._last("mod_llr", ("ms", "units", "reads", "launches"))
 
     # ---- variants ------------------------------------------------------------------------
     def target_set_variants(self, target_id, model_id, lo, hi, n_alt, context_units):
@@ -588,9 +595,7 @@ class Context(object):
 
     def last_variants(self):
         """The variant pass of the last run call: {'launches', 'passages', 'ms', 'reads'} (strq_last_variants)."""
-        out = np.zeros(4)
-        self._check(self._lib.strq_last_variants(self._h, _ptr(out)))
-        return {'launches': int(out[0]), 'passages': int(out[1]), 'ms': float(out[2]), 'reads': int(out[3])}
+        return self._last("variants", ("launches", "passages", "ms", "reads"))
 
     # ---- anchored counting ---------------------------------------------------------------
     def target_set_anchored(self, target_id, end_model_id, end_bias, start_model_id, start_bias):
@@ -605,18 +610,13 @@ class Context(object):
 
     def batch_fetch_anchored(self):
         """Records of the last batch (strq_batch_fetch_anchored): a structured array of ANCHORED_DTYPE, one element per read."""
-        n = getattr(self, '_n_batch', 0)
-        out = np.zeros(max(1, n), dtype=ANCHORED_DTYPE)
-        self._check(self._lib.strq_batch_fetch_anchored(self._h, _ptr(out), ctypes.c_int64(n)))
-        return out[:n]
+        return self._fetch_records("anchored", ANCHORED_DTYPE)
 
     def last_anchored(self):
         """The anchored pass of the last run call (strq_last_anchored): {'ms', 'kinds' (reads of kind 0..3), 'launches',
         'register_resident', 'lane_layout' (windows decoded on those kernel shapes)}."""
-        out = np.zeros(8)
-        self._check(self._lib.strq_last_anchored(self._h, _ptr(out)))
-        return {'ms': float(out[0]), 'kinds': tuple(int(v) for v in out[1:5]), 'launches': int(out[5]),
-                'register_resident': int(out[6]), 'lane_layout': int(out[7])}
+        d = self._last("anchored", ("ms", 0, 1, 2, 3, "launches", "register_resident", "lane_layout"))
+        return {'ms': d['ms'], 'kinds': tuple(d[k] for k in range(4)), **{k: d[k] for k in ('launches', 'register_resident', 'lane_layout')}}
 
     def target_set_tracts(self, target_id, model_id, n_tracts=0, bias=()):
         """strq_target_set_tracts: the compound model of a target (hmm.CompoundRepeatModel, with model_set_tracts applied) and the
@@ -632,16 +632,11 @@ class Context(object):
 
     def batch_fetch_tracts(self):
         """Records of the last batch (strq_batch_fetch_tracts): a structured array of TRACTS_DTYPE, one element per read."""
-        n = getattr(self, '_n_batch', 0)
-        out = np.zeros(max(1, n), dtype=TRACTS_DTYPE)
-        self._check(self._lib.strq_batch_fetch_tracts(self._h, _ptr(out), ctypes.c_int64(n)))
-        return out[:n]
+        return self._fetch_records("tracts", TRACTS_DTYPE)
 
     def last_tracts(self):
         """The tract pass of the last run call (strq_last_tracts): {'ms', 'windows' (decoded), 'launches', 'failed' (status 2 or 3)}."""
-        out = np.zeros(4)
-        self._check(self._lib.strq_last_tracts(self._h, _ptr(out)))
-        return {'ms': float(out[0]), 'windows': int(out[1]), 'launches': int(out[2]), 'failed': int(out[3])}
+        return self._last("tracts", ("ms", "windows", "launches", "failed"))
 
     def set_anchored_mod(self, on):
         """strq_set_anchored_mod: later run calls with anchored counting on also call the methylation pattern of every read of
@@ -668,9 +663,7 @@ class Context(object):
 
     def last_anchored_mod(self):
         """The methylation calls of the last run call (strq_last_anchored_mod): {'ms', 'reads', 'units', 'launches'}."""
-        out = np.zeros(4)
-        self._check(self._lib.strq_last_anchored_mod(self._h, _ptr(out)))
-        return {'ms': float(out[0]), 'reads': int(out[1]), 'units': int(out[2]), 'launches': int(out[3])}
+        return self._last("anchored_mod", ("ms", "reads", "units", "launches"))
 
     # ---- renorm: the second normalisation step ---------------------------------------------
     def target_set_renorm(self, target_id, Q, A, model_min, model_max):
@@ -692,10 +685,7 @@ class Context(object):
     def batch_fetch_renorm(self):
         """Records of the last batch (strq_batch_fetch_renorm): a structured array of RENORM_DTYPE, one element per read; 'fit' holds
         the morphology levels, the filtered and the raw signal in that order."""
-        n = getattr(self, '_n_batch', 0)
-        out = np.zeros(max(1, n), dtype=RENORM_DTYPE)
-        self._check(self._lib.strq_batch_fetch_renorm(self._h, _ptr(out), ctypes.c_int64(n)))
-        return out[:n]
+        return self._fetch_records("renorm", RENORM_DTYPE)
 
     def debug_renorm_fit(self, target_id, h3):
         """strq_debug_renorm_fit: the fit kernel alone on three histograms (uint32 [3, 1024]); one element of RENORM_DTYPE."""
@@ -708,9 +698,7 @@ class Context(object):
 
     def last_renorm(self):
         """The renorm pass of the last run call (strq_last_renorm): {'ms', 'fitted', 'applied', 'launches'}."""
-        out = np.zeros(4)
-        self._check(self._lib.strq_last_renorm(self._h, _ptr(out)))
-        return {'ms': float(out[0]), 'fitted': int(out[1]), 'applied': int(out[2]), 'launches': int(out[3])}
+        return self._last("renorm", ("ms", "fitted", "applied", "launches"))
 
     def batch_upload(self, signals, offsets, target_ids, host_stats=None):
         """signals: one concatenated int16 or float64 array; offsets: n_reads + 1."""

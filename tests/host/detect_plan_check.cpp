@@ -1,5 +1,6 @@
 // Stand-alone host program over strique_amd/csrc/detect_plan.h (no HIP): the anchored record from the marks of a MARK decode, the
-// per-read rows, the grouping of tasks, the layout of a workspace (Carve).  Built and run under ASan/UBSan by tests/test_detect_plan_host.py; exits 0 when every check holds.
+// per-read rows, the grouping of tasks, the layout of a workspace (Carve), the ragged packer of the fetches, the pass table with the
+// layouts of strq_last_*, the order of a second decode.  Built and run under ASan/UBSan by tests/test_detect_plan_host.py; exits 0 when every check holds.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -71,9 +72,126 @@ static void carve_checks()
     CHECK(same(Carve::at<Odd>(block.data(), a)[2], value_of<Odd>(9, 2)) && *Carve::at<char>(block.data(), b) == 'x' && Carve::at<int32_t>(block.data(), c)[4] == -5);
 }
 
+// The ragged packer on lengths {0, 3, 0, 1}: offsets, a pool that is exactly filled, one that is an element short, no pool, no reads,
+// and two pools at once.  Pools are exactly as large as their capacity (ASan sees a copy behind it).
+static void packer_checks()
+{
+    const std::vector<std::vector<int32_t>> reads = {{}, {7, 8, 9}, {}, {5}};
+    const int64_t want[5] = {0, 0, 3, 3, 4};
+    auto len = [&](int64_t i) { return (int64_t)reads[(size_t)i].size(); };
+    int copies = 0;
+    auto run = [&](int64_t n, int64_t* off, int32_t* pool, int64_t cap) {
+        return pack_ragged(n, off, pool != nullptr, cap, len, [&](int64_t i, int64_t pos) {
+            ++copies;
+            for (size_t j = 0; j < reads[(size_t)i].size(); ++j) pool[pos + (int64_t)j] = reads[(size_t)i][j];
+        });
+    };
+    std::vector<int64_t> off(5, -1); std::vector<int32_t> pool(4, -1);
+    CHECK(run(4, off.data(), pool.data(), 4) == 4);
+    for (int k = 0; k < 5; ++k) CHECK(off[(size_t)k] == want[k]);
+    CHECK(pool[0] == 7 && pool[1] == 8 && pool[2] == 9 && pool[3] == 5);
+    // capacity 3: read 3 does not fit; the offsets up to it are written, nothing behind them
+    std::vector<int64_t> off3(5, -1); std::vector<int32_t> pool3(3, -1);
+    CHECK(run(4, off3.data(), pool3.data(), 3) == 3);
+    CHECK(off3[0] == 0 && off3[1] == 0 && off3[2] == 3 && off3[3] == 3 && off3[4] == -1 && pool3[2] == 9);
+    // no pool: the same offsets, nothing copied
+    std::vector<int64_t> offm(5, -1);
+    copies = 0;
+    CHECK(run(4, offm.data(), nullptr, 0) == 4 && copies == 0);
+    for (int k = 0; k < 5; ++k) CHECK(offm[(size_t)k] == want[k]);
+    // no reads: off[0] alone
+    std::vector<int64_t> off0(1, -1);
+    CHECK(run(0, off0.data(), pool.data(), 4) == 0 && off0[0] == 0);
+    // two pools: values of lengths {0, 6, 0, 2} beside them
+    const int64_t vlen[4] = {0, 6, 0, 2}, want2[5] = {0, 0, 6, 6, 8};
+    std::vector<int64_t> offa(5, -1), offb(5, -1); std::vector<int32_t> pa(4, -1); std::vector<double> pb(8, -1.0);
+    int64_t total2 = -1;
+    auto run2 = [&](int64_t* o2, bool pools, int64_t cap, int64_t cap2) {
+        return pack_ragged2(4, offa.data(), o2, pools, cap, cap2, &total2, [&](int64_t i, int64_t* k, int64_t* k2) { *k = len(i); *k2 = vlen[i]; },
+                            [&](int64_t i, int64_t pos, int64_t pos2) {
+                                for (int64_t j = 0; j < len(i); ++j) pa[(size_t)(pos + j)] = reads[(size_t)i][(size_t)j];
+                                for (int64_t j = 0; j < vlen[i]; ++j) pb[(size_t)(pos2 + j)] = (double)(10 * i + j);
+                            });
+    };
+    CHECK(run2(offb.data(), true, 4, 8) == 4 && total2 == 8);
+    for (int k = 0; k < 5; ++k) CHECK(offa[(size_t)k] == want[k] && offb[(size_t)k] == want2[k]);
+    CHECK(pa[3] == 5 && pb[0] == 10.0 && pb[5] == 15.0 && pb[6] == 30.0 && pb[7] == 31.0);
+    CHECK(run2(nullptr, true, 4, 7) == 3);          // the second pool an element short, no offsets of its own
+    CHECK(run2(offb.data(), true, 2, 8) == 1);      // the first pool too small for read 1
+    total2 = -1;
+    CHECK(run2(nullptr, false, 0, 0) == 4 && total2 == 8);
+}
+
+// The layouts of strq_last_*: every field of a PassStats distinct, the two layouts that do not start with the milliseconds as literals.
+static void stats_checks()
+{
+    PassStats s; s.ms = 0.5f;
+    for (int k = 0; k < 7; ++k) s.v[k] = 10.0 + k;
+    for (int p = 0; p < N_PASS; ++p) {
+        double out[9]; for (double& o : out) o = -1.0;
+        pass_stats_out((Pass)p, s, out);
+        const int n = PASSES[p].n_out;
+        CHECK(n == (p == PASS_ANCH ? 8 : 4) && out[n] == -1.0);
+        if (p == PASS_VAR) CHECK(out[0] == 10.0 && out[1] == 11.0 && out[2] == 0.5 && out[3] == 12.0);          // launches, passages, ms, reads
+        else if (p == PASS_ANCH) {          // ms, kinds[4], launches, g2, lane
+            CHECK(out[0] == 0.5 && out[1] == 10.0 && out[2] == 11.0 && out[3] == 12.0 && out[4] == 13.0 && out[5] == 14.0 && out[6] == 15.0 && out[7] == 16.0);
+        } else CHECK(out[0] == 0.5 && out[1] == 10.0 && out[2] == 11.0 && out[3] == 12.0);
+        for (int a = 0; a < n; ++a) for (int b = a + 1; b < n; ++b) CHECK(out[a] != out[b]);          // no field handed out twice
+    }
+    CHECK(VAR_LAUNCHES == 0 && VAR_PASSAGES == 1 && VAR_READS == 2 && ANCH_KINDS == 0 && ANCH_LAUNCHES == 4 && ANCH_G2 == 5 && ANCH_LANE == 6);
+    PassStats all[N_PASS];
+    for (PassStats& t : all) t = s;
+    std::fill(all, all + N_PASS, PassStats());
+    for (const PassStats& t : all) { CHECK(t.ms == 0.0f); for (double v : t.v) CHECK(v == 0.0); }
+    // what a scan refuses, in the order the run call looks: anchored-mod in front of anchored; units, confidence and mod-llr never
+    Extras ex;
+    CHECK(scan_refusal(ex) == N_PASS);
+    ex.units = ex.conf = ex.llr = true;
+    CHECK(scan_refusal(ex) == N_PASS);
+    ex.renorm = true; CHECK(scan_refusal(ex) == PASS_RENORM);
+    ex.tracts = true; CHECK(scan_refusal(ex) == PASS_TRACTS);
+    ex.var = true; CHECK(scan_refusal(ex) == PASS_VAR);
+    ex.anch = true; CHECK(scan_refusal(ex) == PASS_ANCH);
+    ex.amod = true; CHECK(scan_refusal(ex) == PASS_AMOD);
+    CHECK(scan_refusal_text(PASS_AMOD) == "anchored-mod: not available in a scan (strq_scan_set)");
+    CHECK(ran_without_text(PASS_UNITS) == "the last batch ran without unit positions (strq_set_units)");
+    CHECK(ran_without_text(PASS_AMOD) == "the last batch ran without anchored methylation calls (strq_set_anchored_mod)");
+}
+
+// The order of a second decode: five reads over two shapes and two routes.
+static void decode_order_checks()
+{
+    struct M { int id; };
+    const M models[5] = {{0}, {1}, {2}, {3}, {4}};
+    const std::vector<int> who = {3, 4, 7, 9, 12};
+    const GroupItem item[5] = {{1, 9, 100}, {0, 5, 300}, {0, 9, 200}, {1, 9, 50}, {0, 5, 10}};
+    auto of = [&](int i, GroupItem& it, const M*& m) {
+        const size_t k = (size_t)(std::find(who.begin(), who.end(), i) - who.begin());
+        it = item[k]; m = &models[k];
+        return true;
+    };
+    DecodeOrder<M> D;
+    CHECK(decode_order<M>(who, of, D));
+    CHECK(D.G.groups.size() == 3 && D.G.groups[0].route == 0 && D.G.groups[0].shape == 5 && D.G.groups[1].shape == 9 && D.G.groups[2].route == 1 && D.G.groups[2].count == 2);
+    CHECK(D.read_of.size() == 5 && D.model.size() == 5);
+    for (size_t at = 0; at < 5; ++at) {
+        const size_t k = (size_t)D.G.order[at];
+        CHECK(D.read_of[at] == who[k] && D.model[at] == &models[k] && D.G.pos[k] == (int32_t)at);
+    }
+    CHECK(D.read_of[0] == 4 && D.read_of[1] == 12 && D.read_of[2] == 7 && D.read_of[3] == 3 && D.read_of[4] == 9);
+    // a read the pass cannot take: nothing is planned
+    DecodeOrder<M> R;
+    CHECK(!decode_order<M>(who, [&](int i, GroupItem& it, const M*& m) { return i != 7 && of(i, it, m); }, R) && R.G.groups.empty() && R.read_of.empty());
+    DecodeOrder<M> E;
+    CHECK(decode_order<M>(std::vector<int>(), of, E) && E.G.groups.empty() && E.read_of.empty() && E.model.empty());
+}
+
 int main()
 {
     carve_checks();
+    packer_checks();
+    stats_checks();
+    decode_order_checks();
 
     // a read that ends in the repeat: window of 1000 observations from sample 5000, section from observation 40 to 979, 20 behind it
     strq_anchored a = anchored_record(2, 5000, 1000, 0, 44, -1, -1234.5, 41, 981);
