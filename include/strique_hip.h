@@ -358,6 +358,39 @@ int strq_batch_run(strq_ctx* ctx);
  * the order (STRQ_SERIAL=1: everything on one stream, rows before the run call returns, as up to ABI 11). */
 int strq_batch_run_range(strq_ctx* ctx, int64_t first, int64_t last);
 int strq_batch_fetch(strq_ctx* ctx, strq_result* out);
+/* Methylation calls for the CpG groups of the configured flanks (strique_amd/flank_mod.py states the rule).  One record per group
+ * of a flank whose stretch exists: flank 0 prefix / 1 suffix as configured, pos the + strand position of the group's first C in the
+ * configured string, status 0 scored, 1 no path, 2 edge, 3 skipped, 4 too long; begin / end the raw samples of u and w (-1 unless
+ * scored), v_base / v_mod the two masked Viterbi log-probabilities (NaN unless scored; llr = v_mod - v_base). */
+typedef struct {
+    int32_t flank, pos, n_sites, n_columns, status, pad_;
+    int64_t begin, end;
+    double v_base, v_mod;
+} strq_flank_mod_group;
+/* The models of one flank of a target, `which` 0 prefix / 1 suffix AS THE STRAND OF THE TARGET READS IT: profile_model_id the flank
+ * profile model (hmm.FlankProfileModel of the whole configured flank, flank_len bases; it must fit a Viterbi kernel with
+ * back-pointers), column_of one entry per emitting state of it (-1: no column), and n_groups (0 .. 64) groups of six int32 each:
+ * c0, c1 (profile columns, inclusive), the site model (hmm.SiteModModel, at most 128 emitting states: its edge image is built here),
+ * and what the records report -- flank as configured, pos, n_sites.  Both flanks and a modification model (strq_target_set_mod) make
+ * a target one whose reads are called. */
+int strq_target_set_flank_mod(strq_ctx* ctx, int32_t target_id, int32_t which, int32_t profile_model_id, int32_t flank_len,
+                              const int32_t* column_of, int32_t n_groups, const int32_t* groups);
+/* on = 1: later run calls also call the CpG groups of the flanks of every read whose gate passed, that could be conditioned and whose
+ * target has the models above -- the prefix flank on the raw samples [whole prefix begin, prefix_end), the suffix flank on
+ * [suffix_begin, whole suffix end) (strq_batch_fetch_flank_ranges), where begin < end.  Segmentation in pieces of at most
+ * STRQ_FLANK_MOD_WS_BYTES of back-pointers (default 8 GiB).  Rows and every other output are unchanged; refused by a scan. */
+int strq_set_flank_mod(strq_ctx* ctx, int32_t on);
+/* The records of the last batch, ragged: called[r] = 1 for a read that qualified, records off[r] .. off[r + 1] of `pool` (prefix
+ * groups first, in flank order).  Two calls: pool = NULL measures (off is written), then with pool_cap >= off[n]. */
+int strq_batch_fetch_flank_mod(strq_ctx* ctx, int32_t* called, int64_t* off, strq_flank_mod_group* pool, int64_t pool_cap);
+/* The pass of the last run call: [0] GPU ms  [1] flank stretches decoded  [2] groups scored  [3] launches. */
+int strq_last_flank_mod(strq_ctx* ctx, double* out4);
+/* The stretches of the whole configured flanks of every read of the last batch, in raw samples: out4[4 r ..] = where flank row 0
+ * of the prefix alignment sits, prefix_end, suffix_begin, where the last flank row of the suffix alignment sits -- the positions of
+ * __detect_range__ (scripts/STRique.py:538-548) without pre_trim / post_trim.  The row's prefix_begin and suffix_end are taken
+ * `trim` rows further in (STRique.py:598-599) and bound the inner 50 nt of a 150-nt flank; the flank methylation calls
+ * (strique_amd/flank_mod.py) are defined on the whole flank.  Zeros for a read without a row.  n: the reads of the batch. */
+int strq_batch_fetch_flank_ranges(strq_ctx* ctx, int64_t* out4, int64_t n);
 int strq_batch_fetch_range(strq_ctx* ctx, int64_t first, int64_t last, strq_result* out);
 /* ---- scan: which target and strand a read spans, from its signal alone (no counterpart in the reference, which takes both from a
  * SAM record: scripts/STRique.py:673-679,689-692) ----
@@ -704,6 +737,17 @@ int strq_debug_variant_bounds(strq_ctx* ctx, int32_t model_id, int32_t n_alt, in
                               const int32_t* path, const uint64_t* rec, const uint32_t* last, const int32_t* status,
                               const int32_t* cap, int32_t stride, int32_t guard, int32_t* n, int32_t* bad, int32_t* w,
                               int32_t* branch, int32_t* untouched);
+/* Test hook: the bounds kernel of the flank methylation calls (strique_amd/flank_mod.py states the rule) for n_flanks (1 ...) flank
+ * stretches decoded with one flank profile model of n_emit emitting states, column_of[s] the profile column of emitting state s
+ * (-1: none).  Stretch f has T_f = off[f + 1] - off[f] observations (below 2^30), path[off[f] ..] the emitting state of every
+ * observation, status[f] the decode status to present (0 a path, anything else none; NULL: a path everywhere), and the CpG groups
+ * g_off[f] .. g_off[f + 1] (at most 64 per stretch): group g covers the profile columns groups[2 g] .. groups[2 g + 1].
+ * out: three int32 per group -- status (0 scored, 1 no path, 2 edge: the first emission from the group's columns is the stretch's
+ * first observation or the last one its last, 3 skipped: no emission from them), u = first - 1 and w = last + 1 (-1, -1 unless
+ * scored).  STRQ_ERR_ARG for a state outside the emitting ones or more than 64 groups in a stretch.  Own buffers on the context's
+ * stream: a batch in flight and its results are left alone. */
+int strq_debug_flank_mod_bounds(strq_ctx* ctx, int32_t n_flanks, const int64_t* off, const int32_t* path, const int32_t* status,
+                                int32_t n_emit, const int32_t* column_of, const int64_t* g_off, const int32_t* groups, int32_t* out);
 
 /* Kernel timing of the last batched call, milliseconds (HIP events on the library's stream):
  * [0] table build  [1] forward DP  [2] trace pass  [3] total  [4] table entries re-evaluated on

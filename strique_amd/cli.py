@@ -22,6 +22,7 @@ from collections import defaultdict, deque, namedtuple
 import numpy as np
 
 from . import anchored as anchored_mod
+from . import flank_mod as flank_mod_rule
 from . import renorm as renorm_mod
 from . import scan as scan_mod
 from . import tracts as tracts_mod
@@ -274,6 +275,10 @@ def count(argv):
                                                                                                   "that end or start inside the repeat, on the samples their record puts into the repeat, and "
                                                                                                   "write it to FILE: one row per count row, columns " + " ".join(anchored_mod.MOD_HEADER) +
                                                                                                   " (llr: the per-unit ratios when --mod-llr is given as well, else -)")
+    parser.add_argument("--flank-mod", dest="flank_mod", default=None, metavar="FILE", help="With --mod_model: also call the CpG groups of the configured flanks (one mCpG "
+                                                                                            "log-likelihood ratio per group of CpG sites that share a k-mer) and write them to FILE: one row "
+                                                                                            "per count row, columns " + " ".join(flank_mod_rule.HEADER) + " (calls: flank p|s : position of "
+                                                                                            "the group's first C in the configured flank : sites : ratio, - without a score)")
     parser.add_argument("--renorm", type=float, default=None, metavar="MIN_SHARE", help="Refit scale and shift of every read's normalised signals against its target's k-mer "
                                                                                       "composition, and count on the corrected signals where the fitted repeat share is at least "
                                                                                       "MIN_SHARE (inside (0, 1); there is no default: README, 'Renorm').  The count rows of such "
@@ -319,6 +324,10 @@ def count(argv):
         parser.error("--anchored-mod needs --mod_model: the calls are those of the modification model")
     if args.anchored_mod and args.scan:
         parser.error("--anchored-mod cannot be combined with --scan: a scan takes a read for a target when it finds both flanks")
+    if args.flank_mod and not args.mod_model:
+        parser.error("--flank-mod needs --mod_model: the calls compare the modification model's k-mer table with the base table")
+    if args.flank_mod and args.scan:
+        parser.error("--flank-mod cannot be combined with --scan: the flank pass runs on reads whose target and strand an alignment gives")
     if args.renorm is not None and not 0 < args.renorm < 1:
         parser.error("--renorm MIN_SHARE must be inside (0, 1)")
     if args.renorm_out and args.renorm is None:
@@ -406,7 +415,7 @@ def count(argv):
     stats = {}
     fault = 0
     paths = dict(units=args.units, confidence=args.confidence, mod_llr=args.mod_llr, scores=args.scan_scores, anchored=args.anchored, variants=args.variants,
-                 renorm=args.renorm_out, anchored_mod=args.anchored_mod, tracts=args.tracts)
+                 renorm=args.renorm_out, anchored_mod=args.anchored_mod, tracts=args.tracts, flank_mod=args.flank_mod)
     with contextlib.ExitStack() as stack:
         # rank 0 writes: as the batches are done in a single process (run_count), after the gather otherwise
         files = {name: stack.enter_context(open(path, 'w')) if (path and rank == 0) else None for name, path in paths.items()}
@@ -419,7 +428,8 @@ def count(argv):
                              anchored=args.anchored_min_score, anchored_out=now['anchored'],
                              anchored_mod=bool(args.anchored_mod), anchored_mod_out=now['anchored_mod'],
                              variants=alt_units if args.variants else None, variants_out=now['variants'],
-                             renorm=args.renorm, renorm_out=now['renorm'], tracts=bool(args.tracts), tracts_out=now['tracts'])
+                             renorm=args.renorm, renorm_out=now['renorm'], tracts=bool(args.tracts), tracts_out=now['tracts'],
+                             flank_mod=bool(args.flank_mod), flank_mod_out=now['flank_mod'])
         except DeviceFault:
             if world == 1:
                 raise SystemExit(3)
@@ -435,7 +445,7 @@ def count(argv):
                 raise SystemExit(3)
             merged = gather_rows(rows, stats["items"], sdist, units=bool(args.units), scan=scan, confidence=bool(args.confidence), mod_llr=bool(args.mod_llr),
                                  anchored=bool(args.anchored), variants=bool(args.variants), renorm=args.renorm is not None, anchored_mod=bool(args.anchored_mod),
-                                 tracts=bool(args.tracts))
+                                 tracts=bool(args.tracts), flank_mod=bool(args.flank_mod))
             if rank == 0:
                 write_rows(out, merged.rows)
                 for o in OUTPUTS:
@@ -658,6 +668,8 @@ OUTPUTS = (
            lambda v: renorm_mod.pack(v), lambda text: renorm_mod.unpack(text), 'renorm_rows', False),
     Output('variants', lambda scan: VARIANTS_HEADER, lambda q, t, s, row, v: format_variants(q, t, s, row[0], v),
            lambda v: _pack_variants(v), lambda text: _unpack_variants(text), 'variant_rows', False),
+    Output('flank_mod', lambda scan: flank_mod_rule.HEADER, lambda q, t, s, row, v: flank_mod_rule.format_row(q, t, s, row[0], v),
+           lambda v: _pack_flank_mod(v), lambda text: _unpack_flank_mod(text), 'flank_mod_rows', False),
     Output('tracts', lambda scan: tracts_mod.HEADER, lambda q, t, s, row, v: tracts_mod.format_row(q, t, s, row[0], v),
            lambda v: _pack_tracts(v), lambda text: _unpack_tracts(text), 'tract_rows', False),
     Output('anchored_mod', lambda scan: anchored_mod.MOD_HEADER, lambda q, t, s, row, v: anchored_mod.format_mod_row(q, t, s, *(v or (None, None))),
@@ -665,10 +677,31 @@ OUTPUTS = (
     Output('anchored', lambda scan: anchored_mod.HEADER, lambda q, t, s, row, v: anchored_mod.format_row(q, t, s, v),
            lambda v: _pack_anchored(v), lambda text: _unpack_anchored(text), 'anchored_rows', False),
 )
-# (`renorm`, `variants`, `tracts`, `anchored_mod` and `anchored`, the last fields, default to None: callers that build a Merged from the five
+# (`renorm`, `variants`, `flank_mod`, `tracts`, `anchored_mod` and `anchored`, the last fields, default to None: callers that build a Merged from the five
 # values before them keep working.  `anchored` stays the last field, as it did when `variants`, `anchored_mod` and `tracts` came in: fields
 # behind the first five are taken by name.)
-Merged = namedtuple('Merged', ['rows'] + [o.name for o in OUTPUTS], defaults=(None, None, None, None, None))
+Merged = namedtuple('Merged', ['rows'] + [o.name for o in OUTPUTS], defaults=(None, None, None, None, None, None))
+
+
+def flank_mod_value(calls):
+    """The value of the flank_mod output from Detected.flank_mod: None, or [(flank, pos, n_sites, llr or None)] -- a group that was not
+    scored has no ratio."""
+    if calls is None:
+        return None
+    return [(int(f), int(pos), int(ns), float(llr) if status == flank_mod_rule.SCORED else None) for f, pos, ns, _, status, _, _, llr in calls]
+
+
+def _pack_flank_mod(v):
+    """The calls of a read as they travel between ranks: flank:pos:n_sites:ratio per group, the ratio as repr(), '-' for none."""
+    return ','.join('%d:%d:%d:%s' % (f, pos, ns, '-' if llr is None else repr(float(llr))) for f, pos, ns, llr in v)
+
+
+def _unpack_flank_mod(text):
+    out = []
+    for item in text.split(','):
+        f, pos, ns, llr = item.split(':')
+        out.append((int(f), int(pos), int(ns), None if llr == '-' else float(llr)))
+    return out
 
 
 def _pack_tracts(v):
@@ -710,7 +743,7 @@ def _unpack_anchored(text):
 
 
 def outputs_on(**flags):
-    """The entries of OUTPUTS whose flag (units=, confidence=, mod_llr=, scores=, anchored=, variants=, renorm=, anchored_mod=, tracts=) is set."""
+    """The entries of OUTPUTS whose flag (units=, confidence=, mod_llr=, scores=, anchored=, variants=, renorm=, anchored_mod=, tracts=, flank_mod=) is set."""
     return [o for o in OUTPUTS if flags.get(o.name)]
 
 
@@ -732,7 +765,7 @@ def _read_values(target, strand, det, scores=None):
         return target, strand, None, dict(scores=scores)
     return target, strand, det.row, dict(units=det.units, confidence=det.conf, mod_llr=det.llr, scores=scores, anchored=det.anchored, variants=det.variants,
                                          renorm=getattr(det, 'renorm', None), anchored_mod=(det.anchored, getattr(det, 'anchored_mod', None)),
-                                         tracts=getattr(det, 'tracts', None))
+                                         tracts=getattr(det, 'tracts', None), flank_mod=flank_mod_value(getattr(det, 'flank_mod', None)))
 
 
 def _emit(sink, on, seq, qname, target, strand, row, values):
@@ -767,14 +800,14 @@ def unpack_blob(on, blob):
 
 
 def gather_rows(rows, items, sdist, units=False, scan=None, confidence=False, mod_llr=False, anchored=False, variants=False, renorm=False, anchored_mod=False,
-                tracts=False):
+                tracts=False, flank_mod=False):
     """Reads of this rank (run_count with world > 1) -> fixed-size records + one blob per read (pack_blob) -> one gather -> on rank 0
-    the rows of every file in input order: Merged(rows, units, confidence, mod_llr, scores, renorm, variants, tracts, anchored_mod, anchored), [(sequence number, TSV row)] each, None
+    the rows of every file in input order: Merged(rows, units, confidence, mod_llr, scores, renorm, variants, flank_mod, tracts, anchored_mod, anchored), [(sequence number, TSV row)] each, None
     for an output that was not asked for (scores: asked for by scan) and for every field off rank 0.  `items`: every accepted (qname,
     strand, target) of the input, which each rank derives from the same SAM file (scan: from the same index).  A read that failed
     travels as a record with valid = 0 and writes nothing; a scan read without a winner as one with valid = 2: it writes a score row."""
     on = outputs_on(units=units, confidence=confidence, mod_llr=mod_llr, scores=bool(scan), anchored=anchored, variants=variants, renorm=renorm,
-                    anchored_mod=anchored_mod, tracts=tracts)
+                    anchored_mod=anchored_mod, tracts=tracts, flank_mod=flank_mod)
     rec = np.zeros(len(rows), ROW_DTYPE); blobs = []; idx = np.zeros(len(rows), np.int64)
     for k, (seq, read) in enumerate(rows):
         idx[k] = seq
@@ -831,7 +864,8 @@ def route(stream, loci, log):
 
 def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, out=None, readers=0, stats=None, units=False, units_out=None,
               scan=None, scores_out=None, confidence=False, conf_out=None, mod_llr=False, llr_out=None, anchored=None, anchored_out=None,
-              variants=None, variants_out=None, renorm=None, renorm_out=None, anchored_mod=False, anchored_mod_out=None, tracts=False, tracts_out=None):
+              variants=None, variants_out=None, renorm=None, renorm_out=None, anchored_mod=False, anchored_mod_out=None, tracts=False, tracts_out=None,
+              flank_mod=False, flank_mod_out=None):
     """Route the SAM records of `stream` to their targets, run this rank's share through
     `counter.detect_batch` and return [(sequence number, TSV row or -- several ranks -- what gather_rows takes)].
 
@@ -862,6 +896,9 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
     `tracts` (not with scan; the counter's targets were added with their compound definitions): the tract pass is on for this run
     (counter.set_tracts(True)) and the counter is asked for Detected records; their rows (strique_amd.tracts.format_row) go to
     `tracts_out` and to stats["tract_rows"].  The count rows and the other files do not change.
+    `flank_mod` (not with scan; a counter with a modification model): the flank pass is on for this run (counter.set_flank_mod(True))
+    and the counter is asked for Detected records; their rows (strique_amd.flank_mod.format_row) go to `flank_mod_out` and to
+    stats["flank_mod_rows"].  The count rows and the other files do not change.
     `scan` ({"min_score", "candidates", "scores"}): `stream` is a list of read ids instead of a SAM stream; every read goes through
     counter.scan_batch and takes target and strand from its winner -- a read without one writes no row, as a read without a target
     writes none; single process: the score rows (strique_amd.scan.format_scores, every read) go to `scores_out` and to
@@ -881,19 +918,22 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
         raise ValueError("renorm cannot be combined with a scan")
     if tracts and scan:
         raise ValueError("tracts cannot be combined with a scan")
+    if flank_mod and scan:
+        raise ValueError("flank methylation calls cannot be combined with a scan")
     if renorm is not None and not 0 < renorm < 1:
         raise ValueError("the renorm share threshold must be inside (0, 1)")
     files = dict(rows=out, units=units_out, confidence=conf_out, mod_llr=llr_out, scores=scores_out, anchored=anchored_out, variants=variants_out,
-                 renorm=renorm_out, anchored_mod=anchored_mod_out, tracts=tracts_out)
+                 renorm=renorm_out, anchored_mod=anchored_mod_out, tracts=tracts_out, flank_mod=flank_mod_out)
     on = outputs_on(units=units, confidence=confidence, mod_llr=mod_llr, scores=scan and scan["scores"], anchored=anchored is not None,
-                    variants=variants is not None, renorm=renorm is not None, anchored_mod=anchored_mod, tracts=tracts)
+                    variants=variants is not None, renorm=renorm is not None, anchored_mod=anchored_mod, tracts=tracts,
+                    flank_mod=flank_mod)
     if out is not None:
         print('\t'.join(HEADER), file=out)
     for o in OUTPUTS:
         stats.setdefault(o.stat, [])
         if files[o.name] is not None:
             print('\t'.join(o.header(scan)), file=files[o.name])
-    extras = {o.name: True for o in on if o.name not in ('scores', 'anchored', 'variants', 'renorm', 'anchored_mod', 'tracts')}
+    extras = {o.name: True for o in on if o.name not in ('scores', 'anchored', 'variants', 'renorm', 'anchored_mod', 'tracts', 'flank_mod')}
     if anchored is not None:
         extras.update(anchored=anchored, records=True)
     if anchored_mod:
@@ -906,6 +946,9 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
         extras.update(records=True)
     if tracts:
         counter.set_tracts(True)
+        extras.update(records=True)
+    if flank_mod:
+        counter.set_flank_mod(True)
         extras.update(records=True)
     rows = []
     records = ((rid, '.', ['.'], 0) for rid in stream) if scan else route(stream, loci, log)
@@ -1097,6 +1140,8 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
                 counter.set_renorm(None)
             if tracts:
                 counter.set_tracts(False)
+            if flank_mod:
+                counter.set_flank_mod(False)
         else:
             # an exception is on its way out (a DeviceFault from the engine thread, a broken input): the batch queued behind
             # the failed one must not be handed to a device that may be hung, and nobody waits for it -- the caller exits,

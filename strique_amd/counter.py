@@ -16,6 +16,7 @@ import numpy as np
 
 from . import anchored as anchored_mod
 from . import ffi
+from . import flank_mod as flank_mod_rule
 from . import hmm as hmm_mod
 from . import renorm as renorm_mod
 from . import tracts as tracts_mod
@@ -41,8 +42,11 @@ target_classifier = namedtuple('target_classifier',
 # renorm: (applied, {signal: None or (a, b, w, score)}) of the second normalisation step, see repeatCounter.set_renorm
 # anchored_mod: None or (pattern, llr) -- the methylation call of an anchored read, see repeatCounter.set_anchored_mod
 # tracts: None or (counts in configured order, log_p) of the compound model, see repeatCounter.set_tracts
-Detected = namedtuple('Detected', ['row', 'units', 'conf', 'llr', 'anchored', 'variants', 'renorm', 'anchored_mod', 'tracts'],
-                      defaults=(None, None, None, None, None))
+# (`tracts` stays the last field, as an existing test asks; `flank_mod` sits in front of it, so a caller that passed a ninth positional
+# value for `tracts` would now fill `flank_mod` -- there is none in the tree: the fields behind `llr` are given by name)
+# flank_mod: None or [(flank, pos, n_sites, n_columns, status, begin, end, llr)] -- the calls of the flanks' CpG groups, see repeatCounter.set_flank_mod
+Detected = namedtuple('Detected', ['row', 'units', 'conf', 'llr', 'anchored', 'variants', 'renorm', 'anchored_mod', 'flank_mod', 'tracts'],
+                      defaults=(None, None, None, None, None, None))
 
 
 class repeatCounter(object):
@@ -80,6 +84,13 @@ class repeatCounter(object):
         self.tract_models = {}
         self.tracts = False            # set_tracts
         self._renorm_done = set()      # classifiers whose tables are registered
+        # flank methylation calls: the whole flanks of every classifier as its strand reads them, its strand, and the classifiers whose
+        # models are registered or were refused ({target_id: message}); built when the switch first meets them, like the anchored models
+        self._flank_src = {}
+        self._flank_strand = {}
+        self.flank_mod_models = {}
+        self.flank_mod_refused = {}
+        self.flank_mod = False         # set_flank_mod
 
     # -------------------------------------------------------------------------------------
     def _classifier(self, repeat, prefix, suffix, prefix_ext, suffix_ext):
@@ -96,6 +107,7 @@ class repeatCounter(object):
             mod.model_id = self.ctx.model_create(mod.baked)
             self.ctx.target_set_mod(tid, mod.model_id, mod.model_min, mod.model_max)
         self._anchored_src[tid] = (repeat, prefix, suffix)
+        self._flank_src[tid] = (prefix_ext, suffix_ext)
         return target_classifier(p, s, pe, se, flanked, mod, tid)
 
     def _ensure_anchored(self):
@@ -187,6 +199,43 @@ class repeatCounter(object):
         """Width of a bin of the rule's grid in pA (beta of a fit is b bins)."""
         return renorm_mod.grid(self.pm.model_min, self.pm.model_max)[1]
 
+    def _ensure_flank_mod(self):
+        """The two flank profile models and the site models of every classifier that has none yet: baked, uploaded and registered.  A
+        flank flank_mod.check refuses leaves its target without calls (flank_mod_refused holds the message); the rows are unchanged."""
+        for tid, flanks in self._flank_src.items():
+            if tid in self.flank_mod_models or tid in self.flank_mod_refused or tid not in self._flank_strand:
+                continue
+            strand, k = self._flank_strand[tid], self.pm.kmer
+            try:
+                checked = [flank_mod_rule.check(f, k, ("prefix", "suffix")[w]) for w, f in enumerate(flanks)]
+            except ValueError as e:
+                self.flank_mod_refused[tid] = str(e)
+                continue
+            made = []
+            for which, (flank, groups) in enumerate(zip(flanks, checked)):
+                seg = hmm_mod.FlankProfileModel(flank, self.pm, self.HMM_config)
+                seg.model_id = self.ctx.model_create(seg.baked)
+                rows = []
+                for g in groups:
+                    site = hmm_mod.SiteModModel(flank_mod_rule.site_sequence(flank, g, k), self.pm, self.pm_mod, self.HMM_config)
+                    cfg_flank, pos = flank_mod_rule.configured(which, g, len(flank), strand)
+                    rows.append((g.c0, g.c1, self.ctx.model_create(site.baked), cfg_flank, pos, g.n_sites))
+                self.ctx.target_set_flank_mod(tid, which, seg.model_id, len(flank), seg.column_of[:seg.baked.silent_start], rows)
+                made.append((seg, groups))
+            self.flank_mod_models[tid] = made
+
+    def set_flank_mod(self, on):
+        """on: detect and detect_batch also call the CpG groups of the configured flanks (strique_amd.flank_mod states the rule) and
+        report one more element per read, behind all others: None -- the gate failed, the read could not be conditioned, or its target
+        has no flank calls -- or a list of (flank, pos, n_sites, n_columns, status, begin, end, llr), one per group of a flank whose
+        stretch exists: the flank (0 prefix, 1 suffix) and the position of the group's first C as configured on the + strand, the
+        status (flank_mod.STATUS_NAMES), the raw samples of u and w and llr = V_mod - V_base (-1, -1 and NaN unless scored).
+        records=True: Detected.flank_mod.  A switch of the counter, like set_anchored_mod.  ValueError without a modification
+        model.  Not with scan_batch."""
+        if on and self.pm is self.pm_mod:
+            raise ValueError("RepeatCounter: flank_mod needs a modification model.")
+        self.flank_mod = bool(on)
+
     def set_anchored_mod(self, on):
         """on: detect and detect_batch with anchored=m also call the methylation pattern of the reads that hold one flank only
         (strique_amd.anchored states which reads get a call and on which stretch) and report one more element per read, directly
@@ -224,6 +273,7 @@ class repeatCounter(object):
         # reverse strand: flanks swap roles (STRique.py:569-575)
         tc_minus = self._classifier(rc(repeat), rc(suffix), rc(prefix), rc(suffix_ext), rc(prefix_ext))
         self.targets[target_name] = (tc_plus, tc_minus)
+        self._flank_strand[tc_plus.target_id] = '+'; self._flank_strand[tc_minus.target_id] = '-'
         if alts:
             # the - strand reads the reverse complement of unit and alt units; calls are reported with the number of the unit as configured
             self._variant_src[tc_plus.target_id] = (repeat, alts)
@@ -286,10 +336,11 @@ class repeatCounter(object):
             raise ValueError("RepeatCounter: anchored_mod needs anchored=m (the calls hang on the anchored records).")
         variants = self.variants
         tracts = self.tracts
+        fmod = self.flank_mod
         reads = [(self._classifier_for(t, s).target_id, r) for t, r, s in items]
         out = [None] * len(items)
         for i, d, _, _ in self._run(reads, units=units, confidence=confidence, mod_llr=mod_llr, anchored=anchored, variants=variants, renorm=self.renorm,
-                                    anchored_mod=self.anchored_mod, tracts=tracts):
+                                    anchored_mod=self.anchored_mod, tracts=tracts, flank_mod=fmod):
             if records:
                 out[i] = d
                 continue
@@ -303,11 +354,13 @@ class repeatCounter(object):
                 extra += (d.variants,)
             if tracts:
                 extra += (d.tracts,)
+            if fmod:
+                extra += (d.flank_mod,)
             out[i] = (d.row,) + extra if extra else d.row
         return out
 
     @contextlib.contextmanager
-    def _switches(self, units, confidence, mod_llr, anchored=None, variants=False, renorm=None, anchored_mod=False, tracts=False):
+    def _switches(self, units, confidence, mod_llr, anchored=None, variants=False, renorm=None, anchored_mod=False, tracts=False, flank_mod=False):
         """The optional passes that were asked for are on inside the block, and all of them off after it."""
         try:
             if anchored is not None:
@@ -332,8 +385,12 @@ class repeatCounter(object):
             if tracts:
                 self._ensure_tracts()
                 self.ctx.set_tracts(True)
+            if flank_mod:
+                self._ensure_flank_mod()
+                self.ctx.set_flank_mod(True)
             yield
         finally:
+            self.ctx.set_flank_mod(False)
             self.ctx.set_tracts(False)
             self.ctx.set_renorm(False)
             self.ctx.set_variants(False)
@@ -343,7 +400,8 @@ class repeatCounter(object):
             self.ctx.set_units(False)
             self.ctx.set_confidence(False)
 
-    def _run(self, reads, units=False, confidence=False, mod_llr=False, scan=None, anchored=None, variants=False, renorm=None, anchored_mod=False, tracts=False):
+    def _run(self, reads, units=False, confidence=False, mod_llr=False, scan=None, anchored=None, variants=False, renorm=None, anchored_mod=False, tracts=False,
+             flank_mod=False):
         """reads: [(target_id, raw_signal)] through the context.  Yields (position in `reads`, Detected, winner, scores) per read, the
         fields of Detected that were not asked for being None.  scan=(candidate target ids, min_score): the target ids of the reads
         are ignored, every read is compared with every candidate (Context.scan_batch_reads); winner is its position in the candidate
@@ -357,7 +415,7 @@ class repeatCounter(object):
             if not idx:
                 continue
             arrs = [sigs[i].astype(np.int16 if want_int else np.float64, copy=False) for i in idx]
-            with self._switches(units, confidence, mod_llr, anchored, variants, renorm, anchored_mod, tracts):
+            with self._switches(units, confidence, mod_llr, anchored, variants, renorm, anchored_mod, tracts, flank_mod):
                 if scan is None:
                     res = self.ctx.detect_batch_reads(arrs, [reads[i][0] for i in idx])      # one pointer per read: no host-side concatenation
                     win = sc = [None] * len(res)
@@ -396,10 +454,14 @@ class repeatCounter(object):
                             strand = self.tract_models[reads[i][0]][1]
                             rec = (tracts_mod.configured_order([int(c) for c in t['count'][:int(t['n_tracts'])]], strand), float(t['log_p']))
                         tr.append(rec)
-            for i, r, m, u, cf, v, w, s, a, vr, rnr, amr, trr in zip(idx, res, mods, pos, conf, vs, win, sc, an, var, rn, am, tr):
+                fm = [None] * len(res)
+                if flank_mod:
+                    fm = [None if g is None else [(int(x['flank']), int(x['pos']), int(x['n_sites']), int(x['n_columns']), int(x['status']), int(x['begin']), int(x['end']),
+                                                   float(x['v_mod'] - x['v_base'])) for x in g] for g in self.ctx.batch_fetch_flank_mod()]
+            for i, r, m, u, cf, v, w, s, a, vr, rnr, amr, trr, fmr in zip(idx, res, mods, pos, conf, vs, win, sc, an, var, rn, am, tr, fm):
                 n = int(r['count']); p = float(r['log_p']) if n or r['log_p'] != 0 else 0
                 row = (n, float(r['score_prefix']), float(r['score_suffix']), p, int(r['offset']), int(r['ticks']), m)
-                yield i, Detected(row, u, cf, None if v is None else v[:, 1] - v[:, 0], a, vr, rnr, amr, trr), w, s
+                yield i, Detected(row, u, cf, None if v is None else v[:, 1] - v[:, 0], a, vr, rnr, amr, fmr, trr), w, s
 
     def candidates(self, targets=None):
         """[(target_name, strand)] of a scan: every target added (or the named ones), in add_target order, '+' before '-'."""

@@ -32,17 +32,18 @@ struct Carve {
 // come with.  DetectState holds what the next run call uses, a slot what its sub-batch was launched with, Batch what the last run call
 // ran with.
 struct Extras { bool units = false, conf = false, llr = false, anch = false, var = false; double anch_min = 0.0; bool renorm = false; double renorm_min = 0.0; bool amod = false;
-                bool tracts = false; };
+                bool tracts = false, fmod = false; };
 
 // The passes, said once.  What the last run call's pass did is one PassStats: the GPU milliseconds and up to seven counters, which the
 // pass's own enum names.  A row of PASSES holds what the entry points need of a pass: its name in messages, its switch, what a batch
 // that ran without it lacks and the entry that turns it on (the "ran without" refusal of its fetch), whether a scan refuses it, and the
 // layout strq_last_* hands out -- `out[k]` is the counter at position k, MS the milliseconds.
-enum Pass { PASS_UNITS, PASS_CONF, PASS_LLR, PASS_VAR, PASS_ANCH, PASS_AMOD, PASS_TRACTS, PASS_RENORM, N_PASS };
+enum Pass { PASS_UNITS, PASS_CONF, PASS_LLR, PASS_VAR, PASS_ANCH, PASS_AMOD, PASS_TRACTS, PASS_RENORM, PASS_FMOD, N_PASS };
 struct PassStats { float ms; double v[7]; };
 enum { UNIT_BYTES, UNIT_READS, UNIT_POSITIONS, CONF_WINDOWS = 0, CONF_NOPATH, CONF_EXPO, LLR_UNITS = 0, LLR_READS, LLR_LAUNCHES,
        VAR_LAUNCHES = 0, VAR_PASSAGES, VAR_READS, ANCH_KINDS = 0 /* .. 3: reads of kind 0 .. 3 */, ANCH_LAUNCHES = 4, ANCH_G2, ANCH_LANE,
-       AMOD_READS = 0, AMOD_UNITS, AMOD_LAUNCHES, TRACT_WINDOWS = 0, TRACT_LAUNCHES, TRACT_FAILED, RN_FITTED = 0, RN_APPLIED, RN_LAUNCHES };
+       AMOD_READS = 0, AMOD_UNITS, AMOD_LAUNCHES, TRACT_WINDOWS = 0, TRACT_LAUNCHES, TRACT_FAILED, RN_FITTED = 0, RN_APPLIED, RN_LAUNCHES,
+       FMOD_FLANKS = 0, FMOD_GROUPS, FMOD_LAUNCHES };
 constexpr int8_t MS = -1;
 struct PassInfo { const char* name; bool Extras::* on; const char* lacks; const char* entry; bool scan_refuses; int n_out; int8_t out[8]; };
 constexpr PassInfo PASSES[N_PASS] = {
@@ -54,13 +55,14 @@ constexpr PassInfo PASSES[N_PASS] = {
     {"anchored-mod", &Extras::amod, "anchored methylation calls", "strq_set_anchored_mod", true, 4, {MS, 0, 1, 2}},
     {"tracts", &Extras::tracts, "tracts", "strq_set_tracts", true, 4, {MS, 0, 1, 2}},
     {"renorm", &Extras::renorm, "renorm", "strq_set_renorm", true, 4, {MS, 0, 1, 2}},
+    {"flank-mod", &Extras::fmod, "flank methylation calls", "strq_set_flank_mod", true, 4, {MS, 0, 1, 2}},
 };
 inline void pass_stats_out(Pass p, const PassStats& s, double* out)
 {
     for (int k = 0; k < PASSES[p].n_out; ++k) out[k] = PASSES[p].out[k] == MS ? (double)s.ms : s.v[PASSES[p].out[k]];
 }
 // The pass a scan refuses first among those switched on, in the order the run call has always looked (N_PASS: none); the refusals as text
-constexpr Pass SCAN_CHECKS[] = {PASS_AMOD, PASS_ANCH, PASS_VAR, PASS_TRACTS, PASS_RENORM};
+constexpr Pass SCAN_CHECKS[] = {PASS_AMOD, PASS_ANCH, PASS_VAR, PASS_TRACTS, PASS_RENORM, PASS_FMOD};
 inline Pass scan_refusal(const Extras& ex)
 {
     for (Pass p : SCAN_CHECKS) if (PASSES[p].scan_refuses && ex.*PASSES[p].on) return p;
@@ -111,6 +113,7 @@ struct VariantRow {
 struct ReadRows {
     std::vector<strq_result> results;
     std::vector<std::string> mod;                 // modification pattern ('-' if none)
+    std::vector<int64_t> flank_ends;              // two per read: where the whole prefix flank begins and the whole suffix flank ends (strq_batch_fetch_flank_ranges)
     std::vector<std::vector<int64_t>> units;      // unit positions (strq_batch_fetch_units)
     std::vector<uint8_t> unit_dec;                // 1: the read was decoded (gate passed, the flanked model found a path)
     std::vector<double> conf;                     // log_lik, count_mean, count_sd (strq_batch_fetch_confidence); NaN while not decoded
@@ -127,17 +130,21 @@ struct ReadRows {
     void size_reads(int64_t n)
     {
         const size_t m = (size_t)n;
-        results.assign(m, strq_result()); mod.assign(m, std::string("-"));
+        results.assign(m, strq_result()); mod.assign(m, std::string("-")); flank_ends.assign(2 * m, 0);
         units.assign(m, std::vector<int64_t>()); unit_dec.assign(m, 0);
         conf.assign(3 * m, NAN); conf_dec.assign(m, 0);
         llr.assign(m, std::vector<double>());
         anch.assign(m, strq_anchored());
         amod_called.clear(); amod.clear(); amod_llr.clear();
         var.assign(m, VariantRow());
-        renorm.clear(); tracts.clear();
+        renorm.clear(); tracts.clear(); fmod_called.clear(); fmod.clear();
     }
     std::vector<strq_tracts> tracts;              // per-tract counts of the compound model (strq_batch_fetch_tracts); status 1: not decoded.  Empty
                                                   // until a run call with the switch on sizes it (size_tracts)
+    // flank methylation calls (strq_batch_fetch_flank_mod): empty until a run call with the switch on sizes them (size_fmod)
+    std::vector<uint8_t> fmod_called;             // 1: the read qualified
+    std::vector<std::vector<strq_flank_mod_group>> fmod;      // ... its records, prefix groups first
+    void size_fmod() { if (fmod_called.size() != results.size()) { fmod_called.assign(results.size(), 0); fmod.assign(results.size(), std::vector<strq_flank_mod_group>()); } }
     static strq_tracts no_tracts() { strq_tracts t = strq_tracts(); t.status = 1; return t; }
     void size_tracts() { if (tracts.size() != results.size()) tracts.assign(results.size(), no_tracts()); }
     void size_renorm() { if (renorm.size() != results.size()) renorm.assign(results.size(), strq_renorm()); }
@@ -150,7 +157,7 @@ struct ReadRows {
     {
         const size_t r = (size_t)read;
         if (read < 0 || r >= results.size()) return;
-        results[r] = strq_result(); mod[r] = "-";
+        results[r] = strq_result(); mod[r] = "-"; flank_ends[2 * r] = flank_ends[2 * r + 1] = 0;
         units[r].clear(); unit_dec[r] = 0;
         conf[3 * r] = conf[3 * r + 1] = conf[3 * r + 2] = NAN; conf_dec[r] = 0;
         llr[r].clear();
@@ -159,6 +166,7 @@ struct ReadRows {
         var[r] = VariantRow();
         if (r < renorm.size()) renorm[r] = strq_renorm();
         if (r < tracts.size()) tracts[r] = no_tracts();
+        if (r < fmod_called.size()) { fmod_called[r] = 0; fmod[r].clear(); }
     }
 };
 

@@ -14,6 +14,8 @@ struct ReadGeom {           // per read, written by finalize_kernel / scan_selec
     int64_t prefix_begin, prefix_end, suffix_begin, suffix_end;
     int32_t gate, pad_;
     float best_prefix, best_suffix;      // raw alignment scores (the overlap planning of the next sub-batch reads their distribution)
+    int64_t prefix_begin_whole, suffix_end_whole;      // where flank row 0 of the prefix and the last row of the suffix sit: the ends before the trim
+                                                       // (strq_batch_fetch_flank_ranges: the stretches of the whole configured flanks)
 };
 
 #ifdef __HIPCC__
@@ -40,6 +42,7 @@ static __device__ inline void prefix_geometry(const AlignTask& tp, const AlignRe
     g.score_prefix = e > b ? (double)rp.best / (double)(e - b) : 0.0;
     g.best_prefix = rp.best;
     g.prefix_begin = row_position(tp.rec, tp.m_total, trim, tp.n);
+    g.prefix_begin_whole = b;
     g.prefix_end = e;
 }
 
@@ -51,6 +54,7 @@ static __device__ inline void suffix_geometry(const AlignTask& ts, const AlignRe
     g.best_suffix = rs.best;
     g.suffix_begin = b;
     g.suffix_end = row_position(ts.rec, ts.m_total, ts.m_total - 1 - trim, ts.n);
+    g.suffix_end_whole = e;
 }
 
 // the reference's gate (STRique.py:602) looks at the two alignments only: a read whose 8-bit morphology signal

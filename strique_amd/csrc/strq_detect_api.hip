@@ -29,6 +29,7 @@
 #include "tract_kernels.h"
 #include "renorm_kernels.h"
 #include "variant_kernels.h"
+#include "flank_mod_kernels.h"
 
 using namespace strq;
 
@@ -79,6 +80,11 @@ struct Target {
     int var_model_id = -1, var_nalt = 0, var_ctx = 0; double var_lo = 0, var_hi = 0;      // strq_target_set_variants
     const RenormTable* rn_dev = nullptr;      // strq_target_set_renorm: the tables of the target on the device (DetectState::rn_tables owns them)
     int tract_model_id = -1, n_tracts = 0, tract_bias[3] = {0, 0, 0};      // strq_target_set_tracts
+    // strq_target_set_flank_mod: per flank as the strand reads it the profile model, the flank's length, its column table on the device,
+    // and per group the columns, the site model and what the records report (flank as configured, pos, n_sites)
+    struct FlankMod { int model_id = -1, len = 0; std::shared_ptr<DevBuf> col; std::vector<FlankGroupRange> range; std::vector<int> site; std::vector<int32_t> info; };
+    FlankMod fmod[2];
+    bool has_fmod() const { return mod_model_id >= 0 && fmod[0].model_id >= 0 && fmod[1].model_id >= 0; }
 };
 
 struct Batch : ReadRows {
@@ -123,6 +129,7 @@ struct DetectState {
     DevBuf llr_ws;                       // per-unit scores (run_llr_pass): tasks, unit bounds, scores
     DevBuf var_ws, var_bounds, var_out;  // variant pass (run_variant_tail): tasks and passage counts; passage bounds; scores
     DevBuf conf_task;                    // forward pass (run_conf_pass): tasks, model images, c0, results, order
+    DevBuf fmod_ws, fmod_bp;             // flank methylation calls (run_flank_mod_pass): tasks, stretches and paths of a piece; its back-pointers
     DevBuf tract_ws, tract_task;         // tract pass (run_tract_pass): geometry and conditioning rows of a sub-batch; tasks, results, their reads and models
     DevBuf anch_ws, anch_task;           // anchored pass (run_anchored_pass): geometry, conditioning rows and kinds of a sub-batch; tasks, results, their reads and models
     hipEvent_t amod_ev[2] = {};          // methylation calls of anchored reads (run_anchored_mod): their own bracket, inside the anchored pass
@@ -1082,6 +1089,169 @@ static int run_tract_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
     return STRQ_OK;
 }
 
+// Methylation calls for the CpG groups of the flanks of one sub-batch (strq_set_flank_mod; strique_amd/flank_mod.py states the rule):
+// every read whose gate passed, that could be conditioned and whose target has a modification model and the flank models.  Per flank
+// with begin < end -- the prefix on the raw samples [whole prefix begin, prefix_end), the suffix on [suffix_begin, whole suffix end) --
+// the stretch is normalised like the modification pass's (mod_compact_kernel without a path), decoded with the flank's profile model
+// (back-pointers, traceback), flank_mod_bounds_kernel turns the path into the groups' bounds and their score tasks, and the passage
+// scorer of the per-unit scores scores them, one launch per mode.  Runs behind the rows on the context's stream, in pieces of at most
+// STRQ_FLANK_MOD_WS_BYTES of back-pointers (default: the unit pass's 8 GiB); one read-back and one wait per piece.  The geometry, the
+// conditioning constants and so the lengths are on the host already (the slot's pinned block), so the tasks are written there.
+static int run_flank_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
+{
+    Batch& B = d->batch;
+    hipStream_t st = c->stream;
+    const int64_t r0 = sl.r0; const int nr = sl.nr;
+    if (nr <= 0 || sl.scan) return STRQ_OK;
+    const DetectState::Slot::Pinned h = sl.host();
+    const int esz = B.dtype == 0 ? 2 : 8;
+    const int64_t s0 = B.off[r0];
+    size_t budget = (size_t)8 << 30;
+    if (const char* e = strq::opt("STRQ_FLANK_MOD_WS_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
+    // test hook: the observations per flank base beyond which a stretch is not decoded (the rule's 64), so that the too_long branch can be reached
+    int64_t max_per_base = 64;
+    if (const char* e = strq::opt("STRQ_FLANK_MOD_MAX_STRETCH")) { const long long v = atoll(e); if (v > 0) max_per_base = (int64_t)v; }
+    struct F { int i, which; int64_t begin, T; size_t bytes, first_rec; };
+    std::vector<F> fl;
+    const double nan = std::nan("");
+    for (int i = 0; i < nr; ++i) {
+        const Target& t = target_of(d, r0 + i);
+        const ReadGeom& g = h.geom[i]; const ReadCond& rc = h.rc[i];
+        if (!t.has_fmod() || !g.gate || rc.status != COND_OK) continue;
+        std::vector<strq_flank_mod_group>& recs = B.fmod[(size_t)(r0 + i)];
+        B.fmod_called[(size_t)(r0 + i)] = 1; recs.clear();
+        for (int which = 0; which < 2; ++which) {
+            const Target::FlankMod& fm = t.fmod[which];
+            const int64_t begin = which == 0 ? g.prefix_begin_whole : g.suffix_begin, end = which == 0 ? g.prefix_end : g.suffix_end_whole;
+            if (!(begin >= 0 && begin < end && end <= (int64_t)rc.n) || fm.range.empty()) continue;
+            const int64_t T = end - begin;
+            const bool too_long = T > max_per_base * fm.len;          // a flank alignment that spread over a wrong place must not size the back-pointers
+            const size_t first_rec = recs.size();
+            for (size_t k = 0; k < fm.range.size(); ++k) {
+                strq_flank_mod_group o = strq_flank_mod_group();
+                o.flank = fm.info[3 * k]; o.pos = fm.info[3 * k + 1]; o.n_sites = fm.info[3 * k + 2]; o.n_columns = fm.range[k].c1 - fm.range[k].c0 + 1;
+                o.status = too_long ? FMOD_TOO_LONG : FMOD_NO_PATH; o.begin = o.end = -1; o.v_base = o.v_mod = nan;
+                recs.push_back(o);
+            }
+            if (!too_long) fl.push_back({i, which, begin, T, (size_t)(T + 1) * (size_t)c->models[fm.model_id]->h.n_states * 2, first_rec});
+        }
+    }
+    if (fl.empty()) return STRQ_OK;
+    if (const int rc = pass_start(c, pass_ev(d))) return rc;
+    for (size_t c0 = 0; c0 < fl.size();) {
+        size_t c1 = c0, bytes = 0;
+        while (c1 < fl.size() && (c1 == c0 || bytes + ((fl[c1].bytes + 15) & ~(size_t)15) <= budget)) bytes += (fl[c1++].bytes + 15) & ~(size_t)15;
+        const int m = (int)(c1 - c0);
+        std::vector<GroupItem> items((size_t)m);
+        size_t sumT = 0, Gs = 0; int n_mode[3] = {0, 0, 0};
+        for (int k = 0; k < m; ++k) {
+            const F& f = fl[c0 + (size_t)k];
+            const Target::FlankMod& fm = target_of(d, r0 + f.i).fmod[f.which];
+            HostModel* hm = c->models[fm.model_id];
+            const int shape = vit_shape_for(hm->h, VIT_BACKPTR);
+            if (shape < 0) { c->err = "flank-mod: the flank profile model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
+            items[(size_t)k] = {0, shape, hm->h.n_cells};
+            sumT += (size_t)f.T; Gs += fm.range.size();
+            for (int sid : fm.site) {
+                HostModel* sm = c->models[sid];
+                if (!sm->llr_dev || sm->llr_mode < 0 || sm->llr_mode > 2) { c->err = "flank-mod: site model without an edge image (strq_target_set_flank_mod builds them)"; return STRQ_ERR_DEVICE; }
+                ++n_mode[sm->llr_mode];
+            }
+        }
+        const Grouping G = group_items(items);
+        Carve lay;
+        const size_t o_mt = lay.add<ModTask>((size_t)m), o_len = lay.add<int64_t>((size_t)m), o_vt = lay.add<VitTask>((size_t)m), o_vr = lay.add<VitResult>((size_t)m),
+                     o_pp = lay.add<int32_t*>((size_t)m), o_bt = lay.add<FlankBoundTask>((size_t)m), o_order = lay.add<int>((size_t)m + 16),
+                     o_gr = lay.add<FlankGroupRange>(Gs), o_ss = lay.add<FlankScoreSlot>(Gs), o_gb = lay.add<FlankGroupBounds>(Gs), o_rd = lay.add<LlrRead>(Gs),
+                     o_w = lay.add<int32_t>(Gs), o_sc = lay.add<double>(2 * Gs), o_iota = lay.add<int64_t>(Gs + 1), o_x = lay.add<double>(sumT), o_path = lay.add<int32_t>(sumT);
+        STRQ_HIP(c, d->fmod_ws.reserve(lay.total() + 64));
+        STRQ_HIP(c, d->fmod_bp.reserve(bytes + 64));
+        void* ws = d->fmod_ws.p;
+        ModTask* d_mt = Carve::at<ModTask>(ws, o_mt); int64_t* d_len = Carve::at<int64_t>(ws, o_len); VitTask* d_vt = Carve::at<VitTask>(ws, o_vt);
+        VitResult* d_vr = Carve::at<VitResult>(ws, o_vr); int32_t** d_pp = Carve::at<int32_t*>(ws, o_pp); FlankBoundTask* d_bt = Carve::at<FlankBoundTask>(ws, o_bt);
+        int* d_order = Carve::at<int>(ws, o_order); FlankGroupRange* d_gr = Carve::at<FlankGroupRange>(ws, o_gr); FlankScoreSlot* d_ss = Carve::at<FlankScoreSlot>(ws, o_ss);
+        FlankGroupBounds* d_gb = Carve::at<FlankGroupBounds>(ws, o_gb); LlrRead* d_rd = Carve::at<LlrRead>(ws, o_rd); int32_t* d_w = Carve::at<int32_t>(ws, o_w);
+        double* d_sc = Carve::at<double>(ws, o_sc); int64_t* d_iota = Carve::at<int64_t>(ws, o_iota); double* d_x = Carve::at<double>(ws, o_x); int32_t* d_path = Carve::at<int32_t>(ws, o_path);
+        std::vector<ModTask> mt((size_t)m); std::vector<VitTask> vt((size_t)m); std::vector<int32_t*> pp((size_t)m); std::vector<FlankBoundTask> bt((size_t)m);
+        std::vector<FlankGroupRange> gr(Gs); std::vector<FlankScoreSlot> ss(Gs); std::vector<int64_t> iota(Gs + 1); std::vector<size_t> g_at((size_t)m);
+        for (size_t k = 0; k <= Gs; ++k) iota[k] = (int64_t)k;
+        int next_slot[3] = {0, n_mode[0], n_mode[0] + n_mode[1]};
+        size_t xo = 0, go = 0, bo = 0;
+        for (int k = 0; k < m; ++k) {
+            const F& f = fl[c0 + (size_t)k];
+            const Target& t = target_of(d, r0 + f.i); const Target::FlankMod& fm = t.fmod[f.which];
+            const ReadCond& rc = h.rc[f.i];
+            HostModel* hm = c->models[fm.model_id];
+            const int at = G.pos[(size_t)k];
+            ModTask& mk = mt[(size_t)k]; std::memset(&mk, 0, sizeof(mk));
+            mk.raw = d->batch.raw.as<char>() + (size_t)(s0 + rc.off + f.begin) * esz;
+            mk.out = d_x + xo; mk.T = f.T; mk.is_f64 = B.dtype;
+            mk.c1 = rc.r_c1; mk.h1 = rc.r_h1; mk.h2 = rc.h2; mk.c2 = rc.c2;
+            mk.clip_lo = d->ps.clip_lo; mk.clip_hi = d->ps.clip_hi; mk.mod_lo = t.mod_min; mk.mod_hi = t.mod_max;
+            VitTask& v = vt[(size_t)at]; v = VitTask();
+            v.model = hm->dev; v.sig = mk.out; v.T = f.T; v.src_kind = VIT_SRC_F64;
+            v.bp = reinterpret_cast<uint16_t*>(d->fmod_bp.as<char>() + bo); bo += (f.bytes + 15) & ~(size_t)15;
+            pp[(size_t)at] = d_path + xo;
+            FlankBoundTask& b = bt[(size_t)k]; std::memset(&b, 0, sizeof(b));
+            b.path = d_path + xo; b.vit_status = &d_vr[at].status; b.column_of = fm.col->as<int32_t>();
+            b.groups = d_gr + go; b.out = d_gb + go; b.T = f.T; b.n_emit = hm->silent_start; b.n_groups = (int32_t)fm.range.size();
+            b.score = d_ss + go; b.x = mk.out; b.reads = d_rd; b.wloc = d_w; b.scores = d_sc;
+            g_at[(size_t)k] = go;
+            for (size_t j = 0; j < fm.range.size(); ++j) {
+                HostModel* sm = c->models[fm.site[j]];
+                gr[go + j] = fm.range[j];
+                ss[go + j] = {sm->llr_dev, next_slot[sm->llr_mode]++, 0};
+            }
+            go += fm.range.size(); xo += (size_t)f.T;
+        }
+        if (bo > d->fmod_bp.cap) { c->err = "flank-mod: workspace"; return STRQ_ERR_NOMEM; }
+        STRQ_HIP(c, hipMemcpyAsync(d_mt, mt.data(), (size_t)m * sizeof(ModTask), hipMemcpyHostToDevice, st));
+        STRQ_HIP(c, hipMemcpyAsync(d_vt, vt.data(), (size_t)m * sizeof(VitTask), hipMemcpyHostToDevice, st));
+        STRQ_HIP(c, hipMemcpyAsync(d_pp, pp.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
+        STRQ_HIP(c, hipMemcpyAsync(d_bt, bt.data(), (size_t)m * sizeof(FlankBoundTask), hipMemcpyHostToDevice, st));
+        STRQ_HIP(c, hipMemcpyAsync(d_gr, gr.data(), Gs * sizeof(FlankGroupRange), hipMemcpyHostToDevice, st));
+        STRQ_HIP(c, hipMemcpyAsync(d_ss, ss.data(), Gs * sizeof(FlankScoreSlot), hipMemcpyHostToDevice, st));
+        STRQ_HIP(c, hipMemcpyAsync(d_iota, iota.data(), (Gs + 1) * 8, hipMemcpyHostToDevice, st));
+        STRQ_HIP(c, hipMemsetAsync(d_path, 0, sumT * 4, st));          // a traceback that stops early leaves valid states behind
+        if (launch_mod_compact(st, d_mt, m, d_len)) { c->err = "flank-mod: normalisation launch failed"; return STRQ_ERR_DEVICE; }
+        d->stat(PASS_FMOD, FMOD_LAUNCHES) += 1;
+        const GroupHook trace = [&](const VitGroup& g) -> int {
+            if (launch_vit_traceback(st, d_vt + g.first, d_vr + g.first, d_pp + g.first, g.count)) { c->err = "flank-mod: traceback launch failed"; return STRQ_ERR_DEVICE; }
+            d->stat(PASS_FMOD, FMOD_LAUNCHES) += 1;
+            return STRQ_OK;
+        };
+        if (const int grc = launch_groups(c, st, G.groups, {d_vt, d_vr, d_order, {VIT_BACKPTR}, "flank-mod: ", false, &d->stat(PASS_FMOD, FMOD_LAUNCHES), nullptr, trace})) return grc;
+        if (launch_flank_mod_bounds(st, d_bt, m)) { c->err = "flank-mod: bounds launch failed"; return STRQ_ERR_DEVICE; }
+        d->stat(PASS_FMOD, FMOD_LAUNCHES) += 1;
+        for (int mode = 0, at = 0; mode < 3; at += n_mode[mode++]) {
+            if (!n_mode[mode]) continue;
+            if (launch_llr_score(st, mode, d_rd + at, d_iota, n_mode[mode], n_mode[mode], c->n_cu)) { c->err = "flank-mod: score launch failed"; return STRQ_ERR_DEVICE; }
+            d->stat(PASS_FMOD, FMOD_LAUNCHES) += 1;
+        }
+        std::vector<FlankGroupBounds> gb(Gs); std::vector<double> sc(2 * Gs);
+        STRQ_HIP(c, hipMemcpyAsync(gb.data(), d_gb, Gs * sizeof(FlankGroupBounds), hipMemcpyDeviceToHost, st));
+        STRQ_HIP(c, hipMemcpyAsync(sc.data(), d_sc, 2 * Gs * 8, hipMemcpyDeviceToHost, st));
+        STRQ_HIP(c, hipStreamSynchronize(st));
+        for (int k = 0; k < m; ++k) {
+            const F& f = fl[c0 + (size_t)k];
+            const Target::FlankMod& fm = target_of(d, r0 + f.i).fmod[f.which];
+            std::vector<strq_flank_mod_group>& recs = B.fmod[(size_t)(r0 + f.i)];
+            for (size_t j = 0; j < fm.range.size(); ++j) {
+                const FlankGroupBounds& b = gb[g_at[(size_t)k] + j];
+                strq_flank_mod_group& o = recs[f.first_rec + j];
+                o.status = b.status;
+                if (b.status != FMOD_SCORED) continue;
+                const int slot = ss[g_at[(size_t)k] + j].slot;
+                o.begin = f.begin + b.u; o.end = f.begin + b.w; o.v_base = sc[2 * (size_t)slot]; o.v_mod = sc[2 * (size_t)slot + 1];
+                d->stat(PASS_FMOD, FMOD_GROUPS) += 1;
+            }
+        }
+        d->stat(PASS_FMOD, FMOD_FLANKS) += m;
+        c0 = c1;
+    }
+    return pass_stop(c, pass_ev(d), d->stats[PASS_FMOD]);
+}
+
 // Methylation calls of the anchored reads of one sub-batch (strq_set_anchored_mod), behind their records: a read of `R` is called
 // when its record has status 0 -- its stretch [begin, end) is then not empty.  queued: dual_decode and dual_patterns ran behind the
 // anchored decode on window-sized buffers (hub route); the patterns of the reads that turned out not to qualify are dropped and the
@@ -1395,6 +1565,7 @@ static int take_rows(strq_ctx* c, DetectState* d, DetectState::Slot& sl, bool un
         o.score_prefix = g.score_prefix; o.score_suffix = g.score_suffix;
         o.prefix_begin = g.prefix_begin; o.prefix_end = g.prefix_end; o.suffix_begin = g.suffix_begin; o.suffix_end = g.suffix_end;
         o.offset = g.prefix_end; o.ticks = std::max<int64_t>(g.suffix_begin - g.prefix_end, 0);
+        B.flank_ends[2 * (size_t)(r0 + i)] = g.prefix_begin_whole; B.flank_ends[2 * (size_t)(r0 + i) + 1] = g.suffix_end_whole;
         if (g.gate) c->counters[7] += (double)(g.suffix_end - g.prefix_begin);
         if (g.gate && v.status == 0) {
             o.count = (int32_t)v.counted + target_of(d, r0 + i).count_bias;
@@ -1429,6 +1600,7 @@ static int take_rows(strq_ctx* c, DetectState* d, DetectState::Slot& sl, bool un
         }
     }
     if (sl.ex.tracts) { const int trc = run_tract_pass(c, d, sl); if (trc) return trc; }
+    if (sl.ex.fmod) { const int frc = run_flank_mod_pass(c, d, sl); if (frc) return frc; }
     return sl.ex.anch ? run_anchored_pass(c, d, sl) : STRQ_OK;
 }
 
@@ -2070,6 +2242,7 @@ int run_range(strq_ctx* c, DetectState* d, int64_t first, int64_t last)
         }
     }
     if (d->extras.tracts) B.size_tracts();
+    if (d->extras.fmod) B.size_fmod();
     if (d->extras.renorm) {
         // nothing is launched for a call whose reads the pass could not fit
         if (!d->rn_have_grid) { c->err = "renorm: no tables (strq_target_set_renorm)"; return STRQ_ERR_ARG; }
@@ -2522,6 +2695,65 @@ int strq_last_tracts(strq_ctx* c, double* out4)
     return last_pass(c, PASS_TRACTS, out4);
 }
 
+int strq_target_set_flank_mod(strq_ctx* c, int32_t target_id, int32_t which, int32_t profile_model_id, int32_t flank_len,
+                              const int32_t* column_of, int32_t n_groups, const int32_t* groups)
+{
+    STRQ_ENTER(c);
+    DetectState* d = dstate(c);
+    auto model = [&](int32_t id) -> HostModel* { return id >= 0 && id < (int32_t)c->models.size() ? c->models[(size_t)id] : nullptr; };
+    HostModel* hm = model(profile_model_id);
+    if (target_id < 0 || target_id >= (int32_t)d->targets.size() || (which != 0 && which != 1) || !hm || flank_len < 1 || !column_of ||
+        n_groups < 0 || (n_groups > 0 && !groups)) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    if (n_groups > FMOD_MAX_GROUPS) { c->err = "flank-mod: at most " + std::to_string(FMOD_MAX_GROUPS) + " CpG groups per flank"; return STRQ_ERR_UNSUPPORTED; }
+    if (vit_shape_for(hm->h, VIT_BACKPTR) < 0) { c->err = "flank-mod: the flank profile model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
+    if (const int rc = drain(c, d)) return rc;          // a sub-batch in flight is taken with the models it ran with
+    Target::FlankMod fm;
+    fm.model_id = profile_model_id; fm.len = flank_len;
+    for (int32_t k = 0; k < n_groups; ++k) {
+        const int32_t* g = groups + 6 * k;
+        HostModel* sm = model(g[2]);
+        if (!sm || g[0] < 0 || g[1] < g[0] || (g[3] != 0 && g[3] != 1)) { c->err = "bad argument (a group's columns, site model or flank)"; return STRQ_ERR_ARG; }
+        if (const int rc = llr_model(c, sm)) return rc;
+        fm.range.push_back({g[0], g[1]}); fm.site.push_back(g[2]);
+        fm.info.push_back(g[3]); fm.info.push_back(g[4]); fm.info.push_back(g[5]);
+    }
+    fm.col = std::make_shared<DevBuf>();
+    STRQ_HIP(c, fm.col->reserve((size_t)hm->silent_start * 4 + 64));
+    STRQ_HIP(c, hipMemcpy(fm.col->p, column_of, (size_t)hm->silent_start * 4, hipMemcpyHostToDevice));
+    d->targets[(size_t)target_id].fmod[which] = fm;
+    return STRQ_OK;
+}
+
+int strq_set_flank_mod(strq_ctx* c, int32_t on)
+{
+    STRQ_ENTER(c);
+    return set_extra(c, on, PASS_FMOD);
+}
+
+int strq_batch_fetch_flank_mod(strq_ctx* c, int32_t* called, int64_t* off, strq_flank_mod_group* pool, int64_t pool_cap)
+{
+    STRQ_ENTER(c);
+    if (!off) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    DetectState* d = dstate(c);
+    if (const int rc = fetch_begin(c, d, PASS_FMOD)) return rc;
+    const Batch& B = d->batch;
+    const int64_t done = pack_ragged(B.n_reads, off, pool != nullptr, pool_cap, [&](int64_t i) {
+        if (called) called[i] = B.fmod_called[(size_t)i];
+        return (int64_t)B.fmod[(size_t)i].size();
+    }, [&](int64_t i, int64_t pos) {
+        const std::vector<strq_flank_mod_group>& v = B.fmod[(size_t)i];
+        if (!v.empty()) std::memcpy(pool + pos, v.data(), v.size() * sizeof(strq_flank_mod_group));
+    });
+    if (done < B.n_reads) { c->err = "flank-mod pool too small"; return STRQ_ERR_ARG; }
+    return STRQ_OK;
+}
+
+int strq_last_flank_mod(strq_ctx* c, double* out4)
+{
+    STRQ_ENTER(c);
+    return last_pass(c, PASS_FMOD, out4);
+}
+
 int strq_set_anchored_mod(strq_ctx* c, int32_t on)
 {
     STRQ_ENTER(c);
@@ -2773,6 +3005,21 @@ int strq_batch_fetch(strq_ctx* c, strq_result* out)
     return STRQ_OK;
 }
 
+// the stretches of the whole configured flanks: the row's prefix_end / suffix_begin and the ends before the trim
+int strq_batch_fetch_flank_ranges(strq_ctx* c, int64_t* out4, int64_t n)
+{
+    STRQ_ENTER(c);
+    DetectState* d = dstate(c);
+    if (const int rc = drain(c, d)) return rc;
+    const Batch& B = d->batch;
+    if (n != B.n_reads || (n > 0 && !out4) || B.flank_ends.size() != 2 * (size_t)n) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    for (int64_t r = 0; r < n; ++r) {
+        const strq_result& o = B.results[(size_t)r];
+        out4[4 * r] = B.flank_ends[2 * (size_t)r]; out4[4 * r + 1] = o.prefix_end; out4[4 * r + 2] = o.suffix_begin; out4[4 * r + 3] = B.flank_ends[2 * (size_t)r + 1];
+    }
+    return STRQ_OK;
+}
+
 int strq_batch_fetch_range(strq_ctx* c, int64_t first, int64_t last, strq_result* out)
 {
     STRQ_ENTER(c);
@@ -2987,6 +3234,48 @@ int strq_debug_variant_bounds(strq_ctx* c, int32_t model_id, int32_t n_alt, int3
             if (w[(size_t)r * (size_t)stride + (size_t)k] != 0x7F7F7F7F || branch[(size_t)r * (size_t)stride + (size_t)k] != 0x7F7F7F7F) same = 0;
         untouched[r] = same;
     }
+    return STRQ_OK;
+}
+
+// one launch of flank_mod_bounds_kernel over the caller's paths: one task per stretch, all of one model's column table
+int strq_debug_flank_mod_bounds(strq_ctx* c, int32_t n_flanks, const int64_t* off, const int32_t* path, const int32_t* status,
+                                int32_t n_emit, const int32_t* column_of, const int64_t* g_off, const int32_t* groups, int32_t* out)
+{
+    STRQ_ENTER(c);
+    if (n_flanks < 1 || !off || off[0] != 0 || n_emit < 1 || !column_of || !g_off || g_off[0] != 0 || !out) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    for (int32_t f = 0; f < n_flanks; ++f) {
+        const int64_t T = off[f + 1] - off[f], G = g_off[f + 1] - g_off[f];
+        if (T < 0 || T >= ((int64_t)1 << 30) || (T > 0 && !path)) { c->err = "bad argument (a stretch's length)"; return STRQ_ERR_ARG; }
+        if (G < 0 || G > FMOD_MAX_GROUPS || (G > 0 && !groups)) { c->err = "bad argument (at most " + std::to_string(FMOD_MAX_GROUPS) + " groups per flank)"; return STRQ_ERR_ARG; }
+        for (int64_t t = off[f]; t < off[f + 1]; ++t) if (path[t] < 0 || path[t] >= n_emit) { c->err = "bad argument (a path state that does not emit)"; return STRQ_ERR_ARG; }
+    }
+    const int64_t nT = off[n_flanks], nG = g_off[n_flanks];
+    if (!nG) return STRQ_OK;
+    hipStream_t st = c->stream;
+    Carve lay;
+    const size_t o_path = lay.add<int32_t>((size_t)nT), o_col = lay.add<int32_t>((size_t)n_emit), o_st = lay.add<int32_t>((size_t)n_flanks),
+                 o_g = lay.add<FlankGroupRange>((size_t)nG), o_out = lay.add<FlankGroupBounds>((size_t)nG), o_task = lay.add<FlankBoundTask>((size_t)n_flanks);
+    DevBuf ws;
+    STRQ_HIP(c, ws.reserve(lay.total() + 64));
+    int32_t* d_path = Carve::at<int32_t>(ws.p, o_path); int32_t* d_col = Carve::at<int32_t>(ws.p, o_col); int32_t* d_st = Carve::at<int32_t>(ws.p, o_st);
+    FlankGroupRange* d_g = Carve::at<FlankGroupRange>(ws.p, o_g); FlankGroupBounds* d_out = Carve::at<FlankGroupBounds>(ws.p, o_out);
+    FlankBoundTask* d_task = Carve::at<FlankBoundTask>(ws.p, o_task);
+    std::vector<FlankBoundTask> tasks((size_t)n_flanks);
+    for (int32_t f = 0; f < n_flanks; ++f) {
+        FlankBoundTask& t = tasks[(size_t)f];
+        t.path = d_path + off[f]; t.vit_status = status ? d_st + f : nullptr; t.column_of = d_col;
+        t.groups = d_g + g_off[f]; t.out = d_out + g_off[f];
+        t.T = off[f + 1] - off[f]; t.n_emit = n_emit; t.n_groups = (int32_t)(g_off[f + 1] - g_off[f]);
+    }
+    if (nT) STRQ_HIP(c, hipMemcpyAsync(d_path, path, (size_t)nT * 4, hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, hipMemcpyAsync(d_col, column_of, (size_t)n_emit * 4, hipMemcpyHostToDevice, st));
+    if (status) STRQ_HIP(c, hipMemcpyAsync(d_st, status, (size_t)n_flanks * 4, hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, hipMemcpyAsync(d_g, groups, (size_t)nG * sizeof(FlankGroupRange), hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, hipMemcpyAsync(d_task, tasks.data(), (size_t)n_flanks * sizeof(FlankBoundTask), hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, hipMemsetAsync(d_out, 0x7F, (size_t)nG * sizeof(FlankGroupBounds), st));
+    if (launch_flank_mod_bounds(st, d_task, n_flanks)) { c->err = "flank-mod: bounds launch failed"; return STRQ_ERR_DEVICE; }
+    STRQ_HIP(c, hipMemcpyAsync(out, d_out, (size_t)nG * sizeof(FlankGroupBounds), hipMemcpyDeviceToHost, st));
+    STRQ_HIP(c, hipStreamSynchronize(st));
     return STRQ_OK;
 }
 

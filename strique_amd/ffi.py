@@ -638,6 +638,33 @@ class Context(object):
         """The tract pass of the last run call (strq_last_tracts): {'ms', 'windows' (decoded), 'launches', 'failed' (status 2 or 3)}."""
         return self._last("tracts", ("ms", "windows", "launches", "failed"))
 
+    def target_set_flank_mod(self, target_id, which, profile_model_id, flank_len, column_of, groups):
+        """strq_target_set_flank_mod: the models of flank `which` (0 prefix, 1 suffix, as the strand of the target reads it) --
+        column_of one entry per emitting state of the profile model, groups rows of (c0, c1, site model id, flank as configured, pos,
+        n_sites)."""
+        col = _c(column_of, np.int32)
+        g = _c(groups if len(groups) else np.zeros((0, 6)), np.int32).reshape(-1, 6)
+        self._check(self._lib.strq_target_set_flank_mod(self._h, ctypes.c_int32(target_id), ctypes.c_int32(which), ctypes.c_int32(profile_model_id),
+                                                        ctypes.c_int32(flank_len), _ptr(col), ctypes.c_int32(len(g)), _ptr(g) if len(g) else None))
+
+    def set_flank_mod(self, on):
+        """strq_set_flank_mod: later run calls also call the CpG groups of the flanks (batch_fetch_flank_mod)."""
+        self._check(self._lib.strq_set_flank_mod(self._h, ctypes.c_int32(1 if on else 0)))
+
+    def batch_fetch_flank_mod(self):
+        """Flank methylation calls of the last batch (strq_batch_fetch_flank_mod): per read None (it did not qualify) or a structured
+        array of FLANK_MOD_DTYPE, one element per group of a flank whose stretch exists, prefix groups first."""
+        n = getattr(self, '_n_batch', 0)
+        called = np.zeros(max(1, n), np.int32); off = np.zeros(n + 1, np.int64)
+        self._check(self._lib.strq_batch_fetch_flank_mod(self._h, _ptr(called), _ptr(off), None, ctypes.c_int64(0)))
+        pool = np.zeros(max(1, int(off[-1])), FLANK_MOD_DTYPE)
+        self._check(self._lib.strq_batch_fetch_flank_mod(self._h, _ptr(called), _ptr(off), _ptr(pool), ctypes.c_int64(len(pool))))
+        return [pool[int(off[i]):int(off[i + 1])].copy() if called[i] else None for i in range(n)]
+
+    def last_flank_mod(self):
+        """The flank-mod pass of the last run call (strq_last_flank_mod): {'ms', 'flanks' (decoded), 'groups' (scored), 'launches'}."""
+        return self._last("flank_mod", ("ms", "flanks", "groups", "launches"))
+
     def set_anchored_mod(self, on):
         """strq_set_anchored_mod: later run calls with anchored counting on also call the methylation pattern of every read of
         kind 2 / 3 whose record was decoded and whose target has a modification model (batch_fetch_anchored_mod)."""
@@ -736,6 +763,13 @@ class Context(object):
     def batch_fetch(self):
         out = np.zeros(self._n_batch, dtype=RESULT_DTYPE)
         self._check(self._lib.strq_batch_fetch(self._h, _ptr(out)))
+        return out
+
+    def batch_fetch_flank_ranges(self):
+        """strq_batch_fetch_flank_ranges: (n, 4) int64 -- per read of the last batch the raw samples [begin, end) of the whole prefix
+        flank and of the whole suffix flank: the ends of the flank alignments before the trim."""
+        out = np.zeros((self._n_batch, 4), np.int64)
+        self._check(self._lib.strq_batch_fetch_flank_ranges(self._h, _ptr(out), ctypes.c_int64(self._n_batch)))
         return out
 
     def batch_fetch_range(self, first, last):
@@ -916,6 +950,26 @@ class Context(object):
                         "branch": br[i, :k].copy(), "untouched": bool(same[i])})
         return out
 
+    def debug_flank_mod_bounds(self, paths, column_of, groups, status=None):
+        """strq_debug_flank_mod_bounds: one launch of the bounds kernel of the flank methylation calls.  paths: one int32 state path
+        per flank stretch, all of one flank profile model; column_of: the profile column per emitting state of that model (-1 for
+        none); groups: per stretch a list of (c0, c1) column ranges; status: the decode status per stretch (default: a path).
+        Per stretch an (n_groups, 3) int32 array of (status, u, w) as strique_amd.flank_mod.bounds gives them."""
+        nf = len(paths)
+        if nf != len(groups):
+            raise ValueError("one list of groups per stretch")
+        p, off = _offsets(paths, np.int32)
+        col = _c(column_of, np.int32)
+        g_off = np.zeros(nf + 1, np.int64); g_off[1:] = np.cumsum([len(g) for g in groups])
+        flat = _c([c for g in groups for c in g] or [(0, 0)], np.int32).reshape(-1, 2)
+        st = None if status is None else _c(status, np.int32)
+        if st is not None and len(st) != nf:
+            raise ValueError("one decode status per stretch")
+        out = np.zeros((max(1, int(g_off[-1])), 3), np.int32)
+        self._check(self._lib.strq_debug_flank_mod_bounds(self._h, ctypes.c_int32(nf), _ptr(off), _ptr(p), _ptr(st), ctypes.c_int32(len(col)), _ptr(col),
+                                                          _ptr(g_off), _ptr(flat), _ptr(out)))
+        return [out[int(g_off[f]):int(g_off[f + 1])].copy() for f in range(nf)]
+
     def debug_filtered(self, read, n, dtype=np.int16):
         """strq_debug_filtered: the first `n` median-filtered samples of read `read` of the last sub-batch; `dtype` is the
         element type of the batch (int16 or float64)."""
@@ -934,6 +988,8 @@ RESULT_DTYPE = np.dtype([("count", np.int32), ("status", np.int32), ("score_pref
 RENORM_FIT_DTYPE = np.dtype([("a", np.int32), ("b", np.int32), ("w", np.int32), ("fitted", np.int32), ("score", np.int64)], align=True)
 RENORM_DTYPE = np.dtype([("applied", np.int32), ("pad_", np.int32), ("fit", RENORM_FIT_DTYPE, (3,))], align=True)
 
+FLANK_MOD_DTYPE = np.dtype([("flank", np.int32), ("pos", np.int32), ("n_sites", np.int32), ("n_columns", np.int32), ("status", np.int32), ("pad_", np.int32),
+                            ("begin", np.int64), ("end", np.int64), ("v_base", np.float64), ("v_mod", np.float64)], align=True)
 TRACTS_DTYPE = np.dtype([("status", np.int32), ("n_tracts", np.int32), ("count", np.int32, (3,)), ("pad_", np.int32), ("log_p", np.float64)], align=True)
 ANCHORED_DTYPE = np.dtype([("kind", np.int32), ("status", np.int32), ("count", np.int32), ("pad_", np.int32), ("log_p", np.float64),
                            ("begin", np.int64), ("end", np.int64), ("free_samples", np.int64)], align=True)

@@ -392,6 +392,76 @@ class RepeatModModel(object):
         self.baked = bake(g, count_states=(), tag_substring='mod', tag2_states=(s0, e0))
 
 
+class FlankProfileModel(object):
+    """One flank profile on its own, for the segmentation of a flank stretch (strique_amd/flank_mod.py states the rule):
+    start -> (e1_ratio) s1 | s2 -> profile of `flank` with the seq_std_* parameters -> end, i.e. the flanked model's prefix
+    section alone.  `column_of[state]` is the profile column of a baked match or insert state, -1 for every other state."""
+
+    def __init__(self, flank, pm, config=None):
+        tp = _layer({'skip': 1 - 1e-4, 'seq_std_scale': 1.0, 'seq_std_offset': 0.0, 'e1_ratio': 0.1},
+                    config if isinstance(config, dict) else None)
+        g = Graph()
+        prof = add_profile(g, flank, pm, tp, 'flank', std_scale=tp['seq_std_scale'], std_offset=tp['seq_std_offset'])
+        g.add_transition(g.start, prof.s1, tp['e1_ratio'])
+        g.add_transition(g.start, prof.s2, 1 - tp['e1_ratio'])
+        g.add_transition(prof.e1, g.end, 1)
+        g.add_transition(prof.e2, g.end, 1)
+        # two slots where the columns fit the lanes (match-type, insert-type; lane = column); a longer flank takes whatever
+        # kernel shape holds its states.  The same states as a chain of positions
+        pos = {}
+        for p_, st in enumerate(prof.match): pos[st] = (0, p_)
+        for p_, st in enumerate(prof.insert): pos[st] = (1, p_)
+        g.positions = pos
+        if len(prof.match) <= 64:
+            g.layout = dict(pos)          # (slot, lane) = (kind, column)
+        self.graph = g
+        self.n_columns = len(prof.match)
+        self.baked = bake(g)
+        new = {int(old): k for k, old in enumerate(self.baked.orig_index)}
+        self.column_of = np.full(self.baked.n_states, -1, np.int32)
+        for p_, (m_, i_) in enumerate(zip(prof.match, prof.insert)):
+            self.column_of[new[m_]] = p_
+            self.column_of[new[i_]] = p_
+
+
+class SiteModModel(object):
+    """RepeatModModel over a linear sequence -- the bases the columns of one CpG group of a flank spell -- passed once: the same
+    topology, tags, std scaling and layout hint, but no extend_repeat, no e0 -> s0 edge, and e0 -> end with probability 1."""
+
+    def __init__(self, sequence, pm_base, pm_mod, config=None):
+        tp = _layer({'rep_std_scale': 1.5, 'rep_std_offset': 0.0},
+                    config if isinstance(config, dict) else None)
+        self.model_min = min(pm_base.model_min, pm_mod.model_min)
+        self.model_max = max(pm_base.model_max, pm_mod.model_max)
+        g = Graph()
+        s0 = g.add_state('s0', UNIFORM, (self.model_min, self.model_max))
+        e0 = g.add_state('e0', UNIFORM, (self.model_min, self.model_max))
+        base = add_profile(g, sequence, pm_base, tp, 'base', no_silent=True, std_scale=tp['rep_std_scale'],
+                           std_offset=tp['rep_std_offset'])
+        mod = add_profile(g, sequence, pm_mod, tp, 'mod', no_silent=True,
+                          std_scale=tp['rep_std_scale'] * pm_mod.scale2stdv(pm_base),
+                          std_offset=tp['rep_std_offset'])
+        g.add_transition(g.start, s0, 1)
+        for p in (base, mod):
+            g.add_transition(s0, p.s1, 0.25)
+            g.add_transition(s0, p.s2, 0.25)
+        for p in (base, mod):
+            g.add_transition(p.e1, e0, 1)
+            g.add_transition(p.e2, e0, 1)
+        g.add_transition(e0, g.end, 1)
+        lay = {}
+        lane = 0
+        for group in (base.match, base.insert, mod.match, mod.insert, [s0, e0]):
+            for st in group:
+                lay[st] = (0, lane); lane += 1
+        if lane <= 64:
+            g.layout = lay
+        self.graph = g
+        self.hub_states = (s0, e0)
+        self.n_columns = len(base.match)
+        self.baked = bake(g, count_states=(), tag_substring='mod', tag2_states=(s0, e0))
+
+
 VARIANT_TAGS = (1, 3, 4)        # state tag of alt branch 1 / 2 / 3 (0 base, 2 hub: as the dual model of RepeatModModel)
 
 
