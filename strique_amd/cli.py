@@ -287,20 +287,10 @@ def count(argv):
                                                                                                 " ".join(renorm_mod.HEADER) + " ('-' where a signal was not fitted)")
     parser.add_argument("--strict", action="store_true", help="Exit with status 2 when any read could not be processed (the reference only logs such reads and exits 0)")
     args = parser.parse_args(argv)
-    if args.scan and args.confidence:
-        parser.error("--confidence cannot be combined with --scan: the forward pass runs on reads whose target and strand an alignment gives")
-    if args.mod_llr and not args.mod_model:
-        parser.error("--mod-llr needs --mod_model: the ratios belong to the calls of the modification model")
-    if args.scan and args.mod_llr:
-        parser.error("--mod-llr cannot be combined with --scan: the scoring pass runs on reads whose target and strand an alignment gives")
     if args.variants and not args.alt_units:
         parser.error("--variants needs --alt-units FILE: the units to tell from the repeat unit")
-    if args.variants and args.scan:
-        parser.error("--variants cannot be combined with --scan: the variant pass runs on reads whose target and strand an alignment gives")
     if bool(args.tracts) != bool(args.tract_units):
         parser.error("--tract-units FILE and --tracts FILE need each other: the definitions, and where the counts go")
-    if args.tracts and args.scan:
-        parser.error("--tracts cannot be combined with --scan: the tract pass runs on reads whose target and strand an alignment gives")
     if args.scan and args.algn:
         parser.error("--scan takes the target and strand of a read from its signal: it cannot be combined with --algn")
     if not args.scan and (args.scan_scores or args.scan_min_score is not None):
@@ -310,8 +300,6 @@ def count(argv):
                      "(a first run with a high X and --scan-scores FILE shows what to choose from)")
     if args.scan_min_score is not None and not args.scan_min_score > 0:
         parser.error("--scan-min-score must be above 0")
-    if args.anchored and args.scan:
-        parser.error("--anchored cannot be combined with --scan: a scan takes a read for a target when it finds both flanks")
     if args.anchored and args.anchored_min_score is None:
         parser.error("--anchored needs --anchored-min-score X: the scores of a flank that is there and of one that is not overlap on noisy reads, so there is no default")
     if args.anchored_min_score is not None and not args.anchored:
@@ -320,20 +308,17 @@ def count(argv):
         parser.error("--anchored-min-score must be above 0")
     if args.anchored_mod and not args.anchored:
         parser.error("--anchored-mod needs --anchored FILE --anchored-min-score X: the calls are made on the reads anchored counting finds")
-    if args.anchored_mod and not args.mod_model:
-        parser.error("--anchored-mod needs --mod_model: the calls are those of the modification model")
-    if args.anchored_mod and args.scan:
-        parser.error("--anchored-mod cannot be combined with --scan: a scan takes a read for a target when it finds both flanks")
-    if args.flank_mod and not args.mod_model:
-        parser.error("--flank-mod needs --mod_model: the calls compare the modification model's k-mer table with the base table")
-    if args.flank_mod and args.scan:
-        parser.error("--flank-mod cannot be combined with --scan: the flank pass runs on reads whose target and strand an alignment gives")
     if args.renorm is not None and not 0 < args.renorm < 1:
         parser.error("--renorm MIN_SHARE must be inside (0, 1)")
     if args.renorm_out and args.renorm is None:
         parser.error("--renorm-out needs --renorm MIN_SHARE")
-    if args.renorm is not None and args.scan:
-        parser.error("--renorm cannot be combined with --scan: the fit needs the target of a read, which a scan finds with the maps as they are")
+    # then what every output needs and excludes, in the order of OUTPUTS: said once, there
+    for o in OUTPUTS:
+        if getattr(args, _dest(o.flag)):
+            if o.needs_mod and not args.mod_model:
+                parser.error("%s needs --mod_model: %s" % (o.flag, o.needs_mod))
+            if o.no_scan and args.scan:
+                parser.error("%s cannot be combined with --scan: %s" % (o.flag, o.no_scan))
     log = Log(args.log_level)
     config = parse_config(args.repeat, args.config, log)
     alt_units = {}
@@ -414,8 +399,8 @@ def count(argv):
         readers = max(1, min(24, share))            # inflating is what the readers do: one per core they can get, 16 ... 24 measure the same end to end
     stats = {}
     fault = 0
-    paths = dict(units=args.units, confidence=args.confidence, mod_llr=args.mod_llr, scores=args.scan_scores, anchored=args.anchored, variants=args.variants,
-                 renorm=args.renorm_out, anchored_mod=args.anchored_mod, tracts=args.tracts, flank_mod=args.flank_mod)
+    paths = {o.name: getattr(args, o.dest or _dest(o.flag)) for o in OUTPUTS}
+    asked = {o.name: o.arg(args, alt_units) if o.arg else bool(paths[o.name]) for o in OUTPUTS if o.ask}
     with contextlib.ExitStack() as stack:
         # rank 0 writes: as the batches are done in a single process (run_count), after the gather otherwise
         files = {name: stack.enter_context(open(path, 'w')) if (path and rank == 0) else None for name, path in paths.items()}
@@ -423,13 +408,7 @@ def count(argv):
         now = {name: f if world == 1 else None for name, f in files.items()}
         try:
             rows = run_count(stream, loci, f5.get_raw, counter, log, args.batch, rank, world, out if world == 1 else None, readers=readers, stats=stats,
-                             units=bool(args.units), units_out=now['units'], scan=scan, scores_out=now['scores'],
-                             confidence=bool(args.confidence), conf_out=now['confidence'], mod_llr=bool(args.mod_llr), llr_out=now['mod_llr'],
-                             anchored=args.anchored_min_score, anchored_out=now['anchored'],
-                             anchored_mod=bool(args.anchored_mod), anchored_mod_out=now['anchored_mod'],
-                             variants=alt_units if args.variants else None, variants_out=now['variants'],
-                             renorm=args.renorm, renorm_out=now['renorm'], tracts=bool(args.tracts), tracts_out=now['tracts'],
-                             flank_mod=bool(args.flank_mod), flank_mod_out=now['flank_mod'])
+                             scan=scan, **asked, **{o.file: now[o.name] for o in OUTPUTS})
         except DeviceFault:
             if world == 1:
                 raise SystemExit(3)
@@ -443,9 +422,7 @@ def count(argv):
                     log("Main: a rank reported a device error; no output written.", 'error')
                 dist.destroy_process_group()
                 raise SystemExit(3)
-            merged = gather_rows(rows, stats["items"], sdist, units=bool(args.units), scan=scan, confidence=bool(args.confidence), mod_llr=bool(args.mod_llr),
-                                 anchored=bool(args.anchored), variants=bool(args.variants), renorm=args.renorm is not None, anchored_mod=bool(args.anchored_mod),
-                                 tracts=bool(args.tracts), flank_mod=bool(args.flank_mod))
+            merged = gather_rows(rows, stats["items"], sdist, scan=scan, **asked)
             if rank == 0:
                 write_rows(out, merged.rows)
                 for o in OUTPUTS:
@@ -652,30 +629,84 @@ def _unfloats(text):
 # run_count / counter.detect_batch and the field of `Merged`; header(scan): the header of its file; format(qname, target, strand, row,
 # value): one row of its file (row: the count row's tuple, None for a scan read without a winner -- only an output with rowless=True
 # writes one then); pack(value) / unpack(text): its field of the gather blob (absent values are '-' and never reach them); stat: the
-# key of run_count's `stats` that collects its rows.
-Output = namedtuple('Output', ['name', 'header', 'format', 'pack', 'unpack', 'stat', 'rowless'])
+# key of run_count's `stats` that collects its rows; file: run_count's keyword of its file.
+# ask: how run_count asks the counter for it -- 'keyword': detect_batch(..., name=True); 'switch': counter.set_<name>(True) for the run,
+# set_<name>(False) behind it, and detect_batch(..., records=True); with `level` run_count's own value travels instead of True (as a
+# keyword with records=True, as a switch with None behind the run); None: the scan gives it, not the counter.
+# value(det, target, counter, asked): its value from a Detected record (asked: run_count's {name: value}).
+# refuse(asked, scan): the text of run_count's ValueError for what was asked, or None.
+# For count(): flag, its argument -- what the errors name, and the attribute that tells whether it was asked for; dest: the attribute
+# of its file where that is another one; arg(args, alt_units): what run_count is given for it (default: whether the file was named);
+# needs_mod / no_scan: why "<flag> needs --mod_model" / "<flag> cannot be combined with --scan" (None: it does not / it can).
+Output = namedtuple('Output', ['name', 'header', 'format', 'pack', 'unpack', 'stat', 'rowless', 'file', 'ask', 'value', 'flag',
+                               'level', 'refuse', 'dest', 'arg', 'needs_mod', 'no_scan'], defaults=(False, None, None, None, None, None))
+_ALIGNED = "the %s pass runs on reads whose target and strand an alignment gives"
+_BOTH_FLANKS = "a scan takes a read for a target when it finds both flanks"
+
+
+def _asked(o, value):
+    """Whether run_count's value for output `o` asks for it: by truth, but for an output whose value says more than yes (the ones with
+    `arg`: a threshold, the alt units) -- such a one is on unless None, as an empty {target: alt units} is."""
+    return value is not None if o.arg else bool(value)
+
+
+def _dest(flag):
+    return flag[2:].replace('-', '_')
+
+
+def _not_with_scan(text):
+    return lambda asked, scan: text if scan else None
+
+
 OUTPUTS = (
     Output('units', lambda scan: UNITS_HEADER, lambda q, t, s, row, v: format_units(q, t, s, row[0], v),
-           lambda v: ','.join(str(int(x)) for x in v), lambda text: [int(x) for x in text.split(',')], 'unit_rows', False),
+           lambda v: ','.join(str(int(x)) for x in v), lambda text: [int(x) for x in text.split(',')], 'unit_rows', False,
+           file='units_out', ask='keyword', flag='--units', value=lambda d, t, c, a: d.units),
     Output('confidence', lambda scan: CONF_HEADER, lambda q, t, s, row, v: format_confidence(q, t, s, row[0], row[3], v),
-           _floats, _unfloats, 'conf_rows', False),
+           _floats, _unfloats, 'conf_rows', False,
+           file='conf_out', ask='keyword', flag='--confidence', value=lambda d, t, c, a: d.conf, no_scan=_ALIGNED % "forward"),
     Output('mod_llr', lambda scan: MODLLR_HEADER, lambda q, t, s, row, v: format_mod_llr(q, t, s, row[0], row[6], v),
-           _floats, _unfloats, 'llr_rows', False),
+           _floats, _unfloats, 'llr_rows', False,
+           file='llr_out', ask='keyword', flag='--mod-llr', value=lambda d, t, c, a: d.llr,
+           needs_mod="the ratios belong to the calls of the modification model", no_scan=_ALIGNED % "scoring"),
     Output('scores', lambda scan: scan_mod.scores_header(scan["candidates"]),
            lambda q, t, s, row, v: scan_mod.format_scores(q, None if row is None else (t, s), v),
-           lambda v: _floats(x for pair in v for x in pair), lambda text: list(zip(*[iter(_unfloats(text))] * 2)), 'score_rows', True),
+           lambda v: _floats(x for pair in v for x in pair), lambda text: list(zip(*[iter(_unfloats(text))] * 2)), 'score_rows', True,
+           file='scores_out', ask=None, flag='--scan-scores', value=None),
     Output('renorm', lambda scan: renorm_mod.HEADER, lambda q, t, s, row, v: renorm_mod.format_row(q, t, s, v),
-           lambda v: renorm_mod.pack(v), lambda text: renorm_mod.unpack(text), 'renorm_rows', False),
+           lambda v: renorm_mod.pack(v), lambda text: renorm_mod.unpack(text), 'renorm_rows', False,
+           file='renorm_out', ask='switch', level=True, flag='--renorm',
+           value=lambda d, t, c, a: d.renorm and renorm_mod.report(d.renorm, c.renorm_bin_width),
+           refuse=lambda asked, scan: ("renorm cannot be combined with a scan" if scan else
+                                       None if 0 < asked['renorm'] < 1 else "the renorm share threshold must be inside (0, 1)"),
+           dest='renorm_out', arg=lambda args, alt_units: args.renorm,
+           no_scan="the fit needs the target of a read, which a scan finds with the maps as they are"),
     Output('variants', lambda scan: VARIANTS_HEADER, lambda q, t, s, row, v: format_variants(q, t, s, row[0], v),
-           lambda v: _pack_variants(v), lambda text: _unpack_variants(text), 'variant_rows', False),
+           lambda v: _pack_variants(v), lambda text: _unpack_variants(text), 'variant_rows', False,
+           file='variants_out', ask='switch', flag='--variants',
+           value=lambda d, t, c, a: variant_value(d.variants, (a.get('variants') or {}).get(t, ())),
+           refuse=_not_with_scan("variants cannot be combined with a scan"),
+           arg=lambda args, alt_units: alt_units if args.variants else None, no_scan=_ALIGNED % "variant"),
     Output('flank_mod', lambda scan: flank_mod_rule.HEADER, lambda q, t, s, row, v: flank_mod_rule.format_row(q, t, s, row[0], v),
-           lambda v: _pack_flank_mod(v), lambda text: _unpack_flank_mod(text), 'flank_mod_rows', False),
+           lambda v: _pack_flank_mod(v), lambda text: _unpack_flank_mod(text), 'flank_mod_rows', False,
+           file='flank_mod_out', ask='switch', flag='--flank-mod',
+           value=lambda d, t, c, a: flank_mod_value(d.flank_mod),
+           refuse=_not_with_scan("flank methylation calls cannot be combined with a scan"),
+           needs_mod="the calls compare the modification model's k-mer table with the base table", no_scan=_ALIGNED % "flank"),
     Output('tracts', lambda scan: tracts_mod.HEADER, lambda q, t, s, row, v: tracts_mod.format_row(q, t, s, row[0], v),
-           lambda v: _pack_tracts(v), lambda text: _unpack_tracts(text), 'tract_rows', False),
+           lambda v: _pack_tracts(v), lambda text: _unpack_tracts(text), 'tract_rows', False,
+           file='tracts_out', ask='switch', flag='--tracts', value=lambda d, t, c, a: d.tracts,
+           refuse=_not_with_scan("tracts cannot be combined with a scan"), no_scan=_ALIGNED % "tract"),
     Output('anchored_mod', lambda scan: anchored_mod.MOD_HEADER, lambda q, t, s, row, v: anchored_mod.format_mod_row(q, t, s, *(v or (None, None))),
-           lambda v: _pack_anchored_mod(v), lambda text: _unpack_anchored_mod(text), 'anchored_mod_rows', False),
+           lambda v: _pack_anchored_mod(v), lambda text: _unpack_anchored_mod(text), 'anchored_mod_rows', False,
+           file='anchored_mod_out', ask='switch', flag='--anchored-mod', value=lambda d, t, c, a: (d.anchored, d.anchored_mod),
+           refuse=lambda asked, scan: None if asked.get('anchored') is not None else "anchored methylation calls need anchored counting",
+           needs_mod="the calls are those of the modification model", no_scan=_BOTH_FLANKS),
     Output('anchored', lambda scan: anchored_mod.HEADER, lambda q, t, s, row, v: anchored_mod.format_row(q, t, s, v),
-           lambda v: _pack_anchored(v), lambda text: _unpack_anchored(text), 'anchored_rows', False),
+           lambda v: _pack_anchored(v), lambda text: _unpack_anchored(text), 'anchored_rows', False,
+           file='anchored_out', ask='keyword', level=True, flag='--anchored', value=lambda d, t, c, a: d.anchored,
+           refuse=_not_with_scan("anchored counting cannot be combined with a scan"),
+           arg=lambda args, alt_units: args.anchored_min_score, no_scan=_BOTH_FLANKS),
 )
 # (`renorm`, `variants`, `flank_mod`, `tracts`, `anchored_mod` and `anchored`, the last fields, default to None: callers that build a Merged from the five
 # values before them keep working.  `anchored` stays the last field, as it did when `variants`, `anchored_mod` and `tracts` came in: fields
@@ -743,7 +774,10 @@ def _unpack_anchored(text):
 
 
 def outputs_on(**flags):
-    """The entries of OUTPUTS whose flag (units=, confidence=, mod_llr=, scores=, anchored=, variants=, renorm=, anchored_mod=, tracts=, flank_mod=) is set."""
+    """The entries of OUTPUTS whose flag (its name as a keyword) is set."""
+    unknown = set(flags) - set(Merged._fields[1:])
+    if unknown:
+        raise TypeError("no such output: %s" % ", ".join(sorted(unknown)))
     return [o for o in OUTPUTS if flags.get(o.name)]
 
 
@@ -759,13 +793,13 @@ def as_detected(res, units=False, confidence=False, mod_llr=False):
     return Detected(res[0], *[next(rest) if asked else None for asked in (units, confidence, mod_llr)])
 
 
-def _read_values(target, strand, det, scores=None):
-    """What the writers know of one read: (target, strand, row or None, {output name: value or None})."""
+def _read_values(target, strand, det, scores=None, counter=None, asked=None):
+    """What the writers know of one read: (target, strand, row or None, {output name: value or None}); counter and asked (run_count's
+    {name: value}): what the value functions of OUTPUTS take -- run_count hands over both for every read; without them a record
+    gives the values that need neither."""
     if det is None:
         return target, strand, None, dict(scores=scores)
-    return target, strand, det.row, dict(units=det.units, confidence=det.conf, mod_llr=det.llr, scores=scores, anchored=det.anchored, variants=det.variants,
-                                         renorm=getattr(det, 'renorm', None), anchored_mod=(det.anchored, getattr(det, 'anchored_mod', None)),
-                                         tracts=getattr(det, 'tracts', None), flank_mod=flank_mod_value(getattr(det, 'flank_mod', None)))
+    return target, strand, det.row, dict({o.name: o.value(det, target, counter, asked or {}) for o in OUTPUTS if o.value}, scores=scores)
 
 
 def _emit(sink, on, seq, qname, target, strand, row, values):
@@ -799,15 +833,14 @@ def unpack_blob(on, blob):
     return fields[0], fields[1], fields[2], values
 
 
-def gather_rows(rows, items, sdist, units=False, scan=None, confidence=False, mod_llr=False, anchored=False, variants=False, renorm=False, anchored_mod=False,
-                tracts=False, flank_mod=False):
+def gather_rows(rows, items, sdist, units=False, scan=None, **flags):
     """Reads of this rank (run_count with world > 1) -> fixed-size records + one blob per read (pack_blob) -> one gather -> on rank 0
-    the rows of every file in input order: Merged(rows, units, confidence, mod_llr, scores, renorm, variants, flank_mod, tracts, anchored_mod, anchored), [(sequence number, TSV row)] each, None
-    for an output that was not asked for (scores: asked for by scan) and for every field off rank 0.  `items`: every accepted (qname,
+    the rows of every file in input order: Merged(rows, one field per entry of OUTPUTS), [(sequence number, TSV row)] each, None for
+    an output whose flag (its name, given as a keyword like units= and scan=; outputs_on raises TypeError for a name that is no output)
+    was not set (scores: asked for by scan) and for every field off rank 0.  `items`: every accepted (qname,
     strand, target) of the input, which each rank derives from the same SAM file (scan: from the same index).  A read that failed
     travels as a record with valid = 0 and writes nothing; a scan read without a winner as one with valid = 2: it writes a score row."""
-    on = outputs_on(units=units, confidence=confidence, mod_llr=mod_llr, scores=bool(scan), anchored=anchored, variants=variants, renorm=renorm,
-                    anchored_mod=anchored_mod, tracts=tracts, flank_mod=flank_mod)
+    on = outputs_on(units=units, scores=bool(scan), **flags)
     rec = np.zeros(len(rows), ROW_DTYPE); blobs = []; idx = np.zeros(len(rows), np.int64)
     for k, (seq, read) in enumerate(rows):
         idx[k] = seq
@@ -862,10 +895,7 @@ def route(stream, loci, log):
         yield sr.QNAME, ('+' if sr.FLAG & 0x10 == 0 else '-'), targets, sr.QLEN
 
 
-def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, out=None, readers=0, stats=None, units=False, units_out=None,
-              scan=None, scores_out=None, confidence=False, conf_out=None, mod_llr=False, llr_out=None, anchored=None, anchored_out=None,
-              variants=None, variants_out=None, renorm=None, renorm_out=None, anchored_mod=False, anchored_mod_out=None, tracts=False, tracts_out=None,
-              flank_mod=False, flank_mod_out=None):
+def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, out=None, readers=0, stats=None, scan=None, **asked):
     """Route the SAM records of `stream` to their targets, run this rank's share through
     `counter.detect_batch` and return [(sequence number, TSV row or -- several ranks -- what gather_rows takes)].
 
@@ -877,28 +907,14 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
     `readers` > 0: raw signals are fetched by that many threads ahead of the GPU batches (inflating
     the deflate chunks of a fast5 releases the GIL and is what bounds a `count` run on real files);
     the order of the rows does not change.
-    `units`, `confidence`, `mod_llr` (the latter two not with scan; mod_llr: a counter with a modification model): the optional outputs
-    of OUTPUTS -- the counter is asked for them (counter.detect_batch(..., units=True) and so on), and every result is normalised to a
-    Detected record (as_detected); single process: their rows (format_units, format_confidence, format_mod_llr) go to `units_out`,
-    `conf_out`, `llr_out` with the count rows and to stats["unit_rows"], stats["conf_rows"], stats["llr_rows"].
-    `anchored` (a score threshold, not with scan): the counter is asked for Detected records with the anchored record of every read
-    (counter.detect_batch(..., anchored=threshold, records=True)); their rows (strique_amd.anchored.format_row) go to `anchored_out`
-    and to stats["anchored_rows"].  The count rows and the other files do not change.
-    `anchored_mod` (with `anchored`, a counter with a modification model): the methylation calls of the anchored reads are on for this
-    run (counter.set_anchored_mod(True)); their rows (strique_amd.anchored.format_mod_row; the ratios with `mod_llr`) go to
-    `anchored_mod_out` and to stats["anchored_mod_rows"].  The count rows and the other files do not change.
-    `variants` ({target: [alt units as configured]}, not with scan; the counter's targets were added with them): the counter is asked
-    for Detected records with the variant pass on (counter.set_variants(True), counter.detect_batch(..., records=True)); their rows
-    (variant_value, format_variants) go to `variants_out` and to stats["variant_rows"].  The count rows and the other files do not change.
-    `renorm` (a share threshold inside (0, 1), not with scan): the second normalisation step is on for this run
-    (counter.set_renorm(threshold)) and the counter is asked for Detected records; the fit of every read (strique_amd.renorm.report,
-    format_row) goes to `renorm_out` and to stats["renorm_rows"].  The count rows of the reads it applies to change.
-    `tracts` (not with scan; the counter's targets were added with their compound definitions): the tract pass is on for this run
-    (counter.set_tracts(True)) and the counter is asked for Detected records; their rows (strique_amd.tracts.format_row) go to
-    `tracts_out` and to stats["tract_rows"].  The count rows and the other files do not change.
-    `flank_mod` (not with scan; a counter with a modification model): the flank pass is on for this run (counter.set_flank_mod(True))
-    and the counter is asked for Detected records; their rows (strique_amd.flank_mod.format_row) go to `flank_mod_out` and to
-    stats["flank_mod_rows"].  The count rows and the other files do not change.
+    Further keywords: the optional outputs of OUTPUTS, each by its name and by the keyword of its file (units=True, units_out=FILE;
+    confidence, conf_out; mod_llr, llr_out; anchored=score threshold, anchored_out; anchored_mod, anchored_mod_out; variants={target:
+    [alt units as configured]}, variants_out; renorm=share threshold, renorm_out; tracts, tracts_out; flank_mod, flank_mod_out; the
+    score rows of a scan: scores_out); any other keyword is a TypeError.  OUTPUTS says how the counter is asked for each of them, which
+    of them a scan excludes (ValueError) and how the value of a read is taken from its result, which is normalised to a Detected record
+    (as_detected).  Single process: the rows of an output go to its file with the count rows; they are collected in stats[its `stat`
+    key] either way.  A switch of the counter that an output turns on belongs to this run: it is off again when the run is through.
+    The count rows and the other files do not depend on what else is asked for, but with renorm: the rows of the reads it applies to change.
     `scan` ({"min_score", "candidates", "scores"}): `stream` is a list of read ids instead of a SAM stream; every read goes through
     counter.scan_batch and takes target and strand from its winner -- a read without one writes no row, as a read without a target
     writes none; single process: the score rows (strique_amd.scan.format_scores, every read) go to `scores_out` and to
@@ -908,48 +924,31 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
     if stats is None:
         stats = {}
     stats.setdefault("failed", 0)
-    if anchored is not None and scan:
-        raise ValueError("anchored counting cannot be combined with a scan")
-    if anchored_mod and anchored is None:
-        raise ValueError("anchored methylation calls need anchored counting")
-    if variants is not None and scan:
-        raise ValueError("variants cannot be combined with a scan")
-    if renorm is not None and scan:
-        raise ValueError("renorm cannot be combined with a scan")
-    if tracts and scan:
-        raise ValueError("tracts cannot be combined with a scan")
-    if flank_mod and scan:
-        raise ValueError("flank methylation calls cannot be combined with a scan")
-    if renorm is not None and not 0 < renorm < 1:
-        raise ValueError("the renorm share threshold must be inside (0, 1)")
-    files = dict(rows=out, units=units_out, confidence=conf_out, mod_llr=llr_out, scores=scores_out, anchored=anchored_out, variants=variants_out,
-                 renorm=renorm_out, anchored_mod=anchored_mod_out, tracts=tracts_out, flank_mod=flank_mod_out)
-    on = outputs_on(units=units, confidence=confidence, mod_llr=mod_llr, scores=scan and scan["scores"], anchored=anchored is not None,
-                    variants=variants is not None, renorm=renorm is not None, anchored_mod=anchored_mod, tracts=tracts,
-                    flank_mod=flank_mod)
+    files = dict({o.name: asked.pop(o.file, None) for o in OUTPUTS}, rows=out)
+    unknown = set(asked) - {o.name for o in OUTPUTS if o.ask}
+    if unknown:
+        raise TypeError("run_count() got an unexpected keyword argument '%s'" % sorted(unknown)[0])
+    asked['scores'] = bool(scan and scan["scores"])
+    on = [o for o in OUTPUTS if _asked(o, asked.get(o.name))]
+    for o in on:
+        refused = o.refuse and o.refuse(asked, scan)
+        if refused:
+            raise ValueError(refused)
     if out is not None:
         print('\t'.join(HEADER), file=out)
     for o in OUTPUTS:
         stats.setdefault(o.stat, [])
         if files[o.name] is not None:
             print('\t'.join(o.header(scan)), file=files[o.name])
-    extras = {o.name: True for o in on if o.name not in ('scores', 'anchored', 'variants', 'renorm', 'anchored_mod', 'tracts', 'flank_mod')}
-    if anchored is not None:
-        extras.update(anchored=anchored, records=True)
-    if anchored_mod:
-        counter.set_anchored_mod(True)
-    if variants is not None:
-        counter.set_variants(True)
-        extras.update(records=True)
-    if renorm is not None:
-        counter.set_renorm(renorm)
-        extras.update(records=True)
-    if tracts:
-        counter.set_tracts(True)
-        extras.update(records=True)
-    if flank_mod:
-        counter.set_flank_mod(True)
-        extras.update(records=True)
+    legacy = {name: bool(asked.get(name)) for name in ('units', 'confidence', 'mod_llr')}          # the shapes as_detected takes apart
+    extras = {}
+    for o in on:
+        if o.ask == 'switch':
+            getattr(counter, 'set_' + o.name)(asked[o.name] if o.level else True)
+        elif o.ask == 'keyword':
+            extras[o.name] = asked[o.name] if o.level else True
+        if o.ask == 'switch' or o.level:
+            extras['records'] = True
     rows = []
     records = ((rid, '.', ['.'], 0) for rid in stream) if scan else route(stream, loci, log)
     mine_set = None
@@ -974,7 +973,7 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
         if faulted.is_set():                                      # queued behind the batch that faulted: the device is not touched again
             raise DeviceFault("not run: the device failed in an earlier batch")
         def scan_some(raws):
-            got, sc = counter.scan_batch(raws, min_score=scan["min_score"], units=units, scores=True)
+            got, sc = counter.scan_batch(raws, min_score=scan["min_score"], units=legacy['units'], scores=True)
             return [(g, [tuple(x) for x in s]) for g, s in zip(got, sc)]
         try:
             if scan:
@@ -1008,14 +1007,9 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
             read = None
             if res is not None and scan:
                 winner, sc = res
-                read = _read_values(None, None, None, sc) if winner is None else _read_values(winner[0], winner[1], as_detected(winner[2], units), sc)
+                read = _read_values(None, None, None, sc) if winner is None else _read_values(winner[0], winner[1], as_detected(winner[2], legacy['units']), sc, counter, asked)
             elif res is not None:
-                det = as_detected(res, units, confidence, mod_llr)
-                if variants is not None:
-                    det = det._replace(variants=variant_value(det.variants, variants.get(target, ())))
-                if renorm is not None:
-                    det = det._replace(renorm=renorm_mod.report(det.renorm, counter.renorm_bin_width))
-                read = _read_values(target, strand, det)
+                read = _read_values(target, strand, as_detected(res, **legacy), None, counter, asked)
             if world > 1:
                 sink['rows'].append((seq, read))
             elif read is not None:
@@ -1134,14 +1128,9 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
             engine.shutdown(wait=True)
             if pool is not None:
                 pool.shutdown()
-            if variants is not None:
-                counter.set_variants(False)          # the switch belongs to this run
-            if renorm is not None:
-                counter.set_renorm(None)
-            if tracts:
-                counter.set_tracts(False)
-            if flank_mod:
-                counter.set_flank_mod(False)
+            for o in on:
+                if o.ask == 'switch':
+                    getattr(counter, 'set_' + o.name)(None if o.level else False)          # the switch belongs to this run
         else:
             # an exception is on its way out (a DeviceFault from the engine thread, a broken input): the batch queued behind
             # the failed one must not be handed to a device that may be hung, and nobody waits for it -- the caller exits,

@@ -49,6 +49,72 @@ Detected = namedtuple('Detected', ['row', 'units', 'conf', 'llr', 'anchored', 'v
                       defaults=(None, None, None, None, None, None))
 
 
+def _ratios(scores):
+    """(V_base, V_mod) rows -> V_mod - V_base."""
+    return None if scores is None else scores[:, 1] - scores[:, 0]
+
+
+def _fetch_anchored(counter, reads, idx):
+    return [(int(a['kind']), int(a['status']), int(a['count']), float(a['log_p']), int(a['begin']), int(a['end']), int(a['free_samples']))
+            for a in counter.ctx.batch_fetch_anchored()]
+
+
+def _legacy_anchored(a):
+    return (anchored_mod.KIND_NAMES[a[0]],) + tuple(a[2:]) if a[0] in (anchored_mod.ENDS_IN_REPEAT, anchored_mod.STARTS_IN_REPEAT) else None
+
+
+def _fetch_variants(counter, reads, idx):
+    out = []
+    for i, v in zip(idx, counter.ctx.batch_fetch_variants()):
+        if v is not None:
+            m = counter.variant_models[reads[i][0]]
+            pattern = "".join("0" if b == 0 else "0" * m.context_units + str(int(b)) for b in v[1])
+            v = (v[0], pattern, v[1], v[2], v[3].reshape(len(v[1]), m.n_branches))      # (a read without passages: (0, NB))
+        out.append(v)
+    return out
+
+
+def _fetch_renorm(counter, reads, idx):
+    return [(int(r['applied']), {s: (int(f['a']), int(f['b']), int(f['w']), int(f['score'])) if f['fitted'] else None
+                                 for s, f in zip(renorm_mod.SIGNALS, r['fit'])}) for r in counter.ctx.batch_fetch_renorm()]
+
+
+def _fetch_tracts(counter, reads, idx):
+    out = []
+    for i, t in zip(idx, counter.ctx.batch_fetch_tracts()):
+        rec = None
+        if int(t['status']) == 0:
+            strand = counter.tract_models[reads[i][0]][1]
+            rec = (tracts_mod.configured_order([int(c) for c in t['count'][:int(t['n_tracts'])]], strand), float(t['log_p']))
+        out.append(rec)
+    return out
+
+
+def _fetch_flank_mod(counter, reads, idx):
+    return [None if g is None else [(int(x['flank']), int(x['pos']), int(x['n_sites']), int(x['n_columns']), int(x['status']), int(x['begin']), int(x['end']),
+                                     float(x['v_mod'] - x['v_base'])) for x in g] for g in counter.ctx.batch_fetch_flank_mod()]
+
+
+# The optional passes of detect / detect_batch, in the order their switches go on.  name: the pass -- a keyword of detect and
+# detect_batch (keyword) or the attribute a set_<name> switch of the counter keeps; what it holds is the pass's value in a request and,
+# with `level`, travels to the context's switch.  field: its field of Detected.  ensure: the method that registers its models first.
+# fetch(counter, reads, idx): its value for every read of the device batch, reads[idx[k]] being read k.  place: where it stands
+# behind the row in the tuple detect_batch returns without records=True (None: in Detected only), as legacy(value).
+Pass = namedtuple('Pass', ['name', 'field', 'keyword', 'ensure', 'level', 'fetch', 'place', 'legacy'], defaults=(lambda value: value,))
+PASSES = (
+    Pass('anchored', 'anchored', True, '_ensure_anchored', True, _fetch_anchored, 3, _legacy_anchored),
+    Pass('anchored_mod', 'anchored_mod', False, None, False,
+         lambda c, reads, idx: [None if x is None else (x[0], _ratios(x[1])) for x in c.ctx.batch_fetch_anchored_mod()], 4),
+    Pass('units', 'units', True, None, False, lambda c, reads, idx: c.ctx.batch_fetch_units(), 0),
+    Pass('confidence', 'conf', True, None, False, lambda c, reads, idx: c.ctx.batch_fetch_confidence(), 1),
+    Pass('mod_llr', 'llr', True, None, False, lambda c, reads, idx: [_ratios(v) for v in c.ctx.batch_fetch_mod_llr()], 2),
+    Pass('variants', 'variants', False, '_ensure_variants', False, _fetch_variants, 5),
+    Pass('renorm', 'renorm', False, '_ensure_renorm', True, _fetch_renorm, None),
+    Pass('tracts', 'tracts', False, '_ensure_tracts', False, _fetch_tracts, 6),
+    Pass('flank_mod', 'flank_mod', False, '_ensure_flank_mod', False, _fetch_flank_mod, 7),
+)
+
+
 class repeatCounter(object):
     def __init__(self, model_file, mod_model_file=None, align_config=None, HMM_config=None, device=0, context=None):
         cfg = dict(ALIGN_DEFAULTS)
@@ -324,7 +390,7 @@ class repeatCounter(object):
         With set_anchored_mod(True) and anchored=m: the methylation call of the read, (pattern, llr) or None, directly behind the
         anchored element -- see set_anchored_mod.
         With set_tracts(True) (a counter with a target added with tracts=): one last element, None or (counts, log_p) -- see set_tracts.
-        Order of the elements: (tuple[, positions][, conf][, llr][, anchored][, anchored_mod][, variants][, tracts]); without any of them the bare tuple.
+        Order of the elements: (tuple[, positions][, conf][, llr][, anchored][, anchored_mod][, variants][, tracts][, flank_mod]); without any of them the bare tuple.
         records=True: a list of Detected records instead (the fields that were not asked for None; `anchored` the record of every
         read, whatever its kind: (kind number, status, count, log_p, begin, end, free_samples))."""
         items = list(items)
@@ -334,78 +400,45 @@ class repeatCounter(object):
             raise ValueError("RepeatCounter: the anchored score threshold must be above 0.")
         if self.anchored_mod and anchored is None:
             raise ValueError("RepeatCounter: anchored_mod needs anchored=m (the calls hang on the anchored records).")
-        variants = self.variants
-        tracts = self.tracts
-        fmod = self.flank_mod
+        asked = dict(units=units, confidence=confidence, mod_llr=mod_llr, anchored=anchored)
+        request = {}
+        for p in PASSES:
+            value = asked[p.name] if p.keyword else getattr(self, p.name)
+            if value:          # (a level that is on is never 0: anchored was checked above, set_renorm keeps None or a share inside (0, 1))
+                request[p.name] = value
+        legacy = sorted((p for p in PASSES if p.name in request and p.place is not None), key=lambda p: p.place)
         reads = [(self._classifier_for(t, s).target_id, r) for t, r, s in items]
         out = [None] * len(items)
-        for i, d, _, _ in self._run(reads, units=units, confidence=confidence, mod_llr=mod_llr, anchored=anchored, variants=variants, renorm=self.renorm,
-                                    anchored_mod=self.anchored_mod, tracts=tracts, flank_mod=fmod):
+        for i, d, _, _ in self._run(reads, request):
             if records:
                 out[i] = d
                 continue
-            extra = ((d.units,) if units else ()) + ((d.conf,) if confidence else ()) + ((d.llr,) if mod_llr else ())
-            if anchored is not None:
-                a = d.anchored
-                extra += ((anchored_mod.KIND_NAMES[a[0]],) + tuple(a[2:]) if a[0] in (anchored_mod.ENDS_IN_REPEAT, anchored_mod.STARTS_IN_REPEAT) else None,)
-            if self.anchored_mod:
-                extra += (d.anchored_mod,)
-            if variants:
-                extra += (d.variants,)
-            if tracts:
-                extra += (d.tracts,)
-            if fmod:
-                extra += (d.flank_mod,)
+            extra = tuple(p.legacy(getattr(d, p.field)) for p in legacy)
             out[i] = (d.row,) + extra if extra else d.row
         return out
 
     @contextlib.contextmanager
-    def _switches(self, units, confidence, mod_llr, anchored=None, variants=False, renorm=None, anchored_mod=False, tracts=False, flank_mod=False):
-        """The optional passes that were asked for are on inside the block, and all of them off after it."""
+    def _switches(self, request):
+        """The passes of `request` ({name: value}, see PASSES) are on inside the block, and every pass is off after it."""
         try:
-            if anchored is not None:
-                self._ensure_anchored()
-                self.ctx.set_anchored(True, anchored)
-            if anchored_mod:
-                self.ctx.set_anchored_mod(True)
             # inside the try: set_mod_llr refuses a modification model the scoring pass does not cover, and the switches a
             # failed call leaves behind must not stay on for the next caller of a shared context
-            if units:
-                self.ctx.set_units(True)
-            if confidence:
-                self.ctx.set_confidence(True)
-            if mod_llr:
-                self.ctx.set_mod_llr(True)
-            if variants:
-                self._ensure_variants()
-                self.ctx.set_variants(True)
-            if renorm is not None:
-                self._ensure_renorm()
-                self.ctx.set_renorm(True, renorm)
-            if tracts:
-                self._ensure_tracts()
-                self.ctx.set_tracts(True)
-            if flank_mod:
-                self._ensure_flank_mod()
-                self.ctx.set_flank_mod(True)
+            for p in PASSES:
+                if p.name in request:
+                    if p.ensure:
+                        getattr(self, p.ensure)()
+                    getattr(self.ctx, 'set_' + p.name)(True, *((request[p.name],) if p.level else ()))
             yield
         finally:
-            self.ctx.set_flank_mod(False)
-            self.ctx.set_tracts(False)
-            self.ctx.set_renorm(False)
-            self.ctx.set_variants(False)
-            self.ctx.set_anchored_mod(False)
-            self.ctx.set_anchored(False)
-            self.ctx.set_mod_llr(False)
-            self.ctx.set_units(False)
-            self.ctx.set_confidence(False)
+            for p in reversed(PASSES):
+                getattr(self.ctx, 'set_' + p.name)(False)
 
-    def _run(self, reads, units=False, confidence=False, mod_llr=False, scan=None, anchored=None, variants=False, renorm=None, anchored_mod=False, tracts=False,
-             flank_mod=False):
-        """reads: [(target_id, raw_signal)] through the context.  Yields (position in `reads`, Detected, winner, scores) per read, the
-        fields of Detected that were not asked for being None.  scan=(candidate target ids, min_score): the target ids of the reads
-        are ignored, every read is compared with every candidate (Context.scan_batch_reads); winner is its position in the candidate
-        list or -1, scores the [n_candidates, 2] array of its flank scores (both None without scan)."""
+    def _run(self, reads, request, scan=None):
+        """reads: [(target_id, raw_signal)] through the context with the passes of `request` on (_switches).  Yields (position in
+        `reads`, Detected, winner, scores) per read, the fields of Detected that were not asked for being None.  scan=(candidate
+        target ids, min_score): the target ids of the reads are ignored, every read is compared with every candidate
+        (Context.scan_batch_reads); winner is its position in the candidate list or -1, scores the [n_candidates, 2] array of its
+        flank scores (both None without scan)."""
         sigs = [np.asarray(r) for _, r in reads]
         # DAC samples that fit int16 take their order statistics from exact histograms; everything else is float64
         # (radix selection on the GPU, cond_kernels.hip: f64_stats_kernel).  A mixed batch runs as two device batches.
@@ -415,53 +448,20 @@ class repeatCounter(object):
             if not idx:
                 continue
             arrs = [sigs[i].astype(np.int16 if want_int else np.float64, copy=False) for i in idx]
-            with self._switches(units, confidence, mod_llr, anchored, variants, renorm, anchored_mod, tracts, flank_mod):
+            with self._switches(request):
                 if scan is None:
                     res = self.ctx.detect_batch_reads(arrs, [reads[i][0] for i in idx])      # one pointer per read: no host-side concatenation
                     win = sc = [None] * len(res)
                 else:
                     res, win, sc = self.ctx.scan_batch_reads(arrs, scan[0], scan[1], scores=True)
                 mods = self.ctx.batch_fetch_mod() if self.pm is not self.pm_mod else ['-'] * len(res)
-                pos = self.ctx.batch_fetch_units() if units else [None] * len(res)
-                conf = self.ctx.batch_fetch_confidence() if confidence else [None] * len(res)
-                vs = self.ctx.batch_fetch_mod_llr() if mod_llr else [None] * len(res)
-                var = [None] * len(res)
-                if variants:
-                    var = []
-                    for i, v in zip(idx, self.ctx.batch_fetch_variants()):
-                        if v is not None:
-                            m = self.variant_models[reads[i][0]]
-                            pattern = "".join("0" if b == 0 else "0" * m.context_units + str(int(b)) for b in v[1])
-                            v = (v[0], pattern, v[1], v[2], v[3].reshape(len(v[1]), m.n_branches))      # (a read without passages: (0, NB))
-                        var.append(v)
-                rn = [None] * len(res)
-                if renorm is not None:
-                    rn = [(int(r['applied']), {s: (int(f['a']), int(f['b']), int(f['w']), int(f['score'])) if f['fitted'] else None
-                                               for s, f in zip(renorm_mod.SIGNALS, r['fit'])}) for r in self.ctx.batch_fetch_renorm()]
-                an = [None] * len(res)
-                if anchored is not None:
-                    an = [(int(a['kind']), int(a['status']), int(a['count']), float(a['log_p']), int(a['begin']), int(a['end']), int(a['free_samples']))
-                          for a in self.ctx.batch_fetch_anchored()]
-                am = [None] * len(res)
-                if anchored_mod:
-                    am = [None if x is None else (x[0], None if x[1] is None else x[1][:, 1] - x[1][:, 0]) for x in self.ctx.batch_fetch_anchored_mod()]
-                tr = [None] * len(res)
-                if tracts:
-                    tr = []
-                    for i, t in zip(idx, self.ctx.batch_fetch_tracts()):
-                        rec = None
-                        if int(t['status']) == 0:
-                            strand = self.tract_models[reads[i][0]][1]
-                            rec = (tracts_mod.configured_order([int(c) for c in t['count'][:int(t['n_tracts'])]], strand), float(t['log_p']))
-                        tr.append(rec)
-                fm = [None] * len(res)
-                if flank_mod:
-                    fm = [None if g is None else [(int(x['flank']), int(x['pos']), int(x['n_sites']), int(x['n_columns']), int(x['status']), int(x['begin']), int(x['end']),
-                                                   float(x['v_mod'] - x['v_base'])) for x in g] for g in self.ctx.batch_fetch_flank_mod()]
-            for i, r, m, u, cf, v, w, s, a, vr, rnr, amr, trr, fmr in zip(idx, res, mods, pos, conf, vs, win, sc, an, var, rn, am, tr, fm):
+                fetched = {p.field: p.fetch(self, reads, idx) for p in PASSES if p.name in request}
+            # one column per field of Detected behind the row, in the record's own order: all None for a pass that is off
+            columns = zip(*[fetched.get(f, [None] * len(res)) for f in Detected._fields[1:]])
+            for i, r, m, w, s, values in zip(idx, res, mods, win, sc, columns):
                 n = int(r['count']); p = float(r['log_p']) if n or r['log_p'] != 0 else 0
                 row = (n, float(r['score_prefix']), float(r['score_suffix']), p, int(r['offset']), int(r['ticks']), m)
-                yield i, Detected(row, u, cf, None if v is None else v[:, 1] - v[:, 0], a, vr, rnr, amr, fmr, trr), w, s
+                yield i, Detected(row, *values), w, s
 
     def candidates(self, targets=None):
         """[(target_name, strand)] of a scan: every target added (or the named ones), in add_target order, '+' before '-'."""
@@ -496,7 +496,7 @@ class repeatCounter(object):
         reads = [(None, r) for r in signals]
         out = [None] * len(reads)
         all_scores = np.zeros((len(reads), len(cands), 2), np.float64)
-        for i, d, w, sc in self._run(reads, units=units, scan=(ids, min_score)):
+        for i, d, w, sc in self._run(reads, {'units': True} if units else {}, scan=(ids, min_score)):
             all_scores[i] = sc
             if w >= 0:
                 out[i] = cands[int(w)] + ((d.row, d.units) if units else d.row,)

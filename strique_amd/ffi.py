@@ -503,9 +503,14 @@ class Context(object):
         self._check(getattr(self._lib, "strq_batch_fetch_" + entry)(self._h, _ptr(out), ctypes.c_int64(n)))
         return out[:n]
 
+    def _switch(self, entry, on, level=None):
+        """strq_set_<entry>: the pass on or off; `level` for an entry that takes one with it (0.0 when switching off)."""
+        args = [ctypes.c_int32(1 if on else 0)] + ([] if level is None else [ctypes.c_double(level if on else 0.0)])
+        self._check(getattr(self._lib, "strq_set_" + entry)(self._h, *args))
+
     def set_units(self, on):
         """strq_set_units: later run calls also produce repeat-unit positions (batch_fetch_units)."""
-        self._check(self._lib.strq_set_units(self._h, ctypes.c_int32(1 if on else 0)))
+        self._switch("units", on)
 
     def batch_fetch_units(self):
         """Unit positions of the last batch: one ascending np.int64 array of raw-signal sample indices per read, or None for a
@@ -523,7 +528,7 @@ class Context(object):
 
     def set_confidence(self, on):
         """strq_set_confidence: later run calls also run the forward pass over every decoded window (batch_fetch_confidence)."""
-        self._check(self._lib.strq_set_confidence(self._h, ctypes.c_int32(1 if on else 0)))
+        self._switch("confidence", on)
 
     def batch_fetch_confidence(self):
         """Confidence of the last batch: per read (log_lik, count_mean, count_sd) as Python floats, or None for a read that was
@@ -540,7 +545,7 @@ class Context(object):
     def set_mod_llr(self, on):
         """strq_set_mod_llr: later run calls also score every repeat unit of a modification pattern under both branches of the
         dual model (batch_fetch_mod_llr).  StriqueHipError (STRQ_ERR_UNSUPPORTED) for a modification model the pass does not cover."""
-        self._check(self._lib.strq_set_mod_llr(self._h, ctypes.c_int32(1 if on else 0)))
+        self._switch("mod_llr", on)
 
     def batch_fetch_mod_llr(self):
         """Per-unit scores of the last batch: per read an (n_units, 2) float64 array of (V_base, V_mod), one row per character of
@@ -567,7 +572,7 @@ class Context(object):
     def set_variants(self, on):
         """strq_set_variants: later run calls also decode the variant model of every decoded read whose target has one
         (batch_fetch_variants)."""
-        self._check(self._lib.strq_set_variants(self._h, ctypes.c_int32(1 if on else 0)))
+        self._switch("variants", on)
 
     def batch_fetch_variants(self):
         """Variants of the last batch (strq_batch_fetch_variants): per read None (not decoded, or a target without a variant model) or
@@ -606,7 +611,7 @@ class Context(object):
     def set_anchored(self, on, min_score=0.0):
         """strq_set_anchored: later run calls also classify every read (strique_amd.anchored) and decode those that hold one flank
         only.  StriqueHipError (STRQ_ERR_ARG) for a min_score that is not above 0."""
-        self._check(self._lib.strq_set_anchored(self._h, ctypes.c_int32(1 if on else 0), ctypes.c_double(min_score if on else 0.0)))
+        self._switch("anchored", on, min_score)
 
     def batch_fetch_anchored(self):
         """Records of the last batch (strq_batch_fetch_anchored): a structured array of ANCHORED_DTYPE, one element per read."""
@@ -628,7 +633,7 @@ class Context(object):
     def set_tracts(self, on):
         """strq_set_tracts: later run calls also decode the compound model of every decoded read whose target has one
         (batch_fetch_tracts)."""
-        self._check(self._lib.strq_set_tracts(self._h, ctypes.c_int32(1 if on else 0)))
+        self._switch("tracts", on)
 
     def batch_fetch_tracts(self):
         """Records of the last batch (strq_batch_fetch_tracts): a structured array of TRACTS_DTYPE, one element per read."""
@@ -649,7 +654,7 @@ class Context(object):
 
     def set_flank_mod(self, on):
         """strq_set_flank_mod: later run calls also call the CpG groups of the flanks (batch_fetch_flank_mod)."""
-        self._check(self._lib.strq_set_flank_mod(self._h, ctypes.c_int32(1 if on else 0)))
+        self._switch("flank_mod", on)
 
     def batch_fetch_flank_mod(self):
         """Flank methylation calls of the last batch (strq_batch_fetch_flank_mod): per read None (it did not qualify) or a structured
@@ -668,7 +673,7 @@ class Context(object):
     def set_anchored_mod(self, on):
         """strq_set_anchored_mod: later run calls with anchored counting on also call the methylation pattern of every read of
         kind 2 / 3 whose record was decoded and whose target has a modification model (batch_fetch_anchored_mod)."""
-        self._check(self._lib.strq_set_anchored_mod(self._h, ctypes.c_int32(1 if on else 0)))
+        self._switch("anchored_mod", on)
 
     def batch_fetch_anchored_mod(self):
         """Methylation calls of the anchored reads of the last batch (strq_batch_fetch_anchored_mod): per read None (no call), or
@@ -707,7 +712,7 @@ class Context(object):
     def set_renorm(self, on, min_share=0.0):
         """strq_set_renorm: later run calls refit the maps of every read against its target's composition and fold the fit in where
         the fitted repeat share reaches min_share.  StriqueHipError (STRQ_ERR_ARG) for a min_share outside (0, 1), or with a scan set."""
-        self._check(self._lib.strq_set_renorm(self._h, ctypes.c_int32(1 if on else 0), ctypes.c_double(min_share if on else 0.0)))
+        self._switch("renorm", on, min_share)
 
     def batch_fetch_renorm(self):
         """Records of the last batch (strq_batch_fetch_renorm): a structured array of RENORM_DTYPE, one element per read; 'fit' holds
