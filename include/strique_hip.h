@@ -190,6 +190,20 @@ int strq_model_set_tracts(strq_ctx* ctx, int32_t model_id, int32_t n_tracts, con
  */
 int strq_viterbi_tracts(strq_ctx* ctx, int32_t model_id, int64_t n_seq, const double* x, const int64_t* x_off,
                         double* logp, int64_t* counts, int32_t* status);
+/*
+ * strq_viterbi_tracts, plus where the counted emissions lie: the windows of status 0 are decoded once more with back-pointers (the
+ * model's lane row or the general kernel), traced back, and the state path is scanned with one ballot per tract -- the kernels of
+ * the tract-position pass (strq_set_tract_positions), in pieces of at most STRQ_TRACT_POS_WS_BYTES of back-pointers.
+ *   pos_off[3 n_seq + 1]  tract j of window i is pool[pos_off[3 i + j] .. pos_off[3 i + j + 1]): counts[3 i + j] ascending
+ *                         observation indices (0-based), empty without a path and for a window that was not traced
+ *   status                as strq_viterbi_tracts, and 4: decoded, counts valid, but the window's back-pointers alone exceed the
+ *                         budget -- not traced, no positions
+ * logp, counts: as strq_viterbi_tracts, bit for bit.  pool may be NULL (pool_cap 0) to query the total in pos_off[3 n_seq];
+ * STRQ_ERR_ARG for a pool that is too small (the observations of all windows always suffice).  STRQ_ERR_DEVICE when the
+ * back-pointer decode of a window disagrees with its count decode.
+ */
+int strq_viterbi_tract_positions(strq_ctx* ctx, int32_t model_id, int64_t n_seq, const double* x, const int64_t* x_off,
+                                 double* logp, int64_t* counts, int32_t* status, int64_t* pos_off, int64_t* pool, int64_t pool_cap);
 /* Test hook: the kernel shape id (as strq_debug_viterbi_plan gives it) of the context's last tract launch; -1 before the first. */
 int strq_debug_tract_shape(const strq_ctx* ctx, int32_t* shape);
 
@@ -506,6 +520,25 @@ int strq_batch_fetch_tracts(strq_ctx* ctx, strq_tracts* out, int64_t n);
 /* The tract pass of the last run call: out[0] = ms on the GPU (all its sub-batches), out[1] = windows decoded (status 0),
  * out[2] = kernels launched (tasks, sorts and decodes; 0 with the switch off), out[3] = windows with status 2 or 3. */
 int strq_last_tracts(strq_ctx* ctx, double* out4);
+/* Where the units of every tract lie (strique_amd/tracts.py states the rule).  on = 1: later run calls, behind the tract pass and once
+ * its records are on the host, decode every window of tract status 0 once more with back-pointers (its task as the tract pass wrote
+ * it, (T + 1) * n_states * 2 bytes), trace it back and scan the state path with one ballot per tract.  Position prefix_begin + t
+ * belongs to tract j when the best path emits observation t from a counted state of loop j; per tract the positions ascend and there
+ * are count[j] - bias[j] of them.  Pieces of at most STRQ_TRACT_POS_WS_BYTES of back-pointers (default 8 GiB), one read-back and one
+ * wait per piece; a window whose back-pointers alone exceed the budget is not traced (pos_status 2, its counts stay).  A run call
+ * with the switch on fails before any launch: STRQ_ERR_ARG without strq_set_tracts or in a scan, STRQ_ERR_UNSUPPORTED when a
+ * target's compound model has no back-pointer decode.  STRQ_ERR_DEVICE when the back-pointer decode of a window disagrees with its
+ * count decode.  Rows, tract records and every other output do not change.  Sub-batches still in flight keep the mode they were
+ * launched with (the call waits for them).  Default 0: no further kernel runs and no further buffer is reserved. */
+int strq_set_tract_positions(strq_ctx* ctx, int32_t on);
+/* Tract positions of the last batch of n reads, ragged: off[3 n + 1], tract j of read i is pool[off[3 i + j] .. off[3 i + j + 1]) in
+ * model order (raw-signal sample indices); pos_status[i] (nullable): 0 positions, 1 none (the tract record's status is not 0),
+ * 2 back-pointers over the budget.  pool may be NULL to query the total in off[3 n], like strq_batch_fetch_units.  STRQ_ERR_ARG
+ * when the last run call ran with the switch off. */
+int strq_batch_fetch_tract_positions(strq_ctx* ctx, int32_t* pos_status, int64_t* off, int64_t* pool, int64_t pool_cap);
+/* The tract-position pass of the last run call: out[0] = ms on the GPU (all its sub-batches), out[1] = windows traced,
+ * out[2] = kernels launched (sorts, decodes, tracebacks, scans; 0 with the switch off), out[3] = peak back-pointer bytes of a piece. */
+int strq_last_tract_positions(strq_ctx* ctx, double* out4);
 /* ---- renorm: a second normalisation step for reads that are mostly repeat (no counterpart in the reference, whose 'minmax' map,
  * STRique.py:150-180, assumes that a read's k-mer composition looks like the pore model's) ----
  * Between the conditioning statistics and the flank alignments, every conditioned read of a target with tables gets scale and shift

@@ -259,6 +259,10 @@ def count(argv):
                                                                                               "strand; - or no third column: empty linkers; # comments and blank lines allowed)")
     parser.add_argument("--tracts", default=None, metavar="FILE", help="With --tract-units: also write the unit count of every tract of a read to FILE: one row per count row, "
                                                                        "columns " + " ".join(tracts_mod.HEADER) + " (counts in the configured order, joined by commas)")
+    parser.add_argument("--tract-positions", dest="tract_positions", default=None, metavar="FILE", help="With --tract-units and --tracts: also write where the units of every tract lie in "
+                                                                                                       "the raw signal to FILE: one row per count row, columns " + " ".join(tracts_mod.POS_HEADER) +
+                                                                                                       " (spans first-last per tract joined by commas; positions joined by commas within a "
+                                                                                                       "tract and ; between tracts; - for a tract or a read without positions)")
     parser.add_argument("--scan", action="store_true", help="No alignment: every read of the index is compared with every target of the repeat config on both strands, "
                                                              "from its raw signal alone, and counted for the one it spans (if any).  Excludes --algn; stdin is not read")
     parser.add_argument("--scan-min-score", type=float, default=None, metavar="X", help="--scan: the smallest min(score_prefix, score_suffix) a target and strand needs to be "
@@ -291,6 +295,8 @@ def count(argv):
         parser.error("--variants needs --alt-units FILE: the units to tell from the repeat unit")
     if bool(args.tracts) != bool(args.tract_units):
         parser.error("--tract-units FILE and --tracts FILE need each other: the definitions, and where the counts go")
+    if args.tract_positions and not args.tracts:
+        parser.error("--tract-positions FILE needs --tract-units FILE --tracts FILE: the positions are those of the tract counts")
     if args.scan and args.algn:
         parser.error("--scan takes the target and strand of a read from its signal: it cannot be combined with --algn")
     if not args.scan and (args.scan_scores or args.scan_min_score is not None):
@@ -313,7 +319,7 @@ def count(argv):
     if args.renorm_out and args.renorm is None:
         parser.error("--renorm-out needs --renorm MIN_SHARE")
     # then what every output needs and excludes, in the order of OUTPUTS: said once, there
-    for o in OUTPUTS:
+    for o in ALL_OUTPUTS:
         if getattr(args, _dest(o.flag)):
             if o.needs_mod and not args.mod_model:
                 parser.error("%s needs --mod_model: %s" % (o.flag, o.needs_mod))
@@ -399,8 +405,8 @@ def count(argv):
         readers = max(1, min(24, share))            # inflating is what the readers do: one per core they can get, 16 ... 24 measure the same end to end
     stats = {}
     fault = 0
-    paths = {o.name: getattr(args, o.dest or _dest(o.flag)) for o in OUTPUTS}
-    asked = {o.name: o.arg(args, alt_units) if o.arg else bool(paths[o.name]) for o in OUTPUTS if o.ask}
+    paths = {o.name: getattr(args, o.dest or _dest(o.flag)) for o in ALL_OUTPUTS}
+    asked = {o.name: o.arg(args, alt_units) if o.arg else bool(paths[o.name]) for o in ALL_OUTPUTS if o.ask}
     with contextlib.ExitStack() as stack:
         # rank 0 writes: as the batches are done in a single process (run_count), after the gather otherwise
         files = {name: stack.enter_context(open(path, 'w')) if (path and rank == 0) else None for name, path in paths.items()}
@@ -408,7 +414,7 @@ def count(argv):
         now = {name: f if world == 1 else None for name, f in files.items()}
         try:
             rows = run_count(stream, loci, f5.get_raw, counter, log, args.batch, rank, world, out if world == 1 else None, readers=readers, stats=stats,
-                             scan=scan, **asked, **{o.file: now[o.name] for o in OUTPUTS})
+                             scan=scan, **asked, **{o.file: now[o.name] for o in ALL_OUTPUTS})
         except DeviceFault:
             if world == 1:
                 raise SystemExit(3)
@@ -425,9 +431,9 @@ def count(argv):
             merged = gather_rows(rows, stats["items"], sdist, scan=scan, **asked)
             if rank == 0:
                 write_rows(out, merged.rows)
-                for o in OUTPUTS:
+                for o in ALL_OUTPUTS:
                     if files[o.name] is not None:
-                        write_rows(files[o.name], getattr(merged, o.name), header=o.header(scan))
+                        write_rows(files[o.name], merged.riders[o.name] if o.rides else getattr(merged, o.name), header=o.header(scan))
             dist.barrier()
             dist.destroy_process_group()
     if stats.get("failed"):
@@ -638,8 +644,9 @@ def _unfloats(text):
 # For count(): flag, its argument -- what the errors name, and the attribute that tells whether it was asked for; dest: the attribute
 # of its file where that is another one; arg(args, alt_units): what run_count is given for it (default: whether the file was named);
 # needs_mod / no_scan: why "<flag> needs --mod_model" / "<flag> cannot be combined with --scan" (None: it does not / it can).
+# rides (RIDERS below): (the output whose value it formats, the keyword of that output's switch that makes the value carry it).
 Output = namedtuple('Output', ['name', 'header', 'format', 'pack', 'unpack', 'stat', 'rowless', 'file', 'ask', 'value', 'flag',
-                               'level', 'refuse', 'dest', 'arg', 'needs_mod', 'no_scan'], defaults=(False, None, None, None, None, None))
+                               'level', 'refuse', 'dest', 'arg', 'needs_mod', 'no_scan', 'rides'], defaults=(False, None, None, None, None, None, None))
 _ALIGNED = "the %s pass runs on reads whose target and strand an alignment gives"
 _BOTH_FLANKS = "a scan takes a read for a target when it finds both flanks"
 
@@ -693,7 +700,7 @@ OUTPUTS = (
            value=lambda d, t, c, a: flank_mod_value(d.flank_mod),
            refuse=_not_with_scan("flank methylation calls cannot be combined with a scan"),
            needs_mod="the calls compare the modification model's k-mer table with the base table", no_scan=_ALIGNED % "flank"),
-    Output('tracts', lambda scan: tracts_mod.HEADER, lambda q, t, s, row, v: tracts_mod.format_row(q, t, s, row[0], v),
+    Output('tracts', lambda scan: tracts_mod.HEADER, lambda q, t, s, row, v: tracts_mod.format_row(q, t, s, row[0], v and v[:2]),
            lambda v: _pack_tracts(v), lambda text: _unpack_tracts(text), 'tract_rows', False,
            file='tracts_out', ask='switch', flag='--tracts', value=lambda d, t, c, a: d.tracts,
            refuse=_not_with_scan("tracts cannot be combined with a scan"), no_scan=_ALIGNED % "tract"),
@@ -708,10 +715,23 @@ OUTPUTS = (
            refuse=_not_with_scan("anchored counting cannot be combined with a scan"),
            arg=lambda args, alt_units: args.anchored_min_score, no_scan=_BOTH_FLANKS),
 )
+# Outputs that ride on another output: a file, a flag, a keyword of run_count and a stat of their own, but no pass of the counter, no
+# field of Detected, of `Merged` or of the gather blob -- the value is the one of the output they ride on (with the keyword on, that
+# value carries what they write; it travels between ranks in that output's field), asked for as run_count(..., <name>=True).
+RIDERS = (
+    Output('tract_positions', lambda scan: tracts_mod.POS_HEADER, lambda q, t, s, row, v: tracts_mod.format_positions_row(q, t, s, row[0], v),
+           None, None, 'tract_position_rows', False,
+           file='tract_positions_out', ask='rider', flag='--tract-positions', value=None,
+           refuse=lambda asked, scan: ("tract positions cannot be combined with a scan" if scan else
+                                       None if asked.get('tracts') else "tract positions need the tract counts"),
+           no_scan=_ALIGNED % "tract", rides=('tracts', 'positions')),
+)
+ALL_OUTPUTS = OUTPUTS + RIDERS
 # (`renorm`, `variants`, `flank_mod`, `tracts`, `anchored_mod` and `anchored`, the last fields, default to None: callers that build a Merged from the five
 # values before them keep working.  `anchored` stays the last field, as it did when `variants`, `anchored_mod` and `tracts` came in: fields
 # behind the first five are taken by name.)
-Merged = namedtuple('Merged', ['rows'] + [o.name for o in OUTPUTS], defaults=(None, None, None, None, None, None))
+class Merged(namedtuple('Merged', ['rows'] + [o.name for o in OUTPUTS], defaults=(None, None, None, None, None, None))):
+    riders = {}          # gather_rows: {name: rows} of the RIDERS that were on (no field: the fields are those of OUTPUTS)
 
 
 def flank_mod_value(calls):
@@ -736,14 +756,20 @@ def _unpack_flank_mod(text):
 
 
 def _pack_tracts(v):
-    """(counts, log_p) of a read as it travels between ranks: the log-probability as repr(), which float() reads back bit for bit."""
-    counts, log_p = v
-    return ','.join(str(int(c)) for c in counts) + ';' + repr(float(log_p))
+    """(counts, log_p[, positions]) of a read as it travels between ranks: the log-probability as repr(), which float() reads back bit
+    for bit; with positions a third part -- 'x' for None, else the tracts joined by '|', a tract's positions by commas, '-' for none."""
+    text = ','.join(str(int(c)) for c in v[0]) + ';' + repr(float(v[1]))
+    if len(v) == 3:
+        text += ';' + ('x' if v[2] is None else '|'.join(','.join(str(int(x)) for x in p) if len(p) else '-' for p in v[2]))
+    return text
 
 
 def _unpack_tracts(text):
-    counts, log_p = text.split(';')
-    return tuple(int(c) for c in counts.split(',')), float(log_p)
+    f = text.split(';')
+    rec = (tuple(int(c) for c in f[0].split(',')), float(f[1]))
+    if len(f) == 3:
+        rec += (None if f[2] == 'x' else tuple(np.array([] if p == '-' else [int(x) for x in p.split(',')], np.int64) for p in f[2].split('|')),)
+    return rec
 
 
 def _pack_anchored_mod(v):
@@ -775,10 +801,10 @@ def _unpack_anchored(text):
 
 def outputs_on(**flags):
     """The entries of OUTPUTS whose flag (its name as a keyword) is set."""
-    unknown = set(flags) - set(Merged._fields[1:])
+    unknown = set(flags) - set(Merged._fields[1:]) - {o.name for o in RIDERS}
     if unknown:
         raise TypeError("no such output: %s" % ", ".join(sorted(unknown)))
-    return [o for o in OUTPUTS if flags.get(o.name)]
+    return [o for o in ALL_OUTPUTS if flags.get(o.name)]
 
 
 def as_detected(res, units=False, confidence=False, mod_llr=False):
@@ -806,7 +832,7 @@ def _emit(sink, on, seq, qname, target, strand, row, values):
     """The rows of one read, (seq, text) each: its count row to sink['rows'], the row of every output of `on` to sink[name]."""
     for o in on:
         if row is not None or o.rowless:
-            sink[o.name].append((seq, o.format(qname, target, strand, row, values.get(o.name))))
+            sink[o.name].append((seq, o.format(qname, target, strand, row, values.get(o.rides[0] if o.rides else o.name))))
     if row is not None:
         sink['rows'].append((seq, format_row(qname, target, strand, row)))
 
@@ -869,7 +895,9 @@ def gather_rows(rows, items, sdist, units=False, scan=None, **flags):
             p = lp if (n or lp != 0) else 0              # the reference prints the integer 0 for a failed gate (STRique.py:602,616)
             row = (n, float(r["score_prefix"]), float(r["score_suffix"]), p, int(r["offset"]), int(r["ticks"]), mod)
         _emit(sink, on, seq, qname, target, strand, row, values)
-    return Merged(sink['rows'], *[sink[o.name] if o in on else None for o in OUTPUTS])
+    merged = Merged(sink['rows'], *[sink[o.name] if o in on else None for o in OUTPUTS])
+    merged.riders = {o.name: sink[o.name] for o in RIDERS if o in on}
+    return merged
 
 
 def write_rows(out, rows, header=True):
@@ -909,7 +937,7 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
     the order of the rows does not change.
     Further keywords: the optional outputs of OUTPUTS, each by its name and by the keyword of its file (units=True, units_out=FILE;
     confidence, conf_out; mod_llr, llr_out; anchored=score threshold, anchored_out; anchored_mod, anchored_mod_out; variants={target:
-    [alt units as configured]}, variants_out; renorm=share threshold, renorm_out; tracts, tracts_out; flank_mod, flank_mod_out; the
+    [alt units as configured]}, variants_out; renorm=share threshold, renorm_out; tracts, tracts_out; tract_positions (with tracts), tract_positions_out; flank_mod, flank_mod_out; the
     score rows of a scan: scores_out); any other keyword is a TypeError.  OUTPUTS says how the counter is asked for each of them, which
     of them a scan excludes (ValueError) and how the value of a read is taken from its result, which is normalised to a Detected record
     (as_detected).  Single process: the rows of an output go to its file with the count rows; they are collected in stats[its `stat`
@@ -924,19 +952,20 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
     if stats is None:
         stats = {}
     stats.setdefault("failed", 0)
-    files = dict({o.name: asked.pop(o.file, None) for o in OUTPUTS}, rows=out)
-    unknown = set(asked) - {o.name for o in OUTPUTS if o.ask}
+    files = dict({o.name: asked.pop(o.file, None) for o in ALL_OUTPUTS}, rows=out)
+    unknown = set(asked) - {o.name for o in ALL_OUTPUTS if o.ask}
     if unknown:
         raise TypeError("run_count() got an unexpected keyword argument '%s'" % sorted(unknown)[0])
     asked['scores'] = bool(scan and scan["scores"])
-    on = [o for o in OUTPUTS if _asked(o, asked.get(o.name))]
+    on = [o for o in ALL_OUTPUTS if _asked(o, asked.get(o.name))]
+    riding = {o.rides[0]: {o.rides[1]: True} for o in on if o.rides}
     for o in on:
         refused = o.refuse and o.refuse(asked, scan)
         if refused:
             raise ValueError(refused)
     if out is not None:
         print('\t'.join(HEADER), file=out)
-    for o in OUTPUTS:
+    for o in ALL_OUTPUTS:
         stats.setdefault(o.stat, [])
         if files[o.name] is not None:
             print('\t'.join(o.header(scan)), file=files[o.name])
@@ -944,7 +973,7 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
     extras = {}
     for o in on:
         if o.ask == 'switch':
-            getattr(counter, 'set_' + o.name)(asked[o.name] if o.level else True)
+            getattr(counter, 'set_' + o.name)(asked[o.name] if o.level else True, **riding.get(o.name, {}))
         elif o.ask == 'keyword':
             extras[o.name] = asked[o.name] if o.level else True
         if o.ask == 'switch' or o.level:
@@ -1028,7 +1057,7 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
             sink, failed = in_flight.popleft().result()          # re-raises DeviceFault from the engine thread
             stats["failed"] += failed
             rows.extend(sink['rows'])
-            for o in OUTPUTS:
+            for o in ALL_OUTPUTS:
                 stats[o.stat].extend(sink[o.name])
             for name, f in files.items():
                 if f is not None:
@@ -1168,6 +1197,8 @@ def plot(argv):
     parser.add_argument("--extension", type=float, default=0.1, help="Extension as fraction of repeat signal around STR region to plot")
     parser.add_argument("--zoom", type=int, default=500, help="Region around prefix and suffix to plot")
     parser.add_argument("--units", default=None, metavar="FILE", help="Repeat-unit positions from `count --units`: marked in the panels")
+    parser.add_argument("--tract-positions", dest="tract_positions", default=None, metavar="FILE",
+                        help="Unit positions per tract from `count --tract-positions`: marked in the panels, one tick colour per tract")
     parser.add_argument("--log_level", default='warning', choices=LEVELS, help="Log level")
     args = parser.parse_args(argv)
     log = Log(args.log_level)
@@ -1184,6 +1215,10 @@ def plot(argv):
     if args.units:
         with open(args.units) as f:
             unit_pos = {(r[0], r[1], r[2]): r[4] for r in parse_units(f)}
+    tract_pos = None
+    if args.tract_positions:
+        with open(args.tract_positions) as f:
+            tract_pos = {(r[0], r[1], r[2]): r[4][2] for r in tracts_mod.parse_positions(f) if r[4] is not None and r[4][2] is not None}
     made = []
     with (open(args.counts) if args.counts else sys.stdin) as stream:
         for row in plotting.parse_counts(stream):
@@ -1195,11 +1230,13 @@ def plot(argv):
             else:
                 import matplotlib.pyplot as plt
                 fig = plt.figure(figsize=(args.width, args.height), dpi=args.dpi, layout="constrained")
-            if unit_pos is None:
-                plotting.draw(fig, raw, row, extension=args.extension, zoom=args.zoom)
-            else:
-                plotting.draw(fig, raw, row, extension=args.extension, zoom=args.zoom,
-                              units=unit_pos.get((row.read_id, row.target, row.strand), []))
+            key = (row.read_id, row.target, row.strand)
+            extra = {}
+            if unit_pos is not None:
+                extra['units'] = unit_pos.get(key, [])
+            if tract_pos is not None:
+                extra['tract_positions'] = tract_pos.get(key, ())          # (a read without positions: every Axes carries an empty tuple)
+            plotting.draw(fig, raw, row, extension=args.extension, zoom=args.zoom, **extra)
             if args.output:
                 path = os.path.join(args.output, plotting.figure_name(row, args.format))
                 fig.savefig(path); made.append(path)

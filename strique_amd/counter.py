@@ -81,11 +81,17 @@ def _fetch_renorm(counter, reads, idx):
 
 def _fetch_tracts(counter, reads, idx):
     out = []
-    for i, t in zip(idx, counter.ctx.batch_fetch_tracts()):
+    recs = counter.ctx.batch_fetch_tracts()
+    # set_tracts(True, positions=True): the positions come with the records (None: back-pointers over the budget)
+    positions = counter.ctx.batch_fetch_tract_positions() if counter.tract_positions else [None] * len(recs)
+    for i, t, p in zip(idx, recs, positions):
         rec = None
         if int(t['status']) == 0:
             strand = counter.tract_models[reads[i][0]][1]
-            rec = (tracts_mod.configured_order([int(c) for c in t['count'][:int(t['n_tracts'])]], strand), float(t['log_p']))
+            k = int(t['n_tracts'])
+            rec = (tracts_mod.configured_order([int(c) for c in t['count'][:k]], strand), float(t['log_p']))
+            if counter.tract_positions:
+                rec += (tracts_mod.configured_order(p[1][:k], strand) if p[0] == 0 else None,)
         out.append(rec)
     return out
 
@@ -149,6 +155,7 @@ class repeatCounter(object):
         self._tract_src = {}
         self.tract_models = {}
         self.tracts = False            # set_tracts
+        self.tract_positions = False   # set_tracts(True, positions=True)
         self._renorm_done = set()      # classifiers whose tables are registered
         # flank methylation calls: the whole flanks of every classifier as its strand reads them, its strand, and the classifiers whose
         # models are registered or were refused ({target_id: message}); built when the switch first meets them, like the anchored models
@@ -226,16 +233,20 @@ class repeatCounter(object):
             self.ctx.target_set_tracts(tid, m.model_id, m.n_tracts, m.count_bias)
             self.tract_models[tid] = (m, strand)
 
-    def set_tracts(self, on):
+    def set_tracts(self, on, positions=False):
         """on: detect and detect_batch also decode the compound model of every read of a target added with tracts=(units, linkers)
         (strique_amd.tracts states the rule) and report one more element per read, behind all others: None -- the read was not
         decoded, its window has 2^21 samples or more, the compound model found no path, or its target has no tracts -- or (counts,
         log_p): the unit count of every tract in the order the definition was configured in, on either strand, and the
         log-probability of the compound model's best path.  records=True: Detected.tracts.  A switch of the counter, like
-        set_variants.  ValueError when no target was added with tracts.  Not with scan_batch."""
+        set_variants.  ValueError when no target was added with tracts.  Not with scan_batch.
+        positions=True: the element is (counts, log_p, positions) -- positions a tuple of one ascending np.int64 array of raw-signal
+        samples per tract, in configured order like the counts (count_j - bias_j of them: strique_amd.tracts states the rule), or
+        None for a read whose back-pointers exceed STRQ_TRACT_POS_WS_BYTES.  Without it the element is exactly (counts, log_p)."""
         if on and not self._tract_src:
             raise ValueError("RepeatCounter: tracts needs a target added with tracts=(units, linkers).")
         self.tracts = bool(on)
+        self.tract_positions = bool(on and positions)
 
     def _ensure_renorm(self):
         """The tables of the second normalisation step for every classifier that has none yet (strique_amd.renorm.tables)."""
@@ -389,7 +400,8 @@ class repeatCounter(object):
         count_v = len(pattern) + count_bias is an estimate on the scale of the tuple's count, not equal to it in general.
         With set_anchored_mod(True) and anchored=m: the methylation call of the read, (pattern, llr) or None, directly behind the
         anchored element -- see set_anchored_mod.
-        With set_tracts(True) (a counter with a target added with tracts=): one last element, None or (counts, log_p) -- see set_tracts.
+        With set_tracts(True) (a counter with a target added with tracts=): one last element, None or (counts, log_p) -- see set_tracts;
+        (counts, log_p, positions) with set_tracts(True, positions=True).
         Order of the elements: (tuple[, positions][, conf][, llr][, anchored][, anchored_mod][, variants][, tracts][, flank_mod]); without any of them the bare tuple.
         records=True: a list of Detected records instead (the fields that were not asked for None; `anchored` the record of every
         read, whatever its kind: (kind number, status, count, log_p, begin, end, free_samples))."""
@@ -420,6 +432,7 @@ class repeatCounter(object):
     @contextlib.contextmanager
     def _switches(self, request):
         """The passes of `request` ({name: value}, see PASSES) are on inside the block, and every pass is off after it."""
+        with_positions = 'tracts' in request and self.tract_positions      # (rides on the tracts switch; a context is asked only then)
         try:
             # inside the try: set_mod_llr refuses a modification model the scoring pass does not cover, and the switches a
             # failed call leaves behind must not stay on for the next caller of a shared context
@@ -428,8 +441,12 @@ class repeatCounter(object):
                     if p.ensure:
                         getattr(self, p.ensure)()
                     getattr(self.ctx, 'set_' + p.name)(True, *((request[p.name],) if p.level else ()))
+            if with_positions:
+                self.ctx.set_tract_positions(True)
             yield
         finally:
+            if with_positions:
+                self.ctx.set_tract_positions(False)
             for p in reversed(PASSES):
                 getattr(self.ctx, 'set_' + p.name)(False)
 

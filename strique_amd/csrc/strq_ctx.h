@@ -187,6 +187,14 @@ int detect_drain(strq_ctx* c);              // rows of every detect sub-batch in
 int viterbi_launch_status(int vrc);
 // the forward image of a model (HostModel::fwd_dev), built if it is not there; STRQ_ERR_UNSUPPORTED (c->err says why) for a model without one
 int forward_model(strq_ctx* c, HostModel* hm);
+// Unit positions of the tracts of decoded windows (strq_set_tract_positions, strq_viterbi_tract_positions; strq_detect_api.hip): every
+// window once more with back-pointers, traced back and scanned (tract_scan_kernel), in pieces of at most STRQ_TRACT_POS_WS_BYTES of
+// back-pointers.  task: the window as its count decode had it (bp is set here); n[j]: the visits of tract j that decode found; base:
+// what position 0 of the window is reported as.  status[i]: 0 positions in pos[3 i + j] (model order), 2 the window's back-pointers
+// alone exceed the budget (not traced).  stats (or null): windows traced, kernels launched, peak back-pointer bytes of a piece.
+struct TractPosWindow { VitTask task; const HostModel* hm; int64_t base; int64_t n[3]; };
+struct TractPosOut { std::vector<int32_t> status; std::vector<std::vector<int64_t>> pos; };
+int tract_positions(strq_ctx* c, const std::vector<TractPosWindow>& w, TractPosOut& out, double* stats);
 void host_stats_batch(const double* signals, const int64_t* offsets, int64_t n_reads, bool want_raw, double* out,
                       const double* const* reads = nullptr);   // host_stats.hip; reads: one buffer per read instead of `signals`
 }

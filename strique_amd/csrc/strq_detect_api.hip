@@ -131,6 +131,7 @@ struct DetectState {
     DevBuf conf_task;                    // forward pass (run_conf_pass): tasks, model images, c0, results, order
     DevBuf fmod_ws, fmod_bp;             // flank methylation calls (run_flank_mod_pass): tasks, stretches and paths of a piece; its back-pointers
     DevBuf tract_ws, tract_task;         // tract pass (run_tract_pass): geometry and conditioning rows of a sub-batch; tasks, results, their reads and models
+    DevBuf tpos_task, tpos_bp, tpos_path, tpos_pool;      // tract positions (tract_positions): tasks and results of a piece, its back-pointers, state paths, positions
     DevBuf anch_ws, anch_task;           // anchored pass (run_anchored_pass): geometry, conditioning rows and kinds of a sub-batch; tasks, results, their reads and models
     hipEvent_t amod_ev[2] = {};          // methylation calls of anchored reads (run_anchored_mod): their own bracket, inside the anchored pass
     // renorm (run_renorm_part): the tables of the targets, the grid and the shares, the histograms and the per-read table rows of a sub-batch
@@ -1021,6 +1022,100 @@ static int upload_slot_rows(strq_ctx* c, const DetectState::Slot& sl, DevBuf& bu
     return STRQ_OK;
 }
 
+// Unit positions of the tracts of decoded windows (strq_ctx.h states the interface; strique_amd/tracts.py the rule): the windows of a
+// piece grouped by kernel shape, decoded with back-pointers, traced back into a zeroed path buffer and scanned with one ballot per tract
+// (tract_scan_kernel).  One read-back and one wait per piece; the buffers are the detect state's own and exist only once this ran.
+int tract_positions(strq_ctx* c, const std::vector<TractPosWindow>& w, TractPosOut& out, double* stats)
+{
+    DetectState* d = dstate(c);
+    hipStream_t st = c->stream;
+    const size_t nw = w.size();
+    out.status.assign(nw, 0); out.pos.assign(3 * nw, std::vector<int64_t>());
+    size_t budget = (size_t)8 << 30;
+    if (const char* e = strq::opt("STRQ_TRACT_POS_WS_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
+    struct W { int i; int shape; size_t bytes; };
+    std::vector<W> ws;
+    for (size_t i = 0; i < nw; ++i) {
+        const VitModel& h = w[i].hm->h;
+        const int shape = vit_shape_for(h, VIT_BACKPTR);
+        if (shape < 0 || !vit_mode_ok(shape, VIT_BACKPTR) || !h.tract_inc) { c->err = "tract positions: the model has no back-pointer decode"; return STRQ_ERR_UNSUPPORTED; }
+        // back-pointers: uint16 per (time step, state); every window starts on a 16-byte boundary
+        const size_t bytes = ((size_t)(w[i].task.T + 1) * (size_t)h.n_states * 2 + 15) & ~(size_t)15;
+        if (bytes > budget) { out.status[i] = 2; continue; }
+        ws.push_back({(int)i, shape, bytes});
+    }
+    for (size_t c0 = 0; c0 < ws.size();) {
+        size_t c1 = c0, bytes = 0;
+        while (c1 < ws.size() && bytes + ws[c1].bytes <= budget) bytes += ws[c1++].bytes;          // (every window fits alone)
+        const int m = (int)(c1 - c0);
+        std::vector<GroupItem> items((size_t)m);
+        size_t path_n = 0, pos_n = 0;
+        for (int k = 0; k < m; ++k) {
+            const TractPosWindow& x = w[(size_t)ws[c0 + (size_t)k].i];
+            items[(size_t)k] = {0, ws[c0 + (size_t)k].shape, x.hm->h.n_cells};
+            path_n += (size_t)x.task.T;
+            for (int j = 0; j < x.hm->n_tracts; ++j) pos_n += (size_t)x.n[j];
+        }
+        const Grouping G = group_items(items);
+        Carve lay;
+        const size_t o_vt = lay.add<VitTask>((size_t)m), o_vr = lay.add<VitResult>((size_t)m), o_paths = lay.add<int32_t*>((size_t)m),
+                     o_ts = lay.add<TractScanTask>((size_t)m), o_bad = lay.add<int32_t>((size_t)m), o_order = lay.add<int>((size_t)m);
+        STRQ_HIP(c, d->tpos_task.reserve(lay.total() + 64));
+        void* tb = d->tpos_task.p;
+        VitTask* d_vt = Carve::at<VitTask>(tb, o_vt); VitResult* d_vr = Carve::at<VitResult>(tb, o_vr); int32_t** d_paths = Carve::at<int32_t*>(tb, o_paths);
+        TractScanTask* d_ts = Carve::at<TractScanTask>(tb, o_ts); int32_t* d_bad = Carve::at<int32_t>(tb, o_bad); int* d_order = Carve::at<int>(tb, o_order);
+        STRQ_HIP(c, d->tpos_bp.reserve(bytes));
+        STRQ_HIP(c, d->tpos_path.reserve(path_n * 4 + 64));
+        STRQ_HIP(c, d->tpos_pool.reserve(pos_n * 8 + 64));
+        std::vector<VitTask> tv((size_t)m); std::vector<int32_t*> pv((size_t)m); std::vector<TractScanTask> sv((size_t)m);
+        std::vector<int> win_of((size_t)m); std::vector<size_t> pos_off((size_t)m);
+        size_t wo = 0, po = 0, xo = 0;
+        for (int at = 0; at < m; ++at) {          // in task order: the back-pointers, the paths and the positions lie in that order too
+            const W& ww = ws[c0 + (size_t)G.order[(size_t)at]];
+            const TractPosWindow& x = w[(size_t)ww.i];
+            VitTask t = x.task;
+            t.bp = reinterpret_cast<uint16_t*>(d->tpos_bp.as<char>() + wo); wo += ww.bytes;
+            if (wo > d->tpos_bp.cap) { c->err = "tract positions: workspace"; return STRQ_ERR_NOMEM; }
+            pv[(size_t)at] = d->tpos_path.as<int32_t>() + po; po += (size_t)t.T;
+            TractScanTask s; std::memset(&s, 0, sizeof(s));
+            s.path = pv[(size_t)at]; s.tract_inc = x.hm->h.tract_inc; s.result = d_vr + at; s.out = d->tpos_pool.as<int64_t>() + xo;
+            s.T = t.T; s.base = x.base; s.n_tracts = x.hm->n_tracts; s.n_states = x.hm->h.n_states; s.bad = d_bad + at;
+            pos_off[(size_t)at] = xo;
+            for (int j = 0; j < x.hm->n_tracts; ++j) { s.off[j] = (int64_t)(xo - pos_off[(size_t)at]); s.n[j] = x.n[j]; xo += (size_t)x.n[j]; }
+            tv[(size_t)at] = t; sv[(size_t)at] = s; win_of[(size_t)at] = ww.i;
+        }
+        STRQ_HIP(c, hipMemcpyAsync(d_vt, tv.data(), (size_t)m * sizeof(VitTask), hipMemcpyHostToDevice, st));
+        STRQ_HIP(c, hipMemcpyAsync(d_paths, pv.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
+        STRQ_HIP(c, hipMemcpyAsync(d_ts, sv.data(), (size_t)m * sizeof(TractScanTask), hipMemcpyHostToDevice, st));
+        STRQ_HIP(c, hipMemsetAsync(d_bad, 0, (size_t)m * 4, st));
+        if (path_n) STRQ_HIP(c, hipMemsetAsync(d->tpos_path.p, 0, path_n * 4, st));      // a traceback that stops early leaves valid states behind
+        double launches = 0;
+        const GroupHook trace = [&](const VitGroup& g) -> int {
+            if (launch_vit_traceback(st, d_vt + g.first, d_vr + g.first, d_paths + g.first, g.count)) { c->err = "tract positions: traceback launch failed"; return STRQ_ERR_DEVICE; }
+            launches += 1;
+            return STRQ_OK;
+        };
+        if (const int grc = launch_groups(c, st, G.groups, {d_vt, d_vr, d_order, {VIT_BACKPTR}, "tract positions: ", false, &launches, nullptr, trace})) return grc;
+        if (launch_tract_scan(st, d_ts, m)) { c->err = "tract positions: scan launch failed"; return STRQ_ERR_DEVICE; }
+        launches += 1;
+        std::vector<int64_t> pos(xo + 1); std::vector<int32_t> bad((size_t)m);
+        if (xo) STRQ_HIP(c, hipMemcpyAsync(pos.data(), d->tpos_pool.p, xo * 8, hipMemcpyDeviceToHost, st));
+        STRQ_HIP(c, hipMemcpyAsync(bad.data(), d_bad, (size_t)m * 4, hipMemcpyDeviceToHost, st));
+        STRQ_HIP(c, hipStreamSynchronize(st));
+        for (int at = 0; at < m; ++at) {
+            if (bad[(size_t)at]) { c->err = "tract positions: the back-pointer decode of a window disagrees with its count decode"; return STRQ_ERR_DEVICE; }
+            const TractScanTask& s = sv[(size_t)at];
+            for (int j = 0; j < s.n_tracts; ++j) {
+                const int64_t* from = pos.data() + pos_off[(size_t)at] + s.off[j];
+                out.pos[3 * (size_t)win_of[(size_t)at] + (size_t)j].assign(from, from + s.n[j]);
+            }
+        }
+        if (stats) { stats[0] += m; stats[1] += launches; stats[2] = std::max(stats[2], (double)bytes); }
+        c0 = c1;
+    }
+    return STRQ_OK;
+}
+
 // Tract counts of the reads of one sub-batch (strq_set_tracts): every read whose gate passed, that was normalised, whose flanked decode
 // found a path and whose target has a compound model is decoded once more with that model, on the window of the count decode.  Runs
 // on the context's stream when the rows of the sub-batch are taken, like the forward pass: the geometry and the conditioning rows go
@@ -1069,8 +1164,10 @@ static int run_tract_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
     if (launch_tract_tasks(st, ta)) { c->err = "tracts: task launch failed"; return STRQ_ERR_DEVICE; }
     d->stat(PASS_TRACTS, TRACT_LAUNCHES) += 1;
     if (const int grc = launch_groups(c, st, D.G.groups, {d_vt, d_vr, d_order, {VIT_COUNT}, "tracts: ", true, &d->stat(PASS_TRACTS, TRACT_LAUNCHES)})) return grc;
-    std::vector<VitResult> vr((size_t)m);
+    std::vector<VitResult> vr((size_t)m); std::vector<VitTask> tv(sl.ex.tpos ? (size_t)m : 0);
     STRQ_HIP(c, hipMemcpyAsync(vr.data(), d_vr, (size_t)m * sizeof(VitResult), hipMemcpyDeviceToHost, st));
+    // (the positions start from the tasks as tract_task_kernel wrote them: they come back in the same wait)
+    if (sl.ex.tpos) STRQ_HIP(c, hipMemcpyAsync(tv.data(), d_vt, (size_t)m * sizeof(VitTask), hipMemcpyDeviceToHost, st));
     if (const int rc = pass_stop(c, pass_ev(d), d->stats[PASS_TRACTS])) return rc;
     for (int at = 0; at < m; ++at) {
         const int i = read_of[(size_t)at];
@@ -1086,7 +1183,26 @@ static int run_tract_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
         } else d->stat(PASS_TRACTS, TRACT_FAILED) += 1;
         B.tracts[(size_t)(r0 + i)] = o;
     }
-    return STRQ_OK;
+    if (!sl.ex.tpos) return STRQ_OK;
+    // Unit positions of the tracts (strq_set_tract_positions): the windows of status 0 once more, their counters sizing the pool
+    std::vector<TractPosWindow> pw; std::vector<int> pw_read;
+    for (int at = 0; at < m; ++at) {
+        if (vr[(size_t)at].status != 0) continue;
+        const int i = read_of[(size_t)at];
+        TractPosWindow x; x.task = tv[(size_t)at]; x.hm = c->models[target_of(d, r0 + i).tract_model_id]; x.base = h.geom[i].prefix_begin;
+        for (int j = 0; j < 3; ++j) x.n[j] = (int64_t)(((uint64_t)vr[(size_t)at].counted >> (VIT_TRACT_BITS * j)) & (((uint64_t)1 << VIT_TRACT_BITS) - 1));
+        pw.push_back(x); pw_read.push_back(i);
+    }
+    if (pw.empty()) return STRQ_OK;
+    if (const int rc = pass_start(c, pass_ev(d))) return rc;
+    TractPosOut po;
+    if (const int rc = tract_positions(c, pw, po, d->stats[PASS_TPOS].v)) return rc;
+    for (size_t k = 0; k < pw.size(); ++k) {
+        const size_t r = (size_t)(r0 + pw_read[k]);
+        B.tpos_status[r] = po.status[k];
+        for (int j = 0; j < 3; ++j) B.tpos[3 * r + (size_t)j].swap(po.pos[3 * k + (size_t)j]);
+    }
+    return pass_stop(c, pass_ev(d), d->stats[PASS_TPOS]);
 }
 
 // Methylation calls for the CpG groups of the flanks of one sub-batch (strq_set_flank_mod; strique_amd/flank_mod.py states the rule):
@@ -2242,6 +2358,17 @@ int run_range(strq_ctx* c, DetectState* d, int64_t first, int64_t last)
         }
     }
     if (d->extras.tracts) B.size_tracts();
+    if (d->extras.tpos) {
+        // (the positions hang on the tract records); nothing is launched for a call whose compound models cannot be traced back
+        if (!d->extras.tracts) { c->err = "tract-positions: needs the tract pass (strq_set_tracts)"; return STRQ_ERR_ARG; }
+        for (int64_t r = first; r < last; ++r) {
+            const Target& t = d->targets[B.target_given.empty() ? B.target[(size_t)r] : B.target_given[(size_t)r]];
+            if (t.tract_model_id < 0) continue;
+            const VitModel& mh = c->models[t.tract_model_id]->h;
+            if (!vit_mode_ok(vit_shape_for(mh, VIT_BACKPTR), VIT_BACKPTR)) { c->err = "tract-positions: a target's compound model has no back-pointer decode"; return STRQ_ERR_UNSUPPORTED; }
+        }
+        B.size_tpos();
+    }
     if (d->extras.fmod) B.size_fmod();
     if (d->extras.renorm) {
         // nothing is launched for a call whose reads the pass could not fit
@@ -2693,6 +2820,35 @@ int strq_last_tracts(strq_ctx* c, double* out4)
 {
     STRQ_ENTER(c);
     return last_pass(c, PASS_TRACTS, out4);
+}
+
+int strq_set_tract_positions(strq_ctx* c, int32_t on)
+{
+    STRQ_ENTER(c);
+    return set_extra(c, on, PASS_TPOS);
+}
+
+int strq_batch_fetch_tract_positions(strq_ctx* c, int32_t* pos_status, int64_t* off, int64_t* pool, int64_t pool_cap)
+{
+    STRQ_ENTER(c);
+    if (!off) return STRQ_ERR_ARG;
+    DetectState* d = dstate(c);
+    if (const int rc = fetch_begin(c, d, PASS_TPOS)) return rc;
+    const Batch& B = d->batch;
+    const int64_t n = (int64_t)B.tpos.size();          // three entries per read
+    const int64_t done = pack_ragged(n, off, pool != nullptr, pool_cap, [&](int64_t i) { return (int64_t)B.tpos[(size_t)i].size(); }, [&](int64_t i, int64_t pos) {
+        const std::vector<int64_t>& u = B.tpos[(size_t)i];
+        if (!u.empty()) std::memcpy(pool + pos, u.data(), u.size() * 8);
+    });
+    if (pos_status) for (int64_t i = 0; i < done / 3; ++i) pos_status[i] = B.tpos_status[(size_t)i];          // (of the reads that fitted)
+    if (done < n) { c->err = "tract position pool too small"; return STRQ_ERR_ARG; }
+    return STRQ_OK;
+}
+
+int strq_last_tract_positions(strq_ctx* c, double* out4)
+{
+    STRQ_ENTER(c);
+    return last_pass(c, PASS_TPOS, out4);
 }
 
 int strq_target_set_flank_mod(strq_ctx* c, int32_t target_id, int32_t which, int32_t profile_model_id, int32_t flank_len,

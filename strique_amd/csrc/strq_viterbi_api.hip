@@ -948,10 +948,11 @@ int strq_model_set_tracts(strq_ctx* c, int32_t model_id, int32_t n_tracts, const
     return STRQ_OK;
 }
 
-int strq_viterbi_tracts(strq_ctx* c, int32_t model_id, int64_t n_seq, const double* x, const int64_t* x_off,
-                        double* logp, int64_t* counts, int32_t* status)
+// strq_viterbi_tracts and strq_viterbi_tract_positions: the tract decode of the windows; `keep` (or null) takes the tasks as they were
+// launched and their results
+static int viterbi_tracts(strq_ctx* c, int32_t model_id, int64_t n_seq, const double* x, const int64_t* x_off,
+                          double* logp, int64_t* counts, int32_t* status, std::pair<std::vector<VitTask>, std::vector<VitResult>>* keep)
 {
-    STRQ_ENTER(c);
     if (model_id < 0 || model_id >= (int32_t)c->models.size() || !c->models[model_id] || n_seq < 0 || n_seq > 8192 || (n_seq > 0 && !x_off)) { c->err = "bad argument"; return STRQ_ERR_ARG; }
     HostModel* hm = c->models[model_id];
     if (!hm->h.tract_inc) { c->err = "the model has no tracts (strq_model_set_tracts)"; return STRQ_ERR_ARG; }
@@ -991,6 +992,47 @@ int strq_viterbi_tracts(strq_ctx* c, int32_t model_id, int64_t n_seq, const doub
         if (status) status[i] = r.status;
         if (counts) for (int j = 0; j < VIT_TRACTS_MAX; ++j) counts[3 * i + j] = (int64_t)((pay >> (VIT_TRACT_BITS * j)) & (((uint64_t)1 << VIT_TRACT_BITS) - 1));
     }
+    if (keep) { keep->first.swap(tasks); keep->second.swap(res); }
+    return STRQ_OK;
+}
+
+int strq_viterbi_tracts(strq_ctx* c, int32_t model_id, int64_t n_seq, const double* x, const int64_t* x_off,
+                        double* logp, int64_t* counts, int32_t* status)
+{
+    STRQ_ENTER(c);
+    return viterbi_tracts(c, model_id, n_seq, x, x_off, logp, counts, status, nullptr);
+}
+
+int strq_viterbi_tract_positions(strq_ctx* c, int32_t model_id, int64_t n_seq, const double* x, const int64_t* x_off,
+                                 double* logp, int64_t* counts, int32_t* status, int64_t* pos_off, int64_t* pool, int64_t pool_cap)
+{
+    STRQ_ENTER(c);
+    if (!pos_off || pool_cap < 0 || (pool_cap > 0 && !pool)) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    std::pair<std::vector<VitTask>, std::vector<VitResult>> kept;
+    std::vector<int32_t> st_own((size_t)std::max<int64_t>(n_seq, 0));
+    if (const int rc = viterbi_tracts(c, model_id, n_seq, x, x_off, logp, counts, st_own.data(), &kept)) return rc;
+    pos_off[0] = 0;
+    if (n_seq == 0) return STRQ_OK;
+    const HostModel* hm = c->models[model_id];
+    std::vector<TractPosWindow> pw; std::vector<int64_t> win;
+    for (int64_t i = 0; i < n_seq; ++i) {
+        const VitResult& r = kept.second[(size_t)i];
+        if (r.status != 0) continue;
+        TractPosWindow w; w.task = kept.first[(size_t)i]; w.hm = hm; w.base = 0;
+        for (int j = 0; j < 3; ++j) w.n[j] = (int64_t)(((uint64_t)r.counted >> (VIT_TRACT_BITS * j)) & (((uint64_t)1 << VIT_TRACT_BITS) - 1));
+        pw.push_back(w); win.push_back(i);
+    }
+    TractPosOut po;
+    if (!pw.empty()) { if (const int rc = tract_positions(c, pw, po, nullptr)) return rc; }
+    std::vector<const std::vector<int64_t>*> of((size_t)n_seq * 3, nullptr);
+    for (size_t k = 0; k < pw.size(); ++k) {
+        if (po.status[k] == 2) st_own[(size_t)win[k]] = 4;
+        for (int j = 0; j < 3; ++j) of[3 * (size_t)win[k] + (size_t)j] = &po.pos[3 * k + (size_t)j];
+    }
+    if (status) std::memcpy(status, st_own.data(), (size_t)n_seq * 4);
+    const int64_t done = pack_ragged(3 * n_seq, pos_off, pool != nullptr, pool_cap, [&](int64_t i) { return of[(size_t)i] ? (int64_t)of[(size_t)i]->size() : 0; },
+                                     [&](int64_t i, int64_t pos) { if (of[(size_t)i] && !of[(size_t)i]->empty()) std::memcpy(pool + pos, of[(size_t)i]->data(), of[(size_t)i]->size() * 8); });
+    if (done < 3 * n_seq) { c->err = "tract position pool too small"; return STRQ_ERR_ARG; }
     return STRQ_OK;
 }
 

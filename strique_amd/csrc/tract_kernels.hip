@@ -31,4 +31,48 @@ int launch_tract_tasks(hipStream_t s, const TractTaskArgs& a)
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
+// One wave per window: 64 observations per round, the counted ones of every tract compacted with a ballot (ascending order).
+__global__ void __launch_bounds__(256) tract_scan_kernel(const TractScanTask* __restrict__ tasks, int n_tasks)
+{
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= n_tasks) return;
+    const TractScanTask tk = tasks[i];
+    const VitResult* r = static_cast<const VitResult*>(tk.result);
+    if (r->status != 0) { if (lane == 0) *tk.bad = 1; return; }
+    const int K = tk.n_tracts < VIT_TRACTS_MAX ? tk.n_tracts : VIT_TRACTS_MAX;
+    int64_t k[VIT_TRACTS_MAX] = {0, 0, 0};
+    const uint64_t below = ((uint64_t)1 << lane) - 1ull;
+    for (int64_t t0 = 0; t0 < tk.T; t0 += 64) {
+        const int64_t t = t0 + lane;
+        int tract = -1;
+        if (t < tk.T) {
+            const int32_t s = tk.path[t];
+            const uint64_t inc = s >= 0 && s <= tk.n_states ? tk.tract_inc[s] : 0;
+            if (inc) tract = (int)(__builtin_ctzll(inc) / VIT_TRACT_BITS);
+        }
+#pragma unroll
+        for (int j = 0; j < VIT_TRACTS_MAX; ++j) {
+            if (j >= K) break;
+            const bool hit = tract == j;
+            const uint64_t m = __builtin_amdgcn_ballot_w64(hit);
+            const int64_t at = k[j] + __builtin_popcountll(m & below);
+            if (hit && at < tk.n[j]) tk.out[tk.off[j] + at] = tk.base + t;
+            k[j] += __builtin_popcountll(m);
+        }
+    }
+    if (lane == 0) {
+        bool ok = true;
+        for (int j = 0; j < K; ++j) ok = ok && k[j] == tk.n[j];
+        if (!ok) *tk.bad = 1;
+    }
+}
+
+int launch_tract_scan(hipStream_t s, const TractScanTask* tasks, int n)
+{
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(tract_scan_kernel, dim3((n + 3) / 4), dim3(256), 0, s, tasks, n);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
 }  // namespace strq

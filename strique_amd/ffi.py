@@ -455,6 +455,19 @@ class Context(object):
                                                   _ptr(logp), _ptr(counts), _ptr(status)))
         return logp, counts, status
 
+    def viterbi_tract_positions(self, model_id, xs):
+        """strq_viterbi_tract_positions: viterbi_tracts plus the positions.  Returns (logp[], counts (n, 3) int64, status[],
+        positions): positions[i] a tuple of three ascending np.int64 arrays of observation indices, tract by tract in model order
+        (empty beyond the model's tracts, without a path, and for status 4: the window's back-pointers exceed
+        STRQ_TRACT_POS_WS_BYTES -- counts valid, not traced)."""
+        n = len(xs)
+        x, off = _offsets(xs, np.float64)
+        logp = np.zeros(n); counts = np.zeros((n, 3), np.int64); status = np.zeros(max(1, n), np.int32)
+        pos_off = np.zeros(3 * n + 1, np.int64); pool = np.zeros(max(1, int(off[-1])), np.int64)      # (a tract emits each observation at most once)
+        self._check(self._lib.strq_viterbi_tract_positions(self._h, ctypes.c_int32(model_id), ctypes.c_int64(n), _ptr(x), _ptr(off), _ptr(logp), _ptr(counts),
+                                                           _ptr(status), _ptr(pos_off), _ptr(pool), ctypes.c_int64(len(pool))))
+        return logp, counts, status[:n], [tuple(pool[pos_off[3 * i + j]:pos_off[3 * i + j + 1]].copy() for j in range(3)) for i in range(n)]
+
     def debug_tract_shape(self):
         """strq_debug_tract_shape: the kernel shape id of this context's last tract launch (-1: none yet)."""
         shape = ctypes.c_int32(-1)
@@ -642,6 +655,27 @@ class Context(object):
     def last_tracts(self):
         """The tract pass of the last run call (strq_last_tracts): {'ms', 'windows' (decoded), 'launches', 'failed' (status 2 or 3)}."""
         return self._last("tracts", ("ms", "windows", "launches", "failed"))
+
+    def set_tract_positions(self, on):
+        """strq_set_tract_positions: later run calls with set_tracts on also trace every tract window of status 0 back
+        (batch_fetch_tract_positions)."""
+        self._switch("tract_positions", on)
+
+    def batch_fetch_tract_positions(self):
+        """Tract positions of the last batch (strq_batch_fetch_tract_positions): per read (pos_status, positions) -- pos_status 0
+        and a tuple of three ascending np.int64 arrays of raw-signal sample indices in model order (empty beyond the model's
+        tracts), or 1 (the tract record's status is not 0) / 2 (back-pointers over the budget) and None."""
+        n = getattr(self, '_n_batch', 0)
+        off = np.zeros(3 * n + 1, np.int64); ps = np.zeros(max(1, n), np.int32)
+        self._check(self._lib.strq_batch_fetch_tract_positions(self._h, _ptr(ps), _ptr(off), None, ctypes.c_int64(0)))
+        pool = np.zeros(max(1, int(off[-1])), np.int64)
+        self._check(self._lib.strq_batch_fetch_tract_positions(self._h, _ptr(ps), _ptr(off), _ptr(pool), ctypes.c_int64(len(pool))))
+        return [(int(ps[i]), tuple(pool[off[3 * i + j]:off[3 * i + j + 1]].copy() for j in range(3)) if ps[i] == 0 else None) for i in range(n)]
+
+    def last_tract_positions(self):
+        """The tract-position pass of the last run call (strq_last_tract_positions): {'ms', 'windows' (traced), 'launches', 'bp_bytes'
+        (peak back-pointer bytes of a piece)}."""
+        return self._last("tract_positions", ("ms", "windows", "launches", "bp_bytes"), floats=("ms", "bp_bytes"))
 
     def target_set_flank_mod(self, target_id, which, profile_model_id, flank_len, column_of, groups):
         """strq_target_set_flank_mod: the models of flank `which` (0 prefix, 1 suffix, as the strand of the target reads it) --

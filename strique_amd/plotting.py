@@ -68,11 +68,17 @@ def smooth(raw):
 PANELS = (("overview", "whole"), ("left", "begin"), ("right", "end"))
 
 
-def draw(fig, raw, row, extension=0.1, zoom=500, units=None):
+TRACT_COLOURS = ("tab:orange", "tab:purple", "tab:brown")          # one tick colour per tract, in configured order
+
+
+def draw(fig, raw, row, extension=0.1, zoom=500, units=None, tract_positions=None):
     """One read on `fig` (a matplotlib Figure).  Returns {panel: Axes}; every Axes carries `strique_span`, the
     (first, past) sample pair it shades, so that a caller or a test can read back what was drawn.
     `units`: repeat-unit positions (`count --units`), marked as ticks along the bottom of every panel; each Axes then
-    also carries `strique_units`, the positions inside its range."""
+    also carries `strique_units`, the positions inside its range.
+    `tract_positions`: per tract (configured order) the unit positions of `count --tract-positions`, marked like `units` one row of
+    ticks higher, one colour per tract; each Axes then also carries `strique_tract_positions`, per tract the positions inside its
+    range."""
     sig = smooth(raw)
     win = Windows(len(sig), row.offset, row.ticks, extension, zoom)
     grid = fig.add_gridspec(2, 2, height_ratios=(3, 2))
@@ -99,6 +105,16 @@ def draw(fig, raw, row, extension=0.1, zoom=500, units=None):
             if u.size:
                 ax.plot(u, np.full(u.size, 0.02), transform=ax.get_xaxis_transform(), linestyle="none", marker="|",
                         markersize=8, color="tab:green")
+        if tract_positions is not None:
+            inside = []
+            for j, p in enumerate(tract_positions):
+                u = np.asarray(p, np.int64)
+                u = u[(u >= lo) & (u < hi)]
+                inside.append(u)
+                if u.size:
+                    ax.plot(u, np.full(u.size, 0.06), transform=ax.get_xaxis_transform(), linestyle="none", marker="|",
+                            markersize=8, color=TRACT_COLOURS[j % len(TRACT_COLOURS)])
+            ax.strique_tract_positions = tuple(inside)
         ax.set_xlim(lo, max(hi, lo + 1))
         ax.set_title(captions[panel], fontsize=9)
         ax.set_xlabel("sample of the read")

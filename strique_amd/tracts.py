@@ -178,3 +178,71 @@ def parse(stream):
             rec = (counts, float(f[6]))
         rows.append((f[0], f[1], f[2], int(f[3]), rec))
     return rows
+
+
+# ---- where the units of a tract lie (`count --tract-positions`) ------------------------------------------------------------------
+# The rule.  A read gets positions exactly when its tract record has status 0.  With the window [prefix_begin, suffix_end) of the
+# filtered signal under the read's conditioning record -- the window of the tract decode -- position prefix_begin + t belongs to tract
+# j when the best path of the compound model emits observation t from one of the two dummy states of loop j.  Per tract the positions
+# ascend and there are count_j - bias_j of them: the visits, no bias applied (the bias units sit in the neighbouring profiles and have
+# no position).  Tracts come back in configured order on both strands (`configured_order`: on '-' the tract that is first in the
+# signal is configured last).  The span of a tract is (first position, last position).
+POS_HEADER = ['ID', 'target', 'strand', 'count', 'n_tracts', 'tract_counts', 'tract_spans', 'tract_positions']
+
+
+def spans(positions):
+    """(first, last) per tract, None for a tract without positions."""
+    return tuple((int(p[0]), int(p[-1])) if len(p) else None for p in positions)
+
+
+def format_positions_row(read_id, target, strand, count, rec):
+    """One row.  rec: None (no tract record) or (counts, log_p, positions) in configured order, positions None (back-pointers over
+    the budget) or one ascending sequence per tract.  Spans `first-last` per tract joined by commas; positions joined by commas
+    within a tract and ';' between tracts; '-' for a field without a value and for a tract without positions."""
+    head = [str(read_id), str(target), str(strand), str(int(count))]
+    if rec is None:
+        return '\t'.join(head + ['-', '-', '-', '-'])
+    counts, positions = rec[0], rec[2]
+    fields = [str(len(counts)), ','.join(str(int(c)) for c in counts)]
+    if positions is None:
+        return '\t'.join(head + fields + ['-', '-'])
+    if len(positions) != len(counts):
+        raise ValueError("tract positions of %s: %d tracts, %d position lists" % (read_id, len(counts), len(positions)))
+    fields.append(','.join('-' if s is None else '%d-%d' % s for s in spans(positions)))
+    fields.append(';'.join(','.join(str(int(x)) for x in p) if len(p) else '-' for p in positions))
+    return '\t'.join(head + fields)
+
+
+def parse_positions(stream):
+    """Rows of the positions file: [(ID, target, strand, count, None or (counts tuple, spans or None, positions or None))] -- spans a
+    tuple of (first, last) or None per tract, positions a tuple of tuples of int."""
+    rows, seen_header = [], False
+    for line in stream:
+        if not line.strip():
+            continue
+        f = line.rstrip('\n').split('\t')
+        if not seen_header:
+            if f != POS_HEADER:
+                raise ValueError("not a --tract-positions file")
+            seen_header = True
+            continue
+        if len(f) != len(POS_HEADER):
+            raise ValueError("tract positions row of %s: %r" % (f[0], f[1:]))
+        if f[4] == '-':
+            if f[5:] != ['-', '-', '-']:
+                raise ValueError("tract positions row of %s: %r" % (f[0], f[1:]))
+            rec = None
+        else:
+            counts = tuple(int(c) for c in f[5].split(','))
+            if len(counts) != int(f[4]):
+                raise ValueError("tract positions row of %s: %d counts, n_tracts = %s" % (f[0], len(counts), f[4]))
+            if f[6] == '-' and f[7] == '-':
+                rec = (counts, None, None)
+            else:
+                sp = tuple(None if s == '-' else tuple(int(v) for v in s.split('-')) for s in f[6].split(','))
+                pos = tuple(() if p == '-' else tuple(int(v) for v in p.split(',')) for p in f[7].split(';'))
+                if len(sp) != len(counts) or len(pos) != len(counts) or spans(pos) != sp:
+                    raise ValueError("tract positions row of %s: spans and positions disagree" % f[0])
+                rec = (counts, sp, pos)
+        rows.append((f[0], f[1], f[2], int(f[3]), rec))
+    return rows
