@@ -822,7 +822,10 @@ int strq_last_screen(const strq_ctx* ctx, double out[8]);
  * kernel)   [5] alignments of the last batched call that missed the first look's certificate and were resolved by the coarse screen's second look
  * (or belonged to an attempt that started over with the fine screen)   [6] LDS layout of the score tables in the two-flank kernels of that
  * screen: 1 the lane-major image (one 16-bit column per lane, no bank conflicts), 2 class rows (STRQ_SCREEN_LDS=rows, or an image that
- * would not fit: wide bands), 0 the one-flank kernel or no screen   [7] 0. */
+ * would not fit: wide bands), 3 the level image of the coarse screen (one row of byte entries per level, STRQ_SCREEN_LDS=levels or the
+ * default where the alignment parameters admit a byte scale and every read's image fits), 0 the one-flank kernel or no screen   [7] on the level
+ * image, the scale the kernel rounds its byte entries at inside (6 for STRique's parameters; its chunk values are converted up to the scale of
+ * strq_last_screen [6], in which everything behind the kernel works); 0 otherwise. */
 int strq_last_screen_mode(const strq_ctx* ctx, int32_t out[8]);
 /* The two sub-batches in flight, since the start of the last run call: [0] ms of HMM Viterbi launches whose rows were taken
  * [1] of them, ms that lay under the screen kernel of the sub-batch that followed   [2] ... under its whole alignment stage

@@ -18,7 +18,8 @@ struct LutJob {
     int32_t* band_lo;         // k packed row descriptors (see AlignTask::band_lo)
     int32_t k, pad_;
 };
-struct LutInfo { int32_t total, n_hard, need, packed; };   // total: entries of the ragged table; need: widest row; packed: table3 is exact
+struct LutInfo { int32_t total, n_hard, need, packed, lvl; };   // total: entries of the ragged table; need: widest row; packed: table3 is exact;
+                                                                // lvl: first | last << 8 level of the span of the bands (outside it every class is clamped)
 struct HardEntry { int32_t job, k, level, index; };
 
 int launch_lut_build(hipStream_t stream, const LutJob* jobs, LutInfo* info, int n_jobs, int max_k,

@@ -60,13 +60,14 @@ lut_build_kernel(const LutJob* __restrict__ jobs, LutInfo* __restrict__ info, Ha
     __shared__ float cls[STRQ_LUT_MAX_K];
     __shared__ int lo[STRQ_LUT_MAX_K], hi[STRQ_LUT_MAX_K + 1];      // later: e_l | e_r << 8 and the row offsets
     __shared__ int width, n_local, plat_lo, plat_hi, rebuild, unpackable;
+    __shared__ int lvl_lo, lvl_hi;      // span of the bands (classes without a band do not depend on the level): LutInfo::lvl
     __shared__ unsigned char dup[STRQ_LUT_MAX_K];
     __shared__ unsigned short local_hard[STRQ_LUT_LOCAL_HARD][2];
     const LutJob jb = jobs[blockIdx.x];
     const int q = threadIdx.x, lane = q & 63, wave = q >> 6;
     v[q] = jb.level_val[q];
     for (int k = q; k < jb.k; k += 256) cls[k] = jb.cls_val[k];
-    if (q == 0) { width = 0; n_local = 0; plat_lo = 255; plat_hi = 0; rebuild = 0; unpackable = 0; }
+    if (q == 0) { width = 0; n_local = 0; plat_lo = 255; plat_hi = 0; rebuild = 0; unpackable = 0; lvl_lo = 255; lvl_hi = 0; }
     __syncthreads();
     {
         // plateaus: levels 0..plat_lo share the value of level 0, levels plat_hi..255 that of level 255
@@ -76,7 +77,7 @@ lut_build_kernel(const LutJob* __restrict__ jobs, LutInfo* __restrict__ info, Ha
         if (q > 0 && !(v[q - 1] <= vq)) rebuild = 1;          // not monotone (or NaN): no contiguous bands
     }
     __syncthreads();
-    if (rebuild) { if (q == 0) { info[blockIdx.x].total = 0; info[blockIdx.x].need = 0; info[blockIdx.x].packed = 0; info[blockIdx.x].n_hard = -1; } return; }
+    if (rebuild) { if (q == 0) { info[blockIdx.x].total = 0; info[blockIdx.x].need = 0; info[blockIdx.x].packed = 0; info[blockIdx.x].n_hard = -1; info[blockIdx.x].lvl = 255 << 8; } return; }
     // 256 level values with the same bits leave plat_lo = 255 above plat_hi = 0: one plateau, rows of the one entry at level 255
     const int plat_lo_r = plat_lo, plat_hi_r = plat_hi < plat_lo ? plat_lo : plat_hi;
     auto in_band = [&](int lv, float c) { bool hd; return cell_score_dev(p, v[lv], c, &hd) > p.dist_min; };
@@ -105,6 +106,7 @@ lut_build_kernel(const LutJob* __restrict__ jobs, LutInfo* __restrict__ info, Ha
         lo[k] = el | (er << 8) | ((!none && l <= plat_lo_r) ? 0 : 1 << 16) | ((!none && h >= plat_hi_r) ? 0 : 1 << 17);   // bits 16/17: the edge entry is a clipped one
         hi[k] = er - el + 1;
         atomicMax(&width, er - el + 1);
+        if (!none) { atomicMin(&lvl_lo, el); atomicMax(&lvl_hi, er); }
     }
     __syncthreads();
     // classes with the same value (a k-mer that occurs more than once in the flank: 27 of the 145 of
@@ -167,6 +169,7 @@ lut_build_kernel(const LutJob* __restrict__ jobs, LutInfo* __restrict__ info, Ha
         info[blockIdx.x].need = width;
         info[blockIdx.x].packed = (nh == 0 && !unpackable) ? 1 : 0;      // patched or rebuilt tables stay float32
         info[blockIdx.x].n_hard = nh;
+        info[blockIdx.x].lvl = lvl_lo <= lvl_hi ? lvl_lo | (lvl_hi << 8) : 0;
         for (int i = 0; i < nh; ++i) {
             const int k = local_hard[i][0], lv = local_hard[i][1];
             const int slot = atomicAdd(hard_count, 1);

@@ -6,7 +6,9 @@
 
 #define STRQ_SCREEN_R 14                 // rows per lane of the screen (flanks up to 64 x 14 = 896 rows: STRique's are 870)
 #define STRQ_SCREEN_S 6                  // samples per k-mer class
-#define STRQ_SCREEN_SEG 4                // pieces (waves) per read
+#define STRQ_SCREEN_SEG 4                // pieces (waves) per read (the level image of the coarse screen: STRQ_SCREEN_SEG_LEVELS)
+#define STRQ_SCREEN_SEG_LEVELS 8         // ... of a launch on the level image (screen_levels_layout.h): ScreenParams::seg says which
+#define STRQ_SCREEN_SEG_MAX 8
 #define STRQ_SCREEN_CHUNK_COLS 128       // columns per reported chunk (64 steps x 2 columns)
 #define STRQ_SCREEN_MAX_WINDOWS 4
 // the coarse screen (align_screen2 / 3 / 6_kernel): 2, 3 or 6 flank rows per DP row, both flanks of a read in the two halves of one wave
@@ -18,13 +20,16 @@ namespace strq {
 
 // integer frame of the screen (units of 1 / sc of a score)
 struct ScreenParams {
-    int32_t sc;          // scale: a power of two
+    int32_t sc;          // scale of everything that leaves a screen kernel (chunk values, bounds, thresholds): a power of two
     int32_t hh, v;       // -ext_h * sc, -ext_v * sc (exact integers)
     int32_t cadd;        // hh + v: added to every table entry (the two potentials absorb the gap scores)
     int32_t slack;       // float32 rounding slack of the exact DP, scaled (32 * sc)
     int32_t merge_gap;   // candidate chunks closer than this many columns share a window
     int32_t max_cand;    // coarse screen: at most this many candidate chunks per alignment in the first look (0: no limit)
     int32_t margin;      // coarse screen: how far below the best chunk value a chunk is still a candidate (scaled); 0: the fine rule (m + 2 slack)
+    int32_t seg;         // pieces (waves) per read of the launch's tasks: STRQ_SCREEN_SEG, or STRQ_SCREEN_SEG_LEVELS on the level image
+    int32_t byte_sc;     // level image: the scale the kernel rounds its byte entries at INSIDE (screen_levels::byte_scale; 0: no level image).  Its chunk
+                         // values are converted up to the frame above where they leave the kernel, so nothing behind the kernel knows of it
 };
 
 // one piece (wave) of one alignment
@@ -47,6 +52,7 @@ struct Screen2Task {
     int32_t* out[2];             // chunk maxima of this piece, per flank
     int32_t tsize[2], k[2];
     int32_t n, col_off, n_chunks;
+    uint32_t lvl;                // level image: first | last << 8 level of the span of both tables' bands (screen_levels::join_ranges)
 };
 
 // per alignment: the columns the exact DP has to look at
@@ -74,14 +80,27 @@ static inline bool screen2_flank_ok(int m, int k) { return k >= 1 && k <= STRQ_S
 // The two LDS layouts of the read's 16-bit tables (screen_kernels.hip: screen2_body).  Class rows: screen2_lds_bytes from the entries of
 // the two float32 tables.  Lane-major image (screen_lds_layout.h, no bank conflicts): screen2_lanes_rows bounds its rows from the widest
 // band of either table (LutInfo::need), screen2_lanes_fit says whether a launch may use it (the LDS budget beside the Viterbi),
-// screen2_lanes_lds_bytes sizes it.  launch_screen2: lanes_rows > 0 runs the lane-major kernels with an image of that many rows
-// (lds_bytes covers it), 0 the class-row ones.
+// screen2_lanes_lds_bytes sizes it.
 size_t screen2_lds_bytes(int tsize_a, int tsize_b);
 int screen2_lanes_rows(int need_a, int need_b);
 bool screen2_lanes_fit(int rows);
 size_t screen2_lanes_lds_bytes(int rows);
+// Level image (screen_levels_layout.h; coarse screen only): one row per level of the span of the read's bands, byte entries in units
+// of T / MERGE.  screen2_levels_plan: screen2_plan plus the kernel's byte scale in sp->byte_sc (0: the parameters admit none -- the flank keeps
+// the other layouts), sp->seg = STRQ_SCREEN_SEG_LEVELS; screen2_byte_frame: the frame of a plan AT the byte scale (tests: the other layouts there); screen2_levels_rows: rows of a read's image from the two tables' LutInfo::lvl;
+// launch_screen2 with layout = STRQ_SCREEN_LDS_LEVELS runs it (rows = the tallest image of the launch).
+#define STRQ_SCREEN_LDS_LANES 1
+#define STRQ_SCREEN_LDS_ROWS 2
+#define STRQ_SCREEN_LDS_LEVELS 3
+int screen2_levels_plan(const AlignParams& p, int samples, int max_n, int merge, ScreenParams* sp);
+ScreenParams screen2_byte_frame(const ScreenParams& sp);
+uint32_t screen2_levels_range(uint32_t lvl_a, uint32_t lvl_b);
+int screen2_levels_rows(uint32_t range);
+bool screen2_levels_fit(int rows);
+size_t screen2_levels_lds_bytes(int rows);
+// layout: STRQ_SCREEN_LDS_*; rows: of the tallest lane-major / level image of the launch (ignored for the class rows)
 int launch_screen2(hipStream_t stream, const Screen2Task* tasks, int n_groups, int* queue, const ScreenParams& sp,
-                   size_t lds_bytes, int groups_per_cu, int n_cu, int merge, int lanes_rows);
+                   size_t lds_bytes, int groups_per_cu, int n_cu, int merge, int layout, int rows);
 // list / theta_list (nullable, device): only the alignments list[0 .. n_groups), each with the candidate threshold theta_list[idx]
 // in chunk units (the coarse screen's second look: every chunk whose bound reaches the score the first look found); out[idx]
 int launch_screen_windows(hipStream_t stream, const ScreenTask* tasks, int n_groups, const ScreenParams& sp,

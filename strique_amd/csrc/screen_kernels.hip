@@ -31,6 +31,7 @@
 #include <cmath>
 #include "screen_kernels.h"
 #include "screen_lds_layout.h"
+#include "screen_levels_layout.h"
 
 namespace strq {
 
@@ -80,6 +81,29 @@ __device__ __forceinline__ int sel_mask(int if0, int if1, uint64_t mask)      //
     int r;
     asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(if0), "v"(if1), "s"(mask));
     return r;
+}
+
+// 3 x one 16-bit half of q plus `add`: the level image's column address (screen_levels::column_address) from the level pair, one
+// instruction per column and no unpacking of the pair
+__device__ __forceinline__ int mad3_lo16(int q, int add)
+{
+    int r;
+    asm("v_mad_u32_u16 %0, %1, 3, %2" : "=v"(r) : "v"(q), "v"(add));
+    return r;
+}
+__device__ __forceinline__ int mad3_hi16(int q, int add)
+{
+    int r;
+    asm("v_mad_u32_u16 %0, %1, 3, %2 op_sel:[1,0,0,0]" : "=v"(r) : "v"(q), "v"(add));
+    return r;
+}
+// ceil(s sc) + cadd for a scale that is no power of two: s sc rounds in float32, and a product rounded DOWN onto an integer would lose
+// the ceiling's step -- the fused multiply-add says on which side of that integer the real product lies
+__device__ __forceinline__ int ceil_scaled(float s, float scf)
+{
+    float c = ceilf(s * scf);
+    if (fmaf(s, scf, -c) > 0.0f) c += 1.0f;
+    return (int)c;
 }
 
 struct LaneConst { int lo2[C], hi2[C], off[C]; };
@@ -295,9 +319,10 @@ constexpr int CPL = STRQ_SCREEN2_CPL, LPF = STRQ_SCREEN2_LPF, LB = STRQ_SCREEN2_
 struct Lane2Const { int lo2[CPL], hi2[CPL], off[CPL]; };
 
 // CMG: how many steps of a full chunk share one sample of the last row for the chunk's maximum (1: every column, the fine bound)
-template <int RPC, int CMG>
+template <int RPC, int CMG, int LAYOUT>
 struct Screen2 {
     static constexpr int R2 = RPC * CPL;
+    static constexpr bool LEVELS = LAYOUT == STRQ_SCREEN_LDS_LEVELS;
     static_assert(CMG == 1 || CMG == 2 || CMG == 4, "groups must divide the 64 steps of a chunk");
     const char* lds;
     const Lane2Const& lc;
@@ -308,15 +333,27 @@ struct Screen2 {
     int qq;
     int scA[CPL], scB[CPL];
 
+    // What a column's look-ups start from: the level's byte offset (one 16-bit half of the level pair), or on the level image the
+    // column's address -- the row of the level plus the lane's slot (lc.off[0]), 3 x the half in one v_mad_u32_u16
+    template <bool HI>
+    __device__ __forceinline__ int column(int qpair) const
+    {
+        if constexpr (LEVELS) return HI ? mad3_hi16(qpair, lc.off[0]) : mad3_lo16(qpair, lc.off[0]);
+        else return HI ? (int)((unsigned)qpair >> 16) : (qpair & 0xffff);
+    }
+    // class rows, lane-major image: clamp into the class's band, add its offset, ds_read_u16.  Level image: the clamp was evaluated when
+    // the image was filled -- a plain ds_read_u8 off the column's address with the class's immediate offset
     __device__ __forceinline__ int score(int q2, int c) const
     {
-        return *reinterpret_cast<const uint16_t*>(lds + med3i(q2, lc.lo2[c], lc.hi2[c]) + lc.off[c]);
+        if constexpr (LEVELS) return *reinterpret_cast<const uint8_t*>(lds + q2 + screen_levels::class_offset(c));
+        else return *reinterpret_cast<const uint16_t*>(lds + med3i(q2, lc.lo2[c], lc.hi2[c]) + lc.off[c]);
     }
     __device__ __forceinline__ void prime(int qcur)
     {
         qq = __builtin_amdgcn_update_dpp(__builtin_amdgcn_readlane(qcur, 0), 0, 0x138, 0xF, 0xF, false);
+        const int qa = column<false>(qq), qb = column<true>(qq);
 #pragma unroll
-        for (int c = 0; c < CPL; ++c) { scA[c] = score(qq & 0xffff, c); scB[c] = score((int)((unsigned)qq >> 16), c); }
+        for (int c = 0; c < CPL; ++c) { scA[c] = score(qa, c); scB[c] = score(qb, c); }
     }
 
     // One step = the lane's two columns.  Written so that nothing is copied from one step to the next: column B of row r - 1 is
@@ -337,7 +374,7 @@ struct Screen2 {
     __device__ __forceinline__ void step(int t, int qsrc, int snext, bool gfirst = true, bool glast = true)
     {
         const int qn = __builtin_amdgcn_update_dpp(__builtin_amdgcn_readlane(qsrc, snext), qq, 0x138, 0xF, 0xF, false);
-        const int qa = qn & 0xffff, qb = (int)((unsigned)qn >> 16);
+        const int qa = column<false>(qn), qb = column<true>(qn);
         const int potA = add_uniform(potB, hh), potBn = add_uniform(potA, hh);
         // the row above the lane: lane - 1's bottom cells; lanes 0 and LB: the top row (the column potential).  The select overwrites
         // the one lane the shift leaves without a source, so the shift needs no defined value there (and no copy to provide it)
@@ -388,14 +425,16 @@ struct Screen2 {
 
 // The level pairs of a chunk, each level pre-scaled to the byte offset of its table entry: by 2 (16-bit entries side by side in a class
 // row) or by screen_lanes::ROW_BYTES (one entry per row of the lane-major image)
-template <int SHIFT>
-__device__ __forceinline__ int load_chunk2(const Screen2Task& tk, int chunk, int lane)
+// (level image: the level clamped into the image's range [lvl0, lvl1] and scaled to its row -- screen_levels::scaled_level; SHIFT unused)
+template <int SHIFT, bool LEVELS>
+__device__ __forceinline__ int load_chunk2(const Screen2Task& tk, int chunk, int lane, int lvl0, int lvl1)
 {
     const int idx = (chunk * 64 + lane) * 2;
     int a = 0, b = 0;
     if (idx < tk.n) a = tk.levels[idx];
     if (idx + 1 < tk.n) b = tk.levels[idx + 1];
-    return (a << SHIFT) | (b << (SHIFT + 16));
+    if constexpr (LEVELS) return screen_levels::scaled_level(a, lvl0, lvl1) | (screen_levels::scaled_level(b, lvl0, lvl1) << 16);
+    else return (a << SHIFT) | (b << (SHIFT + 16));
 }
 
 // The two 16-bit score tables of a read in LDS.  Both layouts hold the same numbers -- MERGE (ceil(s * sc) + hh + v): what the merged row
@@ -407,11 +446,22 @@ __device__ __forceinline__ int load_chunk2(const Screen2Task& tk, int chunk, int
 //   LANES = true, lane-major image (screen_lds_layout.h): every lane reads its own 16-bit column of 128-byte rows, no conflicts.
 //     Larger (a row per level of the tallest lane; repeated k-mers stored per occurrence): the host launches it only where the image
 //     stays within screen_lanes::MAX_ROWS (launch_screen2), lds_rows is what it allocated.
-template <int RPC, int CMG, bool LANES>
+//   LAYOUT = STRQ_SCREEN_LDS_LEVELS, level image (screen_levels_layout.h; MERGE 3 only): one row per level of the span of the read's
+//     bands, the band clamp evaluated at fill time, byte entries ceil(s sc) + hh + v in units of T / MERGE -- the whole DP runs divided
+//     by MERGE at the kernel's own BYTE scale sp.byte_sc (screen2_levels_plan; potential step hh_b / MERGE, hh_b = -e_h byte_sc a multiple
+//     of MERGE).  Where a chunk value leaves the kernel it is multiplied back by MERGE and converted UP to the frame of sp.sc
+//     (ceil(x sc / byte_sc): still an upper bound, less than 1 / sc looser), so everything downstream -- the windows kernel, the
+//     cold-start bounds, the margin, the second look -- works in the frame it always had and knows nothing of the byte scale.  A look-up is a
+//     plain ds_read_u8; a column costs one v_mad_u32_u16 for its address.  SEGW = 8 waves (pieces of the read) share the image.
+template <int RPC, int CMG, int LAYOUT, int SEGW>
 __device__ __forceinline__ void screen2_body(const Screen2Task* __restrict__ tasks, int n_groups, int* __restrict__ queue, const ScreenParams& sp, int lds_rows)
 {
     constexpr int R2 = RPC * CPL, MERGE = S / RPC;
+    constexpr bool LANES = LAYOUT == STRQ_SCREEN_LDS_LANES, LEVELS = LAYOUT == STRQ_SCREEN_LDS_LEVELS;
     constexpr int QSHIFT = LANES ? screen_lanes::ROW_SHIFT : 1;
+    constexpr int UNIT = LEVELS ? MERGE : 1;          // what a stored value counts in units of 1 / (the kernel's scale)
+    static_assert(!LEVELS || (MERGE == screen_levels::MERGE && SEGW == screen_levels::SEG && CPL == screen_levels::CPL), "the level image is the coarse screen's");
+    static_assert((SEGW & (SEGW - 1)) == 0, "the prologue deals rows to waves by a mask");
     static_assert(CPL == screen_lanes::CPL, "screen_lds_layout.h stacks the lane's five classes");
     extern __shared__ uint32_t lds_all[];
     __shared__ int next_group;
@@ -424,9 +474,47 @@ __device__ __forceinline__ void screen2_body(const Screen2Task* __restrict__ tas
         __syncthreads();
         const int gi = __builtin_amdgcn_readfirstlane(next_group);
         if (gi >= n_groups) break;
-        const Screen2Task& t0 = tasks[(size_t)gi * SEG];
-        const float scf = (float)sp.sc;
+        const Screen2Task& t0 = tasks[(size_t)gi * SEGW];
+        // the scale the entries are rounded at, and the potentials in it (exact: hh, v are -e_h sc, -e_v sc and so are the byte frame's)
+        const int ksc = LEVELS ? sp.byte_sc : sp.sc;
+        const int khh = LEVELS ? sp.hh * ksc / sp.sc : sp.hh, kcadd = LEVELS ? khh + sp.v * ksc / sp.sc : sp.cadd;
+        const float scf = (float)ksc;
         Lane2Const lc;
+        [[maybe_unused]] int lvl0 = 0, lvl1 = 0;
+        if constexpr (LEVELS) {
+            // the lane's classes (the same for all pieces of the read); wave w fills the rows = w (mod SEGW): the 32 lanes of a flank store
+            // to 32 banks.  Every lane writes all three of its slots in every row -- padding classes and the lanes beyond the flank: 0
+            lvl0 = screen_levels::range_lo(t0.lvl); lvl1 = screen_levels::range_hi(t0.lvl);
+            uint32_t desc[CPL];
+            int nc = 0;
+#pragma unroll
+            for (int c = 0; c < CPL; ++c) {
+                const int k = lf * CPL + c;
+                const bool in = lf < LPF && k < t0.k[f];
+                desc[c] = in ? (uint32_t)t0.band_lo[f][k] : 0u;
+                nc += in ? 1 : 0;
+            }
+            char* dst = reinterpret_cast<char*>(lds_all) + screen_levels::slot(lane);
+            const float* src = t0.table[f];
+            const int rows = lvl1 - lvl0 + 1 < lds_rows ? lvl1 - lvl0 + 1 : lds_rows;
+            for (int r = wave; r < rows; r += SEGW) {
+                int e[CPL];
+#pragma unroll
+                for (int c = 0; c < CPL; ++c) {
+                    e[c] = 0;
+                    if (c < nc) {
+                        const int v = ceil_scaled(src[screen_levels::desc_off(desc[c]) + screen_levels::band_index(desc[c], lvl0 + r)], scf) + kcadd;
+                        e[c] = v < 255 ? v : 255;
+                    }
+                }
+                char* row = dst + r * screen_levels::ROW_BYTES;
+                *reinterpret_cast<uint16_t*>(row + screen_levels::class_offset(0)) = (uint16_t)(e[0] | (e[1] << 8));
+                *reinterpret_cast<uint16_t*>(row + screen_levels::class_offset(2)) = (uint16_t)(e[2] | (e[3] << 8));
+                *reinterpret_cast<uint16_t*>(row + screen_levels::class_offset(4)) = (uint16_t)e[4];
+            }
+#pragma unroll
+            for (int c = 0; c < CPL; ++c) { lc.lo2[c] = 0; lc.hi2[c] = 0; lc.off[c] = screen_levels::slot(lane); }
+        }
         if constexpr (LANES) {
             // the lane's classes (the same for the four pieces of the read: every wave fills rows of the one image)
             uint32_t desc[CPL];
@@ -449,28 +537,28 @@ __device__ __forceinline__ void screen2_body(const Screen2Task* __restrict__ tas
                 if (c < nc) {
                     const float* src = t0.table[f] + screen_lanes::desc_off(desc[c]);
                     const int w1 = screen_lanes::desc_w1(desc[c]);
-                    for (int i = (wave - rowbase[c]) & (SEG - 1); i <= w1; i += SEG)
+                    for (int i = (wave - rowbase[c]) & (SEGW - 1); i <= w1; i += SEGW)
                         if (rowbase[c] + i < lds_rows)
-                            *reinterpret_cast<uint16_t*>(dst + screen_lanes::entry_address(lane, rowbase[c], i)) = (uint16_t)(MERGE * ((int)ceilf(src[i] * scf) + sp.cadd));
+                            *reinterpret_cast<uint16_t*>(dst + screen_lanes::entry_address(lane, rowbase[c], i)) = (uint16_t)(MERGE * (ceil_scaled(src[i], scf) + sp.cadd));
                 }
             }
         }
         [[maybe_unused]] int base[2], zero_idx[2];          // class rows, in 16-bit entries
         base[0] = 0; zero_idx[0] = (t0.tsize[0] + 1) & ~1;
         base[1] = zero_idx[0] + 2; zero_idx[1] = base[1] + ((t0.tsize[1] + 1) & ~1);
-        if constexpr (!LANES) {
+        if constexpr (!LANES && !LEVELS) {
             uint16_t* dst = reinterpret_cast<uint16_t*>(lds_all);
 #pragma unroll
             for (int ff = 0; ff < 2; ++ff) {
-                for (int i = threadIdx.x; i < t0.tsize[ff]; i += 64 * SEG) dst[base[ff] + i] = (uint16_t)(MERGE * ((int)ceilf(t0.table[ff][i] * scf) + sp.cadd));
+                for (int i = threadIdx.x; i < t0.tsize[ff]; i += 64 * SEGW) dst[base[ff] + i] = (uint16_t)(MERGE * (ceil_scaled(t0.table[ff][i], scf) + sp.cadd));
                 if (threadIdx.x == 0) { dst[zero_idx[ff]] = 0; dst[zero_idx[ff] + 1] = 0; }
             }
         }
         __syncthreads();
-        const Screen2Task& tk = tasks[(size_t)gi * SEG + wave];
+        const Screen2Task& tk = tasks[(size_t)gi * SEGW + wave];
         if (tk.n <= 0) continue;
 
-        if constexpr (!LANES) {
+        if constexpr (!LANES && !LEVELS) {
 #pragma unroll
             for (int c = 0; c < CPL; ++c) {
                 const int k = lf * CPL + c;
@@ -487,19 +575,20 @@ __device__ __forceinline__ void screen2_body(const Screen2Task* __restrict__ tas
         const uint64_t top_mask = 1ull | (1ull << LB);
         // lanes whose last register holds a flank's last row (rows below a flank score 0 and copy it)
         const int lMa = (tk.k[0] - 1) / CPL, lMb = LB + (tk.k[1] - 1) / CPL;
-        Screen2<RPC, CMG> s2{ldsb, lc, top_mask, lane, tk.n, sp.hh};
+        const int hh = khh / UNIT;          // the potential's step per column in the kernel's units
+        Screen2<RPC, CMG, LAYOUT> s2{ldsb, lc, top_mask, lane, tk.n, hh};
         {
 #pragma unroll
             for (int r = 0; r < R2; ++r) s2.T[r] = STRQ_SCREEN_BIAS;
             s2.SbotA = STRQ_SCREEN_BIAS; s2.upS = STRQ_SCREEN_BIAS;
-            s2.potB = STRQ_SCREEN_BIAS - 2 * lane * sp.hh;
+            s2.potB = STRQ_SCREEN_BIAS - 2 * lane * hh;
             s2.cmax = STRQ_SCREEN_BIAS; s2.gpot = 0; s2.gmax = 0;
         }
         const int nsteps = (tk.n + 1) / 2 + 63;
-        int qcur = load_chunk2<QSHIFT>(tk, 0, lane);
+        int qcur = load_chunk2<QSHIFT, LEVELS>(tk, 0, lane, lvl0, lvl1);
         s2.prime(qcur);
         for (int t0s = 0; t0s < nsteps; t0s += 64) {
-            const int qnext = load_chunk2<QSHIFT>(tk, t0s / 64 + 1, lane);
+            const int qnext = load_chunk2<QSHIFT, LEVELS>(tk, t0s / 64 + 1, lane, lvl0, lvl1);
             const bool full = (t0s >= 63) && (2 * (t0s + 64) <= tk.n);
             const int send = nsteps - t0s < 64 ? nsteps - t0s : 64;
             if (full) {
@@ -525,7 +614,12 @@ __device__ __forceinline__ void screen2_body(const Screen2Task* __restrict__ tas
             }
             const int cma = __builtin_amdgcn_readlane(s2.cmax, lMa) - STRQ_SCREEN_BIAS;
             const int cmb = __builtin_amdgcn_readlane(s2.cmax, lMb) - STRQ_SCREEN_BIAS;
-            if (lane == 0) { tk.out[0][t0s / 64] = cma; tk.out[1][t0s / 64] = cmb; }
+            if (lane == 0) {
+                if constexpr (LEVELS) {          // back from T / MERGE at the byte scale to the frame of sp.sc, rounded up
+                    tk.out[0][t0s / 64] = (int)(((long long)cma * UNIT * sp.sc + ksc - 1) / ksc);
+                    tk.out[1][t0s / 64] = (int)(((long long)cmb * UNIT * sp.sc + ksc - 1) / ksc);
+                } else { tk.out[0][t0s / 64] = cma; tk.out[1][t0s / 64] = cmb; }
+            }
             s2.cmax = STRQ_SCREEN_BIAS;
             qcur = qnext;
         }
@@ -550,16 +644,21 @@ size_t screen2_lanes_lds_bytes(int rows) { return screen_lanes::bytes(rows); }
 #define STRQ_SCREEN3_CMG 2         // steps per sample of the chunk maximum in the coarse screen's full chunks (1, 2 or 4): the bound is up to
                                    // (2 CMG - 1) hh looser -- 3 score units; 4 measured the same step time as 2
 #endif
-#define STRQ_SCREEN2_ATTR(WPE_) __attribute__((amdgpu_flat_work_group_size(64 * STRQ_SCREEN_SEG, 64 * STRQ_SCREEN_SEG), amdgpu_waves_per_eu(WPE_, WPE_)))
+#define STRQ_SCREEN2_ATTR_SEG(WPE_, SEG_) __attribute__((amdgpu_flat_work_group_size(64 * SEG_, 64 * SEG_), amdgpu_waves_per_eu(WPE_, WPE_)))
+#define STRQ_SCREEN2_ATTR(WPE_) STRQ_SCREEN2_ATTR_SEG(WPE_, STRQ_SCREEN_SEG)
 #define STRQ_SCREEN2_ARGS const Screen2Task* __restrict__ tasks, int n_groups, int* __restrict__ queue, ScreenParams sp, int lds_rows
-__global__ void STRQ_SCREEN2_ATTR(6) align_screen3_kernel(STRQ_SCREEN2_ARGS) { screen2_body<2, STRQ_SCREEN3_CMG, true>(tasks, n_groups, queue, sp, lds_rows); }
+// the coarse screen on the level image: eight waves per workgroup, two workgroups per CU beside the Viterbi (screen_levels_layout.h); the
+// register cap stays that of six waves per SIMD (80 VGPRs: four waves fit next to the Viterbi's 192)
+__global__ void STRQ_SCREEN2_ATTR_SEG(6, STRQ_SCREEN_SEG_LEVELS) align_screen3_kernel(STRQ_SCREEN2_ARGS) { screen2_body<2, STRQ_SCREEN3_CMG, STRQ_SCREEN_LDS_LEVELS, STRQ_SCREEN_SEG_LEVELS>(tasks, n_groups, queue, sp, lds_rows); }
+// ... on the lane-major image: parameters without a byte scale, images over screen_levels::MAX_ROWS, STRQ_SCREEN_LDS=lanes
+__global__ void STRQ_SCREEN2_ATTR(6) align_screen3_lanes_kernel(STRQ_SCREEN2_ARGS) { screen2_body<2, STRQ_SCREEN3_CMG, STRQ_SCREEN_LDS_LANES, STRQ_SCREEN_SEG>(tasks, n_groups, queue, sp, lds_rows); }
 // ... and no merging at all: the fine screen's bound (one DP row per flank row, 30 per lane) for both flanks of a read in one wave, without the class
 // selects of align_screen_kernel -- what the fine screen runs on whenever a sub-batch holds both alignments of its reads (every detect call)
-__global__ void STRQ_SCREEN2_ATTR(4) align_screen1_kernel(STRQ_SCREEN2_ARGS) { screen2_body<6, 1, true>(tasks, n_groups, queue, sp, lds_rows); }
+__global__ void STRQ_SCREEN2_ATTR(4) align_screen1_kernel(STRQ_SCREEN2_ARGS) { screen2_body<6, 1, STRQ_SCREEN_LDS_LANES, STRQ_SCREEN_SEG>(tasks, n_groups, queue, sp, lds_rows); }
 // the same two on the class-row layout: launches whose lane-major image would exceed screen_lanes::MAX_ROWS (a flat level map: wide bands),
 // and STRQ_SCREEN_LDS=rows
-__global__ void STRQ_SCREEN2_ATTR(6) align_screen3_rows_kernel(STRQ_SCREEN2_ARGS) { screen2_body<2, STRQ_SCREEN3_CMG, false>(tasks, n_groups, queue, sp, lds_rows); }
-__global__ void STRQ_SCREEN2_ATTR(4) align_screen1_rows_kernel(STRQ_SCREEN2_ARGS) { screen2_body<6, 1, false>(tasks, n_groups, queue, sp, lds_rows); }
+__global__ void STRQ_SCREEN2_ATTR(6) align_screen3_rows_kernel(STRQ_SCREEN2_ARGS) { screen2_body<2, STRQ_SCREEN3_CMG, STRQ_SCREEN_LDS_ROWS, STRQ_SCREEN_SEG>(tasks, n_groups, queue, sp, lds_rows); }
+__global__ void STRQ_SCREEN2_ATTR(4) align_screen1_rows_kernel(STRQ_SCREEN2_ARGS) { screen2_body<6, 1, STRQ_SCREEN_LDS_ROWS, STRQ_SCREEN_SEG>(tasks, n_groups, queue, sp, lds_rows); }
 #undef STRQ_SCREEN2_ARGS
 
 // Candidate windows of every alignment.
@@ -581,6 +680,7 @@ screen_windows_kernel(const ScreenTask* __restrict__ tasks, int n_groups, Screen
     const int idx = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (idx >= n_groups) return;
     const int g = list ? list[idx] : idx;
+    const int SEG = sp.seg;          // pieces per alignment of this launch's tasks
     const ScreenTask* tg = tasks + (size_t)g * SEG;
     const int m = tg[0].m, lM = tg[0].lane_last;
     const int shift = -m * sp.v;            // v' = v + shift
@@ -732,7 +832,7 @@ int screen_plan(const AlignParams& p, int samples, int max_n, ScreenParams* sp)
             if (!(e < 1.0e4)) continue;
             sp->slack = ((int)std::ceil(e) + 1) * sc;
         }
-        sp->merge_gap = 3072; sp->margin = 0; sp->max_cand = 0;
+        sp->merge_gap = 3072; sp->margin = 0; sp->max_cand = 0; sp->seg = STRQ_SCREEN_SEG; sp->byte_sc = 0;
         return 1;
     }
     return 0;
@@ -753,18 +853,56 @@ int screen2_plan(const AlignParams& p, int samples, int max_n, int merge, Screen
     return 0;
 }
 
+int screen2_levels_plan(const AlignParams& p, int samples, int max_n, int merge, ScreenParams* sp)
+{
+    // the coarse screen's usual frame (screen2_plan) -- what leaves the kernel stays in it -- plus the scale the kernel rounds its byte
+    // entries at.  Stored values are T / MERGE <= rows x 255 + columns x hh_b / MERGE: far below 2^31 for any read
+    if (merge != screen_levels::MERGE) return 0;
+    if (!screen2_plan(p, samples, max_n, merge, sp)) return 0;
+    const int bsc = screen_levels::byte_scale((double)p.ext_h, (double)p.ext_v, (double)p.dist_offset);
+    if (bsc <= 0) return 0;
+    const double hhb = -(double)p.ext_h * bsc;
+    if ((double)(max_n + 256) * hhb / screen_levels::MERGE + 64.0 * CPL * 2 * 255.0 + (double)STRQ_SCREEN_BIAS > 2.0e9) return 0;
+    sp->byte_sc = bsc; sp->seg = STRQ_SCREEN_SEG_LEVELS;
+    return 1;
+}
+
+// The frame of `sp` at its byte scale, four pieces per read: what the lane-major / class-row kernels need to run the level image's bound
+// value for value (STRQ_SCREEN2_BYTE_SCALE, tests)
+ScreenParams screen2_byte_frame(const ScreenParams& sp)
+{
+    ScreenParams b = sp;
+    const int bsc = sp.byte_sc;
+    b.hh = (int)((long long)sp.hh * bsc / sp.sc); b.v = (int)((long long)sp.v * bsc / sp.sc); b.cadd = b.hh + b.v;
+    b.slack = sp.slack / sp.sc * bsc; b.sc = bsc; b.seg = STRQ_SCREEN_SEG; b.byte_sc = 0;
+    return b;
+}
+
+uint32_t screen2_levels_range(uint32_t lvl_a, uint32_t lvl_b) { return screen_levels::join_ranges(lvl_a, lvl_b); }
+int screen2_levels_rows(uint32_t range) { return screen_levels::rows_of(range); }
+bool screen2_levels_fit(int rows) { return screen_levels::fits(rows); }
+size_t screen2_levels_lds_bytes(int rows) { return screen_levels::bytes(rows); }
+
 int launch_screen2(hipStream_t stream, const Screen2Task* tasks, int n_groups, int* queue, const ScreenParams& sp,
-                   size_t lds_bytes, int groups_per_cu, int n_cu, int merge, int lanes_rows)
+                   size_t lds_bytes, int groups_per_cu, int n_cu, int merge, int layout, int rows)
 {
     if (n_groups <= 0) return 0;
     if (merge != 3 && merge != 1) return 2;
-    const bool lanes = lanes_rows > 0;
-    if (lanes && (!screen_lanes::fits(lanes_rows) || lds_bytes < screen_lanes::bytes(lanes_rows))) return 2;
-    auto kern = merge == 3 ? (lanes ? align_screen3_kernel : align_screen3_rows_kernel) : (lanes ? align_screen1_kernel : align_screen1_rows_kernel);
+    const bool lanes = layout == STRQ_SCREEN_LDS_LANES, levels = layout == STRQ_SCREEN_LDS_LEVELS;
+    if (!lanes && !levels && layout != STRQ_SCREEN_LDS_ROWS) return 2;
+    if (lanes && (!screen_lanes::fits(rows) || lds_bytes < screen_lanes::bytes(rows))) return 2;
+    // the level image: the coarse screen at a byte scale (hh a multiple of MERGE), tasks cut into its eight pieces
+    if (levels) {
+        if (merge != screen_levels::MERGE || !screen_levels::fits(rows) || lds_bytes < screen_levels::bytes(rows) || sp.seg != STRQ_SCREEN_SEG_LEVELS || sp.byte_sc <= 0) return 2;
+        const ScreenParams b = screen2_byte_frame(sp);
+        if (b.hh < screen_levels::MERGE || b.hh % screen_levels::MERGE != 0 || b.cadd > 255 || (long long)b.hh * sp.sc != (long long)sp.hh * b.sc) return 2;
+    }
+    if (!levels && sp.seg != SEG) return 2;
+    auto kern = merge == 3 ? (levels ? align_screen3_kernel : lanes ? align_screen3_lanes_kernel : align_screen3_rows_kernel) : (lanes ? align_screen1_kernel : align_screen1_rows_kernel);
     if (merge == 1 && groups_per_cu > 4) groups_per_cu = 4;          // ... for four
     if (groups_per_cu > 6) groups_per_cu = 6;
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    hipLaunchKernelGGL(kern, dim3(groups_per_cu * n_cu), dim3(64 * SEG), lds_bytes, stream, tasks, n_groups, queue, sp, lanes_rows);
+    hipLaunchKernelGGL(kern, dim3(groups_per_cu * n_cu), dim3(64 * sp.seg), lds_bytes, stream, tasks, n_groups, queue, sp, lanes || levels ? rows : 0);
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 

@@ -351,7 +351,7 @@ static int run_table_build(strq_ctx* c, hipStream_t st, TableBuild& b)
         }
         STRQ_HIP(c, hipMemcpy(jobs[j].table, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
         STRQ_HIP(c, hipMemcpy(jobs[j].band_lo, blo.data(), (size_t)kk * 4, hipMemcpyHostToDevice));
-        info[j].total = kk * 256; info[j].need = 256;
+        info[j].total = kk * 256; info[j].need = 256; info[j].lvl = 255 << 8;
     }
     b.hard_count = hard_count;
     return STRQ_OK;
@@ -415,7 +415,8 @@ static void read_switches(CorePlan& p)
 // Result per alignment: up to four column windows and a lower bound of its best score -- or nothing, then the whole read runs.
 
 // The tasks of one screen launch.  A view is one alignment; the views of a group share a wave: a read's two flank alignments on
-// the two-flank kernel (screen2_body), one alignment on the one-flank kernel.  Every view has STRQ_SCREEN_SEG pieces.
+// the two-flank kernel (screen2_body), one alignment on the one-flank kernel.  Every view has ScreenParams::seg pieces (STRQ_SCREEN_SEG; eight on
+// the coarse screen's level image).
 struct ScreenJob {
     int flanks = 1;                      // views per group
     std::vector<int> al;                 // alignment of each view
@@ -425,6 +426,9 @@ struct ScreenJob {
     std::vector<size_t> out_off;         // per view and piece: its chunk maxima in the output
     size_t out_words = 0, lds_bytes = 0;
     int lanes_rows = 0;                  // two-flank kernel: rows of the tallest lane-major table image of the launch (a bound: screen2_lanes_rows)
+    int levels_rows = 0;                 // ... of the tallest level image (screen2_levels_rows of the reads' band spans)
+    int layout = 0;                      // two-flank kernel: STRQ_SCREEN_LDS_*; screen_two_flank asks for the level image (it sets the scale and the
+                                         // piece count before the tasks are cut), run_screen settles the rest
     double steps = 0;
 };
 
@@ -443,7 +447,7 @@ struct ScreenRules {
 // Tasks of a screen over the groups of j.al (j.flanks alignments each).
 static void screen_tasks(CorePlan& p, const ScreenParams& sp, ScreenJob& j)
 {
-    constexpr int SSEG = STRQ_SCREEN_SEG;
+    const int SSEG = sp.seg;
     const AlignCoreIn& in = p.in;
     const int F = j.flanks, ng = (int)j.al.size() / F;
     if (F == 2) j.t2.resize((size_t)ng * SSEG);
@@ -455,17 +459,19 @@ static void screen_tasks(CorePlan& p, const ScreenParams& sp, ScreenJob& j)
         const int n = in.n[a[0]];
         const int m_big = F == 2 ? std::max(in.m[a[0]], in.m[a[1]]) : in.m[a[0]];
         const int ov_worst = align_segment_overlap(p.c->ap, m_big), ov_s = overlap_for(p, m_big, ov_worst, 16);
-        Piece pc[SSEG];
+        Piece pc[STRQ_SCREEN_SEG_MAX];
         const int used = cut(n, SSEG, ov_s, pc);
         j.lds_bytes = std::max(j.lds_bytes, F == 2 ? screen2_lds_bytes(p.info[p.J0[a[0]]].total, p.info[p.J0[a[1]]].total) : screen_lds_bytes(p.info[p.J0[a[0]]].total));
         if (F == 2) j.lanes_rows = std::max(j.lanes_rows, screen2_lanes_rows(p.info[p.J0[a[0]]].need, p.info[p.J0[a[1]]].need));
+        const uint32_t lvl = F == 2 ? screen2_levels_range((uint32_t)p.info[p.J0[a[0]]].lvl, (uint32_t)p.info[p.J0[a[1]]].lvl) : 0u;
+        if (F == 2) j.levels_rows = std::max(j.levels_rows, screen2_levels_rows(lvl));
         // what the cold start of the pieces costs: below this score a piece's values are not bounds of the whole matrix
         for (int f = 0; f < F; ++f)
             j.bound[(size_t)g * F + f] = used <= 1 ? INT32_MIN / 2 : (ov_s >= ov_worst ? 0 : (int32_t)std::ceil((double)align_segment_min_score(p.c->ap, in.m[a[f]], ov_s) * sp.sc));
         for (int w = 0; w < SSEG; ++w) {
             Screen2Task t; std::memset(&t, 0, sizeof(t));
             t.levels = in.d_levels + in.read_off[in.read[a[0]]] + pc[w].col_off;
-            t.n = pc[w].n; t.col_off = pc[w].col_off;
+            t.n = pc[w].n; t.col_off = pc[w].col_off; t.lvl = lvl;
             t.n_chunks = pc[w].n > 0 ? (align_num_steps(pc[w].n) + 63) / 64 : 0;
             for (int f = 0; f < F; ++f) {
                 const LutJob& job = p.jobs[p.J0[a[f]]];
@@ -487,17 +493,20 @@ static void screen_tasks(CorePlan& p, const ScreenParams& sp, ScreenJob& j)
 // screen_stats, and judges whether the screen pays.
 static int run_screen(CorePlan& p, ScreenJob& j, const ScreenParams& sp, const ScreenRules& r)
 {
-    constexpr int SSEG = STRQ_SCREEN_SEG;
+    const int SSEG = sp.seg;
     strq_ctx* c = p.c; const AlignCoreIn& in = p.in;
     hipStream_t st = p.st;
     const int nv = (int)j.al.size();
     // Two-flank kernels: the lane-major table image (screen_lds_layout.h: no bank conflicts) when the tallest image of the launch stays
     // within the LDS budget, else -- wide bands: a flat level map, a host-rebuilt table -- the class rows for the whole launch.
-    // STRQ_SCREEN_LDS=rows|lanes: the class rows always / the default.
-    int lanes_rows = 0;
+    // STRQ_SCREEN_LDS=rows|lanes|levels: the class rows always / the lane-major image where it fits / the default.  The coarse screen's level
+    // image (one row per level, byte entries) was asked for by screen_two_flank -- its tasks are cut into eight pieces at the byte scale.
+    int layout = 0, image_rows = 0;
     if (j.flanks == 2) {
         const char* e = strq::opt("STRQ_SCREEN_LDS");
-        if (!(e && std::strcmp(e, "rows") == 0) && screen2_lanes_fit(j.lanes_rows)) { lanes_rows = j.lanes_rows; j.lds_bytes = screen2_lanes_lds_bytes(lanes_rows); }
+        layout = STRQ_SCREEN_LDS_ROWS;
+        if (j.layout == STRQ_SCREEN_LDS_LEVELS) { layout = STRQ_SCREEN_LDS_LEVELS; image_rows = j.levels_rows; j.lds_bytes = screen2_levels_lds_bytes(image_rows); }
+        else if (!(e && std::strcmp(e, "rows") == 0) && screen2_lanes_fit(j.lanes_rows)) { layout = STRQ_SCREEN_LDS_LANES; image_rows = j.lanes_rows; j.lds_bytes = screen2_lanes_lds_bytes(image_rows); }
     }
     if (j.lds_bytes > 160 * 1024 - 64) { c->err = r.lds_err; return STRQ_ERR_UNSUPPORTED; }
     const int groups = std::max(1, std::min(r.groups_per_cu, (int)((160 * 1024 - 64) / j.lds_bytes)));
@@ -520,7 +529,7 @@ static int run_screen(CorePlan& p, ScreenJob& j, const ScreenParams& sp, const S
     STRQ_HIP(c, hipEventRecord(c->ev[5], st));
     int* queue = c->queue.as<int>() + STRQ_QUEUE_FIRST - 1;
     if (j.flanks == 2) {
-        if (launch_screen2(st, d_t2, nv / 2, queue, sp, j.lds_bytes, groups, c->n_cu, r.merge, lanes_rows)) { c->err = "coarse screen launch failed"; return STRQ_ERR_DEVICE; }
+        if (launch_screen2(st, d_t2, nv / 2, queue, sp, j.lds_bytes, groups, c->n_cu, r.merge, layout, image_rows)) { c->err = "coarse screen launch failed"; return STRQ_ERR_DEVICE; }
     } else {
         if (launch_screen(st, d_st, nv, queue, sp, j.lds_bytes, groups, c->n_cu)) { c->err = "screen launch failed"; return STRQ_ERR_DEVICE; }
     }
@@ -530,7 +539,7 @@ static int run_screen(CorePlan& p, ScreenJob& j, const ScreenParams& sp, const S
     STRQ_HIP(c, hipMemcpyAsync(hw.data(), d_win, hw.size() * sizeof(ScreenWindows), hipMemcpyDeviceToHost, st));
     STRQ_HIP(c, hipStreamSynchronize(st));
     c->screen_ran = true; c->screen_mode_last = r.merge > 1 ? 2 : 1; c->coarse_merge_last = r.merge;
-    c->screen_lds_last = j.flanks == 2 ? (lanes_rows > 0 ? 1 : 2) : 0;
+    c->screen_lds_last = layout; c->screen_byte_sc_last = layout == STRQ_SCREEN_LDS_LEVELS ? sp.byte_sc : 0;
     if (const char* path = strq::opt("STRQ_SCREEN_DUMP")) {
         // tests: the chunk maxima as the kernel wrote them (tests/test_gpu_screen.py checks them against the exact last row)
         std::vector<int32_t> ho(j.out_words);
@@ -592,8 +601,8 @@ static int run_screen(CorePlan& p, ScreenJob& j, const ScreenParams& sp, const S
         else if (windowed < 0.9 * (nv - (p.ov_fixed ? 0 : below_bound)) || cols > r.max_cols * all || (long)heavy * 100 > 2L * nv) pause_after_fail(*r.pause, *r.fail);
         else *r.fail = 0;
     }
-    STRQ_DBG("screen (%d flanks per wave, merge %d): %d alignments, scale %d, margin %.0f, %d groups per CU, LDS %zu bytes: %d with windows (%d below the cold-start bound), %.2f %% of the columns, %d heavy -> pause %d",
-             j.flanks, r.merge, nv, sp.sc, (double)sp.margin / sp.sc, groups, j.lds_bytes, windowed, below_bound, 100.0 * cols / std::max(1.0, all), heavy, *r.pause);
+    STRQ_DBG("screen (%d flanks per wave, merge %d, LDS layout %d, %d image rows, %d pieces): %d alignments, scale %d, margin %.0f, %d groups per CU, LDS %zu bytes: %d with windows (%d below the cold-start bound), %.2f %% of the columns, %d heavy -> pause %d",
+             j.flanks, r.merge, layout, image_rows, SSEG, nv, sp.sc, (double)sp.margin / sp.sc, groups, j.lds_bytes, windowed, below_bound, 100.0 * cols / std::max(1.0, all), heavy, *r.pause);
     return STRQ_OK;
 }
 
@@ -626,6 +635,40 @@ static int screen_two_flank(CorePlan& p, int merge, int max_n)
     std::stable_sort(pairs.begin(), pairs.end(), [&](const std::pair<int, int>& x, const std::pair<int, int>& y) { return in.n[x.first] > in.n[y.first]; });
     const int ngr = (int)pairs.size();
     if (ngr == 0 || 2 * ngr < (nb * 9) / 10) return STRQ_OK;
+    // The coarse screen runs on the level image (screen_levels_layout.h) when the parameters admit a byte scale and every read's image
+    // -- one row per level of the span of BOTH its tables' bands -- fits the LDS budget: one read over the limit sends the launch to the
+    // lane-major image.  STRQ_SCREEN_LDS=lanes|rows keep the 16-bit tables.  Settled here because the image has its own piece count
+    // (screen2_levels_plan: eight; the frame -- scale, margin, bounds -- is the coarse screen's usual one, the byte scale stays inside the kernel),
+    // which the tasks below are cut for.
+    // STRQ_SCREEN2_BYTE_SCALE=1 (tests) runs the other layouts at the byte scale too: the same bound at the same scale, value for value.
+    bool levels = false;
+    if (merge == 3) {
+        const char* e = strq::opt("STRQ_SCREEN_LDS");
+        ScreenParams spb;
+        if (screen2_levels_plan(c->ap, p.S, max_n, merge, &spb)) {
+            levels = !e || std::strcmp(e, "levels") == 0;
+            for (size_t x = 0; levels && x < pairs.size(); ++x)
+                levels = screen2_levels_fit(screen2_levels_rows(screen2_levels_range((uint32_t)p.info[p.J0[pairs[x].first]].lvl, (uint32_t)p.info[p.J0[pairs[x].second]].lvl)));
+            if (levels && !e) {
+                // ... and where eight pieces per read pay.  The image's workgroup has eight waves: a read cut into fewer leaves waves idle
+                // (two workgroups per CU: nothing fills in), and every further piece computes its cold-start overlap again.  The step is
+                // about a quarter shorter; the image is taken when at least nine waves in ten get a piece and the four
+                // further overlaps add at most a tenth to the columns of the launch -- 50 kb reads: 4 x 8192 in ~380 k on the first
+                // sub-batch, half that once the overlap follows the scores.
+                double extra = 0, all = 0; long used = 0;
+                for (const auto& pr : pairs) {
+                    const int m_big = std::max(in.m[pr.first], in.m[pr.second]);
+                    const int ov_s = overlap_for(p, m_big, align_segment_overlap(c->ap, m_big), 16);
+                    Piece pc[STRQ_SCREEN_SEG_MAX];
+                    const int u8 = cut(in.n[pr.first], STRQ_SCREEN_SEG_LEVELS, ov_s, pc), u4 = cut(in.n[pr.first], STRQ_SCREEN_SEG, ov_s, pc);
+                    extra += (double)(u8 - u4) * ov_s; all += in.n[pr.first]; used += u8;
+                }
+                levels = extra <= 0.10 * all && used * 10 >= 9L * STRQ_SCREEN_SEG_LEVELS * (long)pairs.size();
+            }
+            if (levels) sp = spb;
+            else if (strq::opt("STRQ_SCREEN2_BYTE_SCALE")) sp = screen2_byte_frame(spb);
+        }
+    }
     sp.margin = (int32_t)std::lround((double)c->coarse_margin * (merge == 3 ? 1.3 : 1.0) * sp.sc);
     if (const char* e = strq::opt("STRQ_SCREEN2_MARGIN")) sp.margin = (int32_t)std::lround(atof(e) * sp.sc);
     sp.max_cand = 8;          // (8, 16, 32 candidates and margins of 300 ... 700 score units measure within 1.5 % of each other: run r5n)
@@ -634,6 +677,7 @@ static int screen_two_flank(CorePlan& p, int merge, int max_n)
     ScreenJob j;
     j.flanks = 2;
     for (const auto& pr : pairs) { j.al.push_back(pr.first); j.al.push_back(pr.second); }
+    j.layout = levels ? STRQ_SCREEN_LDS_LEVELS : 0;
     screen_tasks(p, sp, j);
     // The coarse pass costs ~0.36 of the float32 pass over whole reads, the fine bound ~0.72, the exact pass over a share x of the
     // columns (windows + their cold-start overlaps) ~1.3 x: the coarse path beats the fine one while x < ~0.3 (short reads sit at
@@ -1628,6 +1672,7 @@ int strq_last_screen_mode(const strq_ctx* c, int32_t out[8])
     out[5] = (int32_t)std::min<int64_t>(c->look2_served, INT32_MAX);
     out[4] = c->screen_mode_last ? c->coarse_merge_last : 0;
     out[6] = c->screen_mode_last ? c->screen_lds_last : 0;
+    out[7] = c->screen_mode_last ? c->screen_byte_sc_last : 0;
     return STRQ_OK;
 }
 

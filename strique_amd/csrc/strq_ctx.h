@@ -157,7 +157,8 @@ struct strq_ctx {
     float aborted_fwd_ms = 0, aborted_screen_ms = 0;      // forward / screen time of an attempt align_core stopped and started over (added to the call's times)
     int screen_mode_last = 0;                 // screen of the last align_core call: 0 none, 1 fine, 2 coarse
     int coarse_merge_last = 0;                // ... and the flank rows per DP row of the coarse one
-    int screen_lds_last = 0;                  // ... and the LDS layout of its score tables: 1 lane-major image, 2 class rows (0: the one-flank kernel)
+    int screen_byte_sc_last = 0;              // ... and, on the level image, the scale the kernel rounds its byte entries at (0 otherwise)
+    int screen_lds_last = 0;                  // ... and the LDS layout of its score tables: 1 lane-major image, 2 class rows, 3 level image (0: the one-flank kernel)
     
     // workspace
     strq::DevBuf levels, level_val, flank_cls, tables, tables3, band_lo, col0, ckpt, rec, tasks, results,

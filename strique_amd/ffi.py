@@ -318,7 +318,8 @@ class Context(object):
         out["mode"] = {0: None, 1: "fine", 2: "coarse"}.get(int(m[0]))
         out["coarse_pause"], out["fine_pause"], out["coarse_margin"], out["merge"] = int(m[1]), int(m[2]), int(m[3]), int(m[4])
         out["second_look"] = int(m[5])          # alignments resolved by the coarse screen's second look (not in strq_last_second_round)
-        out["lds_layout"] = {0: None, 1: "lanes", 2: "rows"}.get(int(m[6]))          # score tables of the two-flank screen kernels
+        out["lds_layout"] = {0: None, 1: "lanes", 2: "rows", 3: "levels"}.get(int(m[6]))          # score tables of the two-flank screen kernels
+        out["byte_scale"] = int(m[7])           # level image: the scale of the kernel's byte entries (its chunk values leave it at `scale`)
         return out
 
     def last_overlap(self):
