@@ -89,6 +89,8 @@ size_t screen2_lanes_lds_bytes(int rows);
 // of T / MERGE.  screen2_levels_plan: screen2_plan plus the kernel's byte scale in sp->byte_sc (0: the parameters admit none -- the flank keeps
 // the other layouts), sp->seg = STRQ_SCREEN_SEG_LEVELS; screen2_byte_frame: the frame of a plan AT the byte scale (tests: the other layouts there); screen2_levels_rows: rows of a read's image from the two tables' LutInfo::lvl;
 // launch_screen2 with layout = STRQ_SCREEN_LDS_LEVELS runs it (rows = the tallest image of the launch).
+// merge 3 or 6 (one DP row per k-mer class, align_screen6_kernel: the level image only): both leave their values in the frame of merge 3,
+// merge 6 needs a byte scale whose hh is a multiple of 6 (screen2_levels_plan returns 0 where there is none).
 #define STRQ_SCREEN_LDS_LANES 1
 #define STRQ_SCREEN_LDS_ROWS 2
 #define STRQ_SCREEN_LDS_LEVELS 3

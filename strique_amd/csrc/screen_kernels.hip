@@ -446,13 +446,15 @@ __device__ __forceinline__ int load_chunk2(const Screen2Task& tk, int chunk, int
 //   LANES = true, lane-major image (screen_lds_layout.h): every lane reads its own 16-bit column of 128-byte rows, no conflicts.
 //     Larger (a row per level of the tallest lane; repeated k-mers stored per occurrence): the host launches it only where the image
 //     stays within screen_lanes::MAX_ROWS (launch_screen2), lds_rows is what it allocated.
-//   LAYOUT = STRQ_SCREEN_LDS_LEVELS, level image (screen_levels_layout.h; MERGE 3 only): one row per level of the span of the read's
+//   LAYOUT = STRQ_SCREEN_LDS_LEVELS, level image (screen_levels_layout.h; MERGE 3 and 6): one row per level of the span of the read's
 //     bands, the band clamp evaluated at fill time, byte entries ceil(s sc) + hh + v in units of T / MERGE -- the whole DP runs divided
 //     by MERGE at the kernel's own BYTE scale sp.byte_sc (screen2_levels_plan; potential step hh_b / MERGE, hh_b = -e_h byte_sc a multiple
 //     of MERGE).  Where a chunk value leaves the kernel it is multiplied back by MERGE and converted UP to the frame of sp.sc
 //     (ceil(x sc / byte_sc): still an upper bound, less than 1 / sc looser), so everything downstream -- the windows kernel, the
 //     cold-start bounds, the margin, the second look -- works in the frame it always had and knows nothing of the byte scale.  A look-up is a
 //     plain ds_read_u8; a column costs one v_mad_u32_u16 for its address.  SEGW = 8 waves (pieces of the read) share the image.
+//     The entry does not depend on MERGE, so MERGE 6 (RPC = 1: one DP row per class, five per lane, ten cells per step) reads the SAME image:
+//     its stored values are T / 6, its potential step hh_b / 6 and a chunk value leaves as ceil(x 6 sc / byte_sc).
 template <int RPC, int CMG, int LAYOUT, int SEGW>
 __device__ __forceinline__ void screen2_body(const Screen2Task* __restrict__ tasks, int n_groups, int* __restrict__ queue, const ScreenParams& sp, int lds_rows)
 {
@@ -460,7 +462,7 @@ __device__ __forceinline__ void screen2_body(const Screen2Task* __restrict__ tas
     constexpr bool LANES = LAYOUT == STRQ_SCREEN_LDS_LANES, LEVELS = LAYOUT == STRQ_SCREEN_LDS_LEVELS;
     constexpr int QSHIFT = LANES ? screen_lanes::ROW_SHIFT : 1;
     constexpr int UNIT = LEVELS ? MERGE : 1;          // what a stored value counts in units of 1 / (the kernel's scale)
-    static_assert(!LEVELS || (MERGE == screen_levels::MERGE && SEGW == screen_levels::SEG && CPL == screen_levels::CPL), "the level image is the coarse screen's");
+    static_assert(!LEVELS || (screen_levels::merge_ok(MERGE) && SEGW == screen_levels::SEG && CPL == screen_levels::CPL), "the level image is the coarse screen's");
     static_assert((SEGW & (SEGW - 1)) == 0, "the prologue deals rows to waves by a mask");
     static_assert(CPL == screen_lanes::CPL, "screen_lds_layout.h stacks the lane's five classes");
     extern __shared__ uint32_t lds_all[];
@@ -638,8 +640,8 @@ int screen2_lanes_rows(int need_a, int need_b) { return screen_lanes::rows_bound
 bool screen2_lanes_fit(int rows) { return screen_lanes::fits(rows); }
 size_t screen2_lanes_lds_bytes(int rows) { return screen_lanes::bytes(rows); }
 
-// MERGE = 3: two DP rows per class, ten per lane.  (Rounds 5 measured MERGE 2 and 6 as well -- 114.4 and 96.6 ms per 4096 reads against
-// 94.7, with 2.4 % / 14 % of the alignments in the second look against 6 %: DESIGN.md 4.2e -- those instances are gone.)
+// MERGE = 3: two DP rows per class, ten per lane.  (Round 5 measured MERGE 2 and 6 on the 16-bit class rows as well -- 114.4 and 96.6 ms per
+// 4096 reads against 94.7: DESIGN.md 4.2e -- those instances are gone; MERGE 6 is back on the level image, below.)
 #ifndef STRQ_SCREEN3_CMG
 #define STRQ_SCREEN3_CMG 2         // steps per sample of the chunk maximum in the coarse screen's full chunks (1, 2 or 4): the bound is up to
                                    // (2 CMG - 1) hh looser -- 3 score units; 4 measured the same step time as 2
@@ -650,6 +652,9 @@ size_t screen2_lanes_lds_bytes(int rows) { return screen_lanes::bytes(rows); }
 // the coarse screen on the level image: eight waves per workgroup, two workgroups per CU beside the Viterbi (screen_levels_layout.h); the
 // register cap stays that of six waves per SIMD (80 VGPRs: four waves fit next to the Viterbi's 192)
 __global__ void STRQ_SCREEN2_ATTR_SEG(6, STRQ_SCREEN_SEG_LEVELS) align_screen3_kernel(STRQ_SCREEN2_ARGS) { screen2_body<2, STRQ_SCREEN3_CMG, STRQ_SCREEN_LDS_LEVELS, STRQ_SCREEN_SEG_LEVELS>(tasks, n_groups, queue, sp, lds_rows); }
+// one DP row per class on the same image (MERGE 6: half the cells of a step; what the coarse screen runs by default where it takes the level
+// image, DESIGN.md 4.2e last part)
+__global__ void STRQ_SCREEN2_ATTR_SEG(6, STRQ_SCREEN_SEG_LEVELS) align_screen6_kernel(STRQ_SCREEN2_ARGS) { screen2_body<1, STRQ_SCREEN3_CMG, STRQ_SCREEN_LDS_LEVELS, STRQ_SCREEN_SEG_LEVELS>(tasks, n_groups, queue, sp, lds_rows); }
 // ... on the lane-major image: parameters without a byte scale, images over screen_levels::MAX_ROWS, STRQ_SCREEN_LDS=lanes
 __global__ void STRQ_SCREEN2_ATTR(6) align_screen3_lanes_kernel(STRQ_SCREEN2_ARGS) { screen2_body<2, STRQ_SCREEN3_CMG, STRQ_SCREEN_LDS_LANES, STRQ_SCREEN_SEG>(tasks, n_groups, queue, sp, lds_rows); }
 // ... and no merging at all: the fine screen's bound (one DP row per flank row, 30 per lane) for both flanks of a read in one wave, without the class
@@ -856,13 +861,15 @@ int screen2_plan(const AlignParams& p, int samples, int max_n, int merge, Screen
 int screen2_levels_plan(const AlignParams& p, int samples, int max_n, int merge, ScreenParams* sp)
 {
     // the coarse screen's usual frame (screen2_plan) -- what leaves the kernel stays in it -- plus the scale the kernel rounds its byte
-    // entries at.  Stored values are T / MERGE <= rows x 255 + columns x hh_b / MERGE: far below 2^31 for any read
-    if (merge != screen_levels::MERGE) return 0;
-    if (!screen2_plan(p, samples, max_n, merge, sp)) return 0;
-    const int bsc = screen_levels::byte_scale((double)p.ext_h, (double)p.ext_v, (double)p.dist_offset);
+    // entries at.  Stored values are T / MERGE <= rows x 255 + columns x hh_b / MERGE: far below 2^31 for any read.
+    // merge 6 (one DP row per class) keeps the FRAME of merge 3 -- this path has no 16-bit table, so screen2_plan's limit on merge x entry
+    // does not bind it -- and needs a byte scale at which hh_b is a multiple of 6
+    if (!screen_levels::merge_ok(merge)) return 0;
+    if (!screen2_plan(p, samples, max_n, screen_levels::MERGE, sp)) return 0;
+    const int bsc = screen_levels::byte_scale((double)p.ext_h, (double)p.ext_v, (double)p.dist_offset, merge);
     if (bsc <= 0) return 0;
     const double hhb = -(double)p.ext_h * bsc;
-    if ((double)(max_n + 256) * hhb / screen_levels::MERGE + 64.0 * CPL * 2 * 255.0 + (double)STRQ_SCREEN_BIAS > 2.0e9) return 0;
+    if ((double)(max_n + 256) * hhb / merge + 64.0 * CPL * 2 * 255.0 + (double)STRQ_SCREEN_BIAS > 2.0e9) return 0;
     sp->byte_sc = bsc; sp->seg = STRQ_SCREEN_SEG_LEVELS;
     return 1;
 }
@@ -887,18 +894,19 @@ int launch_screen2(hipStream_t stream, const Screen2Task* tasks, int n_groups, i
                    size_t lds_bytes, int groups_per_cu, int n_cu, int merge, int layout, int rows)
 {
     if (n_groups <= 0) return 0;
-    if (merge != 3 && merge != 1) return 2;
+    if (merge != 3 && merge != 1 && merge != 6) return 2;
     const bool lanes = layout == STRQ_SCREEN_LDS_LANES, levels = layout == STRQ_SCREEN_LDS_LEVELS;
     if (!lanes && !levels && layout != STRQ_SCREEN_LDS_ROWS) return 2;
     if (lanes && (!screen_lanes::fits(rows) || lds_bytes < screen_lanes::bytes(rows))) return 2;
-    // the level image: the coarse screen at a byte scale (hh a multiple of MERGE), tasks cut into its eight pieces
+    // the level image: the coarse screen at a byte scale (hh a multiple of merge), tasks cut into its eight pieces; merge 6 has no other layout
+    if (merge == 6 && !levels) return 2;
     if (levels) {
-        if (merge != screen_levels::MERGE || !screen_levels::fits(rows) || lds_bytes < screen_levels::bytes(rows) || sp.seg != STRQ_SCREEN_SEG_LEVELS || sp.byte_sc <= 0) return 2;
+        if (!screen_levels::merge_ok(merge) || !screen_levels::fits(rows) || lds_bytes < screen_levels::bytes(rows) || sp.seg != STRQ_SCREEN_SEG_LEVELS || sp.byte_sc <= 0) return 2;
         const ScreenParams b = screen2_byte_frame(sp);
-        if (b.hh < screen_levels::MERGE || b.hh % screen_levels::MERGE != 0 || b.cadd > 255 || (long long)b.hh * sp.sc != (long long)sp.hh * b.sc) return 2;
+        if (b.hh < merge || b.hh % merge != 0 || b.cadd > 255 || (long long)b.hh * sp.sc != (long long)sp.hh * b.sc) return 2;
     }
     if (!levels && sp.seg != SEG) return 2;
-    auto kern = merge == 3 ? (levels ? align_screen3_kernel : lanes ? align_screen3_lanes_kernel : align_screen3_rows_kernel) : (lanes ? align_screen1_kernel : align_screen1_rows_kernel);
+    auto kern = merge == 6 ? align_screen6_kernel : merge == 3 ? (levels ? align_screen3_kernel : lanes ? align_screen3_lanes_kernel : align_screen3_rows_kernel) : (lanes ? align_screen1_kernel : align_screen1_rows_kernel);
     if (merge == 1 && groups_per_cu > 4) groups_per_cu = 4;          // ... for four
     if (groups_per_cu > 6) groups_per_cu = 6;
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);

@@ -7,7 +7,8 @@
 // and the row holds, for every lane, the entries of its five classes AT that level -- the band clamp is evaluated when the image
 // is filled (entry = table[clamp(level, lo, lo + w1)]), so a column needs ONE address (row offset + the lane's slot) and its
 // five scores are plain byte reads off it with immediate offsets.  A byte holds an entry because the kernel works in units of
-// T / MERGE: entry = ceil(s sc) + hh + v (not MERGE times that), potential step hh / MERGE -- see byte_scale below.
+// T / MERGE: entry = ceil(s sc) + hh + v (not MERGE times that), potential step hh / MERGE -- see byte_scale below.  The entry is
+// the same for every merge factor: align_screen6_kernel (MERGE_CLASS = 6, one DP row per class) reads the image align_screen3_kernel reads.
 //
 // A row is 384 bytes = three sub-rows of 128 bytes = three passes over the 32 LDS banks.  Lane l owns the same 16-bit slot of
 // every sub-row as in the lane-major image: lanes 0 .. 31 (prefix flank) the low halves of dwords 0 .. 31, lanes 32 .. 63
@@ -94,12 +95,16 @@ STRQ_LEVELS_HD bool fits(int rows) { return rows >= 1 && rows <= MAX_ROWS; }
 // The byte scale: the largest integer sc at which -ext_h sc and -ext_v sc are integers, hh = -ext_h sc is a multiple of MERGE (the
 // kernel's potential step is hh / MERGE) and the largest entry ceil(dist_offset sc) + hh + v fits a byte.  0: none (the flank keeps
 // the lane-major image and its power-of-two scale).  STRique's parameters (-1, -16, 16) give 6: hh = 6, v = 96, entries <= 198.
-inline int byte_scale(double ext_h, double ext_v, double dist_offset)
+// `merge`: the flank rows per DP row of the kernel that reads the image -- MERGE, or MERGE_CLASS (one DP row per k-mer class:
+// align_screen6_kernel).  The entry does not depend on it, only the divisibility of hh: STRique's parameters give 6 for both.
+constexpr int MERGE_CLASS = 6;
+constexpr STRQ_LEVELS_HD bool merge_ok(int merge) { return merge == MERGE || merge == MERGE_CLASS; }
+inline int byte_scale(double ext_h, double ext_v, double dist_offset, int merge = MERGE)
 {
     for (int sc = 255; sc >= 1; --sc) {
         const double hh = -ext_h * sc, v = -ext_v * sc;
-        if (hh != (double)(long)hh || v != (double)(long)v || hh < MERGE) continue;
-        if ((long)hh % MERGE != 0) continue;
+        if (hh != (double)(long)hh || v != (double)(long)v || hh < merge) continue;
+        if ((long)hh % merge != 0) continue;
         const double top = dist_offset * sc;
         const long smax = (long)top + ((double)(long)top < top ? 1 : 0);
         if ((double)smax + hh + v > 255.0) continue;

@@ -434,7 +434,7 @@ struct ScreenJob {
 
 // How the screens differ beyond their tasks.
 struct ScreenRules {
-    int merge;                 // flank rows per DP row of the two-flank kernel (1: fine rules, 3: coarse); 0: the one-flank kernel
+    int merge;                 // flank rows per DP row of the two-flank kernel (1: fine rules, 3 / 6: coarse); 0: the one-flank kernel
     int groups_per_cu;
     const char* lds_err;
     bool below_bound_free;     // an alignment below the pieces' cold-start bound counts no columns in the verdict
@@ -607,8 +607,8 @@ static int run_screen(CorePlan& p, ScreenJob& j, const ScreenParams& sp, const S
 }
 
 // The screen that takes both flank alignments of a read per wave, on the reads whose two alignments are both in this sub-batch.
-// merge 3: the coarse screen (merged rows, its own candidate rules and second look); 1: the same kernel with the fine screen's
-// bound and rules.
+// merge 3: the coarse screen (merged rows, its own candidate rules and second look; six rows per DP row where it runs on the level
+// image by default, below); 1: the same kernel with the fine screen's bound and rules.
 static int screen_two_flank(CorePlan& p, int merge, int max_n)
 {
     strq_ctx* c = p.c; const AlignCoreIn& in = p.in;
@@ -641,11 +641,25 @@ static int screen_two_flank(CorePlan& p, int merge, int max_n)
     // (screen2_levels_plan: eight; the frame -- scale, margin, bounds -- is the coarse screen's usual one, the byte scale stays inside the kernel),
     // which the tasks below are cut for.
     // STRQ_SCREEN2_BYTE_SCALE=1 (tests) runs the other layouts at the byte scale too: the same bound at the same scale, value for value.
+    // Flank rows per DP row ON the level image: 6 (one DP row per k-mer class, align_screen6_kernel: half the cells of a step) where the image
+    // is the default and the launch is larger than one round of workgroups (below), 3 where STRQ_SCREEN_LDS pins a layout -- the three merge-3 kernels stay what they were -- and where no byte
+    // scale makes hh a multiple of 6.  STRQ_SCREEN2_MERGE=3|6 pins it (6 together with STRQ_SCREEN_LDS=levels: the new kernel on any read
+    // size, tests).  The frame of what leaves the kernel is that of merge 3 either way.
     bool levels = false;
     if (merge == 3) {
         const char* e = strq::opt("STRQ_SCREEN_LDS");
+        int rows_per = e ? 3 : 6;
+        // ... and only where the launch holds more reads than workgroups are resident (two per CU on the image).  There the screen's time is
+        // throughput, and halving the cells saves twice what the looser bound costs the exact pass (4096 reads: -25 ms against +13 ms per
+        // step).  A launch that fits one round of workgroups lasts as long as its longest read whichever kernel runs -- a few ms to win --
+        // while its exact pass grows all the same: 512 reads measure 43.1 / 43.9 ms per step at three rows and 43.5 / 44.2 at six, the
+        // Viterbi's 41.5 ms binding either (profiles/screen_class_rows.md)
+        if (ngr <= 2 * c->n_cu) rows_per = 3;
+        if (const char* mg = strq::opt("STRQ_SCREEN2_MERGE")) { const int v = atoi(mg); if (v == 3 || v == 6) rows_per = v; }
         ScreenParams spb;
-        if (screen2_levels_plan(c->ap, p.S, max_n, merge, &spb)) {
+        bool plan = screen2_levels_plan(c->ap, p.S, max_n, rows_per, &spb) != 0;
+        if (!plan && rows_per == 6) { rows_per = 3; plan = screen2_levels_plan(c->ap, p.S, max_n, rows_per, &spb) != 0; }
+        if (plan) {
             levels = !e || std::strcmp(e, "levels") == 0;
             for (size_t x = 0; levels && x < pairs.size(); ++x)
                 levels = screen2_levels_fit(screen2_levels_rows(screen2_levels_range((uint32_t)p.info[p.J0[pairs[x].first]].lvl, (uint32_t)p.info[p.J0[pairs[x].second]].lvl)));
@@ -665,13 +679,16 @@ static int screen_two_flank(CorePlan& p, int merge, int max_n)
                 }
                 levels = extra <= 0.10 * all && used * 10 >= 9L * STRQ_SCREEN_SEG_LEVELS * (long)pairs.size();
             }
-            if (levels) sp = spb;
-            else if (strq::opt("STRQ_SCREEN2_BYTE_SCALE")) sp = screen2_byte_frame(spb);
+            if (levels) { sp = spb; merge = rows_per; }
+            else if (strq::opt("STRQ_SCREEN2_BYTE_SCALE") && screen2_levels_plan(c->ap, p.S, max_n, 3, &spb)) sp = screen2_byte_frame(spb);          // merge 3's byte scale
         }
     }
-    sp.margin = (int32_t)std::lround((double)c->coarse_margin * (merge == 3 ? 1.3 : 1.0) * sp.sc);
+    sp.margin = (int32_t)std::lround((double)c->coarse_margin * (fine_rules ? 1.0 : 1.3) * sp.sc);
     if (const char* e = strq::opt("STRQ_SCREEN2_MARGIN")) sp.margin = (int32_t)std::lround(atof(e) * sp.sc);
     sp.max_cand = 8;          // (8, 16, 32 candidates and margins of 300 ... 700 score units measure within 1.5 % of each other: run r5n)
+    // six rows per DP row: the bound is ~70 score units looser, and with eight candidates 27 % of a first step's alignments went to the
+    // second look (24.7 % over six steps); sixteen leave 17 % (profiles/screen_class_rows.md, gates B and C)
+    if (merge == 6) sp.max_cand = 16;
     if (const char* e = strq::opt("STRQ_SCREEN2_MAX_CAND")) sp.max_cand = atoi(e);
     if (fine_rules) { sp.margin = 0; sp.max_cand = 0; }          // the fine screen's rule: everything within m + 2 slack of the best chunk
     ScreenJob j;
@@ -731,9 +748,10 @@ static int run_screens(CorePlan& p)
     int max_n = 0;
     for (int i = 0; i < nb; ++i) max_n = std::max(max_n, in.n[i]);
     c->screen_mode_last = 0;
-    // flank rows per DP row of the coarse screen.  Measured on configs[2] (run r5j): screen 114.4 / 94.7 / 96.6 ms per 4096 reads
-    // at 2 / 3 / 6 rows, forward stage 131.6 / 115.8 / 130.9 ms -- with six rows per DP row the 10 table reads of a step bind, and
-    // the looser bound sends 14 % of the alignments into the second look (2.4 % at two, 6 % at three)
+    // flank rows per DP row of the coarse screen: 3 here, the frame (scale, margin, bounds) of everything behind the kernel; on the level
+    // image screen_two_flank takes 6 -- one DP row per k-mer class, half the cells of a step.  (On the 16-bit class rows six rows lost: ten
+    // clamped look-ups of two VALU instructions each on random banks bound the step.  On the image a look-up is one ds_read_u8 without a
+    // VALU instruction or a bank conflict: profiles/screen_class_rows.md)
     const int coarse_merge = 3;
     p.g2_of.assign(nb, -1);
     for (int attempt = 0; attempt < 2 && !p.screen2_ran; ++attempt) {
