@@ -204,6 +204,23 @@ int strq_viterbi_tracts(strq_ctx* ctx, int32_t model_id, int64_t n_seq, const do
  */
 int strq_viterbi_tract_positions(strq_ctx* ctx, int32_t model_id, int64_t n_seq, const double* x, const int64_t* x_off,
                                  double* logp, int64_t* counts, int32_t* status, int64_t* pos_off, int64_t* pool, int64_t pool_cap);
+/*
+ * State statistics of the best path (strique_amd/state_stats.py states the rule): for n_seq float64 windows as they are given
+ * (x_off[n_seq + 1] from 0, at most 8192 windows, offsets must not decrease) and every emitting state s < silent_start of the model,
+ *   n_obs[i n_emit + s]  observations of window i that strq_viterbi's best path emits from s and that are numbers (a NaN is skipped)
+ *   sum, sumsq           their sum and the sum of their squares: float64 from +0.0, one addition per observation in ascending
+ *                        order, the square rounded before it is added -- defined to the bit
+ * rows of n_emit = silent_start entries, row-major; a state the path never visits has 0, +0.0, +0.0.  The windows are decoded as by
+ * strq_viterbi_batch (logp, counted: its bits), those with a path once more with back-pointers (the model's lane row or the general
+ * kernel), traced back and summed by state_stats_kernel -- the kernels of the pass of strq_set_state_stats -- in pieces of at most
+ * STRQ_STATE_STATS_WS_BYTES of back-pointers (default 8 GiB).
+ *   status  0 ok, 1 no path (zero rows), 4: decoded, logp and counted valid, but the window's back-pointers alone exceed the
+ *           budget -- not traced, zero rows
+ * logp, counted, status are nullable.  Every model strq_model_create accepts.  STRQ_ERR_DEVICE when the back-pointer decode of a
+ * window disagrees with its count decode in logp bits or counted.
+ */
+int strq_viterbi_state_stats(strq_ctx* ctx, int32_t model_id, int64_t n_seq, const double* x, const int64_t* x_off,
+                             double* logp, int64_t* counted, int32_t* status, int64_t* n_obs, double* sum, double* sumsq);
 /* Test hook: the kernel shape id (as strq_debug_viterbi_plan gives it) of the context's last tract launch; -1 before the first. */
 int strq_debug_tract_shape(const strq_ctx* ctx, int32_t* shape);
 
@@ -539,6 +556,27 @@ int strq_batch_fetch_tract_positions(strq_ctx* ctx, int32_t* pos_status, int64_t
 /* The tract-position pass of the last run call: out[0] = ms on the GPU (all its sub-batches), out[1] = windows traced,
  * out[2] = kernels launched (sorts, decodes, tracebacks, scans; 0 with the switch off), out[3] = peak back-pointer bytes of a piece. */
 int strq_last_tract_positions(strq_ctx* ctx, double* out4);
+/* ---- state statistics: what the best path of the flanked decode assigns to every emitting state (no counterpart in the reference;
+ * strique_amd/state_stats.py states the rule, strique_amd/calibrate.py re-estimates k-mer levels from it) ----
+ * on = 1: later run calls, once the rows of a sub-batch are on the host, decode every window whose gate passed and whose flanked decode
+ * found a path once more with back-pointers -- the task of the count / MARK launch: same window, same affine source on the filtered
+ * signal, (T + 1) * n_states * 2 bytes -- trace it back and sum the observations per emitting state as strq_viterbi_state_stats does.
+ * Pieces of at most STRQ_STATE_STATS_WS_BYTES of back-pointers (default 8 GiB), launches grouped by kernel shape, one read-back and one
+ * wait per piece; a window whose back-pointers alone exceed the budget is not traced (status 2).  A run call with the switch on fails
+ * before any launch: STRQ_ERR_ARG in a scan, STRQ_ERR_UNSUPPORTED when a target's model has no back-pointer decode.  STRQ_ERR_DEVICE
+ * when the back-pointer decode of a window disagrees with its count decode in logp bits or counted.  Rows and every other output do not
+ * change.  Sub-batches still in flight keep the mode they were launched with (the call waits for them).  Default 0: no further kernel
+ * runs, no further buffer is reserved. */
+int strq_set_state_stats(strq_ctx* ctx, int32_t on);
+/* State statistics of the last batch of n reads, ragged: off[n + 1], read i owns entries off[i] .. off[i + 1] of the three pools --
+ * silent_start of its flanked model, or none for a read without statistics; status[i] (nullable): 0 statistics, 1 none (the gate
+ * failed, the read was not conditioned, or the flanked decode found no path), 2 back-pointers over the budget.  The pools (cap entries
+ * each) may all be NULL to query the total in off[n], like strq_batch_fetch_units.  STRQ_ERR_ARG when the last run call ran with the
+ * switch off. */
+int strq_batch_fetch_state_stats(strq_ctx* ctx, int64_t* off, int64_t* n_obs, double* sum, double* sumsq, int64_t cap, int32_t* status);
+/* The state-statistics pass of the last run call: out[0] = ms on the GPU (all its sub-batches), out[1] = windows traced,
+ * out[2] = kernels launched (sorts, decodes, tracebacks, sums; 0 with the switch off), out[3] = peak back-pointer bytes of a piece. */
+int strq_last_state_stats(strq_ctx* ctx, double* out4);
 /* ---- renorm: a second normalisation step for reads that are mostly repeat (no counterpart in the reference, whose 'minmax' map,
  * STRique.py:150-180, assumes that a read's k-mer composition looks like the pore model's) ----
  * Between the conditioning statistics and the flank alignments, every conditioned read of a target with tables gets scale and shift

@@ -1245,6 +1245,91 @@ def plot(argv):
     return made
 
 
+def calibrate_reads(items, counter, min_score):
+    """One pass of `calibrate` over a batch: items [(target, raw signal, strand)] through counter.state_stats_batch; the records
+    calibrate.pool takes, of the reads that have statistics and whose two flank scores are at least min_score."""
+    records = []
+    for (target, _, strand), (row, stats) in zip(items, counter.state_stats_batch(items)):
+        if stats is None or row[1] < min_score or row[2] < min_score:
+            continue
+        model = counter.targets[target][0 if strand == '+' else 1].repeatHMM
+        records.append((model.state_kmers(),) + tuple(stats))
+    return records
+
+
+def calibrate(argv):
+    from . import calibrate as cal
+    parser = argparse.ArgumentParser(prog="STRique.py calibrate",
+                                     description="Re-estimate the k-mer levels of the configured repeat loci from the reads that span them: the mean of the "
+                                                 "observations the best path of the count decode assigns to every match state (one pass; for a second "
+                                                 "round run the command again with the table it wrote as the model)")
+    parser.add_argument("f5Index", help="Fast5 index")
+    parser.add_argument("model", help="Pore model")
+    parser.add_argument("repeat", help="Repeat region config file")
+    parser.add_argument("--out", required=True, metavar="MODEL", help="The re-estimated pore model: every k-mer of the input table in input order")
+    parser.add_argument("--min-score", dest="min_score", type=float, default=None, metavar="S",
+                        help="A read contributes when both of its flank scores are at least S.  Required: there is no default (README, 'Calibrate')")
+    parser.add_argument("--min-obs", dest="min_obs", type=int, default=None, metavar="N",
+                        help="A k-mer's mean is replaced when at least N observations were assigned to it: the standard error of a level is stdv / sqrt(N).  "
+                             "Required: there is no default (README, 'Calibrate')")
+    parser.add_argument("--stats", default=None, metavar="FILE", help="Also write one row per k-mer seen to FILE, columns " + " ".join(cal.STATS_HEADER))
+    parser.add_argument("--config", help="Config file with HMM transition probabilities")
+    parser.add_argument("--algn", default=None, help="Alignment in sam format, if not given read from stdin")
+    parser.add_argument("--batch", type=int, default=2048, help="Reads per GPU batch")
+    parser.add_argument("--device", type=int, default=0, help="HIP device")
+    parser.add_argument("--log_level", default='warning', choices=LEVELS, help="Log level")
+    parser.add_argument("--mod_model", default=None, help=argparse.SUPPRESS)
+    parser.add_argument("--scan", action="store_true", help=argparse.SUPPRESS)
+    args = parser.parse_args(argv)
+    if args.min_score is None:
+        parser.error("calibrate needs --min-score S: which reads hold their flanks well enough to teach the table is the caller's decision, so there is no default")
+    if args.min_obs is None:
+        parser.error("calibrate needs --min-obs N: the standard error of a level is stdv / sqrt(N), so there is no default")
+    if args.min_obs < 1:
+        parser.error("--min-obs must be at least 1")
+    if args.mod_model:
+        parser.error("calibrate cannot be combined with --mod_model: it re-estimates the levels of one table from the flanked decode")
+    if args.scan:
+        parser.error("calibrate cannot be combined with --scan: the state statistics are not available in a scan")
+    from . import dist as sdist
+    if sdist.env_rank_world()[1] > 1:
+        parser.error("calibrate runs in a single process: the statistics of several ranks are not pooled")
+    log = Log(args.log_level)
+    config = parse_config(args.repeat, args.config, log)
+    for path, what in ((args.f5Index, "Fast5 index file"), (args.model, "Pore model file")):
+        if not os.path.isfile(path):
+            log("Main: %s does not exist." % what, 'error'); raise SystemExit(1)
+    from .counter import repeatCounter
+    counter = repeatCounter(args.model, align_config=config['align'], HMM_config=config['HMM'], device=args.device)
+    loci = defaultdict(list)
+    for name, (chrom, begin, end, repeat, prefix, suffix) in config['repeat'].items():
+        counter.add_target(name, repeat, prefix, suffix)
+        loci[chrom].append((name, begin, end))
+    f5 = Fast5Index(args.f5Index)
+    stream = open(args.algn) if args.algn else sys.stdin
+    records, batch, n_reads = [], [], 0
+    try:
+        for qname, strand, targets, _ in route(stream, loci, log):
+            raw = f5.get_raw(qname)
+            if raw is None:
+                log("Detector: No fast5 for ID %s" % qname, 'warning'); continue
+            for target in targets:
+                batch.append((target, raw, strand)); n_reads += 1
+            if len(batch) >= max(1, args.batch):
+                records += calibrate_reads(batch, counter, args.min_score); batch = []
+        if batch:
+            records += calibrate_reads(batch, counter, args.min_score)
+    finally:
+        if args.algn:
+            stream.close()
+    new_means, rows = cal.estimate(cal.pool(records), counter.pm, args.min_obs)
+    cal.write_model(args.out, counter.pm, new_means)
+    if args.stats:
+        with open(args.stats, 'w') as fp:
+            fp.write(cal.format(rows))
+    log("Main: %d of %d read(s) contributed, %d k-mer(s) updated." % (len(records), n_reads, len(new_means)), 'info')
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     parser = argparse.ArgumentParser(description='STRique: a nanopore raw signal repeat detection pipeline (MI355X engine)',
@@ -1253,6 +1338,7 @@ Available commands are:
    index      Index batch(es) of bulk-fast5 or tar archived single fast5
    count      Count single read repeat expansions
    plot       Plot repeat signal after counting
+   calibrate  Re-estimate the k-mer levels of the repeat loci from spanning reads
 ''')
     parser.add_argument('command', help='Subcommand to run')
     args = parser.parse_args(argv[:1])
@@ -1262,6 +1348,8 @@ Available commands are:
         index(argv[1:])
     elif args.command == 'plot':
         plot(argv[1:])
+    elif args.command == 'calibrate':
+        calibrate(argv[1:])
     else:
         print('Unrecognized command', file=sys.stderr)
         parser.print_help(file=sys.stderr)

@@ -429,6 +429,33 @@ class repeatCounter(object):
             out[i] = (d.row,) + extra if extra else d.row
         return out
 
+    def state_stats_batch(self, items):
+        """items: iterable of (target_name, raw_signal, strand).  Returns [(row, stats)] in input order: row the tuple detect()
+        returns, unchanged; stats None -- the gate failed, the read was not conditioned, the flanked decode found no path, or the
+        window's back-pointers exceed STRQ_STATE_STATS_WS_BYTES -- or (n, sum, sumsq): per emitting state of the read's flanked model
+        (targets[name][0 | 1].repeatHMM.state_kmers() says what each stands for) the count, the sum and the sum of squares of the
+        observations the best path assigns to it (strique_amd.state_stats states the rule, strique_amd.calibrate uses it).  A method
+        of its own, not a keyword of detect_batch: it turns the context's switch on around the run and off again before it returns;
+        the switches of the counter (set_renorm, ...) work underneath it.  Not with scan_batch."""
+        items = list(items)
+        request = {p.name: getattr(self, p.name) for p in PASSES if not p.keyword and getattr(self, p.name)}
+        reads = [(self._classifier_for(t, s).target_id, np.asarray(r)) for t, r, s in items]
+        out = [None] * len(items)
+        is_int = [self._fits_int16(r) for _, r in reads]
+        try:
+            for want_int in (True, False):          # one device batch each, as _run splits them: the statistics are those of the last batch
+                idx = [i for i, f in enumerate(is_int) if f == want_int]
+                if not idx:
+                    continue
+                self.ctx.set_state_stats(True)
+                rows = {k: d.row for k, d, _, _ in self._run([reads[i] for i in idx], request)}
+                stats = self.ctx.batch_fetch_state_stats()
+                for k, i in enumerate(idx):
+                    out[i] = (rows[k], stats[k])
+        finally:
+            self.ctx.set_state_stats(False)
+        return out
+
     @contextlib.contextmanager
     def _switches(self, request):
         """The passes of `request` ({name: value}, see PASSES) are on inside the block, and every pass is off after it."""

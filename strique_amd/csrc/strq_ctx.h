@@ -196,6 +196,15 @@ int forward_model(strq_ctx* c, HostModel* hm);
 struct TractPosWindow { VitTask task; const HostModel* hm; int64_t base; int64_t n[3]; };
 struct TractPosOut { std::vector<int32_t> status; std::vector<std::vector<int64_t>> pos; };
 int tract_positions(strq_ctx* c, const std::vector<TractPosWindow>& w, TractPosOut& out, double* stats);
+// State statistics of decoded windows (strq_set_state_stats, strq_viterbi_state_stats; strq_detect_api.hip, the rule: strique_amd/
+// state_stats.py): every window once more with back-pointers, traced back and summed per emitting state (state_stats_kernel), in pieces
+// of at most STRQ_STATE_STATS_WS_BYTES of back-pointers.  task: the window as its count decode had it (bp is set here); logp, counted:
+// what that decode found -- a back-pointer decode with other bits fails the call (STRQ_ERR_DEVICE).  status[i]: 0 the rows n / sum /
+// sumsq[i] hold silent_start entries, 2 the window's back-pointers alone exceed the budget (no rows).  stats (or null): windows, kernels
+// launched, peak back-pointer bytes of a piece.
+struct StateStatsWindow { VitTask task; const HostModel* hm; double logp; int64_t counted; };
+struct StateStatsOut { std::vector<int32_t> status; std::vector<std::vector<int64_t>> n; std::vector<std::vector<double>> sum, sumsq; };
+int state_stats(strq_ctx* c, const std::vector<StateStatsWindow>& w, StateStatsOut& out, double* stats);
 void host_stats_batch(const double* signals, const int64_t* offsets, int64_t n_reads, bool want_raw, double* out,
                       const double* const* reads = nullptr);   // host_stats.hip; reads: one buffer per read instead of `signals`
 }

@@ -30,6 +30,7 @@
 #include "renorm_kernels.h"
 #include "variant_kernels.h"
 #include "flank_mod_kernels.h"
+#include "state_stats_kernels.h"
 
 using namespace strq;
 
@@ -132,6 +133,7 @@ struct DetectState {
     DevBuf fmod_ws, fmod_bp;             // flank methylation calls (run_flank_mod_pass): tasks, stretches and paths of a piece; its back-pointers
     DevBuf tract_ws, tract_task;         // tract pass (run_tract_pass): geometry and conditioning rows of a sub-batch; tasks, results, their reads and models
     DevBuf tpos_task, tpos_bp, tpos_path, tpos_pool;      // tract positions (tract_positions): tasks and results of a piece, its back-pointers, state paths, positions
+    DevBuf sst_task, sst_bp, sst_path, sst_out;           // state statistics (state_stats): tasks and results of a piece, its back-pointers, state paths, rows
     DevBuf anch_ws, anch_task;           // anchored pass (run_anchored_pass): geometry, conditioning rows and kinds of a sub-batch; tasks, results, their reads and models
     hipEvent_t amod_ev[2] = {};          // methylation calls of anchored reads (run_anchored_mod): their own bracket, inside the anchored pass
     // renorm (run_renorm_part): the tables of the targets, the grid and the shares, the histograms and the per-read table rows of a sub-batch
@@ -1116,6 +1118,129 @@ int tract_positions(strq_ctx* c, const std::vector<TractPosWindow>& w, TractPosO
     return STRQ_OK;
 }
 
+// State statistics of decoded windows (strq_ctx.h states the interface; strique_amd/state_stats.py the rule), built like
+// tract_positions: the windows of a piece grouped by kernel shape, decoded with back-pointers, traced back into a zeroed path buffer and
+// summed per emitting state (state_stats_kernel).  One read-back and one wait per piece; the buffers exist only once this ran.
+int state_stats(strq_ctx* c, const std::vector<StateStatsWindow>& w, StateStatsOut& out, double* stats)
+{
+    DetectState* d = dstate(c);
+    hipStream_t st = c->stream;
+    const size_t nw = w.size();
+    out.status.assign(nw, 0); out.n.assign(nw, std::vector<int64_t>()); out.sum.assign(nw, std::vector<double>()); out.sumsq.assign(nw, std::vector<double>());
+    size_t budget = (size_t)8 << 30;
+    if (const char* e = strq::opt("STRQ_STATE_STATS_WS_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
+    struct W { int i; int shape; size_t bytes; };
+    std::vector<W> ws;
+    for (size_t i = 0; i < nw; ++i) {
+        const VitModel& h = w[i].hm->h;
+        const int shape = vit_shape_for(h, VIT_BACKPTR);
+        if (shape < 0 || !vit_mode_ok(shape, VIT_BACKPTR)) { c->err = "state-stats: the model has no back-pointer decode"; return STRQ_ERR_UNSUPPORTED; }
+        if (w[i].hm->silent_start < 1 || w[i].hm->silent_start > STATE_STATS_MAX_EMIT) { c->err = "state-stats: the model's emitting states do not fit the kernel"; return STRQ_ERR_UNSUPPORTED; }
+        // back-pointers: uint16 per (time step, state); every window starts on a 16-byte boundary
+        const size_t bytes = ((size_t)(w[i].task.T + 1) * (size_t)h.n_states * 2 + 15) & ~(size_t)15;
+        if (bytes > budget) { out.status[i] = 2; continue; }
+        ws.push_back({(int)i, shape, bytes});
+    }
+    for (size_t c0 = 0; c0 < ws.size();) {
+        size_t c1 = c0, bytes = 0;
+        while (c1 < ws.size() && bytes + ws[c1].bytes <= budget) bytes += ws[c1++].bytes;          // (every window fits alone)
+        const int m = (int)(c1 - c0);
+        std::vector<GroupItem> items((size_t)m);
+        size_t path_n = 0, row_n = 0; int max_emit = 1;
+        for (int k = 0; k < m; ++k) {
+            const StateStatsWindow& x = w[(size_t)ws[c0 + (size_t)k].i];
+            items[(size_t)k] = {0, ws[c0 + (size_t)k].shape, x.hm->h.n_cells};
+            path_n += (size_t)x.task.T; row_n += (size_t)x.hm->silent_start;
+            max_emit = std::max(max_emit, (int)x.hm->silent_start);
+        }
+        const Grouping G = group_items(items);
+        Carve lay;
+        const size_t o_vt = lay.add<VitTask>((size_t)m), o_vr = lay.add<VitResult>((size_t)m), o_paths = lay.add<int32_t*>((size_t)m),
+                     o_ts = lay.add<StateStatsTask>((size_t)m), o_bad = lay.add<int32_t>((size_t)m), o_order = lay.add<int>((size_t)m);
+        STRQ_HIP(c, d->sst_task.reserve(lay.total() + 64));
+        void* tb = d->sst_task.p;
+        VitTask* d_vt = Carve::at<VitTask>(tb, o_vt); VitResult* d_vr = Carve::at<VitResult>(tb, o_vr); int32_t** d_paths = Carve::at<int32_t*>(tb, o_paths);
+        StateStatsTask* d_ts = Carve::at<StateStatsTask>(tb, o_ts); int32_t* d_bad = Carve::at<int32_t>(tb, o_bad); int* d_order = Carve::at<int>(tb, o_order);
+        STRQ_HIP(c, d->sst_bp.reserve(bytes));
+        STRQ_HIP(c, d->sst_path.reserve(path_n * 4 + 64));
+        STRQ_HIP(c, d->sst_out.reserve(row_n * 24 + 64));          // n | sum | sumsq, row_n entries each
+        int64_t* o_n = d->sst_out.as<int64_t>(); double* o_sum = reinterpret_cast<double*>(o_n + row_n); double* o_sq = o_sum + row_n;
+        std::vector<VitTask> tv((size_t)m); std::vector<int32_t*> pv((size_t)m); std::vector<StateStatsTask> sv((size_t)m);
+        std::vector<int> win_of((size_t)m); std::vector<size_t> row_off((size_t)m);
+        size_t wo = 0, po = 0, xo = 0;
+        for (int at = 0; at < m; ++at) {          // in task order: the back-pointers, the paths and the rows lie in that order too
+            const W& ww = ws[c0 + (size_t)G.order[(size_t)at]];
+            const StateStatsWindow& x = w[(size_t)ww.i];
+            VitTask t = x.task;
+            t.bp = reinterpret_cast<uint16_t*>(d->sst_bp.as<char>() + wo); wo += ww.bytes;
+            if (wo > d->sst_bp.cap) { c->err = "state-stats: workspace"; return STRQ_ERR_NOMEM; }
+            pv[(size_t)at] = d->sst_path.as<int32_t>() + po; po += (size_t)t.T;
+            StateStatsTask s; std::memset(&s, 0, sizeof(s));
+            s.path = pv[(size_t)at]; s.result = d_vr + at; s.n = o_n + xo; s.sum = o_sum + xo; s.sumsq = o_sq + xo;
+            s.n_emit = x.hm->silent_start; s.bad = d_bad + at;
+            row_off[(size_t)at] = xo; xo += (size_t)x.hm->silent_start;
+            tv[(size_t)at] = t; sv[(size_t)at] = s; win_of[(size_t)at] = ww.i;
+        }
+        STRQ_HIP(c, hipMemcpyAsync(d_vt, tv.data(), (size_t)m * sizeof(VitTask), hipMemcpyHostToDevice, st));
+        STRQ_HIP(c, hipMemcpyAsync(d_paths, pv.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
+        STRQ_HIP(c, hipMemcpyAsync(d_ts, sv.data(), (size_t)m * sizeof(StateStatsTask), hipMemcpyHostToDevice, st));
+        STRQ_HIP(c, hipMemsetAsync(d_bad, 0, (size_t)m * 4, st));
+        if (path_n) STRQ_HIP(c, hipMemsetAsync(d->sst_path.p, 0, path_n * 4, st));      // a traceback that stops early leaves valid states behind
+        double launches = 0;
+        const GroupHook trace = [&](const VitGroup& g) -> int {
+            if (launch_vit_traceback(st, d_vt + g.first, d_vr + g.first, d_paths + g.first, g.count)) { c->err = "state-stats: traceback launch failed"; return STRQ_ERR_DEVICE; }
+            launches += 1;
+            return STRQ_OK;
+        };
+        if (const int grc = launch_groups(c, st, G.groups, {d_vt, d_vr, d_order, {VIT_BACKPTR}, "state-stats: ", false, &launches, nullptr, trace})) return grc;
+        if (launch_state_stats(st, d_vt, d_ts, m, max_emit)) { c->err = "state-stats: kernel launch failed"; return STRQ_ERR_DEVICE; }
+        launches += 1;
+        std::vector<int64_t> rows(3 * row_n + 1); std::vector<int32_t> bad((size_t)m); std::vector<VitResult> vr((size_t)m);
+        STRQ_HIP(c, hipMemcpyAsync(rows.data(), d->sst_out.p, row_n * 24, hipMemcpyDeviceToHost, st));
+        STRQ_HIP(c, hipMemcpyAsync(bad.data(), d_bad, (size_t)m * 4, hipMemcpyDeviceToHost, st));
+        STRQ_HIP(c, hipMemcpyAsync(vr.data(), d_vr, (size_t)m * sizeof(VitResult), hipMemcpyDeviceToHost, st));
+        STRQ_HIP(c, hipStreamSynchronize(st));
+        const int64_t* h_n = rows.data(); const double* h_sum = reinterpret_cast<const double*>(h_n + row_n); const double* h_sq = h_sum + row_n;
+        for (int at = 0; at < m; ++at) {
+            const StateStatsWindow& x = w[(size_t)win_of[(size_t)at]];
+            const VitResult& v = vr[(size_t)at];
+            if (bad[(size_t)at] || v.status != 0 || std::memcmp(&v.logp, &x.logp, 8) != 0 || v.counted != x.counted) {
+                c->err = "state-stats: the back-pointer decode of a window disagrees with its count decode"; return STRQ_ERR_DEVICE;
+            }
+            const size_t o = row_off[(size_t)at], ne = (size_t)x.hm->silent_start, i = (size_t)win_of[(size_t)at];
+            out.n[i].assign(h_n + o, h_n + o + ne); out.sum[i].assign(h_sum + o, h_sum + o + ne); out.sumsq[i].assign(h_sq + o, h_sq + o + ne);
+        }
+        if (stats) { stats[0] += m; stats[1] += launches; stats[2] = std::max(stats[2], (double)bytes); }
+        c0 = c1;
+    }
+    return STRQ_OK;
+}
+
+// State statistics of the reads of one sub-batch (strq_set_state_stats): the windows the count / MARK launch decoded, once more with the
+// same tasks -- same windows, same affine source on the slot's filtered signal -- like the back-pointer route of the unit pass.  Runs on
+// the context's stream when the rows of the sub-batch are taken.
+static int run_state_stats_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, const Decoded& dec)
+{
+    Batch& B = d->batch;
+    const int64_t r0 = sl.r0;
+    const VitResult* vres = sl.host().vres;
+    if (const int rc = pass_start(c, pass_ev(d))) return rc;
+    std::vector<StateStatsWindow> sw;
+    for (int i : dec.who) {
+        const VitResult& v0 = vres[sl.vit_slot[i]];
+        StateStatsWindow x; x.task = dec.vt[(size_t)sl.vit_slot[i]]; x.task.bp = nullptr; x.hm = flank_model(c, d, r0 + i); x.logp = v0.logp; x.counted = v0.counted;
+        sw.push_back(x);
+    }
+    StateStatsOut so;
+    if (const int rc = state_stats(c, sw, so, d->stats[PASS_SSTATS].v)) return rc;
+    for (size_t k = 0; k < sw.size(); ++k) {
+        const size_t r = (size_t)(r0 + dec.who[k]);
+        B.sst_status[r] = so.status[k];
+        B.sst[r].n.swap(so.n[k]); B.sst[r].sum.swap(so.sum[k]); B.sst[r].sumsq.swap(so.sumsq[k]);
+    }
+    return pass_stop(c, pass_ev(d), d->stats[PASS_SSTATS]);
+}
+
 // Tract counts of the reads of one sub-batch (strq_set_tracts): every read whose gate passed, that was normalised, whose flanked decode
 // found a path and whose target has a compound model is decoded once more with that model, on the window of the count decode.  Runs
 // on the context's stream when the rows of the sub-batch are taken, like the forward pass: the geometry and the conditioning rows go
@@ -1707,12 +1832,13 @@ static int take_rows(strq_ctx* c, DetectState* d, DetectState::Slot& sl, bool un
     // the mode the launches ran with decides, not what the targets say by now
     if (sl.vit_mode == VIT_MARK) { const int mrc = run_mod_pass(c, d, sl); if (mrc) return mrc; }
     if (sl.vit_mode == VIT_MARK && sl.ex.var) { const int vrc = run_mod_pass(c, d, sl, DUAL_VAR); if (vrc) return vrc; }
-    if (sl.ex.units || sl.ex.conf) {
+    if (sl.ex.units || sl.ex.conf || sl.ex.sstats) {
         Decoded dec;
         if (const int drc = read_decoded(c, sl, dec)) return drc;
         if (!dec.who.empty()) {
             if (sl.ex.units) { const int urc = run_unit_pass(c, d, sl, dec); if (urc) return urc; }
             if (sl.ex.conf) { const int crc = run_conf_pass(c, d, sl, dec); if (crc) return crc; }
+            if (sl.ex.sstats) { const int src = run_state_stats_pass(c, d, sl, dec); if (src) return src; }
         }
     }
     if (sl.ex.tracts) { const int trc = run_tract_pass(c, d, sl); if (trc) return trc; }
@@ -2370,6 +2496,14 @@ int run_range(strq_ctx* c, DetectState* d, int64_t first, int64_t last)
         B.size_tpos();
     }
     if (d->extras.fmod) B.size_fmod();
+    if (d->extras.sstats) {
+        // nothing is launched for a call whose flanked models cannot be traced back
+        for (int64_t r = first; r < last; ++r) {
+            const VitModel& mh = c->models[d->targets[B.target_given.empty() ? B.target[(size_t)r] : B.target_given[(size_t)r]].model_id]->h;
+            if (!vit_mode_ok(vit_shape_for(mh, VIT_BACKPTR), VIT_BACKPTR)) { c->err = "state-stats: a target's model has no back-pointer decode"; return STRQ_ERR_UNSUPPORTED; }
+        }
+        B.size_sst();
+    }
     if (d->extras.renorm) {
         // nothing is launched for a call whose reads the pass could not fit
         if (!d->rn_have_grid) { c->err = "renorm: no tables (strq_target_set_renorm)"; return STRQ_ERR_ARG; }
@@ -2849,6 +2983,38 @@ int strq_last_tract_positions(strq_ctx* c, double* out4)
 {
     STRQ_ENTER(c);
     return last_pass(c, PASS_TPOS, out4);
+}
+
+int strq_set_state_stats(strq_ctx* c, int32_t on)
+{
+    STRQ_ENTER(c);
+    return set_extra(c, on, PASS_SSTATS);
+}
+
+int strq_batch_fetch_state_stats(strq_ctx* c, int64_t* off, int64_t* n_obs, double* sum, double* sumsq, int64_t cap, int32_t* status)
+{
+    STRQ_ENTER(c);
+    if (!off || cap < 0) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    const bool pools = n_obs || sum || sumsq;
+    if (pools && !(n_obs && sum && sumsq)) { c->err = "bad argument (strq_batch_fetch_state_stats: all pools or none)"; return STRQ_ERR_ARG; }
+    DetectState* d = dstate(c);
+    if (const int rc = fetch_begin(c, d, PASS_SSTATS)) return rc;
+    const Batch& B = d->batch;
+    const int64_t n = (int64_t)B.sst.size();
+    const int64_t done = pack_ragged(n, off, pools, cap, [&](int64_t i) { return (int64_t)B.sst[(size_t)i].n.size(); }, [&](int64_t i, int64_t pos) {
+        const ReadRows::StateStatsRow& r = B.sst[(size_t)i];
+        if (r.n.empty()) return;
+        std::memcpy(n_obs + pos, r.n.data(), r.n.size() * 8); std::memcpy(sum + pos, r.sum.data(), r.n.size() * 8); std::memcpy(sumsq + pos, r.sumsq.data(), r.n.size() * 8);
+    });
+    if (status) for (int64_t i = 0; i < done; ++i) status[i] = B.sst_status[(size_t)i];          // (of the reads that fitted)
+    if (done < n) { c->err = "state statistics pool too small"; return STRQ_ERR_ARG; }
+    return STRQ_OK;
+}
+
+int strq_last_state_stats(strq_ctx* c, double* out4)
+{
+    STRQ_ENTER(c);
+    return last_pass(c, PASS_SSTATS, out4);
 }
 
 int strq_target_set_flank_mod(strq_ctx* c, int32_t target_id, int32_t which, int32_t profile_model_id, int32_t flank_len,

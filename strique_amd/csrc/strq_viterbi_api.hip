@@ -1036,6 +1036,44 @@ int strq_viterbi_tract_positions(strq_ctx* c, int32_t model_id, int64_t n_seq, c
     return STRQ_OK;
 }
 
+int strq_viterbi_state_stats(strq_ctx* c, int32_t model_id, int64_t n_seq, const double* x, const int64_t* x_off,
+                             double* logp, int64_t* counted, int32_t* status, int64_t* n_obs, double* sum, double* sumsq)
+{
+    STRQ_ENTER(c);
+    if (model_id < 0 || model_id >= (int32_t)c->models.size() || !c->models[model_id] || n_seq < 0 || n_seq > 8192 || (n_seq > 0 && (!x_off || !n_obs || !sum || !sumsq))) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    if (n_seq == 0) return STRQ_OK;
+    const int64_t tot = x_off[n_seq];
+    if (x_off[0] != 0 || tot < 0 || (tot > 0 && !x)) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    for (int64_t i = 0; i < n_seq; ++i) if (x_off[i + 1] < x_off[i]) { c->err = "bad argument (x_off must not decrease)"; return STRQ_ERR_ARG; }
+    const HostModel* hm = c->models[model_id];
+    // the count decode first: logp, counted and status are strq_viterbi_batch's, and the observations stay in the context's buffer
+    std::vector<double> lp((size_t)n_seq); std::vector<int64_t> cn((size_t)n_seq); std::vector<int32_t> stv((size_t)n_seq);
+    if (const int rc = strq_viterbi_batch(c, model_id, n_seq, x, x_off, lp.data(), cn.data(), stv.data(), nullptr)) return rc;
+    const size_t ne = (size_t)hm->silent_start;
+    std::fill(n_obs, n_obs + (size_t)n_seq * ne, (int64_t)0); std::fill(sum, sum + (size_t)n_seq * ne, 0.0); std::fill(sumsq, sumsq + (size_t)n_seq * ne, 0.0);
+    std::vector<StateStatsWindow> sw; std::vector<int64_t> win;
+    for (int64_t i = 0; i < n_seq; ++i) {
+        if (stv[(size_t)i] != 0) continue;
+        StateStatsWindow w; std::memset(&w.task, 0, sizeof(w.task));
+        w.task.model = hm->dev; w.task.sig = c->vit_x.as<double>() + x_off[i]; w.task.T = x_off[i + 1] - x_off[i]; w.task.src_kind = VIT_SRC_F64;
+        w.hm = hm; w.logp = lp[(size_t)i]; w.counted = cn[(size_t)i];
+        sw.push_back(w); win.push_back(i);
+    }
+    StateStatsOut so;
+    if (!sw.empty()) { if (const int rc = state_stats(c, sw, so, nullptr)) return rc; }
+    for (size_t k = 0; k < sw.size(); ++k) {
+        const size_t i = (size_t)win[k];
+        if (so.status[k] == 2) { stv[i] = 4; continue; }
+        std::memcpy(n_obs + i * ne, so.n[k].data(), ne * 8); std::memcpy(sum + i * ne, so.sum[k].data(), ne * 8); std::memcpy(sumsq + i * ne, so.sumsq[k].data(), ne * 8);
+    }
+    for (int64_t i = 0; i < n_seq; ++i) {
+        if (logp) logp[i] = lp[(size_t)i];
+        if (counted) counted[i] = cn[(size_t)i];
+        if (status) status[i] = stv[(size_t)i];
+    }
+    return STRQ_OK;
+}
+
 int strq_debug_tract_shape(const strq_ctx* c, int32_t* shape)
 {
     if (!c || !shape) return STRQ_ERR_ARG;

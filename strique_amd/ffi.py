@@ -347,6 +347,7 @@ class Context(object):
         self._check(self._lib.strq_model_create(self._h, ctypes.c_int32(baked.n_states), ctypes.c_int32(baked.silent_start),
                                                 ctypes.c_int32(baked.start), ctypes.c_int32(baked.end),
                                                 *[_ptr(a) for a in arrs], ctypes.byref(mid)))
+        self.__dict__.setdefault('_model_emit', {})[mid.value] = int(baked.silent_start)      # row length of viterbi_state_stats
         psum = getattr(baked, 'in_logp_sum', None)
         if psum is not None and len(psum) == len(baked.in_logp) and np.all(psum >= baked.in_logp) and not np.array_equal(psum, baked.in_logp):
             # edges that stand for several parallel paths: the forward pass sums them (the decode took the largest).  Arrays whose
@@ -468,6 +469,20 @@ class Context(object):
         self._check(self._lib.strq_viterbi_tract_positions(self._h, ctypes.c_int32(model_id), ctypes.c_int64(n), _ptr(x), _ptr(off), _ptr(logp), _ptr(counts),
                                                            _ptr(status), _ptr(pos_off), _ptr(pool), ctypes.c_int64(len(pool))))
         return logp, counts, status[:n], [tuple(pool[pos_off[3 * i + j]:pos_off[3 * i + j + 1]].copy() for j in range(3)) for i in range(n)]
+
+    def viterbi_state_stats(self, model_id, xs):
+        """strq_viterbi_state_stats: xs a list of float64 arrays (NaN: missing).  Returns (logp[], counted[], status[], n, sum,
+        sumsq): logp / counted as viterbi_batch gives them, n (int64), sum and sumsq (float64) of shape (windows, silent_start) --
+        what the best path assigns to every emitting state (strique_amd/state_stats.py); status 0 ok, 1 no path, 4 the window's
+        back-pointers exceed STRQ_STATE_STATS_WS_BYTES (logp and counted valid, zero rows)."""
+        n = len(xs)
+        x, off = _offsets(xs, np.float64)
+        n_emit = int(self._model_emit[model_id])
+        logp = np.zeros(n); counted = np.zeros(n, np.int64); status = np.zeros(max(1, n), np.int32)
+        cnt = np.zeros((max(1, n), n_emit), np.int64); s1 = np.zeros((max(1, n), n_emit)); s2 = np.zeros((max(1, n), n_emit))
+        self._check(self._lib.strq_viterbi_state_stats(self._h, ctypes.c_int32(model_id), ctypes.c_int64(n), _ptr(x), _ptr(off), _ptr(logp), _ptr(counted),
+                                                       _ptr(status), _ptr(cnt), _ptr(s1), _ptr(s2)))
+        return logp, counted, status[:n], cnt[:n], s1[:n], s2[:n]
 
     def debug_tract_shape(self):
         """strq_debug_tract_shape: the kernel shape id of this context's last tract launch (-1: none yet)."""
@@ -677,6 +692,29 @@ class Context(object):
         """The tract-position pass of the last run call (strq_last_tract_positions): {'ms', 'windows' (traced), 'launches', 'bp_bytes'
         (peak back-pointer bytes of a piece)}."""
         return self._last("tract_positions", ("ms", "windows", "launches", "bp_bytes"), floats=("ms", "bp_bytes"))
+
+    def set_state_stats(self, on):
+        """strq_set_state_stats: later run calls also sum, per emitting state of the flanked model, the observations the best path
+        assigns to it (batch_fetch_state_stats; strique_amd/state_stats.py states the rule)."""
+        self._switch("state_stats", on)
+
+    def batch_fetch_state_stats(self, with_status=False):
+        """State statistics of the last batch (strq_batch_fetch_state_stats): per read None, or (n, sum, sumsq) -- np.int64 / float64
+        arrays with one entry per emitting state of the read's flanked model.  with_status: (status[], that list) -- 0 statistics,
+        1 none, 2 back-pointers over the budget."""
+        n = getattr(self, '_n_batch', 0)
+        off = np.zeros(n + 1, np.int64); st = np.zeros(max(1, n), np.int32)
+        self._check(self._lib.strq_batch_fetch_state_stats(self._h, _ptr(off), None, None, None, ctypes.c_int64(0), _ptr(st)))
+        m = max(1, int(off[-1]))
+        cnt = np.zeros(m, np.int64); s1 = np.zeros(m); s2 = np.zeros(m)
+        self._check(self._lib.strq_batch_fetch_state_stats(self._h, _ptr(off), _ptr(cnt), _ptr(s1), _ptr(s2), ctypes.c_int64(m), _ptr(st)))
+        out = [None if st[i] != 0 else (cnt[off[i]:off[i + 1]].copy(), s1[off[i]:off[i + 1]].copy(), s2[off[i]:off[i + 1]].copy()) for i in range(n)]
+        return (st[:n].copy(), out) if with_status else out
+
+    def last_state_stats(self):
+        """The state-statistics pass of the last run call (strq_last_state_stats): {'ms', 'windows' (traced), 'launches', 'bp_bytes'
+        (peak back-pointer bytes of a piece)}."""
+        return self._last("state_stats", ("ms", "windows", "launches", "bp_bytes"), floats=("ms", "bp_bytes"))
 
     def target_set_flank_mod(self, target_id, which, profile_model_id, flank_len, column_of, groups):
         """strq_target_set_flank_mod: the models of flank `which` (0 prefix, 1 suffix, as the strand of the target reads it) --

@@ -205,6 +205,21 @@ class FlankedRepeatModel(object):
         self.count_states = (rep.d1, rep.d2)
         self.count_bias = self.flanking_count - self.repeat_offset
         self.baked = bake(g, count_states=self.count_states, tag_substring='repeat')
+        # what every emitting state stands for (state_kmers): section, column type and, for a match state, the k-mer of its column
+        k = pm.kmer
+        rep_seq = extend_repeat(repeat, k)[0]
+        what = {rep.d1: ('repeat', 'dummy', None), rep.d2: ('repeat', 'dummy', None)}
+        for section, prof, seq in (('prefix', pre, prefix_seq), ('repeat', rep.profile, rep_seq), ('suffix', suf, suffix_seq)):
+            for c_, st in enumerate(prof.match): what[st] = (section, 'match', seq[c_:c_ + k])
+            for st in prof.insert: what[st] = (section, 'insert', None)
+        self._state_what = what
+
+    def state_kmers(self):
+        """Per emitting state in baked order (state s of a decode path, s < baked.silent_start): (section, kind, kmer) -- section
+        'prefix' | 'repeat' | 'suffix', kind 'match' | 'insert' | 'dummy', kmer the k-mer of a match state's column (prefix_seq[c:c+k],
+        the extend_repeat sequence for the loop, suffix_seq[c:c+k]) and None otherwise.  The sequences are the model's own: a model
+        built for the - strand carries the k-mers of the reverse-complemented locus."""
+        return [self._state_what[int(o)] for o in self.baked.orig_index[:self.baked.silent_start]]
 
 
 class CompoundRepeatModel(object):
