@@ -221,6 +221,26 @@ int strq_viterbi_tract_positions(strq_ctx* ctx, int32_t model_id, int64_t n_seq,
  */
 int strq_viterbi_state_stats(strq_ctx* ctx, int32_t model_id, int64_t n_seq, const double* x, const int64_t* x_off,
                              double* logp, int64_t* counted, int32_t* status, int64_t* n_obs, double* sum, double* sumsq);
+/*
+ * State posteriors, the soft counterpart of strq_viterbi_state_stats (strique_amd/state_posteriors.py states the rule): for n_seq
+ * float64 windows as they are given (x_off[n_seq + 1] from 0, at most 8192 windows, offsets must not decrease) and every emitting
+ * state s < silent_start of the model, with gamma_t(s) = P(the path emits x_t from s | x) over all start -> end paths (the transition
+ * probabilities of the forward pass: strq_model_set_forward_logp),
+ *   w[i n_emit + s]   sum of gamma_t(s) over the observations t of window i that are numbers (a NaN is skipped)
+ *   wx, wxx           sum of gamma_t(s) x_t and of gamma_t(s) x_t^2 over the same t
+ *   log_lik           log sum_paths P(path, x), the quantity strq_forward_batch reports (-inf without a path)
+ * rows of n_emit = silent_start entries, row-major, float64.  Forward-backward in linear space, one wave per window
+ * (posterior_kernels.hip): rescaled by a power of two after every time step (no interval switch; STRQ_FWD_RESCALE_EVERY is not
+ * read), deterministic to the bit -- no atomics on values, no tree reduction, nothing depends on which windows share the call or on
+ * how it was cut into pieces -- and not defined to the bit against a log-space restatement.  The forward half stores its scaled
+ * vector of every time step: T * epl * 64 * 8 + 4 T bytes per window (epl = ceil(n_emit / 64)), in pieces of at most
+ * STRQ_STATE_POST_WS_BYTES of them (default 8 GiB).
+ *   status  0 ok, 1 no path (zero rows, log_lik -inf), 4: log_lik valid, but the window's stored vectors alone exceed the budget --
+ *           no backward half, zero rows
+ * log_lik, status are nullable.  Models with a forward kernel (see strq_forward_batch); others return STRQ_ERR_UNSUPPORTED.
+ */
+int strq_forward_state_stats(strq_ctx* ctx, int32_t model_id, int64_t n_seq, const double* x, const int64_t* x_off,
+                             double* log_lik, int32_t* status, double* w, double* wx, double* wxx);
 /* Test hook: the kernel shape id (as strq_debug_viterbi_plan gives it) of the context's last tract launch; -1 before the first. */
 int strq_debug_tract_shape(const strq_ctx* ctx, int32_t* shape);
 
@@ -577,6 +597,26 @@ int strq_batch_fetch_state_stats(strq_ctx* ctx, int64_t* off, int64_t* n_obs, do
 /* The state-statistics pass of the last run call: out[0] = ms on the GPU (all its sub-batches), out[1] = windows traced,
  * out[2] = kernels launched (sorts, decodes, tracebacks, sums; 0 with the switch off), out[3] = peak back-pointer bytes of a piece. */
 int strq_last_state_stats(strq_ctx* ctx, double* out4);
+/* ---- state posteriors: the soft counterpart of the state statistics (no counterpart in the reference; strique_amd/state_posteriors.py
+ * states the rule, `calibrate --posterior` re-estimates k-mer levels from it) ----
+ * on = 1: later run calls, once the rows of a sub-batch are on the host, run forward-backward (strq_forward_state_stats) over every
+ * window whose gate passed and whose flanked decode found a path -- the task of the count / MARK launch: same window, same affine
+ * source on the filtered signal.  Pieces of at most STRQ_STATE_POST_WS_BYTES of stored forward vectors (default 8 GiB), launches
+ * grouped by kernel shape, one read-back and one wait per piece; a window whose vectors alone exceed the budget gets its likelihood
+ * and no rows (status 2).  A run call with the switch on fails before any launch: STRQ_ERR_ARG in a scan, STRQ_ERR_UNSUPPORTED when a
+ * target's flanked model has no forward kernel.  Rows and every other output do not change.  Sub-batches still in flight keep the
+ * mode they were launched with (the call waits for them).  Default 0: no further kernel runs, no further buffer is reserved. */
+int strq_set_state_posteriors(strq_ctx* ctx, int32_t on);
+/* State posteriors of the last batch of n reads, ragged like strq_batch_fetch_state_stats: off[n + 1], read i owns entries off[i] ..
+ * off[i + 1] of the three pools -- silent_start of its flanked model, or none; log_lik[i] (nullable): the forward log-likelihood of its
+ * window (NaN for a read that was not decoded, -inf without a forward path); status[i] (nullable): 0 statistics, 1 none (the gate
+ * failed, the read was not conditioned, the flanked decode found no path, or the forward pass found none), 2 stored vectors over the
+ * budget.  The pools (cap entries each) may all be NULL to query the total in off[n].  STRQ_ERR_ARG when the last run call ran with the
+ * switch off. */
+int strq_batch_fetch_state_posteriors(strq_ctx* ctx, int64_t* off, double* w, double* wx, double* wxx, int64_t cap, double* log_lik, int32_t* status);
+/* The state-posteriors pass of the last run call: out[0] = ms on the GPU (all its sub-batches), out[1] = windows, out[2] = kernels
+ * launched (sorts, forward and backward halves; 0 with the switch off), out[3] = peak bytes of stored forward vectors of a piece. */
+int strq_last_state_posteriors(strq_ctx* ctx, double* out4);
 /* ---- renorm: a second normalisation step for reads that are mostly repeat (no counterpart in the reference, whose 'minmax' map,
  * STRique.py:150-180, assumes that a read's k-mer composition looks like the pore model's) ----
  * Between the conditioning statistics and the flank alignments, every conditioned read of a target with tables gets scale and shift

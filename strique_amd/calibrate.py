@@ -16,10 +16,21 @@ decodes.  The rule, said once:
 Limits: means only (no stdv fitting); only the k-mers of the configured loci; the decode clips observations to
 [model_min + .5, model_max - .5], which biases levels at the edge of the range; hard assignment -- two neighbouring k-mers with
 nearly equal levels share their error.
+
+Soft assignment (`calibrate --posterior`): the same estimator over the state posteriors (strique_amd/state_posteriors.py) -- the EM
+(Baum-Welch) step where the rule above is segmental k-means.  Every observation is shared among the states in proportion to the
+posterior probability that the state emitted it:
+
+    pool_posterior  per k-mer  W = math.fsum of w,  S and Q = math.fsum of wx and wxx over the per-(read, state) rows of the states
+                    that carry it; a read counts in n_reads where that k-mer's states together hold at least one expected
+                    observation (sum of w >= 1)
+    estimate        unchanged, on the float W: the new mean is S / W where W >= min_obs
+    --stats         the third column is `exp_obs` (a repr float) instead of `n_obs`
 """
 import math
 
 STATS_HEADER = ['kmer', 'n_reads', 'n_obs', 'mean', 'sd', 'table_mean', 'table_stdv', 'delta', 'updated']
+STATS_HEADER_POSTERIOR = STATS_HEADER[:2] + ['exp_obs'] + STATS_HEADER[3:]
 
 
 def pool(records):
@@ -39,6 +50,33 @@ def pool(records):
                 seen.add(kmer); p[0] += 1
             p[1] += int(ni); p[2].append(float(si)); p[3].append(float(qi))
     return {k: (parts[k][0], parts[k][1], math.fsum(parts[k][2]), math.fsum(parts[k][3])) for k in sorted(parts)}
+
+
+def pool_posterior(records):
+    """records: per read (state_kmers, w, wx, wxx) -- the three rows of that read's state posteriors (the soft counterpart of pool's
+    records).  Returns {kmer: (n_reads, W, S, Q)} sorted by k-mer, W, S, Q the math.fsum over the per-(read, state) rows of the states
+    that carry the k-mer: exactly rounded, so independent of the order of the reads.  n_reads: the reads in which those states
+    together hold at least one expected observation.  A k-mer whose W is 0 does not appear."""
+    parts = {}
+    for what, w, wx, wxx in records:
+        if not (len(what) == len(w) == len(wx) == len(wxx)):
+            raise ValueError("one statistics entry per emitting state")
+        mine = {}
+        for (section, kind, kmer), wi, si, qi in zip(what, w, wx, wxx):
+            if kmer is None:
+                continue
+            p = parts.setdefault(kmer, [0, [], [], []])
+            p[1].append(float(wi)); p[2].append(float(si)); p[3].append(float(qi))
+            mine.setdefault(kmer, []).append(float(wi))
+        for kmer, ws in mine.items():
+            if math.fsum(ws) >= 1.0:
+                parts[kmer][0] += 1
+    out = {}
+    for k in sorted(parts):
+        W = math.fsum(parts[k][1])
+        if W > 0.0:
+            out[k] = (parts[k][0], W, math.fsum(parts[k][2]), math.fsum(parts[k][3]))
+    return out
 
 
 def estimate(pooled, pm, min_obs):
@@ -67,25 +105,30 @@ def write_model(path, pm, new_means):
             fp.write("%s\t%r\t%r\n" % (kmer, float(new_means.get(kmer, mean)), float(stdv)))
 
 
-def format_row(row):
+def format_row(row, posterior=False):
     kmer, n_reads, n_obs, mean, sd, t_mean, t_stdv, delta, updated = row
-    return "\t".join([kmer, str(int(n_reads)), str(int(n_obs))] + [repr(float(v)) for v in (mean, sd, t_mean, t_stdv, delta)] + [str(int(updated))])
+    obs = repr(float(n_obs)) if posterior else str(int(n_obs))
+    return "\t".join([kmer, str(int(n_reads)), obs] + [repr(float(v)) for v in (mean, sd, t_mean, t_stdv, delta)] + [str(int(updated))])
 
 
-def format(rows):
-    """The text of a --stats file: header and one line per row."""
-    return "".join(line + "\n" for line in ["\t".join(STATS_HEADER)] + [format_row(r) for r in rows])
+def format(rows, posterior=False):
+    """The text of a --stats file: header and one line per row.  posterior: the third column is the expected number of observations,
+    a repr float under the header `exp_obs`."""
+    header = STATS_HEADER_POSTERIOR if posterior else STATS_HEADER
+    return "".join(line + "\n" for line in ["\t".join(header)] + [format_row(r, posterior) for r in rows])
 
 
 def parse(text):
-    """Rows of a --stats file as format() wrote them (exact inverse)."""
+    """Rows of a --stats file as format() wrote them, either header (exact inverse: the third column is an int under `n_obs`, a
+    float under `exp_obs`)."""
     lines = text.splitlines()
-    if not lines or lines[0].split("\t") != STATS_HEADER:
+    if not lines or lines[0].split("\t") not in (STATS_HEADER, STATS_HEADER_POSTERIOR):
         raise ValueError("not a calibrate --stats file")
+    obs = float if lines[0].split("\t") == STATS_HEADER_POSTERIOR else int
     rows = []
     for line in lines[1:]:
         c = line.split("\t")
         if len(c) != len(STATS_HEADER):
             raise ValueError("bad --stats row: %r" % line)
-        rows.append((c[0], int(c[1]), int(c[2]), float(c[3]), float(c[4]), float(c[5]), float(c[6]), float(c[7]), int(c[8])))
+        rows.append((c[0], int(c[1]), obs(c[2]), float(c[3]), float(c[4]), float(c[5]), float(c[6]), float(c[7]), int(c[8])))
     return rows

@@ -1245,15 +1245,17 @@ def plot(argv):
     return made
 
 
-def calibrate_reads(items, counter, min_score):
+def calibrate_reads(items, counter, min_score, posterior=False):
     """One pass of `calibrate` over a batch: items [(target, raw signal, strand)] through counter.state_stats_batch; the records
-    calibrate.pool takes, of the reads that have statistics and whose two flank scores are at least min_score."""
+    calibrate.pool takes (posterior: calibrate.pool_posterior, from the state posteriors), of the reads that have statistics and whose
+    two flank scores are at least min_score."""
     records = []
-    for (target, _, strand), (row, stats) in zip(items, counter.state_stats_batch(items)):
+    got = counter.state_stats_batch(items, posterior=True) if posterior else counter.state_stats_batch(items)
+    for (target, _, strand), (row, stats) in zip(items, got):
         if stats is None or row[1] < min_score or row[2] < min_score:
             continue
         model = counter.targets[target][0 if strand == '+' else 1].repeatHMM
-        records.append((model.state_kmers(),) + tuple(stats))
+        records.append((model.state_kmers(),) + tuple(stats[:3]))
     return records
 
 
@@ -1273,6 +1275,10 @@ def calibrate(argv):
                         help="A k-mer's mean is replaced when at least N observations were assigned to it: the standard error of a level is stdv / sqrt(N).  "
                              "Required: there is no default (README, 'Calibrate')")
     parser.add_argument("--stats", default=None, metavar="FILE", help="Also write one row per k-mer seen to FILE, columns " + " ".join(cal.STATS_HEADER))
+    parser.add_argument("--posterior", action="store_true",
+                        help="Soft assignment: every observation is shared among the states in proportion to the posterior probability that the state "
+                             "emitted it (forward-backward over all paths) instead of going wholly to the state of the best path; --min-obs then counts "
+                             "expected observations, and the third column of --stats is exp_obs (README, 'Calibrate')")
     parser.add_argument("--config", help="Config file with HMM transition probabilities")
     parser.add_argument("--algn", default=None, help="Alignment in sam format, if not given read from stdin")
     parser.add_argument("--batch", type=int, default=2048, help="Reads per GPU batch")
@@ -1316,17 +1322,17 @@ def calibrate(argv):
             for target in targets:
                 batch.append((target, raw, strand)); n_reads += 1
             if len(batch) >= max(1, args.batch):
-                records += calibrate_reads(batch, counter, args.min_score); batch = []
+                records += calibrate_reads(batch, counter, args.min_score, args.posterior); batch = []
         if batch:
-            records += calibrate_reads(batch, counter, args.min_score)
+            records += calibrate_reads(batch, counter, args.min_score, args.posterior)
     finally:
         if args.algn:
             stream.close()
-    new_means, rows = cal.estimate(cal.pool(records), counter.pm, args.min_obs)
+    new_means, rows = cal.estimate(cal.pool_posterior(records) if args.posterior else cal.pool(records), counter.pm, args.min_obs)
     cal.write_model(args.out, counter.pm, new_means)
     if args.stats:
         with open(args.stats, 'w') as fp:
-            fp.write(cal.format(rows))
+            fp.write(cal.format(rows, posterior=True) if args.posterior else cal.format(rows))
     log("Main: %d of %d read(s) contributed, %d k-mer(s) updated." % (len(records), n_reads, len(new_means)), 'info')
 
 

@@ -429,14 +429,20 @@ class repeatCounter(object):
             out[i] = (d.row,) + extra if extra else d.row
         return out
 
-    def state_stats_batch(self, items):
+    def state_stats_batch(self, items, posterior=False):
         """items: iterable of (target_name, raw_signal, strand).  Returns [(row, stats)] in input order: row the tuple detect()
         returns, unchanged; stats None -- the gate failed, the read was not conditioned, the flanked decode found no path, or the
         window's back-pointers exceed STRQ_STATE_STATS_WS_BYTES -- or (n, sum, sumsq): per emitting state of the read's flanked model
         (targets[name][0 | 1].repeatHMM.state_kmers() says what each stands for) the count, the sum and the sum of squares of the
         observations the best path assigns to it (strique_amd.state_stats states the rule, strique_amd.calibrate uses it).  A method
         of its own, not a keyword of detect_batch: it turns the context's switch on around the run and off again before it returns;
-        the switches of the counter (set_renorm, ...) work underneath it.  Not with scan_batch."""
+        the switches of the counter (set_renorm, ...) work underneath it.  Not with scan_batch.
+        posterior=True: the soft counterpart -- the switch of the state posteriors instead (forward-backward over the same windows,
+        strique_amd.state_posteriors states the rule); stats is then None -- as above, or the forward pass found no path, or the
+        window's stored vectors exceed STRQ_STATE_POST_WS_BYTES -- or (w, wx, wxx, log_lik): per emitting state the posterior
+        occupancy and its first two moments of the observations, and the window's forward log-likelihood."""
+        switch, fetch = ((self.ctx.set_state_posteriors, self.ctx.batch_fetch_state_posteriors) if posterior else
+                         (self.ctx.set_state_stats, self.ctx.batch_fetch_state_stats))
         items = list(items)
         request = {p.name: getattr(self, p.name) for p in PASSES if not p.keyword and getattr(self, p.name)}
         reads = [(self._classifier_for(t, s).target_id, np.asarray(r)) for t, r, s in items]
@@ -447,13 +453,13 @@ class repeatCounter(object):
                 idx = [i for i, f in enumerate(is_int) if f == want_int]
                 if not idx:
                     continue
-                self.ctx.set_state_stats(True)
+                switch(True)
                 rows = {k: d.row for k, d, _, _ in self._run([reads[i] for i in idx], request)}
-                stats = self.ctx.batch_fetch_state_stats()
+                stats = fetch()
                 for k, i in enumerate(idx):
                     out[i] = (rows[k], stats[k])
         finally:
-            self.ctx.set_state_stats(False)
+            switch(False)
         return out
 
     @contextlib.contextmanager

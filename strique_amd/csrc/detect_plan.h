@@ -32,19 +32,19 @@ struct Carve {
 // come with.  DetectState holds what the next run call uses, a slot what its sub-batch was launched with, Batch what the last run call
 // ran with.
 struct Extras { bool units = false, conf = false, llr = false, anch = false, var = false; double anch_min = 0.0; bool renorm = false; double renorm_min = 0.0; bool amod = false;
-                bool tracts = false, fmod = false, tpos = false, sstats = false; };
+                bool tracts = false, fmod = false, tpos = false, sstats = false, spost = false; };
 
 // The passes, said once.  What the last run call's pass did is one PassStats: the GPU milliseconds and up to seven counters, which the
 // pass's own enum names.  A row of PASSES holds what the entry points need of a pass: its name in messages, its switch, what a batch
 // that ran without it lacks and the entry that turns it on (the "ran without" refusal of its fetch), whether a scan refuses it, and the
 // layout strq_last_* hands out -- `out[k]` is the counter at position k, MS the milliseconds.
-enum Pass { PASS_UNITS, PASS_CONF, PASS_LLR, PASS_VAR, PASS_ANCH, PASS_AMOD, PASS_TRACTS, PASS_RENORM, PASS_FMOD, PASS_TPOS, PASS_SSTATS, N_PASS };
+enum Pass { PASS_UNITS, PASS_CONF, PASS_LLR, PASS_VAR, PASS_ANCH, PASS_AMOD, PASS_TRACTS, PASS_RENORM, PASS_FMOD, PASS_TPOS, PASS_SSTATS, PASS_SPOST, N_PASS };
 struct PassStats { float ms; double v[7]; };
 enum { UNIT_BYTES, UNIT_READS, UNIT_POSITIONS, CONF_WINDOWS = 0, CONF_NOPATH, CONF_EXPO, LLR_UNITS = 0, LLR_READS, LLR_LAUNCHES,
        VAR_LAUNCHES = 0, VAR_PASSAGES, VAR_READS, ANCH_KINDS = 0 /* .. 3: reads of kind 0 .. 3 */, ANCH_LAUNCHES = 4, ANCH_G2, ANCH_LANE,
        AMOD_READS = 0, AMOD_UNITS, AMOD_LAUNCHES, TRACT_WINDOWS = 0, TRACT_LAUNCHES, TRACT_FAILED, RN_FITTED = 0, RN_APPLIED, RN_LAUNCHES,
        FMOD_FLANKS = 0, FMOD_GROUPS, FMOD_LAUNCHES, TPOS_WINDOWS = 0, TPOS_LAUNCHES, TPOS_BYTES,
-       SST_WINDOWS = 0, SST_LAUNCHES, SST_BYTES };
+       SST_WINDOWS = 0, SST_LAUNCHES, SST_BYTES, SPOST_WINDOWS = 0, SPOST_LAUNCHES, SPOST_BYTES };
 constexpr int8_t MS = -1;
 struct PassInfo { const char* name; bool Extras::* on; const char* lacks; const char* entry; bool scan_refuses; int n_out; int8_t out[8]; };
 constexpr PassInfo PASSES[N_PASS] = {
@@ -59,13 +59,14 @@ constexpr PassInfo PASSES[N_PASS] = {
     {"flank-mod", &Extras::fmod, "flank methylation calls", "strq_set_flank_mod", true, 4, {MS, 0, 1, 2}},
     {"tract-positions", &Extras::tpos, "tract positions", "strq_set_tract_positions", true, 4, {MS, 0, 1, 2}},
     {"state-stats", &Extras::sstats, "state statistics", "strq_set_state_stats", true, 4, {MS, 0, 1, 2}},
+    {"state-posteriors", &Extras::spost, "state posteriors", "strq_set_state_posteriors", true, 4, {MS, 0, 1, 2}},
 };
 inline void pass_stats_out(Pass p, const PassStats& s, double* out)
 {
     for (int k = 0; k < PASSES[p].n_out; ++k) out[k] = PASSES[p].out[k] == MS ? (double)s.ms : s.v[PASSES[p].out[k]];
 }
 // The pass a scan refuses first among those switched on, in the order the run call has always looked (N_PASS: none); the refusals as text
-constexpr Pass SCAN_CHECKS[] = {PASS_AMOD, PASS_ANCH, PASS_VAR, PASS_TRACTS, PASS_RENORM, PASS_FMOD, PASS_TPOS, PASS_SSTATS};
+constexpr Pass SCAN_CHECKS[] = {PASS_AMOD, PASS_ANCH, PASS_VAR, PASS_TRACTS, PASS_RENORM, PASS_FMOD, PASS_TPOS, PASS_SSTATS, PASS_SPOST};
 inline Pass scan_refusal(const Extras& ex)
 {
     for (Pass p : SCAN_CHECKS) if (PASSES[p].scan_refuses && ex.*PASSES[p].on) return p;
@@ -140,7 +141,7 @@ struct ReadRows {
         anch.assign(m, strq_anchored());
         amod_called.clear(); amod.clear(); amod_llr.clear();
         var.assign(m, VariantRow());
-        renorm.clear(); tracts.clear(); fmod_called.clear(); fmod.clear(); tpos_status.clear(); tpos.clear(); sst_status.clear(); sst.clear();
+        renorm.clear(); tracts.clear(); fmod_called.clear(); fmod.clear(); tpos_status.clear(); tpos.clear(); sst_status.clear(); sst.clear(); spost_status.clear(); spost.clear();
     }
     std::vector<strq_tracts> tracts;              // per-tract counts of the compound model (strq_batch_fetch_tracts); status 1: not decoded.  Empty
                                                   // until a run call with the switch on sizes it (size_tracts)
@@ -157,6 +158,11 @@ struct ReadRows {
     std::vector<int32_t> sst_status;              // 0 statistics, 1 none (not decoded), 2 back-pointers over the budget
     std::vector<StateStatsRow> sst;               // n_emit entries each where the status is 0, else empty
     void size_sst() { if (sst_status.size() != results.size()) { sst_status.assign(results.size(), 1); sst.assign(results.size(), StateStatsRow()); } }
+    // state posteriors of the flanked decode (strq_batch_fetch_state_posteriors): empty until a run call with the switch on sizes them (size_spost)
+    struct StatePostRow { double log_lik = NAN; std::vector<double> w, wx, wxx; };
+    std::vector<int32_t> spost_status;            // 0 statistics, 1 none (not decoded, or no path in the forward pass), 2 stored vectors over the budget
+    std::vector<StatePostRow> spost;              // n_emit entries each where the status is 0, else empty
+    void size_spost() { if (spost_status.size() != results.size()) { spost_status.assign(results.size(), 1); spost.assign(results.size(), StatePostRow()); } }
     static strq_tracts no_tracts() { strq_tracts t = strq_tracts(); t.status = 1; return t; }
     void size_tracts() { if (tracts.size() != results.size()) tracts.assign(results.size(), no_tracts()); }
     void size_renorm() { if (renorm.size() != results.size()) renorm.assign(results.size(), strq_renorm()); }
@@ -181,6 +187,7 @@ struct ReadRows {
         if (r < fmod_called.size()) { fmod_called[r] = 0; fmod[r].clear(); }
         if (r < tpos_status.size()) { tpos_status[r] = 1; for (int j = 0; j < 3; ++j) tpos[3 * r + j].clear(); }
         if (r < sst_status.size()) { sst_status[r] = 1; sst[r] = StateStatsRow(); }
+        if (r < spost_status.size()) { spost_status[r] = 1; spost[r] = StatePostRow(); }
     }
 };
 

@@ -42,30 +42,6 @@ namespace strq {
 
 #define FWD_WAVES 4
 
-// lane l receives lane l - N of its row of 16; the first N lanes of a row keep `old`
-template <int N>
-static __device__ __forceinline__ double fwd_row_shr(double old, double v)
-{
-    const uint64_t u = __builtin_bit_cast(uint64_t, v), o = __builtin_bit_cast(uint64_t, old);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)o, (int)(uint32_t)u, 0x110 + N, 0xF, 0xF, false);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)(o >> 32), (int)(uint32_t)(u >> 32), 0x110 + N, 0xF, 0xF, false);
-    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
-}
-// largest value of the wave, in every lane: butterflies inside the rows of 16 (quad_perm, row_half_mirror, row_mirror), the four
-// row maxima through v_readlane
-static __device__ __forceinline__ int fwd_wave_max(int v)
-{
-    int o;
-    o = __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true); v = v > o ? v : o;       // quad_perm [1,0,3,2]
-    o = __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, true); v = v > o ? v : o;       // quad_perm [2,3,0,1]
-    o = __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, true); v = v > o ? v : o;      // row_half_mirror
-    o = __builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, true); v = v > o ? v : o;      // row_mirror
-    const int a = __builtin_amdgcn_readlane(v, 0), b = __builtin_amdgcn_readlane(v, 16);
-    const int c = __builtin_amdgcn_readlane(v, 32), d = __builtin_amdgcn_readlane(v, 48);
-    const int ab = a > b ? a : b, cd = c > d ? c : d;
-    return ab > cd ? ab : cd;
-}
-
 // x * 2^-e, exactly
 static __device__ __forceinline__ double fwd_scale(double x, int e) { return __builtin_ldexp(x, -e); }
 
@@ -164,8 +140,8 @@ forward_kernel(const VitTask* __restrict__ tasks, const FwdModel* const* __restr
                 // inclusive scan of the maps inside each row of 16 lanes
 #define FWD_SCAN_STEP(N)                                                                           \
                 {                                                                                  \
-                    const double a_src = fwd_row_shr<N>(1.0, A);                                   \
-                    const double b0 = fwd_row_shr<N>(0.0, B[0]), b1 = fwd_row_shr<N>(0.0, B[1]), b2 = fwd_row_shr<N>(0.0, B[2]); \
+                    const double a_src = row_shr_f64<N>(1.0, A);                                   \
+                    const double b0 = row_shr_f64<N>(0.0, B[0]), b1 = row_shr_f64<N>(0.0, B[1]), b2 = row_shr_f64<N>(0.0, B[2]); \
                     B[0] = B[0] + A * b0; B[1] = B[1] + A * b1; B[2] = B[2] + A * b2;              \
                     A = A * a_src;                                                                 \
                 }
@@ -223,11 +199,7 @@ forward_kernel(const VitTask* __restrict__ tasks, const FwdModel* const* __restr
                         const int cidx = esrc[s][j]; const double w = ew[s][j];
                         p = p + w * RD[cidx]; r = r + w * RD[PL + cidx]; q = q + w * RD[2 * PL + cidx];
                     }
-                    double em;
-                    if (x != x) em = has_e[s] ? 1.0 : 0.0;          // a missing observation has probability 1 under every distribution
-                    else if (ekind[s] == 1) { const double d = x - ea[s]; em = exp(ec[s] - (d * d) * eb[s]); }
-                    else if (ekind[s] == 2) em = (x >= ea[s] && x <= eb[s]) ? eu[s] : 0.0;
-                    else em = 0.0;
+                    const double em = hmm_emission(x, has_e[s], ekind[s], ea[s], eb[s], ec[s], eu[s]);
                     p = p * em; r = r * em; q = q * em;
                     if (ecnt[s]) { q = q + 2.0 * r + p; r = r + p; }
                     np_[s] = p; nr_[s] = r; nq_[s] = q;
@@ -237,7 +209,7 @@ forward_kernel(const VitTask* __restrict__ tasks, const FwdModel* const* __restr
                     int hi = 0;          // p >= 0: the high word orders like the value
 #pragma unroll
                     for (int s = 0; s < EPL; ++s) { const int h = (int)(uint32_t)(__builtin_bit_cast(uint64_t, np_[s]) >> 32); hi = h > hi ? h : hi; }
-                    hi = fwd_wave_max(hi);
+                    hi = wave_max_i32(hi);
                     if (hi != 0) {          // (zero: no path is alive, or nothing above 2^-1043 -- nothing to scale by)
                         const int e = ((hi >> 20) & 0x7FF) - 1023;
                         if (e != 0) {

@@ -13,6 +13,7 @@
 #include "align_kernels.h"
 #include "viterbi_kernels.h"
 #include "forward_kernels.h"
+#include "posterior_kernels.h"
 #include "mod_llr_kernels.h"
 #include "variant_kernels.h"
 #include "screen_kernels.h"
@@ -104,6 +105,11 @@ struct HostModel {
     std::vector<double> fwd_logp;
     DevBuf fwd_blob;
     const FwdModel* fwd_dev = nullptr;
+    // state posteriors (posterior_kernels.h): the state held by every cell of the lane layout (VitModel::cell_state), and the transposed
+    // image of the forward image -- built on first use, dropped with it
+    std::vector<int32_t> cell_state;
+    DevBuf post_blob;
+    const PostModel* post_dev = nullptr;
     // per-unit scores of the modification pass (mod_llr_kernels.h): the edge image of a dual model, built on first use
     DevBuf llr_blob;
     const LlrModel* llr_dev = nullptr;
@@ -188,6 +194,8 @@ int detect_drain(strq_ctx* c);              // rows of every detect sub-batch in
 int viterbi_launch_status(int vrc);
 // the forward image of a model (HostModel::fwd_dev), built if it is not there; STRQ_ERR_UNSUPPORTED (c->err says why) for a model without one
 int forward_model(strq_ctx* c, HostModel* hm);
+// ... and its transposed image (HostModel::post_dev) behind it, for the backward half of the state posteriors
+int posterior_model(strq_ctx* c, HostModel* hm);
 // Unit positions of the tracts of decoded windows (strq_set_tract_positions, strq_viterbi_tract_positions; strq_detect_api.hip): every
 // window once more with back-pointers, traced back and scanned (tract_scan_kernel), in pieces of at most STRQ_TRACT_POS_WS_BYTES of
 // back-pointers.  task: the window as its count decode had it (bp is set here); n[j]: the visits of tract j that decode found; base:
@@ -205,6 +213,14 @@ int tract_positions(strq_ctx* c, const std::vector<TractPosWindow>& w, TractPosO
 struct StateStatsWindow { VitTask task; const HostModel* hm; double logp; int64_t counted; };
 struct StateStatsOut { std::vector<int32_t> status; std::vector<std::vector<int64_t>> n; std::vector<std::vector<double>> sum, sumsq; };
 int state_stats(strq_ctx* c, const std::vector<StateStatsWindow>& w, StateStatsOut& out, double* stats);
+// State posteriors of windows (strq_set_state_posteriors, strq_forward_state_stats; strq_detect_api.hip, the rule: strique_amd/
+// state_posteriors.py): forward-backward over every window (posterior_kernels.h), in pieces of at most STRQ_STATE_POST_WS_BYTES of stored
+// forward vectors.  task: the window (bp unused).  fwd[i]: the forward half's result of every window (fwd_finish gives the likelihood);
+// status[i]: 0 the rows w / wx / wxx[i] hold silent_start entries, 1 no path (no rows), 2 the window's stored vectors alone exceed the
+// budget (no rows; fwd[i] is valid).  stats (or null): windows, kernels launched, peak workspace bytes of a piece.
+struct StatePostWindow { VitTask task; HostModel* hm; };
+struct StatePostOut { std::vector<int32_t> status; std::vector<FwdResult> fwd; std::vector<std::vector<double>> w, wx, wxx; };
+int state_posteriors(strq_ctx* c, const std::vector<StatePostWindow>& w, StatePostOut& out, double* stats);
 void host_stats_batch(const double* signals, const int64_t* offsets, int64_t n_reads, bool want_raw, double* out,
                       const double* const* reads = nullptr);   // host_stats.hip; reads: one buffer per read instead of `signals`
 }

@@ -31,6 +31,7 @@
 #include "variant_kernels.h"
 #include "flank_mod_kernels.h"
 #include "state_stats_kernels.h"
+#include "posterior_kernels.h"
 
 using namespace strq;
 
@@ -134,6 +135,7 @@ struct DetectState {
     DevBuf tract_ws, tract_task;         // tract pass (run_tract_pass): geometry and conditioning rows of a sub-batch; tasks, results, their reads and models
     DevBuf tpos_task, tpos_bp, tpos_path, tpos_pool;      // tract positions (tract_positions): tasks and results of a piece, its back-pointers, state paths, positions
     DevBuf sst_task, sst_bp, sst_path, sst_out;           // state statistics (state_stats): tasks and results of a piece, its back-pointers, state paths, rows
+    DevBuf post_task, post_ws, post_out;                  // state posteriors (state_posteriors): tasks and results of a piece, its stored forward vectors, rows
     DevBuf anch_ws, anch_task;           // anchored pass (run_anchored_pass): geometry, conditioning rows and kinds of a sub-batch; tasks, results, their reads and models
     hipEvent_t amod_ev[2] = {};          // methylation calls of anchored reads (run_anchored_mod): their own bracket, inside the anchored pass
     // renorm (run_renorm_part): the tables of the targets, the grid and the shares, the histograms and the per-read table rows of a sub-batch
@@ -1216,6 +1218,127 @@ int state_stats(strq_ctx* c, const std::vector<StateStatsWindow>& w, StateStatsO
     return STRQ_OK;
 }
 
+// State posteriors of windows (strq_ctx.h states the interface; strique_amd/state_posteriors.py the rule), built like state_stats: the
+// windows of a piece grouped by kernel shape, one forward and one backward launch per shape on two queue heads (posterior_kernels.h),
+// the stored forward vectors of the piece in one buffer.  A window whose vectors alone exceed the budget rides along in the first piece
+// with nothing stored: its forward half still gives the likelihood.  One read-back and one wait per piece; the buffers exist only once
+// this ran.
+int state_posteriors(strq_ctx* c, const std::vector<StatePostWindow>& w, StatePostOut& out, double* stats)
+{
+    DetectState* d = dstate(c);
+    hipStream_t st = c->stream;
+    const size_t nw = w.size();
+    out.status.assign(nw, 0); out.fwd.assign(nw, FwdResult()); out.w.assign(nw, std::vector<double>()); out.wx.assign(nw, std::vector<double>()); out.wxx.assign(nw, std::vector<double>());
+    size_t budget = (size_t)8 << 30;
+    if (const char* e = strq::opt("STRQ_STATE_POST_WS_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
+    struct W { int i; int shape; size_t bytes; };
+    std::vector<W> ws, over;
+    for (size_t i = 0; i < nw; ++i) {
+        if (const int rc = posterior_model(c, w[i].hm)) return rc;
+        const VitModel& h = w[i].hm->h;
+        const int shape = vit_shape_of(h);
+        if (vit_shape_family(shape) != VIT_FAMILY_LANE) { c->err = "state posteriors: the model has no forward kernel"; return STRQ_ERR_UNSUPPORTED; }
+        const size_t bytes = post_window_bytes(w[i].task.T, h.epl);
+        if (bytes > budget) { out.status[i] = 2; over.push_back({(int)i, shape, 0}); continue; }
+        ws.push_back({(int)i, shape, bytes});
+    }
+    ws.insert(ws.begin(), over.begin(), over.end());
+    for (size_t c0 = 0; c0 < ws.size();) {
+        size_t c1 = c0, bytes = 0;
+        while (c1 < ws.size() && c1 - c0 < 8192 && bytes + ws[c1].bytes <= budget) bytes += ws[c1++].bytes;          // (every window fits alone)
+        const int m = (int)(c1 - c0);
+        std::vector<GroupItem> items((size_t)m);
+        size_t row_n = 0;
+        for (int k = 0; k < m; ++k) {
+            const StatePostWindow& x = w[(size_t)ws[c0 + (size_t)k].i];
+            items[(size_t)k] = {0, ws[c0 + (size_t)k].shape, x.hm->h.n_cells};
+            row_n += (size_t)x.hm->silent_start;
+        }
+        const Grouping G = group_items(items);
+        if (2 * G.groups.size() > 256) { c->err = "state posteriors: too many kernel shapes in one piece"; return STRQ_ERR_UNSUPPORTED; }
+        Carve lay;
+        const size_t o_vt = lay.add<VitTask>((size_t)m), o_fr = lay.add<FwdResult>((size_t)m), o_pm = lay.add<const PostModel*>((size_t)m),
+                     o_pt = lay.add<PostTask>((size_t)m), o_order = lay.add<int>((size_t)m);
+        STRQ_HIP(c, d->post_task.reserve(lay.total() + 64));
+        void* tb = d->post_task.p;
+        VitTask* d_vt = Carve::at<VitTask>(tb, o_vt); FwdResult* d_fr = Carve::at<FwdResult>(tb, o_fr); const PostModel** d_pm = Carve::at<const PostModel*>(tb, o_pm);
+        PostTask* d_pt = Carve::at<PostTask>(tb, o_pt); int* d_order = Carve::at<int>(tb, o_order);
+        STRQ_HIP(c, d->post_ws.reserve(bytes + 64));
+        STRQ_HIP(c, d->post_out.reserve(row_n * 24 + 64));          // w | wx | wxx, row_n entries each
+        double* o_w = d->post_out.as<double>(); double* o_wx = o_w + row_n; double* o_wxx = o_wx + row_n;
+        std::vector<VitTask> tv((size_t)m); std::vector<const PostModel*> mv((size_t)m); std::vector<PostTask> pv((size_t)m);
+        std::vector<int> win_of((size_t)m); std::vector<size_t> row_off((size_t)m);
+        size_t wo = 0, xo = 0;
+        for (int at = 0; at < m; ++at) {          // in task order: the stored vectors and the rows lie in that order too
+            const W& ww = ws[c0 + (size_t)G.order[(size_t)at]];
+            const StatePostWindow& x = w[(size_t)ww.i];
+            PostTask p; std::memset(&p, 0, sizeof(p));
+            if (ww.bytes) {
+                p.alpha = reinterpret_cast<double*>(d->post_ws.as<char>() + wo);
+                p.expo = reinterpret_cast<int32_t*>(d->post_ws.as<char>() + wo + post_alpha_bytes(x.task.T, x.hm->h.epl));
+                wo += ww.bytes;
+                if (wo > d->post_ws.cap) { c->err = "state posteriors: workspace"; return STRQ_ERR_NOMEM; }
+            }
+            p.w = o_w + xo; p.wx = o_wx + xo; p.wxx = o_wxx + xo;
+            row_off[(size_t)at] = xo; xo += (size_t)x.hm->silent_start;
+            tv[(size_t)at] = x.task; tv[(size_t)at].bp = nullptr; mv[(size_t)at] = x.hm->post_dev; pv[(size_t)at] = p; win_of[(size_t)at] = ww.i;
+        }
+        STRQ_HIP(c, hipMemcpyAsync(d_vt, tv.data(), (size_t)m * sizeof(VitTask), hipMemcpyHostToDevice, st));
+        STRQ_HIP(c, hipMemcpyAsync(d_pm, mv.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
+        STRQ_HIP(c, hipMemcpyAsync(d_pt, pv.data(), (size_t)m * sizeof(PostTask), hipMemcpyHostToDevice, st));
+        STRQ_HIP(c, hipMemsetAsync(d->post_out.p, 0, row_n * 24, st));          // a window without a path keeps +0.0 rows
+        if (const int qrc = reset_queue_heads(c, st)) return qrc;
+        double launches = 0; int qi = 0;
+        for (const VitGroup& g : G.groups) {
+            if (launch_vit_sort(st, d_vt + g.first, g.count, d_order + g.first)) { c->err = "state posteriors: sort launch failed"; return STRQ_ERR_DEVICE; }
+            const int lrc = launch_posterior(st, g.shape, g.max_cells, d_vt + g.first, d_pm + g.first, d_pt + g.first, d_fr + g.first, g.count,
+                                             c->queue.as<int>() + qi, c->n_cu, d_order + g.first);
+            if (lrc) { c->err = lrc == 2 ? "state posteriors: no kernel for this model's layout" : "state posteriors: kernel launch failed"; return lrc == 2 ? STRQ_ERR_UNSUPPORTED : STRQ_ERR_DEVICE; }
+            qi += 2; launches += 3;
+        }
+        std::vector<double> rows(3 * row_n + 1); std::vector<FwdResult> fr((size_t)m);
+        STRQ_HIP(c, hipMemcpyAsync(rows.data(), d->post_out.p, row_n * 24, hipMemcpyDeviceToHost, st));
+        STRQ_HIP(c, hipMemcpyAsync(fr.data(), d_fr, (size_t)m * sizeof(FwdResult), hipMemcpyDeviceToHost, st));
+        STRQ_HIP(c, hipStreamSynchronize(st));
+        const double* h_w = rows.data(); const double* h_wx = h_w + row_n; const double* h_wxx = h_wx + row_n;
+        for (int at = 0; at < m; ++at) {
+            const size_t i = (size_t)win_of[(size_t)at], o = row_off[(size_t)at], ne = (size_t)w[i].hm->silent_start;
+            out.fwd[i] = fr[(size_t)at];
+            if (out.status[i] == 2) continue;
+            if (!(fr[(size_t)at].p > 0.0)) { out.status[i] = 1; continue; }
+            out.w[i].assign(h_w + o, h_w + o + ne); out.wx[i].assign(h_wx + o, h_wx + o + ne); out.wxx[i].assign(h_wxx + o, h_wxx + o + ne);
+        }
+        if (stats) { stats[0] += m; stats[1] += launches; stats[2] = std::max(stats[2], (double)bytes); }
+        c0 = c1;
+    }
+    return STRQ_OK;
+}
+
+// State posteriors of the reads of one sub-batch (strq_set_state_posteriors): the windows the count / MARK launch decoded, once more
+// with the same tasks -- same windows, same affine source on the slot's filtered signal -- like the forward pass of strq_set_confidence.
+// Runs on the context's stream when the rows of the sub-batch are taken.
+static int run_state_posteriors_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, const Decoded& dec)
+{
+    Batch& B = d->batch;
+    const int64_t r0 = sl.r0;
+    if (const int rc = pass_start(c, pass_ev(d))) return rc;
+    std::vector<StatePostWindow> pw;
+    for (int i : dec.who) {
+        StatePostWindow x; x.task = dec.vt[(size_t)sl.vit_slot[i]]; x.task.bp = nullptr; x.hm = flank_model(c, d, r0 + i);
+        pw.push_back(x);
+    }
+    StatePostOut po;
+    if (const int rc = state_posteriors(c, pw, po, d->stats[PASS_SPOST].v)) return rc;
+    for (size_t k = 0; k < pw.size(); ++k) {
+        const size_t r = (size_t)(r0 + dec.who[k]);
+        double mean, var;
+        (void)fwd_finish(po.fwd[k], 0, &B.spost[r].log_lik, &mean, &var);
+        B.spost_status[r] = po.status[k];
+        B.spost[r].w.swap(po.w[k]); B.spost[r].wx.swap(po.wx[k]); B.spost[r].wxx.swap(po.wxx[k]);
+    }
+    return pass_stop(c, pass_ev(d), d->stats[PASS_SPOST]);
+}
+
 // State statistics of the reads of one sub-batch (strq_set_state_stats): the windows the count / MARK launch decoded, once more with the
 // same tasks -- same windows, same affine source on the slot's filtered signal -- like the back-pointer route of the unit pass.  Runs on
 // the context's stream when the rows of the sub-batch are taken.
@@ -1832,13 +1955,14 @@ static int take_rows(strq_ctx* c, DetectState* d, DetectState::Slot& sl, bool un
     // the mode the launches ran with decides, not what the targets say by now
     if (sl.vit_mode == VIT_MARK) { const int mrc = run_mod_pass(c, d, sl); if (mrc) return mrc; }
     if (sl.vit_mode == VIT_MARK && sl.ex.var) { const int vrc = run_mod_pass(c, d, sl, DUAL_VAR); if (vrc) return vrc; }
-    if (sl.ex.units || sl.ex.conf || sl.ex.sstats) {
+    if (sl.ex.units || sl.ex.conf || sl.ex.sstats || sl.ex.spost) {
         Decoded dec;
         if (const int drc = read_decoded(c, sl, dec)) return drc;
         if (!dec.who.empty()) {
             if (sl.ex.units) { const int urc = run_unit_pass(c, d, sl, dec); if (urc) return urc; }
             if (sl.ex.conf) { const int crc = run_conf_pass(c, d, sl, dec); if (crc) return crc; }
             if (sl.ex.sstats) { const int src = run_state_stats_pass(c, d, sl, dec); if (src) return src; }
+            if (sl.ex.spost) { const int prc = run_state_posteriors_pass(c, d, sl, dec); if (prc) return prc; }
         }
     }
     if (sl.ex.tracts) { const int trc = run_tract_pass(c, d, sl); if (trc) return trc; }
@@ -2504,6 +2628,14 @@ int run_range(strq_ctx* c, DetectState* d, int64_t first, int64_t last)
         }
         B.size_sst();
     }
+    if (d->extras.spost) {
+        // nothing is launched for a call whose flanked models have no forward kernel
+        for (int64_t r = first; r < last; ++r) {
+            HostModel* hm = c->models[d->targets[B.target_given.empty() ? B.target[(size_t)r] : B.target_given[(size_t)r]].model_id];
+            if (const int rc = posterior_model(c, hm)) return rc;
+        }
+        B.size_spost();
+    }
     if (d->extras.renorm) {
         // nothing is launched for a call whose reads the pass could not fit
         if (!d->rn_have_grid) { c->err = "renorm: no tables (strq_target_set_renorm)"; return STRQ_ERR_ARG; }
@@ -3015,6 +3147,41 @@ int strq_last_state_stats(strq_ctx* c, double* out4)
 {
     STRQ_ENTER(c);
     return last_pass(c, PASS_SSTATS, out4);
+}
+
+int strq_set_state_posteriors(strq_ctx* c, int32_t on)
+{
+    STRQ_ENTER(c);
+    return set_extra(c, on, PASS_SPOST);
+}
+
+int strq_batch_fetch_state_posteriors(strq_ctx* c, int64_t* off, double* w, double* wx, double* wxx, int64_t cap, double* log_lik, int32_t* status)
+{
+    STRQ_ENTER(c);
+    if (!off || cap < 0) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    const bool pools = w || wx || wxx;
+    if (pools && !(w && wx && wxx)) { c->err = "bad argument (strq_batch_fetch_state_posteriors: all pools or none)"; return STRQ_ERR_ARG; }
+    DetectState* d = dstate(c);
+    if (const int rc = fetch_begin(c, d, PASS_SPOST)) return rc;
+    const Batch& B = d->batch;
+    const int64_t n = (int64_t)B.spost.size();
+    const int64_t done = pack_ragged(n, off, pools, cap, [&](int64_t i) { return (int64_t)B.spost[(size_t)i].w.size(); }, [&](int64_t i, int64_t pos) {
+        const ReadRows::StatePostRow& r = B.spost[(size_t)i];
+        if (r.w.empty()) return;
+        std::memcpy(w + pos, r.w.data(), r.w.size() * 8); std::memcpy(wx + pos, r.wx.data(), r.w.size() * 8); std::memcpy(wxx + pos, r.wxx.data(), r.w.size() * 8);
+    });
+    for (int64_t i = 0; i < done; ++i) {          // (of the reads that fitted)
+        if (log_lik) log_lik[i] = B.spost[(size_t)i].log_lik;
+        if (status) status[i] = B.spost_status[(size_t)i];
+    }
+    if (done < n) { c->err = "state posteriors pool too small"; return STRQ_ERR_ARG; }
+    return STRQ_OK;
+}
+
+int strq_last_state_posteriors(strq_ctx* c, double* out4)
+{
+    STRQ_ENTER(c);
+    return last_pass(c, PASS_SPOST, out4);
 }
 
 int strq_target_set_flank_mod(strq_ctx* c, int32_t target_id, int32_t which, int32_t profile_model_id, int32_t flank_len,

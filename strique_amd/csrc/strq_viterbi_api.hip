@@ -279,7 +279,7 @@ int build_vit_model(strq_ctx* c, int32_t n_states, int32_t silent_start, int32_t
     HostModel* hm = new HostModel();
     VitModel& m = hm->h;
     m = P.m;
-    hm->edge_csr.swap(P.edge_csr); hm->chain_csr.swap(P.chain_csr); hm->fwd_stages = P.fwd_stages;
+    hm->edge_csr.swap(P.edge_csr); hm->chain_csr.swap(P.chain_csr); hm->fwd_stages = P.fwd_stages; hm->cell_state = P.cell_state;
     // one device blob: the arrays, the VitModel that points to them behind
     Image im;
     const size_t o_lp = im.put(P.lp), o_a = im.put(P.a), o_b = im.put(P.b), o_c = im.put(P.cc), o_src = im.put(P.src), o_kind = im.put(P.kind), o_inc = im.put(P.inc),
@@ -588,6 +588,67 @@ int forward_model(strq_ctx* c, HostModel* hm)
     F.vit = hm->dev; F.edge_w = Carve::at<const double>(d, o_e); F.chain_w = Carve::at<const double>(d, o_c); F.n_stages = hm->fwd_stages;
     if (hipMemcpy(d, im.host().data(), im.lay.total(), hipMemcpyHostToDevice) != hipSuccess) { c->err = "model upload failed"; return STRQ_ERR_DEVICE; }
     hm->fwd_dev = Carve::at<const FwdModel>(d, o_m);
+    hm->post_dev = nullptr;          // (it points to the image this one replaced)
+    return STRQ_OK;
+}
+
+// Transposed image of a model (PostModel): every entry of the forward image's edge rows is an in-edge of the cell that owns the row --
+// turned round it is an out-edge of its source cell, with the same probability.  The out-edges of a cell keep the order of the rows
+// (and of the lanes inside a row) they come from; the chain edges turn into chain_next_w.
+int posterior_model(strq_ctx* c, HostModel* hm)
+{
+    if (const int rc = forward_model(c, hm)) return rc;
+    if (hm->post_dev) return STRQ_OK;
+    const VitModel& m = hm->h;
+    const int epl = m.epl, spl = m.spl, dummy = m.n_cells - 1;
+    if (hm->cell_state.size() != (size_t)m.n_cells) { c->err = "state posteriors: the model has no lane layout"; return STRQ_ERR_UNSUPPORTED; }
+    std::vector<int32_t> cell_of((size_t)hm->n_states, -1);
+    for (int cell = 0; cell < m.n_cells; ++cell) if (hm->cell_state[(size_t)cell] >= 0) cell_of[(size_t)hm->cell_state[(size_t)cell]] = cell;
+    const std::vector<double>& lp = hm->fwd_logp.empty() ? hm->in_logp : hm->fwd_logp;
+    std::vector<std::vector<std::pair<int32_t, double>>> outs((size_t)m.n_cells);
+    auto turn = [&](int slot_base, int deg, int lane, int dst_cell) {
+        for (int j = 0; j < deg; ++j) {
+            const int e = hm->edge_csr[(size_t)(slot_base + j) * 64 + (size_t)lane];
+            if (e < 0) continue;
+            outs[(size_t)cell_of[(size_t)hm->in_src[(size_t)e]]].push_back({dst_cell, std::exp(lp[(size_t)e])});
+        }
+    };
+    for (int s = 0; s < epl; ++s) for (int lane = 0; lane < 64; ++lane) turn(m.e_base[s], m.e_deg[s], lane, s * 64 + lane);
+    for (int s = 0; s < spl; ++s) for (int lane = 0; lane < 64; ++lane) turn(m.s_base[s], m.s_deg[s], lane, epl * 64 + lane * spl + s);
+    PostModel P; std::memset(&P, 0, sizeof(P));
+    int rows = 0;
+    for (int s = 0; s < epl; ++s) {
+        size_t deg = 0;
+        for (int lane = 0; lane < 64; ++lane) deg = std::max(deg, outs[(size_t)(s * 64 + lane)].size());
+        P.oe_deg[s] = (int32_t)deg; P.oe_base[s] = rows; rows += (int)deg;
+    }
+    for (int s = 0; s < spl; ++s) {
+        size_t deg = 0;
+        for (int lane = 0; lane < 64; ++lane) deg = std::max(deg, outs[(size_t)(epl * 64 + lane * spl + s)].size());
+        P.os_deg[s] = (int32_t)deg; P.os_base[s] = rows; rows += (int)deg;
+    }
+    std::vector<int32_t> dst((size_t)std::max(rows, 1) * 64, dummy); std::vector<double> w((size_t)std::max(rows, 1) * 64, 0.0);
+    auto fill = [&](int base, int lane, int cell) {
+        const auto& o = outs[(size_t)cell];
+        for (size_t j = 0; j < o.size(); ++j) { dst[((size_t)base + j) * 64 + (size_t)lane] = o[j].first; w[((size_t)base + j) * 64 + (size_t)lane] = o[j].second; }
+    };
+    for (int s = 0; s < epl; ++s) for (int lane = 0; lane < 64; ++lane) fill(P.oe_base[s], lane, s * 64 + lane);
+    for (int s = 0; s < spl; ++s) for (int lane = 0; lane < 64; ++lane) fill(P.os_base[s], lane, epl * 64 + lane * spl + s);
+    // the chain edge INTO position p (slot p % spl of lane p / spl) leaves position p - 1
+    std::vector<double> nw((size_t)spl * 64, 0.0);
+    for (int i = 0; i < spl * 64; ++i) {
+        if (hm->chain_csr[(size_t)i] < 0) continue;
+        const int p = (i % 64) * spl + i / 64 - 1;
+        if (p < 0) { c->err = "state posteriors: chain edge into the first chain position"; return STRQ_ERR_UNSUPPORTED; }
+        nw[(size_t)(p % spl) * 64 + (size_t)(p / spl)] = std::exp(lp[(size_t)hm->chain_csr[(size_t)i]]);
+    }
+    Image im;
+    const size_t o_d = im.put(dst), o_w = im.put(w), o_n = im.put(nw), o_m = im.put(&P, 1);
+    if (hm->post_blob.reserve(im.lay.total()) != hipSuccess) { c->err = "out of device memory"; return STRQ_ERR_NOMEM; }
+    void* d = hm->post_blob.p;
+    P.fwd = hm->fwd_dev; P.out_dst = Carve::at<const int32_t>(d, o_d); P.out_w = Carve::at<const double>(d, o_w); P.chain_next_w = Carve::at<const double>(d, o_n);
+    if (hipMemcpy(d, im.host().data(), im.lay.total(), hipMemcpyHostToDevice) != hipSuccess) { c->err = "model upload failed"; return STRQ_ERR_DEVICE; }
+    hm->post_dev = Carve::at<const PostModel>(d, o_m);
     return STRQ_OK;
 }
 
@@ -866,7 +927,7 @@ int strq_model_set_forward_logp(strq_ctx* c, int32_t model_id, const double* in_
     // a detect sub-batch in flight may be about to run its forward pass on the present image
     { const int rc = detect_drain(c); if (rc) return rc; }
     hm->fwd_logp.assign(in_logp_sum, in_logp_sum + hm->in_logp.size());
-    hm->fwd_dev = nullptr;          // built again on the next forward pass
+    hm->fwd_dev = nullptr; hm->post_dev = nullptr;          // built again on the next forward pass
     return STRQ_OK;
 }
 
@@ -1070,6 +1131,42 @@ int strq_viterbi_state_stats(strq_ctx* c, int32_t model_id, int64_t n_seq, const
         if (logp) logp[i] = lp[(size_t)i];
         if (counted) counted[i] = cn[(size_t)i];
         if (status) status[i] = stv[(size_t)i];
+    }
+    return STRQ_OK;
+}
+
+int strq_forward_state_stats(strq_ctx* c, int32_t model_id, int64_t n_seq, const double* x, const int64_t* x_off,
+                             double* log_lik, int32_t* status, double* w, double* wx, double* wxx)
+{
+    STRQ_ENTER(c);
+    if (model_id < 0 || model_id >= (int32_t)c->models.size() || !c->models[model_id] || n_seq < 0 || n_seq > 8192 || (n_seq > 0 && (!x_off || !w || !wx || !wxx))) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    if (n_seq == 0) return STRQ_OK;
+    const int64_t tot = x_off[n_seq];
+    if (x_off[0] != 0 || tot < 0 || (tot > 0 && !x)) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    for (int64_t i = 0; i < n_seq; ++i) if (x_off[i + 1] < x_off[i]) { c->err = "bad argument (x_off must not decrease)"; return STRQ_ERR_ARG; }
+    HostModel* hm = c->models[model_id];
+    if (const int rc = posterior_model(c, hm)) return rc;
+    STRQ_HIP(c, c->vit_x.reserve((size_t)tot * 8 + 64));
+    if (tot) STRQ_HIP(c, hipMemcpyAsync(c->vit_x.p, x, (size_t)tot * 8, hipMemcpyHostToDevice, c->stream));
+    std::vector<StatePostWindow> pw((size_t)n_seq);
+    for (int64_t i = 0; i < n_seq; ++i) {
+        StatePostWindow& p = pw[(size_t)i];
+        std::memset(&p.task, 0, sizeof(p.task));
+        p.task.model = hm->dev; p.task.sig = c->vit_x.as<double>() + x_off[i]; p.task.T = x_off[i + 1] - x_off[i]; p.task.src_kind = VIT_SRC_F64;
+        p.hm = hm;
+    }
+    StatePostOut po;
+    if (const int rc = state_posteriors(c, pw, po, nullptr)) return rc;
+    const size_t ne = (size_t)hm->silent_start;
+    std::fill(w, w + (size_t)n_seq * ne, 0.0); std::fill(wx, wx + (size_t)n_seq * ne, 0.0); std::fill(wxx, wxx + (size_t)n_seq * ne, 0.0);
+    for (int64_t i = 0; i < n_seq; ++i) {
+        double ll, mean, var;
+        (void)fwd_finish(po.fwd[(size_t)i], 0, &ll, &mean, &var);
+        if (log_lik) log_lik[i] = ll;
+        if (status) status[i] = po.status[(size_t)i] == 2 ? 4 : po.status[(size_t)i];
+        if (po.status[(size_t)i] != 0) continue;
+        std::memcpy(w + (size_t)i * ne, po.w[(size_t)i].data(), ne * 8); std::memcpy(wx + (size_t)i * ne, po.wx[(size_t)i].data(), ne * 8);
+        std::memcpy(wxx + (size_t)i * ne, po.wxx[(size_t)i].data(), ne * 8);
     }
     return STRQ_OK;
 }

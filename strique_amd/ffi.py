@@ -484,6 +484,20 @@ class Context(object):
                                                        _ptr(status), _ptr(cnt), _ptr(s1), _ptr(s2)))
         return logp, counted, status[:n], cnt[:n], s1[:n], s2[:n]
 
+    def forward_state_stats(self, model_id, xs):
+        """strq_forward_state_stats: xs a list of float64 arrays (NaN: missing).  Returns (log_lik[], status[], w, wx, wxx): w, wx
+        and wxx (float64) of shape (windows, silent_start) -- per emitting state the posterior occupancy over all paths and its
+        first two moments of the observations (strique_amd/state_posteriors.py); status 0 ok, 1 no path (zero rows, log_lik -inf),
+        4 the window's stored forward vectors exceed STRQ_STATE_POST_WS_BYTES (log_lik valid, zero rows)."""
+        n = len(xs)
+        x, off = _offsets(xs, np.float64)
+        n_emit = int(self._model_emit[model_id])
+        ll = np.zeros(max(1, n)); status = np.zeros(max(1, n), np.int32)
+        w = np.zeros((max(1, n), n_emit)); wx = np.zeros((max(1, n), n_emit)); wxx = np.zeros((max(1, n), n_emit))
+        self._check(self._lib.strq_forward_state_stats(self._h, ctypes.c_int32(model_id), ctypes.c_int64(n), _ptr(x), _ptr(off), _ptr(ll), _ptr(status),
+                                                       _ptr(w), _ptr(wx), _ptr(wxx)))
+        return ll[:n], status[:n], w[:n], wx[:n], wxx[:n]
+
     def debug_tract_shape(self):
         """strq_debug_tract_shape: the kernel shape id of this context's last tract launch (-1: none yet)."""
         shape = ctypes.c_int32(-1)
@@ -715,6 +729,29 @@ class Context(object):
         """The state-statistics pass of the last run call (strq_last_state_stats): {'ms', 'windows' (traced), 'launches', 'bp_bytes'
         (peak back-pointer bytes of a piece)}."""
         return self._last("state_stats", ("ms", "windows", "launches", "bp_bytes"), floats=("ms", "bp_bytes"))
+
+    def set_state_posteriors(self, on):
+        """strq_set_state_posteriors: later run calls also run forward-backward over every decoded window and sum, per emitting state
+        of the flanked model, its posterior occupancy (batch_fetch_state_posteriors; strique_amd/state_posteriors.py states the rule)."""
+        self._switch("state_posteriors", on)
+
+    def batch_fetch_state_posteriors(self, with_status=False):
+        """State posteriors of the last batch (strq_batch_fetch_state_posteriors): per read None, or (w, wx, wxx, log_lik) -- float64
+        arrays with one entry per emitting state of the read's flanked model and the forward log-likelihood of its window.
+        with_status: (status[], that list) -- 0 statistics, 1 none, 2 stored vectors over the budget."""
+        n = getattr(self, '_n_batch', 0)
+        off = np.zeros(n + 1, np.int64); st = np.zeros(max(1, n), np.int32); ll = np.zeros(max(1, n))
+        self._check(self._lib.strq_batch_fetch_state_posteriors(self._h, _ptr(off), None, None, None, ctypes.c_int64(0), _ptr(ll), _ptr(st)))
+        m = max(1, int(off[-1]))
+        w = np.zeros(m); wx = np.zeros(m); wxx = np.zeros(m)
+        self._check(self._lib.strq_batch_fetch_state_posteriors(self._h, _ptr(off), _ptr(w), _ptr(wx), _ptr(wxx), ctypes.c_int64(m), _ptr(ll), _ptr(st)))
+        out = [None if st[i] != 0 else (w[off[i]:off[i + 1]].copy(), wx[off[i]:off[i + 1]].copy(), wxx[off[i]:off[i + 1]].copy(), float(ll[i])) for i in range(n)]
+        return (st[:n].copy(), out) if with_status else out
+
+    def last_state_posteriors(self):
+        """The state-posteriors pass of the last run call (strq_last_state_posteriors): {'ms', 'windows', 'launches', 'ws_bytes' (peak
+        bytes of stored forward vectors of a piece)}."""
+        return self._last("state_posteriors", ("ms", "windows", "launches", "ws_bytes"), floats=("ms", "ws_bytes"))
 
     def target_set_flank_mod(self, target_id, which, profile_model_id, flank_len, column_of, groups):
         """strq_target_set_flank_mod: the models of flank `which` (0 prefix, 1 suffix, as the strand of the target reads it) --
