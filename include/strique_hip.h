@@ -243,6 +243,25 @@ int strq_forward_state_stats(strq_ctx* ctx, int32_t model_id, int64_t n_seq, con
                              double* log_lik, int32_t* status, double* w, double* wx, double* wxx);
 /* Test hook: the kernel shape id (as strq_debug_viterbi_plan gives it) of the context's last tract launch; -1 before the first. */
 int strq_debug_tract_shape(const strq_ctx* ctx, int32_t* shape);
+/*
+ * The motif track (strique_amd/motifs.py states the rule): which of n_models = K candidate repeat units (2 to 4) each stretch of a
+ * window is made of.  model_ids: the candidates' loop models -- models of strq_model_create with at most 64 emitting states, no
+ * silent state besides start and end, at most 8 in-edges per emitting state from emitting states, and an end state every emitting
+ * state reaches once with log-probability 0 (motifs.loop_arrays builds them); any other model returns STRQ_ERR_UNSUPPORTED.
+ * n_seq float64 windows as they are given (x_off[n_seq + 1] from 0; every window holds at least one observation; NaN: missing).
+ * A window of T observations has n_seg = max(1, T / segment) segments (32 <= segment <= 4096): segment s < n_seg - 1 covers
+ * [s segment, (s + 1) segment), the last one runs to T.
+ *   n_seg[i]            segments of window i; the pools below hold the segments of all windows in window order
+ *   V[seg K + j]        the largest Viterbi value over the emitting states after the last observation of the segment under loop model
+ *                       j, every segment decoded from the start state: float64, evaluated like strq_viterbi -- defined to the bit,
+ *                       whatever windows share the call
+ *   winners[seg]        the candidate with the largest V (the lowest index among equals)
+ *   obs_won[4 i + j]    observations of the segments of window i that candidate j won (0 for j >= K)
+ *   majority[i]         the candidate with the most observations won (the lowest index among equals)
+ * seg_cap: segments the pools V (seg_cap * K doubles) and winners hold; STRQ_ERR_ARG when the windows have more.
+ */
+int strq_motif_track(strq_ctx* ctx, int32_t n_models, const int32_t* model_ids, int32_t segment, int64_t n_seq, const double* x, const int64_t* x_off,
+                     int64_t seg_cap, double* V, int32_t* winners, int64_t* n_seg, int64_t* obs_won, int32_t* majority);
 
 /*
  * ---- repeatCounter.add_target / detect (scripts/STRique.py:553-618) as one device pipeline ----
@@ -576,6 +595,47 @@ int strq_batch_fetch_tract_positions(strq_ctx* ctx, int32_t* pos_status, int64_t
 /* The tract-position pass of the last run call: out[0] = ms on the GPU (all its sub-batches), out[1] = windows traced,
  * out[2] = kernels launched (sorts, decodes, tracebacks, scans; 0 with the switch off), out[3] = peak back-pointer bytes of a piece. */
 int strq_last_tract_positions(strq_ctx* ctx, double* out4);
+/* ---- motifs: which repeat unit each stretch of the array is made of (no counterpart in the reference; strique_amd/motifs.py states
+ * the rule, strq_motif_track is the model-level entry) ----
+ * A target may hold K = 2 to 4 candidate units: per candidate a loop model (see strq_motif_track) and the flanked model of that
+ * unit with its count bias; candidate 0 is the unit of the target's own flanked model.  With the switch on, every read whose gate
+ * passed, that could be conditioned, with prefix_end < suffix_begin and whose target has candidates is scored: the stretch
+ * [prefix_end, suffix_begin) of the filtered signal under the read's conditioning record -- the row's offset and offset + ticks,
+ * which come from the two flank alignments and so do not depend on the configured unit -- cut into segments and scored as
+ * strq_motif_track scores a window.  A flanked decode is not required.  A read whose majority is not candidate 0 is decoded once
+ * more with the flanked model of the majority unit on the window of the count decode, [prefix_begin, suffix_end).
+ * Limits: no anchored reads (their stretch has one end), no scan. */
+typedef struct strq_motifs {
+    int32_t status;         /* 0 scored, 1 not scored (gate failed, read not conditioned, empty stretch, target without candidates):
+                             * the fields below are zero and the read has no segments */
+    int32_t n_cand;
+    int64_t n_seg;
+    int32_t majority;       /* candidate with the most observations won */
+    int32_t decode_status;  /* 0: count_m and log_p_m are valid; 1: none -- majority 0 and the row has no decode, or the majority
+                             * model found no path */
+    int64_t begin, end;     /* the stretch in raw samples */
+    int64_t obs_won[4];     /* zero beyond n_cand */
+    int32_t count_m;        /* the count under the majority unit: the row's count for majority 0, else visits + that model's bias */
+    int32_t pad_;
+    double log_p_m;
+} strq_motifs;
+/* The candidates of a target: n = 2 to 4, loop_model_ids[j] / flanked_model_ids[j] / bias[j] of candidate j; flanked_model_ids[0] is
+ * not read (candidate 0 takes the row's decode).  n = 0 takes them away.  STRQ_ERR_UNSUPPORTED for a loop model the track does not
+ * cover or a flanked model no compiled Viterbi kernel takes; the target stays as it was.  Never in the middle of a batch. */
+int strq_target_set_motifs(strq_ctx* ctx, int32_t target_id, int32_t n, const int32_t* loop_model_ids, const int32_t* flanked_model_ids, const int32_t* bias);
+/* on = 1: later run calls run the motif pass behind the rows with segments of `segment` observations (32 .. 4096): the host writes
+ * the stretches from the geometry it holds, one launch of the track kernel and one of the reduction per sub-batch, one read-back;
+ * then, for the reads whose majority is not candidate 0, a task kernel and one count-decode launch per kernel instance in use.
+ * Rows and every other output do not change.  A run call with the switch on fails before any launch (STRQ_ERR_ARG) when it is a
+ * scan.  Default 0: no further kernel runs and no further buffer is reserved. */
+int strq_set_motifs(strq_ctx* ctx, int32_t on, int32_t segment);
+/* One record per read of the last batch (n = its reads), and ragged the segments: off[n + 1] counts segments, segment s of read i has
+ * winners[off[i] + s] and the scores V[4 (off[i] + s) + j] of candidate j (zero beyond n_cand).  V and winners may both be NULL to
+ * query the total in off[n]; seg_cap: segments the pools hold.  STRQ_ERR_ARG when the last run call ran with the switch off. */
+int strq_batch_fetch_motifs(strq_ctx* ctx, strq_motifs* out, int64_t n, int64_t* off, double* V, int32_t* winners, int64_t seg_cap);
+/* The motif pass of the last run call: out[0] = ms on the GPU (all its sub-batches), out[1] = reads scored, out[2] = segments,
+ * out[3] = kernels launched (track, reduction, tasks, sorts and decodes; 0 with the switch off), out[4] = majority decodes. */
+int strq_last_motifs(strq_ctx* ctx, double* out5);
 /* ---- state statistics: what the best path of the flanked decode assigns to every emitting state (no counterpart in the reference;
  * strique_amd/state_stats.py states the rule, strique_amd/calibrate.py re-estimates k-mer levels from it) ----
  * on = 1: later run calls, once the rows of a sub-batch are on the host, decode every window whose gate passed and whose flanked decode

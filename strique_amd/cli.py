@@ -23,6 +23,7 @@ import numpy as np
 
 from . import anchored as anchored_mod
 from . import flank_mod as flank_mod_rule
+from . import motifs as motifs_mod
 from . import renorm as renorm_mod
 from . import scan as scan_mod
 from . import tracts as tracts_mod
@@ -263,6 +264,14 @@ def count(argv):
                                                                                                        "the raw signal to FILE: one row per count row, columns " + " ".join(tracts_mod.POS_HEADER) +
                                                                                                        " (spans first-last per tract joined by commas; positions joined by commas within a "
                                                                                                        "tract and ; between tracts; - for a tract or a read without positions)")
+    parser.add_argument("--motif-units", dest="motif_units", default=None, metavar="FILE", help="Loci whose array may be made of another unit than the configured one (RFC1: AAAAG, "
+                                                                                              "AAAGG or AAGGG): a TSV of target<TAB>U1[,U2[,U3]] (1 to 3 alternative units on the + "
+                                                                                              "strand, of any length; # comments and blank lines allowed)")
+    parser.add_argument("--motifs", default=None, metavar="FILE", help="With --motif-units: also write which unit each stretch of a read's array is made of to FILE: one row per count "
+                                                                       "row, columns " + " ".join(motifs_mod.HEADER) + " (shares in the configured order, the configured unit first; runs "
+                                                                       "unit:first-end in raw samples; count_m the count under the majority unit)")
+    parser.add_argument("--motif-segment", dest="motif_segment", type=int, default=None, metavar="N", help="--motifs: observations per segment, %d to %d (default %d: a resolution "
+                                                                                                           "chosen on synthetic reads, not a tuned value)" % (motifs_mod.SEGMENT_MIN, motifs_mod.SEGMENT_MAX, motifs_mod.SEGMENT))
     parser.add_argument("--scan", action="store_true", help="No alignment: every read of the index is compared with every target of the repeat config on both strands, "
                                                              "from its raw signal alone, and counted for the one it spans (if any).  Excludes --algn; stdin is not read")
     parser.add_argument("--scan-min-score", type=float, default=None, metavar="X", help="--scan: the smallest min(score_prefix, score_suffix) a target and strand needs to be "
@@ -295,6 +304,12 @@ def count(argv):
         parser.error("--variants needs --alt-units FILE: the units to tell from the repeat unit")
     if bool(args.tracts) != bool(args.tract_units):
         parser.error("--tract-units FILE and --tracts FILE need each other: the definitions, and where the counts go")
+    if bool(args.motifs) != bool(args.motif_units):
+        parser.error("--motif-units FILE and --motifs FILE need each other: the alternative units, and where the track goes")
+    if args.motif_segment is not None and not args.motifs:
+        parser.error("--motif-segment N needs --motif-units FILE --motifs FILE")
+    if args.motif_segment is not None and not motifs_mod.SEGMENT_MIN <= args.motif_segment <= motifs_mod.SEGMENT_MAX:
+        parser.error("--motif-segment N must lie between %d and %d" % (motifs_mod.SEGMENT_MIN, motifs_mod.SEGMENT_MAX))
     if args.tract_positions and not args.tracts:
         parser.error("--tract-positions FILE needs --tract-units FILE --tracts FILE: the positions are those of the tract counts")
     if args.scan and args.algn:
@@ -349,6 +364,17 @@ def count(argv):
             log("Main: %s" % e, 'error'); raise SystemExit(1)
         if not tract_defs:
             log("Main: --tracts: the tract-units file defines no target.", 'error'); raise SystemExit(1)
+    motif_defs = {}
+    if args.motif_units:
+        if not os.path.isfile(args.motif_units):
+            log("Main: Motif-units file does not exist.", 'error'); raise SystemExit(1)
+        try:
+            with open(args.motif_units) as fp:
+                motif_defs = motifs_mod.parse_definitions(fp, {name: (v[3], None) for name, v in config['repeat'].items()})
+        except ValueError as e:
+            log("Main: %s" % e, 'error'); raise SystemExit(1)
+        if not motif_defs:
+            log("Main: --motifs: the motif-units file defines no target.", 'error'); raise SystemExit(1)
     for path, what in ((args.f5Index, "Fast5 index file"), (args.model, "Pore model file")):
         if not os.path.isfile(path):
             log("Main: %s does not exist." % what, 'error'); raise SystemExit(1)
@@ -375,7 +401,8 @@ def count(argv):
     for name, (chrom, begin, end, repeat, prefix, suffix) in config['repeat'].items():
         try:
             counter.add_target(name, repeat, prefix, suffix, **({'alt_units': alt_units[name]} if name in alt_units else {}),
-                               **({'tracts': tract_defs[name]} if name in tract_defs else {}))
+                               **({'tracts': tract_defs[name]} if name in tract_defs else {}),
+                               **({'motifs': list(motif_defs[name])} if name in motif_defs else {}))
         except ValueError:
             raise
         except Exception as e:                # e.g. a flank longer than the compiled kernel shapes cover
@@ -433,7 +460,7 @@ def count(argv):
                 write_rows(out, merged.rows)
                 for o in ALL_OUTPUTS:
                     if files[o.name] is not None:
-                        write_rows(files[o.name], merged.riders[o.name] if o.rides else getattr(merged, o.name), header=o.header(scan))
+                        write_rows(files[o.name], merged.riders[o.name] if o.name in merged.riders else getattr(merged, o.name), header=o.header(scan))
             dist.barrier()
             dist.destroy_process_group()
     if stats.get("failed"):
@@ -726,7 +753,42 @@ RIDERS = (
                                        None if asked.get('tracts') else "tract positions need the tract counts"),
            no_scan=_ALIGNED % "tract", rides=('tracts', 'positions')),
 )
-ALL_OUTPUTS = OUTPUTS + RIDERS
+
+def motifs_value(rec, units):
+    """The value of the motifs output from a record of repeatCounter.motif_records and the target's candidates: None or a motifs.Row."""
+    if rec is None:
+        return None
+    majority, shares, count_m, log_p_m, runs, winners, _ = rec
+    return motifs_mod.Row(tuple(units), len(winners), majority, tuple(shares), count_m, log_p_m, [tuple(r) for r in runs])
+
+
+def _pack_motifs(v):
+    """A motifs.Row as it travels between ranks: units | segments | majority | shares | count_m | log_p_m | runs, floats as repr()."""
+    return '|'.join([','.join(v.units), str(int(v.n_segments)), str(int(v.majority)), ','.join(repr(float(x)) for x in v.shares),
+                     '-' if v.count_m is None else str(int(v.count_m)), '-' if v.log_p_m is None else repr(float(v.log_p_m)),
+                     ','.join('%d:%d:%d' % tuple(r) for r in v.runs)])
+
+
+def _unpack_motifs(text):
+    f = text.split('|')
+    return motifs_mod.Row(tuple(f[0].split(',')), int(f[1]), int(f[2]), tuple(float(x) for x in f[3].split(',')), None if f[4] == '-' else int(f[4]),
+                          None if f[5] == '-' else float(f[5]), [tuple(int(x) for x in r.split(':')) for r in f[6].split(',')])
+
+
+# Outputs beside the passes of the counter: a file, a flag, a keyword of run_count and a stat of their own, and a field of their own at
+# the end of the gather blob when they are on -- but no row of counter.PASSES and no field of Detected or `Merged`: the counter keeps
+# their values beside the records of its last call (ask 'side': set_<name>(True, value) before the run, set_<name>(False) behind it;
+# side(counter, target, k): the value of read k of that call).  They travel between ranks like the RIDERS' rows, in Merged.riders.
+SIDE_RECORDS = {'motifs': 'motif_records'}          # where the counter keeps the values of its last call
+SIDES = (
+    Output('motifs', lambda scan: motifs_mod.HEADER, lambda q, t, s, row, v: motifs_mod.format_row(q, t, s, row[0], v),
+           _pack_motifs, _unpack_motifs, 'motif_rows', False,
+           file='motifs_out', ask='side', flag='--motifs', value=None,
+           refuse=_not_with_scan("motifs cannot be combined with a scan"),
+           arg=lambda args, alt_units: (args.motif_segment or motifs_mod.SEGMENT) if args.motifs else None,
+           no_scan="the track scores the stretch between the two flanks of the target an alignment gives"),
+)
+ALL_OUTPUTS = OUTPUTS + RIDERS + SIDES
 # (`renorm`, `variants`, `flank_mod`, `tracts`, `anchored_mod` and `anchored`, the last fields, default to None: callers that build a Merged from the five
 # values before them keep working.  `anchored` stays the last field, as it did when `variants`, `anchored_mod` and `tracts` came in: fields
 # behind the first five are taken by name.)
@@ -801,7 +863,7 @@ def _unpack_anchored(text):
 
 def outputs_on(**flags):
     """The entries of OUTPUTS whose flag (its name as a keyword) is set."""
-    unknown = set(flags) - set(Merged._fields[1:]) - {o.name for o in RIDERS}
+    unknown = set(flags) - set(Merged._fields[1:]) - {o.name for o in RIDERS + SIDES}
     if unknown:
         raise TypeError("no such output: %s" % ", ".join(sorted(unknown)))
     return [o for o in ALL_OUTPUTS if flags.get(o.name)]
@@ -849,6 +911,10 @@ def pack_blob(on, target, strand, mod, values):
     for o in OUTPUTS:
         v = values.get(o.name) if o in on else None
         fields.append('-' if _absent(v) else o.pack(v))
+    for o in SIDES:          # (a field of their own, only when they are on)
+        if o in on:
+            v = values.get(o.name)
+            fields.append('-' if v is None else o.pack(v))
     return '\t'.join(fields)
 
 
@@ -856,6 +922,8 @@ def unpack_blob(on, blob):
     """(target, strand, mod, values) of pack_blob(on, ...): target and strand as they travelled, None for every '-' value."""
     fields = blob.split('\t')
     values = {o.name: None if (o not in on or f == '-') else o.unpack(f) for o, f in zip(OUTPUTS, fields[3:])}
+    for o, f in zip([o for o in SIDES if o in on], fields[3 + len(OUTPUTS):]):
+        values[o.name] = None if f == '-' else o.unpack(f)
     return fields[0], fields[1], fields[2], values
 
 
@@ -896,7 +964,7 @@ def gather_rows(rows, items, sdist, units=False, scan=None, **flags):
             row = (n, float(r["score_prefix"]), float(r["score_suffix"]), p, int(r["offset"]), int(r["ticks"]), mod)
         _emit(sink, on, seq, qname, target, strand, row, values)
     merged = Merged(sink['rows'], *[sink[o.name] if o in on else None for o in OUTPUTS])
-    merged.riders = {o.name: sink[o.name] for o in RIDERS if o in on}
+    merged.riders = {o.name: sink[o.name] for o in RIDERS + SIDES if o in on}
     return merged
 
 
@@ -976,8 +1044,11 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
             getattr(counter, 'set_' + o.name)(asked[o.name] if o.level else True, **riding.get(o.name, {}))
         elif o.ask == 'keyword':
             extras[o.name] = asked[o.name] if o.level else True
+        elif o.ask == 'side':
+            getattr(counter, 'set_' + o.name)(True, asked[o.name])
         if o.ask == 'switch' or o.level:
             extras['records'] = True
+    sides = [o for o in on if o.ask == 'side']
     rows = []
     records = ((rid, '.', ['.'], 0) for rid in stream) if scan else route(stream, loci, log)
     mine_set = None
@@ -999,6 +1070,7 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
         formatted; returns (rows, number of failed reads)."""
         failed = 0
         results = None
+        side_values = {}
         if faulted.is_set():                                      # queued behind the batch that faulted: the device is not touched again
             raise DeviceFault("not run: the device failed in an earlier batch")
         def scan_some(raws):
@@ -1009,6 +1081,7 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
                 results = scan_some([raw for _, _, _, _, raw in batch])
             else:
                 results = counter.detect_batch([(t, raw, s) for _, _, t, s, raw in batch], **extras)
+                side_values = {o.name: list(getattr(counter, SIDE_RECORDS[o.name])) for o in sides}
         except StriqueHipError as e:
             if e.code not in (STRQ_ERR_ARG, STRQ_ERR_UNSUPPORTED):
                 # a device fault or an out-of-memory condition will not go away read by read
@@ -1023,6 +1096,8 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
             for _, _, t, s, raw in batch:
                 try:
                     results.append(scan_some([raw])[0] if scan else counter.detect(t, raw, s, **extras))
+                    for o in sides:
+                        side_values.setdefault(o.name, []).append(getattr(counter, SIDE_RECORDS[o.name])[0])
                 except StriqueHipError as e1:
                     if e1.code not in (STRQ_ERR_ARG, STRQ_ERR_UNSUPPORTED):
                         faulted.set()
@@ -1031,14 +1106,20 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
                     log("Detector: read failed: %s" % e1, 'warning'); results.append(None); failed += 1
                 except Exception as e1:
                     log("Detector: read failed: %s" % e1, 'warning'); results.append(None); failed += 1
+                for o in sides:          # (a read that failed has no value)
+                    side_values.setdefault(o.name, [])
+                    if len(side_values[o.name]) < len(results):
+                        side_values[o.name].append(None)
         sink = defaultdict(list)
-        for (seq, qname, target, strand, _), res in zip(batch, results):
+        for k, ((seq, qname, target, strand, _), res) in enumerate(zip(batch, results)):
             read = None
             if res is not None and scan:
                 winner, sc = res
                 read = _read_values(None, None, None, sc) if winner is None else _read_values(winner[0], winner[1], as_detected(winner[2], legacy['units']), sc, counter, asked)
             elif res is not None:
                 read = _read_values(target, strand, as_detected(res, **legacy), None, counter, asked)
+                for o in sides:
+                    read[3][o.name] = motifs_value(side_values[o.name][k], counter.motif_units.get(target, ()))
             if world > 1:
                 sink['rows'].append((seq, read))
             elif read is not None:
@@ -1160,6 +1241,8 @@ def run_count(stream, loci, get_raw, counter, log, batch_size, rank=0, world=1, 
             for o in on:
                 if o.ask == 'switch':
                     getattr(counter, 'set_' + o.name)(None if o.level else False)          # the switch belongs to this run
+                elif o.ask == 'side':
+                    getattr(counter, 'set_' + o.name)(False)
         else:
             # an exception is on its way out (a DeviceFault from the engine thread, a broken input): the batch queued behind
             # the failed one must not be handed to a device that may be hung, and nobody waits for it -- the caller exits,

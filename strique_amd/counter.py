@@ -18,6 +18,7 @@ from . import anchored as anchored_mod
 from . import ffi
 from . import flank_mod as flank_mod_rule
 from . import hmm as hmm_mod
+from . import motifs as motifs_mod
 from . import renorm as renorm_mod
 from . import tracts as tracts_mod
 from .pore_model import pore_model
@@ -164,6 +165,14 @@ class repeatCounter(object):
         self.flank_mod_models = {}
         self.flank_mod_refused = {}
         self.flank_mod = False         # set_flank_mod
+        # motifs: (strand, candidates as the strand reads them, prefix, suffix) of the classifiers of a target added with motifs, and the
+        # classifiers whose loop and flanked models are registered ({target_id: [(unit, loop id, flanked id, bias)]}); baked on first use
+        self._motif_src = {}
+        self.motif_models = {}
+        self.motif_units = {}          # {target name: the candidates as configured}
+        self.motifs = None             # set_motifs: the segment length, or None
+        self.motif_records = None      # with set_motifs on: the motif record of every read of the last detect_batch call, in input order
+        self._motif_values = {}
 
     # -------------------------------------------------------------------------------------
     def _classifier(self, repeat, prefix, suffix, prefix_ext, suffix_ext):
@@ -232,6 +241,62 @@ class repeatCounter(object):
             self.ctx.model_set_tracts(m.model_id, m.n_tracts, m.tract_of)
             self.ctx.target_set_tracts(tid, m.model_id, m.n_tracts, m.count_bias)
             self.tract_models[tid] = (m, strand)
+
+    def _ensure_motifs(self):
+        """The loop model of every candidate, and the flanked model of every alternative, of the classifiers with motifs that have
+        none yet: baked, uploaded and registered.  Candidate 0 decodes with the classifier's own flanked model."""
+        for tid, (strand, units, prefix, suffix) in self._motif_src.items():
+            if tid in self.motif_models:
+                continue
+            made = []
+            for j, unit in enumerate(units):
+                flanked = hmm_mod.FlankedRepeatModel(unit, prefix, suffix, self.pm, self.HMM_config)
+                loop_id = self.ctx.model_create(motifs_mod.loop_arrays(flanked.baked))
+                made.append((unit, loop_id, self.ctx.model_create(flanked.baked) if j else -1, flanked.count_bias))
+            self.ctx.target_set_motifs(tid, [m[1] for m in made], [max(m[2], 0) for m in made], [m[3] for m in made])
+            self.motif_models[tid] = made
+
+    def motifs_batch(self, items, segment=motifs_mod.SEGMENT):
+        """Which repeat unit each stretch of the array is made of (strique_amd.motifs states the rule).  items: iterable of
+        (target_name, raw_signal, strand).  Returns [(row, motifs)] in input order: row the tuple detect() returns, unchanged;
+        motifs None -- the gate failed, the read was not conditioned, the two flanks leave no stretch between them, or the target
+        was added without motifs -- or (majority, shares, count_m, log_p_m, runs, winners, V): the candidate (0 = `repeat`, then the
+        alternatives in configured order, on either strand) with the most observations won; every candidate's share of the
+        stretch; the count and log-probability of the flanked decode under the majority unit (the row's own for majority 0; None,
+        None without a decode); the maximal runs of equal winners as (candidate, first_sample, end_sample) in raw samples, in
+        signal order; per segment the winner (int32) and the scores V (n_seg, K) float64.  `segment`: observations per segment, 32
+        to 4096.  set_motifs(True, segment) around one detect_batch call; the switch is put back to what it was before it returns, and
+        the other switches of the counter (set_renorm, ...) work underneath it.  ValueError when no target was added with motifs.  Not with scan_batch, and not for anchored reads."""
+        before = self.motifs
+        self.set_motifs(True, segment)
+        try:
+            rows = self.detect_batch(list(items), records=True)
+            return [(d.row, m) for d, m in zip(rows, self.motif_records)]
+        finally:
+            self.motifs = before
+
+    def set_motifs(self, on, segment=motifs_mod.SEGMENT):
+        """on: detect and detect_batch also run the motif track on every read of a target added with motifs=[...], in segments of
+        `segment` observations (32 to 4096), and keep the records of their last call in `motif_records`: one entry per read, in input
+        order, None or (majority, shares, count_m, log_p_m, runs, winners, V) as motifs_batch describes them.  The tuples detect_batch
+        returns and the fields of Detected stay as they are.  A switch of the counter, like set_tracts.  ValueError when no target was
+        added with motifs, or for a segment length outside the range.  Not with scan_batch."""
+        if not on:
+            self.motifs = None
+            return
+        if not self._motif_src:
+            raise ValueError("RepeatCounter: motifs needs a target added with motifs=[...].")
+        self.motifs = motifs_mod.check_segment(segment)
+
+    @staticmethod
+    def _motif_record(rec, V, win, segment):
+        if int(rec['status']) != 0:
+            return None
+        K, T = int(rec['n_cand']), int(rec['end'] - rec['begin'])
+        bounds = motifs_mod.segments(T, segment)
+        decoded = int(rec['decode_status']) == 0
+        return (int(rec['majority']), tuple(int(o) / T for o in rec['obs_won'][:K]), int(rec['count_m']) if decoded else None,
+                float(rec['log_p_m']) if decoded else None, motifs_mod.runs(win, bounds, int(rec['begin'])), win, V)
 
     def set_tracts(self, on, positions=False):
         """on: detect and detect_batch also decode the compound model of every read of a target added with tracts=(units, linkers)
@@ -332,16 +397,19 @@ class repeatCounter(object):
             raise ValueError("RepeatCounter: variants needs a target added with alt_units.")
         self.variants = bool(on)
 
-    def add_target(self, target_name, repeat, prefix, suffix, alt_units=None, tracts=None):
+    def add_target(self, target_name, repeat, prefix, suffix, alt_units=None, tracts=None, motifs=None):
         """alt_units: 1 to 3 sequence variants of the repeat unit (on the + strand, as `repeat`) that detect
         tells from it once set_variants(True) is called; ValueError for units hmm.check_alt_units does not take.
         tracts: (units, linkers), the compound definition of the locus on the + strand (strique_amd.tracts: 2 or 3 units, one linker
         -- possibly empty -- between neighbours), counted per tract once set_tracts(True) is called; ValueError for what
-        tracts.check does not take.  `repeat` stays the unit of the count row."""
+        tracts.check does not take.  `repeat` stays the unit of the count row.
+        motifs: 1 to 3 alternative units of any length (on the + strand, as `repeat`) the array may be made of instead; motifs_batch
+        says which one each stretch of a read's array is made of; ValueError for what strique_amd.motifs.check does not take."""
         if target_name in self.targets:
             raise ValueError("RepeatCounter: Target with name " + str(target_name) + " already defined.")
         alts = hmm_mod.check_alt_units(repeat, alt_units) if alt_units else None
         tract_def = tracts_mod.check(*tracts) if tracts else None
+        candidates = motifs_mod.check(repeat, motifs, self.pm.kmer) if motifs else None
         prefix_ext = prefix.upper(); prefix = prefix[-50:].upper()            # STRique.py:555-559
         suffix_ext = suffix.upper(); suffix = suffix[:50].upper()
         repeat = repeat.upper()
@@ -355,6 +423,11 @@ class repeatCounter(object):
             # the - strand reads the reverse complement of unit and alt units; calls are reported with the number of the unit as configured
             self._variant_src[tc_plus.target_id] = (repeat, alts)
             self._variant_src[tc_minus.target_id] = (rc(repeat), [rc(a) for a in alts])
+        if candidates:
+            # the - strand reads the reverse complement of every candidate; results are reported in the configured order
+            self.motif_units[target_name] = tuple(candidates)
+            self._motif_src[tc_plus.target_id] = ('+', motifs_mod.strand_units(candidates, '+'), prefix, suffix)
+            self._motif_src[tc_minus.target_id] = ('-', motifs_mod.strand_units(candidates, '-'), rc(suffix), rc(prefix))
         if tract_def:
             # the - strand reads the reverse complements in reverse order; counts are reported in the configured order
             self._tract_src[tc_plus.target_id] = ('+',) + tracts_mod.strand_definition(*tract_def, '+') + (prefix, suffix)
@@ -421,12 +494,16 @@ class repeatCounter(object):
         legacy = sorted((p for p in PASSES if p.name in request and p.place is not None), key=lambda p: p.place)
         reads = [(self._classifier_for(t, s).target_id, r) for t, r, s in items]
         out = [None] * len(items)
+        self._motif_values = {}
+        self.motif_records = None
         for i, d, _, _ in self._run(reads, request):
             if records:
                 out[i] = d
                 continue
             extra = tuple(p.legacy(getattr(d, p.field)) for p in legacy)
             out[i] = (d.row,) + extra if extra else d.row
+        if self.motifs is not None:
+            self.motif_records = [self._motif_values.get(i) for i in range(len(items))]
         return out
 
     def state_stats_batch(self, items, posterior=False):
@@ -466,6 +543,7 @@ class repeatCounter(object):
     def _switches(self, request):
         """The passes of `request` ({name: value}, see PASSES) are on inside the block, and every pass is off after it."""
         with_positions = 'tracts' in request and self.tract_positions      # (rides on the tracts switch; a context is asked only then)
+        with_motifs = self.motifs is not None                              # (a switch of its own behind the passes; a context is asked only then)
         try:
             # inside the try: set_mod_llr refuses a modification model the scoring pass does not cover, and the switches a
             # failed call leaves behind must not stay on for the next caller of a shared context
@@ -476,8 +554,13 @@ class repeatCounter(object):
                     getattr(self.ctx, 'set_' + p.name)(True, *((request[p.name],) if p.level else ()))
             if with_positions:
                 self.ctx.set_tract_positions(True)
+            if with_motifs:
+                self._ensure_motifs()
+                self.ctx.set_motifs(True, self.motifs)
             yield
         finally:
+            if with_motifs:
+                self.ctx.set_motifs(False)
             if with_positions:
                 self.ctx.set_tract_positions(False)
             for p in reversed(PASSES):
@@ -506,6 +589,10 @@ class repeatCounter(object):
                     res, win, sc = self.ctx.scan_batch_reads(arrs, scan[0], scan[1], scores=True)
                 mods = self.ctx.batch_fetch_mod() if self.pm is not self.pm_mod else ['-'] * len(res)
                 fetched = {p.field: p.fetch(self, reads, idx) for p in PASSES if p.name in request}
+                if self.motifs is not None and scan is None:
+                    rec, V, win = self.ctx.batch_fetch_motifs()
+                    for k, i in enumerate(idx):
+                        self._motif_values[i] = self._motif_record(rec[k], V[k], win[k], self.motifs)
             # one column per field of Detected behind the row, in the record's own order: all None for a pass that is off
             columns = zip(*[fetched.get(f, [None] * len(res)) for f in Detected._fields[1:]])
             for i, r, m, w, s, values in zip(idx, res, mods, win, sc, columns):
@@ -535,6 +622,8 @@ class repeatCounter(object):
             raise ValueError("RepeatCounter: renorm is not available in a scan (set_renorm(None) first).")
         if self.tracts:
             raise ValueError("RepeatCounter: tracts are not available in a scan (set_tracts(False) first).")
+        if self.motifs is not None:
+            raise ValueError("RepeatCounter: motifs are not available in a scan (set_motifs(False) first).")
         if min_score is None:
             raise ValueError("RepeatCounter: scan_batch needs min_score (there is no default: see README, 'Scan').")
         if not min_score > 0:

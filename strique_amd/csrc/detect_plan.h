@@ -32,19 +32,21 @@ struct Carve {
 // come with.  DetectState holds what the next run call uses, a slot what its sub-batch was launched with, Batch what the last run call
 // ran with.
 struct Extras { bool units = false, conf = false, llr = false, anch = false, var = false; double anch_min = 0.0; bool renorm = false; double renorm_min = 0.0; bool amod = false;
-                bool tracts = false, fmod = false, tpos = false, sstats = false, spost = false; };
+                bool tracts = false, fmod = false, tpos = false, sstats = false, spost = false;
+                bool motifs = false; int motif_segment = 0; };
 
 // The passes, said once.  What the last run call's pass did is one PassStats: the GPU milliseconds and up to seven counters, which the
 // pass's own enum names.  A row of PASSES holds what the entry points need of a pass: its name in messages, its switch, what a batch
 // that ran without it lacks and the entry that turns it on (the "ran without" refusal of its fetch), whether a scan refuses it, and the
 // layout strq_last_* hands out -- `out[k]` is the counter at position k, MS the milliseconds.
-enum Pass { PASS_UNITS, PASS_CONF, PASS_LLR, PASS_VAR, PASS_ANCH, PASS_AMOD, PASS_TRACTS, PASS_RENORM, PASS_FMOD, PASS_TPOS, PASS_SSTATS, PASS_SPOST, N_PASS };
+enum Pass { PASS_UNITS, PASS_CONF, PASS_LLR, PASS_VAR, PASS_ANCH, PASS_AMOD, PASS_TRACTS, PASS_RENORM, PASS_FMOD, PASS_TPOS, PASS_SSTATS, PASS_SPOST, PASS_MOTIFS, N_PASS };
 struct PassStats { float ms; double v[7]; };
 enum { UNIT_BYTES, UNIT_READS, UNIT_POSITIONS, CONF_WINDOWS = 0, CONF_NOPATH, CONF_EXPO, LLR_UNITS = 0, LLR_READS, LLR_LAUNCHES,
        VAR_LAUNCHES = 0, VAR_PASSAGES, VAR_READS, ANCH_KINDS = 0 /* .. 3: reads of kind 0 .. 3 */, ANCH_LAUNCHES = 4, ANCH_G2, ANCH_LANE,
        AMOD_READS = 0, AMOD_UNITS, AMOD_LAUNCHES, TRACT_WINDOWS = 0, TRACT_LAUNCHES, TRACT_FAILED, RN_FITTED = 0, RN_APPLIED, RN_LAUNCHES,
        FMOD_FLANKS = 0, FMOD_GROUPS, FMOD_LAUNCHES, TPOS_WINDOWS = 0, TPOS_LAUNCHES, TPOS_BYTES,
-       SST_WINDOWS = 0, SST_LAUNCHES, SST_BYTES, SPOST_WINDOWS = 0, SPOST_LAUNCHES, SPOST_BYTES };
+       SST_WINDOWS = 0, SST_LAUNCHES, SST_BYTES, SPOST_WINDOWS = 0, SPOST_LAUNCHES, SPOST_BYTES,
+       MOTIF_READS = 0, MOTIF_SEGMENTS, MOTIF_LAUNCHES, MOTIF_DECODES /* strq_last_motifs hands it out behind the row's four */ };
 constexpr int8_t MS = -1;
 struct PassInfo { const char* name; bool Extras::* on; const char* lacks; const char* entry; bool scan_refuses; int n_out; int8_t out[8]; };
 constexpr PassInfo PASSES[N_PASS] = {
@@ -60,13 +62,14 @@ constexpr PassInfo PASSES[N_PASS] = {
     {"tract-positions", &Extras::tpos, "tract positions", "strq_set_tract_positions", true, 4, {MS, 0, 1, 2}},
     {"state-stats", &Extras::sstats, "state statistics", "strq_set_state_stats", true, 4, {MS, 0, 1, 2}},
     {"state-posteriors", &Extras::spost, "state posteriors", "strq_set_state_posteriors", true, 4, {MS, 0, 1, 2}},
+    {"motifs", &Extras::motifs, "the motif track", "strq_set_motifs", true, 4, {MS, 0, 1, 2}},
 };
 inline void pass_stats_out(Pass p, const PassStats& s, double* out)
 {
     for (int k = 0; k < PASSES[p].n_out; ++k) out[k] = PASSES[p].out[k] == MS ? (double)s.ms : s.v[PASSES[p].out[k]];
 }
 // The pass a scan refuses first among those switched on, in the order the run call has always looked (N_PASS: none); the refusals as text
-constexpr Pass SCAN_CHECKS[] = {PASS_AMOD, PASS_ANCH, PASS_VAR, PASS_TRACTS, PASS_RENORM, PASS_FMOD, PASS_TPOS, PASS_SSTATS, PASS_SPOST};
+constexpr Pass SCAN_CHECKS[] = {PASS_AMOD, PASS_ANCH, PASS_VAR, PASS_TRACTS, PASS_RENORM, PASS_FMOD, PASS_TPOS, PASS_SSTATS, PASS_SPOST, PASS_MOTIFS};
 inline Pass scan_refusal(const Extras& ex)
 {
     for (Pass p : SCAN_CHECKS) if (PASSES[p].scan_refuses && ex.*PASSES[p].on) return p;
@@ -142,6 +145,7 @@ struct ReadRows {
         amod_called.clear(); amod.clear(); amod_llr.clear();
         var.assign(m, VariantRow());
         renorm.clear(); tracts.clear(); fmod_called.clear(); fmod.clear(); tpos_status.clear(); tpos.clear(); sst_status.clear(); sst.clear(); spost_status.clear(); spost.clear();
+        motifs.clear(); motif_V.clear(); motif_win.clear();
     }
     std::vector<strq_tracts> tracts;              // per-tract counts of the compound model (strq_batch_fetch_tracts); status 1: not decoded.  Empty
                                                   // until a run call with the switch on sizes it (size_tracts)
@@ -162,6 +166,12 @@ struct ReadRows {
     struct StatePostRow { double log_lik = NAN; std::vector<double> w, wx, wxx; };
     std::vector<int32_t> spost_status;            // 0 statistics, 1 none (not decoded, or no path in the forward pass), 2 stored vectors over the budget
     std::vector<StatePostRow> spost;              // n_emit entries each where the status is 0, else empty
+    // the motif track (strq_batch_fetch_motifs): empty until a run call with the switch on sizes them (size_motifs)
+    std::vector<strq_motifs> motifs;              // status 1: not scored
+    std::vector<std::vector<double>> motif_V;     // n_seg * n_cand scores per read, segment-major
+    std::vector<std::vector<int32_t>> motif_win;  // n_seg winners per read
+    static strq_motifs no_motifs() { strq_motifs m = strq_motifs(); m.status = 1; m.decode_status = 1; return m; }
+    void size_motifs() { if (motifs.size() != results.size()) { motifs.assign(results.size(), no_motifs()); motif_V.assign(results.size(), std::vector<double>()); motif_win.assign(results.size(), std::vector<int32_t>()); } }
     void size_spost() { if (spost_status.size() != results.size()) { spost_status.assign(results.size(), 1); spost.assign(results.size(), StatePostRow()); } }
     static strq_tracts no_tracts() { strq_tracts t = strq_tracts(); t.status = 1; return t; }
     void size_tracts() { if (tracts.size() != results.size()) tracts.assign(results.size(), no_tracts()); }
@@ -188,6 +198,7 @@ struct ReadRows {
         if (r < tpos_status.size()) { tpos_status[r] = 1; for (int j = 0; j < 3; ++j) tpos[3 * r + j].clear(); }
         if (r < sst_status.size()) { sst_status[r] = 1; sst[r] = StateStatsRow(); }
         if (r < spost_status.size()) { spost_status[r] = 1; spost[r] = StatePostRow(); }
+        if (r < motifs.size()) { motifs[r] = no_motifs(); motif_V[r].clear(); motif_win[r].clear(); }
     }
 };
 

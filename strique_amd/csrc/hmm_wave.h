@@ -1,5 +1,5 @@
 // Internal: what the wave-per-window HMM kernels share (viterbi_kernels.hip, forward_kernels.hip, posterior_kernels.hip,
-// mod_llr_kernels.hip) -- the fetch of the next task, lane exchange of doubles, the DPP row shifts and the wave maximum of the
+// mod_llr_kernels.hip, motif_kernels.hip) -- the fetch of the next task, lane exchange of doubles, the DPP row shifts and the wave maximum of the
 // linear-space kernels with their emission density, the wavefront fence, and how a window is read from its VitTask.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -72,6 +72,18 @@ static __device__ __forceinline__ double hmm_emission(double x, bool has, int ki
     else if (kind == 1) { const double d = x - a; em = exp(c - (d * d) * b); }
     else if (kind == 2) em = (x >= a && x <= b) ? u : 0.0;
     else em = 0.0;
+    return em;
+}
+// Log emission density of observation x, as oracle/viterbi_oracle.c writes it (the motif track; the Viterbi and score kernels
+// carry the same expressions inline): a missing observation (NaN) has log-probability 0 under every distribution; kind 1 Normal
+// c - (x - a)^2 b, otherwise Uniform: c inside [a, b], -inf outside.  A lane without a state (kind 0) must not use the value.
+static __device__ __forceinline__ double hmm_log_emission(double x, int kind, double a, double b, double c)
+{
+    const double d = x - a;
+    const double en = c - (d * d) * b;
+    const double eu = (x >= a && x <= b) ? c : -INFINITY;
+    double em = kind == 1 ? en : eu;
+    if (x != x) em = 0.0;
     return em;
 }
 // Observation `idx` (< T: the caller tests it) of a window: x = clip((s - c1) / h1 * h2 + c2, lo, hi) for the affine sources.

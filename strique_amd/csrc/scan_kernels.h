@@ -65,8 +65,9 @@ static __device__ inline int geometry_gate(const ReadGeom& g)
     return (g.prefix_begin < g.suffix_end && g.score_prefix > 0.0 && g.score_suffix > 0.0) ? 1 : 0;
 }
 
-// the Viterbi task of a window [begin, end) of a read's filtered signal (an empty task when `open` is 0)
-static __device__ inline VitTask window_task(int open, int64_t begin, int64_t end, const ReadCond& rc, const VitModel* model, const void* flt, int is_f64, const PoreStats& ps)
+// the Viterbi task of a window [begin, end) of a read's filtered signal (an empty task when `open` is 0); the host writes the windows
+// of the motif pass with it
+static __host__ __device__ inline VitTask window_task(int open, int64_t begin, int64_t end, const ReadCond& rc, const VitModel* model, const void* flt, int is_f64, const PoreStats& ps)
 {
     VitTask vt = {};
     vt.model = model;

@@ -16,6 +16,7 @@
 #include "posterior_kernels.h"
 #include "mod_llr_kernels.h"
 #include "variant_kernels.h"
+#include "motif_kernels.h"
 #include "screen_kernels.h"
 #include "strq_opt.h"
 
@@ -118,6 +119,9 @@ struct HostModel {
     DevBuf var_blob;
     const VarModel* var_dev = nullptr;
     int32_t var_mode = -1, var_nb = 0;
+    // motif track (motif_kernels.h): the edge image of a loop model, built on first use
+    DevBuf motif_blob;
+    const MotifModel* motif_dev = nullptr;
     // tract decodes (strq_model_set_tracts): the per-state increments behind VitModel::tract_inc
     DevBuf tract_blob;
     int32_t n_tracts = 0;
@@ -196,6 +200,9 @@ int viterbi_launch_status(int vrc);
 int forward_model(strq_ctx* c, HostModel* hm);
 // ... and its transposed image (HostModel::post_dev) behind it, for the backward half of the state posteriors
 int posterior_model(strq_ctx* c, HostModel* hm);
+// the edge image of a loop model for the motif track (HostModel::motif_dev), built if it is not there; STRQ_ERR_UNSUPPORTED (c->err says
+// why) for a model that is no loop model (strq_motif_api.hip)
+int motif_model(strq_ctx* c, HostModel* hm);
 // Unit positions of the tracts of decoded windows (strq_set_tract_positions, strq_viterbi_tract_positions; strq_detect_api.hip): every
 // window once more with back-pointers, traced back and scanned (tract_scan_kernel), in pieces of at most STRQ_TRACT_POS_WS_BYTES of
 // back-pointers.  task: the window as its count decode had it (bp is set here); n[j]: the visits of tract j that decode found; base:

@@ -86,6 +86,7 @@ struct Target {
     // and per group the columns, the site model and what the records report (flank as configured, pos, n_sites)
     struct FlankMod { int model_id = -1, len = 0; std::shared_ptr<DevBuf> col; std::vector<FlankGroupRange> range; std::vector<int> site; std::vector<int32_t> info; };
     FlankMod fmod[2];
+    int n_motifs = 0, motif_loop[MOTIF_MAX_CAND] = {-1, -1, -1, -1}, motif_flanked[MOTIF_MAX_CAND] = {-1, -1, -1, -1}, motif_bias[MOTIF_MAX_CAND] = {0, 0, 0, 0};      // strq_target_set_motifs
     bool has_fmod() const { return mod_model_id >= 0 && fmod[0].model_id >= 0 && fmod[1].model_id >= 0; }
 };
 
@@ -133,7 +134,8 @@ struct DetectState {
     DevBuf conf_task;                    // forward pass (run_conf_pass): tasks, model images, c0, results, order
     DevBuf fmod_ws, fmod_bp;             // flank methylation calls (run_flank_mod_pass): tasks, stretches and paths of a piece; its back-pointers
     DevBuf tract_ws, tract_task;         // tract pass (run_tract_pass): geometry and conditioning rows of a sub-batch; tasks, results, their reads and models
-    DevBuf tpos_task, tpos_bp, tpos_path, tpos_pool;      // tract positions (tract_positions): tasks and results of a piece, its back-pointers, state paths, positions
+    DevBuf motif_ws, motif_rows, motif_task;              // motif pass (run_motif_pass): windows, tasks and results of the track; rows and tasks of the majority decodes
+    DevBuf tpos_task, tpos_bp, tpos_path, tpos_pool;     // tract positions (tract_positions): tasks and results of a piece, its back-pointers, state paths, positions
     DevBuf sst_task, sst_bp, sst_path, sst_out;           // state statistics (state_stats): tasks and results of a piece, its back-pointers, state paths, rows
     DevBuf post_task, post_ws, post_out;                  // state posteriors (state_posteriors): tasks and results of a piece, its stored forward vectors, rows
     DevBuf anch_ws, anch_task;           // anchored pass (run_anchored_pass): geometry, conditioning rows and kinds of a sub-batch; tasks, results, their reads and models
@@ -1453,6 +1455,128 @@ static int run_tract_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
     return pass_stop(c, pass_ev(d), d->stats[PASS_TPOS]);
 }
 
+// The motif track of the reads of one sub-batch (strq_set_motifs; strique_amd/motifs.py states the rule): every read whose gate passed,
+// that was conditioned, with prefix_end < suffix_begin and whose target has candidates.  The geometry and the conditioning constants are
+// on the host (the slot's pinned block), so the stretches -- [prefix_end, suffix_begin) on the slot's filtered signal -- are written
+// there; motif_track_kernel scores their segments, motif_reduce_kernel sums them up, one read-back.  Then the reads whose majority is
+// not candidate 0 are decoded with the flanked model of the majority unit as the tract pass decodes its windows: tract_task_kernel
+// on [prefix_begin, suffix_end), a count launch per kernel instance in use.  Runs on the context's stream when the rows are taken.
+static int run_motif_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
+{
+    Batch& B = d->batch;
+    hipStream_t st = c->stream;
+    const int64_t r0 = sl.r0; const int nr = sl.nr;
+    if (nr <= 0 || sl.scan) return STRQ_OK;
+    const DetectState::Slot::Pinned h = sl.host();
+    const int S = sl.ex.motif_segment, run = motif_run_segments(S);
+    std::vector<int> who; std::vector<MotifWindow> wv; std::vector<MotifTask> tv; std::vector<size_t> seg_at, v_at;
+    size_t total_seg = 0, total_v = 0;
+    for (int i = 0; i < nr; ++i) {
+        const Target& t = target_of(d, r0 + i);
+        const ReadGeom& g = h.geom[i]; const ReadCond& rc = h.rc[i];
+        if (t.n_motifs < 2 || !g.gate || rc.status != COND_OK || !(g.prefix_end >= 0 && g.prefix_end < g.suffix_begin && g.suffix_begin <= (int64_t)rc.n)) continue;
+        MotifWindow w; std::memset(&w, 0, sizeof(w));
+        w.obs = window_task(1, g.prefix_end, g.suffix_begin, rc, nullptr, sl.flt_base, B.dtype, d->ps);
+        w.n_cand = t.n_motifs; w.segment = S; w.n_seg = w.obs.T / S > 1 ? w.obs.T / S : 1;
+        for (int j = 0; j < t.n_motifs; ++j) {
+            const HostModel* lm = t.motif_loop[j] >= 0 && t.motif_loop[j] < (int)c->models.size() ? c->models[t.motif_loop[j]] : nullptr;
+            if (!lm || !lm->motif_dev) { c->err = "motifs: loop model without an edge image (strq_target_set_motifs builds them)"; return STRQ_ERR_DEVICE; }
+            w.model[j] = lm->motif_dev;
+        }
+        for (int64_t s = 0; s < w.n_seg; s += run) {
+            MotifTask k; k.window = (int32_t)who.size(); k.seg_first = s; k.seg_count = (int32_t)(w.n_seg - s < run ? w.n_seg - s : run);
+            tv.push_back(k);
+        }
+        who.push_back(i); wv.push_back(w); seg_at.push_back(total_seg); v_at.push_back(total_v);
+        total_seg += (size_t)w.n_seg; total_v += (size_t)w.n_seg * (size_t)w.n_cand;
+    }
+    const int m = (int)who.size();
+    if (!m) return STRQ_OK;
+    if (const int rc = pass_start(c, pass_ev(d))) return rc;
+    Carve lay;
+    const size_t o_V = lay.add<double>(total_v), o_win = lay.add<int32_t>(total_seg), o_won = lay.add<int64_t>((size_t)m * MOTIF_MAX_CAND), o_maj = lay.add<int32_t>((size_t)m),
+                 o_w = lay.add<MotifWindow>((size_t)m), o_t = lay.add<MotifTask>(tv.size());
+    STRQ_HIP(c, d->motif_ws.reserve(lay.total() + 64));
+    void* ws = d->motif_ws.p;
+    double* d_V = Carve::at<double>(ws, o_V); int32_t* d_win = Carve::at<int32_t>(ws, o_win); int64_t* d_won = Carve::at<int64_t>(ws, o_won);
+    int32_t* d_maj = Carve::at<int32_t>(ws, o_maj); MotifWindow* d_w = Carve::at<MotifWindow>(ws, o_w); MotifTask* d_t = Carve::at<MotifTask>(ws, o_t);
+    for (int k = 0; k < m; ++k) {
+        MotifWindow& w = wv[(size_t)k];
+        w.V = d_V + v_at[(size_t)k]; w.winner = d_win + seg_at[(size_t)k]; w.obs_won = d_won + (size_t)k * MOTIF_MAX_CAND; w.majority = d_maj + k;
+    }
+    STRQ_HIP(c, hipMemcpyAsync(d_w, wv.data(), (size_t)m * sizeof(MotifWindow), hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, hipMemcpyAsync(d_t, tv.data(), tv.size() * sizeof(MotifTask), hipMemcpyHostToDevice, st));
+    if (launch_motif_track(st, d_w, m, d_t, (int64_t)tv.size(), c->n_cu)) { c->err = "motifs: launch failed"; return STRQ_ERR_DEVICE; }
+    d->stat(PASS_MOTIFS, MOTIF_LAUNCHES) += 2;
+    std::vector<double> hV(total_v); std::vector<int32_t> hwin(total_seg), hmaj((size_t)m); std::vector<int64_t> hwon((size_t)m * MOTIF_MAX_CAND);
+    STRQ_HIP(c, hipMemcpyAsync(hV.data(), d_V, total_v * 8, hipMemcpyDeviceToHost, st));
+    STRQ_HIP(c, hipMemcpyAsync(hwin.data(), d_win, total_seg * 4, hipMemcpyDeviceToHost, st));
+    STRQ_HIP(c, hipMemcpyAsync(hwon.data(), d_won, (size_t)m * MOTIF_MAX_CAND * 8, hipMemcpyDeviceToHost, st));
+    STRQ_HIP(c, hipMemcpyAsync(hmaj.data(), d_maj, (size_t)m * 4, hipMemcpyDeviceToHost, st));
+    STRQ_HIP(c, hipStreamSynchronize(st));
+    std::vector<int> other;          // reads whose array is not made of the configured unit
+    for (int k = 0; k < m; ++k) {
+        const int i = who[(size_t)k];
+        const size_t r = (size_t)(r0 + i);
+        const MotifWindow& w = wv[(size_t)k];
+        strq_motifs o = strq_motifs();
+        o.n_cand = w.n_cand; o.n_seg = w.n_seg; o.majority = hmaj[(size_t)k]; o.begin = h.geom[i].prefix_end; o.end = h.geom[i].suffix_begin;
+        for (int j = 0; j < MOTIF_MAX_CAND; ++j) o.obs_won[j] = hwon[(size_t)k * MOTIF_MAX_CAND + (size_t)j];
+        if (o.majority < 0 || o.majority >= w.n_cand) { c->err = "motifs: the reduction returned a majority beyond the candidates"; return STRQ_ERR_DEVICE; }
+        o.decode_status = 1;
+        if (o.majority == 0) {
+            if (h.vres[sl.vit_slot[i]].status == 0) { o.decode_status = 0; o.count_m = B.results[r].count; o.log_p_m = B.results[r].log_p; }
+        } else other.push_back(k);
+        B.motifs[r] = o;
+        B.motif_V[r].assign(hV.begin() + (ptrdiff_t)v_at[(size_t)k], hV.begin() + (ptrdiff_t)(v_at[(size_t)k] + (size_t)w.n_seg * (size_t)w.n_cand));
+        B.motif_win[r].assign(hwin.begin() + (ptrdiff_t)seg_at[(size_t)k], hwin.begin() + (ptrdiff_t)(seg_at[(size_t)k] + (size_t)w.n_seg));
+        d->stat(PASS_MOTIFS, MOTIF_READS) += 1; d->stat(PASS_MOTIFS, MOTIF_SEGMENTS) += (double)w.n_seg;
+    }
+    if (other.empty()) return pass_stop(c, pass_ev(d), d->stats[PASS_MOTIFS]);
+    // the count decode under the majority unit
+    std::vector<int> who2;
+    for (int k : other) who2.push_back(who[(size_t)k]);
+    const int m2 = (int)who2.size();
+    DecodeOrder<VitModel> D;
+    if (!decode_order(who2, [&](int i, GroupItem& it, const VitModel*& vm) {
+            const Target& t = target_of(d, r0 + i);
+            const int id = t.motif_flanked[B.motifs[(size_t)(r0 + i)].majority];
+            HostModel* hm = id >= 0 && id < (int)c->models.size() ? c->models[id] : nullptr;
+            const int shape = hm ? vit_shape_for(hm->h, VIT_COUNT) : -1;
+            if (shape < 0) return false;
+            it = {0, shape, hm->h.n_cells}; vm = hm->dev;
+            return true;
+        }, D)) { c->err = "motifs: a candidate's flanked model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
+    SlotRows rows;
+    if (const int rc = upload_slot_rows(c, sl, d->motif_rows, rows)) return rc;
+    Carve tl;
+    const size_t o_vt = tl.add<VitTask>((size_t)m2), o_vr = tl.add<VitResult>((size_t)m2), o_md = tl.add<const VitModel*>((size_t)m2), o_rd = tl.add<int32_t>((size_t)m2),
+                 o_order = tl.add<int>((size_t)m2);
+    STRQ_HIP(c, d->motif_task.reserve(tl.total() + 64));
+    void* tb = d->motif_task.p;
+    VitTask* d_vt = Carve::at<VitTask>(tb, o_vt); VitResult* d_vr = Carve::at<VitResult>(tb, o_vr);
+    const VitModel** d_md = Carve::at<const VitModel*>(tb, o_md); int32_t* d_rd = Carve::at<int32_t>(tb, o_rd); int* d_order = Carve::at<int>(tb, o_order);
+    STRQ_HIP(c, hipMemcpyAsync(d_rd, D.read_of.data(), (size_t)m2 * 4, hipMemcpyHostToDevice, st));
+    STRQ_HIP(c, hipMemcpyAsync(d_md, D.model.data(), (size_t)m2 * 8, hipMemcpyHostToDevice, st));
+    TractTaskArgs ta;
+    ta.geom = rows.geom; ta.rc = rows.rc; ta.read = d_rd; ta.model = d_md; ta.flt = sl.flt_base; ta.is_f64 = B.dtype; ta.ps = d->ps;
+    ta.vit = d_vt; ta.n_tasks = m2; ta.n_reads = nr;
+    if (launch_tract_tasks(st, ta)) { c->err = "motifs: task launch failed"; return STRQ_ERR_DEVICE; }
+    d->stat(PASS_MOTIFS, MOTIF_LAUNCHES) += 1;
+    if (const int grc = launch_groups(c, st, D.G.groups, {d_vt, d_vr, d_order, {VIT_COUNT}, "motifs: ", false, &d->stat(PASS_MOTIFS, MOTIF_LAUNCHES)})) return grc;
+    std::vector<VitResult> vr((size_t)m2);
+    STRQ_HIP(c, hipMemcpyAsync(vr.data(), d_vr, (size_t)m2 * sizeof(VitResult), hipMemcpyDeviceToHost, st));
+    if (const int rc = pass_stop(c, pass_ev(d), d->stats[PASS_MOTIFS])) return rc;
+    for (int at = 0; at < m2; ++at) {
+        const int i = D.read_of[(size_t)at];
+        strq_motifs& o = B.motifs[(size_t)(r0 + i)];
+        const VitResult& v = vr[(size_t)at];
+        if (v.status == 0) { o.decode_status = 0; o.count_m = (int32_t)v.counted + target_of(d, r0 + i).motif_bias[o.majority]; o.log_p_m = v.logp; }
+        d->stat(PASS_MOTIFS, MOTIF_DECODES) += 1;
+    }
+    return STRQ_OK;
+}
+
 // Methylation calls for the CpG groups of the flanks of one sub-batch (strq_set_flank_mod; strique_amd/flank_mod.py states the rule):
 // every read whose gate passed, that could be conditioned and whose target has a modification model and the flank models.  Per flank
 // with begin < end -- the prefix on the raw samples [whole prefix begin, prefix_end), the suffix on [suffix_begin, whole suffix end) --
@@ -1967,6 +2091,7 @@ static int take_rows(strq_ctx* c, DetectState* d, DetectState::Slot& sl, bool un
     }
     if (sl.ex.tracts) { const int trc = run_tract_pass(c, d, sl); if (trc) return trc; }
     if (sl.ex.fmod) { const int frc = run_flank_mod_pass(c, d, sl); if (frc) return frc; }
+    if (sl.ex.motifs) { const int mrc = run_motif_pass(c, d, sl); if (mrc) return mrc; }
     return sl.ex.anch ? run_anchored_pass(c, d, sl) : STRQ_OK;
 }
 
@@ -2620,6 +2745,7 @@ int run_range(strq_ctx* c, DetectState* d, int64_t first, int64_t last)
         B.size_tpos();
     }
     if (d->extras.fmod) B.size_fmod();
+    if (d->extras.motifs) B.size_motifs();
     if (d->extras.sstats) {
         // nothing is launched for a call whose flanked models cannot be traced back
         for (int64_t r = first; r < last; ++r) {
@@ -3086,6 +3212,65 @@ int strq_last_tracts(strq_ctx* c, double* out4)
 {
     STRQ_ENTER(c);
     return last_pass(c, PASS_TRACTS, out4);
+}
+
+int strq_target_set_motifs(strq_ctx* c, int32_t target_id, int32_t n, const int32_t* loop_model_ids, const int32_t* flanked_model_ids, const int32_t* bias)
+{
+    STRQ_ENTER(c);
+    DetectState* d = dstate(c);
+    if (target_id < 0 || target_id >= (int32_t)d->targets.size() || (n != 0 && (n < 2 || n > MOTIF_MAX_CAND || !loop_model_ids || !flanked_model_ids || !bias))) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    for (int32_t j = 0; j < n; ++j) {
+        const int32_t l = loop_model_ids[j], f = flanked_model_ids[j];
+        if (l < 0 || l >= (int32_t)c->models.size() || !c->models[l] || (j > 0 && (f < 0 || f >= (int32_t)c->models.size() || !c->models[f]))) { c->err = "bad argument (no such model)"; return STRQ_ERR_ARG; }
+        if (const int rc = motif_model(c, c->models[l])) return rc;
+        if (j > 0 && vit_shape_for(c->models[f]->h, VIT_COUNT) < 0) { c->err = "motifs: a candidate's flanked model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
+    }
+    if (const int rc = drain(c, d)) return rc;          // a sub-batch in flight is taken with the target it ran with
+    Target& t = d->targets[target_id];
+    t.n_motifs = n;
+    for (int j = 0; j < MOTIF_MAX_CAND; ++j) {
+        t.motif_loop[j] = j < n ? loop_model_ids[j] : -1; t.motif_flanked[j] = (j < n && j > 0) ? flanked_model_ids[j] : -1; t.motif_bias[j] = j < n ? bias[j] : 0;
+    }
+    return STRQ_OK;
+}
+
+int strq_set_motifs(strq_ctx* c, int32_t on, int32_t segment)
+{
+    STRQ_ENTER(c);
+    if (on == 1 && (segment < MOTIF_SEG_MIN || segment > MOTIF_SEG_MAX)) {
+        c->err = "motifs: the segment length must lie between " + std::to_string(MOTIF_SEG_MIN) + " and " + std::to_string(MOTIF_SEG_MAX); return STRQ_ERR_ARG;
+    }
+    if (const int rc = set_extra(c, on, PASS_MOTIFS)) return rc;
+    dstate(c)->extras.motif_segment = on ? segment : 0;
+    return STRQ_OK;
+}
+
+int strq_batch_fetch_motifs(strq_ctx* c, strq_motifs* out, int64_t n, int64_t* off, double* V, int32_t* winners, int64_t seg_cap)
+{
+    STRQ_ENTER(c);
+    DetectState* d = dstate(c);
+    if (const int rc = fetch_begin(c, d, PASS_MOTIFS)) return rc;
+    const Batch& B = d->batch;
+    if (n != B.n_reads || !off || (n > 0 && !out) || B.motifs.size() != (size_t)n || (V == nullptr) != (winners == nullptr) || seg_cap < 0) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    if (n) std::memcpy(out, B.motifs.data(), (size_t)n * sizeof(strq_motifs));
+    if (pack_ragged(n, off, V != nullptr, seg_cap, [&](int64_t i) { return (int64_t)B.motif_win[(size_t)i].size(); },
+                    [&](int64_t i, int64_t pos) {
+                        const std::vector<int32_t>& w = B.motif_win[(size_t)i]; const std::vector<double>& v = B.motif_V[(size_t)i];
+                        const int K = B.motifs[(size_t)i].n_cand;
+                        for (size_t s = 0; s < w.size(); ++s) {
+                            winners[pos + (int64_t)s] = w[s];
+                            for (int j = 0; j < MOTIF_MAX_CAND; ++j) V[MOTIF_MAX_CAND * (pos + (int64_t)s) + j] = j < K ? v[s * (size_t)K + (size_t)j] : 0.0;
+                        }
+                    }) < n) { c->err = "segment pool too small"; return STRQ_ERR_ARG; }
+    return STRQ_OK;
+}
+
+int strq_last_motifs(strq_ctx* c, double* out5)
+{
+    STRQ_ENTER(c);
+    if (const int rc = last_pass(c, PASS_MOTIFS, out5)) return rc;
+    out5[4] = dstate(c)->stats[PASS_MOTIFS].v[MOTIF_DECODES];
+    return STRQ_OK;
 }
 
 int strq_set_tract_positions(strq_ctx* c, int32_t on)

@@ -498,6 +498,26 @@ class Context(object):
                                                        _ptr(w), _ptr(wx), _ptr(wxx)))
         return ll[:n], status[:n], w[:n], wx[:n], wxx[:n]
 
+    def motif_track(self, model_ids, xs, segment=256):
+        """strq_motif_track: model_ids the loop models of the K = 2 to 4 candidates (motifs.loop_arrays through model_create), xs a
+        list of float64 arrays of at least one observation (NaN: missing).  Returns per window (V (n_seg, K) float64, winners
+        (n_seg,) int32, obs_won (K,) int64, majority): strique_amd/motifs.py states the rule."""
+        n, K = len(xs), len(model_ids)
+        if any(len(s) < 1 for s in xs):
+            raise ValueError("motif_track: a window needs at least one observation")
+        x, off = _offsets(xs, np.float64)
+        cap = sum(max(1, len(s) // max(1, int(segment))) for s in xs)
+        V = np.zeros((max(1, cap), max(1, K))); win = np.zeros(max(1, cap), np.int32)
+        n_seg = np.zeros(max(1, n), np.int64); won = np.zeros((max(1, n), 4), np.int64); maj = np.zeros(max(1, n), np.int32)
+        self._check(self._lib.strq_motif_track(self._h, ctypes.c_int32(K), _ptr(_c(model_ids, np.int32)), ctypes.c_int32(segment), ctypes.c_int64(n),
+                                               _ptr(x), _ptr(off), ctypes.c_int64(cap), _ptr(V), _ptr(win), _ptr(n_seg), _ptr(won), _ptr(maj)))
+        out, at = [], 0
+        for i in range(n):
+            k = int(n_seg[i])
+            out.append((V[at:at + k].copy(), win[at:at + k].copy(), won[i, :K].copy(), int(maj[i])))
+            at += k
+        return out
+
     def debug_tract_shape(self):
         """strq_debug_tract_shape: the kernel shape id of this context's last tract launch (-1: none yet)."""
         shape = ctypes.c_int32(-1)
@@ -685,6 +705,40 @@ class Context(object):
     def last_tracts(self):
         """The tract pass of the last run call (strq_last_tracts): {'ms', 'windows' (decoded), 'launches', 'failed' (status 2 or 3)}."""
         return self._last("tracts", ("ms", "windows", "launches", "failed"))
+
+    def target_set_motifs(self, target_id, loop_model_ids=(), flanked_model_ids=(), bias=()):
+        """strq_target_set_motifs: the candidates of a target -- per candidate its loop model (motifs.loop_arrays), the flanked model
+        of that unit and its count bias; candidate 0 is the unit of the target's own model (its flanked id is not read).  No ids:
+        the candidates are taken away."""
+        n = len(loop_model_ids)
+        if len(flanked_model_ids) != n or len(bias) != n:
+            raise ValueError("target_set_motifs: one loop model, one flanked model and one bias per candidate")
+        a, b, c = (np.zeros(4, np.int32) for _ in range(3))
+        a[:n] = loop_model_ids; b[:n] = flanked_model_ids; c[:n] = bias
+        self._check(self._lib.strq_target_set_motifs(self._h, ctypes.c_int32(target_id), ctypes.c_int32(n), _ptr(a), _ptr(b), _ptr(c)))
+
+    def set_motifs(self, on, segment=256):
+        """strq_set_motifs: later run calls also score the stretch between the flanks of every read whose target has candidates,
+        in segments of `segment` observations (batch_fetch_motifs; strique_amd/motifs.py states the rule)."""
+        self._check(self._lib.strq_set_motifs(self._h, ctypes.c_int32(1 if on else 0), ctypes.c_int32(segment if on else 0)))
+
+    def batch_fetch_motifs(self):
+        """The motif track of the last batch (strq_batch_fetch_motifs): (records, V, winners) -- a structured array of MOTIFS_DTYPE
+        with one element per read, and per read the scores (n_seg, n_cand) float64 and the winners (n_seg,) int32 (empty for a read
+        that was not scored)."""
+        n = getattr(self, '_n_batch', 0)
+        rec = np.zeros(max(1, n), dtype=MOTIFS_DTYPE); off = np.zeros(n + 1, np.int64)
+        self._check(self._lib.strq_batch_fetch_motifs(self._h, _ptr(rec), ctypes.c_int64(n), _ptr(off), None, None, ctypes.c_int64(0)))
+        m = max(1, int(off[-1]))
+        V = np.zeros((m, 4)); win = np.zeros(m, np.int32)
+        self._check(self._lib.strq_batch_fetch_motifs(self._h, _ptr(rec), ctypes.c_int64(n), _ptr(off), _ptr(V), _ptr(win), ctypes.c_int64(m)))
+        rec = rec[:n]
+        return (rec, [V[off[i]:off[i + 1], :int(rec[i]['n_cand'])].copy() for i in range(n)], [win[off[i]:off[i + 1]].copy() for i in range(n)])
+
+    def last_motifs(self):
+        """The motif pass of the last run call (strq_last_motifs): {'ms', 'reads' (scored), 'segments', 'launches', 'decodes' (of
+        reads whose majority is not the configured unit)}."""
+        return self._last("motifs", ("ms", "reads", "segments", "launches", "decodes"))
 
     def set_tract_positions(self, on):
         """strq_set_tract_positions: later run calls with set_tracts on also trace every tract window of status 0 back
@@ -1106,5 +1160,8 @@ RENORM_DTYPE = np.dtype([("applied", np.int32), ("pad_", np.int32), ("fit", RENO
 FLANK_MOD_DTYPE = np.dtype([("flank", np.int32), ("pos", np.int32), ("n_sites", np.int32), ("n_columns", np.int32), ("status", np.int32), ("pad_", np.int32),
                             ("begin", np.int64), ("end", np.int64), ("v_base", np.float64), ("v_mod", np.float64)], align=True)
 TRACTS_DTYPE = np.dtype([("status", np.int32), ("n_tracts", np.int32), ("count", np.int32, (3,)), ("pad_", np.int32), ("log_p", np.float64)], align=True)
+MOTIFS_DTYPE = np.dtype([("status", np.int32), ("n_cand", np.int32), ("n_seg", np.int64), ("majority", np.int32), ("decode_status", np.int32),
+                         ("begin", np.int64), ("end", np.int64), ("obs_won", np.int64, (4,)), ("count_m", np.int32), ("pad_", np.int32),
+                         ("log_p_m", np.float64)], align=True)
 ANCHORED_DTYPE = np.dtype([("kind", np.int32), ("status", np.int32), ("count", np.int32), ("pad_", np.int32), ("log_p", np.float64),
                            ("begin", np.int64), ("end", np.int64), ("free_samples", np.int64)], align=True)
