@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <map>
 #include <string>
 #include <utility>
@@ -27,6 +28,36 @@ struct Carve {
     size_t total() const { return end; }
     template <class T> static T* at(void* base, size_t offset) { return base ? reinterpret_cast<T*>(static_cast<char*>(base) + offset) : nullptr; }
 };
+
+// The piece rule of the passes that decode windows once more into a workspace (records, back-pointers, stored forward vectors), said
+// once.  The windows, in their order, are cut into pieces: a piece takes windows while the sum of their sizes stays within the budget
+// and, with `max_windows`, while it holds fewer than that many.  A window that alone exceeds the budget is oversize, and a pass names
+// what becomes of it: ALONE, it stays in its place as a piece of its own, over the budget (unit pass, flank-mod pass); LEFT_OUT, it is
+// in no piece (tract positions, state statistics: status 2); IN_FRONT, it is carried ahead of all others with no bytes (state
+// posteriors: status 2, the forward half still runs).  The sizes are the caller's: whoever places windows on 16-byte boundaries
+// passes rounded sizes (bp_window_bytes), and the bytes of a piece are the sum of what was passed.
+enum Oversize { OVERSIZE_ALONE, OVERSIZE_LEFT_OUT, OVERSIZE_IN_FRONT };
+struct Piece { size_t first, last, bytes; };          // the windows order[first .. last) and what they take together
+// order: the windows the pieces hold, as indices into the sizes; bytes: per position of `order`, what the window takes (0 for one carried
+// in front); oversize: the windows left out or carried in front, ascending
+struct PiecePlan { std::vector<int32_t> order; std::vector<size_t> bytes; std::vector<Piece> pieces; std::vector<int32_t> oversize; };
+inline PiecePlan plan_pieces(const std::vector<size_t>& sizes, size_t budget, Oversize policy, size_t max_windows = 0)
+{
+    PiecePlan P;
+    for (size_t i = 0; i < sizes.size(); ++i) if (policy != OVERSIZE_ALONE && sizes[i] > budget) P.oversize.push_back((int32_t)i);
+    if (policy == OVERSIZE_IN_FRONT) { P.order = P.oversize; P.bytes.assign(P.oversize.size(), 0); }
+    for (size_t i = 0; i < sizes.size(); ++i) if (policy == OVERSIZE_ALONE || sizes[i] <= budget) { P.order.push_back((int32_t)i); P.bytes.push_back(sizes[i]); }
+    for (size_t c0 = 0; c0 < P.order.size();) {
+        size_t c1 = c0, sum = 0;
+        while (c1 < P.order.size() && (!max_windows || c1 - c0 < max_windows) && (c1 == c0 || sum + P.bytes[c1] <= budget)) sum += P.bytes[c1++];
+        P.pieces.push_back({c0, c1, sum}); c0 = c1;
+    }
+    return P;
+}
+// the budget of a pass: 8 GiB, or what its option says where that is a number above 0 (callers pass strq::opt("STRQ_..._WS_BYTES"))
+inline size_t ws_budget(const char* option_value) { const long long v = option_value ? atoll(option_value) : 0; return v > 0 ? (size_t)v : (size_t)8 << 30; }
+// back-pointers of one window: uint16 per (time step, state), T + 1 steps; every window starts on a 16-byte boundary
+inline size_t bp_window_bytes(int64_t T, int n_states) { return ((size_t)(T + 1) * (size_t)n_states * 2 + 15) & ~(size_t)15; }
 
 // The switches of the optional passes around the count decode (PASSES below lists them), and the thresholds anchored counting and renorm
 // come with.  DetectState holds what the next run call uses, a slot what its sub-batch was launched with, Batch what the last run call

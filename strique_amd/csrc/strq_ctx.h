@@ -204,16 +204,16 @@ int posterior_model(strq_ctx* c, HostModel* hm);
 // why) for a model that is no loop model (strq_motif_api.hip)
 int motif_model(strq_ctx* c, HostModel* hm);
 // Unit positions of the tracts of decoded windows (strq_set_tract_positions, strq_viterbi_tract_positions; strq_detect_api.hip): every
-// window once more with back-pointers, traced back and scanned (tract_scan_kernel), in pieces of at most STRQ_TRACT_POS_WS_BYTES of
-// back-pointers.  task: the window as its count decode had it (bp is set here); n[j]: the visits of tract j that decode found; base:
+// window once more with back-pointers, traced back and scanned (tract_scan_kernel).  Pieces: the rule of detect_plan.h on the windows'
+// back-pointers against STRQ_TRACT_POS_WS_BYTES, an oversize window left out.  task: the window as its count decode had it (bp is set here); n[j]: the visits of tract j that decode found; base:
 // what position 0 of the window is reported as.  status[i]: 0 positions in pos[3 i + j] (model order), 2 the window's back-pointers
 // alone exceed the budget (not traced).  stats (or null): windows traced, kernels launched, peak back-pointer bytes of a piece.
 struct TractPosWindow { VitTask task; const HostModel* hm; int64_t base; int64_t n[3]; };
 struct TractPosOut { std::vector<int32_t> status; std::vector<std::vector<int64_t>> pos; };
 int tract_positions(strq_ctx* c, const std::vector<TractPosWindow>& w, TractPosOut& out, double* stats);
 // State statistics of decoded windows (strq_set_state_stats, strq_viterbi_state_stats; strq_detect_api.hip, the rule: strique_amd/
-// state_stats.py): every window once more with back-pointers, traced back and summed per emitting state (state_stats_kernel), in pieces
-// of at most STRQ_STATE_STATS_WS_BYTES of back-pointers.  task: the window as its count decode had it (bp is set here); logp, counted:
+// state_stats.py): every window once more with back-pointers, traced back and summed per emitting state (state_stats_kernel).  Pieces:
+// the rule of detect_plan.h on the windows' back-pointers against STRQ_STATE_STATS_WS_BYTES, an oversize window left out.  task: the window as its count decode had it (bp is set here); logp, counted:
 // what that decode found -- a back-pointer decode with other bits fails the call (STRQ_ERR_DEVICE).  status[i]: 0 the rows n / sum /
 // sumsq[i] hold silent_start entries, 2 the window's back-pointers alone exceed the budget (no rows).  stats (or null): windows, kernels
 // launched, peak back-pointer bytes of a piece.
@@ -221,8 +221,8 @@ struct StateStatsWindow { VitTask task; const HostModel* hm; double logp; int64_
 struct StateStatsOut { std::vector<int32_t> status; std::vector<std::vector<int64_t>> n; std::vector<std::vector<double>> sum, sumsq; };
 int state_stats(strq_ctx* c, const std::vector<StateStatsWindow>& w, StateStatsOut& out, double* stats);
 // State posteriors of windows (strq_set_state_posteriors, strq_forward_state_stats; strq_detect_api.hip, the rule: strique_amd/
-// state_posteriors.py): forward-backward over every window (posterior_kernels.h), in pieces of at most STRQ_STATE_POST_WS_BYTES of stored
-// forward vectors.  task: the window (bp unused).  fwd[i]: the forward half's result of every window (fwd_finish gives the likelihood);
+// state_posteriors.py): forward-backward over every window (posterior_kernels.h).  Pieces: the rule of detect_plan.h on the windows'
+// stored forward vectors against STRQ_STATE_POST_WS_BYTES, at most 8192 windows each, an oversize window carried in front.  task: the window (bp unused).  fwd[i]: the forward half's result of every window (fwd_finish gives the likelihood);
 // status[i]: 0 the rows w / wx / wxx[i] hold silent_start entries, 1 no path (no rows), 2 the window's stored vectors alone exceed the
 // budget (no rows; fwd[i] is valid).  stats (or null): windows, kernels launched, peak workspace bytes of a piece.
 struct StatePostWindow { VitTask task; HostModel* hm; };

@@ -850,7 +850,8 @@ static int run_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, Dual
 // windows the count / MARK launch decoded, once more with the same tasks (same windows, same affine source) -- in UNIT mode (unit
 // records, VIT_UNIT_T_MAX) where the model and the window allow it, else (STRQ_UNITS_BACKPOINTERS=1: always) with back-pointers and a
 // traceback.  Runs on the context's stream when the rows of the sub-batch are taken: the slot's filtered signal and tasks are live
-// until the slot is used again, which harvests it first.  Pieces of at most STRQ_UNITS_WS_BYTES (8 GiB) of records / back-pointers.
+// until the slot is used again, which harvests it first.  Pieces (detect_plan.h) of records / back-pointers against STRQ_UNITS_WS_BYTES,
+// an oversize window alone.  Two routes and two position kernels: it uses the plan, not the traced re-decode.
 static int run_unit_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, const Decoded& dec)
 {
     Batch& B = d->batch;
@@ -860,10 +861,8 @@ static int run_unit_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, con
     const std::vector<int>& who = dec.who; const std::vector<VitTask>& vt = dec.vt;
     if (const int rc = pass_start(c, pass_ev(d))) return rc;
     const bool force_bp = strq::opt("STRQ_UNITS_BACKPOINTERS") != nullptr;
-    size_t budget = (size_t)8 << 30;
-    if (const char* e = strq::opt("STRQ_UNITS_WS_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
-    struct W { int i; int shape; bool rec; size_t bytes; };
-    std::vector<W> ws;
+    struct W { int i; int shape; bool rec; };
+    std::vector<W> ws; std::vector<size_t> sizes;
     for (int i : who) {
         HostModel* hm = flank_model(c, d, r0 + i);
         const int64_t T = vt[(size_t)sl.vit_slot[i]].T;
@@ -872,12 +871,12 @@ static int run_unit_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, con
         if (!w.rec) w.shape = vit_shape_of(hm->h);
         if (w.shape < 0) { c->err = "unit pass: model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
         // unit records: two uint32 per observation; back-pointers: uint16 per (time step, state), and the state path
-        w.bytes = w.rec ? (size_t)T * 8 : (size_t)(T + 1) * (size_t)hm->h.n_states * 2;
+        sizes.push_back(w.rec ? (size_t)T * 8 : (size_t)(T + 1) * (size_t)hm->h.n_states * 2);
         ws.push_back(w);
     }
-    for (size_t c0 = 0; c0 < ws.size();) {
-        size_t c1 = c0, bytes = 0;
-        while (c1 < ws.size() && (c1 == c0 || bytes + ws[c1].bytes <= budget)) bytes += ws[c1++].bytes;
+    const PiecePlan plan = plan_pieces(sizes, ws_budget(strq::opt("STRQ_UNITS_WS_BYTES")), OVERSIZE_ALONE);
+    for (const Piece& pc : plan.pieces) {
+        const size_t c0 = pc.first, c1 = pc.last, bytes = pc.bytes;
         // this piece's windows grouped by (route, kernel shape): unit-record launches (route 0) first
         const int m = (int)(c1 - c0);
         std::vector<GroupItem> items((size_t)m);
@@ -909,7 +908,7 @@ static int run_unit_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, con
             HostModel* hm = flank_model(c, d, r0 + w.i);
             const VitResult& v0 = vres[sl.vit_slot[w.i]];
             VitTask t = vt[(size_t)sl.vit_slot[w.i]];
-            t.bp = reinterpret_cast<uint16_t*>(d->unit_ws.as<char>() + wo); wo += (w.bytes + 15) & ~(size_t)15;
+            t.bp = reinterpret_cast<uint16_t*>(d->unit_ws.as<char>() + wo); wo += (sizes[c0 + (size_t)G.order[(size_t)at]] + 15) & ~(size_t)15;
             if (wo > d->unit_ws.cap) { c->err = "unit pass: workspace"; return STRQ_ERR_NOMEM; }
             UnitTask u; std::memset(&u, 0, sizeof(u));
             u.rec = w.rec ? reinterpret_cast<const uint32_t*>(t.bp) : nullptr;
@@ -942,7 +941,6 @@ static int run_unit_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl, con
             B.unit_dec[(size_t)(r0 + i)] = 1;
         }
         d->stat(PASS_UNITS, UNIT_BYTES) = std::max(d->stat(PASS_UNITS, UNIT_BYTES), (double)bytes); d->stat(PASS_UNITS, UNIT_READS) += m; d->stat(PASS_UNITS, UNIT_POSITIONS) += (double)xo;
-        c0 = c1;
     }
     return pass_stop(c, pass_ev(d), d->stats[PASS_UNITS]);
 }
@@ -1028,200 +1026,173 @@ static int upload_slot_rows(strq_ctx* c, const DetectState::Slot& sl, DevBuf& bu
     return STRQ_OK;
 }
 
-// Unit positions of the tracts of decoded windows (strq_ctx.h states the interface; strique_amd/tracts.py the rule): the windows of a
-// piece grouped by kernel shape, decoded with back-pointers, traced back into a zeroed path buffer and scanned with one ballot per tract
-// (tract_scan_kernel).  One read-back and one wait per piece; the buffers are the detect state's own and exist only once this ran.
+// The traced re-decode of windows (tract positions, state statistics): every window (`task`, `hm` of a Window) once more with
+// back-pointers, traced back into a zeroed path buffer, then one kernel of the consumer over the paths.  The windows whose back-pointers
+// alone exceed the budget get status 2, the others go in pieces (detect_plan.h: OVERSIZE_LEFT_OUT); a piece's windows are grouped by
+// kernel shape, and its back-pointers, paths and the consumer's output lie in task order.  One set of uploads, one launch per shape
+// (two where it sorts), one traceback per shape, the consumer's kernel, one read-back and one wait per piece.  A consumer K has: name
+// and budget_option (the prefix of its messages, the option of its budget); bufs (the pass's buffers in the detect state); Task (its
+// kernel's task, zeroed for fill); refuses(hm): why it cannot take this model, or null; size_pool: a piece begins with these m windows,
+// the bytes of its output pool; fill: the task of window x at task position `at`, dev its path, result and bad flag on the device;
+// launch: its kernel over the piece, what failed or null; read_back: queues its copies to the host (the driver adds the bad flags and
+// waits); scatter: the output of window i at task position `at`, false where the decode disagrees with the count decode.
+// stats (or null): windows traced, kernels launched, peak back-pointer bytes of a piece.
+struct TraceBufs { DevBuf &task, &bp, &path, &pool; };
+struct TraceSlot { int32_t* path; VitResult* result; int32_t* bad; };
+template <class Window, class K>
+static int traced_redecode(strq_ctx* c, const std::vector<Window>& w, K& k, std::vector<int32_t>& status, double* stats)
+{
+    hipStream_t st = c->stream;
+    const std::string name = k.name;
+    status.assign(w.size(), 0);
+    std::vector<int> shape(w.size()); std::vector<size_t> sizes(w.size());
+    for (size_t i = 0; i < w.size(); ++i) {
+        const VitModel& h = w[i].hm->h; shape[i] = vit_shape_for(h, VIT_BACKPTR);
+        const char* why = (shape[i] < 0 || !vit_mode_ok(shape[i], VIT_BACKPTR)) ? "the model has no back-pointer decode" : k.refuses(*w[i].hm);
+        if (why) { c->err = name + why; return STRQ_ERR_UNSUPPORTED; }
+        sizes[i] = bp_window_bytes(w[i].task.T, h.n_states);
+    }
+    const PiecePlan plan = plan_pieces(sizes, ws_budget(strq::opt(k.budget_option)), OVERSIZE_LEFT_OUT);
+    for (int32_t i : plan.oversize) status[(size_t)i] = 2;
+    for (const Piece& pc : plan.pieces) {
+        const int m = (int)(pc.last - pc.first); const int32_t* wins = plan.order.data() + pc.first;
+        std::vector<GroupItem> items((size_t)m); size_t path_n = 0;
+        for (int j = 0; j < m; ++j) { const Window& x = w[(size_t)wins[j]]; items[(size_t)j] = {0, shape[(size_t)wins[j]], x.hm->h.n_cells}; path_n += (size_t)x.task.T; }
+        const Grouping G = group_items(items);
+        Carve lay;
+        const size_t o_vt = lay.add<VitTask>((size_t)m), o_vr = lay.add<VitResult>((size_t)m), o_paths = lay.add<int32_t*>((size_t)m),
+                     o_ts = lay.add<typename K::Task>((size_t)m), o_bad = lay.add<int32_t>((size_t)m), o_order = lay.add<int>((size_t)m);
+        STRQ_HIP(c, k.bufs.task.reserve(lay.total() + 64));
+        void* tb = k.bufs.task.p;
+        VitTask* d_vt = Carve::at<VitTask>(tb, o_vt); VitResult* d_vr = Carve::at<VitResult>(tb, o_vr); int32_t** d_paths = Carve::at<int32_t*>(tb, o_paths);
+        typename K::Task* d_ts = Carve::at<typename K::Task>(tb, o_ts); int32_t* d_bad = Carve::at<int32_t>(tb, o_bad); int* d_order = Carve::at<int>(tb, o_order);
+        STRQ_HIP(c, k.bufs.bp.reserve(pc.bytes)); STRQ_HIP(c, k.bufs.path.reserve(path_n * 4 + 64));
+        STRQ_HIP(c, k.bufs.pool.reserve(k.size_pool(w, wins, m)));
+        std::vector<VitTask> tv((size_t)m); std::vector<int32_t*> pv((size_t)m); std::vector<typename K::Task> sv((size_t)m);
+        size_t wo = 0, po = 0;
+        for (int at = 0; at < m; ++at) {          // in task order
+            const int32_t i = wins[G.order[(size_t)at]]; const Window& x = w[(size_t)i]; VitTask t = x.task;
+            t.bp = reinterpret_cast<uint16_t*>(k.bufs.bp.template as<char>() + wo); wo += sizes[(size_t)i];
+            if (wo > k.bufs.bp.cap) { c->err = name + "workspace"; return STRQ_ERR_NOMEM; }
+            pv[(size_t)at] = k.bufs.path.template as<int32_t>() + po; po += (size_t)t.T;
+            std::memset(&sv[(size_t)at], 0, sizeof(typename K::Task));
+            k.fill(at, x, TraceSlot{pv[(size_t)at], d_vr + at, d_bad + at}, sv[(size_t)at]);
+            tv[(size_t)at] = t;
+        }
+        STRQ_HIP(c, hipMemcpyAsync(d_vt, tv.data(), (size_t)m * sizeof(VitTask), hipMemcpyHostToDevice, st));
+        STRQ_HIP(c, hipMemcpyAsync(d_paths, pv.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
+        STRQ_HIP(c, hipMemcpyAsync(d_ts, sv.data(), (size_t)m * sizeof(typename K::Task), hipMemcpyHostToDevice, st));
+        STRQ_HIP(c, hipMemsetAsync(d_bad, 0, (size_t)m * 4, st));
+        if (path_n) STRQ_HIP(c, hipMemsetAsync(k.bufs.path.p, 0, path_n * 4, st));      // a traceback that stops early leaves valid states behind
+        double launches = 0;
+        const GroupHook trace = [&](const VitGroup& g) -> int {
+            if (launch_vit_traceback(st, d_vt + g.first, d_vr + g.first, d_paths + g.first, g.count)) { c->err = name + "traceback launch failed"; return STRQ_ERR_DEVICE; }
+            launches += 1; return STRQ_OK;
+        };
+        if (const int grc = launch_groups(c, st, G.groups, {d_vt, d_vr, d_order, {VIT_BACKPTR}, k.name, false, &launches, nullptr, trace})) return grc;
+        if (const char* why = k.launch(st, d_vt, d_ts, m)) { c->err = name + why; return STRQ_ERR_DEVICE; }
+        launches += 1; std::vector<int32_t> bad((size_t)m);
+        if (const int rc = k.read_back(c, st, d_vr, m)) return rc;
+        STRQ_HIP(c, hipMemcpyAsync(bad.data(), d_bad, (size_t)m * 4, hipMemcpyDeviceToHost, st));
+        STRQ_HIP(c, hipStreamSynchronize(st));
+        for (int at = 0; at < m; ++at) {
+            const size_t i = (size_t)wins[G.order[(size_t)at]];
+            if (bad[(size_t)at] || !k.scatter(at, i, w[i], sv[(size_t)at])) { c->err = name + "the back-pointer decode of a window disagrees with its count decode"; return STRQ_ERR_DEVICE; }
+        }
+        if (stats) { stats[0] += m; stats[1] += launches; stats[2] = std::max(stats[2], (double)pc.bytes); }
+    }
+    return STRQ_OK;
+}
+
+// Unit positions of the tracts of decoded windows (strq_ctx.h states the interface; strique_amd/tracts.py the rule): the traced paths
+// scanned with one ballot per tract (tract_scan_kernel).  The buffers are the detect state's own and exist only once this ran.
+struct TractPosConsumer {
+    using Task = TractScanTask;
+    TraceBufs bufs; TractPosOut& out;
+    const char *name = "tract positions: ", *budget_option = "STRQ_TRACT_POS_WS_BYTES";
+    std::vector<size_t> pos_off; size_t xo = 0;          // of the piece: where a task's positions begin in the pool, and its fill
+    std::vector<int64_t> pos;
+    const char* refuses(const HostModel& hm) const { return hm.h.tract_inc ? nullptr : "the model has no back-pointer decode"; }
+    size_t size_pool(const std::vector<TractPosWindow>& w, const int32_t* wins, int m)
+    {
+        size_t pos_n = 0; pos_off.assign((size_t)m, 0); xo = 0;
+        for (int k = 0; k < m; ++k) { const TractPosWindow& x = w[(size_t)wins[k]]; for (int j = 0; j < x.hm->n_tracts; ++j) pos_n += (size_t)x.n[j]; }
+        return pos_n * 8 + 64;
+    }
+    void fill(int at, const TractPosWindow& x, const TraceSlot& dev, TractScanTask& s)
+    {
+        s.path = dev.path; s.tract_inc = x.hm->h.tract_inc; s.result = dev.result; s.out = bufs.pool.as<int64_t>() + xo;
+        s.T = x.task.T; s.base = x.base; s.n_tracts = x.hm->n_tracts; s.n_states = x.hm->h.n_states; s.bad = dev.bad;
+        pos_off[(size_t)at] = xo;
+        for (int j = 0; j < x.hm->n_tracts; ++j) { s.off[j] = (int64_t)(xo - pos_off[(size_t)at]); s.n[j] = x.n[j]; xo += (size_t)x.n[j]; }
+    }
+    const char* launch(hipStream_t st, const VitTask*, const TractScanTask* d_ts, int m) { return launch_tract_scan(st, d_ts, m) ? "scan launch failed" : nullptr; }
+    int read_back(strq_ctx* c, hipStream_t st, const VitResult*, int)
+    {
+        pos.resize(xo + 1); if (xo) STRQ_HIP(c, hipMemcpyAsync(pos.data(), bufs.pool.p, xo * 8, hipMemcpyDeviceToHost, st));
+        return STRQ_OK;
+    }
+    bool scatter(int at, size_t i, const TractPosWindow&, const TractScanTask& s)
+    {
+        for (int j = 0; j < s.n_tracts; ++j) { const int64_t* from = pos.data() + pos_off[(size_t)at] + s.off[j]; out.pos[3 * i + (size_t)j].assign(from, from + s.n[j]); }
+        return true;
+    }
+};
 int tract_positions(strq_ctx* c, const std::vector<TractPosWindow>& w, TractPosOut& out, double* stats)
 {
-    DetectState* d = dstate(c);
-    hipStream_t st = c->stream;
-    const size_t nw = w.size();
-    out.status.assign(nw, 0); out.pos.assign(3 * nw, std::vector<int64_t>());
-    size_t budget = (size_t)8 << 30;
-    if (const char* e = strq::opt("STRQ_TRACT_POS_WS_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
-    struct W { int i; int shape; size_t bytes; };
-    std::vector<W> ws;
-    for (size_t i = 0; i < nw; ++i) {
-        const VitModel& h = w[i].hm->h;
-        const int shape = vit_shape_for(h, VIT_BACKPTR);
-        if (shape < 0 || !vit_mode_ok(shape, VIT_BACKPTR) || !h.tract_inc) { c->err = "tract positions: the model has no back-pointer decode"; return STRQ_ERR_UNSUPPORTED; }
-        // back-pointers: uint16 per (time step, state); every window starts on a 16-byte boundary
-        const size_t bytes = ((size_t)(w[i].task.T + 1) * (size_t)h.n_states * 2 + 15) & ~(size_t)15;
-        if (bytes > budget) { out.status[i] = 2; continue; }
-        ws.push_back({(int)i, shape, bytes});
-    }
-    for (size_t c0 = 0; c0 < ws.size();) {
-        size_t c1 = c0, bytes = 0;
-        while (c1 < ws.size() && bytes + ws[c1].bytes <= budget) bytes += ws[c1++].bytes;          // (every window fits alone)
-        const int m = (int)(c1 - c0);
-        std::vector<GroupItem> items((size_t)m);
-        size_t path_n = 0, pos_n = 0;
-        for (int k = 0; k < m; ++k) {
-            const TractPosWindow& x = w[(size_t)ws[c0 + (size_t)k].i];
-            items[(size_t)k] = {0, ws[c0 + (size_t)k].shape, x.hm->h.n_cells};
-            path_n += (size_t)x.task.T;
-            for (int j = 0; j < x.hm->n_tracts; ++j) pos_n += (size_t)x.n[j];
-        }
-        const Grouping G = group_items(items);
-        Carve lay;
-        const size_t o_vt = lay.add<VitTask>((size_t)m), o_vr = lay.add<VitResult>((size_t)m), o_paths = lay.add<int32_t*>((size_t)m),
-                     o_ts = lay.add<TractScanTask>((size_t)m), o_bad = lay.add<int32_t>((size_t)m), o_order = lay.add<int>((size_t)m);
-        STRQ_HIP(c, d->tpos_task.reserve(lay.total() + 64));
-        void* tb = d->tpos_task.p;
-        VitTask* d_vt = Carve::at<VitTask>(tb, o_vt); VitResult* d_vr = Carve::at<VitResult>(tb, o_vr); int32_t** d_paths = Carve::at<int32_t*>(tb, o_paths);
-        TractScanTask* d_ts = Carve::at<TractScanTask>(tb, o_ts); int32_t* d_bad = Carve::at<int32_t>(tb, o_bad); int* d_order = Carve::at<int>(tb, o_order);
-        STRQ_HIP(c, d->tpos_bp.reserve(bytes));
-        STRQ_HIP(c, d->tpos_path.reserve(path_n * 4 + 64));
-        STRQ_HIP(c, d->tpos_pool.reserve(pos_n * 8 + 64));
-        std::vector<VitTask> tv((size_t)m); std::vector<int32_t*> pv((size_t)m); std::vector<TractScanTask> sv((size_t)m);
-        std::vector<int> win_of((size_t)m); std::vector<size_t> pos_off((size_t)m);
-        size_t wo = 0, po = 0, xo = 0;
-        for (int at = 0; at < m; ++at) {          // in task order: the back-pointers, the paths and the positions lie in that order too
-            const W& ww = ws[c0 + (size_t)G.order[(size_t)at]];
-            const TractPosWindow& x = w[(size_t)ww.i];
-            VitTask t = x.task;
-            t.bp = reinterpret_cast<uint16_t*>(d->tpos_bp.as<char>() + wo); wo += ww.bytes;
-            if (wo > d->tpos_bp.cap) { c->err = "tract positions: workspace"; return STRQ_ERR_NOMEM; }
-            pv[(size_t)at] = d->tpos_path.as<int32_t>() + po; po += (size_t)t.T;
-            TractScanTask s; std::memset(&s, 0, sizeof(s));
-            s.path = pv[(size_t)at]; s.tract_inc = x.hm->h.tract_inc; s.result = d_vr + at; s.out = d->tpos_pool.as<int64_t>() + xo;
-            s.T = t.T; s.base = x.base; s.n_tracts = x.hm->n_tracts; s.n_states = x.hm->h.n_states; s.bad = d_bad + at;
-            pos_off[(size_t)at] = xo;
-            for (int j = 0; j < x.hm->n_tracts; ++j) { s.off[j] = (int64_t)(xo - pos_off[(size_t)at]); s.n[j] = x.n[j]; xo += (size_t)x.n[j]; }
-            tv[(size_t)at] = t; sv[(size_t)at] = s; win_of[(size_t)at] = ww.i;
-        }
-        STRQ_HIP(c, hipMemcpyAsync(d_vt, tv.data(), (size_t)m * sizeof(VitTask), hipMemcpyHostToDevice, st));
-        STRQ_HIP(c, hipMemcpyAsync(d_paths, pv.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
-        STRQ_HIP(c, hipMemcpyAsync(d_ts, sv.data(), (size_t)m * sizeof(TractScanTask), hipMemcpyHostToDevice, st));
-        STRQ_HIP(c, hipMemsetAsync(d_bad, 0, (size_t)m * 4, st));
-        if (path_n) STRQ_HIP(c, hipMemsetAsync(d->tpos_path.p, 0, path_n * 4, st));      // a traceback that stops early leaves valid states behind
-        double launches = 0;
-        const GroupHook trace = [&](const VitGroup& g) -> int {
-            if (launch_vit_traceback(st, d_vt + g.first, d_vr + g.first, d_paths + g.first, g.count)) { c->err = "tract positions: traceback launch failed"; return STRQ_ERR_DEVICE; }
-            launches += 1;
-            return STRQ_OK;
-        };
-        if (const int grc = launch_groups(c, st, G.groups, {d_vt, d_vr, d_order, {VIT_BACKPTR}, "tract positions: ", false, &launches, nullptr, trace})) return grc;
-        if (launch_tract_scan(st, d_ts, m)) { c->err = "tract positions: scan launch failed"; return STRQ_ERR_DEVICE; }
-        launches += 1;
-        std::vector<int64_t> pos(xo + 1); std::vector<int32_t> bad((size_t)m);
-        if (xo) STRQ_HIP(c, hipMemcpyAsync(pos.data(), d->tpos_pool.p, xo * 8, hipMemcpyDeviceToHost, st));
-        STRQ_HIP(c, hipMemcpyAsync(bad.data(), d_bad, (size_t)m * 4, hipMemcpyDeviceToHost, st));
-        STRQ_HIP(c, hipStreamSynchronize(st));
-        for (int at = 0; at < m; ++at) {
-            if (bad[(size_t)at]) { c->err = "tract positions: the back-pointer decode of a window disagrees with its count decode"; return STRQ_ERR_DEVICE; }
-            const TractScanTask& s = sv[(size_t)at];
-            for (int j = 0; j < s.n_tracts; ++j) {
-                const int64_t* from = pos.data() + pos_off[(size_t)at] + s.off[j];
-                out.pos[3 * (size_t)win_of[(size_t)at] + (size_t)j].assign(from, from + s.n[j]);
-            }
-        }
-        if (stats) { stats[0] += m; stats[1] += launches; stats[2] = std::max(stats[2], (double)bytes); }
-        c0 = c1;
-    }
-    return STRQ_OK;
+    DetectState* d = dstate(c); out.pos.assign(3 * w.size(), std::vector<int64_t>());
+    TractPosConsumer k{{d->tpos_task, d->tpos_bp, d->tpos_path, d->tpos_pool}, out};
+    return traced_redecode(c, w, k, out.status, stats);
 }
 
-// State statistics of decoded windows (strq_ctx.h states the interface; strique_amd/state_stats.py the rule), built like
-// tract_positions: the windows of a piece grouped by kernel shape, decoded with back-pointers, traced back into a zeroed path buffer and
-// summed per emitting state (state_stats_kernel).  One read-back and one wait per piece; the buffers exist only once this ran.
+// State statistics of decoded windows (strq_ctx.h states the interface; strique_amd/state_stats.py the rule): the observations of the
+// traced paths summed per emitting state (state_stats_kernel), n | sum | sumsq rows of the piece's windows in one pool.  A decode whose
+// status, log-probability or count is not what the count decode found disagrees with it.  The buffers exist only once this ran.
+struct StateStatsConsumer {
+    using Task = StateStatsTask;
+    TraceBufs bufs; StateStatsOut& out;
+    const char *name = "state-stats: ", *budget_option = "STRQ_STATE_STATS_WS_BYTES";
+    size_t row_n = 0, xo = 0; int max_emit = 1; std::vector<size_t> row_off;          // of the piece: rows in all, rows handed out, a task's first row
+    std::vector<int64_t> rows; std::vector<VitResult> vr;
+    const char* refuses(const HostModel& hm) const { return (hm.silent_start < 1 || hm.silent_start > STATE_STATS_MAX_EMIT) ? "the model's emitting states do not fit the kernel" : nullptr; }
+    size_t size_pool(const std::vector<StateStatsWindow>& w, const int32_t* wins, int m)
+    {
+        row_n = 0; xo = 0; max_emit = 1; row_off.assign((size_t)m, 0);
+        for (int k = 0; k < m; ++k) { const int ne = (int)w[(size_t)wins[k]].hm->silent_start; row_n += (size_t)ne; max_emit = std::max(max_emit, ne); }
+        return row_n * 24 + 64;
+    }
+    void fill(int at, const StateStatsWindow& x, const TraceSlot& dev, StateStatsTask& s)
+    {
+        int64_t* o_n = bufs.pool.as<int64_t>(); double* o_sum = reinterpret_cast<double*>(o_n + row_n); double* o_sq = o_sum + row_n;
+        s.path = dev.path; s.result = dev.result; s.n = o_n + xo; s.sum = o_sum + xo; s.sumsq = o_sq + xo; s.n_emit = x.hm->silent_start; s.bad = dev.bad;
+        row_off[(size_t)at] = xo; xo += (size_t)x.hm->silent_start;
+    }
+    const char* launch(hipStream_t st, const VitTask* d_vt, const StateStatsTask* d_ts, int m) { return launch_state_stats(st, d_vt, d_ts, m, max_emit) ? "kernel launch failed" : nullptr; }
+    int read_back(strq_ctx* c, hipStream_t st, const VitResult* d_vr, int m)
+    {
+        rows.resize(3 * row_n + 1); vr.resize((size_t)m);
+        STRQ_HIP(c, hipMemcpyAsync(rows.data(), bufs.pool.p, row_n * 24, hipMemcpyDeviceToHost, st));
+        STRQ_HIP(c, hipMemcpyAsync(vr.data(), d_vr, (size_t)m * sizeof(VitResult), hipMemcpyDeviceToHost, st));
+        return STRQ_OK;
+    }
+    bool scatter(int at, size_t i, const StateStatsWindow& x, const StateStatsTask&)
+    {
+        const VitResult& v = vr[(size_t)at]; if (v.status != 0 || std::memcmp(&v.logp, &x.logp, 8) != 0 || v.counted != x.counted) return false;
+        const int64_t* h_n = rows.data(); const double* h_sum = reinterpret_cast<const double*>(h_n + row_n); const double* h_sq = h_sum + row_n;
+        const size_t o = row_off[(size_t)at], ne = (size_t)x.hm->silent_start;
+        out.n[i].assign(h_n + o, h_n + o + ne); out.sum[i].assign(h_sum + o, h_sum + o + ne); out.sumsq[i].assign(h_sq + o, h_sq + o + ne);
+        return true;
+    }
+};
 int state_stats(strq_ctx* c, const std::vector<StateStatsWindow>& w, StateStatsOut& out, double* stats)
 {
-    DetectState* d = dstate(c);
-    hipStream_t st = c->stream;
-    const size_t nw = w.size();
-    out.status.assign(nw, 0); out.n.assign(nw, std::vector<int64_t>()); out.sum.assign(nw, std::vector<double>()); out.sumsq.assign(nw, std::vector<double>());
-    size_t budget = (size_t)8 << 30;
-    if (const char* e = strq::opt("STRQ_STATE_STATS_WS_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
-    struct W { int i; int shape; size_t bytes; };
-    std::vector<W> ws;
-    for (size_t i = 0; i < nw; ++i) {
-        const VitModel& h = w[i].hm->h;
-        const int shape = vit_shape_for(h, VIT_BACKPTR);
-        if (shape < 0 || !vit_mode_ok(shape, VIT_BACKPTR)) { c->err = "state-stats: the model has no back-pointer decode"; return STRQ_ERR_UNSUPPORTED; }
-        if (w[i].hm->silent_start < 1 || w[i].hm->silent_start > STATE_STATS_MAX_EMIT) { c->err = "state-stats: the model's emitting states do not fit the kernel"; return STRQ_ERR_UNSUPPORTED; }
-        // back-pointers: uint16 per (time step, state); every window starts on a 16-byte boundary
-        const size_t bytes = ((size_t)(w[i].task.T + 1) * (size_t)h.n_states * 2 + 15) & ~(size_t)15;
-        if (bytes > budget) { out.status[i] = 2; continue; }
-        ws.push_back({(int)i, shape, bytes});
-    }
-    for (size_t c0 = 0; c0 < ws.size();) {
-        size_t c1 = c0, bytes = 0;
-        while (c1 < ws.size() && bytes + ws[c1].bytes <= budget) bytes += ws[c1++].bytes;          // (every window fits alone)
-        const int m = (int)(c1 - c0);
-        std::vector<GroupItem> items((size_t)m);
-        size_t path_n = 0, row_n = 0; int max_emit = 1;
-        for (int k = 0; k < m; ++k) {
-            const StateStatsWindow& x = w[(size_t)ws[c0 + (size_t)k].i];
-            items[(size_t)k] = {0, ws[c0 + (size_t)k].shape, x.hm->h.n_cells};
-            path_n += (size_t)x.task.T; row_n += (size_t)x.hm->silent_start;
-            max_emit = std::max(max_emit, (int)x.hm->silent_start);
-        }
-        const Grouping G = group_items(items);
-        Carve lay;
-        const size_t o_vt = lay.add<VitTask>((size_t)m), o_vr = lay.add<VitResult>((size_t)m), o_paths = lay.add<int32_t*>((size_t)m),
-                     o_ts = lay.add<StateStatsTask>((size_t)m), o_bad = lay.add<int32_t>((size_t)m), o_order = lay.add<int>((size_t)m);
-        STRQ_HIP(c, d->sst_task.reserve(lay.total() + 64));
-        void* tb = d->sst_task.p;
-        VitTask* d_vt = Carve::at<VitTask>(tb, o_vt); VitResult* d_vr = Carve::at<VitResult>(tb, o_vr); int32_t** d_paths = Carve::at<int32_t*>(tb, o_paths);
-        StateStatsTask* d_ts = Carve::at<StateStatsTask>(tb, o_ts); int32_t* d_bad = Carve::at<int32_t>(tb, o_bad); int* d_order = Carve::at<int>(tb, o_order);
-        STRQ_HIP(c, d->sst_bp.reserve(bytes));
-        STRQ_HIP(c, d->sst_path.reserve(path_n * 4 + 64));
-        STRQ_HIP(c, d->sst_out.reserve(row_n * 24 + 64));          // n | sum | sumsq, row_n entries each
-        int64_t* o_n = d->sst_out.as<int64_t>(); double* o_sum = reinterpret_cast<double*>(o_n + row_n); double* o_sq = o_sum + row_n;
-        std::vector<VitTask> tv((size_t)m); std::vector<int32_t*> pv((size_t)m); std::vector<StateStatsTask> sv((size_t)m);
-        std::vector<int> win_of((size_t)m); std::vector<size_t> row_off((size_t)m);
-        size_t wo = 0, po = 0, xo = 0;
-        for (int at = 0; at < m; ++at) {          // in task order: the back-pointers, the paths and the rows lie in that order too
-            const W& ww = ws[c0 + (size_t)G.order[(size_t)at]];
-            const StateStatsWindow& x = w[(size_t)ww.i];
-            VitTask t = x.task;
-            t.bp = reinterpret_cast<uint16_t*>(d->sst_bp.as<char>() + wo); wo += ww.bytes;
-            if (wo > d->sst_bp.cap) { c->err = "state-stats: workspace"; return STRQ_ERR_NOMEM; }
-            pv[(size_t)at] = d->sst_path.as<int32_t>() + po; po += (size_t)t.T;
-            StateStatsTask s; std::memset(&s, 0, sizeof(s));
-            s.path = pv[(size_t)at]; s.result = d_vr + at; s.n = o_n + xo; s.sum = o_sum + xo; s.sumsq = o_sq + xo;
-            s.n_emit = x.hm->silent_start; s.bad = d_bad + at;
-            row_off[(size_t)at] = xo; xo += (size_t)x.hm->silent_start;
-            tv[(size_t)at] = t; sv[(size_t)at] = s; win_of[(size_t)at] = ww.i;
-        }
-        STRQ_HIP(c, hipMemcpyAsync(d_vt, tv.data(), (size_t)m * sizeof(VitTask), hipMemcpyHostToDevice, st));
-        STRQ_HIP(c, hipMemcpyAsync(d_paths, pv.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
-        STRQ_HIP(c, hipMemcpyAsync(d_ts, sv.data(), (size_t)m * sizeof(StateStatsTask), hipMemcpyHostToDevice, st));
-        STRQ_HIP(c, hipMemsetAsync(d_bad, 0, (size_t)m * 4, st));
-        if (path_n) STRQ_HIP(c, hipMemsetAsync(d->sst_path.p, 0, path_n * 4, st));      // a traceback that stops early leaves valid states behind
-        double launches = 0;
-        const GroupHook trace = [&](const VitGroup& g) -> int {
-            if (launch_vit_traceback(st, d_vt + g.first, d_vr + g.first, d_paths + g.first, g.count)) { c->err = "state-stats: traceback launch failed"; return STRQ_ERR_DEVICE; }
-            launches += 1;
-            return STRQ_OK;
-        };
-        if (const int grc = launch_groups(c, st, G.groups, {d_vt, d_vr, d_order, {VIT_BACKPTR}, "state-stats: ", false, &launches, nullptr, trace})) return grc;
-        if (launch_state_stats(st, d_vt, d_ts, m, max_emit)) { c->err = "state-stats: kernel launch failed"; return STRQ_ERR_DEVICE; }
-        launches += 1;
-        std::vector<int64_t> rows(3 * row_n + 1); std::vector<int32_t> bad((size_t)m); std::vector<VitResult> vr((size_t)m);
-        STRQ_HIP(c, hipMemcpyAsync(rows.data(), d->sst_out.p, row_n * 24, hipMemcpyDeviceToHost, st));
-        STRQ_HIP(c, hipMemcpyAsync(bad.data(), d_bad, (size_t)m * 4, hipMemcpyDeviceToHost, st));
-        STRQ_HIP(c, hipMemcpyAsync(vr.data(), d_vr, (size_t)m * sizeof(VitResult), hipMemcpyDeviceToHost, st));
-        STRQ_HIP(c, hipStreamSynchronize(st));
-        const int64_t* h_n = rows.data(); const double* h_sum = reinterpret_cast<const double*>(h_n + row_n); const double* h_sq = h_sum + row_n;
-        for (int at = 0; at < m; ++at) {
-            const StateStatsWindow& x = w[(size_t)win_of[(size_t)at]];
-            const VitResult& v = vr[(size_t)at];
-            if (bad[(size_t)at] || v.status != 0 || std::memcmp(&v.logp, &x.logp, 8) != 0 || v.counted != x.counted) {
-                c->err = "state-stats: the back-pointer decode of a window disagrees with its count decode"; return STRQ_ERR_DEVICE;
-            }
-            const size_t o = row_off[(size_t)at], ne = (size_t)x.hm->silent_start, i = (size_t)win_of[(size_t)at];
-            out.n[i].assign(h_n + o, h_n + o + ne); out.sum[i].assign(h_sum + o, h_sum + o + ne); out.sumsq[i].assign(h_sq + o, h_sq + o + ne);
-        }
-        if (stats) { stats[0] += m; stats[1] += launches; stats[2] = std::max(stats[2], (double)bytes); }
-        c0 = c1;
-    }
-    return STRQ_OK;
+    DetectState* d = dstate(c); out.n.assign(w.size(), std::vector<int64_t>()); out.sum.assign(w.size(), std::vector<double>()); out.sumsq.assign(w.size(), std::vector<double>());
+    StateStatsConsumer k{{d->sst_task, d->sst_bp, d->sst_path, d->sst_out}, out};
+    return traced_redecode(c, w, k, out.status, stats);
 }
 
-// State posteriors of windows (strq_ctx.h states the interface; strique_amd/state_posteriors.py the rule), built like state_stats: the
-// windows of a piece grouped by kernel shape, one forward and one backward launch per shape on two queue heads (posterior_kernels.h),
+// State posteriors of windows (strq_ctx.h states the interface; strique_amd/state_posteriors.py the rule).  No back-pointers and no
+// traceback, so it plans its pieces like the traced re-decode but runs them itself: the windows of a piece grouped by kernel shape, one forward and one backward launch per shape on two queue heads (posterior_kernels.h),
 // the stored forward vectors of the piece in one buffer.  A window whose vectors alone exceed the budget rides along in the first piece
 // with nothing stored: its forward half still gives the likelihood.  One read-back and one wait per piece; the buffers exist only once
 // this ran.
@@ -1231,29 +1202,25 @@ int state_posteriors(strq_ctx* c, const std::vector<StatePostWindow>& w, StatePo
     hipStream_t st = c->stream;
     const size_t nw = w.size();
     out.status.assign(nw, 0); out.fwd.assign(nw, FwdResult()); out.w.assign(nw, std::vector<double>()); out.wx.assign(nw, std::vector<double>()); out.wxx.assign(nw, std::vector<double>());
-    size_t budget = (size_t)8 << 30;
-    if (const char* e = strq::opt("STRQ_STATE_POST_WS_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
-    struct W { int i; int shape; size_t bytes; };
-    std::vector<W> ws, over;
+    std::vector<int> shape(nw); std::vector<size_t> sizes(nw);
     for (size_t i = 0; i < nw; ++i) {
         if (const int rc = posterior_model(c, w[i].hm)) return rc;
         const VitModel& h = w[i].hm->h;
-        const int shape = vit_shape_of(h);
-        if (vit_shape_family(shape) != VIT_FAMILY_LANE) { c->err = "state posteriors: the model has no forward kernel"; return STRQ_ERR_UNSUPPORTED; }
-        const size_t bytes = post_window_bytes(w[i].task.T, h.epl);
-        if (bytes > budget) { out.status[i] = 2; over.push_back({(int)i, shape, 0}); continue; }
-        ws.push_back({(int)i, shape, bytes});
+        shape[i] = vit_shape_of(h);
+        if (vit_shape_family(shape[i]) != VIT_FAMILY_LANE) { c->err = "state posteriors: the model has no forward kernel"; return STRQ_ERR_UNSUPPORTED; }
+        sizes[i] = post_window_bytes(w[i].task.T, h.epl);
     }
-    ws.insert(ws.begin(), over.begin(), over.end());
-    for (size_t c0 = 0; c0 < ws.size();) {
-        size_t c1 = c0, bytes = 0;
-        while (c1 < ws.size() && c1 - c0 < 8192 && bytes + ws[c1].bytes <= budget) bytes += ws[c1++].bytes;          // (every window fits alone)
-        const int m = (int)(c1 - c0);
+    // at most 8192 windows a piece; a window over the budget rides in front with nothing stored (detect_plan.h: OVERSIZE_IN_FRONT)
+    const PiecePlan plan = plan_pieces(sizes, ws_budget(strq::opt("STRQ_STATE_POST_WS_BYTES")), OVERSIZE_IN_FRONT, 8192);
+    for (int32_t i : plan.oversize) out.status[(size_t)i] = 2;
+    for (const Piece& pc : plan.pieces) {
+        const size_t c0 = pc.first, bytes = pc.bytes;
+        const int m = (int)(pc.last - pc.first);
         std::vector<GroupItem> items((size_t)m);
         size_t row_n = 0;
         for (int k = 0; k < m; ++k) {
-            const StatePostWindow& x = w[(size_t)ws[c0 + (size_t)k].i];
-            items[(size_t)k] = {0, ws[c0 + (size_t)k].shape, x.hm->h.n_cells};
+            const StatePostWindow& x = w[(size_t)plan.order[c0 + (size_t)k]];
+            items[(size_t)k] = {0, shape[(size_t)plan.order[c0 + (size_t)k]], x.hm->h.n_cells};
             row_n += (size_t)x.hm->silent_start;
         }
         const Grouping G = group_items(items);
@@ -1272,18 +1239,18 @@ int state_posteriors(strq_ctx* c, const std::vector<StatePostWindow>& w, StatePo
         std::vector<int> win_of((size_t)m); std::vector<size_t> row_off((size_t)m);
         size_t wo = 0, xo = 0;
         for (int at = 0; at < m; ++at) {          // in task order: the stored vectors and the rows lie in that order too
-            const W& ww = ws[c0 + (size_t)G.order[(size_t)at]];
-            const StatePostWindow& x = w[(size_t)ww.i];
+            const size_t at_plan = c0 + (size_t)G.order[(size_t)at];
+            const StatePostWindow& x = w[(size_t)plan.order[at_plan]];
             PostTask p; std::memset(&p, 0, sizeof(p));
-            if (ww.bytes) {
+            if (plan.bytes[at_plan]) {
                 p.alpha = reinterpret_cast<double*>(d->post_ws.as<char>() + wo);
                 p.expo = reinterpret_cast<int32_t*>(d->post_ws.as<char>() + wo + post_alpha_bytes(x.task.T, x.hm->h.epl));
-                wo += ww.bytes;
+                wo += plan.bytes[at_plan];
                 if (wo > d->post_ws.cap) { c->err = "state posteriors: workspace"; return STRQ_ERR_NOMEM; }
             }
             p.w = o_w + xo; p.wx = o_wx + xo; p.wxx = o_wxx + xo;
             row_off[(size_t)at] = xo; xo += (size_t)x.hm->silent_start;
-            tv[(size_t)at] = x.task; tv[(size_t)at].bp = nullptr; mv[(size_t)at] = x.hm->post_dev; pv[(size_t)at] = p; win_of[(size_t)at] = ww.i;
+            tv[(size_t)at] = x.task; tv[(size_t)at].bp = nullptr; mv[(size_t)at] = x.hm->post_dev; pv[(size_t)at] = p; win_of[(size_t)at] = plan.order[at_plan];
         }
         STRQ_HIP(c, hipMemcpyAsync(d_vt, tv.data(), (size_t)m * sizeof(VitTask), hipMemcpyHostToDevice, st));
         STRQ_HIP(c, hipMemcpyAsync(d_pm, mv.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
@@ -1311,7 +1278,6 @@ int state_posteriors(strq_ctx* c, const std::vector<StatePostWindow>& w, StatePo
             out.w[i].assign(h_w + o, h_w + o + ne); out.wx[i].assign(h_wx + o, h_wx + o + ne); out.wxx[i].assign(h_wxx + o, h_wxx + o + ne);
         }
         if (stats) { stats[0] += m; stats[1] += launches; stats[2] = std::max(stats[2], (double)bytes); }
-        c0 = c1;
     }
     return STRQ_OK;
 }
@@ -1428,7 +1394,7 @@ static int run_tract_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
         if (o.status == 0) {
             o.n_tracts = t.n_tracts; o.log_p = v.logp;
             for (int j = 0; j < t.n_tracts; ++j)
-                o.count[j] = (int32_t)(((uint64_t)v.counted >> (VIT_TRACT_BITS * j)) & (((uint64_t)1 << VIT_TRACT_BITS) - 1)) + t.tract_bias[j];
+                o.count[j] = (int32_t)vit_tract_count((uint64_t)v.counted, j) + t.tract_bias[j];
             d->stat(PASS_TRACTS, TRACT_WINDOWS) += 1;
         } else d->stat(PASS_TRACTS, TRACT_FAILED) += 1;
         B.tracts[(size_t)(r0 + i)] = o;
@@ -1440,7 +1406,7 @@ static int run_tract_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
         if (vr[(size_t)at].status != 0) continue;
         const int i = read_of[(size_t)at];
         TractPosWindow x; x.task = tv[(size_t)at]; x.hm = c->models[target_of(d, r0 + i).tract_model_id]; x.base = h.geom[i].prefix_begin;
-        for (int j = 0; j < 3; ++j) x.n[j] = (int64_t)(((uint64_t)vr[(size_t)at].counted >> (VIT_TRACT_BITS * j)) & (((uint64_t)1 << VIT_TRACT_BITS) - 1));
+        for (int j = 0; j < 3; ++j) x.n[j] = vit_tract_count((uint64_t)vr[(size_t)at].counted, j);
         pw.push_back(x); pw_read.push_back(i);
     }
     if (pw.empty()) return STRQ_OK;
@@ -1582,8 +1548,8 @@ static int run_motif_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
 // with begin < end -- the prefix on the raw samples [whole prefix begin, prefix_end), the suffix on [suffix_begin, whole suffix end) --
 // the stretch is normalised like the modification pass's (mod_compact_kernel without a path), decoded with the flank's profile model
 // (back-pointers, traceback), flank_mod_bounds_kernel turns the path into the groups' bounds and their score tasks, and the passage
-// scorer of the per-unit scores scores them, one launch per mode.  Runs behind the rows on the context's stream, in pieces of at most
-// STRQ_FLANK_MOD_WS_BYTES of back-pointers (default: the unit pass's 8 GiB); one read-back and one wait per piece.  The geometry, the
+// scorer of the per-unit scores scores them, one launch per mode.  Runs behind the rows on the context's stream, in pieces (detect_plan.h)
+// of back-pointers against STRQ_FLANK_MOD_WS_BYTES, an oversize stretch alone; one read-back and one wait per piece.  The geometry, the
 // conditioning constants and so the lengths are on the host already (the slot's pinned block), so the tasks are written there.
 static int run_flank_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl)
 {
@@ -1594,13 +1560,11 @@ static int run_flank_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl
     const DetectState::Slot::Pinned h = sl.host();
     const int esz = B.dtype == 0 ? 2 : 8;
     const int64_t s0 = B.off[r0];
-    size_t budget = (size_t)8 << 30;
-    if (const char* e = strq::opt("STRQ_FLANK_MOD_WS_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
     // test hook: the observations per flank base beyond which a stretch is not decoded (the rule's 64), so that the too_long branch can be reached
     int64_t max_per_base = 64;
     if (const char* e = strq::opt("STRQ_FLANK_MOD_MAX_STRETCH")) { const long long v = atoll(e); if (v > 0) max_per_base = (int64_t)v; }
-    struct F { int i, which; int64_t begin, T; size_t bytes, first_rec; };
-    std::vector<F> fl;
+    struct F { int i, which; int64_t begin, T; size_t first_rec; };
+    std::vector<F> fl; std::vector<size_t> sizes;
     const double nan = std::nan("");
     for (int i = 0; i < nr; ++i) {
         const Target& t = target_of(d, r0 + i);
@@ -1621,14 +1585,14 @@ static int run_flank_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl
                 o.status = too_long ? FMOD_TOO_LONG : FMOD_NO_PATH; o.begin = o.end = -1; o.v_base = o.v_mod = nan;
                 recs.push_back(o);
             }
-            if (!too_long) fl.push_back({i, which, begin, T, (size_t)(T + 1) * (size_t)c->models[fm.model_id]->h.n_states * 2, first_rec});
+            if (!too_long) { fl.push_back({i, which, begin, T, first_rec}); sizes.push_back(bp_window_bytes(T, c->models[fm.model_id]->h.n_states)); }
         }
     }
     if (fl.empty()) return STRQ_OK;
     if (const int rc = pass_start(c, pass_ev(d))) return rc;
-    for (size_t c0 = 0; c0 < fl.size();) {
-        size_t c1 = c0, bytes = 0;
-        while (c1 < fl.size() && (c1 == c0 || bytes + ((fl[c1].bytes + 15) & ~(size_t)15) <= budget)) bytes += (fl[c1++].bytes + 15) & ~(size_t)15;
+    const PiecePlan plan = plan_pieces(sizes, ws_budget(strq::opt("STRQ_FLANK_MOD_WS_BYTES")), OVERSIZE_ALONE);
+    for (const Piece& pc : plan.pieces) {
+        const size_t c0 = pc.first, c1 = pc.last, bytes = pc.bytes;
         const int m = (int)(c1 - c0);
         std::vector<GroupItem> items((size_t)m);
         size_t sumT = 0, Gs = 0; int n_mode[3] = {0, 0, 0};
@@ -1678,7 +1642,7 @@ static int run_flank_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl
             mk.clip_lo = d->ps.clip_lo; mk.clip_hi = d->ps.clip_hi; mk.mod_lo = t.mod_min; mk.mod_hi = t.mod_max;
             VitTask& v = vt[(size_t)at]; v = VitTask();
             v.model = hm->dev; v.sig = mk.out; v.T = f.T; v.src_kind = VIT_SRC_F64;
-            v.bp = reinterpret_cast<uint16_t*>(d->fmod_bp.as<char>() + bo); bo += (f.bytes + 15) & ~(size_t)15;
+            v.bp = reinterpret_cast<uint16_t*>(d->fmod_bp.as<char>() + bo); bo += sizes[c0 + (size_t)k];
             pp[(size_t)at] = d_path + xo;
             FlankBoundTask& b = bt[(size_t)k]; std::memset(&b, 0, sizeof(b));
             b.path = d_path + xo; b.vit_status = &d_vr[at].status; b.column_of = fm.col->as<int32_t>();
@@ -1735,7 +1699,6 @@ static int run_flank_mod_pass(strq_ctx* c, DetectState* d, DetectState::Slot& sl
             }
         }
         d->stat(PASS_FMOD, FMOD_FLANKS) += m;
-        c0 = c1;
     }
     return pass_stop(c, pass_ev(d), d->stats[PASS_FMOD]);
 }

@@ -745,48 +745,70 @@ int strq_debug_viterbi_plan(int32_t n_states, int32_t silent_start, int32_t star
 
 int strq_model_set_positions(strq_ctx* c, int32_t model_id, const int32_t* kind, const int32_t* pos)
 {
-    strq::CtxScope scope_(c);
-    if (!c) return STRQ_ERR_ARG;
+    STRQ_ENTER(c);
     if (model_id < 0 || model_id >= (int32_t)c->models.size() || !c->models[model_id] || !kind || !pos) { c->err = "bad argument"; return STRQ_ERR_ARG; }
-    STRQ_HIP(c, hipSetDevice(c->device));
     // a detect sub-batch whose Viterbi launches are not yet queued points to the model's present device image through its tasks
     { const int rc = detect_drain(c); if (rc) return rc; }
     return build_vit_g2(c, c->models[model_id], kind, pos);
 }
 
-int strq_viterbi_batch(strq_ctx* c, int32_t model_id, int64_t n_seq, const double* x, const int64_t* x_off,
-                       double* logp, int64_t* counted, int32_t* status, int32_t* paths)
+// One window of a model: T observations at `sig` (with an affine kind the caller adds the constants); everything else zero
+static VitTask plain_task(const HostModel* hm, const void* sig, int64_t T, int32_t src_kind = VIT_SRC_F64)
 {
-    strq::CtxScope scope_(c);
-    if (!c) return STRQ_ERR_ARG;
-    if (model_id < 0 || model_id >= (int32_t)c->models.size() || !c->models[model_id] || n_seq < 0 || (n_seq > 0 && (!x || !x_off))) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    VitTask t; std::memset(&t, 0, sizeof(t));
+    t.model = hm->dev; t.sig = sig; t.T = T; t.src_kind = src_kind;
+    return t;
+}
+
+// The windows of a standalone entry point.  check_windows: the model, at most max_seq windows (0: any number), x_off from 0 up and never
+// decreasing, observations where there are any.  upload_windows (n_seq > 0, checked): the observations into c->vit_x, a float64 task each.
+static int check_windows(strq_ctx* c, int32_t model_id, int64_t n_seq, const double* x, const int64_t* x_off, int64_t max_seq)
+{
+    if (model_id < 0 || model_id >= (int32_t)c->models.size() || !c->models[model_id] || n_seq < 0 || (max_seq && n_seq > max_seq) || (n_seq > 0 && !x_off)) { c->err = "bad argument"; return STRQ_ERR_ARG; }
     if (n_seq == 0) return STRQ_OK;
-    STRQ_HIP(c, hipSetDevice(c->device));
+    if (x_off[n_seq] < 0 || (x_off[n_seq] > 0 && !x)) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    for (int64_t i = 0; i < n_seq; ++i) if (x_off[i + 1] < x_off[i] || x_off[i] < 0) { c->err = "bad argument (x_off must not decrease)"; return STRQ_ERR_ARG; }
+    return STRQ_OK;
+}
+static int upload_windows(strq_ctx* c, const HostModel* hm, int64_t n_seq, const double* x, const int64_t* x_off, std::vector<VitTask>& tasks)
+{
+    const int64_t tot = x_off[n_seq];
+    STRQ_HIP(c, c->vit_x.reserve((size_t)tot * 8 + 64));
+    if (tot) STRQ_HIP(c, hipMemcpyAsync(c->vit_x.p, x, (size_t)tot * 8, hipMemcpyHostToDevice, c->stream));
+    tasks.resize((size_t)n_seq);
+    for (int64_t i = 0; i < n_seq; ++i) tasks[(size_t)i] = plain_task(hm, c->vit_x.as<double>() + x_off[i], x_off[i + 1] - x_off[i]);
+    return STRQ_OK;
+}
+
+// strq_viterbi_batch, strq_viterbi, the count decode of strq_viterbi_state_stats; `keep` (or null) takes the tasks, input order, no bp
+static int viterbi_batch(strq_ctx* c, int32_t model_id, int64_t n_seq, const double* x, const int64_t* x_off, int64_t max_seq,
+                         double* logp, int64_t* counted, int32_t* status, int32_t* paths, std::vector<VitTask>* keep)
+{
+    if (n_seq > 0 && !x) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    if (const int rc = check_windows(c, model_id, n_seq, x, x_off, max_seq)) return rc;
+    if (n_seq == 0) return STRQ_OK;
     HostModel* hm = c->models[model_id];
     hipStream_t st = c->stream;
     const int64_t tot = x_off[n_seq];
     const int n = hm->h.n_states;
-    STRQ_HIP(c, c->vit_x.reserve((size_t)tot * 8 + 64));
-    STRQ_HIP(c, hipMemcpyAsync(c->vit_x.p, x, (size_t)tot * 8, hipMemcpyHostToDevice, st));
+    std::vector<VitTask> in;
+    if (const int rc = upload_windows(c, hm, n_seq, x, x_off, in)) return rc;
     Carve lay;
     const size_t o_tasks = lay.add<VitTask>((size_t)n_seq), o_res = lay.add<VitResult>((size_t)n_seq), o_paths = lay.add<int32_t*>((size_t)n_seq);
     STRQ_HIP(c, c->vit_tasks.reserve(lay.total()));
     VitTask* d_tasks = Carve::at<VitTask>(c->vit_tasks.p, o_tasks); VitResult* d_res = Carve::at<VitResult>(c->vit_tasks.p, o_res);
     int32_t** d_paths = Carve::at<int32_t*>(c->vit_tasks.p, o_paths);
     size_t bp_cells = 0;
-    if (paths) { for (int64_t i = 0; i < n_seq; ++i) bp_cells += (size_t)(x_off[i + 1] - x_off[i] + 1) * n; }
+    for (int64_t i = 0; paths && i < n_seq; ++i) bp_cells += (size_t)(in[(size_t)i].T + 1) * n;
     if (paths) { STRQ_HIP(c, c->vit_bp.reserve(bp_cells * 2 + 64)); STRQ_HIP(c, c->vit_path.reserve((size_t)tot * 4 + 64)); }
-    // longest first
-    std::vector<int64_t> order(n_seq);
+    std::vector<int64_t> order(n_seq);          // longest first
     for (int64_t i = 0; i < n_seq; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return x_off[a + 1] - x_off[a] > x_off[b + 1] - x_off[b]; });
+    std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return in[(size_t)a].T > in[(size_t)b].T; });
     std::vector<VitTask> tasks(n_seq); std::vector<int32_t*> hp(n_seq, nullptr);
     size_t bp_off = 0;
     for (int64_t pos = 0; pos < n_seq; ++pos) {
         const int64_t i = order[pos];
-        VitTask& t = tasks[pos];
-        std::memset(&t, 0, sizeof(t));
-        t.model = hm->dev; t.sig = c->vit_x.as<double>() + x_off[i]; t.T = x_off[i + 1] - x_off[i]; t.src_kind = VIT_SRC_F64;
+        VitTask& t = tasks[pos] = in[(size_t)i];
         if (paths) { t.bp = c->vit_bp.as<uint16_t>() + bp_off; bp_off += (size_t)(t.T + 1) * n; hp[pos] = c->vit_path.as<int32_t>() + x_off[i]; }
     }
     STRQ_HIP(c, hipMemcpyAsync(d_tasks, tasks.data(), (size_t)n_seq * sizeof(VitTask), hipMemcpyHostToDevice, st));
@@ -798,9 +820,7 @@ int strq_viterbi_batch(strq_ctx* c, int32_t model_id, int64_t n_seq, const doubl
     int rc = launch_viterbi(st, shape, hm->h.n_cells, d_tasks, d_res, (int)n_seq, c->queue.as<int>(), c->n_cu, paths ? VIT_BACKPTR : VIT_COUNT);
     if (rc) { c->err = "viterbi launch failed"; return viterbi_launch_status(rc); }
     STRQ_HIP(c, hipEventRecord(c->ev[1], st));
-    if (paths) {
-        if (launch_vit_traceback(st, d_tasks, d_res, d_paths, (int)n_seq)) { c->err = "traceback launch failed"; return STRQ_ERR_DEVICE; }
-    }
+    if (paths && launch_vit_traceback(st, d_tasks, d_res, d_paths, (int)n_seq)) { c->err = "traceback launch failed"; return STRQ_ERR_DEVICE; }
     STRQ_HIP(c, hipEventRecord(c->ev[2], st));
     std::vector<VitResult> res(n_seq);
     STRQ_HIP(c, hipMemcpyAsync(res.data(), d_res, (size_t)n_seq * sizeof(VitResult), hipMemcpyDeviceToHost, st));
@@ -816,7 +836,15 @@ int strq_viterbi_batch(strq_ctx* c, int32_t model_id, int64_t n_seq, const doubl
     STRQ_HIP(c, hipEventElapsedTime(&c->timing[0], c->ev[0], c->ev[1]));
     STRQ_HIP(c, hipEventElapsedTime(&c->timing[1], c->ev[1], c->ev[2]));
     c->timing[3] = c->timing[0] + c->timing[1];
+    if (keep) keep->swap(in);
     return STRQ_OK;
+}
+
+int strq_viterbi_batch(strq_ctx* c, int32_t model_id, int64_t n_seq, const double* x, const int64_t* x_off,
+                       double* logp, int64_t* counted, int32_t* status, int32_t* paths)
+{
+    STRQ_ENTER(c);
+    return viterbi_batch(c, model_id, n_seq, x, x_off, 0, logp, counted, status, paths, nullptr);
 }
 
 // The two test hooks below: one launch_viterbi of `mode` over the windows, on buffers of the call's own (strique_hip.h).  src_kind
@@ -867,8 +895,7 @@ static int debug_viterbi_launch(strq_ctx* c, int32_t model_id, int32_t mode, int
     std::vector<VitTask> tasks((size_t)n_seq);
     for (int64_t i = 0; i < n_seq; ++i) {
         VitTask& t = tasks[(size_t)i];
-        std::memset(&t, 0, sizeof(t));
-        t.model = hm->dev; t.sig = b_x.as<char>() + (size_t)x_off[i] * esz; t.T = x_off[i + 1] - x_off[i]; t.src_kind = src_kind;
+        t = plain_task(hm, b_x.as<char>() + (size_t)x_off[i] * esz, x_off[i + 1] - x_off[i], src_kind);
         if (src_kind != VIT_SRC_F64) { const double* k = consts + 6 * i; t.c1 = k[0]; t.h1 = k[1]; t.h2 = k[2]; t.c2 = k[3]; t.lo = k[4]; t.hi = k[5]; }
         if (rec) t.bp = reinterpret_cast<uint16_t*>(b_rec.as<char>() + rec_off[i]);
     }
@@ -893,7 +920,7 @@ static int debug_viterbi_launch(strq_ctx* c, int32_t model_id, int32_t mode, int
         if (dbg) std::memcpy(dbg + 4 * i, r.dbg, sizeof(r.dbg));
         if (tracts) {          // as strq_viterbi_tracts unpacks them
             const uint64_t pay = r.status == 0 ? (uint64_t)r.counted : 0;
-            for (int j = 0; j < VIT_TRACTS_MAX; ++j) tract_counts[3 * i + j] = (int64_t)((pay >> (VIT_TRACT_BITS * j)) & (((uint64_t)1 << VIT_TRACT_BITS) - 1));
+            for (int j = 0; j < VIT_TRACTS_MAX; ++j) tract_counts[3 * i + j] = vit_tract_count(pay, j);
         }
     }
     return STRQ_OK;
@@ -935,16 +962,13 @@ int strq_forward_batch(strq_ctx* c, int32_t model_id, int64_t n_seq, const doubl
                        double* log_lik, double* visits_mean, double* visits_var, int32_t* status)
 {
     STRQ_ENTER(c);
-    if (model_id < 0 || model_id >= (int32_t)c->models.size() || !c->models[model_id] || n_seq < 0 || n_seq > 8192 || (n_seq > 0 && !x_off)) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    if (const int rc = check_windows(c, model_id, n_seq, x, x_off, 8192)) return rc;
     if (n_seq == 0) return STRQ_OK;
-    const int64_t tot = x_off[n_seq];
-    if (tot < 0 || (tot > 0 && !x)) { c->err = "bad argument"; return STRQ_ERR_ARG; }
-    for (int64_t i = 0; i < n_seq; ++i) if (x_off[i + 1] < x_off[i] || x_off[i] < 0) { c->err = "bad argument (x_off must not decrease)"; return STRQ_ERR_ARG; }
     HostModel* hm = c->models[model_id];
     if (const int rc = forward_model(c, hm)) return rc;
     hipStream_t st = c->stream;
-    STRQ_HIP(c, c->vit_x.reserve((size_t)tot * 8 + 64));
-    if (tot) STRQ_HIP(c, hipMemcpyAsync(c->vit_x.p, x, (size_t)tot * 8, hipMemcpyHostToDevice, st));
+    std::vector<VitTask> tasks;
+    if (const int rc = upload_windows(c, hm, n_seq, x, x_off, tasks)) return rc;
     Carve lay;
     const size_t o_tasks = lay.add<VitTask>((size_t)n_seq), o_res = lay.add<FwdResult>((size_t)n_seq), o_fm = lay.add<const FwdModel*>((size_t)n_seq),
                  o_c0 = lay.add<int64_t>((size_t)n_seq), o_order = lay.add<int>((size_t)n_seq);
@@ -952,13 +976,8 @@ int strq_forward_batch(strq_ctx* c, int32_t model_id, int64_t n_seq, const doubl
     void* tb = c->vit_tasks.p;
     VitTask* d_tasks = Carve::at<VitTask>(tb, o_tasks); FwdResult* d_res = Carve::at<FwdResult>(tb, o_res); const FwdModel** d_fm = Carve::at<const FwdModel*>(tb, o_fm);
     int64_t* d_c0 = Carve::at<int64_t>(tb, o_c0); int* d_order = Carve::at<int>(tb, o_order);
-    std::vector<VitTask> tasks(n_seq); std::vector<const FwdModel*> fms((size_t)n_seq, hm->fwd_dev); std::vector<int64_t> c0v((size_t)n_seq, 0);
-    for (int64_t i = 0; i < n_seq; ++i) {
-        VitTask& t = tasks[i];
-        std::memset(&t, 0, sizeof(t));
-        t.model = hm->dev; t.sig = c->vit_x.as<double>() + x_off[i]; t.T = x_off[i + 1] - x_off[i]; t.src_kind = VIT_SRC_F64;
-        if (c0) c0v[(size_t)i] = c0[i];
-    }
+    std::vector<const FwdModel*> fms((size_t)n_seq, hm->fwd_dev); std::vector<int64_t> c0v((size_t)n_seq, 0);
+    if (c0) c0v.assign(c0, c0 + n_seq);
     STRQ_HIP(c, hipMemcpyAsync(d_tasks, tasks.data(), (size_t)n_seq * sizeof(VitTask), hipMemcpyHostToDevice, st));
     STRQ_HIP(c, hipMemcpyAsync(d_fm, fms.data(), (size_t)n_seq * 8, hipMemcpyHostToDevice, st));
     STRQ_HIP(c, hipMemcpyAsync(d_c0, c0v.data(), (size_t)n_seq * 8, hipMemcpyHostToDevice, st));
@@ -1014,29 +1033,20 @@ int strq_model_set_tracts(strq_ctx* c, int32_t model_id, int32_t n_tracts, const
 static int viterbi_tracts(strq_ctx* c, int32_t model_id, int64_t n_seq, const double* x, const int64_t* x_off,
                           double* logp, int64_t* counts, int32_t* status, std::pair<std::vector<VitTask>, std::vector<VitResult>>* keep)
 {
-    if (model_id < 0 || model_id >= (int32_t)c->models.size() || !c->models[model_id] || n_seq < 0 || n_seq > 8192 || (n_seq > 0 && !x_off)) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    if (const int rc = check_windows(c, model_id, n_seq, x, x_off, 8192)) return rc;
     HostModel* hm = c->models[model_id];
     if (!hm->h.tract_inc) { c->err = "the model has no tracts (strq_model_set_tracts)"; return STRQ_ERR_ARG; }
     const int shape = vit_shape_of(hm->h);          // never the register-resident image: it has one loop
     if (n_seq == 0) return STRQ_OK;
-    const int64_t tot = x_off[n_seq];
-    if (tot < 0 || (tot > 0 && !x)) { c->err = "bad argument"; return STRQ_ERR_ARG; }
-    for (int64_t i = 0; i < n_seq; ++i) if (x_off[i + 1] < x_off[i] || x_off[i] < 0) { c->err = "bad argument (x_off must not decrease)"; return STRQ_ERR_ARG; }
     if (shape < 0) { c->err = "model does not fit a compiled Viterbi kernel"; return STRQ_ERR_UNSUPPORTED; }
     hipStream_t st = c->stream;
-    STRQ_HIP(c, c->vit_x.reserve((size_t)tot * 8 + 64));
-    if (tot) STRQ_HIP(c, hipMemcpyAsync(c->vit_x.p, x, (size_t)tot * 8, hipMemcpyHostToDevice, st));
+    std::vector<VitTask> tasks;
+    if (const int rc = upload_windows(c, hm, n_seq, x, x_off, tasks)) return rc;
     Carve lay;
     const size_t o_tasks = lay.add<VitTask>((size_t)n_seq), o_res = lay.add<VitResult>((size_t)n_seq), o_order = lay.add<int>((size_t)n_seq);
     STRQ_HIP(c, c->vit_tasks.reserve(lay.total() + 64));
     VitTask* d_tasks = Carve::at<VitTask>(c->vit_tasks.p, o_tasks); VitResult* d_res = Carve::at<VitResult>(c->vit_tasks.p, o_res);
     int* d_order = Carve::at<int>(c->vit_tasks.p, o_order);
-    std::vector<VitTask> tasks((size_t)n_seq);
-    for (int64_t i = 0; i < n_seq; ++i) {
-        VitTask& t = tasks[(size_t)i];
-        std::memset(&t, 0, sizeof(t));
-        t.model = hm->dev; t.sig = c->vit_x.as<double>() + x_off[i]; t.T = x_off[i + 1] - x_off[i]; t.src_kind = VIT_SRC_F64;
-    }
     STRQ_HIP(c, hipMemcpyAsync(d_tasks, tasks.data(), (size_t)n_seq * sizeof(VitTask), hipMemcpyHostToDevice, st));
     if (const int qrc = reset_queue_heads(c, st)) return qrc;
     if (launch_vit_sort(st, d_tasks, (int)n_seq, d_order)) { c->err = "tract decode: sort launch failed"; return STRQ_ERR_DEVICE; }
@@ -1051,7 +1061,7 @@ static int viterbi_tracts(strq_ctx* c, int32_t model_id, int64_t n_seq, const do
         const uint64_t pay = r.status == 0 ? (uint64_t)r.counted : 0;
         if (logp) logp[i] = r.logp;
         if (status) status[i] = r.status;
-        if (counts) for (int j = 0; j < VIT_TRACTS_MAX; ++j) counts[3 * i + j] = (int64_t)((pay >> (VIT_TRACT_BITS * j)) & (((uint64_t)1 << VIT_TRACT_BITS) - 1));
+        if (counts) for (int j = 0; j < VIT_TRACTS_MAX; ++j) counts[3 * i + j] = vit_tract_count(pay, j);
     }
     if (keep) { keep->first.swap(tasks); keep->second.swap(res); }
     return STRQ_OK;
@@ -1080,7 +1090,7 @@ int strq_viterbi_tract_positions(strq_ctx* c, int32_t model_id, int64_t n_seq, c
         const VitResult& r = kept.second[(size_t)i];
         if (r.status != 0) continue;
         TractPosWindow w; w.task = kept.first[(size_t)i]; w.hm = hm; w.base = 0;
-        for (int j = 0; j < 3; ++j) w.n[j] = (int64_t)(((uint64_t)r.counted >> (VIT_TRACT_BITS * j)) & (((uint64_t)1 << VIT_TRACT_BITS) - 1));
+        for (int j = 0; j < 3; ++j) w.n[j] = vit_tract_count((uint64_t)r.counted, j);
         pw.push_back(w); win.push_back(i);
     }
     TractPosOut po;
@@ -1101,22 +1111,19 @@ int strq_viterbi_state_stats(strq_ctx* c, int32_t model_id, int64_t n_seq, const
                              double* logp, int64_t* counted, int32_t* status, int64_t* n_obs, double* sum, double* sumsq)
 {
     STRQ_ENTER(c);
-    if (model_id < 0 || model_id >= (int32_t)c->models.size() || !c->models[model_id] || n_seq < 0 || n_seq > 8192 || (n_seq > 0 && (!x_off || !n_obs || !sum || !sumsq))) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    if (n_seq > 0 && (!x_off || x_off[0] != 0 || !n_obs || !sum || !sumsq)) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    if (const int rc = check_windows(c, model_id, n_seq, x, x_off, 8192)) return rc;
     if (n_seq == 0) return STRQ_OK;
-    const int64_t tot = x_off[n_seq];
-    if (x_off[0] != 0 || tot < 0 || (tot > 0 && !x)) { c->err = "bad argument"; return STRQ_ERR_ARG; }
-    for (int64_t i = 0; i < n_seq; ++i) if (x_off[i + 1] < x_off[i]) { c->err = "bad argument (x_off must not decrease)"; return STRQ_ERR_ARG; }
     const HostModel* hm = c->models[model_id];
     // the count decode first: logp, counted and status are strq_viterbi_batch's, and the observations stay in the context's buffer
-    std::vector<double> lp((size_t)n_seq); std::vector<int64_t> cn((size_t)n_seq); std::vector<int32_t> stv((size_t)n_seq);
-    if (const int rc = strq_viterbi_batch(c, model_id, n_seq, x, x_off, lp.data(), cn.data(), stv.data(), nullptr)) return rc;
+    std::vector<double> lp((size_t)n_seq); std::vector<int64_t> cn((size_t)n_seq); std::vector<int32_t> stv((size_t)n_seq); std::vector<VitTask> tasks;
+    if (const int rc = viterbi_batch(c, model_id, n_seq, x, x_off, 8192, lp.data(), cn.data(), stv.data(), nullptr, &tasks)) return rc;
     const size_t ne = (size_t)hm->silent_start;
     std::fill(n_obs, n_obs + (size_t)n_seq * ne, (int64_t)0); std::fill(sum, sum + (size_t)n_seq * ne, 0.0); std::fill(sumsq, sumsq + (size_t)n_seq * ne, 0.0);
     std::vector<StateStatsWindow> sw; std::vector<int64_t> win;
     for (int64_t i = 0; i < n_seq; ++i) {
         if (stv[(size_t)i] != 0) continue;
-        StateStatsWindow w; std::memset(&w.task, 0, sizeof(w.task));
-        w.task.model = hm->dev; w.task.sig = c->vit_x.as<double>() + x_off[i]; w.task.T = x_off[i + 1] - x_off[i]; w.task.src_kind = VIT_SRC_F64;
+        StateStatsWindow w; w.task = tasks[(size_t)i];
         w.hm = hm; w.logp = lp[(size_t)i]; w.counted = cn[(size_t)i];
         sw.push_back(w); win.push_back(i);
     }
@@ -1139,22 +1146,15 @@ int strq_forward_state_stats(strq_ctx* c, int32_t model_id, int64_t n_seq, const
                              double* log_lik, int32_t* status, double* w, double* wx, double* wxx)
 {
     STRQ_ENTER(c);
-    if (model_id < 0 || model_id >= (int32_t)c->models.size() || !c->models[model_id] || n_seq < 0 || n_seq > 8192 || (n_seq > 0 && (!x_off || !w || !wx || !wxx))) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    if (n_seq > 0 && (!x_off || x_off[0] != 0 || !w || !wx || !wxx)) { c->err = "bad argument"; return STRQ_ERR_ARG; }
+    if (const int rc = check_windows(c, model_id, n_seq, x, x_off, 8192)) return rc;
     if (n_seq == 0) return STRQ_OK;
-    const int64_t tot = x_off[n_seq];
-    if (x_off[0] != 0 || tot < 0 || (tot > 0 && !x)) { c->err = "bad argument"; return STRQ_ERR_ARG; }
-    for (int64_t i = 0; i < n_seq; ++i) if (x_off[i + 1] < x_off[i]) { c->err = "bad argument (x_off must not decrease)"; return STRQ_ERR_ARG; }
     HostModel* hm = c->models[model_id];
     if (const int rc = posterior_model(c, hm)) return rc;
-    STRQ_HIP(c, c->vit_x.reserve((size_t)tot * 8 + 64));
-    if (tot) STRQ_HIP(c, hipMemcpyAsync(c->vit_x.p, x, (size_t)tot * 8, hipMemcpyHostToDevice, c->stream));
+    std::vector<VitTask> tasks;
+    if (const int rc = upload_windows(c, hm, n_seq, x, x_off, tasks)) return rc;
     std::vector<StatePostWindow> pw((size_t)n_seq);
-    for (int64_t i = 0; i < n_seq; ++i) {
-        StatePostWindow& p = pw[(size_t)i];
-        std::memset(&p.task, 0, sizeof(p.task));
-        p.task.model = hm->dev; p.task.sig = c->vit_x.as<double>() + x_off[i]; p.task.T = x_off[i + 1] - x_off[i]; p.task.src_kind = VIT_SRC_F64;
-        p.hm = hm;
-    }
+    for (int64_t i = 0; i < n_seq; ++i) { pw[(size_t)i].task = tasks[(size_t)i]; pw[(size_t)i].hm = hm; }
     StatePostOut po;
     if (const int rc = state_posteriors(c, pw, po, nullptr)) return rc;
     const size_t ne = (size_t)hm->silent_start;
@@ -1181,9 +1181,9 @@ int strq_debug_tract_shape(const strq_ctx* c, int32_t* shape)
 int strq_viterbi(strq_ctx* c, int32_t model_id, const double* x, int64_t T, double* logp, int64_t* counted,
                  int32_t* status, int32_t* path)
 {
-    strq::CtxScope scope_(c);
+    STRQ_ENTER(c);
     const int64_t off[2] = {0, T};
-    return strq_viterbi_batch(c, model_id, 1, x, off, logp, counted, status, path);
+    return viterbi_batch(c, model_id, 1, x, off, 0, logp, counted, status, path, nullptr);
 }
 
 }  // extern "C"

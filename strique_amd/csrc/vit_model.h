@@ -105,6 +105,8 @@ struct VitModel {
 // three counters of 21 bits: windows below VIT_MARK_T_MAX observations cannot carry from one into the next (every counted state emits)
 #define VIT_TRACT_BITS 21
 #define VIT_TRACTS_MAX 3
+// counter j of such a payload (VitResult::counted of a tract decode), on the host
+inline int64_t vit_tract_count(uint64_t payload, int j) { return (int64_t)((payload >> (VIT_TRACT_BITS * j)) & (((uint64_t)1 << VIT_TRACT_BITS) - 1)); }
 #define VIT_CSR_MAX_STATES 4096      // two buffers of 16-byte cells in 160 KB of LDS
 
 enum { VIT_SRC_F64 = 0, VIT_SRC_F64_AFFINE = 1, VIT_SRC_I16_AFFINE = 2 };

@@ -1,10 +1,11 @@
 // Stand-alone host program over strique_amd/csrc/detect_plan.h (no HIP): the anchored record from the marks of a MARK decode, the
 // per-read rows, the grouping of tasks, the layout of a workspace (Carve), the ragged packer of the fetches, the pass table with the
-// layouts of strq_last_*, the order of a second decode.  Built and run under ASan/UBSan by tests/test_detect_plan_host.py; exits 0 when every check holds.
+// layouts of strq_last_*, the order of a second decode, the piece planner against the five loops it replaced.  Built and run under ASan/UBSan by tests/test_detect_plan_host.py; exits 0 when every check holds.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include "../../strique_amd/csrc/detect_plan.h"
+#include "../../strique_amd/csrc/vit_model.h"
 
 using namespace strq;
 
@@ -186,8 +187,224 @@ static void decode_order_checks()
     CHECK(decode_order<M>(std::vector<int>(), of, E) && E.G.groups.empty() && E.read_of.empty() && E.model.empty());
 }
 
+// The piece planner against the five loops it replaced, each as its pass had it (the pass's own names: ws / fl, c0, c1, bytes, budget);
+// a loop records the windows in its order, what it added per window, its pieces and the windows it gave status 2.
+struct RefPlan { std::vector<int32_t> order; std::vector<size_t> bytes; std::vector<Piece> pieces; std::vector<int32_t> oversize; };
+struct RefW { int i; size_t bytes; };
+
+static RefPlan ref_unit_pass(const std::vector<size_t>& raw, size_t budget)          // sums the sizes as they are
+{
+    RefPlan R; std::vector<RefW> ws;
+    for (size_t i = 0; i < raw.size(); ++i) ws.push_back({(int)i, raw[i]});
+    for (size_t c0 = 0; c0 < ws.size();) {
+        size_t c1 = c0, bytes = 0;
+        while (c1 < ws.size() && (c1 == c0 || bytes + ws[c1].bytes <= budget)) bytes += ws[c1++].bytes;
+        R.pieces.push_back({c0, c1, bytes});
+        c0 = c1;
+    }
+    for (const RefW& w : ws) { R.order.push_back(w.i); R.bytes.push_back(w.bytes); }
+    return R;
+}
+static RefPlan ref_flank_mod_pass(const std::vector<size_t>& raw, size_t budget)     // sums the 16-byte-rounded sizes
+{
+    RefPlan R; std::vector<RefW> fl;
+    for (size_t i = 0; i < raw.size(); ++i) fl.push_back({(int)i, raw[i]});
+    for (size_t c0 = 0; c0 < fl.size();) {
+        size_t c1 = c0, bytes = 0;
+        while (c1 < fl.size() && (c1 == c0 || bytes + ((fl[c1].bytes + 15) & ~(size_t)15) <= budget)) bytes += (fl[c1++].bytes + 15) & ~(size_t)15;
+        R.pieces.push_back({c0, c1, bytes});
+        c0 = c1;
+    }
+    for (const RefW& f : fl) { R.order.push_back(f.i); R.bytes.push_back((f.bytes + 15) & ~(size_t)15); }
+    return R;
+}
+static RefPlan ref_tract_positions(const std::vector<size_t>& sizes, size_t budget)  // an oversize window is dropped first
+{
+    RefPlan R; std::vector<RefW> ws;
+    for (size_t i = 0; i < sizes.size(); ++i) {
+        const size_t bytes = sizes[i];
+        if (bytes > budget) { R.oversize.push_back((int32_t)i); continue; }
+        ws.push_back({(int)i, bytes});
+    }
+    for (size_t c0 = 0; c0 < ws.size();) {
+        size_t c1 = c0, bytes = 0;
+        while (c1 < ws.size() && bytes + ws[c1].bytes <= budget) bytes += ws[c1++].bytes;          // (every window fits alone)
+        R.pieces.push_back({c0, c1, bytes});
+        c0 = c1;
+    }
+    for (const RefW& w : ws) { R.order.push_back(w.i); R.bytes.push_back(w.bytes); }
+    return R;
+}
+static RefPlan ref_state_stats(const std::vector<size_t>& sizes, size_t budget)      // as tract_positions, its own copy
+{
+    RefPlan R; std::vector<RefW> ws;
+    for (size_t i = 0; i < sizes.size(); ++i) {
+        const size_t bytes = sizes[i];
+        if (bytes > budget) { R.oversize.push_back((int32_t)i); continue; }
+        ws.push_back({(int)i, bytes});
+    }
+    for (size_t c0 = 0; c0 < ws.size();) {
+        size_t c1 = c0, bytes = 0;
+        while (c1 < ws.size() && bytes + ws[c1].bytes <= budget) bytes += ws[c1++].bytes;          // (every window fits alone)
+        R.pieces.push_back({c0, c1, bytes});
+        c0 = c1;
+    }
+    for (const RefW& w : ws) { R.order.push_back(w.i); R.bytes.push_back(w.bytes); }
+    return R;
+}
+static RefPlan ref_state_posteriors(const std::vector<size_t>& sizes, size_t budget) // oversize windows in front with 0 bytes, 8192 a piece
+{
+    RefPlan R; std::vector<RefW> ws, over;
+    for (size_t i = 0; i < sizes.size(); ++i) {
+        const size_t bytes = sizes[i];
+        if (bytes > budget) { R.oversize.push_back((int32_t)i); over.push_back({(int)i, 0}); continue; }
+        ws.push_back({(int)i, bytes});
+    }
+    ws.insert(ws.begin(), over.begin(), over.end());
+    for (size_t c0 = 0; c0 < ws.size();) {
+        size_t c1 = c0, bytes = 0;
+        while (c1 < ws.size() && c1 - c0 < 8192 && bytes + ws[c1].bytes <= budget) bytes += ws[c1++].bytes;          // (every window fits alone)
+        R.pieces.push_back({c0, c1, bytes});
+        c0 = c1;
+    }
+    for (const RefW& w : ws) { R.order.push_back(w.i); R.bytes.push_back(w.bytes); }
+    return R;
+}
+
+static bool same_plan(const PiecePlan& P, const RefPlan& R)
+{
+    if (P.order != R.order || P.bytes != R.bytes || P.oversize != R.oversize || P.pieces.size() != R.pieces.size()) return false;
+    for (size_t k = 0; k < P.pieces.size(); ++k)
+        if (P.pieces[k].first != R.pieces[k].first || P.pieces[k].last != R.pieces[k].last || P.pieces[k].bytes != R.pieces[k].bytes) return false;
+    return true;
+}
+// what every plan holds, whatever the policy: the pieces tile the order, none is empty, every window is in the order or oversize
+static bool sound_plan(const PiecePlan& P, size_t n, size_t budget, Oversize policy)
+{
+    size_t at = 0;
+    for (const Piece& pc : P.pieces) {
+        if (pc.first != at || pc.last <= pc.first) return false;
+        size_t sum = 0;
+        for (size_t k = pc.first; k < pc.last; ++k) sum += P.bytes[k];
+        if (sum != pc.bytes || (pc.bytes > budget && !(policy == OVERSIZE_ALONE && pc.last - pc.first == 1))) return false;
+        at = pc.last;
+    }
+    if (at != P.order.size() || P.bytes.size() != P.order.size()) return false;
+    std::vector<int> seen(n, 0);
+    for (int32_t i : P.order) ++seen[(size_t)i];
+    if (policy == OVERSIZE_LEFT_OUT) for (int32_t i : P.oversize) ++seen[(size_t)i];
+    for (int v : seen) if (v != 1) return false;
+    return policy != OVERSIZE_ALONE || P.oversize.empty();
+}
+static int plan_cases = 0;
+static bool seen_rounding_differs = false;
+static void planner_case(const std::vector<size_t>& raw, size_t budget)
+{
+    ++plan_cases;
+    std::vector<size_t> rounded(raw);
+    for (size_t& b : rounded) b = (b + 15) & ~(size_t)15;
+    const PiecePlan units = plan_pieces(raw, budget, OVERSIZE_ALONE), fmod = plan_pieces(rounded, budget, OVERSIZE_ALONE);
+    CHECK(same_plan(units, ref_unit_pass(raw, budget)) && sound_plan(units, raw.size(), budget, OVERSIZE_ALONE));
+    CHECK(same_plan(fmod, ref_flank_mod_pass(raw, budget)) && sound_plan(fmod, raw.size(), budget, OVERSIZE_ALONE));
+    if (units.pieces.size() != fmod.pieces.size()) seen_rounding_differs = true;
+    // the traced passes and the posteriors hand in sizes they rounded themselves; the raw ones are as good a list
+    const std::vector<size_t>* const lists[2] = {&raw, &rounded};
+    for (const std::vector<size_t>* sizes : lists) {
+        const PiecePlan out = plan_pieces(*sizes, budget, OVERSIZE_LEFT_OUT), front = plan_pieces(*sizes, budget, OVERSIZE_IN_FRONT, 8192);
+        CHECK(same_plan(out, ref_tract_positions(*sizes, budget)) && same_plan(out, ref_state_stats(*sizes, budget)) && sound_plan(out, sizes->size(), budget, OVERSIZE_LEFT_OUT));
+        CHECK(same_plan(front, ref_state_posteriors(*sizes, budget)) && sound_plan(front, sizes->size(), budget, OVERSIZE_IN_FRONT));
+        for (const Piece& pc : front.pieces) CHECK(pc.last - pc.first <= 8192);
+    }
+}
+static void planner_checks()
+{
+    const size_t B = 4096;
+    // the named cases: no windows, sizes of 0, sums and single windows at the budget and a byte over, sizes that are no multiple of 16,
+    // every window oversize
+    planner_case({}, B);
+    planner_case({0}, B); planner_case({0, 0, 0}, B); planner_case({0, B, 0}, B); planner_case({0, B + 1, 0}, B);
+    planner_case({B}, B); planner_case({B + 1}, B); planner_case({B, B}, B); planner_case({B + 1, B + 1, B + 1}, B);
+    planner_case({1000, 3096}, B); planner_case({1000, 3097}, B); planner_case({1000, 2000, 1096, 1}, B); planner_case({1000, 2000, 1097}, B);
+    planner_case({4081, 1}, B); planner_case({4081}, B); planner_case({4090, 4090}, B); planner_case({100, 100, 100}, 300); planner_case({100, 100, 100}, 299);
+    planner_case({8, 8}, 16); planner_case({9, 7}, 16); planner_case({1, 1, 1}, 32); planner_case({1, 1, 1}, 31);
+    planner_case({5000, 1, 6000, 2, 7000}, B); planner_case({1, 5000, 2}, B);
+    // an oversize window rides alone where the policy lets it, is left out or carried in front with no bytes elsewhere
+    {
+        const std::vector<size_t> sizes = {16, 5008, 32, 4096, 16};
+        const PiecePlan a = plan_pieces(sizes, B, OVERSIZE_ALONE), o = plan_pieces(sizes, B, OVERSIZE_LEFT_OUT), f = plan_pieces(sizes, B, OVERSIZE_IN_FRONT, 8192);
+        CHECK(a.pieces.size() == 5 && a.pieces[1].first == 1 && a.pieces[1].last == 2 && a.pieces[1].bytes == 5008 && a.pieces[2].bytes == 32 && a.pieces[3].bytes == 4096 && a.oversize.empty());
+        CHECK(o.order == std::vector<int32_t>({0, 2, 3, 4}) && o.oversize == std::vector<int32_t>({1}) && o.pieces.size() == 3 && o.pieces[0].bytes == 48 && o.pieces[1].bytes == 4096);
+        CHECK(f.order == std::vector<int32_t>({1, 0, 2, 3, 4}) && f.bytes[0] == 0 && f.oversize == std::vector<int32_t>({1}) && f.pieces.size() == 3 && f.pieces[0].last == 3 && f.pieces[0].bytes == 48);
+    }
+    // the cap of the state posteriors: 8193 windows of no bytes are two pieces; without a cap they are one
+    {
+        const std::vector<size_t> zeros(8193, 0);
+        planner_case(zeros, B);
+        const PiecePlan f = plan_pieces(zeros, B, OVERSIZE_IN_FRONT, 8192);
+        CHECK(f.pieces.size() == 2 && f.pieces[0].last == 8192 && f.pieces[1].last == 8193 && f.pieces[1].bytes == 0);
+        CHECK(plan_pieces(zeros, B, OVERSIZE_LEFT_OUT).pieces.size() == 1);
+        std::vector<size_t> mixed(8193, 0); mixed[8192] = B + 1; mixed[17] = B;          // the oversize one comes to the front and counts towards the cap
+        planner_case(mixed, B);
+        CHECK(plan_pieces(mixed, B, OVERSIZE_IN_FRONT, 8192).order[0] == 8192);
+    }
+    // generated lists: 0 to 40 windows; a list draws from one of several mixes so that zeros, windows at the budget and a byte over,
+    // all-oversize lists and sums that land on the budget or a byte over all come up (fixed seed)
+    uint64_t rng = 0x9E3779B97F4A7C15ull;
+    auto next = [&](uint64_t below) { rng = rng * 6364136223846793005ull + 1442695040888963407ull; return (size_t)((rng >> 33) % below); };
+    const size_t budgets[] = {16, 100, 4096, 65536, (size_t)1 << 33};
+    int n_exact = 0, n_over1 = 0, n_all_over = 0;
+    for (int t = 0; t < 4000; ++t) {
+        const size_t budget = budgets[next(5)], n = next(41), mix = next(6);
+        std::vector<size_t> raw(n);
+        size_t run = 0;
+        for (size_t i = 0; i < n; ++i) {
+            size_t b;
+            switch (mix) {
+            case 0: b = next(budget / 3 + 2); break;                                      // several to a piece, mostly no multiple of 16
+            case 1: b = next(4) == 0 ? 0 : next(budget + budget / 4 + 2); break;          // zeros, some oversize
+            case 2: b = budget + 1 + next(budget); break;                                 // every window oversize
+            case 3: b = next(3) == 0 ? budget : next(2) ? budget + 1 : next(budget + 1); break;
+            case 4: b = 16 * next(budget / 48 + 2); break;                                // multiples of 16
+            default:                                                                      // runs that end exactly at the budget, or a byte over
+                b = next(budget / 2 + 1);
+                if (run + b > budget || next(4) == 0) { b = budget - run + next(2); }
+                break;
+            }
+            run = run + b > budget ? 0 : run + b;
+            if (run == budget) run = 0;
+            raw[i] = b;
+        }
+        planner_case(raw, budget);
+        const PiecePlan p = plan_pieces(raw, budget, OVERSIZE_LEFT_OUT);
+        for (const Piece& pc : p.pieces) {
+            if (pc.last - pc.first > 1 && pc.bytes == budget) ++n_exact;
+            if (pc.last < p.order.size() && pc.bytes + p.bytes[pc.last] == budget + 1) ++n_over1;
+        }
+        if (n && p.oversize.size() == n) ++n_all_over;
+    }
+    CHECK(plan_cases > 4000 && n_exact > 50 && n_over1 > 50 && n_all_over > 50 && seen_rounding_differs);
+
+    CHECK(ws_budget(nullptr) == (size_t)8 << 30 && ws_budget("0") == (size_t)8 << 30 && ws_budget("-5") == (size_t)8 << 30 && ws_budget("4096") == 4096);
+    CHECK(ws_budget("") == (size_t)8 << 30 && ws_budget("x") == (size_t)8 << 30 && ws_budget("1") == 1);
+    // back-pointers: uint16 per (time step, state), T + 1 steps, rounded up to 16 bytes
+    CHECK(bp_window_bytes(0, 1) == 16 && bp_window_bytes(0, 8) == 16 && bp_window_bytes(0, 9) == 32);
+    CHECK(bp_window_bytes(6, 1) == 16 && bp_window_bytes(6, 9) == 128 && bp_window_bytes(7, 1) == 16 && bp_window_bytes(14, 1) == 32);          // 7, 63, 8, 15 cells
+    CHECK(bp_window_bytes(((int64_t)1 << 21) - 1, 4096) == (size_t)1 << 34);
+    // the three 21-bit counters of a tract payload, each at 0 and at 2^21 - 1
+    const int64_t top = ((int64_t)1 << VIT_TRACT_BITS) - 1;
+    for (int mask = 0; mask < 8; ++mask) {
+        uint64_t pay = 0;
+        for (int j = 0; j < VIT_TRACTS_MAX; ++j) if (mask >> j & 1) pay += (uint64_t)top << (VIT_TRACT_BITS * j);
+        for (int j = 0; j < VIT_TRACTS_MAX; ++j) CHECK(vit_tract_count(pay, j) == ((mask >> j & 1) ? top : 0));
+    }
+    const uint64_t pay = (uint64_t)5 | (uint64_t)70000 << VIT_TRACT_BITS | (uint64_t)1 << (2 * VIT_TRACT_BITS);
+    CHECK(vit_tract_count(pay, 0) == 5 && vit_tract_count(pay, 1) == 70000 && vit_tract_count(pay, 2) == 1);
+    CHECK(vit_tract_count(~(uint64_t)0, 2) == top);          // the bit above the three counters is not theirs
+}
+
 int main()
 {
+    planner_checks();
     carve_checks();
     packer_checks();
     stats_checks();
